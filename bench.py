@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: bootstrapped gate ops/s on level-batched circuits.
 
-  python bench.py --gpus N --steps K --warmup W [--workload add16|mul32|...] [--batch B]
+  python bench.py --gpus N --steps K --warmup W [--workload add16|mul32|...] [--batch B] [--dump-outputs DIR]
 
 One "step" = one pass of a whole circuit (every level, every gate) over one
 batch of expressions whose ciphertexts are already resident in HBM.  The timed
@@ -13,6 +13,10 @@ full timed pass each of
   * configs[4]'s circuit: 128-bit MUL, a time-boxed sub-batch of 128 of its 1024 per GPU -> `mul128`
 every product decrypt-checked, each with its own roofline object.  (--extras adds the two opt-in,
 decrypt-identical-only multipliers: constant-folded and carry-save.)
+
+--dump-outputs DIR writes what the last of the K timed steps left in the output buffer -- the LWE samples a caller of
+eval_batch_device receives -- to DIR/<workload>_out.npy (dump_outputs below).  Keys, operands and encryption noise are all
+seeded, so equal arguments give equal inputs and two builds can be compared sample for sample.
 
 N > 1: `python bench.py --gpus N ...` starts its own ranks (python -m torch.distributed.run, one
 child process per GPU, before this process touches the GPU) unless it already runs under
@@ -374,6 +378,26 @@ def make_inputs(ia, tools, torch, ctx, p, lwe_key, kind, bits, batch, rank, dev,
     return info, inb, d_in, d_out
 
 
+DUMP_LIMIT = 64 * 10 ** 6   # bytes --dump-outputs writes at most, all ranks together
+DUMP_SEED = 20240
+
+
+def dump_outputs(directory, name, d_out, n, world=1):
+    """d_out [expressions][n_outputs][lwe_stride] int32 -> directory/name.npy, [rows][n_outputs][n+1] float64 (exact for Torus32
+    words; float32 would not be).  An output larger than this rank's share of DUMP_LIMIT is cut to a fixed, seeded choice of
+    whole expressions in ascending order, the same for equal shapes.  Returns the file's path."""
+    batch, n_outputs = int(d_out.shape[0]), int(d_out.shape[1])
+    rows = max(1, (DUMP_LIMIT // world - 4096) // (n_outputs * (n + 1) * 8))   # 4096: room for the .npy header
+    picked = d_out[:, :, :n + 1]
+    if batch > rows:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(batch, size=rows, replace=False))
+        picked = picked[idx.tolist()]
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, name + ".npy")
+    np.save(path, picked.cpu().numpy().astype(np.float64))
+    return path
+
+
 def check_outputs(tools, p, lwe_key, kind, bits, inb, d_out, rank):
     """Every expression of the batch must decrypt to the integer result (P1 at full size)."""
     batch = inb.shape[0]
@@ -505,6 +529,9 @@ def main():
     ap.add_argument("--metric-passes", type=int, default=2,
                     help="timed passes of the mul32 leg (the config BASELINE.json quotes its metric on); the line reports each and their spread")
     ap.add_argument("--details", default=None, help="where the full record goes (default: bench_details.json next to this script)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the output samples of the last timed step to DIR/<workload>_out.npy (float64; at most 64 MB, a fixed "
+                         "seeded choice of expressions beyond that; ranks other than 0 append _rank<r> to the name)")
     ap.add_argument("--roofline-steps", type=int, default=3,
                     help="steps of the primary batch run with every launch on one stream (overlap = 0) after the timed region, for the per-kernel roofline figures")
     ap.add_argument("--exact-leg", default="on", choices=["on", "off"],
@@ -514,6 +541,8 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: rehearse the N>1 flow with CPU collectives (ranks may then share one GPU)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step is needed")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))  # before anything touches the GPU in this process
@@ -565,6 +594,9 @@ def main():
     elapsed, per_rank = timed(torch, dist, world, dev, args.backend, lambda: [step(stats) for _ in range(args.steps)])
     primary_rate = info.bootstraps * batch * args.steps * world / elapsed
     progress(rank, "%s x%d: %.0f gate ops/s" % (args.workload, batch, primary_rate))
+    if args.dump_outputs:  # here, before the untimed legs below write the same buffer again
+        dumped = dump_outputs(args.dump_outputs, "%s_out%s" % (args.workload, "_rank%d" % rank if rank else ""), d_out, p.n, world)
+        progress(rank, "outputs of the last timed step: %s" % dumped)
 
     # ---- per-kernel figures: the evaluator issues wide levels as two halves on two streams (option "overlap"), whose kernels share
     # the chip, so a launch's own duration is taken with every launch on ONE stream: a few more steps of the same batch with

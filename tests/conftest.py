@@ -1,5 +1,8 @@
 import os
+import pathlib
+import shutil
 import sys
+import tempfile
 
 import numpy as np
 import pytest
@@ -12,6 +15,16 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
+
+
+@pytest.fixture
+def sock_dir():
+    """A directory for AF_UNIX sockets.  sun_path holds 107 bytes and pytest's tmp_path (base directory + user + test name)
+    can alone be longer than that, so socket names live under a short name of their own."""
+    base = tempfile.gettempdir()
+    d = pathlib.Path(tempfile.mkdtemp(prefix="ia-", dir=base if len(base) <= 64 else "/tmp"))
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
 
 
 @pytest.fixture(scope="session")

@@ -200,3 +200,29 @@ def test_details_file_holds_the_full_record(bench, ia, tmp_path, monkeypatch):
     assert bench.write_details(full) == "bench_details.json"
     back = json.load(open(tmp_path / "bench_details.json"))
     assert back["roofline"]["note"] == full["roofline"]["note"] and back["mul32"]["roofline"]["hbm_model"]["note"]
+
+
+def test_dump_outputs_is_exact_bounded_and_repeatable(bench, tmp_path, monkeypatch):
+    """--dump-outputs: the output samples as float64 without their stride padding, every Torus32 word exact; past the size limit a
+    fixed choice of whole expressions in ascending order, the same on every call; all ranks together stay under 64 MB."""
+    import numpy as np
+    import torch
+    n, stride = 6, 8
+    rng = np.random.default_rng(3)
+    host = rng.integers(-2 ** 31, 2 ** 31, size=(40, 3, stride), dtype=np.int64).astype(np.int32)
+    host[0, 0, :2] = (-2 ** 31, 2 ** 31 - 1)
+    d_out = torch.from_numpy(host)
+    assert bench.DUMP_LIMIT <= 64 * 10 ** 6
+    path = bench.dump_outputs(str(tmp_path / "new" / "dir"), "add16_out", d_out, n)
+    assert path == str(tmp_path / "new" / "dir" / "add16_out.npy")
+    whole = np.load(path)
+    assert whole.dtype == np.float64 and whole.shape == (40, 3, n + 1) and np.array_equal(whole.astype(np.int32), host[:, :, :n + 1])
+    # room for 10 expressions of 3 x 7 words (and the file's header); two ranks get half of it each
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4096 + 10 * 3 * (n + 1) * 8)
+    cut = np.load(bench.dump_outputs(str(tmp_path), "cut", d_out, n))
+    assert cut.shape == (10, 3, n + 1) and os.path.getsize(tmp_path / "cut.npy") <= bench.DUMP_LIMIT
+    rows = [int(np.flatnonzero((whole == c).all(axis=(1, 2)))[0]) for c in cut]
+    assert rows == sorted(set(rows)) and rows != list(range(10))
+    assert np.array_equal(np.load(bench.dump_outputs(str(tmp_path), "again", d_out, n)), cut)
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 2 * (4096 + 5 * 3 * (n + 1) * 8))
+    assert np.load(bench.dump_outputs(str(tmp_path), "half", d_out, n, world=2)).shape == (5, 3, n + 1)

@@ -73,9 +73,9 @@ def test_wire_format_matches_the_header(ia):
         daemon.unpack_response_header(struct.pack("<IiQQ", daemon.MAGIC, 0, daemon.MAX_PAYLOAD + 1, 0))
 
 
-def test_python_client_roundtrip(ia, tmp_path):
+def test_python_client_roundtrip(ia, tmp_path, sock_dir):
     from ieache_amd import daemon
-    sock = tmp_path / "d.sock"
+    sock = sock_dir / "d.sock"
     srv = FakeDaemon(sock, [(0, b"pong", b""), (126, b"Cannot multiply 256 bit number!\n", b""), (0, b"log", b"ANSWER"),
                             "garbage", "hangup", (0, b"bye", b"")])
     assert daemon.ping(sock)[:2] == (0, "pong")
@@ -91,12 +91,12 @@ def test_python_client_roundtrip(ia, tmp_path):
     assert srv.seen[1][4] == os.fsencode(os.path.abspath(tmp_path))
     assert srv.seen[2][4] == struct.pack("<i", 4) + b"\x01\x02\x03"
     with pytest.raises(daemon.DaemonError):  # nobody listens any more
-        daemon.ping(tmp_path / "nobody.sock")
+        daemon.ping(sock_dir / "nobody.sock")
 
 
-def test_native_client_roundtrip(ia, tmp_path, capfd):
+def test_native_client_roundtrip(ia, tmp_path, sock_dir, capfd):
     L = ia.lib()
-    sock = tmp_path / "d.sock"
+    sock = sock_dir / "d.sock"
     answer = bytes(range(200))
     srv = FakeDaemon(sock, [(0, b"pong", b""), (126, b"chatter\n", b""), (0, b"", answer), (0, b"", answer),
                             (-5, b"cannot open cloud.data", b""), "garbage", (0, b"bye", b"")])
@@ -118,16 +118,16 @@ def test_native_client_roundtrip(ia, tmp_path, capfd):
     # error paths that never reach a socket
     assert L.ieache_client_ping(None) == -22
     assert L.ieache_client_run_dir(sp, None) == -22
-    assert L.ieache_client_ping(os.fsencode(tmp_path / "nobody.sock")) == -19
+    assert L.ieache_client_ping(os.fsencode(sock_dir / "nobody.sock")) == -19
     assert b"cannot reach" in L.ieache_last_error()
     assert L.ieache_client_ping(b"/" + b"x" * 200) == -22  # longer than sun_path
     assert L.ieache_serve(None, b"k", None, 0, 0) == -22
-    assert L.ieache_serve(os.fsencode(tmp_path / "s.sock"), os.fsencode(tmp_path / "missing.key"), None, 0, 0) == -5
+    assert L.ieache_serve(os.fsencode(sock_dir / "s.sock"), os.fsencode(tmp_path / "missing.key"), None, 0, 0) == -5
 
 
-def test_cloud_shim_forwards_to_the_daemon(ia, tmp_path):
+def test_cloud_shim_forwards_to_the_daemon(ia, tmp_path, sock_dir):
     exe = os.path.join(os.path.dirname(ia.library_path()), "cloud")
-    sock = tmp_path / "d.sock"
+    sock = sock_dir / "d.sock"
     work = tmp_path / "work"
     work.mkdir()
     srv = FakeDaemon(sock, [(126, b"Cannot multiply 256 bit number!\n", b"")])
@@ -136,30 +136,30 @@ def test_cloud_shim_forwards_to_the_daemon(ia, tmp_path):
     assert r.returncode == 126 and b"Cannot multiply" in r.stdout
     assert srv.seen[0][2] == 2 and srv.seen[0][4] == os.fsencode(os.path.realpath(work))
     # no daemon behind the socket path: the shim says so and does the run itself (which fails here: no files)
-    r = subprocess.run([exe], cwd=work, env=dict(os.environ, IEACHE_DAEMON=str(tmp_path / "nobody.sock")),
+    r = subprocess.run([exe], cwd=work, env=dict(os.environ, IEACHE_DAEMON=str(sock_dir / "nobody.sock")),
                        capture_output=True, timeout=60)
     assert r.returncode == 1 and b"daemon" in r.stderr and b"cloud.key" in r.stderr
 
 
-def test_cloudd_fails_loudly_without_a_gpu(ia, tmp_path):
+def test_cloudd_fails_loudly_without_a_gpu(ia, tmp_path, sock_dir):
     from ieache_amd import tools
     exe = os.path.join(os.path.dirname(ia.library_path()), "cloudd")
     r = subprocess.run([exe, "--bogus"], capture_output=True, timeout=60)
     assert r.returncode == 2 and b"usage" in r.stderr
-    r = subprocess.run([exe, "--socket", str(tmp_path / "s"), "--key", str(tmp_path / "missing.key"), "--max-requests", "0"],
+    r = subprocess.run([exe, "--socket", str(sock_dir / "s"), "--key", str(tmp_path / "missing.key"), "--max-requests", "0"],
                        capture_output=True, timeout=60)
     assert r.returncode == 1 and b"missing.key" in r.stderr
     tools.keygen_files(tmp_path, ia.default_params().copy(n=6, N=64))
-    r = subprocess.run([exe, "--socket", str(tmp_path / "s"), "--key", str(tmp_path / "cloud.key"), "--max-requests", "0"],
+    r = subprocess.run([exe, "--socket", str(sock_dir / "s"), "--key", str(tmp_path / "cloud.key"), "--max-requests", "0"],
                        capture_output=True, timeout=120)
     if ia.device_count() == 0:
         assert r.returncode == 1 and r.stderr.startswith(b"cloudd: ")  # no CPU fallback
     else:
         assert r.returncode == 0 and b"served 0 requests" in r.stdout
-    assert not (tmp_path / "s").exists()
+    assert not (sock_dir / "s").exists()
 
 
-def test_device_list_parsing_and_stats_format(ia, tmp_path, monkeypatch):
+def test_device_list_parsing_and_stats_format(ia, tmp_path, sock_dir, monkeypatch):
     """cloudd --devices / IEACHE_DEVICES take a comma-separated list (anything else: exit 2 before any key is read); the client
     parses the STATS line with its per-device job counts; spawn() passes the list on."""
     from ieache_amd import daemon
@@ -170,7 +170,7 @@ def test_device_list_parsing_and_stats_format(ia, tmp_path, monkeypatch):
     r = subprocess.run([exe, "--key", str(tmp_path / "missing.key")], env=dict(os.environ, IEACHE_DEVICES="zero"), capture_output=True, timeout=60)
     assert r.returncode == 2 and b"IEACHE_DEVICES" in r.stderr
     # a well-formed list gets as far as the key file (missing here): exit 1, the key's name in the message
-    r = subprocess.run([exe, "--devices", "0,0,1", "--socket", str(tmp_path / "s"), "--key", str(tmp_path / "missing.key")], capture_output=True, timeout=60)
+    r = subprocess.run([exe, "--devices", "0,0,1", "--socket", str(sock_dir / "s"), "--key", str(tmp_path / "missing.key")], capture_output=True, timeout=60)
     assert r.returncode == 1 and b"missing.key" in r.stderr
     st = daemon.parse_stats("evaluations=3 batched_requests=8 largest_batch=6 devices=2 sharded_evaluations=1 device_jobs=5,3")
     assert st == {"evaluations": 3, "batched_requests": 8, "largest_batch": 6, "devices": 2, "sharded_evaluations": 1, "device_jobs": [5, 3]}

@@ -1447,7 +1447,7 @@ def test_old_libtfhe_parameter_set_on_fast_kernel(ia, gpu_ctx):
     ctx.force_generic(False)
 
 
-def test_resident_key_daemon(ia, O, tmp_path):
+def test_resident_key_daemon(ia, O, tmp_path, sock_dir):
     """`cloudd` keeps the cloud key on the GPU and serves the ./cloud contract over a
     local socket; results equal the in-process run and the oracle, bit for bit."""
     import ctypes as C
@@ -1457,7 +1457,7 @@ def test_resident_key_daemon(ia, O, tmp_path):
     p = ia.default_params().copy(n=6, N=64)
     S = 4 * p.n + 16
     tools.keygen_files(tmp_path, p)
-    sock = tmp_path / "cloudd.sock"
+    sock = sock_dir / "cloudd.sock"
     proc = daemon.spawn(sock, tmp_path / "cloud.key")
     try:
         assert daemon.ping(sock)[0] == 0
@@ -1521,7 +1521,7 @@ def test_resident_key_daemon(ia, O, tmp_path):
 
 
 @pytest.mark.parametrize("devices", [None, (0, 0)])
-def test_daemon_batches_concurrent_requests(ia, O, tmp_path, devices):
+def test_daemon_batches_concurrent_requests(ia, O, tmp_path, sock_dir, devices):
     """cloudd --batch-window-ms: requests of several clients that arrive together are answered together, those asking
     for the same circuit as ONE level-batched evaluation.  Every client still gets exactly its own answer: the value
     samples equal a one-at-a-time run (and the oracle) bit for bit.
@@ -1547,7 +1547,7 @@ def test_daemon_batches_concurrent_requests(ia, O, tmp_path, devices):
         tools.alice(d, 0, bits, a, seed=100 + i)
         tools.alice(d, 0, bits, b, seed=200 + i, append=True)
         jobs.append((d, operator, bits, a, b))
-    sock = tmp_path / "cloudd.sock"
+    sock = sock_dir / "cloudd.sock"
     proc = daemon.spawn(sock, tmp_path / "cloud.key", batch_window_ms=400, max_batch=64, devices=devices)
     try:
         results = [None] * 8
@@ -1714,15 +1714,18 @@ def test_bench_default_command_shape_with_three_ranks_on_one_gpu(tmp_path):
 
 
 @pytest.mark.gpu
-def test_bench_collectives_on_rccl_with_one_rank(tmp_path):
+def test_bench_collectives_on_rccl_with_one_rank(ia, tmp_path):
     """The collective calls of the N>1 job on RCCL itself, as far as one GPU allows: IEACHE_DIST_SINGLE=1 makes bench.py
     form a process group of ONE rank on backend "nccl" (= RCCL), so init_process_group(device_id=...), the device-side
-    broadcast of BK / KSK / the LWE key, the barriers, all_gather and all_reduce of the timing path all run on the GPU."""
+    broadcast of BK / KSK / the LWE key, the barriers, all_gather and all_reduce of the timing path all run on the GPU.
+    --dump-outputs: the file holds the timed step's output samples (they decrypt, under bench.py's key, to the sums of its fixed
+    edge operands in slots 0-3)."""
     import subprocess
     import sys
+    from ieache_amd import tools
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--batch", "64",
-           "--backend", "nccl", "--no-cpu-baseline", "--legs", "mul32", "--mul32-batch", "4"]
+           "--backend", "nccl", "--no-cpu-baseline", "--legs", "mul32", "--mul32-batch", "4", "--dump-outputs", str(tmp_path / "dump")]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=tmp_path,
                        env=dict(env, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", IEACHE_DIST_SINGLE="1"))
@@ -1734,6 +1737,13 @@ def test_bench_collectives_on_rccl_with_one_rank(tmp_path):
     assert out["n_gpus"] == 1 and cfg["rccl_ranks"] == 1 and cfg["collective_backend"] == "nccl" and cfg["key_broadcast_s"] > 0
     assert len(cfg["per_rank_gate_ops_per_s"]) == 1 and out["value"] > 0 and out["mul32_per_s"] > 0 and out["mul32"]["expressions_per_s"] > 0
     assert out["metric_leg"]["passes"] == 2 and len(lines[0]) < 6000
+    p = ia.default_params()
+    dump = np.load(tmp_path / "dump" / "add16_out.npy")
+    assert dump.dtype == np.float64 and dump.shape == (64, ia.circuit_info(ia.CIRC_ADD, 16).n_outputs, p.n + 1)
+    assert np.array_equal(dump, dump.astype(np.int32))
+    lwe_key = tools.keygen_raw(p, (314, 1592, 657), with_cloud=False)["lwe_key"]
+    dec = tools.decrypt_bits(p, lwe_key, dump.astype(np.int32))
+    assert [tools.bits_to_int(dec[e]) for e in range(4)] == [0, 2, 0xFFFE, 0x8000]   # 0+0, 1+1, 2 (2^16-1), 2 x 2^14
 
 
 def test_output_noise_matches_the_published_variance(ia, gpu_ctx):
