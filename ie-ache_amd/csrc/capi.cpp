@@ -446,11 +446,85 @@ int ieache_prepare_batch(ieache_ctx* ctx, int kind, int bits, size_t batch) {
     });
 }
 
+// ---- caller-defined netlists: a compiled Circuit behind an opaque handle (host only) ----
+struct ieache_netlist {
+    Circuit circuit;
+};
+
+ieache_netlist* ieache_netlist_create(int32_t n_inputs, const ieache_net_gate* gates, size_t n_gates, const int32_t* outputs,
+                                      size_t n_outputs, int flags) {
+    static_assert(sizeof(ieache_net_gate) == sizeof(NetGate), "ieache_net_gate is circuit.h's NetGate");
+    ieache_netlist* nl = nullptr;
+    guarded([&] {
+        if (flags & ~IEACHE_NETLIST_BALANCED) return fail(IEACHE_EINVAL, "netlist: unknown flag");
+        std::unique_ptr<ieache_netlist> made(new ieache_netlist);
+        made->circuit = build_netlist(n_inputs, reinterpret_cast<const NetGate*>(gates), n_gates, outputs, n_outputs,
+                                      (flags & IEACHE_NETLIST_BALANCED) != 0);
+        nl = made.release();
+        return 0;
+    });
+    return nl;
+}
+
+void ieache_netlist_destroy(ieache_netlist* nl) { delete nl; }
+
+int ieache_netlist_info(const ieache_netlist* nl, ieache_circuit_info* out, int64_t gates_by_type[IEACHE_GATE_TYPES]) {
+    return guarded([&] {
+        if (!nl || !out) return fail(IEACHE_EINVAL, "null argument");
+        fill_info(nl->circuit, false, out);
+        if (gates_by_type)
+            for (int t = 0; t < GATE_TYPES; t++) gates_by_type[t] = nl->circuit.n_by_type[t];
+        return 0;
+    });
+}
+
+int ieache_netlist_simulate(const ieache_netlist* nl, const uint8_t* in_bits, uint8_t* out_bits) {
+    return guarded([&] {
+        if (!nl || !in_bits || !out_bits) return fail(IEACHE_EINVAL, "null argument");
+        simulate_circuit(nl->circuit, in_bits, out_bits);
+        return 0;
+    });
+}
+
+int ieache_prepare_netlist(ieache_ctx* ctx, const ieache_netlist* nl, size_t batch) {
+    return guarded([&] {
+        if (!ctx || !nl) return fail(IEACHE_EINVAL, "null argument");
+        ctx->eval->prepare_circuit(nl->circuit, batch);
+        return 0;
+    });
+}
+
+int ieache_eval_netlist(ieache_ctx* ctx, const ieache_netlist* nl, size_t batch, const int32_t* in_lwe, int32_t* out_lwe,
+                        ieache_stats* stats) {
+    return guarded([&] {
+        if (!ctx || !nl || !in_lwe || !out_lwe) return fail(IEACHE_EINVAL, "null argument");
+        EvalStats st;
+        eval_circuit_host(*ctx->eval, nl->circuit, batch, in_lwe, out_lwe, stats ? &st : nullptr);
+        to_stats(st, stats);
+        return 0;
+    });
+}
+
+int ieache_eval_netlist_device(ieache_ctx* ctx, const ieache_netlist* nl, size_t batch, const int32_t* d_in, int32_t* d_out,
+                               ieache_stats* stats) {
+    return guarded([&] {
+        if (!ctx || !nl || !d_in || !d_out) return fail(IEACHE_EINVAL, "null argument");
+        if (batch) {
+            require_device_pointer(d_in, "d_in");
+            require_device_pointer(d_out, "d_out");
+        }
+        EvalStats st;
+        ctx->eval->eval_circuit_device(nl->circuit, batch, d_in, d_out, stats ? &st : nullptr);
+        to_stats(st, stats);
+        return 0;
+    });
+}
+
 int ieache_gates_device(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* d_a, const int32_t* d_b,
                         int32_t* d_out, ieache_stats* stats) {
     return guarded([&] {
         if (!ctx || !d_a || !d_b || !d_out) return fail(IEACHE_EINVAL, "null argument");
-        if (gate_type < 0 || gate_type > 3) return fail(IEACHE_EINVAL, "unknown gate type");
+        if (gate_type < 0 || gate_type >= GATE_TYPES || gate_type == GATE_MUX) return fail(IEACHE_EINVAL, "unknown gate type");
         if (count) {
             require_device_pointer(d_a, "d_a");
             require_device_pointer(d_b, "d_b");
@@ -499,7 +573,7 @@ int ieache_gates(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* a,
                  ieache_stats* stats) {
     return guarded([&] {
         if (!ctx || !a || !b || !out) return fail(IEACHE_EINVAL, "null argument");
-        if (gate_type < 0 || gate_type > 3) return fail(IEACHE_EINVAL, "unknown gate type");
+        if (gate_type < 0 || gate_type >= GATE_TYPES || gate_type == GATE_MUX) return fail(IEACHE_EINVAL, "unknown gate type");
         const Params& p = ctx->eval->params();
         HIP_CHECK(hipSetDevice(ctx->eval->device()));
         StagedRows da(*ctx->eval, 0, count, p.lwe_stride()), db(*ctx->eval, 1, count, p.lwe_stride()), dout(*ctx->eval, 3, count, p.lwe_stride());

@@ -26,6 +26,18 @@ Word CircuitBuilder::input_word(int32_t first, int32_t count) const {
 Ref CircuitBuilder::gate(int32_t type, Ref a, Ref b) {
     if (a.id == kUndefId || b.id == kUndefId)
         throw std::logic_error("gate consumes a never-written sample");
+    if (type < 0 || type >= GATE_TYPES || type == GATE_MUX) throw std::invalid_argument("not a two-input gate type");
+    const int32_t requested = type;
+    // boot-gates.cpp: NOR / ANDNY / ANDYN / ORNY / ORYN are AND / OR of +-ca, +-cb -- recorded as such (the sign flags
+    // of the operands), which is the same linear combination word for word
+    switch (type) {
+        case GATE_NOR: type = GATE_AND; a.neg = !a.neg; b.neg = !b.neg; break;
+        case GATE_ANDNY: type = GATE_AND; a.neg = !a.neg; break;
+        case GATE_ANDYN: type = GATE_AND; b.neg = !b.neg; break;
+        case GATE_ORNY: type = GATE_OR; a.neg = !a.neg; break;
+        case GATE_ORYN: type = GATE_OR; b.neg = !b.neg; break;
+        default: break;
+    }
     n_requested_++;
     bool out_neg = false;
     if (fold_ && (type == GATE_AND || type == GATE_XOR)) {
@@ -57,7 +69,30 @@ Ref CircuitBuilder::gate(int32_t type, Ref a, Ref b) {
     g.level = std::max(la, lb) + 1;
     wire_level_.push_back(g.level);
     gates_.push_back(g);
+    requested_type_.push_back(requested);
     return Ref{g.out, out_neg};
+}
+
+// bootsMUX(a, b, c) = a ? b : c.  Recorded as given: no folding, no sharing.
+Ref CircuitBuilder::gate3(int32_t type, Ref a, Ref b, Ref c) {
+    if (type != GATE_MUX) throw std::invalid_argument("not a three-input gate type");
+    if (a.id == kUndefId || b.id == kUndefId || c.id == kUndefId)
+        throw std::logic_error("gate consumes a never-written sample");
+    n_requested_++;
+    int32_t lv = 0;
+    for (const Ref& r : {a, b, c})
+        if (r.id >= 0) lv = std::max(lv, wire_level_[r.id]);
+    Gate g;
+    g.type = type;
+    g.a = a;
+    g.b = b;
+    g.c = c;
+    g.out = next_wire_++;
+    g.level = lv + 1;
+    wire_level_.push_back(g.level);
+    gates_.push_back(g);
+    requested_type_.push_back(type);
+    return Ref{g.out, false};
 }
 
 // cloud.c:18-51.  carry-in is c[0] (bootsCOPY :24); carry-out lands in
@@ -153,12 +188,16 @@ Circuit finalize_circuit(const std::string& name, const CircuitBuilder& b, const
     int32_t depth = 0;  // ASAP depth; becomes the scheduled depth below when a level cap stretches the schedule
     for (const Gate& g : gates) depth = std::max(depth, g.level);
     c.depth = depth;
-    c.n_bootstraps = (int64_t)gates.size();
+    // widths and counts are in blind rotations: a MUX is two (level_items.h)
+    auto cost = [](const Gate& g) { return g.type == GATE_MUX ? 2 : 1; };
+    int64_t n_rot = 0;
+    for (const Gate& g : gates) n_rot += cost(g);
+    c.n_bootstraps = n_rot;
 
     // ASAP statistics: width of each ASAP level
     {
         std::vector<int32_t> w(depth + 1, 0);
-        for (const Gate& g : gates) w[g.level]++;
+        for (const Gate& g : gates) w[g.level] += cost(g);
         for (int32_t L = 1; L <= depth; L++) c.max_width = std::max(c.max_width, w[L]);
     }
     // Execution schedule.  ASAP piles every gate with slack into the earliest level (all 1024
@@ -180,7 +219,7 @@ Circuit finalize_circuit(const std::string& name, const CircuitBuilder& b, const
         std::vector<std::vector<int32_t>> users(n_gates);
         std::vector<int32_t> n_operands(n_gates, 0);
         for (int32_t i = 0; i < n_gates; i++)
-            for (const Ref& r : {gates[i].a, gates[i].b})
+            for (const Ref& r : {gates[i].a, gates[i].b, gates[i].c})
                 if (r.id >= 0 && producer[r.id] >= 0) {
                     users[producer[r.id]].push_back(i);
                     n_operands[i]++;
@@ -189,14 +228,14 @@ Circuit finalize_circuit(const std::string& name, const CircuitBuilder& b, const
         // the batch is a whole number of the workgroup rounds the GPU holds at once.  A cap under the mean width
         // cannot fit the ASAP depth: the schedule is then stretched (more levels, each of them full), which is the
         // better trade whenever a level is a few rounds wide -- 1.2 rounds cost 2.
-        const int32_t mean = std::max<int32_t>((n_gates + depth - 1) / depth, 1);
+        const int32_t mean = (int32_t)std::max<int64_t>((n_rot + depth - 1) / depth, 1);
         const int32_t cap = level_cap > 0 ? level_cap : mean;
         int32_t sched_depth = depth;
-        if (cap < mean) sched_depth = std::max<int32_t>(depth, (n_gates + cap - 1) / cap);
+        if (cap < mean) sched_depth = std::max<int32_t>(depth, (int32_t)((n_rot + cap - 1) / cap));
         for (;; sched_depth += std::max(1, sched_depth / 50)) {
             std::vector<int32_t> alap(n_gates, sched_depth);
             for (int32_t i = n_gates - 1; i >= 0; i--)  // builder order is topological
-                for (const Ref& r : {gates[i].a, gates[i].b})
+                for (const Ref& r : {gates[i].a, gates[i].b, gates[i].c})
                     if (r.id >= 0 && producer[r.id] >= 0) alap[producer[r.id]] = std::min(alap[producer[r.id]], alap[i] - 1);
             std::vector<int32_t> pending = n_operands;
             auto cmp = [&](int32_t x, int32_t y) { return alap[x] != alap[y] ? alap[x] > alap[y] : x > y; };  // min-heap on ALAP
@@ -207,14 +246,19 @@ Circuit finalize_circuit(const std::string& name, const CircuitBuilder& b, const
             int32_t done = 0, overflowing = 0;  // levels in which critical gates had to exceed the cap
             for (int32_t L = 1; L <= sched_depth; L++) {
                 int32_t taken = 0;
+                bool over = false;
                 next_ready.clear();
                 while (!ready.empty()) {
                     const int32_t g = ready.top();
-                    if (alap[g] > L && taken >= cap) break;  // only critical gates may exceed the cap
-                    if (taken == cap) overflowing++;
+                    // only critical gates may exceed the cap (a MUX that starts under it may end one rotation over)
+                    if (alap[g] > L && taken >= cap) break;
+                    if (taken >= cap && !over) {
+                        overflowing++;
+                        over = true;
+                    }
                     ready.pop();
                     sched[g] = L;
-                    taken++;
+                    taken += cost(gates[g]);
                     done++;
                     for (int32_t u : users[g])
                         if (--pending[u] == 0) next_ready.push_back(u);  // usable from the next level on
@@ -234,11 +278,18 @@ Circuit finalize_circuit(const std::string& name, const CircuitBuilder& b, const
     // order gates by scheduled level (stable: keeps the reference's program order inside a level)
     std::vector<int32_t> order(gates.size());
     for (size_t i = 0; i < order.size(); i++) order[i] = (int32_t)i;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return sched[x] < sched[y]; });
+    // ... with the MUX gates of a level after its two-input gates: the executor's item arithmetic relies on it (level_items.h)
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
+        return sched[x] != sched[y] ? sched[x] < sched[y] : (gates[x].type == GATE_MUX) < (gates[y].type == GATE_MUX);
+    });
     c.level_offset.assign(depth + 1, 0);
-    for (int32_t i = 0; i < n_gates; i++) c.level_offset[sched[i]]++;
+    c.level_mux.assign(depth, 0);
+    for (int32_t i = 0; i < n_gates; i++) {
+        c.level_offset[sched[i]]++;
+        if (gates[i].type == GATE_MUX) c.level_mux[sched[i] - 1]++;
+    }
     for (int32_t L = 1; L <= depth; L++) {
-        c.sched_max_width = std::max(c.sched_max_width, c.level_offset[L]);
+        c.sched_max_width = std::max(c.sched_max_width, c.level_offset[L] + c.level_mux[L - 1]);  // in blind rotations
         c.level_offset[L] += c.level_offset[L - 1];
     }
 
@@ -249,6 +300,7 @@ Circuit finalize_circuit(const std::string& name, const CircuitBuilder& b, const
         const Gate& g = gates[i];
         if (g.a.id >= 0) last_use[g.a.id] = std::max(last_use[g.a.id], sched[i]);
         if (g.b.id >= 0) last_use[g.b.id] = std::max(last_use[g.b.id], sched[i]);
+        if (g.c.id >= 0) last_use[g.c.id] = std::max(last_use[g.c.id], sched[i]);
     }
     for (const Ref& r : outputs) {
         if (r.id == kUndefId) throw std::logic_error("circuit output was never written");
@@ -288,6 +340,9 @@ Circuit finalize_circuit(const std::string& name, const CircuitBuilder& b, const
             d.b_slot = g.b.id >= 0 ? slot_of[g.b.id] : -1;
             d.b_neg = g.b.neg;
             d.out_slot = s;
+            d.c_slot = g.c.id >= 0 ? slot_of[g.c.id] : -1;
+            d.c_neg = g.type == GATE_MUX ? (int32_t)g.c.neg : 0;
+            c.n_by_type[b.requested_types()[order[pos]]]++;
             if (g.type == GATE_AND) c.n_and++;
             if (g.type == GATE_XOR) c.n_xor++;
         }
@@ -669,6 +724,49 @@ int32_t circuit_level_cap(const Circuit& base, int64_t batch, int32_t resident, 
     return (int32_t)(k * q);
 }
 
+Circuit build_netlist(int32_t n_inputs, const NetGate* gates, size_t n_gates, const int32_t* outputs, size_t n_outputs,
+                      bool balanced) {
+    auto bad = [](const std::string& msg) { throw std::invalid_argument("netlist: " + msg); };
+    if (n_inputs < 1) bad("needs at least one input");
+    if (n_outputs < 1 || !outputs) bad("needs at least one output");
+    if (n_gates && !gates) bad("null gate list");
+    // a reference is wire << 1 | negated in an int32_t; slots, level offsets and widths (a MUX counts 2) are int32_t
+    constexpr int64_t kMaxWires = (int64_t)1 << 30;
+    if ((int64_t)n_inputs + (int64_t)n_gates >= kMaxWires || n_gates >= (size_t)kMaxWires)
+        bad("too large: inputs + gates must stay under 2^30 (gate " + std::to_string(kMaxWires - n_inputs) + " has no wire number)");
+    if (n_outputs >= (size_t)kMaxWires) bad("too many outputs");
+    CircuitBuilder b(n_inputs, /*fold=*/false);
+    // -> the sample a reference names; `limit`: wires defined so far
+    auto ref = [&](int32_t r, int64_t limit, const std::string& where) -> Ref {
+        if (r == -1) return CircuitBuilder::constant(1);
+        if (r == -2) return CircuitBuilder::constant(0);
+        if (r < 0) bad(where + " is not a reference (" + std::to_string(r) + ")");
+        const int32_t w = r >> 1;
+        if (w >= limit)
+            bad(where + " refers to wire " + std::to_string(w) + ", which is not defined there (" + std::to_string(limit) + " wires so far)");
+        return Ref{w, (r & 1) != 0};
+    };
+    for (size_t g = 0; g < n_gates; g++) {
+        const NetGate& ng = gates[g];
+        const std::string at = "gate " + std::to_string(g);
+        if (ng.type < 0 || ng.type >= GATE_TYPES) bad(at + ": unknown gate type " + std::to_string(ng.type));
+        const int64_t limit = (int64_t)n_inputs + (int64_t)g;
+        const Ref a = ref(ng.a, limit, at + ": operand a"), bb = ref(ng.b, limit, at + ": operand b");
+        if (ng.type == GATE_MUX) {
+            b.gate3(GATE_MUX, a, bb, ref(ng.c, limit, at + ": operand c"));
+        } else {
+            if (ng.c != 0) bad(at + ": a two-input gate takes no third operand (c must be 0)");
+            b.gate(ng.type, a, bb);
+        }
+    }
+    Word outs(n_outputs);
+    for (size_t i = 0; i < n_outputs; i++)
+        outs[i] = ref(outputs[i], (int64_t)n_inputs + (int64_t)n_gates, "output " + std::to_string(i) + " (after gate " + std::to_string(n_gates) + ")");
+    Circuit c = finalize_circuit("netlist", b, outs, balanced, 0);
+    c.n_reference_bootstraps = c.n_bootstraps;
+    return c;
+}
+
 void simulate_circuit(const Circuit& c, const uint8_t* in, uint8_t* out) {
     std::vector<uint8_t> store(c.n_slots, 0);
     for (int32_t i = 0; i < c.n_inputs; i++) store[i] = in[i] & 1;
@@ -689,6 +787,8 @@ void simulate_circuit(const Circuit& c, const uint8_t* in, uint8_t* out) {
                 case GATE_XOR: r = a ^ b; break;
                 case GATE_OR: r = a | b; break;
                 case GATE_NAND: r = !(a & b); break;
+                case GATE_XNOR: r = !(a ^ b); break;
+                case GATE_MUX: r = a ? b : val(d.c_slot, d.c_neg); break;
             }
             res[g - lo] = r;
         }

@@ -27,13 +27,27 @@ struct Ref {
 constexpr int32_t kConstId = -1;
 constexpr int32_t kUndefId = -2;
 
-enum GateType : int32_t { GATE_AND = 0, GATE_XOR = 1, GATE_OR = 2, GATE_NAND = 3 };
+// libtfhe's boot-gates.cpp.  AND / XOR / OR / NAND / XNOR / MUX are what the device executes.  NOR, ANDNY, ANDYN, ORNY, ORYN
+// are AND / OR with operand signs flipped -- the same linear combination as libtfhe's, word for word -- and are recorded
+// that way (CircuitBuilder::gate lowers them), so a DevGate's type is never one of them.
+enum GateType : int32_t {
+    GATE_AND = 0, GATE_XOR = 1, GATE_OR = 2, GATE_NAND = 3,
+    GATE_MUX = 4,    // a ? b : c -- two blind rotations, one key switch
+    GATE_NOR = 5,    // (0,-1/8) - ca - cb   = AND(NOT a, NOT b)
+    GATE_XNOR = 6,   // (0,-1/4) - 2(ca+cb)  -- the negated INPUT of XOR's bootstrap, not NOT(XOR): a type of its own
+    GATE_ANDNY = 7,  // (0,-1/8) - ca + cb   = AND(NOT a, b)
+    GATE_ANDYN = 8,  // (0,-1/8) + ca - cb   = AND(a, NOT b)
+    GATE_ORNY = 9,   // (0, 1/8) - ca + cb   = OR(NOT a, b)
+    GATE_ORYN = 10,  // (0, 1/8) + ca - cb   = OR(a, NOT b)
+    GATE_TYPES = 11
+};
 
 struct Gate {
     int32_t type;
     Ref a, b;
     int32_t out;    // wire id
     int32_t level;  // 1-based ASAP level
+    Ref c{kConstId, false};  // third operand (GATE_MUX only)
 };
 
 using Word = std::vector<Ref>;
@@ -53,6 +67,7 @@ public:
     static Ref NOT(Ref a) { return Ref{a.id, !a.neg}; }                     // bootsNOT
     static Word fresh(int32_t count = 32) { return Word(count, Ref{kUndefId, false}); }
     Ref gate(int32_t type, Ref a, Ref b);                                    // bootsAND / bootsXOR ...
+    Ref gate3(int32_t type, Ref a, Ref b, Ref c);                            // bootsMUX: a ? b : c
     Ref AND(Ref a, Ref b) { return gate(GATE_AND, a, b); }
     Ref XOR(Ref a, Ref b) { return gate(GATE_XOR, a, b); }
 
@@ -76,6 +91,7 @@ public:
     int32_t n_inputs() const { return n_inputs_; }
     const std::vector<Gate>& gates() const { return gates_; }
     int32_t n_wires() const { return next_wire_; }
+    const std::vector<int32_t>& requested_types() const { return requested_type_; }
     int64_t n_requested() const { return n_requested_; }  // gates the reference performs (before folding)
 
 private:
@@ -84,17 +100,20 @@ private:
     bool fold_;
     int64_t n_requested_ = 0;
     std::vector<Gate> gates_;
+    std::vector<int32_t> requested_type_;  // per recorded gate: the type asked for (before NOR .. ORYN were lowered)
     std::vector<int32_t> wire_level_;
     std::map<std::tuple<int32_t, int32_t, int32_t, int32_t, int32_t>, int32_t> known_;  // (type,a,na,b,nb) -> wire
 };
 
 // One gate as the device executor consumes it.  Slots index the wire store;
 // slot -1 means the constant (0,-1/8).  flags bit0 = negate the operand.
+// c_*: third operand of a GATE_MUX (unused, slot -1, otherwise).
 struct DevGate {
     int32_t type;
     int32_t a_slot, a_neg;
     int32_t b_slot, b_neg;
     int32_t out_slot;
+    int32_t c_slot, c_neg;
 };
 
 struct OutRef {
@@ -109,14 +128,18 @@ struct Circuit {
     int32_t n_slots = 0;                // wire-store rows per expression
     std::vector<DevGate> gates;         // sorted by level
     std::vector<int32_t> level_offset;  // gates of level L are [level_offset[L-1], level_offset[L])
+    std::vector<int32_t> level_mux;     // [L-1]: how many of level L's gates are MUX -- the LAST ones of the level (level_items.h)
     std::vector<OutRef> outputs;        // output samples per expression
-    // statistics
+    // statistics.  Counts and widths are in BLIND ROTATIONS: a MUX gate counts 2 (as libtfhe's bootsMUX
+    // bootstraps twice), so that batch x n_bootstraps is what an evaluation reports and a width is what a launch holds.
     int64_t n_bootstraps = 0, n_and = 0, n_xor = 0;
+    int64_t n_by_type[GATE_TYPES] = {};  // gates by the type they were requested as (a MUX counts 1 here)
     int32_t depth = 0, max_width = 0;  // ASAP depth / widest ASAP level
     int32_t sched_max_width = 0;       // widest level of the schedule actually executed
     int64_t n_reference_bootstraps = 0;  // what cloud.c performs for this circuit (== n_bootstraps unless folded)
     bool balanced_schedule = false;      // slack-balanced list schedule (64/128-bit multipliers) rather than ASAP levels
     int32_t n_levels() const { return (int32_t)level_offset.size() - 1; }
+    int32_t n_mux(int32_t L) const { return level_mux.empty() ? 0 : level_mux[L - 1]; }  // MUX gates of level L (1-based)
 };
 
 // Levelise + allocate slots.  `outputs` are the samples to return per expression.
@@ -124,6 +147,15 @@ struct Circuit {
 // level_cap > 0: gates per level of the balanced schedule (0 = the mean ASAP width); see circuit_level_cap().
 Circuit finalize_circuit(const std::string& name, const CircuitBuilder& b, const Word& outputs, bool balanced = true,
                          int32_t level_cap = 0);
+
+// A caller-defined netlist (include/ieache.h: ieache_netlist_create).  Gate g's output is wire n_inputs + g; a reference is
+// wire << 1 | negated, or -2 / -1 for the constants false / true.  Every recorded gate is bootstrapped (no folding).
+// Throws std::invalid_argument naming the offending gate; nothing is returned half-built.
+struct NetGate {
+    int32_t type, a, b, c;
+};
+Circuit build_netlist(int32_t n_inputs, const NetGate* gates, size_t n_gates, const int32_t* outputs, size_t n_outputs,
+                      bool balanced);
 
 // ---- the circuits main() dispatches to (cloud.c:870-2718) ----
 // Input sample order for all of them: operand 1 words (32 samples each, LSB

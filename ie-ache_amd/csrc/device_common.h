@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "circuit.h"
+#include "level_items.h"
 #include "params.h"
 
 namespace ieache {
@@ -20,9 +21,14 @@ struct DevKeys {
 };
 
 // Where the gate instances of one launch live.
+// Circuit mode: a level is `ng` gates per expression of which the last `nm` are MUX, i.e. ni = ng + nm ROTATION items per
+// expression (level_items.h); item0 and the item index of a blind-rotation launch count rotation items.  The key switch of
+// such a level runs on one row per GATE: it gets the same descriptor with nm = 0 and item0 in gate instances, for which
+// the arithmetic below is the identity it has always been (only GateInst::out is used there).
 struct WorkDesc {
     const DevGate* gates;  // circuit mode when non-null
     int32_t g0, ng;
+    int32_t nm;            // circuit mode: MUX gates among the ng (the last ones)
     Torus32* store;
     int32_t n_slots;
     const Torus32* flat_a;  // flat mode: rows [item]
@@ -45,30 +51,51 @@ struct GateInst {
     uint32_t cst;
 };
 
-__device__ __forceinline__ void gate_coeffs(int32_t type, int32_t& k, uint32_t& cst) {
-    // boot-gates.cpp: AND (0,-1/8)+ca+cb ; XOR (0,1/4)+2(ca+cb) ; OR (0,1/8)+ca+cb ; NAND (0,1/8)-ca-cb
+// multipliers of the two operands and the constant term of a two-input gate
+__device__ __forceinline__ void gate_coeffs(int32_t type, int32_t& ka, int32_t& kb, uint32_t& cst) {
+    // boot-gates.cpp: AND (0,-1/8)+ca+cb ; XOR (0,1/4)+2(ca+cb) ; OR (0,1/8)+ca+cb ; NAND (0,1/8)-ca-cb ;
+    // XNOR (0,-1/4)-2(ca+cb) ; NOR (0,-1/8)-ca-cb ; ANDNY (0,-1/8)-ca+cb ; ANDYN (0,-1/8)+ca-cb ; ORNY (0,1/8)-ca+cb ;
+    // ORYN (0,1/8)+ca-cb.  (In a circuit the last five arrive as AND / OR with operand sign flags; flat calls name them.)
     switch (type) {
-        case GATE_AND: k = 1; cst = 0xE0000000u; break;
-        case GATE_XOR: k = 2; cst = 0x40000000u; break;
-        case GATE_OR: k = 1; cst = 0x20000000u; break;
-        default: k = -1; cst = 0x20000000u; break;  // NAND
+        case GATE_AND: ka = kb = 1; cst = 0xE0000000u; break;
+        case GATE_XOR: ka = kb = 2; cst = 0x40000000u; break;
+        case GATE_OR: ka = kb = 1; cst = 0x20000000u; break;
+        case GATE_XNOR: ka = kb = -2; cst = 0xC0000000u; break;
+        case GATE_NOR: ka = kb = -1; cst = 0xE0000000u; break;
+        case GATE_ANDNY: ka = -1; kb = 1; cst = 0xE0000000u; break;
+        case GATE_ANDYN: ka = 1; kb = -1; cst = 0xE0000000u; break;
+        case GATE_ORNY: ka = -1; kb = 1; cst = 0x20000000u; break;
+        case GATE_ORYN: ka = 1; kb = -1; cst = 0x20000000u; break;
+        default: ka = kb = -1; cst = 0x20000000u; break;  // NAND
     }
 }
 
 __device__ __forceinline__ GateInst resolve(const WorkDesc& W, int64_t item, int32_t stride) {
     GateInst g;
-    int32_t type, k;
+    int32_t type, ka, kb;
     if (W.gates) {
-        const int64_t b = item / W.ng;
-        const DevGate d = W.gates[W.g0 + (int32_t)(item % W.ng)];
-        Torus32* base = W.store + (size_t)b * W.n_slots * stride;
+        const LevelItem it = level_item(item, W.ng, W.nm);  // nm == 0: (item / ng, item % ng, 0)
+        const DevGate d = W.gates[W.g0 + it.gate];
+        Torus32* base = W.store + (size_t)it.expr * W.n_slots * stride;
         type = d.type;
-        gate_coeffs(type, k, g.cst);
+        int32_t y_slot = d.b_slot, y_neg = d.b_neg;  // second operand of this rotation
+        if (type == GATE_MUX) {
+            // bootsMUX(a, b, c): half 0 is (0,-1/8) + a + b, half 1 is (0,-1/8) - a + c
+            g.cst = 0xE0000000u;
+            ka = it.half ? -1 : 1;
+            kb = 1;
+            if (it.half) {
+                y_slot = d.c_slot;
+                y_neg = d.c_neg;
+            }
+        } else {
+            gate_coeffs(type, ka, kb, g.cst);
+        }
         g.a = d.a_slot >= 0 ? base + (size_t)d.a_slot * stride : nullptr;
-        g.b = d.b_slot >= 0 ? base + (size_t)d.b_slot * stride : nullptr;
+        g.b = y_slot >= 0 ? base + (size_t)y_slot * stride : nullptr;
         g.out = base + (size_t)d.out_slot * stride;
-        g.sa = d.a_neg ? -k : k;
-        g.sb = d.b_neg ? -k : k;
+        g.sa = d.a_neg ? -ka : ka;
+        g.sb = y_neg ? -kb : kb;
         // a constant operand is (0, -1/8): only its b term contributes
         if (!g.a) g.cst += (uint32_t)g.sa * 0xE0000000u;
         if (!g.b) g.cst += (uint32_t)g.sb * 0xE0000000u;
@@ -83,12 +110,12 @@ __device__ __forceinline__ GateInst resolve(const WorkDesc& W, int64_t item, int
         g.sb = 1;
     } else {
         type = W.flat_type;
-        gate_coeffs(type, k, g.cst);
+        gate_coeffs(type, ka, kb, g.cst);
         g.a = W.flat_a + (size_t)item * stride;
         g.b = W.flat_b ? W.flat_b + (size_t)item * stride : nullptr;
         g.out = W.flat_out + (size_t)item * stride;
-        g.sa = k;
-        g.sb = k;
+        g.sa = ka;
+        g.sb = kb;
         if (type < 0) {  // raw bootstrap of the row in flat_a (debug hook)
             g.sa = 1;
             g.sb = 0;

@@ -485,6 +485,34 @@ __global__ void k_mux_combine(const Torus32* ext, Torus32* dst, int32_t N) {
         d[j] = (int32_t)((uint32_t)u1[j] + (uint32_t)u2[j] + (j == N ? (uint32_t)kMU : 0u));
 }
 
+// A circuit level with MUX gates (level_items.h): the rows of extracted samples of one piece, one per ROTATION item, become
+// one row per GATE for the key switch -- a two-input gate's row as it is, a MUX gate's as k_mux_combine forms it,
+// (0, 1/8) + u1 + u2 over its two rotations (boot-gates.cpp).  One workgroup per gate of the piece; pure streaming, rows
+// of N + 4 words moved as 16-byte words (N is a multiple of 4, so word N -- the b term -- is lane x of 16-byte word N / 4).
+// gate0 / item0: the piece's first gate instance / rotation item; the caller cuts pieces at gate boundaries, so both rows of
+// a MUX are inside ext's `cnt` rows.
+__global__ __launch_bounds__(256) void k_level_combine(const Torus32* ext, Torus32* dst, int32_t N, int64_t gate0, int64_t item0,
+                                                       int32_t ng, int32_t nm) {
+    const int64_t q = gate0 + (int64_t)blockIdx.x;
+    const int64_t row = level_first_item(q, ng, nm) - item0;
+    const bool mux = (int32_t)(q % ng) >= ng - nm;
+    const int32_t R = (N + 4) >> 2;
+    const int4* u1 = reinterpret_cast<const int4*>(ext) + (size_t)row * R;
+    const int4* u2 = u1 + R;
+    int4* d = reinterpret_cast<int4*>(dst) + (size_t)blockIdx.x * R;
+    for (int32_t v = threadIdx.x; v < R; v += 256) {
+        int4 x = u1[v];
+        if (mux) {
+            const int4 y = u2[v];
+            x.x = (int32_t)((uint32_t)x.x + (uint32_t)y.x + (v == (N >> 2) ? (uint32_t)kMU : 0u));
+            x.y = (int32_t)((uint32_t)x.y + (uint32_t)y.y);
+            x.z = (int32_t)((uint32_t)x.z + (uint32_t)y.z);
+            x.w = (int32_t)((uint32_t)x.w + (uint32_t)y.w);
+        }
+        d[v] = x;
+    }
+}
+
 // Audit of the one-limb blind rotation: rows of extracted samples it produced against the same gate instances run on the
 // two-limb (provably exact) kernel.  One workgroup per row; any differing word counts the row in *mismatches.
 // inject: test hook -- row 0 is compared as if its first word differed.
@@ -528,6 +556,8 @@ struct Lane {
     hipStream_t stream = nullptr;
     Torus32* ext = nullptr;
     size_t ext_items = 0;
+    Torus32* comb = nullptr;   // levels with MUX gates: one combined row per gate of a piece (k_level_combine).  Per lane, not
+    size_t comb_items = 0;     // per context: two lanes run their combines and key switches side by side
     void* br_state = nullptr;  // sliced blind rotation: accumulators + rotation amounts
     size_t br_state_items = 0;
     void* ks_digits = nullptr;
@@ -762,6 +792,7 @@ void Evaluator::destroy() {
     (void)hipFree(d_->wtab);
     for (Lane& ln : d_->lane) {
         (void)hipFree(ln.ext);
+        (void)hipFree(ln.comb);
         (void)hipFree(ln.br_state);
         (void)hipFree(ln.ks_digits);
         (void)hipFree(ln.audit_ext);
@@ -1297,14 +1328,27 @@ static LevelPlan plan_level(const Evaluator::Impl* d, int64_t items) {
     const int64_t chunk = (int64_t)d->chunk;
     LevelPlan pl{false, chunk};
     if (d->overlap && d->use_w64 && d->concurrency == 1 && items >= d->overlap_min && items >= 2) {
-        pl.two_lanes = true;
         const int64_t half = (((items + 1) / 2) + 3) & ~(int64_t)3;  // whole workgroups of the one-wave-per-gate kernels
-        pl.piece = std::min(chunk, half);
+        // two lanes only when there are two pieces to give them: up to 4 items the rounded half is the whole level, and a
+        // fork would then use a second stream nobody has created (reserve_scratch sees nothing to reserve for it)
+        if (std::min(chunk, half) < items) {
+            pl.two_lanes = true;
+            pl.piece = std::min(chunk, half);
+        }
     }
     return pl;
 }
 
-static void reserve_lane(const Params& p, Evaluator::Impl* d, Lane& ln, size_t need) {
+// need: rotation items of the lane's widest piece; need_comb: gates of its widest piece of a level with MUX gates (0 = none)
+static void reserve_lane(const Params& p, Evaluator::Impl* d, Lane& ln, size_t need, size_t need_comb = 0) {
+    if (ln.comb_items < need_comb) {
+        const size_t n = grown(ln.comb_items, need_comb, d->chunk);
+        if (ln.comb) HIP_CHECK(hipFree(ln.comb));
+        ln.comb = nullptr;
+        ln.comb_items = 0;
+        HIP_CHECK(hipMalloc(&ln.comb, n * (size_t)(d->K.N + 4) * 4));
+        ln.comb_items = n;
+    }
     if (ln.ext_items < need) {
         const size_t n = grown(ln.ext_items, need, d->chunk);
         if (ln.ext) HIP_CHECK(hipFree(ln.ext));
@@ -1348,19 +1392,29 @@ static void join_lanes(Evaluator::Impl* d, int lanes) {
 // Before an evaluation starts: scratch for its widest launch in one go (the per-launch checks below then find it in place),
 // so that a circuit whose levels widen does not reallocate -- and synchronise -- between them.  level_items: gate instances
 // of each level the evaluation will issue.
-static void reserve_scratch(const Params& p, Evaluator::Impl* d, const int64_t* level_items, size_t n_levels) {
-    size_t need0 = 1, need1 = 0;
+// level_gates (may be null: no level has MUX gates): gate instances of each level -- fewer than its rotation items where it
+// has MUX gates.  A piece of such a level may end one item past the planned size (level_items.h: level_piece_items) and needs
+// combined rows, one per gate: at most as many as it has items, and never more than the level has gates.
+static void reserve_scratch(const Params& p, Evaluator::Impl* d, const int64_t* level_items, size_t n_levels,
+                            const int64_t* level_gates = nullptr) {
+    size_t need0 = 1, need1 = 0, comb0 = 0, comb1 = 0;
     for (size_t i = 0; i < n_levels; i++) {
         const int64_t items = std::max<int64_t>(level_items[i], 1);
+        const bool mux = level_gates && level_gates[i] < level_items[i];
         const LevelPlan pl = plan_level(d, items);
-        const size_t piece = (size_t)std::min<int64_t>(pl.piece, items);
+        const size_t piece = (size_t)std::min<int64_t>(pl.piece + (mux ? 1 : 0), items);
         need0 = std::max(need0, piece);
-        if (pl.two_lanes) need1 = std::max(need1, std::min<size_t>(piece, (size_t)(items - (int64_t)piece)));
+        if (mux) comb0 = std::max(comb0, std::min<size_t>(piece, (size_t)level_gates[i]));
+        if (pl.two_lanes) {
+            const size_t rest = std::min<size_t>(piece, (size_t)(items - pl.piece));
+            need1 = std::max(need1, rest);
+            if (mux) comb1 = std::max(comb1, std::min<size_t>(rest, (size_t)level_gates[i]));
+        }
     }
-    reserve_lane(p, d, d->lane[0], need0);
+    reserve_lane(p, d, d->lane[0], need0, comb0);
     if (need1) {
         ensure_second_lane(d);
-        reserve_lane(p, d, d->lane[1], need1);
+        reserve_lane(p, d, d->lane[1], need1, comb1);
     }
 }
 
@@ -1371,12 +1425,24 @@ static void reserve_scratch(const Params& p, Evaluator::Impl* d, const int64_t* 
 static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t items, Timer& tbr, Timer& tks, EvalStats* stats,
                       int fixed_lane = -1) {
     LevelPlan pl = plan_level(d, items);
+    // A level with MUX gates (circuit mode, W.nm > 0): `items` are rotation items, two per MUX.  PIECES ARE CUT AT GATE
+    // BOUNDARIES (level_piece_items), so both rotations of a MUX are in the same piece, on the same lane, in the same `ext`,
+    // before its combine runs.  That one rule covers every way a level is cut:
+    //   * "chunk", odd values included: a piece that would end between a MUX's two items takes the second one as well;
+    //   * level halves on two lanes (plan_level): the halves are pieces like any other, each lane combines its own;
+    //   * expression-half pipelines (fixed_lane): a pipeline's share starts and ends at an expression, which is a gate boundary;
+    //   * the rotation of roles cuts a launch into subsets INSIDE launch_blind_rotate, and its last act is to make the lane's
+    //     stream wait for every subset's stream (launch_mixed_phases' join) before the final slices write `ext` there: what is
+    //     queued on the lane's stream afterwards -- audit, combine, key switch -- sees the whole piece.
+    const bool mux = W.gates && W.nm > 0;
+    const int64_t gates = mux ? items / (W.ng + W.nm) * W.ng : items;  // gate instances of the level
     if (fixed_lane >= 0) {
         pl.two_lanes = false;
         pl.piece = (int64_t)d->chunk;
-        reserve_lane(p, d, d->lane[fixed_lane], (size_t)std::min<int64_t>(pl.piece, std::max<int64_t>(items, 1)));
+        const size_t need = (size_t)std::min<int64_t>(pl.piece + (mux ? 1 : 0), std::max<int64_t>(items, 1));
+        reserve_lane(p, d, d->lane[fixed_lane], need, mux ? std::min<size_t>(need, (size_t)gates) : 0);
     } else {
-        reserve_scratch(p, d, &items, 1);
+        reserve_scratch(p, d, &items, 1, mux ? &gates : nullptr);
     }
     if (pl.two_lanes) {
         fork_lanes(d, 2);
@@ -1384,18 +1450,35 @@ static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t i
     }
     d->level_on_two_lanes = pl.two_lanes;
     int k = 0;
-    for (int64_t done = 0; done < items; done += pl.piece, k++) {
-        const int64_t cnt = std::min<int64_t>(pl.piece, items - done);
+    for (int64_t done = 0, cnt = 0; done < items; done += cnt, k++) {
+        cnt = mux ? level_piece_items(W.item0 + done, pl.piece, items - done, W.ng, W.nm) : std::min<int64_t>(pl.piece, items - done);
         Lane& ln = d->lane[fixed_lane >= 0 ? fixed_lane : (pl.two_lanes ? (k & 1) : 0)];
         WorkDesc w = W;
         w.item0 = W.item0 + done;
+        if ((size_t)cnt > ln.ext_items) throw std::logic_error("piece larger than the lane's extracted-sample rows");
         tbr.mark(ln.stream);
         const int nbr = launch_blind_rotate(p, d, ln, w, cnt, ln.ext, -1, nullptr);
         tbr.mark(ln.stream);
         HIP_CHECK(hipGetLastError());
         maybe_audit(p, d, ln, w, cnt, ln.ext);
         tks.mark(ln.stream);
-        launch_keyswitch(d, ln, w, cnt, ln.ext, nullptr, d->force_generic_ks);
+        if (mux) {
+            // one row per gate, then the key switch over GATES: the same level descriptor read with nm = 0 and item0 in gate
+            // instances, for which resolve() is the identity the key-switch kernels have always used to find out_slot
+            if (!level_gate_boundary(w.item0, W.ng, W.nm) || !level_gate_boundary(w.item0 + cnt, W.ng, W.nm))
+                throw std::logic_error("piece of a level cut inside a MUX gate");
+            const int64_t gate0 = level_gates_before(w.item0, W.ng, W.nm);
+            const int64_t gcnt = level_gates_before(w.item0 + cnt, W.ng, W.nm) - gate0;
+            if ((size_t)gcnt > ln.comb_items || (d->K.N & 3)) throw std::logic_error("combined rows of a MUX level not reserved");
+            hipLaunchKernelGGL(k_level_combine, dim3((unsigned)gcnt), dim3(256), 0, ln.stream, ln.ext, ln.comb, d->K.N, gate0, w.item0,
+                               W.ng, W.nm);
+            WorkDesc wk = w;
+            wk.nm = 0;
+            wk.item0 = gate0;
+            launch_keyswitch(d, ln, wk, gcnt, ln.comb, nullptr, d->force_generic_ks);
+        } else {
+            launch_keyswitch(d, ln, w, cnt, ln.ext, nullptr, d->force_generic_ks);
+        }
         tks.mark(ln.stream);
         HIP_CHECK(hipGetLastError());
         if (stats) {
@@ -1612,7 +1695,8 @@ static int pipelined(Evaluator::Impl* d, const Circuit& c, size_t batch, int* tr
     if (trial) *trial = -1;
     if (!d->overlap || !d->use_w64 || batch < 2 || c.n_levels() < 1) return 0;
     const int lanes = (int)std::min<size_t>((size_t)d->pipe_lanes, batch);
-    const int64_t gates = (int64_t)c.level_offset[c.n_levels()] - (int64_t)c.level_offset[0];
+    int64_t gates = (int64_t)c.level_offset[c.n_levels()] - (int64_t)c.level_offset[0];
+    for (int32_t m : c.level_mux) gates += m;  // in blind rotations: a MUX is two
     const int64_t work = gates * (int64_t)batch, bar = d->pipe_min * (int64_t)c.n_levels();  // mean level against pipe_min
     // From 2 x pipe_min on pipelines won every measurement.  Below, it depends on where the levels fall among the kernels'
     // regimes (a level of 2 200 gate instances as two pipelines' launches of 1 100 costs a second, nearly empty round; on one
@@ -1673,23 +1757,32 @@ void Evaluator::prepare_circuit(const Circuit& c, size_t batch) {
         HIP_CHECK(hipMalloc(&d_->d_outs, c.outputs.size() * sizeof(OutRef)));
         d_->d_outs_cap = c.outputs.size();
     }
-    std::vector<int64_t> level_items;
-    for (int32_t L = 1; L <= c.n_levels(); L++)
-        level_items.push_back((int64_t)(c.level_offset[L] - c.level_offset[L - 1]) * (int64_t)batch);
+    // rotation items (a MUX gate is two) and gate instances of each level
+    std::vector<int64_t> level_items, level_gates;
+    int64_t widest = 1, widest_mux_gates = 0;  // per expression: the widest level in items; the most gates of a level that has MUX gates
+    bool mux = false;
+    for (int32_t L = 1; L <= c.n_levels(); L++) {
+        const int64_t ng = c.level_offset[L] - c.level_offset[L - 1], nm = c.n_mux(L);
+        level_items.push_back((ng + nm) * (int64_t)batch);
+        level_gates.push_back(ng * (int64_t)batch);
+        widest = std::max(widest, ng + nm);
+        if (nm) widest_mux_gates = std::max(widest_mux_gates, ng);
+        mux = mux || nm > 0;
+    }
+    const int64_t* lg = mux ? level_gates.data() : nullptr;
     if (const int lanes = pipelined(d_, c, batch, nullptr, /*either=*/true)) {
         // pipelines of batch / lanes expressions each (the first ones take the odd ones); where the mode is still being
         // tried out (pipe_auto) the one-stream scratch is reserved as well
-        if (!pipelined(d_, c, batch)) reserve_scratch(p_, d_, level_items.data(), level_items.size());
-        int64_t widest = 1;
-        for (int32_t L = 1; L <= c.n_levels(); L++) widest = std::max<int64_t>(widest, c.level_offset[L] - c.level_offset[L - 1]);
+        if (!pipelined(d_, c, batch)) reserve_scratch(p_, d_, level_items.data(), level_items.size(), lg);
         ensure_lanes(d_, lanes);
         for (int k = 0; k < lanes; k++) {
             size_t first = 0, count = 0;
             pipe_slice(batch, lanes, k, &first, &count);
-            reserve_lane(p_, d_, d_->lane[k], std::min<size_t>(d_->chunk, (size_t)widest * count));
+            const size_t need = std::min<size_t>(d_->chunk + (mux ? 1 : 0), (size_t)widest * count);
+            reserve_lane(p_, d_, d_->lane[k], need, mux ? std::min<size_t>(need, (size_t)widest_mux_gates * count) : 0);
         }
     } else {
-        reserve_scratch(p_, d_, level_items.data(), level_items.size());
+        reserve_scratch(p_, d_, level_items.data(), level_items.size(), lg);
     }
 }
 
@@ -1726,18 +1819,21 @@ void Evaluator::eval_circuit_device_once(const Circuit& c, size_t batch, const T
             W.gates = d_->d_gates;
             W.g0 = c.level_offset[L - 1];
             W.ng = c.level_offset[L] - c.level_offset[L - 1];
+            W.nm = c.n_mux(L);
             W.store = d_->store;
             W.n_slots = c.n_slots;
             W.item0 = 0;
+            const int64_t ni = (int64_t)W.ng + (int64_t)W.nm;  // rotation items per expression (level_items.h)
             if (!pipes) {
-                run_items(p_, d_, W, (int64_t)W.ng * (int64_t)batch, tbr, tks, stats);
+                run_items(p_, d_, W, ni * (int64_t)batch, tbr, tks, stats);
             } else {
-                // items are expression-major (item = expression x ng + gate): a contiguous range of expressions is a contiguous range of items
+                // items are expression-major (item = expression x ni + position): a contiguous range of expressions is a
+                // contiguous range of items that starts and ends at a gate boundary
                 for (int k = 0; k < pipes; k++) {
                     size_t first = 0, count = 0;
                     pipe_slice(batch, pipes, k, &first, &count);
-                    W.item0 = (int64_t)W.ng * (int64_t)first;
-                    run_items(p_, d_, W, (int64_t)W.ng * (int64_t)count, tbr, tks, stats, k);
+                    W.item0 = ni * (int64_t)first;
+                    run_items(p_, d_, W, ni * (int64_t)count, tbr, tks, stats, k);
                 }
             }
             if (stats) stats->levels++;

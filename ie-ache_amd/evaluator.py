@@ -17,6 +17,15 @@ CIRC_ADD, CIRC_SUB, CIRC_RSUB, CIRC_MUL, CIRC_MULADD = 1, 2, 3, 4, 5
 CIRC_ADD_KS, CIRC_SUB_KS, CIRC_RSUB_KS = 6, 7, 8  # Kogge-Stone variants (decrypt-identical, not bit-identical)
 CIRC_MUL_WALLACE = 9  # carry-save multiplier (decrypt-identical, not bit-identical)
 GATE_AND, GATE_XOR, GATE_OR, GATE_NAND, GATE_MUX = 0, 1, 2, 3, 4
+GATE_NOR, GATE_XNOR, GATE_ANDNY, GATE_ANDYN, GATE_ORNY, GATE_ORYN = 5, 6, 7, 8, 9, 10  # libtfhe boot-gates.cpp
+GATE_TYPES = 11
+# references inside a Netlist (IEACHE_NET_*): wire << 1 | negated, or a constant
+FALSE, TRUE = -2, -1
+
+
+def NOT(ref):
+    """bootsNOT of a netlist reference (free: a sign flag, no bootstrap)."""
+    return int(ref) ^ 1
 
 
 def circ_chain(k1, k2, flip=True):
@@ -145,6 +154,14 @@ def lib():
     L.ieache_prepare_batch.argtypes = [vp, C.c_int, C.c_int, C.c_size_t]
     L.ieache_gates_device.argtypes = [vp, C.c_int, C.c_size_t, vp, vp, vp, sp]
     L.ieache_gates.argtypes = [vp, C.c_int, C.c_size_t, i32p, i32p, i32p, sp]
+    L.ieache_netlist_create.restype = vp
+    L.ieache_netlist_create.argtypes = [C.c_int32, vp, C.c_size_t, i32p, C.c_size_t, C.c_int]
+    L.ieache_netlist_destroy.argtypes = [vp]
+    L.ieache_netlist_info.argtypes = [vp, C.POINTER(CircuitInfo), C.POINTER(C.c_int64)]
+    L.ieache_netlist_simulate.argtypes = [vp, u8p, u8p]
+    L.ieache_prepare_netlist.argtypes = [vp, vp, C.c_size_t]
+    L.ieache_eval_netlist.argtypes = [vp, vp, C.c_size_t, i32p, i32p, sp]
+    L.ieache_eval_netlist_device.argtypes = [vp, vp, C.c_size_t, vp, vp, sp]
     L.ieache_debug_blind_rotate.argtypes = [vp, C.c_size_t, i32p, i32p, C.c_int32]
     L.ieache_debug_keyswitch.argtypes = [vp, C.c_size_t, i32p, i32p]
     L.ieache_keygen_raw.argtypes = [pp, u32p, C.c_int, i32p, i32p, i32p, i32p]
@@ -215,6 +232,103 @@ def circuit_simulate(kind, bits, in_bits, fold=False, level_cap=0):
     check(lib().ieache_circuit_simulate_cap(kind, bits, int(fold), int(level_cap), in_bits.ctypes.data_as(C.POINTER(C.c_uint8)),
                                             out.ctypes.data_as(C.POINTER(C.c_uint8))))
     return out
+
+
+class Netlist:
+    """A circuit of your own, recorded gate by gate as a program would call libtfhe's bootsAND / bootsXNOR / bootsMUX ...:
+
+        nl = Netlist(3)
+        s = nl.XOR(nl.input(0), nl.input(1))
+        out = nl.MUX(nl.input(2), s, NOT(s))
+        compiled = nl.compile([out, TRUE])
+
+    Every method returns a reference usable as a later gate's operand or as an output; NOT(ref), TRUE and FALSE are free
+    (bootsNOT / bootsCONSTANT).  Nothing is folded: each recorded gate is bootstrapped.  Host only -- no GPU, no context."""
+
+    def __init__(self, n_inputs):
+        self.n_inputs = int(n_inputs)
+        self._gates = []  # (type, a, b, c)
+
+    def input(self, i):
+        if not 0 <= i < self.n_inputs:
+            raise IndexError("netlist input %d of %d" % (i, self.n_inputs))
+        return int(i) << 1
+
+    def inputs(self, first, count):
+        return [self.input(first + i) for i in range(count)]
+
+    def gate(self, gate_type, a, b, c=0):
+        """Records one gate and returns the reference of its output; c is bootsMUX's third operand (a ? b : c)."""
+        self._gates.append((int(gate_type), int(a), int(b), int(c)))
+        return (self.n_inputs + len(self._gates) - 1) << 1
+
+    def AND(self, a, b): return self.gate(GATE_AND, a, b)
+    def OR(self, a, b): return self.gate(GATE_OR, a, b)
+    def XOR(self, a, b): return self.gate(GATE_XOR, a, b)
+    def NAND(self, a, b): return self.gate(GATE_NAND, a, b)
+    def NOR(self, a, b): return self.gate(GATE_NOR, a, b)
+    def XNOR(self, a, b): return self.gate(GATE_XNOR, a, b)
+    def ANDNY(self, a, b): return self.gate(GATE_ANDNY, a, b)
+    def ANDYN(self, a, b): return self.gate(GATE_ANDYN, a, b)
+    def ORNY(self, a, b): return self.gate(GATE_ORNY, a, b)
+    def ORYN(self, a, b): return self.gate(GATE_ORYN, a, b)
+    def MUX(self, a, b, c): return self.gate(GATE_MUX, a, b, c)
+
+    def __len__(self):
+        return len(self._gates)
+
+    def compile(self, outputs, balanced=False):
+        """-> CompiledNetlist returning `outputs` (references) per expression.  balanced: the slack-balanced schedule at the
+        mean level width instead of ASAP levels.  Raises IeacheError naming the offending gate when the list is not valid."""
+        gates = np.ascontiguousarray(np.array(self._gates, dtype=np.int32).reshape(-1, 4))
+        outs = np.ascontiguousarray(np.array(list(outputs), dtype=np.int32).reshape(-1))
+        h = lib().ieache_netlist_create(self.n_inputs, gates.ctypes.data_as(C.c_void_p), gates.shape[0], _i32(outs), outs.size,
+                                        1 if balanced else 0)
+        if not h:
+            raise IeacheError(-22, lib().ieache_last_error().decode())
+        return CompiledNetlist(h, self.n_inputs, list(self._gates), [int(o) for o in outs])
+
+
+class CompiledNetlist:
+    """ieache_netlist: validated, levelised, slot-allocated; what Context.eval_netlist takes.  May be shared by contexts."""
+
+    def __init__(self, handle, n_inputs=0, gates=(), outputs=()):
+        self.h = handle
+        # the gate list it was compiled from, (type, a, b, c) per gate, and its output references: for walking it elsewhere
+        self.n_inputs, self.gates, self.outputs = n_inputs, gates, outputs
+        self._info = CircuitInfo()
+        self._by_type = (C.c_int64 * GATE_TYPES)()
+        check(lib().ieache_netlist_info(self.h, C.byref(self._info), self._by_type))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ieache_netlist_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def info(self):
+        """CircuitInfo; bootstraps and widths count blind rotations (a MUX gate is two)."""
+        return self._info
+
+    def gates_by_type(self):
+        """Gates recorded, indexed by GATE_* (a MUX counts 1)."""
+        return [int(v) for v in self._by_type]
+
+    def simulate(self, in_bits):
+        """Plaintext run (host only): in_bits [n_inputs] -> [n_outputs], each 0/1."""
+        in_bits = np.ascontiguousarray(in_bits, dtype=np.uint8)
+        assert in_bits.shape == (self._info.n_inputs,), in_bits.shape
+        out = np.zeros(self._info.n_outputs, dtype=np.uint8)
+        check(lib().ieache_netlist_simulate(self.h, in_bits.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                            out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
 
 
 class Context:
@@ -339,6 +453,25 @@ class Context:
         """Device pointers (ints); rows of lwe_stride int32."""
         check(lib().ieache_eval_batch_device(self.h, kind, bits, batch, C.c_void_p(d_in), C.c_void_p(d_out),
                                              C.byref(stats) if stats is not None else None))
+
+    def eval_netlist(self, nl, in_lwe, stats=None):
+        """A CompiledNetlist over a batch: in_lwe [batch][n_inputs][n+1] int32 on the host -> [batch][n_outputs][n+1]."""
+        info = nl.info()
+        in_lwe = np.ascontiguousarray(in_lwe, dtype=np.int32)
+        batch = in_lwe.shape[0]
+        assert in_lwe.shape == (batch, info.n_inputs, self.params.n + 1), in_lwe.shape
+        out = np.zeros((batch, info.n_outputs, self.params.n + 1), dtype=np.int32)
+        check(lib().ieache_eval_netlist(self.h, nl.h, batch, _i32(in_lwe), _i32(out), C.byref(stats) if stats is not None else None))
+        return out
+
+    def prepare_netlist(self, nl, batch):
+        """Allocates what eval_netlist* of this netlist and batch needs, so that the evaluation itself allocates nothing."""
+        check(lib().ieache_prepare_netlist(self.h, nl.h, batch))
+
+    def eval_netlist_device(self, nl, batch, d_in, d_out, stats=None):
+        """Device pointers (ints); rows of lwe_stride int32."""
+        check(lib().ieache_eval_netlist_device(self.h, nl.h, batch, C.c_void_p(d_in), C.c_void_p(d_out),
+                                               C.byref(stats) if stats is not None else None))
 
     def gates(self, gate_type, a, b, stats=None):
         a = np.ascontiguousarray(a, dtype=np.int32)

@@ -95,6 +95,16 @@ typedef struct ieache_stats {
 /* three-input gate, own entry points (ieache_mux*): bootsMUX(a,b,c) = a ? b : c.
  * Not called by Cloud/cloud.c; BASELINE.json's north_star names it. */
 #define IEACHE_GATE_MUX 4
+/* the other two-input gates of libtfhe's boot-gates.cpp, with its linear combinations word for word:
+ * bootsNOR (0,-1/8)-ca-cb, bootsXNOR (0,-1/4)-2(ca+cb), bootsANDNY (0,-1/8)-ca+cb, bootsANDYN (0,-1/8)+ca-cb,
+ * bootsORNY (0,1/8)-ca+cb, bootsORYN (0,1/8)+ca-cb.  Accepted by ieache_gates* and as netlist gates (section 3b). */
+#define IEACHE_GATE_NOR 5
+#define IEACHE_GATE_XNOR 6
+#define IEACHE_GATE_ANDNY 7
+#define IEACHE_GATE_ANDYN 8
+#define IEACHE_GATE_ORNY 9
+#define IEACHE_GATE_ORYN 10
+#define IEACHE_GATE_TYPES 11
 
 typedef struct ieache_circuit_info {
     int32_t n_inputs;    /* samples per expression: A bits, B bits, 32-sample carry word [, C bits] */
@@ -236,7 +246,8 @@ int ieache_eval_batch_device(ieache_ctx* ctx, int kind, int bits, size_t batch, 
  * cloud.c:651-700). */
 int ieache_prepare_batch(ieache_ctx* ctx, int kind, int bits, size_t batch);
 /* `count` independent gates: out[i] = gate(a[i], b[i]); replaces bootsAND /
- * bootsXOR / bootsOR / bootsNAND (cloud.c:30-43,159).  Device rows. */
+ * bootsXOR / bootsOR / bootsNAND (cloud.c:30-43,159) and, with gate types 5 .. 10, bootsNOR / bootsXNOR /
+ * bootsANDNY / bootsANDYN / bootsORNY / bootsORYN.  Device rows. */
 int ieache_gates_device(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* d_a, const int32_t* d_b,
                         int32_t* d_out, ieache_stats* stats);
 /* host rows of n+1 */
@@ -249,6 +260,52 @@ int ieache_mux_device(ieache_ctx* ctx, size_t count, const int32_t* d_a, const i
                       int32_t* d_out, ieache_stats* stats);
 int ieache_mux(ieache_ctx* ctx, size_t count, const int32_t* a, const int32_t* b, const int32_t* c, int32_t* out,
                ieache_stats* stats);
+
+/* ------------------------------------------------------------------ *
+ * 3b. Your own circuit: a netlist of gates, evaluated like the        *
+ *     built-in kinds -- levelised, slot-allocated, a whole level x    *
+ *     batch per launch, on two streams.  Replaces a program that      *
+ *     calls libtfhe's bootsAND / bootsXNOR / bootsMUX ... gate by     *
+ *     gate, as Cloud/cloud.c:30-43 calls bootsAND / bootsXOR.         *
+ * ------------------------------------------------------------------ */
+/* Reference to a sample inside a netlist: wire w (inputs are wires 0 .. n_inputs-1, gate g's output is wire
+ * n_inputs + g), optionally negated (bootsNOT: free), or a constant (bootsCONSTANT: free). */
+#define IEACHE_NET_WIRE(w) ((int32_t)(w) << 1)
+#define IEACHE_NET_NOT(ref) ((ref) ^ 1)
+#define IEACHE_NET_FALSE (-2)
+#define IEACHE_NET_TRUE (-1)
+/* one gate: type is an IEACHE_GATE_* value; c is read for IEACHE_GATE_MUX only (a ? b : c) and must be 0 otherwise */
+typedef struct ieache_net_gate {
+    int32_t type, a, b, c;
+} ieache_net_gate;
+#define IEACHE_NETLIST_BALANCED 1 /* slack-balanced schedule at the mean level width instead of ASAP levels */
+typedef struct ieache_netlist ieache_netlist;
+/* Validates and compiles a gate list (the place of the C source that calls libtfhe's bootsXXX one after the other).  A host
+ * object: it belongs to no context and holds no device memory; several contexts may evaluate it, and it must outlive
+ * every call that uses it.  A gate may only refer to inputs and to gates before it.  Every recorded gate is bootstrapped:
+ * the context options "fold_constants" and "level_quantum" do not apply to netlists (fold what you want folded before
+ * recording).  -> NULL with ieache_last_error() naming the offending gate: an operand or output that refers to a wire not
+ * defined at that point, an unknown type, a third operand on a two-input gate, no inputs / no outputs, more than 2^30 wires. */
+ieache_netlist* ieache_netlist_create(int32_t n_inputs, const ieache_net_gate* gates, size_t n_gates, const int32_t* outputs,
+                                      size_t n_outputs, int flags);
+void ieache_netlist_destroy(ieache_netlist* nl);
+/* statistics of the compiled netlist, as ieache_circuit_info_get gives for a built-in kind.  bootstraps and the widths count
+ * BLIND ROTATIONS -- a MUX gate is two, as in libtfhe's bootsMUX -- so that an evaluation reports batch x bootstraps;
+ * n_and / n_xor count the AND / XOR gates the executor runs (NOR, ANDNY, ANDYN run as AND with negated operands).
+ * gates_by_type (may be NULL): gates recorded, by the IEACHE_GATE_* type they were given as (a MUX counts 1 here). */
+int ieache_netlist_info(const ieache_netlist* nl, ieache_circuit_info* out, int64_t gates_by_type[IEACHE_GATE_TYPES]);
+/* plaintext simulation (host only, no GPU): in_bits [n_inputs] -> out_bits [n_outputs], each 0/1 */
+int ieache_netlist_simulate(const ieache_netlist* nl, const uint8_t* in_bits, uint8_t* out_bits);
+/* the netlist counterparts of ieache_prepare_batch / ieache_eval_batch / ieache_eval_batch_device: same buffer shapes
+ * (in [batch][n_inputs] rows, out [batch][n_outputs] rows; host rows of n+1, device rows of ieache_lwe_stride()), same
+ * stream ordering, device-pointer checks and error conventions.  Replaces the gate-by-gate bootsXNOR / bootsMUX / ...
+ * program of the netlist run once per expression. */
+int ieache_prepare_netlist(ieache_ctx* ctx, const ieache_netlist* nl, size_t batch);
+int ieache_eval_netlist(ieache_ctx* ctx, const ieache_netlist* nl, size_t batch, const int32_t* in_lwe, int32_t* out_lwe,
+                        ieache_stats* stats);
+int ieache_eval_netlist_device(ieache_ctx* ctx, const ieache_netlist* nl, size_t batch, const int32_t* d_in, int32_t* d_out,
+                               ieache_stats* stats);
+
 /* plaintext simulation of the levelised circuit (host only, no GPU): bits in/out 0/1 */
 int ieache_circuit_simulate(int kind, int bits, const uint8_t* in_bits, uint8_t* out_bits);
 int ieache_circuit_simulate_ex(int kind, int bits, int fold_constants, const uint8_t* in_bits, uint8_t* out_bits);

@@ -1,0 +1,344 @@
+"""Caller-defined netlists on the GPU, through the C ABI: every gate type of libtfhe's boot-gates.cpp as a circuit gate, MUX-bearing
+levels under every way the executor cuts a level, and the worked examples of ieache_amd.netlists -- bit-exact against the CPU oracle
+walked gate by gate."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+TWO_INPUT = {0: "and", 1: "xor", 2: "or", 3: "nand"}
+# libtfhe boot-gates.cpp: (constant term, multiplier of ca, multiplier of cb) of the gates the oracle has no entry point for
+LINEAR = {5: (-1 << 29, -1, -1), 6: (-2 << 29, -2, -2), 7: (-1 << 29, -1, 1), 8: (-1 << 29, 1, -1), 9: (1 << 29, -1, 1), 10: (1 << 29, 1, -1)}
+
+
+def _neg(row):
+    return (0 - row.view(np.uint32)).view(np.int32)
+
+
+def oracle_gate(ck, t, a, b, c=None):
+    if t in TWO_INPUT:
+        return ck.gate(TWO_INPUT[t], a, b)
+    if t == 4:
+        return ck.mux(a, b, c)
+    cst, ka, kb = LINEAR[t]
+    x = (np.uint32(ka & 0xFFFFFFFF) * a.view(np.uint32) + np.uint32(kb & 0xFFFFFFFF) * b.view(np.uint32)).astype(np.uint32)
+    x[-1:] += np.uint32(cst & 0xFFFFFFFF)
+    return ck.bootstrap(x.view(np.int32))
+
+
+def oracle_netlist(kb, cn, rows):
+    """The compiled netlist `cn` on one expression's input rows, one libtfhe gate after the other."""
+    ck = kb.ck
+    wires = [np.ascontiguousarray(r) for r in rows]
+
+    def ref(r):
+        if r < 0:
+            return ck.constant(1 if r == -1 else 0)
+        return _neg(wires[r >> 1]) if r & 1 else wires[r >> 1]
+
+    for t, a, b, c in cn.gates:
+        wires.append(oracle_gate(ck, t, ref(a), ref(b), ref(c) if t == 4 else None))
+    return np.stack([ref(o) for o in cn.outputs])
+
+
+def all_types_netlist(ia):
+    """One level holding every gate type with plain, negated and constant operands in every position."""
+    nl = ia.Netlist(3)
+    a, b, c = nl.input(0), nl.input(1), nl.input(2)
+    N, T, F = ia.NOT, ia.TRUE, ia.FALSE
+    outs, plain = [], {}
+    for t in (0, 1, 2, 3, 5, 6, 7, 8, 9, 10):
+        plain[t] = len(outs)
+        for x, y in ((a, b), (N(a), b), (a, N(b)), (N(c), N(b)), (T, b), (a, F), (F, T)):
+            outs.append(nl.gate(t, x, y))
+    for x, y, z in ((a, b, c), (N(a), b, c), (a, N(b), N(c)), (T, b, c), (F, b, N(c)), (a, F, c), (a, b, T), (c, a, a)):
+        outs.append(nl.MUX(x, y, z))
+    return nl.compile(outs), plain
+
+
+def plain_gate(t, a, b):
+    return {0: a & b, 1: a ^ b, 2: a | b, 3: 1 - (a & b), 5: 1 - (a | b), 6: 1 - (a ^ b), 7: (1 - a) & b, 8: a & (1 - b), 9: (1 - a) | b,
+            10: a | (1 - b)}[t]
+
+
+def abc_inputs(kb, seed):
+    bits = np.array([[(v >> i) & 1 for i in range(3)] for v in range(8)], dtype=np.uint8)
+    return bits, kb.enc(bits, seed)
+
+
+@pytest.mark.parametrize("n,N,checked", [(5, 64, 8), (16, 1024, 2)])
+def test_every_gate_type_in_one_level(ia, gpu_ctx, n, N, checked):
+    kb, ctx = gpu_ctx(n, N)
+    cn, plain = all_types_netlist(ia)
+    info = cn.info()
+    assert info.depth == 1 and info.bootstraps == 70 + 16 and info.max_width == 86
+    bits, inp = abc_inputs(kb, 301)
+    st = ia.Stats()
+    out = ctx.eval_netlist(cn, inp, st)
+    assert st.bootstraps == 8 * info.bootstraps and st.levels == 1
+    assert np.array_equal(kb.dec(out), np.stack([cn.simulate(b) for b in bits]))
+    for e in range(checked):
+        assert np.array_equal(oracle_netlist(kb, cn, inp[e]), out[e]), e
+    # the flat call with the new two-input types gives the rows the circuit gives
+    for t in (5, 6, 7, 8, 9, 10):
+        flat = ctx.gates(t, inp[:, 0], inp[:, 1])
+        assert np.array_equal(flat, out[:, plain[t]]), t
+        assert np.array_equal(kb.dec(flat), plain_gate(t, bits[:, 0], bits[:, 1]))
+    # a chunk that ends inside a MUX gate, and one rotation item at a time
+    try:
+        for chunk in (7, 1):
+            ctx.set_chunk(chunk)
+            assert np.array_equal(ctx.eval_netlist(cn, inp), out), chunk
+    finally:
+        ctx.set_chunk(65536)
+
+
+def test_a_handful_of_gates_at_product_parameters(ia, gpu_ctx):
+    kb, ctx = gpu_ctx(630, 1024)
+    nl = ia.Netlist(3)
+    a, b, c = nl.input(0), nl.input(1), nl.input(2)
+    x = nl.XNOR(a, ia.NOT(b))
+    m = nl.MUX(x, b, ia.NOT(c))
+    cn = nl.compile([x, m, nl.ORYN(m, a), nl.NOR(ia.TRUE, m)])
+    bits, inp = abc_inputs(kb, 302)
+    out = ctx.eval_netlist(cn, inp)
+    assert np.array_equal(kb.dec(out), np.stack([cn.simulate(v) for v in bits]))
+    assert np.array_equal(oracle_netlist(kb, cn, inp[5]), out[5])
+
+
+def operands(ia, kb, bits, pairs, seed):
+    from ieache_amd import tools
+    inb = np.zeros((len(pairs), 2 * bits), dtype=np.uint8)
+    for e, (a, b) in enumerate(pairs):
+        inb[e, :bits], inb[e, bits:] = tools.int_to_bits(a, bits), tools.int_to_bits(b, bits)
+    return kb.enc(inb, seed)
+
+
+def values(dec, bits):
+    from ieache_amd import tools
+    return [tuple(tools.bits_to_int(row[i:i + bits]) for i in range(0, len(row), bits)) for row in dec]
+
+
+def test_minmax_same_bits_however_the_levels_are_cut(ia, gpu_ctx):
+    from ieache_amd import netlists
+    kb, ctx = gpu_ctx(16, 1024)
+    cn = netlists.minmax(8)
+    rng = np.random.default_rng(5)
+    pairs = [(int(a), int(b)) for a, b in rng.integers(0, 256, size=(64, 2))]
+    pairs[:3] = [(7, 7), (0, 255), (255, 0)]
+    inp = operands(ia, kb, 8, pairs, 303)
+    st = ia.Stats()
+    ref = ctx.eval_netlist(cn, inp, st)
+    assert st.bootstraps == 64 * cn.info().bootstraps == 64 * 56
+    assert values(kb.dec(ref), 8) == [(min(a, b), max(a, b)) for a, b in pairs]
+    for e in (0, 17):
+        assert np.array_equal(oracle_netlist(kb, cn, inp[e]), ref[e]), e
+    saved = {k: ctx.get_option(k) for k in ("chunk", "overlap", "overlap_min", "pipe_min", "pipe_auto", "br_mix", "exact_fft")}
+    try:
+        ctx.set_chunk(7)
+        assert np.array_equal(ctx.eval_netlist(cn, inp), ref)
+        ctx.set_chunk(saved["chunk"])
+        ctx.set_option("overlap", 0)
+        assert np.array_equal(ctx.eval_netlist(cn, inp), ref)
+        ctx.set_option("overlap", 1)
+        # level halves on two lanes: 64 x 32 rotation items in the last level, halves that end where a MUX ends
+        ctx.set_option("overlap_min", 100)
+        lv = ctx.get_option("overlapped_levels")
+        assert np.array_equal(ctx.eval_netlist(cn, inp), ref) and ctx.get_option("overlapped_levels") > lv
+        ctx.set_chunk(333)
+        assert np.array_equal(ctx.eval_netlist(cn, inp), ref)
+        ctx.set_chunk(saved["chunk"])
+        ctx.set_option("overlap_min", saved["overlap_min"])
+        # expression-half pipelines, forced on; an odd batch as well
+        ctx.set_option("pipe_auto", 0)
+        ctx.set_option("pipe_min", 1)
+        pe = ctx.get_option("pipelined_evals")
+        assert np.array_equal(ctx.eval_netlist(cn, inp), ref)
+        assert np.array_equal(ctx.eval_netlist(cn, inp[:33]), ref[:33]) and ctx.get_option("pipelined_evals") == pe + 2
+        ctx.set_chunk(7)
+        assert np.array_equal(ctx.eval_netlist(cn, inp[:9]), ref[:9])
+        ctx.set_chunk(saved["chunk"])
+        ctx.set_option("pipe_min", saved["pipe_min"])
+        ctx.set_option("pipe_auto", saved["pipe_auto"])
+        ctx.set_option("exact_fft", 1)
+        assert np.array_equal(ctx.eval_netlist(cn, inp), ref)
+        ctx.set_option("exact_fft", saved["exact_fft"])
+        ctx.force_generic(True)
+        assert np.array_equal(ctx.eval_netlist(cn, inp[:4]), ref[:4])
+        ctx.force_generic(False)
+    finally:
+        ctx.set_chunk(saved["chunk"])
+        ctx.force_generic(False)
+        for k in ("overlap", "overlap_min", "pipe_min", "pipe_auto", "br_mix", "exact_fft"):
+            ctx.set_option(k, saved[k])
+
+
+def test_tiny_levels_with_overlap_min_two(ia, gpu_ctx):
+    """A level of two to four items with overlap_min = 2 is one piece: it must not fork to a second stream."""
+    kb, ctx = gpu_ctx(16, 1024)
+    nl = ia.Netlist(3)
+    a, b, c = nl.input(0), nl.input(1), nl.input(2)
+    cn = nl.compile([nl.AND(a, b), nl.MUX(a, b, c)])  # one level of three rotation items
+    bits, inp = abc_inputs(kb, 304)
+    ref = ctx.eval_netlist(cn, inp[:1])
+    flat = ctx.gates(ia.GATE_XNOR, inp[:3, 0], inp[:3, 1])
+    saved = ctx.get_option("overlap_min")
+    try:
+        ctx.set_option("overlap_min", 2)
+        with ia.Context.from_arrays(kb.p, kb.bk, kb.ksk) as fresh:  # no second stream created yet
+            fresh.set_option("overlap_min", 2)
+            assert np.array_equal(fresh.eval_netlist(cn, inp[:1]), ref)
+            assert np.array_equal(fresh.gates(ia.GATE_XNOR, inp[:3, 0], inp[:3, 1]), flat)
+            assert fresh.get_option("overlapped_levels") == 0
+        assert np.array_equal(ctx.eval_netlist(cn, inp[:1]), ref)
+        assert np.array_equal(ctx.eval_netlist(cn, inp), np.concatenate([ctx.eval_netlist(cn, inp[e:e + 1]) for e in range(8)]))
+    finally:
+        ctx.set_option("overlap_min", saved)
+    assert np.array_equal(kb.dec(ref)[0], cn.simulate(bits[0]))
+
+
+def add_transcription(ia, bits):
+    """Cloud/cloud.c's add(), gate by gate, on the input layout of IEACHE_CIRC_ADD: A, B, then the 32-sample carry word."""
+    nl = ia.Netlist(2 * bits + 32)
+    carry, sums = nl.input(2 * bits), []
+    for i in range(bits):
+        x, y = nl.input(i), nl.input(bits + i)
+        axc = nl.XOR(x, carry)
+        bxc = nl.XOR(y, carry)
+        sums.append(nl.XOR(x, bxc))
+        axc = nl.AND(axc, bxc)
+        carry = nl.XOR(carry, axc)
+    return nl.compile(sums)
+
+
+def test_add_as_a_netlist_is_the_built_in_ciphertext(ia, gpu_ctx):
+    kb, ctx = gpu_ctx(16, 1024)
+    cn = add_transcription(ia, 16)
+    rng = np.random.default_rng(6)
+    inb = np.zeros((32, 64), dtype=np.uint8)
+    inb[:, :32] = rng.integers(0, 2, size=(32, 32))
+    inp = kb.enc(inb, 305)
+    assert np.array_equal(ctx.eval_netlist(cn, inp), ctx.eval_batch(ia.CIRC_ADD, 16, inp))
+
+
+def test_worked_examples_at_product_parameters(ia, gpu_ctx):
+    from ieache_amd import netlists
+    kb, ctx = gpu_ctx(630, 1024)
+    rng = np.random.default_rng(7)
+    # compare(32) x 256
+    cn = netlists.compare(32)
+    pairs = [(int(a), int(b)) for a, b in rng.integers(0, 1 << 32, size=(256, 2))]
+    pairs[:4] = [(5, 5), (0, 1), (1 << 31, (1 << 31) - 1), (0xFFFFFFFF, 0xFFFFFFFF)]
+    inp = operands(ia, kb, 32, pairs, 306)
+    out = ctx.eval_netlist(cn, inp)
+    assert [tuple(r) for r in kb.dec(out)] == [(int(a < b), int(a == b)) for a, b in pairs]
+    # word for word against the oracle at these parameters: the same chain four bits long (a libtfhe bootstrap takes the CPU
+    # half a second here)
+    cn4 = netlists.compare(4)
+    inp4 = operands(ia, kb, 4, [(9, 11), (6, 6)], 312)
+    out4 = ctx.eval_netlist(cn4, inp4)
+    assert np.array_equal(oracle_netlist(kb, cn4, inp4[0]), out4[0]) and [tuple(r) for r in kb.dec(out4)] == [(1, 0), (0, 1)]
+    # rotation of roles (it needs a full-length rotation, hence these parameters): a batch whose last level -- 32 rotation items
+    # per expression, all of them MUX halves -- lies in the 4 .. 7 gates-per-CU band gives the bits the single kernel gives
+    cn8 = netlists.minmax(8)
+    mid = max(2, 5 * ctx.get_option("cus") // 32)
+    pairs = [(int(a), int(b)) for a, b in rng.integers(0, 256, size=(mid, 2))]
+    inp8 = operands(ia, kb, 8, pairs, 313)
+    saved = ctx.get_option("br_mix")
+    try:
+        ctx.set_option("br_mix", 1)
+        ml = ctx.get_option("mixed_launches")
+        mixed = ctx.eval_netlist(cn8, inp8)
+        if "w2r+w1b" in ctx.kernel_for_launch(32 * mid):
+            assert ctx.get_option("mixed_launches") > ml
+        ctx.set_option("br_mix", 0)
+        assert np.array_equal(ctx.eval_netlist(cn8, inp8), mixed)
+    finally:
+        ctx.set_option("br_mix", saved)
+    assert values(kb.dec(mixed), 8) == [(min(a, b), max(a, b)) for a, b in pairs]
+    # divmod(8) x 64, B = 0 included: all-ones quotient, remainder A
+    cn = netlists.divmod(8)
+    pairs = [(int(a), int(b)) for a, b in rng.integers(0, 256, size=(64, 2))]
+    pairs[:4] = [(200, 0), (0, 0), (255, 1), (17, 200)]
+    st = ia.Stats()
+    out = ctx.eval_netlist(cn, operands(ia, kb, 8, pairs, 307), st)
+    assert values(kb.dec(out), 8) == [divmod(a, b) if b else (255, a) for a, b in pairs]
+    assert st.bootstraps == 64 * cn.info().bootstraps
+    # minmax(32) x 1024: about 230 k blind rotations
+    cn = netlists.minmax(32)
+    pairs = [(int(a), int(b)) for a, b in rng.integers(0, 1 << 32, size=(1024, 2))]
+    out = ctx.eval_netlist(cn, operands(ia, kb, 32, pairs, 308), st)
+    assert values(kb.dec(out), 32) == [(min(a, b), max(a, b)) for a, b in pairs]
+    assert st.bootstraps == 1024 * cn.info().bootstraps == 1024 * 224
+
+
+def test_prepared_evaluation_allocates_nothing(ia, gpu_ctx):
+    import torch
+    from ieache_amd import netlists
+    kb, ctx = gpu_ctx(16, 1024)
+    cn = netlists.minmax(8)
+    pairs = [(3 * e % 256, 7 * e % 256) for e in range(48)]
+    inp = operands(ia, kb, 8, pairs, 309)
+    stride, S = ctx.lwe_stride, kb.p.n + 1
+    rows = np.zeros((48, 16, stride), dtype=np.int32)
+    rows[:, :, :S] = inp
+    d_in = torch.from_numpy(rows).cuda()
+    d_out = torch.zeros((48, 16, stride), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    auto = ctx.get_option("pipe_auto")
+    try:
+        ctx.set_option("pipe_auto", 0)  # (the first evaluations of a mid-size batch otherwise alternate between the two stream modes)
+        ctx.prepare_netlist(cn, 48)
+        n0 = ctx.get_option("staging_allocations")
+        s1, s2 = ia.Stats(), ia.Stats()
+        ctx.eval_netlist_device(cn, 48, d_in.data_ptr(), d_out.data_ptr(), s1)
+        first = d_out.cpu().numpy().copy()
+        ctx.eval_netlist_device(cn, 48, d_in.data_ptr(), d_out.data_ptr(), s2)
+        assert ctx.get_option("staging_allocations") == n0
+    finally:
+        ctx.set_option("pipe_auto", auto)
+    assert np.array_equal(d_out.cpu().numpy(), first) and np.array_equal(first[:, :, :S], ctx.eval_netlist(cn, inp))
+    for f in ("blind_rotate_launches", "keyswitch_launches", "bootstraps", "levels", "chunks"):
+        assert getattr(s1, f) == getattr(s2, f) > 0, f
+    with pytest.raises(ia.IeacheError, match="not a device pointer"):
+        ctx.eval_netlist_device(cn, 48, rows.ctypes.data, d_out.data_ptr())
+
+
+def test_guard_and_audit_on_a_mux_netlist(ia, gpu_ctx):
+    from ieache_amd import netlists
+    kb, ctx = gpu_ctx(16, 1024)
+    cn = netlists.minmax(8)
+    cus = ctx.get_option("cus")
+    batch = cus // 8 + 8  # last level: 32 x batch rotation items, more than one per CU, so that it takes a one-limb kernel
+    pairs = [(11 * e % 256, 5 * e % 256) for e in range(batch)]
+    inp = operands(ia, kb, 8, pairs, 310)
+    ref = ctx.eval_netlist(cn, inp)
+    saved = ctx.get_option("fft_audit")
+    try:
+        _, reruns = ctx.fft_guard()
+        ctx.set_option("fft_guard_inject", 1)
+        assert np.array_equal(ctx.eval_netlist(cn, inp), ref) and ctx.fft_guard()[1] == reruns + 1
+        ctx.set_option("fft_audit", 1)
+        before = ctx.fft_audit()
+        assert np.array_equal(ctx.eval_netlist(cn, inp), ref)
+        after = ctx.fft_audit()
+        assert after["audits"] > before["audits"] and after["mismatches"] == before["mismatches"]  # (other tests inject some)
+    finally:
+        ctx.set_option("fft_audit", saved)
+
+
+def test_empty_batch_and_outputs_that_are_not_gates(ia, gpu_ctx):
+    kb, ctx = gpu_ctx(16, 1024)
+    nl = ia.Netlist(3)
+    a, b, c = nl.input(0), nl.input(1), nl.input(2)
+    m = nl.MUX(a, b, c)
+    cn = nl.compile([b, ia.NOT(m), ia.TRUE, ia.FALSE, ia.NOT(c), m])
+    bits, inp = abc_inputs(kb, 311)
+    out = ctx.eval_netlist(cn, inp)
+    assert np.array_equal(kb.dec(out), np.stack([cn.simulate(v) for v in bits]))
+    assert np.array_equal(out[:, 0], inp[:, 1]) and np.array_equal(out[:, 1], _neg(out[:, 5])) and np.array_equal(out[:, 4], _neg(inp[:, 2]))
+    for e in range(8):
+        assert np.array_equal(out[e, 5], kb.ck.mux(inp[e, 0], inp[e, 1], inp[e, 2]))
+        assert np.array_equal(out[e, 2], kb.ck.constant(1)) and np.array_equal(out[e, 3], kb.ck.constant(0))
+    st = ia.Stats()
+    assert ctx.eval_netlist(cn, inp[:0], st).shape == (0, 6, kb.p.n + 1) and st.bootstraps == 0
