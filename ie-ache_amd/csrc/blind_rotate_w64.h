@@ -23,8 +23,8 @@ size_t state_bytes_per_item(const Params& p);
 // IEACHE_BR_SLICE; the evaluator passes 64 / the whole rotation for launches whose gates are all resident at once).
 // state: items * state_bytes_per_item() bytes of scratch.
 // ext rows of N+4 int32 (may be null), dbg_acc [items][2][N] (may be null; when set, pass ext = null).
-// Returns the number of k_blind_rotate_w2 launches issued.
-// d_bkf1 / guard: the one-limb spectrum and the two-word guard record of k_blind_rotate_w1 (may be null for the
+// Returns the number of blind-rotation kernel launches issued (the prologue not counted).
+// d_bkf1 / guard: the one-limb spectrum and the two-word guard record of the one-limb kernels (may be null for the
 // two-limb variants).
 // Rotation of roles for mid-size launches (blind_rotate_w64.hip: launch_mixed_phases): k <= 4 subsets of the items on k streams
 // (streams[0] = the launch's own), tw of them at a time on the two-waves-per-gate kernel for s2 steps while the others take s1
@@ -45,7 +45,7 @@ int launch(const Params& p, const dev::DevKeys& K, const double2* d_bkf, const d
 // wg_gates: gate instances per workgroup of the two one-wave-per-gate kernels (k_blind_rotate_w1b, guard on one coefficient
 // in four, and k_blind_rotate_x1): 1 .. 4, 0 = 4.  Four gates share a workgroup only for the twiddle table; fewer per
 // workgroup let a launch that does not fill the chip spread evenly over the CUs (LDS: 4 -> 2 workgroups per CU, 3 -> 2, 2 -> 3, 1 -> 6).
-// one-limb form (k_blind_rotate_w1): raw BK -> spectrum [n][2l][2][8][64] double2
+// one-limb form (k_blind_rotate_w1b and the other guarded kernels): raw BK -> spectrum [n][2l][2][8][64] double2
 size_t spectrum1_elems(const Params& p);
 void prepare_spectrum1(const Params& p, const Torus32* d_bk_raw, double2* d_bkf1, hipStream_t stream);
 size_t lds_bytes_w1(int wg_gates = 4);
@@ -53,7 +53,8 @@ int gates_per_workgroup_w1();
 // the kernels' twiddle table (twiddle_table_elems() double2 in device memory), built once per context
 size_t twiddle_table_elems();
 void build_twiddle_table(double2* d_tw, hipStream_t stream);
-// Kernel variants ("br_variant" / IEACHE_BR_VARIANT; all produce identical bits).  0 lets the EVALUATOR choose by launch size
+// Kernel variants ("br_variant" / IEACHE_BR_VARIANT; all produce identical bits; kVariants in blind_rotate_w64.hip is the table
+// everything is derived from, one row per number below).  0 lets the EVALUATOR choose by launch size
 // (evaluator.hip: <= one gate per CU -> 38, <= 2 per CU -> 43, <= 5 per CU -> 36, above -> 31; "exact_fft": 7 / 0 / 9);
 // passed to launch() itself, 0 is the two-limb two-wave kernel.
 //   two limbs (exact by construction):
@@ -71,6 +72,9 @@ void build_twiddle_table(double2* d_tw, hipStream_t stream);
 int32_t default_variant();
 bool variant_known(int32_t v);
 bool variant_one_limb(int32_t v);  // takes the one-limb spectrum and the guard record (the sampled audit applies)
+// the kernel's name for the numbers the evaluator's own choice uses (0, 7, 9, 31, 36, 38, 43); null for the measurement and
+// diagnostic builds, which are reported by number, and for unknown numbers
+const char* variant_kernel_name(int32_t v);
 constexpr int32_t kVariantWide = 7;
 constexpr int32_t kVariantExactOneWave = 9;         // k_blind_rotate_x1 (round 4): two limbs, one wave per gate
 constexpr int32_t kVariantTwoWavesLds = 12;

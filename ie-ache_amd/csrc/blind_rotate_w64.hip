@@ -23,6 +23,8 @@
 //   k_blind_rotate_x1     one wave per gate            more than 4 gates per CU (round 4)
 //   k_blind_rotate_w2     two waves per gate           1 .. 4 gates per CU
 //   k_blind_rotate_wide   2L waves per gate            at most one gate per CU
+// The pieces of a CMux step the kernels share (guard publication, digit conversion, row product, epilogue, ...) are in
+// br_step.h, with the list of what each kernel still writes out itself and why.
 // Kernels and template flags that lost their A/B: attic/ (not built by default).
 #include "blind_rotate_w64.h"
 
@@ -33,7 +35,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "fft512.h"
+#include "br_step.h"
 #include "mix_plan.h"
 
 namespace ieache {
@@ -156,23 +158,15 @@ __global__ __launch_bounds__(128, 2) void k_blind_rotate_w2(DevKeys K, const dou
     int32_t* gacc = st_acc + (size_t)item * 2 * kN;
     load_twiddles(sTw, gtw, tid, 128);
     const LaneRoots R = make_roots(sTw, lane);
-    {
-        const int4* src = reinterpret_cast<const int4*>(gacc);
-        int4* dst = reinterpret_cast<int4*>(acc);
-#pragma unroll
-        for (int r = 0; r < 4; r++) dst[128 * r + tid] = src[128 * r + tid];
-    }
+    copy_acc<128>(acc, gacc, tid);
     __syncthreads();
 
-    constexpr uint32_t halfBg = 1u << (BGBIT - 1);
-    uint32_t dec_offset = 0;
-#pragma unroll
-    for (int q = 1; q <= L; q++) dec_offset += halfBg << (32 - q * BGBIT);
+    uint32_t dec_offset = decomposition_offset<L, BGBIT>();
     int32_t* accw = acc + wave * kN;  // the polynomial this wave decomposes and updates
 
     // this slice's rotation amounts: one per lane, fetched once, then read with readlane
     // (a dependent global load at the head of every step costs ~2-3k cycles)
-    const int32_t my_a = (i0 + lane < i1) ? (int32_t)bara[i0 + lane] : 0;
+    const int32_t my_a = lane_amounts(bara, i0, i1, lane);
 #pragma unroll 1
     for (int32_t i = i0; i < i1; i++) {
         const int32_t a = __builtin_amdgcn_readlane(my_a, i - i0);
@@ -196,12 +190,7 @@ __global__ __launch_bounds__(128, 2) void k_blind_rotate_w2(DevKeys K, const dou
             const double2* __restrict__ bown = bki + (size_t)(wave * L + q) * (4 * kM);
             const double2* __restrict__ bpar = bki + (size_t)((wave ^ 1) * L + q) * (4 * kM);
             double2 x[8];
-#pragma unroll
-            for (int r = 0; r < 8; r++) {
-                const int32_t e0 = __builtin_amdgcn_sbfe((int32_t)v0[r], sh, BGBIT);  // v_bfe_i32
-                const int32_t e1 = __builtin_amdgcn_sbfe((int32_t)v1[r], sh, BGBIT);
-                x[r] = make_double2((double)e0, (double)e1);  // untwisted: the first radix-8 pass applies e^{i pi r/16} itself
-            }
+            digits_to_double2<BGBIT>(x, v0, v1, sh);
             // BK loads are issued well ahead of their use (each is an L2 round trip of ~700 cycles):
             //   bA = own row, limb 0      before the transform
             //   bB = own row, limb 1      } right after it, consumed behind bA's MACs
@@ -220,32 +209,18 @@ __global__ __launch_bounds__(128, 2) void k_blind_rotate_w2(DevKeys K, const dou
 #pragma unroll
             for (int k = 0; k < 8; k++) bC[k] = bpar[k * 64];
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int k = 0; k < 8; k++)
-                s[0][k] = FIRST ? cmulx<false>(x[k], bA[k])
-                                : make_double2(fma(x[k].x, bA[k].x, fma(-x[k].y, bA[k].y, s[0][k].x)),
-                                               fma(x[k].x, bA[k].y, fma(x[k].y, bA[k].x, s[0][k].y)));
+            mac_row<FIRST>(s[0], x, bA);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int k = 0; k < 8; k++) bA[k] = bpar[(8 + k) * 64];  // bD
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int k = 0; k < 8; k++)
-                s[1][k] = FIRST ? cmulx<false>(x[k], bB[k])
-                                : make_double2(fma(x[k].x, bB[k].x, fma(-x[k].y, bB[k].y, s[1][k].x)),
-                                               fma(x[k].x, bB[k].y, fma(x[k].y, bB[k].x, s[1][k].y)));
+            mac_row<FIRST>(s[1], x, bB);
             __syncthreads();
             // partner's row
 #pragma unroll
             for (int k = 0; k < 8; k++) x[k] = sTp[k * 64 + lane];
-#pragma unroll
-            for (int k = 0; k < 8; k++)
-                s[0][k] = make_double2(fma(x[k].x, bC[k].x, fma(-x[k].y, bC[k].y, s[0][k].x)),
-                                       fma(x[k].x, bC[k].y, fma(x[k].y, bC[k].x, s[0][k].y)));
-#pragma unroll
-            for (int k = 0; k < 8; k++)
-                s[1][k] = make_double2(fma(x[k].x, bA[k].x, fma(-x[k].y, bA[k].y, s[1][k].x)),
-                                       fma(x[k].x, bA[k].y, fma(x[k].y, bA[k].x, s[1][k].y)));
+            mac_row<false>(s[0], x, bC);
+            mac_row<false>(s[1], x, bA);
             __syncthreads();  // partner has read our tile before the next transform reuses it
         };
         digit_row(0, std::true_type{});
@@ -266,22 +241,10 @@ __global__ __launch_bounds__(128, 2) void k_blind_rotate_w2(DevKeys K, const dou
         // last digit's second barrier: nothing crosses waves here, so no barrier (round 1's cost 0.3-0.4 %)
     }
     __syncthreads();  // the epilogue below reads both polynomials with all threads
-    if (ext) {
-        // K4: sample extract after the last slice
-        Torus32* u = ext + (size_t)item * (kN + 4);
-        for (int32_t j = tid; j <= kN; j += 128)
-            u[j] = j == 0 ? acc[0] : (j == kN ? acc[kN] : (int32_t)(0u - (uint32_t)acc[kN - j]));
-    } else {
-        const int4* src = reinterpret_cast<const int4*>(acc);
-        int4* dst = reinterpret_cast<int4*>(gacc);
-#pragma unroll
-        for (int r = 0; r < 4; r++) dst[128 * r + tid] = src[128 * r + tid];
-    }
+    finish_slice<128>(ext, item, acc, gacc, tid);
 }
 
 
-constexpr int kW1Gates = 4;
-constexpr float kGuardLimit = 0.0625f;
 // ---- K3 (+K4), throughput form (rounds 2-3): ONE wave per gate instance on the ONE-limb spectrum ----
 // The two-limb product (k_blind_rotate_x1 / _w2 / _wide below) is exact by construction (every rounded sum stays below 2^35
 // of the 2^53 an FP64 mantissa holds) and pays for it with a second inverse transform and a second set of row products per
@@ -341,21 +304,14 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_w1b(DevKeys K, const
     for (int q = 1; q <= L; q++) dec_offset += halfBg << (32 - q * BGBIT);
     double dev_max = 0.0;
     constexpr int kRowBytes = 2 * kM * (int)sizeof(double2), kStepBytes = 2 * L * kRowBytes;
-    const __amdgpu_buffer_rsrc_t bk_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<double2*>(bkf1), (short)0, K.n * kStepBytes, 0x00020000);
-    const int lane16 = lane * (int)sizeof(double2);
+    const __amdgpu_buffer_rsrc_t bk_rsrc = bk_resource(bkf1, K.n, kStepBytes);
+    const int lane16 = bk_lane_offset(lane);
     const unsigned char* accb = reinterpret_cast<const unsigned char*>(acc_all);  // LDS offset 0 of the workgroup
     const uint32_t pb0 = (uint32_t)wave * (2 * kN * 4);                            // this gate's polynomial 0; polynomial 1 at + 4096
 
     unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
     if (DIAG) tlast = stamp();
-#define IEACHE_STAMP(idx)                      \
-    if (DIAG) {                                \
-        const unsigned long long t_ = stamp(); \
-        tsum[idx] += t_ - tlast;               \
-        tlast = t_;                            \
-    }
-    const int32_t my_a = (i0 + lane < i1) ? (int32_t)bara[i0 + lane] : 0;
+    const int32_t my_a = lane_amounts(bara, i0, i1, lane);
 #pragma unroll 1
     for (int32_t i = i0; i < i1; i++) {
         const int32_t a = __builtin_amdgcn_readlane(my_a, i - i0);
@@ -367,57 +323,36 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_w1b(DevKeys K, const
         const uint32_t jb4 = ((uint32_t)(lane - a) & (2 * kN - 1)) << 2;
         auto decompose = [&](const uint32_t pb) {
             const int32_t* accp = reinterpret_cast<const int32_t*>(accb + pb);
-#pragma unroll
-            for (int r = 0; r < 8; r++) {
-                const uint32_t t = jb4 + 256u * r;
-                const uint32_t o0 = (t & 4092u) | pb, o1 = o0 ^ 2048u;
-                const int32_t m0 = __builtin_amdgcn_sbfe((int32_t)t, 12, 1), m1 = __builtin_amdgcn_sbfe((int32_t)(t + 2048u), 12, 1);
-                const uint32_t rv0 = *reinterpret_cast<const uint32_t*>(accb + o0), rv1 = *reinterpret_cast<const uint32_t*>(accb + o1);
-                const uint32_t pv0 = (uint32_t)accp[64 * r + lane], pv1 = (uint32_t)accp[64 * r + lane + kM];
-                // +/- rot - acc_j + offset, then ^ offset: digit q's field holds digit ^ halfBg, whose sign-extended value IS the digit
-                v0[r] = ((rv0 ^ (uint32_t)m0) + ((dec_offset - pv0) - (uint32_t)m0)) ^ dec_offset;
-                v1[r] = ((rv1 ^ (uint32_t)m1) + ((dec_offset - pv1) - (uint32_t)m1)) ^ dec_offset;
-            }
+            decompose_rotated(v0, v1, accb, accp, pb, jb4, lane, dec_offset);
         };
         auto digit_row = [&](const int sh, const int brow, auto first) {
             constexpr bool FIRST = decltype(first)::value;
             double2 x[8], bA[8], bB[8];
             load_bk_block(bA, bk_rsrc, lane16, brow);
-#pragma unroll
-            for (int r = 0; r < 8; r++) {
-                const int32_t e0 = __builtin_amdgcn_sbfe((int32_t)v0[r], sh, BGBIT);  // v_bfe_i32
-                const int32_t e1 = __builtin_amdgcn_sbfe((int32_t)v1[r], sh, BGBIT);
-                x[r] = make_double2((double)e0, (double)e1);  // untwisted: the first radix-8 pass applies e^{i pi r/16} itself
-            }
+            digits_to_double2<BGBIT>(x, v0, v1, sh);
             __builtin_amdgcn_sched_barrier(0);
-            IEACHE_STAMP(1)
+            stamp_phase<DIAG>(tsum, tlast, 1);
             fft512_forward<true, 1>(x, sT, lane, R);
-            IEACHE_STAMP(2)
+            stamp_phase<DIAG>(tsum, tlast, 2);
             load_bk_block(bB, bk_rsrc, lane16, brow + kRowBytes / 2);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int k = 0; k < 8; k++)
-                s[0][k] = FIRST ? cmulx<false>(x[k], bA[k])
-                                : make_double2(fma(x[k].x, bA[k].x, fma(-x[k].y, bA[k].y, s[0][k].x)),
-                                               fma(x[k].x, bA[k].y, fma(x[k].y, bA[k].x, s[0][k].y)));
+            for (int k = 0; k < 8; k++) s[0][k] = mac<FIRST>(s[0][k], x[k], bA[k]);
 #pragma unroll
-            for (int k = 0; k < 8; k++)
-                s[1][k] = FIRST ? cmulx<false>(x[k], bB[k])
-                                : make_double2(fma(x[k].x, bB[k].x, fma(-x[k].y, bB[k].y, s[1][k].x)),
-                                               fma(x[k].x, bB[k].y, fma(x[k].y, bB[k].x, s[1][k].y)));
-            IEACHE_STAMP(3)
+            for (int k = 0; k < 8; k++) s[1][k] = mac<FIRST>(s[1][k], x[k], bB[k]);
+            stamp_phase<DIAG>(tsum, tlast, 3);
         };
         decompose(pb0);
-        IEACHE_STAMP(0)
+        stamp_phase<DIAG>(tsum, tlast, 0);
         digit_row(32 - BGBIT, bki, std::true_type{});
 #pragma unroll 1
         for (int row = 1; row < L; row++) digit_row(32 - (row + 1) * BGBIT, bki + row * kRowBytes, std::false_type{});
         decompose(pb0 + 4096u);
-        IEACHE_STAMP(0)
+        stamp_phase<DIAG>(tsum, tlast, 0);
 #pragma unroll 1
         for (int row = L; row < 2 * L; row++) digit_row(32 - (row - L + 1) * BGBIT, bki + row * kRowBytes, std::false_type{});
         fft512_inverse_pair<true>(s[0], s[1], sT, lane, R);
-        IEACHE_STAMP(4)
+        stamp_phase<DIAG>(tsum, tlast, 4);
 #pragma unroll
         for (int c = 0; c < 2; c++) {
             uint32_t* accc = reinterpret_cast<uint32_t*>(acc) + c * kN;
@@ -432,33 +367,14 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_w1b(DevKeys K, const
             }
         }
         wave_sync();
-        IEACHE_STAMP(5)
+        stamp_phase<DIAG>(tsum, tlast, 5);
     }
-#undef IEACHE_STAMP
     if (DIAG && diag && lane == 0) {
 #pragma unroll
         for (int t = 0; t < 8; t++) atomicAdd(&diag[(wave & 1) * 8 + t], tsum[t]);
     }
-    if (GUARD) {
-        float m = (float)dev_max;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        if (lane == 0) {
-            const unsigned bits = __float_as_uint(m);
-            if (bits > __builtin_nontemporal_load(&guard[1])) atomicMax(&guard[1], bits);
-            if (m > kGuardLimit) atomicAdd(&guard[0], 1u);
-        }
-    }
-    if (ext) {
-        Torus32* u = ext + (size_t)item * (kN + 4);
-        for (int32_t j = lane; j <= kN; j += 64)
-            u[j] = j == 0 ? acc[0] : (j == kN ? acc[kN] : (int32_t)(0u - (uint32_t)acc[kN - j]));
-    } else {
-        const int4* src = reinterpret_cast<const int4*>(acc);
-        int4* dst = reinterpret_cast<int4*>(gacc);
-#pragma unroll
-        for (int r = 0; r < 8; r++) dst[64 * r + lane] = src[64 * r + lane];
-    }
+    if (GUARD) publish_guard(dev_max, guard, lane);
+    finish_slice<64>(ext, item, acc, gacc, lane);
 }
 
 // ---- K3 (+K4), throughput form of the PROVABLY EXACT product, round 4: one wave per gate on the TWO-limb spectrum ----
@@ -508,13 +424,12 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_x1(DevKeys K, const 
 #pragma unroll
     for (int q = 1; q <= L; q++) dec_offset += halfBg << (32 - q * BGBIT);
     constexpr int kBlockBytes = kM * (int)sizeof(double2), kRowBytes = 4 * kBlockBytes, kStepBytes = 2 * L * kRowBytes;
-    const __amdgpu_buffer_rsrc_t bk_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<double2*>(bkf), (short)0, K.n * kStepBytes, 0x00020000);
-    const int lane16 = lane * (int)sizeof(double2);
+    const __amdgpu_buffer_rsrc_t bk_rsrc = bk_resource(bkf, K.n, kStepBytes);
+    const int lane16 = bk_lane_offset(lane);
     const unsigned char* accb = reinterpret_cast<const unsigned char*>(acc_all);  // LDS offset 0 of the workgroup
     const uint32_t pb0 = (uint32_t)wave * (2 * kN * 4);                            // this gate's polynomial 0; polynomial 1 at + 4096
 
-    const int32_t my_a = (i0 + lane < i1) ? (int32_t)bara[i0 + lane] : 0;
+    const int32_t my_a = lane_amounts(bara, i0, i1, lane);
 #pragma unroll 1
     for (int32_t i = i0; i < i1; i++) {
         const int32_t a = __builtin_amdgcn_readlane(my_a, i - i0);
@@ -526,33 +441,12 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_x1(DevKeys K, const 
         const uint32_t jb4 = ((uint32_t)(lane - a) & (2 * kN - 1)) << 2;
         auto decompose = [&](const uint32_t pb, const uint32_t jb) {
             const int32_t* accp = reinterpret_cast<const int32_t*>(accb + pb);
-#pragma unroll
-            for (int r = 0; r < 8; r++) {
-                const uint32_t t = jb + 256u * r;
-                const uint32_t o0 = (t & 4092u) | pb, o1 = o0 ^ 2048u;
-                const int32_t m0 = __builtin_amdgcn_sbfe((int32_t)t, 12, 1), m1 = __builtin_amdgcn_sbfe((int32_t)(t + 2048u), 12, 1);
-                const uint32_t rv0 = *reinterpret_cast<const uint32_t*>(accb + o0), rv1 = *reinterpret_cast<const uint32_t*>(accb + o1);
-                const uint32_t pv0 = (uint32_t)accp[64 * r + lane], pv1 = (uint32_t)accp[64 * r + lane + kM];
-                v0[r] = ((rv0 ^ (uint32_t)m0) + ((dec_offset - pv0) - (uint32_t)m0)) ^ dec_offset;
-                v1[r] = ((rv1 ^ (uint32_t)m1) + ((dec_offset - pv1) - (uint32_t)m1)) ^ dec_offset;
-            }
-        };
-        auto mac = [&](double2 (&acc_s)[8], const double2 (&x)[8], const double2 (&b)[8], auto first) {
-            constexpr bool FIRST = decltype(first)::value;
-#pragma unroll
-            for (int k = 0; k < 8; k++)
-                acc_s[k] = FIRST ? cmulx<false>(x[k], b[k])
-                                 : make_double2(fma(x[k].x, b[k].x, fma(-x[k].y, b[k].y, acc_s[k].x)),
-                                                fma(x[k].x, b[k].y, fma(x[k].y, b[k].x, acc_s[k].y)));
+            decompose_rotated(v0, v1, accb, accp, pb, jb, lane, dec_offset);
         };
         auto digit_row = [&](const int sh, const int brow, auto first) {
+            constexpr bool FIRST = decltype(first)::value;
             double2 x[8], bA[8], bB[8];
-#pragma unroll
-            for (int r = 0; r < 8; r++) {
-                const int32_t e0 = __builtin_amdgcn_sbfe((int32_t)v0[r], sh, BGBIT);  // v_bfe_i32
-                const int32_t e1 = __builtin_amdgcn_sbfe((int32_t)v1[r], sh, BGBIT);
-                x[r] = make_double2((double)e0, (double)e1);  // untwisted: the first radix-8 pass applies e^{i pi r/16} itself
-            }
+            digits_to_double2<BGBIT>(x, v0, v1, sh);
             __builtin_amdgcn_sched_barrier(0);
             auto req = [&]() { load_bk_block(bA, bk_rsrc, lane16, brow); };  // block 0: output 0, low limb
             fft512_forward<true, 1, decltype(req), true>(x, sT, lane, R, req);
@@ -560,16 +454,16 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_x1(DevKeys K, const 
             __builtin_amdgcn_sched_barrier(0);
             // block q + 2 is requested when block q has been multiplied (re-requesting register by register, right behind the
             // products that consumed each one, measured the same: profiles/r4_x1_ab.txt)
-            mac(s[0], x, bA, first);
+            mac_row<FIRST>(s[0], x, bA);
             __builtin_amdgcn_sched_barrier(0);
             load_bk_block(bA, bk_rsrc, lane16, brow + 2 * kBlockBytes);            // block 2: output 1, low limb
             __builtin_amdgcn_sched_barrier(0);
-            mac(s[1], x, bB, first);
+            mac_row<FIRST>(s[1], x, bB);
             __builtin_amdgcn_sched_barrier(0);
             load_bk_block(bB, bk_rsrc, lane16, brow + 3 * kBlockBytes);            // block 3: output 1, high limb
             __builtin_amdgcn_sched_barrier(0);
-            mac(s[2], x, bA, first);
-            mac(s[3], x, bB, first);
+            mac_row<FIRST>(s[2], x, bA);
+            mac_row<FIRST>(s[3], x, bB);
         };
         decompose(pb0, jb4);
         digit_row(32 - BGBIT, bki, std::true_type{});
@@ -599,16 +493,7 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_x1(DevKeys K, const 
         }
         wave_sync();
     }
-    if (ext) {
-        Torus32* u = ext + (size_t)item * (kN + 4);
-        for (int32_t j = lane; j <= kN; j += 64)
-            u[j] = j == 0 ? acc[0] : (j == kN ? acc[kN] : (int32_t)(0u - (uint32_t)acc[kN - j]));
-    } else {
-        const int4* src = reinterpret_cast<const int4*>(acc);
-        int4* dst = reinterpret_cast<int4*>(gacc);
-#pragma unroll
-        for (int r = 0; r < 8; r++) dst[64 * r + lane] = src[64 * r + lane];
-    }
+    finish_slice<64>(ext, item, acc, gacc, lane);
 }
 
 // ---- K3 (+K4), mid-size launches, round 3: two waves per gate, the ROWS split between them ----
@@ -653,9 +538,8 @@ __global__ __launch_bounds__(128, 2) void k_blind_rotate_w2r(DevKeys K, const do
     for (int q = 1; q <= L; q++) dec_offset += halfBg << (32 - q * BGBIT);
     double dev_max = 0.0;
     constexpr int kRowBytes = 2 * kM * (int)sizeof(double2), kStepBytes = 2 * L * kRowBytes;
-    const __amdgpu_buffer_rsrc_t bk_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<double2*>(bkf1), (short)0, K.n * kStepBytes, 0x00020000);
-    const int lane16 = lane * (int)sizeof(double2);
+    const __amdgpu_buffer_rsrc_t bk_rsrc = bk_resource(bkf1, K.n, kStepBytes);
+    const int lane16 = bk_lane_offset(lane);
     const unsigned char* accb = reinterpret_cast<const unsigned char*>(acc);  // LDS offset 0 of the workgroup
     const uint32_t pb = (uint32_t)wave * (kN * 4);                             // this wave's polynomial
     const int32_t* accp = acc + wave * kN;
@@ -685,26 +569,15 @@ __global__ __launch_bounds__(128, 2) void k_blind_rotate_w2r(DevKeys K, const do
             constexpr bool FIRST = decltype(first)::value;
             double2 x[8], bA[8], bB[8];
             load_bk_block(bA, bk_rsrc, lane16, brow);
-#pragma unroll
-            for (int r = 0; r < 8; r++) {
-                const int32_t e0 = __builtin_amdgcn_sbfe((int32_t)v0[r], sh, BGBIT);
-                const int32_t e1 = __builtin_amdgcn_sbfe((int32_t)v1[r], sh, BGBIT);
-                x[r] = make_double2((double)e0, (double)e1);  // untwisted: the first radix-8 pass applies e^{i pi r/16} itself
-            }
+            digits_to_double2<BGBIT>(x, v0, v1, sh);
             __builtin_amdgcn_sched_barrier(0);
             fft512_forward<true, 1>(x, sT, lane, R);
             load_bk_block(bB, bk_rsrc, lane16, brow + kRowBytes / 2);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int k = 0; k < 8; k++)
-                s[0][k] = FIRST ? cmulx<false>(x[k], bA[k])
-                                : make_double2(fma(x[k].x, bA[k].x, fma(-x[k].y, bA[k].y, s[0][k].x)),
-                                               fma(x[k].x, bA[k].y, fma(x[k].y, bA[k].x, s[0][k].y)));
+            for (int k = 0; k < 8; k++) s[0][k] = mac<FIRST>(s[0][k], x[k], bA[k]);
 #pragma unroll
-            for (int k = 0; k < 8; k++)
-                s[1][k] = FIRST ? cmulx<false>(x[k], bB[k])
-                                : make_double2(fma(x[k].x, bB[k].x, fma(-x[k].y, bB[k].y, s[1][k].x)),
-                                               fma(x[k].x, bB[k].y, fma(x[k].y, bB[k].x, s[1][k].y)));
+            for (int k = 0; k < 8; k++) s[1][k] = mac<FIRST>(s[1][k], x[k], bB[k]);
         };
         digit_row(32 - BGBIT, bki, std::true_type{});
 #pragma unroll 1
@@ -736,26 +609,8 @@ __global__ __launch_bounds__(128, 2) void k_blind_rotate_w2r(DevKeys K, const do
         wave_sync();  // wave w reads and updates only polynomial w: nothing crosses waves here
     }
     __syncthreads();  // the epilogue below reads both polynomials with all threads
-    if (GUARD) {
-        float m = (float)dev_max;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        if (lane == 0) {
-            const unsigned bits = __float_as_uint(m);
-            if (bits > __builtin_nontemporal_load(&guard[1])) atomicMax(&guard[1], bits);
-            if (m > kGuardLimit) atomicAdd(&guard[0], 1u);
-        }
-    }
-    if (ext) {
-        Torus32* u = ext + (size_t)item * (kN + 4);
-        for (int32_t j = tid; j <= kN; j += 128)
-            u[j] = j == 0 ? acc[0] : (j == kN ? acc[kN] : (int32_t)(0u - (uint32_t)acc[kN - j]));
-    } else {
-        const int4* src = reinterpret_cast<const int4*>(acc);
-        int4* dst = reinterpret_cast<int4*>(gacc);
-#pragma unroll
-        for (int r = 0; r < 4; r++) dst[128 * r + tid] = src[128 * r + tid];
-    }
+    if (GUARD) publish_guard(dev_max, guard, lane);
+    finish_slice<128>(ext, item, acc, gacc, tid);
 }
 
 // ---- K3 (+K4), one to two gates per CU, round 3: FOUR waves per gate, the rows split 2 : 1 : 2 : 1 ----
@@ -806,9 +661,8 @@ __global__ __launch_bounds__(256, 2) void k_blind_rotate_w4r(DevKeys K, const do
     for (int q = 1; q <= L; q++) dec_offset += halfBg << (32 - q * BGBIT);
     double dev_max = 0.0;
     constexpr int kRowBytes = 2 * kM * (int)sizeof(double2), kStepBytes = 2 * L * kRowBytes;
-    const __amdgpu_buffer_rsrc_t bk_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<double2*>(bkf1), (short)0, K.n * kStepBytes, 0x00020000);
-    const int lane16 = lane * (int)sizeof(double2);
+    const __amdgpu_buffer_rsrc_t bk_rsrc = bk_resource(bkf1, K.n, kStepBytes);
+    const int lane16 = bk_lane_offset(lane);
     const unsigned char* accb = reinterpret_cast<const unsigned char*>(acc);
     const uint32_t pb = (uint32_t)pol * (kN * 4);
     const int32_t* accp = acc + pol * kN;
@@ -833,40 +687,20 @@ __global__ __launch_bounds__(256, 2) void k_blind_rotate_w4r(DevKeys K, const do
         double2 s[2][8];
         uint32_t v0[8], v1[8];
         const uint32_t jb4 = ((uint32_t)(lane - a) & (2 * kN - 1)) << 2;
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const uint32_t t = jb4 + 256u * r;
-            const uint32_t o0 = (t & 4092u) | pb, o1 = o0 ^ 2048u;
-            const int32_t m0 = __builtin_amdgcn_sbfe((int32_t)t, 12, 1), m1 = __builtin_amdgcn_sbfe((int32_t)(t + 2048u), 12, 1);
-            const uint32_t rv0 = *reinterpret_cast<const uint32_t*>(accb + o0), rv1 = *reinterpret_cast<const uint32_t*>(accb + o1);
-            const uint32_t pv0 = (uint32_t)accp[64 * r + lane], pv1 = (uint32_t)accp[64 * r + lane + kM];
-            v0[r] = ((rv0 ^ (uint32_t)m0) + ((dec_offset - pv0) - (uint32_t)m0)) ^ dec_offset;
-            v1[r] = ((rv1 ^ (uint32_t)m1) + ((dec_offset - pv1) - (uint32_t)m1)) ^ dec_offset;
-        }
+        decompose_rotated(v0, v1, accb, accp, pb, jb4, lane, dec_offset);
         auto digit_row = [&](const int sh, const int brow, auto first) {
             constexpr bool FIRST = decltype(first)::value;
             double2 x[8], bA[8], bB[8];
             load_bk_block(bA, bk_rsrc, lane16, brow);
-#pragma unroll
-            for (int r = 0; r < 8; r++) {
-                const int32_t e0 = __builtin_amdgcn_sbfe((int32_t)v0[r], sh, BGBIT);
-                const int32_t e1 = __builtin_amdgcn_sbfe((int32_t)v1[r], sh, BGBIT);
-                x[r] = make_double2((double)e0, (double)e1);  // untwisted: the first radix-8 pass applies e^{i pi r/16} itself
-            }
+            digits_to_double2<BGBIT>(x, v0, v1, sh);
             __builtin_amdgcn_sched_barrier(0);
             fft512_forward<true, 1>(x, sT, lane, R);
             load_bk_block(bB, bk_rsrc, lane16, brow + kRowBytes / 2);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int k = 0; k < 8; k++)
-                s[0][k] = FIRST ? cmulx<false>(x[k], bA[k])
-                                : make_double2(fma(x[k].x, bA[k].x, fma(-x[k].y, bA[k].y, s[0][k].x)),
-                                               fma(x[k].x, bA[k].y, fma(x[k].y, bA[k].x, s[0][k].y)));
+            for (int k = 0; k < 8; k++) s[0][k] = mac<FIRST>(s[0][k], x[k], bA[k]);
 #pragma unroll
-            for (int k = 0; k < 8; k++)
-                s[1][k] = FIRST ? cmulx<false>(x[k], bB[k])
-                                : make_double2(fma(x[k].x, bB[k].x, fma(-x[k].y, bB[k].y, s[1][k].x)),
-                                               fma(x[k].x, bB[k].y, fma(x[k].y, bB[k].x, s[1][k].y)));
+            for (int k = 0; k < 8; k++) s[1][k] = mac<FIRST>(s[1][k], x[k], bB[k]);
         };
         digit_row(32 - (q0 + 1) * BGBIT, bki + q0 * kRowBytes, std::true_type{});
 #pragma unroll 1
@@ -903,26 +737,8 @@ __global__ __launch_bounds__(256, 2) void k_blind_rotate_w4r(DevKeys K, const do
         }
         __syncthreads();  // accumulator complete; every handed-over sum consumed; the tiles are scratch again
     }
-    if (GUARD && light) {
-        float m = (float)dev_max;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        if (lane == 0) {
-            const unsigned bits = __float_as_uint(m);
-            if (bits > __builtin_nontemporal_load(&guard[1])) atomicMax(&guard[1], bits);
-            if (m > kGuardLimit) atomicAdd(&guard[0], 1u);
-        }
-    }
-    if (ext) {
-        Torus32* u = ext + (size_t)item * (kN + 4);
-        for (int32_t j = tid; j <= kN; j += 256)
-            u[j] = j == 0 ? acc[0] : (j == kN ? acc[kN] : (int32_t)(0u - (uint32_t)acc[kN - j]));
-    } else {
-        const int4* src = reinterpret_cast<const int4*>(acc);
-        int4* dst = reinterpret_cast<int4*>(gacc);
-#pragma unroll
-        for (int r = 0; r < 2; r++) dst[256 * r + tid] = src[256 * r + tid];
-    }
+    if (GUARD && light) publish_guard(dev_max, guard, lane);
+    finish_slice<256>(ext, item, acc, gacc, tid);
 }
 
 // ---- K3 (+K4), latency-oriented: 2L waves per gate instance ----
@@ -960,9 +776,7 @@ __global__ __launch_bounds__(128 * L) void k_blind_rotate_wide(DevKeys K, const 
     load_twiddles(sTw, gtw, tid, NT);
     const LaneRoots R = make_roots(sTw, lane);
     {
-        const int4* src = reinterpret_cast<const int4*>(gacc);
-        int4* dst = reinterpret_cast<int4*>(acc);
-        for (int idx = tid; idx < 2 * kN / 4; idx += NT) dst[idx] = src[idx];
+        copy_acc_strided<NT>(acc, gacc, tid);
         const uint16_t* bara = st_bara + (size_t)item * nb;
         for (int idx = tid; idx < i1 - i0; idx += NT) s_bara[idx] = bara[i0 + idx];
     }
@@ -981,12 +795,6 @@ __global__ __launch_bounds__(128 * L) void k_blind_rotate_wide(DevKeys K, const 
     double dev_max = 0.0;
     unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
     if (DIAG) tlast = stamp();
-#define IEACHE_STAMP(idx)                      \
-    if (DIAG) {                                \
-        const unsigned long long t_ = stamp(); \
-        tsum[idx] += t_ - tlast;               \
-        tlast = t_;                            \
-    }
 
 #pragma unroll 1
     for (int32_t i = i0; i < i1; i++) {
@@ -1034,9 +842,9 @@ __global__ __launch_bounds__(128 * L) void k_blind_rotate_wide(DevKeys K, const 
             const int32_t e1 = __builtin_amdgcn_sbfe((int32_t)(u1 ^ (halfBg << sh)), sh, BGBIT);
             x[r] = make_double2((double)e0, (double)e1);  // untwisted: the first radix-8 pass applies e^{i pi r/16} itself
         }
-        IEACHE_STAMP(0)
+        stamp_phase<DIAG>(tsum, tlast, 0);
         fft512_forward<true>(x, sT, lane, R);
-        IEACHE_STAMP(1)
+        stamp_phase<DIAG>(tsum, tlast, 1);
 #pragma unroll
         for (int k = 0; k < 8; k++) sT[k * 64 + lane] = x[k];  // publish
         __builtin_amdgcn_sched_barrier(0);
@@ -1047,9 +855,9 @@ __global__ __launch_bounds__(128 * L) void k_blind_rotate_wide(DevKeys K, const 
                 bB[1][k] = bki[(size_t)3 * RS + k * 64];
             }
         }
-        IEACHE_STAMP(2)
+        stamp_phase<DIAG>(tsum, tlast, 2);
         __syncthreads();  // A: all 2L spectra are in their tiles
-        IEACHE_STAMP(3)
+        stamp_phase<DIAG>(tsum, tlast, 3);
         if (is_out) {
 #pragma unroll
             for (int k = 0; k < 8; k++) s[k] = make_double2(0.0, 0.0);
@@ -1078,9 +886,9 @@ __global__ __launch_bounds__(128 * L) void k_blind_rotate_wide(DevKeys K, const 
             }
 #undef IEACHE_MAC_ROW
         }
-        IEACHE_STAMP(4)
+        stamp_phase<DIAG>(tsum, tlast, 4);
         __syncthreads();  // B: every spectrum has been consumed, tiles are scratch again
-        IEACHE_STAMP(5)
+        stamp_phase<DIAG>(tsum, tlast, 5);
         if (is_out) {
             fft512_inverse<true>(s, sT, lane, R);
 #pragma unroll
@@ -1092,21 +900,11 @@ __global__ __launch_bounds__(128 * L) void k_blind_rotate_wide(DevKeys K, const 
                 atomicAdd(&acco[j + kM], c1);
             }
         }
-        IEACHE_STAMP(6)
+        stamp_phase<DIAG>(tsum, tlast, 6);
         __syncthreads();  // C: accumulator complete before the next decomposition
-        IEACHE_STAMP(7)
+        stamp_phase<DIAG>(tsum, tlast, 7);
     }
-#undef IEACHE_STAMP
-    if (LIMBS == 1 && guard && is_out) {
-        float m = (float)dev_max;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        if (lane == 0) {
-            const unsigned bits = __float_as_uint(m);
-            if (bits > __builtin_nontemporal_load(&guard[1])) atomicMax(&guard[1], bits);
-            if (m > 0.0625f) atomicAdd(&guard[0], 1u);
-        }
-    }
+    if (LIMBS == 1 && guard && is_out) publish_guard(dev_max, guard, lane);
     if (DIAG && diag && lane == 0 && (wave == 0 || wave == 4)) {
 #pragma unroll
         for (int t = 0; t < 8; t++) atomicAdd(&diag[(wave >> 2) * 8 + t], tsum[t]);
@@ -1238,8 +1036,7 @@ __global__ __launch_bounds__(128 * L) void k_blind_rotate_wide4(DevKeys K, const
 #pragma unroll
                 for (int k = 0; k < 8; k++) {
                     const double2 y = sp[k * 64];
-                    s[k] = q == 0 ? cmulx<false>(y, bk[0][k])
-                                  : make_double2(fma(y.x, bk[q][k].x, fma(-y.y, bk[q][k].y, s[k].x)), fma(y.x, bk[q][k].y, fma(y.y, bk[q][k].x, s[k].y)));
+                    s[k] = q == 0 ? mac<true>(s[k], y, bk[0][k]) : mac<false>(s[k], y, bk[q][k]);
                 }
             }
             fft512_inverse<true>(s, sTi, lane, R);
@@ -1254,16 +1051,7 @@ __global__ __launch_bounds__(128 * L) void k_blind_rotate_wide4(DevKeys K, const
         }
         __syncthreads();  // C: accumulator complete before the next decomposition; every published spectrum consumed
     }
-    if (GUARD && is_out) {
-        float m = (float)dev_max;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        if (lane == 0) {
-            const unsigned bits = __float_as_uint(m);
-            if (bits > __builtin_nontemporal_load(&guard[1])) atomicMax(&guard[1], bits);
-            if (m > kGuardLimit) atomicAdd(&guard[0], 1u);
-        }
-    }
+    if (GUARD && is_out) publish_guard(dev_max, guard, lane);
     if (ext) {
         Torus32* u = ext + (size_t)item * (kN + 4);
         for (int32_t j = tid; j <= kN; j += NT)
@@ -1293,10 +1081,8 @@ size_t spectrum1_elems(const Params& p) { return (size_t)p.n * p.kpl() * 2 * kM;
 size_t lds_bytes_w1(int wg_gates) { return (size_t)(wg_gates * kTile + kTwElems) * sizeof(double2) + (size_t)wg_gates * 2 * kN * 4; }
 int gates_per_workgroup_w1() { return kW1Gates; }
 
-size_t lds_bytes(const Params& p) {
-    (void)p;
-    return (size_t)(2 * kTile + kTwElems) * sizeof(double2) + (size_t)2 * kN * 4;
-}
+static size_t lds_w2(int, int32_t, int);
+size_t lds_bytes(const Params& p) { return lds_w2(p.l, 0, 1); }  // k_blind_rotate_w2 / _w2r
 
 int32_t bara_stride(const Params& p) { return (p.n + 7) & ~7; }
 
@@ -1316,26 +1102,6 @@ void prepare_spectrum(const Params& p, const Torus32* d_bk_raw, double2* d_bkf, 
 void prepare_spectrum1(const Params& p, const Torus32* d_bk_raw, double2* d_bkf1, hipStream_t stream) {
     const size_t npoly = (size_t)p.n * p.kpl() * 2;
     hipLaunchKernelGGL(k_bk_to_spectrum_w64_1, dim3((unsigned)npoly), dim3(64), 0, stream, d_bk_raw, d_bkf1);
-}
-
-bool variant_known(int32_t v) {
-    switch (v) {
-        case 0: case kVariantTwoWavesLds: case kVariantWide: case kVariantWide + 1: case kVariantExactOneWave:
-        case kVariantWideOneLimb:
-        case kVariantOneLimbDefault: case kVariantOneLimbDefault + 1: case kVariantOneLimbDefault + 4: case kVariantOneLimbStamps:
-        case kVariantOneLimbTwoWaves: case kVariantOneLimbTwoWaves + 1:
-        case kVariantWideHandoverOneLimb: case kVariantWideHandoverOneLimb + 1:
-        case kVariantOneLimbFourWaves: case kVariantOneLimbFourWaves + 1:
-            return true;
-        default: return false;
-    }
-}
-bool variant_one_limb(int32_t v) { return variant_known(v) && v >= kVariantWideOneLimb; }
-// kernels that keep a slice's rotation amounts in LDS or reload them every 64 steps: a slice may be the whole rotation
-static bool variant_long_slices(int32_t v) {
-    return v == kVariantWide || v == kVariantWide + 1 || v == kVariantWideOneLimb || v == kVariantOneLimbTwoWaves ||
-           v == kVariantOneLimbTwoWaves + 1 || v == kVariantWideHandoverOneLimb || v == kVariantWideHandoverOneLimb + 1 ||
-           v == kVariantOneLimbFourWaves || v == kVariantOneLimbFourWaves + 1;
 }
 
 static int32_t device_cus() {
@@ -1379,112 +1145,172 @@ static int32_t w4r_flip_period() {
     return v;
 }
 
-// > 64 KiB of dynamic LDS has to be allowed explicitly, once per kernel instantiation
-#define IEACHE_ALLOW_LDS(KERNEL, BYTES)                                                                                        \
-    {                                                                                                                          \
-        static const bool attr_set =                                                                                           \
-            hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES)) == hipSuccess;  \
-        if (!attr_set) throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for " #KERNEL);        \
-    }
+// ---- the variants: one row per br_variant number that exists (blind_rotate_w64.h lists them for readers) ----
+// one launch: CMux steps [i0, i1) of `items` gate instances, parameter set l
+struct Slice {
+    int32_t l;
+    int64_t items;
+    hipStream_t stream;
+    const DevKeys& K;
+    const double2 *bkf2, *bkf1;
+    const uint16_t* st_bara;
+    int32_t nb;
+    int32_t* st_acc;
+    int32_t i0, i1;
+    Torus32* ext;
+    unsigned* guard;
+    const double2* gtw;
+};
+constexpr int kTwoLWaves = 0;
+struct Variant {
+    int32_t number;     // "br_variant"
+    const char* name;   // the kernel
+    bool chosen;        // what the evaluator's choice by launch size reports under the kernel's name; false: a measurement or
+                        // diagnostic build of it, reported by number
+    int limbs;          // 1: the one-limb spectrum and the guard record (the sampled audit applies); 2: exact by construction
+    bool long_slices;   // keeps a slice's rotation amounts in LDS or reloads them every 64 steps: a slice may be the whole rotation
+    int threads;        // per workgroup; kTwoLWaves: 128 L (2L waves per gate)
+    int gates;          // per workgroup
+    size_t (*lds)(int L, int32_t nb, int gates);  // dynamic LDS of a launch
+    size_t allow;       // bytes of dynamic LDS to be allowed first; 0: the launch fits the default 64 KiB
+    void (*launch)(const Variant&, const Slice&);
+    mutable LdsGrant granted[2];  // ... remembered per kernel (parameter set) and device
+};
 
-// one slice [i0, i1) of CMux steps for `items` gate instances on the kernel `variant` names
-template <int L, int BGBIT>
-static void launch_slice(int variant, int64_t items, hipStream_t stream, const DevKeys& K, const double2* bkf2, const double2* bkf1,
-                         const uint16_t* st_bara, int32_t nb, int32_t* st_acc, int32_t i0, int32_t i1, Torus32* e, unsigned* guard,
-                         const double2* gtw, int wg) {
-    const dim3 per_gate((unsigned)items), per4((unsigned)((items + kW1Gates - 1) / kW1Gates));
-    const size_t lds_w1 = lds_bytes_w1(kW1Gates);
-    // the two kernels wide launches take, built for G = 1 .. 4 gates per workgroup (wg; evaluator: by how the launch fills the CUs)
-#define IEACHE_W1_G(GG)                                                                                                                     \
-    {                                                                                                                                       \
-        const dim3 grid((unsigned)((items + GG - 1) / GG));                                                                                 \
-        if (variant == kVariantExactOneWave) {                                                                                              \
-            IEACHE_ALLOW_LDS((k_blind_rotate_x1<L, BGBIT, GG>), lds_bytes_w1(GG))                                                           \
-            hipLaunchKernelGGL((k_blind_rotate_x1<L, BGBIT, GG>), grid, dim3(64 * GG), lds_bytes_w1(GG), stream, K, bkf2, st_bara, nb,      \
-                               st_acc, items, i0, i1, e, gtw);                                                                              \
-        } else {                                                                                                                            \
-            IEACHE_ALLOW_LDS((k_blind_rotate_w1b<L, BGBIT, 2, false, GG>), lds_bytes_w1(GG))                                                \
-            hipLaunchKernelGGL((k_blind_rotate_w1b<L, BGBIT, 2, false, GG>), grid, dim3(64 * GG), lds_bytes_w1(GG), stream, K, bkf1,        \
-                               st_bara, nb, st_acc, items, i0, i1, e, guard, gtw, (unsigned long long*)nullptr);                            \
-        }                                                                                                                                   \
-        return;                                                                                                                             \
+// the one place that turns the runtime parameter set into template arguments (supported(): these two only)
+template <int L_, int BGBIT_>
+struct ParamSet {
+    static constexpr int L = L_, BGBIT = BGBIT_, index = L_ == 3 ? 0 : 1;
+};
+template <class F>
+static void with_param_set(int32_t l, F&& f) {
+    if (l == 3)
+        f(ParamSet<3, 7>{});
+    else
+        f(ParamSet<2, 10>{});
+}
+template <class T>
+struct as_is {
+    using type = T;
+};
+template <class PS, class... P>
+static void launch_row(PS, const Variant& v, const Slice& s, void (*kernel)(P...), typename as_is<P>::type... args) {
+    if (v.allow) {
+        char what[96];  // the instantiation, for the message of a refused opt-in
+        snprintf(what, sizeof what, "%s<%d,%d> (br_variant %d, %d gates per workgroup)", v.name, PS::L, PS::BGBIT, (int)v.number, v.gates);
+        allow_dynamic_lds_once(v.granted[PS::index], (const void*)kernel, v.allow, what);
     }
-    if ((variant == kVariantExactOneWave || variant == kVariantOneLimbDefault) && wg >= 1 && wg < kW1Gates) {
-        if (wg == 1) IEACHE_W1_G(1)
-        if (wg == 2) IEACHE_W1_G(2)
-        IEACHE_W1_G(3)
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((s.items + v.gates - 1) / v.gates)), dim3(v.threads == kTwoLWaves ? 128 * PS::L : v.threads),
+                       v.lds(PS::L, s.nb, v.gates), s.stream, args...);
+}
+// one launcher per kernel (their argument lists differ), instantiated for both parameter sets
+template <int XLANE>
+static void go_w2(const Variant& v, const Slice& s) {
+    with_param_set(s.l, [&](auto ps) {
+        launch_row(ps, v, s, k_blind_rotate_w2<ps.L, ps.BGBIT, XLANE>, s.K, s.bkf2, s.st_bara, s.nb, s.st_acc, s.i0, s.i1, s.ext, s.gtw);
+    });
+}
+template <int G>
+static void go_x1(const Variant& v, const Slice& s) {
+    with_param_set(s.l, [&](auto ps) {
+        launch_row(ps, v, s, k_blind_rotate_x1<ps.L, ps.BGBIT, G>, s.K, s.bkf2, s.st_bara, s.nb, s.st_acc, s.items, s.i0, s.i1, s.ext, s.gtw);
+    });
+}
+template <bool DIAG, int LIMBS>
+static void go_wide(const Variant& v, const Slice& s) {
+    with_param_set(s.l, [&](auto ps) {
+        launch_row(ps, v, s, k_blind_rotate_wide<ps.L, ps.BGBIT, DIAG, LIMBS>, s.K, LIMBS == 2 ? s.bkf2 : s.bkf1, s.st_bara, s.nb, s.st_acc,
+                   s.i0, s.i1, s.ext, DIAG ? diag_buf() : nullptr, s.gtw, LIMBS == 2 ? nullptr : s.guard);
+    });
+}
+template <int GUARD, bool DIAG = false, int G = kW1Gates>
+static void go_w1b(const Variant& v, const Slice& s) {
+    with_param_set(s.l, [&](auto ps) {
+        launch_row(ps, v, s, k_blind_rotate_w1b<ps.L, ps.BGBIT, GUARD, DIAG, G>, s.K, s.bkf1, s.st_bara, s.nb, s.st_acc, s.items, s.i0, s.i1,
+                   s.ext, s.guard, s.gtw, DIAG ? diag_buf() : nullptr);
+    });
+}
+template <int GUARD>
+static void go_w2r(const Variant& v, const Slice& s) {
+    with_param_set(s.l, [&](auto ps) {
+        launch_row(ps, v, s, k_blind_rotate_w2r<ps.L, ps.BGBIT, GUARD>, s.K, s.bkf1, s.st_bara, s.nb, s.st_acc, s.i0, s.i1, s.ext, s.guard, s.gtw);
+    });
+}
+template <int GUARD>
+static void go_w4r(const Variant& v, const Slice& s) {
+    with_param_set(s.l, [&](auto ps) {
+        launch_row(ps, v, s, k_blind_rotate_w4r<ps.L, ps.BGBIT, GUARD>, s.K, s.bkf1, s.st_bara, s.nb, s.st_acc, s.i0, s.i1, s.ext, s.guard, s.gtw,
+                   w4r_flip_period());
+    });
+}
+template <int GUARD>
+static void go_wide4(const Variant& v, const Slice& s) {
+    with_param_set(s.l, [&](auto ps) {
+        launch_row(ps, v, s, k_blind_rotate_wide4<ps.L, ps.BGBIT, GUARD>, s.K, s.bkf1, s.st_bara, s.nb, s.st_acc, s.i0, s.i1, s.ext, s.guard, s.gtw);
+    });
+}
+
+constexpr size_t kAccBytes = (size_t)2 * kN * 4, kCuLds = 160 * 1024;
+static size_t lds_w1(int, int32_t, int gates) { return lds_bytes_w1(gates); }
+static size_t lds_w2(int, int32_t, int) { return (size_t)(2 * kTile + kTwElems) * sizeof(double2) + kAccBytes; }
+static size_t lds_w4(int, int32_t, int) { return (size_t)(4 * kTile + 2 * 8 * 64 + kTwElems) * sizeof(double2) + kAccBytes; }
+static size_t lds_wide(int L, int32_t nb, int) { return (size_t)(2 * L * kTile + kTwElems) * sizeof(double2) + kAccBytes + (size_t)nb * 2; }
+static size_t lds_wide4(int L, int32_t nb, int) { return (size_t)((2 * L + 4) * kTile + kTwElems) * sizeof(double2) + kAccBytes + (size_t)nb * 2; }
+
+// The default row of a number stands first; the rows behind it with fewer gates per workgroup are the builds a launch that
+// does not fill the chip takes (wg_gates of launch(): the two kernels wide launches use, G = 1 .. 3).
+static const Variant kVariants[] = {
+    // number                        kernel                 chosen limbs long threads gates LDS      allow            launcher
+    // ---- two limbs: exact by construction ----
+    {0,                              "k_blind_rotate_w2",    true,  2, false, 128, 1, lds_w2,    0,               go_w2<1>},
+    {kVariantTwoWavesLds,            "k_blind_rotate_w2",    false, 2, false, 128, 1, lds_w2,    0,               go_w2<0>},         // every transpose through LDS (round 1)
+    {kVariantExactOneWave,           "k_blind_rotate_x1",    true,  2, false, 256, 4, lds_w1,    lds_bytes_w1(4), go_x1<4>},
+    {kVariantExactOneWave,           "k_blind_rotate_x1",    true,  2, false, 192, 3, lds_w1,    lds_bytes_w1(3), go_x1<3>},
+    {kVariantExactOneWave,           "k_blind_rotate_x1",    true,  2, false, 128, 2, lds_w1,    lds_bytes_w1(2), go_x1<2>},
+    {kVariantExactOneWave,           "k_blind_rotate_x1",    true,  2, false, 64,  1, lds_w1,    lds_bytes_w1(1), go_x1<1>},
+    {kVariantWide,                   "k_blind_rotate_wide",  true,  2, true,  kTwoLWaves, 1, lds_wide,  kCuLds,          go_wide<false, 2>},
+    {kVariantWide + 1,               "k_blind_rotate_wide",  false, 2, true,  kTwoLWaves, 1, lds_wide,  kCuLds,          go_wide<true, 2>},  // phase stamps
+    // ---- one limb, guarded (on one rounded coefficient in four unless noted) ----
+    {kVariantWideOneLimb,            "k_blind_rotate_wide",  false, 1, true,  kTwoLWaves, 1, lds_wide,  kCuLds,          go_wide<false, 1>}, // A/B partner of k_blind_rotate_wide4
+    {kVariantOneLimbDefault,         "k_blind_rotate_w1b",   true,  1, false, 256, 4, lds_w1,    lds_bytes_w1(4), go_w1b<2>},
+    {kVariantOneLimbDefault,         "k_blind_rotate_w1b",   true,  1, false, 192, 3, lds_w1,    lds_bytes_w1(3), go_w1b<2, false, 3>},
+    {kVariantOneLimbDefault,         "k_blind_rotate_w1b",   true,  1, false, 128, 2, lds_w1,    lds_bytes_w1(2), go_w1b<2, false, 2>},
+    {kVariantOneLimbDefault,         "k_blind_rotate_w1b",   true,  1, false, 64,  1, lds_w1,    lds_bytes_w1(1), go_w1b<2, false, 1>},
+    {kVariantOneLimbDefault + 1,     "k_blind_rotate_w1b",   false, 1, false, 256, 4, lds_w1,    lds_bytes_w1(4), go_w1b<1>},         // guard on every coefficient
+    {kVariantOneLimbDefault + 4,     "k_blind_rotate_w1b",   false, 1, false, 256, 4, lds_w1,    lds_bytes_w1(4), go_w1b<0>},         // no guard arithmetic (measurement)
+    {kVariantOneLimbStamps,          "k_blind_rotate_w1b",   false, 1, false, 256, 4, lds_w1,    lds_bytes_w1(4), go_w1b<2, true>},   // phase stamps
+    {kVariantOneLimbTwoWaves,        "k_blind_rotate_w2r",   true,  1, true,  128, 1, lds_w2,    0,               go_w2r<2>},
+    {kVariantOneLimbTwoWaves + 1,    "k_blind_rotate_w2r",   false, 1, true,  128, 1, lds_w2,    0,               go_w2r<1>},         // guard on every coefficient
+    {kVariantOneLimbFourWaves,       "k_blind_rotate_w4r",   true,  1, true,  256, 1, lds_w4,    kCuLds,          go_w4r<2>},
+    {kVariantOneLimbFourWaves + 1,   "k_blind_rotate_w4r",   false, 1, true,  256, 1, lds_w4,    kCuLds,          go_w4r<1>},
+    {kVariantWideHandoverOneLimb,    "k_blind_rotate_wide4", true,  1, true,  kTwoLWaves, 1, lds_wide4, kCuLds,          go_wide4<2>},
+    {kVariantWideHandoverOneLimb + 1, "k_blind_rotate_wide4", false, 1, true, kTwoLWaves, 1, lds_wide4, kCuLds,          go_wide4<1>},
+};
+// the row of `number` built for `gates` per workgroup, else its default row; null: no such variant
+static const Variant* find_variant(int32_t number, int gates = 0) {
+    const Variant* first = nullptr;
+    for (const Variant& v : kVariants) {
+        if (v.number != number) continue;
+        if (v.gates == gates) return &v;
+        if (!first) first = &v;
     }
-#undef IEACHE_W1_G
-    const size_t lds_w2 = (size_t)(2 * kTile + kTwElems) * sizeof(double2) + (size_t)2 * kN * 4;
-    const size_t lds_w4 = (size_t)(4 * kTile + 2 * 8 * 64 + kTwElems) * sizeof(double2) + (size_t)2 * kN * 4;
-    const size_t lds_wide = (size_t)(2 * L * kTile + kTwElems) * sizeof(double2) + (size_t)2 * kN * 4 + (size_t)nb * 2;
-    const size_t lds_wide4 = (size_t)((2 * L + 4) * kTile + kTwElems) * sizeof(double2) + (size_t)2 * kN * 4 + (size_t)nb * 2;
-    unsigned long long* const nodiag = nullptr;
-    switch (variant) {
-        // ---- two limbs: exact by construction ----
-        case 0:  // two waves per gate
-            hipLaunchKernelGGL((k_blind_rotate_w2<L, BGBIT, 1>), per_gate, dim3(128), lds_w2, stream, K, bkf2, st_bara, nb, st_acc, i0, i1, e, gtw);
-            break;
-        case kVariantTwoWavesLds:  // ... with every transpose through LDS (round 1)
-            hipLaunchKernelGGL((k_blind_rotate_w2<L, BGBIT, 0>), per_gate, dim3(128), lds_w2, stream, K, bkf2, st_bara, nb, st_acc, i0, i1, e, gtw);
-            break;
-        case kVariantExactOneWave:  // one wave per gate (round 4)
-            IEACHE_ALLOW_LDS((k_blind_rotate_x1<L, BGBIT>), lds_w1)
-            hipLaunchKernelGGL((k_blind_rotate_x1<L, BGBIT>), per4, dim3(64 * kW1Gates), lds_w1, stream, K, bkf2, st_bara, nb, st_acc, items, i0, i1, e, gtw);
-            break;
-        case kVariantWide:  // 2L waves per gate (latency)
-            IEACHE_ALLOW_LDS((k_blind_rotate_wide<L, BGBIT, false, 2>), 160 * 1024)
-            hipLaunchKernelGGL((k_blind_rotate_wide<L, BGBIT, false, 2>), per_gate, dim3(128 * L), lds_wide, stream, K, bkf2, st_bara, nb, st_acc, i0, i1, e, nodiag, gtw, (unsigned*)nullptr);
-            break;
-        case kVariantWide + 1:  // ... with phase stamps
-            IEACHE_ALLOW_LDS((k_blind_rotate_wide<L, BGBIT, true, 2>), 160 * 1024)
-            hipLaunchKernelGGL((k_blind_rotate_wide<L, BGBIT, true, 2>), per_gate, dim3(128 * L), lds_wide, stream, K, bkf2, st_bara, nb, st_acc, i0, i1, e, diag_buf(), gtw, (unsigned*)nullptr);
-            break;
-        // ---- one limb, guarded ----
-        case kVariantWideOneLimb:  // round 2's latency kernel on the one-limb spectrum (A/B partner of k_blind_rotate_wide4)
-            IEACHE_ALLOW_LDS((k_blind_rotate_wide<L, BGBIT, false, 1>), 160 * 1024)
-            hipLaunchKernelGGL((k_blind_rotate_wide<L, BGBIT, false, 1>), per_gate, dim3(128 * L), lds_wide, stream, K, bkf1, st_bara, nb, st_acc, i0, i1, e, nodiag, gtw, guard);
-            break;
-        case kVariantOneLimbDefault:  // one wave per gate, guard on one coefficient in four
-            IEACHE_ALLOW_LDS((k_blind_rotate_w1b<L, BGBIT, 2>), lds_w1)
-            hipLaunchKernelGGL((k_blind_rotate_w1b<L, BGBIT, 2>), per4, dim3(64 * kW1Gates), lds_w1, stream, K, bkf1, st_bara, nb, st_acc, items, i0, i1, e, guard, gtw, nodiag);
-            break;
-        case kVariantOneLimbDefault + 1:  // ... on every coefficient
-            IEACHE_ALLOW_LDS((k_blind_rotate_w1b<L, BGBIT, 1>), lds_w1)
-            hipLaunchKernelGGL((k_blind_rotate_w1b<L, BGBIT, 1>), per4, dim3(64 * kW1Gates), lds_w1, stream, K, bkf1, st_bara, nb, st_acc, items, i0, i1, e, guard, gtw, nodiag);
-            break;
-        case kVariantOneLimbDefault + 4:  // ... no guard arithmetic (measurement)
-            IEACHE_ALLOW_LDS((k_blind_rotate_w1b<L, BGBIT, 0>), lds_w1)
-            hipLaunchKernelGGL((k_blind_rotate_w1b<L, BGBIT, 0>), per4, dim3(64 * kW1Gates), lds_w1, stream, K, bkf1, st_bara, nb, st_acc, items, i0, i1, e, guard, gtw, nodiag);
-            break;
-        case kVariantOneLimbStamps:  // ... with phase stamps
-            IEACHE_ALLOW_LDS((k_blind_rotate_w1b<L, BGBIT, 2, true>), lds_w1)
-            hipLaunchKernelGGL((k_blind_rotate_w1b<L, BGBIT, 2, true>), per4, dim3(64 * kW1Gates), lds_w1, stream, K, bkf1, st_bara, nb, st_acc, items, i0, i1, e, guard, gtw, diag_buf());
-            break;
-        case kVariantOneLimbTwoWaves:  // two waves per gate, rows split
-            hipLaunchKernelGGL((k_blind_rotate_w2r<L, BGBIT, 2>), per_gate, dim3(128), lds_w2, stream, K, bkf1, st_bara, nb, st_acc, i0, i1, e, guard, gtw);
-            break;
-        case kVariantOneLimbTwoWaves + 1:
-            hipLaunchKernelGGL((k_blind_rotate_w2r<L, BGBIT, 1>), per_gate, dim3(128), lds_w2, stream, K, bkf1, st_bara, nb, st_acc, i0, i1, e, guard, gtw);
-            break;
-        case kVariantOneLimbFourWaves:  // four waves per gate, rows 2 : 1 : 2 : 1
-            IEACHE_ALLOW_LDS((k_blind_rotate_w4r<L, BGBIT, 2>), 160 * 1024)
-            hipLaunchKernelGGL((k_blind_rotate_w4r<L, BGBIT, 2>), per_gate, dim3(256), lds_w4, stream, K, bkf1, st_bara, nb, st_acc, i0, i1, e, guard, gtw, w4r_flip_period());
-            break;
-        case kVariantOneLimbFourWaves + 1:
-            IEACHE_ALLOW_LDS((k_blind_rotate_w4r<L, BGBIT, 1>), 160 * 1024)
-            hipLaunchKernelGGL((k_blind_rotate_w4r<L, BGBIT, 1>), per_gate, dim3(256), lds_w4, stream, K, bkf1, st_bara, nb, st_acc, i0, i1, e, guard, gtw, w4r_flip_period());
-            break;
-        case kVariantWideHandoverOneLimb:  // 2L waves per gate, four output waves (latency)
-            IEACHE_ALLOW_LDS((k_blind_rotate_wide4<L, BGBIT, 2>), 160 * 1024)
-            hipLaunchKernelGGL((k_blind_rotate_wide4<L, BGBIT, 2>), per_gate, dim3(128 * L), lds_wide4, stream, K, bkf1, st_bara, nb, st_acc, i0, i1, e, guard, gtw);
-            break;
-        case kVariantWideHandoverOneLimb + 1:
-            IEACHE_ALLOW_LDS((k_blind_rotate_wide4<L, BGBIT, 1>), 160 * 1024)
-            hipLaunchKernelGGL((k_blind_rotate_wide4<L, BGBIT, 1>), per_gate, dim3(128 * L), lds_wide4, stream, K, bkf1, st_bara, nb, st_acc, i0, i1, e, guard, gtw);
-            break;
-        default: throw std::invalid_argument("unknown blind-rotation variant");
-    }
+    return first;
+}
+bool variant_known(int32_t v) { return find_variant(v) != nullptr; }
+bool variant_one_limb(int32_t v) {
+    const Variant* r = find_variant(v);
+    return r && r->limbs == 1;
+}
+const char* variant_kernel_name(int32_t v) {
+    const Variant* r = find_variant(v);
+    return r && r->chosen ? r->name : nullptr;
+}
+
+// one slice of CMux steps on the kernel `variant` names, wg gates per workgroup where the kernel is built for that
+static void launch_slice(int variant, int wg, const Slice& s) {
+    const Variant* v = find_variant(variant, wg);
+    if (!v) throw std::invalid_argument("unknown blind-rotation variant");
+    v->launch(*v, s);
 }
 
 int32_t default_variant() {
@@ -1539,12 +1365,8 @@ static int launch_mixed_phases(const Params& p, const DevKeys& K, const double2*
                 while (todo > 0) {  // the one-wave kernel takes at most 64 steps per launch (one rotation amount per lane)
                     const int32_t s = two ? todo : std::min<int32_t>(todo, 64);
                     const int v = two ? kVariantOneLimbTwoWaves : kVariantOneLimbDefault;
-                    if (p.l == 3)
-                        launch_slice<3, 7>(v, m, plan.streams[j], K, nullptr, d_bkf1, st_bara + (size_t)off * nb, nb, st_acc + (size_t)off * 2 * kN,
-                                           pos[j], pos[j] + s, nullptr, guard, d_twiddles, plan.wg);
-                    else
-                        launch_slice<2, 10>(v, m, plan.streams[j], K, nullptr, d_bkf1, st_bara + (size_t)off * nb, nb, st_acc + (size_t)off * 2 * kN,
-                                            pos[j], pos[j] + s, nullptr, guard, d_twiddles, plan.wg);
+                    launch_slice(v, plan.wg, Slice{p.l, m, plan.streams[j], K, nullptr, d_bkf1, st_bara + (size_t)off * nb, nb,
+                                                   st_acc + (size_t)off * 2 * kN, pos[j], pos[j] + s, nullptr, guard, d_twiddles});
                     pos[j] += s;
                     todo -= s;
                     launches++;
@@ -1579,13 +1401,10 @@ int launch(const Params& p, const DevKeys& K, const double2* d_bkf, const double
     uint16_t* st_bara = reinterpret_cast<uint16_t*>(st_acc + (size_t)items * 2 * kN);
     hipLaunchKernelGGL(k_br_prologue, dim3((unsigned)items), dim3(128), 0, stream, K, W, st_bara, nb, st_acc);
     const int32_t nsteps = steps < 0 ? p.n : (steps < p.n ? steps : p.n);
-    const int32_t max_slice = variant_long_slices(variant) ? nb : 64;
+    const int32_t max_slice = find_variant(variant)->long_slices ? nb : 64;
     const int32_t S = (slice >= 1 && slice <= max_slice) ? slice : default_slice();
     auto one = [&](int v, int32_t i0, int32_t i1, Torus32* e) {
-        if (p.l == 3)
-            launch_slice<3, 7>(v, items, stream, K, d_bkf, d_bkf1, st_bara, nb, st_acc, i0, i1, e, guard, d_twiddles, wg_gates);
-        else
-            launch_slice<2, 10>(v, items, stream, K, d_bkf, d_bkf1, st_bara, nb, st_acc, i0, i1, e, guard, d_twiddles, wg_gates);
+        launch_slice(v, wg_gates, Slice{p.l, items, stream, K, d_bkf, d_bkf1, st_bara, nb, st_acc, i0, i1, e, guard, d_twiddles});
     };
     int32_t first = 0;
     if (mix && mix->k >= 2 && mix->cycles >= 1 && variant_one_limb(variant) && mix->streams[0] == stream) {

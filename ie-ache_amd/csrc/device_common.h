@@ -2,7 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
+#include <stdexcept>
+#include <string>
 
 #include "circuit.h"
 #include "level_items.h"
@@ -158,6 +161,28 @@ __device__ __forceinline__ double2 cfma(double2 a, double2 b, double2 c) {  // a
     return make_double2(fma(a.x, b.x, fma(-a.y, b.y, c.x)), fma(a.x, b.y, fma(a.y, b.x, c.y)));
 }
 
+// ---- host: dynamic LDS beyond the default 64 KiB ----
+// A kernel has to be allowed its dynamic LDS size explicitly (hipFuncAttributeMaxDynamicSharedMemorySize), and the
+// permission belongs to the (kernel, device) pair: a process that drives two devices needs it on each.  This is the only
+// place that asks for it.
+inline void allow_dynamic_lds(const void* kernel, size_t bytes, const char* name) {
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+        throw std::runtime_error(std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for ") + name);
+}
+// ... remembered for launch paths that would otherwise ask before every launch: one word per kernel, bit d = granted on
+// device d, so later launches on a device cost one hipGetDevice (a thread-local read) and no attribute call.  `bytes` must
+// not depend on the call (devices past 63 are asked every time).
+struct LdsGrant {
+    std::atomic<uint64_t> devices{0};
+};
+inline void allow_dynamic_lds_once(LdsGrant& grant, const void* kernel, size_t bytes, const char* name) {
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) throw std::runtime_error(std::string("hipGetDevice failed before launching ") + name);
+    const uint64_t bit = device < 64 ? 1ull << device : 0;
+    if (grant.devices.load(std::memory_order_acquire) & bit) return;
+    allow_dynamic_lds(kernel, bytes, name);
+    grant.devices.fetch_or(bit, std::memory_order_release);
+}
 
 }  // namespace dev
 }  // namespace ieache

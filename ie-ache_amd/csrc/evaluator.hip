@@ -750,8 +750,9 @@ void Evaluator::init() {
     d_->ks_lds = (size_t)(p.N + 4) * 4 + (size_t)p.N * p.ks_t * 4;
     if (d_->br_lds > 160 * 1024 || d_->ks_lds > 160 * 1024)
         throw std::invalid_argument("parameter set exceeds the 160 KiB LDS of a CU");
-    HIP_CHECK(hipFuncSetAttribute((const void*)k_blind_rotate_generic, hipFuncAttributeMaxDynamicSharedMemorySize, (int)d_->br_lds));
-    HIP_CHECK(hipFuncSetAttribute((const void*)k_keyswitch_generic, hipFuncAttributeMaxDynamicSharedMemorySize, (int)d_->ks_lds));
+    // (per context, on the context's device: the sizes depend on the parameter set)
+    dev::allow_dynamic_lds((const void*)k_blind_rotate_generic, d_->br_lds, "k_blind_rotate_generic");
+    dev::allow_dynamic_lds((const void*)k_keyswitch_generic, d_->ks_lds, "k_keyswitch_generic");
     {
         const int nvec = K.stride / 4, nld = (nvec + 63) / 64;
         d_->ksv_lds = (size_t)(p.N + 4) * 4 + (size_t)p.N * p.ks_t * 4 + (size_t)8 * K.stride * 4;
@@ -762,13 +763,12 @@ void Evaluator::init() {
         d_->ks_mfma_ok = ksm::supported(p);
         if (const char* e = getenv("IEACHE_KS_MFMA_MIN")) d_->ks_mfma_min = atoll(e);
         if (d_->ks_batch_ok)
-            HIP_CHECK(hipFuncSetAttribute((const void*)k_keyswitch_batch<16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)((size_t)16 * p.N * 2 + 64)));
+            dev::allow_dynamic_lds((const void*)k_keyswitch_batch<16>, (size_t)16 * p.N * 2 + 64, "k_keyswitch_batch");
         if (nld <= 4 && d_->ksv_lds <= 160 * 1024) {
             d_->ks_nld = nld;
             const void* f = nld == 1 ? (const void*)k_keyswitch_vec<1> : nld == 2 ? (const void*)k_keyswitch_vec<2>
                           : nld == 3 ? (const void*)k_keyswitch_vec<3> : (const void*)k_keyswitch_vec<4>;
-            HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)d_->ksv_lds));
+            dev::allow_dynamic_lds(f, d_->ksv_lds, "k_keyswitch_vec");
         }
     }
 }
@@ -1148,15 +1148,11 @@ std::string Evaluator::kernel_for_launch(int64_t gates) const {
         snprintf(tag, sizeof tag, "<%d,%d> %d of %d subsets on two waves", (int)p_.l, (int)p_.Bgbit, mtw, mk);
         return std::string("k_blind_rotate_w2r+w1b") + tag;
     }
-    switch (variant) {
-        case w64::kVariantOneLimbDefault: name = "k_blind_rotate_w1b"; break;
-        case w64::kVariantOneLimbTwoWaves: name = "k_blind_rotate_w2r"; break;
-        case w64::kVariantOneLimbFourWaves: name = "k_blind_rotate_w4r"; break;
-        case w64::kVariantWideHandoverOneLimb: name = "k_blind_rotate_wide4"; break;
-        case w64::kVariantWide: name = "k_blind_rotate_wide"; break;
-        case w64::kVariantExactOneWave: name = "k_blind_rotate_x1"; break;
-        case 0: name = "k_blind_rotate_w2"; break;
-        default: snprintf(tag, sizeof tag, "<%d,%d> br_variant %d", (int)p_.l, (int)p_.Bgbit, (int)variant); name = "k_blind_rotate"; break;
+    if (const char* kernel = w64::variant_kernel_name(variant)) {
+        name = kernel;
+    } else {  // a measurement or diagnostic build: by number
+        snprintf(tag, sizeof tag, "<%d,%d> br_variant %d", (int)p_.l, (int)p_.Bgbit, (int)variant);
+        name = "k_blind_rotate";
     }
     return name + tag;
 }

@@ -239,11 +239,8 @@ int32_t max_slice() { return 1024; }  // digits of a slice in LDS: slice * G * 2
 template <int G>
 static void launch_g(const DevKeys& K, const WorkDesc& W, int64_t items, const Torus32* ext, Torus32* flat_out, int32_t i0, int32_t i1,
                      int nld, hipStream_t stream) {
-    static const bool attr = [] {
-        return hipFuncSetAttribute((const void*)k_keyswitch_sliced<G>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) ==
-               hipSuccess;
-    }();
-    if (!attr) throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for k_keyswitch_sliced");
+    static LdsGrant grant;  // per instantiation, i.e. per kernel
+    allow_dynamic_lds_once(grant, (const void*)k_keyswitch_sliced<G>, 64 * 1024, "k_keyswitch_sliced");
     hipLaunchKernelGGL(k_keyswitch_sliced<G>, dim3((unsigned)((items + G - 1) / G)), dim3(64 * nld), (size_t)(i1 - i0) * G * 2, stream,
                        K, W, ext, flat_out, items, i0, i1);
 }
