@@ -1,18 +1,29 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: bootstrapped gate ops/s on level-batched circuits.
 
-  python bench.py --gpus N --steps K --warmup W [--workload add16|mul32|...] [--batch B] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--full] [--workload add16|mul32|...] [--batch B] [--dump-outputs DIR]
 
 One "step" = one pass of a whole circuit (every level, every gate) over one
 batch of expressions whose ciphertexts are already resident in HBM.  The timed
 K steps run the primary workload = BASELINE.json configs[1]: 16-bit ADD, batch
-4096 per GPU.  The default invocation then adds, on the same resident key, one
-full timed pass each of
-  * configs[2]: 32-bit shift-add MUL, batch 1024 per GPU   -> `mul32`   (gate ops/s, encrypted 32-bit MUL/s)
-  * configs[3]'s per-GPU share: 64-bit a*b+c, batch 128     -> `muladd64`
-  * configs[4]'s circuit: 128-bit MUL, a time-boxed sub-batch of 128 of its 1024 per GPU -> `mul128`
-every product decrypt-checked, each with its own roofline object.  (--extras adds the two opt-in,
-decrypt-identical-only multipliers: constant-folded and carry-save.)
+4096 per GPU.
+
+A plain run does what the headline figure needs and no more: keys and inputs, W warm-up steps (the last one's outputs
+decrypt-checked, 0.3 s: the figure is quoted for right answers, and the timed steps start from the device state they always
+started from), the K timed steps, the dump when --dump-outputs is given, the JSON line (its roofline object is priced on
+the timed steps themselves).
+
+--full is the whole measurement: after the timed steps it adds, on the same resident key,
+  * a few steps of the primary batch with every launch on one stream, for the per-kernel roofline figures (--roofline-steps)
+  * the primary batch once more on the provably exact two-limb kernels, compared word for word -> `exact` (--exact-leg)
+  * one full timed pass each (--legs) of
+      configs[2]: 32-bit shift-add MUL, batch 1024 per GPU   -> `mul32`   (gate ops/s, encrypted 32-bit MUL/s)
+      configs[3]'s per-GPU share: 64-bit a*b+c, batch 128     -> `muladd64`
+      configs[4]'s circuit: 128-bit MUL, a time-boxed sub-batch of 128 of its 1024 per GPU -> `mul128`
+    every product decrypt-checked, each with its own roofline object (--extras adds the two opt-in,
+    decrypt-identical-only multipliers: constant-folded and carry-save)
+  * the CPU baseline (N = 1; --no-cpu-baseline, --cpu-seconds).
+The options in parentheses shape those parts; without --full they have nothing to shape, and asking for legs is an error.
 
 --dump-outputs DIR writes what the last of the K timed steps left in the output buffer -- the LWE samples a caller of
 eval_batch_device receives -- to DIR/<workload>_out.npy (dump_outputs below).  Keys, operands and encryption noise are all
@@ -507,13 +518,16 @@ def self_launch(args):
 DEFAULT_LEGS = (("mul32", "mul32", 1024, 1024), ("muladd64", "muladd64", 128, 128), ("mul128", "mul128", 128, 1024))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="add16", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="expressions per GPU (default: the config's)")
+    ap.add_argument("--full", action="store_true",
+                    help="the whole measurement: after the K timed steps also the one-stream roofline steps, the exact leg, the mul32 / "
+                         "muladd64 / mul128 legs and the CPU baseline (a plain run stops at the timed steps and prints the line)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--chunk", type=int, default=0)
@@ -540,10 +554,18 @@ def main():
                     help="also time the two opt-in, decrypt-identical-only 32-bit multipliers (constant-folded, carry-save) in the mul32 leg")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: rehearse the N>1 flow with CPU collectives (ranks may then share one GPU)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps: at least one timed step is needed")
+    if not args.full:  # a plain run ends with the timed steps: every part after them is switched off here, in one place
+        if args.extras or args.mul32_leg == "on" or args.legs not in ("auto", "none"):
+            ap.error("--legs / --mul32-leg on / --extras ask for legs that only a --full run times: add --full")
+        args.legs, args.exact_leg, args.roofline_steps, args.no_cpu_baseline = "none", "off", 0, True
+    return args
 
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))  # before anything touches the GPU in this process
 

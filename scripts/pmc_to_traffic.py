@@ -79,7 +79,7 @@ for a in sys.argv[5:]:
             if KERNELS[key][0].split("<")[0] in row["Name"] and "prologue" not in row["Name"]:
                 out[key]["rocprof_avg_launch_ms"] = float(row["AverageNs"]) * 1e-6
                 out[key]["rocprof_calls"] = int(row["Calls"])
-                out[key]["rocprof_stats"] = os.path.relpath(os.path.abspath(f), ROOT) + " (rocprofv3 --kernel-trace --stats -- python3 bench.py %s)" % ("--steps 3 --warmup 1 --no-cpu-baseline --legs none --exact-leg off" if key.startswith("w1") else "--steps 1 --warmup 1 --no-cpu-baseline --legs none: the primary leg, then the exact leg's two passes")
+                out[key]["rocprof_stats"] = os.path.relpath(os.path.abspath(f), ROOT) + " (rocprofv3 --kernel-trace --stats -- python3 bench.py %s)" % ("--steps 3 --warmup 1 --no-cpu-baseline --legs none --exact-leg off" if key.startswith("w1") else "--steps 1 --warmup 1 --full --no-cpu-baseline --legs none: the primary leg, then the exact leg's two passes")
                 break
 json.dump(out, open(path, "w"), indent=1)
 print(json.dumps(out[key], indent=1))

@@ -4,7 +4,7 @@
 mkdir -p gpurun_out/r4
 ( while sleep 60; do echo "tick $(date +%H:%M:%S)"; done ) &
 T=$!
-timeout -k 10 1100 python bench.py --batch 64 --steps 1 --warmup 1 --legs mul128 --mul128-batch 1024 --time-box 5000 \
+timeout -k 10 1100 python bench.py --batch 64 --steps 1 --warmup 1 --full --legs mul128 --mul128-batch 1024 --time-box 5000 \
     --exact-leg off --cpu-seconds 3 > gpurun_out/r4/mul128x1024_bench.json 2> gpurun_out/r4/mul128x1024_bench.err
 rc=$?
 kill $T

@@ -8,7 +8,7 @@ mkdir -p $O
 rm -rf $O/stats_all
 ( while sleep 60; do echo tick; done ) &
 T=$!
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_all -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --details $O/all_rocprof_details.json > $O/all_rocprof.json 2> $O/all_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_all -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --details $O/all_rocprof_details.json > $O/all_rocprof.json 2> $O/all_rocprof.err
 rc=$?
 kill $T
 f=$(find $O/stats_all -name "*kernel_stats.csv" | head -1)

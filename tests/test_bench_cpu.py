@@ -101,6 +101,25 @@ def test_self_launch_builds_a_torchrun_command_and_relays(bench, monkeypatch, ca
     assert bench.self_launch(types.SimpleNamespace(gpus=3, backend="nccl")) == 7 and seen["cmd"][1:3] == ["-m", "torch.distributed.run"]
 
 
+def test_plain_run_ends_with_the_timed_steps_and_full_restores_the_rest(bench, capsys):
+    """Without --full every part after the timed steps is off, whatever else the command line says; --full leaves the defaults
+    the whole measurement always had.  Asking for legs without --full is an error, not a silently shorter run."""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", "d"])
+    assert not plain.full and (plain.steps, plain.warmup, plain.dump_outputs) == (20, 5, "d")
+    assert (plain.legs, plain.exact_leg, plain.roofline_steps, plain.no_cpu_baseline) == ("none", "off", 0, True)
+    switched_off = bench.parse_args(["--legs", "none", "--exact-leg", "on", "--roofline-steps", "5", "--mul32-leg", "off"])
+    assert (switched_off.legs, switched_off.exact_leg, switched_off.roofline_steps, switched_off.no_cpu_baseline) == ("none", "off", 0, True)
+    full = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full.full and (full.legs, full.exact_leg, full.roofline_steps, full.no_cpu_baseline, full.extras) == ("auto", "on", 3, False, False)
+    assert (full.time_box, full.metric_passes, full.cpu_seconds) == (330.0, 2, 20.0)
+    shaped = bench.parse_args(["--full", "--legs", "mul32,muladd64", "--extras", "--exact-leg", "off", "--no-cpu-baseline", "--roofline-steps", "0"])
+    assert (shaped.legs, shaped.exact_leg, shaped.roofline_steps, shaped.no_cpu_baseline, shaped.extras) == ("mul32,muladd64", "off", 0, True, True)
+    for argv in (["--legs", "mul32"], ["--extras"], ["--mul32-leg", "on"]):
+        with pytest.raises(SystemExit) as e:
+            bench.parse_args(argv)
+        assert e.value.code == 2 and "--full" in capsys.readouterr().err
+
+
 def test_launcher_counts_gpus_from_the_kfd_topology(bench, tmp_path, monkeypatch):
     """The launcher's GPU count comes from sysfs (nodes with SIMDs are GPUs, the CPU node has none), narrowed by the
     visible-devices variables; no HIP call."""

@@ -1643,7 +1643,7 @@ def test_bench_two_rank_flow_on_one_gpu(tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--full",
            "--batch", "48", "--backend", "gloo", "--no-cpu-baseline", "--legs", "mul32,muladd64", "--mul32-batch", "6",
            "--muladd64-batch", "2", "--extras", "--details", str(tmp_path / "details.json")]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
@@ -1677,7 +1677,7 @@ def test_bench_two_rank_flow_on_one_gpu(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_default_command_shape_with_three_ranks_on_one_gpu(tmp_path):
-    """First-contact rehearsal of the multi-GPU job: the DEFAULT command shape -- every leg: add16 steps, the exact leg, mul32,
+    """First-contact rehearsal of the multi-GPU job: the --full command shape -- every leg: add16 steps, the exact leg, mul32,
     muladd64, mul128 -- with `--gpus 3`, started by bench.py itself, ranks wrapping onto this box's one GPU, CPU
     collectives.  Three, not eight: this pool allows at most six processes on a card, and this test process and the launcher's
     agent count too (a six-rank attempt was killed by the box's process guard; four ran, at the limit); the eight-rank plumbing runs on CPU in
@@ -1686,7 +1686,7 @@ def test_bench_default_command_shape_with_three_ranks_on_one_gpu(tmp_path):
     import sys
     import time
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "3", "--backend", "gloo", "--batch", "64", "--legs",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "3", "--full", "--backend", "gloo", "--batch", "64", "--legs",
            "mul32,muladd64,mul128", "--mul32-batch", "8", "--muladd64-batch", "4", "--mul128-batch", "2", "--no-cpu-baseline",
            "--details", str(tmp_path / "details.json")]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
@@ -1724,7 +1724,7 @@ def test_bench_collectives_on_rccl_with_one_rank(ia, tmp_path):
     import sys
     from ieache_amd import tools
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--batch", "64",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--full", "--batch", "64",
            "--backend", "nccl", "--no-cpu-baseline", "--legs", "mul32", "--mul32-batch", "4", "--dump-outputs", str(tmp_path / "dump")]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=tmp_path,
@@ -1744,6 +1744,35 @@ def test_bench_collectives_on_rccl_with_one_rank(ia, tmp_path):
     lwe_key = tools.keygen_raw(p, (314, 1592, 657), with_cloud=False)["lwe_key"]
     dec = tools.decrypt_bits(p, lwe_key, dump.astype(np.int32))
     assert [tools.bits_to_int(dec[e]) for e in range(4)] == [0, 2, 0xFFFE, 0x8000]   # 0+0, 1+1, 2 (2^16-1), 2 x 2^14
+
+
+def test_bench_plain_run_stops_at_the_timed_steps(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: set-up, warm-up, the K timed steps, the line.  No exact leg, no
+    further workload, no CPU baseline, the roofline object priced on the timed steps themselves; and the whole process, start to
+    exit, spends less than 30 s outside its K + W steps (a --full run spends minutes there)."""
+    import subprocess
+    import sys
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--details", str(tmp_path / "details.json")]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
+    t0 = time.perf_counter()
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=tmp_path, env=env)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and len(lines[0]) < 6000, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                "data", "config", "roofline", "fft_guard", "details"):
+        assert key in line, key
+    for key in ("exact", "mul32", "muladd64", "mul128", "metric_leg", "mul32_per_s", "cpu_baseline", "skipped_legs"):
+        assert key not in line, key
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["config"]["batch_per_gpu"] == 4096 and line["unit"] == "gate ops/s"
+    assert line["value"] == pytest.approx(80 * 4096 / (line["ms_per_step"] * 1e-3), rel=1e-4)
+    assert line["roofline"]["mode"] == "timed region" and 0 < line["roofline"]["frac"] < 1
+    assert wall - 3 * line["ms_per_step"] * 1e-3 < 30, (wall, line["ms_per_step"])
+    assert "--legs" in subprocess.run(cmd + ["--legs", "mul32"], capture_output=True, text=True, timeout=60, cwd=tmp_path, env=env).stderr
 
 
 def test_output_noise_matches_the_published_variance(ia, gpu_ctx):
