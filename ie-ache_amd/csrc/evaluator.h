@@ -14,6 +14,8 @@
 
 namespace ieache {
 
+struct OptionRow;  // evaluator_options.h
+
 struct EvalStats {
     double total_ms = 0;         // wall time of the call on the GPU timeline (events on the stream)
     double blind_rotate_ms = 0;  // time with a blind-rotation launch in flight: the sum over launches on one stream; with
@@ -38,9 +40,9 @@ public:
     hipStream_t stream() const { return stream_; }
     // gate instances the blind-rotation kernel keeps resident at once (one workgroup each, 4 per CU): a launch
     // takes ceil(gate instances / this) rounds
-    int resident_gates() const { return resident_gates_; }
+    int resident_gates() const;
     // ... and by the two-waves-per-gate one-limb kernel that takes launches up to that size (0 when "exact_fft" leaves one size)
-    int resident_gates_two_wave() const { return resident_two_wave_; }
+    int resident_gates_two_wave() const;
     // Orders everything launched later on the evaluator's stream after the work queued so far on
     // `producer` (the stream that wrote the key / input buffers handed over as device pointers).
     void wait_for_stream(hipStream_t producer);
@@ -83,30 +85,16 @@ public:
     void debug_keyswitch(size_t count, const Torus32* d_u, Torus32* d_out);
 
     // Force the generic (any-parameter) kernels even where a specialised one exists.
-    void set_force_generic(bool v) { force_generic_ = v; }
+    void set_force_generic(bool v);
     // Maximum gate instances per launch (bounds the scratch buffers).
     void set_chunk(size_t items);
-    // Named tuning knobs: "chunk", "force_generic", "ks_mfma_min" (gate instances per launch from which the key switch runs
-    // as an int8 product on the MFMA pipe, keyswitch_mfma.hip; default 64), "ks_mfma_split" (workgroups its walk is cut into
-    // per tile: 1, 2, 4, 8, or 0 = by launch size), "ks_sliced_min" (gate instances per launch from which, below that or
-    // with it disabled, the hand-scheduled walk is used; default 576), "ks_gates" (its gate instances per workgroup:
-    // 4, 8, 16, 32, or 0 = by launch size), "ks_slice" (coefficients per launch of it, 0 = whole walk),
-    // "ks_batch_min" (same threshold for the compiler-scheduled gate-batched kernel, the cross-check),
-    // "ks_split_max" (workgroups the per-gate key switch may cut one gate's walk into when a launch holds only a
-    // handful of gates; default 16, 1 = never),
-    // "br_slice" (CMux steps per blind-rotation launch; 0 = by kernel and launch size: 16 for wide launches that take
-    // several rounds of resident gates, 64 while every gate of the launch is resident at once, the whole rotation for the
-    // four-waves-per-gate and latency kernels),
-    // "br_wide_max" (launches of at most this many gate instances use the latency-oriented
-    // 2L-waves-per-gate kernel; default = the device's CU count, 0 = never), "br_variant",
-    // "exact_fft" (1 = two-limb blind rotation always), "one_limb_min" (launches of at least this many gate
-    // instances use the one-limb kernels; default: one per CU + 1), "two_wave_max" (of those, launches up to this many
-    // gate instances take two waves per gate, k_blind_rotate_w2r; default 5 per CU), "four_wave_max" (launches up to this many
-    // take four waves per gate, k_blind_rotate_w4r; default 2 per CU), "fft_guard_inject" (test hook: 1 makes
-    // the next call find the rounding guard tripped, so that it repeats itself on the two-limb kernels), "fft_audit" (see
-    // fft_audit_counts), "fft_audit_inject" (test hook: 1 makes the next audit report a differing row).
-    // Returns false for an unknown name or a value out of range.
+    // Named options and read-only figures: evaluator_options.h holds THE table -- every name, its environment variable,
+    // accepted range, default and a line on what it does.  set_option returns false for an unknown name, a read-only
+    // figure or a value the row refuses; get_option reads every row, false for an unknown name.  An environment variable is
+    // read once, when the context is created, and treated as a set_option: a value out of range is ignored.
     bool set_option(const std::string& name, int64_t value);
+    bool get_option(const std::string& name, int64_t* value) const;
+    // The stream modes those options steer:
     // "overlap" (default 1; IEACHE_OVERLAP): launches go to TWO streams of the context (own scratch each, the one key copy),
     // so that the ragged end of one stream's launch, its key switch and its prologue run under the other stream's rotation:
     //   * a circuit over a batch whose mean level holds at least "pipe_min" gate instances (default 8 per CU;
@@ -130,10 +118,6 @@ public:
     // The same gate instances go through the same kernels' arithmetic either way: output bits do not depend on it.
     // 0 = every launch on one stream -- the mode per-kernel timings (rocprofv3 averages, bench.py's roofline) are taken
     // in, since overlapped kernels share the chip.
-    // Current value of an option, or of a read-only figure: "cus", "resident_gates", "overlapped_levels" (levels issued as
-    // halves on two streams so far), "pipelined_evals" (circuit evaluations run as two expression-half pipelines so far),
-    // "staging_allocations".  false for an unknown name.
-    bool get_option(const std::string& name, int64_t* value) const;
     std::string kernel_variant() const;
     // name of the blind-rotation kernel a launch of `gates` gate instances takes under the current options
     std::string kernel_for_launch(int64_t gates) const;
@@ -159,13 +143,12 @@ private:
     void debug_blind_rotate_once(size_t count, const Torus32* d_x, Torus32* d_acc, int32_t steps);
     void init();
     void destroy();
+    void begin_call();
+    bool option_hook(const OptionRow& row, int64_t& value);
     Params p_;
     int device_;
-    hipStream_t stream_ = nullptr;
+    hipStream_t stream_ = nullptr;  // lane 0's, owned by Impl
     bool keys_loaded_ = false;
-    bool force_generic_ = false;
-    int resident_gates_ = 1024;
-    int resident_two_wave_ = 0;
     Impl* d_ = nullptr;
 };
 

@@ -22,8 +22,11 @@
 #include "blind_rotate_w64.h"
 #include "keyswitch_mfma.h"
 #include "keyswitch_sliced.h"
+#include "device_buffer.h"
 #include "device_common.h"
+#include "evaluator_options.h"
 #include "mix_plan.h"
+#include "scoped_set.h"
 
 #include <algorithm>
 #include <cmath>
@@ -551,119 +554,62 @@ __global__ void k_gather_outputs(const OutRef* outs, int32_t n_out, const Torus3
 // extracted-sample rows, blind-rotation state, key-switch digits and audit scratch -- take either a contiguous share of a
 // batch's expressions through every level of a circuit (pipelines: one fork, one join per evaluation) or every other piece
 // of a wide level (lane 0 then waits for lane 1 before the next level starts).  See Evaluator::set_option in evaluator.h.
-constexpr int kMaxLanes = 4;
 struct Lane {
-    hipStream_t stream = nullptr;
-    Torus32* ext = nullptr;
-    size_t ext_items = 0;
-    Torus32* comb = nullptr;   // levels with MUX gates: one combined row per gate of a piece (k_level_combine).  Per lane, not
-    size_t comb_items = 0;     // per context: two lanes run their combines and key switches side by side
-    void* br_state = nullptr;  // sliced blind rotation: accumulators + rotation amounts
-    size_t br_state_items = 0;
-    void* ks_digits = nullptr;
-    size_t ks_digits_bytes = 0;
-    Torus32* audit_ext = nullptr;
-    void* audit_state = nullptr;
+    Stream stream;                  // lane 0: the evaluator's own
+    DeviceBuffer<Torus32> ext;      // extracted samples, rows of N + 4 words
+    DeviceBuffer<Torus32> comb;     // levels with MUX gates: one combined row per gate of a piece (k_level_combine).  Per lane, not
+                                    // per context: two lanes run their combines and key switches side by side
+    DeviceBuffer<char> br_state;    // sliced blind rotation: accumulators + rotation amounts, w64::state_bytes_per_item() per item
+    DeviceBuffer<char> ks_digits;   // MFMA key switch (counted in bytes)
+    DeviceBuffer<Torus32> audit_ext;
+    DeviceBuffer<char> audit_state;
+    Event ev_join;                  // the lane's share of a level / of an evaluation is queued
+    Event ev_mix;
 };
 
+// Members are released in reverse order; Evaluator::destroy() has every stream idle before that starts.
 struct Evaluator::Impl {
     Params p;
     Lane lane[kMaxLanes];
-    hipEvent_t ev_fork = nullptr, ev_join[kMaxLanes] = {};  // ev_join[k]: lane k's share of a level / of an evaluation is queued
-    // "overlap": 1 = levels of at least overlap_min gate instances are cut in two and issued on two streams (the tail of one
-    // piece's launches fills with the other's workgroups, a piece's key switch runs under the next piece's rotation); 0 = one stream
-    int32_t overlap = 1;
-    int64_t overlap_min = 0;     // set in init(): 16 gates per CU -- each half is then a full round of resident gates
-    int64_t overlapped_levels = 0;
-    // Circuits over a batch: the batch is cut into two contiguous halves of EXPRESSIONS and each half runs through every
-    // level on its own stream -- expressions are independent, so the two pipelines never wait for each other between
-    // levels (one fork after the input copy, one join before the outputs are gathered).  Used when the circuit's mean
-    // level holds at least pipe_min gate instances over the whole batch.  While both pipelines run, a launch shares the
-    // chip with the other stream's launch of the same level: kernels are chosen by the gates in flight on BOTH streams.
-    int64_t pipe_min = 0;        // set in init(): 8 gates per CU (measured: 11 per CU +2.9 %, 4 per CU -10 %, profiles/r5_overlap_ab.txt)
-    int32_t pipe_lanes = 2;      // pipelines a qualifying evaluation is cut into (2 .. kMaxLanes; "pipe_lanes", IEACHE_PIPE_LANES)
-    int32_t concurrency = 1;     // streams issuing launches side by side right now (kernel choice is by cnt x concurrency)
-    int64_t pipelined_evals = 0;
-    // "pipe_auto" (default 1): with a mean level between pipe_min / 8 and 2 x pipe_min neither stream mode wins everywhere
-    // (mul32 x 40: pipelines +5.6 %, muladd64 x 16: -9.7 %, profiles/r5_pipes_vs_mix.txt), so the first four evaluations of a
-    // (circuit, batch) there alternate -- without pipelines, with, without, with -- and later ones take whichever mode had the
-    // faster evaluation.  Every one of them is a complete evaluation with the same output bits; only the schedule differs.
-    int32_t pipe_auto = 1;
+    Event ev_fork;
+    EvalOptions opt;  // evaluator_options.h: everything set_option / get_option name
+    // per-call state (begin_call, ScopedSet)
+    bool use_w64 = false;
+    bool force_generic_ks = false;
+    bool exact_once = false;          // set while a call is repeated after a guard trip
+    int32_t concurrency = 1;          // streams issuing launches side by side right now (kernel choice is by cnt x concurrency)
+    bool level_on_two_lanes = false;  // set while a level's halves are being queued on two streams (no rotation of roles then)
+    // "pipe_auto": the first four evaluations of a (circuit, batch) in the band where neither stream mode wins everywhere
+    // alternate -- without pipelines, with, without, with -- and later ones take whichever mode had the faster evaluation
     struct Tuned {
         double ms[2] = {-1.0, -1.0};  // best wall time of an evaluation without / with pipelines
         int n[2] = {0, 0};            // trials so far (two each, alternating: a first call also pays for allocations)
     };
     std::map<std::tuple<size_t, int32_t, size_t, size_t, bool>, Tuned> tuned;  // (gates, levels, outputs, batch, exact_fft)
-    int64_t tuned_evals = 0;
-    // device rows the host-buffer entry points stage their operands and results in: kept between calls, grown on demand
-    Torus32* stage[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t stage_bytes[4] = {0, 0, 0, 0};
-    int64_t stage_allocs = 0;
+    DeviceBuffer<Torus32> stage[4];  // rows the host-buffer entry points stage operands and results in (counted in bytes)
     DevKeys K{};
-    double2* bkf = nullptr;
-    double2* bkf_w64 = nullptr;  // spectrum in the wave-per-gate kernel's layout
-    double2* tw_w64 = nullptr;   // its twiddle table
-    double2* bkf1_w64 = nullptr; // one-limb spectrum of k_blind_rotate_w1
-    unsigned* fft_guard = nullptr;  // [0] launches whose rounding deviation exceeded the limit, [1] max deviation (float bits), [2] audit rows that differed
-    bool exact_fft = false;      // "exact_fft": never use the one-limb kernel
-    bool exact_once = false;     // set while a call is repeated after a guard trip
-    int64_t one_limb_min = 0;    // launches of at least this many gate instances use the one-limb kernels
-    int64_t four_wave_max = 0;   // ... the four-waves-per-gate one (k_blind_rotate_w4r) up to this many (2 per CU),
-    int64_t two_wave_max = 0;    // ... the two-waves-per-gate one up to this many (4 per CU: all resident at once), the one-wave one above
+    DeviceBuffer<double2> bkf;
+    DeviceBuffer<double2> bkf_w64;   // spectrum in the wave-per-gate kernel's layout
+    DeviceBuffer<double2> tw_w64;    // its twiddle table
+    DeviceBuffer<double2> bkf1_w64;  // one-limb spectrum of k_blind_rotate_w1
+    DeviceBuffer<unsigned> fft_guard;  // [0] launches whose rounding deviation exceeded the limit, [1] max deviation (float bits), [2] audit rows that differed
     double guard_max = 0;        // largest rounding deviation seen by the one-limb kernel (of 0.5)
     int64_t guard_reruns = 0;    // calls repeated on the two-limb kernel
-    // "fft_audit" = K: every K-th (level, chunk) launch that took a one-limb kernel has a sample of kAuditGates of its gate
-    // instances run again on the two-limb kernel and compared word for word (fft_guard[2] counts differing rows); 0 = off
-    int32_t fft_audit = 64;
-    int64_t exact_one_wave_min = 1025;  // two-limb launches from this size on take k_blind_rotate_x1 (one wave per gate)
     int64_t audit_seq = 0;       // one-limb (level, chunk) launches so far
     int64_t audits = 0, audit_gates = 0, audit_mismatches = 0;
-    bool audit_inject = false;   // test hook: the next audit reports a mismatch
-    int cus = 0;
-    bool use_w64 = false;
-    bool force_generic_ks = false;
-    int32_t* ksk = nullptr;
-    double2* twist = nullptr;
-    double2* wtab = nullptr;
-    Torus32* ext_mux = nullptr;  // bootsMUX: combined extracted samples, chunk/2 rows
-    size_t ext_mux_items = 0;
-    size_t chunk = 65536;         // gate instances per launch at most (scratch grows on demand, see grown())
-    Torus32* store = nullptr;
-    size_t store_bytes = 0;
-    DevGate* d_gates = nullptr;
-    size_t d_gates_cap = 0;
-    OutRef* d_outs = nullptr;
-    size_t d_outs_cap = 0;
+    DeviceBuffer<int32_t> ksk;
+    DeviceBuffer<int8_t> ks_limbs;  // byte-limb form of the key for the MFMA key switch
+    DeviceBuffer<double2> twist, wtab;
+    DeviceBuffer<Torus32> ext_mux;  // bootsMUX: combined extracted samples, chunk/2 rows
+    DeviceBuffer<Torus32> store;    // circuits: the wire store, the gate and the output table
+    DeviceBuffer<DevGate> d_gates;
+    DeviceBuffer<OutRef> d_outs;
     size_t br_lds = 0, ks_lds = 0, ksv_lds = 0;
     int ks_nld = 0;  // dwordx4 loads per KSK row per wave; 0 = use the scalar kernel
-    bool ks_batch_ok = false;     // gate-batched key switch usable (base == 4, digits fit 16 bits, columns fit 8 waves)
-    int64_t ks_batch_min = 4096;  // use it from this many gate instances per launch (one workgroup walk takes ~5 ms)
-    bool ks_sliced_ok = false;    // hand-scheduled sliced variant of it usable (t = 8, basebit = 2)
-    int64_t ks_sliced_min = 576;  // ... and used from this many gate instances per launch (measured crossover with the per-gate kernel: ~560)
-    int32_t ks_slice = 0;         // coefficients per launch of the sliced key switch; 0 = the whole walk
-    int32_t ks_gates = 0;         // gate instances per workgroup there (8 / 16 / 32); 0 = by launch size
-    // key switch as an int8 product on the MFMA pipe (keyswitch_mfma.hip): byte-limb form of the key, digit scratch, and the
-    // launch size from which it takes over from the hand-scheduled walk
-    int8_t* ks_limbs = nullptr;
+    bool ks_batch_ok = false;   // gate-batched key switch usable (base == 4, digits fit 16 bits, columns fit 8 waves)
+    bool ks_sliced_ok = false;  // hand-scheduled sliced variant of it usable (t = 8, basebit = 2)
     bool ks_mfma_ok = false;
-    int64_t ks_mfma_min = 64;     // measured crossover with the per-gate walk: ~40 gates (0.08 ms either way)
-    int32_t ks_mfma_split = 0;    // K split of the product; 0 = by launch size
-    int32_t ks_split_max = 16;    // per-gate key switch: workgroups one gate's walk may be cut into when the launch is tiny
-    int32_t br_slice = 0;         // CMux steps per blind-rotation launch; 0 = the kernel's default
-    int32_t br_variant = w64::default_variant();
-    // gate instances per workgroup of the one-wave-per-gate kernels (k_blind_rotate_w1b / _x1): 1 .. 4, 0 = by launch size
-    // launches of 4 .. 7 and 8 .. 10.5 gates per CU (mix_plan.h): rotation of roles between the two-waves- and the
-    // one-wave-per-gate kernel on three streams (w64::MixPlan); "br_mix" 0/1, "mix_s1" steps of a one-wave turn,
-    // "mix_ratio" = 100 x (two-wave steps per one-wave step), "mix_sync" phase barriers, "mix_k" / "mix_tw" a forced geometry
-    int32_t br_mix = 1, mix_s1 = 16, mix_ratio = 200, mix_sync = 0, mix_wg = 2, mix_k = 0, mix_tw = 0;
-    int64_t mixed_launches = 0;
-    bool level_on_two_lanes = false;  // set while a level's halves are being queued on two streams (no rotation of roles then)
-    hipEvent_t ev_mix[kMaxLanes] = {};
-    int32_t wg_gates = 0;
-    int64_t wg3_max = 0;          // set in init(): launches of up to this many gate instances (6 per CU) take three per workgroup
-    // launches of at most this many gate instances (one per CU) use the 2L-waves-per-gate kernel in a
-    // single launch: what matters there is the latency of one blind rotation, not throughput
-    int64_t br_wide_max = 0;
+    size_t ext_row_bytes() const { return (size_t)(K.N + 4) * 4; }
 };
 
 Evaluator::Evaluator(const Params& p, int device) : p_(p), device_(device), d_(new Impl) {
@@ -683,39 +629,27 @@ void Evaluator::init() {
     HIP_CHECK(hipGetDeviceCount(&count));
     if (device < 0 || device >= count) throw std::runtime_error("no such HIP device");
     HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    d_->lane[0].stream = stream_;
+    d_->lane[0].stream.ensure();
+    stream_ = d_->lane[0].stream;
     {
         int cus = 0;
         HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-        d_->cus = cus;
-        d_->br_wide_max = cus;  // one workgroup of the wide kernel fills a CU
-        d_->overlap_min = 16 * (int64_t)cus;
-        d_->pipe_min = 8 * (int64_t)cus;
-        if (const char* e = getenv("IEACHE_PIPE_MIN")) d_->pipe_min = atoll(e);
-        if (const char* e = getenv("IEACHE_PIPE_LANES")) d_->pipe_lanes = atoi(e) >= 2 && atoi(e) <= kMaxLanes ? atoi(e) : 2;
-        d_->wg3_max = 6 * (int64_t)cus;
-        if (const char* e = getenv("IEACHE_BR_MIX")) d_->br_mix = atoi(e) != 0;
-        if (const char* e = getenv("IEACHE_WG_GATES")) d_->wg_gates = atoi(e) >= 0 && atoi(e) <= 4 ? atoi(e) : 0;
-        if (const char* e = getenv("IEACHE_WG3_MAX")) d_->wg3_max = atoll(e);
-        if (const char* e = getenv("IEACHE_OVERLAP")) d_->overlap = atoi(e) != 0;
-        if (const char* e = getenv("IEACHE_OVERLAP_MIN")) d_->overlap_min = atoll(e);
+        EvalOptions& o = d_->opt;
+        o.cus = cus;
+        o.br_wide_max = cus;  // one workgroup of the wide kernel fills a CU
+        o.overlap_min = 16 * (int64_t)cus;  // each half of a level is then a full round of resident gates
+        o.pipe_min = 8 * (int64_t)cus;      // measured: 11 per CU +2.9 %, 4 per CU -10 %, profiles/r5_overlap_ab.txt
+        o.wg3_max = 6 * (int64_t)cus;
         // k_blind_rotate_w1: one wave per gate, 256 VGPRs -> 2 per SIMD = 8 gates per CU
         // ("exact_fft": k_blind_rotate_x1 holds 8 gates per CU too; k_blind_rotate_w2, 2 waves per gate and 35.8 KB of LDS, 4 per CU)
-        resident_gates_ = 8 * cus;
-        d_->one_limb_min = cus + 1;  // everything the latency kernel does not take
-        d_->four_wave_max = 2 * cus;
-        d_->two_wave_max = 5 * cus;  // measured crossover with one wave per gate: 1 216 gates 8.6 against 10.0 ms, 1 400 gates 10.8 against 10.1
-        if (const char* e = getenv("IEACHE_TWO_WAVE_MAX")) d_->two_wave_max = atoll(e);
-        if (const char* e = getenv("IEACHE_BR_WIDE_MAX")) d_->br_wide_max = atoll(e);
-        if (const char* e = getenv("IEACHE_ONE_LIMB_MIN")) d_->one_limb_min = atoll(e);
-        if (const char* e = getenv("IEACHE_EXACT_FFT")) d_->exact_fft = atoi(e) != 0;
-        if (const char* e = getenv("IEACHE_FFT_AUDIT")) d_->fft_audit = atoi(e) > 0 ? atoi(e) : 0;
-        if (!w64::one_limb_supported(p)) d_->exact_fft = true;
-        resident_two_wave_ = 4 * cus;
-        d_->exact_one_wave_min = 4 * cus + 1;  // two-limb launches that do not fit the two-waves-per-gate kernel's 4 gates per CU
-        if (const char* e = getenv("IEACHE_EXACT_ONE_WAVE_MIN")) d_->exact_one_wave_min = atoll(e);
-        if (d_->exact_fft) resident_two_wave_ = 0;  // k_blind_rotate_x1 holds 8 gates per CU, as k_blind_rotate_w1b does
+        o.resident_gates = 8 * cus;
+        o.one_limb_min = cus + 1;  // everything the latency kernel does not take
+        o.four_wave_max = 2 * cus;
+        o.two_wave_max = 5 * cus;  // measured crossover with one wave per gate: 1 216 gates 8.6 against 10.0 ms, 1 400 gates 10.8 against 10.1
+        o.exact_one_wave_min = 4 * cus + 1;  // two-limb launches that do not fit the two-waves-per-gate kernel's 4 gates per CU
+        o.br_variant = w64::default_variant();
+        if (!w64::one_limb_supported(p)) o.exact_fft = 1;
+        options_from_environment(o, [this](const OptionRow& r, int64_t& v) { return option_hook(r, v); });
     }
     d_->p = p;
     DevKeys& K = d_->K;
@@ -739,8 +673,8 @@ void Evaluator::init() {
     for (int32_t j = 0; j < M; j++) tw[j] = make_double2(std::cos(M_PI * j / p.N), std::sin(M_PI * j / p.N));
     for (int32_t j = 0; j < M / 2; j++)
         w[j] = make_double2(std::cos(-2.0 * M_PI * j / M), std::sin(-2.0 * M_PI * j / M));
-    HIP_CHECK(hipMalloc(&d_->twist, sizeof(double2) * tw.size()));
-    HIP_CHECK(hipMalloc(&d_->wtab, sizeof(double2) * w.size()));
+    d_->twist.allocate(tw.size());
+    d_->wtab.allocate(w.size());
     HIP_CHECK(hipMemcpy(d_->twist, tw.data(), sizeof(double2) * tw.size(), hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(d_->wtab, w.data(), sizeof(double2) * w.size(), hipMemcpyHostToDevice));
     K.twist = d_->twist;
@@ -757,11 +691,8 @@ void Evaluator::init() {
         const int nvec = K.stride / 4, nld = (nvec + 63) / 64;
         d_->ksv_lds = (size_t)(p.N + 4) * 4 + (size_t)p.N * p.ks_t * 4 + (size_t)8 * K.stride * 4;
         d_->ks_batch_ok = K.ks_base == 4 && p.ks_t * p.ks_basebit <= 16 && p.ks_t % 4 == 0 && nld <= 4;
-        if (const char* e = getenv("IEACHE_KS_BATCH_MIN")) d_->ks_batch_min = atoll(e);
         d_->ks_sliced_ok = kss::supported(p) && nld <= 4;
-        if (const char* e = getenv("IEACHE_KS_SLICED_MIN")) d_->ks_sliced_min = atoll(e);
         d_->ks_mfma_ok = ksm::supported(p);
-        if (const char* e = getenv("IEACHE_KS_MFMA_MIN")) d_->ks_mfma_min = atoll(e);
         if (d_->ks_batch_ok)
             dev::allow_dynamic_lds((const void*)k_keyswitch_batch<16>, (size_t)16 * p.N * 2 + 64, "k_keyswitch_batch");
         if (nld <= 4 && d_->ksv_lds <= 160 * 1024) {
@@ -775,45 +706,15 @@ void Evaluator::init() {
 
 Evaluator::~Evaluator() { destroy(); }
 
+// Every stream idle, then Impl's members release what they own.
 void Evaluator::destroy() {
     if (!d_) return;
     (void)hipSetDevice(device_);
-    for (int k = 1; k < kMaxLanes; k++)
+    for (int k = kMaxLanes - 1; k >= 0; k--)
         if (d_->lane[k].stream) (void)hipStreamSynchronize(d_->lane[k].stream);
-    if (stream_) (void)hipStreamSynchronize(stream_);
-    (void)hipFree(d_->bkf);
-    (void)hipFree(d_->bkf_w64);
-    (void)hipFree(d_->tw_w64);
-    (void)hipFree(d_->bkf1_w64);
-    (void)hipFree(d_->fft_guard);
-    (void)hipFree(d_->ksk);
-    (void)hipFree(d_->ks_limbs);
-    (void)hipFree(d_->twist);
-    (void)hipFree(d_->wtab);
-    for (Lane& ln : d_->lane) {
-        (void)hipFree(ln.ext);
-        (void)hipFree(ln.comb);
-        (void)hipFree(ln.br_state);
-        (void)hipFree(ln.ks_digits);
-        (void)hipFree(ln.audit_ext);
-        (void)hipFree(ln.audit_state);
-    }
-    (void)hipFree(d_->ext_mux);
-    for (Torus32* st : d_->stage) (void)hipFree(st);
-    if (d_->ev_fork) (void)hipEventDestroy(d_->ev_fork);
-    for (int k = 0; k < kMaxLanes; k++)
-        if (d_->ev_mix[k]) (void)hipEventDestroy(d_->ev_mix[k]);
-    for (int k = 1; k < kMaxLanes; k++) {
-        if (d_->ev_join[k]) (void)hipEventDestroy(d_->ev_join[k]);
-        if (d_->lane[k].stream) (void)hipStreamDestroy(d_->lane[k].stream);
-    }
-    (void)hipFree(d_->store);
-    (void)hipFree(d_->d_gates);
-    (void)hipFree(d_->d_outs);
-    if (stream_) (void)hipStreamDestroy(stream_);
-    stream_ = nullptr;
     delete d_;
     d_ = nullptr;
+    stream_ = nullptr;
 }
 
 void Evaluator::wait_for_stream(hipStream_t producer) {
@@ -835,179 +736,74 @@ Torus32* Evaluator::staging(int slot, size_t bytes) {
     if (slot < 0 || slot >= 4) throw std::invalid_argument("staging slot");
     HIP_CHECK(hipSetDevice(device_));
     bytes = (bytes + 255) & ~(size_t)255;
-    if (d_->stage_bytes[slot] < bytes || !d_->stage[slot]) {
-        const size_t want = std::max(bytes, std::min<size_t>(2 * d_->stage_bytes[slot], (size_t)1 << 30));
-        if (d_->stage[slot]) HIP_CHECK(hipFree(d_->stage[slot]));
-        d_->stage[slot] = nullptr;
-        d_->stage_bytes[slot] = 0;
-        HIP_CHECK(hipMalloc(&d_->stage[slot], want + 16));
-        HIP_CHECK(hipMemset(d_->stage[slot], 0, want + 16));
-        d_->stage_bytes[slot] = want;
-        d_->stage_allocs++;
+    DeviceBuffer<Torus32>& st = d_->stage[slot];
+    if (st.items() < bytes || !st) {
+        st.allocate(std::max(bytes, std::min<size_t>(2 * st.items(), (size_t)1 << 30)), 1, /*slack=*/16, /*zero=*/true);
+        d_->opt.staging_allocations++;
     }
-    return d_->stage[slot];
+    return st;
 }
 
-void Evaluator::set_chunk(size_t items) {
-    if (items < 1) items = 1;
-    d_->chunk = items;
-}
+int Evaluator::resident_gates() const { return (int)d_->opt.resident_gates; }
+int Evaluator::resident_gates_two_wave() const { return d_->opt.exact_fft ? 0 : 4 * (int)d_->opt.cus; }
+void Evaluator::set_force_generic(bool v) { d_->opt.force_generic = v; }
+void Evaluator::set_chunk(size_t items) { d_->opt.chunk = items < 1 ? 1 : (int64_t)items; }
 
-bool Evaluator::set_option(const std::string& name, int64_t value) {
-    if (name == "chunk" && value >= 1) {
-        set_chunk((size_t)value);
-    } else if (name == "force_generic") {
-        force_generic_ = value != 0;
-    } else if (name == "ks_batch_min" && value >= 0) {
-        d_->ks_batch_min = value;
-    } else if (name == "ks_sliced_min" && value >= 0) {
-        d_->ks_sliced_min = value;
-    } else if (name == "ks_slice" && value >= 0 && value <= kss::max_slice()) {
-        d_->ks_slice = (int32_t)value;
-    } else if (name == "ks_gates" && (value == 0 || value == 4 || value == 8 || value == 16 || value == 32)) {
-        d_->ks_gates = (int32_t)value;
-    } else if (name == "ks_mfma_min" && value >= 0) {
-        d_->ks_mfma_min = value;
-    } else if (name == "ks_mfma_split" && value >= 0 && value <= 64 && (value & (value - 1)) == 0 &&
-               (value == 0 || ksm::split_ok(p_, (int32_t)value))) {  // 0 = by launch size; else a power of two every split of which holds whole loop trips
-        d_->ks_mfma_split = (int32_t)value;
-    } else if (name == "ks_split_max" && value >= 1 && value <= 64) {
-        d_->ks_split_max = (int32_t)value;
-    } else if (name == "br_mix" && (value == 0 || value == 1)) {
-        d_->br_mix = (int32_t)value;
-    } else if (name == "mix_s1" && value >= 1 && value <= 630) {
-        d_->mix_s1 = (int32_t)value;
-    } else if (name == "mix_ratio" && value >= 100 && value <= 400) {
-        d_->mix_ratio = (int32_t)value;
-    } else if (name == "mix_k" && value >= 0 && value <= kMaxLanes && value != 1) {
-        d_->mix_k = (int32_t)value;
-    } else if (name == "mix_tw" && value >= 0 && value < kMaxLanes) {
-        d_->mix_tw = (int32_t)value;
-    } else if (name == "mix_wg" && value >= 1 && value <= 4) {
-        d_->mix_wg = (int32_t)value;
-    } else if (name == "mix_sync" && (value == 0 || value == 1)) {
-        d_->mix_sync = (int32_t)value;
-    } else if (name == "wg_gates" && value >= 0 && value <= 4) {
-        d_->wg_gates = (int32_t)value;
-    } else if (name == "wg3_max" && value >= 0) {
-        d_->wg3_max = value;
-    } else if (name == "overlap" && (value == 0 || value == 1)) {
-        d_->overlap = (int32_t)value;
-    } else if (name == "overlap_min" && value >= 2) {
-        d_->overlap_min = value;
-    } else if (name == "pipe_min" && value >= 0) {
-        d_->pipe_min = value;
-    } else if (name == "pipe_auto" && (value == 0 || value == 1)) {
-        d_->pipe_auto = (int32_t)value;
-    } else if (name == "pipe_lanes" && value >= 2 && value <= kMaxLanes) {
-        d_->pipe_lanes = (int32_t)value;
-    } else if (name == "br_wide_max" && value >= 0) {
-        d_->br_wide_max = value;
-    } else if (name == "br_slice" && value >= 0 && value <= 4096) {  // 0 = by kernel and launch size
-        d_->br_slice = (int32_t)value;
-    } else if (name == "br_variant" && value >= 0 && value <= 1000 && w64::variant_known((int32_t)value)) {
-        d_->br_variant = (int32_t)value;
-    } else if (name == "exact_fft" && (value == 1 || (value == 0 && w64::one_limb_supported(p_)))) {
-        d_->exact_fft = value != 0;
-        resident_two_wave_ = d_->exact_fft ? 0 : 4 * d_->cus;
-    } else if (name == "one_limb_min" && value >= 0) {
-        d_->one_limb_min = value;
-    } else if (name == "exact_one_wave_min" && value >= 0) {
-        d_->exact_one_wave_min = value;
-    } else if (name == "two_wave_max" && value >= 0) {
-        d_->two_wave_max = value;
-    } else if (name == "four_wave_max" && value >= 0) {
-        d_->four_wave_max = value;
-
-    } else if (name == "fft_audit" && value >= 0 && value <= (1 << 30)) {
-        d_->fft_audit = (int32_t)value;
-    } else if (name == "fft_audit_inject" && value == 1) {
-        d_->audit_inject = true;
-    } else if (name == "fft_guard_inject" && value == 1 && d_->fft_guard) {
-        // test hook: the next call finds the guard tripped and repeats itself on the two-limb kernel
+// What a row of the option table cannot say: conditions that need the parameter set or the device, and effects beyond
+// storing the value.
+bool Evaluator::option_hook(const OptionRow& r, int64_t& v) {
+    if (r.at == &EvalOptions::force_generic) v = v != 0;
+    if (r.at == &EvalOptions::ks_mfma_split) return v == 0 || ksm::split_ok(p_, (int32_t)v);  // every split holds whole loop trips
+    if (r.at == &EvalOptions::br_variant) return w64::variant_known((int32_t)v);
+    if (r.at == &EvalOptions::exact_fft) return v == 1 || w64::one_limb_supported(p_);
+    if (r.at == &EvalOptions::fft_guard_inject) {
+        if (!d_->fft_guard) return false;
         const unsigned one = 1;
         HIP_CHECK(hipSetDevice(device_));
         HIP_CHECK(hipMemcpy(d_->fft_guard, &one, sizeof one, hipMemcpyHostToDevice));
-    } else {
-        return false;
     }
+    return true;
+}
+
+bool Evaluator::set_option(const std::string& name, int64_t value) {
+    const OptionRow* r = find_option(name.c_str());
+    if (!r || !option_set(d_->opt, *r, value, [this](const OptionRow& row, int64_t& v) { return option_hook(row, v); })) return false;
     d_->tuned.clear();  // whatever was timed was timed under the old options
     return true;
 }
 
 bool Evaluator::get_option(const std::string& name, int64_t* value) const {
-    int64_t v;
-    if (name == "overlap") v = d_->overlap;
-    else if (name == "overlap_min") v = d_->overlap_min;
-    else if (name == "overlapped_levels") v = d_->overlapped_levels;  // levels issued on two streams so far (a counter)
-    else if (name == "pipe_min") v = d_->pipe_min;
-    else if (name == "pipe_lanes") v = d_->pipe_lanes;
-    else if (name == "pipe_auto") v = d_->pipe_auto;
-    else if (name == "tuned_evals") v = d_->tuned_evals;  // evaluations that were one of the two timed trials of a (circuit, batch)
-    else if (name == "pipelined_evals") v = d_->pipelined_evals;      // circuit evaluations run as two expression-half pipelines so far
-    else if (name == "br_mix") v = d_->br_mix;
-    else if (name == "mix_s1") v = d_->mix_s1;
-    else if (name == "mix_ratio") v = d_->mix_ratio;
-    else if (name == "mix_sync") v = d_->mix_sync;
-    else if (name == "mix_wg") v = d_->mix_wg;
-    else if (name == "mix_k") v = d_->mix_k;
-    else if (name == "mix_tw") v = d_->mix_tw;
-    else if (name == "mixed_launches") v = d_->mixed_launches;  // (level, piece) launches run as a rotation of roles so far
-    else if (name == "wg_gates") v = d_->wg_gates;
-    else if (name == "wg3_max") v = d_->wg3_max;
-    else if (name == "staging_allocations") v = d_->stage_allocs;  // (re)allocations of the host entry points' staging rows so far
-    else if (name == "cus") v = d_->cus;
-    else if (name == "chunk") v = (int64_t)d_->chunk;
-    else if (name == "resident_gates") v = resident_gates_;
-    else if (name == "exact_fft") v = d_->exact_fft ? 1 : 0;
-    else if (name == "exact_one_wave_min") v = d_->exact_one_wave_min;
-    else if (name == "one_limb_min") v = d_->one_limb_min;
-    else if (name == "two_wave_max") v = d_->two_wave_max;
-    else if (name == "four_wave_max") v = d_->four_wave_max;
-    else if (name == "br_wide_max") v = d_->br_wide_max;
-    else if (name == "br_variant") v = d_->br_variant;
-    else if (name == "br_slice") v = d_->br_slice;
-    else if (name == "fft_audit") v = d_->fft_audit;
-    else if (name == "ks_mfma_min") v = d_->ks_mfma_min;
-    else if (name == "ks_mfma_split") v = d_->ks_mfma_split;
-    else return false;
-    if (value) *value = v;
+    const OptionRow* r = find_option(name.c_str());
+    if (!r) return false;
+    if (value) *value = d_->opt.*r->at;
     return true;
 }
 
 std::string Evaluator::kernel_variant() const {
-    if (!w64::supported(p_) || force_generic_) return "generic-radix2";
+    if (!w64::supported(p_) || d_->opt.force_generic) return "generic-radix2";
     // the kernel wide launches take: one wave per gate, on the one-limb spectrum or ("exact_fft") on the two-limb one
-    return d_->exact_fft ? "x1x64-radix8-twolimb" : "w1x64-radix8-onelimb";
+    return d_->opt.exact_fft ? "x1x64-radix8-twolimb" : "w1x64-radix8-onelimb";
 }
 
 void Evaluator::load_keys_host(const Torus32* bk, const Torus32* ksk) {
     HIP_CHECK(hipSetDevice(device_));
-    Torus32 *d_bk = nullptr, *d_ksk = nullptr;
-    HIP_CHECK(hipMalloc(&d_bk, p_.bk_count() * 4));
-    HIP_CHECK(hipMalloc(&d_ksk, p_.ksk_count() * 4));
+    DeviceBuffer<Torus32> d_bk, d_ksk;
+    d_bk.allocate(p_.bk_count());
+    d_ksk.allocate(p_.ksk_count());
     HIP_CHECK(hipMemcpy(d_bk, bk, p_.bk_count() * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(d_ksk, ksk, p_.ksk_count() * 4, hipMemcpyHostToDevice));
-    try {
-        load_keys_device(d_bk, d_ksk);
-    } catch (...) {
-        (void)hipFree(d_bk);
-        (void)hipFree(d_ksk);
-        throw;
-    }
-    HIP_CHECK(hipFree(d_bk));
-    HIP_CHECK(hipFree(d_ksk));
+    load_keys_device(d_bk, d_ksk);
 }
 
 void Evaluator::load_keys_device(const Torus32* d_bk, const Torus32* d_ksk) {
     HIP_CHECK(hipSetDevice(device_));
     DevKeys& K = d_->K;
     const size_t npoly = (size_t)p_.n * K.kpl * 2;
-    if (!d_->bkf) HIP_CHECK(hipMalloc(&d_->bkf, npoly * 2 * K.M * sizeof(double2)));
+    if (!d_->bkf) d_->bkf.allocate(npoly * 2 * K.M);
     const size_t ks_rows = (size_t)p_.k * p_.N * p_.ks_t * K.ks_base;
     if (!d_->ksk) {
         // 16 rows of slack: the sliced key switch prefetches four positions past the end of its walk
-        HIP_CHECK(hipMalloc(&d_->ksk, (ks_rows + 16) * K.stride * 4));
+        d_->ksk.allocate((ks_rows + 16) * K.stride);
         HIP_CHECK(hipMemsetAsync(d_->ksk + ks_rows * K.stride, 0, (size_t)16 * K.stride * 4, stream_));
     }
     K.bkf = d_->bkf;
@@ -1016,17 +812,17 @@ void Evaluator::load_keys_device(const Torus32* d_bk, const Torus32* d_ksk) {
                        d_bk, d_->bkf);
     HIP_CHECK(hipGetLastError());
     if (w64::supported(p_)) {
-        if (!d_->bkf_w64) HIP_CHECK(hipMalloc(&d_->bkf_w64, w64::spectrum_elems(p_) * sizeof(double2)));
+        if (!d_->bkf_w64) d_->bkf_w64.allocate(w64::spectrum_elems(p_));
         if (!d_->tw_w64) {
-            HIP_CHECK(hipMalloc(&d_->tw_w64, w64::twiddle_table_elems() * sizeof(double2)));
+            d_->tw_w64.allocate(w64::twiddle_table_elems());
             w64::build_twiddle_table(d_->tw_w64, stream_);
             HIP_CHECK(hipGetLastError());
         }
         w64::prepare_spectrum(p_, d_bk, d_->bkf_w64, stream_);
         HIP_CHECK(hipGetLastError());
-        if (!d_->bkf1_w64) HIP_CHECK(hipMalloc(&d_->bkf1_w64, w64::spectrum1_elems(p_) * sizeof(double2)));
+        if (!d_->bkf1_w64) d_->bkf1_w64.allocate(w64::spectrum1_elems(p_));
         if (!d_->fft_guard) {
-            HIP_CHECK(hipMalloc(&d_->fft_guard, 4 * sizeof(unsigned)));
+            d_->fft_guard.allocate(4);
             HIP_CHECK(hipMemsetAsync(d_->fft_guard, 0, 4 * sizeof(unsigned), stream_));
         }
         w64::prepare_spectrum1(p_, d_bk, d_->bkf1_w64, stream_);
@@ -1036,7 +832,7 @@ void Evaluator::load_keys_device(const Torus32* d_bk, const Torus32* d_ksk) {
                        K.stride);
     HIP_CHECK(hipGetLastError());
     if (d_->ks_mfma_ok) {
-        if (!d_->ks_limbs) HIP_CHECK(hipMalloc(&d_->ks_limbs, ksm::limb_matrix_bytes(p_)));
+        if (!d_->ks_limbs) d_->ks_limbs.allocate(ksm::limb_matrix_bytes(p_));
         ksm::prepare(p_, d_->ksk, d_->ks_limbs, stream_);
         HIP_CHECK(hipGetLastError());
     }
@@ -1088,38 +884,45 @@ struct Timer {
         return tot;
     }
 };
+// the three timers of a call, folded into its statistics once the stream is idle
+void add_times(EvalStats* stats, Timer& tall, Timer& tbr, Timer& tks) {
+    if (!stats) return;
+    stats->total_ms += tall.sum_ms();
+    stats->blind_rotate_ms += tbr.sum_ms();
+    stats->keyswitch_ms += tks.sum_ms();
+}
 }  // namespace
 
 // Which blind-rotation kernel a launch of `cnt` gate instances takes (br_variant 0 = by launch size: the 2L-waves-per-gate
 // kernel for a handful of gates, two waves per gate on the one-limb spectrum while every gate is resident at once, one wave
 // per gate above; "exact_fft" / a repeat after a guard trip: the two-limb kernels).
 static void pick_br_variant(const Params& p, const Evaluator::Impl* d, int64_t cnt, int32_t* variant_out, int32_t* slice_out) {
-    int32_t variant = d->br_variant, slice = d->br_slice;
+    int32_t variant = d->opt.br_variant, slice = d->opt.br_slice;
     cnt *= d->concurrency;  // the other stream's launch of the same level shares the chip: choose by the gates in flight
     if (variant == 0) {
-        if (cnt <= d->br_wide_max) {
+        if (cnt <= d->opt.br_wide_max) {
             // the latency kernel, on the one-limb spectrum unless exactness by construction is asked for
-            variant = (d->exact_fft || d->exact_once) ? w64::kVariantWide : w64::kVariantWideHandoverOneLimb;
+            variant = (d->opt.exact_fft || d->exact_once) ? w64::kVariantWide : w64::kVariantWideHandoverOneLimb;
             slice = w64::bara_stride(p);
-        } else if (!d->exact_fft && !d->exact_once && cnt >= d->one_limb_min) {
+        } else if (!d->opt.exact_fft && !d->exact_once && cnt >= d->opt.one_limb_min) {
             // one to two gates per CU: four waves per gate (two waves per SIMD); while every gate fits a two-wave slot, two
             // waves per gate finish a step sooner than one
-            variant = cnt <= d->four_wave_max ? w64::kVariantOneLimbFourWaves
-                      : cnt <= d->two_wave_max ? w64::kVariantOneLimbTwoWaves : w64::kVariantOneLimbDefault;
+            variant = cnt <= d->opt.four_wave_max ? w64::kVariantOneLimbFourWaves
+                      : cnt <= d->opt.two_wave_max ? w64::kVariantOneLimbTwoWaves : w64::kVariantOneLimbDefault;
             // every gate of such a launch is resident at once, so nothing is gained from short slices (they keep the rounds
             // of a WIDE launch on the same BK blocks) and each launch boundary costs a tail and a reload of the accumulators:
             // the whole rotation in one launch for four waves per gate, 64 steps for two (interleaved A/B, profiles/r3_slice_ab.txt)
             // (likewise one wave per gate while the launch is a single round of 8 gates per CU)
             if (slice <= 0)
                 slice = variant == w64::kVariantOneLimbFourWaves ? w64::bara_stride(p)
-                        : (variant == w64::kVariantOneLimbTwoWaves || cnt <= 8 * (int64_t)d->cus) ? 64 : slice;
+                        : (variant == w64::kVariantOneLimbTwoWaves || cnt <= 8 * (int64_t)d->opt.cus) ? 64 : slice;
         }
-        else if (cnt >= d->exact_one_wave_min) {
+        else if (cnt >= d->opt.exact_one_wave_min) {
             variant = w64::kVariantExactOneWave;  // "exact_fft" / a repeat: the two-limb product, one wave per gate
-            if (slice <= 0 && cnt <= 8 * (int64_t)d->cus) slice = 64;  // a single round of resident gates: as above
+            if (slice <= 0 && cnt <= 8 * (int64_t)d->opt.cus) slice = 64;  // a single round of resident gates: as above
         }
     } else if (d->exact_once && w64::variant_one_limb(variant)) {
-        variant = cnt >= d->exact_one_wave_min ? w64::kVariantExactOneWave : 0;
+        variant = cnt >= d->opt.exact_one_wave_min ? w64::kVariantExactOneWave : 0;
     }
     *variant_out = variant;
     *slice_out = slice;
@@ -1129,11 +932,81 @@ static void pick_br_variant(const Params& p, const Evaluator::Impl* d, int64_t c
 // two such workgroups fill a CU; a launch of at most six gates per CU in fours leaves half the CUs with two workgroups and
 // half with one, in threes every CU gets the same six waves.
 static int pick_wg_gates(const Evaluator::Impl* d, int64_t cnt) {
-    if (d->wg_gates) return d->wg_gates;
-    return cnt * d->concurrency <= d->wg3_max ? 3 : 4;
+    if (d->opt.wg_gates) return d->opt.wg_gates;
+    return cnt * d->concurrency <= d->opt.wg3_max ? 3 : 4;
 }
 
-static bool mix_geometry(const Evaluator::Impl* d, int64_t cnt, int32_t variant, int* k_out, int* tw_out);
+// Whether a launch of `cnt` gate instances runs as a rotation of roles (w64::MixPlan), and with which geometry.  Only where it
+// can pay: the kernels chosen by launch size (br_variant 0) on the one-limb spectrum, the launch alone on the chip (no other
+// stream of this context at work), a whole rotation, and a size mix_plan.h names: 4 .. 7 gates per CU, or a full round of the
+// one-wave kernel plus a small remainder (8 .. 10.5 per CU).
+// -> false, or the geometry (k subsets, tw of them on two waves at a time) a launch of cnt gate instances takes
+static bool mix_geometry(const Evaluator::Impl* d, int64_t cnt, int32_t variant, int* k_out, int* tw_out) {
+    if (!d->opt.overlap || !d->opt.br_mix || d->opt.br_variant != 0 || d->concurrency != 1 || d->level_on_two_lanes || d->opt.exact_fft || d->exact_once) return false;
+    if (!d->use_w64 || !w64::variant_one_limb(variant)) return false;
+    MixGeometry g;  // mix_plan.h: "mix_k" / "mix_tw" force a geometry (measurement aid), 0 = by launch size
+    if (!mix_geometry_for(d->opt.cus, cnt, d->opt.mix_k, d->opt.mix_tw, &g) || g.k > kMaxLanes) return false;
+    *k_out = g.k;
+    *tw_out = g.tw;
+    return true;
+}
+// streams and join events of lanes 1 .. lanes-1, and the fork event
+static void ensure_lanes(Evaluator::Impl* d, int lanes) {
+    d->ev_fork.ensure();
+    for (int k = 1; k < lanes; k++) {
+        d->lane[k].stream.ensure();
+        d->lane[k].ev_join.ensure();
+    }
+}
+// Fork: lanes 1 .. lanes-1 start when everything queued so far on lane 0 is done (lanes < 2: nothing happens, here or
+// later); join(): lane 0 waits for all of them.  A Fork that goes without having been joined -- an exception is on its way
+// out -- waits on the host for the lanes it forked, so that nothing of the failed call is still queued on them, writing the
+// wire store or their scratch, when the caller goes on using the context.
+struct Fork {
+    Evaluator::Impl* d;
+    int lanes;
+    bool joined = false;
+    Fork(Evaluator::Impl* d_, int lanes_) : d(d_), lanes(lanes_) {
+        if (lanes < 2) return;
+        HIP_CHECK(hipEventRecord(d->ev_fork, d->lane[0].stream));
+        for (int k = 1; k < lanes; k++) HIP_CHECK(hipStreamWaitEvent(d->lane[k].stream, d->ev_fork, 0));
+    }
+    Fork(const Fork&) = delete;
+    Fork& operator=(const Fork&) = delete;
+    void join() {
+        for (int k = 1; k < lanes; k++) {
+            HIP_CHECK(hipEventRecord(d->lane[k].ev_join, d->lane[k].stream));
+            HIP_CHECK(hipStreamWaitEvent(d->lane[0].stream, d->lane[k].ev_join, 0));
+        }
+        joined = true;
+    }
+    ~Fork() {
+        for (int k = 1; k < lanes && !joined; k++) (void)hipStreamSynchronize(d->lane[k].stream);
+    }
+};
+
+static bool plan_mix(const Params& p, Evaluator::Impl* d, Lane& ln, int64_t cnt, int32_t variant, int32_t steps, w64::MixPlan* mix) {
+    MixGeometry g;
+    if (steps >= 0 || &ln != &d->lane[0] || !mix_geometry(d, cnt, variant, &g.k, &g.tw)) return false;
+    MixSteps m;
+    if (!mix_steps_for(p.n, g, d->opt.mix_s1, d->opt.mix_ratio, &m)) return false;
+    ensure_lanes(d, g.k);
+    for (int j = 0; j < g.k; j++) d->lane[j].ev_mix.ensure();
+    mix->k = g.k;
+    mix->tw = g.tw;
+    mix->s1 = m.s1;
+    mix->s2 = m.s2;
+    mix->cycles = m.cycles;
+    mix->tail_s1 = m.tail_s1;
+    mix->tail_s2 = m.tail_s2;
+    mix->sync = d->opt.mix_sync != 0;
+    mix->wg = d->opt.mix_wg;
+    for (int j = 0; j < g.k; j++) {
+        mix->streams[j] = d->lane[j].stream;
+        mix->ev[j] = d->lane[j].ev_mix;
+    }
+    return true;
+}
 
 std::string Evaluator::kernel_for_launch(int64_t gates) const {
     if (!d_->use_w64) return "k_blind_rotate_generic";
@@ -1157,50 +1030,9 @@ std::string Evaluator::kernel_for_launch(int64_t gates) const {
     return name + tag;
 }
 
-// Scratch sized by what calls have needed so far, not by the largest chunk a launch may take (65 536 gate instances are
-// ~1 GB of accumulators, extracted samples and key-switch digits): at least `need` (<= cap) items, doubling from 4 096 so
-// that a run of growing batches does not reallocate every time.
-static size_t grown(size_t have, size_t need, size_t cap) {
-    return std::max(need, std::min(std::max(cap, need), std::max<size_t>(2 * have, 4096)));
-}
-
-// Whether a launch of `cnt` gate instances runs as a rotation of roles (w64::MixPlan), and with which geometry.  Only where it
-// can pay: the kernels chosen by launch size (br_variant 0) on the one-limb spectrum, the launch alone on the chip (no other
-// stream of this context at work), a whole rotation, and a size mix_plan.h names: 4 .. 7 gates per CU, or a full round of the
-// one-wave kernel plus a small remainder (8 .. 10.5 per CU).
-static void ensure_lanes(Evaluator::Impl* d, int lanes);
-// -> false, or the geometry (k subsets, tw of them on two waves at a time) a launch of cnt gate instances takes
-static bool mix_geometry(const Evaluator::Impl* d, int64_t cnt, int32_t variant, int* k_out, int* tw_out) {
-    if (!d->overlap || !d->br_mix || d->br_variant != 0 || d->concurrency != 1 || d->level_on_two_lanes || d->exact_fft || d->exact_once) return false;
-    if (!d->use_w64 || !w64::variant_one_limb(variant)) return false;
-    MixGeometry g;  // mix_plan.h: "mix_k" / "mix_tw" force a geometry (measurement aid), 0 = by launch size
-    if (!mix_geometry_for(d->cus, cnt, d->mix_k, d->mix_tw, &g) || g.k > kMaxLanes) return false;
-    *k_out = g.k;
-    *tw_out = g.tw;
-    return true;
-}
-static bool plan_mix(const Params& p, Evaluator::Impl* d, Lane& ln, int64_t cnt, int32_t variant, int32_t steps, w64::MixPlan* mix) {
-    MixGeometry g;
-    if (steps >= 0 || &ln != &d->lane[0] || !mix_geometry(d, cnt, variant, &g.k, &g.tw)) return false;
-    MixSteps m;
-    if (!mix_steps_for(p.n, g, d->mix_s1, d->mix_ratio, &m)) return false;
-    ensure_lanes(d, g.k);
-    for (int j = 0; j < g.k; j++)
-        if (!d->ev_mix[j]) HIP_CHECK(hipEventCreateWithFlags(&d->ev_mix[j], hipEventDisableTiming));
-    mix->k = g.k;
-    mix->tw = g.tw;
-    mix->s1 = m.s1;
-    mix->s2 = m.s2;
-    mix->cycles = m.cycles;
-    mix->tail_s1 = m.tail_s1;
-    mix->tail_s2 = m.tail_s2;
-    mix->sync = d->mix_sync != 0;
-    mix->wg = d->mix_wg;
-    for (int j = 0; j < g.k; j++) {
-        mix->streams[j] = d->lane[j].stream;
-        mix->ev[j] = d->ev_mix[j];
-    }
-    return true;
+// blind-rotation state of the specialised kernels for launches of up to `need` items on this lane
+static void reserve_br_state(const Params& p, Evaluator::Impl* d, Lane& ln, size_t need) {
+    if (d->use_w64) ln.br_state.reserve(need, (size_t)d->opt.chunk, w64::state_bytes_per_item(p));
 }
 
 // Runs `items` gate instances described by W (item0 is advanced per chunk).
@@ -1208,19 +1040,12 @@ static int launch_blind_rotate(const Params& p, Evaluator::Impl* d, Lane& ln, co
                                 Torus32* ext, int32_t steps, Torus32* dbg_acc) {
     hipStream_t stream = ln.stream;
     if (d->use_w64) {
-        if (ln.br_state_items < (size_t)cnt) {
-            if (ln.br_state) HIP_CHECK(hipFree(ln.br_state));
-            ln.br_state = nullptr;
-            const size_t items = grown(ln.br_state_items, (size_t)cnt, d->chunk);
-            ln.br_state_items = 0;
-            HIP_CHECK(hipMalloc(&ln.br_state, items * w64::state_bytes_per_item(p)));
-            ln.br_state_items = items;
-        }
+        reserve_br_state(p, d, ln, (size_t)cnt);  // in place already unless the caller is not run_items
         int32_t variant, slice;
         pick_br_variant(p, d, cnt, &variant, &slice);
         w64::MixPlan mix;
         const bool mixed = plan_mix(p, d, ln, cnt, variant, steps, &mix);
-        if (mixed) d->mixed_launches++;
+        if (mixed) d->opt.mixed_launches++;
         return w64::launch(p, d->K, d->bkf_w64, d->bkf1_w64, d->fft_guard, w, cnt, ln.br_state, ext, steps, dbg_acc, slice, variant,
                            d->tw_w64, stream, pick_wg_gates(d, cnt), mixed ? &mix : nullptr);
     }
@@ -1239,39 +1064,31 @@ static int launch_blind_rotate(const Params& p, Evaluator::Impl* d, Lane& ln, co
 constexpr int64_t kAuditGates = 64;
 static void maybe_audit(const Params& p, Evaluator::Impl* d, Lane& ln, const WorkDesc& w, int64_t cnt, const Torus32* ext) {
     hipStream_t stream = ln.stream;
-    if (!d->use_w64 || d->fft_audit <= 0 || !d->fft_guard) return;
+    if (!d->use_w64 || d->opt.fft_audit <= 0 || !d->fft_guard) return;
     int32_t variant, slice;
     pick_br_variant(p, d, cnt, &variant, &slice);
     if (!w64::variant_one_limb(variant)) return;  // the launch was exact by construction
-    if (++d->audit_seq % d->fft_audit != 0) return;
+    if (++d->audit_seq % d->opt.fft_audit != 0) return;
     const int64_t m = std::min<int64_t>(kAuditGates, cnt);
     const int64_t off = cnt > m ? (int64_t)(((uint64_t)d->audit_seq * 0x9E3779B97F4A7C15ull >> 33) % (uint64_t)(cnt - m + 1)) : 0;
-    if (!ln.audit_ext) HIP_CHECK(hipMalloc(&ln.audit_ext, (size_t)kAuditGates * (size_t)(d->K.N + 4) * 4));
-    if (!ln.audit_state) HIP_CHECK(hipMalloc(&ln.audit_state, (size_t)kAuditGates * w64::state_bytes_per_item(p)));
+    if (!ln.audit_ext) ln.audit_ext.allocate((size_t)kAuditGates, d->ext_row_bytes());
+    if (!ln.audit_state) ln.audit_state.allocate((size_t)kAuditGates, w64::state_bytes_per_item(p));
     WorkDesc wa = w;
     wa.item0 = w.item0 + off;
     w64::launch(p, d->K, d->bkf_w64, d->bkf1_w64, d->fft_guard, wa, m, ln.audit_state, ln.audit_ext, -1, nullptr, w64::bara_stride(p),
                 w64::kVariantWide, d->tw_w64, stream);
     hipLaunchKernelGGL(k_audit_compare, dim3((unsigned)m), dim3(256), 0, stream, ext + (size_t)off * (size_t)(d->K.N + 4), ln.audit_ext,
-                       d->K.N, d->fft_guard + 2, d->audit_inject ? 1 : 0);
+                       d->K.N, d->fft_guard + 2, d->opt.fft_audit_inject ? 1 : 0);
     HIP_CHECK(hipGetLastError());
-    d->audit_inject = false;
+    d->opt.fft_audit_inject = 0;
     d->audits++;
     d->audit_gates += m;
 }
 
-// digit scratch of the MFMA key switch for launches of up to `cnt` gates (doubling from 4 096 gates' worth, capped at a chunk's)
+// digit scratch of the MFMA key switch for launches of up to `cnt` gates: the grown() policy in bytes
 static void reserve_ks_digits(Evaluator::Impl* d, Lane& ln, int64_t cnt) {
-    const size_t need = ksm::digit_scratch_bytes(d->p, cnt);
-    if (ln.ks_digits_bytes >= need) return;
-    const size_t have = ln.ks_digits_bytes;
-    if (ln.ks_digits) HIP_CHECK(hipFree(ln.ks_digits));
-    ln.ks_digits = nullptr;
-    ln.ks_digits_bytes = 0;
-    const size_t want = std::max(need, std::min(ksm::digit_scratch_bytes(d->p, (int64_t)d->chunk),
-                                                std::max<size_t>(2 * have, ksm::digit_scratch_bytes(d->p, 4096))));
-    HIP_CHECK(hipMalloc(&ln.ks_digits, want));
-    ln.ks_digits_bytes = want;
+    ln.ks_digits.reserve(ksm::digit_scratch_bytes(d->p, cnt), ksm::digit_scratch_bytes(d->p, d->opt.chunk), 1,
+                         ksm::digit_scratch_bytes(d->p, 4096));
 }
 
 static void launch_keyswitch(Evaluator::Impl* d, Lane& ln, const WorkDesc& w, int64_t cnt, const Torus32* ext,
@@ -1280,16 +1097,16 @@ static void launch_keyswitch(Evaluator::Impl* d, Lane& ln, const WorkDesc& w, in
     const DevKeys& K = d->K;
     const dim3 grid((unsigned)cnt), blk(kKsThreads);
     const int nld = force_generic ? 0 : d->ks_nld;
-    if (!force_generic && d->ks_mfma_ok && d->ks_limbs && cnt >= d->ks_mfma_min) {
+    if (!force_generic && d->ks_mfma_ok && d->ks_limbs && cnt >= d->opt.ks_mfma_min) {
         reserve_ks_digits(d, ln, cnt);
-        ksm::launch(d->p, K, w, cnt, ext, flat_out, d->ks_limbs, ln.ks_digits, d->ks_mfma_split, d->cus, stream);
+        ksm::launch(d->p, K, w, cnt, ext, flat_out, d->ks_limbs, ln.ks_digits, d->opt.ks_mfma_split, d->opt.cus, stream);
         return;
     }
-    if (nld > 0 && d->ks_sliced_ok && cnt >= d->ks_sliced_min) {
-        kss::launch(d->p, K, w, cnt, ext, flat_out, d->ks_slice, d->ks_gates, stream);
+    if (nld > 0 && d->ks_sliced_ok && cnt >= d->opt.ks_sliced_min) {
+        kss::launch(d->p, K, w, cnt, ext, flat_out, d->opt.ks_slice, d->opt.ks_gates, stream);
         return;
     }
-    if (nld > 0 && d->ks_batch_ok && cnt >= d->ks_batch_min) {
+    if (nld > 0 && d->ks_batch_ok && cnt >= d->opt.ks_batch_min) {
         constexpr int G = 16;
         const size_t lds = (size_t)G * K.N * 2 + (size_t)G * 4;
         hipLaunchKernelGGL(k_keyswitch_batch<G>, dim3((unsigned)((cnt + G - 1) / G)), dim3(64 * nld), lds, stream, K, w, ext,
@@ -1298,9 +1115,9 @@ static void launch_keyswitch(Evaluator::Impl* d, Lane& ln, const WorkDesc& w, in
     }
     // a handful of gates: cut each gate's walk into `splits` workgroups
     int32_t splits = 1;
-    if (nld > 0 && d->ks_split_max > 1) {
+    if (nld > 0 && d->opt.ks_split_max > 1) {
         // measured: pays while gates x splits stays within ~1.5 workgroups per CU (1-8 gates: 0.18 -> 0.03 ms, 44: 0.09, 256: no gain)
-        while (splits < d->ks_split_max && cnt * splits * 2 <= (3 * (int64_t)d->cus) / 2 && K.N % (splits * 2) == 0) splits *= 2;
+        while (splits < d->opt.ks_split_max && cnt * splits * 2 <= (3 * (int64_t)d->opt.cus) / 2 && K.N % (splits * 2) == 0) splits *= 2;
     }
     dim3 vgrid((unsigned)cnt, (unsigned)splits);
     if (splits > 1) hipLaunchKernelGGL(k_keyswitch_init, grid, dim3(256), 0, stream, K, w, ext, flat_out);
@@ -1321,9 +1138,9 @@ struct LevelPlan {
     int64_t piece;  // gate instances per (blind rotation, key switch) pair of launches at most
 };
 static LevelPlan plan_level(const Evaluator::Impl* d, int64_t items) {
-    const int64_t chunk = (int64_t)d->chunk;
+    const int64_t chunk = (int64_t)d->opt.chunk;
     LevelPlan pl{false, chunk};
-    if (d->overlap && d->use_w64 && d->concurrency == 1 && items >= d->overlap_min && items >= 2) {
+    if (d->opt.overlap && d->use_w64 && d->concurrency == 1 && items >= d->opt.overlap_min && items >= 2) {
         const int64_t half = (((items + 1) / 2) + 3) & ~(int64_t)3;  // whole workgroups of the one-wave-per-gate kernels
         // two lanes only when there are two pieces to give them: up to 4 items the rounded half is the whole level, and a
         // fork would then use a second stream nobody has created (reserve_scratch sees nothing to reserve for it)
@@ -1337,52 +1154,11 @@ static LevelPlan plan_level(const Evaluator::Impl* d, int64_t items) {
 
 // need: rotation items of the lane's widest piece; need_comb: gates of its widest piece of a level with MUX gates (0 = none)
 static void reserve_lane(const Params& p, Evaluator::Impl* d, Lane& ln, size_t need, size_t need_comb = 0) {
-    if (ln.comb_items < need_comb) {
-        const size_t n = grown(ln.comb_items, need_comb, d->chunk);
-        if (ln.comb) HIP_CHECK(hipFree(ln.comb));
-        ln.comb = nullptr;
-        ln.comb_items = 0;
-        HIP_CHECK(hipMalloc(&ln.comb, n * (size_t)(d->K.N + 4) * 4));
-        ln.comb_items = n;
-    }
-    if (ln.ext_items < need) {
-        const size_t n = grown(ln.ext_items, need, d->chunk);
-        if (ln.ext) HIP_CHECK(hipFree(ln.ext));
-        ln.ext = nullptr;
-        ln.ext_items = 0;
-        HIP_CHECK(hipMalloc(&ln.ext, n * (size_t)(d->K.N + 4) * 4));
-        ln.ext_items = n;
-    }
-    if (d->use_w64 && ln.br_state_items < need) {
-        const size_t n = grown(ln.br_state_items, need, d->chunk);
-        if (ln.br_state) HIP_CHECK(hipFree(ln.br_state));
-        ln.br_state = nullptr;
-        ln.br_state_items = 0;
-        HIP_CHECK(hipMalloc(&ln.br_state, n * w64::state_bytes_per_item(p)));
-        ln.br_state_items = n;
-    }
+    ln.comb.reserve(need_comb, (size_t)d->opt.chunk, d->ext_row_bytes());
+    ln.ext.reserve(need, (size_t)d->opt.chunk, d->ext_row_bytes());
+    reserve_br_state(p, d, ln, need);
     // the MFMA key switch's digit scratch for the widest launch that will take it
-    if (!d->force_generic_ks && d->ks_mfma_ok && d->ks_limbs && (int64_t)need >= d->ks_mfma_min) reserve_ks_digits(d, ln, (int64_t)need);
-}
-
-static void ensure_lanes(Evaluator::Impl* d, int lanes) {
-    if (!d->ev_fork) HIP_CHECK(hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming));
-    for (int k = 1; k < lanes; k++) {
-        if (!d->lane[k].stream) HIP_CHECK(hipStreamCreateWithFlags(&d->lane[k].stream, hipStreamNonBlocking));
-        if (!d->ev_join[k]) HIP_CHECK(hipEventCreateWithFlags(&d->ev_join[k], hipEventDisableTiming));
-    }
-}
-static void ensure_second_lane(Evaluator::Impl* d) { ensure_lanes(d, 2); }
-// fork: lanes 1 .. lanes-1 start when everything queued so far on lane 0 is done; join: lane 0 waits for all of them
-static void fork_lanes(Evaluator::Impl* d, int lanes) {
-    HIP_CHECK(hipEventRecord(d->ev_fork, d->lane[0].stream));
-    for (int k = 1; k < lanes; k++) HIP_CHECK(hipStreamWaitEvent(d->lane[k].stream, d->ev_fork, 0));
-}
-static void join_lanes(Evaluator::Impl* d, int lanes) {
-    for (int k = 1; k < lanes; k++) {
-        HIP_CHECK(hipEventRecord(d->ev_join[k], d->lane[k].stream));
-        HIP_CHECK(hipStreamWaitEvent(d->lane[0].stream, d->ev_join[k], 0));
-    }
+    if (!d->force_generic_ks && d->ks_mfma_ok && d->ks_limbs && (int64_t)need >= d->opt.ks_mfma_min) reserve_ks_digits(d, ln, (int64_t)need);
 }
 
 // Before an evaluation starts: scratch for its widest launch in one go (the per-launch checks below then find it in place),
@@ -1409,7 +1185,7 @@ static void reserve_scratch(const Params& p, Evaluator::Impl* d, const int64_t* 
     }
     reserve_lane(p, d, d->lane[0], need0, comb0);
     if (need1) {
-        ensure_second_lane(d);
+        ensure_lanes(d, 2);
         reserve_lane(p, d, d->lane[1], need1, comb1);
     }
 }
@@ -1434,24 +1210,22 @@ static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t i
     const int64_t gates = mux ? items / (W.ng + W.nm) * W.ng : items;  // gate instances of the level
     if (fixed_lane >= 0) {
         pl.two_lanes = false;
-        pl.piece = (int64_t)d->chunk;
+        pl.piece = (int64_t)d->opt.chunk;
         const size_t need = (size_t)std::min<int64_t>(pl.piece + (mux ? 1 : 0), std::max<int64_t>(items, 1));
         reserve_lane(p, d, d->lane[fixed_lane], need, mux ? std::min<size_t>(need, (size_t)gates) : 0);
     } else {
         reserve_scratch(p, d, &items, 1, mux ? &gates : nullptr);
     }
-    if (pl.two_lanes) {
-        fork_lanes(d, 2);
-        d->overlapped_levels++;
-    }
-    d->level_on_two_lanes = pl.two_lanes;
+    Fork fork(d, pl.two_lanes ? 2 : 1);
+    if (pl.two_lanes) d->opt.overlapped_levels++;
+    ScopedSet<bool> halves(d->level_on_two_lanes, pl.two_lanes);
     int k = 0;
     for (int64_t done = 0, cnt = 0; done < items; done += cnt, k++) {
         cnt = mux ? level_piece_items(W.item0 + done, pl.piece, items - done, W.ng, W.nm) : std::min<int64_t>(pl.piece, items - done);
         Lane& ln = d->lane[fixed_lane >= 0 ? fixed_lane : (pl.two_lanes ? (k & 1) : 0)];
         WorkDesc w = W;
         w.item0 = W.item0 + done;
-        if ((size_t)cnt > ln.ext_items) throw std::logic_error("piece larger than the lane's extracted-sample rows");
+        if ((size_t)cnt > ln.ext.items()) throw std::logic_error("piece larger than the lane's extracted-sample rows");
         tbr.mark(ln.stream);
         const int nbr = launch_blind_rotate(p, d, ln, w, cnt, ln.ext, -1, nullptr);
         tbr.mark(ln.stream);
@@ -1465,7 +1239,7 @@ static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t i
                 throw std::logic_error("piece of a level cut inside a MUX gate");
             const int64_t gate0 = level_gates_before(w.item0, W.ng, W.nm);
             const int64_t gcnt = level_gates_before(w.item0 + cnt, W.ng, W.nm) - gate0;
-            if ((size_t)gcnt > ln.comb_items || (d->K.N & 3)) throw std::logic_error("combined rows of a MUX level not reserved");
+            if ((size_t)gcnt > ln.comb.items() || (d->K.N & 3)) throw std::logic_error("combined rows of a MUX level not reserved");
             hipLaunchKernelGGL(k_level_combine, dim3((unsigned)gcnt), dim3(256), 0, ln.stream, ln.ext, ln.comb, d->K.N, gate0, w.item0,
                                W.ng, W.nm);
             WorkDesc wk = w;
@@ -1483,8 +1257,7 @@ static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t i
             stats->chunks++;
         }
     }
-    d->level_on_two_lanes = false;
-    if (pl.two_lanes) join_lanes(d, 2);
+    fork.join();
     if (stats) stats->bootstraps += items;
 }
 
@@ -1499,6 +1272,7 @@ bool Evaluator::fft_guard_tripped() {
     if ((double)m > d_->guard_max) d_->guard_max = (double)m;
     if (h[0] == 0 && h[2] == 0) return false;
     d_->audit_mismatches += h[2];
+    d_->opt.fft_guard_inject = 0;
     // the two counts only; the maximum stays
     HIP_CHECK(hipMemset(d_->fft_guard, 0, sizeof(unsigned)));
     HIP_CHECK(hipMemset(d_->fft_guard + 2, 0, sizeof(unsigned)));
@@ -1524,14 +1298,10 @@ bool overlaps(const Torus32* a, size_t na, const Torus32* b, size_t nb) {
 template <class F>
 void run_guarded(Evaluator& ev, bool* exact_once, int64_t* reruns, bool inputs_intact, EvalStats* stats, F&& once) {
     if (!inputs_intact && !*exact_once) {
-        *exact_once = true;
-        try {
+        {
+            ScopedSet<bool> exact(*exact_once, true);
             once();
-        } catch (...) {
-            *exact_once = false;
-            throw;
         }
-        *exact_once = false;
         (void)ev.fft_guard_tripped();  // folds the record of earlier calls; nothing this call did can trip it
         return;
     }
@@ -1544,14 +1314,8 @@ void run_guarded(Evaluator& ev, bool* exact_once, int64_t* reruns, bool inputs_i
         first = *stats;
         *stats = before;
     }
-    *exact_once = true;
-    try {
-        once();
-    } catch (...) {
-        *exact_once = false;
-        throw;
-    }
-    *exact_once = false;
+    ScopedSet<bool> exact(*exact_once, true);
+    once();
     if (stats) stats->total_ms += first.total_ms - before.total_ms;
 }
 }  // namespace
@@ -1582,13 +1346,19 @@ void Evaluator::debug_blind_rotate(size_t count, const Torus32* d_x, Torus32* d_
     run_guarded(*this, &d_->exact_once, &d_->guard_reruns, true, nullptr, [&] { debug_blind_rotate_once(count, d_x, d_acc, steps); });
 }
 
-void Evaluator::gates_device_once(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b, Torus32* d_out,
-                                  EvalStats* stats) {
+// What every entry point that launches starts with: the key is there, the device is current, and the kernels this call
+// takes follow the options as they are now.
+void Evaluator::begin_call() {
     if (!keys_loaded_) throw std::runtime_error("cloud key not loaded");
     HIP_CHECK(hipSetDevice(device_));
+    d_->use_w64 = w64::supported(p_) && !d_->opt.force_generic;
+    d_->force_generic_ks = d_->opt.force_generic;
+}
+
+void Evaluator::gates_device_once(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b, Torus32* d_out,
+                                  EvalStats* stats) {
+    begin_call();
     if (count == 0) return;
-    d_->use_w64 = w64::supported(p_) && !force_generic_;
-    d_->force_generic_ks = force_generic_;
     Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(stats != nullptr, stream_);
     WorkDesc W{};
     W.gates = nullptr;
@@ -1601,42 +1371,21 @@ void Evaluator::gates_device_once(int32_t type, size_t count, const Torus32* d_a
     run_items(p_, d_, W, (int64_t)count, tbr, tks, stats);
     tall.mark();
     HIP_CHECK(hipStreamSynchronize(stream_));
-    if (stats) {
-        stats->total_ms += tall.sum_ms();
-        stats->blind_rotate_ms += tbr.sum_ms();
-        stats->keyswitch_ms += tks.sum_ms();
-        stats->levels += 1;
-    }
+    add_times(stats, tall, tbr, tks);
+    if (stats) stats->levels += 1;
 }
 
 // bootsMUX (boot-gates.cpp): two blind rotations per gate, their extracted samples added, one key switch
 void Evaluator::mux_device_once(size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,
                                 EvalStats* stats) {
-    if (!keys_loaded_) throw std::runtime_error("cloud key not loaded");
-    HIP_CHECK(hipSetDevice(device_));
+    begin_call();
     if (count == 0) return;
-    d_->use_w64 = w64::supported(p_) && !force_generic_;
-    d_->force_generic_ks = force_generic_;
     const DevKeys& K = d_->K;
-    const size_t chunk = std::max<size_t>(d_->chunk & ~(size_t)1, 2), gates_per_chunk = chunk / 2;
+    const size_t chunk = std::max<size_t>(d_->opt.chunk & ~(size_t)1, 2), gates_per_chunk = chunk / 2;
     const size_t mux_need = std::min(gates_per_chunk, count);  // two extracted samples per MUX gate
     Lane& ln = d_->lane[0];
-    if (ln.ext_items < 2 * mux_need) {
-        const size_t n = grown(ln.ext_items, 2 * mux_need, chunk);
-        if (ln.ext) HIP_CHECK(hipFree(ln.ext));
-        ln.ext = nullptr;
-        ln.ext_items = 0;
-        HIP_CHECK(hipMalloc(&ln.ext, n * (size_t)(K.N + 4) * 4));
-        ln.ext_items = n;
-    }
-    if (d_->ext_mux_items < mux_need) {
-        const size_t n = grown(d_->ext_mux_items, mux_need, gates_per_chunk);
-        if (d_->ext_mux) HIP_CHECK(hipFree(d_->ext_mux));
-        d_->ext_mux = nullptr;
-        d_->ext_mux_items = 0;
-        HIP_CHECK(hipMalloc(&d_->ext_mux, n * (size_t)(K.N + 4) * 4));
-        d_->ext_mux_items = n;
-    }
+    ln.ext.reserve(2 * mux_need, chunk, d_->ext_row_bytes());
+    d_->ext_mux.reserve(mux_need, gates_per_chunk, d_->ext_row_bytes());
     Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(stats != nullptr, stream_);
     tall.mark();
     for (size_t done = 0; done < count; done += gates_per_chunk) {
@@ -1666,39 +1415,33 @@ void Evaluator::mux_device_once(size_t count, const Torus32* d_a, const Torus32*
     }
     tall.mark();
     HIP_CHECK(hipStreamSynchronize(stream_));
+    add_times(stats, tall, tbr, tks);
     if (stats) {
         stats->bootstraps += 2 * (int64_t)count;  // blind rotations; libtfhe counts a MUX as two bootstraps and one key switch
-        stats->total_ms += tall.sum_ms();
-        stats->blind_rotate_ms += tbr.sum_ms();
-        stats->keyswitch_ms += tks.sum_ms();
         stats->levels += 1;
     }
 }
 
-// Everything an evaluation of `c` over `batch` expressions allocates -- the wire store, the gate / output tables, the scratch
-// of its widest level (extracted samples, blind-rotation state, key-switch digits) -- so that the evaluation itself makes no
-// allocation (each one is a device-wide synchronisation).  eval_circuit_device calls it; a caller that times its first
-// evaluation calls it beforehand (ieache_prepare_batch).
-// Whether an evaluation of `c` over `batch` expressions runs as two expression-half pipelines (Impl::pipe_min).
+using TuneKey = std::tuple<size_t, int32_t, size_t, size_t, bool>;
+static TuneKey tune_key(const Evaluator::Impl* d, const Circuit& c, size_t batch) {
+    return std::make_tuple(c.gates.size(), (int32_t)c.n_levels(), c.outputs.size(), batch, d->opt.exact_fft || d->exact_once);
+}
+// Whether an evaluation of `c` over `batch` expressions runs as expression pipelines ("pipe_min").
 // -> 0 (no) or the number of pipelines (each gets at least one expression)
 // trial (may be null): set to 0 / 1 when this evaluation is one of the two timed trials of its (circuit, batch) -- without /
 // with pipelines -- and to -1 otherwise; the caller then reports the evaluation's wall time to tune_report().
-using TuneKey = std::tuple<size_t, int32_t, size_t, size_t, bool>;
-static TuneKey tune_key(const Evaluator::Impl* d, const Circuit& c, size_t batch) {
-    return std::make_tuple(c.gates.size(), (int32_t)c.n_levels(), c.outputs.size(), batch, d->exact_fft || d->exact_once);
-}
 static int pipelined(Evaluator::Impl* d, const Circuit& c, size_t batch, int* trial = nullptr, bool either = false) {
     if (trial) *trial = -1;
-    if (!d->overlap || !d->use_w64 || batch < 2 || c.n_levels() < 1) return 0;
-    const int lanes = (int)std::min<size_t>((size_t)d->pipe_lanes, batch);
+    if (!d->opt.overlap || !d->use_w64 || batch < 2 || c.n_levels() < 1) return 0;
+    const int lanes = (int)std::min<size_t>((size_t)d->opt.pipe_lanes, batch);
     int64_t gates = (int64_t)c.level_offset[c.n_levels()] - (int64_t)c.level_offset[0];
     for (int32_t m : c.level_mux) gates += m;  // in blind rotations: a MUX is two
-    const int64_t work = gates * (int64_t)batch, bar = d->pipe_min * (int64_t)c.n_levels();  // mean level against pipe_min
+    const int64_t work = gates * (int64_t)batch, bar = d->opt.pipe_min * (int64_t)c.n_levels();  // mean level against pipe_min
     // From 2 x pipe_min on pipelines won every measurement.  Below, it depends on where the levels fall among the kernels'
     // regimes (a level of 2 200 gate instances as two pipelines' launches of 1 100 costs a second, nearly empty round; on one
     // stream it runs as a rotation of roles): tried both ways from pipe_min / 8 up.
-    if (work >= 2 * bar || (!d->pipe_auto && work >= bar)) return lanes;
-    if (d->pipe_auto && d->pipe_min > 0 && work * 8 >= bar) {
+    if (work >= 2 * bar || (!d->opt.pipe_auto && work >= bar)) return lanes;
+    if (d->opt.pipe_auto && d->opt.pipe_min > 0 && work * 8 >= bar) {
         if (either) return lanes;  // scratch for both modes
         const auto it = d->tuned.find(tune_key(d, c, batch));
         const Evaluator::Impl::Tuned t = it == d->tuned.end() ? Evaluator::Impl::Tuned{} : it->second;
@@ -1715,7 +1458,7 @@ static void tune_report(Evaluator::Impl* d, const Circuit& c, size_t batch, int 
     Evaluator::Impl::Tuned& t = d->tuned[tune_key(d, c, batch)];
     t.ms[trial] = t.n[trial] == 0 ? ms : std::min(t.ms[trial], ms);
     t.n[trial]++;
-    d->tuned_evals++;
+    d->opt.tuned_evals++;
 }
 // expressions [first, first + count) of pipeline k of `lanes`: contiguous, sizes differing by at most one, the first ones longer
 static void pipe_slice(size_t batch, int lanes, int k, size_t* first, size_t* count) {
@@ -1724,35 +1467,16 @@ static void pipe_slice(size_t batch, int lanes, int k, size_t* first, size_t* co
     *count = base + ((size_t)k < extra ? 1 : 0);
 }
 
+// Everything an evaluation of `c` over `batch` expressions allocates -- the wire store, the gate / output tables, the scratch
+// of its widest level (extracted samples, blind-rotation state, key-switch digits) -- so that the evaluation itself makes no
+// allocation (each one is a device-wide synchronisation).  eval_circuit_device calls it; a caller that times its first
+// evaluation calls it beforehand (ieache_prepare_batch).
 void Evaluator::prepare_circuit(const Circuit& c, size_t batch) {
-    if (!keys_loaded_) throw std::runtime_error("cloud key not loaded");
-    HIP_CHECK(hipSetDevice(device_));
+    begin_call();
     if (batch == 0) return;
-    d_->use_w64 = w64::supported(p_) && !force_generic_;
-    d_->force_generic_ks = force_generic_;
-    const size_t row_bytes = (size_t)d_->K.stride * 4;
-    const size_t need = batch * (size_t)c.n_slots * row_bytes;
-    if (d_->store_bytes < need) {
-        if (d_->store) HIP_CHECK(hipFree(d_->store));
-        d_->store = nullptr;
-        d_->store_bytes = 0;
-        HIP_CHECK(hipMalloc(&d_->store, need));
-        d_->store_bytes = need;
-    }
-    if (d_->d_gates_cap < c.gates.size()) {
-        if (d_->d_gates) HIP_CHECK(hipFree(d_->d_gates));
-        d_->d_gates = nullptr;
-        d_->d_gates_cap = 0;
-        HIP_CHECK(hipMalloc(&d_->d_gates, c.gates.size() * sizeof(DevGate)));
-        d_->d_gates_cap = c.gates.size();
-    }
-    if (d_->d_outs_cap < c.outputs.size()) {
-        if (d_->d_outs) HIP_CHECK(hipFree(d_->d_outs));
-        d_->d_outs = nullptr;
-        d_->d_outs_cap = 0;
-        HIP_CHECK(hipMalloc(&d_->d_outs, c.outputs.size() * sizeof(OutRef)));
-        d_->d_outs_cap = c.outputs.size();
-    }
+    d_->store.reserve_exact(batch * (size_t)c.n_slots, (size_t)d_->K.stride * 4);
+    d_->d_gates.reserve_exact(c.gates.size());
+    d_->d_outs.reserve_exact(c.outputs.size());
     // rotation items (a MUX gate is two) and gate instances of each level
     std::vector<int64_t> level_items, level_gates;
     int64_t widest = 1, widest_mux_gates = 0;  // per expression: the widest level in items; the most gates of a level that has MUX gates
@@ -1774,7 +1498,7 @@ void Evaluator::prepare_circuit(const Circuit& c, size_t batch) {
         for (int k = 0; k < lanes; k++) {
             size_t first = 0, count = 0;
             pipe_slice(batch, lanes, k, &first, &count);
-            const size_t need = std::min<size_t>(d_->chunk + (mux ? 1 : 0), (size_t)widest * count);
+            const size_t need = std::min<size_t>(d_->opt.chunk + (mux ? 1 : 0), (size_t)widest * count);
             reserve_lane(p_, d_, d_->lane[k], need, mux ? std::min<size_t>(need, (size_t)widest_mux_gates * count) : 0);
         }
     } else {
@@ -1784,11 +1508,8 @@ void Evaluator::prepare_circuit(const Circuit& c, size_t batch) {
 
 void Evaluator::eval_circuit_device_once(const Circuit& c, size_t batch, const Torus32* d_in, Torus32* d_out,
                                          EvalStats* stats) {
-    if (!keys_loaded_) throw std::runtime_error("cloud key not loaded");
-    HIP_CHECK(hipSetDevice(device_));
+    begin_call();
     if (batch == 0) return;
-    d_->use_w64 = w64::supported(p_) && !force_generic_;
-    d_->force_generic_ks = force_generic_;
     const int32_t stride = d_->K.stride;
     const size_t row_bytes = (size_t)stride * 4;
     prepare_circuit(c, batch);
@@ -1803,13 +1524,10 @@ void Evaluator::eval_circuit_device_once(const Circuit& c, size_t batch, const T
     int trial = -1;
     const int pipes = pipelined(d_, c, batch, &trial);
     const auto wall0 = std::chrono::steady_clock::now();
-    if (pipes) {
-        // fork: the other pipelines start when the inputs are in the wire store
-        fork_lanes(d_, pipes);
-        d_->concurrency = pipes;
-        d_->pipelined_evals++;
-    }
-    try {
+    {
+        Fork fork(d_, pipes);  // the other pipelines start when the inputs are in the wire store
+        ScopedSet<int32_t> side_by_side(d_->concurrency, std::max(pipes, 1));
+        if (pipes) d_->opt.pipelined_evals++;
         for (int32_t L = 1; L <= c.n_levels(); L++) {
             WorkDesc W{};
             W.gates = d_->d_gates;
@@ -1834,13 +1552,7 @@ void Evaluator::eval_circuit_device_once(const Circuit& c, size_t batch, const T
             }
             if (stats) stats->levels++;
         }
-    } catch (...) {
-        d_->concurrency = 1;
-        throw;
-    }
-    if (pipes) {
-        d_->concurrency = 1;
-        join_lanes(d_, pipes);
+        fork.join();
     }
     const int32_t n_out = (int32_t)c.outputs.size();
     hipLaunchKernelGGL(k_gather_outputs, dim3((unsigned)(batch * n_out)), dim3(128), 0, stream_, d_->d_outs, n_out,
@@ -1849,41 +1561,32 @@ void Evaluator::eval_circuit_device_once(const Circuit& c, size_t batch, const T
     tall.mark();
     HIP_CHECK(hipStreamSynchronize(stream_));
     tune_report(d_, c, batch, trial, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count());
-    if (stats) {
-        stats->total_ms += tall.sum_ms();
-        stats->blind_rotate_ms += tbr.sum_ms();
-        stats->keyswitch_ms += tks.sum_ms();
-    }
+    add_times(stats, tall, tbr, tks);
 }
 
 void Evaluator::debug_blind_rotate_once(size_t count, const Torus32* d_x, Torus32* d_acc, int32_t steps) {
-    if (!keys_loaded_) throw std::runtime_error("cloud key not loaded");
-    HIP_CHECK(hipSetDevice(device_));
+    begin_call();
     WorkDesc W{};
     W.flat_a = d_x;
     W.flat_b = nullptr;
     W.flat_out = nullptr;
     W.flat_type = -1;
-    d_->use_w64 = w64::supported(p_) && !force_generic_;
-    d_->force_generic_ks = force_generic_;
     launch_blind_rotate(p_, d_, d_->lane[0], W, (int64_t)count, nullptr, steps, d_acc);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
 void Evaluator::debug_keyswitch(size_t count, const Torus32* d_u, Torus32* d_out) {
-    if (!keys_loaded_) throw std::runtime_error("cloud key not loaded");
-    HIP_CHECK(hipSetDevice(device_));
+    begin_call();
     // the kernel reads rows of N+4 ints; repack the caller's N+1 rows
-    Torus32* tmp = nullptr;
-    HIP_CHECK(hipMalloc(&tmp, count * (size_t)(p_.N + 4) * 4));
+    DeviceBuffer<Torus32> tmp;
+    tmp.allocate(count, d_->ext_row_bytes());
     HIP_CHECK(hipMemcpy2DAsync(tmp, (size_t)(p_.N + 4) * 4, d_u, (size_t)(p_.N + 1) * 4, (size_t)(p_.N + 1) * 4, count,
                                hipMemcpyDeviceToDevice, stream_));
     WorkDesc W{};
-    launch_keyswitch(d_, d_->lane[0], W, (int64_t)count, tmp, d_out, force_generic_);
+    launch_keyswitch(d_, d_->lane[0], W, (int64_t)count, tmp, d_out, d_->force_generic_ks);
     hipError_t e = hipGetLastError();
-    (void)hipStreamSynchronize(stream_);
-    (void)hipFree(tmp);
+    (void)hipStreamSynchronize(stream_);  // before tmp goes
     HIP_CHECK(e);
 }
 

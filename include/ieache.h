@@ -184,10 +184,9 @@ int ieache_ctx_cloud_run(ieache_ctx* ctx, const char* workdir);
 /* tuning / test knobs */
 int ieache_ctx_set_chunk(ieache_ctx* ctx, int64_t gate_instances_per_launch);
 int ieache_ctx_force_generic(ieache_ctx* ctx, int on);
-/* named knobs: "chunk", "force_generic", "ks_mfma_min" (launches of at least this many gate instances key-switch as an
- * int8 product on the MFMA pipe; default 64), "ks_mfma_split", "ks_sliced_min", "ks_gates", "ks_slice", "ks_batch_min",
- * "br_slice", "br_wide_max", "br_variant" (0 or a number of csrc/blind_rotate_w64.h's table), "exact_fft", "exact_one_wave_min", "fft_audit", "one_limb_min", "four_wave_max", "two_wave_max", "ks_split_max"
- * (see csrc/evaluator.h), and
+/* Named knobs.  The evaluator's are the rows of ONE table, csrc/evaluator_options.h: name, environment variable (read once,
+ * when the context is created), accepted range, default, and a line on what the option does.  A value a row refuses --
+ * through this call or in the environment -- changes nothing; here it returns IEACHE_EINVAL.  Two more belong to this layer:
  * "level_quantum" (0/1, default 1: the slack-balanced circuits -- 64/128-bit multipliers -- get a level
  * width that makes level x batch a whole number of resident-workgroup rounds; same DAG and output bits, more
  * levels of exactly-full launches when the batch is small), and
@@ -206,9 +205,9 @@ int ieache_ctx_set_option(ieache_ctx* ctx, const char* name, int64_t value);
  * between the two-waves- and the one-wave-per-gate kernel on three streams ("mix_s1", "mix_ratio", "mix_wg": turn length,
  * step ratio x 100, gates per workgroup).  "wg_gates" (0 = by launch size, 1 .. 4): gate instances per workgroup of the
  * one-wave-per-gate kernels.
- * ieache_ctx_get_option: the current value of any option above, or of the read-only figures "cus" (compute units of the
- * context's device), "resident_gates", "overlapped_levels", "pipelined_evals", "tuned_evals", "mixed_launches",
- * "staging_allocations". */
+ * ieache_ctx_get_option: the current value of any row of that table -- every option that can be set, and the read-only
+ * figures ("cus", "resident_gates", "overlapped_levels", "pipelined_evals", "tuned_evals", "mixed_launches",
+ * "staging_allocations") -- and of "level_quantum" / "fold_constants". */
 int ieache_ctx_get_option(const ieache_ctx* ctx, const char* name, int64_t* value);
 const char* ieache_ctx_kernel_variant(const ieache_ctx* ctx);
 /* Name of the blind-rotation kernel a launch of `gates` gate instances takes under the context's
