@@ -7,7 +7,7 @@
 //   K3 blind rotation         n x  acc += BK_i (x) ((X^bara_i - 1) acc)
 //   K4 sample extract
 //   K5 key switch                                                 (lwe-keyswitch-functions.cpp)
-// K0-K4 are one kernel (k_blind_rotate_*), K5 is a second (k_keyswitch_*).
+// K0-K4 are one kernel (k_blind_rotate_*), K5 is the key-switch unit (keyswitch.h).
 //
 // The external product is EXACT.  libtfhe multiplies polynomials with an
 // approximate FP64 FFT; here every BK polynomial is split into two balanced
@@ -20,11 +20,10 @@
 #include <cstring>
 
 #include "blind_rotate_w64.h"
-#include "keyswitch_mfma.h"
-#include "keyswitch_sliced.h"
 #include "device_buffer.h"
 #include "device_common.h"
 #include "evaluator_options.h"
+#include "keyswitch.h"
 #include "mix_plan.h"
 #include "scoped_set.h"
 
@@ -226,257 +225,6 @@ __global__ __launch_bounds__(kThreads) void k_blind_rotate_generic(DevKeys K, Wo
     }
 }
 
-// ---- K5, generic: one workgroup per gate instance ----
-// LDS: u [N+1] | list [N*t] | count
-__global__ __launch_bounds__(kThreads) void k_keyswitch_generic(DevKeys K, WorkDesc W, const Torus32* ext,
-                                                                Torus32* flat_out) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int32_t N = K.N, n = K.n, t = K.ks_t, basebit = K.ks_basebit, stride = K.stride;
-    int32_t* u = reinterpret_cast<int32_t*>(smem);
-    uint32_t* list = reinterpret_cast<uint32_t*>(u + N + 4);
-    __shared__ uint32_t s_count;
-    const int64_t item = (int64_t)blockIdx.x;
-    const Torus32* src = ext + (size_t)item * (N + 4);
-    if (threadIdx.x == 0) s_count = 0;
-    for (int32_t j = threadIdx.x; j <= N; j += blockDim.x) u[j] = src[j];
-    __syncthreads();
-    const uint32_t prec_offset = 1u << (32 - (1 + basebit * t));
-    const uint32_t mask = (1u << basebit) - 1;
-    for (int32_t idx = threadIdx.x; idx < N * t; idx += blockDim.x) {
-        const int32_t i = idx / t, j = idx - i * t;
-        const uint32_t d = (((uint32_t)u[i] + prec_offset) >> (32 - (j + 1) * basebit)) & mask;
-        if (d) list[atomicAdd(&s_count, 1u)] = ((uint32_t)idx << basebit) + d;  // row index [i][j][d]
-    }
-    __syncthreads();
-    const uint32_t cnt = s_count;
-    // subtraction mod 2^32 commutes, so the (non-deterministic) list order does not matter
-    uint32_t r0 = 0, r1 = 0, r2 = 0;
-    const int32_t q0 = threadIdx.x, q1 = q0 + kThreads, q2 = q0 + 2 * kThreads;
-    for (uint32_t e = 0; e < cnt; e++) {
-        const int32_t* row = K.ksk + (size_t)list[e] * stride;
-        if (q0 < stride) r0 -= (uint32_t)row[q0];
-        if (q1 < stride) r1 -= (uint32_t)row[q1];
-        if (q2 < stride) r2 -= (uint32_t)row[q2];
-    }
-    Torus32* out = flat_out ? flat_out + (size_t)item * stride : resolve(W, W.item0 + item, stride).out;
-    const uint32_t bprime = (uint32_t)u[N];
-    if (q0 <= n) out[q0] = (int32_t)(r0 + (q0 == n ? bprime : 0u));
-    else if (q0 < stride) out[q0] = 0;
-    if (q1 < stride) out[q1] = q1 <= n ? (int32_t)(r1 + (q1 == n ? bprime : 0u)) : 0;
-    if (q2 < stride) out[q2] = q2 <= n ? (int32_t)(r2 + (q2 == n ? bprime : 0u)) : 0;
-}
-
-// ---- K5, vectorised: one 512-thread workgroup per gate instance ----
-// The non-zero digits are compacted into a row list; the 8 waves take list
-// entries round-robin, each wave subtracting whole 16-byte-per-lane row pieces
-// (NLD dwordx4 loads cover one padded KSK row), four rows in flight per wave;
-// the 8 partial sums meet in LDS.  Subtraction mod 2^32 commutes, so neither the
-// list order nor the split changes a single bit.
-// LDS: u [N+4] | list [N*t] | part [8][stride]
-constexpr int kKsThreads = 512;
-template <int NLD>
-__global__ __launch_bounds__(kKsThreads) void k_keyswitch_vec(DevKeys K, WorkDesc W, const Torus32* ext,
-                                                              Torus32* flat_out, int32_t splits) {
-    // splits > 1 (launches of a handful of gates, where one workgroup per gate leaves the chip idle and the walk's
-    // latency is what counts): blockIdx.y takes coefficients [y*N/splits, (y+1)*N/splits) and ADDS its share to an
-    // output row that k_keyswitch_init has set to (0, ..., 0, b); int32 addition commutes, so the bits do not change
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int32_t N = K.N, n = K.n, t = K.ks_t, basebit = K.ks_basebit, stride = K.stride;
-    int32_t* u = reinterpret_cast<int32_t*>(smem);
-    uint32_t* list = reinterpret_cast<uint32_t*>(u + N + 4);
-    int4* part = reinterpret_cast<int4*>(list + (size_t)N * t);
-    __shared__ uint32_t s_count;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t item = (int64_t)blockIdx.x;
-    const Torus32* src = ext + (size_t)item * (N + 4);
-    if (tid == 0) s_count = 0;
-    for (int32_t j = tid; j <= N; j += kKsThreads) u[j] = src[j];
-    __syncthreads();
-    const uint32_t prec_offset = 1u << (32 - (1 + basebit * t));
-    const uint32_t mask = (1u << basebit) - 1;
-    const int32_t idx0 = splits > 1 ? (int32_t)blockIdx.y * (N / splits) * t : 0;
-    const int32_t idx1 = splits > 1 ? idx0 + (N / splits) * t : N * t;
-    for (int32_t idx = idx0 + tid; idx < idx1; idx += kKsThreads) {
-        const int32_t i = idx / t, j = idx - i * t;
-        const uint32_t d = (((uint32_t)u[i] + prec_offset) >> (32 - (j + 1) * basebit)) & mask;
-        if (d) list[atomicAdd(&s_count, 1u)] = ((uint32_t)idx << basebit) + d;  // row index [i][j][d]
-    }
-    __syncthreads();
-    const uint32_t cnt = s_count;
-    const int32_t nvec = stride >> 2;
-    int4 acc[NLD];
-#pragma unroll
-    for (int v = 0; v < NLD; v++) acc[v] = make_int4(0, 0, 0, 0);
-    const int4* kbase = reinterpret_cast<const int4*>(K.ksk);
-    uint32_t e = wave;
-    for (; e + 24 < cnt; e += 32) {  // four rows (e, e+8, e+16, e+24) in flight
-        int4 r[4][NLD];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int4* row = kbase + (size_t)list[e + 8 * q] * nvec;
-#pragma unroll
-            for (int v = 0; v < NLD; v++)
-                r[q][v] = (lane + 64 * v < nvec) ? row[lane + 64 * v] : make_int4(0, 0, 0, 0);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-#pragma unroll
-            for (int v = 0; v < NLD; v++) {
-                acc[v].x -= r[q][v].x;
-                acc[v].y -= r[q][v].y;
-                acc[v].z -= r[q][v].z;
-                acc[v].w -= r[q][v].w;
-            }
-    }
-    for (; e < cnt; e += 8) {
-        const int4* row = kbase + (size_t)list[e] * nvec;
-#pragma unroll
-        for (int v = 0; v < NLD; v++)
-            if (lane + 64 * v < nvec) {
-                const int4 rr = row[lane + 64 * v];
-                acc[v].x -= rr.x;
-                acc[v].y -= rr.y;
-                acc[v].z -= rr.z;
-                acc[v].w -= rr.w;
-            }
-    }
-#pragma unroll
-    for (int v = 0; v < NLD; v++)
-        if (lane + 64 * v < nvec) part[(size_t)wave * nvec + lane + 64 * v] = acc[v];
-    __syncthreads();
-    Torus32* out = flat_out ? flat_out + (size_t)item * stride : resolve(W, W.item0 + item, stride).out;
-    const int32_t* parti = reinterpret_cast<const int32_t*>(part);
-    for (int32_t q = tid; q < stride; q += kKsThreads) {
-        uint32_t v = 0;
-#pragma unroll
-        for (int w = 0; w < 8; w++) v += (uint32_t)parti[(size_t)w * stride + q];
-        if (splits > 1) {
-            if (q <= n) atomicAdd(reinterpret_cast<uint32_t*>(out) + q, v);
-            continue;
-        }
-        if (q == n) v += (uint32_t)u[N];
-        out[q] = q <= n ? (int32_t)v : 0;
-    }
-}
-
-// output rows of a split key switch: (0, ..., 0, b) with b the extracted sample's last word
-__global__ __launch_bounds__(256) void k_keyswitch_init(DevKeys K, WorkDesc W, const Torus32* ext, Torus32* flat_out) {
-    const int64_t item = (int64_t)blockIdx.x;
-    const int32_t n = K.n, stride = K.stride;
-    Torus32* out = flat_out ? flat_out + (size_t)item * stride : resolve(W, W.item0 + item, stride).out;
-    const Torus32 b = ext[(size_t)item * (K.N + 4) + K.N];
-    for (int32_t q = threadIdx.x; q < stride; q += 256) out[q] = q == n ? b : 0;
-}
-
-// ---- K5, gate-batched: one workgroup per G gate instances ----
-// The key-switch key does not fit the L2s (83 MB), so K5 is bound by how many KSK bytes
-// are fetched per gate.  Here a workgroup walks ALL (i, j) positions once, loads the
-// three candidate rows [i][j][1..3] and lets each of its G gates subtract the one its
-// digit selects: 3 x 2.5 KB x N x t / G bytes per gate instead of ~0.75 x 2.5 KB x N x t.
-// One wave per 64 int4 columns of a row (3 waves at n=630), each lane owning one column
-// for all G gates, so no partial sums cross waves.  The t digits of a'_i are packed into
-// one word per gate, pulled into SGPRs once per i; the digit (wave-uniform) indexes a 4-row
-// register table {0, r1, r2, r3} through the SGPR-indexed VGPR mode (s_set_gpr_idx), which is
-// 3x cheaper than v_cndmask chains or scalar branches.  Subtraction mod 2^32 commutes, so the
-// result is bit-identical to the other kernels.
-// LDS: dw [G][N] u16 | bprime [G]
-template <int G>
-__global__ __launch_bounds__(256) void k_keyswitch_batch(DevKeys K, WorkDesc W, const Torus32* ext, Torus32* flat_out,
-                                                         int64_t items) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int32_t N = K.N, n = K.n, t = K.ks_t, basebit = K.ks_basebit, stride = K.stride;
-    uint16_t* dw = reinterpret_cast<uint16_t*>(smem);
-    int32_t* bprime = reinterpret_cast<int32_t*>(dw + (size_t)G * N);
-    const int tid = threadIdx.x, nthreads = blockDim.x;
-    const int64_t item0 = (int64_t)blockIdx.x * G;
-    const int32_t gcount = (int32_t)(items - item0 < G ? items - item0 : G);
-    const uint32_t prec_offset = 1u << (32 - (1 + basebit * t));
-    const uint32_t mask = (1u << basebit) - 1;
-    // pack the digits of every a'_i of every gate: digit j sits at bits [j*basebit, (j+1)*basebit)
-    for (int32_t idx = tid; idx < G * N; idx += nthreads) {
-        const int32_t g = idx / N, i = idx - g * N;
-        uint32_t packed = 0;
-        if (g < gcount) {
-            const uint32_t a = (uint32_t)ext[(size_t)(item0 + g) * (N + 4) + i] + prec_offset;
-            for (int32_t j = 0; j < t; j++) packed |= ((a >> (32 - (j + 1) * basebit)) & mask) << (j * basebit);
-        }
-        dw[idx] = (uint16_t)packed;
-    }
-    if (tid < G) bprime[tid] = tid < gcount ? ext[(size_t)(item0 + tid) * (N + 4) + N] : 0;
-    __syncthreads();
-
-    const int32_t nvec = stride >> 2;
-    const int32_t col = tid;  // one int4 column per thread
-    const bool active = col < nvec;
-    const int4* kbase = reinterpret_cast<const int4*>(K.ksk) + (active ? col : 0);  // idle lanes shadow column 0
-    const size_t rowpitch = (size_t)nvec;  // int4 per row; rows [pos][d] are consecutive
-    int4 acc[G];
-#pragma unroll
-    for (int g = 0; g < G; g++) acc[g] = make_int4(0, 0, 0, 0);
-
-    // Walk i (the extracted coefficient), then its t digits.  The packed digits of a'_i of all
-    // G gates are pulled into SGPRs once per i.  Candidate rows are requested two positions
-    // ahead into a ring of three named row sets (the walk is latency-bound otherwise).
-    const size_t npos = (size_t)N * t;
-#define KS_LOAD(A, B, C, POS)                                        \
-    {                                                                \
-        size_t pp_ = (POS);                                          \
-        if (pp_ >= npos) pp_ = npos - 1;                             \
-        const int4* row_ = kbase + pp_ * 4 * rowpitch;               \
-        A = row_[1 * rowpitch];                                      \
-        B = row_[2 * rowpitch];                                      \
-        C = row_[3 * rowpitch];                                      \
-    }
-#define KS_USE(A, B, C, SH)                                                        \
-    {                                                                              \
-        const int32_t tab_[16] = {0, 0, 0, 0, A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w, C.x, C.y, C.z, C.w}; \
-        _Pragma("unroll") for (int g = 0; g < G; g++) {                            \
-            const uint32_t d_ = ((dg[g] >> (SH)) & mask) * 4;  /* uniform: SGPR-indexed register read */ \
-            acc[g].x -= tab_[d_ + 0];                                              \
-            acc[g].y -= tab_[d_ + 1];                                              \
-            acc[g].z -= tab_[d_ + 2];                                              \
-            acc[g].w -= tab_[d_ + 3];                                              \
-        }                                                                          \
-    }
-    int4 a1, a2, a3, b1, b2, b3, c1, c2, c3;
-    KS_LOAD(a1, a2, a3, 0)
-    KS_LOAD(b1, b2, b3, 1)
-    size_t pos = 0;
-    for (int32_t i = 0; i < N; i++) {
-        uint32_t dg[G];
-#pragma unroll
-        for (int g = 0; g < G; g++) dg[g] = __builtin_amdgcn_readfirstlane((uint32_t)dw[g * N + i]);
-        int32_t sh = 0;
-        for (int32_t j = 0; j < t; j++, pos++, sh += basebit) {
-            KS_LOAD(c1, c2, c3, pos + 2)
-            KS_USE(a1, a2, a3, sh)
-            a1 = b1; a2 = b2; a3 = b3;
-            b1 = c1; b2 = c2; b3 = c3;
-        }
-    }
-#undef KS_LOAD
-#undef KS_USE
-    if (active) {
-#pragma unroll
-        for (int g = 0; g < G; g++) {
-            if (g < gcount) {
-                int4 v = acc[g];
-                if (col == (n >> 2)) {  // the column holding b'
-                    const int32_t bp = bprime[g];
-                    switch (n & 3) {
-                        case 0: v.x += bp; break;
-                        case 1: v.y += bp; break;
-                        case 2: v.z += bp; break;
-                        default: v.w += bp; break;
-                    }
-                }
-                Torus32* out = flat_out ? flat_out + (size_t)(item0 + g) * stride : resolve(W, W.item0 + item0 + g, stride).out;
-                reinterpret_cast<int4*>(out)[col] = v;
-            }
-        }
-    }
-}
-
 // bootsMUX: u = (0, 1/8) + u1 + u2 over the extracted samples of the two blind rotations of a gate
 // (rows 2g and 2g+1 of `ext`), written to row g of `dst`; the key switch follows on `dst`
 __global__ void k_mux_combine(const Torus32* ext, Torus32* dst, int32_t N) {
@@ -560,7 +308,7 @@ struct Lane {
     DeviceBuffer<Torus32> comb;     // levels with MUX gates: one combined row per gate of a piece (k_level_combine).  Per lane, not
                                     // per context: two lanes run their combines and key switches side by side
     DeviceBuffer<char> br_state;    // sliced blind rotation: accumulators + rotation amounts, w64::state_bytes_per_item() per item
-    DeviceBuffer<char> ks_digits;   // MFMA key switch (counted in bytes)
+    KsScratch ks;                   // key switch
     DeviceBuffer<Torus32> audit_ext;
     DeviceBuffer<char> audit_state;
     Event ev_join;                  // the lane's share of a level / of an evaluation is queued
@@ -569,7 +317,6 @@ struct Lane {
 
 // Members are released in reverse order; Evaluator::destroy() has every stream idle before that starts.
 struct Evaluator::Impl {
-    Params p;
     Lane lane[kMaxLanes];
     Event ev_fork;
     EvalOptions opt;  // evaluator_options.h: everything set_option / get_option name
@@ -598,17 +345,13 @@ struct Evaluator::Impl {
     int64_t audit_seq = 0;       // one-limb (level, chunk) launches so far
     int64_t audits = 0, audit_gates = 0, audit_mismatches = 0;
     DeviceBuffer<int32_t> ksk;
-    DeviceBuffer<int8_t> ks_limbs;  // byte-limb form of the key for the MFMA key switch
+    KeySwitch ks;  // K5: kernels, key form, LDS grants and the choice among them
     DeviceBuffer<double2> twist, wtab;
     DeviceBuffer<Torus32> ext_mux;  // bootsMUX: combined extracted samples, chunk/2 rows
     DeviceBuffer<Torus32> store;    // circuits: the wire store, the gate and the output table
     DeviceBuffer<DevGate> d_gates;
     DeviceBuffer<OutRef> d_outs;
-    size_t br_lds = 0, ks_lds = 0, ksv_lds = 0;
-    int ks_nld = 0;  // dwordx4 loads per KSK row per wave; 0 = use the scalar kernel
-    bool ks_batch_ok = false;   // gate-batched key switch usable (base == 4, digits fit 16 bits, columns fit 8 waves)
-    bool ks_sliced_ok = false;  // hand-scheduled sliced variant of it usable (t = 8, basebit = 2)
-    bool ks_mfma_ok = false;
+    size_t br_lds = 0;
     size_t ext_row_bytes() const { return (size_t)(K.N + 4) * 4; }
 };
 
@@ -651,7 +394,6 @@ void Evaluator::init() {
         if (!w64::one_limb_supported(p)) o.exact_fft = 1;
         options_from_environment(o, [this](const OptionRow& r, int64_t& v) { return option_hook(r, v); });
     }
-    d_->p = p;
     DevKeys& K = d_->K;
     K.n = p.n;
     K.N = p.N;
@@ -681,27 +423,10 @@ void Evaluator::init() {
     K.wtab = d_->wtab;
     const int32_t frows = K.kpl > 4 ? K.kpl : 4;
     d_->br_lds = (size_t)frows * M * sizeof(double2) + (size_t)2 * p.N * 4 + (((size_t)p.n * 2 + 15) & ~(size_t)15);
-    d_->ks_lds = (size_t)(p.N + 4) * 4 + (size_t)p.N * p.ks_t * 4;
-    if (d_->br_lds > 160 * 1024 || d_->ks_lds > 160 * 1024)
-        throw std::invalid_argument("parameter set exceeds the 160 KiB LDS of a CU");
+    if (d_->br_lds > 160 * 1024) throw std::invalid_argument("parameter set exceeds the 160 KiB LDS of a CU");
     // (per context, on the context's device: the sizes depend on the parameter set)
     dev::allow_dynamic_lds((const void*)k_blind_rotate_generic, d_->br_lds, "k_blind_rotate_generic");
-    dev::allow_dynamic_lds((const void*)k_keyswitch_generic, d_->ks_lds, "k_keyswitch_generic");
-    {
-        const int nvec = K.stride / 4, nld = (nvec + 63) / 64;
-        d_->ksv_lds = (size_t)(p.N + 4) * 4 + (size_t)p.N * p.ks_t * 4 + (size_t)8 * K.stride * 4;
-        d_->ks_batch_ok = K.ks_base == 4 && p.ks_t * p.ks_basebit <= 16 && p.ks_t % 4 == 0 && nld <= 4;
-        d_->ks_sliced_ok = kss::supported(p) && nld <= 4;
-        d_->ks_mfma_ok = ksm::supported(p);
-        if (d_->ks_batch_ok)
-            dev::allow_dynamic_lds((const void*)k_keyswitch_batch<16>, (size_t)16 * p.N * 2 + 64, "k_keyswitch_batch");
-        if (nld <= 4 && d_->ksv_lds <= 160 * 1024) {
-            d_->ks_nld = nld;
-            const void* f = nld == 1 ? (const void*)k_keyswitch_vec<1> : nld == 2 ? (const void*)k_keyswitch_vec<2>
-                          : nld == 3 ? (const void*)k_keyswitch_vec<3> : (const void*)k_keyswitch_vec<4>;
-            dev::allow_dynamic_lds(f, d_->ksv_lds, "k_keyswitch_vec");
-        }
-    }
+    d_->ks.init(p, K);
 }
 
 Evaluator::~Evaluator() { destroy(); }
@@ -753,7 +478,7 @@ void Evaluator::set_chunk(size_t items) { d_->opt.chunk = items < 1 ? 1 : (int64
 // storing the value.
 bool Evaluator::option_hook(const OptionRow& r, int64_t& v) {
     if (r.at == &EvalOptions::force_generic) v = v != 0;
-    if (r.at == &EvalOptions::ks_mfma_split) return v == 0 || ksm::split_ok(p_, (int32_t)v);  // every split holds whole loop trips
+    if (r.at == &EvalOptions::ks_mfma_split) return v == 0 || ks_mfma_split_ok(p_, (int32_t)v);  // every split holds whole loop trips
     if (r.at == &EvalOptions::br_variant) return w64::variant_known((int32_t)v);
     if (r.at == &EvalOptions::exact_fft) return v == 1 || w64::one_limb_supported(p_);
     if (r.at == &EvalOptions::fft_guard_inject) {
@@ -831,11 +556,7 @@ void Evaluator::load_keys_device(const Torus32* d_bk, const Torus32* d_ksk) {
     hipLaunchKernelGGL(k_pad_rows, dim3(2048), dim3(256), 0, stream_, d_ksk, d_->ksk, (int64_t)ks_rows, p_.n + 1,
                        K.stride);
     HIP_CHECK(hipGetLastError());
-    if (d_->ks_mfma_ok) {
-        if (!d_->ks_limbs) d_->ks_limbs.allocate(ksm::limb_matrix_bytes(p_));
-        ksm::prepare(p_, d_->ksk, d_->ks_limbs, stream_);
-        HIP_CHECK(hipGetLastError());
-    }
+    d_->ks.load_key(d_->ksk, stream_);
     HIP_CHECK(hipStreamSynchronize(stream_));
     keys_loaded_ = true;
 }
@@ -1085,50 +806,9 @@ static void maybe_audit(const Params& p, Evaluator::Impl* d, Lane& ln, const Wor
     d->audit_gates += m;
 }
 
-// digit scratch of the MFMA key switch for launches of up to `cnt` gates: the grown() policy in bytes
-static void reserve_ks_digits(Evaluator::Impl* d, Lane& ln, int64_t cnt) {
-    ln.ks_digits.reserve(ksm::digit_scratch_bytes(d->p, cnt), ksm::digit_scratch_bytes(d->p, d->opt.chunk), 1,
-                         ksm::digit_scratch_bytes(d->p, 4096));
-}
-
-static void launch_keyswitch(Evaluator::Impl* d, Lane& ln, const WorkDesc& w, int64_t cnt, const Torus32* ext,
-                             Torus32* flat_out, bool force_generic) {
-    hipStream_t stream = ln.stream;
-    const DevKeys& K = d->K;
-    const dim3 grid((unsigned)cnt), blk(kKsThreads);
-    const int nld = force_generic ? 0 : d->ks_nld;
-    if (!force_generic && d->ks_mfma_ok && d->ks_limbs && cnt >= d->opt.ks_mfma_min) {
-        reserve_ks_digits(d, ln, cnt);
-        ksm::launch(d->p, K, w, cnt, ext, flat_out, d->ks_limbs, ln.ks_digits, d->opt.ks_mfma_split, d->opt.cus, stream);
-        return;
-    }
-    if (nld > 0 && d->ks_sliced_ok && cnt >= d->opt.ks_sliced_min) {
-        kss::launch(d->p, K, w, cnt, ext, flat_out, d->opt.ks_slice, d->opt.ks_gates, stream);
-        return;
-    }
-    if (nld > 0 && d->ks_batch_ok && cnt >= d->opt.ks_batch_min) {
-        constexpr int G = 16;
-        const size_t lds = (size_t)G * K.N * 2 + (size_t)G * 4;
-        hipLaunchKernelGGL(k_keyswitch_batch<G>, dim3((unsigned)((cnt + G - 1) / G)), dim3(64 * nld), lds, stream, K, w, ext,
-                           flat_out, cnt);
-        return;
-    }
-    // a handful of gates: cut each gate's walk into `splits` workgroups
-    int32_t splits = 1;
-    if (nld > 0 && d->opt.ks_split_max > 1) {
-        // measured: pays while gates x splits stays within ~1.5 workgroups per CU (1-8 gates: 0.18 -> 0.03 ms, 44: 0.09, 256: no gain)
-        while (splits < d->opt.ks_split_max && cnt * splits * 2 <= (3 * (int64_t)d->opt.cus) / 2 && K.N % (splits * 2) == 0) splits *= 2;
-    }
-    dim3 vgrid((unsigned)cnt, (unsigned)splits);
-    if (splits > 1) hipLaunchKernelGGL(k_keyswitch_init, grid, dim3(256), 0, stream, K, w, ext, flat_out);
-    switch (nld) {
-        case 1: hipLaunchKernelGGL(k_keyswitch_vec<1>, vgrid, blk, d->ksv_lds, stream, K, w, ext, flat_out, splits); break;
-        case 2: hipLaunchKernelGGL(k_keyswitch_vec<2>, vgrid, blk, d->ksv_lds, stream, K, w, ext, flat_out, splits); break;
-        case 3: hipLaunchKernelGGL(k_keyswitch_vec<3>, vgrid, blk, d->ksv_lds, stream, K, w, ext, flat_out, splits); break;
-        case 4: hipLaunchKernelGGL(k_keyswitch_vec<4>, vgrid, blk, d->ksv_lds, stream, K, w, ext, flat_out, splits); break;
-        default:
-            hipLaunchKernelGGL(k_keyswitch_generic, grid, dim3(kThreads), d->ks_lds, stream, K, w, ext, flat_out);
-    }
+// the key switch of `cnt` extracted samples on a lane's stream, with the lane's scratch
+static void launch_keyswitch(Evaluator::Impl* d, Lane& ln, const WorkDesc& w, int64_t cnt, const Torus32* ext, Torus32* flat_out) {
+    d->ks.launch(ln.ks, ln.stream, w, cnt, ext, flat_out, d->opt, d->force_generic_ks);
 }
 
 // How a level of `items` gate instances is issued: on lane 0 in pieces of at most a chunk, or (overlap) in pieces of at most
@@ -1157,8 +837,7 @@ static void reserve_lane(const Params& p, Evaluator::Impl* d, Lane& ln, size_t n
     ln.comb.reserve(need_comb, (size_t)d->opt.chunk, d->ext_row_bytes());
     ln.ext.reserve(need, (size_t)d->opt.chunk, d->ext_row_bytes());
     reserve_br_state(p, d, ln, need);
-    // the MFMA key switch's digit scratch for the widest launch that will take it
-    if (!d->force_generic_ks && d->ks_mfma_ok && d->ks_limbs && (int64_t)need >= d->opt.ks_mfma_min) reserve_ks_digits(d, ln, (int64_t)need);
+    d->ks.reserve(ln.ks, (int64_t)need, d->opt, d->force_generic_ks);  // for the widest launch
 }
 
 // Before an evaluation starts: scratch for its widest launch in one go (the per-launch checks below then find it in place),
@@ -1245,9 +924,9 @@ static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t i
             WorkDesc wk = w;
             wk.nm = 0;
             wk.item0 = gate0;
-            launch_keyswitch(d, ln, wk, gcnt, ln.comb, nullptr, d->force_generic_ks);
+            launch_keyswitch(d, ln, wk, gcnt, ln.comb, nullptr);
         } else {
-            launch_keyswitch(d, ln, w, cnt, ln.ext, nullptr, d->force_generic_ks);
+            launch_keyswitch(d, ln, w, cnt, ln.ext, nullptr);
         }
         tks.mark(ln.stream);
         HIP_CHECK(hipGetLastError());
@@ -1404,7 +1083,7 @@ void Evaluator::mux_device_once(size_t count, const Torus32* d_a, const Torus32*
         tks.mark();
         hipLaunchKernelGGL(k_mux_combine, dim3((unsigned)cnt), dim3(256), 0, stream_, ln.ext, d_->ext_mux, K.N);
         WorkDesc Wk{};
-        launch_keyswitch(d_, ln, Wk, cnt, d_->ext_mux, d_out + done * K.stride, d_->force_generic_ks);
+        launch_keyswitch(d_, ln, Wk, cnt, d_->ext_mux, d_out + done * K.stride);
         tks.mark();
         HIP_CHECK(hipGetLastError());
         if (stats) {
@@ -1584,7 +1263,7 @@ void Evaluator::debug_keyswitch(size_t count, const Torus32* d_u, Torus32* d_out
     HIP_CHECK(hipMemcpy2DAsync(tmp, (size_t)(p_.N + 4) * 4, d_u, (size_t)(p_.N + 1) * 4, (size_t)(p_.N + 1) * 4, count,
                                hipMemcpyDeviceToDevice, stream_));
     WorkDesc W{};
-    launch_keyswitch(d_, d_->lane[0], W, (int64_t)count, tmp, d_out, d_->force_generic_ks);
+    launch_keyswitch(d_, d_->lane[0], W, (int64_t)count, tmp, d_out);
     hipError_t e = hipGetLastError();
     (void)hipStreamSynchronize(stream_);  // before tmp goes
     HIP_CHECK(e);

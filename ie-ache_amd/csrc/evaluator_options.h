@@ -22,6 +22,7 @@ struct EvalOptions {
     int64_t ks_slice = 0, ks_gates = 0;
     int64_t ks_mfma_min = 64;     // measured crossover with the per-gate walk: ~40 gates (0.08 ms either way)
     int64_t ks_mfma_split = 0, ks_split_max = 16;
+    int64_t ks_xcd = 0;
     // blind rotation: which kernel takes a launch of how many gate instances (pick_br_variant)
     int64_t br_slice = 0, br_variant = 0;
     int64_t br_wide_max = 0, one_limb_min = 0, four_wave_max = 0, two_wave_max = 0;  // per CU
@@ -54,6 +55,7 @@ inline bool not_1(int64_t v) { return v != 1; }
 #define IEACHE_OPT(name, env) #name, env, &EvalOptions::name
 #define IEACHE_FIGURE(name) #name, nullptr, &EvalOptions::name, 1, 0, nullptr
 
+// Which key-switch kernel these select for a launch is stated in ks_plan.h.
 // Conditions that need the device or the parameter set, and effects beyond storing the value, are in Evaluator::option_hook
 // (evaluator.hip); the rows they apply to say "hook".
 inline constexpr OptionRow kOptionTable[] = {
@@ -61,10 +63,11 @@ inline constexpr OptionRow kOptionTable[] = {
     {IEACHE_OPT(force_generic, nullptr), INT64_MIN, kNoLimit, nullptr, "hook (stored as 0 / 1): the any-parameter kernels even where a specialised one exists"},
     {IEACHE_OPT(ks_batch_min, "IEACHE_KS_BATCH_MIN"), 0, kNoLimit, nullptr, "launches from this size: the compiler-scheduled gate-batched key switch (the cross-check)"},
     {IEACHE_OPT(ks_sliced_min, "IEACHE_KS_SLICED_MIN"), 0, kNoLimit, nullptr, "launches from this size: the hand-scheduled sliced key switch"},
-    {IEACHE_OPT(ks_slice, nullptr), 0, 1024, nullptr, "coefficients per launch of the sliced key switch (up to kss::max_slice()); 0 = the whole walk"},
+    {IEACHE_OPT(ks_slice, nullptr), 0, 1024, nullptr, "coefficients per launch of the sliced key switch (up to kKsMaxSlice, ks_plan.h); 0 = the whole walk"},
     {IEACHE_OPT(ks_gates, nullptr), 0, 32, ks_gates_ok, "its gate instances per workgroup: 4, 8, 16, 32; 0 = by launch size"},
     {IEACHE_OPT(ks_mfma_min, "IEACHE_KS_MFMA_MIN"), 0, kNoLimit, nullptr, "launches from this size: the key switch as an int8 product on the MFMA pipe (keyswitch_mfma.hip)"},
-    {IEACHE_OPT(ks_mfma_split, nullptr), 0, 64, pow2_or_0, "hook (ksm::split_ok): workgroups its walk is cut into per tile, a power of two; 0 = by launch size"},
+    {IEACHE_OPT(ks_mfma_split, nullptr), 0, 64, pow2_or_0, "hook (ks_mfma_split_ok, ks_plan.h): workgroups its walk is cut into per tile, a power of two; 0 = by launch size"},
+    {IEACHE_OPT(ks_xcd, "IEACHE_KS_XCD"), 0, 1, nullptr, "measurement aid: 1 = each XCD walks its own eighth of the MFMA key switch's streams (measured slower, see k_ksm_gemm)"},
     {IEACHE_OPT(ks_split_max, nullptr), 1, 64, nullptr, "workgroups the per-gate key switch may cut one gate's walk into when a launch holds a handful of gates; 1 = never"},
     {IEACHE_OPT(br_slice, nullptr), 0, 4096, nullptr, "CMux steps per blind-rotation launch; 0 = by kernel and launch size (16 over several rounds of resident gates, 64 while all are resident, the whole rotation for the four-wave and latency kernels)"},
     {IEACHE_OPT(br_variant, nullptr), 0, 1000, nullptr, "hook (w64::variant_known): a number of blind_rotate_w64.h's table; 0 = by launch size.  Default: IEACHE_BR_VARIANT, read there"},

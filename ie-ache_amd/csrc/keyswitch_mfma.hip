@@ -24,11 +24,10 @@
 // pre-pass ([coefficient][gate] order, so that the 32 gates of a tile load as one row).
 // Which lane / byte of an operand register is "k" does not matter as long as A and B agree: both use
 // k = 16 (lane / 32) + byte, i.e. positions j = 4 (lane / 32) + (byte / 4), digit value d = byte % 4.
-#include "keyswitch_mfma.h"
+#include "keyswitch_dev.h"
 
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <stdexcept>
 
 namespace ieache {
@@ -41,14 +40,10 @@ namespace {
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
-// coefficients of B fragments in flight per wave: 8 (round 4; 4 until then: 0.658 -> 0.610 ms per 8 192 gates, profiles/r4_keyswitch_ahead.txt).
-// 4 or 8: the walk of a K split is a multiple of 8 coefficients for every supported N (N % 64 == 0, splits <= 8).
-#ifndef IEACHE_KS_AHEAD
-#define IEACHE_KS_AHEAD 8
-#endif
 constexpr int kWaveGates = 128;   // four 32-row tiles
 constexpr int kWgWaves = 4;
 constexpr int kWgGates = kWaveGates * kWgWaves;
+static_assert(kWgGates == kKsMfmaWgGates, "ks_plan.h pads launches and sizes the digit scratch by the product's workgroup");
 
 // ---- key preparation: padded KSK [N][8][4][stride] int32 -> B fragments [N][ncb][4 limbs][64 lanes][16 bytes] ----
 __global__ __launch_bounds__(256) void k_ksm_prepare(const int32_t* __restrict__ ksk, int8_t* __restrict__ limbs, int32_t stride, int32_t ncb) {
@@ -97,7 +92,7 @@ __global__ __launch_bounds__(256) void k_ksm_init(DevKeys K, WorkDesc W, const T
                                                   Torus32** out_ptr) {
     const int64_t item = (int64_t)blockIdx.x;
     const int32_t n = K.n, stride = K.stride;
-    Torus32* out = flat_out ? flat_out + (size_t)item * stride : resolve(W, W.item0 + item, stride).out;
+    Torus32* out = ks_out_row(W, flat_out, item, stride);
     if (threadIdx.x == 0) out_ptr[item] = out;
     const Torus32 b = ext[(size_t)item * (K.N + 4) + K.N];
     for (int32_t q = threadIdx.x; q < stride; q += 256) out[q] = q == n ? b : 0;
@@ -120,7 +115,7 @@ __global__ __launch_bounds__(64 * kWgWaves) void k_ksm_gemm(const v4i* __restric
     __syncthreads();
     // Which (coefficient block, K split) stream and which block of 512 gates this workgroup takes.  Default: streams
     // fastest, so that every XCD (workgroups are dealt round-robin over them) walks all streams and each pulls the whole
-    // 84 MB through its L2 (measured: L2 hit rate 59 %, 0.55 GB of fetch per 8 192 gates).  xcd_map (IEACHE_KS_XCD=1) gives
+    // 84 MB through its L2 (measured: L2 hit rate 59 %, 0.55 GB of fetch per 8 192 gates).  xcd_map ("ks_xcd", IEACHE_KS_XCD=1) gives
     // each XCD its own eighth of the streams instead, walked by all its CUs together -- fewer bytes, but MEASURED SLOWER
     // (0.77 against 0.66 ms per 8 192 gates: thirty-two CUs hammering the same few L2 channels); kept as the A/B partner.
     const int32_t streams = ncb * ksplit;
@@ -157,7 +152,7 @@ __global__ __launch_bounds__(64 * kWgWaves) void k_ksm_gemm(const v4i* __restric
     // buffer c holds coefficient 4 i4 + c (kAhead = 8: of two consecutive i4) and is refilled with the coefficient kAhead further
     // on right after its products are issued
     constexpr int kAhead = IEACHE_KS_AHEAD;   // 4 or 8
-    constexpr int kGroups = kAhead / 4;       // i4 values per trip of the loop: every K split must hold a whole number of trips (split_ok)
+    constexpr int kGroups = kAhead / 4;       // i4 values per trip of the loop: every K split must hold a whole number of trips (ks_mfma_split_ok)
     static_assert(kAhead == 4 || kAhead == 8, "IEACHE_KS_AHEAD: B fragments are requested 4 or 8 coefficients ahead");
     v4i bq[kAhead][4];
     const v4i* bp0 = limbs + (size_t)cb * 256 + lane;
@@ -211,59 +206,20 @@ __global__ __launch_bounds__(64 * kWgWaves) void k_ksm_gemm(const v4i* __restric
 
 }  // namespace
 
-// A K split is usable when it divides the N / 4 digit groups and leaves every split a whole number (>= 1) of the loop's trips
-// of IEACHE_KS_AHEAD / 4 groups: the B fragments are preloaded a whole trip ahead, so a split shorter than a trip would multiply
-// the NEXT split's fragments by stale digits and preload past the end of the limb table.
-bool split_ok(const Params& p, int32_t ksplit) {
-    constexpr int32_t groups_per_trip = IEACHE_KS_AHEAD / 4;
-    if (ksplit < 1 || (p.N / 4) % ksplit != 0) return false;
-    const int32_t per_split = p.N / 4 / ksplit;
-    return per_split >= groups_per_trip && per_split % groups_per_trip == 0;
-}
-
-bool supported(const Params& p) { return p.ks_t == 8 && p.ks_basebit == 2 && p.k == 1 && p.N % 64 == 0 && p.N >= 64; }
-
-static int32_t coef_blocks(const Params& p) { return (p.lwe_stride() + 31) / 32; }
-static int64_t padded_items(int64_t items) { return (items + kWgGates - 1) / kWgGates * kWgGates; }
-
-size_t limb_matrix_bytes(const Params& p) { return (size_t)p.N * coef_blocks(p) * 4096; }
-
-size_t digit_scratch_bytes(const Params& p, int64_t items) {
-    const int64_t gpad = padded_items(items);
-    return (size_t)(p.N / 4) * gpad * 8 + (size_t)gpad * sizeof(Torus32*);
-}
-
 void prepare(const Params& p, const int32_t* d_ksk_padded, int8_t* d_limbs, hipStream_t stream) {
-    hipLaunchKernelGGL(k_ksm_prepare, dim3((unsigned)p.N, (unsigned)coef_blocks(p)), dim3(256), 0, stream, d_ksk_padded, d_limbs,
-                       p.lwe_stride(), coef_blocks(p));
+    hipLaunchKernelGGL(k_ksm_prepare, dim3((unsigned)p.N, (unsigned)ks_coef_blocks(p)), dim3(256), 0, stream, d_ksk_padded, d_limbs,
+                       p.lwe_stride(), ks_coef_blocks(p));
 }
 
 int launch(const Params& p, const DevKeys& K, const WorkDesc& W, int64_t items, const Torus32* ext, Torus32* flat_out,
-           const int8_t* d_limbs, void* d_digits, int32_t ksplit, int32_t cus, hipStream_t stream) {
+           const int8_t* d_limbs, void* d_digits, int32_t ksplit, int32_t xcd_map, hipStream_t stream) {
     if (items <= 0) return 0;
-    if (cus <= 0) cus = 256;
-    const int64_t gpad = padded_items(items);
-    const int32_t ncb = coef_blocks(p);
+    if (!ks_mfma_split_ok(p, ksplit)) throw std::invalid_argument("key-switch K split does not leave every split a whole trip of the product's loop");
+    const int64_t gpad = ks_mfma_padded_items(items);
+    const int32_t ncb = ks_coef_blocks(p);
     unsigned long long* dig4 = reinterpret_cast<unsigned long long*>(d_digits);
     Torus32** out_ptr = reinterpret_cast<Torus32**>(dig4 + (size_t)(p.N / 4) * gpad);
     const int64_t gblocks = gpad / kWgGates;
-    if (ksplit <= 0) {
-        // One workgroup (4 waves, all 512 registers each) per CU at a time: W = gblocks * ncb workgroups take ceil(W k / CUs)
-        // rounds of 1 / k of the walk each, plus a fixed cost per split (table build, one more pass of atomic adds).
-        // Measured at n = 630 (profiles/r3_keyswitch_mfma.txt): 512 gates k = 8, 1 024 k = 4, 2 304 k = 2, 8 192 k = 4, 16 384 k = 2.
-        const int64_t W0 = gblocks * ncb;
-        double best = 0;
-        for (int32_t k = 1; k <= 8; k *= 2) {
-            if (!split_ok(p, k)) break;
-            const double cost = (double)((W0 * k + cus - 1) / cus) / k + 0.02 * k;
-            if (ksplit <= 0 || cost < best) {
-                best = cost;
-                ksplit = k;
-            }
-        }
-    }
-    if (!split_ok(p, ksplit)) throw std::invalid_argument("key-switch K split does not leave every split a whole trip of the product's loop");
-    static const int32_t xcd_map = getenv("IEACHE_KS_XCD") ? atoi(getenv("IEACHE_KS_XCD")) : 0;  // measurement aid, see k_ksm_gemm
     hipLaunchKernelGGL(k_ksm_digits, dim3((unsigned)(p.N / 64), (unsigned)(gpad / 64)), dim3(256), 0, stream, ext, dig4, items, gpad, p.N);
     hipLaunchKernelGGL(k_ksm_init, dim3((unsigned)items), dim3(256), 0, stream, K, W, ext, flat_out, out_ptr);
     hipLaunchKernelGGL(k_ksm_gemm, dim3((unsigned)(gblocks * ncb * ksplit)), dim3(64 * kWgWaves), 0, stream,

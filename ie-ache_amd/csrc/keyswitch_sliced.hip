@@ -18,7 +18,7 @@
 //      from HBM / Infinity Cache once per XCD and served to all other workgroups by the L2, exactly
 //      like the blind rotation's BK blocks.  Partial sums live in the output rows between launches.
 // Subtraction mod 2^32 commutes, so the result is bit-identical to the other key-switch kernels.
-#include "keyswitch_sliced.h"
+#include "keyswitch_dev.h"
 
 #include <hip/hip_runtime.h>
 
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256) void k_keyswitch_sliced(DevKeys K, WorkDesc W,
         if (g < gcount) {
             const uint32_t a = (uint32_t)ext[(size_t)(item0 + g) * (N + 4) + i0 + ii] + prec_offset;
 #pragma unroll
-            for (int32_t j = 0; j < 8; j++) packed |= ((a >> (30 - 2 * j)) & 3u) << (2 * j);
+            for (int32_t j = 0; j < 8; j++) packed |= ks_digit(a, j, 2, 3u) << (2 * j);
         }
         dw[ii * G + g] = (uint16_t)packed;
     }
@@ -147,10 +147,7 @@ __global__ __launch_bounds__(256) void k_keyswitch_sliced(DevKeys K, WorkDesc W,
     for (int q = 0; q < (G + 7) / 8; q++)
 #pragma unroll
         for (int e = 0; e < 32; e++) acc[q][e] = 0;
-    auto out_row = [&](int g) -> Torus32* {
-        const int64_t it = item0 + g;
-        return flat_out ? flat_out + (size_t)it * stride : resolve(W, W.item0 + it, stride).out;
-    };
+    auto out_row = [&](int g) -> Torus32* { return ks_out_row(W, flat_out, item0 + g, stride); };
     if (i0 == 0) {
         if (col == (n >> 2)) {  // the column holding b'
 #pragma unroll
@@ -229,13 +226,6 @@ __global__ __launch_bounds__(256) void k_keyswitch_sliced(DevKeys K, WorkDesc W,
 
 }  // namespace
 
-bool supported(const Params& p) {
-    // one int4 column per lane of at most 4 waves; libtfhe's key-switch decomposition
-    return p.ks_t == 8 && p.ks_basebit == 2 && p.lwe_stride() / 4 <= 256 && p.N % 8 == 0;
-}
-
-int32_t max_slice() { return 1024; }  // digits of a slice in LDS: slice * G * 2 bytes <= 64 KiB
-
 template <int G>
 static void launch_g(const DevKeys& K, const WorkDesc& W, int64_t items, const Torus32* ext, Torus32* flat_out, int32_t i0, int32_t i1,
                      int nld, hipStream_t stream) {
@@ -249,12 +239,8 @@ int launch(const Params& p, const DevKeys& K, const WorkDesc& W, int64_t items, 
            int32_t slice, int32_t gates_per_wg, hipStream_t stream) {
     const int nld = (p.lwe_stride() / 4 + 63) / 64;
     const int32_t nco = p.N * p.k;
-    if (slice < 1 || slice > max_slice()) slice = max_slice();
-    if (slice > nco) slice = nco;
-    // gates per workgroup: fewer row fetches per gate with 32, more workgroups in flight with 16 / 8
-    int g = gates_per_wg;
-    if (g != 4 && g != 8 && g != 16 && g != 32)  // measured (profiles/r1_v8_kernel_microbench.txt): 1024 -> 4, 2048-4096 -> 8, 8192 -> 16
-        g = items >= 14336 ? 32 : (items >= 5120 ? 16 : (items >= 1536 ? 8 : 4));
+    const int g = gates_per_wg;
+    if (slice < 1 || slice > kKsMaxSlice || (g != 4 && g != 8 && g != 16 && g != 32)) throw std::invalid_argument("sliced key switch: slice or gates per workgroup");
     int launches = 0;
     for (int32_t i0 = 0; i0 < nco; i0 += slice) {
         const int32_t i1 = i0 + slice < nco ? i0 + slice : nco;
