@@ -13,7 +13,7 @@
 //     9 KiB LDS table.
 //   * the 512-point complex transform is 8 x 8 x 8 (fft512.h) with the register part of the negacyclic twist folded into its
 //     first / last radix-8 pass.
-// One kernel per launch-size regime (variant table in blind_rotate_w64.h):
+// One kernel per launch-size regime (which one takes a launch: br_plan.h):
 //   k_blind_rotate_w1b    one wave per gate            launches of more than 5 gates per CU (the throughput kernel)
 //   k_blind_rotate_w2r    two waves per gate           2 .. 5 gates per CU
 //   k_blind_rotate_w4r    four waves per gate          1 .. 2 gates per CU
@@ -29,7 +29,6 @@
 #include "blind_rotate_w64.h"
 
 #include <cstdio>
-#include <cstdlib>
 #include <algorithm>
 #include <stdexcept>
 #include <type_traits>
@@ -1065,29 +1064,8 @@ __global__ __launch_bounds__(128 * L) void k_blind_rotate_wide4(DevKeys K, const
 
 }  // namespace
 
-// N=1024, k=1 with either libtfhe parameter set: l=3/Bgbit=7 (>= v1.1, "128-bit") or l=2/Bgbit=10
-// (v1.0 and the paper's 78 MiB keys).  Exactness margin for the latter: 4 rows x 1024 x 512 x 2^15 < 2^37.
-bool supported(const Params& p) {
-    return p.N == kN && p.k == 1 && ((p.l == 3 && p.Bgbit == 7) || (p.l == 2 && p.Bgbit == 10)) && p.n <= 4096;
-}
-
-// The one-limb kernels round sums of up to 2l x N x 2^(Bgbit-1) x 2^31: 2^49.6 for l=3 / Bgbit=7, where the measured
-// rounding error is 35x below the guard's limit.  For l=2 / Bgbit=10 the worst case is 2^52 and the typical error 6.5x
-// larger -- inside 0.5 but no longer clear of the limit -- so that set stays on the two-limb kernels.
-bool one_limb_supported(const Params& p) { return supported(p) && p.l == 3 && p.Bgbit == 7; }
-
 size_t spectrum_elems(const Params& p) { return (size_t)p.n * p.kpl() * 4 * kM; }
 size_t spectrum1_elems(const Params& p) { return (size_t)p.n * p.kpl() * 2 * kM; }
-size_t lds_bytes_w1(int wg_gates) { return (size_t)(wg_gates * kTile + kTwElems) * sizeof(double2) + (size_t)wg_gates * 2 * kN * 4; }
-int gates_per_workgroup_w1() { return kW1Gates; }
-
-static size_t lds_w2(int, int32_t, int);
-size_t lds_bytes(const Params& p) { return lds_w2(p.l, 0, 1); }  // k_blind_rotate_w2 / _w2r
-
-int32_t bara_stride(const Params& p) { return (p.n + 7) & ~7; }
-
-size_t state_bytes_per_item(const Params& p) { return (size_t)bara_stride(p) * 2 + (size_t)2 * kN * 4; }
-
 size_t twiddle_table_elems() { return kTwElems; }
 
 void build_twiddle_table(double2* d_tw, hipStream_t stream) {
@@ -1104,29 +1082,12 @@ void prepare_spectrum1(const Params& p, const Torus32* d_bk_raw, double2* d_bkf1
     hipLaunchKernelGGL(k_bk_to_spectrum_w64_1, dim3((unsigned)npoly), dim3(64), 0, stream, d_bk_raw, d_bkf1);
 }
 
-static int32_t device_cus() {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return cus > 0 ? cus : 256;
-}
-
 // diagnostic builds (br_variant 8 / 49): per-segment s_memtime sums, printed per launch() call
-static unsigned long long* diag_buf() {
-    static unsigned long long* p = nullptr;
-    if (!p) {
-        if (hipMalloc(&p, 16 * sizeof(unsigned long long)) != hipSuccess ||
-            hipMemset(p, 0, 16 * sizeof(unsigned long long)) != hipSuccess) {
-            p = nullptr;
-            throw std::runtime_error("hipMalloc failed for the blind-rotation diagnostic buffer");
-        }
-    }
-    return p;
-}
-static void diag_report(hipStream_t stream, const char* tag, const char* const* names, int nnames, double denom) {
+static void diag_report(hipStream_t stream, unsigned long long* buf, const char* tag, const char* const* names, int nnames, double denom) {
     unsigned long long h[16];
     (void)hipStreamSynchronize(stream);
-    (void)hipMemcpy(h, diag_buf(), sizeof h, hipMemcpyDeviceToHost);
-    (void)hipMemset(diag_buf(), 0, sizeof h);
+    (void)hipMemcpy(h, buf, sizeof h, hipMemcpyDeviceToHost);
+    (void)hipMemset(buf, 0, sizeof h);
     for (int w = 0; w < 2; w++) {
         double tot = 0;
         for (int t = 0; t < nnames; t++) tot += (double)h[w * 8 + t];
@@ -1136,48 +1097,33 @@ static void diag_report(hipStream_t stream, const char* tag, const char* const* 
     }
 }
 
-// workgroups i and i + period are taken to share a CU: the device's CU count (IEACHE_W4R_FLIP overrides; a huge value = never flip)
-static int32_t w4r_flip_period() {
-    static const int32_t v = [] {
-        if (const char* e = getenv("IEACHE_W4R_FLIP")) return atoi(e) > 0 ? atoi(e) : 1 << 30;
-        return device_cus();
-    }();
-    return v;
-}
-
-// ---- the variants: one row per br_variant number that exists (blind_rotate_w64.h lists them for readers) ----
+// ---- the launch half of the variant table: one row per build of a br_variant number (br_plan.h: kBrVariants) ----
 // one launch: CMux steps [i0, i1) of `items` gate instances, parameter set l
 struct Slice {
     int32_t l;
     int64_t items;
     hipStream_t stream;
     const DevKeys& K;
-    const double2 *bkf2, *bkf1;
+    const Tables& t;
     const uint16_t* st_bara;
     int32_t nb;
     int32_t* st_acc;
     int32_t i0, i1;
     Torus32* ext;
-    unsigned* guard;
-    const double2* gtw;
+    int32_t flip;  // k_blind_rotate_w4r: BrPlan::w4r_flip
 };
 constexpr int kTwoLWaves = 0;
-struct Variant {
-    int32_t number;     // "br_variant"
-    const char* name;   // the kernel
-    bool chosen;        // what the evaluator's choice by launch size reports under the kernel's name; false: a measurement or
-                        // diagnostic build of it, reported by number
-    int limbs;          // 1: the one-limb spectrum and the guard record (the sampled audit applies); 2: exact by construction
-    bool long_slices;   // keeps a slice's rotation amounts in LDS or reloads them every 64 steps: a slice may be the whole rotation
+struct LaunchRow {
+    int32_t number;     // "br_variant": a row of kBrVariants
+    int gates;          // per workgroup: the variant's default build, or one of its smaller ones
     int threads;        // per workgroup; kTwoLWaves: 128 L (2L waves per gate)
-    int gates;          // per workgroup
     size_t (*lds)(int L, int32_t nb, int gates);  // dynamic LDS of a launch
     size_t allow;       // bytes of dynamic LDS to be allowed first; 0: the launch fits the default 64 KiB
-    void (*launch)(const Variant&, const Slice&);
-    mutable LdsGrant granted[2];  // ... remembered per kernel (parameter set) and device
+    void (*launch)(const LaunchRow&, const Slice&);
 };
+static LdsGrant& granted(const LaunchRow& v, int param_set);  // ... remembered per kernel (parameter set) and device
 
-// the one place that turns the runtime parameter set into template arguments (supported(): these two only)
+// the one place that turns the runtime parameter set into template arguments (br_supported(): these two only)
 template <int L_, int BGBIT_>
 struct ParamSet {
     static constexpr int L = L_, BGBIT = BGBIT_, index = L_ == 3 ? 0 : 1;
@@ -1194,167 +1140,153 @@ struct as_is {
     using type = T;
 };
 template <class PS, class... P>
-static void launch_row(PS, const Variant& v, const Slice& s, void (*kernel)(P...), typename as_is<P>::type... args) {
+static void launch_row(PS, const LaunchRow& v, const Slice& s, void (*kernel)(P...), typename as_is<P>::type... args) {
     if (v.allow) {
         char what[96];  // the instantiation, for the message of a refused opt-in
-        snprintf(what, sizeof what, "%s<%d,%d> (br_variant %d, %d gates per workgroup)", v.name, PS::L, PS::BGBIT, (int)v.number, v.gates);
-        allow_dynamic_lds_once(v.granted[PS::index], (const void*)kernel, v.allow, what);
+        snprintf(what, sizeof what, "%s<%d,%d> (br_variant %d, %d gates per workgroup)", br_variant(v.number)->name, PS::L, PS::BGBIT, (int)v.number, v.gates);
+        allow_dynamic_lds_once(granted(v, PS::index), (const void*)kernel, v.allow, what);
     }
     hipLaunchKernelGGL(kernel, dim3((unsigned)((s.items + v.gates - 1) / v.gates)), dim3(v.threads == kTwoLWaves ? 128 * PS::L : v.threads),
                        v.lds(PS::L, s.nb, v.gates), s.stream, args...);
 }
 // one launcher per kernel (their argument lists differ), instantiated for both parameter sets
 template <int XLANE>
-static void go_w2(const Variant& v, const Slice& s) {
+static void go_w2(const LaunchRow& v, const Slice& s) {
     with_param_set(s.l, [&](auto ps) {
-        launch_row(ps, v, s, k_blind_rotate_w2<ps.L, ps.BGBIT, XLANE>, s.K, s.bkf2, s.st_bara, s.nb, s.st_acc, s.i0, s.i1, s.ext, s.gtw);
+        launch_row(ps, v, s, k_blind_rotate_w2<ps.L, ps.BGBIT, XLANE>, s.K, s.t.bkf, s.st_bara, s.nb, s.st_acc, s.i0, s.i1, s.ext, s.t.twiddles);
     });
 }
 template <int G>
-static void go_x1(const Variant& v, const Slice& s) {
+static void go_x1(const LaunchRow& v, const Slice& s) {
     with_param_set(s.l, [&](auto ps) {
-        launch_row(ps, v, s, k_blind_rotate_x1<ps.L, ps.BGBIT, G>, s.K, s.bkf2, s.st_bara, s.nb, s.st_acc, s.items, s.i0, s.i1, s.ext, s.gtw);
+        launch_row(ps, v, s, k_blind_rotate_x1<ps.L, ps.BGBIT, G>, s.K, s.t.bkf, s.st_bara, s.nb, s.st_acc, s.items, s.i0, s.i1, s.ext, s.t.twiddles);
     });
 }
 template <bool DIAG, int LIMBS>
-static void go_wide(const Variant& v, const Slice& s) {
+static void go_wide(const LaunchRow& v, const Slice& s) {
     with_param_set(s.l, [&](auto ps) {
-        launch_row(ps, v, s, k_blind_rotate_wide<ps.L, ps.BGBIT, DIAG, LIMBS>, s.K, LIMBS == 2 ? s.bkf2 : s.bkf1, s.st_bara, s.nb, s.st_acc,
-                   s.i0, s.i1, s.ext, DIAG ? diag_buf() : nullptr, s.gtw, LIMBS == 2 ? nullptr : s.guard);
+        launch_row(ps, v, s, k_blind_rotate_wide<ps.L, ps.BGBIT, DIAG, LIMBS>, s.K, LIMBS == 2 ? s.t.bkf : s.t.bkf1, s.st_bara, s.nb, s.st_acc,
+                   s.i0, s.i1, s.ext, DIAG ? s.t.diag : nullptr, s.t.twiddles, LIMBS == 2 ? nullptr : s.t.guard);
     });
 }
 template <int GUARD, bool DIAG = false, int G = kW1Gates>
-static void go_w1b(const Variant& v, const Slice& s) {
+static void go_w1b(const LaunchRow& v, const Slice& s) {
     with_param_set(s.l, [&](auto ps) {
-        launch_row(ps, v, s, k_blind_rotate_w1b<ps.L, ps.BGBIT, GUARD, DIAG, G>, s.K, s.bkf1, s.st_bara, s.nb, s.st_acc, s.items, s.i0, s.i1,
-                   s.ext, s.guard, s.gtw, DIAG ? diag_buf() : nullptr);
+        launch_row(ps, v, s, k_blind_rotate_w1b<ps.L, ps.BGBIT, GUARD, DIAG, G>, s.K, s.t.bkf1, s.st_bara, s.nb, s.st_acc, s.items, s.i0, s.i1,
+                   s.ext, s.t.guard, s.t.twiddles, DIAG ? s.t.diag : nullptr);
     });
 }
 template <int GUARD>
-static void go_w2r(const Variant& v, const Slice& s) {
+static void go_w2r(const LaunchRow& v, const Slice& s) {
     with_param_set(s.l, [&](auto ps) {
-        launch_row(ps, v, s, k_blind_rotate_w2r<ps.L, ps.BGBIT, GUARD>, s.K, s.bkf1, s.st_bara, s.nb, s.st_acc, s.i0, s.i1, s.ext, s.guard, s.gtw);
+        launch_row(ps, v, s, k_blind_rotate_w2r<ps.L, ps.BGBIT, GUARD>, s.K, s.t.bkf1, s.st_bara, s.nb, s.st_acc, s.i0, s.i1, s.ext, s.t.guard, s.t.twiddles);
     });
 }
 template <int GUARD>
-static void go_w4r(const Variant& v, const Slice& s) {
+static void go_w4r(const LaunchRow& v, const Slice& s) {
     with_param_set(s.l, [&](auto ps) {
-        launch_row(ps, v, s, k_blind_rotate_w4r<ps.L, ps.BGBIT, GUARD>, s.K, s.bkf1, s.st_bara, s.nb, s.st_acc, s.i0, s.i1, s.ext, s.guard, s.gtw,
-                   w4r_flip_period());
+        launch_row(ps, v, s, k_blind_rotate_w4r<ps.L, ps.BGBIT, GUARD>, s.K, s.t.bkf1, s.st_bara, s.nb, s.st_acc, s.i0, s.i1, s.ext, s.t.guard, s.t.twiddles,
+                   s.flip);
     });
 }
 template <int GUARD>
-static void go_wide4(const Variant& v, const Slice& s) {
+static void go_wide4(const LaunchRow& v, const Slice& s) {
     with_param_set(s.l, [&](auto ps) {
-        launch_row(ps, v, s, k_blind_rotate_wide4<ps.L, ps.BGBIT, GUARD>, s.K, s.bkf1, s.st_bara, s.nb, s.st_acc, s.i0, s.i1, s.ext, s.guard, s.gtw);
+        launch_row(ps, v, s, k_blind_rotate_wide4<ps.L, ps.BGBIT, GUARD>, s.K, s.t.bkf1, s.st_bara, s.nb, s.st_acc, s.i0, s.i1, s.ext, s.t.guard, s.t.twiddles);
     });
 }
 
 constexpr size_t kAccBytes = (size_t)2 * kN * 4, kCuLds = 160 * 1024;
+// LDS per workgroup: 4 gates -> 2 workgroups per CU, 3 -> 2, 2 -> 3, 1 -> 6
+constexpr size_t lds_bytes_w1(int wg_gates) { return (size_t)(wg_gates * kTile + kTwElems) * sizeof(double2) + (size_t)wg_gates * 2 * kN * 4; }
 static size_t lds_w1(int, int32_t, int gates) { return lds_bytes_w1(gates); }
 static size_t lds_w2(int, int32_t, int) { return (size_t)(2 * kTile + kTwElems) * sizeof(double2) + kAccBytes; }
 static size_t lds_w4(int, int32_t, int) { return (size_t)(4 * kTile + 2 * 8 * 64 + kTwElems) * sizeof(double2) + kAccBytes; }
 static size_t lds_wide(int L, int32_t nb, int) { return (size_t)(2 * L * kTile + kTwElems) * sizeof(double2) + kAccBytes + (size_t)nb * 2; }
 static size_t lds_wide4(int L, int32_t nb, int) { return (size_t)((2 * L + 4) * kTile + kTwElems) * sizeof(double2) + kAccBytes + (size_t)nb * 2; }
 
-// The default row of a number stands first; the rows behind it with fewer gates per workgroup are the builds a launch that
-// does not fill the chip takes (wg_gates of launch(): the two kernels wide launches use, G = 1 .. 3).
-static const Variant kVariants[] = {
-    // number                        kernel                 chosen limbs long threads gates LDS      allow            launcher
+// What a number means (kernel, limbs, slice lengths, which builds exist) is its row in kBrVariants; the rows here with
+// fewer gates per workgroup than the variant's default are the builds a launch that does not fill the chip takes.
+static constexpr LaunchRow kLaunchRows[] = {
+    // number, gates per workgroup, threads, LDS, allow, launcher
     // ---- two limbs: exact by construction ----
-    {0,                              "k_blind_rotate_w2",    true,  2, false, 128, 1, lds_w2,    0,               go_w2<1>},
-    {kVariantTwoWavesLds,            "k_blind_rotate_w2",    false, 2, false, 128, 1, lds_w2,    0,               go_w2<0>},         // every transpose through LDS (round 1)
-    {kVariantExactOneWave,           "k_blind_rotate_x1",    true,  2, false, 256, 4, lds_w1,    lds_bytes_w1(4), go_x1<4>},
-    {kVariantExactOneWave,           "k_blind_rotate_x1",    true,  2, false, 192, 3, lds_w1,    lds_bytes_w1(3), go_x1<3>},
-    {kVariantExactOneWave,           "k_blind_rotate_x1",    true,  2, false, 128, 2, lds_w1,    lds_bytes_w1(2), go_x1<2>},
-    {kVariantExactOneWave,           "k_blind_rotate_x1",    true,  2, false, 64,  1, lds_w1,    lds_bytes_w1(1), go_x1<1>},
-    {kVariantWide,                   "k_blind_rotate_wide",  true,  2, true,  kTwoLWaves, 1, lds_wide,  kCuLds,          go_wide<false, 2>},
-    {kVariantWide + 1,               "k_blind_rotate_wide",  false, 2, true,  kTwoLWaves, 1, lds_wide,  kCuLds,          go_wide<true, 2>},  // phase stamps
-    // ---- one limb, guarded (on one rounded coefficient in four unless noted) ----
-    {kVariantWideOneLimb,            "k_blind_rotate_wide",  false, 1, true,  kTwoLWaves, 1, lds_wide,  kCuLds,          go_wide<false, 1>}, // A/B partner of k_blind_rotate_wide4
-    {kVariantOneLimbDefault,         "k_blind_rotate_w1b",   true,  1, false, 256, 4, lds_w1,    lds_bytes_w1(4), go_w1b<2>},
-    {kVariantOneLimbDefault,         "k_blind_rotate_w1b",   true,  1, false, 192, 3, lds_w1,    lds_bytes_w1(3), go_w1b<2, false, 3>},
-    {kVariantOneLimbDefault,         "k_blind_rotate_w1b",   true,  1, false, 128, 2, lds_w1,    lds_bytes_w1(2), go_w1b<2, false, 2>},
-    {kVariantOneLimbDefault,         "k_blind_rotate_w1b",   true,  1, false, 64,  1, lds_w1,    lds_bytes_w1(1), go_w1b<2, false, 1>},
-    {kVariantOneLimbDefault + 1,     "k_blind_rotate_w1b",   false, 1, false, 256, 4, lds_w1,    lds_bytes_w1(4), go_w1b<1>},         // guard on every coefficient
-    {kVariantOneLimbDefault + 4,     "k_blind_rotate_w1b",   false, 1, false, 256, 4, lds_w1,    lds_bytes_w1(4), go_w1b<0>},         // no guard arithmetic (measurement)
-    {kVariantOneLimbStamps,          "k_blind_rotate_w1b",   false, 1, false, 256, 4, lds_w1,    lds_bytes_w1(4), go_w1b<2, true>},   // phase stamps
-    {kVariantOneLimbTwoWaves,        "k_blind_rotate_w2r",   true,  1, true,  128, 1, lds_w2,    0,               go_w2r<2>},
-    {kVariantOneLimbTwoWaves + 1,    "k_blind_rotate_w2r",   false, 1, true,  128, 1, lds_w2,    0,               go_w2r<1>},         // guard on every coefficient
-    {kVariantOneLimbFourWaves,       "k_blind_rotate_w4r",   true,  1, true,  256, 1, lds_w4,    kCuLds,          go_w4r<2>},
-    {kVariantOneLimbFourWaves + 1,   "k_blind_rotate_w4r",   false, 1, true,  256, 1, lds_w4,    kCuLds,          go_w4r<1>},
-    {kVariantWideHandoverOneLimb,    "k_blind_rotate_wide4", true,  1, true,  kTwoLWaves, 1, lds_wide4, kCuLds,          go_wide4<2>},
-    {kVariantWideHandoverOneLimb + 1, "k_blind_rotate_wide4", false, 1, true, kTwoLWaves, 1, lds_wide4, kCuLds,          go_wide4<1>},
+    {0, 1, 128, lds_w2, 0, go_w2<1>},
+    {kVariantTwoWavesLds, 1, 128, lds_w2, 0, go_w2<0>},
+    {kVariantExactOneWave, 4, 256, lds_w1, lds_bytes_w1(4), go_x1<4>},
+    {kVariantExactOneWave, 3, 192, lds_w1, lds_bytes_w1(3), go_x1<3>},
+    {kVariantExactOneWave, 2, 128, lds_w1, lds_bytes_w1(2), go_x1<2>},
+    {kVariantExactOneWave, 1, 64, lds_w1, lds_bytes_w1(1), go_x1<1>},
+    {kVariantWide, 1, kTwoLWaves, lds_wide, kCuLds, go_wide<false, 2>},
+    {kVariantWideStamps, 1, kTwoLWaves, lds_wide, kCuLds, go_wide<true, 2>},
+    // ---- one limb, guarded ----
+    {kVariantWideOneLimb, 1, kTwoLWaves, lds_wide, kCuLds, go_wide<false, 1>},
+    {kVariantOneLimbDefault, 4, 256, lds_w1, lds_bytes_w1(4), go_w1b<2>},
+    {kVariantOneLimbDefault, 3, 192, lds_w1, lds_bytes_w1(3), go_w1b<2, false, 3>},
+    {kVariantOneLimbDefault, 2, 128, lds_w1, lds_bytes_w1(2), go_w1b<2, false, 2>},
+    {kVariantOneLimbDefault, 1, 64, lds_w1, lds_bytes_w1(1), go_w1b<2, false, 1>},
+    {kVariantOneLimbDefault + 1, 4, 256, lds_w1, lds_bytes_w1(4), go_w1b<1>},
+    {kVariantOneLimbDefault + 4, 4, 256, lds_w1, lds_bytes_w1(4), go_w1b<0>},
+    {kVariantOneLimbStamps, 4, 256, lds_w1, lds_bytes_w1(4), go_w1b<2, true>},
+    {kVariantOneLimbTwoWaves, 1, 128, lds_w2, 0, go_w2r<2>},
+    {kVariantOneLimbTwoWaves + 1, 1, 128, lds_w2, 0, go_w2r<1>},
+    {kVariantOneLimbFourWaves, 1, 256, lds_w4, kCuLds, go_w4r<2>},
+    {kVariantOneLimbFourWaves + 1, 1, 256, lds_w4, kCuLds, go_w4r<1>},
+    {kVariantWideHandoverOneLimb, 1, kTwoLWaves, lds_wide4, kCuLds, go_wide4<2>},
+    {kVariantWideHandoverOneLimb + 1, 1, kTwoLWaves, lds_wide4, kCuLds, go_wide4<1>},
 };
-// the row of `number` built for `gates` per workgroup, else its default row; null: no such variant
-static const Variant* find_variant(int32_t number, int gates = 0) {
-    const Variant* first = nullptr;
-    for (const Variant& v : kVariants) {
-        if (v.number != number) continue;
-        if (v.gates == gates) return &v;
-        if (!first) first = &v;
-    }
-    return first;
+constexpr size_t kLaunchRowCount = sizeof kLaunchRows / sizeof kLaunchRows[0];
+static LdsGrant g_granted[kLaunchRowCount][2];
+static LdsGrant& granted(const LaunchRow& v, int param_set) { return g_granted[&v - kLaunchRows][param_set]; }
+
+// every launch row is a build kBrVariants names, and every build it names has exactly one launch row
+constexpr bool launch_rows_match_variants() {
+    for (const LaunchRow& r : kLaunchRows)
+        if (!br_variant_build(r.number, r.gates)) return false;
+    for (const BrVariant& v : kBrVariants)
+        for (int g = v.wg_builds ? 1 : v.gates; g <= v.gates; g++) {
+            int rows = 0;
+            for (const LaunchRow& r : kLaunchRows) rows += r.number == v.number && r.gates == g;
+            if (rows != 1) return false;
+        }
+    return true;
 }
-bool variant_known(int32_t v) { return find_variant(v) != nullptr; }
-bool variant_one_limb(int32_t v) {
-    const Variant* r = find_variant(v);
-    return r && r->limbs == 1;
-}
-const char* variant_kernel_name(int32_t v) {
-    const Variant* r = find_variant(v);
-    return r && r->chosen ? r->name : nullptr;
-}
+static_assert(launch_rows_match_variants(), "kLaunchRows and kBrVariants (br_plan.h) name different variants or builds");
 
 // one slice of CMux steps on the kernel `variant` names, wg gates per workgroup where the kernel is built for that
 static void launch_slice(int variant, int wg, const Slice& s) {
-    const Variant* v = find_variant(variant, wg);
+    const BrVariant* v = br_variant(variant);
     if (!v) throw std::invalid_argument("unknown blind-rotation variant");
-    v->launch(*v, s);
-}
-
-int32_t default_variant() {
-    static const int32_t v = [] {
-        const int32_t e = getenv("IEACHE_BR_VARIANT") ? atoi(getenv("IEACHE_BR_VARIANT")) : 0;
-        if (variant_known(e)) return e;
-        // a retired number (an old A/B script): say so rather than measure the default kernel under the wrong label
-        fprintf(stderr, "ieache: IEACHE_BR_VARIANT=%d names no kernel of this build (csrc/blind_rotate_w64.h); using the default choice by launch size\n", (int)e);
-        return (int32_t)0;
-    }();
-    return v;
-}
-
-int32_t default_slice() {
-    static const int32_t s = getenv("IEACHE_BR_SLICE") ? atoi(getenv("IEACHE_BR_SLICE")) : 16;
-    return s > 0 ? (s < 64 ? s : 64) : 16;  // <= 64: one rotation amount per lane
+    const int gates = br_variant_build(variant, wg) ? wg : v->gates;
+    for (const LaunchRow& r : kLaunchRows)
+        if (r.number == variant && r.gates == gates) return r.launch(r, s);
 }
 
 // A mid-size launch (more gates than fit two waves each, fewer than fill the chip with one wave each) as a ROTATION OF ROLES:
-// the items are cut into plan.k contiguous subsets, each driven by its own stream; in phase t the subsets t .. t + tw - 1
+// the items are cut into mix.k contiguous subsets, each driven by its own stream; in phase t the subsets t .. t + tw - 1
 // (mod k) advance s2 CMux steps on the two-waves-per-gate kernel while the others advance s1 steps on the one-wave-per-gate
 // kernel, so that all eight wave slots of every CU work (a gate is one sequential chain of steps: with one wave per gate
 // 1 536 gates can keep only 1 536 of the chip's 2 048 slots busy).  After `cycles` rounds of k phases every subset has done
 // cycles x (tw s2 + (k - tw) s1) steps; the caller's ordinary slice loop finishes the rotation from there on the main stream.
 // Same kernels, same arithmetic per step: bit-identical to any other schedule.  Returns the kernel launches issued.
-static int launch_mixed_phases(const Params& p, const DevKeys& K, const double2* d_bkf1, unsigned* guard, int64_t items,
-                               int32_t* st_acc, uint16_t* st_bara, int32_t nb, const double2* d_twiddles, const MixPlan& plan,
-                               int32_t* steps_done) {
+static int launch_mixed_phases(const Params& p, const DevKeys& K, const Tables& tab, int64_t items, int32_t* st_acc, uint16_t* st_bara,
+                               int32_t nb, const BrPlan& plan, const BrLanes& on, int32_t* steps_done) {
     int launches = 0;
-    const int k = plan.k, tw = plan.tw;
+    const int k = plan.mix.k, tw = plan.mix.tw;
+    const MixSteps& ms = plan.mix_steps;
     auto ok = [](hipError_t e) {  // a failed record / wait would leave the streams unordered: stop here rather than compute on stale state
         if (e != hipSuccess) throw std::runtime_error(std::string("rotation of roles: ") + hipGetErrorString(e));
     };
     // contiguous subsets of whole workgroups of the one-wave kernel (4 gates) -- and of 3, the other workgroup size
     const int64_t per = mix_subset_size(items, k);
     std::vector<int32_t> pos(k, 0);
-    hipStream_t main = plan.streams[0];
-    ok(hipEventRecord(plan.ev[0], main));  // the prologue is on the main stream
-    for (int j = 1; j < k; j++) ok(hipStreamWaitEvent(plan.streams[j], plan.ev[0], 0));
-    const int32_t rounds = plan.cycles + ((plan.tail_s1 > 0 && plan.tail_s2 > 0) ? 1 : 0);
+    hipStream_t main = on.streams[0];
+    ok(hipEventRecord(on.ev[0], main));  // the prologue is on the main stream
+    for (int j = 1; j < k; j++) ok(hipStreamWaitEvent(on.streams[j], on.ev[0], 0));
+    const int32_t rounds = ms.cycles + ((ms.tail_s1 > 0 && ms.tail_s2 > 0) ? 1 : 0);
     int32_t total = 0;
     for (int32_t c = 0; c < rounds; c++) {
         // the last round may be a shortened one (tail_s1 / tail_s2) that takes the rotation close to its end
-        const int32_t s1c = c < plan.cycles ? plan.s1 : plan.tail_s1, s2c = c < plan.cycles ? plan.s2 : plan.tail_s2;
+        const int32_t s1c = c < ms.cycles ? ms.s1 : ms.tail_s1, s2c = c < ms.cycles ? ms.s2 : ms.tail_s2;
         total += tw * s2c + (k - tw) * s1c;
         for (int t = 0; t < k; t++) {
             for (int j = 0; j < k; j++) {
@@ -1365,66 +1297,71 @@ static int launch_mixed_phases(const Params& p, const DevKeys& K, const double2*
                 while (todo > 0) {  // the one-wave kernel takes at most 64 steps per launch (one rotation amount per lane)
                     const int32_t s = two ? todo : std::min<int32_t>(todo, 64);
                     const int v = two ? kVariantOneLimbTwoWaves : kVariantOneLimbDefault;
-                    launch_slice(v, plan.wg, Slice{p.l, m, plan.streams[j], K, nullptr, d_bkf1, st_bara + (size_t)off * nb, nb,
-                                                   st_acc + (size_t)off * 2 * kN, pos[j], pos[j] + s, nullptr, guard, d_twiddles});
+                    launch_slice(v, plan.mix_wg, Slice{p.l, m, on.streams[j], K, tab, st_bara + (size_t)off * nb, nb,
+                                                       st_acc + (size_t)off * 2 * kN, pos[j], pos[j] + s, nullptr, plan.w4r_flip});
                     pos[j] += s;
                     todo -= s;
                     launches++;
                 }
             }
-            if (plan.sync && !(c == rounds - 1 && t == k - 1)) {
+            if (plan.mix_sync && !(c == rounds - 1 && t == k - 1)) {
                 // phase boundary: nobody starts the next phase before everybody has finished this one (the roles change)
-                for (int j = 0; j < k; j++) ok(hipEventRecord(plan.ev[j], plan.streams[j]));
+                for (int j = 0; j < k; j++) ok(hipEventRecord(on.ev[j], on.streams[j]));
                 for (int j = 0; j < k; j++)
                     for (int q = 0; q < k; q++)
-                        if (q != j) ok(hipStreamWaitEvent(plan.streams[j], plan.ev[q], 0));
+                        if (q != j) ok(hipStreamWaitEvent(on.streams[j], on.ev[q], 0));
             }
         }
     }
     for (int j = 1; j < k; j++) {  // join: the main stream finishes the rotation
-        ok(hipEventRecord(plan.ev[j], plan.streams[j]));
-        ok(hipStreamWaitEvent(main, plan.ev[j], 0));
+        ok(hipEventRecord(on.ev[j], on.streams[j]));
+        ok(hipStreamWaitEvent(main, on.ev[j], 0));
     }
     *steps_done = total;
     return launches;
 }
 
-int launch(const Params& p, const DevKeys& K, const double2* d_bkf, const double2* d_bkf1, unsigned* guard, const WorkDesc& W,
-           int64_t items, void* state, Torus32* ext, int32_t steps, Torus32* dbg_acc, int32_t slice, int32_t variant,
-           const double2* d_twiddles, hipStream_t stream, int wg_gates, const MixPlan* mix) {
-    if (!variant_known(variant)) throw std::invalid_argument("unknown blind-rotation variant");
-    if (variant_one_limb(variant) && (!d_bkf1 || !guard)) throw std::runtime_error("one-limb blind rotation without its spectrum / guard word");
+int launch(const Params& p, const DevKeys& K, const Tables& t, const BrPlan& plan, const BrLanes& mix, hipStream_t stream,
+           const WorkDesc& W, int64_t items, void* state, Torus32* ext, int32_t steps, Torus32* dbg_acc) {
+    const BrVariant* row = br_variant(plan.variant);
+    if (plan.generic || !row) throw std::invalid_argument("unknown blind-rotation variant");
+    if (row->limbs == 1 && (!t.bkf1 || !t.guard)) throw std::runtime_error("one-limb blind rotation without its spectrum / guard word");
+    const int32_t nb = br_bara_stride(p);
+    const int32_t nsteps = steps < 0 ? p.n : (steps < p.n ? steps : p.n);
+    // not decisions, the kernels' bounds: a slice's rotation amounts fit a lane each unless the kernel has long_slices (every
+    // slice ends at nsteps <= nb at the latest); a rotation of roles leaves the loop below a step, runs on the launch's own
+    // stream and on streams that exist
+    const int32_t S = plan.slice;
+    if (S < 1 || (!row->long_slices && S > 64)) throw std::logic_error("blind-rotation plan: slice length out of the kernel's range");
+    const int k = plan.mix.k;
+    if (k && (k < 2 || k > kMaxLanes || plan.mix.tw < 1 || plan.mix.tw >= k || row->limbs != 1 || plan.mix_steps.s1 < 1 || plan.mix_steps.s2 < 1 ||
+              plan.mix_steps.cycles < 1 || plan.mix_steps.covered >= nsteps || mix.streams[0] != stream))
+        throw std::logic_error("blind-rotation plan: rotation of roles outside what the launch can run");
+    for (int j = 0; j < k; j++)
+        if (!mix.streams[j] || !mix.ev[j]) throw std::logic_error("blind-rotation plan: rotation of roles without its streams");
+    if ((plan.variant == kVariantOneLimbStamps || plan.variant == kVariantWideStamps) && !t.diag) throw std::logic_error("diagnostic blind-rotation build without its stamp buffer");
     int launches = 0;
-    const int32_t nb = bara_stride(p);
     // state block: [items][2][1024] int32 accumulators, then [items][nb] u16 rotation amounts
     int32_t* st_acc = reinterpret_cast<int32_t*>(state);
     uint16_t* st_bara = reinterpret_cast<uint16_t*>(st_acc + (size_t)items * 2 * kN);
     hipLaunchKernelGGL(k_br_prologue, dim3((unsigned)items), dim3(128), 0, stream, K, W, st_bara, nb, st_acc);
-    const int32_t nsteps = steps < 0 ? p.n : (steps < p.n ? steps : p.n);
-    const int32_t max_slice = find_variant(variant)->long_slices ? nb : 64;
-    const int32_t S = (slice >= 1 && slice <= max_slice) ? slice : default_slice();
     auto one = [&](int v, int32_t i0, int32_t i1, Torus32* e) {
-        launch_slice(v, wg_gates, Slice{p.l, items, stream, K, d_bkf, d_bkf1, st_bara, nb, st_acc, i0, i1, e, guard, d_twiddles});
+        launch_slice(v, plan.wg_gates, Slice{p.l, items, stream, K, t, st_bara, nb, st_acc, i0, i1, e, plan.w4r_flip});
     };
     int32_t first = 0;
-    if (mix && mix->k >= 2 && mix->cycles >= 1 && variant_one_limb(variant) && mix->streams[0] == stream) {
-        const int32_t cyc = mix->tw * mix->s2 + (mix->k - mix->tw) * mix->s1;
-        const int32_t tail = (mix->tail_s1 > 0 && mix->tail_s2 > 0) ? mix->tw * mix->tail_s2 + (mix->k - mix->tw) * mix->tail_s1 : 0;
-        if (mix->tw >= 1 && mix->tw < mix->k && mix->k <= 4 && mix->s1 >= 1 && mix->s2 >= 1 && mix->cycles * cyc + tail < nsteps)
-            launches += launch_mixed_phases(p, K, d_bkf1, guard, items, st_acc, st_bara, nb, d_twiddles, *mix, &first);
-    }
+    if (k) launches += launch_mixed_phases(p, K, t, items, st_acc, st_bara, nb, plan, mix, &first);
     for (int32_t i0 = first; i0 < nsteps; i0 += S) {
         const int32_t i1 = i0 + S < nsteps ? i0 + S : nsteps;
         launches++;
-        one(variant, i0, i1, (i1 == nsteps) ? ext : nullptr);  // the last slice extracts instead of storing the accumulator
+        one(plan.variant, i0, i1, (i1 == nsteps) ? ext : nullptr);  // the last slice extracts instead of storing the accumulator
     }
     const double denom = (double)items * (nsteps > 0 ? nsteps : 1);
-    if (variant == kVariantOneLimbStamps) {
+    if (plan.variant == kVariantOneLimbStamps) {
         static const char* names[6] = {"decomposition (x2)", "digits+cvt+twist (x6)", "forward transform (x6)", "2nd BK block + products (x6)", "inverse pair", "round+update"};
-        diag_report(stream, "w1b, waves by parity", names, 6, denom / 2.0);  // each of the two slots collects half of the waves
-    } else if (variant == kVariantWide + 1) {
+        diag_report(stream, t.diag, "w1b, waves by parity", names, 6, denom / 2.0);  // each of the two slots collects half of the waves
+    } else if (plan.variant == kVariantWideStamps) {
         static const char* names[8] = {"head+decompose", "fwdFFT", "publish+BK issue", "barrier A", "MAC rows", "barrier B", "invFFT+update", "barrier C"};
-        diag_report(stream, "wide, waves 0 / 4", names, 8, denom);
+        diag_report(stream, t.diag, "wide, waves 0 / 4", names, 8, denom);
     }
     if (nsteps == 0 && ext) one(kVariantTwoWavesLds, 0, 0, ext);  // degenerate (steps == 0): extraction straight from the initial accumulator
     if (dbg_acc)

@@ -7,7 +7,7 @@
 //   K3 blind rotation         n x  acc += BK_i (x) ((X^bara_i - 1) acc)
 //   K4 sample extract
 //   K5 key switch                                                 (lwe-keyswitch-functions.cpp)
-// K0-K4 are one kernel (k_blind_rotate_*), K5 is the key-switch unit (keyswitch.h).
+// K0-K4 are one kernel (k_blind_rotate_*) of the blind-rotation unit (blind_rotate.h), K5 is the key-switch unit (keyswitch.h).
 //
 // The external product is EXACT.  libtfhe multiplies polynomials with an
 // approximate FP64 FFT; here every BK polynomial is split into two balanced
@@ -19,12 +19,11 @@
 
 #include <cstring>
 
-#include "blind_rotate_w64.h"
+#include "blind_rotate.h"
 #include "device_buffer.h"
 #include "device_common.h"
 #include "evaluator_options.h"
 #include "keyswitch.h"
-#include "mix_plan.h"
 #include "scoped_set.h"
 
 #include <algorithm>
@@ -50,65 +49,7 @@ void hip_check(hipError_t e, const char* what, const char* file, int line) {
 
 namespace {
 
-constexpr int kThreads = 256;
-
 using namespace dev;
-
-// In-LDS radix-2 transforms over `npoly` polynomials of M complex points.
-// Forward: DIF, natural in -> bit-reversed out.  Inverse: DIT, bit-reversed in
-// -> natural out, unscaled.  Neither needs a permutation pass.
-__device__ void fft_forward_lds(double2* F, int32_t npoly, int32_t M, int32_t logM, const double2* wtab) {
-    const int32_t halfM = M >> 1, total = npoly * halfM;
-    for (int32_t sh = 0; sh < logM; sh++) {
-        const int32_t half = halfM >> sh;
-        for (int32_t t = threadIdx.x; t < total; t += blockDim.x) {
-            const int32_t poly = t / halfM, bf = t - poly * halfM;
-            const int32_t j = bf & (half - 1), grp = bf >> (logM - 1 - sh);
-            const int32_t a = poly * M + (grp * 2 * half) + j, b = a + half;
-            const double2 w = wtab[j << sh];
-            const double2 u = F[a], v = F[b];
-            F[a] = make_double2(u.x + v.x, u.y + v.y);
-            F[b] = cmul(make_double2(u.x - v.x, u.y - v.y), w);
-        }
-        __syncthreads();
-    }
-}
-__device__ void fft_inverse_lds(double2* F, int32_t npoly, int32_t M, int32_t logM, const double2* wtab) {
-    const int32_t halfM = M >> 1, total = npoly * halfM;
-    for (int32_t st = 0; st < logM; st++) {
-        const int32_t half = 1 << st, sh = logM - 1 - st;
-        for (int32_t t = threadIdx.x; t < total; t += blockDim.x) {
-            const int32_t poly = t / halfM, bf = t - poly * halfM;
-            const int32_t j = bf & (half - 1), grp = bf >> st;
-            const int32_t a = poly * M + (grp * 2 * half) + j, b = a + half;
-            const double2 w = wtab[j << sh];
-            const double2 u = F[a], v = cmul_conj(F[b], w);
-            F[a] = make_double2(u.x + v.x, u.y + v.y);
-            F[b] = make_double2(u.x - v.x, u.y - v.y);
-        }
-        __syncthreads();
-    }
-}
-
-// ---- key preparation: BK polynomial -> two-limb spectrum ----
-__global__ __launch_bounds__(kThreads) void k_bk_to_spectrum(DevKeys K, const Torus32* bk_raw, double2* bkf) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    double2* F = reinterpret_cast<double2*>(smem);  // [2][M]
-    const int32_t M = K.M;
-    const Torus32* src = bk_raw + (size_t)blockIdx.x * K.N;
-    for (int32_t j = threadIdx.x; j < M; j += blockDim.x) {
-        const int32_t v0 = src[j], v1 = src[j + M];
-        const int32_t lo0 = (int16_t)(v0 & 0xFFFF), lo1 = (int16_t)(v1 & 0xFFFF);
-        const int32_t hi0 = (int32_t)(((int64_t)v0 - lo0) >> 16), hi1 = (int32_t)(((int64_t)v1 - lo1) >> 16);
-        const double2 tw = K.twist[j];
-        F[j] = cmul(make_double2((double)lo0, (double)lo1), tw);
-        F[M + j] = cmul(make_double2((double)hi0, (double)hi1), tw);
-    }
-    __syncthreads();
-    fft_forward_lds(F, 2, M, K.logM, K.wtab);
-    double2* dst = bkf + (size_t)blockIdx.x * 2 * M;
-    for (int32_t j = threadIdx.x; j < 2 * M; j += blockDim.x) dst[j] = F[j];
-}
 
 // raw KSK rows (n+1) -> padded rows (stride)
 __global__ void k_pad_rows(const Torus32* src, Torus32* dst, int64_t rows, int32_t width, int32_t stride) {
@@ -117,111 +58,6 @@ __global__ void k_pad_rows(const Torus32* src, Torus32* dst, int64_t rows, int32
         const int64_t r = i / stride;
         const int32_t c = (int32_t)(i - r * stride);
         dst[i] = c < width ? src[r * width + c] : 0;
-    }
-}
-
-// ---- K0..K4, generic parameters: one workgroup per gate instance ----
-// LDS: F [max(kpl,4)][M] double2 | acc [2][N] int32 | bara [n] u16
-__global__ __launch_bounds__(kThreads) void k_blind_rotate_generic(DevKeys K, WorkDesc W, Torus32* ext,
-                                                                   int32_t steps, Torus32* dbg_acc) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int32_t N = K.N, M = K.M, n = K.n, l = K.l, kpl = K.kpl;
-    const int32_t frows = kpl > 4 ? kpl : 4;
-    double2* F = reinterpret_cast<double2*>(smem);
-    int32_t* acc = reinterpret_cast<int32_t*>(F + (size_t)frows * M);
-    uint16_t* bara = reinterpret_cast<uint16_t*>(acc + 2 * N);
-    __shared__ int32_t s_barb;
-
-    const int64_t item = (int64_t)blockIdx.x;
-    const GateInst g = resolve(W, W.item0 + item, K.stride);
-    const int32_t log2N2 = K.logM + 2;
-
-    // K0 + K1
-    for (int32_t i = threadIdx.x; i <= n; i += blockDim.x) {
-        const int32_t bar = modswitch2N(combined_coef(g, i, n), log2N2);
-        if (i < n)
-            bara[i] = (uint16_t)bar;
-        else
-            s_barb = bar;
-    }
-    __syncthreads();
-    // K2: acc = (0, X^{2N-barb} * (mu,...,mu))
-    {
-        const int32_t a0 = (2 * N - s_barb) & (2 * N - 1);
-        for (int32_t j = threadIdx.x; j < N; j += blockDim.x) {
-            acc[j] = 0;
-            const int32_t idx = (j - a0) & (2 * N - 1);
-            acc[N + j] = idx < N ? kMU : -kMU;
-        }
-    }
-    __syncthreads();
-
-    const uint32_t halfBg = 1u << (K.Bgbit - 1), maskBg = (1u << K.Bgbit) - 1;
-    const double invM = 1.0 / (double)M;
-    const int32_t nsteps = steps < 0 ? n : steps;
-    // K3
-    for (int32_t i = 0; i < nsteps; i++) {
-        const int32_t a = bara[i];
-        if (a == 0) continue;  // uniform across the workgroup; exact arithmetic makes the step a no-op
-        // (X^a - 1) * acc, gadget decomposition, fold + twist
-        for (int32_t j = threadIdx.x; j < M; j += blockDim.x) {
-            const double2 tw = K.twist[j];
-#pragma unroll 2
-            for (int32_t c = 0; c < 2; c++) {
-                const int32_t* p = acc + c * N;
-                const uint32_t d0 = (uint32_t)rot_coef(p, j, a, N) - (uint32_t)p[j] + K.dec_offset;
-                const uint32_t d1 = (uint32_t)rot_coef(p, j + M, a, N) - (uint32_t)p[j + M] + K.dec_offset;
-                for (int32_t q = 0; q < l; q++) {
-                    const int32_t sh = 32 - (q + 1) * K.Bgbit;
-                    const int32_t e0 = (int32_t)((d0 >> sh) & maskBg) - (int32_t)halfBg;
-                    const int32_t e1 = (int32_t)((d1 >> sh) & maskBg) - (int32_t)halfBg;
-                    F[(size_t)(c * l + q) * M + j] = cmul(make_double2((double)e0, (double)e1), tw);
-                }
-            }
-        }
-        __syncthreads();
-        fft_forward_lds(F, kpl, M, K.logM, K.wtab);
-        // spectrum-domain accumulate: out(c,limb) = sum_row dec[row] * BK_i[row][c][limb]
-        const double2* bki = K.bkf + (size_t)i * kpl * 4 * M;
-        for (int32_t pt = threadIdx.x; pt < M; pt += blockDim.x) {
-            double2 s[4];
-#pragma unroll
-            for (int32_t q = 0; q < 4; q++) s[q] = make_double2(0.0, 0.0);
-            for (int32_t row = 0; row < kpl; row++) {
-                const double2 d = F[(size_t)row * M + pt];
-                const double2* b = bki + (size_t)row * 4 * M + pt;
-#pragma unroll
-                for (int32_t q = 0; q < 4; q++) s[q] = cfma(d, b[(size_t)q * M], s[q]);
-            }
-            // every thread has consumed its own column of F; rows 0..3 become the outputs
-#pragma unroll
-            for (int32_t q = 0; q < 4; q++) F[(size_t)q * M + pt] = s[q];
-        }
-        __syncthreads();
-        fft_inverse_lds(F, 4, M, K.logM, K.wtab);
-        // untwist, round, recombine limbs, accumulate
-        for (int32_t j = threadIdx.x; j < M; j += blockDim.x) {
-            const double2 tw = K.twist[j];
-#pragma unroll 2
-            for (int32_t c = 0; c < 2; c++) {
-                const double2 lo = cmul_conj(F[(size_t)(2 * c) * M + j], tw);
-                const double2 hi = cmul_conj(F[(size_t)(2 * c + 1) * M + j], tw);
-                const int64_t r0 = __double2ll_rn(lo.x * invM) + (__double2ll_rn(hi.x * invM) << 16);
-                const int64_t r1 = __double2ll_rn(lo.y * invM) + (__double2ll_rn(hi.y * invM) << 16);
-                acc[c * N + j] = (int32_t)((uint32_t)acc[c * N + j] + (uint32_t)r0);
-                acc[c * N + j + M] = (int32_t)((uint32_t)acc[c * N + j + M] + (uint32_t)r1);
-            }
-        }
-        __syncthreads();
-    }
-    if (dbg_acc) {
-        for (int32_t j = threadIdx.x; j < 2 * N; j += blockDim.x) dbg_acc[(size_t)item * 2 * N + j] = acc[j];
-    }
-    // K4: u = (a'_0 = acc.a_0, a'_j = -acc.a_{N-j}; b' = acc.b_0)
-    if (ext) {
-        Torus32* u = ext + (size_t)item * (N + 4);
-        for (int32_t j = threadIdx.x; j <= N; j += blockDim.x)
-            u[j] = j == 0 ? acc[0] : (j == N ? acc[N] : (int32_t)(0u - (uint32_t)acc[N - j]));
     }
 }
 
@@ -264,18 +100,6 @@ __global__ __launch_bounds__(256) void k_level_combine(const Torus32* ext, Torus
     }
 }
 
-// Audit of the one-limb blind rotation: rows of extracted samples it produced against the same gate instances run on the
-// two-limb (provably exact) kernel.  One workgroup per row; any differing word counts the row in *mismatches.
-// inject: test hook -- row 0 is compared as if its first word differed.
-__global__ void k_audit_compare(const Torus32* primary, const Torus32* exact, int32_t N, unsigned* mismatches, int inject) {
-    const size_t g = blockIdx.x;
-    const Torus32* a = primary + g * (size_t)(N + 4);
-    const Torus32* b = exact + g * (size_t)(N + 4);
-    int bad = (inject && g == 0 && threadIdx.x == 0) ? 1 : 0;
-    for (int32_t j = threadIdx.x; j <= N; j += blockDim.x) bad |= a[j] != b[j];
-    if (__syncthreads_or(bad) && threadIdx.x == 0) atomicAdd(mismatches, 1u);
-}
-
 // outputs of a circuit: out[b][o] = +-store[b][slot] or the constant
 __global__ void k_gather_outputs(const OutRef* outs, int32_t n_out, const Torus32* store, int32_t n_slots,
                                  Torus32* out, int64_t batch, int32_t stride, int32_t n) {
@@ -299,7 +123,7 @@ __global__ void k_gather_outputs(const OutRef* outs, int32_t n_out, const Torus3
 // ------------------------------------------------------------------------
 // One stream's worth of per-launch scratch.  Lane 0 runs on the evaluator's own stream and is all a call uses with
 // "overlap" = 0.  Otherwise further lanes -- more streams of the SAME context (one copy of the key), each with its own
-// extracted-sample rows, blind-rotation state, key-switch digits and audit scratch -- take either a contiguous share of a
+// extracted-sample rows, blind-rotation and key-switch scratch -- take either a contiguous share of a
 // batch's expressions through every level of a circuit (pipelines: one fork, one join per evaluation) or every other piece
 // of a wide level (lane 0 then waits for lane 1 before the next level starts).  See Evaluator::set_option in evaluator.h.
 struct Lane {
@@ -307,10 +131,8 @@ struct Lane {
     DeviceBuffer<Torus32> ext;      // extracted samples, rows of N + 4 words
     DeviceBuffer<Torus32> comb;     // levels with MUX gates: one combined row per gate of a piece (k_level_combine).  Per lane, not
                                     // per context: two lanes run their combines and key switches side by side
-    DeviceBuffer<char> br_state;    // sliced blind rotation: accumulators + rotation amounts, w64::state_bytes_per_item() per item
+    BrScratch br;                   // blind rotation: state between slices, the audit's sample
     KsScratch ks;                   // key switch
-    DeviceBuffer<Torus32> audit_ext;
-    DeviceBuffer<char> audit_state;
     Event ev_join;                  // the lane's share of a level / of an evaluation is queued
     Event ev_mix;
 };
@@ -335,23 +157,15 @@ struct Evaluator::Impl {
     std::map<std::tuple<size_t, int32_t, size_t, size_t, bool>, Tuned> tuned;  // (gates, levels, outputs, batch, exact_fft)
     DeviceBuffer<Torus32> stage[4];  // rows the host-buffer entry points stage operands and results in (counted in bytes)
     DevKeys K{};
-    DeviceBuffer<double2> bkf;
-    DeviceBuffer<double2> bkf_w64;   // spectrum in the wave-per-gate kernel's layout
-    DeviceBuffer<double2> tw_w64;    // its twiddle table
-    DeviceBuffer<double2> bkf1_w64;  // one-limb spectrum of k_blind_rotate_w1
-    DeviceBuffer<unsigned> fft_guard;  // [0] launches whose rounding deviation exceeded the limit, [1] max deviation (float bits), [2] audit rows that differed
+    BlindRotate br;  // K0-K4: kernels, key forms, guard record, audit and LDS grants; the choice among the kernels is br_plan.h
     double guard_max = 0;        // largest rounding deviation seen by the one-limb kernel (of 0.5)
     int64_t guard_reruns = 0;    // calls repeated on the two-limb kernel
-    int64_t audit_seq = 0;       // one-limb (level, chunk) launches so far
-    int64_t audits = 0, audit_gates = 0, audit_mismatches = 0;
     DeviceBuffer<int32_t> ksk;
     KeySwitch ks;  // K5: kernels, key form, LDS grants and the choice among them
-    DeviceBuffer<double2> twist, wtab;
     DeviceBuffer<Torus32> ext_mux;  // bootsMUX: combined extracted samples, chunk/2 rows
     DeviceBuffer<Torus32> store;    // circuits: the wire store, the gate and the output table
     DeviceBuffer<DevGate> d_gates;
     DeviceBuffer<OutRef> d_outs;
-    size_t br_lds = 0;
     size_t ext_row_bytes() const { return (size_t)(K.N + 4) * 4; }
 };
 
@@ -390,8 +204,7 @@ void Evaluator::init() {
         o.four_wave_max = 2 * cus;
         o.two_wave_max = 5 * cus;  // measured crossover with one wave per gate: 1 216 gates 8.6 against 10.0 ms, 1 400 gates 10.8 against 10.1
         o.exact_one_wave_min = 4 * cus + 1;  // two-limb launches that do not fit the two-waves-per-gate kernel's 4 gates per CU
-        o.br_variant = w64::default_variant();
-        if (!w64::one_limb_supported(p)) o.exact_fft = 1;
+        if (!br_one_limb_supported(p)) o.exact_fft = 1;
         options_from_environment(o, [this](const OptionRow& r, int64_t& v) { return option_hook(r, v); });
     }
     DevKeys& K = d_->K;
@@ -409,23 +222,7 @@ void Evaluator::init() {
     K.stride = p.lwe_stride();
     K.dec_offset = 0;
     for (int32_t i = 1; i <= p.l; i++) K.dec_offset += (1u << (p.Bgbit - 1)) << (32 - i * p.Bgbit);
-    // twiddles, computed once in double precision on the host
-    const int32_t M = K.M;
-    std::vector<double2> tw(M), w(M / 2 > 0 ? M / 2 : 1);
-    for (int32_t j = 0; j < M; j++) tw[j] = make_double2(std::cos(M_PI * j / p.N), std::sin(M_PI * j / p.N));
-    for (int32_t j = 0; j < M / 2; j++)
-        w[j] = make_double2(std::cos(-2.0 * M_PI * j / M), std::sin(-2.0 * M_PI * j / M));
-    d_->twist.allocate(tw.size());
-    d_->wtab.allocate(w.size());
-    HIP_CHECK(hipMemcpy(d_->twist, tw.data(), sizeof(double2) * tw.size(), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d_->wtab, w.data(), sizeof(double2) * w.size(), hipMemcpyHostToDevice));
-    K.twist = d_->twist;
-    K.wtab = d_->wtab;
-    const int32_t frows = K.kpl > 4 ? K.kpl : 4;
-    d_->br_lds = (size_t)frows * M * sizeof(double2) + (size_t)2 * p.N * 4 + (((size_t)p.n * 2 + 15) & ~(size_t)15);
-    if (d_->br_lds > 160 * 1024) throw std::invalid_argument("parameter set exceeds the 160 KiB LDS of a CU");
-    // (per context, on the context's device: the sizes depend on the parameter set)
-    dev::allow_dynamic_lds((const void*)k_blind_rotate_generic, d_->br_lds, "k_blind_rotate_generic");
+    d_->br.init(p, K);
     d_->ks.init(p, K);
 }
 
@@ -479,13 +276,15 @@ void Evaluator::set_chunk(size_t items) { d_->opt.chunk = items < 1 ? 1 : (int64
 bool Evaluator::option_hook(const OptionRow& r, int64_t& v) {
     if (r.at == &EvalOptions::force_generic) v = v != 0;
     if (r.at == &EvalOptions::ks_mfma_split) return v == 0 || ks_mfma_split_ok(p_, (int32_t)v);  // every split holds whole loop trips
-    if (r.at == &EvalOptions::br_variant) return w64::variant_known((int32_t)v);
-    if (r.at == &EvalOptions::exact_fft) return v == 1 || w64::one_limb_supported(p_);
+    if (r.at == &EvalOptions::br_variant && !variant_known((int32_t)v)) {
+        // a retired number (an old A/B script): say so rather than measure another kernel under the wrong label
+        fprintf(stderr, "ieache: br_variant %d names no kernel of this build (csrc/br_plan.h); the choice of kernels stays as it is\n", (int)v);
+        return false;
+    }
+    if (r.at == &EvalOptions::exact_fft) return v == 1 || br_one_limb_supported(p_);
     if (r.at == &EvalOptions::fft_guard_inject) {
-        if (!d_->fft_guard) return false;
-        const unsigned one = 1;
         HIP_CHECK(hipSetDevice(device_));
-        HIP_CHECK(hipMemcpy(d_->fft_guard, &one, sizeof one, hipMemcpyHostToDevice));
+        return d_->br.guard_inject();
     }
     return true;
 }
@@ -505,7 +304,7 @@ bool Evaluator::get_option(const std::string& name, int64_t* value) const {
 }
 
 std::string Evaluator::kernel_variant() const {
-    if (!w64::supported(p_) || d_->opt.force_generic) return "generic-radix2";
+    if (!br_supported(p_) || d_->opt.force_generic) return "generic-radix2";
     // the kernel wide launches take: one wave per gate, on the one-limb spectrum or ("exact_fft") on the two-limb one
     return d_->opt.exact_fft ? "x1x64-radix8-twolimb" : "w1x64-radix8-onelimb";
 }
@@ -523,36 +322,14 @@ void Evaluator::load_keys_host(const Torus32* bk, const Torus32* ksk) {
 void Evaluator::load_keys_device(const Torus32* d_bk, const Torus32* d_ksk) {
     HIP_CHECK(hipSetDevice(device_));
     DevKeys& K = d_->K;
-    const size_t npoly = (size_t)p_.n * K.kpl * 2;
-    if (!d_->bkf) d_->bkf.allocate(npoly * 2 * K.M);
     const size_t ks_rows = (size_t)p_.k * p_.N * p_.ks_t * K.ks_base;
     if (!d_->ksk) {
         // 16 rows of slack: the sliced key switch prefetches four positions past the end of its walk
         d_->ksk.allocate((ks_rows + 16) * K.stride);
         HIP_CHECK(hipMemsetAsync(d_->ksk + ks_rows * K.stride, 0, (size_t)16 * K.stride * 4, stream_));
     }
-    K.bkf = d_->bkf;
     K.ksk = d_->ksk;
-    hipLaunchKernelGGL(k_bk_to_spectrum, dim3((unsigned)npoly), dim3(kThreads), 2 * K.M * sizeof(double2), stream_, K,
-                       d_bk, d_->bkf);
-    HIP_CHECK(hipGetLastError());
-    if (w64::supported(p_)) {
-        if (!d_->bkf_w64) d_->bkf_w64.allocate(w64::spectrum_elems(p_));
-        if (!d_->tw_w64) {
-            d_->tw_w64.allocate(w64::twiddle_table_elems());
-            w64::build_twiddle_table(d_->tw_w64, stream_);
-            HIP_CHECK(hipGetLastError());
-        }
-        w64::prepare_spectrum(p_, d_bk, d_->bkf_w64, stream_);
-        HIP_CHECK(hipGetLastError());
-        if (!d_->bkf1_w64) d_->bkf1_w64.allocate(w64::spectrum1_elems(p_));
-        if (!d_->fft_guard) {
-            d_->fft_guard.allocate(4);
-            HIP_CHECK(hipMemsetAsync(d_->fft_guard, 0, 4 * sizeof(unsigned), stream_));
-        }
-        w64::prepare_spectrum1(p_, d_bk, d_->bkf1_w64, stream_);
-        HIP_CHECK(hipGetLastError());
-    }
+    d_->br.load_key(d_bk, stream_);
     hipLaunchKernelGGL(k_pad_rows, dim3(2048), dim3(256), 0, stream_, d_ksk, d_->ksk, (int64_t)ks_rows, p_.n + 1,
                        K.stride);
     HIP_CHECK(hipGetLastError());
@@ -614,63 +391,6 @@ void add_times(EvalStats* stats, Timer& tall, Timer& tbr, Timer& tks) {
 }
 }  // namespace
 
-// Which blind-rotation kernel a launch of `cnt` gate instances takes (br_variant 0 = by launch size: the 2L-waves-per-gate
-// kernel for a handful of gates, two waves per gate on the one-limb spectrum while every gate is resident at once, one wave
-// per gate above; "exact_fft" / a repeat after a guard trip: the two-limb kernels).
-static void pick_br_variant(const Params& p, const Evaluator::Impl* d, int64_t cnt, int32_t* variant_out, int32_t* slice_out) {
-    int32_t variant = d->opt.br_variant, slice = d->opt.br_slice;
-    cnt *= d->concurrency;  // the other stream's launch of the same level shares the chip: choose by the gates in flight
-    if (variant == 0) {
-        if (cnt <= d->opt.br_wide_max) {
-            // the latency kernel, on the one-limb spectrum unless exactness by construction is asked for
-            variant = (d->opt.exact_fft || d->exact_once) ? w64::kVariantWide : w64::kVariantWideHandoverOneLimb;
-            slice = w64::bara_stride(p);
-        } else if (!d->opt.exact_fft && !d->exact_once && cnt >= d->opt.one_limb_min) {
-            // one to two gates per CU: four waves per gate (two waves per SIMD); while every gate fits a two-wave slot, two
-            // waves per gate finish a step sooner than one
-            variant = cnt <= d->opt.four_wave_max ? w64::kVariantOneLimbFourWaves
-                      : cnt <= d->opt.two_wave_max ? w64::kVariantOneLimbTwoWaves : w64::kVariantOneLimbDefault;
-            // every gate of such a launch is resident at once, so nothing is gained from short slices (they keep the rounds
-            // of a WIDE launch on the same BK blocks) and each launch boundary costs a tail and a reload of the accumulators:
-            // the whole rotation in one launch for four waves per gate, 64 steps for two (interleaved A/B, profiles/r3_slice_ab.txt)
-            // (likewise one wave per gate while the launch is a single round of 8 gates per CU)
-            if (slice <= 0)
-                slice = variant == w64::kVariantOneLimbFourWaves ? w64::bara_stride(p)
-                        : (variant == w64::kVariantOneLimbTwoWaves || cnt <= 8 * (int64_t)d->opt.cus) ? 64 : slice;
-        }
-        else if (cnt >= d->opt.exact_one_wave_min) {
-            variant = w64::kVariantExactOneWave;  // "exact_fft" / a repeat: the two-limb product, one wave per gate
-            if (slice <= 0 && cnt <= 8 * (int64_t)d->opt.cus) slice = 64;  // a single round of resident gates: as above
-        }
-    } else if (d->exact_once && w64::variant_one_limb(variant)) {
-        variant = cnt >= d->opt.exact_one_wave_min ? w64::kVariantExactOneWave : 0;
-    }
-    *variant_out = variant;
-    *slice_out = slice;
-}
-
-// Gate instances per workgroup of the one-wave-per-gate kernels.  Four share a workgroup (for the twiddle table only) and
-// two such workgroups fill a CU; a launch of at most six gates per CU in fours leaves half the CUs with two workgroups and
-// half with one, in threes every CU gets the same six waves.
-static int pick_wg_gates(const Evaluator::Impl* d, int64_t cnt) {
-    if (d->opt.wg_gates) return d->opt.wg_gates;
-    return cnt * d->concurrency <= d->opt.wg3_max ? 3 : 4;
-}
-
-// Whether a launch of `cnt` gate instances runs as a rotation of roles (w64::MixPlan), and with which geometry.  Only where it
-// can pay: the kernels chosen by launch size (br_variant 0) on the one-limb spectrum, the launch alone on the chip (no other
-// stream of this context at work), a whole rotation, and a size mix_plan.h names: 4 .. 7 gates per CU, or a full round of the
-// one-wave kernel plus a small remainder (8 .. 10.5 per CU).
-// -> false, or the geometry (k subsets, tw of them on two waves at a time) a launch of cnt gate instances takes
-static bool mix_geometry(const Evaluator::Impl* d, int64_t cnt, int32_t variant, int* k_out, int* tw_out) {
-    if (!d->opt.overlap || !d->opt.br_mix || d->opt.br_variant != 0 || d->concurrency != 1 || d->level_on_two_lanes || d->opt.exact_fft || d->exact_once) return false;
-    if (!d->use_w64 || !w64::variant_one_limb(variant)) return false;
-    MixGeometry g;  // mix_plan.h: "mix_k" / "mix_tw" force a geometry (measurement aid), 0 = by launch size
-    if (!mix_geometry_for(d->opt.cus, cnt, d->opt.mix_k, d->opt.mix_tw, &g) || g.k > kMaxLanes) return false;
-    *k_out = g.k;
-    *tw_out = g.tw;
-    return true;
-}
 // streams and join events of lanes 1 .. lanes-1, and the fork event
 static void ensure_lanes(Evaluator::Impl* d, int lanes) {
     d->ev_fork.ensure();
@@ -706,104 +426,30 @@ struct Fork {
     }
 };
 
-static bool plan_mix(const Params& p, Evaluator::Impl* d, Lane& ln, int64_t cnt, int32_t variant, int32_t steps, w64::MixPlan* mix) {
-    MixGeometry g;
-    if (steps >= 0 || &ln != &d->lane[0] || !mix_geometry(d, cnt, variant, &g.k, &g.tw)) return false;
-    MixSteps m;
-    if (!mix_steps_for(p.n, g, d->opt.mix_s1, d->opt.mix_ratio, &m)) return false;
-    ensure_lanes(d, g.k);
-    for (int j = 0; j < g.k; j++) d->lane[j].ev_mix.ensure();
-    mix->k = g.k;
-    mix->tw = g.tw;
-    mix->s1 = m.s1;
-    mix->s2 = m.s2;
-    mix->cycles = m.cycles;
-    mix->tail_s1 = m.tail_s1;
-    mix->tail_s2 = m.tail_s2;
-    mix->sync = d->opt.mix_sync != 0;
-    mix->wg = d->opt.mix_wg;
-    for (int j = 0; j < g.k; j++) {
-        mix->streams[j] = d->lane[j].stream;
-        mix->ev[j] = d->lane[j].ev_mix;
-    }
-    return true;
+// The plan of a launch of `cnt` gate instances on lane `ln` under the call's state as it is now (br_plan.h).
+static BrPlan plan_blind_rotate(const Params& p, const Evaluator::Impl* d, const Lane& ln, int64_t cnt, int32_t steps = -1) {
+    return br_plan(p, d->opt, BrCall{d->exact_once, d->concurrency, d->level_on_two_lanes, steps < 0, &ln == &d->lane[0]}, d->use_w64, cnt);
 }
 
 std::string Evaluator::kernel_for_launch(int64_t gates) const {
-    if (!d_->use_w64) return "k_blind_rotate_generic";
-    int32_t variant, slice;
-    pick_br_variant(p_, d_, gates < 1 ? 1 : gates, &variant, &slice);
-    char tag[96];
-    snprintf(tag, sizeof tag, "<%d,%d>", (int)p_.l, (int)p_.Bgbit);
-    std::string name;
-    int mk = 0, mtw = 0;
-    if (mix_geometry(d_, gates < 1 ? 1 : gates, variant, &mk, &mtw)) {
-        // a rotation of roles between the two kernels (w64::MixPlan): mtw of mk subsets on two waves at a time
-        snprintf(tag, sizeof tag, "<%d,%d> %d of %d subsets on two waves", (int)p_.l, (int)p_.Bgbit, mtw, mk);
-        return std::string("k_blind_rotate_w2r+w1b") + tag;
-    }
-    if (const char* kernel = w64::variant_kernel_name(variant)) {
-        name = kernel;
-    } else {  // a measurement or diagnostic build: by number
-        snprintf(tag, sizeof tag, "<%d,%d> br_variant %d", (int)p_.l, (int)p_.Bgbit, (int)variant);
-        name = "k_blind_rotate";
-    }
-    return name + tag;
+    return br_kernel_label(p_, plan_blind_rotate(p_, d_, d_->lane[0], gates < 1 ? 1 : gates));
 }
 
-// blind-rotation state of the specialised kernels for launches of up to `need` items on this lane
-static void reserve_br_state(const Params& p, Evaluator::Impl* d, Lane& ln, size_t need) {
-    if (d->use_w64) ln.br_state.reserve(need, (size_t)d->opt.chunk, w64::state_bytes_per_item(p));
-}
-
-// Runs `items` gate instances described by W (item0 is advanced per chunk).
-static int launch_blind_rotate(const Params& p, Evaluator::Impl* d, Lane& ln, const WorkDesc& w, int64_t cnt,
-                                Torus32* ext, int32_t steps, Torus32* dbg_acc) {
-    hipStream_t stream = ln.stream;
-    if (d->use_w64) {
-        reserve_br_state(p, d, ln, (size_t)cnt);  // in place already unless the caller is not run_items
-        int32_t variant, slice;
-        pick_br_variant(p, d, cnt, &variant, &slice);
-        w64::MixPlan mix;
-        const bool mixed = plan_mix(p, d, ln, cnt, variant, steps, &mix);
-        if (mixed) d->opt.mixed_launches++;
-        return w64::launch(p, d->K, d->bkf_w64, d->bkf1_w64, d->fft_guard, w, cnt, ln.br_state, ext, steps, dbg_acc, slice, variant,
-                           d->tw_w64, stream, pick_wg_gates(d, cnt), mixed ? &mix : nullptr);
+// Runs the `cnt` gate instances described by w as `plan` says.  A rotation of roles gets the context's first plan.mix.k
+// lanes: their streams and an event each.
+static int launch_blind_rotate(Evaluator::Impl* d, Lane& ln, const BrPlan& plan, const WorkDesc& w, int64_t cnt, Torus32* ext, int32_t steps,
+                               Torus32* dbg_acc) {
+    BrLanes lanes;
+    if (plan.mix.k) {
+        ensure_lanes(d, plan.mix.k);
+        for (int j = 0; j < plan.mix.k; j++) {
+            d->lane[j].ev_mix.ensure();
+            lanes.streams[j] = d->lane[j].stream;
+            lanes.ev[j] = d->lane[j].ev_mix;
+        }
+        d->opt.mixed_launches++;
     }
-    else
-        hipLaunchKernelGGL(k_blind_rotate_generic, dim3((unsigned)cnt), dim3(kThreads), d->br_lds, stream, d->K, w, ext,
-                           steps, dbg_acc);
-    return 1;
-}
-
-// The sampled audit behind the rounding guard: after a (level, chunk) launch that took a one-limb kernel, every
-// fft_audit-th time, kAuditGates consecutive gate instances of it (at an offset that moves from audit to audit) are run
-// again on the two-limb kernel -- exact by construction -- and their extracted samples compared word for word with what the
-// one-limb kernel wrote to `ext`.  A differing row is counted on the device; the call then repeats itself on the
-// two-limb kernels like a call whose guard tripped (Evaluator::fft_guard_tripped).  The guard watches the error LEVEL of
-// every launch; this compares BITS, of a sample.
-constexpr int64_t kAuditGates = 64;
-static void maybe_audit(const Params& p, Evaluator::Impl* d, Lane& ln, const WorkDesc& w, int64_t cnt, const Torus32* ext) {
-    hipStream_t stream = ln.stream;
-    if (!d->use_w64 || d->opt.fft_audit <= 0 || !d->fft_guard) return;
-    int32_t variant, slice;
-    pick_br_variant(p, d, cnt, &variant, &slice);
-    if (!w64::variant_one_limb(variant)) return;  // the launch was exact by construction
-    if (++d->audit_seq % d->opt.fft_audit != 0) return;
-    const int64_t m = std::min<int64_t>(kAuditGates, cnt);
-    const int64_t off = cnt > m ? (int64_t)(((uint64_t)d->audit_seq * 0x9E3779B97F4A7C15ull >> 33) % (uint64_t)(cnt - m + 1)) : 0;
-    if (!ln.audit_ext) ln.audit_ext.allocate((size_t)kAuditGates, d->ext_row_bytes());
-    if (!ln.audit_state) ln.audit_state.allocate((size_t)kAuditGates, w64::state_bytes_per_item(p));
-    WorkDesc wa = w;
-    wa.item0 = w.item0 + off;
-    w64::launch(p, d->K, d->bkf_w64, d->bkf1_w64, d->fft_guard, wa, m, ln.audit_state, ln.audit_ext, -1, nullptr, w64::bara_stride(p),
-                w64::kVariantWide, d->tw_w64, stream);
-    hipLaunchKernelGGL(k_audit_compare, dim3((unsigned)m), dim3(256), 0, stream, ext + (size_t)off * (size_t)(d->K.N + 4), ln.audit_ext,
-                       d->K.N, d->fft_guard + 2, d->opt.fft_audit_inject ? 1 : 0);
-    HIP_CHECK(hipGetLastError());
-    d->opt.fft_audit_inject = 0;
-    d->audits++;
-    d->audit_gates += m;
+    return d->br.launch(ln.br, plan, d->opt, lanes, ln.stream, w, cnt, ext, steps, dbg_acc);
 }
 
 // the key switch of `cnt` extracted samples on a lane's stream, with the lane's scratch
@@ -836,7 +482,7 @@ static LevelPlan plan_level(const Evaluator::Impl* d, int64_t items) {
 static void reserve_lane(const Params& p, Evaluator::Impl* d, Lane& ln, size_t need, size_t need_comb = 0) {
     ln.comb.reserve(need_comb, (size_t)d->opt.chunk, d->ext_row_bytes());
     ln.ext.reserve(need, (size_t)d->opt.chunk, d->ext_row_bytes());
-    reserve_br_state(p, d, ln, need);
+    d->br.reserve(ln.br, need, d->opt, d->use_w64);
     d->ks.reserve(ln.ks, (int64_t)need, d->opt, d->force_generic_ks);  // for the widest launch
 }
 
@@ -905,11 +551,12 @@ static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t i
         WorkDesc w = W;
         w.item0 = W.item0 + done;
         if ((size_t)cnt > ln.ext.items()) throw std::logic_error("piece larger than the lane's extracted-sample rows");
+        const BrPlan plan = plan_blind_rotate(p, d, ln, cnt);  // once: the launch and the audit see the same choice
         tbr.mark(ln.stream);
-        const int nbr = launch_blind_rotate(p, d, ln, w, cnt, ln.ext, -1, nullptr);
+        const int nbr = launch_blind_rotate(d, ln, plan, w, cnt, ln.ext, -1, nullptr);
         tbr.mark(ln.stream);
         HIP_CHECK(hipGetLastError());
-        maybe_audit(p, d, ln, w, cnt, ln.ext);
+        d->br.audit(ln.br, plan, d->opt, ln.stream, w, cnt, ln.ext);
         tks.mark(ln.stream);
         if (mux) {
             // one row per gate, then the key switch over GATES: the same level descriptor read with nm = 0 and item0 in gate
@@ -943,25 +590,22 @@ static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t i
 // After a synchronous call: fold the one-limb kernel's guard record into the context and tell whether the call has to be
 // repeated on the two-limb kernel (some launch saw a coefficient further than kGuardLimit from an integer).
 bool Evaluator::fft_guard_tripped() {
-    if (!d_->fft_guard) return false;
     unsigned h[3] = {0, 0, 0};
-    HIP_CHECK(hipMemcpy(h, d_->fft_guard, sizeof h, hipMemcpyDeviceToHost));
+    if (!d_->br.guard_read(h)) return false;
     float m;
     memcpy(&m, &h[1], sizeof m);
     if ((double)m > d_->guard_max) d_->guard_max = (double)m;
     if (h[0] == 0 && h[2] == 0) return false;
-    d_->audit_mismatches += h[2];
+    d_->br.audit_counts.mismatches += h[2];
     d_->opt.fft_guard_inject = 0;
-    // the two counts only; the maximum stays
-    HIP_CHECK(hipMemset(d_->fft_guard, 0, sizeof(unsigned)));
-    HIP_CHECK(hipMemset(d_->fft_guard + 2, 0, sizeof(unsigned)));
+    d_->br.guard_rearm();
     return true;
 }
 
 void Evaluator::fft_audit_counts(int64_t* audits, int64_t* gates, int64_t* mismatches) const {
-    if (audits) *audits = d_->audits;
-    if (gates) *gates = d_->audit_gates;
-    if (mismatches) *mismatches = d_->audit_mismatches;
+    if (audits) *audits = d_->br.audit_counts.audits;
+    if (gates) *gates = d_->br.audit_counts.gates;
+    if (mismatches) *mismatches = d_->br.audit_counts.mismatches;
 }
 
 double Evaluator::fft_guard_max() const { return d_->guard_max; }
@@ -1030,7 +674,7 @@ void Evaluator::debug_blind_rotate(size_t count, const Torus32* d_x, Torus32* d_
 void Evaluator::begin_call() {
     if (!keys_loaded_) throw std::runtime_error("cloud key not loaded");
     HIP_CHECK(hipSetDevice(device_));
-    d_->use_w64 = w64::supported(p_) && !d_->opt.force_generic;
+    d_->use_w64 = br_supported(p_) && !d_->opt.force_generic;
     d_->force_generic_ks = d_->opt.force_generic;
 }
 
@@ -1075,11 +719,12 @@ void Evaluator::mux_device_once(size_t count, const Torus32* d_a, const Torus32*
         W.flat_c = d_c + done * K.stride;
         W.flat_type = kFlatMux;
         W.item0 = 0;
+        const BrPlan plan = plan_blind_rotate(p_, d_, ln, 2 * cnt);
         tbr.mark();
-        const int nbr = launch_blind_rotate(p_, d_, ln, W, 2 * cnt, ln.ext, -1, nullptr);
+        const int nbr = launch_blind_rotate(d_, ln, plan, W, 2 * cnt, ln.ext, -1, nullptr);
         tbr.mark();
         HIP_CHECK(hipGetLastError());
-        maybe_audit(p_, d_, ln, W, 2 * cnt, ln.ext);
+        d_->br.audit(ln.br, plan, d_->opt, stream_, W, 2 * cnt, ln.ext);
         tks.mark();
         hipLaunchKernelGGL(k_mux_combine, dim3((unsigned)cnt), dim3(256), 0, stream_, ln.ext, d_->ext_mux, K.N);
         WorkDesc Wk{};
@@ -1250,7 +895,8 @@ void Evaluator::debug_blind_rotate_once(size_t count, const Torus32* d_x, Torus3
     W.flat_b = nullptr;
     W.flat_out = nullptr;
     W.flat_type = -1;
-    launch_blind_rotate(p_, d_, d_->lane[0], W, (int64_t)count, nullptr, steps, d_acc);
+    Lane& ln = d_->lane[0];
+    launch_blind_rotate(d_, ln, plan_blind_rotate(p_, d_, ln, (int64_t)count, steps), W, (int64_t)count, nullptr, steps, d_acc);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(stream_));
 }

@@ -23,11 +23,12 @@ struct EvalOptions {
     int64_t ks_mfma_min = 64;     // measured crossover with the per-gate walk: ~40 gates (0.08 ms either way)
     int64_t ks_mfma_split = 0, ks_split_max = 16;
     int64_t ks_xcd = 0;
-    // blind rotation: which kernel takes a launch of how many gate instances (pick_br_variant)
-    int64_t br_slice = 0, br_variant = 0;
+    // blind rotation: which kernel takes a launch of how many gate instances (br_plan.h)
+    int64_t br_slice = 0, br_slice_default = 16, br_variant = 0;
     int64_t br_wide_max = 0, one_limb_min = 0, four_wave_max = 0, two_wave_max = 0;  // per CU
     int64_t exact_one_wave_min = 1025;                                                // per CU
     int64_t wg_gates = 0, wg3_max = 0;                                                // wg3_max per CU
+    int64_t w4r_flip = 0;
     int64_t exact_fft = 0;
     int64_t fft_audit = 64, fft_audit_inject = 0, fft_guard_inject = 0;
     // stream modes
@@ -55,7 +56,7 @@ inline bool not_1(int64_t v) { return v != 1; }
 #define IEACHE_OPT(name, env) #name, env, &EvalOptions::name
 #define IEACHE_FIGURE(name) #name, nullptr, &EvalOptions::name, 1, 0, nullptr
 
-// Which key-switch kernel these select for a launch is stated in ks_plan.h.
+// Which key-switch kernel these select for a launch is stated in ks_plan.h, which blind-rotation kernel in br_plan.h.
 // Conditions that need the device or the parameter set, and effects beyond storing the value, are in Evaluator::option_hook
 // (evaluator.hip); the rows they apply to say "hook".
 inline constexpr OptionRow kOptionTable[] = {
@@ -70,7 +71,8 @@ inline constexpr OptionRow kOptionTable[] = {
     {IEACHE_OPT(ks_xcd, "IEACHE_KS_XCD"), 0, 1, nullptr, "measurement aid: 1 = each XCD walks its own eighth of the MFMA key switch's streams (measured slower, see k_ksm_gemm)"},
     {IEACHE_OPT(ks_split_max, nullptr), 1, 64, nullptr, "workgroups the per-gate key switch may cut one gate's walk into when a launch holds a handful of gates; 1 = never"},
     {IEACHE_OPT(br_slice, nullptr), 0, 4096, nullptr, "CMux steps per blind-rotation launch; 0 = by kernel and launch size (16 over several rounds of resident gates, 64 while all are resident, the whole rotation for the four-wave and latency kernels)"},
-    {IEACHE_OPT(br_variant, nullptr), 0, 1000, nullptr, "hook (w64::variant_known): a number of blind_rotate_w64.h's table; 0 = by launch size.  Default: IEACHE_BR_VARIANT, read there"},
+    {IEACHE_OPT(br_slice_default, "IEACHE_BR_SLICE"), 1, 64, nullptr, "... where neither br_slice nor the launch size says otherwise, and where the kernel cannot take what br_slice says"},
+    {IEACHE_OPT(br_variant, "IEACHE_BR_VARIANT"), 0, 1000, nullptr, "hook (variant_known; a retired number is reported on stderr): a number of br_plan.h's table; 0 = by launch size"},
     {IEACHE_OPT(br_wide_max, "IEACHE_BR_WIDE_MAX"), 0, kNoLimit, nullptr, "launches up to this size: the latency-oriented 2L-waves-per-gate kernel (default 1 per CU; 0 = never)"},
     {IEACHE_OPT(one_limb_min, "IEACHE_ONE_LIMB_MIN"), 0, kNoLimit, nullptr, "launches from this size: the one-limb kernels (default 1 per CU + 1)"},
     {IEACHE_OPT(four_wave_max, nullptr), 0, kNoLimit, nullptr, "of those, launches up to this size: four waves per gate, k_blind_rotate_w4r (default 2 per CU)"},
@@ -78,7 +80,8 @@ inline constexpr OptionRow kOptionTable[] = {
     {IEACHE_OPT(exact_one_wave_min, "IEACHE_EXACT_ONE_WAVE_MIN"), 0, kNoLimit, nullptr, "two-limb launches from this size: one wave per gate, k_blind_rotate_x1 (default 4 per CU + 1)"},
     {IEACHE_OPT(wg_gates, "IEACHE_WG_GATES"), 0, 4, nullptr, "gate instances per workgroup of the one-wave-per-gate kernels; 0 = by launch size"},
     {IEACHE_OPT(wg3_max, "IEACHE_WG3_MAX"), 0, kNoLimit, nullptr, "... by launch size: three up to this many gate instances (default 6 per CU), four above"},
-    {IEACHE_OPT(exact_fft, "IEACHE_EXACT_FFT"), 0, 1, nullptr, "hook (0 needs w64::one_limb_supported): 1 = the two-limb blind rotation always"},
+    {IEACHE_OPT(w4r_flip, "IEACHE_W4R_FLIP"), 0, 1 << 30, nullptr, "k_blind_rotate_w4r: workgroups i and i + this are taken to share a CU; 0 = the device's CU count, a huge value = never flip"},
+    {IEACHE_OPT(exact_fft, "IEACHE_EXACT_FFT"), 0, 1, nullptr, "hook (0 needs br_one_limb_supported): 1 = the two-limb blind rotation always"},
     {IEACHE_OPT(fft_audit, "IEACHE_FFT_AUDIT"), 0, 1 << 30, nullptr, "every K-th one-limb launch has a sample run again on the two-limb kernel (Evaluator::fft_audit_counts); 0 = off"},
     {IEACHE_OPT(fft_audit_inject, nullptr), 1, 1, nullptr, "test hook: the next audit reports a differing row (reads 1 until it has)"},
     {IEACHE_OPT(fft_guard_inject, nullptr), 1, 1, nullptr, "hook (device write), test hook: the next call finds the rounding guard tripped (reads 1 until it has)"},

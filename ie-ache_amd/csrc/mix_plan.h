@@ -1,4 +1,4 @@
-// The arithmetic of the rotation of roles for mid-size blind-rotation launches (evaluator.hip: plan_mix; blind_rotate_w64.hip:
+// The arithmetic of the rotation of roles for mid-size blind-rotation launches (br_plan.h: br_plan; blind_rotate_w64.hip:
 // launch_mixed_phases), free of any device state so that the CPU tests can check it (ieache_debug_mix_plan).
 //
 // A launch of `gates` gate instances on a device of `cus` compute units (8 wave slots each) is cut into k subsets; tw of them

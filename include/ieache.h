@@ -211,7 +211,7 @@ int ieache_ctx_set_option(ieache_ctx* ctx, const char* name, int64_t value);
 int ieache_ctx_get_option(const ieache_ctx* ctx, const char* name, int64_t* value);
 const char* ieache_ctx_kernel_variant(const ieache_ctx* ctx);
 /* Name of the blind-rotation kernel a launch of `gates` gate instances takes under the context's
- * current options (launch sizes select different kernels: docs in csrc/blind_rotate_w64.h).  Like
+ * current options (launch sizes select different kernels: docs in csrc/br_plan.h).  Like
  * ieache_ctx_kernel_variant the string lives in the context until the next such call. */
 const char* ieache_ctx_kernel_for_launch(const ieache_ctx* ctx, int64_t gates);
 
