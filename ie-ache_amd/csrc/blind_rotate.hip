@@ -3,8 +3,10 @@
 // their launcher are in blind_rotate_w64.hip.
 //
 // The external product is EXACT on the two-limb spectrum: every BK polynomial is split into two balanced 16-bit limbs before
-// the transform, so every inverse-transform output is an integer of magnitude < 2^37 carried with > 15 spare mantissa bits
-// and rounding recovers it exactly (evaluator.hip).
+// the transform, so every inverse-transform output is an integer of magnitude <= kpl x N x 2^(Bgbit-1) x 2^15.  That is 2^37
+// for libtfhe's two sets (l = 3 / Bgbit = 7, l = 2 / Bgbit = 10), carried with 15 spare mantissa bits, and at most 2^46 for
+// any set Params::supported() admits (params.h: kpl x N x 2^Bgbit <= 2^32), where the modelled distance to an integer is 1/32
+// at worst (tests/test_rounding_model_cpu.py, profiles/param_lattice.txt); rounding recovers the integer exactly.
 #include "blind_rotate_w64.h"
 
 #include <algorithm>
@@ -197,8 +199,11 @@ __global__ void k_audit_compare(const Torus32* primary, const Torus32* exact, in
 
 void BlindRotate::init(const Params& p, DevKeys& K) {
     p_ = p;
-    // twiddles, computed once in double precision on the host
     const int32_t M = K.M;
+    const int32_t frows = K.kpl > 4 ? K.kpl : 4;
+    generic_lds_ = (size_t)frows * M * sizeof(double2) + (size_t)2 * p.N * 4 + (((size_t)p.n * 2 + 15) & ~(size_t)15);
+    if (generic_lds_ > 160 * 1024) throw std::invalid_argument("parameter set exceeds the 160 KiB LDS of a CU");
+    // twiddles, computed once in double precision on the host
     std::vector<double2> tw(M), w(M / 2 > 0 ? M / 2 : 1);
     for (int32_t j = 0; j < M; j++) tw[j] = make_double2(std::cos(M_PI * j / p.N), std::sin(M_PI * j / p.N));
     for (int32_t j = 0; j < M / 2; j++)
@@ -210,9 +215,6 @@ void BlindRotate::init(const Params& p, DevKeys& K) {
     K.twist = twist_;
     K.wtab = wtab_;
     K_ = K;
-    const int32_t frows = K.kpl > 4 ? K.kpl : 4;
-    generic_lds_ = (size_t)frows * M * sizeof(double2) + (size_t)2 * p.N * 4 + (((size_t)p.n * 2 + 15) & ~(size_t)15);
-    if (generic_lds_ > 160 * 1024) throw std::invalid_argument("parameter set exceeds the 160 KiB LDS of a CU");
     // (per context, on the context's device: the sizes depend on the parameter set)
     allow_dynamic_lds((const void*)k_blind_rotate_generic, generic_lds_, "k_blind_rotate_generic");
 }

@@ -39,20 +39,14 @@ __global__ __launch_bounds__(kThreads) void k_keyswitch_generic(DevKeys K, WorkD
     __syncthreads();
     const uint32_t cnt = s_count;
     // subtraction mod 2^32 commutes, so the (non-deterministic) list order does not matter
-    uint32_t r0 = 0, r1 = 0, r2 = 0;
-    const int32_t q0 = threadIdx.x, q1 = q0 + kThreads, q2 = q0 + 2 * kThreads;
-    for (uint32_t e = 0; e < cnt; e++) {
-        const int32_t* row = K.ksk + (size_t)list[e] * stride;
-        if (q0 < stride) r0 -= (uint32_t)row[q0];
-        if (q1 < stride) r1 -= (uint32_t)row[q1];
-        if (q2 < stride) r2 -= (uint32_t)row[q2];
-    }
     Torus32* out = flat_out ? flat_out + (size_t)item * stride : resolve(W, W.item0 + item, stride).out;
     const uint32_t bprime = (uint32_t)u[N];
-    if (q0 <= n) out[q0] = (int32_t)(r0 + (q0 == n ? bprime : 0u));
-    else if (q0 < stride) out[q0] = 0;
-    if (q1 < stride) out[q1] = q1 <= n ? (int32_t)(r1 + (q1 == n ? bprime : 0u)) : 0;
-    if (q2 < stride) out[q2] = q2 <= n ? (int32_t)(r2 + (q2 == n ? bprime : 0u)) : 0;
+    // every column of the row, kThreads at a time (any n: the list is walked once per pass of columns)
+    for (int32_t q = threadIdx.x; q < stride; q += kThreads) {
+        uint32_t r = 0;
+        for (uint32_t e = 0; e < cnt; e++) r -= (uint32_t)K.ksk[(size_t)list[e] * stride + q];
+        out[q] = q <= n ? (int32_t)(r + (q == n ? bprime : 0u)) : 0;
+    }
 }
 
 // ---- K5, vectorised: one 512-thread workgroup per gate instance ----

@@ -31,9 +31,15 @@ struct Params {
     int32_t lwe_stride() const { return (n + 1 + 3) & ~3; }  // row stride in int32, 16-B aligned
     size_t bk_count() const { return (size_t)n * kpl() * (k + 1) * N; }
     size_t ksk_count() const { return (size_t)k * N * ks_t * ks_base() * (n + 1); }
+    // The two-limb external product (blind_rotate.hip) rounds sums of kpl x N products of a digit (magnitude 2^(Bgbit-1)) and
+    // a balanced 16-bit key limb (magnitude 2^15) out of one FP64 transform.  It is exact with the rounded distance under the
+    // guard limit of 1/16 while the largest such sum stays <= 2^46, that is kpl x N x 2^Bgbit <= 2^32: derived on the model in
+    // tests/test_rounding_model_cpu.py (worst distance 1/32 at the bound, 1/16 one Bgbit above it; profiles/param_lattice.txt).
+    // Only l = 1 reaches it (Bgbit <= 31 - log2 N); Bgbit = 32, whose digit mask 1u << Bgbit is undefined, lies outside too.
+    bool br_exact() const { return Bgbit < 32 && ((int64_t)kpl() * N << Bgbit) <= ((int64_t)1 << 32); }
     bool supported() const {
         return k == 1 && N >= 16 && N <= 1024 && (N & (N - 1)) == 0 && n >= 1 && l >= 1 &&
-               l * Bgbit <= 32 && Bgbit >= 1 && ks_t >= 1 && ks_basebit >= 1 &&
+               l * Bgbit <= 32 && Bgbit >= 1 && br_exact() && ks_t >= 1 && ks_basebit >= 1 &&
                ks_t * ks_basebit < 32 && ks_basebit <= 4;
     }
 };

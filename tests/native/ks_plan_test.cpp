@@ -143,8 +143,94 @@ static int check_support_and_splits() {
     return 0;
 }
 
+// The boundaries of ks_support / ks_plan over the sets a key header may carry (tests/test_param_lattice_gpu.py runs the
+// kernels at them and relies on these answers for which family ran), and of Params::supported() itself.
+static int check_parameter_lattice() {
+    auto at = [](int32_t n, int32_t N, int32_t t, int32_t basebit) {
+        Params p;
+        p.n = n, p.N = N, p.ks_t = t, p.ks_basebit = basebit;
+        return p;
+    };
+    EvalOptions never = defaults();  // neither the product nor a gate-batched walk
+    never.ks_mfma_min = never.ks_sliced_min = never.ks_batch_min = H;
+    auto family = [](const Params& p, const EvalOptions& o, bool force_generic, int64_t cnt) {
+        return ks_plan(ks_support(p), p, o, true, force_generic, cnt).family;
+    };
+    // dwordx4 loads per key row: n = 255 -> 1, 256 -> 2, 508 .. 511 -> 2, 512 -> 3, 1023 -> 4, 1024 -> none
+    struct { int32_t n, stride, nld; } rows[] = {{3, 4, 1},     {7, 8, 1},     {31, 32, 1},    {63, 64, 1},   {255, 256, 1}, {256, 260, 2},
+                                                 {508, 512, 2}, {511, 512, 2}, {512, 516, 3},  {767, 768, 3}, {768, 772, 4},
+                                                 {1023, 1024, 4}, {1024, 1028, 0}, {1100, 1104, 0}};
+    for (const auto& r : rows) {
+        const Params p = at(r.n, 64, 8, 2);
+        const KsSupport s = ks_support(p);
+        CHECK(p.supported() && p.lwe_stride() == r.stride && s.nld == r.nld);
+        CHECK(s.mfma && s.batch == (r.nld > 0) && s.sliced == (r.nld > 0));
+        CHECK(ks_coef_blocks(p) == (r.stride + 31) / 32);
+        for (int64_t cnt : {1, 5, 70}) {
+            CHECK(family(p, never, true, cnt) == KsFamily::Generic);
+            CHECK(family(p, never, false, cnt) == (r.nld ? KsFamily::PerGate : KsFamily::Generic));
+            EvalOptions o = never;
+            o.ks_mfma_min = 1;
+            CHECK(family(p, o, false, cnt) == KsFamily::Mfma);  // also past n = 1023: the product has no column limit
+            o = never, o.ks_sliced_min = 1;
+            CHECK(family(p, o, false, cnt) == (r.nld ? KsFamily::Sliced : KsFamily::Generic));
+            o = never, o.ks_batch_min = 1;
+            CHECK(family(p, o, false, cnt) == (r.nld ? KsFamily::Batched : KsFamily::Generic));
+            // no option set: the product from 64 gate instances, below it the per-gate walk or, past n = 1023, the generic kernel
+            CHECK(family(p, defaults(), false, cnt) == (cnt >= 64 ? KsFamily::Mfma : r.nld ? KsFamily::PerGate : KsFamily::Generic));
+        }
+    }
+    // the per-gate walk cut into workgroups: 1 and 16 at five gates of a 64-coefficient ring
+    {
+        const Params p = at(255, 64, 8, 2);
+        EvalOptions o = never;
+        o.ks_split_max = 1;
+        CHECK(ks_plan(ks_support(p), p, o, true, false, 5).splits == 1);
+        o.ks_split_max = 16;
+        CHECK(ks_plan(ks_support(p), p, o, true, false, 5).splits == 16 && ks_plan(ks_support(p), p, o, true, false, 70).splits == 4);
+    }
+    // the decomposition: t = 4 at basebit 2 is gate-batched only; basebit 1, 3, 4 and t x basebit > 16 are per-gate / generic only
+    struct { int32_t t, basebit; bool batch, sliced, mfma; } dec[] = {{8, 2, true, true, true},     {4, 2, true, false, false},
+                                                                      {16, 1, false, false, false}, {31, 1, false, false, false},
+                                                                      {5, 3, false, false, false},  {10, 3, false, false, false},
+                                                                      {7, 4, false, false, false},  {1, 4, false, false, false}};
+    for (const auto& d : dec)
+        for (int32_t n : {7, 256}) {
+            const Params p = at(n, 64, d.t, d.basebit);
+            const KsSupport s = ks_support(p);
+            CHECK(p.supported() && s.nld == (n == 7 ? 1 : 2) && s.batch == d.batch && s.sliced == d.sliced && s.mfma == d.mfma);
+            EvalOptions o = defaults();
+            o.ks_batch_min = 1;
+            for (int64_t cnt : {1, 5, 70}) {
+                CHECK(family(p, o, true, cnt) == KsFamily::Generic);
+                CHECK(family(p, never, false, cnt) == KsFamily::PerGate);
+                if (!d.mfma) CHECK(family(p, o, false, cnt) == (d.batch ? KsFamily::Batched : KsFamily::PerGate));
+            }
+        }
+    // t = 31 on the largest ring: 131 088 bytes of list for the generic kernel, 256 more for the per-gate walk -- both inside a CU's
+    // LDS, as is every other set supported() admits (t <= 31, N <= 1024), so KeySwitch::init's refusal is never reached from a key header
+    {
+        const Params p = at(4, 1024, 31, 1);
+        const KsSupport s = ks_support(p);
+        CHECK(p.supported() && s.generic_lds == 131088 && s.vec_lds == 131088 + 256 && s.nld == 1 && s.vec_lds <= kKsLdsMax);
+        CHECK(!at(4, 1024, 32, 1).supported() && !at(4, 1024, 16, 2).supported() && !at(4, 64, 2, 5).supported());
+        Params wide = at(4, 1024, 40, 1);  // what the refusal is there for, should supported() ever widen
+        CHECK(!wide.supported() && ks_support(wide).generic_lds > kKsLdsMax);
+    }
+    // Params::br_exact(): kpl x N x 2^Bgbit <= 2^32 (tests/test_rounding_model_cpu.py), which only l = 1 reaches
+    auto br = [](int32_t l, int32_t Bgbit, int32_t N) {
+        Params p;
+        p.n = 5, p.N = N, p.l = l, p.Bgbit = Bgbit;
+        return p.supported();
+    };
+    for (int32_t logN = 4; logN <= 10; logN++) CHECK(br(1, 31 - logN, 1 << logN) && !br(1, 32 - logN, 1 << logN));
+    CHECK(!br(1, 32, 16) && !br(1, 32, 1024) && !br(3, 11, 64) && !br(1, 0, 64));
+    CHECK(br(3, 7, 1024) && br(2, 10, 1024) && br(2, 16, 1024) && br(4, 8, 1024) && br(32, 1, 1024) && br(16, 2, 512) && br(10, 3, 1024));
+    return 0;
+}
+
 int main() {
-    if (check_product_parameters() || check_support_and_splits()) return 1;
+    if (check_product_parameters() || check_support_and_splits() || check_parameter_lattice()) return 1;
     printf("KS_PLAN_OK\n");
     return 0;
 }

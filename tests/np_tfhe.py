@@ -117,7 +117,9 @@ def _u32(x):
 def _negacyclic(small, big):
     """small (int64, |.| < 2^8) * big (int32 torus) mod X^N+1 -> int32 with wraparound."""
     N = small.shape[0]
-    full = np.convolve(small.astype(np.int64), big.astype(np.int64))  # |digit| <= 2^9, |key| < 2^31, N <= 2^10 terms: < 2^51, exact in int64
+    # |digit| <= 2^(Bgbit-1), |key| <= 2^31, N terms: below 2^61 for every set Params::supported() admits
+    # (N x 2^(Bgbit-1) <= 2^30 there: 2^51 for libtfhe's sets), exact in int64
+    full = np.convolve(small.astype(np.int64), big.astype(np.int64))
     res = full[:N].copy()
     res[:N - 1] -= full[N:]
     return _wrap32(res)
@@ -181,6 +183,23 @@ def np_bootstrap(K, x):
             if d:
                 r -= K.ksk[i, j, d].astype(np.int64)
     return _wrap32(r)
+
+
+def np_keyswitch(ksk, t, basebit, u):
+    """lweKeySwitch as one statement: out = (0, b') - sum_i sum_j KSK[i][j][digit_j(a_i + prec_offset)] in int64, wrapped to
+    int32.  ksk [N][t][base][n+1], u [rows][N+1] (or one row) -> [rows][n+1].  Digit 0 subtracts nothing (libtfhe skips it),
+    whatever the key holds there.  The second reference of the key-switch tests, beside the oracle's loop."""
+    ksk, u = np.asarray(ksk), np.atleast_2d(np.asarray(u, dtype=np.int32))
+    N = ksk.shape[0]
+    abar = (_u32(u[:, :N]) + (1 << (32 - (1 + basebit * t)))) & 0xFFFFFFFF
+    shifts = 32 - (np.arange(t) + 1) * basebit
+    dig = (abar[:, :, None] >> shifts) & ((1 << basebit) - 1)                            # [rows][N][t]
+    out = np.zeros((u.shape[0], ksk.shape[3]), dtype=np.int64)
+    out[:, -1] = u[:, N]
+    for r in range(u.shape[0]):
+        rows = ksk[np.arange(N)[:, None], np.arange(t)[None, :], dig[r]].astype(np.int64)  # [N][t][n+1]
+        out[r] -= (rows * (dig[r] != 0)[:, :, None]).sum(axis=(0, 1))
+    return _wrap32(out)
 
 
 def np_gate(K, name, ca, cb):

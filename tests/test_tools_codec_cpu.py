@@ -346,3 +346,25 @@ def test_missing_extension_fails_loudly(ia, monkeypatch, tmp_path):
     monkeypatch.setattr(evaluator, "_PKG", str(tmp_path))
     with pytest.raises(ia.IeacheError, match="no CPU fallback"):
         evaluator.lib()
+
+
+def test_key_header_outside_the_accepted_parameter_sets_is_refused(ia, tmp_path):
+    """Params::supported() (csrc/params.h) is the one gate: a key header carrying a set outside it -- the two-limb product's
+    exactness bound 2l x N x 2^Bgbit <= 2^32 (tests/test_rounding_model_cpu.py), Bgbit = 32, l x Bgbit > 32,
+    ks_t x ks_basebit >= 32, ks_basebit > 4 -- is refused when the header is read, and the key generator refuses the same sets."""
+    from ieache_amd import tools
+    p = ia.default_params().copy(n=3, N=32, l=1, Bgbit=26, ks_t=15, ks_basebit=2)  # the last Bgbit the bound keeps at N = 32
+    tools.keygen_files(tmp_path, p, seed=(1, 2, 3), nbit_seed=(4, 5))
+    raw = (tmp_path / "cloud.key").read_bytes()
+    q, _, _ = tools.read_cloud_key(tmp_path / "cloud.key")
+    assert bytes(q) == bytes(p)
+    for old, new, kw in ((b"Bgbit: 26\n", b"Bgbit: 27\n", dict(Bgbit=27)), (b"Bgbit: 26\n", b"Bgbit: 32\n", dict(Bgbit=32)),
+                         (b"l: 1\n", b"l: 2\n", dict(l=2)), (b"N: 32\n", b"N: 64\n", dict(N=64)),
+                         (b"ks_t: 15\n", b"ks_t: 16\n", dict(ks_t=16)), (b"ks_basebit: 2\n", b"ks_basebit: 5\n", dict(ks_basebit=5))):
+        assert raw.count(old) == 1
+        f = tmp_path / "refused.key"
+        f.write_bytes(raw.replace(old, new))
+        with pytest.raises(ia.IeacheError, match="not supported"):
+            tools.read_cloud_key(f)
+        with pytest.raises(ia.IeacheError, match="unsupported parameter set"):
+            tools.keygen_raw(p.copy(**kw), (1, 2, 3), with_cloud=False)
