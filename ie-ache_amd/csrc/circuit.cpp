@@ -775,7 +775,10 @@ void simulate_circuit(const Circuit& c, const uint8_t* in, uint8_t* out) {
         return v ^ (uint8_t)(neg & 1);
     };
     for (int32_t L = 1; L <= c.n_levels(); L++) {
-        // read every operand of the level before writing any output, as the GPU does
+        // A model of the levelised DAG, not of the executor: every operand of the level is read before any output is written.
+        // The GPU runs a level in pieces (chunks, two lanes, pipelines), one piece's outputs written before the next piece's
+        // operands are read; that this gives the same result -- no gate of a level writes a slot the level reads -- is what
+        // tests/native/circuit_store_test.cpp checks, by executing the slot table with every output written at once.
         const int32_t lo = c.level_offset[L - 1], hi = c.level_offset[L];
         std::vector<uint8_t> res(hi - lo);
         for (int32_t g = lo; g < hi; g++) {

@@ -4,41 +4,9 @@ walked gate by gate."""
 import numpy as np
 import pytest
 
+from random_netlists import _neg, oracle_gate, oracle_netlist  # noqa: F401  (the references live with the random netlists)
+
 pytestmark = pytest.mark.gpu
-
-TWO_INPUT = {0: "and", 1: "xor", 2: "or", 3: "nand"}
-# libtfhe boot-gates.cpp: (constant term, multiplier of ca, multiplier of cb) of the gates the oracle has no entry point for
-LINEAR = {5: (-1 << 29, -1, -1), 6: (-2 << 29, -2, -2), 7: (-1 << 29, -1, 1), 8: (-1 << 29, 1, -1), 9: (1 << 29, -1, 1), 10: (1 << 29, 1, -1)}
-
-
-def _neg(row):
-    return (0 - row.view(np.uint32)).view(np.int32)
-
-
-def oracle_gate(ck, t, a, b, c=None):
-    if t in TWO_INPUT:
-        return ck.gate(TWO_INPUT[t], a, b)
-    if t == 4:
-        return ck.mux(a, b, c)
-    cst, ka, kb = LINEAR[t]
-    x = (np.uint32(ka & 0xFFFFFFFF) * a.view(np.uint32) + np.uint32(kb & 0xFFFFFFFF) * b.view(np.uint32)).astype(np.uint32)
-    x[-1:] += np.uint32(cst & 0xFFFFFFFF)
-    return ck.bootstrap(x.view(np.int32))
-
-
-def oracle_netlist(kb, cn, rows):
-    """The compiled netlist `cn` on one expression's input rows, one libtfhe gate after the other."""
-    ck = kb.ck
-    wires = [np.ascontiguousarray(r) for r in rows]
-
-    def ref(r):
-        if r < 0:
-            return ck.constant(1 if r == -1 else 0)
-        return _neg(wires[r >> 1]) if r & 1 else wires[r >> 1]
-
-    for t, a, b, c in cn.gates:
-        wires.append(oracle_gate(ck, t, ref(a), ref(b), ref(c) if t == 4 else None))
-    return np.stack([ref(o) for o in cn.outputs])
 
 
 def all_types_netlist(ia):
