@@ -478,6 +478,23 @@ int ieache_netlist_info(const ieache_netlist* nl, ieache_circuit_info* out, int6
     });
 }
 
+int64_t ieache_netlist_gate_count(const ieache_netlist* nl, int gate_type) {
+    if (!nl) return fail(IEACHE_EINVAL, "null argument");
+    const int64_t n = nl->circuit.count_of(gate_type);
+    return n < 0 ? fail(IEACHE_EINVAL, "unknown gate type") : n;
+}
+
+int64_t ieache_circuit_gate_count(int kind, int bits, int fold_constants, int gate_type) {
+    int64_t n = 0;
+    const int rc = guarded([&] {
+        Circuit c;
+        if (!build_circuit(kind, bits, &c, true, fold_constants != 0)) return fail(IEACHE_EINVAL, "unsupported circuit kind/bits");
+        n = c.count_of(gate_type);
+        return n < 0 ? fail(IEACHE_EINVAL, "unknown gate type") : 0;
+    });
+    return rc != 0 ? rc : n;
+}
+
 int ieache_netlist_simulate(const ieache_netlist* nl, const uint8_t* in_bits, uint8_t* out_bits) {
     return guarded([&] {
         if (!nl || !in_bits || !out_bits) return fail(IEACHE_EINVAL, "null argument");
@@ -581,6 +598,44 @@ int ieache_gates(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* a,
         db.upload(b, p.n + 1);
         EvalStats st;
         ctx->eval->gates_device(gate_type, count, da.p, db.p, dout.p, stats ? &st : nullptr);
+        dout.download(out, p.n + 1);
+        to_stats(st, stats);
+        return 0;
+    });
+}
+
+int ieache_gates3_device(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* d_a, const int32_t* d_b, const int32_t* d_c,
+                         int32_t* d_out, ieache_stats* stats) {
+    return guarded([&] {
+        if (!is_gate3(gate_type)) return fail(IEACHE_EINVAL, "not a three-input gate type (IEACHE_GATE_MAJ3 / IEACHE_GATE_XOR3)");
+        if (!ctx || !d_a || !d_b || !d_c || !d_out) return fail(IEACHE_EINVAL, "null argument");
+        if (count) {
+            require_device_pointer(d_a, "d_a");
+            require_device_pointer(d_b, "d_b");
+            require_device_pointer(d_c, "d_c");
+            require_device_pointer(d_out, "d_out");
+        }
+        EvalStats st;
+        ctx->eval->gates3_device(gate_type, count, d_a, d_b, d_c, d_out, stats ? &st : nullptr);
+        to_stats(st, stats);
+        return 0;
+    });
+}
+
+int ieache_gates3(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* a, const int32_t* b, const int32_t* c, int32_t* out,
+                  ieache_stats* stats) {
+    return guarded([&] {
+        if (!is_gate3(gate_type)) return fail(IEACHE_EINVAL, "not a three-input gate type (IEACHE_GATE_MAJ3 / IEACHE_GATE_XOR3)");
+        if (!ctx || !a || !b || !c || !out) return fail(IEACHE_EINVAL, "null argument");
+        const Params& p = ctx->eval->params();
+        HIP_CHECK(hipSetDevice(ctx->eval->device()));
+        StagedRows da(*ctx->eval, 0, count, p.lwe_stride()), db(*ctx->eval, 1, count, p.lwe_stride()), dc(*ctx->eval, 2, count, p.lwe_stride()),
+            dout(*ctx->eval, 3, count, p.lwe_stride());
+        da.upload(a, p.n + 1);
+        db.upload(b, p.n + 1);
+        dc.upload(c, p.n + 1);
+        EvalStats st;
+        ctx->eval->gates3_device(gate_type, count, da.p, db.p, dc.p, dout.p, stats ? &st : nullptr);
         dout.download(out, p.n + 1);
         to_stats(st, stats);
         return 0;

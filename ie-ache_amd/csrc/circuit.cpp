@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <queue>
 #include <stdexcept>
+#include <utility>
 
 namespace ieache {
 
@@ -54,7 +55,7 @@ Ref CircuitBuilder::gate(int32_t type, Ref a, Ref b) {
             a.neg = b.neg = false;
         }
         if (a.id > b.id) std::swap(a, b);  // both gates commute
-        const auto key = std::make_tuple(type, a.id, (int32_t)a.neg, b.id, (int32_t)b.neg);
+        const auto key = std::make_tuple(type, a.id, (int32_t)a.neg, b.id, (int32_t)b.neg, kUndefId, 0);
         const auto it = known_.find(key);
         if (it != known_.end()) return Ref{it->second, out_neg};
         known_[key] = next_wire_;
@@ -74,10 +75,64 @@ Ref CircuitBuilder::gate(int32_t type, Ref a, Ref b) {
 }
 
 // bootsMUX(a, b, c) = a ? b : c.  Recorded as given: no folding, no sharing.
+// GATE_MAJ3 / GATE_XOR3: one blind rotation of ca + cb + cc resp. (0,1/2) + 2(ca + cb + cc).
 Ref CircuitBuilder::gate3(int32_t type, Ref a, Ref b, Ref c) {
-    if (type != GATE_MUX) throw std::invalid_argument("not a three-input gate type");
+    if (type != GATE_MUX && !is_gate3(type)) throw std::invalid_argument("not a three-input gate type");
     if (a.id == kUndefId || b.id == kUndefId || c.id == kUndefId)
         throw std::logic_error("gate consumes a never-written sample");
+    bool out_neg = false;
+    if (is_gate3(type)) {
+        Ref r[3] = {a, b, c};
+        int same = -1;  // r[same] and r[same2] name one wire
+        int same2 = -1;
+        for (int i = 0; i < 3 && same < 0; i++)
+            for (int j = i + 1; j < 3; j++)
+                if (r[i].id >= 0 && r[i].id == r[j].id) {
+                    same = i;
+                    same2 = j;
+                    break;
+                }
+        if (same >= 0 && !fold_) throw std::invalid_argument("a three-input gate names the same wire twice");
+        if (fold_) {
+            if (same >= 0) {  // MAJ3(x,x,z) = x ; MAJ3(x,~x,z) = z ; XOR3(x,x,z) = z ; XOR3(x,~x,z) = ~z
+                n_requested_++;
+                const Ref z = r[3 - same - same2];
+                const bool equal = r[same].neg == r[same2].neg;
+                if (type == GATE_MAJ3) return equal ? r[same] : z;
+                return Ref{z.id, z.neg != !equal};
+            }
+            for (int i = 0; i < 3; i++)
+                if (r[i].id == kConstId) {  // a constant operand: the two-input gate of the other two (which folds further)
+                    const Ref x = r[(i + 1) % 3], y = r[(i + 2) % 3];
+                    const bool k = r[i].neg;
+                    if (type == GATE_XOR3) {
+                        const Ref t = gate(GATE_XOR, x, y);  // XOR3(x,y,1) = XNOR(x,y) = NOT XOR(x,y): the negation is free
+                        return Ref{t.id, t.neg != k};
+                    }
+                    if (x.id == kConstId || y.id == kConstId) {  // MAJ3(x, k', k) = k when k' == k, else x
+                        n_requested_++;
+                        const Ref w = x.id == kConstId ? y : x, k2 = x.id == kConstId ? x : y;
+                        return k2.neg == k ? constant(k) : w;
+                    }
+                    return gate(k ? GATE_OR : GATE_AND, x, y);
+                }
+            // share: both gates are symmetric; XOR3's operand negations move to the output
+            std::sort(r, r + 3, [](const Ref& p, const Ref& q) { return p.id < q.id; });
+            if (type == GATE_XOR3)
+                for (Ref& q : r) {
+                    out_neg = out_neg != q.neg;
+                    q.neg = false;
+                }
+            a = r[0], b = r[1], c = r[2];
+            const auto key = std::make_tuple(type, a.id, (int32_t)a.neg, b.id, (int32_t)b.neg, c.id, (int32_t)c.neg);
+            const auto it = known_.find(key);
+            if (it != known_.end()) {
+                n_requested_++;
+                return Ref{it->second, out_neg};
+            }
+            known_[key] = next_wire_;
+        }
+    }
     n_requested_++;
     int32_t lv = 0;
     for (const Ref& r : {a, b, c})
@@ -92,7 +147,7 @@ Ref CircuitBuilder::gate3(int32_t type, Ref a, Ref b, Ref c) {
     wire_level_.push_back(g.level);
     gates_.push_back(g);
     requested_type_.push_back(type);
-    return Ref{g.out, false};
+    return Ref{g.out, out_neg};
 }
 
 // cloud.c:18-51.  carry-in is c[0] (bootsCOPY :24); carry-out lands in
@@ -341,8 +396,11 @@ Circuit finalize_circuit(const std::string& name, const CircuitBuilder& b, const
             d.b_neg = g.b.neg;
             d.out_slot = s;
             d.c_slot = g.c.id >= 0 ? slot_of[g.c.id] : -1;
-            d.c_neg = g.type == GATE_MUX ? (int32_t)g.c.neg : 0;
-            c.n_by_type[b.requested_types()[order[pos]]]++;
+            d.c_neg = g.type == GATE_MUX || is_gate3(g.type) ? (int32_t)g.c.neg : 0;
+            const int32_t requested = b.requested_types()[order[pos]];
+            if (requested < GATE_TYPES) c.n_by_type[requested]++;
+            if (requested == GATE_MAJ3) c.n_maj3++;
+            if (requested == GATE_XOR3) c.n_xor3++;
             if (g.type == GATE_AND) c.n_and++;
             if (g.type == GATE_XOR) c.n_xor++;
         }
@@ -383,6 +441,10 @@ int32_t circuit_n_inputs(int32_t kind, int32_t bits) {
         case CIRC_SUB_KS:
         case CIRC_RSUB_KS:
         case CIRC_MUL_WALLACE:
+        case CIRC_ADD_FA:
+        case CIRC_SUB_FA:
+        case CIRC_RSUB_FA:
+        case CIRC_MUL_FA:
             return 2 * bits + 32;
     }
     return -1;
@@ -402,9 +464,13 @@ int32_t circuit_n_outputs(int32_t kind, int32_t bits) {
         case CIRC_ADD_KS:
         case CIRC_SUB_KS:
         case CIRC_RSUB_KS:
+        case CIRC_ADD_FA:
+        case CIRC_SUB_FA:
+        case CIRC_RSUB_FA:
             return bits;
         case CIRC_MUL:
         case CIRC_MUL_WALLACE:
+        case CIRC_MUL_FA:
             return 2 * bits;
     }
     return -1;
@@ -531,6 +597,57 @@ static Word wallace_mul(CircuitBuilder& b, const Word& A, const Word& B) {
     return kogge_stone_add(b, x, y, CircuitBuilder::constant(0));
 }
 
+// x + y + cin as a ripple of two-bootstrap full adders: sum = XOR3, carry = MAJ3, one level per bit.  The carry out of the
+// top bit is computed as the reference's add() computes it (cloud.c:43-46), though no caller here reads it.
+static Word full_adder_ripple(CircuitBuilder& b, const Word& x, const Word& y, Ref cin) {
+    const int n = (int)x.size();
+    Word sum(n);
+    Ref carry = cin;
+    for (int i = 0; i < n; i++) {
+        sum[i] = b.XOR3(x[i], y[i], carry);
+        carry = b.MAJ3(x[i], y[i], carry);
+    }
+    return sum;
+}
+
+// A * B on full adders (see CIRC_MUL_FA).  Row i holds A[j] & B[i] at weight i + j.  The array keeps a sum row S and a
+// carry row C; adding row i takes one full adder per column, FA(row[j], S[j+1], C[j]), and gives the next S and C and the
+// product bit S[0] -- one level per row, since no carry travels inside a row.  A cell with two constant-zero operands is a
+// wire (the top cell of every row: its carry is always zero); a cell with one is still a MAJ3 / XOR3 with that constant
+// (row 1, whose C is all zero), which `fold` lowers to AND / XOR.  The last S and C are added by a ripple.
+// Bootstraps: n*n ANDs + 2 (n-1)(n-1) in the array + 2 (n-1) in the ripple = 3 n*n - 2 n; depth 2 n - 1.
+static Word full_adder_mul(CircuitBuilder& b, const Word& A, const Word& B) {
+    const int n = (int)A.size();
+    const Ref zero = CircuitBuilder::constant(0);
+    auto is_zero = [](Ref r) { return r.id == kConstId && !r.neg; };
+    // -> (sum, carry)
+    auto cell = [&](Ref x, Ref y, Ref z) -> std::pair<Ref, Ref> {
+        if (is_zero(y) && is_zero(z)) return {x, zero};
+        if (is_zero(x) && is_zero(z)) return {y, zero};
+        if (is_zero(x) && is_zero(y)) return {z, zero};
+        return {b.XOR3(x, y, z), b.MAJ3(x, y, z)};
+    };
+    std::vector<Word> row(n, Word(n));
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++) row[i][j] = b.AND(A[j], B[i]);
+    Word S = row[0], C(n, zero), P(2 * n);
+    P[0] = S[0];
+    for (int i = 1; i < n; i++) {
+        Word S2(n), C2(n);
+        for (int j = 0; j < n; j++) std::tie(S2[j], C2[j]) = cell(row[i][j], j + 1 < n ? S[j + 1] : zero, C[j]);
+        S.swap(S2);
+        C.swap(C2);
+        P[i] = S[0];
+    }
+    Ref carry = zero;  // weights n .. 2n-1: S[1 .. n-1] + C[0 .. n-1]; the carry out of the top bit is 2^(2n): dropped
+    for (int k = 0; k < n; k++) {
+        const auto sc = cell(k + 1 < n ? S[k + 1] : zero, C[k], carry);
+        P[n + k] = sc.first;
+        carry = sc.second;
+    }
+    return P;
+}
+
 // One branch of main() (cloud.c:870-2718) on symbolic operands: `bits`-wide A and B (a multiple
 // of 32 except for the generalised adders), carry = ciphertextcarry1.  Returns the value samples
 // LSB first, or an empty word for an unsupported (kind, bits).
@@ -558,6 +675,20 @@ static Word build_stage(CircuitBuilder& b, int32_t kind, int32_t bits, const Wor
         }
         case CIRC_MUL_WALLACE:
             return wallace_mul(b, A, B);
+        case CIRC_ADD_FA:
+            return full_adder_ripple(b, A, B, carry1[0]);
+        case CIRC_SUB_FA: {  // A + ~B + 1 (the reference's carry word encrypts 0: alice.c:147-149)
+            Word nb(bits);
+            CircuitBuilder::NOT(nb, B, bits);
+            return full_adder_ripple(b, A, nb, CircuitBuilder::constant(1));
+        }
+        case CIRC_RSUB_FA: {
+            Word na(bits);
+            CircuitBuilder::NOT(na, A, bits);
+            return full_adder_ripple(b, B, na, CircuitBuilder::constant(1));
+        }
+        case CIRC_MUL_FA:
+            return full_adder_mul(b, A, B);
         case CIRC_MUL:
             if (bits == 32) {  // cloud.c:2655-2718
                 Word r1 = b.fresh(), r2 = b.fresh();
@@ -614,6 +745,10 @@ static const char* stage_name(int32_t kind) {
         case CIRC_SUB_KS: return "sub_ks";
         case CIRC_RSUB_KS: return "rsub_ks";
         case CIRC_MUL_WALLACE: return "mul_wallace";
+        case CIRC_ADD_FA: return "add_fa";
+        case CIRC_SUB_FA: return "sub_fa";
+        case CIRC_RSUB_FA: return "rsub_fa";
+        case CIRC_MUL_FA: return "mul_fa";
     }
     return "?";
 }
@@ -631,7 +766,7 @@ bool build_circuit(int32_t kind, int32_t bits, Circuit* out, bool balanced, bool
     std::string name;
     int32_t k1, k2;
     bool flip;
-    bool has_mul = kind == CIRC_MUL || kind == CIRC_MUL_WALLACE;
+    bool has_mul = kind == CIRC_MUL || kind == CIRC_MUL_WALLACE || kind == CIRC_MUL_FA;
     int32_t sched_bits = bits;
     if (decode_chain(kind, &k1, &k2, &flip)) {
         // Two ./cloud runs of compute() / compute_final() (dragonfly_cipher_cloud.py:1219-1327) as
@@ -654,7 +789,7 @@ bool build_circuit(int32_t kind, int32_t bits, Circuit* out, bool balanced, bool
         has_mul = k1 == CIRC_MUL || k2 == CIRC_MUL;
         if (k2 == CIRC_MUL) sched_bits = w2;  // the wider multiplier decides the schedule below
     } else {
-        if ((kind == CIRC_MUL || kind == CIRC_MUL_WALLACE) && bits != 32 && bits != 64 && bits != 128) return false;
+        if (has_mul && bits != 32 && bits != 64 && bits != 128) return false;
         result = build_stage(b, kind, bits, A, B, carry1);
         name = stage_name(kind);
     }
@@ -672,9 +807,12 @@ bool build_circuit(int32_t kind, int32_t bits, Circuit* out, bool balanced, bool
     *out = finalize_circuit(name + std::to_string(bits) + (fold ? "_folded" : ""), b, result, use_balanced, use_balanced ? level_cap : 0);
     out->n_reference_bootstraps = b.n_requested();
     out->balanced_schedule = use_balanced;
-    if (kind == CIRC_MUL_WALLACE) {  // what cloud.c performs for the same product
+    int32_t ref_kind = 0;  // the opt-in kinds that are not the reference's gate list: what cloud.c performs for the same result
+    if (kind == CIRC_MUL_WALLACE || kind == CIRC_MUL_FA) ref_kind = CIRC_MUL;
+    if (kind >= CIRC_ADD_FA && kind <= CIRC_RSUB_FA) ref_kind = kind - CIRC_ADD_FA + CIRC_ADD;
+    if (ref_kind) {
         Circuit ref;
-        if (build_circuit(CIRC_MUL, bits, &ref, false, false)) out->n_reference_bootstraps = ref.n_bootstraps;
+        if (build_circuit(ref_kind, bits, &ref, false, false)) out->n_reference_bootstraps = ref.n_bootstraps;
     }
     return true;
 }
@@ -749,11 +887,17 @@ Circuit build_netlist(int32_t n_inputs, const NetGate* gates, size_t n_gates, co
     for (size_t g = 0; g < n_gates; g++) {
         const NetGate& ng = gates[g];
         const std::string at = "gate " + std::to_string(g);
-        if (ng.type < 0 || ng.type >= GATE_TYPES) bad(at + ": unknown gate type " + std::to_string(ng.type));
+        if ((ng.type < 0 || ng.type >= GATE_TYPES) && !is_gate3(ng.type)) bad(at + ": unknown gate type " + std::to_string(ng.type));
         const int64_t limit = (int64_t)n_inputs + (int64_t)g;
         const Ref a = ref(ng.a, limit, at + ": operand a"), bb = ref(ng.b, limit, at + ": operand b");
         if (ng.type == GATE_MUX) {
             b.gate3(GATE_MUX, a, bb, ref(ng.c, limit, at + ": operand c"));
+        } else if (is_gate3(ng.type)) {
+            const Ref cc = ref(ng.c, limit, at + ": operand c");
+            // the same wire twice adds its noise coherently (XOR3(a,a,a): 13 sigma instead of 19): refused, constants may repeat
+            if ((a.id >= 0 && (a.id == bb.id || a.id == cc.id)) || (bb.id >= 0 && bb.id == cc.id))
+                bad(at + ": a three-input gate must name three different wires (constants may repeat)");
+            b.gate3(ng.type, a, bb, cc);
         } else {
             if (ng.c != 0) bad(at + ": a two-input gate takes no third operand (c must be 0)");
             b.gate(ng.type, a, bb);
@@ -792,6 +936,8 @@ void simulate_circuit(const Circuit& c, const uint8_t* in, uint8_t* out) {
                 case GATE_NAND: r = !(a & b); break;
                 case GATE_XNOR: r = !(a ^ b); break;
                 case GATE_MUX: r = a ? b : val(d.c_slot, d.c_neg); break;
+                case GATE_MAJ3: r = (uint8_t)((a + b + val(d.c_slot, d.c_neg)) >= 2); break;
+                case GATE_XOR3: r = a ^ b ^ val(d.c_slot, d.c_neg); break;
             }
             res[g - lo] = r;
         }

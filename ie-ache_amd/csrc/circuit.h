@@ -39,15 +39,20 @@ enum GateType : int32_t {
     GATE_ANDYN = 8,  // (0,-1/8) + ca - cb   = AND(a, NOT b)
     GATE_ORNY = 9,   // (0, 1/8) - ca + cb   = OR(NOT a, b)
     GATE_ORYN = 10,  // (0, 1/8) + ca - cb   = OR(a, NOT b)
-    GATE_TYPES = 11
+    GATE_TYPES = 11,  // the libtfhe types above; Circuit::n_by_type and the ABI's count array have this length
+    // Three-input gates of ONE blind rotation each (not libtfhe's; DESIGN.md section 7 has the noise budget).  Their codes lie
+    // outside 0 .. GATE_TYPES-1 so that everything sized or bounded by GATE_TYPES stays as it is.
+    GATE_MAJ3 = 32,  // ca + cb + cc              majority of three: phases +-1/8, +-3/8
+    GATE_XOR3 = 33,  // (0,1/2) + 2(ca+cb+cc)     parity of three: phases +-1/4
 };
+constexpr bool is_gate3(int32_t type) { return type == GATE_MAJ3 || type == GATE_XOR3; }
 
 struct Gate {
     int32_t type;
     Ref a, b;
     int32_t out;    // wire id
     int32_t level;  // 1-based ASAP level
-    Ref c{kConstId, false};  // third operand (GATE_MUX only)
+    Ref c{kConstId, false};  // third operand (GATE_MUX, GATE_MAJ3, GATE_XOR3)
 };
 
 using Word = std::vector<Ref>;
@@ -67,7 +72,12 @@ public:
     static Ref NOT(Ref a) { return Ref{a.id, !a.neg}; }                     // bootsNOT
     static Word fresh(int32_t count = 32) { return Word(count, Ref{kUndefId, false}); }
     Ref gate(int32_t type, Ref a, Ref b);                                    // bootsAND / bootsXOR ...
-    Ref gate3(int32_t type, Ref a, Ref b, Ref c);                            // bootsMUX: a ? b : c
+    // bootsMUX: a ? b : c (recorded as given), or GATE_MAJ3 / GATE_XOR3.  The latter two must name three different wires
+    // (constants may repeat): the same wire twice adds its noise coherently.  With fold on, a repeated wire or a constant
+    // operand lowers the gate instead (MAJ3(a,b,0) = AND, MAJ3(a,b,1) = OR, XOR3(a,b,k) = XOR / XNOR) and gates are shared.
+    Ref gate3(int32_t type, Ref a, Ref b, Ref c);
+    Ref MAJ3(Ref a, Ref b, Ref c) { return gate3(GATE_MAJ3, a, b, c); }
+    Ref XOR3(Ref a, Ref b, Ref c) { return gate3(GATE_XOR3, a, b, c); }
     Ref AND(Ref a, Ref b) { return gate(GATE_AND, a, b); }
     Ref XOR(Ref a, Ref b) { return gate(GATE_XOR, a, b); }
 
@@ -102,12 +112,13 @@ private:
     std::vector<Gate> gates_;
     std::vector<int32_t> requested_type_;  // per recorded gate: the type asked for (before NOR .. ORYN were lowered)
     std::vector<int32_t> wire_level_;
-    std::map<std::tuple<int32_t, int32_t, int32_t, int32_t, int32_t>, int32_t> known_;  // (type,a,na,b,nb) -> wire
+    // (type,a,na,b,nb,c,nc) -> wire; c = kUndefId for a two-input gate
+    std::map<std::tuple<int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t>, int32_t> known_;
 };
 
 // One gate as the device executor consumes it.  Slots index the wire store;
 // slot -1 means the constant (0,-1/8).  flags bit0 = negate the operand.
-// c_*: third operand of a GATE_MUX (unused, slot -1, otherwise).
+// c_*: third operand of a GATE_MUX, GATE_MAJ3 or GATE_XOR3 (unused, slot -1, otherwise).
 struct DevGate {
     int32_t type;
     int32_t a_slot, a_neg;
@@ -134,6 +145,11 @@ struct Circuit {
     // bootstraps twice), so that batch x n_bootstraps is what an evaluation reports and a width is what a launch holds.
     int64_t n_bootstraps = 0, n_and = 0, n_xor = 0;
     int64_t n_by_type[GATE_TYPES] = {};  // gates by the type they were requested as (a MUX counts 1 here)
+    int64_t n_maj3 = 0, n_xor3 = 0;      // the three-input gates, whose codes lie outside n_by_type
+    int64_t count_of(int32_t type) const {  // gates of any valid type code; -1 for a code that names no gate
+        if (type >= 0 && type < GATE_TYPES) return n_by_type[type];
+        return type == GATE_MAJ3 ? n_maj3 : type == GATE_XOR3 ? n_xor3 : -1;
+    }
     int32_t depth = 0, max_width = 0;  // ASAP depth / widest ASAP level
     int32_t sched_max_width = 0;       // widest level of the schedule actually executed
     int64_t n_reference_bootstraps = 0;  // what cloud.c performs for this circuit (== n_bootstraps unless folded)
@@ -180,6 +196,15 @@ enum CircuitKind : int32_t {
     // 32 levels instead of mul32's 255 and fewer bootstraps -- for single expressions, where depth is
     // what a level-batched evaluator pays for (cloud.c:115-218 is a 32-round ripple accumulate).
     CIRC_MUL_WALLACE = 9,
+    // The same operators on the two-bootstrap full adder: sum = XOR3(x, y, c), carry = MAJ3(x, y, c) (opt-in; same inputs,
+    // outputs and decrypted result as ADD / SUB / RSUB / MUL, NOT the reference's gate sequence).  ADD_FA is a ripple whose
+    // carry-in is bit 0 of the carry word, as the reference's; SUB_FA / RSUB_FA add the complement with a constant-true
+    // carry-in, so like the _KS kinds they need a carry word that encrypts 0 (alice.c:147-149).  MUL_FA: bits*bits ANDs, a
+    // row-by-row carry-save array of full adders, one full-adder ripple over the last two rows.
+    CIRC_ADD_FA = 16,
+    CIRC_SUB_FA = 17,
+    CIRC_RSUB_FA = 18,
+    CIRC_MUL_FA = 19,
     // any two operators chained as compute_final() does
     // (Cloud/dragonfly_cipher_cloud.py:1300-1327), fused into one DAG: stage 1 = k1(A, B),
     // stage 2 = k2(op1, op2) with (op1, op2) = (answer, C) when flip (cloud.data = answer | C,

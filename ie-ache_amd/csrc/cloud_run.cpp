@@ -244,9 +244,12 @@ void cloud_prepare(const CloudRunIO& io, CloudJob* job, CloudRunReport* report) 
     // single expression; NOT the reference's gate sequence, so off unless asked for.
     if (const char* adder = getenv("IEACHE_ADDER")) {
         if (std::string(adder) == "kogge-stone" && kind >= CIRC_ADD && kind <= CIRC_RSUB) kind += CIRC_ADD_KS - CIRC_ADD;
+        // ... or the two-bootstrap full adder (MAJ3 / XOR3): 2.5x fewer bootstraps and 3x fewer levels, at any batch
+        else if (std::string(adder) == "full-adder" && kind >= CIRC_ADD && kind <= CIRC_RSUB) kind += CIRC_ADD_FA - CIRC_ADD;
     }
     if (const char* mult = getenv("IEACHE_MULTIPLIER")) {  // opt-in carry-save multiplier: 32 levels instead of 255 at 32 bits
         if (std::string(mult) == "wallace" && kind == CIRC_MUL) kind = CIRC_MUL_WALLACE;
+        else if (std::string(mult) == "full-adder" && kind == CIRC_MUL) kind = CIRC_MUL_FA;  // carry-save array of full adders
     }
     // Opt-in constant folding (SURVEY App. C note): fewer bootstraps, same decrypted answer, not the
     // reference's ciphertext bits
@@ -274,7 +277,7 @@ void cloud_finish(const CloudRunIO& io, const CloudJob& job, const Torus32* out,
     const int32_t n = job.params.n;
     const size_t S = (size_t)n + 1;
     fprintf(log, "Computation Time: %lf[sec]\n", seconds);
-    if (job.kind == CIRC_MUL || job.kind == CIRC_MUL_WALLACE) {  // cloud.c:2467-2471
+    if (job.kind == CIRC_MUL || job.kind == CIRC_MUL_WALLACE || job.kind == CIRC_MUL_FA) {  // cloud.c:2467-2471
         FILE* t_file = io.stats_path.empty() ? nullptr : fopen(io.stats_path.c_str(), "a");
         if (t_file) {
             fprintf(t_file, "%lf\n", seconds);

@@ -36,7 +36,7 @@ struct WorkDesc {
     int32_t n_slots;
     const Torus32* flat_a;  // flat mode: rows [item]
     const Torus32* flat_b;
-    const Torus32* flat_c;  // third operand of bootsMUX (flat_type == kFlatMux)
+    const Torus32* flat_c;  // third operand: of bootsMUX (flat_type == kFlatMux), of GATE_MAJ3 / GATE_XOR3
     Torus32* flat_out;
     int32_t flat_type;
     int64_t item0;
@@ -49,17 +49,22 @@ constexpr int32_t kFlatMux = 16;
 struct GateInst {
     const Torus32* a;
     const Torus32* b;
+    const Torus32* c;  // third operand (GATE_MAJ3 / GATE_XOR3; null otherwise)
     Torus32* out;
-    int32_t sa, sb;  // signed multipliers (0 = operand is the constant, handled via cst)
+    int32_t sa, sb, sc;  // signed multipliers (0 = operand is the constant, handled via cst)
     uint32_t cst;
 };
 
-// multipliers of the two operands and the constant term of a two-input gate
-__device__ __forceinline__ void gate_coeffs(int32_t type, int32_t& ka, int32_t& kb, uint32_t& cst) {
+// multipliers of the operands and the constant term of a one-rotation gate (kc = 0: a two-input gate)
+__device__ __forceinline__ void gate_coeffs(int32_t type, int32_t& ka, int32_t& kb, int32_t& kc, uint32_t& cst) {
     // boot-gates.cpp: AND (0,-1/8)+ca+cb ; XOR (0,1/4)+2(ca+cb) ; OR (0,1/8)+ca+cb ; NAND (0,1/8)-ca-cb ;
     // XNOR (0,-1/4)-2(ca+cb) ; NOR (0,-1/8)-ca-cb ; ANDNY (0,-1/8)-ca+cb ; ANDYN (0,-1/8)+ca-cb ; ORNY (0,1/8)-ca+cb ;
     // ORYN (0,1/8)+ca-cb.  (In a circuit the last five arrive as AND / OR with operand sign flags; flat calls name them.)
+    // Not in libtfhe: MAJ3 ca+cb+cc (phases +-1/8, +-3/8) ; XOR3 (0,1/2)+2(ca+cb+cc) (phases +-1/4) -- DESIGN.md section 7.
+    kc = 0;
     switch (type) {
+        case GATE_MAJ3: ka = kb = kc = 1; cst = 0u; break;
+        case GATE_XOR3: ka = kb = kc = 2; cst = 0x80000000u; break;
         case GATE_AND: ka = kb = 1; cst = 0xE0000000u; break;
         case GATE_XOR: ka = kb = 2; cst = 0x40000000u; break;
         case GATE_OR: ka = kb = 1; cst = 0x20000000u; break;
@@ -75,7 +80,9 @@ __device__ __forceinline__ void gate_coeffs(int32_t type, int32_t& ka, int32_t& 
 
 __device__ __forceinline__ GateInst resolve(const WorkDesc& W, int64_t item, int32_t stride) {
     GateInst g;
-    int32_t type, ka, kb;
+    int32_t type, ka, kb, kc;
+    g.c = nullptr;
+    g.sc = 0;
     if (W.gates) {
         const LevelItem it = level_item(item, W.ng, W.nm);  // nm == 0: (item / ng, item % ng, 0)
         const DevGate d = W.gates[W.g0 + it.gate];
@@ -92,7 +99,11 @@ __device__ __forceinline__ GateInst resolve(const WorkDesc& W, int64_t item, int
                 y_neg = d.c_neg;
             }
         } else {
-            gate_coeffs(type, ka, kb, g.cst);
+            gate_coeffs(type, ka, kb, kc, g.cst);
+            if (kc) {  // a constant third operand has sc != 0 and no row: its b term goes into cst below
+                g.c = d.c_slot >= 0 ? base + (size_t)d.c_slot * stride : nullptr;
+                g.sc = d.c_neg ? -kc : kc;
+            }
         }
         g.a = d.a_slot >= 0 ? base + (size_t)d.a_slot * stride : nullptr;
         g.b = y_slot >= 0 ? base + (size_t)y_slot * stride : nullptr;
@@ -102,6 +113,7 @@ __device__ __forceinline__ GateInst resolve(const WorkDesc& W, int64_t item, int
         // a constant operand is (0, -1/8): only its b term contributes
         if (!g.a) g.cst += (uint32_t)g.sa * 0xE0000000u;
         if (!g.b) g.cst += (uint32_t)g.sb * 0xE0000000u;
+        if (!g.c) g.cst += (uint32_t)g.sc * 0xE0000000u;
     } else if (W.flat_type == kFlatMux) {
         const int64_t gi = item >> 1;
         const bool second = item & 1;
@@ -113,12 +125,16 @@ __device__ __forceinline__ GateInst resolve(const WorkDesc& W, int64_t item, int
         g.sb = 1;
     } else {
         type = W.flat_type;
-        gate_coeffs(type, ka, kb, g.cst);
+        gate_coeffs(type, ka, kb, kc, g.cst);
         g.a = W.flat_a + (size_t)item * stride;
         g.b = W.flat_b ? W.flat_b + (size_t)item * stride : nullptr;
         g.out = W.flat_out + (size_t)item * stride;
         g.sa = ka;
         g.sb = kb;
+        if (kc) {
+            g.c = W.flat_c + (size_t)item * stride;
+            g.sc = kc;
+        }
         if (type < 0) {  // raw bootstrap of the row in flat_a (debug hook)
             g.sa = 1;
             g.sb = 0;
@@ -133,6 +149,7 @@ __device__ __forceinline__ uint32_t combined_coef(const GateInst& g, int32_t i, 
     uint32_t v = 0;
     if (g.a) v += (uint32_t)g.sa * (uint32_t)g.a[i];
     if (g.b) v += (uint32_t)g.sb * (uint32_t)g.b[i];
+    if (g.c) v += (uint32_t)g.sc * (uint32_t)g.c[i];
     if (i == n) v += g.cst;
     return v;
 }

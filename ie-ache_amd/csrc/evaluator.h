@@ -59,6 +59,11 @@ public:
     void gates_device(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b,
                       Torus32* d_out, EvalStats* stats);
 
+    // GATE_MAJ3 / GATE_XOR3: out[i] = gate(a[i], b[i], c[i]), one blind rotation and one key switch per gate like any
+    // two-input gate
+    void gates3_device(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,
+                       EvalStats* stats);
+
     // bootsMUX: out[i] = a[i] ? b[i] : c[i] (two blind rotations + one key switch per gate)
     void mux_device(size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,
                     EvalStats* stats);
@@ -137,7 +142,8 @@ public:
     struct Impl;  // device buffers; defined in evaluator.hip
 
 private:
-    void gates_device_once(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b, Torus32* d_out, EvalStats* stats);
+    void gates_device_once(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,
+                           EvalStats* stats);  // d_c: third operand of GATE_MAJ3 / GATE_XOR3, null otherwise
     void mux_device_once(size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out, EvalStats* stats);
     void eval_circuit_device_once(const Circuit& c, size_t batch, const Torus32* d_in, Torus32* d_out, EvalStats* stats);
     void debug_blind_rotate_once(size_t count, const Torus32* d_x, Torus32* d_acc, int32_t steps);

@@ -647,7 +647,16 @@ void Evaluator::gates_device(int32_t type, size_t count, const Torus32* d_a, con
                              EvalStats* stats) {
     const size_t len = count * (size_t)d_->K.stride;
     run_guarded(*this, &d_->exact_once, &d_->guard_reruns, !overlaps(d_out, len, d_a, len) && !overlaps(d_out, len, d_b, len), stats,
-                [&] { gates_device_once(type, count, d_a, d_b, d_out, stats); });
+                [&] { gates_device_once(type, count, d_a, d_b, nullptr, d_out, stats); });
+}
+
+void Evaluator::gates3_device(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,
+                              EvalStats* stats) {
+    if (!is_gate3(type)) throw std::invalid_argument("not a one-rotation three-input gate type");
+    const size_t len = count * (size_t)d_->K.stride;
+    run_guarded(*this, &d_->exact_once, &d_->guard_reruns,
+                !overlaps(d_out, len, d_a, len) && !overlaps(d_out, len, d_b, len) && !overlaps(d_out, len, d_c, len), stats,
+                [&] { gates_device_once(type, count, d_a, d_b, d_c, d_out, stats); });
 }
 
 void Evaluator::mux_device(size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,
@@ -678,8 +687,8 @@ void Evaluator::begin_call() {
     d_->force_generic_ks = d_->opt.force_generic;
 }
 
-void Evaluator::gates_device_once(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b, Torus32* d_out,
-                                  EvalStats* stats) {
+void Evaluator::gates_device_once(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c,
+                                  Torus32* d_out, EvalStats* stats) {
     begin_call();
     if (count == 0) return;
     Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(stats != nullptr, stream_);
@@ -687,6 +696,7 @@ void Evaluator::gates_device_once(int32_t type, size_t count, const Torus32* d_a
     W.gates = nullptr;
     W.flat_a = d_a;
     W.flat_b = d_b;
+    W.flat_c = d_c;
     W.flat_out = d_out;
     W.flat_type = type;
     W.item0 = 0;

@@ -19,6 +19,8 @@ CIRC_MUL_WALLACE = 9  # carry-save multiplier (decrypt-identical, not bit-identi
 GATE_AND, GATE_XOR, GATE_OR, GATE_NAND, GATE_MUX = 0, 1, 2, 3, 4
 GATE_NOR, GATE_XNOR, GATE_ANDNY, GATE_ANDYN, GATE_ORNY, GATE_ORYN = 5, 6, 7, 8, 9, 10  # libtfhe boot-gates.cpp
 GATE_TYPES = 11
+GATE_MAJ3, GATE_XOR3 = 32, 33  # three-input gates of one bootstrap each (codes outside 0 .. GATE_TYPES-1: include/ieache.h)
+CIRC_ADD_FA, CIRC_SUB_FA, CIRC_RSUB_FA, CIRC_MUL_FA = 16, 17, 18, 19  # on the MAJ3 / XOR3 full adder (decrypt-identical)
 # references inside a Netlist (IEACHE_NET_*): wire << 1 | negated, or a constant
 FALSE, TRUE = -2, -1
 
@@ -154,6 +156,12 @@ def lib():
     L.ieache_prepare_batch.argtypes = [vp, C.c_int, C.c_int, C.c_size_t]
     L.ieache_gates_device.argtypes = [vp, C.c_int, C.c_size_t, vp, vp, vp, sp]
     L.ieache_gates.argtypes = [vp, C.c_int, C.c_size_t, i32p, i32p, i32p, sp]
+    L.ieache_gates3_device.argtypes = [vp, C.c_int, C.c_size_t, vp, vp, vp, vp, sp]
+    L.ieache_gates3.argtypes = [vp, C.c_int, C.c_size_t, i32p, i32p, i32p, i32p, sp]
+    L.ieache_circuit_gate_count.restype = C.c_int64
+    L.ieache_circuit_gate_count.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    L.ieache_netlist_gate_count.restype = C.c_int64
+    L.ieache_netlist_gate_count.argtypes = [vp, C.c_int]
     L.ieache_netlist_create.restype = vp
     L.ieache_netlist_create.argtypes = [C.c_int32, vp, C.c_size_t, i32p, C.c_size_t, C.c_int]
     L.ieache_netlist_destroy.argtypes = [vp]
@@ -217,6 +225,11 @@ def circuit_info(kind, bits, fold=False, level_cap=0):
     return info
 
 
+def circuit_gate_count(kind, bits, gate_type, fold=False):
+    """Gates of one GATE_* type (MAJ3 / XOR3 included) in a built-in circuit."""
+    return check(lib().ieache_circuit_gate_count(kind, bits, int(fold), int(gate_type)))
+
+
 def circuit_level_cap(kind, bits, batch, resident_workgroups=1024, fold=False):
     """Level width for `batch` expressions on a GPU that holds `resident_workgroups` blind rotations at once ("level_quantum");
     0 = the default schedule.  What a given context picks (its device's residency, both kernels): Context.circuit_level_cap."""
@@ -258,7 +271,7 @@ class Netlist:
         return [self.input(first + i) for i in range(count)]
 
     def gate(self, gate_type, a, b, c=0):
-        """Records one gate and returns the reference of its output; c is bootsMUX's third operand (a ? b : c)."""
+        """Records one gate and returns the reference of its output; c is the third operand of MUX (a ? b : c), MAJ3 and XOR3."""
         self._gates.append((int(gate_type), int(a), int(b), int(c)))
         return (self.n_inputs + len(self._gates) - 1) << 1
 
@@ -273,6 +286,9 @@ class Netlist:
     def ORNY(self, a, b): return self.gate(GATE_ORNY, a, b)
     def ORYN(self, a, b): return self.gate(GATE_ORYN, a, b)
     def MUX(self, a, b, c): return self.gate(GATE_MUX, a, b, c)
+    # one bootstrap each; three different wires (constants may repeat) -- compile() refuses a repeated wire
+    def MAJ3(self, a, b, c): return self.gate(GATE_MAJ3, a, b, c)
+    def XOR3(self, a, b, c): return self.gate(GATE_XOR3, a, b, c)
 
     def __len__(self):
         return len(self._gates)
@@ -318,8 +334,12 @@ class CompiledNetlist:
         return self._info
 
     def gates_by_type(self):
-        """Gates recorded, indexed by GATE_* (a MUX counts 1)."""
+        """Gates recorded, indexed by GATE_* (a MUX counts 1).  MAJ3 / XOR3 lie outside this list: gate_count()."""
         return [int(v) for v in self._by_type]
+
+    def gate_count(self, gate_type):
+        """Gates recorded with one GATE_* type, MAJ3 / XOR3 included."""
+        return check(lib().ieache_netlist_gate_count(self.h, int(gate_type)))
 
     def simulate(self, in_bits):
         """Plaintext run (host only): in_bits [n_inputs] -> [n_outputs], each 0/1."""
@@ -486,6 +506,19 @@ class Context:
     def gates_device(self, gate_type, count, d_a, d_b, d_out, stats=None):
         check(lib().ieache_gates_device(self.h, gate_type, count, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out),
                                         C.byref(stats) if stats is not None else None))
+
+    def gates3(self, gate_type, a, b, c, stats=None):
+        """GATE_MAJ3 / GATE_XOR3 on host rows: out[i] = gate(a[i], b[i], c[i]), one bootstrap per gate."""
+        a, b, c = (np.ascontiguousarray(v, dtype=np.int32) for v in (a, b, c))
+        assert a.shape == b.shape == c.shape and a.shape[-1] == self.params.n + 1
+        out = np.zeros_like(a)
+        check(lib().ieache_gates3(self.h, gate_type, a.size // (self.params.n + 1), _i32(a), _i32(b), _i32(c), _i32(out),
+                                  C.byref(stats) if stats is not None else None))
+        return out
+
+    def gates3_device(self, gate_type, count, d_a, d_b, d_c, d_out, stats=None):
+        check(lib().ieache_gates3_device(self.h, gate_type, count, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_c),
+                                         C.c_void_p(d_out), C.byref(stats) if stats is not None else None))
 
     def mux(self, a, b, c, stats=None):
         """bootsMUX on host rows: out[i] = a[i] ? b[i] : c[i]."""

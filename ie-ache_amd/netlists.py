@@ -1,8 +1,9 @@
 """Worked examples of caller-defined circuits (evaluator.Netlist): comparison, minimum / maximum and division of unsigned
 integers, built from the gates the libtfhe tutorial builds them from -- bootsXNOR and bootsMUX -- plus XOR / AND for the
-subtraction.  Pure Python over Netlist; each returns a CompiledNetlist.
+subtraction; and an adder on the two-bootstrap full adder (MAJ3 / XOR3).  Pure Python over Netlist; each returns a
+CompiledNetlist.
 
-Input samples per expression, for all three: A's bits (LSB first), then B's bits.  Nothing here is folded: a gate with a
+Input samples per expression, for all of them: A's bits (LSB first), then B's bits.  Nothing here is folded: a gate with a
 constant operand is bootstrapped like any other, as the reference does.
 """
 from .evaluator import FALSE, NOT, TRUE, Netlist
@@ -60,3 +61,16 @@ def divmod(bits, balanced=False):
         quo[i] = NOT(borrow)
         rem = [nl.MUX(borrow, xj, dj) for xj, dj in zip(x[:bits], diff[:bits])]
     return nl.compile(quo + rem, balanced=balanced)
+
+
+def adder_fa(bits, balanced=False):
+    """Outputs A + B (bits samples, LSB first), then the carry out: a ripple of full adders of two bootstraps each --
+    sum = XOR3(a, b, carry), carry = MAJ3(a, b, carry) -- where the reference's add() (Cloud/cloud.c:18-51) spends five.
+    Bit 0 has no carry in: it is the half adder XOR / AND.  2 x bits bootstraps, bits levels."""
+    nl = Netlist(2 * bits)
+    a, b = nl.inputs(0, bits), nl.inputs(bits, bits)
+    sums, carry = [nl.XOR(a[0], b[0])], nl.AND(a[0], b[0])
+    for ai, bi in zip(a[1:], b[1:]):
+        sums.append(nl.XOR3(ai, bi, carry))
+        carry = nl.MAJ3(ai, bi, carry)
+    return nl.compile(sums + [carry], balanced=balanced)

@@ -12,7 +12,7 @@
  * Streams: a context launches on its own non-blocking HIP stream
  * (ieache_ctx_stream).  Every entry point that takes DEVICE pointers
  * (ieache_ctx_create_device, ieache_eval_batch_device, ieache_gates_device,
- * ieache_mux_device) reads them on that stream without ordering against the
+ * ieache_gates3_device, ieache_mux_device) reads them on that stream without ordering against the
  * stream that produced them: the caller must either have synchronised the
  * producing stream (torch.cuda.synchronize(), hipStreamSynchronize) or call
  * ieache_ctx_wait_stream(ctx, producer) first.  Outputs are complete when the
@@ -74,6 +74,16 @@ typedef struct ieache_stats {
                                      product as MUL, ~8x fewer levels (32 instead of 255 at 32 bits) and fewer
                                      bootstraps; not the reference's ciphertext; IEACHE_MULTIPLIER=wallace selects
                                      it for the process contract */
+/* The same four operators on the two-bootstrap full adder, sum = XOR3(x,y,c), carry = MAJ3(x,y,c) (opt-in: same inputs,
+ * outputs and decrypted result, not the reference's gate sequence; IEACHE_ADDER=full-adder / IEACHE_MULTIPLIER=full-adder
+ * select them for the process contract).  ADD_FA: 2 bootstraps per bit instead of 5, one level per bit instead of 3; its
+ * carry-in is bit 0 of the carry word, as the reference's.  SUB_FA / RSUB_FA add the complement with a constant-true carry-in
+ * and so need a carry word that encrypts 0 (alice.c:147-149), like the _KS kinds.  MUL_FA (32/64/128 bits): bits*bits ANDs, a
+ * carry-save array of full adders, one full-adder ripple: 3*bits*bits - 2*bits bootstraps, 2*bits - 1 levels. */
+#define IEACHE_CIRC_ADD_FA 16
+#define IEACHE_CIRC_SUB_FA 17
+#define IEACHE_CIRC_RSUB_FA 18
+#define IEACHE_CIRC_MUL_FA 19
 #define IEACHE_CIRC_MULADD 5  /* (A*B)+C, the compute_final() chaining of
                                  Cloud/dragonfly_cipher_cloud.py:1300-1327 fused; 32-, 64- or 128-bit A,B
                                  (= IEACHE_CIRC_CHAIN(MUL, ADD, 1)) */
@@ -105,6 +115,13 @@ typedef struct ieache_stats {
 #define IEACHE_GATE_ORNY 9
 #define IEACHE_GATE_ORYN 10
 #define IEACHE_GATE_TYPES 11
+/* Three-input gates of ONE bootstrap each (not libtfhe's): a gate bootstrap takes the sign of a linear combination of its
+ * inputs, and with the +-1/8 encoding MAJ3(a,b,c) = bootstrap(ca + cb + cc) (phases +-1/8, +-3/8) and XOR3(a,b,c) =
+ * bootstrap((0,1/2) + 2(ca + cb + cc)) (phases +-1/4).  Noise budget: DESIGN.md section 7.  Own entry points
+ * (ieache_gates3*), netlist gates, and the gates of the IEACHE_CIRC_*_FA kinds.  Their codes lie outside
+ * 0 .. IEACHE_GATE_TYPES-1: arrays sized by IEACHE_GATE_TYPES do not count them (ieache_netlist_gate_count does). */
+#define IEACHE_GATE_MAJ3 32
+#define IEACHE_GATE_XOR3 33
 
 typedef struct ieache_circuit_info {
     int32_t n_inputs;    /* samples per expression: A bits, B bits, 32-sample carry word [, C bits] */
@@ -233,6 +250,9 @@ int ieache_circuit_level_cap(int kind, int bits, int fold_constants, int64_t bat
 int ieache_ctx_circuit_level_cap(const ieache_ctx* ctx, int kind, int bits, int64_t batch);
 int ieache_circuit_info_get_cap(int kind, int bits, int fold_constants, int level_cap, ieache_circuit_info* out);
 int ieache_circuit_simulate_cap(int kind, int bits, int fold_constants, int level_cap, const uint8_t* in_bits, uint8_t* out_bits);
+/* gates of one IEACHE_GATE_* type (MAJ3 / XOR3 included) in a built-in circuit, counted as ieache_netlist_info counts them;
+ * IEACHE_EINVAL for a code that names no gate type */
+int64_t ieache_circuit_gate_count(int kind, int bits, int fold_constants, int gate_type);
 /* host buffers: in [batch][n_inputs][n+1], out [batch][n_outputs][n+1] */
 int ieache_eval_batch(ieache_ctx* ctx, int kind, int bits, size_t batch, const int32_t* in_lwe, int32_t* out_lwe,
                       ieache_stats* stats);
@@ -252,6 +272,12 @@ int ieache_gates_device(ieache_ctx* ctx, int gate_type, size_t count, const int3
 /* host rows of n+1 */
 int ieache_gates(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* a, const int32_t* b, int32_t* out,
                  ieache_stats* stats);
+/* out[i] = gate(a[i], b[i], c[i]) for gate_type IEACHE_GATE_MAJ3 or IEACHE_GATE_XOR3 (any other type: IEACHE_EINVAL): one
+ * blind rotation and one key switch per gate, like a two-input gate.  No libtfhe counterpart; a full adder is these two. */
+int ieache_gates3_device(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* d_a, const int32_t* d_b, const int32_t* d_c,
+                         int32_t* d_out, ieache_stats* stats);
+int ieache_gates3(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* a, const int32_t* b, const int32_t* c, int32_t* out,
+                  ieache_stats* stats);
 /* out[i] = a[i] ? b[i] : c[i]; replaces bootsMUX (libtfhe boot-gates.cpp): per gate two blind
  * rotations without key switch, their extracted samples added to (0, 1/8), one key switch.
  * stats->bootstraps counts the blind rotations (2 per gate). */
@@ -273,7 +299,9 @@ int ieache_mux(ieache_ctx* ctx, size_t count, const int32_t* a, const int32_t* b
 #define IEACHE_NET_NOT(ref) ((ref) ^ 1)
 #define IEACHE_NET_FALSE (-2)
 #define IEACHE_NET_TRUE (-1)
-/* one gate: type is an IEACHE_GATE_* value; c is read for IEACHE_GATE_MUX only (a ? b : c) and must be 0 otherwise */
+/* one gate: type is an IEACHE_GATE_* value; c is the third operand of IEACHE_GATE_MUX (a ? b : c), IEACHE_GATE_MAJ3 and
+ * IEACHE_GATE_XOR3, and must be 0 otherwise.  MAJ3 / XOR3 must name three different wires (constants may repeat): the same
+ * wire twice adds its noise coherently and eats the margin. */
 typedef struct ieache_net_gate {
     int32_t type, a, b, c;
 } ieache_net_gate;
@@ -284,7 +312,8 @@ typedef struct ieache_netlist ieache_netlist;
  * every call that uses it.  A gate may only refer to inputs and to gates before it.  Every recorded gate is bootstrapped:
  * the context options "fold_constants" and "level_quantum" do not apply to netlists (fold what you want folded before
  * recording).  -> NULL with ieache_last_error() naming the offending gate: an operand or output that refers to a wire not
- * defined at that point, an unknown type, a third operand on a two-input gate, no inputs / no outputs, more than 2^30 wires. */
+ * defined at that point, an unknown type, a third operand on a two-input gate, a MAJ3 / XOR3 that names a wire twice, no
+ * inputs / no outputs, more than 2^30 wires. */
 ieache_netlist* ieache_netlist_create(int32_t n_inputs, const ieache_net_gate* gates, size_t n_gates, const int32_t* outputs,
                                       size_t n_outputs, int flags);
 void ieache_netlist_destroy(ieache_netlist* nl);
@@ -293,6 +322,9 @@ void ieache_netlist_destroy(ieache_netlist* nl);
  * n_and / n_xor count the AND / XOR gates the executor runs (NOR, ANDNY, ANDYN run as AND with negated operands).
  * gates_by_type (may be NULL): gates recorded, by the IEACHE_GATE_* type they were given as (a MUX counts 1 here). */
 int ieache_netlist_info(const ieache_netlist* nl, ieache_circuit_info* out, int64_t gates_by_type[IEACHE_GATE_TYPES]);
+/* gates recorded with one IEACHE_GATE_* type, for any valid type code -- IEACHE_GATE_MAJ3 / _XOR3 too, which gates_by_type
+ * above has no room for; IEACHE_EINVAL for a code that names no gate type */
+int64_t ieache_netlist_gate_count(const ieache_netlist* nl, int gate_type);
 /* plaintext simulation (host only, no GPU): in_bits [n_inputs] -> out_bits [n_outputs], each 0/1 */
 int ieache_netlist_simulate(const ieache_netlist* nl, const uint8_t* in_bits, uint8_t* out_bits);
 /* the netlist counterparts of ieache_prepare_batch / ieache_eval_batch / ieache_eval_batch_device: same buffer shapes
