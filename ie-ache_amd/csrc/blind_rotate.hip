@@ -103,13 +103,14 @@ __global__ __launch_bounds__(kThreads) void k_blind_rotate_generic(DevKeys K, Wo
             s_barb = bar;
     }
     __syncthreads();
-    // K2: acc = (0, X^{2N-barb} * (mu,...,mu))
+    // K2: acc = (0, X^{2N-barb} * (mu,...,mu)); a programmable bootstrap starts from its item's test polynomial instead
     {
         const int32_t a0 = (2 * N - s_barb) & (2 * N - 1);
+        const Torus32* v = test_poly_row(W, W.item0 + item, N);
         for (int32_t j = threadIdx.x; j < N; j += blockDim.x) {
             acc[j] = 0;
             const int32_t idx = (j - a0) & (2 * N - 1);
-            acc[N + j] = idx < N ? kMU : -kMU;
+            acc[N + j] = v ? rot_coef(v, j, a0, N) : (idx < N ? kMU : -kMU);
         }
     }
     __syncthreads();
@@ -249,6 +250,7 @@ void BlindRotate::reserve(BrScratch& scratch, size_t need, const EvalOptions& op
 
 int BlindRotate::launch(BrScratch& scratch, const BrPlan& plan, const EvalOptions& opt, const BrLanes& lanes, hipStream_t stream, const WorkDesc& w,
                         int64_t cnt, Torus32* ext, int32_t steps, Torus32* dbg_acc) {
+    if (!w.gates && w.tv && w.n_tv < 1) throw std::invalid_argument("programmable bootstrap without test polynomials");
     if (plan.generic) {
         hipLaunchKernelGGL(k_blind_rotate_generic, dim3((unsigned)cnt), dim3(kThreads), generic_lds_, stream, K_, w, ext, steps, dbg_acc);
         return 1;

@@ -101,6 +101,9 @@ __global__ __launch_bounds__(64) void k_bk_to_spectrum_w64_1(const Torus32* bk_r
 // One 128-thread workgroup per gate instance.  Writes the rotation amounts
 // bara[n] (u16, row stride nb) and the initial accumulator [2][1024] to the
 // blind-rotation state in HBM, from where the sliced kernel below picks up.
+// TV: a programmable bootstrap -- the accumulator starts from the item's row of W.tv (device_common.h) instead of the constant
+// polynomial; the TV = false build is the gate path's prologue, instruction for instruction what it was without the template.
+template <bool TV>
 __global__ __launch_bounds__(128) void k_br_prologue(DevKeys K, WorkDesc W, uint16_t* st_bara, int32_t nb, int32_t* st_acc) {
     __shared__ int32_t s_barb;
     const int tid = threadIdx.x;
@@ -116,14 +119,18 @@ __global__ __launch_bounds__(128) void k_br_prologue(DevKeys K, WorkDesc W, uint
             s_barb = bar;
     }
     __syncthreads();
-    // acc = (0, X^{2N-barb} * (mu,...,mu))
+    // acc = (0, X^{2N-barb} * (mu,...,mu)), or (0, X^{2N-barb} * v) for the item's test polynomial v
     const int32_t a0 = (2 * kN - s_barb) & (2 * kN - 1);
     int32_t* acc = st_acc + (size_t)item * 2 * kN;
+    const Torus32* v = TV ? test_poly_row(W, W.item0 + item, kN) : nullptr;
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         const int32_t j = 128 * r + tid;
         acc[j] = 0;
-        acc[kN + j] = ((j - a0) & (2 * kN - 1)) < kN ? kMU : -kMU;
+        if (TV)
+            acc[kN + j] = rot_coef(v, j, a0, kN);
+        else
+            acc[kN + j] = ((j - a0) & (2 * kN - 1)) < kN ? kMU : -kMU;
     }
 }
 
@@ -1344,7 +1351,10 @@ int launch(const Params& p, const DevKeys& K, const Tables& t, const BrPlan& pla
     // state block: [items][2][1024] int32 accumulators, then [items][nb] u16 rotation amounts
     int32_t* st_acc = reinterpret_cast<int32_t*>(state);
     uint16_t* st_bara = reinterpret_cast<uint16_t*>(st_acc + (size_t)items * 2 * kN);
-    hipLaunchKernelGGL(k_br_prologue, dim3((unsigned)items), dim3(128), 0, stream, K, W, st_bara, nb, st_acc);
+    if (!W.gates && W.tv)  // a programmable bootstrap (BlindRotate::launch has checked the table)
+        hipLaunchKernelGGL(k_br_prologue<true>, dim3((unsigned)items), dim3(128), 0, stream, K, W, st_bara, nb, st_acc);
+    else
+        hipLaunchKernelGGL(k_br_prologue<false>, dim3((unsigned)items), dim3(128), 0, stream, K, W, st_bara, nb, st_acc);
     auto one = [&](int v, int32_t i0, int32_t i1, Torus32* e) {
         launch_slice(v, plan.wg_gates, Slice{p.l, items, stream, K, t, st_bara, nb, st_acc, i0, i1, e, plan.w4r_flip});
     };

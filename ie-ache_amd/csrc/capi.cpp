@@ -642,6 +642,70 @@ int ieache_gates3(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* a
     });
 }
 
+int ieache_extract_stride(const ieache_ctx* ctx) { return ctx ? ctx->eval->extract_stride() : IEACHE_EINVAL; }
+
+int ieache_pbs_device(ieache_ctx* ctx, size_t count, const int32_t* d_x, const int32_t* d_test_polys, int32_t n_polys,
+                      const int32_t* d_poly_of, int32_t* d_out, int flags, ieache_stats* stats) {
+    return guarded([&] {
+        if (flags & ~IEACHE_PBS_NO_KEYSWITCH) return fail(IEACHE_EINVAL, "pbs: unknown flag");
+        if (n_polys < 1) return fail(IEACHE_EINVAL, "pbs: n_polys must be at least 1");
+        if (!d_test_polys) return fail(IEACHE_EINVAL, "pbs: null test polynomial table");
+        if (!ctx || !d_x || !d_out) return fail(IEACHE_EINVAL, "null argument");
+        if (count) {
+            require_device_pointer(d_x, "d_x");
+            require_device_pointer(d_test_polys, "d_test_polys");
+            if (d_poly_of) require_device_pointer(d_poly_of, "d_poly_of");
+            require_device_pointer(d_out, "d_out");
+        }
+        EvalStats st;
+        ctx->eval->pbs_device(count, d_x, d_test_polys, n_polys, d_poly_of, d_out, flags, stats ? &st : nullptr);
+        to_stats(st, stats);
+        return 0;
+    });
+}
+
+int ieache_pbs(ieache_ctx* ctx, size_t count, const int32_t* x, const int32_t* test_polys, int32_t n_polys, const int32_t* poly_of,
+               int32_t* out, int flags, ieache_stats* stats) {
+    return guarded([&] {
+        // what can be judged without the context comes first
+        if (flags & ~IEACHE_PBS_NO_KEYSWITCH) return fail(IEACHE_EINVAL, "pbs: unknown flag");
+        if (n_polys < 1) return fail(IEACHE_EINVAL, "pbs: n_polys must be at least 1");
+        if (!test_polys) return fail(IEACHE_EINVAL, "pbs: null test polynomial table");
+        for (size_t i = 0; poly_of && i < count; i++)
+            if (poly_of[i] < 0 || poly_of[i] >= n_polys)
+                return fail(IEACHE_EINVAL, "pbs: poly_of[" + std::to_string(i) + "] = " + std::to_string(poly_of[i]) + " is outside [0, n_polys)");
+        if (!ctx || !x || !out) return fail(IEACHE_EINVAL, "null argument");
+        const Params& p = ctx->eval->params();
+        const bool woks = (flags & IEACHE_PBS_NO_KEYSWITCH) != 0;
+        const size_t out_stride = woks ? (size_t)ctx->eval->extract_stride() : (size_t)p.lwe_stride();
+        const size_t out_width = woks ? (size_t)p.N + 1 : (size_t)p.n + 1;
+        HIP_CHECK(hipSetDevice(ctx->eval->device()));
+        StagedRows dx(*ctx->eval, 0, count, p.lwe_stride()), dout(*ctx->eval, 3, count, out_stride);
+        StagedRows dtv(*ctx->eval, 4, (size_t)n_polys, (size_t)p.N), dof(*ctx->eval, 5, poly_of ? count : 0, 1);
+        dx.upload(x, p.n + 1);
+        dtv.upload(test_polys, (size_t)p.N);
+        if (poly_of) dof.upload(poly_of, 1);
+        EvalStats st;
+        ctx->eval->pbs_device(count, dx.p, dtv.p, n_polys, poly_of ? dof.p : nullptr, dout.p, flags, stats ? &st : nullptr);
+        dout.download(out, out_width);
+        to_stats(st, stats);
+        return 0;
+    });
+}
+
+int ieache_lut_test_poly(const ieache_params* p, int32_t entries, const int32_t* f, int32_t* v) {
+    if (!p || !f || !v) return fail(IEACHE_EINVAL, "null argument");
+    const int64_t N = p->N;
+    if (N < 2 || entries < 1 || N % (2 * (int64_t)entries) != 0) return fail(IEACHE_EINVAL, "lut_test_poly: 2 x entries must divide N");
+    const int64_t half_slot = N / (2 * (int64_t)entries);
+    for (int64_t j = 0; j < N; j++) {
+        const int64_t e = (j + half_slot) * entries / N;  // the slot centred on message e covers phases (e -+ 1/2) / (2 entries)
+        v[j] = e < entries ? f[e] : (int32_t)(0u - (uint32_t)f[0]);  // past the last slot: f[0] through the negacyclic wrap
+    }
+    g_err.clear();
+    return 0;
+}
+
 int ieache_mux_device(ieache_ctx* ctx, size_t count, const int32_t* d_a, const int32_t* d_b, const int32_t* d_c,
                       int32_t* d_out, ieache_stats* stats) {
     return guarded([&] {

@@ -28,11 +28,25 @@ struct DevKeys {
 // expression (level_items.h); item0 and the item index of a blind-rotation launch count rotation items.  The key switch of
 // such a level runs on one row per GATE: it gets the same descriptor with nm = 0 and item0 in gate instances, for which
 // the arithmetic below is the identity it has always been (only GateInst::out is used there).
+// Programmable bootstrap (flat mode only, tv non-null): the row in flat_a is bootstrapped as it stands (flat_type < 0) and the
+// accumulator starts from X^(2N-barb) * tv[row] instead of the constant polynomial, row = tv_of[item] (null: row 0) clamped
+// into [0, n_tv).  Only the two prologues read these fields.  The descriptor is an argument of every key-switch kernel as
+// well, and a larger one would move their other arguments -- and with them their code -- so the three fields take the bytes
+// of circuit-mode fields, which a flat launch leaves at zero, and of a padding word: sizeof(WorkDesc) is what it was.
 struct WorkDesc {
     const DevGate* gates;  // circuit mode when non-null
-    int32_t g0, ng;
+    union {
+        struct {
+            int32_t g0, ng;
+        };
+        const Torus32* tv;  // flat mode: test polynomials, [n_tv][N]
+    };
     int32_t nm;            // circuit mode: MUX gates among the ng (the last ones)
-    Torus32* store;
+    int32_t n_tv;          // flat mode: rows of tv
+    union {
+        Torus32* store;
+        const int32_t* tv_of;  // flat mode: row of tv per item (indexed like flat_a: item0 + item), or null
+    };
     int32_t n_slots;
     const Torus32* flat_a;  // flat mode: rows [item]
     const Torus32* flat_b;
@@ -41,6 +55,15 @@ struct WorkDesc {
     int32_t flat_type;
     int64_t item0;
 };
+static_assert(sizeof(WorkDesc) == 88, "WorkDesc is a kernel argument: its size and field offsets are part of every kernel that takes it");
+
+// the test polynomial of a programmable-bootstrap item, or null for a gate item (whose test polynomial is the constant kMU)
+__device__ __forceinline__ const Torus32* test_poly_row(const WorkDesc& W, int64_t item, int32_t N) {
+    if (W.gates || !W.tv) return nullptr;
+    int32_t r = W.tv_of ? W.tv_of[item] : 0;
+    r = r < 0 ? 0 : (r >= W.n_tv ? W.n_tv - 1 : r);  // a bad index gives a wrong answer, never a read outside the table
+    return W.tv + (size_t)r * N;
+}
 
 // flat_type of the two blind rotations of bootsMUX(a,b,c) (boot-gates.cpp): item 2g is
 // (0,-1/8) + a + b, item 2g+1 is (0,-1/8) - a + c; neither is key-switched on its own

@@ -64,6 +64,19 @@ public:
     void gates3_device(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,
                        EvalStats* stats);
 
+    // Programmable bootstrap: out[i] = bootstrap of the row x[i] as it stands from the test polynomial tv[tv_of[i]] (row 0
+    // when d_tv_of is null) of d_tv [n_tv][N]: libtfhe's tfhe_blindRotateAndExtract_FFT with testvectbis = X^(2N-barb) * v,
+    // then the key switch.  The result encrypts v[phi] for a mod-switched phase phi < N, -v[phi - N] otherwise
+    // (include/ieache.h states the convention).  One blind rotation and one key switch per row through the flat path of
+    // gates_device: pieces, level halves, rotation of roles, guard and audit.  kPbsNoKeyswitch: the extracted samples are
+    // the result (tfhe_bootstrap_woKS_FFT) -- rows of extract_stride() words, N + 1 of them written, no key-switch launch;
+    // d_out must then not overlap an input (its rows are longer than x's).  An index outside [0, n_tv) is clamped on the device.
+    static constexpr int32_t kPbsNoKeyswitch = 1;
+    void pbs_device(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of, Torus32* d_out,
+                    int32_t flags, EvalStats* stats);
+    // words per device row of extracted samples (N + 1 rounded up to a multiple of 4)
+    int32_t extract_stride() const { return p_.N + 4; }
+
     // bootsMUX: out[i] = a[i] ? b[i] : c[i] (two blind rotations + one key switch per gate)
     void mux_device(size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,
                     EvalStats* stats);
@@ -78,7 +91,8 @@ public:
 
     // Device rows the host-buffer entry points stage operands (slot 0 .. 2) and results (slot 3) in: owned by the evaluator,
     // kept between calls and grown on demand, so that a warm call allocates nothing.  Operand slots are zero outside what
-    // the caller uploads (rows of lwe_stride() words, n + 1 of them uploaded).  get_option("staging_allocations") counts
+    // the caller uploads (rows of lwe_stride() words, n + 1 of them uploaded).  Slots 4 and 5 hold the test polynomials and
+    // the row indices of a programmable bootstrap (whole rows are uploaded; no other call reads them).  get_option("staging_allocations") counts
     // the (re)allocations made so far.
     Torus32* staging(int slot, size_t bytes);
 
@@ -144,6 +158,8 @@ public:
 private:
     void gates_device_once(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,
                            EvalStats* stats);  // d_c: third operand of GATE_MAJ3 / GATE_XOR3, null otherwise
+    void pbs_device_once(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of, Torus32* d_out,
+                         int32_t flags, EvalStats* stats);
     void mux_device_once(size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out, EvalStats* stats);
     void eval_circuit_device_once(const Circuit& c, size_t batch, const Torus32* d_in, Torus32* d_out, EvalStats* stats);
     void debug_blind_rotate_once(size_t count, const Torus32* d_x, Torus32* d_acc, int32_t steps);

@@ -155,7 +155,7 @@ struct Evaluator::Impl {
         int n[2] = {0, 0};            // trials so far (two each, alternating: a first call also pays for allocations)
     };
     std::map<std::tuple<size_t, int32_t, size_t, size_t, bool>, Tuned> tuned;  // (gates, levels, outputs, batch, exact_fft)
-    DeviceBuffer<Torus32> stage[4];  // rows the host-buffer entry points stage operands and results in (counted in bytes)
+    DeviceBuffer<Torus32> stage[6];  // rows the host-buffer entry points stage operands and results in (counted in bytes)
     DevKeys K{};
     BlindRotate br;  // K0-K4: kernels, key forms, guard record, audit and LDS grants; the choice among the kernels is br_plan.h
     double guard_max = 0;        // largest rounding deviation seen by the one-limb kernel (of 0.5)
@@ -249,13 +249,14 @@ void Evaluator::wait_for_stream(hipStream_t producer) {
     HIP_CHECK(e);
 }
 
-// Staging rows for the host-buffer entry points (slot 0 .. 2: operands, 3: results).  A slot grows to at least `bytes`
+// Staging rows for the host-buffer entry points (slot 0 .. 2: operands, 3: results, 4 / 5: test polynomials and row indices
+// of a programmable bootstrap).  A slot grows to at least `bytes`
 // (doubling, so a run of growing batches does not reallocate every call) and is zeroed when it is (re)allocated: callers
 // upload n + 1 words per row of lwe_stride() and rely on the padding words of OPERAND rows being zero, which holds because
 // nothing but such uploads ever writes slots 0 .. 2.  Every hipMalloc / hipFree is a device-wide synchronisation, which is
 // why a warm daemon request must not make one.
 Torus32* Evaluator::staging(int slot, size_t bytes) {
-    if (slot < 0 || slot >= 4) throw std::invalid_argument("staging slot");
+    if (slot < 0 || slot >= 6) throw std::invalid_argument("staging slot");
     HIP_CHECK(hipSetDevice(device_));
     bytes = (bytes + 255) & ~(size_t)255;
     DeviceBuffer<Torus32>& st = d_->stage[slot];
@@ -519,8 +520,10 @@ static void reserve_scratch(const Params& p, Evaluator::Impl* d, const int64_t* 
 // on lane 0 (the previous level) is complete before any piece starts; lane 0 has every piece behind it when this returns.
 // fixed_lane >= 0: the whole level on that lane, in pieces of at most a chunk, no fork / join (a pipeline of its own, see
 // eval_circuit_device_once); its scratch has been reserved by the caller.
+// ext_out (flat mode): the extracted samples are the result -- every piece's blind rotation writes its rows of N + 4 words
+// there, at the piece's first item, and no key switch follows.
 static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t items, Timer& tbr, Timer& tks, EvalStats* stats,
-                      int fixed_lane = -1) {
+                      int fixed_lane = -1, Torus32* ext_out = nullptr) {
     LevelPlan pl = plan_level(d, items);
     // A level with MUX gates (circuit mode, W.nm > 0): `items` are rotation items, two per MUX.  PIECES ARE CUT AT GATE
     // BOUNDARIES (level_piece_items), so both rotations of a MUX are in the same piece, on the same lane, in the same `ext`,
@@ -552,11 +555,19 @@ static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t i
         w.item0 = W.item0 + done;
         if ((size_t)cnt > ln.ext.items()) throw std::logic_error("piece larger than the lane's extracted-sample rows");
         const BrPlan plan = plan_blind_rotate(p, d, ln, cnt);  // once: the launch and the audit see the same choice
+        Torus32* ext = ext_out ? ext_out + (size_t)done * (size_t)(d->K.N + 4) : (Torus32*)ln.ext;
         tbr.mark(ln.stream);
-        const int nbr = launch_blind_rotate(d, ln, plan, w, cnt, ln.ext, -1, nullptr);
+        const int nbr = launch_blind_rotate(d, ln, plan, w, cnt, ext, -1, nullptr);
         tbr.mark(ln.stream);
         HIP_CHECK(hipGetLastError());
-        d->br.audit(ln.br, plan, d->opt, ln.stream, w, cnt, ln.ext);
+        d->br.audit(ln.br, plan, d->opt, ln.stream, w, cnt, ext);
+        if (ext_out) {
+            if (stats) {
+                stats->blind_rotate_launches += nbr;
+                stats->chunks++;
+            }
+            continue;
+        }
         tks.mark(ln.stream);
         if (mux) {
             // one row per gate, then the key switch over GATES: the same level descriptor read with nm = 0 and item0 in gate
@@ -702,6 +713,48 @@ void Evaluator::gates_device_once(int32_t type, size_t count, const Torus32* d_a
     W.item0 = 0;
     tall.mark();
     run_items(p_, d_, W, (int64_t)count, tbr, tks, stats);
+    tall.mark();
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    add_times(stats, tall, tbr, tks);
+    if (stats) stats->levels += 1;
+}
+
+void Evaluator::pbs_device(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of, Torus32* d_out,
+                           int32_t flags, EvalStats* stats) {
+    if (flags & ~kPbsNoKeyswitch) throw std::invalid_argument("programmable bootstrap: unknown flag");
+    if (n_tv < 1 || !d_tv) throw std::invalid_argument("programmable bootstrap: no test polynomial");
+    const bool woks = (flags & kPbsNoKeyswitch) != 0;
+    const size_t len = count * (size_t)d_->K.stride, out_len = count * (size_t)(woks ? extract_stride() : d_->K.stride);
+    const bool over_x = overlaps(d_out, out_len, d_x, len);
+    // a repeat reads the table and the indices again: an output over either of them is over an input as much as one over x
+    const bool over_table = overlaps(d_out, out_len, d_tv, (size_t)n_tv * (size_t)p_.N) ||
+                            overlaps(d_out, out_len, reinterpret_cast<const Torus32*>(d_tv_of), count);
+    if (over_table || (woks && over_x))
+        throw std::invalid_argument(over_table ? "programmable bootstrap: the output overlaps the test polynomials or their indices"
+                                               : "programmable bootstrap without key switch: the output overlaps the input rows");
+    run_guarded(*this, &d_->exact_once, &d_->guard_reruns, !over_x, stats,
+                [&] { pbs_device_once(count, d_x, d_tv, n_tv, d_tv_of, d_out, flags, stats); });
+}
+
+// tfhe_blindRotateAndExtract_FFT from a caller's test polynomial (+ lweKeySwitch): gates_device_once with the raw row of
+// flat_a as the combination and the descriptor carrying the table, so every cut of the launch finds its polynomial
+void Evaluator::pbs_device_once(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of,
+                                Torus32* d_out, int32_t flags, EvalStats* stats) {
+    begin_call();
+    if (count == 0) return;
+    const bool woks = (flags & kPbsNoKeyswitch) != 0;
+    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(stats != nullptr, stream_);
+    WorkDesc W{};
+    W.gates = nullptr;
+    W.flat_a = d_x;
+    W.flat_out = woks ? nullptr : d_out;
+    W.flat_type = -1;  // resolve(): the row as it stands, no second operand, no constant
+    W.tv = d_tv;
+    W.n_tv = n_tv;
+    W.tv_of = d_tv_of;
+    W.item0 = 0;
+    tall.mark();
+    run_items(p_, d_, W, (int64_t)count, tbr, tks, stats, -1, woks ? d_out : nullptr);
     tall.mark();
     HIP_CHECK(hipStreamSynchronize(stream_));
     add_times(stats, tall, tbr, tks);

@@ -19,6 +19,7 @@ CIRC_MUL_WALLACE = 9  # carry-save multiplier (decrypt-identical, not bit-identi
 GATE_AND, GATE_XOR, GATE_OR, GATE_NAND, GATE_MUX = 0, 1, 2, 3, 4
 GATE_NOR, GATE_XNOR, GATE_ANDNY, GATE_ANDYN, GATE_ORNY, GATE_ORYN = 5, 6, 7, 8, 9, 10  # libtfhe boot-gates.cpp
 GATE_TYPES = 11
+PBS_NO_KEYSWITCH = 1  # flag of ieache_pbs*: the extracted samples are the result (tfhe_bootstrap_woKS_FFT)
 GATE_MAJ3, GATE_XOR3 = 32, 33  # three-input gates of one bootstrap each (codes outside 0 .. GATE_TYPES-1: include/ieache.h)
 CIRC_ADD_FA, CIRC_SUB_FA, CIRC_RSUB_FA, CIRC_MUL_FA = 16, 17, 18, 19  # on the MAJ3 / XOR3 full adder (decrypt-identical)
 # references inside a Netlist (IEACHE_NET_*): wire << 1 | negated, or a constant
@@ -158,6 +159,10 @@ def lib():
     L.ieache_gates.argtypes = [vp, C.c_int, C.c_size_t, i32p, i32p, i32p, sp]
     L.ieache_gates3_device.argtypes = [vp, C.c_int, C.c_size_t, vp, vp, vp, vp, sp]
     L.ieache_gates3.argtypes = [vp, C.c_int, C.c_size_t, i32p, i32p, i32p, i32p, sp]
+    L.ieache_pbs_device.argtypes = [vp, C.c_size_t, vp, vp, C.c_int32, vp, vp, C.c_int, sp]
+    L.ieache_pbs.argtypes = [vp, C.c_size_t, i32p, i32p, C.c_int32, i32p, i32p, C.c_int, sp]
+    L.ieache_extract_stride.argtypes = [vp]
+    L.ieache_lut_test_poly.argtypes = [pp, C.c_int32, i32p, i32p]
     L.ieache_circuit_gate_count.restype = C.c_int64
     L.ieache_circuit_gate_count.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     L.ieache_netlist_gate_count.restype = C.c_int64
@@ -519,6 +524,33 @@ class Context:
     def gates3_device(self, gate_type, count, d_a, d_b, d_c, d_out, stats=None):
         check(lib().ieache_gates3_device(self.h, gate_type, count, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_c),
                                          C.c_void_p(d_out), C.byref(stats) if stats is not None else None))
+
+    @property
+    def extract_stride(self):
+        """int32 per device row of extracted samples (pbs_device with keyswitch=False): N + 1 rounded up to a multiple of 4."""
+        return lib().ieache_extract_stride(self.h)
+
+    def pbs(self, x, test_polys, poly_of=None, keyswitch=True, stats=None):
+        """Programmable bootstrap on host rows: x [count][n+1] is bootstrapped row by row as it stands from the test polynomial
+        test_polys[poly_of[i]] (test_polys [n_polys][N] or one polynomial [N]; poly_of None: row 0 for every row).  With the
+        row's mod-switched phase phi in [0, 2N) the result encrypts v[phi] for phi < N and -v[phi - N] otherwise
+        (include/ieache.h; tools.lut_test_poly builds v from a table) -> [count][n+1], or with keyswitch=False the
+        extracted samples [count][N+1] under the ring key."""
+        x = np.ascontiguousarray(x, dtype=np.int32).reshape(-1, self.params.n + 1)
+        tv = np.ascontiguousarray(test_polys, dtype=np.int32).reshape(-1, self.params.N)
+        of = None if poly_of is None else np.ascontiguousarray(poly_of, dtype=np.int32).reshape(-1)
+        assert of is None or of.shape[0] == x.shape[0]
+        out = np.zeros((x.shape[0], (self.params.n if keyswitch else self.params.N) + 1), dtype=np.int32)
+        check(lib().ieache_pbs(self.h, x.shape[0], _i32(x), _i32(tv), tv.shape[0], None if of is None else _i32(of), _i32(out),
+                               0 if keyswitch else PBS_NO_KEYSWITCH, C.byref(stats) if stats is not None else None))
+        return out
+
+    def pbs_device(self, count, d_x, d_test_polys, n_polys, d_poly_of, d_out, keyswitch=True, stats=None):
+        """Device pointers (ints; d_poly_of may be None / 0): x rows of lwe_stride, test polynomials [n_polys][N] packed, out rows of
+        lwe_stride or, with keyswitch=False, of extract_stride."""
+        check(lib().ieache_pbs_device(self.h, count, C.c_void_p(d_x), C.c_void_p(d_test_polys), int(n_polys),
+                                      C.c_void_p(d_poly_of or None), C.c_void_p(d_out), 0 if keyswitch else PBS_NO_KEYSWITCH,
+                                      C.byref(stats) if stats is not None else None))
 
     def mux(self, a, b, c, stats=None):
         """bootsMUX on host rows: out[i] = a[i] ? b[i] : c[i]."""

@@ -60,6 +60,15 @@ def decrypt_bits(params, lwe_key, samples):
     return bits
 
 
+def lut_test_poly(params, table):
+    """Test polynomial [N] of a lookup table of Torus32 values for Context.pbs: messages m < len(table) encoded at phase
+    m / (2 len(table)), every slot centred on its message (ieache_lut_test_poly; 2 len(table) must divide N)."""
+    f = np.ascontiguousarray(table, dtype=np.int32).reshape(-1)
+    v = np.zeros(params.N, dtype=np.int32)
+    check(lib().ieache_lut_test_poly(C.byref(params), f.shape[0], _i32(f), _i32(v)))
+    return v
+
+
 def int_to_bits(value, nbits):
     return np.array([(int(value) >> i) & 1 for i in range(nbits)], dtype=np.uint8)
 

@@ -12,7 +12,7 @@
  * Streams: a context launches on its own non-blocking HIP stream
  * (ieache_ctx_stream).  Every entry point that takes DEVICE pointers
  * (ieache_ctx_create_device, ieache_eval_batch_device, ieache_gates_device,
- * ieache_gates3_device, ieache_mux_device) reads them on that stream without ordering against the
+ * ieache_gates3_device, ieache_pbs_device, ieache_mux_device) reads them on that stream without ordering against the
  * stream that produced them: the caller must either have synchronised the
  * producing stream (torch.cuda.synchronize(), hipStreamSynchronize) or call
  * ieache_ctx_wait_stream(ctx, producer) first.  Outputs are complete when the
@@ -278,6 +278,38 @@ int ieache_gates3_device(ieache_ctx* ctx, int gate_type, size_t count, const int
                          int32_t* d_out, ieache_stats* stats);
 int ieache_gates3(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* a, const int32_t* b, const int32_t* c, int32_t* out,
                   ieache_stats* stats);
+/* Programmable (functional) bootstrap: one blind rotation from a CALLER'S test polynomial instead of the constant
+ * (1/8, ..., 1/8) every gate starts from.  Replaces libtfhe's tfhe_blindRotateAndExtract_FFT(result, v, bk, barb, bara, ...)
+ * (arbitrary test polynomial v), tfhe_bootstrap_woKS_FFT (IEACHE_PBS_NO_KEYSWITCH) and tfhe_bootstrap_FFT with an arbitrary
+ * mu (the constant polynomial v = (mu, ..., mu)); like MAJ3 / XOR3 none of it is called by Cloud/cloud.c, which only reaches
+ * bootsAND / bootsXOR.
+ * Convention: row x[i] is bootstrapped as it stands (no gate combination).  With its mod-switched phase
+ * phi = barb - sum_j bara_j s_j (mod 2N) and v = test_polys[poly_of[i]] (row 0 when poly_of is NULL), out[i] encrypts
+ *     v[phi]        when phi < N,
+ *     -v[phi - N]   otherwise
+ * -- libtfhe's testvectbis = X^(2N-barb) * v, the n CMux steps, extraction of coefficient 0 -- and is key-switched back to
+ * the LWE key unless IEACHE_PBS_NO_KEYSWITCH is set.  ieache_lut_test_poly builds v from a table of values.
+ * test_polys: [n_polys][N] Torus32, rows packed on the host and on the device alike.  poly_of: [count] row indices or NULL.
+ * Host form: IEACHE_EINVAL for n_polys < 1, a NULL table, or an index outside [0, n_polys).  Device form: the indices are
+ * not read on the host; the kernel clamps each into [0, n_polys), so a bad one gives a wrong answer, never a stray read.
+ * IEACHE_PBS_NO_KEYSWITCH: the extracted samples (a'[0..N-1], b) under the ring key are the result and no key switch is
+ * launched (stats->keyswitch_launches == 0); host rows of N+1, device rows of ieache_extract_stride() int32 (N+1 rounded
+ * up to a multiple of 4), and d_out must not overlap d_x.  ieache_debug_keyswitch is its partner.  Otherwise rows as for
+ * ieache_gates*, and d_out may be d_x (the call then runs on the two-limb kernels from the start).
+ * One blind rotation and (unless skipped) one key switch per row; stats->bootstraps == count.  Noise budget of tables:
+ * DESIGN.md section 7 (at libtfhe's gate parameters four entries is the recommended ceiling). */
+#define IEACHE_PBS_NO_KEYSWITCH 1
+int ieache_pbs_device(ieache_ctx* ctx, size_t count, const int32_t* d_x, const int32_t* d_test_polys, int32_t n_polys,
+                      const int32_t* d_poly_of, int32_t* d_out, int flags, ieache_stats* stats);
+int ieache_pbs(ieache_ctx* ctx, size_t count, const int32_t* x, const int32_t* test_polys, int32_t n_polys, const int32_t* poly_of,
+               int32_t* out, int flags, ieache_stats* stats);
+/* int32 per device row of extracted samples (ieache_pbs_device with IEACHE_PBS_NO_KEYSWITCH) */
+int ieache_extract_stride(const ieache_ctx* ctx);
+/* Host only: the test polynomial of a lookup table f[0 .. entries-1] of Torus32 values for messages m encoded at phase
+ * m / (2 entries) (padding bit clear: phases below 1/2): v[j] = f[((j + N/(2 entries)) * entries) div N] for
+ * j < N - N/(2 entries), -f[0] on the last N/(2 entries) coefficients -- every slot centred on its message, and the negacyclic
+ * wrap returning f[0] just below phase 0.  Only p->N is read.  IEACHE_EINVAL unless 2 x entries divides N. */
+int ieache_lut_test_poly(const ieache_params* p, int32_t entries, const int32_t* f, int32_t* v /*[N]*/);
 /* out[i] = a[i] ? b[i] : c[i]; replaces bootsMUX (libtfhe boot-gates.cpp): per gate two blind
  * rotations without key switch, their extracted samples added to (0, 1/8), one key switch.
  * stats->bootstraps counts the blind rotations (2 per gate). */
