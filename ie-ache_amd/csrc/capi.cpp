@@ -693,6 +693,82 @@ int ieache_pbs(ieache_ctx* ctx, size_t count, const int32_t* x, const int32_t* t
     });
 }
 
+int ieache_pbs_multi_device(ieache_ctx* ctx, size_t count, const int32_t* d_x, const int32_t* d_test_polys, int32_t n_polys,
+                            const int32_t* d_poly_of, const int32_t* d_factors, int32_t n_factors, const int32_t* d_bias, int32_t* d_out,
+                            int flags, ieache_stats* stats) {
+    return guarded([&] {
+        if (flags & ~IEACHE_PBS_NO_KEYSWITCH) return fail(IEACHE_EINVAL, "pbs_multi: unknown flag");
+        if (n_polys < 1) return fail(IEACHE_EINVAL, "pbs_multi: n_polys must be at least 1");
+        if (!d_test_polys) return fail(IEACHE_EINVAL, "pbs_multi: null test polynomial table");
+        if (n_factors < 1 || n_factors > IEACHE_PBS_MULTI_MAX_FACTORS) return fail(IEACHE_EINVAL, "pbs_multi: n_factors must be 1 .. 64");
+        if (!d_factors) return fail(IEACHE_EINVAL, "pbs_multi: null factor table");
+        if (!ctx || !d_x || !d_out) return fail(IEACHE_EINVAL, "null argument");
+        if (count) {
+            require_device_pointer(d_x, "d_x");
+            require_device_pointer(d_test_polys, "d_test_polys");
+            if (d_poly_of) require_device_pointer(d_poly_of, "d_poly_of");
+            require_device_pointer(d_factors, "d_factors");
+            if (d_bias) require_device_pointer(d_bias, "d_bias");
+            require_device_pointer(d_out, "d_out");
+        }
+        EvalStats st;
+        ctx->eval->pbs_multi_device(count, d_x, d_test_polys, n_polys, d_poly_of, d_factors, n_factors, d_bias, d_out, flags, stats ? &st : nullptr);
+        to_stats(st, stats);
+        return 0;
+    });
+}
+
+int ieache_pbs_multi(ieache_ctx* ctx, size_t count, const int32_t* x, const int32_t* test_polys, int32_t n_polys, const int32_t* poly_of,
+                     const int32_t* factors, int32_t n_factors, const int32_t* bias, int32_t* out, int flags, ieache_stats* stats) {
+    return guarded([&] {
+        // what can be judged without the context comes first
+        if (flags & ~IEACHE_PBS_NO_KEYSWITCH) return fail(IEACHE_EINVAL, "pbs_multi: unknown flag");
+        if (n_polys < 1) return fail(IEACHE_EINVAL, "pbs_multi: n_polys must be at least 1");
+        if (!test_polys) return fail(IEACHE_EINVAL, "pbs_multi: null test polynomial table");
+        if (n_factors < 1 || n_factors > IEACHE_PBS_MULTI_MAX_FACTORS) return fail(IEACHE_EINVAL, "pbs_multi: n_factors must be 1 .. 64");
+        if (!factors) return fail(IEACHE_EINVAL, "pbs_multi: null factor table");
+        for (size_t i = 0; poly_of && i < count; i++)
+            if (poly_of[i] < 0 || poly_of[i] >= n_polys)
+                return fail(IEACHE_EINVAL, "pbs_multi: poly_of[" + std::to_string(i) + "] = " + std::to_string(poly_of[i]) + " is outside [0, n_polys)");
+        if (!ctx || !x || !out) return fail(IEACHE_EINVAL, "null argument");
+        const Params& p = ctx->eval->params();
+        const bool woks = (flags & IEACHE_PBS_NO_KEYSWITCH) != 0;
+        const size_t out_stride = woks ? (size_t)ctx->eval->extract_stride() : (size_t)p.lwe_stride();
+        const size_t out_width = woks ? (size_t)p.N + 1 : (size_t)p.n + 1;
+        HIP_CHECK(hipSetDevice(ctx->eval->device()));
+        StagedRows dx(*ctx->eval, 0, count, p.lwe_stride()), dout(*ctx->eval, 3, count * (size_t)n_factors, out_stride);
+        StagedRows dtv(*ctx->eval, 4, (size_t)n_polys, (size_t)p.N), dof(*ctx->eval, 5, poly_of ? count : 0, 1);
+        StagedRows dfa(*ctx->eval, 6, (size_t)n_factors, (size_t)p.N), dbi(*ctx->eval, 7, bias ? (size_t)n_factors : 0, 1);
+        dx.upload(x, p.n + 1);
+        dtv.upload(test_polys, (size_t)p.N);
+        if (poly_of) dof.upload(poly_of, 1);
+        dfa.upload(factors, (size_t)p.N);
+        if (bias) dbi.upload(bias, 1);
+        EvalStats st;
+        ctx->eval->pbs_multi_device(count, dx.p, dtv.p, n_polys, poly_of ? dof.p : nullptr, dfa.p, n_factors, bias ? dbi.p : nullptr, dout.p, flags,
+                                    stats ? &st : nullptr);
+        dout.download(out, out_width);
+        to_stats(st, stats);
+        return 0;
+    });
+}
+
+int ieache_lut_factor_poly(const ieache_params* p, int32_t entries, const int32_t* w, int32_t* P) {
+    if (!p || !w || !P) return fail(IEACHE_EINVAL, "null argument");
+    const int64_t N = p->N;
+    if (N < 2 || entries < 1 || N % (2 * (int64_t)entries) != 0) return fail(IEACHE_EINVAL, "lut_factor_poly: 2 x entries must divide N");
+    // v as ieache_lut_test_poly lays the table out, then P = v (1 - X): P[0] = v[0] + v[N-1], P[j] = v[j] - v[j-1]
+    const int64_t half_slot = N / (2 * (int64_t)entries);
+    auto v = [&](int64_t j) -> uint32_t {
+        const int64_t e = (j + half_slot) * entries / N;
+        return e < entries ? (uint32_t)w[e] : 0u - (uint32_t)w[0];
+    };
+    P[0] = (int32_t)(v(0) + v(N - 1));
+    for (int64_t j = 1; j < N; j++) P[j] = (int32_t)(v(j) - v(j - 1));
+    g_err.clear();
+    return 0;
+}
+
 int ieache_lut_test_poly(const ieache_params* p, int32_t entries, const int32_t* f, int32_t* v) {
     if (!p || !f || !v) return fail(IEACHE_EINVAL, "null argument");
     const int64_t N = p->N;

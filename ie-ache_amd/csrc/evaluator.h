@@ -77,6 +77,18 @@ public:
     // words per device row of extracted samples (N + 1 rounded up to a multiple of 4)
     int32_t extract_stride() const { return p_.N + 4; }
 
+    // Multi-output programmable bootstrap: ONE blind rotation per row x[i], exactly pbs_device's, whose whole accumulator
+    // (A, B) is kept; then for every factor polynomial P_t of d_factors [n_factors][N] (any int32 values) the extracted
+    // sample of coefficient 0 of (P_t A, P_t B), negacyclic and mod 2^32, plus d_bias[t] (null: 0) on its b term, key-switched
+    // unless kPbsNoKeyswitch -> row i x n_factors + t of d_out, shaped as pbs_device shapes its rows.  P = 1 is pbs_device
+    // bit for bit (include/ieache.h states the convention).  The stage between rotation and key switch is multi_extract.h;
+    // a piece of the call is max(1, chunk / n_factors) items, so that its key switch stays within `chunk` rows.  The
+    // sampled audit compares the PLAIN extraction of the audited accumulators, which covers the rotation bit for bit; the
+    // integer products have nothing to audit.  d_out must not overlap any input (it is n_factors times as long as x): such
+    // a call, n_factors outside 1 .. kMultiMaxFactors or a null factor table throw std::invalid_argument.
+    void pbs_multi_device(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of,
+                          const int32_t* d_factors, int32_t n_factors, const Torus32* d_bias, Torus32* d_out, int32_t flags, EvalStats* stats);
+
     // bootsMUX: out[i] = a[i] ? b[i] : c[i] (two blind rotations + one key switch per gate)
     void mux_device(size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,
                     EvalStats* stats);
@@ -92,7 +104,8 @@ public:
     // Device rows the host-buffer entry points stage operands (slot 0 .. 2) and results (slot 3) in: owned by the evaluator,
     // kept between calls and grown on demand, so that a warm call allocates nothing.  Operand slots are zero outside what
     // the caller uploads (rows of lwe_stride() words, n + 1 of them uploaded).  Slots 4 and 5 hold the test polynomials and
-    // the row indices of a programmable bootstrap (whole rows are uploaded; no other call reads them).  get_option("staging_allocations") counts
+    // the row indices of a programmable bootstrap, slots 6 and 7 the factors and the bias of a multi-output one (whole rows are uploaded; no other
+    // call reads them).  get_option("staging_allocations") counts
     // the (re)allocations made so far.
     Torus32* staging(int slot, size_t bytes);
 
@@ -160,6 +173,8 @@ private:
                            EvalStats* stats);  // d_c: third operand of GATE_MAJ3 / GATE_XOR3, null otherwise
     void pbs_device_once(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of, Torus32* d_out,
                          int32_t flags, EvalStats* stats);
+    void pbs_multi_device_once(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of,
+                               const int32_t* d_factors, int32_t n_factors, const Torus32* d_bias, Torus32* d_out, int32_t flags, EvalStats* stats);
     void mux_device_once(size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out, EvalStats* stats);
     void eval_circuit_device_once(const Circuit& c, size_t batch, const Torus32* d_in, Torus32* d_out, EvalStats* stats);
     void debug_blind_rotate_once(size_t count, const Torus32* d_x, Torus32* d_acc, int32_t steps);

@@ -24,6 +24,7 @@
 #include "device_common.h"
 #include "evaluator_options.h"
 #include "keyswitch.h"
+#include "multi_extract.h"
 #include "scoped_set.h"
 
 #include <algorithm>
@@ -133,6 +134,7 @@ struct Lane {
                                     // per context: two lanes run their combines and key switches side by side
     BrScratch br;                   // blind rotation: state between slices, the audit's sample
     KsScratch ks;                   // key switch
+    MvScratch mv;                   // multi-output programmable bootstrap: a piece's accumulators and its extracted rows
     Event ev_join;                  // the lane's share of a level / of an evaluation is queued
     Event ev_mix;
 };
@@ -155,13 +157,14 @@ struct Evaluator::Impl {
         int n[2] = {0, 0};            // trials so far (two each, alternating: a first call also pays for allocations)
     };
     std::map<std::tuple<size_t, int32_t, size_t, size_t, bool>, Tuned> tuned;  // (gates, levels, outputs, batch, exact_fft)
-    DeviceBuffer<Torus32> stage[6];  // rows the host-buffer entry points stage operands and results in (counted in bytes)
+    DeviceBuffer<Torus32> stage[8];  // rows the host-buffer entry points stage operands and results in (counted in bytes)
     DevKeys K{};
     BlindRotate br;  // K0-K4: kernels, key forms, guard record, audit and LDS grants; the choice among the kernels is br_plan.h
     double guard_max = 0;        // largest rounding deviation seen by the one-limb kernel (of 0.5)
     int64_t guard_reruns = 0;    // calls repeated on the two-limb kernel
     DeviceBuffer<int32_t> ksk;
     KeySwitch ks;  // K5: kernels, key form, LDS grants and the choice among them
+    MultiExtract mv;  // between K3 and K5 of a multi-output programmable bootstrap: the factors' lists and the extraction by factor
     DeviceBuffer<Torus32> ext_mux;  // bootsMUX: combined extracted samples, chunk/2 rows
     DeviceBuffer<Torus32> store;    // circuits: the wire store, the gate and the output table
     DeviceBuffer<DevGate> d_gates;
@@ -224,6 +227,7 @@ void Evaluator::init() {
     for (int32_t i = 1; i <= p.l; i++) K.dec_offset += (1u << (p.Bgbit - 1)) << (32 - i * p.Bgbit);
     d_->br.init(p, K);
     d_->ks.init(p, K);
+    d_->mv.init(p);
 }
 
 Evaluator::~Evaluator() { destroy(); }
@@ -250,13 +254,13 @@ void Evaluator::wait_for_stream(hipStream_t producer) {
 }
 
 // Staging rows for the host-buffer entry points (slot 0 .. 2: operands, 3: results, 4 / 5: test polynomials and row indices
-// of a programmable bootstrap).  A slot grows to at least `bytes`
+// of a programmable bootstrap, 6 / 7: factors and bias of a multi-output one).  A slot grows to at least `bytes`
 // (doubling, so a run of growing batches does not reallocate every call) and is zeroed when it is (re)allocated: callers
 // upload n + 1 words per row of lwe_stride() and rely on the padding words of OPERAND rows being zero, which holds because
 // nothing but such uploads ever writes slots 0 .. 2.  Every hipMalloc / hipFree is a device-wide synchronisation, which is
 // why a warm daemon request must not make one.
 Torus32* Evaluator::staging(int slot, size_t bytes) {
-    if (slot < 0 || slot >= 6) throw std::invalid_argument("staging slot");
+    if (slot < 0 || slot >= 8) throw std::invalid_argument("staging slot");
     HIP_CHECK(hipSetDevice(device_));
     bytes = (bytes + 255) & ~(size_t)255;
     DeviceBuffer<Torus32>& st = d_->stage[slot];
@@ -516,15 +520,41 @@ static void reserve_scratch(const Params& p, Evaluator::Impl* d, const int64_t* 
     }
 }
 
+// The stage a multi-output programmable bootstrap puts between a piece's blind rotation and its key switch (multi_extract.h).
+struct MultiStage {
+    int32_t n_factors;
+    const Torus32* bias;  // device, [n_factors], or null
+};
+
+// Scratch of a multi-output call before its loop starts: per lane the piece's extracted samples and blind-rotation state, its
+// accumulators, its n_factors rows per item (not when they go straight to the caller) and a key switch over those rows.
+static void reserve_multi(const Params& p, Evaluator::Impl* d, const LevelPlan& pl, int64_t items, const MultiStage& mv, bool rows_to_caller) {
+    const size_t piece = (size_t)std::min<int64_t>(pl.piece, std::max<int64_t>(items, 1));
+    const size_t rows = piece * (size_t)mv.n_factors, cap = (size_t)d->opt.chunk;
+    if (pl.two_lanes) ensure_lanes(d, 2);
+    for (int k = 0; k < (pl.two_lanes ? 2 : 1); k++) {
+        Lane& ln = d->lane[k];
+        reserve_lane(p, d, ln, piece);
+        d->mv.reserve(ln.mv, piece, rows_to_caller ? 0 : rows, cap, std::max(cap, (size_t)mv.n_factors));
+        if (!rows_to_caller) d->ks.reserve(ln.ks, (int64_t)rows, d->opt, d->force_generic_ks);
+    }
+}
+
 // One level: `items` independent gate instances described by W (item0 is advanced per piece).  Everything queued so far
 // on lane 0 (the previous level) is complete before any piece starts; lane 0 has every piece behind it when this returns.
 // fixed_lane >= 0: the whole level on that lane, in pieces of at most a chunk, no fork / join (a pipeline of its own, see
 // eval_circuit_device_once); its scratch has been reserved by the caller.
 // ext_out (flat mode): the extracted samples are the result -- every piece's blind rotation writes its rows of N + 4 words
 // there, at the piece's first item, and no key switch follows.
+// mv (flat mode, not with fixed_lane): a multi-output programmable bootstrap -- every piece's blind rotation leaves its whole
+// accumulators in the lane's scratch, k_mv_extract turns them into the lane's ordinary `ext` rows (what the audit compares)
+// and n_factors rows per item, and the key switch runs over those rows: output row = item x n_factors + factor.  With
+// ext_out the rows go straight there and no key switch follows.  Pieces are max(1, chunk / n_factors) items at most, so
+// the key switch and the rows stay within what `chunk` bounds (n_factors > chunk: one item, n_factors rows).
 static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t items, Timer& tbr, Timer& tks, EvalStats* stats,
-                      int fixed_lane = -1, Torus32* ext_out = nullptr) {
+                      int fixed_lane = -1, Torus32* ext_out = nullptr, const MultiStage* mv = nullptr) {
     LevelPlan pl = plan_level(d, items);
+    if (mv) pl.piece = std::min<int64_t>(pl.piece, std::max<int64_t>(1, (int64_t)d->opt.chunk / mv->n_factors));
     // A level with MUX gates (circuit mode, W.nm > 0): `items` are rotation items, two per MUX.  PIECES ARE CUT AT GATE
     // BOUNDARIES (level_piece_items), so both rotations of a MUX are in the same piece, on the same lane, in the same `ext`,
     // before its combine runs.  That one rule covers every way a level is cut:
@@ -541,6 +571,8 @@ static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t i
         pl.piece = (int64_t)d->opt.chunk;
         const size_t need = (size_t)std::min<int64_t>(pl.piece + (mux ? 1 : 0), std::max<int64_t>(items, 1));
         reserve_lane(p, d, d->lane[fixed_lane], need, mux ? std::min<size_t>(need, (size_t)gates) : 0);
+    } else if (mv) {
+        reserve_multi(p, d, pl, items, *mv, ext_out != nullptr);
     } else {
         reserve_scratch(p, d, &items, 1, mux ? &gates : nullptr);
     }
@@ -555,11 +587,16 @@ static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t i
         w.item0 = W.item0 + done;
         if ((size_t)cnt > ln.ext.items()) throw std::logic_error("piece larger than the lane's extracted-sample rows");
         const BrPlan plan = plan_blind_rotate(p, d, ln, cnt);  // once: the launch and the audit see the same choice
-        Torus32* ext = ext_out ? ext_out + (size_t)done * (size_t)(d->K.N + 4) : (Torus32*)ln.ext;
+        Torus32* ext = ext_out && !mv ? ext_out + (size_t)done * (size_t)(d->K.N + 4) : (Torus32*)ln.ext;
+        const int64_t nf = mv ? mv->n_factors : 1;
+        Torus32* mv_rows = !mv ? nullptr : ext_out ? ext_out + (size_t)(done * nf) * (size_t)(d->K.N + 4) : (Torus32*)ln.mv.rows;
+        if (mv && ((size_t)cnt > ln.mv.acc.items() || (!ext_out && (size_t)(cnt * nf) > ln.mv.rows.items())))
+            throw std::logic_error("piece larger than the lane's multi-output scratch");
         tbr.mark(ln.stream);
-        const int nbr = launch_blind_rotate(d, ln, plan, w, cnt, ext, -1, nullptr);
+        const int nbr = launch_blind_rotate(d, ln, plan, w, cnt, mv ? nullptr : ext, -1, mv ? (Torus32*)ln.mv.acc : nullptr);
         tbr.mark(ln.stream);
         HIP_CHECK(hipGetLastError());
+        if (mv) d->mv.extract(ln.stream, ln.mv.acc, cnt, mv->n_factors, mv->bias, ext, mv_rows);
         d->br.audit(ln.br, plan, d->opt, ln.stream, w, cnt, ext);
         if (ext_out) {
             if (stats) {
@@ -583,6 +620,14 @@ static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t i
             wk.nm = 0;
             wk.item0 = gate0;
             launch_keyswitch(d, ln, wk, gcnt, ln.comb, nullptr);
+        } else if (mv) {
+            // a flat descriptor over ROWS: row item0 x n_factors + i of flat_out (only GateInst::out is used by the key switch)
+            WorkDesc wk{};
+            wk.flat_a = w.flat_a;
+            wk.flat_out = w.flat_out;
+            wk.flat_type = -1;
+            wk.item0 = w.item0 * nf;
+            launch_keyswitch(d, ln, wk, cnt * nf, mv_rows, nullptr);
         } else {
             launch_keyswitch(d, ln, w, cnt, ln.ext, nullptr);
         }
@@ -755,6 +800,51 @@ void Evaluator::pbs_device_once(size_t count, const Torus32* d_x, const Torus32*
     W.item0 = 0;
     tall.mark();
     run_items(p_, d_, W, (int64_t)count, tbr, tks, stats, -1, woks ? d_out : nullptr);
+    tall.mark();
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    add_times(stats, tall, tbr, tks);
+    if (stats) stats->levels += 1;
+}
+
+void Evaluator::pbs_multi_device(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of,
+                                 const int32_t* d_factors, int32_t n_factors, const Torus32* d_bias, Torus32* d_out, int32_t flags,
+                                 EvalStats* stats) {
+    if (flags & ~kPbsNoKeyswitch) throw std::invalid_argument("multi-output programmable bootstrap: unknown flag");
+    if (n_tv < 1 || !d_tv) throw std::invalid_argument("multi-output programmable bootstrap: no test polynomial");
+    if (n_factors < 1 || n_factors > kMultiMaxFactors || !d_factors)
+        throw std::invalid_argument("multi-output programmable bootstrap: n_factors must be 1 .. 64 and the factor table non-null");
+    const bool woks = (flags & kPbsNoKeyswitch) != 0;
+    const size_t out_len = count * (size_t)n_factors * (size_t)(woks ? extract_stride() : d_->K.stride);
+    // no in-place form: the output is n_factors times the input, and a repeat reads every input again
+    if (overlaps(d_out, out_len, d_x, count * (size_t)d_->K.stride) || overlaps(d_out, out_len, d_tv, (size_t)n_tv * (size_t)p_.N) ||
+        overlaps(d_out, out_len, reinterpret_cast<const Torus32*>(d_tv_of), count) ||
+        overlaps(d_out, out_len, d_factors, (size_t)n_factors * (size_t)p_.N) || overlaps(d_out, out_len, d_bias, (size_t)n_factors))
+        throw std::invalid_argument("multi-output programmable bootstrap: the output overlaps an input (rows, test polynomials, indices, factors or bias)");
+    run_guarded(*this, &d_->exact_once, &d_->guard_reruns, true, stats,
+                [&] { pbs_multi_device_once(count, d_x, d_tv, n_tv, d_tv_of, d_factors, n_factors, d_bias, d_out, flags, stats); });
+}
+
+// pbs_device_once with the stage of multi_extract.h between every piece's rotation and its key switch
+void Evaluator::pbs_multi_device_once(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of,
+                                      const int32_t* d_factors, int32_t n_factors, const Torus32* d_bias, Torus32* d_out, int32_t flags,
+                                      EvalStats* stats) {
+    begin_call();
+    if (count == 0) return;
+    const bool woks = (flags & kPbsNoKeyswitch) != 0;
+    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(stats != nullptr, stream_);
+    WorkDesc W{};
+    W.gates = nullptr;
+    W.flat_a = d_x;
+    W.flat_out = woks ? nullptr : d_out;
+    W.flat_type = -1;
+    W.tv = d_tv;
+    W.n_tv = n_tv;
+    W.tv_of = d_tv_of;
+    W.item0 = 0;
+    const MultiStage mv{n_factors, d_bias};
+    tall.mark();
+    d_->mv.compact(stream_, d_factors, n_factors);  // on lane 0, ahead of the fork: every lane's extraction finds the lists
+    run_items(p_, d_, W, (int64_t)count, tbr, tks, stats, -1, woks ? d_out : nullptr, &mv);
     tall.mark();
     HIP_CHECK(hipStreamSynchronize(stream_));
     add_times(stats, tall, tbr, tks);

@@ -19,6 +19,7 @@ CIRC_MUL_WALLACE = 9  # carry-save multiplier (decrypt-identical, not bit-identi
 GATE_AND, GATE_XOR, GATE_OR, GATE_NAND, GATE_MUX = 0, 1, 2, 3, 4
 GATE_NOR, GATE_XNOR, GATE_ANDNY, GATE_ANDYN, GATE_ORNY, GATE_ORYN = 5, 6, 7, 8, 9, 10  # libtfhe boot-gates.cpp
 GATE_TYPES = 11
+PBS_MULTI_MAX_FACTORS = 64  # most factor polynomials of one ieache_pbs_multi* call
 PBS_NO_KEYSWITCH = 1  # flag of ieache_pbs*: the extracted samples are the result (tfhe_bootstrap_woKS_FFT)
 GATE_MAJ3, GATE_XOR3 = 32, 33  # three-input gates of one bootstrap each (codes outside 0 .. GATE_TYPES-1: include/ieache.h)
 CIRC_ADD_FA, CIRC_SUB_FA, CIRC_RSUB_FA, CIRC_MUL_FA = 16, 17, 18, 19  # on the MAJ3 / XOR3 full adder (decrypt-identical)
@@ -161,6 +162,9 @@ def lib():
     L.ieache_gates3.argtypes = [vp, C.c_int, C.c_size_t, i32p, i32p, i32p, i32p, sp]
     L.ieache_pbs_device.argtypes = [vp, C.c_size_t, vp, vp, C.c_int32, vp, vp, C.c_int, sp]
     L.ieache_pbs.argtypes = [vp, C.c_size_t, i32p, i32p, C.c_int32, i32p, i32p, C.c_int, sp]
+    L.ieache_pbs_multi_device.argtypes = [vp, C.c_size_t, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int, sp]
+    L.ieache_pbs_multi.argtypes = [vp, C.c_size_t, i32p, i32p, C.c_int32, i32p, i32p, C.c_int32, i32p, i32p, C.c_int, sp]
+    L.ieache_lut_factor_poly.argtypes = [pp, C.c_int32, i32p, i32p]
     L.ieache_extract_stride.argtypes = [vp]
     L.ieache_lut_test_poly.argtypes = [pp, C.c_int32, i32p, i32p]
     L.ieache_circuit_gate_count.restype = C.c_int64
@@ -551,6 +555,33 @@ class Context:
         check(lib().ieache_pbs_device(self.h, count, C.c_void_p(d_x), C.c_void_p(d_test_polys), int(n_polys),
                                       C.c_void_p(d_poly_of or None), C.c_void_p(d_out), 0 if keyswitch else PBS_NO_KEYSWITCH,
                                       C.byref(stats) if stats is not None else None))
+
+    def pbs_multi(self, x, test_polys, factors, poly_of=None, bias=None, keyswitch=True, stats=None):
+        """Multi-output programmable bootstrap on host rows: ONE blind rotation per row of x [count][n+1], as pbs does it, and
+        one output per factor polynomial of factors [n_factors][N] (or one [N]): coefficient 0 of factor x accumulator,
+        negacyclic and mod 2^32, plus bias[t] (None: 0) on its b term (include/ieache.h; tools.lut_factor_poly builds a factor
+        from a table of small integers) -> [count][n_factors][n+1], or with keyswitch=False the extracted samples
+        [count][n_factors][N+1] under the ring key.  The factor 1 gives pbs's own output."""
+        x = np.ascontiguousarray(x, dtype=np.int32).reshape(-1, self.params.n + 1)
+        tv = np.ascontiguousarray(test_polys, dtype=np.int32).reshape(-1, self.params.N)
+        fa = np.ascontiguousarray(factors, dtype=np.int32).reshape(-1, self.params.N)
+        of = None if poly_of is None else np.ascontiguousarray(poly_of, dtype=np.int32).reshape(-1)
+        bi = None if bias is None else np.ascontiguousarray(bias, dtype=np.int32).reshape(-1)
+        assert of is None or of.shape[0] == x.shape[0]
+        assert bi is None or bi.shape[0] == fa.shape[0]
+        out = np.zeros((x.shape[0], fa.shape[0], (self.params.n if keyswitch else self.params.N) + 1), dtype=np.int32)
+        check(lib().ieache_pbs_multi(self.h, x.shape[0], _i32(x), _i32(tv), tv.shape[0], None if of is None else _i32(of), _i32(fa),
+                                     fa.shape[0], None if bi is None else _i32(bi), _i32(out), 0 if keyswitch else PBS_NO_KEYSWITCH,
+                                     C.byref(stats) if stats is not None else None))
+        return out
+
+    def pbs_multi_device(self, count, d_x, d_test_polys, n_polys, d_poly_of, d_factors, n_factors, d_bias, d_out, keyswitch=True, stats=None):
+        """Device pointers (ints; d_poly_of and d_bias may be None / 0): x rows of lwe_stride, test polynomials [n_polys][N] and
+        factors [n_factors][N] packed, out [count * n_factors] rows of lwe_stride or, with keyswitch=False, of extract_stride."""
+        check(lib().ieache_pbs_multi_device(self.h, count, C.c_void_p(d_x), C.c_void_p(d_test_polys), int(n_polys),
+                                            C.c_void_p(d_poly_of or None), C.c_void_p(d_factors), int(n_factors), C.c_void_p(d_bias or None),
+                                            C.c_void_p(d_out), 0 if keyswitch else PBS_NO_KEYSWITCH,
+                                            C.byref(stats) if stats is not None else None))
 
     def mux(self, a, b, c, stats=None):
         """bootsMUX on host rows: out[i] = a[i] ? b[i] : c[i]."""

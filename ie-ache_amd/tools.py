@@ -69,6 +69,16 @@ def lut_test_poly(params, table):
     return v
 
 
+def lut_factor_poly(params, table):
+    """Factor polynomial [N] of a lookup table of small INTEGERS for Context.pbs_multi: P = v (1 - X) with v laid out as
+    lut_test_poly lays a table out (ieache_lut_factor_poly; 2 len(table) must divide N).  After a rotation from the constant
+    polynomial c, a message m < len(table) comes out as 2 c table[m] (+ bias)."""
+    w = np.ascontiguousarray(table, dtype=np.int32).reshape(-1)
+    P = np.zeros(params.N, dtype=np.int32)
+    check(lib().ieache_lut_factor_poly(C.byref(params), w.shape[0], _i32(w), _i32(P)))
+    return P
+
+
 def int_to_bits(value, nbits):
     return np.array([(int(value) >> i) & 1 for i in range(nbits)], dtype=np.uint8)
 

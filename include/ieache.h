@@ -12,7 +12,7 @@
  * Streams: a context launches on its own non-blocking HIP stream
  * (ieache_ctx_stream).  Every entry point that takes DEVICE pointers
  * (ieache_ctx_create_device, ieache_eval_batch_device, ieache_gates_device,
- * ieache_gates3_device, ieache_pbs_device, ieache_mux_device) reads them on that stream without ordering against the
+ * ieache_gates3_device, ieache_pbs_device, ieache_pbs_multi_device, ieache_mux_device) reads them on that stream without ordering against the
  * stream that produced them: the caller must either have synchronised the
  * producing stream (torch.cuda.synchronize(), hipStreamSynchronize) or call
  * ieache_ctx_wait_stream(ctx, producer) first.  Outputs are complete when the
@@ -310,6 +310,43 @@ int ieache_extract_stride(const ieache_ctx* ctx);
  * j < N - N/(2 entries), -f[0] on the last N/(2 entries) coefficients -- every slot centred on its message, and the negacyclic
  * wrap returning f[0] just below phase 0.  Only p->N is read.  IEACHE_EINVAL unless 2 x entries divides N. */
 int ieache_lut_test_poly(const ieache_params* p, int32_t entries, const int32_t* f, int32_t* v /*[N]*/);
+/* Multi-output programmable bootstrap: ONE blind rotation per row, several outputs (the multi-value bootstrap of Carpov,
+ * Izabachene and Mollimard, CT-RSA 2019).  Each further output costs one exact integer polynomial product and one key
+ * switch, not a rotation.  Ring: Torus32[X]/(X^N+1); everything below is mod 2^32 with wraparound.
+ * Convention:
+ *   1. Row x[i] is blind-rotated exactly as ieache_pbs does it -- test polynomial test_polys[poly_of[i]], the row as it
+ *      stands, no gate combination -- and the WHOLE accumulator ACC_i = (A, B), two polynomials of N words, is kept.
+ *   2. For every factor polynomial P_t = factors[t] (N int32, any values), t = 0 .. n_factors-1:
+ *        A' = P_t A and B' = P_t B, negacyclic;
+ *        coefficient 0 of (A', B') is extracted the way every bootstrap here extracts:
+ *            u[0] = A'[0],  u[j] = -A'[N-j] (0 < j < N),  u[N] = B'[0] + bias[t]      (bias NULL: 0);
+ *        u is key-switched back to the LWE key unless IEACHE_PBS_NO_KEYSWITCH is set.
+ *   3. Output row i * n_factors + t (item-major), shaped as ieache_pbs shapes its rows: host rows of n+1 (N+1 without the
+ *      key switch), device rows of lwe_stride (ieache_extract_stride(); all its words are written, the padding as zero).
+ * P = 1 is ieache_pbs itself, bit for bit.  P = -X^(N-j) (that is X^(-j)) extracts coefficient j of the accumulator: the
+ * multi-coefficient extraction of "PBS-many-LUT".
+ * Tables -> factors: ieache_lut_factor_poly.  With v = ieache_lut_test_poly(entries, w) for a table w of small INTEGERS (not
+ * torus values), P = v (1 - X): P[0] = v[0] + v[N-1], P[j] = v[j] - v[j-1]; it has at most entries + 1 nonzero
+ * coefficients.  Because (1 + X + ... + X^(N-1)) (1 - X) = 2, rotating the CONSTANT polynomial c and multiplying by P gives
+ * the message a rotation from 2c v gives: a message m comes out as 2c w[m] + bias.  With c = 1/8, w in {0, 1} and
+ * bias = -1/8 the outputs are ordinary gate bits at +-1/8.
+ * Noise: the rotation's share of the output variance is multiplied by |P|_2^2 (sum of squared coefficients); the key switch
+ * adds its share once per output.  DESIGN.md section 7 has the budget.
+ * Flags and argument rules are ieache_pbs's.  In addition IEACHE_EINVAL when n_factors is outside
+ * 1 .. IEACHE_PBS_MULTI_MAX_FACTORS or the factor table is NULL, and when the output overlaps ANY input -- rows, test
+ * polynomials, indices, factors or bias: there is no in-place form, the output is n_factors times the input.  The device
+ * form reads neither the indices nor the factors on the host.
+ * stats->bootstraps == count (rotations, not outputs); stats->keyswitch_launches == 0 with IEACHE_PBS_NO_KEYSWITCH. */
+#define IEACHE_PBS_MULTI_MAX_FACTORS 64
+int ieache_pbs_multi_device(ieache_ctx* ctx, size_t count, const int32_t* d_x, const int32_t* d_test_polys, int32_t n_polys,
+                            const int32_t* d_poly_of, const int32_t* d_factors /*[n_factors][N]*/, int32_t n_factors,
+                            const int32_t* d_bias /*[n_factors] or NULL*/, int32_t* d_out /*[count * n_factors] rows*/, int flags,
+                            ieache_stats* stats);
+int ieache_pbs_multi(ieache_ctx* ctx, size_t count, const int32_t* x, const int32_t* test_polys, int32_t n_polys, const int32_t* poly_of,
+                     const int32_t* factors, int32_t n_factors, const int32_t* bias, int32_t* out, int flags, ieache_stats* stats);
+/* Host only: the factor polynomial P = v (1 - X) of a table w[0 .. entries-1] of small integers, v laid out as
+ * ieache_lut_test_poly lays it out.  Only p->N is read.  IEACHE_EINVAL unless 2 x entries divides N. */
+int ieache_lut_factor_poly(const ieache_params* p, int32_t entries, const int32_t* w, int32_t* P /*[N]*/);
 /* out[i] = a[i] ? b[i] : c[i]; replaces bootsMUX (libtfhe boot-gates.cpp): per gate two blind
  * rotations without key switch, their extracted samples added to (0, 1/8), one key switch.
  * stats->bootstraps counts the blind rotations (2 per gate). */
