@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -104,6 +105,48 @@ void require_device_pointer(const void* ptr, const char* name) {
     if (e != hipSuccess) (void)hipGetLastError();
     if (e != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged && attr.type != hipMemoryTypeUnified))
         throw std::invalid_argument(std::string(name) + " is not a device pointer");
+}
+// ... for every pointer argument of an entry point; an empty call launches nothing and names no memory
+struct DevArg {
+    const void* ptr;
+    const char* name;
+    bool optional = false;  // null is allowed
+};
+void require_device_pointers(size_t count, std::initializer_list<DevArg> args) {
+    if (!count) return;
+    for (const DevArg& a : args)
+        if (a.ptr || !a.optional) require_device_pointer(a.ptr, a.name);
+}
+// Runs `body` with the evaluator's statistics record -- null when the caller wants none -- and hands the caller its copy.
+template <class F>
+int with_stats(ieache_stats* stats, F&& body) {
+    EvalStats st;
+    body(stats ? &st : nullptr);
+    to_stats(st, stats);
+    return 0;
+}
+// What can be judged of a programmable bootstrap's arguments without the context, in the order the entry points report it:
+// the message of the first failing check, or null.  The host and the device form share them.
+const char* pbs_args_error(int flags, int32_t n_polys, const int32_t* test_polys) {
+    if (flags & ~IEACHE_PBS_NO_KEYSWITCH) return "pbs: unknown flag";
+    if (n_polys < 1) return "pbs: n_polys must be at least 1";
+    if (!test_polys) return "pbs: null test polynomial table";
+    return nullptr;
+}
+const char* pbs_multi_args_error(int flags, int32_t n_polys, const int32_t* test_polys, int32_t n_factors, const int32_t* factors) {
+    if (flags & ~IEACHE_PBS_NO_KEYSWITCH) return "pbs_multi: unknown flag";
+    if (n_polys < 1) return "pbs_multi: n_polys must be at least 1";
+    if (!test_polys) return "pbs_multi: null test polynomial table";
+    if (n_factors < 1 || n_factors > IEACHE_PBS_MULTI_MAX_FACTORS) return "pbs_multi: n_factors must be 1 .. 64";
+    if (!factors) return "pbs_multi: null factor table";
+    return nullptr;
+}
+// Host forms only: the device form cannot read the indices, and the kernel clamps.  -> the message, or empty
+std::string poly_of_error(const char* call, const int32_t* poly_of, size_t count, int32_t n_polys) {
+    for (size_t i = 0; poly_of && i < count; i++)
+        if (poly_of[i] < 0 || poly_of[i] >= n_polys)
+            return std::string(call) + ": poly_of[" + std::to_string(i) + "] = " + std::to_string(poly_of[i]) + " is outside [0, n_polys)";
+    return std::string();
 }
 
 const Circuit* get_circuit(ieache_ctx* ctx, int kind, int bits, size_t batch = 0) {
@@ -412,10 +455,7 @@ int ieache_eval_batch(ieache_ctx* ctx, int kind, int bits, size_t batch, const i
         if (!ctx || !in_lwe || !out_lwe) return fail(IEACHE_EINVAL, "null argument");
         const Circuit* c = get_circuit(ctx, kind, bits, batch);
         if (!c) return fail(IEACHE_EINVAL, "unsupported circuit kind/bits");
-        EvalStats st;
-        eval_circuit_host(*ctx->eval, *c, batch, in_lwe, out_lwe, stats ? &st : nullptr);
-        to_stats(st, stats);
-        return 0;
+        return with_stats(stats, [&](EvalStats* st) { eval_circuit_host(*ctx->eval, *c, batch, in_lwe, out_lwe, st); });
     });
 }
 
@@ -425,14 +465,8 @@ int ieache_eval_batch_device(ieache_ctx* ctx, int kind, int bits, size_t batch, 
         if (!ctx || !d_in || !d_out) return fail(IEACHE_EINVAL, "null argument");
         const Circuit* c = get_circuit(ctx, kind, bits, batch);
         if (!c) return fail(IEACHE_EINVAL, "unsupported circuit kind/bits");
-        if (batch) {
-            require_device_pointer(d_in, "d_in");
-            require_device_pointer(d_out, "d_out");
-        }
-        EvalStats st;
-        ctx->eval->eval_circuit_device(*c, batch, d_in, d_out, stats ? &st : nullptr);
-        to_stats(st, stats);
-        return 0;
+        require_device_pointers(batch, {{d_in, "d_in"}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->eval_circuit_device(*c, batch, d_in, d_out, st); });
     });
 }
 
@@ -515,10 +549,7 @@ int ieache_eval_netlist(ieache_ctx* ctx, const ieache_netlist* nl, size_t batch,
                         ieache_stats* stats) {
     return guarded([&] {
         if (!ctx || !nl || !in_lwe || !out_lwe) return fail(IEACHE_EINVAL, "null argument");
-        EvalStats st;
-        eval_circuit_host(*ctx->eval, nl->circuit, batch, in_lwe, out_lwe, stats ? &st : nullptr);
-        to_stats(st, stats);
-        return 0;
+        return with_stats(stats, [&](EvalStats* st) { eval_circuit_host(*ctx->eval, nl->circuit, batch, in_lwe, out_lwe, st); });
     });
 }
 
@@ -526,31 +557,8 @@ int ieache_eval_netlist_device(ieache_ctx* ctx, const ieache_netlist* nl, size_t
                                ieache_stats* stats) {
     return guarded([&] {
         if (!ctx || !nl || !d_in || !d_out) return fail(IEACHE_EINVAL, "null argument");
-        if (batch) {
-            require_device_pointer(d_in, "d_in");
-            require_device_pointer(d_out, "d_out");
-        }
-        EvalStats st;
-        ctx->eval->eval_circuit_device(nl->circuit, batch, d_in, d_out, stats ? &st : nullptr);
-        to_stats(st, stats);
-        return 0;
-    });
-}
-
-int ieache_gates_device(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* d_a, const int32_t* d_b,
-                        int32_t* d_out, ieache_stats* stats) {
-    return guarded([&] {
-        if (!ctx || !d_a || !d_b || !d_out) return fail(IEACHE_EINVAL, "null argument");
-        if (gate_type < 0 || gate_type >= GATE_TYPES || gate_type == GATE_MUX) return fail(IEACHE_EINVAL, "unknown gate type");
-        if (count) {
-            require_device_pointer(d_a, "d_a");
-            require_device_pointer(d_b, "d_b");
-            require_device_pointer(d_out, "d_out");
-        }
-        EvalStats st;
-        ctx->eval->gates_device(gate_type, count, d_a, d_b, d_out, stats ? &st : nullptr);
-        to_stats(st, stats);
-        return 0;
+        require_device_pointers(batch, {{d_in, "d_in"}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->eval_circuit_device(nl->circuit, batch, d_in, d_out, st); });
     });
 }
 
@@ -571,35 +579,63 @@ struct DevRows {
         HIP_CHECK(hipMemcpy2D(h, width * 4, p, stride * 4, width * 4, rows, hipMemcpyDeviceToHost));
     }
 };
-// the same on the evaluator's kept staging rows (Evaluator::staging): what the gate / MUX host entry points use, so that
-// a warm call allocates nothing
+// the same on the evaluator's kept staging rows (Evaluator::staging): what the host forms of the flat calls use, so that a
+// warm call allocates nothing
 struct StagedRows {
     Torus32* p;
     size_t rows, stride;
-    StagedRows(Evaluator& ev, int slot, size_t r, size_t s) : p(ev.staging(slot, r * s * 4)), rows(r), stride(s) {}
-    void upload(const int32_t* h, size_t width) {
+    // rows for results
+    StagedRows(Evaluator& ev, StageSlot slot, size_t r, size_t s) : p(ev.staging(slot, r * s * 4)), rows(r), stride(s) {}
+    // an input: `width` words of every host row uploaded.  A null `h` (an optional argument) stages no rows; p is then null.
+    StagedRows(Evaluator& ev, StageSlot slot, size_t r, size_t s, const int32_t* h, size_t width) : StagedRows(ev, slot, h ? r : 0, s) {
+        if (!h) p = nullptr;
         if (rows) HIP_CHECK(hipMemcpy2D(p, stride * 4, h, width * 4, width * 4, rows, hipMemcpyHostToDevice));
     }
     void download(int32_t* h, size_t width) {
         if (rows) HIP_CHECK(hipMemcpy2D(h, width * 4, p, stride * 4, width * 4, rows, hipMemcpyDeviceToHost));
     }
 };
+// What the host form of a flat call stages with: the context's device current, and operand / result rows of lwe_stride() words.
+struct HostCall {
+    Evaluator& ev;
+    const Params& p;
+    size_t count;
+    HostCall(ieache_ctx* ctx, size_t n) : ev(*ctx->eval), p(ev.params()), count(n) { HIP_CHECK(hipSetDevice(ev.device())); }
+    StagedRows operand(StageSlot slot, const int32_t* h) { return StagedRows(ev, slot, count, (size_t)p.lwe_stride(), h, (size_t)p.n + 1); }
+    // test polynomials / factors: `rows` whole polynomials; indices / bias: `rows` single words, optional
+    StagedRows polys(StageSlot slot, const int32_t* h, size_t rows) { return StagedRows(ev, slot, rows, (size_t)p.N, h, (size_t)p.N); }
+    StagedRows words(StageSlot slot, const int32_t* h, size_t rows) { return StagedRows(ev, slot, rows, 1, h, 1); }
+    StagedRows results(size_t rows, bool extracted = false) {
+        return StagedRows(ev, kStageOut, rows, extracted ? (size_t)ev.extract_stride() : (size_t)p.lwe_stride());
+    }
+    // key-switched rows carry n + 1 words, extracted samples N + 1
+    void download(StagedRows& out, int32_t* h, bool extracted = false) { out.download(h, extracted ? (size_t)p.N + 1 : (size_t)p.n + 1); }
+};
+bool bad_gate2(int gate_type) { return gate_type < 0 || gate_type >= GATE_TYPES || gate_type == GATE_MUX; }
+const char* const kNotGate3 = "not a three-input gate type (IEACHE_GATE_MAJ3 / IEACHE_GATE_XOR3)";
 }  // namespace
+
+// ---- flat calls.  Device form: validate, check the pointers, run.  Host form: validate, stage the inputs, run the same
+// evaluator call on the staged rows, download. ----
+int ieache_gates_device(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* d_a, const int32_t* d_b,
+                        int32_t* d_out, ieache_stats* stats) {
+    return guarded([&] {
+        if (!ctx || !d_a || !d_b || !d_out) return fail(IEACHE_EINVAL, "null argument");
+        if (bad_gate2(gate_type)) return fail(IEACHE_EINVAL, "unknown gate type");
+        require_device_pointers(count, {{d_a, "d_a"}, {d_b, "d_b"}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->gates_device(gate_type, count, d_a, d_b, d_out, st); });
+    });
+}
 
 int ieache_gates(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* a, const int32_t* b, int32_t* out,
                  ieache_stats* stats) {
     return guarded([&] {
         if (!ctx || !a || !b || !out) return fail(IEACHE_EINVAL, "null argument");
-        if (gate_type < 0 || gate_type >= GATE_TYPES || gate_type == GATE_MUX) return fail(IEACHE_EINVAL, "unknown gate type");
-        const Params& p = ctx->eval->params();
-        HIP_CHECK(hipSetDevice(ctx->eval->device()));
-        StagedRows da(*ctx->eval, 0, count, p.lwe_stride()), db(*ctx->eval, 1, count, p.lwe_stride()), dout(*ctx->eval, 3, count, p.lwe_stride());
-        da.upload(a, p.n + 1);
-        db.upload(b, p.n + 1);
-        EvalStats st;
-        ctx->eval->gates_device(gate_type, count, da.p, db.p, dout.p, stats ? &st : nullptr);
-        dout.download(out, p.n + 1);
-        to_stats(st, stats);
+        if (bad_gate2(gate_type)) return fail(IEACHE_EINVAL, "unknown gate type");
+        HostCall h(ctx, count);
+        StagedRows da = h.operand(kStageA, a), db = h.operand(kStageB, b), dout = h.results(count);
+        with_stats(stats, [&](EvalStats* st) { h.ev.gates_device(gate_type, count, da.p, db.p, dout.p, st); });
+        h.download(dout, out);
         return 0;
     });
 }
@@ -607,37 +643,43 @@ int ieache_gates(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* a,
 int ieache_gates3_device(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* d_a, const int32_t* d_b, const int32_t* d_c,
                          int32_t* d_out, ieache_stats* stats) {
     return guarded([&] {
-        if (!is_gate3(gate_type)) return fail(IEACHE_EINVAL, "not a three-input gate type (IEACHE_GATE_MAJ3 / IEACHE_GATE_XOR3)");
+        if (!is_gate3(gate_type)) return fail(IEACHE_EINVAL, kNotGate3);
         if (!ctx || !d_a || !d_b || !d_c || !d_out) return fail(IEACHE_EINVAL, "null argument");
-        if (count) {
-            require_device_pointer(d_a, "d_a");
-            require_device_pointer(d_b, "d_b");
-            require_device_pointer(d_c, "d_c");
-            require_device_pointer(d_out, "d_out");
-        }
-        EvalStats st;
-        ctx->eval->gates3_device(gate_type, count, d_a, d_b, d_c, d_out, stats ? &st : nullptr);
-        to_stats(st, stats);
-        return 0;
+        require_device_pointers(count, {{d_a, "d_a"}, {d_b, "d_b"}, {d_c, "d_c"}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->gates3_device(gate_type, count, d_a, d_b, d_c, d_out, st); });
     });
 }
 
 int ieache_gates3(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* a, const int32_t* b, const int32_t* c, int32_t* out,
                   ieache_stats* stats) {
     return guarded([&] {
-        if (!is_gate3(gate_type)) return fail(IEACHE_EINVAL, "not a three-input gate type (IEACHE_GATE_MAJ3 / IEACHE_GATE_XOR3)");
+        if (!is_gate3(gate_type)) return fail(IEACHE_EINVAL, kNotGate3);
         if (!ctx || !a || !b || !c || !out) return fail(IEACHE_EINVAL, "null argument");
-        const Params& p = ctx->eval->params();
-        HIP_CHECK(hipSetDevice(ctx->eval->device()));
-        StagedRows da(*ctx->eval, 0, count, p.lwe_stride()), db(*ctx->eval, 1, count, p.lwe_stride()), dc(*ctx->eval, 2, count, p.lwe_stride()),
-            dout(*ctx->eval, 3, count, p.lwe_stride());
-        da.upload(a, p.n + 1);
-        db.upload(b, p.n + 1);
-        dc.upload(c, p.n + 1);
-        EvalStats st;
-        ctx->eval->gates3_device(gate_type, count, da.p, db.p, dc.p, dout.p, stats ? &st : nullptr);
-        dout.download(out, p.n + 1);
-        to_stats(st, stats);
+        HostCall h(ctx, count);
+        StagedRows da = h.operand(kStageA, a), db = h.operand(kStageB, b), dc = h.operand(kStageC, c), dout = h.results(count);
+        with_stats(stats, [&](EvalStats* st) { h.ev.gates3_device(gate_type, count, da.p, db.p, dc.p, dout.p, st); });
+        h.download(dout, out);
+        return 0;
+    });
+}
+
+int ieache_mux_device(ieache_ctx* ctx, size_t count, const int32_t* d_a, const int32_t* d_b, const int32_t* d_c,
+                      int32_t* d_out, ieache_stats* stats) {
+    return guarded([&] {
+        if (!ctx || !d_a || !d_b || !d_c || !d_out) return fail(IEACHE_EINVAL, "null argument");
+        require_device_pointers(count, {{d_a, "d_a"}, {d_b, "d_b"}, {d_c, "d_c"}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->mux_device(count, d_a, d_b, d_c, d_out, st); });
+    });
+}
+
+int ieache_mux(ieache_ctx* ctx, size_t count, const int32_t* a, const int32_t* b, const int32_t* c, int32_t* out,
+               ieache_stats* stats) {
+    return guarded([&] {
+        if (!ctx || !a || !b || !c || !out) return fail(IEACHE_EINVAL, "null argument");
+        HostCall h(ctx, count);
+        StagedRows da = h.operand(kStageA, a), db = h.operand(kStageB, b), dc = h.operand(kStageC, c), dout = h.results(count);
+        with_stats(stats, [&](EvalStats* st) { h.ev.mux_device(count, da.p, db.p, dc.p, dout.p, st); });
+        h.download(dout, out);
         return 0;
     });
 }
@@ -647,20 +689,10 @@ int ieache_extract_stride(const ieache_ctx* ctx) { return ctx ? ctx->eval->extra
 int ieache_pbs_device(ieache_ctx* ctx, size_t count, const int32_t* d_x, const int32_t* d_test_polys, int32_t n_polys,
                       const int32_t* d_poly_of, int32_t* d_out, int flags, ieache_stats* stats) {
     return guarded([&] {
-        if (flags & ~IEACHE_PBS_NO_KEYSWITCH) return fail(IEACHE_EINVAL, "pbs: unknown flag");
-        if (n_polys < 1) return fail(IEACHE_EINVAL, "pbs: n_polys must be at least 1");
-        if (!d_test_polys) return fail(IEACHE_EINVAL, "pbs: null test polynomial table");
+        if (const char* e = pbs_args_error(flags, n_polys, d_test_polys)) return fail(IEACHE_EINVAL, e);
         if (!ctx || !d_x || !d_out) return fail(IEACHE_EINVAL, "null argument");
-        if (count) {
-            require_device_pointer(d_x, "d_x");
-            require_device_pointer(d_test_polys, "d_test_polys");
-            if (d_poly_of) require_device_pointer(d_poly_of, "d_poly_of");
-            require_device_pointer(d_out, "d_out");
-        }
-        EvalStats st;
-        ctx->eval->pbs_device(count, d_x, d_test_polys, n_polys, d_poly_of, d_out, flags, stats ? &st : nullptr);
-        to_stats(st, stats);
-        return 0;
+        require_device_pointers(count, {{d_x, "d_x"}, {d_test_polys, "d_test_polys"}, {d_poly_of, "d_poly_of", true}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->pbs_device(count, d_x, d_test_polys, n_polys, d_poly_of, d_out, flags, st); });
     });
 }
 
@@ -668,27 +700,16 @@ int ieache_pbs(ieache_ctx* ctx, size_t count, const int32_t* x, const int32_t* t
                int32_t* out, int flags, ieache_stats* stats) {
     return guarded([&] {
         // what can be judged without the context comes first
-        if (flags & ~IEACHE_PBS_NO_KEYSWITCH) return fail(IEACHE_EINVAL, "pbs: unknown flag");
-        if (n_polys < 1) return fail(IEACHE_EINVAL, "pbs: n_polys must be at least 1");
-        if (!test_polys) return fail(IEACHE_EINVAL, "pbs: null test polynomial table");
-        for (size_t i = 0; poly_of && i < count; i++)
-            if (poly_of[i] < 0 || poly_of[i] >= n_polys)
-                return fail(IEACHE_EINVAL, "pbs: poly_of[" + std::to_string(i) + "] = " + std::to_string(poly_of[i]) + " is outside [0, n_polys)");
+        if (const char* e = pbs_args_error(flags, n_polys, test_polys)) return fail(IEACHE_EINVAL, e);
+        const std::string bad_index = poly_of_error("pbs", poly_of, count, n_polys);
+        if (!bad_index.empty()) return fail(IEACHE_EINVAL, bad_index);
         if (!ctx || !x || !out) return fail(IEACHE_EINVAL, "null argument");
-        const Params& p = ctx->eval->params();
         const bool woks = (flags & IEACHE_PBS_NO_KEYSWITCH) != 0;
-        const size_t out_stride = woks ? (size_t)ctx->eval->extract_stride() : (size_t)p.lwe_stride();
-        const size_t out_width = woks ? (size_t)p.N + 1 : (size_t)p.n + 1;
-        HIP_CHECK(hipSetDevice(ctx->eval->device()));
-        StagedRows dx(*ctx->eval, 0, count, p.lwe_stride()), dout(*ctx->eval, 3, count, out_stride);
-        StagedRows dtv(*ctx->eval, 4, (size_t)n_polys, (size_t)p.N), dof(*ctx->eval, 5, poly_of ? count : 0, 1);
-        dx.upload(x, p.n + 1);
-        dtv.upload(test_polys, (size_t)p.N);
-        if (poly_of) dof.upload(poly_of, 1);
-        EvalStats st;
-        ctx->eval->pbs_device(count, dx.p, dtv.p, n_polys, poly_of ? dof.p : nullptr, dout.p, flags, stats ? &st : nullptr);
-        dout.download(out, out_width);
-        to_stats(st, stats);
+        HostCall h(ctx, count);
+        StagedRows dx = h.operand(kStageA, x), dout = h.results(count, woks);
+        StagedRows dtv = h.polys(kStageTestPolys, test_polys, (size_t)n_polys), dof = h.words(kStagePolyOf, poly_of, count);
+        with_stats(stats, [&](EvalStats* st) { h.ev.pbs_device(count, dx.p, dtv.p, n_polys, dof.p, dout.p, flags, st); });
+        h.download(dout, out, woks);
         return 0;
     });
 }
@@ -697,24 +718,13 @@ int ieache_pbs_multi_device(ieache_ctx* ctx, size_t count, const int32_t* d_x, c
                             const int32_t* d_poly_of, const int32_t* d_factors, int32_t n_factors, const int32_t* d_bias, int32_t* d_out,
                             int flags, ieache_stats* stats) {
     return guarded([&] {
-        if (flags & ~IEACHE_PBS_NO_KEYSWITCH) return fail(IEACHE_EINVAL, "pbs_multi: unknown flag");
-        if (n_polys < 1) return fail(IEACHE_EINVAL, "pbs_multi: n_polys must be at least 1");
-        if (!d_test_polys) return fail(IEACHE_EINVAL, "pbs_multi: null test polynomial table");
-        if (n_factors < 1 || n_factors > IEACHE_PBS_MULTI_MAX_FACTORS) return fail(IEACHE_EINVAL, "pbs_multi: n_factors must be 1 .. 64");
-        if (!d_factors) return fail(IEACHE_EINVAL, "pbs_multi: null factor table");
+        if (const char* e = pbs_multi_args_error(flags, n_polys, d_test_polys, n_factors, d_factors)) return fail(IEACHE_EINVAL, e);
         if (!ctx || !d_x || !d_out) return fail(IEACHE_EINVAL, "null argument");
-        if (count) {
-            require_device_pointer(d_x, "d_x");
-            require_device_pointer(d_test_polys, "d_test_polys");
-            if (d_poly_of) require_device_pointer(d_poly_of, "d_poly_of");
-            require_device_pointer(d_factors, "d_factors");
-            if (d_bias) require_device_pointer(d_bias, "d_bias");
-            require_device_pointer(d_out, "d_out");
-        }
-        EvalStats st;
-        ctx->eval->pbs_multi_device(count, d_x, d_test_polys, n_polys, d_poly_of, d_factors, n_factors, d_bias, d_out, flags, stats ? &st : nullptr);
-        to_stats(st, stats);
-        return 0;
+        require_device_pointers(count, {{d_x, "d_x"}, {d_test_polys, "d_test_polys"}, {d_poly_of, "d_poly_of", true}, {d_factors, "d_factors"},
+                                        {d_bias, "d_bias", true}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) {
+            ctx->eval->pbs_multi_device(count, d_x, d_test_polys, n_polys, d_poly_of, d_factors, n_factors, d_bias, d_out, flags, st);
+        });
     });
 }
 
@@ -722,33 +732,19 @@ int ieache_pbs_multi(ieache_ctx* ctx, size_t count, const int32_t* x, const int3
                      const int32_t* factors, int32_t n_factors, const int32_t* bias, int32_t* out, int flags, ieache_stats* stats) {
     return guarded([&] {
         // what can be judged without the context comes first
-        if (flags & ~IEACHE_PBS_NO_KEYSWITCH) return fail(IEACHE_EINVAL, "pbs_multi: unknown flag");
-        if (n_polys < 1) return fail(IEACHE_EINVAL, "pbs_multi: n_polys must be at least 1");
-        if (!test_polys) return fail(IEACHE_EINVAL, "pbs_multi: null test polynomial table");
-        if (n_factors < 1 || n_factors > IEACHE_PBS_MULTI_MAX_FACTORS) return fail(IEACHE_EINVAL, "pbs_multi: n_factors must be 1 .. 64");
-        if (!factors) return fail(IEACHE_EINVAL, "pbs_multi: null factor table");
-        for (size_t i = 0; poly_of && i < count; i++)
-            if (poly_of[i] < 0 || poly_of[i] >= n_polys)
-                return fail(IEACHE_EINVAL, "pbs_multi: poly_of[" + std::to_string(i) + "] = " + std::to_string(poly_of[i]) + " is outside [0, n_polys)");
+        if (const char* e = pbs_multi_args_error(flags, n_polys, test_polys, n_factors, factors)) return fail(IEACHE_EINVAL, e);
+        const std::string bad_index = poly_of_error("pbs_multi", poly_of, count, n_polys);
+        if (!bad_index.empty()) return fail(IEACHE_EINVAL, bad_index);
         if (!ctx || !x || !out) return fail(IEACHE_EINVAL, "null argument");
-        const Params& p = ctx->eval->params();
         const bool woks = (flags & IEACHE_PBS_NO_KEYSWITCH) != 0;
-        const size_t out_stride = woks ? (size_t)ctx->eval->extract_stride() : (size_t)p.lwe_stride();
-        const size_t out_width = woks ? (size_t)p.N + 1 : (size_t)p.n + 1;
-        HIP_CHECK(hipSetDevice(ctx->eval->device()));
-        StagedRows dx(*ctx->eval, 0, count, p.lwe_stride()), dout(*ctx->eval, 3, count * (size_t)n_factors, out_stride);
-        StagedRows dtv(*ctx->eval, 4, (size_t)n_polys, (size_t)p.N), dof(*ctx->eval, 5, poly_of ? count : 0, 1);
-        StagedRows dfa(*ctx->eval, 6, (size_t)n_factors, (size_t)p.N), dbi(*ctx->eval, 7, bias ? (size_t)n_factors : 0, 1);
-        dx.upload(x, p.n + 1);
-        dtv.upload(test_polys, (size_t)p.N);
-        if (poly_of) dof.upload(poly_of, 1);
-        dfa.upload(factors, (size_t)p.N);
-        if (bias) dbi.upload(bias, 1);
-        EvalStats st;
-        ctx->eval->pbs_multi_device(count, dx.p, dtv.p, n_polys, poly_of ? dof.p : nullptr, dfa.p, n_factors, bias ? dbi.p : nullptr, dout.p, flags,
-                                    stats ? &st : nullptr);
-        dout.download(out, out_width);
-        to_stats(st, stats);
+        HostCall h(ctx, count);
+        StagedRows dx = h.operand(kStageA, x), dout = h.results(count * (size_t)n_factors, woks);
+        StagedRows dtv = h.polys(kStageTestPolys, test_polys, (size_t)n_polys), dof = h.words(kStagePolyOf, poly_of, count);
+        StagedRows dfa = h.polys(kStageFactors, factors, (size_t)n_factors), dbi = h.words(kStageBias, bias, (size_t)n_factors);
+        with_stats(stats, [&](EvalStats* st) {
+            h.ev.pbs_multi_device(count, dx.p, dtv.p, n_polys, dof.p, dfa.p, n_factors, dbi.p, dout.p, flags, st);
+        });
+        h.download(dout, out, woks);
         return 0;
     });
 }
@@ -780,42 +776,6 @@ int ieache_lut_test_poly(const ieache_params* p, int32_t entries, const int32_t*
     }
     g_err.clear();
     return 0;
-}
-
-int ieache_mux_device(ieache_ctx* ctx, size_t count, const int32_t* d_a, const int32_t* d_b, const int32_t* d_c,
-                      int32_t* d_out, ieache_stats* stats) {
-    return guarded([&] {
-        if (!ctx || !d_a || !d_b || !d_c || !d_out) return fail(IEACHE_EINVAL, "null argument");
-        if (count) {
-            require_device_pointer(d_a, "d_a");
-            require_device_pointer(d_b, "d_b");
-            require_device_pointer(d_c, "d_c");
-            require_device_pointer(d_out, "d_out");
-        }
-        EvalStats st;
-        ctx->eval->mux_device(count, d_a, d_b, d_c, d_out, stats ? &st : nullptr);
-        to_stats(st, stats);
-        return 0;
-    });
-}
-
-int ieache_mux(ieache_ctx* ctx, size_t count, const int32_t* a, const int32_t* b, const int32_t* c, int32_t* out,
-               ieache_stats* stats) {
-    return guarded([&] {
-        if (!ctx || !a || !b || !c || !out) return fail(IEACHE_EINVAL, "null argument");
-        const Params& p = ctx->eval->params();
-        HIP_CHECK(hipSetDevice(ctx->eval->device()));
-        StagedRows da(*ctx->eval, 0, count, p.lwe_stride()), db(*ctx->eval, 1, count, p.lwe_stride()), dc(*ctx->eval, 2, count, p.lwe_stride()),
-            dout(*ctx->eval, 3, count, p.lwe_stride());
-        da.upload(a, p.n + 1);
-        db.upload(b, p.n + 1);
-        dc.upload(c, p.n + 1);
-        EvalStats st;
-        ctx->eval->mux_device(count, da.p, db.p, dc.p, dout.p, stats ? &st : nullptr);
-        dout.download(out, p.n + 1);
-        to_stats(st, stats);
-        return 0;
-    });
 }
 
 int ieache_debug_blind_rotate(ieache_ctx* ctx, size_t count, const int32_t* x, int32_t* acc, int32_t steps) {

@@ -373,8 +373,8 @@ void eval_circuit_host(Evaluator& eval, const Circuit& c, size_t batch, const To
     if (batch == 0) return;
     HIP_CHECK(hipSetDevice(eval.device()));
     // the evaluator's own staging rows: a warm call (same or smaller batch) allocates nothing
-    Torus32* d_in = eval.staging(0, n_in * stride * 4);
-    Torus32* d_out = eval.staging(3, n_out * stride * 4);
+    Torus32* d_in = eval.staging(kStageA, n_in * stride * 4);
+    Torus32* d_out = eval.staging(kStageOut, n_out * stride * 4);
     HIP_CHECK(hipMemcpy2D(d_in, stride * 4, in, S * 4, S * 4, n_in, hipMemcpyHostToDevice));
     eval.eval_circuit_device(c, batch, d_in, d_out, stats);
     HIP_CHECK(hipMemcpy2D(out, S * 4, d_out, stride * 4, S * 4, n_out, hipMemcpyDeviceToHost));

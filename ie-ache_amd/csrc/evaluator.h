@@ -28,6 +28,19 @@ struct EvalStats {
     int64_t levels = 0;
 };
 
+// what each staging buffer of an evaluator holds (Evaluator::staging)
+enum StageSlot : int {
+    kStageA,          // operands a, b, c: rows of lwe_stride() words
+    kStageB,
+    kStageC,
+    kStageOut,        // results
+    kStageTestPolys,  // programmable bootstrap: test polynomials [n][N]
+    kStagePolyOf,     //   ... and the row of that table each item takes
+    kStageFactors,    // multi-output programmable bootstrap: factor polynomials [n_factors][N]
+    kStageBias,       //   ... and the bias of each factor
+    kStageSlots
+};
+
 class Evaluator {
 public:
     Evaluator(const Params& p, int device);
@@ -101,13 +114,12 @@ public:
     void eval_circuit_device(const Circuit& c, size_t batch, const Torus32* d_in, Torus32* d_out,
                              EvalStats* stats);
 
-    // Device rows the host-buffer entry points stage operands (slot 0 .. 2) and results (slot 3) in: owned by the evaluator,
-    // kept between calls and grown on demand, so that a warm call allocates nothing.  Operand slots are zero outside what
-    // the caller uploads (rows of lwe_stride() words, n + 1 of them uploaded).  Slots 4 and 5 hold the test polynomials and
-    // the row indices of a programmable bootstrap, slots 6 and 7 the factors and the bias of a multi-output one (whole rows are uploaded; no other
-    // call reads them).  get_option("staging_allocations") counts
-    // the (re)allocations made so far.
-    Torus32* staging(int slot, size_t bytes);
+    // Device rows the host-buffer entry points stage operands and results in, one buffer per StageSlot: owned by the
+    // evaluator, kept between calls and grown on demand, so that a warm call allocates nothing.  Operand slots are zero outside
+    // what the caller uploads (rows of lwe_stride() words, n + 1 of them uploaded); of the tables of a programmable bootstrap
+    // whole rows are uploaded, and no other call reads them.  get_option("staging_allocations") counts the (re)allocations
+    // made so far.
+    Torus32* staging(StageSlot slot, size_t bytes);
 
     // ---- single-stage hooks (parity tests compare each against its oracle stage) ----
     // x [count][lwe_stride] -> acc [count][2][N] after `steps` CMux steps (steps<0: all n),
@@ -166,18 +178,16 @@ public:
     // -> audits run, gate instances compared, rows that differed, over the context's life.
     void fft_audit_counts(int64_t* audits, int64_t* gates, int64_t* mismatches) const;
 
-    struct Impl;  // device buffers; defined in evaluator.hip
+    struct Impl;      // device buffers; defined in evaluator.hip
+    struct FlatCall;  // what a flat call (gates, mux, programmable bootstraps) hands its one body; defined in evaluator.hip
 
 private:
-    void gates_device_once(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,
-                           EvalStats* stats);  // d_c: third operand of GATE_MAJ3 / GATE_XOR3, null otherwise
-    void pbs_device_once(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of, Torus32* d_out,
-                         int32_t flags, EvalStats* stats);
-    void pbs_multi_device_once(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of,
-                               const int32_t* d_factors, int32_t n_factors, const Torus32* d_bias, Torus32* d_out, int32_t flags, EvalStats* stats);
-    void mux_device_once(size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out, EvalStats* stats);
+    void flat_device_once(const FlatCall& call, EvalStats* stats);  // gates, gates3, mux, pbs and pbs_multi, once
     void eval_circuit_device_once(const Circuit& c, size_t batch, const Torus32* d_in, Torus32* d_out, EvalStats* stats);
     void debug_blind_rotate_once(size_t count, const Torus32* d_x, Torus32* d_acc, int32_t steps);
+    // runs `once`, and again on the two-limb kernels if the rounding guard or the audit asks for it (evaluator.hip)
+    template <class F>
+    void run_guarded(bool inputs_intact, EvalStats* stats, F&& once);
     void init();
     void destroy();
     void begin_call();

@@ -18,6 +18,7 @@
 #include "evaluator.h"
 
 #include <cstring>
+#include <initializer_list>
 
 #include "blind_rotate.h"
 #include "device_buffer.h"
@@ -62,20 +63,9 @@ __global__ void k_pad_rows(const Torus32* src, Torus32* dst, int64_t rows, int32
     }
 }
 
-// bootsMUX: u = (0, 1/8) + u1 + u2 over the extracted samples of the two blind rotations of a gate
-// (rows 2g and 2g+1 of `ext`), written to row g of `dst`; the key switch follows on `dst`
-__global__ void k_mux_combine(const Torus32* ext, Torus32* dst, int32_t N) {
-    const size_t g = blockIdx.x;
-    const Torus32* u1 = ext + (2 * g) * (size_t)(N + 4);
-    const Torus32* u2 = u1 + (N + 4);
-    Torus32* d = dst + g * (size_t)(N + 4);
-    for (int32_t j = threadIdx.x; j <= N; j += blockDim.x)
-        d[j] = (int32_t)((uint32_t)u1[j] + (uint32_t)u2[j] + (j == N ? (uint32_t)kMU : 0u));
-}
-
 // A circuit level with MUX gates (level_items.h): the rows of extracted samples of one piece, one per ROTATION item, become
-// one row per GATE for the key switch -- a two-input gate's row as it is, a MUX gate's as k_mux_combine forms it,
-// (0, 1/8) + u1 + u2 over its two rotations (boot-gates.cpp).  One workgroup per gate of the piece; pure streaming, rows
+// one row per GATE for the key switch -- a two-input gate's row as it is, a MUX gate's as bootsMUX forms it,
+// (0, 1/8) + u1 + u2 over its two rotations (boot-gates.cpp), uint32 adds.  A flat MUX call is the level ng = nm = 1.  One workgroup per gate of the piece; pure streaming, rows
 // of N + 4 words moved as 16-byte words (N is a multiple of 4, so word N -- the b term -- is lane x of 16-byte word N / 4).
 // gate0 / item0: the piece's first gate instance / rotation item; the caller cuts pieces at gate boundaries, so both rows of
 // a MUX are inside ext's `cnt` rows.
@@ -157,7 +147,7 @@ struct Evaluator::Impl {
         int n[2] = {0, 0};            // trials so far (two each, alternating: a first call also pays for allocations)
     };
     std::map<std::tuple<size_t, int32_t, size_t, size_t, bool>, Tuned> tuned;  // (gates, levels, outputs, batch, exact_fft)
-    DeviceBuffer<Torus32> stage[8];  // rows the host-buffer entry points stage operands and results in (counted in bytes)
+    DeviceBuffer<Torus32> stage[kStageSlots];  // rows the host-buffer entry points stage operands and results in (counted in bytes)
     DevKeys K{};
     BlindRotate br;  // K0-K4: kernels, key forms, guard record, audit and LDS grants; the choice among the kernels is br_plan.h
     double guard_max = 0;        // largest rounding deviation seen by the one-limb kernel (of 0.5)
@@ -165,7 +155,6 @@ struct Evaluator::Impl {
     DeviceBuffer<int32_t> ksk;
     KeySwitch ks;  // K5: kernels, key form, LDS grants and the choice among them
     MultiExtract mv;  // between K3 and K5 of a multi-output programmable bootstrap: the factors' lists and the extraction by factor
-    DeviceBuffer<Torus32> ext_mux;  // bootsMUX: combined extracted samples, chunk/2 rows
     DeviceBuffer<Torus32> store;    // circuits: the wire store, the gate and the output table
     DeviceBuffer<DevGate> d_gates;
     DeviceBuffer<OutRef> d_outs;
@@ -253,14 +242,13 @@ void Evaluator::wait_for_stream(hipStream_t producer) {
     HIP_CHECK(e);
 }
 
-// Staging rows for the host-buffer entry points (slot 0 .. 2: operands, 3: results, 4 / 5: test polynomials and row indices
-// of a programmable bootstrap, 6 / 7: factors and bias of a multi-output one).  A slot grows to at least `bytes`
+// Staging rows for the host-buffer entry points (StageSlot in evaluator.h).  A slot grows to at least `bytes`
 // (doubling, so a run of growing batches does not reallocate every call) and is zeroed when it is (re)allocated: callers
 // upload n + 1 words per row of lwe_stride() and rely on the padding words of OPERAND rows being zero, which holds because
-// nothing but such uploads ever writes slots 0 .. 2.  Every hipMalloc / hipFree is a device-wide synchronisation, which is
-// why a warm daemon request must not make one.
-Torus32* Evaluator::staging(int slot, size_t bytes) {
-    if (slot < 0 || slot >= 8) throw std::invalid_argument("staging slot");
+// nothing but such uploads ever writes the operand slots.  Every hipMalloc / hipFree is a device-wide synchronisation, which
+// is why a warm daemon request must not make one.
+Torus32* Evaluator::staging(StageSlot slot, size_t bytes) {
+    if (slot < 0 || slot >= kStageSlots) throw std::invalid_argument("staging slot");
     HIP_CHECK(hipSetDevice(device_));
     bytes = (bytes + 255) & ~(size_t)255;
     DeviceBuffer<Torus32>& st = d_->stage[slot];
@@ -520,59 +508,86 @@ static void reserve_scratch(const Params& p, Evaluator::Impl* d, const int64_t* 
     }
 }
 
-// The stage a multi-output programmable bootstrap puts between a piece's blind rotation and its key switch (multi_extract.h).
-struct MultiStage {
-    int32_t n_factors;
-    const Torus32* bias;  // device, [n_factors], or null
+// What follows a piece's blind rotation, and on which lanes the pieces of a level run: the one statement of run_items' mode.
+struct After {
+    // -1: as plan_level says -- lane 0 in pieces of a chunk, or the level's halves alternating between two lanes; k >= 0: the
+    // whole level on lane k in pieces of at most a chunk, no fork / join (a pipeline of its own, see eval_circuit_device_once,
+    // or a flat MUX on lane 0)
+    int lane = -1;
+    // The stage between a piece's rotation and its output rows:
+    //   kMuxCombine: k_level_combine turns the piece's rows, one per ROTATION item, into one per GATE in the lane's `comb`; the
+    //     level's (ng, nm) come from the descriptor, a flat MUX call (flat_type == kFlatMux) is the level ng = nm = 1;
+    //   kMultiExtract (flat calls, planned lanes): a multi-output programmable bootstrap -- the rotation leaves its whole
+    //     accumulators in the lane's scratch, k_mv_extract turns them into the lane's ordinary `ext` rows (what the audit compares)
+    //     and n_factors rows per item: output row = item x n_factors + factor.  Pieces are max(1, chunk / n_factors) items at
+    //     most, so the key switch and the rows stay within what `chunk` bounds (n_factors > chunk: one item, n_factors rows).
+    enum Stage { kNone, kMuxCombine, kMultiExtract } stage = kNone;
+    int32_t n_factors = 1;          // kMultiExtract
+    const Torus32* bias = nullptr;  // kMultiExtract: device, [n_factors], or null
+    // Where the rows go: null -- through the key switch to where the descriptor puts them; else (flat calls, not after
+    // kMuxCombine) the extracted samples are the result -- rows of N + 4 words written there, at the piece's first row, and no
+    // key switch follows.
+    Torus32* rows_out = nullptr;
 };
 
 // Scratch of a multi-output call before its loop starts: per lane the piece's extracted samples and blind-rotation state, its
 // accumulators, its n_factors rows per item (not when they go straight to the caller) and a key switch over those rows.
-static void reserve_multi(const Params& p, Evaluator::Impl* d, const LevelPlan& pl, int64_t items, const MultiStage& mv, bool rows_to_caller) {
+static void reserve_multi(const Params& p, Evaluator::Impl* d, const LevelPlan& pl, int64_t items, int32_t n_factors, bool rows_to_caller) {
     const size_t piece = (size_t)std::min<int64_t>(pl.piece, std::max<int64_t>(items, 1));
-    const size_t rows = piece * (size_t)mv.n_factors, cap = (size_t)d->opt.chunk;
+    const size_t rows = piece * (size_t)n_factors, cap = (size_t)d->opt.chunk;
     if (pl.two_lanes) ensure_lanes(d, 2);
     for (int k = 0; k < (pl.two_lanes ? 2 : 1); k++) {
         Lane& ln = d->lane[k];
         reserve_lane(p, d, ln, piece);
-        d->mv.reserve(ln.mv, piece, rows_to_caller ? 0 : rows, cap, std::max(cap, (size_t)mv.n_factors));
+        d->mv.reserve(ln.mv, piece, rows_to_caller ? 0 : rows, cap, std::max(cap, (size_t)n_factors));
         if (!rows_to_caller) d->ks.reserve(ln.ks, (int64_t)rows, d->opt, d->force_generic_ks);
     }
 }
 
-// One level: `items` independent gate instances described by W (item0 is advanced per piece).  Everything queued so far
-// on lane 0 (the previous level) is complete before any piece starts; lane 0 has every piece behind it when this returns.
-// fixed_lane >= 0: the whole level on that lane, in pieces of at most a chunk, no fork / join (a pipeline of its own, see
-// eval_circuit_device_once); its scratch has been reserved by the caller.
-// ext_out (flat mode): the extracted samples are the result -- every piece's blind rotation writes its rows of N + 4 words
-// there, at the piece's first item, and no key switch follows.
-// mv (flat mode, not with fixed_lane): a multi-output programmable bootstrap -- every piece's blind rotation leaves its whole
-// accumulators in the lane's scratch, k_mv_extract turns them into the lane's ordinary `ext` rows (what the audit compares)
-// and n_factors rows per item, and the key switch runs over those rows: output row = item x n_factors + factor.  With
-// ext_out the rows go straight there and no key switch follows.  Pieces are max(1, chunk / n_factors) items at most, so
-// the key switch and the rows stay within what `chunk` bounds (n_factors > chunk: one item, n_factors rows).
+// The key switch's descriptor over ROWS of a flat call: row item0 + i -> row item0 + i of w.flat_out (only GateInst::out is
+// used by the key switch).  What the multi-output call and the flat MUX hand it: a flat-MUX descriptor must not reach the
+// key switch, resolve() gives it no output row.
+static WorkDesc rows_desc(const WorkDesc& w, int64_t item0) {
+    WorkDesc wk{};
+    wk.flat_a = w.flat_a;
+    wk.flat_out = w.flat_out;
+    wk.flat_type = -1;
+    wk.item0 = item0;
+    return wk;
+}
+
+// One level: `items` independent rotation items described by W (item0 is advanced per piece), followed by what `after` says.
+// Everything queued so far on lane 0 (the previous level) is complete before any piece starts; lane 0 has every piece behind
+// it when this returns.  The scratch of a level on a fixed lane may have been reserved by the caller; it is checked here.
 static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t items, Timer& tbr, Timer& tks, EvalStats* stats,
-                      int fixed_lane = -1, Torus32* ext_out = nullptr, const MultiStage* mv = nullptr) {
-    LevelPlan pl = plan_level(d, items);
-    if (mv) pl.piece = std::min<int64_t>(pl.piece, std::max<int64_t>(1, (int64_t)d->opt.chunk / mv->n_factors));
-    // A level with MUX gates (circuit mode, W.nm > 0): `items` are rotation items, two per MUX.  PIECES ARE CUT AT GATE
-    // BOUNDARIES (level_piece_items), so both rotations of a MUX are in the same piece, on the same lane, in the same `ext`,
-    // before its combine runs.  That one rule covers every way a level is cut:
+                      const After& after = After{}) {
+    // A level with MUX gates: `items` are rotation items, two per MUX.  PIECES ARE CUT AT GATE BOUNDARIES (level_piece_items),
+    // so both rotations of a MUX are in the same piece, on the same lane, in the same `ext`, before its combine runs.  That
+    // one rule covers every way a level is cut:
     //   * "chunk", odd values included: a piece that would end between a MUX's two items takes the second one as well;
     //   * level halves on two lanes (plan_level): the halves are pieces like any other, each lane combines its own;
-    //   * expression-half pipelines (fixed_lane): a pipeline's share starts and ends at an expression, which is a gate boundary;
+    //   * expression-half pipelines (a fixed lane): a pipeline's share starts and ends at an expression, which is a gate boundary;
+    //   * a flat MUX call: every gate is a MUX, so its pieces are planned in whole gates -- max(chunk & ~1, 2) items -- and the
+    //     rule has nothing to add;
     //   * the rotation of roles cuts a launch into subsets INSIDE launch_blind_rotate, and its last act is to make the lane's
     //     stream wait for every subset's stream (launch_mixed_phases' join) before the final slices write `ext` there: what is
     //     queued on the lane's stream afterwards -- audit, combine, key switch -- sees the whole piece.
-    const bool mux = W.gates && W.nm > 0;
-    const int64_t gates = mux ? items / (W.ng + W.nm) * W.ng : items;  // gate instances of the level
-    if (fixed_lane >= 0) {
-        pl.two_lanes = false;
-        pl.piece = (int64_t)d->opt.chunk;
+    // The mode, decided here once for every piece:
+    const bool mux = after.stage == After::kMuxCombine, mv = after.stage == After::kMultiExtract;
+    const bool flat_mux = mux && !W.gates, to_caller = after.rows_out != nullptr;
+    const int32_t ng = flat_mux ? 1 : W.ng, nm = flat_mux ? 1 : W.nm;  // read only where mux
+    const int64_t nf = mv ? after.n_factors : 1;                       // output rows per item
+    const int64_t gates = mux ? items / (ng + nm) * ng : items;        // gate instances of the level
+    const size_t row_words = (size_t)(d->K.N + 4);
+    const int64_t chunk = (int64_t)d->opt.chunk;
+    LevelPlan pl = plan_level(d, items);
+    if (after.lane >= 0) pl = LevelPlan{false, flat_mux ? std::max<int64_t>(chunk & ~(int64_t)1, 2) : chunk};
+    if (mv) {
+        pl.piece = std::min<int64_t>(pl.piece, std::max<int64_t>(1, chunk / nf));
+        reserve_multi(p, d, pl, items, after.n_factors, to_caller);
+    } else if (after.lane >= 0) {
         const size_t need = (size_t)std::min<int64_t>(pl.piece + (mux ? 1 : 0), std::max<int64_t>(items, 1));
-        reserve_lane(p, d, d->lane[fixed_lane], need, mux ? std::min<size_t>(need, (size_t)gates) : 0);
-    } else if (mv) {
-        reserve_multi(p, d, pl, items, *mv, ext_out != nullptr);
+        reserve_lane(p, d, d->lane[after.lane], need, mux ? std::min<size_t>(need, (size_t)gates) : 0);
     } else {
         reserve_scratch(p, d, &items, 1, mux ? &gates : nullptr);
     }
@@ -581,61 +596,53 @@ static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t i
     ScopedSet<bool> halves(d->level_on_two_lanes, pl.two_lanes);
     int k = 0;
     for (int64_t done = 0, cnt = 0; done < items; done += cnt, k++) {
-        cnt = mux ? level_piece_items(W.item0 + done, pl.piece, items - done, W.ng, W.nm) : std::min<int64_t>(pl.piece, items - done);
-        Lane& ln = d->lane[fixed_lane >= 0 ? fixed_lane : (pl.two_lanes ? (k & 1) : 0)];
+        cnt = mux ? level_piece_items(W.item0 + done, pl.piece, items - done, ng, nm) : std::min<int64_t>(pl.piece, items - done);
+        Lane& ln = d->lane[after.lane >= 0 ? after.lane : (pl.two_lanes ? (k & 1) : 0)];
         WorkDesc w = W;
         w.item0 = W.item0 + done;
         if ((size_t)cnt > ln.ext.items()) throw std::logic_error("piece larger than the lane's extracted-sample rows");
-        const BrPlan plan = plan_blind_rotate(p, d, ln, cnt);  // once: the launch and the audit see the same choice
-        Torus32* ext = ext_out && !mv ? ext_out + (size_t)done * (size_t)(d->K.N + 4) : (Torus32*)ln.ext;
-        const int64_t nf = mv ? mv->n_factors : 1;
-        Torus32* mv_rows = !mv ? nullptr : ext_out ? ext_out + (size_t)(done * nf) * (size_t)(d->K.N + 4) : (Torus32*)ln.mv.rows;
-        if (mv && ((size_t)cnt > ln.mv.acc.items() || (!ext_out && (size_t)(cnt * nf) > ln.mv.rows.items())))
+        if (mv && ((size_t)cnt > ln.mv.acc.items() || (!to_caller && (size_t)(cnt * nf) > ln.mv.rows.items())))
             throw std::logic_error("piece larger than the lane's multi-output scratch");
+        const BrPlan plan = plan_blind_rotate(p, d, ln, cnt);  // once: the launch and the audit see the same choice
+        // ext: the rotation's extracted samples, one row per item; rows: what the stage after it leaves for the output
+        Torus32* ext = to_caller && !mv ? after.rows_out + (size_t)done * row_words : (Torus32*)ln.ext;
+        Torus32* rows = mux ? (Torus32*)ln.comb : !mv ? ext : to_caller ? after.rows_out + (size_t)(done * nf) * row_words : (Torus32*)ln.mv.rows;
         tbr.mark(ln.stream);
         const int nbr = launch_blind_rotate(d, ln, plan, w, cnt, mv ? nullptr : ext, -1, mv ? (Torus32*)ln.mv.acc : nullptr);
         tbr.mark(ln.stream);
         HIP_CHECK(hipGetLastError());
-        if (mv) d->mv.extract(ln.stream, ln.mv.acc, cnt, mv->n_factors, mv->bias, ext, mv_rows);
+        if (mv) d->mv.extract(ln.stream, ln.mv.acc, cnt, after.n_factors, after.bias, ext, rows);
         d->br.audit(ln.br, plan, d->opt, ln.stream, w, cnt, ext);
-        if (ext_out) {
-            if (stats) {
-                stats->blind_rotate_launches += nbr;
-                stats->chunks++;
-            }
-            continue;
-        }
-        tks.mark(ln.stream);
-        if (mux) {
-            // one row per gate, then the key switch over GATES: the same level descriptor read with nm = 0 and item0 in gate
-            // instances, for which resolve() is the identity the key-switch kernels have always used to find out_slot
-            if (!level_gate_boundary(w.item0, W.ng, W.nm) || !level_gate_boundary(w.item0 + cnt, W.ng, W.nm))
-                throw std::logic_error("piece of a level cut inside a MUX gate");
-            const int64_t gate0 = level_gates_before(w.item0, W.ng, W.nm);
-            const int64_t gcnt = level_gates_before(w.item0 + cnt, W.ng, W.nm) - gate0;
-            if ((size_t)gcnt > ln.comb.items() || (d->K.N & 3)) throw std::logic_error("combined rows of a MUX level not reserved");
-            hipLaunchKernelGGL(k_level_combine, dim3((unsigned)gcnt), dim3(256), 0, ln.stream, ln.ext, ln.comb, d->K.N, gate0, w.item0,
-                               W.ng, W.nm);
+        if (!to_caller) {
+            tks.mark(ln.stream);
             WorkDesc wk = w;
-            wk.nm = 0;
-            wk.item0 = gate0;
-            launch_keyswitch(d, ln, wk, gcnt, ln.comb, nullptr);
-        } else if (mv) {
-            // a flat descriptor over ROWS: row item0 x n_factors + i of flat_out (only GateInst::out is used by the key switch)
-            WorkDesc wk{};
-            wk.flat_a = w.flat_a;
-            wk.flat_out = w.flat_out;
-            wk.flat_type = -1;
-            wk.item0 = w.item0 * nf;
-            launch_keyswitch(d, ln, wk, cnt * nf, mv_rows, nullptr);
-        } else {
-            launch_keyswitch(d, ln, w, cnt, ln.ext, nullptr);
+            int64_t n_rows = cnt;
+            if (mux) {
+                // one row per gate, then the key switch over GATES: a level's own descriptor read with nm = 0 and item0 in gate
+                // instances, for which resolve() is the identity the key-switch kernels have always used to find out_slot
+                if (!level_gate_boundary(w.item0, ng, nm) || !level_gate_boundary(w.item0 + cnt, ng, nm))
+                    throw std::logic_error("piece of a level cut inside a MUX gate");
+                const int64_t gate0 = level_gates_before(w.item0, ng, nm);
+                n_rows = level_gates_before(w.item0 + cnt, ng, nm) - gate0;
+                if ((size_t)n_rows > ln.comb.items() || (d->K.N & 3)) throw std::logic_error("combined rows of a MUX level not reserved");
+                hipLaunchKernelGGL(k_level_combine, dim3((unsigned)n_rows), dim3(256), 0, ln.stream, ext, rows, d->K.N, gate0, w.item0, ng, nm);
+                if (flat_mux) {
+                    wk = rows_desc(w, gate0);
+                } else {
+                    wk.nm = 0;
+                    wk.item0 = gate0;
+                }
+            } else if (mv) {
+                n_rows = cnt * nf;
+                wk = rows_desc(w, w.item0 * nf);
+            }
+            launch_keyswitch(d, ln, wk, n_rows, rows, nullptr);
+            tks.mark(ln.stream);
+            HIP_CHECK(hipGetLastError());
         }
-        tks.mark(ln.stream);
-        HIP_CHECK(hipGetLastError());
         if (stats) {
             stats->blind_rotate_launches += nbr;
-            stats->keyswitch_launches++;
+            stats->keyswitch_launches += to_caller ? 0 : 1;
             stats->chunks++;
         }
     }
@@ -668,70 +675,46 @@ double Evaluator::fft_guard_max() const { return d_->guard_max; }
 int64_t Evaluator::fft_guard_reruns() const { return d_->guard_reruns; }
 
 namespace {
-bool overlaps(const Torus32* a, size_t na, const Torus32* b, size_t nb) {
-    return a && b && a < b + nb && b < a + na;
+// a device range of an entry point's argument, in words
+struct Range {
+    const void* p;
+    size_t words;
+};
+// whether the output range shares a word with any of the input ranges (a null pointer is no range)
+bool overlaps(const Torus32* out, size_t n_out, std::initializer_list<Range> inputs) {
+    for (const Range& r : inputs) {
+        const Torus32* in = static_cast<const Torus32*>(r.p);
+        if (out && in && out < in + r.words && in < out + n_out) return true;
+    }
+    return false;
 }
+}  // namespace
+
 // Repeats `once` on the two-limb kernels when the guard tripped or an audited row differed; the first attempt's time stays
 // in the stats, its counts do not.  A call whose output overlaps its inputs cannot be repeated (the first attempt has
 // overwritten them), so it runs on the two-limb kernels -- exact by construction -- from the start.
 template <class F>
-void run_guarded(Evaluator& ev, bool* exact_once, int64_t* reruns, bool inputs_intact, EvalStats* stats, F&& once) {
-    if (!inputs_intact && !*exact_once) {
+void Evaluator::run_guarded(bool inputs_intact, EvalStats* stats, F&& once) {
+    if (!inputs_intact && !d_->exact_once) {
         {
-            ScopedSet<bool> exact(*exact_once, true);
+            ScopedSet<bool> exact(d_->exact_once, true);
             once();
         }
-        (void)ev.fft_guard_tripped();  // folds the record of earlier calls; nothing this call did can trip it
+        (void)fft_guard_tripped();  // folds the record of earlier calls; nothing this call did can trip it
         return;
     }
     const EvalStats before = stats ? *stats : EvalStats{};
     once();
-    if (!ev.fft_guard_tripped()) return;
-    (*reruns)++;
+    if (!fft_guard_tripped()) return;
+    d_->guard_reruns++;
     EvalStats first{};
     if (stats) {
         first = *stats;
         *stats = before;
     }
-    ScopedSet<bool> exact(*exact_once, true);
+    ScopedSet<bool> exact(d_->exact_once, true);
     once();
     if (stats) stats->total_ms += first.total_ms - before.total_ms;
-}
-}  // namespace
-
-void Evaluator::gates_device(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b, Torus32* d_out,
-                             EvalStats* stats) {
-    const size_t len = count * (size_t)d_->K.stride;
-    run_guarded(*this, &d_->exact_once, &d_->guard_reruns, !overlaps(d_out, len, d_a, len) && !overlaps(d_out, len, d_b, len), stats,
-                [&] { gates_device_once(type, count, d_a, d_b, nullptr, d_out, stats); });
-}
-
-void Evaluator::gates3_device(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,
-                              EvalStats* stats) {
-    if (!is_gate3(type)) throw std::invalid_argument("not a one-rotation three-input gate type");
-    const size_t len = count * (size_t)d_->K.stride;
-    run_guarded(*this, &d_->exact_once, &d_->guard_reruns,
-                !overlaps(d_out, len, d_a, len) && !overlaps(d_out, len, d_b, len) && !overlaps(d_out, len, d_c, len), stats,
-                [&] { gates_device_once(type, count, d_a, d_b, d_c, d_out, stats); });
-}
-
-void Evaluator::mux_device(size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,
-                           EvalStats* stats) {
-    const size_t len = count * (size_t)d_->K.stride;
-    run_guarded(*this, &d_->exact_once, &d_->guard_reruns,
-                !overlaps(d_out, len, d_a, len) && !overlaps(d_out, len, d_b, len) && !overlaps(d_out, len, d_c, len), stats,
-                [&] { mux_device_once(count, d_a, d_b, d_c, d_out, stats); });
-}
-
-void Evaluator::eval_circuit_device(const Circuit& c, size_t batch, const Torus32* d_in, Torus32* d_out, EvalStats* stats) {
-    const size_t stride = (size_t)d_->K.stride;
-    run_guarded(*this, &d_->exact_once, &d_->guard_reruns,
-                !overlaps(d_out, batch * c.outputs.size() * stride, d_in, batch * (size_t)c.n_inputs * stride), stats,
-                [&] { eval_circuit_device_once(c, batch, d_in, d_out, stats); });
-}
-
-void Evaluator::debug_blind_rotate(size_t count, const Torus32* d_x, Torus32* d_acc, int32_t steps) {
-    run_guarded(*this, &d_->exact_once, &d_->guard_reruns, true, nullptr, [&] { debug_blind_rotate_once(count, d_x, d_acc, steps); });
 }
 
 // What every entry point that launches starts with: the key is there, the device is current, and the kernels this call
@@ -743,25 +726,80 @@ void Evaluator::begin_call() {
     d_->force_generic_ks = d_->opt.force_generic;
 }
 
-void Evaluator::gates_device_once(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c,
-                                  Torus32* d_out, EvalStats* stats) {
+// A flat call: `items` rotation items of one level, no circuit.
+struct Evaluator::FlatCall {
+    WorkDesc W{};                      // flat mode (gates null), item0 = 0
+    int64_t items = 0;                 // rotation items: rows in, except that a MUX is two
+    After after;                       // what follows the rotation
+    const int32_t* factors = nullptr;  // multi-output call: the factor table [after.n_factors][N] to compact first
+};
+
+// One flat call, once: its pieces through run_items on the evaluator's stream, timed, and the stream idle at the end.
+void Evaluator::flat_device_once(const FlatCall& call, EvalStats* stats) {
     begin_call();
-    if (count == 0) return;
+    if (call.items == 0) return;
     Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(stats != nullptr, stream_);
-    WorkDesc W{};
-    W.gates = nullptr;
-    W.flat_a = d_a;
-    W.flat_b = d_b;
-    W.flat_c = d_c;
-    W.flat_out = d_out;
-    W.flat_type = type;
-    W.item0 = 0;
     tall.mark();
-    run_items(p_, d_, W, (int64_t)count, tbr, tks, stats);
+    // on lane 0, ahead of the fork: every lane's extraction finds the lists
+    if (call.factors) d_->mv.compact(stream_, call.factors, call.after.n_factors);
+    run_items(p_, d_, call.W, call.items, tbr, tks, stats, call.after);
     tall.mark();
     HIP_CHECK(hipStreamSynchronize(stream_));
     add_times(stats, tall, tbr, tks);
     if (stats) stats->levels += 1;
+}
+
+// out[i] = gate(a[i], b[i] [, c[i]]): one rotation item and one key-switched row per gate
+static Evaluator::FlatCall gate_call(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out) {
+    Evaluator::FlatCall call;
+    call.W.flat_a = d_a;
+    call.W.flat_b = d_b;
+    call.W.flat_c = d_c;
+    call.W.flat_out = d_out;
+    call.W.flat_type = type;
+    call.items = (int64_t)count;
+    return call;
+}
+
+void Evaluator::gates_device(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b, Torus32* d_out,
+                             EvalStats* stats) {
+    const size_t len = count * (size_t)d_->K.stride;
+    const FlatCall call = gate_call(type, count, d_a, d_b, nullptr, d_out);
+    run_guarded(!overlaps(d_out, len, {{d_a, len}, {d_b, len}}), stats, [&] { flat_device_once(call, stats); });
+}
+
+void Evaluator::gates3_device(int32_t type, size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,
+                              EvalStats* stats) {
+    if (!is_gate3(type)) throw std::invalid_argument("not a one-rotation three-input gate type");
+    const size_t len = count * (size_t)d_->K.stride;
+    const FlatCall call = gate_call(type, count, d_a, d_b, d_c, d_out);
+    run_guarded(!overlaps(d_out, len, {{d_a, len}, {d_b, len}, {d_c, len}}), stats, [&] { flat_device_once(call, stats); });
+}
+
+// bootsMUX (boot-gates.cpp): two blind rotations per gate, their extracted samples added, one key switch -- a one-gate MUX
+// level on lane 0: rotation items 2g and 2g + 1 are gate g's (device_common.h: kFlatMux), k_level_combine sums them, and the
+// key switch runs over gates.  libtfhe counts a MUX as two bootstraps and one key switch; so do the statistics.
+void Evaluator::mux_device(size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,
+                           EvalStats* stats) {
+    const size_t len = count * (size_t)d_->K.stride;
+    FlatCall call = gate_call(kFlatMux, count, d_a, d_b, d_c, d_out);
+    call.items = 2 * (int64_t)count;
+    call.after.lane = 0;
+    call.after.stage = After::kMuxCombine;
+    run_guarded(!overlaps(d_out, len, {{d_a, len}, {d_b, len}, {d_c, len}}), stats, [&] { flat_device_once(call, stats); });
+}
+
+// tfhe_blindRotateAndExtract_FFT from a caller's test polynomial (+ lweKeySwitch): a gate call with the raw row of flat_a as
+// the combination (flat_type < 0 -- resolve(): the row as it stands, no second operand, no constant) and the descriptor
+// carrying the table, so every cut of the launch finds its polynomial.  Without key switch the extracted samples are the result.
+static Evaluator::FlatCall pbs_call(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of, Torus32* d_out,
+                                    bool woks) {
+    Evaluator::FlatCall call = gate_call(-1, count, d_x, nullptr, nullptr, woks ? nullptr : d_out);
+    call.W.tv = d_tv;
+    call.W.n_tv = n_tv;
+    call.W.tv_of = d_tv_of;
+    call.after.rows_out = woks ? d_out : nullptr;
+    return call;
 }
 
 void Evaluator::pbs_device(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of, Torus32* d_out,
@@ -770,42 +808,17 @@ void Evaluator::pbs_device(size_t count, const Torus32* d_x, const Torus32* d_tv
     if (n_tv < 1 || !d_tv) throw std::invalid_argument("programmable bootstrap: no test polynomial");
     const bool woks = (flags & kPbsNoKeyswitch) != 0;
     const size_t len = count * (size_t)d_->K.stride, out_len = count * (size_t)(woks ? extract_stride() : d_->K.stride);
-    const bool over_x = overlaps(d_out, out_len, d_x, len);
+    const bool over_x = overlaps(d_out, out_len, {{d_x, len}});
     // a repeat reads the table and the indices again: an output over either of them is over an input as much as one over x
-    const bool over_table = overlaps(d_out, out_len, d_tv, (size_t)n_tv * (size_t)p_.N) ||
-                            overlaps(d_out, out_len, reinterpret_cast<const Torus32*>(d_tv_of), count);
+    const bool over_table = overlaps(d_out, out_len, {{d_tv, (size_t)n_tv * (size_t)p_.N}, {d_tv_of, count}});
     if (over_table || (woks && over_x))
         throw std::invalid_argument(over_table ? "programmable bootstrap: the output overlaps the test polynomials or their indices"
                                                : "programmable bootstrap without key switch: the output overlaps the input rows");
-    run_guarded(*this, &d_->exact_once, &d_->guard_reruns, !over_x, stats,
-                [&] { pbs_device_once(count, d_x, d_tv, n_tv, d_tv_of, d_out, flags, stats); });
+    const FlatCall call = pbs_call(count, d_x, d_tv, n_tv, d_tv_of, d_out, woks);
+    run_guarded(!over_x, stats, [&] { flat_device_once(call, stats); });
 }
 
-// tfhe_blindRotateAndExtract_FFT from a caller's test polynomial (+ lweKeySwitch): gates_device_once with the raw row of
-// flat_a as the combination and the descriptor carrying the table, so every cut of the launch finds its polynomial
-void Evaluator::pbs_device_once(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of,
-                                Torus32* d_out, int32_t flags, EvalStats* stats) {
-    begin_call();
-    if (count == 0) return;
-    const bool woks = (flags & kPbsNoKeyswitch) != 0;
-    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(stats != nullptr, stream_);
-    WorkDesc W{};
-    W.gates = nullptr;
-    W.flat_a = d_x;
-    W.flat_out = woks ? nullptr : d_out;
-    W.flat_type = -1;  // resolve(): the row as it stands, no second operand, no constant
-    W.tv = d_tv;
-    W.n_tv = n_tv;
-    W.tv_of = d_tv_of;
-    W.item0 = 0;
-    tall.mark();
-    run_items(p_, d_, W, (int64_t)count, tbr, tks, stats, -1, woks ? d_out : nullptr);
-    tall.mark();
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    add_times(stats, tall, tbr, tks);
-    if (stats) stats->levels += 1;
-}
-
+// pbs_device with the stage of multi_extract.h between every piece's rotation and its key switch
 void Evaluator::pbs_multi_device(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of,
                                  const int32_t* d_factors, int32_t n_factors, const Torus32* d_bias, Torus32* d_out, int32_t flags,
                                  EvalStats* stats) {
@@ -816,87 +829,26 @@ void Evaluator::pbs_multi_device(size_t count, const Torus32* d_x, const Torus32
     const bool woks = (flags & kPbsNoKeyswitch) != 0;
     const size_t out_len = count * (size_t)n_factors * (size_t)(woks ? extract_stride() : d_->K.stride);
     // no in-place form: the output is n_factors times the input, and a repeat reads every input again
-    if (overlaps(d_out, out_len, d_x, count * (size_t)d_->K.stride) || overlaps(d_out, out_len, d_tv, (size_t)n_tv * (size_t)p_.N) ||
-        overlaps(d_out, out_len, reinterpret_cast<const Torus32*>(d_tv_of), count) ||
-        overlaps(d_out, out_len, d_factors, (size_t)n_factors * (size_t)p_.N) || overlaps(d_out, out_len, d_bias, (size_t)n_factors))
+    if (overlaps(d_out, out_len,
+                 {{d_x, count * (size_t)d_->K.stride}, {d_tv, (size_t)n_tv * (size_t)p_.N}, {d_tv_of, count},
+                  {d_factors, (size_t)n_factors * (size_t)p_.N}, {d_bias, (size_t)n_factors}}))
         throw std::invalid_argument("multi-output programmable bootstrap: the output overlaps an input (rows, test polynomials, indices, factors or bias)");
-    run_guarded(*this, &d_->exact_once, &d_->guard_reruns, true, stats,
-                [&] { pbs_multi_device_once(count, d_x, d_tv, n_tv, d_tv_of, d_factors, n_factors, d_bias, d_out, flags, stats); });
+    FlatCall call = pbs_call(count, d_x, d_tv, n_tv, d_tv_of, d_out, woks);
+    call.after.stage = After::kMultiExtract;
+    call.after.n_factors = n_factors;
+    call.after.bias = d_bias;
+    call.factors = d_factors;
+    run_guarded(true, stats, [&] { flat_device_once(call, stats); });
 }
 
-// pbs_device_once with the stage of multi_extract.h between every piece's rotation and its key switch
-void Evaluator::pbs_multi_device_once(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of,
-                                      const int32_t* d_factors, int32_t n_factors, const Torus32* d_bias, Torus32* d_out, int32_t flags,
-                                      EvalStats* stats) {
-    begin_call();
-    if (count == 0) return;
-    const bool woks = (flags & kPbsNoKeyswitch) != 0;
-    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(stats != nullptr, stream_);
-    WorkDesc W{};
-    W.gates = nullptr;
-    W.flat_a = d_x;
-    W.flat_out = woks ? nullptr : d_out;
-    W.flat_type = -1;
-    W.tv = d_tv;
-    W.n_tv = n_tv;
-    W.tv_of = d_tv_of;
-    W.item0 = 0;
-    const MultiStage mv{n_factors, d_bias};
-    tall.mark();
-    d_->mv.compact(stream_, d_factors, n_factors);  // on lane 0, ahead of the fork: every lane's extraction finds the lists
-    run_items(p_, d_, W, (int64_t)count, tbr, tks, stats, -1, woks ? d_out : nullptr, &mv);
-    tall.mark();
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    add_times(stats, tall, tbr, tks);
-    if (stats) stats->levels += 1;
+void Evaluator::eval_circuit_device(const Circuit& c, size_t batch, const Torus32* d_in, Torus32* d_out, EvalStats* stats) {
+    const size_t stride = (size_t)d_->K.stride;
+    run_guarded(!overlaps(d_out, batch * c.outputs.size() * stride, {{d_in, batch * (size_t)c.n_inputs * stride}}), stats,
+                [&] { eval_circuit_device_once(c, batch, d_in, d_out, stats); });
 }
 
-// bootsMUX (boot-gates.cpp): two blind rotations per gate, their extracted samples added, one key switch
-void Evaluator::mux_device_once(size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,
-                                EvalStats* stats) {
-    begin_call();
-    if (count == 0) return;
-    const DevKeys& K = d_->K;
-    const size_t chunk = std::max<size_t>(d_->opt.chunk & ~(size_t)1, 2), gates_per_chunk = chunk / 2;
-    const size_t mux_need = std::min(gates_per_chunk, count);  // two extracted samples per MUX gate
-    Lane& ln = d_->lane[0];
-    ln.ext.reserve(2 * mux_need, chunk, d_->ext_row_bytes());
-    d_->ext_mux.reserve(mux_need, gates_per_chunk, d_->ext_row_bytes());
-    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(stats != nullptr, stream_);
-    tall.mark();
-    for (size_t done = 0; done < count; done += gates_per_chunk) {
-        const int64_t cnt = (int64_t)std::min(gates_per_chunk, count - done);
-        WorkDesc W{};
-        W.flat_a = d_a + done * K.stride;
-        W.flat_b = d_b + done * K.stride;
-        W.flat_c = d_c + done * K.stride;
-        W.flat_type = kFlatMux;
-        W.item0 = 0;
-        const BrPlan plan = plan_blind_rotate(p_, d_, ln, 2 * cnt);
-        tbr.mark();
-        const int nbr = launch_blind_rotate(d_, ln, plan, W, 2 * cnt, ln.ext, -1, nullptr);
-        tbr.mark();
-        HIP_CHECK(hipGetLastError());
-        d_->br.audit(ln.br, plan, d_->opt, stream_, W, 2 * cnt, ln.ext);
-        tks.mark();
-        hipLaunchKernelGGL(k_mux_combine, dim3((unsigned)cnt), dim3(256), 0, stream_, ln.ext, d_->ext_mux, K.N);
-        WorkDesc Wk{};
-        launch_keyswitch(d_, ln, Wk, cnt, d_->ext_mux, d_out + done * K.stride);
-        tks.mark();
-        HIP_CHECK(hipGetLastError());
-        if (stats) {
-            stats->blind_rotate_launches += nbr;
-            stats->keyswitch_launches++;
-            stats->chunks++;
-        }
-    }
-    tall.mark();
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    add_times(stats, tall, tbr, tks);
-    if (stats) {
-        stats->bootstraps += 2 * (int64_t)count;  // blind rotations; libtfhe counts a MUX as two bootstraps and one key switch
-        stats->levels += 1;
-    }
+void Evaluator::debug_blind_rotate(size_t count, const Torus32* d_x, Torus32* d_acc, int32_t steps) {
+    run_guarded(true, nullptr, [&] { debug_blind_rotate_once(count, d_x, d_acc, steps); });
 }
 
 using TuneKey = std::tuple<size_t, int32_t, size_t, size_t, bool>;
@@ -1015,8 +967,10 @@ void Evaluator::eval_circuit_device_once(const Circuit& c, size_t batch, const T
             W.n_slots = c.n_slots;
             W.item0 = 0;
             const int64_t ni = (int64_t)W.ng + (int64_t)W.nm;  // rotation items per expression (level_items.h)
+            After after;
+            after.stage = W.nm > 0 ? After::kMuxCombine : After::kNone;
             if (!pipes) {
-                run_items(p_, d_, W, ni * (int64_t)batch, tbr, tks, stats);
+                run_items(p_, d_, W, ni * (int64_t)batch, tbr, tks, stats, after);
             } else {
                 // items are expression-major (item = expression x ni + position): a contiguous range of expressions is a
                 // contiguous range of items that starts and ends at a gate boundary
@@ -1024,7 +978,8 @@ void Evaluator::eval_circuit_device_once(const Circuit& c, size_t batch, const T
                     size_t first = 0, count = 0;
                     pipe_slice(batch, pipes, k, &first, &count);
                     W.item0 = ni * (int64_t)first;
-                    run_items(p_, d_, W, ni * (int64_t)count, tbr, tks, stats, k);
+                    after.lane = k;
+                    run_items(p_, d_, W, ni * (int64_t)count, tbr, tks, stats, after);
                 }
             }
             if (stats) stats->levels++;

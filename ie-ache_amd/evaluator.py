@@ -218,6 +218,11 @@ def _i32(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def _stats_ref(stats):
+    """the optional Stats argument of an entry point: a reference to it, or a null pointer"""
+    return C.byref(stats) if stats is not None else None
+
+
 def default_params():
     p = Params()
     lib().ieache_default_params(C.byref(p))
@@ -469,8 +474,7 @@ class Context:
         batch = in_lwe.shape[0]
         assert in_lwe.shape == (batch, info.n_inputs, self.params.n + 1), in_lwe.shape
         out = np.zeros((batch, info.n_outputs, self.params.n + 1), dtype=np.int32)
-        check(lib().ieache_eval_batch(self.h, kind, bits, batch, _i32(in_lwe), _i32(out),
-                                      C.byref(stats) if stats is not None else None))
+        check(lib().ieache_eval_batch(self.h, kind, bits, batch, _i32(in_lwe), _i32(out), _stats_ref(stats)))
         return out
 
     def prepare(self, kind, bits, batch):
@@ -480,8 +484,7 @@ class Context:
 
     def eval_batch_device(self, kind, bits, batch, d_in, d_out, stats=None):
         """Device pointers (ints); rows of lwe_stride int32."""
-        check(lib().ieache_eval_batch_device(self.h, kind, bits, batch, C.c_void_p(d_in), C.c_void_p(d_out),
-                                             C.byref(stats) if stats is not None else None))
+        check(lib().ieache_eval_batch_device(self.h, kind, bits, batch, C.c_void_p(d_in), C.c_void_p(d_out), _stats_ref(stats)))
 
     def eval_netlist(self, nl, in_lwe, stats=None):
         """A CompiledNetlist over a batch: in_lwe [batch][n_inputs][n+1] int32 on the host -> [batch][n_outputs][n+1]."""
@@ -490,7 +493,7 @@ class Context:
         batch = in_lwe.shape[0]
         assert in_lwe.shape == (batch, info.n_inputs, self.params.n + 1), in_lwe.shape
         out = np.zeros((batch, info.n_outputs, self.params.n + 1), dtype=np.int32)
-        check(lib().ieache_eval_netlist(self.h, nl.h, batch, _i32(in_lwe), _i32(out), C.byref(stats) if stats is not None else None))
+        check(lib().ieache_eval_netlist(self.h, nl.h, batch, _i32(in_lwe), _i32(out), _stats_ref(stats)))
         return out
 
     def prepare_netlist(self, nl, batch):
@@ -499,8 +502,7 @@ class Context:
 
     def eval_netlist_device(self, nl, batch, d_in, d_out, stats=None):
         """Device pointers (ints); rows of lwe_stride int32."""
-        check(lib().ieache_eval_netlist_device(self.h, nl.h, batch, C.c_void_p(d_in), C.c_void_p(d_out),
-                                               C.byref(stats) if stats is not None else None))
+        check(lib().ieache_eval_netlist_device(self.h, nl.h, batch, C.c_void_p(d_in), C.c_void_p(d_out), _stats_ref(stats)))
 
     def gates(self, gate_type, a, b, stats=None):
         a = np.ascontiguousarray(a, dtype=np.int32)
@@ -508,26 +510,23 @@ class Context:
         assert a.shape == b.shape and a.shape[-1] == self.params.n + 1
         out = np.zeros_like(a)
         count = a.size // (self.params.n + 1)
-        check(lib().ieache_gates(self.h, gate_type, count, _i32(a), _i32(b), _i32(out),
-                                 C.byref(stats) if stats is not None else None))
+        check(lib().ieache_gates(self.h, gate_type, count, _i32(a), _i32(b), _i32(out), _stats_ref(stats)))
         return out
 
     def gates_device(self, gate_type, count, d_a, d_b, d_out, stats=None):
-        check(lib().ieache_gates_device(self.h, gate_type, count, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out),
-                                        C.byref(stats) if stats is not None else None))
+        check(lib().ieache_gates_device(self.h, gate_type, count, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out), _stats_ref(stats)))
 
     def gates3(self, gate_type, a, b, c, stats=None):
         """GATE_MAJ3 / GATE_XOR3 on host rows: out[i] = gate(a[i], b[i], c[i]), one bootstrap per gate."""
         a, b, c = (np.ascontiguousarray(v, dtype=np.int32) for v in (a, b, c))
         assert a.shape == b.shape == c.shape and a.shape[-1] == self.params.n + 1
         out = np.zeros_like(a)
-        check(lib().ieache_gates3(self.h, gate_type, a.size // (self.params.n + 1), _i32(a), _i32(b), _i32(c), _i32(out),
-                                  C.byref(stats) if stats is not None else None))
+        check(lib().ieache_gates3(self.h, gate_type, a.size // (self.params.n + 1), _i32(a), _i32(b), _i32(c), _i32(out), _stats_ref(stats)))
         return out
 
     def gates3_device(self, gate_type, count, d_a, d_b, d_c, d_out, stats=None):
         check(lib().ieache_gates3_device(self.h, gate_type, count, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_c),
-                                         C.c_void_p(d_out), C.byref(stats) if stats is not None else None))
+                                         C.c_void_p(d_out), _stats_ref(stats)))
 
     @property
     def extract_stride(self):
@@ -546,15 +545,14 @@ class Context:
         assert of is None or of.shape[0] == x.shape[0]
         out = np.zeros((x.shape[0], (self.params.n if keyswitch else self.params.N) + 1), dtype=np.int32)
         check(lib().ieache_pbs(self.h, x.shape[0], _i32(x), _i32(tv), tv.shape[0], None if of is None else _i32(of), _i32(out),
-                               0 if keyswitch else PBS_NO_KEYSWITCH, C.byref(stats) if stats is not None else None))
+                               0 if keyswitch else PBS_NO_KEYSWITCH, _stats_ref(stats)))
         return out
 
     def pbs_device(self, count, d_x, d_test_polys, n_polys, d_poly_of, d_out, keyswitch=True, stats=None):
         """Device pointers (ints; d_poly_of may be None / 0): x rows of lwe_stride, test polynomials [n_polys][N] packed, out rows of
         lwe_stride or, with keyswitch=False, of extract_stride."""
         check(lib().ieache_pbs_device(self.h, count, C.c_void_p(d_x), C.c_void_p(d_test_polys), int(n_polys),
-                                      C.c_void_p(d_poly_of or None), C.c_void_p(d_out), 0 if keyswitch else PBS_NO_KEYSWITCH,
-                                      C.byref(stats) if stats is not None else None))
+                                      C.c_void_p(d_poly_of or None), C.c_void_p(d_out), 0 if keyswitch else PBS_NO_KEYSWITCH, _stats_ref(stats)))
 
     def pbs_multi(self, x, test_polys, factors, poly_of=None, bias=None, keyswitch=True, stats=None):
         """Multi-output programmable bootstrap on host rows: ONE blind rotation per row of x [count][n+1], as pbs does it, and
@@ -571,8 +569,7 @@ class Context:
         assert bi is None or bi.shape[0] == fa.shape[0]
         out = np.zeros((x.shape[0], fa.shape[0], (self.params.n if keyswitch else self.params.N) + 1), dtype=np.int32)
         check(lib().ieache_pbs_multi(self.h, x.shape[0], _i32(x), _i32(tv), tv.shape[0], None if of is None else _i32(of), _i32(fa),
-                                     fa.shape[0], None if bi is None else _i32(bi), _i32(out), 0 if keyswitch else PBS_NO_KEYSWITCH,
-                                     C.byref(stats) if stats is not None else None))
+                                     fa.shape[0], None if bi is None else _i32(bi), _i32(out), 0 if keyswitch else PBS_NO_KEYSWITCH, _stats_ref(stats)))
         return out
 
     def pbs_multi_device(self, count, d_x, d_test_polys, n_polys, d_poly_of, d_factors, n_factors, d_bias, d_out, keyswitch=True, stats=None):
@@ -580,21 +577,18 @@ class Context:
         factors [n_factors][N] packed, out [count * n_factors] rows of lwe_stride or, with keyswitch=False, of extract_stride."""
         check(lib().ieache_pbs_multi_device(self.h, count, C.c_void_p(d_x), C.c_void_p(d_test_polys), int(n_polys),
                                             C.c_void_p(d_poly_of or None), C.c_void_p(d_factors), int(n_factors), C.c_void_p(d_bias or None),
-                                            C.c_void_p(d_out), 0 if keyswitch else PBS_NO_KEYSWITCH,
-                                            C.byref(stats) if stats is not None else None))
+                                            C.c_void_p(d_out), 0 if keyswitch else PBS_NO_KEYSWITCH, _stats_ref(stats)))
 
     def mux(self, a, b, c, stats=None):
         """bootsMUX on host rows: out[i] = a[i] ? b[i] : c[i]."""
         a, b, c = (np.ascontiguousarray(v, dtype=np.int32) for v in (a, b, c))
         assert a.shape == b.shape == c.shape and a.shape[-1] == self.params.n + 1
         out = np.zeros_like(a)
-        check(lib().ieache_mux(self.h, a.size // (self.params.n + 1), _i32(a), _i32(b), _i32(c), _i32(out),
-                               C.byref(stats) if stats is not None else None))
+        check(lib().ieache_mux(self.h, a.size // (self.params.n + 1), _i32(a), _i32(b), _i32(c), _i32(out), _stats_ref(stats)))
         return out
 
     def mux_device(self, count, d_a, d_b, d_c, d_out, stats=None):
-        check(lib().ieache_mux_device(self.h, count, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_c), C.c_void_p(d_out),
-                                      C.byref(stats) if stats is not None else None))
+        check(lib().ieache_mux_device(self.h, count, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_c), C.c_void_p(d_out), _stats_ref(stats)))
 
     def debug_blind_rotate(self, x, steps=-1):
         x = np.ascontiguousarray(x, dtype=np.int32).reshape(-1, self.params.n + 1)

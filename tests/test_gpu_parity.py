@@ -899,6 +899,58 @@ def test_kernel_variants_agree_bit_for_bit(ia, gpu_ctx):
         ctx.set_option("no_such_knob", 1)
 
 
+def test_flat_mux_cuts_guard_and_audit(ia, gpu_ctx):
+    """A flat MUX call under everything a flat gate call goes through: odd and minimal chunks (pieces are whole gates: 3, 1 and
+    1 of them), the sampled audit, a guard repeat, the two-limb and the any-parameter kernels, an in-place device call and warm
+    staging rows.  37 gates = 74 blind rotations: a ragged last piece, and room for an audit's 64 consecutive items.  Every
+    row equals the oracle's bootsMUX.  (Companion of test_mux_gate_bit_exact; it stands here because it adds guard repeats and
+    an audit mismatch to the session's shared context, whose counts test_kernel_variants_agree_bit_for_bit reads from zero.)"""
+    import torch
+    kb, ctx = gpu_ctx(16, 1024)
+    rng = np.random.default_rng(37)
+    bits = rng.integers(0, 2, size=(3, 37)).astype(np.uint8)
+    a, b, c = kb.enc(bits[0], 84), kb.enc(bits[1], 85), kb.enc(bits[2], 86)
+    want = np.stack([kb.ck.mux(a[i], b[i], c[i]) for i in range(37)])
+    assert np.array_equal(kb.dec(want), np.where(bits[0] == 1, bits[1], bits[2]))
+    try:
+        for chunk, pieces in ((7, 13), (2, 37), (1, 37)):
+            ctx.set_chunk(chunk)
+            st = ia.Stats()
+            assert np.array_equal(ctx.mux(a, b, c, st), want), chunk
+            assert st.keyswitch_launches == pieces and st.bootstraps == 74, (chunk, st.keyswitch_launches, st.bootstraps)
+    finally:
+        ctx.set_chunk(16384)
+    reruns, base = ctx.fft_guard()[1], ctx.fft_audit()
+    try:
+        ctx.set_option("fft_audit", 1)
+        ctx.set_option("fft_audit_inject", 1)      # a differing audited row: the call repeats itself on the two-limb kernels
+        assert np.array_equal(ctx.mux(a, b, c), want)
+        assert ctx.fft_audit()["mismatches"] == base["mismatches"] + 1 and ctx.fft_guard()[1] == reruns + 1
+    finally:
+        ctx.set_option("fft_audit", 64)            # (the two injection hooks clear themselves when they have been used)
+    ctx.set_option("fft_guard_inject", 1)          # a tripped guard: one more repeat
+    assert np.array_equal(ctx.mux(a, b, c), want) and ctx.fft_guard()[1] == reruns + 2
+    try:
+        ctx.set_option("exact_fft", 1)
+        assert np.array_equal(ctx.mux(a, b, c), want) and ctx.fft_guard()[1] == reruns + 2
+    finally:
+        ctx.set_option("exact_fft", 0)
+    try:
+        ctx.force_generic(True)
+        assert np.array_equal(ctx.mux(a, b, c), want)
+    finally:
+        ctx.force_generic(False)
+    # in place, d_out == d_a: it could not be repeated, so it runs on the two-limb kernels from the start -- no rerun counted
+    d = [torch.zeros((37, ctx.lwe_stride), dtype=torch.int32, device="cuda") for _ in range(3)]
+    for t, rows in zip(d, (a, b, c)):
+        t[:, : rows.shape[1]] = torch.from_numpy(rows).cuda()
+    torch.cuda.synchronize()
+    ctx.mux_device(37, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[0].data_ptr())
+    assert np.array_equal(d[0].cpu().numpy()[:, : a.shape[1]], want) and ctx.fft_guard()[1] == reruns + 2
+    n0 = ctx.get_option("staging_allocations")    # the host calls above have grown the rows: a warm one allocates nothing
+    assert np.array_equal(ctx.mux(a, b, c), want) and ctx.get_option("staging_allocations") == n0
+
+
 def test_level_overlap_on_two_streams_same_bits(ia, gpu_ctx):
     """Option "overlap": a level of at least overlap_min gate instances is issued as pieces alternating between two streams of the
     context (own scratch per stream, one key copy, event join before the next level).  Same launches on the same gate instances:
