@@ -6,15 +6,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <new>
 #include <string>
-#include <tuple>
 #include <vector>
 
 #include "circuit.h"
+#include "circuit_cache.h"
 #include "cloud_run.h"
 #include "codec.h"
 #include "daemon.h"
@@ -26,9 +25,7 @@ using namespace ieache;
 
 struct ieache_ctx {
     std::unique_ptr<Evaluator> eval;
-    std::map<std::tuple<int, int, bool, int>, Circuit> circuits;  // (kind, bits, folded, level cap)
-    std::map<std::tuple<int, int, bool, int>, uint64_t> circuit_used;  // last use of each level-capped variant (LRU order)
-    uint64_t circuit_clock = 0;
+    CircuitCache circuits{3};  // a caller alternates between a few batch sizes, or toggles exact_fft per call (bench.py's exact leg)
     std::string variant;
     bool fold = false;           // "fold_constants"
     bool level_quantum = true;   // "level_quantum": batch-aware level widths for the slack-balanced circuits
@@ -149,53 +146,20 @@ std::string poly_of_error(const char* call, const int32_t* poly_of, size_t count
     return std::string();
 }
 
-const Circuit* get_circuit(ieache_ctx* ctx, int kind, int bits, size_t batch = 0) {
-    auto fetch = [&](int cap) -> const Circuit* {
-        auto key = std::make_tuple(kind, bits, ctx->fold, cap);
-        auto it = ctx->circuits.find(key);
-        if (it != ctx->circuits.end()) {
-            if (cap != 0) ctx->circuit_used[key] = ++ctx->circuit_clock;
-            return &it->second;
-        }
-        Circuit c;
-        if (!build_circuit(kind, bits, &c, true, ctx->fold, cap)) return nullptr;
-        if (cap != 0) {
-            // Bounded: the cap follows the batch size (and the kernel family: "exact_fft" changes the resident-gate count), and
-            // a variant of the wide multipliers is several MB, so at most kCappedVariants per (kind, width, folding) are kept.
-            // The least recently used one goes, and only once the new circuit exists -- a caller that alternates between two
-            // batch sizes or toggles exact_fft per call (bench.py's exact leg, the audit flows) rebuilds nothing.
-            constexpr size_t kCappedVariants = 3;
-            std::vector<std::tuple<int, int, bool, int>> mine;
-            for (const auto& kv : ctx->circuits) {
-                const auto& k = kv.first;
-                if (std::get<0>(k) == kind && std::get<1>(k) == bits && std::get<2>(k) == ctx->fold && std::get<3>(k) != 0) mine.push_back(k);
-            }
-            while (mine.size() >= kCappedVariants) {
-                size_t oldest = 0;
-                for (size_t i = 1; i < mine.size(); i++)
-                    if (ctx->circuit_used[mine[i]] < ctx->circuit_used[mine[oldest]]) oldest = i;
-                ctx->circuits.erase(mine[oldest]);
-                ctx->circuit_used.erase(mine[oldest]);
-                mine.erase(mine.begin() + oldest);
-            }
-            ctx->circuit_used[key] = ++ctx->circuit_clock;
-        }
-        return &ctx->circuits.emplace(key, std::move(c)).first->second;
-    };
-    const Circuit* base = fetch(0);
-    if (const char* e = getenv("IEACHE_LEVEL_CAP")) {  // measurement aid: force a level width (and with it the balanced schedule)
-        const int forced = atoi(e);
-        if (base && forced > 0) return fetch(forced);
-    }
-    if (!base || !ctx->level_quantum) return base;
-    // level width chosen so that a level x this batch is a whole number of the rounds of gates the GPU holds at once
-    // (same DAG, same output bits, another level assignment): the slack-balanced 64/128-bit multipliers at any batch
-    // below a round, the ASAP-scheduled 32-bit multiplier family at small batches (circuit_level_cap)
-    const int cap = circuit_level_cap(*base, (int64_t)batch, ctx->eval->resident_gates(), ctx->eval->resident_gates_two_wave());
-    const int mean = (int)((base->n_bootstraps + base->depth - 1) / base->depth);
-    if (cap <= 0 || (base->balanced_schedule && cap == mean)) return base;
-    const Circuit* capped = fetch(cap);
-    return capped && capped->balanced_schedule ? capped : base;
+const char* const kUnsupported = "unsupported circuit kind/bits";
+// The cached circuit a context evaluates `batch` expressions with.  Callers hold the pointer for the call: the evaluator keeps
+// no Circuit beyond it.  IEACHE_LEVEL_CAP is a measurement aid: it forces a level width (and with it the balanced schedule).
+CircuitCache::Ptr get_circuit(ieache_ctx* ctx, int kind, int bits, size_t batch) {
+    const char* forced = getenv("IEACHE_LEVEL_CAP");
+    return ctx->circuits.select(kind, bits, ctx->fold, (int64_t)batch, ctx->eval->resident_gates(), ctx->eval->resident_gates_two_wave(),
+                                ctx->level_quantum, forced ? atoi(forced) : 0);
+}
+// f(circuit) on a throw-away build of the circuit, or the refusal
+template <class F>
+int with_circuit(int kind, int bits, int fold_constants, int level_cap, F&& f) {
+    Circuit c;
+    if (!build_circuit(kind, bits, &c, true, fold_constants != 0, level_cap)) return fail(IEACHE_EINVAL, kUnsupported);
+    return f(c);
 }
 // the context is owned by a unique_ptr until it is handed to the caller, so a throwing key load
 // (or Evaluator constructor) releases it
@@ -381,10 +345,10 @@ const char* ieache_ctx_kernel_for_launch(const ieache_ctx* ctx, int64_t gates) {
 int ieache_circuit_info_get_ex(int kind, int bits, int fold_constants, ieache_circuit_info* out) {
     return guarded([&] {
         if (!out) return fail(IEACHE_EINVAL, "null argument");
-        Circuit c;
-        if (!build_circuit(kind, bits, &c, true, fold_constants != 0)) return fail(IEACHE_EINVAL, "unsupported circuit kind/bits");
-        fill_info(c, fold_constants != 0, out);
-        return 0;
+        return with_circuit(kind, bits, fold_constants, 0, [&](const Circuit& c) {
+            fill_info(c, fold_constants != 0, out);
+            return 0;
+        });
     });
 }
 // The 0.1 entry point: its callers were compiled against the 56-byte struct (through `folded`), so it writes exactly that
@@ -401,48 +365,46 @@ int ieache_circuit_info_get(int kind, int bits, ieache_circuit_info* out) {
 int ieache_ctx_circuit_level_cap(const ieache_ctx* ctx, int kind, int bits, int64_t batch) {
     return guarded([&] {
         if (!ctx) return fail(IEACHE_EINVAL, "null context");
-        Circuit c;
-        if (!build_circuit(kind, bits, &c, true, ctx->fold)) return fail(IEACHE_EINVAL, "unsupported circuit kind/bits");
-        return (int)circuit_level_cap(c, batch, ctx->eval->resident_gates(), ctx->eval->resident_gates_two_wave());
+        return with_circuit(kind, bits, ctx->fold, 0, [&](const Circuit& c) {
+            return (int)circuit_level_cap(c, batch, ctx->eval->resident_gates(), ctx->eval->resident_gates_two_wave());
+        });
     });
 }
 
 int ieache_circuit_level_cap(int kind, int bits, int fold_constants, int64_t batch, int resident_workgroups) {
     return guarded([&] {
-        Circuit c;
-        if (!build_circuit(kind, bits, &c, true, fold_constants != 0)) return fail(IEACHE_EINVAL, "unsupported circuit kind/bits");
-        return (int)circuit_level_cap(c, batch, resident_workgroups);
+        return with_circuit(kind, bits, fold_constants, 0, [&](const Circuit& c) { return (int)circuit_level_cap(c, batch, resident_workgroups); });
     });
 }
 
 int ieache_circuit_info_get_cap(int kind, int bits, int fold_constants, int level_cap, ieache_circuit_info* out) {
     return guarded([&] {
         if (!out || level_cap < 0) return fail(IEACHE_EINVAL, "bad argument");
-        Circuit c;
-        if (!build_circuit(kind, bits, &c, true, fold_constants != 0, level_cap)) return fail(IEACHE_EINVAL, "unsupported circuit kind/bits");
-        fill_info(c, fold_constants != 0, out);
-        out->level_cap = c.balanced_schedule ? level_cap : 0;
-        return 0;
+        return with_circuit(kind, bits, fold_constants, level_cap, [&](const Circuit& c) {
+            fill_info(c, fold_constants != 0, out);
+            out->level_cap = c.balanced_schedule ? level_cap : 0;
+            return 0;
+        });
     });
 }
 
 int ieache_circuit_simulate_cap(int kind, int bits, int fold_constants, int level_cap, const uint8_t* in_bits, uint8_t* out_bits) {
     return guarded([&] {
         if (!in_bits || !out_bits || level_cap < 0) return fail(IEACHE_EINVAL, "bad argument");
-        Circuit c;
-        if (!build_circuit(kind, bits, &c, true, fold_constants != 0, level_cap)) return fail(IEACHE_EINVAL, "unsupported circuit kind/bits");
-        simulate_circuit(c, in_bits, out_bits);
-        return 0;
+        return with_circuit(kind, bits, fold_constants, level_cap, [&](const Circuit& c) {
+            simulate_circuit(c, in_bits, out_bits);
+            return 0;
+        });
     });
 }
 
 int ieache_circuit_simulate_ex(int kind, int bits, int fold_constants, const uint8_t* in_bits, uint8_t* out_bits) {
     return guarded([&] {
         if (!in_bits || !out_bits) return fail(IEACHE_EINVAL, "null argument");
-        Circuit c;
-        if (!build_circuit(kind, bits, &c, true, fold_constants != 0)) return fail(IEACHE_EINVAL, "unsupported circuit kind/bits");
-        simulate_circuit(c, in_bits, out_bits);
-        return 0;
+        return with_circuit(kind, bits, fold_constants, 0, [&](const Circuit& c) {
+            simulate_circuit(c, in_bits, out_bits);
+            return 0;
+        });
     });
 }
 int ieache_circuit_simulate(int kind, int bits, const uint8_t* in_bits, uint8_t* out_bits) {
@@ -453,8 +415,8 @@ int ieache_eval_batch(ieache_ctx* ctx, int kind, int bits, size_t batch, const i
                       ieache_stats* stats) {
     return guarded([&] {
         if (!ctx || !in_lwe || !out_lwe) return fail(IEACHE_EINVAL, "null argument");
-        const Circuit* c = get_circuit(ctx, kind, bits, batch);
-        if (!c) return fail(IEACHE_EINVAL, "unsupported circuit kind/bits");
+        const CircuitCache::Ptr c = get_circuit(ctx, kind, bits, batch);
+        if (!c) return fail(IEACHE_EINVAL, kUnsupported);
         return with_stats(stats, [&](EvalStats* st) { eval_circuit_host(*ctx->eval, *c, batch, in_lwe, out_lwe, st); });
     });
 }
@@ -463,8 +425,8 @@ int ieache_eval_batch_device(ieache_ctx* ctx, int kind, int bits, size_t batch, 
                              ieache_stats* stats) {
     return guarded([&] {
         if (!ctx || !d_in || !d_out) return fail(IEACHE_EINVAL, "null argument");
-        const Circuit* c = get_circuit(ctx, kind, bits, batch);
-        if (!c) return fail(IEACHE_EINVAL, "unsupported circuit kind/bits");
+        const CircuitCache::Ptr c = get_circuit(ctx, kind, bits, batch);
+        if (!c) return fail(IEACHE_EINVAL, kUnsupported);
         require_device_pointers(batch, {{d_in, "d_in"}, {d_out, "d_out"}});
         return with_stats(stats, [&](EvalStats* st) { ctx->eval->eval_circuit_device(*c, batch, d_in, d_out, st); });
     });
@@ -473,8 +435,8 @@ int ieache_eval_batch_device(ieache_ctx* ctx, int kind, int bits, size_t batch, 
 int ieache_prepare_batch(ieache_ctx* ctx, int kind, int bits, size_t batch) {
     return guarded([&] {
         if (!ctx) return fail(IEACHE_EINVAL, "null argument");
-        const Circuit* c = get_circuit(ctx, kind, bits, batch);
-        if (!c) return fail(IEACHE_EINVAL, "unsupported circuit kind/bits");
+        const CircuitCache::Ptr c = get_circuit(ctx, kind, bits, batch);
+        if (!c) return fail(IEACHE_EINVAL, kUnsupported);
         ctx->eval->prepare_circuit(*c, batch);
         return 0;
     });
@@ -521,10 +483,10 @@ int64_t ieache_netlist_gate_count(const ieache_netlist* nl, int gate_type) {
 int64_t ieache_circuit_gate_count(int kind, int bits, int fold_constants, int gate_type) {
     int64_t n = 0;
     const int rc = guarded([&] {
-        Circuit c;
-        if (!build_circuit(kind, bits, &c, true, fold_constants != 0)) return fail(IEACHE_EINVAL, "unsupported circuit kind/bits");
-        n = c.count_of(gate_type);
-        return n < 0 ? fail(IEACHE_EINVAL, "unknown gate type") : 0;
+        return with_circuit(kind, bits, fold_constants, 0, [&](const Circuit& c) {
+            n = c.count_of(gate_type);
+            return n < 0 ? fail(IEACHE_EINVAL, "unknown gate type") : 0;
+        });
     });
     return rc != 0 ? rc : n;
 }

@@ -1,6 +1,8 @@
 // See circuit.h.  Every builder function cites the cloud.c lines it mirrors.
 #include "circuit.h"
 
+#include "../../include/ieache.h"
+
 #include <algorithm>
 #include <cassert>
 #include <cstdlib>
@@ -9,6 +11,13 @@
 #include <utility>
 
 namespace ieache {
+
+// f(wire) for every operand of a gate that is a wire (not a constant); an unused third operand is the constant 0
+template <class F>
+static void for_each_wire(const Gate& g, F&& f) {
+    for (const Ref* r : {&g.a, &g.b, &g.c})
+        if (r->id >= 0) f(r->id);
+}
 
 CircuitBuilder::CircuitBuilder(int32_t n_inputs, bool fold)
     : n_inputs_(n_inputs), next_wire_(n_inputs), fold_(fold), wire_level_(n_inputs, 0) {}
@@ -28,6 +37,11 @@ Ref CircuitBuilder::gate(int32_t type, Ref a, Ref b) {
     if (a.id == kUndefId || b.id == kUndefId)
         throw std::logic_error("gate consumes a never-written sample");
     if (type < 0 || type >= GATE_TYPES || type == GATE_MUX) throw std::invalid_argument("not a two-input gate type");
+    n_requested_++;
+    return gate2(type, a, b);
+}
+
+Ref CircuitBuilder::gate2(int32_t type, Ref a, Ref b) {
     const int32_t requested = type;
     // boot-gates.cpp: NOR / ANDNY / ANDYN / ORNY / ORYN are AND / OR of +-ca, +-cb -- recorded as such (the sign flags
     // of the operands), which is the same linear combination word for word
@@ -39,7 +53,6 @@ Ref CircuitBuilder::gate(int32_t type, Ref a, Ref b) {
         case GATE_ORYN: type = GATE_OR; b.neg = !b.neg; break;
         default: break;
     }
-    n_requested_++;
     bool out_neg = false;
     if (fold_ && (type == GATE_AND || type == GATE_XOR)) {
         const bool ca = a.id == kConstId, cb = b.id == kConstId;
@@ -55,23 +68,8 @@ Ref CircuitBuilder::gate(int32_t type, Ref a, Ref b) {
             a.neg = b.neg = false;
         }
         if (a.id > b.id) std::swap(a, b);  // both gates commute
-        const auto key = std::make_tuple(type, a.id, (int32_t)a.neg, b.id, (int32_t)b.neg, kUndefId, 0);
-        const auto it = known_.find(key);
-        if (it != known_.end()) return Ref{it->second, out_neg};
-        known_[key] = next_wire_;
     }
-    const int32_t la = a.id >= 0 ? wire_level_[a.id] : 0;
-    const int32_t lb = b.id >= 0 ? wire_level_[b.id] : 0;
-    Gate g;
-    g.type = type;
-    g.a = a;
-    g.b = b;
-    g.out = next_wire_++;
-    g.level = std::max(la, lb) + 1;
-    wire_level_.push_back(g.level);
-    gates_.push_back(g);
-    requested_type_.push_back(requested);
-    return Ref{g.out, out_neg};
+    return Ref{record(type, requested, a, b, constant(0)), out_neg};
 }
 
 // bootsMUX(a, b, c) = a ? b : c.  Recorded as given: no folding, no sharing.
@@ -93,9 +91,9 @@ Ref CircuitBuilder::gate3(int32_t type, Ref a, Ref b, Ref c) {
                     break;
                 }
         if (same >= 0 && !fold_) throw std::invalid_argument("a three-input gate names the same wire twice");
+        n_requested_++;
         if (fold_) {
             if (same >= 0) {  // MAJ3(x,x,z) = x ; MAJ3(x,~x,z) = z ; XOR3(x,x,z) = z ; XOR3(x,~x,z) = ~z
-                n_requested_++;
                 const Ref z = r[3 - same - same2];
                 const bool equal = r[same].neg == r[same2].neg;
                 if (type == GATE_MAJ3) return equal ? r[same] : z;
@@ -106,15 +104,14 @@ Ref CircuitBuilder::gate3(int32_t type, Ref a, Ref b, Ref c) {
                     const Ref x = r[(i + 1) % 3], y = r[(i + 2) % 3];
                     const bool k = r[i].neg;
                     if (type == GATE_XOR3) {
-                        const Ref t = gate(GATE_XOR, x, y);  // XOR3(x,y,1) = XNOR(x,y) = NOT XOR(x,y): the negation is free
+                        const Ref t = gate2(GATE_XOR, x, y);  // XOR3(x,y,1) = XNOR(x,y) = NOT XOR(x,y): the negation is free
                         return Ref{t.id, t.neg != k};
                     }
                     if (x.id == kConstId || y.id == kConstId) {  // MAJ3(x, k', k) = k when k' == k, else x
-                        n_requested_++;
                         const Ref w = x.id == kConstId ? y : x, k2 = x.id == kConstId ? x : y;
                         return k2.neg == k ? constant(k) : w;
                     }
-                    return gate(k ? GATE_OR : GATE_AND, x, y);
+                    return gate2(k ? GATE_OR : GATE_AND, x, y);
                 }
             // share: both gates are symmetric; XOR3's operand negations move to the output
             std::sort(r, r + 3, [](const Ref& p, const Ref& q) { return p.id < q.id; });
@@ -124,30 +121,31 @@ Ref CircuitBuilder::gate3(int32_t type, Ref a, Ref b, Ref c) {
                     q.neg = false;
                 }
             a = r[0], b = r[1], c = r[2];
-            const auto key = std::make_tuple(type, a.id, (int32_t)a.neg, b.id, (int32_t)b.neg, c.id, (int32_t)c.neg);
-            const auto it = known_.find(key);
-            if (it != known_.end()) {
-                n_requested_++;
-                return Ref{it->second, out_neg};
-            }
-            known_[key] = next_wire_;
         }
+    } else {
+        n_requested_++;
     }
-    n_requested_++;
-    int32_t lv = 0;
-    for (const Ref& r : {a, b, c})
-        if (r.id >= 0) lv = std::max(lv, wire_level_[r.id]);
+    return Ref{record(type, type, a, b, c), out_neg};
+}
+
+int32_t CircuitBuilder::record(int32_t type, int32_t requested, Ref a, Ref b, Ref c) {
+    if (fold_ && (type == GATE_AND || type == GATE_XOR || is_gate3(type))) {  // the gates that share (a MUX is recorded as given)
+        const auto key = std::make_tuple(type, a.id, (int32_t)a.neg, b.id, (int32_t)b.neg, c.id, (int32_t)c.neg);
+        const auto it = known_.emplace(key, next_wire_);
+        if (!it.second) return it.first->second;
+    }
     Gate g;
     g.type = type;
     g.a = a;
     g.b = b;
     g.c = c;
     g.out = next_wire_++;
-    g.level = lv + 1;
+    g.level = 1;
+    for_each_wire(g, [&](int32_t w) { g.level = std::max(g.level, wire_level_[w] + 1); });
     wire_level_.push_back(g.level);
     gates_.push_back(g);
-    requested_type_.push_back(type);
-    return Ref{g.out, out_neg};
+    requested_type_.push_back(requested);
+    return g.out;
 }
 
 // cloud.c:18-51.  carry-in is c[0] (bootsCOPY :24); carry-out lands in
@@ -224,139 +222,136 @@ void CircuitBuilder::mul32(Word& result, Word& result2, const Word& a, const Wor
                            const Word& carry, int32_t nb_bits) {
     mul_words({&result, &result2}, {&a}, b, carry, nb_bits);
 }
-void CircuitBuilder::mul64(Word& r, Word& r2, Word& r3, const Word& a, const Word& b, const Word& c,
-                           const Word& carry, int32_t nb_bits) {
-    mul_words({&r, &r2, &r3}, {&a, &b}, c, carry, nb_bits);
-}
-void CircuitBuilder::mul128(Word& r, Word& r2, Word& r3, Word& r4, Word& r5, const Word& a,
-                            const Word& b, const Word& c, const Word& d, const Word& e,
-                            const Word& carry, int32_t nb_bits) {
-    mul_words({&r, &r2, &r3, &r4, &r5}, {&a, &b, &c, &d}, e, carry, nb_bits);
-}
 
-Circuit finalize_circuit(const std::string& name, const CircuitBuilder& b, const Word& outputs, bool balanced, int32_t level_cap) {
-    Circuit c;
-    c.name = name;
-    c.n_inputs = b.n_inputs();
-    const auto& gates = b.gates();
-    const int32_t n_wires = b.n_wires();
-    int32_t depth = 0;  // ASAP depth; becomes the scheduled depth below when a level cap stretches the schedule
-    for (const Gate& g : gates) depth = std::max(depth, g.level);
-    c.depth = depth;
-    // widths and counts are in blind rotations: a MUX is two (level_items.h)
-    auto cost = [](const Gate& g) { return g.type == GATE_MUX ? 2 : 1; };
+// widths and counts are in blind rotations: a MUX is two (level_items.h)
+static int32_t cost(const Gate& g) { return g.type == GATE_MUX ? 2 : 1; }
+
+// (a) ASAP statistics: depth, the widest ASAP level, blind rotations in all
+struct AsapStats {
+    int32_t depth = 0, max_width = 0;
     int64_t n_rot = 0;
-    for (const Gate& g : gates) n_rot += cost(g);
-    c.n_bootstraps = n_rot;
-
-    // ASAP statistics: width of each ASAP level
-    {
-        std::vector<int32_t> w(depth + 1, 0);
-        for (const Gate& g : gates) w[g.level] += cost(g);
-        for (int32_t L = 1; L <= depth; L++) c.max_width = std::max(c.max_width, w[L]);
+};
+static AsapStats asap_stats(const std::vector<Gate>& gates) {
+    AsapStats s;
+    for (const Gate& g : gates) {
+        s.depth = std::max(s.depth, g.level);
+        s.n_rot += cost(g);
     }
-    // Execution schedule.  ASAP piles every gate with slack into the earliest level (all 1024
-    // ANDs of mul32 land in level 1) and leaves the carry chains as levels of 2-3 gates.  The
-    // executor instead runs a slack-aware list schedule over the same number of levels: a gate
-    // on the critical path runs at its ASAP = ALAP level, the others are spread, least slack
-    // first, to keep every level near the mean width.  Narrow levels fill up (what matters when
-    // the batch is small) and the wire store shrinks (mul128: 16 800 -> 2 921 rows per
-    // expression).  The DAG, and therefore every output bit, is unchanged.
+    std::vector<int32_t> w(s.depth + 1, 0);
+    for (const Gate& g : gates) w[g.level] += cost(g);
+    for (int32_t L = 1; L <= s.depth; L++) s.max_width = std::max(s.max_width, w[L]);
+    return s;
+}
+
+// (b) The execution schedule.  ASAP piles every gate with slack into the earliest level (all 1024
+// ANDs of mul32 land in level 1) and leaves the carry chains as levels of 2-3 gates.  The
+// executor instead runs a slack-aware list schedule over the same number of levels: a gate
+// on the critical path runs at its ASAP = ALAP level, the others are spread, least slack
+// first, to keep every level near the mean width.  Narrow levels fill up (what matters when
+// the batch is small) and the wire store shrinks (mul128: 16 800 -> 2 921 rows per
+// expression).  The DAG, and therefore every output bit, is unchanged.
+// depth > 0: the ASAP depth.  -> (level of every gate, levels the executor runs)
+static std::pair<std::vector<int32_t>, int32_t> list_schedule(const std::vector<Gate>& gates, int32_t n_wires, int32_t depth, int64_t n_rot,
+                                                              int32_t level_cap) {
+    // Forward list scheduling: a gate is ready one level after its last operand; a gate
+    // whose ALAP level is the current level must run now, the others fill the level up to
+    // the mean width, least slack first.  (A backward, as-late-as-possible pass was tried:
+    // with no spare capacity it starves low-ASAP gates and piles them into the first levels.)
     const int32_t n_gates = (int32_t)gates.size();
     std::vector<int32_t> sched(n_gates, 0);
-    if (balanced && depth > 0) {
-        // Forward list scheduling: a gate is ready one level after its last operand; a gate
-        // whose ALAP level is the current level must run now, the others fill the level up to
-        // the mean width, least slack first.  (A backward, as-late-as-possible pass was tried:
-        // with no spare capacity it starves low-ASAP gates and piles them into the first levels.)
-        std::vector<int32_t> producer(n_wires, -1);  // wire -> gate index
-        for (int32_t i = 0; i < n_gates; i++) producer[gates[i].out] = i;
-        std::vector<std::vector<int32_t>> users(n_gates);
-        std::vector<int32_t> n_operands(n_gates, 0);
+    std::vector<int32_t> producer(n_wires, -1);  // wire -> gate index
+    for (int32_t i = 0; i < n_gates; i++) producer[gates[i].out] = i;
+    // f(producing gate) for every operand of gate i that a gate produces
+    auto for_each_producer = [&](int32_t i, auto&& f) {
+        for_each_wire(gates[i], [&](int32_t w) {
+            if (producer[w] >= 0) f(producer[w]);
+        });
+    };
+    std::vector<std::vector<int32_t>> users(n_gates);
+    std::vector<int32_t> n_operands(n_gates, 0);
+    for (int32_t i = 0; i < n_gates; i++)
+        for_each_producer(i, [&](int32_t p) {
+            users[p].push_back(i);
+            n_operands[i]++;
+        });
+    // level_cap > 0 (the caller knows the batch): levels of exactly that many gates, so that a level times
+    // the batch is a whole number of the workgroup rounds the GPU holds at once.  A cap under the mean width
+    // cannot fit the ASAP depth: the schedule is then stretched (more levels, each of them full), which is the
+    // better trade whenever a level is a few rounds wide -- 1.2 rounds cost 2.
+    const int32_t mean = (int32_t)std::max<int64_t>((n_rot + depth - 1) / depth, 1);
+    const int32_t cap = level_cap > 0 ? level_cap : mean;
+    int32_t sched_depth = depth;
+    if (cap < mean) sched_depth = std::max<int32_t>(depth, (int32_t)((n_rot + cap - 1) / cap));
+    for (;; sched_depth += std::max(1, sched_depth / 50)) {
+        std::vector<int32_t> alap(n_gates, sched_depth);
+        for (int32_t i = n_gates - 1; i >= 0; i--)  // builder order is topological
+            for_each_producer(i, [&](int32_t p) { alap[p] = std::min(alap[p], alap[i] - 1); });
+        std::vector<int32_t> pending = n_operands;
+        auto cmp = [&](int32_t x, int32_t y) { return alap[x] != alap[y] ? alap[x] > alap[y] : x > y; };  // min-heap on ALAP
+        std::priority_queue<int32_t, std::vector<int32_t>, decltype(cmp)> ready(cmp);
+        std::vector<int32_t> next_ready;
         for (int32_t i = 0; i < n_gates; i++)
-            for (const Ref& r : {gates[i].a, gates[i].b, gates[i].c})
-                if (r.id >= 0 && producer[r.id] >= 0) {
-                    users[producer[r.id]].push_back(i);
-                    n_operands[i]++;
+            if (pending[i] == 0) ready.push(i);
+        int32_t done = 0, overflowing = 0;  // levels in which critical gates had to exceed the cap
+        for (int32_t L = 1; L <= sched_depth; L++) {
+            int32_t taken = 0;
+            bool over = false;
+            next_ready.clear();
+            while (!ready.empty()) {
+                const int32_t g = ready.top();
+                // only critical gates may exceed the cap (a MUX that starts under it may end one rotation over)
+                if (alap[g] > L && taken >= cap) break;
+                if (taken >= cap && !over) {
+                    overflowing++;
+                    over = true;
                 }
-        // level_cap > 0 (the caller knows the batch): levels of exactly that many gates, so that a level times
-        // the batch is a whole number of the workgroup rounds the GPU holds at once.  A cap under the mean width
-        // cannot fit the ASAP depth: the schedule is then stretched (more levels, each of them full), which is the
-        // better trade whenever a level is a few rounds wide -- 1.2 rounds cost 2.
-        const int32_t mean = (int32_t)std::max<int64_t>((n_rot + depth - 1) / depth, 1);
-        const int32_t cap = level_cap > 0 ? level_cap : mean;
-        int32_t sched_depth = depth;
-        if (cap < mean) sched_depth = std::max<int32_t>(depth, (int32_t)((n_rot + cap - 1) / cap));
-        for (;; sched_depth += std::max(1, sched_depth / 50)) {
-            std::vector<int32_t> alap(n_gates, sched_depth);
-            for (int32_t i = n_gates - 1; i >= 0; i--)  // builder order is topological
-                for (const Ref& r : {gates[i].a, gates[i].b, gates[i].c})
-                    if (r.id >= 0 && producer[r.id] >= 0) alap[producer[r.id]] = std::min(alap[producer[r.id]], alap[i] - 1);
-            std::vector<int32_t> pending = n_operands;
-            auto cmp = [&](int32_t x, int32_t y) { return alap[x] != alap[y] ? alap[x] > alap[y] : x > y; };  // min-heap on ALAP
-            std::priority_queue<int32_t, std::vector<int32_t>, decltype(cmp)> ready(cmp);
-            std::vector<int32_t> next_ready;
-            for (int32_t i = 0; i < n_gates; i++)
-                if (pending[i] == 0) ready.push(i);
-            int32_t done = 0, overflowing = 0;  // levels in which critical gates had to exceed the cap
-            for (int32_t L = 1; L <= sched_depth; L++) {
-                int32_t taken = 0;
-                bool over = false;
-                next_ready.clear();
-                while (!ready.empty()) {
-                    const int32_t g = ready.top();
-                    // only critical gates may exceed the cap (a MUX that starts under it may end one rotation over)
-                    if (alap[g] > L && taken >= cap) break;
-                    if (taken >= cap && !over) {
-                        overflowing++;
-                        over = true;
-                    }
-                    ready.pop();
-                    sched[g] = L;
-                    taken += cost(gates[g]);
-                    done++;
-                    for (int32_t u : users[g])
-                        if (--pending[u] == 0) next_ready.push_back(u);  // usable from the next level on
-                }
-                for (int32_t u : next_ready) ready.push(u);
+                ready.pop();
+                sched[g] = L;
+                taken += cost(gates[g]);
+                done++;
+                for (int32_t u : users[g])
+                    if (--pending[u] == 0) next_ready.push_back(u);  // usable from the next level on
             }
-            // a stretched schedule is accepted once (almost) every level respects the cap: a level over it costs a
-            // whole extra round for a few gates
-            if (done == n_gates && !(level_cap > 0 && cap < mean && overflowing * 50 > sched_depth)) break;
-            if (sched_depth > 4 * depth + n_gates) throw std::logic_error("list scheduling left gates unscheduled");
+            for (int32_t u : next_ready) ready.push(u);
         }
-        depth = sched_depth;  // levels the executor runs; c.depth keeps the ASAP depth
-    } else {
-        for (int32_t i = 0; i < n_gates; i++) sched[i] = gates[i].level;
+        // a stretched schedule is accepted once (almost) every level respects the cap: a level over it costs a
+        // whole extra round for a few gates
+        if (done == n_gates && !(level_cap > 0 && cap < mean && overflowing * 50 > sched_depth)) break;
+        if (sched_depth > 4 * depth + n_gates) throw std::logic_error("list scheduling left gates unscheduled");
     }
+    return {std::move(sched), sched_depth};
+}
 
-    // order gates by scheduled level (stable: keeps the reference's program order inside a level)
+// (c) Gates ordered by scheduled level (stable: keeps the reference's program order inside a level), the MUX gates of a level
+// after its other gates: the executor's item arithmetic relies on it (level_items.h).  Fills level_offset, level_mux and
+// sched_max_width.  -> the order
+static std::vector<int32_t> order_levels(const std::vector<Gate>& gates, const std::vector<int32_t>& sched, int32_t depth, Circuit* c) {
     std::vector<int32_t> order(gates.size());
     for (size_t i = 0; i < order.size(); i++) order[i] = (int32_t)i;
-    // ... with the MUX gates of a level after its two-input gates: the executor's item arithmetic relies on it (level_items.h)
     std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
         return sched[x] != sched[y] ? sched[x] < sched[y] : (gates[x].type == GATE_MUX) < (gates[y].type == GATE_MUX);
     });
-    c.level_offset.assign(depth + 1, 0);
-    c.level_mux.assign(depth, 0);
-    for (int32_t i = 0; i < n_gates; i++) {
-        c.level_offset[sched[i]]++;
-        if (gates[i].type == GATE_MUX) c.level_mux[sched[i] - 1]++;
+    c->level_offset.assign(depth + 1, 0);
+    c->level_mux.assign(depth, 0);
+    for (size_t i = 0; i < gates.size(); i++) {
+        c->level_offset[sched[i]]++;
+        if (gates[i].type == GATE_MUX) c->level_mux[sched[i] - 1]++;
     }
     for (int32_t L = 1; L <= depth; L++) {
-        c.sched_max_width = std::max(c.sched_max_width, c.level_offset[L] + c.level_mux[L - 1]);  // in blind rotations
-        c.level_offset[L] += c.level_offset[L - 1];
+        c->sched_max_width = std::max(c->sched_max_width, c->level_offset[L] + c->level_mux[L - 1]);  // in blind rotations
+        c->level_offset[L] += c->level_offset[L - 1];
     }
+    return order;
+}
 
+// (d) Liveness and slot allocation: fills n_slots, gates (in `order`) and outputs.
+static void allocate_slots(const std::vector<Gate>& gates, const std::vector<int32_t>& sched, const std::vector<int32_t>& order, int32_t n_wires,
+                           const Word& outputs, Circuit* c) {
     // liveness: last level at which each wire is read; outputs live forever
-    const int32_t kForever = depth + 1;
+    const int32_t depth = c->n_levels(), kForever = depth + 1;
     std::vector<int32_t> last_use(n_wires, 0);
-    for (int32_t i = 0; i < n_gates; i++) {
-        const Gate& g = gates[i];
-        if (g.a.id >= 0) last_use[g.a.id] = std::max(last_use[g.a.id], sched[i]);
-        if (g.b.id >= 0) last_use[g.b.id] = std::max(last_use[g.b.id], sched[i]);
-        if (g.c.id >= 0) last_use[g.c.id] = std::max(last_use[g.c.id], sched[i]);
-    }
+    for (size_t i = 0; i < gates.size(); i++)
+        for_each_wire(gates[i], [&](int32_t w) { last_use[w] = std::max(last_use[w], sched[i]); });
     for (const Ref& r : outputs) {
         if (r.id == kUndefId) throw std::logic_error("circuit output was never written");
         if (r.id >= 0) last_use[r.id] = kForever;
@@ -367,16 +362,17 @@ Circuit finalize_circuit(const std::string& name, const CircuitBuilder& b, const
     std::vector<int32_t> slot_of(n_wires, -1);
     std::vector<int32_t> free_slots;
     std::vector<std::vector<int32_t>> dying(depth + 2);
-    int32_t n_slots = c.n_inputs;
-    for (int32_t w = 0; w < c.n_inputs; w++) {
+    int32_t n_slots = c->n_inputs;
+    for (int32_t w = 0; w < c->n_inputs; w++) {
         slot_of[w] = w;
         dying[last_use[w]].push_back(w);
     }
     for (int32_t w : dying[0]) free_slots.push_back(slot_of[w]);
-    c.gates.resize(gates.size());
+    auto slot = [&](const Ref& r) { return r.id >= 0 ? slot_of[r.id] : -1; };
+    c->gates.resize(gates.size());
     size_t pos = 0;
     for (int32_t L = 1; L <= depth; L++) {
-        const size_t end = (size_t)c.level_offset[L];
+        const size_t end = (size_t)c->level_offset[L];
         for (; pos < end; pos++) {
             const Gate& g = gates[order[pos]];
             int32_t s;
@@ -388,32 +384,137 @@ Circuit finalize_circuit(const std::string& name, const CircuitBuilder& b, const
             }
             slot_of[g.out] = s;
             dying[last_use[g.out] == 0 ? L : last_use[g.out]].push_back(g.out);  // unread wires die at once
-            DevGate& d = c.gates[pos];
+            DevGate& d = c->gates[pos];
             d.type = g.type;
-            d.a_slot = g.a.id >= 0 ? slot_of[g.a.id] : -1;
+            d.a_slot = slot(g.a);
             d.a_neg = g.a.neg;
-            d.b_slot = g.b.id >= 0 ? slot_of[g.b.id] : -1;
+            d.b_slot = slot(g.b);
             d.b_neg = g.b.neg;
             d.out_slot = s;
-            d.c_slot = g.c.id >= 0 ? slot_of[g.c.id] : -1;
+            d.c_slot = slot(g.c);
             d.c_neg = g.type == GATE_MUX || is_gate3(g.type) ? (int32_t)g.c.neg : 0;
-            const int32_t requested = b.requested_types()[order[pos]];
-            if (requested < GATE_TYPES) c.n_by_type[requested]++;
-            if (requested == GATE_MAJ3) c.n_maj3++;
-            if (requested == GATE_XOR3) c.n_xor3++;
-            if (g.type == GATE_AND) c.n_and++;
-            if (g.type == GATE_XOR) c.n_xor++;
         }
         for (int32_t w : dying[L]) free_slots.push_back(slot_of[w]);
     }
-    c.n_slots = n_slots;
-    c.outputs.resize(outputs.size());
+    c->n_slots = n_slots;
+    c->outputs.resize(outputs.size());
     for (size_t i = 0; i < outputs.size(); i++) {
-        c.outputs[i].slot = outputs[i].id >= 0 ? slot_of[outputs[i].id] : -1;
-        c.outputs[i].neg = outputs[i].neg;
+        c->outputs[i].slot = slot(outputs[i]);
+        c->outputs[i].neg = outputs[i].neg;
     }
+}
+
+// (e) gates by the type they were requested as, and the recorded ANDs and XORs
+static void count_types(const CircuitBuilder& b, Circuit* c) {
+    for (int32_t requested : b.requested_types()) {
+        if (requested < GATE_TYPES) c->n_by_type[requested]++;
+        if (requested == GATE_MAJ3) c->n_maj3++;
+        if (requested == GATE_XOR3) c->n_xor3++;
+    }
+    for (const Gate& g : b.gates()) {
+        if (g.type == GATE_AND) c->n_and++;
+        if (g.type == GATE_XOR) c->n_xor++;
+    }
+}
+
+Circuit finalize_circuit(const std::string& name, const CircuitBuilder& b, const Word& outputs, bool balanced, int32_t level_cap) {
+    Circuit c;
+    c.name = name;
+    c.n_inputs = b.n_inputs();
+    const std::vector<Gate>& gates = b.gates();
+    const AsapStats asap = asap_stats(gates);
+    c.depth = asap.depth;  // stays the ASAP depth when a level cap stretches the schedule
+    c.max_width = asap.max_width;
+    c.n_bootstraps = asap.n_rot;
+    std::vector<int32_t> sched(gates.size());
+    int32_t levels = asap.depth;
+    if (balanced && asap.depth > 0)
+        std::tie(sched, levels) = list_schedule(gates, b.n_wires(), asap.depth, asap.n_rot, level_cap);
+    else
+        for (size_t i = 0; i < gates.size(); i++) sched[i] = gates[i].level;
+    const std::vector<int32_t> order = order_levels(gates, sched, levels, &c);
+    allocate_slots(gates, sched, order, b.n_wires(), outputs, &c);
+    count_types(b, &c);
     return c;
 }
+
+// ---- what each plain kind is: one row per code.  Adding a kind: a row here, its builder function (and build_stage's call of it
+// if it is not one of the adder families), one line in include/ieache.h and one in evaluator.py. ----
+namespace {
+enum Operator : int32_t { OP_ADD, OP_SUB, OP_RSUB, OP_MUL };
+enum Widths : int32_t {
+    ANY_WIDTH,   // 1 .. 256 (the reference uses 32/64/128/256; 16 is BASELINE.json's generalisation add(...,16,...))
+    MUL_WIDTHS,  // 32, 64, 128 (cloud.c:860-864 refuses 256)
+};
+struct KindRow {
+    int32_t code;
+    const char* name;
+    Operator op;
+    CircuitFamily family;
+    Widths widths;
+    int32_t out_factor;  // output samples = out_factor x bits
+    int32_t ref_kind;    // n_reference_bootstraps is this kind's bootstrap count: what cloud.c performs for the same result
+    bool force_fold;     // built with folding on whatever the caller asks
+};
+constexpr KindRow kKinds[] = {
+    {CIRC_ADD, "add", OP_ADD, FAMILY_REFERENCE, ANY_WIDTH, 1, CIRC_ADD, false},
+    {CIRC_SUB, "sub", OP_SUB, FAMILY_REFERENCE, ANY_WIDTH, 1, CIRC_SUB, false},
+    {CIRC_RSUB, "rsub", OP_RSUB, FAMILY_REFERENCE, ANY_WIDTH, 1, CIRC_RSUB, false},
+    {CIRC_MUL, "mul", OP_MUL, FAMILY_REFERENCE, MUL_WIDTHS, 2, CIRC_MUL, false},
+    // the Kogge-Stone adders report the gates they were asked for
+    {CIRC_ADD_KS, "add_ks", OP_ADD, FAMILY_KOGGE_STONE, ANY_WIDTH, 1, CIRC_ADD_KS, false},
+    {CIRC_SUB_KS, "sub_ks", OP_SUB, FAMILY_KOGGE_STONE, ANY_WIDTH, 1, CIRC_SUB_KS, false},
+    {CIRC_RSUB_KS, "rsub_ks", OP_RSUB, FAMILY_KOGGE_STONE, ANY_WIDTH, 1, CIRC_RSUB_KS, false},
+    // the carry-save multiplier is built with folding on: it is opt-in and not the reference's gate list
+    // anyway, and its final adder sees constant-zero operands in the outer columns
+    {CIRC_MUL_WALLACE, "mul_wallace", OP_MUL, FAMILY_CARRY_SAVE, MUL_WIDTHS, 2, CIRC_MUL, true},
+    {CIRC_ADD_FA, "add_fa", OP_ADD, FAMILY_FULL_ADDER, ANY_WIDTH, 1, CIRC_ADD, false},
+    {CIRC_SUB_FA, "sub_fa", OP_SUB, FAMILY_FULL_ADDER, ANY_WIDTH, 1, CIRC_SUB, false},
+    {CIRC_RSUB_FA, "rsub_fa", OP_RSUB, FAMILY_FULL_ADDER, ANY_WIDTH, 1, CIRC_RSUB, false},
+    {CIRC_MUL_FA, "mul_fa", OP_MUL, FAMILY_FULL_ADDER, MUL_WIDTHS, 2, CIRC_MUL, false},
+};
+constexpr const KindRow* find_kind(int32_t code) {
+    for (const KindRow& r : kKinds)
+        if (r.code == code) return &r;
+    return nullptr;
+}
+constexpr bool accepts(const KindRow& r, int32_t bits) {
+    return r.widths == ANY_WIDTH ? bits >= 1 && bits <= 256 : bits == 32 || bits == 64 || bits == 128;
+}
+// the table's codes, row by row, are the C ABI's
+constexpr int32_t kAbiCodes[] = {IEACHE_CIRC_ADD,     IEACHE_CIRC_SUB,         IEACHE_CIRC_RSUB,   IEACHE_CIRC_MUL,
+                                 IEACHE_CIRC_ADD_KS,  IEACHE_CIRC_SUB_KS,      IEACHE_CIRC_RSUB_KS, IEACHE_CIRC_MUL_WALLACE,
+                                 IEACHE_CIRC_ADD_FA,  IEACHE_CIRC_SUB_FA,      IEACHE_CIRC_RSUB_FA, IEACHE_CIRC_MUL_FA};
+constexpr bool table_matches_abi() {
+    if (sizeof kAbiCodes / sizeof kAbiCodes[0] != sizeof kKinds / sizeof kKinds[0]) return false;
+    for (size_t i = 0; i < sizeof kKinds / sizeof kKinds[0]; i++)
+        if (kKinds[i].code != kAbiCodes[i] || find_kind(kKinds[i].ref_kind) == nullptr) return false;
+    return true;
+}
+static_assert(table_matches_abi(), "the kind table and include/ieache.h's IEACHE_CIRC_* disagree");
+static_assert(CIRC_MULADD == IEACHE_CIRC_MULADD && chain_kind(CIRC_MUL, CIRC_ADD, true) == IEACHE_CIRC_CHAIN(IEACHE_CIRC_MUL, IEACHE_CIRC_ADD, 1) &&
+                  chain_kind(CIRC_RSUB, CIRC_SUB, false) == IEACHE_CIRC_CHAIN(IEACHE_CIRC_RSUB, IEACHE_CIRC_SUB, 0),
+              "the chain encoding and include/ieache.h's IEACHE_CIRC_CHAIN disagree");
+
+// A kind as its stages: one row for a plain kind, two for a chain (decode_chain's k1, k2 are reference kinds).
+struct Stages {
+    const KindRow* s1 = nullptr;  // null: the code names no kind
+    const KindRow* s2 = nullptr;  // null: not a chain
+    bool flip = true;
+    int32_t w2(int32_t bits) const { return s1->out_factor * bits; }  // stage 1's output width = stage 2's operand width
+};
+Stages stages_of(int32_t kind) {
+    Stages s;
+    int32_t k1, k2;
+    if (decode_chain(kind, &k1, &k2, &s.flip)) {
+        s.s1 = find_kind(k1);
+        s.s2 = find_kind(k2);
+    } else {
+        s.s1 = find_kind(kind);
+    }
+    return s;
+}
+}  // namespace
 
 bool decode_chain(int32_t kind, int32_t* k1, int32_t* k2, bool* flip) {
     if (kind == CIRC_MULADD) kind = chain_kind(CIRC_MUL, CIRC_ADD, true);
@@ -425,55 +526,35 @@ bool decode_chain(int32_t kind, int32_t* k1, int32_t* k2, bool* flip) {
     return true;
 }
 
+bool circuit_multiplies(int32_t kind) {
+    const Stages s = stages_of(kind);
+    return s.s1 && (s.s1->op == OP_MUL || (s.s2 && s.s2->op == OP_MUL));
+}
+
+int32_t circuit_kind_in_family(int32_t kind, CircuitFamily family) {
+    const Stages s = stages_of(kind);
+    if (s.s1 && !s.s2)
+        for (const KindRow& r : kKinds)
+            if (r.op == s.s1->op && r.family == family) return r.code;
+    return kind;
+}
+
+bool circuit_accepts_width(int32_t kind, int32_t bits) {
+    const Stages s = stages_of(kind);
+    return s.s1 && bits >= 1 && bits <= 256 && accepts(*s.s1, bits) && (!s.s2 || accepts(*s.s2, s.w2(bits)));
+}
+
 int32_t circuit_n_inputs(int32_t kind, int32_t bits) {
-    int32_t k1, k2;
-    bool flip;
-    if (decode_chain(kind, &k1, &k2, &flip)) {
-        const int32_t w2 = k1 == CIRC_MUL ? 2 * bits : bits;
-        return 2 * bits + 32 + w2 + (flip ? 0 : 32);
-    }
-    switch (kind) {
-        case CIRC_ADD:
-        case CIRC_SUB:
-        case CIRC_RSUB:
-        case CIRC_MUL:
-        case CIRC_ADD_KS:
-        case CIRC_SUB_KS:
-        case CIRC_RSUB_KS:
-        case CIRC_MUL_WALLACE:
-        case CIRC_ADD_FA:
-        case CIRC_SUB_FA:
-        case CIRC_RSUB_FA:
-        case CIRC_MUL_FA:
-            return 2 * bits + 32;
-    }
-    return -1;
+    const Stages s = stages_of(kind);
+    if (!s.s1) return -1;
+    // A, B, the carry word [, C at stage 2's width [, C's carry word when the answer is operand 2]]
+    return 2 * bits + 32 + (s.s2 ? s.w2(bits) + (s.flip ? 0 : 32) : 0);
 }
 
 int32_t circuit_n_outputs(int32_t kind, int32_t bits) {
-    int32_t k1, k2;
-    bool flip;
-    if (decode_chain(kind, &k1, &k2, &flip)) {
-        const int32_t w2 = k1 == CIRC_MUL ? 2 * bits : bits;
-        return k2 == CIRC_MUL ? 2 * w2 : w2;
-    }
-    switch (kind) {
-        case CIRC_ADD:
-        case CIRC_SUB:
-        case CIRC_RSUB:
-        case CIRC_ADD_KS:
-        case CIRC_SUB_KS:
-        case CIRC_RSUB_KS:
-        case CIRC_ADD_FA:
-        case CIRC_SUB_FA:
-        case CIRC_RSUB_FA:
-            return bits;
-        case CIRC_MUL:
-        case CIRC_MUL_WALLACE:
-        case CIRC_MUL_FA:
-            return 2 * bits;
-    }
-    return -1;
+    const Stages s = stages_of(kind);
+    if (!s.s1) return -1;
+    return (s.s2 ? s.s2->out_factor : 1) * s.w2(bits);
 }
 
 // Split a flat bit vector into 32-bit words (the last may be shorter).
@@ -648,152 +729,100 @@ static Word full_adder_mul(CircuitBuilder& b, const Word& A, const Word& B) {
     return P;
 }
 
-// One branch of main() (cloud.c:870-2718) on symbolic operands: `bits`-wide A and B (a multiple
-// of 32 except for the generalised adders), carry = ciphertextcarry1.  Returns the value samples
-// LSB first, or an empty word for an unsupported (kind, bits).
-static Word build_stage(CircuitBuilder& b, int32_t kind, int32_t bits, const Word& A, const Word& B, const Word& carry1) {
-    const std::vector<Word> Aw = to_words(A), Bw = to_words(B);
+// The reference's multiplier on words (cloud.c:2366-2718): 32, 64 or 128 bits, value samples LSB first.
+static Word reference_mul(CircuitBuilder& b, const std::vector<Word>& Aw, const std::vector<Word>& Bw, const Word& carry1) {
     Word result;
-    switch (kind) {
-        case CIRC_ADD:
-            return chained_add(b, Aw, Bw, carry1);
-        case CIRC_SUB:  // cloud.c:1196-1807: complement operand 2, add to operand 1
-            return chained_add(b, Aw, twos_complement(b, Bw), carry1);
-        case CIRC_RSUB:  // cloud.c:1809-2365: complement operand 1, add to operand 2
-            return chained_add(b, Bw, twos_complement(b, Aw), carry1);
-        case CIRC_ADD_KS:
-            return kogge_stone_add(b, A, B, carry1[0]);
-        case CIRC_SUB_KS: {  // A + ~B + 1 (the reference's carry word encrypts 0: alice.c:147-149)
-            Word nb(bits);
-            CircuitBuilder::NOT(nb, B, bits);
-            return kogge_stone_add(b, A, nb, CircuitBuilder::constant(1));
-        }
-        case CIRC_RSUB_KS: {
-            Word na(bits);
-            CircuitBuilder::NOT(na, A, bits);
-            return kogge_stone_add(b, B, na, CircuitBuilder::constant(1));
-        }
-        case CIRC_MUL_WALLACE:
-            return wallace_mul(b, A, B);
-        case CIRC_ADD_FA:
-            return full_adder_ripple(b, A, B, carry1[0]);
-        case CIRC_SUB_FA: {  // A + ~B + 1 (the reference's carry word encrypts 0: alice.c:147-149)
-            Word nb(bits);
-            CircuitBuilder::NOT(nb, B, bits);
-            return full_adder_ripple(b, A, nb, CircuitBuilder::constant(1));
-        }
-        case CIRC_RSUB_FA: {
-            Word na(bits);
-            CircuitBuilder::NOT(na, A, bits);
-            return full_adder_ripple(b, B, na, CircuitBuilder::constant(1));
-        }
-        case CIRC_MUL_FA:
-            return full_adder_mul(b, A, B);
-        case CIRC_MUL:
-            if (bits == 32) {  // cloud.c:2655-2718
-                Word r1 = b.fresh(), r2 = b.fresh();
-                b.mul32(r1, r2, Aw[0], Bw[0], carry1, 32);
-                result = r2;  // low word first (:2683-2686)
-                result.insert(result.end(), r1.begin(), r1.end());
-            } else if (bits == 64) {  // cloud.c:2568-2654
-                Word r[6], f[3];
-                for (auto& w : r) w = b.fresh();
-                for (auto& w : f) w = b.fresh();
-                b.mul64(r[0], r[1], r[2], Aw[0], Aw[1], Bw[0], carry1, 32);              // :2589
-                b.mul64(r[3], r[4], r[5], Aw[0], Aw[1], Bw[1], carry1, 32);              // :2592
-                b.split(f[0], f[1], f[2], r[0], r[1], r[3], r[4], r[5], carry1, 32);     // :2594
-                for (const Word* w : {&r[2], &f[2], &f[1], &f[0]})                       // :2609-2616
-                    result.insert(result.end(), w->begin(), w->end());
-            } else if (bits == 128) {  // cloud.c:2371-2567
-                Word r[21], sm[16], co[16];
-                for (auto& w : r) w = b.fresh();
-                for (auto& w : sm) w = b.fresh();
-                for (auto& w : co) w = b.fresh();
-                for (int q = 0; q < 4; q++)  // :2434-2443
-                    b.mul128(r[5 * q + 1], r[5 * q + 2], r[5 * q + 3], r[5 * q + 4], r[5 * q + 5],
-                             Aw[0], Aw[1], Aw[2], Aw[3], Bw[q], carry1, 32);
-                b.add(sm[1], co[1], r[10], r[4], carry1, 32);  // :2445-2449
-                b.add(sm[2], co[2], r[9], r[3], co[1], 32);
-                b.add(sm[3], co[3], r[8], r[2], co[2], 32);
-                b.add(sm[4], co[4], r[7], r[1], co[3], 32);
-                b.add(sm[5], co[5], r[6], carry1, co[4], 32);
-                b.add(sm[6], co[6], sm[2], r[15], co[5], 32);  // :2451-2455 (carry-in = previous chain's top carry)
-                b.add(sm[7], co[7], sm[3], r[14], co[6], 32);
-                b.add(sm[8], co[8], sm[4], r[13], co[7], 32);
-                b.add(sm[9], co[9], sm[5], r[12], co[8], 32);
-                b.add(sm[10], co[10], r[11], carry1, co[9], 32);
-                b.add(sm[11], co[11], sm[7], r[20], co[10], 32);  // :2457-2461
-                b.add(sm[12], co[12], sm[8], r[19], co[11], 32);
-                b.add(sm[13], co[13], sm[9], r[18], co[12], 32);
-                b.add(sm[14], co[14], sm[10], r[17], co[13], 32);
-                b.add(sm[15], co[15], r[16], carry1, co[14], 32);
-                for (const Word* w : {&r[5], &sm[1], &sm[6], &sm[11], &sm[12], &sm[13], &sm[14], &sm[15]})  // :2476-2491
-                    result.insert(result.end(), w->begin(), w->end());
-            }
-            return result;
+    if (Aw.size() == 1) {  // cloud.c:2655-2718
+        Word r1 = b.fresh(), r2 = b.fresh();
+        b.mul_words({&r1, &r2}, {&Aw[0]}, Bw[0], carry1, 32);  // mul32, cloud.c:115-218
+        result = r2;  // low word first (:2683-2686)
+        result.insert(result.end(), r1.begin(), r1.end());
+    } else if (Aw.size() == 2) {  // cloud.c:2568-2654
+        Word r[6], f[3];
+        for (auto& w : r) w = b.fresh();
+        for (auto& w : f) w = b.fresh();
+        b.mul_words({&r[0], &r[1], &r[2]}, {&Aw[0], &Aw[1]}, Bw[0], carry1, 32);  // :2589  mul64, cloud.c:220-385
+        b.mul_words({&r[3], &r[4], &r[5]}, {&Aw[0], &Aw[1]}, Bw[1], carry1, 32);  // :2592
+        b.split(f[0], f[1], f[2], r[0], r[1], r[3], r[4], r[5], carry1, 32);      // :2594
+        for (const Word* w : {&r[2], &f[2], &f[1], &f[0]})                        // :2609-2616
+            result.insert(result.end(), w->begin(), w->end());
+    } else if (Aw.size() == 4) {  // cloud.c:2371-2567
+        Word r[21], sm[16], co[16];
+        for (auto& w : r) w = b.fresh();
+        for (auto& w : sm) w = b.fresh();
+        for (auto& w : co) w = b.fresh();
+        for (int q = 0; q < 4; q++)  // :2434-2443  mul128, cloud.c:387-647
+            b.mul_words({&r[5 * q + 1], &r[5 * q + 2], &r[5 * q + 3], &r[5 * q + 4], &r[5 * q + 5]}, {&Aw[0], &Aw[1], &Aw[2], &Aw[3]}, Bw[q],
+                        carry1, 32);
+        b.add(sm[1], co[1], r[10], r[4], carry1, 32);  // :2445-2449
+        b.add(sm[2], co[2], r[9], r[3], co[1], 32);
+        b.add(sm[3], co[3], r[8], r[2], co[2], 32);
+        b.add(sm[4], co[4], r[7], r[1], co[3], 32);
+        b.add(sm[5], co[5], r[6], carry1, co[4], 32);
+        b.add(sm[6], co[6], sm[2], r[15], co[5], 32);  // :2451-2455 (carry-in = previous chain's top carry)
+        b.add(sm[7], co[7], sm[3], r[14], co[6], 32);
+        b.add(sm[8], co[8], sm[4], r[13], co[7], 32);
+        b.add(sm[9], co[9], sm[5], r[12], co[8], 32);
+        b.add(sm[10], co[10], r[11], carry1, co[9], 32);
+        b.add(sm[11], co[11], sm[7], r[20], co[10], 32);  // :2457-2461
+        b.add(sm[12], co[12], sm[8], r[19], co[11], 32);
+        b.add(sm[13], co[13], sm[9], r[18], co[12], 32);
+        b.add(sm[14], co[14], sm[10], r[17], co[13], 32);
+        b.add(sm[15], co[15], r[16], carry1, co[14], 32);
+        for (const Word* w : {&r[5], &sm[1], &sm[6], &sm[11], &sm[12], &sm[13], &sm[14], &sm[15]})  // :2476-2491
+            result.insert(result.end(), w->begin(), w->end());
     }
     return result;
 }
 
-static const char* stage_name(int32_t kind) {
-    switch (kind) {
-        case CIRC_ADD: return "add";
-        case CIRC_SUB: return "sub";
-        case CIRC_RSUB: return "rsub";
-        case CIRC_MUL: return "mul";
-        case CIRC_ADD_KS: return "add_ks";
-        case CIRC_SUB_KS: return "sub_ks";
-        case CIRC_RSUB_KS: return "rsub_ks";
-        case CIRC_MUL_WALLACE: return "mul_wallace";
-        case CIRC_ADD_FA: return "add_fa";
-        case CIRC_SUB_FA: return "sub_fa";
-        case CIRC_RSUB_FA: return "rsub_fa";
-        case CIRC_MUL_FA: return "mul_fa";
+// One branch of main() (cloud.c:870-2718) on symbolic operands: A and B of a width the row accepts, carry = ciphertextcarry1.
+// Returns the value samples LSB first.
+static Word build_stage(CircuitBuilder& b, const KindRow& row, const Word& A, const Word& B, const Word& carry1) {
+    if (row.family == FAMILY_REFERENCE) {
+        const std::vector<Word> Aw = to_words(A), Bw = to_words(B);
+        switch (row.op) {
+            case OP_ADD: return chained_add(b, Aw, Bw, carry1);
+            case OP_SUB: return chained_add(b, Aw, twos_complement(b, Bw), carry1);   // cloud.c:1196-1807: complement operand 2, add to operand 1
+            case OP_RSUB: return chained_add(b, Bw, twos_complement(b, Aw), carry1);  // cloud.c:1809-2365: complement operand 1, add to operand 2
+            case OP_MUL: return reference_mul(b, Aw, Bw, carry1);
+        }
     }
-    return "?";
+    if (row.op == OP_MUL) return row.family == FAMILY_CARRY_SAVE ? wallace_mul(b, A, B) : full_adder_mul(b, A, B);
+    // The opt-in adders, one rule for both families: ADD is x + y with the carry word's bit 0 as carry-in; SUB / RSUB are
+    // minuend + ~subtrahend + 1, the 1 a constant carry-in (the reference's carry word encrypts 0: alice.c:147-149).
+    const auto adder = row.family == FAMILY_KOGGE_STONE ? kogge_stone_add : full_adder_ripple;
+    if (row.op == OP_ADD) return adder(b, A, B, carry1[0]);
+    const Word& minuend = row.op == OP_SUB ? A : B;
+    const Word& subtrahend = row.op == OP_SUB ? B : A;
+    Word complement(subtrahend.size());
+    CircuitBuilder::NOT(complement, subtrahend, subtrahend.size());
+    return adder(b, minuend, complement, CircuitBuilder::constant(1));
 }
 
 bool build_circuit(int32_t kind, int32_t bits, Circuit* out, bool balanced, bool fold, int32_t level_cap) {
-    if (bits < 1 || bits > 256) return false;
-    const int32_t n_in = circuit_n_inputs(kind, bits);
-    if (n_in < 0) return false;
-    // the carry-save multiplier is built with folding on: it is opt-in and not the reference's gate list
-    // anyway, and its final adder sees constant-zero operands in the outer columns
-    CircuitBuilder b(n_in, fold || kind == CIRC_MUL_WALLACE);
+    if (!circuit_accepts_width(kind, bits)) return false;
+    const Stages s = stages_of(kind);
+    CircuitBuilder b(circuit_n_inputs(kind, bits), fold || s.s1->force_fold);
     const Word A = b.input_word(0, bits), B = b.input_word(bits, bits);
     const Word carry1 = b.input_word(2 * bits, 32);  // ciphertextcarry1
-    Word result;
-    std::string name;
-    int32_t k1, k2;
-    bool flip;
-    bool has_mul = kind == CIRC_MUL || kind == CIRC_MUL_WALLACE || kind == CIRC_MUL_FA;
+    Word result = build_stage(b, *s.s1, A, B, carry1);
+    std::string name = s.s1->name;
     int32_t sched_bits = bits;
-    if (decode_chain(kind, &k1, &k2, &flip)) {
+    if (s.s2) {
         // Two ./cloud runs of compute() / compute_final() (dragonfly_cipher_cloud.py:1219-1327) as
         // one DAG.  Stage 1's answer advertises bits (ADD/SUB) or 2*bits (MUL: cloud.c:833-844), the
         // third operand C is given at that width, so stage 2 runs at int_bit = w2 (cloud.c:841-855).
         // Its carry-in is operand 1's carry word (e.g. cloud.c:891): when the answer is operand 1
         // (flip) that is the answer's 11th word, which main() fills with stage 1's
         // ciphertextcarry1 (cloud.c:901-916, 2617-2626); otherwise it is C's own carry word.
-        if ((k1 == CIRC_MUL || k1 > CIRC_MUL) && bits % 32) return false;
-        const int32_t w2 = k1 == CIRC_MUL ? 2 * bits : bits;
-        if (k2 == CIRC_MUL && w2 != 32 && w2 != 64 && w2 != 128) return false;  // cloud.c:860-864 refuses 256
-        if (k1 == CIRC_MUL && bits != 32 && bits != 64 && bits != 128) return false;
-        const Word stage1 = build_stage(b, k1, bits, A, B, carry1);
-        if (stage1.empty()) return false;
+        const int32_t w2 = s.w2(bits);
+        const Word stage1 = result;
         const Word C = b.input_word(2 * bits + 32, w2);
-        const Word carry2 = flip ? carry1 : b.input_word(2 * bits + 32 + w2, 32);
-        result = flip ? build_stage(b, k2, w2, stage1, C, carry2) : build_stage(b, k2, w2, C, stage1, carry2);
-        name = std::string(stage_name(k1)) + "_" + stage_name(k2) + (flip ? "" : "_r");
-        if (kind == CIRC_MULADD) name = "muladd";
-        has_mul = k1 == CIRC_MUL || k2 == CIRC_MUL;
-        if (k2 == CIRC_MUL) sched_bits = w2;  // the wider multiplier decides the schedule below
-    } else {
-        if (has_mul && bits != 32 && bits != 64 && bits != 128) return false;
-        result = build_stage(b, kind, bits, A, B, carry1);
-        name = stage_name(kind);
+        const Word carry2 = s.flip ? carry1 : b.input_word(2 * bits + 32 + w2, 32);
+        result = s.flip ? build_stage(b, *s.s2, stage1, C, carry2) : build_stage(b, *s.s2, C, stage1, carry2);
+        name = kind == CIRC_MULADD ? "muladd" : name + "_" + s.s2->name + (s.flip ? "" : "_r");
+        if (s.s2->op == OP_MUL) sched_bits = w2;  // the wider multiplier decides the schedule below
     }
-    if (result.empty()) return false;
     // Schedule choice.  Measured (mul32, batches 32..1024) plain ASAP is 1-3 % faster than the
     // slack-balanced schedule -- its big early levels run at full machine width -- so the balanced
     // schedule is used where it pays in memory: the 64/128-bit multipliers, whose ASAP wire store
@@ -801,18 +830,15 @@ bool build_circuit(int32_t kind, int32_t bits, Circuit* out, bool balanced, bool
     static const char* force = getenv("IEACHE_SCHEDULE");  // "asap" | "balanced": A/B switch for measurements
     // ... and wherever the caller asks for a level width (level_cap > 0: small batches of the 32-bit multiplier, whose ASAP
     // levels swing between a fraction of a round of resident workgroups and several)
-    bool use_balanced = balanced && has_mul && (sched_bits >= 64 || level_cap > 0);
+    bool use_balanced = balanced && circuit_multiplies(kind) && (sched_bits >= 64 || level_cap > 0);
     if (force && std::string(force) == "asap") use_balanced = false;
     if (force && std::string(force) == "balanced") use_balanced = balanced;
     *out = finalize_circuit(name + std::to_string(bits) + (fold ? "_folded" : ""), b, result, use_balanced, use_balanced ? level_cap : 0);
     out->n_reference_bootstraps = b.n_requested();
     out->balanced_schedule = use_balanced;
-    int32_t ref_kind = 0;  // the opt-in kinds that are not the reference's gate list: what cloud.c performs for the same result
-    if (kind == CIRC_MUL_WALLACE || kind == CIRC_MUL_FA) ref_kind = CIRC_MUL;
-    if (kind >= CIRC_ADD_FA && kind <= CIRC_RSUB_FA) ref_kind = kind - CIRC_ADD_FA + CIRC_ADD;
-    if (ref_kind) {
+    if (!s.s2 && s.s1->ref_kind != kind) {  // an opt-in kind that is not the reference's gate list
         Circuit ref;
-        if (build_circuit(ref_kind, bits, &ref, false, false)) out->n_reference_bootstraps = ref.n_bootstraps;
+        if (build_circuit(s.s1->ref_kind, bits, &ref, false, false)) out->n_reference_bootstraps = ref.n_bootstraps;
     }
     return true;
 }
@@ -834,18 +860,10 @@ static int32_t round_level_cap(const Circuit& base, int64_t batch, int32_t resid
     return (int32_t)cap;
 }
 
-int32_t circuit_level_cap(const Circuit& base, int64_t batch, int32_t resident, int32_t resident_alt) {
-    if (!base.balanced_schedule) return round_level_cap(base, batch, resident);
-    // resident_alt: a second, smaller residency the evaluator also runs efficiently (the two-waves-per-gate kernel's 4 per
-    // CU below the one-wave kernel's 8 per CU): tried when the batch is too small to fill levels of the first
-    if (resident_alt > 0) {
-        const int32_t cap = circuit_level_cap(base, batch, resident, 0);
-        return cap > 0 ? cap : circuit_level_cap(base, batch, resident_alt, 0);
-    }
-    const int64_t n_bootstraps = base.n_bootstraps;
-    const int32_t asap_depth = base.depth;
-    if (!base.balanced_schedule || batch <= 0 || resident <= 0 || asap_depth <= 0 || batch >= resident) return 0;
-    const int64_t mean = (n_bootstraps + asap_depth - 1) / asap_depth;
+// Balanced circuits: the multiple of resident / gcd(resident, batch) nearest to the mean width (see circuit.h).
+static int32_t quantum_level_cap(const Circuit& base, int64_t batch, int32_t resident) {
+    if (batch <= 0 || resident <= 0 || base.depth <= 0 || batch >= resident) return 0;
+    const int64_t mean = (base.n_bootstraps + base.depth - 1) / base.depth;
     // a circuit whose default schedule already needs levels far above the mean has no slack to flatten
     // (the carry-save multipliers: their trees are all critical path); stretching it only adds levels
     if (base.sched_max_width > 2 * mean) return 0;
@@ -860,6 +878,14 @@ int32_t circuit_level_cap(const Circuit& base, int64_t batch, int32_t resident, 
     if (q <= 1 || 2 * q > 3 * mean) return 0;  // a quantum far above what the circuit offers per level cannot be filled
     const int64_t k = std::max<int64_t>(1, (mean + q / 2) / q);
     return (int32_t)(k * q);
+}
+
+int32_t circuit_level_cap(const Circuit& base, int64_t batch, int32_t resident, int32_t resident_alt) {
+    if (!base.balanced_schedule) return round_level_cap(base, batch, resident);
+    // resident_alt: a second, smaller residency the evaluator also runs efficiently (the two-waves-per-gate kernel's 4 per
+    // CU below the one-wave kernel's 8 per CU): tried when the batch is too small to fill levels of the first
+    const int32_t cap = quantum_level_cap(base, batch, resident);
+    return cap > 0 || resident_alt <= 0 ? cap : quantum_level_cap(base, batch, resident_alt);
 }
 
 Circuit build_netlist(int32_t n_inputs, const NetGate* gates, size_t n_gates, const int32_t* outputs, size_t n_outputs,

@@ -1,12 +1,18 @@
-// Gate-DAG form of the arithmetic circuits of /root/reference/Cloud/cloud.c.
+// Gate-DAG form of the arithmetic circuits of the reference's Cloud/cloud.c.
 //
 // The reference evaluates its circuits one libtfhe gate at a time
 // (cloud.c:18-647).  Here the same gates are recorded as a DAG, levelised
-// ASAP (every gate of a level is independent) and given storage slots by
-// liveness so that a whole level -- times the batch of expressions -- is one
-// GPU launch.  bootsNOT / bootsCOPY / bootsCONSTANT cost no bootstrap in
-// libtfhe and none here: they are folded into wire references (sign flag,
-// alias, constant).
+// (every gate of a level is independent: ASAP levels, or a slack-balanced list
+// schedule of the same DAG where build_circuit or the caller asks for one, with
+// an optional cap on the gates per level) and given storage slots by liveness
+// so that a whole level -- times the batch of expressions -- is one GPU launch.
+// bootsNOT / bootsCOPY / bootsCONSTANT cost no bootstrap in libtfhe and none
+// here: they are folded into wire references (sign flag, alias, constant).
+//
+// The parts: CircuitBuilder records gates; finalize_circuit
+// schedules them and allocates slots; a table of kinds in circuit.cpp says what
+// each CIRC_* code is; circuit_level_cap picks a level width for a batch;
+// circuit_cache.h keeps built circuits.
 #pragma once
 #include <cstdint>
 #include <map>
@@ -92,11 +98,7 @@ public:
     // cloud.c:115-218 / 220-385 / 387-647.  `in` low word first; `results` high word first.
     void mul_words(std::vector<Word*> results, const std::vector<const Word*>& in, const Word& m,
                    const Word& carry, int32_t nb_bits);
-    void mul32(Word& result, Word& result2, const Word& a, const Word& b, const Word& carry, int32_t nb_bits);
-    void mul64(Word& r, Word& r2, Word& r3, const Word& a, const Word& b, const Word& c,
-               const Word& carry, int32_t nb_bits);
-    void mul128(Word& r, Word& r2, Word& r3, Word& r4, Word& r5, const Word& a, const Word& b,
-                const Word& c, const Word& d, const Word& e, const Word& carry, int32_t nb_bits);
+    void mul32(Word& result, Word& result2, const Word& a, const Word& b, const Word& carry, int32_t nb_bits);  // :115-218
 
     int32_t n_inputs() const { return n_inputs_; }
     const std::vector<Gate>& gates() const { return gates_; }
@@ -105,6 +107,11 @@ public:
     int64_t n_requested() const { return n_requested_; }  // gates the reference performs (before folding)
 
 private:
+    // gate() after its checks and its count: lowers NOR .. ORYN, folds and shares when fold is on, records the rest
+    Ref gate2(int32_t type, Ref a, Ref b);
+    // The one place a gate is recorded: its ASAP level from its operands, a new wire.  With fold on, a gate already recorded
+    // with this type on these operands is returned instead.  -> the gate's wire
+    int32_t record(int32_t type, int32_t requested, Ref a, Ref b, Ref c);
     int32_t n_inputs_;
     int32_t next_wire_;
     bool fold_;
@@ -112,7 +119,7 @@ private:
     std::vector<Gate> gates_;
     std::vector<int32_t> requested_type_;  // per recorded gate: the type asked for (before NOR .. ORYN were lowered)
     std::vector<int32_t> wire_level_;
-    // (type,a,na,b,nb,c,nc) -> wire; c = kUndefId for a two-input gate
+    // (type,a,na,b,nb,c,nc) -> wire; c = the constant 0 for a two-input gate
     std::map<std::tuple<int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t>, int32_t> known_;
 };
 
@@ -214,6 +221,21 @@ enum CircuitKind : int32_t {
     CIRC_CHAIN_BASE = 32,
     CIRC_CHAIN_END = 64,
 };
+// What a plain (non-chain) kind is built from, besides its operator: the reference's gate list or one of the opt-in circuits.
+enum CircuitFamily : int32_t {
+    FAMILY_REFERENCE = 0,    // ADD / SUB / RSUB / MUL
+    FAMILY_KOGGE_STONE = 1,  // the _KS adders
+    FAMILY_CARRY_SAVE = 2,   // MUL_WALLACE
+    FAMILY_FULL_ADDER = 3,   // the _FA kinds
+};
+// whether a kind multiplies (a chain: in either stage); false for a code that names no kind
+bool circuit_multiplies(int32_t kind);
+// the kind of the same operator in another family (CIRC_SUB, FAMILY_FULL_ADDER -> CIRC_SUB_FA); `kind` itself where that
+// family has no such operator (there is no Kogge-Stone multiplier) and for chains and unknown codes
+int32_t circuit_kind_in_family(int32_t kind, CircuitFamily family);
+// whether build_circuit accepts this operand width for the kind: the adders 1 .. 256, the multipliers 32 / 64 / 128, a chain
+// what its two stages accept (stage 2 at stage 1's output width)
+bool circuit_accepts_width(int32_t kind, int32_t bits);
 constexpr int32_t chain_kind(int32_t k1, int32_t k2, bool flip) { return CIRC_CHAIN_BASE + (k1 - 1) + 4 * (k2 - 1) + (flip ? 0 : 16); }
 // decodes a CHAIN kind (CIRC_MULADD counts as chain(MUL, ADD, flip)); false for plain kinds
 bool decode_chain(int32_t kind, int32_t* k1, int32_t* k2, bool* flip);

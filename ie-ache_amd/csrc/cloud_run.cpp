@@ -1,6 +1,6 @@
 // The `./cloud` process contract of the reference, as a function.
 //
-// Mirrors main() of /root/reference/Cloud/cloud.c:650-2720 step by step: same
+// Mirrors main() of the reference's Cloud/cloud.c:650-2720 step by step: same
 // files in the working directory, same metadata arithmetic, same dispatch on
 // (operator, sign case, bit size), same answer.data layout, same exit codes.
 // The only thing that changes is HOW the gates are evaluated: the selected
@@ -8,11 +8,8 @@
 // one libtfhe bootstrap at a time.
 #include "cloud_run.h"
 
-#include <map>
 #include <memory>
-#include <mutex>
 #include <thread>
-#include <tuple>
 
 #include <sys/time.h>
 
@@ -25,6 +22,7 @@
 #include <vector>
 
 #include "circuit.h"
+#include "circuit_cache.h"
 #include "codec.h"
 #include "evaluator.h"
 #include "tfhe_host.h"
@@ -236,20 +234,20 @@ void cloud_prepare(const CloudRunIO& io, CloudJob* job, CloudRunReport* report) 
     }
     if (kind == 0) return;  // unknown operator: main() falls through, answer.data keeps 64 samples
     fprintf(log, "%d bit %s computation\n", int_bit, label);
-    const bool size_ok = kind == CIRC_MUL ? (int_bit == 32 || int_bit == 64 || int_bit == 128)
-                                          : (int_bit == 32 || int_bit == 64 || int_bit == 128 || int_bit == 256);
+    // main() has branches for operands of 1, 2, 4 and 8 words, as far as the operator takes them
+    const bool size_ok = (int_bit == 32 || int_bit == 64 || int_bit == 128 || int_bit == 256) && circuit_accepts_width(kind, int_bit);
     if (!size_ok) return;  // no branch of main() matches: 64-sample answer.data = failure marker
 
-    // Opt-in parallel-prefix adders: same decrypted answer, 7x fewer levels for a
-    // single expression; NOT the reference's gate sequence, so off unless asked for.
-    if (const char* adder = getenv("IEACHE_ADDER")) {
-        if (std::string(adder) == "kogge-stone" && kind >= CIRC_ADD && kind <= CIRC_RSUB) kind += CIRC_ADD_KS - CIRC_ADD;
-        // ... or the two-bootstrap full adder (MAJ3 / XOR3): 2.5x fewer bootstraps and 3x fewer levels, at any batch
-        else if (std::string(adder) == "full-adder" && kind >= CIRC_ADD && kind <= CIRC_RSUB) kind += CIRC_ADD_FA - CIRC_ADD;
-    }
-    if (const char* mult = getenv("IEACHE_MULTIPLIER")) {  // opt-in carry-save multiplier: 32 levels instead of 255 at 32 bits
-        if (std::string(mult) == "wallace" && kind == CIRC_MUL) kind = CIRC_MUL_WALLACE;
-        else if (std::string(mult) == "full-adder" && kind == CIRC_MUL) kind = CIRC_MUL_FA;  // carry-save array of full adders
+    // Opt-in circuits of the same operator: same decrypted answer, NOT the reference's gate sequence, so off unless asked for.
+    // IEACHE_ADDER=kogge-stone: parallel-prefix adders, 7x fewer levels for a single expression; =full-adder: the
+    // two-bootstrap full adder (MAJ3 / XOR3), 2.5x fewer bootstraps and 3x fewer levels, at any batch.
+    // IEACHE_MULTIPLIER=wallace: carry-save multiplier, 32 levels instead of 255 at 32 bits; =full-adder: carry-save array of
+    // full adders.  A family without this operator (a Kogge-Stone multiplier) leaves the kind as it is.
+    if (const char* family = getenv(circuit_multiplies(kind) ? "IEACHE_MULTIPLIER" : "IEACHE_ADDER")) {
+        const std::string f = family;
+        if (f == "kogge-stone") kind = circuit_kind_in_family(kind, FAMILY_KOGGE_STONE);
+        if (f == "wallace") kind = circuit_kind_in_family(kind, FAMILY_CARRY_SAVE);
+        if (f == "full-adder") kind = circuit_kind_in_family(kind, FAMILY_FULL_ADDER);
     }
     // Opt-in constant folding (SURVEY App. C note): fewer bootstraps, same decrypted answer, not the
     // reference's ciphertext bits
@@ -277,7 +275,7 @@ void cloud_finish(const CloudRunIO& io, const CloudJob& job, const Torus32* out,
     const int32_t n = job.params.n;
     const size_t S = (size_t)n + 1;
     fprintf(log, "Computation Time: %lf[sec]\n", seconds);
-    if (job.kind == CIRC_MUL || job.kind == CIRC_MUL_WALLACE || job.kind == CIRC_MUL_FA) {  // cloud.c:2467-2471
+    if (circuit_multiplies(job.kind)) {  // cloud.c:2467-2471
         FILE* t_file = io.stats_path.empty() ? nullptr : fopen(io.stats_path.c_str(), "a");
         if (t_file) {
             fprintf(t_file, "%lf\n", seconds);
@@ -318,41 +316,13 @@ int cloud_run_io(const CloudRunIO& io, const std::function<Evaluator*()>& get_ev
 void cloud_eval_jobs(Evaluator& eval, const std::vector<CloudJob*>& jobs, std::vector<std::vector<Torus32>>* outs, EvalStats* stats) {
     if (jobs.empty()) return;
     const CloudJob& first = *jobs[0];
-    // built circuits are kept for the life of the process (a daemon evaluates the same handful over and over; building the
-    // 128-bit multiplier's DAG and levelising it takes longer than evaluating a small batch of it), keyed like capi.cpp's
-    // per-context cache: (kind, width, folding, level cap)
-    // Bounded: per (kind, width, folding) the default schedule plus ONE level-capped variant, the most recent (the cap follows
-    // the batch size, and a long-running daemon sees many batch sizes; each entry of the wide multipliers is several MB).
-    // Entries are shared_ptr: an evaluation in flight keeps its circuit alive when another thread's call replaces it.
-    struct Entry {
-        std::shared_ptr<const Circuit> base, capped;
-        int32_t cap = 0;
-    };
-    static std::mutex cache_mutex;
-    static std::map<std::tuple<int32_t, int32_t, bool>, Entry> cache;
-    auto fetch = [&](int32_t cap) -> std::shared_ptr<const Circuit> {
-        std::lock_guard<std::mutex> lock(cache_mutex);
-        Entry& e = cache[std::make_tuple(first.kind, first.int_bit, first.fold)];
-        if (cap == 0 && e.base) return e.base;
-        if (cap != 0 && e.capped && e.cap == cap) return e.capped;
-        std::shared_ptr<Circuit> c(new Circuit);
-        if (!build_circuit(first.kind, first.int_bit, c.get(), true, first.fold, cap)) return nullptr;
-        if (cap == 0) {
-            e.base = c;
-        } else {
-            e.capped = c;  // replaces the variant of another batch size
-            e.cap = cap;
-        }
-        return c;
-    };
-    const std::shared_ptr<const Circuit> base = fetch(0);
-    if (!base) throw std::invalid_argument("unsupported circuit");
-    std::shared_ptr<const Circuit> circ = base;
-    const int32_t cap = circuit_level_cap(*base, (int64_t)jobs.size(), eval.resident_gates(), eval.resident_gates_two_wave());
-    if (cap > 0) {
-        const std::shared_ptr<const Circuit> capped = fetch(cap);
-        if (capped && capped->balanced_schedule) circ = capped;
-    }
+    // built circuits are kept for the life of the process (a daemon evaluates the same handful over and over): per (kind, width,
+    // folding) the default schedule plus ONE level-capped variant, the most recent -- the cap follows the batch size, and a
+    // long-running daemon sees many batch sizes
+    static CircuitCache cache(1);
+    const CircuitCache::Ptr circ = cache.select(first.kind, first.int_bit, first.fold, (int64_t)jobs.size(), eval.resident_gates(),
+                                                eval.resident_gates_two_wave(), /*level_quantum=*/true);
+    if (!circ) throw std::invalid_argument("unsupported circuit");
     const size_t S = (size_t)first.params.n + 1, n_in = (size_t)circ->n_inputs * S, n_out = circ->outputs.size() * S;
     std::vector<Torus32> in(jobs.size() * n_in), out(jobs.size() * n_out);
     for (size_t i = 0; i < jobs.size(); i++) {
