@@ -18,18 +18,14 @@
 #include "codec.h"
 #include "daemon.h"
 #include "evaluator.h"
+#include "group.h"
+#include "group_run.h"
 #include "mix_plan.h"
 #include "tfhe_host.h"
 
 using namespace ieache;
 
-struct ieache_ctx {
-    std::unique_ptr<Evaluator> eval;
-    CircuitCache circuits{3};  // a caller alternates between a few batch sizes, or toggles exact_fft per call (bench.py's exact leg)
-    std::string variant;
-    bool fold = false;           // "fold_constants"
-    bool level_quantum = true;   // "level_quantum": batch-aware level widths for the slack-balanced circuits
-};
+// struct ieache_ctx: group.h (a member of a device group is one)
 
 namespace {
 thread_local std::string g_err;
@@ -153,6 +149,49 @@ CircuitCache::Ptr get_circuit(ieache_ctx* ctx, int kind, int bits, size_t batch)
     const char* forced = getenv("IEACHE_LEVEL_CAP");
     return ctx->circuits.select(kind, bits, ctx->fold, (int64_t)batch, ctx->eval->resident_gates(), ctx->eval->resident_gates_two_wave(),
                                 ctx->level_quantum, forced ? atoi(forced) : 0);
+}
+// ---- The argument checks of the host-buffer entry points: 0, or the code after fail().  Each context form opens with its
+// check; the group form of the same call (section 2b) makes it once, on member 0 and the caller's whole arrays, before any
+// thread starts. ----
+int check_rows(std::initializer_list<const void*> pointers) {  // the context (or group member) and every row array
+    for (const void* p : pointers)
+        if (!p) return fail(IEACHE_EINVAL, "null argument");
+    return 0;
+}
+// ... -> *c: the circuit the context evaluates `batch` expressions with
+int check_prepare(ieache_ctx* ctx, int kind, int bits, size_t batch, CircuitCache::Ptr* c) {
+    if (!ctx) return fail(IEACHE_EINVAL, "null argument");
+    *c = get_circuit(ctx, kind, bits, batch);
+    return *c ? 0 : fail(IEACHE_EINVAL, kUnsupported);
+}
+int check_batch(ieache_ctx* ctx, int kind, int bits, size_t batch, const int32_t* in_lwe, const int32_t* out_lwe, CircuitCache::Ptr* c) {
+    if (const int rc = check_rows({ctx, in_lwe, out_lwe})) return rc;
+    return check_prepare(ctx, kind, bits, batch, c);
+}
+bool bad_gate2(int gate_type) { return gate_type < 0 || gate_type >= GATE_TYPES || gate_type == GATE_MUX; }
+const char* const kNotGate3 = "not a three-input gate type (IEACHE_GATE_MAJ3 / IEACHE_GATE_XOR3)";
+int check_gates(const ieache_ctx* ctx, int gate_type, const int32_t* a, const int32_t* b, const int32_t* out) {
+    if (const int rc = check_rows({ctx, a, b, out})) return rc;
+    return bad_gate2(gate_type) ? fail(IEACHE_EINVAL, "unknown gate type") : 0;
+}
+int check_gates3(const ieache_ctx* ctx, int gate_type, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* out) {
+    if (!is_gate3(gate_type)) return fail(IEACHE_EINVAL, kNotGate3);
+    return check_rows({ctx, a, b, c, out});
+}
+// what can be judged without the context comes first
+int check_pbs(const ieache_ctx* ctx, size_t count, const int32_t* x, const int32_t* test_polys, int32_t n_polys, const int32_t* poly_of,
+              const int32_t* out, int flags) {
+    if (const char* e = pbs_args_error(flags, n_polys, test_polys)) return fail(IEACHE_EINVAL, e);
+    const std::string bad_index = poly_of_error("pbs", poly_of, count, n_polys);
+    if (!bad_index.empty()) return fail(IEACHE_EINVAL, bad_index);
+    return check_rows({ctx, x, out});
+}
+int check_pbs_multi(const ieache_ctx* ctx, size_t count, const int32_t* x, const int32_t* test_polys, int32_t n_polys, const int32_t* poly_of,
+                    const int32_t* factors, int32_t n_factors, const int32_t* out, int flags) {
+    if (const char* e = pbs_multi_args_error(flags, n_polys, test_polys, n_factors, factors)) return fail(IEACHE_EINVAL, e);
+    const std::string bad_index = poly_of_error("pbs_multi", poly_of, count, n_polys);
+    if (!bad_index.empty()) return fail(IEACHE_EINVAL, bad_index);
+    return check_rows({ctx, x, out});
 }
 // f(circuit) on a throw-away build of the circuit, or the refusal
 template <class F>
@@ -414,9 +453,8 @@ int ieache_circuit_simulate(int kind, int bits, const uint8_t* in_bits, uint8_t*
 int ieache_eval_batch(ieache_ctx* ctx, int kind, int bits, size_t batch, const int32_t* in_lwe, int32_t* out_lwe,
                       ieache_stats* stats) {
     return guarded([&] {
-        if (!ctx || !in_lwe || !out_lwe) return fail(IEACHE_EINVAL, "null argument");
-        const CircuitCache::Ptr c = get_circuit(ctx, kind, bits, batch);
-        if (!c) return fail(IEACHE_EINVAL, kUnsupported);
+        CircuitCache::Ptr c;
+        if (const int rc = check_batch(ctx, kind, bits, batch, in_lwe, out_lwe, &c)) return rc;
         return with_stats(stats, [&](EvalStats* st) { eval_circuit_host(*ctx->eval, *c, batch, in_lwe, out_lwe, st); });
     });
 }
@@ -434,9 +472,8 @@ int ieache_eval_batch_device(ieache_ctx* ctx, int kind, int bits, size_t batch, 
 
 int ieache_prepare_batch(ieache_ctx* ctx, int kind, int bits, size_t batch) {
     return guarded([&] {
-        if (!ctx) return fail(IEACHE_EINVAL, "null argument");
-        const CircuitCache::Ptr c = get_circuit(ctx, kind, bits, batch);
-        if (!c) return fail(IEACHE_EINVAL, kUnsupported);
+        CircuitCache::Ptr c;
+        if (const int rc = check_prepare(ctx, kind, bits, batch, &c)) return rc;
         ctx->eval->prepare_circuit(*c, batch);
         return 0;
     });
@@ -501,7 +538,7 @@ int ieache_netlist_simulate(const ieache_netlist* nl, const uint8_t* in_bits, ui
 
 int ieache_prepare_netlist(ieache_ctx* ctx, const ieache_netlist* nl, size_t batch) {
     return guarded([&] {
-        if (!ctx || !nl) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_rows({ctx, nl})) return rc;
         ctx->eval->prepare_circuit(nl->circuit, batch);
         return 0;
     });
@@ -510,7 +547,7 @@ int ieache_prepare_netlist(ieache_ctx* ctx, const ieache_netlist* nl, size_t bat
 int ieache_eval_netlist(ieache_ctx* ctx, const ieache_netlist* nl, size_t batch, const int32_t* in_lwe, int32_t* out_lwe,
                         ieache_stats* stats) {
     return guarded([&] {
-        if (!ctx || !nl || !in_lwe || !out_lwe) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_rows({ctx, nl, in_lwe, out_lwe})) return rc;
         return with_stats(stats, [&](EvalStats* st) { eval_circuit_host(*ctx->eval, nl->circuit, batch, in_lwe, out_lwe, st); });
     });
 }
@@ -573,8 +610,6 @@ struct HostCall {
     // key-switched rows carry n + 1 words, extracted samples N + 1
     void download(StagedRows& out, int32_t* h, bool extracted = false) { out.download(h, extracted ? (size_t)p.N + 1 : (size_t)p.n + 1); }
 };
-bool bad_gate2(int gate_type) { return gate_type < 0 || gate_type >= GATE_TYPES || gate_type == GATE_MUX; }
-const char* const kNotGate3 = "not a three-input gate type (IEACHE_GATE_MAJ3 / IEACHE_GATE_XOR3)";
 }  // namespace
 
 // ---- flat calls.  Device form: validate, check the pointers, run.  Host form: validate, stage the inputs, run the same
@@ -592,8 +627,7 @@ int ieache_gates_device(ieache_ctx* ctx, int gate_type, size_t count, const int3
 int ieache_gates(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* a, const int32_t* b, int32_t* out,
                  ieache_stats* stats) {
     return guarded([&] {
-        if (!ctx || !a || !b || !out) return fail(IEACHE_EINVAL, "null argument");
-        if (bad_gate2(gate_type)) return fail(IEACHE_EINVAL, "unknown gate type");
+        if (const int rc = check_gates(ctx, gate_type, a, b, out)) return rc;
         HostCall h(ctx, count);
         StagedRows da = h.operand(kStageA, a), db = h.operand(kStageB, b), dout = h.results(count);
         with_stats(stats, [&](EvalStats* st) { h.ev.gates_device(gate_type, count, da.p, db.p, dout.p, st); });
@@ -615,8 +649,7 @@ int ieache_gates3_device(ieache_ctx* ctx, int gate_type, size_t count, const int
 int ieache_gates3(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* a, const int32_t* b, const int32_t* c, int32_t* out,
                   ieache_stats* stats) {
     return guarded([&] {
-        if (!is_gate3(gate_type)) return fail(IEACHE_EINVAL, kNotGate3);
-        if (!ctx || !a || !b || !c || !out) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_gates3(ctx, gate_type, a, b, c, out)) return rc;
         HostCall h(ctx, count);
         StagedRows da = h.operand(kStageA, a), db = h.operand(kStageB, b), dc = h.operand(kStageC, c), dout = h.results(count);
         with_stats(stats, [&](EvalStats* st) { h.ev.gates3_device(gate_type, count, da.p, db.p, dc.p, dout.p, st); });
@@ -637,7 +670,7 @@ int ieache_mux_device(ieache_ctx* ctx, size_t count, const int32_t* d_a, const i
 int ieache_mux(ieache_ctx* ctx, size_t count, const int32_t* a, const int32_t* b, const int32_t* c, int32_t* out,
                ieache_stats* stats) {
     return guarded([&] {
-        if (!ctx || !a || !b || !c || !out) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_rows({ctx, a, b, c, out})) return rc;
         HostCall h(ctx, count);
         StagedRows da = h.operand(kStageA, a), db = h.operand(kStageB, b), dc = h.operand(kStageC, c), dout = h.results(count);
         with_stats(stats, [&](EvalStats* st) { h.ev.mux_device(count, da.p, db.p, dc.p, dout.p, st); });
@@ -661,11 +694,7 @@ int ieache_pbs_device(ieache_ctx* ctx, size_t count, const int32_t* d_x, const i
 int ieache_pbs(ieache_ctx* ctx, size_t count, const int32_t* x, const int32_t* test_polys, int32_t n_polys, const int32_t* poly_of,
                int32_t* out, int flags, ieache_stats* stats) {
     return guarded([&] {
-        // what can be judged without the context comes first
-        if (const char* e = pbs_args_error(flags, n_polys, test_polys)) return fail(IEACHE_EINVAL, e);
-        const std::string bad_index = poly_of_error("pbs", poly_of, count, n_polys);
-        if (!bad_index.empty()) return fail(IEACHE_EINVAL, bad_index);
-        if (!ctx || !x || !out) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_pbs(ctx, count, x, test_polys, n_polys, poly_of, out, flags)) return rc;
         const bool woks = (flags & IEACHE_PBS_NO_KEYSWITCH) != 0;
         HostCall h(ctx, count);
         StagedRows dx = h.operand(kStageA, x), dout = h.results(count, woks);
@@ -693,11 +722,7 @@ int ieache_pbs_multi_device(ieache_ctx* ctx, size_t count, const int32_t* d_x, c
 int ieache_pbs_multi(ieache_ctx* ctx, size_t count, const int32_t* x, const int32_t* test_polys, int32_t n_polys, const int32_t* poly_of,
                      const int32_t* factors, int32_t n_factors, const int32_t* bias, int32_t* out, int flags, ieache_stats* stats) {
     return guarded([&] {
-        // what can be judged without the context comes first
-        if (const char* e = pbs_multi_args_error(flags, n_polys, test_polys, n_factors, factors)) return fail(IEACHE_EINVAL, e);
-        const std::string bad_index = poly_of_error("pbs_multi", poly_of, count, n_polys);
-        if (!bad_index.empty()) return fail(IEACHE_EINVAL, bad_index);
-        if (!ctx || !x || !out) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_pbs_multi(ctx, count, x, test_polys, n_polys, poly_of, factors, n_factors, out, flags)) return rc;
         const bool woks = (flags & IEACHE_PBS_NO_KEYSWITCH) != 0;
         HostCall h(ctx, count);
         StagedRows dx = h.operand(kStageA, x), dout = h.results(count * (size_t)n_factors, woks);
@@ -763,6 +788,240 @@ int ieache_debug_keyswitch(ieache_ctx* ctx, size_t count, const int32_t* u, int3
         ctx->eval->debug_keyswitch(count, du.p, dout.p);
         dout.download(out, p.n + 1);
         return 0;
+    });
+}
+
+// ---- 2b. device group: one key on several GPUs, one call ----
+struct ieache_group {
+    std::unique_ptr<DeviceGroup> g;
+    bool precheck = true;  // "precheck" (ieache_group_set_option)
+    ieache_ctx* member(size_t m) const { return g->member(m); }
+    size_t size() const { return g->size(); }
+};
+
+extern "C++" {
+namespace {
+// what a member's entry point returned on its thread, carried to the caller's: g_err is thread_local
+struct MemberFailure {
+    size_t member;
+    int rc;
+    std::string message;
+};
+// One group call over `count` independent rows: call(member context, first row, rows, the member's statistics or null) -- an
+// existing host entry point on the member's slice of the caller's arrays -- for every member with rows, side by side
+// (run_sliced: member 0 on this thread, no thread outlives the call).  count == 0: member 0 alone makes the call.  -> 0, or
+// the code of the lowest-numbered member that failed, its message behind "member M (device D): ".
+template <class Call>
+int group_call(ieache_group* grp, size_t count, ieache_stats* stats, Call&& call) {
+    for (size_t m = 0; stats && m < grp->size(); m++) memset(&stats[m], 0, sizeof stats[m]);  // a member without rows reports zeros
+    if (count == 0) return call(grp->member(0), (size_t)0, (size_t)0, stats);
+    try {
+        run_sliced(grp->size(), count, [&](size_t m, size_t first, size_t rows) {
+            const int rc = call(grp->member(m), first, rows, stats ? stats + m : nullptr);
+            if (rc < 0) throw MemberFailure{m, rc, ieache_last_error()};
+        });
+    } catch (const MemberFailure& f) {
+        return fail(f.rc, grp->g->member_label(f.member) + f.message);
+    }
+    g_err.clear();
+    return 0;
+}
+template <class Make>
+ieache_group* make_group(Make&& make) {
+    ieache_group* grp = nullptr;
+    guarded([&] {
+        std::unique_ptr<ieache_group> made(new ieache_group);
+        made->g = make();
+        grp = made.release();
+        return 0;
+    });
+    return grp;
+}
+const char* const kNullGroup = "null group";
+// rows member 0 takes of `count`: the batch its circuit is chosen for
+size_t first_slice(const ieache_group* grp, size_t count) {
+    size_t first = 0, rows = 0;
+    shard_slice(count, grp->size(), 0, &first, &rows);
+    return rows;
+}
+// a member's share of a caller's array: `words` further on; a null array stays null for the member's own check to find
+template <class T>
+T* at(T* rows, size_t words) {
+    return rows ? rows + words : nullptr;
+}
+}  // namespace
+}  // extern "C++"
+
+ieache_group* ieache_group_create(const char* cloud_key_path, const int* devices, int n_devices) {
+    return make_group([&] {
+        DeviceGroup::validate_devices(devices, n_devices);
+        if (!cloud_key_path) throw std::invalid_argument("null cloud_key_path");
+        return DeviceGroup::from_file(cloud_key_path, devices, n_devices);
+    });
+}
+
+ieache_group* ieache_group_create_raw(const ieache_params* p, const int32_t* bk, const int32_t* ksk, const int* devices, int n_devices) {
+    return make_group([&] {
+        DeviceGroup::validate_devices(devices, n_devices);
+        if (!p) throw std::invalid_argument("null params");
+        return std::unique_ptr<DeviceGroup>(new DeviceGroup(to_params(*p), bk, ksk, devices, n_devices));
+    });
+}
+
+void ieache_group_destroy(ieache_group* g) {
+    try {
+        delete g;
+    } catch (...) {
+    }
+}
+
+int ieache_group_size(const ieache_group* g) { return g ? (int)g->size() : fail(IEACHE_EINVAL, kNullGroup); }
+
+int ieache_group_device(const ieache_group* g, int member) {
+    if (!g || member < 0 || (size_t)member >= g->size()) return fail(IEACHE_EINVAL, g ? "no such member" : kNullGroup);
+    return g->g->device((size_t)member);
+}
+
+ieache_ctx* ieache_group_ctx(ieache_group* g, int member) {
+    if (!g || member < 0 || (size_t)member >= g->size()) {
+        fail(IEACHE_EINVAL, g ? "no such member" : kNullGroup);
+        return nullptr;
+    }
+    return g->member((size_t)member);
+}
+
+int ieache_group_set_option(ieache_group* g, const char* name, int64_t value) {
+    if (!g || !name) return fail(IEACHE_EINVAL, g ? "null argument" : kNullGroup);
+    if (std::string(name) == "precheck") {
+        if (value != 0 && value != 1) return fail(IEACHE_EINVAL, "precheck takes 0 or 1");
+        g->precheck = value != 0;
+        return 0;
+    }
+    return guarded([&] {
+        std::vector<int64_t> before(g->size());
+        for (size_t m = 0; m < g->size(); m++)
+            if (const int rc = ieache_ctx_get_option(g->member(m), name, &before[m])) return rc;  // no such option
+        // member 0's row judges the value first; a later refusal (a hook that asks the device) puts the earlier members back
+        for (size_t m = 0; m < g->size(); m++) {
+            const int rc = ieache_ctx_set_option(g->member(m), name, value);
+            if (rc == 0) continue;
+            const std::string why = g->g->member_label(m) + ieache_last_error();
+            for (size_t j = 0; j < m; j++) (void)ieache_ctx_set_option(g->member(j), name, before[j]);
+            return fail(rc, why);
+        }
+        return 0;
+    });
+}
+
+int ieache_group_prepare_batch(ieache_group* g, int kind, int bits, size_t batch) {
+    if (!g) return fail(IEACHE_EINVAL, kNullGroup);
+    return guarded([&] {
+        CircuitCache::Ptr c;
+        if (g->precheck)
+            if (const int rc = check_prepare(g->member(0), kind, bits, first_slice(g, batch), &c)) return rc;
+        return group_call(g, batch, nullptr, [&](ieache_ctx* ctx, size_t, size_t n, ieache_stats*) { return ieache_prepare_batch(ctx, kind, bits, n); });
+    });
+}
+
+int ieache_group_eval_batch(ieache_group* g, int kind, int bits, size_t batch, const int32_t* in_lwe, int32_t* out_lwe, ieache_stats* stats) {
+    if (!g) return fail(IEACHE_EINVAL, kNullGroup);
+    return guarded([&] {
+        // rows per expression come from the circuit, so this check is made whatever "precheck" says
+        CircuitCache::Ptr c;
+        if (const int rc = check_batch(g->member(0), kind, bits, first_slice(g, batch), in_lwe, out_lwe, &c)) return rc;
+        const size_t S = (size_t)c->n_inputs * (size_t)(g->member(0)->eval->params().n + 1), T = c->outputs.size() * (size_t)(g->member(0)->eval->params().n + 1);
+        return group_call(g, batch, stats, [&](ieache_ctx* ctx, size_t first, size_t n, ieache_stats* st) {
+            return ieache_eval_batch(ctx, kind, bits, n, at(in_lwe, first * S), at(out_lwe, first * T), st);
+        });
+    });
+}
+
+int ieache_group_prepare_netlist(ieache_group* g, const ieache_netlist* nl, size_t batch) {
+    if (!g) return fail(IEACHE_EINVAL, kNullGroup);
+    return guarded([&] {
+        if (g->precheck)
+            if (const int rc = check_rows({g->member(0), nl})) return rc;
+        return group_call(g, batch, nullptr, [&](ieache_ctx* ctx, size_t, size_t n, ieache_stats*) { return ieache_prepare_netlist(ctx, nl, n); });
+    });
+}
+
+int ieache_group_eval_netlist(ieache_group* g, const ieache_netlist* nl, size_t batch, const int32_t* in_lwe, int32_t* out_lwe, ieache_stats* stats) {
+    if (!g) return fail(IEACHE_EINVAL, kNullGroup);
+    return guarded([&] {
+        if (const int rc = check_rows({g->member(0), nl, in_lwe, out_lwe})) return rc;  // the netlist gives the rows per expression
+        const size_t W = (size_t)g->member(0)->eval->params().n + 1, S = (size_t)nl->circuit.n_inputs * W, T = nl->circuit.outputs.size() * W;
+        return group_call(g, batch, stats, [&](ieache_ctx* ctx, size_t first, size_t n, ieache_stats* st) {
+            return ieache_eval_netlist(ctx, nl, n, at(in_lwe, first * S), at(out_lwe, first * T), st);
+        });
+    });
+}
+
+int ieache_group_gates(ieache_group* g, int gate_type, size_t count, const int32_t* a, const int32_t* b, int32_t* out, ieache_stats* stats) {
+    if (!g) return fail(IEACHE_EINVAL, kNullGroup);
+    return guarded([&] {
+        if (g->precheck)
+            if (const int rc = check_gates(g->member(0), gate_type, a, b, out)) return rc;
+        const size_t W = (size_t)g->member(0)->eval->params().n + 1;
+        return group_call(g, count, stats, [&](ieache_ctx* ctx, size_t first, size_t n, ieache_stats* st) {
+            return ieache_gates(ctx, gate_type, n, at(a, first * W), at(b, first * W), at(out, first * W), st);
+        });
+    });
+}
+
+int ieache_group_gates3(ieache_group* g, int gate_type, size_t count, const int32_t* a, const int32_t* b, const int32_t* c, int32_t* out,
+                        ieache_stats* stats) {
+    if (!g) return fail(IEACHE_EINVAL, kNullGroup);
+    return guarded([&] {
+        if (g->precheck)
+            if (const int rc = check_gates3(g->member(0), gate_type, a, b, c, out)) return rc;
+        const size_t W = (size_t)g->member(0)->eval->params().n + 1;
+        return group_call(g, count, stats, [&](ieache_ctx* ctx, size_t first, size_t n, ieache_stats* st) {
+            return ieache_gates3(ctx, gate_type, n, at(a, first * W), at(b, first * W), at(c, first * W), at(out, first * W), st);
+        });
+    });
+}
+
+int ieache_group_mux(ieache_group* g, size_t count, const int32_t* a, const int32_t* b, const int32_t* c, int32_t* out, ieache_stats* stats) {
+    if (!g) return fail(IEACHE_EINVAL, kNullGroup);
+    return guarded([&] {
+        if (g->precheck)
+            if (const int rc = check_rows({g->member(0), a, b, c, out})) return rc;
+        const size_t W = (size_t)g->member(0)->eval->params().n + 1;
+        return group_call(g, count, stats, [&](ieache_ctx* ctx, size_t first, size_t n, ieache_stats* st) {
+            return ieache_mux(ctx, n, at(a, first * W), at(b, first * W), at(c, first * W), at(out, first * W), st);
+        });
+    });
+}
+
+int ieache_group_pbs(ieache_group* g, size_t count, const int32_t* x, const int32_t* test_polys, int32_t n_polys, const int32_t* poly_of,
+                     int32_t* out, int flags, ieache_stats* stats) {
+    if (!g) return fail(IEACHE_EINVAL, kNullGroup);
+    return guarded([&] {
+        if (g->precheck)
+            if (const int rc = check_pbs(g->member(0), count, x, test_polys, n_polys, poly_of, out, flags)) return rc;
+        // rows in: n + 1 words; rows out: N + 1 without the key switch.  The table goes to every member whole, the indices with the rows.
+        const Params& p = g->member(0)->eval->params();
+        const size_t W = (size_t)p.n + 1, V = (flags & IEACHE_PBS_NO_KEYSWITCH) ? (size_t)p.N + 1 : W;
+        return group_call(g, count, stats, [&](ieache_ctx* ctx, size_t first, size_t n, ieache_stats* st) {
+            return ieache_pbs(ctx, n, at(x, first * W), test_polys, n_polys, at(poly_of, first), at(out, first * V), flags, st);
+        });
+    });
+}
+
+int ieache_group_pbs_multi(ieache_group* g, size_t count, const int32_t* x, const int32_t* test_polys, int32_t n_polys, const int32_t* poly_of,
+                           const int32_t* factors, int32_t n_factors, const int32_t* bias, int32_t* out, int flags, ieache_stats* stats) {
+    if (!g) return fail(IEACHE_EINVAL, kNullGroup);
+    return guarded([&] {
+        if (g->precheck)
+            if (const int rc = check_pbs_multi(g->member(0), count, x, test_polys, n_polys, poly_of, factors, n_factors, out, flags)) return rc;
+        // as ieache_group_pbs; factors and bias go to every member whole, and a member's output starts at row first x n_factors
+        const Params& p = g->member(0)->eval->params();
+        const size_t W = (size_t)p.n + 1, V = (flags & IEACHE_PBS_NO_KEYSWITCH) ? (size_t)p.N + 1 : W;
+        const size_t F = n_factors > 0 ? (size_t)n_factors : 0;  // a refused n_factors (precheck off) moves no pointer
+        return group_call(g, count, stats, [&](ieache_ctx* ctx, size_t first, size_t n, ieache_stats* st) {
+            return ieache_pbs_multi(ctx, n, at(x, first * W), test_polys, n_polys, at(poly_of, first), factors, n_factors, bias,
+                                    at(out, first * F * V), flags, st);
+        });
     });
 }
 
@@ -1003,7 +1262,7 @@ int ieache_debug_mix_plan(int cus, int n, int64_t gates, int s1, int ratio_x100,
 
 int ieache_shard_slice(size_t total, size_t parts, size_t part, size_t* first, size_t* count) {
     if (!first || !count || parts == 0 || part >= parts) return fail(IEACHE_EINVAL, "bad shard arguments");
-    daemon_shard(total, parts, part, first, count);
+    shard_slice(total, parts, part, first, count);
     return 0;
 }
 
@@ -1012,7 +1271,7 @@ int64_t ieache_serve_devices(const char* socket_path, const char* cloud_key_path
     int64_t served = 0;
     const int rc = guarded([&] {
         if (!socket_path || !cloud_key_path || !devices) return fail(IEACHE_EINVAL, "null argument");
-        if (n_devices < 1 || n_devices > 64) return fail(IEACHE_EINVAL, "1 .. 64 devices");
+        DeviceGroup::validate_devices(devices, n_devices);  // the daemon's evaluators are a device group
         DaemonConfig cfg;
         cfg.socket_path = socket_path;
         cfg.cloud_key_path = cloud_key_path;

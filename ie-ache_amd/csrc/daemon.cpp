@@ -17,14 +17,14 @@
 #include <memory>
 #include <new>
 #include <stdexcept>
-#include <system_error>
-#include <thread>
 #include <tuple>
 
 #include "../../include/ieache.h"
 #include "cloud_run.h"
 #include "codec.h"
 #include "evaluator.h"
+#include "group.h"
+#include "group_run.h"
 #include "tfhe_host.h"
 
 namespace ieache {
@@ -237,7 +237,7 @@ public:
                 case DAEMON_STATS: {
                     char buf[200];
                     snprintf(buf, sizeof buf, "evaluations=%lld batched_requests=%lld largest_batch=%lld devices=%zu sharded_evaluations=%lld device_jobs=",
-                             (long long)batches, (long long)batched_requests, (long long)largest_batch, evals_.size(), (long long)sharded);
+                             (long long)batches, (long long)batched_requests, (long long)largest_batch, group_ ? group_->size() : (size_t)0, (long long)sharded);
                     *log = buf;
                     for (size_t d = 0; d < device_jobs_.size(); d++) *log += (d ? "," : "") + std::to_string(device_jobs_[d]);
                     return 0;
@@ -265,58 +265,38 @@ private:
         if (!id.valid) throw CodecError("cannot open " + path);
         CloudKeyData ck;
         load_cloud_key(path, &ck);  // read and parsed once, whatever the number of devices
-        evals_.clear();  // frees the old key's 290 MB per device before the new one is uploaded
+        const std::vector<int> devs = cfg_.devices.empty() ? std::vector<int>{cfg_.device} : cfg_.devices;
+        DeviceGroup::validate(ck.p, devs.data(), (int)devs.size());  // before the resident key is given up
         eval_ = nullptr;
-        std::vector<int> devs = cfg_.devices.empty() ? std::vector<int>{cfg_.device} : cfg_.devices;
-        for (int dev : devs) {
-            evals_.emplace_back(new Evaluator(ck.p, dev));
-            evals_.back()->load_keys_host(ck.bk.data(), ck.ksk.data());
-        }
-        eval_ = evals_[0].get();
-        device_jobs_.assign(evals_.size(), 0);
+        group_.reset();  // frees the old key's 290 MB per device before the new one is uploaded
+        group_.reset(new DeviceGroup(ck.p, ck.bk.data(), ck.ksk.data(), devs.data(), (int)devs.size()));
+        eval_ = group_->member(0)->eval.get();
+        device_jobs_.assign(group_->size(), 0);
         key_id_ = id;
         key_path_ = path;
     }
 
-    // The jobs of one circuit over the daemon's devices: contiguous slices (daemon_shard), one host thread per device that
-    // has a slice, each driving its own evaluator (own stream, own key copy); nothing is exchanged between devices.  A
-    // failure on any device fails the evaluation (the first exception is rethrown once every thread has finished).
+    // The jobs of one circuit over the daemon's device group: contiguous slices, one host thread per member that has a slice
+    // (run_sliced, group_run.h), each driving its own evaluator (own stream, own key copy); nothing is exchanged between
+    // devices.  A failure on any device fails the evaluation (the lowest-numbered member's exception is rethrown once every
+    // thread has finished).
     void eval_sharded(const std::vector<CloudJob*>& jobs, std::vector<std::vector<Torus32>>* outs) {
-        const size_t parts = std::min(evals_.size(), jobs.size());
+        const size_t parts = std::min(group_->size(), jobs.size());
         if (parts <= 1) {
-            cloud_eval_jobs(*evals_[0], jobs, outs, nullptr);
+            cloud_eval_jobs(*eval_, jobs, outs, nullptr);
             device_jobs_[0] += (int64_t)jobs.size();
             return;
         }
         outs->assign(jobs.size(), {});
-        std::vector<std::vector<std::vector<Torus32>>> part_outs(parts);
-        std::vector<std::exception_ptr> errors(parts);
-        auto run_part = [&](size_t d) {
-            try {
-                size_t first = 0, count = 0;
-                daemon_shard(jobs.size(), parts, d, &first, &count);
-                const std::vector<CloudJob*> mine(jobs.begin() + first, jobs.begin() + first + count);
-                cloud_eval_jobs(*evals_[d], mine, &part_outs[d], nullptr);
-            } catch (...) {
-                errors[d] = std::current_exception();
-            }
-        };
-        std::vector<std::thread> threads;
-        for (size_t d = 1; d < parts; d++) {
-            try {
-                threads.emplace_back(run_part, d);
-            } catch (const std::system_error&) {
-                run_part(d);  // no thread to be had: this slice runs here, after the ones already started
-            }
-        }
-        run_part(0);  // the first slice on the serving thread itself
-        for (std::thread& t : threads) t.join();
-        for (const std::exception_ptr& e : errors)
-            if (e) std::rethrow_exception(e);
-        for (size_t d = 0; d < parts; d++) {
+        run_sliced(parts, jobs.size(), [&](size_t d, size_t first, size_t count) {
+            const std::vector<CloudJob*> mine(jobs.begin() + first, jobs.begin() + first + count);
+            std::vector<std::vector<Torus32>> part_outs;
+            cloud_eval_jobs(*group_->member(d)->eval, mine, &part_outs, nullptr);
+            for (size_t i = 0; i < count; i++) (*outs)[first + i] = std::move(part_outs[i]);  // its own rows of the answer
+        });
+        for (size_t d = 0; d < parts; d++) {  // counted once the whole evaluation has succeeded
             size_t first = 0, count = 0;
-            daemon_shard(jobs.size(), parts, d, &first, &count);
-            for (size_t i = 0; i < count; i++) (*outs)[first + i] = std::move(part_outs[d][i]);
+            shard_slice(jobs.size(), parts, d, &first, &count);
             device_jobs_[d] += (int64_t)count;
         }
         sharded++;
@@ -409,7 +389,7 @@ private:
                     try {
                         if (members.size() > 1)
                         fprintf(r->log.f, "cloudd: evaluated together with %zu other request(s)%s\n", members.size() - 1,
-                                evals_.size() > 1 ? (" on " + std::to_string(std::min(evals_.size(), members.size())) + " devices").c_str() : "");
+                                group_->size() > 1 ? (" on " + std::to_string(std::min(group_->size(), members.size())) + " devices").c_str() : "");
                         cloud_finish(r->the_io(), r->job, outs[i].data(), outs[i].size() / ((size_t)r->job.params.n + 1), dt);
                         r->reply_ok(0);
                     } catch (...) {
@@ -425,8 +405,8 @@ private:
     }
 
     DaemonConfig cfg_;
-    std::vector<std::unique_ptr<Evaluator>> evals_;  // one per configured device
-    Evaluator* eval_ = nullptr;                      // evals_[0]: parameters, single-request path
+    std::unique_ptr<DeviceGroup> group_;  // one member per configured device (members that share a card: "br_mix" = 0)
+    Evaluator* eval_ = nullptr;           // member 0's: parameters, single-request path
     std::vector<int64_t> device_jobs_;
     FileId key_id_;
     std::string key_path_;
@@ -435,17 +415,6 @@ private:
 };
 
 }  // namespace
-
-void daemon_shard(size_t total, size_t parts, size_t part, size_t* first, size_t* count) {
-    if (parts == 0 || part >= parts) {
-        *first = total;
-        *count = 0;
-        return;
-    }
-    const size_t base = total / parts, extra = total % parts;
-    *first = part * base + std::min(part, extra);
-    *count = base + (part < extra ? 1 : 0);
-}
 
 int64_t daemon_serve(const DaemonConfig& cfg) {
     sockaddr_un addr = make_addr(cfg.socket_path);

@@ -40,11 +40,12 @@ struct DaemonConfig {
     std::string cloud_key_path;  // loaded before the first accept
     std::string nbit_key_path;   // for RUN_DATA; empty = nbit.key next to cloud.key
     int device = 0;
-    // Several GPUs (cloudd --devices 0,1,... / IEACHE_DEVICES): one evaluator per listed device, the cloud key read from
-    // disk once and uploaded to each; the same-circuit jobs of a round are cut into contiguous slices, one per device
-    // (daemon_shard, the rule ie-ache_amd/parallel.py's shard_slice applies across ranks), evaluated concurrently -- no
-    // exchange between devices -- and answered in request order.  A device may be listed twice (two contexts on one card:
-    // how the one-GPU test box exercises this path).  Empty = {device}.
+    // Several GPUs (cloudd --devices 0,1,... / IEACHE_DEVICES): a device group (group.h) -- one evaluator per listed device,
+    // 1 .. kGroupMaxDevices of them, the cloud key read from disk once and uploaded to each; the same-circuit jobs of a round
+    // are cut into contiguous slices, one per device (shard_slice in group_run.h, the rule ie-ache_amd/parallel.py's
+    // shard_slice applies across ranks), evaluated concurrently -- no exchange between devices -- and answered in request
+    // order.  A device may be listed twice (two contexts on one card: how the one-GPU test box exercises this path; such
+    // members run with "br_mix" = 0).  Empty = {device}.
     std::vector<int> devices;
     int64_t max_requests = -1;   // < 0: until SHUTDOWN
     bool announce = true;        // print "cloudd: ready on <path>" once listening
@@ -53,10 +54,6 @@ struct DaemonConfig {
     int batch_window_ms = 0;
     int max_batch = 256;
 };
-
-// Contiguous slice [first, first + count) of `total` jobs that part `part` of `parts` takes: sizes differ by at most one, the
-// first total % parts parts take the extra job (= parallel.shard_slice).
-void daemon_shard(size_t total, size_t parts, size_t part, size_t* first, size_t* count);
 
 // Blocks serving requests; returns the number served.  Throws on setup failure
 // (key load, GPU, bind).  A failing request is answered with a negative rc and

@@ -23,6 +23,7 @@ PBS_MULTI_MAX_FACTORS = 64  # most factor polynomials of one ieache_pbs_multi* c
 PBS_NO_KEYSWITCH = 1  # flag of ieache_pbs*: the extracted samples are the result (tfhe_bootstrap_woKS_FFT)
 GATE_MAJ3, GATE_XOR3 = 32, 33  # three-input gates of one bootstrap each (codes outside 0 .. GATE_TYPES-1: include/ieache.h)
 CIRC_ADD_FA, CIRC_SUB_FA, CIRC_RSUB_FA, CIRC_MUL_FA = 16, 17, 18, 19  # on the MAJ3 / XOR3 full adder (decrypt-identical)
+GROUP_MAX_DEVICES = 16  # most members of a device group (IEACHE_GROUP_MAX_DEVICES)
 # references inside a Netlist (IEACHE_NET_*): wire << 1 | negated, or a constant
 FALSE, TRUE = -2, -1
 
@@ -179,6 +180,27 @@ def lib():
     L.ieache_prepare_netlist.argtypes = [vp, vp, C.c_size_t]
     L.ieache_eval_netlist.argtypes = [vp, vp, C.c_size_t, i32p, i32p, sp]
     L.ieache_eval_netlist_device.argtypes = [vp, vp, C.c_size_t, vp, vp, sp]
+    ip = C.POINTER(C.c_int)
+    L.ieache_group_create.restype = vp
+    L.ieache_group_create.argtypes = [C.c_char_p, ip, C.c_int]
+    L.ieache_group_create_raw.restype = vp
+    L.ieache_group_create_raw.argtypes = [pp, i32p, i32p, ip, C.c_int]
+    L.ieache_group_destroy.restype = None
+    L.ieache_group_destroy.argtypes = [vp]
+    L.ieache_group_size.argtypes = [vp]
+    L.ieache_group_device.argtypes = [vp, C.c_int]
+    L.ieache_group_ctx.restype = vp
+    L.ieache_group_ctx.argtypes = [vp, C.c_int]
+    L.ieache_group_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
+    L.ieache_group_prepare_batch.argtypes = [vp, C.c_int, C.c_int, C.c_size_t]
+    L.ieache_group_eval_batch.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, i32p, i32p, sp]
+    L.ieache_group_prepare_netlist.argtypes = [vp, vp, C.c_size_t]
+    L.ieache_group_eval_netlist.argtypes = [vp, vp, C.c_size_t, i32p, i32p, sp]
+    L.ieache_group_gates.argtypes = [vp, C.c_int, C.c_size_t, i32p, i32p, i32p, sp]
+    L.ieache_group_gates3.argtypes = [vp, C.c_int, C.c_size_t, i32p, i32p, i32p, i32p, sp]
+    L.ieache_group_mux.argtypes = [vp, C.c_size_t, i32p, i32p, i32p, i32p, sp]
+    L.ieache_group_pbs.argtypes = [vp, C.c_size_t, i32p, i32p, C.c_int32, i32p, i32p, C.c_int, sp]
+    L.ieache_group_pbs_multi.argtypes = [vp, C.c_size_t, i32p, i32p, C.c_int32, i32p, i32p, C.c_int32, i32p, i32p, C.c_int, sp]
     L.ieache_debug_blind_rotate.argtypes = [vp, C.c_size_t, i32p, i32p, C.c_int32]
     L.ieache_debug_keyswitch.argtypes = [vp, C.c_size_t, i32p, i32p]
     L.ieache_keygen_raw.argtypes = [pp, u32p, C.c_int, i32p, i32p, i32p, i32p]
@@ -600,4 +622,187 @@ class Context:
         u = np.ascontiguousarray(u, dtype=np.int32).reshape(-1, self.params.N + 1)
         out = np.zeros((u.shape[0], self.params.n + 1), dtype=np.int32)
         check(lib().ieache_debug_keyswitch(self.h, u.shape[0], _i32(u), _i32(out)))
+        return out
+
+
+class _MemberContext(Context):
+    """A member of a Group as a Context (ieache_group_ctx): borrowed -- closing it only forgets the handle, the group destroys it."""
+
+    def close(self):
+        self.h = None
+
+    __del__ = close
+
+
+class _MemberStats:
+    """The stats= argument of a Group call: the ieache_stats array the call fills, handed back as one Stats per member."""
+
+    def __init__(self, stats, members):
+        self.into = stats
+        self.array = (Stats * members)() if stats is not None else None
+
+    @property
+    def ref(self):
+        return self.array  # None: a null pointer
+
+    def deliver(self):
+        if self.into is not None:
+            self.into[:] = [Stats.from_buffer_copy(s) for s in self.array]
+
+
+class Group:
+    """The cloud key resident on several GPUs behind one handle (ieache_group): every host-buffer call of Context, cut into
+    contiguous slices of rows or expressions, one per member, evaluated side by side on host threads of the library.
+
+        with Group.from_file("cloud.key", range(device_count())) as g:
+            out = g.eval_batch(CIRC_ADD, 32, in_lwe)
+
+    Outputs equal a Context's word for word.  A device may be listed more than once (several contexts on one card); such
+    members start with option "br_mix" = 0 (include/ieache.h, section 2b).  One call at a time: not thread-safe.  Every
+    method takes stats=: a list the call fills with one Stats per member (all zero for a member whose slice was empty)."""
+
+    def __init__(self, handle):
+        if not handle:
+            msg = lib().ieache_last_error().decode()
+            # a NULL handle carries no code: a member that could not be made is named first, everything else is an argument
+            raise IeacheError(-19 if msg.startswith("member ") else -22, msg)
+        self.h = handle
+        n = check(lib().ieache_group_size(self.h))
+        self.devices = tuple(check(lib().ieache_group_device(self.h, m)) for m in range(n))
+        # borrowed views: they do not destroy, and lose their handle when the group closes
+        self.contexts = tuple(_MemberContext(lib().ieache_group_ctx(self.h, m)) for m in range(n))
+        self.params = self.contexts[0].params
+        self._fold = False
+
+    @staticmethod
+    def _device_list(devices):
+        devices = [int(d) for d in devices]
+        return (C.c_int * max(len(devices), 1))(*devices), len(devices)
+
+    @classmethod
+    def from_file(cls, cloud_key_path, devices):
+        arr, n = cls._device_list(devices)
+        return cls(lib().ieache_group_create(os.fsencode(cloud_key_path), arr, n))
+
+    @classmethod
+    def from_arrays(cls, params, bk, ksk, devices):
+        bk = np.ascontiguousarray(bk, dtype=np.int32)
+        ksk = np.ascontiguousarray(ksk, dtype=np.int32)
+        assert bk.size == params.bk_count and ksk.size == params.ksk_count
+        arr, n = cls._device_list(devices)
+        return cls(lib().ieache_group_create_raw(C.byref(params), _i32(bk), _i32(ksk), arr, n))
+
+    def close(self):
+        if getattr(self, "h", None):
+            for c in self.contexts:
+                c.close()
+            lib().ieache_group_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __len__(self):
+        return len(self.devices)
+
+    def set_option(self, name, value):
+        """Context.set_option on every member, all or none: a value any member refuses raises and changes no member."""
+        check(lib().ieache_group_set_option(self.h, name.encode(), int(value)))
+        if name == "fold_constants":
+            self._fold = bool(value)
+            for c in self.contexts:
+                c._fold = bool(value)
+
+    def _rows(self, *arrays):
+        arrays = [np.ascontiguousarray(v, dtype=np.int32) for v in arrays]
+        assert all(v.shape == arrays[0].shape for v in arrays) and arrays[0].shape[-1] == self.params.n + 1
+        return arrays, arrays[0].size // (self.params.n + 1)
+
+    def prepare(self, kind, bits, batch):
+        """Context.prepare on every member, each for its slice of `batch` expressions."""
+        check(lib().ieache_group_prepare_batch(self.h, kind, bits, batch))
+
+    def prepare_netlist(self, nl, batch):
+        check(lib().ieache_group_prepare_netlist(self.h, nl.h, batch))
+
+    def eval_batch(self, kind, bits, in_lwe, stats=None):
+        """in_lwe [batch][n_inputs][n+1] int32 on the host -> [batch][n_outputs][n+1], as Context.eval_batch."""
+        info = circuit_info(kind, bits, self._fold)
+        in_lwe = np.ascontiguousarray(in_lwe, dtype=np.int32)
+        batch = in_lwe.shape[0]
+        assert in_lwe.shape == (batch, info.n_inputs, self.params.n + 1), in_lwe.shape
+        out = np.zeros((batch, info.n_outputs, self.params.n + 1), dtype=np.int32)
+        st = _MemberStats(stats, len(self))
+        check(lib().ieache_group_eval_batch(self.h, kind, bits, batch, _i32(in_lwe), _i32(out), st.ref))
+        st.deliver()
+        return out
+
+    def eval_netlist(self, nl, in_lwe, stats=None):
+        """One CompiledNetlist, read by every member, over a batch: as Context.eval_netlist."""
+        info = nl.info()
+        in_lwe = np.ascontiguousarray(in_lwe, dtype=np.int32)
+        batch = in_lwe.shape[0]
+        assert in_lwe.shape == (batch, info.n_inputs, self.params.n + 1), in_lwe.shape
+        out = np.zeros((batch, info.n_outputs, self.params.n + 1), dtype=np.int32)
+        st = _MemberStats(stats, len(self))
+        check(lib().ieache_group_eval_netlist(self.h, nl.h, batch, _i32(in_lwe), _i32(out), st.ref))
+        st.deliver()
+        return out
+
+    def gates(self, gate_type, a, b, stats=None):
+        (a, b), count = self._rows(a, b)
+        out = np.zeros_like(a)
+        st = _MemberStats(stats, len(self))
+        check(lib().ieache_group_gates(self.h, gate_type, count, _i32(a), _i32(b), _i32(out), st.ref))
+        st.deliver()
+        return out
+
+    def gates3(self, gate_type, a, b, c, stats=None):
+        (a, b, c), count = self._rows(a, b, c)
+        out = np.zeros_like(a)
+        st = _MemberStats(stats, len(self))
+        check(lib().ieache_group_gates3(self.h, gate_type, count, _i32(a), _i32(b), _i32(c), _i32(out), st.ref))
+        st.deliver()
+        return out
+
+    def mux(self, a, b, c, stats=None):
+        (a, b, c), count = self._rows(a, b, c)
+        out = np.zeros_like(a)
+        st = _MemberStats(stats, len(self))
+        check(lib().ieache_group_mux(self.h, count, _i32(a), _i32(b), _i32(c), _i32(out), st.ref))
+        st.deliver()
+        return out
+
+    def pbs(self, x, test_polys, poly_of=None, keyswitch=True, stats=None):
+        """Context.pbs: the test polynomials go to every member whole, poly_of is cut with the rows."""
+        x = np.ascontiguousarray(x, dtype=np.int32).reshape(-1, self.params.n + 1)
+        tv = np.ascontiguousarray(test_polys, dtype=np.int32).reshape(-1, self.params.N)
+        of = None if poly_of is None else np.ascontiguousarray(poly_of, dtype=np.int32).reshape(-1)
+        assert of is None or of.shape[0] == x.shape[0]
+        out = np.zeros((x.shape[0], (self.params.n if keyswitch else self.params.N) + 1), dtype=np.int32)
+        st = _MemberStats(stats, len(self))
+        check(lib().ieache_group_pbs(self.h, x.shape[0], _i32(x), _i32(tv), tv.shape[0], None if of is None else _i32(of), _i32(out),
+                                     0 if keyswitch else PBS_NO_KEYSWITCH, st.ref))
+        st.deliver()
+        return out
+
+    def pbs_multi(self, x, test_polys, factors, poly_of=None, bias=None, keyswitch=True, stats=None):
+        """Context.pbs_multi: test polynomials, factors and bias go to every member whole -> [count][n_factors][rows]."""
+        x = np.ascontiguousarray(x, dtype=np.int32).reshape(-1, self.params.n + 1)
+        tv = np.ascontiguousarray(test_polys, dtype=np.int32).reshape(-1, self.params.N)
+        fa = np.ascontiguousarray(factors, dtype=np.int32).reshape(-1, self.params.N)
+        of = None if poly_of is None else np.ascontiguousarray(poly_of, dtype=np.int32).reshape(-1)
+        bi = None if bias is None else np.ascontiguousarray(bias, dtype=np.int32).reshape(-1)
+        assert of is None or of.shape[0] == x.shape[0]
+        assert bi is None or bi.shape[0] == fa.shape[0]
+        out = np.zeros((x.shape[0], fa.shape[0], (self.params.n if keyswitch else self.params.N) + 1), dtype=np.int32)
+        st = _MemberStats(stats, len(self))
+        check(lib().ieache_group_pbs_multi(self.h, x.shape[0], _i32(x), _i32(tv), tv.shape[0], None if of is None else _i32(of), _i32(fa),
+                                           fa.shape[0], None if bi is None else _i32(bi), _i32(out), 0 if keyswitch else PBS_NO_KEYSWITCH, st.ref))
+        st.deliver()
         return out

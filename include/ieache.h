@@ -7,7 +7,7 @@
  * every function returns 0 on success or a negative IEACHE_E* code (the
  * process-contract function returns the reference's exit codes 0 / 126), and
  * ieache_last_error() holds the message.  A context is not thread-safe; use one
- * per process per GPU.
+ * per process per GPU, or a device group (section 2b) for several GPUs behind one handle.
  *
  * Streams: a context launches on its own non-blocking HIP stream
  * (ieache_ctx_stream).  Every entry point that takes DEVICE pointers
@@ -168,7 +168,8 @@ int ieache_cloud_run(const char* workdir);
  * ------------------------------------------------------------------ */
 typedef struct ieache_ctx ieache_ctx;
 
-/* from a cloud.key file */
+/* from a cloud.key file.  The second argument is a device INDEX: one GPU per context -- not the `ngpus` of SURVEY.md 8(b)'s
+ * ieache_ctx_create(cloud_key_path, int ngpus).  A device COUNT lives in a device group (section 2b). */
 ieache_ctx* ieache_ctx_create(const char* cloud_key_path, int device);
 /* from raw arrays on the host: bk [n][(k+1)l][k+1][N], ksk [kN][t][base][n+1] */
 ieache_ctx* ieache_ctx_create_raw(const ieache_params* p, const int32_t* bk, const int32_t* ksk, int device);
@@ -231,6 +232,88 @@ const char* ieache_ctx_kernel_variant(const ieache_ctx* ctx);
  * current options (launch sizes select different kernels: docs in csrc/br_plan.h).  Like
  * ieache_ctx_kernel_variant the string lives in the context until the next such call. */
 const char* ieache_ctx_kernel_for_launch(const ieache_ctx* ctx, int64_t gates);
+
+/* ------------------------------------------------------------------ *
+ * 2b. Device group: the cloud key resident on SEVERAL GPUs of the     *
+ *    node behind one handle, and every host-buffer call of sections   *
+ *    3 and 3b on all of them at once.  What SURVEY.md 8(b) specified  *
+ *    as ieache_ctx_create(cloud_key_path, ngpus) + ieache_eval_batch: *
+ *    one handle, N GPUs, one call -- for a caller at                  *
+ *    dragonfly_cipher_cloud.py:1233 that holds a batch and wants the  *
+ *    whole node without a torchrun job or the socket daemon.          *
+ * ------------------------------------------------------------------ */
+/* A group owns one member per entry of its device list.  A member IS an ieache_ctx (own evaluator, streams, scratch, key
+ * copy, circuit cache and options).  A call is `count` independent rows or expressions: member m evaluates the contiguous
+ * slice ieache_shard_slice(count, members, m) gives it, on a host thread of its own (member 0 on the caller's), through the
+ * context form of the same call.  Nothing crosses GPUs, and outputs equal the context form's word for word: every row goes
+ * through the same circuit and kernels wherever it runs.
+ * One call at a time: a group, like a context, is NOT thread-safe.  Its member contexts (ieache_group_ctx) may be used
+ * directly between group calls, never during one.  No thread outlives a call.
+ * Members that share a card: a device may be listed more than once (two or three contexts on one GPU, as cloudd --devices 0,0).
+ * A member whose device index occurs more than once in the list is created with option "br_mix" = 0: the rotation of roles
+ * assumes that its context has the chip to itself, and each of two contexts on a card would open three streams for it.
+ * Output bits do not depend on the option; ieache_group_set_option(g, "br_mix", 1) overrides the rule.
+ * Rates: profiles/group_rates.txt (scripts/group_rates.py) is the only record; several distinct devices are unmeasured. */
+typedef struct ieache_group ieache_group;
+#define IEACHE_GROUP_MAX_DEVICES 16
+/* Replaces N calls of new_tfheGateBootstrappingCloudKeySet_fromFile (cloud.c:656-658), one per ./cloud process per GPU: the key
+ * file is read and parsed ONCE, then uploaded to every listed device.  -> NULL with ieache_last_error() naming the argument
+ * for n_devices outside 1 .. IEACHE_GROUP_MAX_DEVICES, a NULL device list, a negative index or an unsupported parameter set
+ * -- all judged before the first HIP call, so a machine without a GPU refuses them the same way -- and naming member and
+ * device when a member cannot be made (the members already made are destroyed). */
+ieache_group* ieache_group_create(const char* cloud_key_path, const int* devices, int n_devices);
+/* from raw arrays on the host, as ieache_ctx_create_raw */
+ieache_group* ieache_group_create_raw(const ieache_params* p, const int32_t* bk, const int32_t* ksk, const int* devices, int n_devices);
+void ieache_group_destroy(ieache_group* g);
+int ieache_group_size(const ieache_group* g);                 /* members */
+int ieache_group_device(const ieache_group* g, int member);   /* the device index of one */
+/* the member as a context, for everything section 2 offers per context (options read back, statistics, kernel names).
+ * Borrowed: it dies with the group and must not be given to ieache_ctx_destroy. */
+ieache_ctx* ieache_group_ctx(ieache_group* g, int member);
+/* ieache_ctx_set_option on every member, all or none: member 0's table row judges the value first, and a refusal -- there or,
+ * for an option whose hook asks the device, at a later member, after which the earlier members get their old value back --
+ * returns IEACHE_EINVAL with no member changed.  One name belongs to this layer, a test hook: "precheck" (0/1, default 1);
+ * 0 = the evaluating forms below leave value checks to each member's own call, on its thread. */
+int ieache_group_set_option(ieache_group* g, const char* name, int64_t value);
+/* The group forms of the host-buffer entry points of sections 3 and 3b: the context form's arguments behind the group, same
+ * buffer shapes, same error conventions.  (The *_device forms have no group form: device buffers would need cross-device
+ * stream ordering and peer copies.)
+ * Slicing: per-row arrays (operands, outputs, poly_of) are cut with the rows; shared tables (test polynomials, factors, bias,
+ * a compiled netlist) go to every member whole; ieache_group_pbs_multi's output slice starts at row first x n_factors; rows
+ * are N + 1 words under IEACHE_PBS_NO_KEYSWITCH.  ieache_group_prepare_* prepares each member for its slice size.
+ * stats: NULL, or an array of ieache_group_size() records: stats[m] is member m's own, all zero when its slice was empty.
+ * count == 0: member 0 alone makes the call and its return value is the group's.
+ * Errors: arguments are checked once, before any thread starts, by the checks of the context forms.  If members fail, the
+ * return code is that of the lowest-numbered one and ieache_last_error() -- on the CALLING thread -- carries its message
+ * behind "member M (device D): ".  The output buffer's contents are then unspecified; the group stays usable.
+ * A NULL group: IEACHE_EINVAL. */
+/* replaces ieache_prepare_batch per GPU */
+int ieache_group_prepare_batch(ieache_group* g, int kind, int bits, size_t batch);
+/* replaces ieache_eval_batch per GPU = the add()/mul32()/... call trees of cloud.c:18-647 over a batch, on the whole node */
+int ieache_group_eval_batch(ieache_group* g, int kind, int bits, size_t batch, const int32_t* in_lwe, int32_t* out_lwe,
+                            ieache_stats* stats /* [n members] or NULL */);
+/* replace ieache_prepare_netlist / ieache_eval_netlist per GPU (section 3b; the netlist is declared there).  ONE compiled
+ * netlist is read by all members at once: it is immutable after ieache_netlist_create. */
+struct ieache_netlist;
+int ieache_group_prepare_netlist(ieache_group* g, const struct ieache_netlist* nl, size_t batch);
+int ieache_group_eval_netlist(ieache_group* g, const struct ieache_netlist* nl, size_t batch, const int32_t* in_lwe, int32_t* out_lwe,
+                              ieache_stats* stats /* [n members] or NULL */);
+/* replaces ieache_gates per GPU = bootsAND / bootsXOR / ... (cloud.c:30-43,159) over `count` gates */
+int ieache_group_gates(ieache_group* g, int gate_type, size_t count, const int32_t* a, const int32_t* b, int32_t* out,
+                       ieache_stats* stats /* [n members] or NULL */);
+/* replaces ieache_gates3 per GPU (MAJ3 / XOR3; no libtfhe counterpart) */
+int ieache_group_gates3(ieache_group* g, int gate_type, size_t count, const int32_t* a, const int32_t* b, const int32_t* c, int32_t* out,
+                        ieache_stats* stats /* [n members] or NULL */);
+/* replaces ieache_mux per GPU = bootsMUX */
+int ieache_group_mux(ieache_group* g, size_t count, const int32_t* a, const int32_t* b, const int32_t* c, int32_t* out,
+                     ieache_stats* stats /* [n members] or NULL */);
+/* replaces ieache_pbs per GPU = tfhe_blindRotateAndExtract_FFT / tfhe_bootstrap_woKS_FFT / tfhe_bootstrap_FFT over `count` rows */
+int ieache_group_pbs(ieache_group* g, size_t count, const int32_t* x, const int32_t* test_polys, int32_t n_polys, const int32_t* poly_of,
+                     int32_t* out, int flags, ieache_stats* stats /* [n members] or NULL */);
+/* replaces ieache_pbs_multi per GPU (the multi-value bootstrap; no libtfhe counterpart) */
+int ieache_group_pbs_multi(ieache_group* g, size_t count, const int32_t* x, const int32_t* test_polys, int32_t n_polys,
+                           const int32_t* poly_of, const int32_t* factors, int32_t n_factors, const int32_t* bias, int32_t* out, int flags,
+                           ieache_stats* stats /* [n members] or NULL */);
 
 /* ------------------------------------------------------------------ *
  * 3. Batch evaluation: `batch` independent expressions through one    *
@@ -486,7 +569,8 @@ int64_t ieache_serve(const char* socket_path, const char* cloud_key_path, const 
  * contiguous slices, one per device -- ieache_shard_slice's rule, the one bench.py and ie-ache_amd/parallel.py apply across
  * ranks (independent expressions, no exchange between GPUs) --, evaluated concurrently and answered in request
  * order; a lone request runs on devices[0].  A device may be listed twice (two contexts on one card).  Answers do not
- * depend on the device list: every expression goes through the same circuit and kernels.
+ * depend on the device list: every expression goes through the same circuit and kernels.  The evaluators are a device group
+ * (section 2b): 1 .. IEACHE_GROUP_MAX_DEVICES entries, and contexts that share a card run with "br_mix" = 0.
  * Reference caller served: dragonfly_cipher_cloud.py:1233 (one ./cloud per operator; batches come from concurrent clients). */
 int64_t ieache_serve_devices(const char* socket_path, const char* cloud_key_path, const char* nbit_key_path, const int* devices,
                              int n_devices, int64_t max_requests);
