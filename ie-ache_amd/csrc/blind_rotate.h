@@ -23,6 +23,14 @@ struct BrLanes {
     hipEvent_t ev[kMaxLanes] = {};
 };
 
+// One share of a launch: `cnt` consecutive rotation items of one descriptor, from W.item0 on.  A launch is a list of parts;
+// their items are the launch's items one after another (rows of the state block and of `ext` in that order).  Every call
+// but a joint evaluation (joint_plan.h) passes a list of one.
+struct BrPart {
+    dev::WorkDesc W;
+    int64_t cnt;
+};
+
 // One per evaluator.  All methods expect the evaluator's device to be current.
 struct BlindRotate {
     // The twist and twiddle tables of the any-parameter kernel (K.twist / K.wtab are set to them) and its dynamic LDS on the
@@ -35,18 +43,25 @@ struct BlindRotate {
     // State for a launch of `need` gate instances ahead of time, so that launch() finds it in place (an allocation is a
     // device-wide synchronisation).
     void reserve(BrScratch& scratch, size_t need, const EvalOptions& opt, bool use_w64);
-    // K0..K4 of `cnt` gate instances described by W as `plan` says, on `stream`.  ext: rows of N + 4 words (may be null);
-    // steps < 0: the whole rotation; dbg_acc [cnt][2][N] (may be null; then pass ext = null).  lanes: plan.mix.k streams and
-    // events when the plan is a rotation of roles.  Returns the kernel launches issued (the prologue not counted).
-    int launch(BrScratch& scratch, const BrPlan& plan, const EvalOptions& opt, const BrLanes& lanes, hipStream_t stream, const dev::WorkDesc& W,
-               int64_t cnt, Torus32* ext, int32_t steps, Torus32* dbg_acc);
+    // K0..K4 of the gate instances the parts describe -- sum of cnt of them, `plan` made for that sum -- on `stream`.  ext: rows
+    // of N + 4 words (may be null); steps < 0: the whole rotation; dbg_acc [sum][2][N] (may be null; then pass ext = null).
+    // lanes: plan.mix.k streams and events when the plan is a rotation of roles.  Returns the kernel launches issued (the
+    // prologues not counted).
+    // 64-lane kernels: only the prologue reads a descriptor, so there is ONE prologue per part, at the part's row offset of
+    // the state block, and one sequence of CMux slices over all rows -- the parts SHARE every rotation launch.
+    // Any-parameter kernel: its prologue is inside it, so the parts are launched one after another on `stream`, each over its
+    // rows of ext.  Same results, nothing shared.
+    int launch(BrScratch& scratch, const BrPlan& plan, const EvalOptions& opt, const BrLanes& lanes, hipStream_t stream, const BrPart* parts,
+               size_t n_parts, Torus32* ext, int32_t steps, Torus32* dbg_acc);
     // The sampled audit behind the rounding guard: after a (level, chunk) launch that took a one-limb kernel, every
     // fft_audit-th time, kAuditGates consecutive gate instances of it (at an offset that moves from audit to audit) are run
     // again on the two-limb kernel -- exact by construction -- and their extracted samples compared word for word with what the
     // one-limb kernel wrote to `ext`.  A differing row is counted on the device; the call then repeats itself on the
     // two-limb kernels like a call whose guard tripped (Evaluator::fft_guard_tripped).  The guard watches the error LEVEL of
     // every launch; this compares BITS, of a sample.  Clears "fft_audit_inject" when it has used it.
-    void audit(BrScratch& scratch, const BrPlan& plan, EvalOptions& opt, hipStream_t stream, const dev::WorkDesc& W, int64_t cnt, const Torus32* ext);
+    // One decision per launch, whatever the number of parts.  The window lies inside ONE part (the exact kernel's prologue
+    // reads one descriptor); a part shorter than the window is audited whole; which part moves from audit to audit.
+    void audit(BrScratch& scratch, const BrPlan& plan, EvalOptions& opt, hipStream_t stream, const BrPart* parts, size_t n_parts, const Torus32* ext);
     static constexpr int64_t kAuditGates = 64;
     struct AuditCounts {
         int64_t seq = 0;  // one-limb (level, chunk) launches so far

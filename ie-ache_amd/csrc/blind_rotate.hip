@@ -248,22 +248,41 @@ void BlindRotate::reserve(BrScratch& scratch, size_t need, const EvalOptions& op
     if (use_w64) scratch.state.reserve(need, (size_t)opt.chunk, br_state_bytes_per_item(p_));
 }
 
-int BlindRotate::launch(BrScratch& scratch, const BrPlan& plan, const EvalOptions& opt, const BrLanes& lanes, hipStream_t stream, const WorkDesc& w,
-                        int64_t cnt, Torus32* ext, int32_t steps, Torus32* dbg_acc) {
-    if (!w.gates && w.tv && w.n_tv < 1) throw std::invalid_argument("programmable bootstrap without test polynomials");
+int BlindRotate::launch(BrScratch& scratch, const BrPlan& plan, const EvalOptions& opt, const BrLanes& lanes, hipStream_t stream, const BrPart* parts,
+                        size_t n_parts, Torus32* ext, int32_t steps, Torus32* dbg_acc) {
+    int64_t cnt = 0;
+    for (size_t q = 0; q < n_parts; q++) {
+        const WorkDesc& w = parts[q].W;
+        if (!w.gates && w.tv && w.n_tv < 1) throw std::invalid_argument("programmable bootstrap without test polynomials");
+        if (parts[q].cnt < 1) throw std::logic_error("blind-rotation launch: an empty part");
+        cnt += parts[q].cnt;
+    }
     if (plan.generic) {
-        hipLaunchKernelGGL(k_blind_rotate_generic, dim3((unsigned)cnt), dim3(kThreads), generic_lds_, stream, K_, w, ext, steps, dbg_acc);
-        return 1;
+        // the any-parameter kernel has its prologue inside it: the parts one after another, each over its own rows -- the
+        // same results as a shared launch would give, without the sharing
+        int64_t off = 0;
+        for (size_t q = 0; q < n_parts; q++) {
+            hipLaunchKernelGGL(k_blind_rotate_generic, dim3((unsigned)parts[q].cnt), dim3(kThreads), generic_lds_, stream, K_, parts[q].W,
+                               ext ? ext + (size_t)off * (size_t)(K_.N + 4) : nullptr, steps, dbg_acc ? dbg_acc + (size_t)off * 2 * (size_t)K_.N : nullptr);
+            off += parts[q].cnt;
+        }
+        return (int)n_parts;
     }
     reserve(scratch, (size_t)cnt, opt, true);  // in place already unless the caller did not reserve
     if ((plan.variant == kVariantWideStamps || plan.variant == kVariantOneLimbStamps) && !diag_) diag_.allocate(16, sizeof(unsigned long long), 0, /*zero=*/true);
-    return w64::launch(p_, K_, w64::Tables{bkf_w64_, bkf1_w64_, tw_w64_, guard_, diag_}, plan, lanes, stream, w, cnt, scratch.state, ext, steps, dbg_acc);
+    return w64::launch(p_, K_, w64::Tables{bkf_w64_, bkf1_w64_, tw_w64_, guard_, diag_}, plan, lanes, stream, parts, n_parts, scratch.state, ext, steps, dbg_acc);
 }
 
-void BlindRotate::audit(BrScratch& scratch, const BrPlan& plan, EvalOptions& opt, hipStream_t stream, const WorkDesc& w, int64_t cnt, const Torus32* ext) {
-    if (plan.generic || opt.fft_audit <= 0 || !guard_) return;
+void BlindRotate::audit(BrScratch& scratch, const BrPlan& plan, EvalOptions& opt, hipStream_t stream, const BrPart* parts, size_t n_parts, const Torus32* ext) {
+    if (plan.generic || opt.fft_audit <= 0 || !guard_ || n_parts == 0) return;
     if (!variant_one_limb(plan.variant)) return;  // the launch was exact by construction
     if (++audit_counts.seq % opt.fft_audit != 0) return;
+    // the part: by the count of audits made so far, so that consecutive audits of a joint evaluation visit its parts in turn
+    const size_t part = (size_t)((uint64_t)audit_counts.audits % (uint64_t)n_parts);
+    int64_t row0 = 0;  // the part's first row of ext
+    for (size_t q = 0; q < part; q++) row0 += parts[q].cnt;
+    const WorkDesc& w = parts[part].W;
+    const int64_t cnt = parts[part].cnt;
     const int64_t m = std::min<int64_t>(kAuditGates, cnt);
     const int64_t off = cnt > m ? (int64_t)(((uint64_t)audit_counts.seq * 0x9E3779B97F4A7C15ull >> 33) % (uint64_t)(cnt - m + 1)) : 0;
     const size_t ext_row_bytes = (size_t)(K_.N + 4) * 4;
@@ -271,9 +290,10 @@ void BlindRotate::audit(BrScratch& scratch, const BrPlan& plan, EvalOptions& opt
     if (!scratch.audit_state) scratch.audit_state.allocate((size_t)kAuditGates, br_state_bytes_per_item(p_));
     WorkDesc wa = w;
     wa.item0 = w.item0 + off;
-    w64::launch(p_, K_, w64::Tables{bkf_w64_, bkf1_w64_, tw_w64_, guard_, nullptr}, br_exact_plan(p_), BrLanes{}, stream, wa, m, scratch.audit_state,
+    const BrPart pa{wa, m};
+    w64::launch(p_, K_, w64::Tables{bkf_w64_, bkf1_w64_, tw_w64_, guard_, nullptr}, br_exact_plan(p_), BrLanes{}, stream, &pa, 1, scratch.audit_state,
                 scratch.audit_ext, -1, nullptr);
-    hipLaunchKernelGGL(k_audit_compare, dim3((unsigned)m), dim3(256), 0, stream, ext + (size_t)off * (size_t)(K_.N + 4), scratch.audit_ext, K_.N,
+    hipLaunchKernelGGL(k_audit_compare, dim3((unsigned)m), dim3(256), 0, stream, ext + (size_t)(row0 + off) * (size_t)(K_.N + 4), scratch.audit_ext, K_.N,
                        guard_ + 2, opt.fft_audit_inject ? 1 : 0);
     HIP_CHECK(hipGetLastError());
     opt.fft_audit_inject = 0;

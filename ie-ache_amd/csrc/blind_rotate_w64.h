@@ -32,8 +32,10 @@ struct Tables {
 // state: items * br_state_bytes_per_item() bytes of scratch.
 // ext rows of N+4 int32 (may be null), dbg_acc [items][2][N] (may be null; when set, pass ext = null).
 // Returns the number of blind-rotation kernel launches issued (the prologue not counted).
+// parts: the items' descriptors -- one prologue per part into consecutive rows of the state block (the TV build chosen per
+// part), then everything else over all `items` = sum of the parts' counts.
 int launch(const Params& p, const dev::DevKeys& K, const Tables& t, const BrPlan& plan, const BrLanes& mix, hipStream_t stream,
-           const dev::WorkDesc& W, int64_t items, void* state, Torus32* ext, int32_t steps, Torus32* dbg_acc);
+           const BrPart* parts, size_t n_parts, void* state, Torus32* ext, int32_t steps, Torus32* dbg_acc);
 
 }  // namespace w64
 }  // namespace ieache

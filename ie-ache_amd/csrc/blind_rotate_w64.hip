@@ -1329,7 +1329,13 @@ static int launch_mixed_phases(const Params& p, const DevKeys& K, const Tables& 
 }
 
 int launch(const Params& p, const DevKeys& K, const Tables& t, const BrPlan& plan, const BrLanes& mix, hipStream_t stream,
-           const WorkDesc& W, int64_t items, void* state, Torus32* ext, int32_t steps, Torus32* dbg_acc) {
+           const BrPart* parts, size_t n_parts, void* state, Torus32* ext, int32_t steps, Torus32* dbg_acc) {
+    int64_t items = 0;
+    for (size_t q = 0; q < n_parts; q++) {
+        if (parts[q].cnt < 1) throw std::logic_error("blind-rotation launch: an empty part");
+        items += parts[q].cnt;
+    }
+    if (items < 1) throw std::logic_error("blind-rotation launch without items");
     const BrVariant* row = br_variant(plan.variant);
     if (plan.generic || !row) throw std::invalid_argument("unknown blind-rotation variant");
     if (row->limbs == 1 && (!t.bkf1 || !t.guard)) throw std::runtime_error("one-limb blind rotation without its spectrum / guard word");
@@ -1351,10 +1357,18 @@ int launch(const Params& p, const DevKeys& K, const Tables& t, const BrPlan& pla
     // state block: [items][2][1024] int32 accumulators, then [items][nb] u16 rotation amounts
     int32_t* st_acc = reinterpret_cast<int32_t*>(state);
     uint16_t* st_bara = reinterpret_cast<uint16_t*>(st_acc + (size_t)items * 2 * kN);
-    if (!W.gates && W.tv)  // a programmable bootstrap (BlindRotate::launch has checked the table)
-        hipLaunchKernelGGL(k_br_prologue<true>, dim3((unsigned)items), dim3(128), 0, stream, K, W, st_bara, nb, st_acc);
-    else
-        hipLaunchKernelGGL(k_br_prologue<false>, dim3((unsigned)items), dim3(128), 0, stream, K, W, st_bara, nb, st_acc);
+    // the prologue writes row (block index) of what it is given: a part's rows start `off` rows into the state block
+    int64_t off = 0;
+    for (size_t q = 0; q < n_parts; q++) {
+        const WorkDesc& W = parts[q].W;
+        uint16_t* bara = st_bara + (size_t)off * nb;
+        int32_t* acc = st_acc + (size_t)off * 2 * kN;
+        if (!W.gates && W.tv)  // a programmable bootstrap (BlindRotate::launch has checked the table)
+            hipLaunchKernelGGL(k_br_prologue<true>, dim3((unsigned)parts[q].cnt), dim3(128), 0, stream, K, W, bara, nb, acc);
+        else
+            hipLaunchKernelGGL(k_br_prologue<false>, dim3((unsigned)parts[q].cnt), dim3(128), 0, stream, K, W, bara, nb, acc);
+        off += parts[q].cnt;
+    }
     auto one = [&](int v, int32_t i0, int32_t i1, Torus32* e) {
         launch_slice(v, plan.wg_gates, Slice{p.l, items, stream, K, t, st_bara, nb, st_acc, i0, i1, e, plan.w4r_flip});
     };

@@ -561,6 +561,74 @@ int ieache_eval_netlist_device(ieache_ctx* ctx, const ieache_netlist* nl, size_t
     });
 }
 
+// ---- 3c. several circuits' batches in one call (Evaluator::eval_jobs_device, joint_plan.h) ----
+extern "C++" {
+namespace {
+// The jobs of a call resolved to circuits, or the refusal: everything that can fail is judged here, before anything is
+// launched, staged or written.  What needs no context comes first.  held: the cached circuits, kept for the call.
+struct ResolvedJobs {
+    std::vector<EvalJob> jobs;  // one per caller's job, circuit null and batch 0 where the job is skipped
+    std::vector<CircuitCache::Ptr> held;
+};
+int resolve_jobs(ieache_ctx* ctx, const ieache_job* jobs, size_t n_jobs, bool need_rows, ResolvedJobs* r) {
+    if (n_jobs && !jobs) return fail(IEACHE_EINVAL, "null argument");
+    for (size_t j = 0; need_rows && j < n_jobs; j++)
+        if (jobs[j].batch && (!jobs[j].in_lwe || !jobs[j].out_lwe)) return fail(IEACHE_EINVAL, "job " + std::to_string(j) + ": null argument");
+    if (!ctx) return fail(IEACHE_EINVAL, "null argument");
+    r->jobs.assign(n_jobs, EvalJob{});
+    for (size_t j = 0; j < n_jobs; j++) {
+        if (!jobs[j].batch) continue;
+        const Circuit* c = nullptr;
+        if (jobs[j].netlist) {
+            c = &jobs[j].netlist->circuit;
+        } else {
+            // the base circuit: a level cap is chosen for ONE batch filling rounds alone
+            const CircuitCache::Ptr held = ctx->circuits.fetch(jobs[j].kind, jobs[j].bits, ctx->fold, 0);
+            if (!held) return fail(IEACHE_EINVAL, "job " + std::to_string(j) + ": " + kUnsupported);
+            r->held.push_back(held);
+            c = held.get();
+        }
+        r->jobs[j].circuit = c;
+        r->jobs[j].batch = jobs[j].batch;
+    }
+    return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int ieache_prepare_jobs(ieache_ctx* ctx, const ieache_job* jobs, size_t n_jobs) {
+    return guarded([&] {
+        ResolvedJobs r;
+        if (const int rc = resolve_jobs(ctx, jobs, n_jobs, false, &r)) return rc;
+        ctx->eval->prepare_jobs(r.jobs.data(), r.jobs.size());
+        return 0;
+    });
+}
+
+int ieache_eval_jobs_device(ieache_ctx* ctx, const ieache_job* jobs, size_t n_jobs, ieache_eval_stats* stats) {
+    return guarded([&] {
+        ResolvedJobs r;
+        if (const int rc = resolve_jobs(ctx, jobs, n_jobs, true, &r)) return rc;
+        for (size_t j = 0; j < n_jobs; j++) {
+            require_device_pointers(jobs[j].batch, {{jobs[j].in_lwe, "in_lwe"}, {jobs[j].out_lwe, "out_lwe"}});
+            r.jobs[j].d_in = jobs[j].in_lwe;
+            r.jobs[j].d_out = jobs[j].out_lwe;
+        }
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->eval_jobs_device(r.jobs.data(), r.jobs.size(), st); });
+    });
+}
+
+int ieache_eval_jobs(ieache_ctx* ctx, const ieache_job* jobs, size_t n_jobs, ieache_eval_stats* stats) {
+    return guarded([&] {
+        ResolvedJobs r;
+        if (const int rc = resolve_jobs(ctx, jobs, n_jobs, true, &r)) return rc;
+        std::vector<HostJob> host(n_jobs);
+        for (size_t j = 0; j < n_jobs; j++)
+            if (r.jobs[j].batch) host[j] = HostJob{r.jobs[j].circuit, r.jobs[j].batch, jobs[j].in_lwe, jobs[j].out_lwe};
+        return with_stats(stats, [&](EvalStats* st) { eval_jobs_host(*ctx->eval, host.data(), host.size(), st); });
+    });
+}
+
 namespace {
 // host rows (n+1) <-> device rows (stride)
 struct DevRows {
@@ -956,6 +1024,30 @@ int ieache_group_eval_netlist(ieache_group* g, const ieache_netlist* nl, size_t 
     });
 }
 
+// Every job's batch cut over the members (shard_jobs): a member is one "row" of run_sliced, so each runs on its own thread
+// whatever the batches are; one whose slices are all empty does nothing and reports zeros.
+int ieache_group_eval_jobs(ieache_group* g, const ieache_job* jobs, size_t n_jobs, ieache_stats* stats) {
+    if (!g) return fail(IEACHE_EINVAL, kNullGroup);
+    return guarded([&] {
+        // rows per expression come from the circuits, so this check is made whatever "precheck" says
+        ResolvedJobs r;
+        if (const int rc = resolve_jobs(g->member(0), jobs, n_jobs, true, &r)) return rc;
+        const size_t W = (size_t)g->member(0)->eval->params().n + 1;
+        std::vector<size_t> in_words(n_jobs, 0), out_words(n_jobs, 0);
+        for (size_t j = 0; j < n_jobs; j++) {
+            if (!r.jobs[j].batch) continue;
+            in_words[j] = (size_t)r.jobs[j].circuit->n_inputs * W;
+            out_words[j] = r.jobs[j].circuit->outputs.size() * W;
+        }
+        return group_call(g, g->size(), stats, [&](ieache_ctx* ctx, size_t m, size_t, ieache_stats* st) {
+            std::vector<ieache_job> mine;
+            shard_jobs(jobs, n_jobs, in_words.data(), out_words.data(), g->size(), m, &mine);
+            if (mine.empty()) return 0;
+            return ieache_eval_jobs(ctx, mine.data(), mine.size(), st);
+        });
+    });
+}
+
 int ieache_group_gates(ieache_group* g, int gate_type, size_t count, const int32_t* a, const int32_t* b, int32_t* out, ieache_stats* stats) {
     if (!g) return fail(IEACHE_EINVAL, kNullGroup);
     return guarded([&] {
@@ -1281,6 +1373,7 @@ int64_t ieache_serve_devices(const char* socket_path, const char* cloud_key_path
         cfg.max_requests = max_requests;
         if (const char* w = getenv("IEACHE_DAEMON_BATCH_WINDOW_MS")) cfg.batch_window_ms = atoi(w) > 0 ? atoi(w) : 0;
         if (const char* m = getenv("IEACHE_DAEMON_MAX_BATCH")) cfg.max_batch = atoi(m) > 0 ? atoi(m) : 1;
+        if (const char* j = getenv("IEACHE_DAEMON_JOINT")) cfg.joint = atoi(j) != 0;
         served = daemon_serve(cfg);
         return 0;
     });

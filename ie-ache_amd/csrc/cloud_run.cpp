@@ -311,6 +311,11 @@ int cloud_run_io(const CloudRunIO& io, const std::function<Evaluator*()>& get_ev
     return 0;
 }
 
+CircuitCache& cloud_circuit_cache() {
+    static CircuitCache cache(1);
+    return cache;
+}
+
 // Several prepared jobs of one (kind, width, folding) as ONE level-batched evaluation: what makes a resident
 // daemon with many clients use the GPU the way bench.py does.  outs[i] receives job i's value samples.
 void cloud_eval_jobs(Evaluator& eval, const std::vector<CloudJob*>& jobs, std::vector<std::vector<Torus32>>* outs, EvalStats* stats) {
@@ -319,8 +324,7 @@ void cloud_eval_jobs(Evaluator& eval, const std::vector<CloudJob*>& jobs, std::v
     // built circuits are kept for the life of the process (a daemon evaluates the same handful over and over): per (kind, width,
     // folding) the default schedule plus ONE level-capped variant, the most recent -- the cap follows the batch size, and a
     // long-running daemon sees many batch sizes
-    static CircuitCache cache(1);
-    const CircuitCache::Ptr circ = cache.select(first.kind, first.int_bit, first.fold, (int64_t)jobs.size(), eval.resident_gates(),
+    const CircuitCache::Ptr circ = cloud_circuit_cache().select(first.kind, first.int_bit, first.fold, (int64_t)jobs.size(), eval.resident_gates(),
                                                 eval.resident_gates_two_wave(), /*level_quantum=*/true);
     if (!circ) throw std::invalid_argument("unsupported circuit");
     const size_t S = (size_t)first.params.n + 1, n_in = (size_t)circ->n_inputs * S, n_out = circ->outputs.size() * S;
@@ -348,6 +352,37 @@ void eval_circuit_host(Evaluator& eval, const Circuit& c, size_t batch, const To
     HIP_CHECK(hipMemcpy2D(d_in, stride * 4, in, S * 4, S * 4, n_in, hipMemcpyHostToDevice));
     eval.eval_circuit_device(c, batch, d_in, d_out, stats);
     HIP_CHECK(hipMemcpy2D(out, S * 4, d_out, stride * 4, S * 4, n_out, hipMemcpyDeviceToHost));
+}
+
+void eval_jobs_host(Evaluator& eval, const HostJob* jobs, size_t n_jobs, EvalStats* stats) {
+    const Params& p = eval.params();
+    const size_t S = (size_t)p.n + 1, stride = (size_t)p.lwe_stride();
+    std::vector<EvalJob> dev(n_jobs);
+    size_t rows_in = 0, rows_out = 0;
+    for (size_t j = 0; j < n_jobs; j++) {
+        if (!jobs[j].batch) continue;
+        if (!jobs[j].circuit || !jobs[j].in_lwe || !jobs[j].out_lwe) throw std::invalid_argument("joint evaluation: job " + std::to_string(j) + ": null argument");
+        rows_in += (size_t)jobs[j].circuit->n_inputs * jobs[j].batch;
+        rows_out += jobs[j].circuit->outputs.size() * jobs[j].batch;
+    }
+    if (rows_in + rows_out == 0) return;
+    HIP_CHECK(hipSetDevice(eval.device()));
+    Torus32* d_in = eval.staging(kStageA, std::max<size_t>(rows_in, 1) * stride * 4);
+    Torus32* d_out = eval.staging(kStageOut, std::max<size_t>(rows_out, 1) * stride * 4);
+    size_t at_in = 0, at_out = 0;
+    for (size_t j = 0; j < n_jobs; j++) {
+        if (!jobs[j].batch) continue;
+        const size_t n_in = (size_t)jobs[j].circuit->n_inputs * jobs[j].batch;
+        dev[j] = EvalJob{jobs[j].circuit, jobs[j].batch, d_in + at_in * stride, d_out + at_out * stride};
+        if (n_in) HIP_CHECK(hipMemcpy2D(d_in + at_in * stride, stride * 4, jobs[j].in_lwe, S * 4, S * 4, n_in, hipMemcpyHostToDevice));
+        at_in += n_in;
+        at_out += jobs[j].circuit->outputs.size() * jobs[j].batch;
+    }
+    eval.eval_jobs_device(dev.data(), dev.size(), stats);
+    for (size_t j = 0; j < n_jobs; j++) {
+        const size_t n_out = jobs[j].batch ? jobs[j].circuit->outputs.size() * jobs[j].batch : 0;
+        if (n_out) HIP_CHECK(hipMemcpy2D(jobs[j].out_lwe, S * 4, dev[j].d_out, stride * 4, S * 4, n_out, hipMemcpyDeviceToHost));
+    }
 }
 
 }  // namespace ieache

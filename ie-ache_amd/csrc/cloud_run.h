@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "circuit.h"
+#include "circuit_cache.h"
 #include "evaluator.h"
 #include "params.h"
 
@@ -71,11 +72,24 @@ void cloud_prepare(const CloudRunIO& io, CloudJob* job, CloudRunReport* report);
 void cloud_finish(const CloudRunIO& io, const CloudJob& job, const Torus32* out, size_t n_out_samples, double seconds);
 void cloud_eval_jobs(Evaluator& eval, const std::vector<CloudJob*>& jobs, std::vector<std::vector<Torus32>>* outs, EvalStats* stats);
 
+// the process-wide cache cloud_eval_jobs takes its circuits from; a joint round (daemon.cpp) takes its base circuits there too
+CircuitCache& cloud_circuit_cache();
+
 // get_eval is called only if a circuit is actually evaluated.
 int cloud_run_io(const CloudRunIO& io, const std::function<Evaluator*()>& get_eval, CloudRunReport* report);
 
 // Host-buffer convenience: rows of (n+1) int32 in and out.
 void eval_circuit_host(Evaluator& eval, const Circuit& c, size_t batch, const Torus32* in, Torus32* out,
                        EvalStats* stats);
+
+// A joint evaluation (Evaluator::eval_jobs_device) on host rows of (n+1) int32: every job's rows behind each other in the
+// evaluator's own staging rows, so that a warm call allocates nothing.  Jobs with batch 0 are skipped.
+struct HostJob {
+    const Circuit* circuit = nullptr;
+    size_t batch = 0;
+    const Torus32* in_lwe = nullptr;  // [batch][circuit.n_inputs][n + 1]
+    Torus32* out_lwe = nullptr;       // [batch][circuit.outputs.size()][n + 1]
+};
+void eval_jobs_host(Evaluator& eval, const HostJob* jobs, size_t n_jobs, EvalStats* stats);
 
 }  // namespace ieache

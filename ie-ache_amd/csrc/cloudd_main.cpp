@@ -1,6 +1,8 @@
 // `cloudd`: the Cloud evaluator as a resident-key daemon.
 //   cloudd [--socket PATH] [--key cloud.key] [--nbit nbit.key] [--device N | --devices N,M,...] [--max-requests K]
-//          [--batch-window-ms T] [--max-batch B]
+//          [--batch-window-ms T] [--max-batch B] [--joint 0|1]
+// --joint 0|1 (default 1): a round that holds requests for several circuits, each narrow on its own, evaluates them together
+// level by level so that they share their GPU launches; 0 = one circuit after another.  Same answers either way.
 // --devices 0,1,...,7 (or IEACHE_DEVICES): one evaluator per listed GPU, the key loaded once and uploaded to each; the
 // same-circuit requests of a batching round are cut into contiguous slices, one per GPU, and answered in request order.
 // --batch-window-ms T: requests arriving within T ms of each other are answered together; those asking for the same
@@ -64,9 +66,10 @@ int main(int argc, char** argv) {
         else if (a == "--max-requests") max_requests = atoll(need("--max-requests"));
         else if (a == "--batch-window-ms") setenv("IEACHE_DAEMON_BATCH_WINDOW_MS", need("--batch-window-ms"), 1);
         else if (a == "--max-batch") setenv("IEACHE_DAEMON_MAX_BATCH", need("--max-batch"), 1);
+        else if (a == "--joint") setenv("IEACHE_DAEMON_JOINT", need("--joint"), 1);
         else {
             fprintf(stderr, "usage: cloudd [--socket PATH] [--key cloud.key] [--nbit nbit.key] [--device N | --devices N,M,...] [--max-requests K] "
-                            "[--batch-window-ms T] [--max-batch B]\n");
+                            "[--batch-window-ms T] [--max-batch B] [--joint 0|1]\n");
             return a == "--help" || a == "-h" ? 0 : 2;
         }
     }

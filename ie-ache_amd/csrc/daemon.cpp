@@ -9,6 +9,7 @@
 #include <sys/un.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
@@ -25,6 +26,7 @@
 #include "evaluator.h"
 #include "group.h"
 #include "group_run.h"
+#include "joint_plan.h"
 #include "tfhe_host.h"
 
 namespace ieache {
@@ -226,7 +228,7 @@ public:
         evaluate(runs);
     }
 
-    int64_t batches = 0, batched_requests = 0, largest_batch = 0, sharded = 0;
+    int64_t batches = 0, batched_requests = 0, largest_batch = 0, sharded = 0, joint_rounds = 0, joint_requests = 0;
 
     // returns rc; fills log and data
     int32_t handle(uint32_t op, const std::vector<unsigned char>& payload, std::string* log, std::vector<unsigned char>* data) {
@@ -235,9 +237,10 @@ public:
                 case DAEMON_PING: *log = std::string(ieache_version()) + ", key " + key_path_; return 0;
                 case DAEMON_SHUTDOWN: *log = "bye"; return 0;
                 case DAEMON_STATS: {
-                    char buf[200];
-                    snprintf(buf, sizeof buf, "evaluations=%lld batched_requests=%lld largest_batch=%lld devices=%zu sharded_evaluations=%lld device_jobs=",
-                             (long long)batches, (long long)batched_requests, (long long)largest_batch, group_ ? group_->size() : (size_t)0, (long long)sharded);
+                    char buf[300];
+                    snprintf(buf, sizeof buf, "evaluations=%lld batched_requests=%lld largest_batch=%lld devices=%zu sharded_evaluations=%lld joint_rounds=%lld joint_requests=%lld device_jobs=",
+                             (long long)batches, (long long)batched_requests, (long long)largest_batch, group_ ? group_->size() : (size_t)0, (long long)sharded,
+                             (long long)joint_rounds, (long long)joint_requests);
                     *log = buf;
                     for (size_t d = 0; d < device_jobs_.size(); d++) *log += (d ? "," : "") + std::to_string(device_jobs_[d]);
                     return 0;
@@ -300,6 +303,51 @@ private:
             device_jobs_[d] += (int64_t)count;
         }
         sharded++;
+    }
+
+    // Two or more circuit groups of a round as ONE joint evaluation (Evaluator::eval_jobs_device): a job per group, its batch
+    // the group's requests.  Over the device group every job's batch is cut over the members with shard_slice -- what
+    // ieache_group_eval_jobs does -- and each member that got anything runs its list on a host thread of its own.
+    // outs[g][i]: the value samples of request i of group g.
+    struct JointGroup {
+        CircuitCache::Ptr circuit;  // the base circuit: a level cap is chosen for one batch filling rounds alone
+        std::vector<CloudJob*> jobs;
+    };
+    void eval_joint(const std::vector<JointGroup>& groups, std::vector<std::vector<std::vector<Torus32>>>* outs) {
+        const size_t S = (size_t)eval_->params().n + 1;
+        std::vector<std::vector<Torus32>> in(groups.size()), out(groups.size());
+        std::vector<HostJob> jobs(groups.size());
+        std::vector<size_t> in_words(groups.size()), out_words(groups.size());
+        for (size_t g = 0; g < groups.size(); g++) {
+            const Circuit& c = *groups[g].circuit;
+            in_words[g] = (size_t)c.n_inputs * S;
+            out_words[g] = c.outputs.size() * S;
+            in[g].resize(groups[g].jobs.size() * in_words[g]);
+            out[g].resize(groups[g].jobs.size() * out_words[g]);
+            for (size_t i = 0; i < groups[g].jobs.size(); i++) {
+                if (groups[g].jobs[i]->in.size() != in_words[g]) throw std::invalid_argument("a request's inputs do not fit its circuit");
+                memcpy(in[g].data() + i * in_words[g], groups[g].jobs[i]->in.data(), in_words[g] * 4);
+            }
+            jobs[g] = HostJob{&c, groups[g].jobs.size(), in[g].data(), out[g].data()};
+        }
+        const size_t members = group_->size();
+        std::vector<std::vector<HostJob>> mine(members);
+        size_t busy = 0;
+        for (size_t m = 0; m < members; m++) {
+            shard_jobs(jobs.data(), jobs.size(), in_words.data(), out_words.data(), members, m, &mine[m]);
+            busy += mine[m].empty() ? 0 : 1;
+        }
+        // a member is one "row": each runs on its own thread (member 0 on this one), whatever the batches are
+        run_sliced(members, members, [&](size_t m, size_t, size_t) {
+            if (!mine[m].empty()) eval_jobs_host(*group_->member(m)->eval, mine[m].data(), mine[m].size(), nullptr);
+        });
+        for (size_t m = 0; m < members; m++)  // counted once the whole evaluation has succeeded
+            for (const HostJob& j : mine[m]) device_jobs_[m] += (int64_t)j.batch;
+        if (busy > 1) sharded++;
+        outs->assign(groups.size(), {});
+        for (size_t g = 0; g < groups.size(); g++)
+            for (size_t i = 0; i < groups[g].jobs.size(); i++)
+                (*outs)[g].emplace_back(out[g].begin() + i * out_words[g], out[g].begin() + (i + 1) * out_words[g]);
     }
 
     // one RUN_DIR / RUN_DATA request on its way through cloud_prepare -> (batched) evaluation -> cloud_finish
@@ -369,8 +417,77 @@ private:
             }
             groups[std::make_tuple(r->job.kind, r->job.int_bit, r->job.fold)].push_back(r.get());
         }
+        // what follows a group's evaluation: the log lines and cloud_finish of each of its requests.  with: the other circuits
+        // of a joint evaluation ("" = the group was evaluated on its own)
+        auto finish = [&](std::vector<Run*>& members, std::vector<std::vector<Torus32>>& outs, double dt, size_t devices_used, const std::string& with) {
+            batched_requests += (int64_t)members.size();
+            largest_batch = std::max<int64_t>(largest_batch, (int64_t)members.size());
+            for (size_t i = 0; i < members.size(); i++) {
+                Run* r = members[i];
+                try {
+                    if (members.size() > 1)
+                        fprintf(r->log.f, "cloudd: evaluated together with %zu other request(s)%s\n", members.size() - 1,
+                                devices_used > 1 ? (" on " + std::to_string(devices_used) + " devices").c_str() : "");
+                    if (!with.empty()) fprintf(r->log.f, "cloudd: evaluated jointly, level by level, with %s\n", with.c_str());
+                    cloud_finish(r->the_io(), r->job, outs[i].data(), outs[i].size() / ((size_t)r->job.params.n + 1), dt);
+                    r->reply_ok(0);
+                } catch (...) {
+                    r->fail(std::current_exception());
+                }
+            }
+        };
+        auto fail_all = [&](std::vector<Run*>& members, std::exception_ptr e) {
+            for (Run* r : members)
+                if (!r->failed && r->req->log.empty()) r->fail(e);
+        };
+        // The groups that are narrow on their own -- joint_plan.h states the rule -- run as ONE joint evaluation when there are at
+        // least two of them; every other group goes the way it always went, pipelines included.
+        std::vector<JointGroup> joint;
+        std::vector<std::vector<Run*>*> joint_members;
+        std::vector<std::string> joint_names;
+        if (cfg_.joint && groups.size() >= 2) {
+            int64_t pipe_min = 0;
+            eval_->get_option("pipe_min", &pipe_min);
+            for (auto& g : groups) {
+                const CircuitCache::Ptr c = cloud_circuit_cache().fetch(std::get<0>(g.first), std::get<1>(g.first), std::get<2>(g.first), 0);
+                if (!c || !joint_group_joins(c->n_bootstraps, c->n_levels(), (int64_t)g.second.size(), pipe_min)) continue;
+                JointGroup jg;
+                jg.circuit = c;
+                for (Run* r : g.second) jg.jobs.push_back(&r->job);
+                joint.push_back(std::move(jg));
+                joint_members.push_back(&g.second);
+                joint_names.push_back("circuit " + std::to_string(std::get<0>(g.first)) + " at " + std::to_string(std::get<1>(g.first)) + " bits x " +
+                                      std::to_string(g.second.size()));
+            }
+            if (!joint_round_joins(joint.size())) {
+                joint.clear();
+                joint_members.clear();
+            }
+        }
+        if (!joint.empty()) {
+            for (std::vector<Run*>* members : joint_members)
+                for (Run* r : *members) fprintf(r->log.f, "Doing the homomorphic computation...\n");
+            try {
+                std::vector<std::vector<std::vector<Torus32>>> outs;
+                const double t0 = now_s();
+                eval_joint(joint, &outs);
+                const double dt = now_s() - t0;
+                batches++;
+                joint_rounds++;
+                for (size_t g = 0; g < joint.size(); g++) {
+                    std::string with;
+                    for (size_t q = 0; q < joint.size(); q++)
+                        if (q != g) with += (with.empty() ? "" : ", ") + joint_names[q];
+                    joint_requests += (int64_t)joint_members[g]->size();
+                    finish(*joint_members[g], outs[g], dt, std::min(group_->size(), joint_members[g]->size()), with);
+                }
+            } catch (...) {
+                for (std::vector<Run*>* members : joint_members) fail_all(*members, std::current_exception());
+            }
+        }
         for (auto& g : groups) {
             std::vector<Run*>& members = g.second;
+            if (std::find(joint_members.begin(), joint_members.end(), &members) != joint_members.end()) continue;
             std::vector<CloudJob*> jobs;
             for (Run* r : members) {
                 jobs.push_back(&r->job);
@@ -382,23 +499,9 @@ private:
                 eval_sharded(jobs, &outs);
                 const double dt = now_s() - t0;
                 batches++;
-                batched_requests += (int64_t)members.size();
-                largest_batch = std::max<int64_t>(largest_batch, (int64_t)members.size());
-                for (size_t i = 0; i < members.size(); i++) {
-                    Run* r = members[i];
-                    try {
-                        if (members.size() > 1)
-                        fprintf(r->log.f, "cloudd: evaluated together with %zu other request(s)%s\n", members.size() - 1,
-                                group_->size() > 1 ? (" on " + std::to_string(std::min(group_->size(), members.size())) + " devices").c_str() : "");
-                        cloud_finish(r->the_io(), r->job, outs[i].data(), outs[i].size() / ((size_t)r->job.params.n + 1), dt);
-                        r->reply_ok(0);
-                    } catch (...) {
-                        r->fail(std::current_exception());
-                    }
-                }
+                finish(members, outs, dt, std::min(group_->size(), members.size()), std::string());
             } catch (...) {
-                for (Run* r : members)
-                    if (!r->failed && r->req->log.empty()) r->fail(std::current_exception());
+                fail_all(members, std::current_exception());
             }
         }
         runs.clear();

@@ -17,7 +17,9 @@
 //                 (metadata key = the daemon's nbit key)
 //   op SHUTDOWN : no payload; the daemon answers and exits its loop
 //   op STATS    : no payload; log = "evaluations=E batched_requests=R largest_batch=B devices=D sharded_evaluations=S
-//                 device_jobs=j0,j1,..." (S: evaluations whose jobs were split over more than one device; j_i: jobs device i ran)
+//                 joint_rounds=J joint_requests=Q device_jobs=j0,j1,..." (S: evaluations whose jobs were split over more than
+//                 one device; J: evaluations that joined two or more circuit groups, Q: the requests in them; j_i: jobs
+//                 device i ran)
 //   rc: 0 or 126 as main() of cloud.c, negative IEACHE_E* on failure (message in log)
 #pragma once
 #include <cstddef>
@@ -53,6 +55,11 @@ struct DaemonConfig {
     // ask for the same circuit as ONE level-batched evaluation.  0 = one request at a time.
     int batch_window_ms = 0;
     int max_batch = 256;
+    // cloudd --joint 0|1 / IEACHE_DAEMON_JOINT (default 1): a round whose requests fall into two or more circuit groups that
+    // are narrow on their own (joint_plan.h: joint_group_joins) evaluates those groups as ONE joint call, level by level, so
+    // that their launches are shared; over several devices every group is cut over the devices as ieache_group_eval_jobs cuts
+    // it.  Answers are bit for bit what they are with 0, where every circuit group is evaluated on its own.
+    bool joint = true;
 };
 
 // Blocks serving requests; returns the number served.  Throws on setup failure

@@ -41,6 +41,15 @@ enum StageSlot : int {
     kStageSlots
 };
 
+// One job of a joint evaluation (Evaluator::eval_jobs_device): a circuit over a batch of its own, rows shaped as
+// eval_circuit_device takes them.  The circuit is read during the call only.
+struct EvalJob {
+    const Circuit* circuit = nullptr;
+    size_t batch = 0;
+    const Torus32* d_in = nullptr;  // [batch][circuit.n_inputs][lwe_stride]
+    Torus32* d_out = nullptr;       // [batch][circuit.outputs.size()][lwe_stride]
+};
+
 class Evaluator {
 public:
     Evaluator(const Params& p, int device);
@@ -114,6 +123,15 @@ public:
     void eval_circuit_device(const Circuit& c, size_t batch, const Torus32* d_in, Torus32* d_out,
                              EvalStats* stats);
 
+    // Several circuits' batches TOGETHER, level by level (joint_plan.h): step s runs level s of every job that still has one
+    // as ONE call of the level machinery over the concatenation of their rotation items, so that narrow levels of different
+    // circuits share every blind-rotation launch -- one prologue and one key switch per job and piece, one sequence of CMux
+    // slices over all of them, the kernel chosen by the joint size.  Each job has its own wire store and tables.  Level mode
+    // only: no expression pipelines.  A job with batch 0 is skipped; every job's output words are what the job gives alone
+    // through eval_circuit_device.  stats: bootstraps summed over jobs, levels = the deepest job's depth, chunks = pieces issued.
+    void prepare_jobs(const EvalJob* jobs, size_t n_jobs);
+    void eval_jobs_device(const EvalJob* jobs, size_t n_jobs, EvalStats* stats);
+
     // Device rows the host-buffer entry points stage operands and results in, one buffer per StageSlot: owned by the
     // evaluator, kept between calls and grown on demand, so that a warm call allocates nothing.  Operand slots are zero outside
     // what the caller uploads (rows of lwe_stride() words, n + 1 of them uploaded); of the tables of a programmable bootstrap
@@ -185,6 +203,7 @@ private:
     void flat_device_once(const FlatCall& call, EvalStats* stats);  // gates, gates3, mux, pbs and pbs_multi, once
     void eval_circuit_device_once(const Circuit& c, size_t batch, const Torus32* d_in, Torus32* d_out, EvalStats* stats);
     void debug_blind_rotate_once(size_t count, const Torus32* d_x, Torus32* d_acc, int32_t steps);
+    void eval_jobs_device_once(const EvalJob* jobs, size_t n_jobs, EvalStats* stats);
     // runs `once`, and again on the two-limb kernels if the rounding guard or the audit asks for it (evaluator.hip)
     template <class F>
     void run_guarded(bool inputs_intact, EvalStats* stats, F&& once);

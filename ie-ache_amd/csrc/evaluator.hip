@@ -24,6 +24,7 @@
 #include "device_buffer.h"
 #include "device_common.h"
 #include "evaluator_options.h"
+#include "joint_plan.h"
 #include "keyswitch.h"
 #include "multi_extract.h"
 #include "scoped_set.h"
@@ -34,6 +35,7 @@
 #include <cstdlib>
 #include <chrono>
 #include <map>
+#include <memory>
 #include <stdexcept>
 #include <tuple>
 #include <vector>
@@ -158,6 +160,14 @@ struct Evaluator::Impl {
     DeviceBuffer<Torus32> store;    // circuits: the wire store, the gate and the output table
     DeviceBuffer<DevGate> d_gates;
     DeviceBuffer<OutRef> d_outs;
+    // a joint evaluation (eval_jobs_device): the same three per job, slot i for the call's i-th job with a batch -- jobs have
+    // disjoint stores
+    struct JobStore {
+        DeviceBuffer<Torus32> store;
+        DeviceBuffer<DevGate> d_gates;
+        DeviceBuffer<OutRef> d_outs;
+    };
+    std::vector<std::unique_ptr<JobStore>> job_store;
     size_t ext_row_bytes() const { return (size_t)(K.N + 4) * 4; }
 };
 
@@ -428,9 +438,9 @@ std::string Evaluator::kernel_for_launch(int64_t gates) const {
     return br_kernel_label(p_, plan_blind_rotate(p_, d_, d_->lane[0], gates < 1 ? 1 : gates));
 }
 
-// Runs the `cnt` gate instances described by w as `plan` says.  A rotation of roles gets the context's first plan.mix.k
+// Runs the gate instances the parts describe as `plan` says.  A rotation of roles gets the context's first plan.mix.k
 // lanes: their streams and an event each.
-static int launch_blind_rotate(Evaluator::Impl* d, Lane& ln, const BrPlan& plan, const WorkDesc& w, int64_t cnt, Torus32* ext, int32_t steps,
+static int launch_blind_rotate(Evaluator::Impl* d, Lane& ln, const BrPlan& plan, const BrPart* parts, size_t n_parts, Torus32* ext, int32_t steps,
                                Torus32* dbg_acc) {
     BrLanes lanes;
     if (plan.mix.k) {
@@ -442,7 +452,7 @@ static int launch_blind_rotate(Evaluator::Impl* d, Lane& ln, const BrPlan& plan,
         }
         d->opt.mixed_launches++;
     }
-    return d->br.launch(ln.br, plan, d->opt, lanes, ln.stream, w, cnt, ext, steps, dbg_acc);
+    return d->br.launch(ln.br, plan, d->opt, lanes, ln.stream, parts, n_parts, ext, steps, dbg_acc);
 }
 
 // the key switch of `cnt` extracted samples on a lane's stream, with the lane's scratch
@@ -457,18 +467,11 @@ struct LevelPlan {
     int64_t piece;  // gate instances per (blind rotation, key switch) pair of launches at most
 };
 static LevelPlan plan_level(const Evaluator::Impl* d, int64_t items) {
-    const int64_t chunk = (int64_t)d->opt.chunk;
-    LevelPlan pl{false, chunk};
-    if (d->opt.overlap && d->use_w64 && d->concurrency == 1 && items >= d->opt.overlap_min && items >= 2) {
-        const int64_t half = (((items + 1) / 2) + 3) & ~(int64_t)3;  // whole workgroups of the one-wave-per-gate kernels
-        // two lanes only when there are two pieces to give them: up to 4 items the rounded half is the whole level, and a
-        // fork would then use a second stream nobody has created (reserve_scratch sees nothing to reserve for it)
-        if (std::min(chunk, half) < items) {
-            pl.two_lanes = true;
-            pl.piece = std::min(chunk, half);
-        }
-    }
-    return pl;
+    // joint_plan.h states the rule (halves of whole workgroups of the one-wave-per-gate kernels; two lanes only when there
+    // are two pieces to give them: up to 4 items the rounded half is the whole level, and a fork would then use a second
+    // stream nobody has created -- reserve_scratch sees nothing to reserve for it)
+    const JointLevelPlan jp = joint_level_plan(items, (int64_t)d->opt.chunk, d->opt.overlap && d->use_w64 && d->concurrency == 1, d->opt.overlap_min);
+    return LevelPlan{jp.two_lanes, jp.piece};
 }
 
 // need: rotation items of the lane's widest piece; need_comb: gates of its widest piece of a level with MUX gates (0 = none)
@@ -608,11 +611,12 @@ static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t i
         Torus32* ext = to_caller && !mv ? after.rows_out + (size_t)done * row_words : (Torus32*)ln.ext;
         Torus32* rows = mux ? (Torus32*)ln.comb : !mv ? ext : to_caller ? after.rows_out + (size_t)(done * nf) * row_words : (Torus32*)ln.mv.rows;
         tbr.mark(ln.stream);
-        const int nbr = launch_blind_rotate(d, ln, plan, w, cnt, mv ? nullptr : ext, -1, mv ? (Torus32*)ln.mv.acc : nullptr);
+        const BrPart part{w, cnt};
+        const int nbr = launch_blind_rotate(d, ln, plan, &part, 1, mv ? nullptr : ext, -1, mv ? (Torus32*)ln.mv.acc : nullptr);
         tbr.mark(ln.stream);
         HIP_CHECK(hipGetLastError());
         if (mv) d->mv.extract(ln.stream, ln.mv.acc, cnt, after.n_factors, after.bias, ext, rows);
-        d->br.audit(ln.br, plan, d->opt, ln.stream, w, cnt, ext);
+        d->br.audit(ln.br, plan, d->opt, ln.stream, &part, 1, ext);
         if (!to_caller) {
             tks.mark(ln.stream);
             WorkDesc wk = w;
@@ -996,6 +1000,228 @@ void Evaluator::eval_circuit_device_once(const Circuit& c, size_t batch, const T
     add_times(stats, tall, tbr, tks);
 }
 
+
+// ------------------------------------------------------------------------
+// Joint evaluation: several circuits' batches together, level by level (joint_plan.h).
+
+// One step of a joint evaluation: run_items' sibling over the concatenation of the parts' rotation items.  parts[i] is job
+// parts[i].job's level, descs[i] its descriptor (item0 = 0: items are numbered within the part).  plan_level, the chunk,
+// the level halves on two lanes, plan_blind_rotate, the rotation of roles and the guard all act on the JOINT item count;
+// every piece is ONE blind-rotation launch over the shares of the parts it touches (a prologue per share, one sequence of CMux
+// slices), one audit decision, and then per share the tail run_items has: k_level_combine where the part's level has MUX gates,
+// and a key switch with the part's own descriptor over its rows of `ext`.  Pieces are cut at gate boundaries of the part the
+// cut falls in (joint_piece_items), so both rotations of a MUX are in the same piece, lane and `ext`.
+static void run_joint_items(const Params& p, Evaluator::Impl* d, const JointPart* parts, const WorkDesc* descs, size_t n_parts, Timer& tbr,
+                            Timer& tks, EvalStats* stats) {
+    const int64_t items = joint_items(parts, n_parts);
+    if (items == 0) return;
+    const size_t row_words = (size_t)(d->K.N + 4);
+    const LevelPlan pl = plan_level(d, items);
+    {
+        JointNeeds needs;
+        joint_step_needs(parts, n_parts, JointLevelPlan{pl.two_lanes, pl.piece}, &needs);
+        reserve_lane(p, d, d->lane[0], needs.items[0], needs.comb[0]);  // in place already: prepare_jobs
+        if (needs.items[1]) {
+            ensure_lanes(d, 2);
+            reserve_lane(p, d, d->lane[1], needs.items[1], needs.comb[1]);
+        }
+    }
+    Fork fork(d, pl.two_lanes ? 2 : 1);
+    if (pl.two_lanes) d->opt.overlapped_levels++;
+    ScopedSet<bool> halves(d->level_on_two_lanes, pl.two_lanes);
+    std::vector<BrPart> sub;
+    std::vector<size_t> of;  // sub[q] is a share of parts[of[q]]
+    int k = 0;
+    for (int64_t done = 0, cnt = 0; done < items; done += cnt, k++) {
+        cnt = joint_piece_items(parts, n_parts, done, pl.piece);
+        Lane& ln = d->lane[pl.two_lanes ? (k & 1) : 0];
+        if (cnt < 1 || (size_t)cnt > ln.ext.items()) throw std::logic_error("joint piece larger than the lane's extracted-sample rows");
+        sub.clear();
+        of.clear();
+        for (size_t i = 0; i < n_parts; i++) {
+            const JointShare sh = joint_share(parts, i, done, cnt);
+            if (!sh.cnt) continue;
+            WorkDesc w = descs[i];
+            w.item0 = sh.local0;
+            sub.push_back(BrPart{w, sh.cnt});
+            of.push_back(i);
+        }
+        const BrPlan plan = plan_blind_rotate(p, d, ln, cnt);  // by the joint size; once: the launch and the audit see the same choice
+        Torus32* ext = ln.ext;
+        tbr.mark(ln.stream);
+        const int nbr = launch_blind_rotate(d, ln, plan, sub.data(), sub.size(), ext, -1, nullptr);
+        tbr.mark(ln.stream);
+        HIP_CHECK(hipGetLastError());
+        d->br.audit(ln.br, plan, d->opt, ln.stream, sub.data(), sub.size(), ext);
+        tks.mark(ln.stream);
+        int64_t row = 0, comb_row = 0;  // the share's first row of ext; combined rows handed out so far
+        for (size_t q = 0; q < sub.size(); q++) {
+            const JointPart& part = parts[of[q]];
+            const WorkDesc& w = sub[q].W;
+            const Torus32* rows = ext + (size_t)row * row_words;
+            WorkDesc wk = w;
+            int64_t n_rows = sub[q].cnt;
+            if (part.nm > 0) {
+                if (!level_gate_boundary(w.item0, part.ng, part.nm) || !level_gate_boundary(w.item0 + sub[q].cnt, part.ng, part.nm))
+                    throw std::logic_error("joint piece cut inside a MUX gate");
+                const int64_t gate0 = level_gates_before(w.item0, part.ng, part.nm);
+                n_rows = level_gates_before(w.item0 + sub[q].cnt, part.ng, part.nm) - gate0;
+                if ((size_t)(comb_row + n_rows) > ln.comb.items() || (d->K.N & 3)) throw std::logic_error("combined rows of a joint MUX level not reserved");
+                Torus32* dst = ln.comb + (size_t)comb_row * row_words;
+                hipLaunchKernelGGL(k_level_combine, dim3((unsigned)n_rows), dim3(256), 0, ln.stream, rows, dst, d->K.N, gate0, w.item0, part.ng, part.nm);
+                rows = dst;
+                comb_row += n_rows;
+                wk.nm = 0;  // the key switch over GATES, as in run_items
+                wk.item0 = gate0;
+            }
+            launch_keyswitch(d, ln, wk, n_rows, rows, nullptr);
+            HIP_CHECK(hipGetLastError());
+            row += sub[q].cnt;
+        }
+        tks.mark(ln.stream);
+        if (stats) {
+            stats->blind_rotate_launches += nbr;
+            stats->keyswitch_launches += (int64_t)sub.size();
+            stats->chunks++;
+        }
+    }
+    fork.join();
+    if (stats) stats->bootstraps += items;
+}
+
+namespace {
+// the jobs of a call that have a batch, and what joint_plan.h reads of them
+struct LiveJobs {
+    std::vector<const EvalJob*> jobs;
+    std::vector<std::vector<int32_t>> ng, nm;
+    std::vector<JointJob> plan;
+    LiveJobs(const EvalJob* all, size_t n) {
+        for (size_t j = 0; j < n; j++) {
+            if (all[j].batch == 0) continue;
+            if (!all[j].circuit) throw std::invalid_argument("joint evaluation: a job without a circuit");
+            jobs.push_back(&all[j]);
+        }
+        ng.resize(jobs.size());
+        nm.resize(jobs.size());
+        for (size_t j = 0; j < jobs.size(); j++) {
+            const Circuit& c = *jobs[j]->circuit;
+            for (int32_t L = 1; L <= c.n_levels(); L++) {
+                ng[j].push_back(c.level_offset[L] - c.level_offset[L - 1]);
+                nm[j].push_back(c.n_mux(L));
+            }
+            plan.push_back(JointJob{c.n_levels(), ng[j].data(), nm[j].data(), (int64_t)jobs[j]->batch});
+        }
+    }
+};
+}  // namespace
+
+// Everything a joint evaluation allocates: per job the wire store and the gate / output tables, and the scratch of the
+// widest joint step, so that the evaluation itself -- and a warm call -- allocates nothing.
+void Evaluator::prepare_jobs(const EvalJob* jobs, size_t n_jobs) {
+    begin_call();
+    const LiveJobs live(jobs, n_jobs);
+    if (live.jobs.empty()) return;
+    while (d_->job_store.size() < live.jobs.size()) d_->job_store.emplace_back(new Impl::JobStore);
+    for (size_t j = 0; j < live.jobs.size(); j++) {
+        const Circuit& c = *live.jobs[j]->circuit;
+        Impl::JobStore& js = *d_->job_store[j];
+        js.store.reserve_exact(live.jobs[j]->batch * (size_t)c.n_slots, (size_t)d_->K.stride * 4);
+        js.d_gates.reserve_exact(std::max<size_t>(c.gates.size(), 1));
+        js.d_outs.reserve_exact(std::max<size_t>(c.outputs.size(), 1));
+    }
+    ScopedSet<int32_t> alone(d_->concurrency, 1);  // no pipelines in a joint evaluation: plan_level sees one stream
+    JointNeeds needs;
+    std::vector<JointPart> parts(live.jobs.size());
+    const int32_t steps = joint_steps(live.plan.data(), live.plan.size());
+    for (int32_t s = 1; s <= steps; s++) {
+        const size_t n = joint_step_parts(live.plan.data(), live.plan.size(), s, parts.data());
+        const LevelPlan pl = plan_level(d_, std::max<int64_t>(joint_items(parts.data(), n), 1));
+        joint_step_needs(parts.data(), n, JointLevelPlan{pl.two_lanes, pl.piece}, &needs);
+    }
+    reserve_lane(p_, d_, d_->lane[0], needs.items[0], needs.comb[0]);
+    if (needs.items[1]) {
+        ensure_lanes(d_, 2);
+        reserve_lane(p_, d_, d_->lane[1], needs.items[1], needs.comb[1]);
+    }
+}
+
+// A joint call repeats as a WHOLE (run_guarded), and runs on the two-limb kernels from the start when any job's output range
+// shares a word with any job's input range: the rule of the single calls, over all pairs.
+void Evaluator::eval_jobs_device(const EvalJob* jobs, size_t n_jobs, EvalStats* stats) {
+    const size_t stride = (size_t)d_->K.stride;
+    bool intact = true;
+    for (size_t a = 0; a < n_jobs && intact; a++) {
+        if (!jobs[a].batch || !jobs[a].circuit) continue;
+        for (size_t b = 0; b < n_jobs && intact; b++) {
+            if (!jobs[b].batch || !jobs[b].circuit) continue;
+            intact = !overlaps(jobs[a].d_out, jobs[a].batch * jobs[a].circuit->outputs.size() * stride,
+                               {{jobs[b].d_in, jobs[b].batch * (size_t)jobs[b].circuit->n_inputs * stride}});
+        }
+    }
+    run_guarded(intact, stats, [&] { eval_jobs_device_once(jobs, n_jobs, stats); });
+}
+
+void Evaluator::eval_jobs_device_once(const EvalJob* jobs, size_t n_jobs, EvalStats* stats) {
+    begin_call();
+    const LiveJobs live(jobs, n_jobs);
+    if (live.jobs.empty()) return;
+    const int32_t stride = d_->K.stride;
+    const size_t row_bytes = (size_t)stride * 4;
+    prepare_jobs(jobs, n_jobs);
+    for (size_t j = 0; j < live.jobs.size(); j++) {
+        const Circuit& c = *live.jobs[j]->circuit;
+        Impl::JobStore& js = *d_->job_store[j];
+        if (!c.gates.empty())
+            HIP_CHECK(hipMemcpyAsync(js.d_gates, c.gates.data(), c.gates.size() * sizeof(DevGate), hipMemcpyHostToDevice, stream_));
+        if (!c.outputs.empty())
+            HIP_CHECK(hipMemcpyAsync(js.d_outs, c.outputs.data(), c.outputs.size() * sizeof(OutRef), hipMemcpyHostToDevice, stream_));
+    }
+    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(stats != nullptr, stream_);
+    tall.mark();
+    // every job's inputs -> slots 0..n_inputs-1 of every expression of ITS store, before any output row is written
+    for (size_t j = 0; j < live.jobs.size(); j++) {
+        const Circuit& c = *live.jobs[j]->circuit;
+        if (c.n_inputs > 0)
+            HIP_CHECK(hipMemcpy2DAsync(d_->job_store[j]->store, (size_t)c.n_slots * row_bytes, live.jobs[j]->d_in, (size_t)c.n_inputs * row_bytes,
+                                       (size_t)c.n_inputs * row_bytes, live.jobs[j]->batch, hipMemcpyDeviceToDevice, stream_));
+    }
+    {
+        ScopedSet<int32_t> alone(d_->concurrency, 1);
+        std::vector<JointPart> parts(live.jobs.size());
+        std::vector<WorkDesc> descs(live.jobs.size());
+        const int32_t steps = joint_steps(live.plan.data(), live.plan.size());
+        for (int32_t s = 1; s <= steps; s++) {
+            const size_t n = joint_step_parts(live.plan.data(), live.plan.size(), s, parts.data());
+            for (size_t i = 0; i < n; i++) {
+                const Circuit& c = *live.jobs[parts[i].job]->circuit;
+                const Impl::JobStore& js = *d_->job_store[parts[i].job];
+                WorkDesc W{};
+                W.gates = js.d_gates;
+                W.g0 = c.level_offset[s - 1];
+                W.ng = parts[i].ng;
+                W.nm = parts[i].nm;
+                W.store = js.store;
+                W.n_slots = c.n_slots;
+                W.item0 = 0;
+                descs[i] = W;
+            }
+            run_joint_items(p_, d_, parts.data(), descs.data(), n, tbr, tks, stats);
+            if (stats) stats->levels++;
+        }
+    }
+    for (size_t j = 0; j < live.jobs.size(); j++) {
+        const Circuit& c = *live.jobs[j]->circuit;
+        const int32_t n_out = (int32_t)c.outputs.size();
+        if (n_out == 0) continue;
+        hipLaunchKernelGGL(k_gather_outputs, dim3((unsigned)(live.jobs[j]->batch * n_out)), dim3(128), 0, stream_, d_->job_store[j]->d_outs, n_out,
+                           d_->job_store[j]->store, c.n_slots, live.jobs[j]->d_out, (int64_t)live.jobs[j]->batch, stride, p_.n);
+        HIP_CHECK(hipGetLastError());
+    }
+    tall.mark();
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    add_times(stats, tall, tbr, tks);
+}
+
 void Evaluator::debug_blind_rotate_once(size_t count, const Torus32* d_x, Torus32* d_acc, int32_t steps) {
     begin_call();
     WorkDesc W{};
@@ -1004,7 +1230,8 @@ void Evaluator::debug_blind_rotate_once(size_t count, const Torus32* d_x, Torus3
     W.flat_out = nullptr;
     W.flat_type = -1;
     Lane& ln = d_->lane[0];
-    launch_blind_rotate(d_, ln, plan_blind_rotate(p_, d_, ln, (int64_t)count, steps), W, (int64_t)count, nullptr, steps, d_acc);
+    const BrPart part{W, (int64_t)count};
+    launch_blind_rotate(d_, ln, plan_blind_rotate(p_, d_, ln, (int64_t)count, steps), &part, 1, nullptr, steps, d_acc);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(stream_));
 }

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/ieache.h"
 #include "circuit_cache.h"
 #include "evaluator.h"
 #include "params.h"
@@ -22,6 +23,14 @@ struct ieache_ctx {
     bool fold = false;           // "fold_constants"
     bool level_quantum = true;   // "level_quantum": batch-aware level widths for the slack-balanced circuits
 };
+
+// ieache_eval_jobs (include/ieache.h, section 3c) over a device group, exported from the library like the group forms of
+// section 2b: every job's batch is cut over the members with ieache_shard_slice (shard_jobs, group_run.h), member m runs
+// ieache_eval_jobs on its slices on a host thread of its own -- slices that are empty dropped -- and a member left without
+// any does nothing and reports zeros.  The jobs are checked once, on member 0, before any thread starts (the circuits give
+// the rows per expression).  stats: NULL or one record per member.  First failing member wins, behind "member M (device D): ";
+// the outputs are then unspecified -- no partial output is promised -- and the group stays usable.  A NULL group: IEACHE_EINVAL.
+extern "C" int ieache_group_eval_jobs(ieache_group* g, const ieache_job* jobs, size_t n_jobs, ieache_stats* stats /* [n members] or NULL */);
 
 namespace ieache {
 

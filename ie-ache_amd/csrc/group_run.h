@@ -25,6 +25,23 @@ inline void shard_slice(size_t total, size_t parts, size_t part, size_t* first, 
     *count = base + (part < extra ? 1 : 0);
 }
 
+// A job list (ieache_job, include/ieache.h: anything with batch, in_lwe, out_lwe) as member `part` of `parts` takes it: every
+// job's batch cut with shard_slice, its rows `in_words[j]` / `out_words[j]` words per expression further on, empty slices
+// dropped.  Appends to *out; order is kept.
+template <class Job>
+void shard_jobs(const Job* jobs, size_t n_jobs, const size_t* in_words, const size_t* out_words, size_t parts, size_t part, std::vector<Job>* out) {
+    for (size_t j = 0; j < n_jobs; j++) {
+        size_t first = 0, count = 0;
+        shard_slice(jobs[j].batch, parts, part, &first, &count);
+        if (!count) continue;
+        Job s = jobs[j];
+        s.batch = count;
+        s.in_lwe = jobs[j].in_lwe + first * in_words[j];
+        s.out_lwe = jobs[j].out_lwe + first * out_words[j];
+        out->push_back(s);
+    }
+}
+
 // run_sliced's default `spawn`: a host thread per part
 struct SpawnThread {
     template <class Body>

@@ -84,8 +84,9 @@ def run_data(socket_path, operator_code, cloud_data):
 
 
 def stats(socket_path):
-    """-> dict(evaluations, batched_requests, largest_batch, devices, sharded_evaluations, device_jobs): how the daemon has
-    grouped its RUN_* requests so far and, with several devices, how many jobs each one ran (a list)."""
+    """-> dict(evaluations, batched_requests, largest_batch, devices, sharded_evaluations, joint_rounds, joint_requests,
+    device_jobs): how the daemon has grouped its RUN_* requests so far -- joint_rounds: evaluations that ran two or more
+    circuits together level by level -- and, with several devices, how many jobs each one ran (a list)."""
     rc, log, _ = request(socket_path, OP_STATS, timeout=30.0)
     if rc != 0:
         raise DaemonError("stats: %s" % log)
@@ -104,10 +105,11 @@ def shutdown(socket_path):
     return request(socket_path, OP_SHUTDOWN, timeout=30.0)[0]
 
 
-def spawn(socket_path, cloud_key, nbit_key=None, device=0, wait=120.0, env=None, batch_window_ms=0, max_batch=None, devices=None):
+def spawn(socket_path, cloud_key, nbit_key=None, device=0, wait=120.0, env=None, batch_window_ms=0, max_batch=None, devices=None, joint=None):
     """Start `cloudd` and wait until it answers a ping (the key load + transform take ~0.4 s at n=630).
     batch_window_ms > 0: requests arriving within that window are answered together, same-circuit ones as one
-    level-batched GPU run (csrc/daemon.h)."""
+    level-batched GPU run (csrc/daemon.h).  joint=0: requests for different circuits in one round are evaluated one circuit
+    after another instead of together level by level (--joint, default 1); the answers are the same."""
     exe = os.path.join(_PKG, "cloudd")
     if not os.path.exists(exe):
         raise DaemonError("%s is missing: run __graft_entry__.build()" % exe)
@@ -120,6 +122,8 @@ def spawn(socket_path, cloud_key, nbit_key=None, device=0, wait=120.0, env=None,
         cmd += ["--batch-window-ms", str(int(batch_window_ms))]
     if max_batch:
         cmd += ["--max-batch", str(int(max_batch))]
+    if joint is not None:
+        cmd += ["--joint", str(int(joint))]
     proc = subprocess.Popen(cmd, env=env)
     t0 = time.monotonic()
     while time.monotonic() - t0 < wait:

@@ -78,6 +78,12 @@ class Stats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class Job(C.Structure):
+    """ieache_job: one circuit's batch of a joint call (Context.eval_jobs builds these)."""
+    _fields_ = [("kind", C.c_int), ("bits", C.c_int), ("netlist", C.c_void_p), ("batch", C.c_size_t),
+                ("in_lwe", C.c_void_p), ("out_lwe", C.c_void_p)]
+
+
 class CircuitInfo(C.Structure):
     _fields_ = [("n_inputs", C.c_int32), ("n_outputs", C.c_int32), ("n_slots", C.c_int32), ("depth", C.c_int32),
                 ("max_width", C.c_int32), ("bootstraps", C.c_int64), ("n_and", C.c_int64), ("n_xor", C.c_int64),
@@ -180,6 +186,11 @@ def lib():
     L.ieache_prepare_netlist.argtypes = [vp, vp, C.c_size_t]
     L.ieache_eval_netlist.argtypes = [vp, vp, C.c_size_t, i32p, i32p, sp]
     L.ieache_eval_netlist_device.argtypes = [vp, vp, C.c_size_t, vp, vp, sp]
+    jp = C.POINTER(Job)
+    L.ieache_prepare_jobs.argtypes = [vp, jp, C.c_size_t]
+    L.ieache_eval_jobs.argtypes = [vp, jp, C.c_size_t, sp]
+    L.ieache_eval_jobs_device.argtypes = [vp, jp, C.c_size_t, sp]
+    L.ieache_group_eval_jobs.argtypes = [vp, jp, C.c_size_t, sp]
     ip = C.POINTER(C.c_int)
     L.ieache_group_create.restype = vp
     L.ieache_group_create.argtypes = [C.c_char_p, ip, C.c_int]
@@ -243,6 +254,32 @@ def _i32(a):
 def _stats_ref(stats):
     """the optional Stats argument of an entry point: a reference to it, or a null pointer"""
     return C.byref(stats) if stats is not None else None
+
+
+def _job_array(jobs, n_words, fold):
+    """jobs: (kind, bits, in_lwe) or (CompiledNetlist, in_lwe) each, in_lwe [batch][n_inputs][n+1] on the host
+    -> (ieache_job array, the arrays it points into, one output array per job)"""
+    arr = (Job * max(len(jobs), 1))()
+    ins, outs = [], []
+    for i, job in enumerate(jobs):
+        if len(job) == 2:
+            nl, in_lwe = job
+            info = nl.info()
+            arr[i].netlist = nl.h
+        else:
+            kind, bits, in_lwe = job
+            info = circuit_info(kind, bits, fold)
+            arr[i].kind, arr[i].bits = int(kind), int(bits)
+        in_lwe = np.ascontiguousarray(in_lwe, dtype=np.int32)
+        batch = in_lwe.shape[0]
+        assert in_lwe.shape == (batch, info.n_inputs, n_words), in_lwe.shape
+        out = np.zeros((batch, info.n_outputs, n_words), dtype=np.int32)
+        arr[i].batch = batch
+        arr[i].in_lwe = in_lwe.ctypes.data
+        arr[i].out_lwe = out.ctypes.data
+        ins.append(in_lwe)
+        outs.append(out)
+    return arr, ins, outs
 
 
 def default_params():
@@ -518,6 +555,38 @@ class Context:
         check(lib().ieache_eval_netlist(self.h, nl.h, batch, _i32(in_lwe), _i32(out), _stats_ref(stats)))
         return out
 
+    def eval_jobs(self, jobs, stats=None):
+        """Several circuits' batches together, level by level, so that their narrow levels share every launch (include/ieache.h,
+        section 3c).  jobs: (kind, bits, in_lwe) or (CompiledNetlist, in_lwe) each, in_lwe as eval_batch / eval_netlist take it
+        -> one output array per job, each word for word what the job gives alone."""
+        jobs = list(jobs)
+        arr, _ins, outs = _job_array(jobs, self.params.n + 1, getattr(self, "_fold", False))
+        check(lib().ieache_eval_jobs(self.h, arr, len(jobs), _stats_ref(stats)))
+        return outs
+
+    def eval_jobs_device(self, jobs, stats=None):
+        """eval_jobs on device rows of lwe_stride int32: (kind, bits, batch, d_in, d_out) or (CompiledNetlist, batch, d_in, d_out)
+        each, pointers as ints."""
+        jobs = list(jobs)
+        arr = (Job * max(len(jobs), 1))()
+        for i, job in enumerate(jobs):
+            if len(job) == 4:
+                arr[i].netlist = job[0].h
+            else:
+                arr[i].kind, arr[i].bits = int(job[0]), int(job[1])
+            arr[i].batch, arr[i].in_lwe, arr[i].out_lwe = int(job[-3]), job[-2], job[-1]
+        check(lib().ieache_eval_jobs_device(self.h, arr, len(jobs), _stats_ref(stats)))
+
+    def prepare_jobs(self, jobs):
+        """Allocates what eval_jobs of these jobs needs: (kind, bits, batch) or (CompiledNetlist, batch) each."""
+        arr = (Job * max(len(jobs), 1))()
+        for i, job in enumerate(jobs):
+            if len(job) == 2:
+                arr[i].netlist, arr[i].batch = job[0].h, int(job[1])
+            else:
+                arr[i].kind, arr[i].bits, arr[i].batch = int(job[0]), int(job[1]), int(job[2])
+        check(lib().ieache_prepare_jobs(self.h, arr, len(jobs)))
+
     def prepare_netlist(self, nl, batch):
         """Allocates what eval_netlist* of this netlist and batch needs, so that the evaluation itself allocates nothing."""
         check(lib().ieache_prepare_netlist(self.h, nl.h, batch))
@@ -753,6 +822,15 @@ class Group:
         check(lib().ieache_group_eval_netlist(self.h, nl.h, batch, _i32(in_lwe), _i32(out), st.ref))
         st.deliver()
         return out
+
+    def eval_jobs(self, jobs, stats=None):
+        """Context.eval_jobs with every job's batch cut over the members (ieache_shard_slice)."""
+        jobs = list(jobs)
+        arr, _ins, outs = _job_array(jobs, self.params.n + 1, self._fold)
+        st = _MemberStats(stats, len(self))
+        check(lib().ieache_group_eval_jobs(self.h, arr, len(jobs), st.ref))
+        st.deliver()
+        return outs
 
     def gates(self, gate_type, a, b, stats=None):
         (a, b), count = self._rows(a, b)

@@ -489,6 +489,50 @@ int ieache_eval_netlist(ieache_ctx* ctx, const ieache_netlist* nl, size_t batch,
 int ieache_eval_netlist_device(ieache_ctx* ctx, const ieache_netlist* nl, size_t batch, const int32_t* d_in, int32_t* d_out,
                                ieache_stats* stats);
 
+/* ------------------------------------------------------------------ *
+ * 3c. Several circuits' batches in ONE call, evaluated together level *
+ *    by level.  What a caller holds who has, in the same moment, a    *
+ *    few additions, a few subtractions and a few multiplications      *
+ *    (dragonfly_cipher_cloud.py:1233 runs one ./cloud per operator):  *
+ *    evaluated one after another each is a run of narrow launches,    *
+ *    and a level costs one rotation's latency however few gates it    *
+ *    holds.  Their gates are independent, so they share every launch. *
+ * ------------------------------------------------------------------ */
+/* A job is what ieache_eval_batch or ieache_eval_netlist takes: a circuit, a batch, input and output rows of the shapes
+ * those calls document.  Step s = 1, 2, ... of the call runs level s of every job that still has one as one launch
+ * sequence over all their gates (one prologue and one key switch per job, one sequence of blind-rotation launches over all,
+ * the kernel chosen by the joint size); a shallow job finishes early.  Every job's output words are what the same job gives
+ * alone -- word for word, whatever it ran with.  Level mode only: no expression pipelines ("overlap" still splits wide joint
+ * levels over two streams), so a job that is wide on its own gains nothing here; the call always joins, the decision is the
+ * caller's (cloudd's rule: csrc/joint_plan.h).
+ * Circuits are the context's base circuits of (kind, bits) under its "fold_constants"; "level_quantum" does not apply (a
+ * level cap is chosen for one batch filling rounds alone).  A compiled netlist carries no parameter set and runs under
+ * any context.
+ * A job with batch 0 is skipped (its pointers are not read); n_jobs == 0 succeeds.  A NULL row pointer with a batch, or an
+ * unknown kind / width, fails the WHOLE call with IEACHE_EINVAL before anything is launched or written;
+ * ieache_last_error() starts with "job I: ", I the failing job's index.
+ * stats: bootstraps summed over the jobs; levels = the deepest job's depth; chunks = launch sequences issued (one per joint
+ * level unless "chunk" or level halves cut it); times as for any call.
+ * The rounding guard and the audit act on the joint launches: a trip repeats the whole call on the two-limb kernels, and a
+ * device-form call in which any job's output range shares a word with any job's input range runs on them from the start. */
+typedef ieache_stats ieache_eval_stats;
+typedef struct ieache_job {
+    int kind, bits;                        /* a CIRC_* kind and its width, or */
+    const struct ieache_netlist* netlist;  /* non-NULL: the netlist instead (kind, bits ignored) */
+    size_t batch;
+    const int32_t* in_lwe;                 /* as ieache_eval_batch / ieache_eval_netlist take them (device rows in the _device form) */
+    int32_t* out_lwe;
+} ieache_job;
+/* allocates what the joint evaluation of these jobs needs (pointers are not read), so that a timed first call allocates nothing */
+int ieache_prepare_jobs(ieache_ctx* ctx, const ieache_job* jobs, size_t n_jobs);
+/* host rows, staged through the context's kept staging rows: a warm call allocates nothing */
+int ieache_eval_jobs(ieache_ctx* ctx, const ieache_job* jobs, size_t n_jobs, ieache_eval_stats* stats);
+/* device rows of ieache_lwe_stride() words; stream ordering and pointer checks as ieache_eval_batch_device */
+int ieache_eval_jobs_device(ieache_ctx* ctx, const ieache_job* jobs, size_t n_jobs, ieache_eval_stats* stats);
+/* The form for a device group (section 2b) is exported as well and declared in csrc/group.h, next to the group it cuts the
+ * jobs over: every job's batch goes over the members by ieache_shard_slice's rule, and each member runs ieache_eval_jobs on
+ * its slices. */
+
 /* plaintext simulation of the levelised circuit (host only, no GPU): bits in/out 0/1 */
 int ieache_circuit_simulate(int kind, int bits, const uint8_t* in_bits, uint8_t* out_bits);
 int ieache_circuit_simulate_ex(int kind, int bits, int fold_constants, const uint8_t* in_bits, uint8_t* out_bits);
