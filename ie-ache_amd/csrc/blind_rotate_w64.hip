@@ -267,7 +267,15 @@ __global__ __launch_bounds__(128, 2) void k_blind_rotate_w2(DevKeys K, const dou
 //     coefficient (j - a) mod N is one v_and_or_b32 of a per-step lane value plus 256 r, and the address of coefficient
 //     j + 512 is that address ^ 2048; the negacyclic sign is a v_bfe_i32 of the same per-step value;
 //   * (X^a - 1) acc + offset is formed as (rot ^ m) + ((offset - acc_j) - m)  (v_xad_u32);
-//   * BK_i through buffer loads: the first block of a row requested before its forward transform, the second behind it;
+//   * BK_i through buffer loads: the first block of a row requested inside its forward transform, once the first twiddle
+//     set's 32 registers are free (fft512_forward's MID hook), the second behind the transform;
+//   * six of the seven second inter-pass twiddles resident in 24 VGPRs for the whole kernel (LaneRootsResident, fft512.h): a
+//     transform reads 9 twiddles from the LDS table instead of 15.  All seven do not fit: the <3,7> builds then spill 5 VGPRs;
+//   * the unrotated operands of a decomposition are read back from LDS, which the compiler pairs as ds_read2st64_b32;
+//     carrying polynomial 0's from the update (ds_add_rtn_u32) measured within noise and is not kept;
+//   * the rounding guard's running maximum between steps is a float (what is published; rounding is monotone, so the
+//     figure is the same), and the epilogue forms its addresses again instead of sharing the prologue's: with these the
+//     kernel holds 256 VGPRs without scratch.  303 LDS instructions per step against 345 (profiles/lds_trim_isa_mix.txt);
 //   * the forward transforms' lane-high transpose cross-lane, every other transpose through the gate's padded LDS tile; the
 //     two inverse transforms interleaved through that one tile; ds_add_u32 update;
 //   * GUARD = 2 watches ONE rounded coefficient in four (registers r = 0 and r = 4 of both output polynomials), 1 every one,
@@ -293,7 +301,7 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_w1b(DevKeys K, const
     load_twiddles(sTw, gtw, tid, 64 * G);
     __syncthreads();  // the only workgroup barrier
     if (item >= items) return;
-    const LaneRoots R = make_roots(sTw, lane);
+    const LaneRootsResident R = make_roots<LaneRootsResident>(sTw, lane);  // second twiddle set: 24 VGPRs for the whole kernel
     const uint16_t* __restrict__ bara = st_bara + (size_t)item * nb;
     int32_t* gacc = st_acc + (size_t)item * 2 * kN;
     {
@@ -308,7 +316,9 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_w1b(DevKeys K, const
     uint32_t dec_offset = 0;
 #pragma unroll
     for (int q = 1; q <= L; q++) dec_offset += halfBg << (32 - q * BGBIT);
-    double dev_max = 0.0;
+    // the launch's largest distance is published as a float: kept as one between steps (rounding is monotone, so the
+    // maximum of the rounded distances is the rounded maximum), one VGPR instead of two across the step loop
+    float dev_maxf = 0.0f;
     constexpr int kRowBytes = 2 * kM * (int)sizeof(double2), kStepBytes = 2 * L * kRowBytes;
     const __amdgpu_buffer_rsrc_t bk_rsrc = bk_resource(bkf1, K.n, kStepBytes);
     const int lane16 = bk_lane_offset(lane);
@@ -325,6 +335,7 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_w1b(DevKeys K, const
         const int bki = i * kStepBytes;
         double2 s[2][8];
         uint32_t v0[8], v1[8];
+        double dev_max = 0.0;  // of this step
         // byte offset of coefficient (lane - a) in the 2N-ring [acc, -acc]: bits 2..11 address, bit 12 = negate
         const uint32_t jb4 = ((uint32_t)(lane - a) & (2 * kN - 1)) << 2;
         auto decompose = [&](const uint32_t pb) {
@@ -334,11 +345,13 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_w1b(DevKeys K, const
         auto digit_row = [&](const int sh, const int brow, auto first) {
             constexpr bool FIRST = decltype(first)::value;
             double2 x[8], bA[8], bB[8];
-            load_bk_block(bA, bk_rsrc, lane16, brow);
+            // the first block of the row is requested once the first twiddle set's 32 registers are free (the resident second
+            // set has taken the room the request used to have before the transform); passes 2 and 3 cover its latency
+            auto request_a = [&]() { load_bk_block(bA, bk_rsrc, lane16, brow); };
             digits_to_double2<BGBIT>(x, v0, v1, sh);
             __builtin_amdgcn_sched_barrier(0);
             stamp_phase<DIAG>(tsum, tlast, 1);
-            fft512_forward<true, 1>(x, sT, lane, R);
+            fft512_forward<true, 1>(x, sT, lane, R, request_a);
             stamp_phase<DIAG>(tsum, tlast, 2);
             load_bk_block(bB, bk_rsrc, lane16, brow + kRowBytes / 2);
             __builtin_amdgcn_sched_barrier(0);
@@ -372,6 +385,7 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_w1b(DevKeys K, const
                 __hip_atomic_fetch_add(&accc[j + kM], d1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             }
         }
+        if (GUARD) dev_maxf = fmaxf(dev_maxf, (float)dev_max);
         wave_sync();
         stamp_phase<DIAG>(tsum, tlast, 5);
     }
@@ -379,8 +393,12 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_w1b(DevKeys K, const
 #pragma unroll
         for (int t = 0; t < 8; t++) atomicAdd(&diag[(wave & 1) * 8 + t], tsum[t]);
     }
-    if (GUARD) publish_guard(dev_max, guard, lane);
-    finish_slice<64>(ext, item, acc, gacc, lane);
+    // the epilogue forms its addresses from the lane number again: shared with the prologue's they would be 12 VGPRs held
+    // across the step loop, which has none to spare
+    int elane = lane;
+    asm volatile("" : "+v"(elane));
+    if (GUARD) publish_guard((double)dev_maxf, guard, elane);
+    finish_slice<64>(ext, item, acc, gacc, elane);
 }
 
 // ---- K3 (+K4), throughput form of the PROVABLY EXACT product, round 4: one wave per gate on the TWO-limb spectrum ----

@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "dft8_twist.h"
+#include "tw_roots.h"
 
 namespace ieache {
 namespace w64 {
@@ -80,18 +81,17 @@ __device__ __forceinline__ void tile_sync() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// Twiddle table, one per workgroup in LDS (9 KiB), used by every transform in both
-// directions (the inverse multiplies by the conjugates):
-//   tw[k*64 + lane]       = exp(i*pi*lane/1024) * exp(-2*pi*i*lane*k/512)   twist (lane part) x first inter-pass twiddle
-//   tw[512 + k*8 + p0]    = exp(-2*pi*i*p0*k/64)                            second inter-pass twiddle, p0 = lane & 7
-// Keeping them in registers costs 60 VGPRs per wave, which the BK prefetch needs more.
-constexpr int kTwElems = 8 * 64 + 8 * 8;
-struct LaneRoots {
-    const double2* t1;  // &tw[lane], stride 64
-    const double2* t2;  // &tw[512 + (lane & 7)], stride 8
-    __device__ __forceinline__ double2 a(int k) const { return t1[k * 64]; }
-    __device__ __forceinline__ double2 b(int k) const { return t2[k * 8]; }
-};
+// Twiddle table, one per workgroup in LDS (9 KiB), used by every transform in both directions (the inverse multiplies by
+// the conjugates); its layout and the two ways a lane reads it are tw_roots.h:
+//   LaneRoots           every transform reads both sets from the table (15 ds_read_b128): the default, every kernel but one.
+//   LaneRootsResident   six of the seven entries of the second set, which depends on lane & 7 alone, held in 24 VGPRs for the
+//                       whole kernel, so a transform reads 9 twiddles (ds_read_b128) instead of 15.  k_blind_rotate_w1b
+//                       takes it, whose eight transforms per step keep the CU's LDS ~80 % busy; it pays with the first BK
+//                       block of a row being requested inside the forward transform (MID hook) instead of before it.  The
+//                       seventh entry spills that kernel; both sets resident cost 60 VGPRs, which the BK prefetch needs more.
+// The transforms take the roots type as a template parameter and read the second set through R.b(k) either way.
+using LaneRoots = TableRoots<double2>;
+using LaneRootsResident = ResidentRoots<double2, 6>;
 __device__ __forceinline__ void build_twiddles(double2* tw, int tid, int nthreads) {
     double s, c;
     for (int idx = tid; idx < 512; idx += nthreads) {
@@ -114,10 +114,10 @@ __device__ __forceinline__ void load_twiddles(double2* sTw, const double2* __res
     for (int idx = tid; idx < kTwElems; idx += nthreads) sTw[idx] = gtw[idx];
 }
 
-__device__ __forceinline__ LaneRoots make_roots(const double2* tw, int lane) {
-    LaneRoots r;
-    r.t1 = tw + lane;
-    r.t2 = tw + 512 + (lane & 7);
+template <class ROOTS = LaneRoots>
+__device__ __forceinline__ ROOTS make_roots(const double2* tw, int lane) {
+    ROOTS r;
+    r.init(tw, lane);
     return r;
 }
 
@@ -206,13 +206,13 @@ constexpr int kTile = 8 * 72;  // double2 elements per tile (9216 B)
 struct NoHook {
     __device__ __forceinline__ void operator()() const {}
 };
-template <bool WSYNC, int XLANE = 0, class MID = NoHook, bool MID_LATE = false>
-__device__ __forceinline__ void fft512_forward(double2 (&x)[8], double2* sT, int lane, const LaneRoots& R, MID mid = MID()) {
+template <bool WSYNC, int XLANE = 0, class MID = NoHook, bool MID_LATE = false, class ROOTS = LaneRoots>
+__device__ __forceinline__ void fft512_forward(double2 (&x)[8], double2* sT, int lane, const ROOTS& R, MID mid = MID()) {
     static_assert(XLANE == 0 || XLANE == 1, "lane-low transposes go through the tile");
     const int hi = lane >> 3, lo = lane & 7;
     const int own = hi * 9 + lo;   // (m, l) = (lane>>3, lane&7) inside a row-block h
     const int blk = hi * 72 + lo;  // (h, l) = (lane>>3, lane&7)
-    // twiddles are fetched from the LDS table ahead of the butterflies that hide their latency
+    // twiddles are fetched from the LDS table ahead of the butterflies that hide their latency (R.b: or are resident)
     double2 tA[8], tB[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) tA[k] = R.a(k);
@@ -258,8 +258,8 @@ __device__ __forceinline__ void fft512_forward(double2 (&x)[8], double2* sT, int
 //   in : spectrum in the layout fft512_forward produces
 //   out: x[r] * untwist_gain(r) = y_{64r+lane}: untwisted and normalised up to one real factor per register, which the
 //        caller folds into the FMA that rounds (round_coef)
-template <bool WSYNC>
-__device__ __forceinline__ void fft512_inverse(double2 (&x)[8], double2* sT, int lane, const LaneRoots& R) {
+template <bool WSYNC, class ROOTS = LaneRoots>
+__device__ __forceinline__ void fft512_inverse(double2 (&x)[8], double2* sT, int lane, const ROOTS& R) {
     const int hi = lane >> 3, lo = lane & 7;
     const int own = hi * 9 + lo, blk = hi * 72 + lo, rd = hi * 72 + lo * 9;
     double2 tA[8], tB[8];
@@ -293,9 +293,9 @@ __device__ __forceinline__ void fft512_inverse(double2 (&x)[8], double2* sT, int
 // long as each [write, read] pair of one transform is issued whole, the other transform's
 // butterflies run while that round trip is in flight.  (Alone, a wave spends ~2/3 of a
 // transform waiting on its four LDS round trips.)
-template <bool WSYNC>
+template <bool WSYNC, class ROOTS = LaneRoots>
 __device__ __forceinline__ void fft512_inverse_pair(double2 (&x)[8], double2 (&y)[8], double2* sT, int lane,
-                                                    const LaneRoots& R) {
+                                                    const ROOTS& R) {
     const int hi = lane >> 3, lo = lane & 7;
     const int own = hi * 9 + lo, blk = hi * 72 + lo, rd = hi * 72 + lo * 9;
     double2 tA[8], tB[8];
