@@ -14,4 +14,7 @@ from .evaluator import (  # noqa: F401
 )
 from . import tools  # noqa: F401
 from . import netlists  # noqa: F401
+from . import programs  # noqa: F401
+from .programs import WordProgram, Register, netlist_export  # noqa: F401
+from .programs import FAMILY_REFERENCE, FAMILY_KOGGE_STONE, FAMILY_CARRY_SAVE, FAMILY_FULL_ADDER  # noqa: F401
 from .compute import compute, compute_final, FAILURE_SIZE  # noqa: F401

@@ -21,6 +21,7 @@
 #include "group.h"
 #include "group_run.h"
 #include "mix_plan.h"
+#include "program.h"
 #include "tfhe_host.h"
 
 using namespace ieache;
@@ -482,6 +483,7 @@ int ieache_prepare_batch(ieache_ctx* ctx, int kind, int bits, size_t batch) {
 // ---- caller-defined netlists: a compiled Circuit behind an opaque handle (host only) ----
 struct ieache_netlist {
     Circuit circuit;
+    RecordedNetlist recorded;  // the gate list as recorded: what ieache_netlist_export gives
 };
 
 ieache_netlist* ieache_netlist_create(int32_t n_inputs, const ieache_net_gate* gates, size_t n_gates, const int32_t* outputs,
@@ -492,7 +494,7 @@ ieache_netlist* ieache_netlist_create(int32_t n_inputs, const ieache_net_gate* g
         if (flags & ~IEACHE_NETLIST_BALANCED) return fail(IEACHE_EINVAL, "netlist: unknown flag");
         std::unique_ptr<ieache_netlist> made(new ieache_netlist);
         made->circuit = build_netlist(n_inputs, reinterpret_cast<const NetGate*>(gates), n_gates, outputs, n_outputs,
-                                      (flags & IEACHE_NETLIST_BALANCED) != 0);
+                                      (flags & IEACHE_NETLIST_BALANCED) != 0, &made->recorded);
         nl = made.release();
         return 0;
     });
@@ -500,6 +502,43 @@ ieache_netlist* ieache_netlist_create(int32_t n_inputs, const ieache_net_gate* g
 }
 
 void ieache_netlist_destroy(ieache_netlist* nl) { delete nl; }
+
+// ---- 3d. word programs: compiled to the same handle (program.h) ----
+ieache_netlist* ieache_program_compile(const ieache_word_instr* instrs, size_t n_instrs, const ieache_word_arg* args, size_t n_args,
+                                       const uint32_t* const_words, size_t n_const_words, const int32_t* outputs, size_t n_outputs,
+                                       int flags) {
+    static_assert(sizeof(ieache_word_instr) == sizeof(WordInstr) && sizeof(ieache_word_arg) == sizeof(WordArg),
+                  "ieache_word_instr / ieache_word_arg are program.h's WordInstr / WordArg");
+    static_assert(IEACHE_WOP_INPUT == WOP_INPUT && IEACHE_WOP_CONST == WOP_CONST && IEACHE_WOP_ZEXT == WOP_ZEXT && IEACHE_WOP_SLICE == WOP_SLICE &&
+                      IEACHE_WOP_SHL == WOP_SHL && IEACHE_WOP_NOT == WOP_NOT && IEACHE_WOP_CONCAT == WOP_CONCAT && IEACHE_WOP_AND == WOP_AND &&
+                      IEACHE_WOP_OR == WOP_OR && IEACHE_WOP_XOR == WOP_XOR && IEACHE_WOP_ANDBIT == WOP_ANDBIT && IEACHE_WOP_ADD == WOP_ADD &&
+                      IEACHE_WOP_SUB == WOP_SUB && IEACHE_WOP_RSUB == WOP_RSUB && IEACHE_WOP_MUL == WOP_MUL && IEACHE_WOP_SUM == WOP_SUM &&
+                      IEACHE_WOP_LT == WOP_LT && IEACHE_WOP_EQ == WOP_EQ && IEACHE_WOP_SELECT == WOP_SELECT && WOP_COUNT == IEACHE_WOP_SELECT + 1,
+                  "program.h's opcodes and include/ieache.h's IEACHE_WOP_* disagree");
+    static_assert(IEACHE_FAMILY_REFERENCE == FAMILY_REFERENCE && IEACHE_FAMILY_FULL_ADDER == FAMILY_FULL_ADDER && IEACHE_FAMILY_KOGGE_STONE == FAMILY_KOGGE_STONE &&
+                      IEACHE_FAMILY_CARRY_SAVE == FAMILY_CARRY_SAVE && IEACHE_PROGRAM_FOLD == kProgramFold &&
+                      IEACHE_NETLIST_BALANCED == kProgramBalanced && IEACHE_WORD_MAX_WIDTH == kMaxWordWidth,
+                  "program.h and include/ieache.h's section 3d disagree");
+    ieache_netlist* nl = nullptr;
+    guarded([&] {
+        std::unique_ptr<ieache_netlist> made(new ieache_netlist);
+        CompiledProgram p = compile_program(reinterpret_cast<const WordInstr*>(instrs), n_instrs, reinterpret_cast<const WordArg*>(args), n_args,
+                                            const_words, n_const_words, outputs, n_outputs, flags);
+        made->circuit = std::move(p.circuit);
+        made->recorded = std::move(p.recorded);
+        nl = made.release();
+        return 0;
+    });
+    return nl;
+}
+
+int64_t ieache_netlist_export(const ieache_netlist* nl, ieache_net_gate* gates, size_t cap, int32_t* outputs, size_t out_cap) {
+    if (!nl) return fail(IEACHE_EINVAL, "null argument");
+    const RecordedNetlist& r = nl->recorded;
+    if (gates && cap >= r.gates.size() && !r.gates.empty()) memcpy(gates, r.gates.data(), r.gates.size() * sizeof(NetGate));
+    if (outputs && out_cap >= r.outputs.size() && !r.outputs.empty()) memcpy(outputs, r.outputs.data(), r.outputs.size() * sizeof(int32_t));
+    return (int64_t)r.gates.size();
+}
 
 int ieache_netlist_info(const ieache_netlist* nl, ieache_circuit_info* out, int64_t gates_by_type[IEACHE_GATE_TYPES]) {
     return guarded([&] {

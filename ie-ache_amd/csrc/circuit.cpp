@@ -799,6 +799,22 @@ static Word build_stage(CircuitBuilder& b, const KindRow& row, const Word& A, co
     return adder(b, minuend, complement, CircuitBuilder::constant(1));
 }
 
+Word build_word_operator(CircuitBuilder& b, int32_t kind, const Word& A, const Word& B, const Word& carry) {
+    const Stages s = stages_of(kind);
+    if (!s.s1 || s.s2) throw std::invalid_argument("not a plain circuit kind");
+    if (A.size() != B.size()) throw std::invalid_argument("operands of different widths");
+    if (A.size() > 256 || !accepts(*s.s1, (int32_t)A.size()))
+        throw std::invalid_argument(std::string("kind ") + s.s1->name + " does not take operands of " + std::to_string(A.size()) + " samples");
+    if (carry.size() != 32) throw std::invalid_argument("the carry word must be 32 samples");
+    return build_stage(b, *s.s1, A, B, carry);
+}
+
+Word build_family_adder(CircuitBuilder& b, CircuitFamily family, const Word& x, const Word& y, Ref cin) {
+    if (family != FAMILY_KOGGE_STONE && family != FAMILY_FULL_ADDER) throw std::invalid_argument("no adder of that family");
+    if (x.empty() || x.size() != y.size()) throw std::invalid_argument("operands of different widths");
+    return family == FAMILY_KOGGE_STONE ? kogge_stone_add(b, x, y, cin) : full_adder_ripple(b, x, y, cin);
+}
+
 bool build_circuit(int32_t kind, int32_t bits, Circuit* out, bool balanced, bool fold, int32_t level_cap) {
     if (!circuit_accepts_width(kind, bits)) return false;
     const Stages s = stages_of(kind);
@@ -888,8 +904,29 @@ int32_t circuit_level_cap(const Circuit& base, int64_t batch, int32_t resident, 
     return cap > 0 || resident_alt <= 0 ? cap : quantum_level_cap(base, batch, resident_alt);
 }
 
+RecordedNetlist export_recorded(const CircuitBuilder& b, const Word& outputs) {
+    auto ref = [](Ref r) -> int32_t { return r.id < 0 ? (r.neg ? -1 : -2) : (int32_t)((uint32_t)r.id << 1 | (r.neg ? 1u : 0u)); };
+    RecordedNetlist out;
+    const std::vector<Gate>& gates = b.gates();
+    out.gates.resize(gates.size());
+    for (size_t i = 0; i < gates.size(); i++) {
+        const Gate& g = gates[i];
+        const int32_t requested = b.requested_types()[i];
+        Ref x = g.a, y = g.b;
+        if (requested != g.type) {  // undo gate2's lowering: the operand signs it flipped
+            if (requested == GATE_NOR || requested == GATE_ANDNY || requested == GATE_ORNY) x.neg = !x.neg;
+            if (requested == GATE_NOR || requested == GATE_ANDYN || requested == GATE_ORYN) y.neg = !y.neg;
+        }
+        const bool three = g.type == GATE_MUX || is_gate3(g.type);
+        out.gates[i] = NetGate{requested, ref(x), ref(y), three ? ref(g.c) : 0};
+    }
+    out.outputs.resize(outputs.size());
+    for (size_t i = 0; i < outputs.size(); i++) out.outputs[i] = ref(outputs[i]);
+    return out;
+}
+
 Circuit build_netlist(int32_t n_inputs, const NetGate* gates, size_t n_gates, const int32_t* outputs, size_t n_outputs,
-                      bool balanced) {
+                      bool balanced, RecordedNetlist* recorded) {
     auto bad = [](const std::string& msg) { throw std::invalid_argument("netlist: " + msg); };
     if (n_inputs < 1) bad("needs at least one input");
     if (n_outputs < 1 || !outputs) bad("needs at least one output");
@@ -934,6 +971,7 @@ Circuit build_netlist(int32_t n_inputs, const NetGate* gates, size_t n_gates, co
         outs[i] = ref(outputs[i], (int64_t)n_inputs + (int64_t)n_gates, "output " + std::to_string(i) + " (after gate " + std::to_string(n_gates) + ")");
     Circuit c = finalize_circuit("netlist", b, outs, balanced, 0);
     c.n_reference_bootstraps = c.n_bootstraps;
+    if (recorded) *recorded = export_recorded(b, outs);
     return c;
 }
 

@@ -177,8 +177,17 @@ Circuit finalize_circuit(const std::string& name, const CircuitBuilder& b, const
 struct NetGate {
     int32_t type, a, b, c;
 };
+// The gate list a builder recorded, in the form build_netlist takes: gate g's output is wire n_inputs + g, the references of
+// `outputs` likewise.  A gate lowered while recording (NOR .. ORYN) is given back as the type it was requested as, so feeding
+// the list to build_netlist records the same gates again; with folding on it is the list AFTER folding and sharing.
+struct RecordedNetlist {
+    std::vector<NetGate> gates;
+    std::vector<int32_t> outputs;
+};
+RecordedNetlist export_recorded(const CircuitBuilder& b, const Word& outputs);
+// recorded (may be null): filled with export_recorded of what was built
 Circuit build_netlist(int32_t n_inputs, const NetGate* gates, size_t n_gates, const int32_t* outputs, size_t n_outputs,
-                      bool balanced);
+                      bool balanced, RecordedNetlist* recorded = nullptr);
 
 // ---- the circuits main() dispatches to (cloud.c:870-2718) ----
 // Input sample order for all of them: operand 1 words (32 samples each, LSB
@@ -247,6 +256,13 @@ bool decode_chain(int32_t kind, int32_t* k1, int32_t* k2, bool* flip);
 // (64/128-bit multipliers); false forces plain ASAP levels.
 // fold=true: constant-folded / gate-shared variant (decrypt-identical, fewer bootstraps; opt-in).
 bool build_circuit(int32_t kind, int32_t bits, Circuit* out, bool balanced = true, bool fold = false, int32_t level_cap = 0);
+// One plain kind's operator on symbolic operands, recorded into `b` exactly as build_circuit records it for that kind (the
+// word programs of program.h are made of these): A and B of one width the kind accepts, carry = the 32-sample carry word.
+// -> the value samples, LSB first (2 x width for a multiplier).  Throws std::invalid_argument for a chain or unknown kind, operands of
+// different widths, a width the kind table refuses or a carry word that is not 32 samples.
+Word build_word_operator(CircuitBuilder& b, int32_t kind, const Word& A, const Word& B, const Word& carry);
+// x + y + cin (equal widths, any width >= 1) as the opt-in adders build it: FAMILY_KOGGE_STONE or FAMILY_FULL_ADDER
+Word build_family_adder(CircuitBuilder& b, CircuitFamily family, const Word& x, const Word& y, Ref cin);
 // Level width (gates per expression) that makes `batch` expressions fill whole rounds of `resident` workgroups:
 // the multiple of resident / gcd(resident, batch) nearest to the circuit's mean width, or 0 (= keep the mean) when
 // a level is under one round anyway or the batch already is a multiple of a round.

@@ -181,6 +181,10 @@ def lib():
     L.ieache_netlist_create.restype = vp
     L.ieache_netlist_create.argtypes = [C.c_int32, vp, C.c_size_t, i32p, C.c_size_t, C.c_int]
     L.ieache_netlist_destroy.argtypes = [vp]
+    L.ieache_program_compile.restype = vp
+    L.ieache_program_compile.argtypes = [vp, C.c_size_t, vp, C.c_size_t, u32p, C.c_size_t, i32p, C.c_size_t, C.c_int]
+    L.ieache_netlist_export.restype = C.c_int64
+    L.ieache_netlist_export.argtypes = [vp, vp, C.c_size_t, i32p, C.c_size_t]
     L.ieache_netlist_info.argtypes = [vp, C.POINTER(CircuitInfo), C.POINTER(C.c_int64)]
     L.ieache_netlist_simulate.argtypes = [vp, u8p, u8p]
     L.ieache_prepare_netlist.argtypes = [vp, vp, C.c_size_t]

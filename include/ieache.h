@@ -533,6 +533,90 @@ int ieache_eval_jobs_device(ieache_ctx* ctx, const ieache_job* jobs, size_t n_jo
  * jobs over: every job's batch goes over the members by ieache_shard_slice's rule, and each member runs ieache_eval_jobs on
  * its slices. */
 
+/* ------------------------------------------------------------------ *
+ * 3d. Word programs: a multi-operator integer expression -- a*b + c*d, *
+ *    (a+b)*c - d, the sum of eight words, max(a+b, c) -- compiled into *
+ *    ONE circuit.  Issued as one call per operator (one ./cloud run    *
+ *    each at dragonfly_cipher_cloud.py:1233), a*b and c*d run one      *
+ *    after the other although their gates are independent, every call  *
+ *    pays its own depth and the intermediates travel through the       *
+ *    caller.  As one program their gates share levels.                 *
+ * ------------------------------------------------------------------ */
+/* A program is a list of instructions; the result of instruction i is REGISTER i, a word of 1 .. 512 samples, LSB first.
+ * Operands a, b, c name earlier registers.  The expression's input samples are the INPUT registers in declaration order; its
+ * output samples are the listed output registers in order.
+ *   wiring only (no gate):
+ *     INPUT   width                        CONST   width, value words const_words[first .. first+count), LSW first
+ *     ZEXT    a to width (>= a's)          SLICE   samples imm0 .. imm0+imm1-1 of a
+ *     SHL     a << imm0, same width        NOT     ~a                       CONCAT  a (low), b (high)
+ *   one gate per bit:
+ *     AND, OR, XOR  a, b of equal widths   ANDBIT  every bit of a ANDed with the 1-sample register b
+ *   word operators ADD (a+b), SUB (a-b), RSUB (b-a), MUL (a*b, double width): the circuit kind of (operator, family) itself --
+ *     family 0 the reference's (IEACHE_CIRC_ADD ...), IEACHE_FAMILY_KOGGE_STONE (_KS), _CARRY_SAVE (MUL_WALLACE), _FULL_ADDER
+ *     (_FA) -- with its width rules (adders 1 .. 256, multipliers 32 / 64 / 128) and refusals (no Kogge-Stone multiplier).
+ *     c = the 32-sample carry word of that kind, or -1 for 32 constant zeros.  A one-instruction program given the caller's carry
+ *     word records the built-in kind's circuit gate for gate (MUL_WALLACE: under IEACHE_PROGRAM_FOLD, which that kind builds with).
+ *   SUM     the sum mod 2^width of count >= 2 operands args[first .. first+count), each a register shifted left by `shift`, zero-
+ *           extended or truncated to width: a carry-save reduction on XOR3 / MAJ3 compressors (one level per stage; stages: the
+ *           least s with w_s >= count, w_0 = 2, w_{s+1} = floor(3 w_s / 2)) down to two rows, then ONE addition in `family`
+ *           (IEACHE_FAMILY_FULL_ADDER or _KOGGE_STONE) -- not count - 1 additions.
+ *   LT, EQ  a < b / a == b, unsigned, equal widths -> 1 sample.   SELECT  a (1 sample) ? b : c, one MUX per bit.
+ * Every recorded gate is bootstrapped, as for netlists and the reference, unless IEACHE_PROGRAM_FOLD asks for the constant-
+ * folded, gate-shared build ("fold_constants" of the built-in kinds); IEACHE_NETLIST_BALANCED keeps its meaning. */
+#define IEACHE_WOP_INPUT 0
+#define IEACHE_WOP_CONST 1
+#define IEACHE_WOP_ZEXT 2
+#define IEACHE_WOP_SLICE 3
+#define IEACHE_WOP_SHL 4
+#define IEACHE_WOP_NOT 5
+#define IEACHE_WOP_CONCAT 6
+#define IEACHE_WOP_AND 7
+#define IEACHE_WOP_OR 8
+#define IEACHE_WOP_XOR 9
+#define IEACHE_WOP_ANDBIT 10
+#define IEACHE_WOP_ADD 11
+#define IEACHE_WOP_SUB 12
+#define IEACHE_WOP_RSUB 13
+#define IEACHE_WOP_MUL 14
+#define IEACHE_WOP_SUM 15
+#define IEACHE_WOP_LT 16
+#define IEACHE_WOP_EQ 17
+#define IEACHE_WOP_SELECT 18
+#define IEACHE_FAMILY_REFERENCE 0
+#define IEACHE_FAMILY_KOGGE_STONE 1
+#define IEACHE_FAMILY_CARRY_SAVE 2
+#define IEACHE_FAMILY_FULL_ADDER 3
+#define IEACHE_PROGRAM_FOLD 2 /* flag, next to IEACHE_NETLIST_BALANCED */
+#define IEACHE_WORD_MAX_WIDTH 512
+typedef struct ieache_word_instr {
+    int32_t op;            /* IEACHE_WOP_* */
+    int32_t family;        /* IEACHE_FAMILY_* of ADD / SUB / RSUB / MUL / SUM, 0 otherwise */
+    int32_t width;         /* INPUT, CONST, ZEXT: the result's width; SUM: the sum's width; 0 otherwise */
+    int32_t a, b, c;       /* register operands; the ones an opcode does not take are ignored */
+    int32_t imm0, imm1;    /* SLICE: first, count; SHL: the shift */
+    int32_t first, count;  /* SUM: into args; CONST: into const_words */
+} ieache_word_instr;
+typedef struct ieache_word_arg {
+    int32_t reg, shift;
+} ieache_word_arg;
+/* -> an ordinary ieache_netlist: every ieache_*netlist* call, ieache_job.netlist and the group forms take it unchanged, and
+ * ieache_netlist_destroy frees it.  NULL with ieache_last_error() on refusal; where an instruction is at fault the message is
+ * "program: instruction I: ...": an operand that names a register not defined there, a width mismatch, a width the kind
+ * table refuses, a word or sum width outside 1 .. IEACHE_WORD_MAX_WIDTH, more than 2^30 wires, side-array ranges that do not lie
+ * in the arrays given and -- without IEACHE_PROGRAM_FOLD -- an instruction that would put one wire twice into a MAJ3 / XOR3
+ * (a SUM of a register with itself at overlapping positions): the noise rule of DESIGN.md section 7 stands.  No outputs,
+ * no inputs and unknown flags are refused too.  Nothing is returned half-built. */
+ieache_netlist* ieache_program_compile(const ieache_word_instr* instrs, size_t n_instrs, const ieache_word_arg* args, size_t n_args,
+                                       const uint32_t* const_words, size_t n_const_words, const int32_t* outputs, size_t n_outputs,
+                                       int flags);
+/* The recorded gate list of ANY compiled netlist -- from ieache_netlist_create too -- in ieache_net_gate form, wire numbering and
+ * reference encoding those of ieache_netlist_create; `outputs` gets the output references.  -> the gate count; gates are
+ * written when cap holds them all and outputs when out_cap holds them all (cap = 0, out_cap = 0: only counts; the output count
+ * is ieache_netlist_info's n_outputs).  For a program built with IEACHE_PROGRAM_FOLD these are the gates AFTER folding.  Fed
+ * back to ieache_netlist_create (same IEACHE_NETLIST_BALANCED) the list gives a netlist with the same ieache_netlist_info:
+ * what lets a caller -- or a test, on another implementation -- walk a program gate by gate. */
+int64_t ieache_netlist_export(const ieache_netlist* nl, ieache_net_gate* gates, size_t cap, int32_t* outputs, size_t out_cap);
+
 /* plaintext simulation of the levelised circuit (host only, no GPU): bits in/out 0/1 */
 int ieache_circuit_simulate(int kind, int bits, const uint8_t* in_bits, uint8_t* out_bits);
 int ieache_circuit_simulate_ex(int kind, int bits, int fold_constants, const uint8_t* in_bits, uint8_t* out_bits);
