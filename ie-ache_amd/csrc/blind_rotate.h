@@ -13,6 +13,7 @@ namespace ieache {
 struct BrScratch {
     dev::DeviceBuffer<char> state;  // sliced blind rotation: accumulators + rotation amounts, br_state_bytes_per_item() per item
     dev::DeviceBuffer<Torus32> audit_ext;
+    dev::DeviceBuffer<Torus32> audit_acc;  // the audit of a multi-output launch: whole accumulators, [kAuditGates][2][N]
     dev::DeviceBuffer<char> audit_state;
 };
 
@@ -61,7 +62,12 @@ struct BlindRotate {
     // every launch; this compares BITS, of a sample.  Clears "fft_audit_inject" when it has used it.
     // One decision per launch, whatever the number of parts.  The window lies inside ONE part (the exact kernel's prologue
     // reads one descriptor); a part shorter than the window is audited whole; which part moves from audit to audit.
-    void audit(BrScratch& scratch, const BrPlan& plan, EvalOptions& opt, hipStream_t stream, const BrPart* parts, size_t n_parts, const Torus32* ext);
+    // acc (may be null): the launch's whole accumulators [sum][2][N] where it left them instead of `ext` -- a multi-output
+    // call, whose factor products read EVERY word of an accumulator, while an extracted sample holds only polynomial a and
+    // coefficient 0 of polynomial b: there the accumulators are what is compared (a wrong word of b elsewhere would be a wrong
+    // output the extraction never shows: tests/test_safety_nets_gpu.py).
+    void audit(BrScratch& scratch, const BrPlan& plan, EvalOptions& opt, hipStream_t stream, const BrPart* parts, size_t n_parts, const Torus32* ext,
+               const Torus32* acc = nullptr);
     static constexpr int64_t kAuditGates = 64;
     struct AuditCounts {
         int64_t seq = 0;  // one-limb (level, chunk) launches so far

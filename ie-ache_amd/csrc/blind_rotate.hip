@@ -184,15 +184,16 @@ __global__ __launch_bounds__(kThreads) void k_blind_rotate_generic(DevKeys K, Wo
     }
 }
 
-// Audit of the one-limb blind rotation: rows of extracted samples it produced against the same gate instances run on the
-// two-limb (provably exact) kernel.  One workgroup per row; any differing word counts the row in *mismatches.
+// Audit of the one-limb blind rotation: rows it produced -- extracted samples (`words` = N + 1 of rows of N + 4) or whole
+// accumulators (2N of 2N) -- against the same gate instances run on the two-limb (provably exact) kernel.  One workgroup per
+// row; any differing word counts the row in *mismatches.
 // inject: test hook -- row 0 is compared as if its first word differed.
-__global__ void k_audit_compare(const Torus32* primary, const Torus32* exact, int32_t N, unsigned* mismatches, int inject) {
+__global__ void k_audit_compare(const Torus32* primary, const Torus32* exact, int32_t words, int32_t stride, unsigned* mismatches, int inject) {
     const size_t g = blockIdx.x;
-    const Torus32* a = primary + g * (size_t)(N + 4);
-    const Torus32* b = exact + g * (size_t)(N + 4);
+    const Torus32* a = primary + g * (size_t)stride;
+    const Torus32* b = exact + g * (size_t)stride;
     int bad = (inject && g == 0 && threadIdx.x == 0) ? 1 : 0;
-    for (int32_t j = threadIdx.x; j <= N; j += blockDim.x) bad |= a[j] != b[j];
+    for (int32_t j = threadIdx.x; j < words; j += blockDim.x) bad |= a[j] != b[j];
     if (__syncthreads_or(bad) && threadIdx.x == 0) atomicAdd(mismatches, 1u);
 }
 
@@ -273,7 +274,8 @@ int BlindRotate::launch(BrScratch& scratch, const BrPlan& plan, const EvalOption
     return w64::launch(p_, K_, w64::Tables{bkf_w64_, bkf1_w64_, tw_w64_, guard_, diag_}, plan, lanes, stream, parts, n_parts, scratch.state, ext, steps, dbg_acc);
 }
 
-void BlindRotate::audit(BrScratch& scratch, const BrPlan& plan, EvalOptions& opt, hipStream_t stream, const BrPart* parts, size_t n_parts, const Torus32* ext) {
+void BlindRotate::audit(BrScratch& scratch, const BrPlan& plan, EvalOptions& opt, hipStream_t stream, const BrPart* parts, size_t n_parts, const Torus32* ext,
+                        const Torus32* acc) {
     if (plan.generic || opt.fft_audit <= 0 || !guard_ || n_parts == 0) return;
     if (!variant_one_limb(plan.variant)) return;  // the launch was exact by construction
     if (++audit_counts.seq % opt.fft_audit != 0) return;
@@ -286,15 +288,22 @@ void BlindRotate::audit(BrScratch& scratch, const BrPlan& plan, EvalOptions& opt
     const int64_t m = std::min<int64_t>(kAuditGates, cnt);
     const int64_t off = cnt > m ? (int64_t)(((uint64_t)audit_counts.seq * 0x9E3779B97F4A7C15ull >> 33) % (uint64_t)(cnt - m + 1)) : 0;
     const size_t ext_row_bytes = (size_t)(K_.N + 4) * 4;
-    if (!scratch.audit_ext) scratch.audit_ext.allocate((size_t)kAuditGates, ext_row_bytes);
+    const size_t acc_row_words = (size_t)2 * (size_t)K_.N;
+    if (acc && !scratch.audit_acc) scratch.audit_acc.allocate((size_t)kAuditGates, acc_row_words * 4);
+    if (!acc && !scratch.audit_ext) scratch.audit_ext.allocate((size_t)kAuditGates, ext_row_bytes);
     if (!scratch.audit_state) scratch.audit_state.allocate((size_t)kAuditGates, br_state_bytes_per_item(p_));
     WorkDesc wa = w;
     wa.item0 = w.item0 + off;
     const BrPart pa{wa, m};
+    // the exact kernel leaves what the launch left: extracted samples, or (acc) its whole accumulators
     w64::launch(p_, K_, w64::Tables{bkf_w64_, bkf1_w64_, tw_w64_, guard_, nullptr}, br_exact_plan(p_), BrLanes{}, stream, &pa, 1, scratch.audit_state,
-                scratch.audit_ext, -1, nullptr);
-    hipLaunchKernelGGL(k_audit_compare, dim3((unsigned)m), dim3(256), 0, stream, ext + (size_t)(row0 + off) * (size_t)(K_.N + 4), scratch.audit_ext, K_.N,
-                       guard_ + 2, opt.fft_audit_inject ? 1 : 0);
+                acc ? nullptr : (Torus32*)scratch.audit_ext, -1, acc ? (Torus32*)scratch.audit_acc : nullptr);
+    if (acc)
+        hipLaunchKernelGGL(k_audit_compare, dim3((unsigned)m), dim3(256), 0, stream, acc + (size_t)(row0 + off) * acc_row_words, scratch.audit_acc,
+                           (int32_t)acc_row_words, (int32_t)acc_row_words, guard_ + 2, opt.fft_audit_inject ? 1 : 0);
+    else
+        hipLaunchKernelGGL(k_audit_compare, dim3((unsigned)m), dim3(256), 0, stream, ext + (size_t)(row0 + off) * (size_t)(K_.N + 4), scratch.audit_ext,
+                           K_.N + 1, K_.N + 4, guard_ + 2, opt.fft_audit_inject ? 1 : 0);
     HIP_CHECK(hipGetLastError());
     opt.fft_audit_inject = 0;
     audit_counts.audits++;

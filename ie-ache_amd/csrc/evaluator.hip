@@ -434,8 +434,10 @@ static BrPlan plan_blind_rotate(const Params& p, const Evaluator::Impl* d, const
     return br_plan(p, d->opt, BrCall{d->exact_once, d->concurrency, d->level_on_two_lanes, steps < 0, &ln == &d->lane[0]}, d->use_w64, cnt);
 }
 
+// By the options as they are now, like begin_call(): a context that has made no call yet names the kernels its first call takes.
 std::string Evaluator::kernel_for_launch(int64_t gates) const {
-    return br_kernel_label(p_, plan_blind_rotate(p_, d_, d_->lane[0], gates < 1 ? 1 : gates));
+    const bool use_w64 = br_supported(p_) && !d_->opt.force_generic;
+    return br_kernel_label(p_, br_plan(p_, d_->opt, BrCall{d_->exact_once, d_->concurrency, d_->level_on_two_lanes, true, true}, use_w64, gates < 1 ? 1 : gates));
 }
 
 // Runs the gate instances the parts describe as `plan` says.  A rotation of roles gets the context's first plan.mix.k
@@ -521,8 +523,8 @@ struct After {
     //   kMuxCombine: k_level_combine turns the piece's rows, one per ROTATION item, into one per GATE in the lane's `comb`; the
     //     level's (ng, nm) come from the descriptor, a flat MUX call (flat_type == kFlatMux) is the level ng = nm = 1;
     //   kMultiExtract (flat calls, planned lanes): a multi-output programmable bootstrap -- the rotation leaves its whole
-    //     accumulators in the lane's scratch, k_mv_extract turns them into the lane's ordinary `ext` rows (what the audit compares)
-    //     and n_factors rows per item: output row = item x n_factors + factor.  Pieces are max(1, chunk / n_factors) items at
+    //     accumulators in the lane's scratch (what the audit compares: the factors read every word of them), k_mv_extract turns
+    //     them into the lane's ordinary `ext` rows and n_factors rows per item: output row = item x n_factors + factor.  Pieces are max(1, chunk / n_factors) items at
     //     most, so the key switch and the rows stay within what `chunk` bounds (n_factors > chunk: one item, n_factors rows).
     enum Stage { kNone, kMuxCombine, kMultiExtract } stage = kNone;
     int32_t n_factors = 1;          // kMultiExtract
@@ -616,7 +618,7 @@ static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t i
         tbr.mark(ln.stream);
         HIP_CHECK(hipGetLastError());
         if (mv) d->mv.extract(ln.stream, ln.mv.acc, cnt, after.n_factors, after.bias, ext, rows);
-        d->br.audit(ln.br, plan, d->opt, ln.stream, &part, 1, ext);
+        d->br.audit(ln.br, plan, d->opt, ln.stream, &part, 1, ext, mv ? (const Torus32*)ln.mv.acc : nullptr);
         if (!to_caller) {
             tks.mark(ln.stream);
             WorkDesc wk = w;

@@ -30,7 +30,7 @@ W_MIN, W_MAX = -(1 << 31), (1 << 31) - 1
 W_BOTH = 0x7FFF8000               # low -2^15, high +2^15
 W_LOW = 0xFFFF8000 - (1 << 32)    # low -2^15, high 0
 
-# p, bk [n][2l][2][N], x [rows][n+1] first, as a caller unpacks them; ksk: all zero.  step: the crafted CMux step (None: no
+# p, bk [n][2l][2][N], x [rows][n+1] first, as a caller unpacks them; ksk: all zero unless the builder was given one.  step: the crafted CMux step (None: no
 # single one); digits: [2l][N] that enter it; neg / pos: per digit row, the two values the digits are drawn from;
 # target: [2][N] accumulator after step 0 (None where step 0 is not a steering step)
 Case = collections.namedtuple("Case", "p bk x ksk name step digits neg pos target")
@@ -134,23 +134,50 @@ def extreme_digits(p):
                  for s in (~ones, ones))
 
 
-def _steered_case(ia, name, l, Bgbit, N, positive, block1, seed=5):
-    """n = 3, 5 rows: step 0 steers, step 1 (amount N) decomposes -2 T with digit signs `positive` [2][l][N] against block1
-    [2l][2][N]; step 2 meets a block of uniform words from the extreme state by amounts 0, 1, N, 2N - 1 and 513."""
-    p = ia.default_params().copy(n=3, N=N, l=l, Bgbit=Bgbit)
+FURTHER_AMOUNTS = (0, 1023, 0, 1025, 2047, 64, 0, 1536)
+
+
+def further_amounts(row, step):
+    """The amount row `row` meets at step `step` >= 3 of a case with n > 3: a fixed mix of 0 (the step is skipped) and non-zero
+    boundary amounts, shifted from row to row so that every step has both."""
+    return FURTHER_AMOUNTS[(3 * row + step) % len(FURTHER_AMOUNTS)]
+
+
+def uniform_ksk(ia, N, n=3, seed=13):
+    """A key-switching key of uniform words for the steered cases' set (n, N): the key switch and the deeper levels of a
+    circuit then do real work against the crafted bootstrapping key."""
+    p = ia.default_params().copy(n=n, N=N)
+    return np_tfhe.uniform32(np.random.default_rng(seed), p.ksk_count)
+
+
+def _steered_case(ia, name, l, Bgbit, N, positive, block1, seed=5, n=3, ksk=None):
+    """5 rows: step 0 steers, step 1 (amount N) decomposes -2 T with digit signs `positive` [2][l][N] against block1
+    [2l][2][N]; step 2 meets a block of uniform words from the extreme state by amounts 0, 1, N, 2N - 1 and 513.  n > 3: the
+    further key blocks are uniform words and the rows meet them by further_amounts(); the first three steps are those of n = 3,
+    array for array.  ksk: None = all zero, or the words of a key for (n, N) (uniform_ksk)."""
+    assert n >= 3
+    p = ia.default_params().copy(n=n, N=N, l=l, Bgbit=Bgbit)
     W = np.stack([field_word(p, positive[c]) for c in range(2)])
     target = target_for_fields(p, W)
-    bk = np.zeros((3, 2 * l, 2, N), dtype=np.int32)
+    bk = np.zeros((n, 2 * l, 2, N), dtype=np.int32)
     bk[0] = steering_block(p, target)
     bk[1] = block1
     bk[2] = np_tfhe.uniform32(np.random.default_rng(seed), (2 * l, 2, N))
-    x = np.zeros((5, 4), dtype=np.int32)
+    if n > 3:  # a generator of their own: bk[2] stays what it is at n = 3
+        bk[3:] = np_tfhe.uniform32(np.random.default_rng([seed, n]), (n - 3, 2 * l, 2, N))
+    x = np.zeros((5, n + 1), dtype=np.int32)
     x[:, 0], x[:, 1] = amount_word(1, N), amount_word(N, N)
     x[:, 2] = [amount_word(a, N) for a in (0, 1, N, 2 * N - 1, 513 % (2 * N))]
+    for s in range(3, n):
+        x[:, s] = [amount_word(further_amounts(r, s), N) for r in range(5)]
     off = decomposition_offset(l, Bgbit)
     digits = np.concatenate([np_digits(_wrap32(W[c] - off), l, Bgbit) for c in range(2)])
     neg, pos = extreme_digits(p)
-    return Case(p, bk, x, np.zeros(p.ksk_count, dtype=np.int32), name, 1, digits, neg * 2, pos * 2, target)
+    if ksk is None:
+        ksk = np.zeros(p.ksk_count, dtype=np.int32)
+    ksk = np.ascontiguousarray(ksk, dtype=np.int32)
+    assert ksk.size == p.ksk_count
+    return Case(p, bk, x, ksk, name, 1, digits, neg * 2, pos * 2, target)
 
 
 WORST_ALIGNMENTS = (  # (label, every digit positive?, key word)
@@ -164,23 +191,31 @@ WORST_ALIGNMENTS = (  # (label, every digit positive?, key word)
 )
 
 
-def worst_alignment(ia, l, Bgbit, N, which):
+# bits_seed of alignment 4 at l = 3 / Bgbit = 7 / N = 1024 under which the unguarded one-limb build (br_variant 35) rounds
+# coefficient 0 of polynomial b wrongly in step 1 -- the one word of b a sample extraction reads (tests/test_safety_nets_gpu.py;
+# under the default 11 its wrong words are b[977], b[1009], b[1019], which only a multi-output bootstrap can show)
+B0_BITS_SEED = 622
+
+
+def worst_alignment(ia, l, Bgbit, N, which, n=3, ksk=None, bits_seed=11):
     """Case 1: every digit of step 1 at one extreme against a constant key block: all 2l x N terms of a coefficient's sum
-    that do not wrap have one sign."""
+    that do not wrap have one sign.  bits_seed: the generator of the random bits of alignment 4 (the sums stay 2^49.56 under any;
+    WHICH words an unguarded one-limb kernel rounds wrongly depends on it)."""
     label, positive, word = WORST_ALIGNMENTS[which]
     block = np.full((2 * l, 2, N), W_MAX if word is None else word, dtype=np.int64)
     if word is None:
-        block -= np.random.default_rng(11).integers(0, 1 << 24, size=block.shape)
+        block -= np.random.default_rng(bits_seed).integers(0, 1 << 24, size=block.shape)
     return _steered_case(ia, "worst alignment %s, l=%d Bgbit=%d N=%d" % (label, l, Bgbit, N), l, Bgbit, N,
-                         np.full((2, l, N), positive), block.astype(np.int32))
+                         np.full((2, l, N), positive), block.astype(np.int32), n=n, ksk=ksk)
 
 
-def extreme_mixed(ia, l, Bgbit, N, seed=7):
+def extreme_mixed(ia, l, Bgbit, N, seed=7, n=3, ksk=None):
     """Case 2: per coefficient and key row, digits from the two extremes and key words from {-2^31, 2^31 - 1, 0x7FFF8000}."""
     rng = np.random.default_rng(seed)
     positive = rng.integers(0, 2, size=(2, l, N)).astype(bool)
     block = rng.choice(np.array([W_MIN, W_MAX, W_BOTH], dtype=np.int64), size=(2 * l, 2, N)).astype(np.int32)
-    return _steered_case(ia, "extreme magnitudes, mixed signs, l=%d Bgbit=%d N=%d" % (l, Bgbit, N), l, Bgbit, N, positive, block)
+    return _steered_case(ia, "extreme magnitudes, mixed signs, l=%d Bgbit=%d N=%d" % (l, Bgbit, N), l, Bgbit, N, positive, block,
+                         n=n, ksk=ksk)
 
 
 INT32_END_WORDS = (-(1 << 31), 0x7FFFFFC0, 0, -64)
@@ -232,6 +267,113 @@ def ks_crafted_keys(n, N, t, bb):
     varied = np.array(KS_WORDS, dtype=np.int64)[rows].astype(np.uint32).view(np.int32)
     keys.append(("a word per (i, j, d) row", np.ascontiguousarray(np.broadcast_to(varied[..., None], shape))))
     return keys
+
+
+# ---- crafted rows as operands of the public entry points ----
+# A gate bootstraps a linear combination of its operand rows (csrc/device_common.h: gate_coeffs, resolve, combined_coef):
+# (0, cst) + k (a + b [+ c]) word for word mod 2^32, bootsMUX the two combinations (0, -1/8) + a + b and (0, -1/8) - a + c.
+# The builders below solve that for operands whose combination IS a crafted row, so that the row reaches the blind rotation
+# through gates, gates3, mux, pbs, a netlist level: every public path, not only the debug hook.
+
+GATE_AND, GATE_XOR, GATE_OR, GATE_NAND, GATE_MUX, GATE_MAJ3, GATE_XOR3 = 0, 1, 2, 3, 4, 32, 33
+GATE_FORM = {GATE_AND: (0xE0000000, 1), GATE_XOR: (0x40000000, 2), GATE_OR: (0x20000000, 1), GATE_NAND: (0x20000000, -1),
+             GATE_MAJ3: (0, 1), GATE_XOR3: (0x80000000, 2)}   # (cst, k) as boot-gates.cpp / DESIGN.md section 7 give them
+MUX_CST = 0xE0000000
+
+
+def _u(rows):
+    return np_tfhe._u32(np.asarray(rows, dtype=np.int32))
+
+
+def _plus_b(rows, word):
+    """rows + (0, word): the constant term enters the b word alone."""
+    out = _u(rows).copy()
+    out[..., -1] = (out[..., -1] + word) & 0xFFFFFFFF
+    return out
+
+
+def gate_combination(gate, a, b, c=None):
+    """The row a gate of type `gate` bootstraps from its operand rows: (0, cst) + k (a + b [+ c]) mod 2^32."""
+    cst, k = GATE_FORM[gate]
+    total = _u(a) + _u(b) + (_u(c) if c is not None else 0)
+    return _wrap32(_plus_b(_wrap32(k * total), cst))
+
+
+def mux_combinations(a, b, c):
+    """The two rows bootsMUX(a, b, c) blind-rotates: (0, -1/8) + a + b and (0, -1/8) - a + c."""
+    return _wrap32(_plus_b(_wrap32(_u(a) + _u(b)), MUX_CST)), _wrap32(_plus_b(_wrap32(_u(c) - _u(a)), MUX_CST))
+
+
+def gate_operands(gate, x):
+    """(a, b) -- (a, b, c) for MAJ3 / XOR3 -- with gate_combination(gate, ...) == x word for word: a = k^-1 (x - (0, cst)), every
+    other operand an all-zero row.  The factor-2 gates (XOR, XOR3) take the halved words; x - (0, cst) has to be even
+    everywhere, which the steered rows are (amount words are multiples of 2^21, their b word is 0, cst is even)."""
+    cst, k = GATE_FORM[gate]
+    d = _plus_b(x, -cst)
+    if abs(k) == 2:
+        assert not (d & 1).any(), "a factor-2 gate needs even words"
+        d = d >> 1
+    a = _wrap32(-d if k < 0 else d)
+    zero = np.zeros_like(a)
+    return (a, zero, zero.copy()) if gate in (GATE_MAJ3, GATE_XOR3) else (a, zero)
+
+
+def mux_operands(x0, x1, a=None):
+    """(a, b, c) with mux_combinations(a, b, c) == (x0, x1): b = x0 - (0, -1/8) - a, c = x1 - (0, -1/8) + a; a: any rows (None: zero)."""
+    a = np.zeros_like(np.asarray(x0, dtype=np.int32)) if a is None else np.asarray(a, dtype=np.int32)
+    return a, _wrap32(_plus_b(x0, -MUX_CST) - _u(a)), _wrap32(_plus_b(x1, -MUX_CST) + _u(a))
+
+
+def pbs_constant_poly(N):
+    """The programmable bootstrap's test polynomial under which a row is bootstrapped as a gate bootstraps it: 2^29 everywhere."""
+    return np.full(N, MU, dtype=np.int32)
+
+
+# The crafted netlist.  Inputs 0 .. 3: the operands that make OR / AND / NAND / XOR bootstrap rows 0 .. 3; inputs 4, 5: b and c
+# of a MUX whose halves are rows 4 and 0; input 6: an all-zero row (every second operand, and the MUX's a).  No netlist
+# constant anywhere.  Level 0 is those five gates (six blind rotations, all on crafted rows); levels 1 and 2 consume every
+# level-0 output through XOR and AND pairs and a MUX, and one output is a level-0 wire as it stands.
+NETLIST_INPUTS = 7
+NETLIST_GATES = (  # (type, a, b, c) in wire numbers; wire 7 + i is gate i
+    (GATE_OR, 0, 6, 0), (GATE_AND, 1, 6, 0), (GATE_NAND, 2, 6, 0), (GATE_XOR, 3, 6, 0), (GATE_MUX, 6, 4, 5),   # level 0: wires 7 .. 11
+    (GATE_XOR, 7, 8, 0), (GATE_AND, 9, 10, 0), (GATE_MUX, 11, 7, 10),                                           # level 1: wires 12 .. 14
+    (GATE_XOR, 12, 13, 0), (GATE_AND, 14, 9, 0))                                                                # level 2: wires 15, 16
+NETLIST_OUTPUTS = (15, 16, 11)
+NETLIST_LEVEL_ITEMS = ((5, 1), (3, 1), (2, 0))   # (gates, of which MUX) per level: 6 + 4 + 2 = 12 blind rotations
+
+
+def crafted_netlist(ia):
+    """-> CompiledNetlist of the gate list above (the caller closes it)."""
+    nl = ia.Netlist(NETLIST_INPUTS)
+    for t, a, b, c in NETLIST_GATES:
+        nl.gate(t, a << 1, b << 1, (c << 1) if t == GATE_MUX else 0)
+    return nl.compile([w << 1 for w in NETLIST_OUTPUTS])
+
+
+def netlist_level0_rows(x):
+    """The crafted rows the six blind rotations of level 0 see, in gate order (both halves of the MUX last)."""
+    return np.stack([x[0], x[1], x[2], x[3], x[4], x[0]])
+
+
+def netlist_inputs(x):
+    """One expression's input rows [7][n+1] from the five crafted rows x."""
+    x = np.asarray(x, dtype=np.int32)
+    ops = [gate_operands(g, x[i:i + 1])[0][0] for i, g in enumerate((GATE_OR, GATE_AND, GATE_NAND, GATE_XOR))]
+    _, mb, mc = mux_operands(x[4:5], x[0:1])
+    return np.stack(ops + [mb[0], mc[0], np.zeros(x.shape[1], dtype=np.int32)])
+
+
+def smallest_mixing_set(ia, cus_list=(256, 304), ratio=200):
+    """(n, mix_s1): the smallest LWE dimension n > 3, and the smallest "mix_s1" there, at which csrc/mix_plan.h
+    (ieache_debug_mix_plan, host only) runs a launch of 5 x cus gate instances as a rotation of roles that leaves the ordinary
+    slice loop at least a step, on every CU count of cus_list; None if there is none below n = 64."""
+    import ctypes
+    out = (ctypes.c_int * 9)()
+    for n in range(4, 64):
+        for s1 in range(1, n):
+            if all(ia.lib().ieache_debug_mix_plan(c, n, 5 * c, s1, ratio, out) == 1 and 0 < out[7] < n for c in cus_list):
+                return n, s1
+    return None
 
 
 # ---- the two references on the same arrays ----

@@ -12,13 +12,22 @@ What could not be built as first stated, and what stands in its place:
   - the steering step has amount 1 (acc += d0 x key block, coefficient by coefficient) rather than amount N with a (1 - X) Q
     key: half the granularity, without which "every digit at -half" cannot be reached at (2, 16).
 What was added: a fifth worst-alignment input with 24 random bits taken off every key word, because on constant keys the
-transform's half-integer outputs all tie to the even exact sum and an unguarded kernel is right by luck."""
+transform's half-integer outputs all tie to the even exact sum and an unguarded kernel is right by luck.
+
+The last section proves the operand builders tests/test_safety_nets_gpu.py feeds the public entry points with: on the oracle
+alone, every builder's gate is the bootstrap of the crafted row it was built for, its blind rotation is the one
+oracle_accumulators gives for that row, and the crafted netlist's level 0 bootstraps exactly the crafted rows."""
+import hashlib
+import types
+
 import numpy as np
 import pytest
 
 import crafted_state as CS
+import lut_reference as LR
 import np_tfhe
 import param_lattice as PL
+from random_netlists import oracle_gate, oracle_netlist
 
 W64_SETS = [(3, 7, 1024), (2, 10, 1024)]
 ALL_SETS = W64_SETS + CS.generic_edge_sets()
@@ -97,6 +106,10 @@ def test_largest_sums_are_the_claimed_ones(ia):
     assert abs(_peak(CS.worst_alignment(ia, 2, 10, 1024, 0)) - 52) < 0.01
     jittered = CS.worst_alignment(ia, 3, 7, 1024, 4)  # 6 x 1024 x 63 x 2^31 = 2^49.56; the random bits take less than 1 % off it
     assert abs(_peak(jittered) - 49.56) < 0.01 and (CS.exact_sums(jittered.digits, jittered.bk[1]) & 1).any()
+    other = CS.worst_alignment(ia, 3, 7, 1024, 4, bits_seed=CS.B0_BITS_SEED)  # other random bits: the same case but for block 1
+    assert abs(_peak(other) - 49.56) < 0.01 and (CS.exact_sums(other.digits, other.bk[1]) & 1).any()
+    assert not np.array_equal(other.bk[1], jittered.bk[1]) and (np.int64(CS.W_MAX) - other.bk[1] < 1 << 24).all() and (other.bk[1] <= CS.W_MAX).all()
+    assert all(np.array_equal(a, b) for a, b in ((other.bk[0], jittered.bk[0]), (other.bk[2], jittered.bk[2]), (other.x, jittered.x), (other.target, jittered.target)))
     for l, Bgbit, N in CS.generic_edge_sets():
         if l == 1:
             assert 2 * N << Bgbit == 1 << 32  # the edge itself
@@ -165,3 +178,141 @@ def test_keyswitch_references_agree_on_crafted_keys(O, n, t, bb):
             assert not ref[r, :n].any() and ref[r, n] == rows[r, N], (label, r)
     varied = keys[-1][1]
     assert len(set(varied[:, :, :, 0].ravel().tolist())) == 8 and (varied == varied[..., :1]).all()
+
+
+# ---- crafted rows as operands of the public entry points ----
+
+def _digest(case):
+    return hashlib.sha256(b"".join(np.ascontiguousarray(v).tobytes() for v in (case.bk, case.x, case.ksk, case.digits, case.target))).hexdigest()[:16]
+
+
+def test_optional_n_and_ksk_leave_existing_callers_their_arrays(ia):
+    """The default call is the n = 3, zero-ksk case it was before the arguments existed (digests taken from the file as it was);
+    n = 6 keeps the first three key blocks and amounts, adds uniform blocks and a mix of zero and non-zero boundary amounts at
+    every further step, and a b word of 0; a uniform ksk goes through unchanged."""
+    assert _digest(CS.worst_alignment(ia, 3, 7, 1024, 4)) == "78bb80ccef4bc3d2"
+    assert _digest(CS.worst_alignment(ia, 2, 10, 1024, 0)) == "1a9db6f2a2ca1e84"
+    for build in (lambda **kw: CS.worst_alignment(ia, 3, 7, 1024, 4, **kw), lambda **kw: CS.extreme_mixed(ia, 3, 7, 1024, **kw)):
+        c3, c3n = build(), build(n=3, ksk=None)
+        assert _digest(c3) == _digest(c3n) and not c3.ksk.any()
+        ksk = CS.uniform_ksk(ia, 1024, 6)
+        c6 = build(n=6, ksk=ksk)
+        assert (c6.p.n, c6.x.shape, c6.bk.shape) == (6, (5, 7), (6, 6, 2, 1024)) and c6.ksk.size == c6.p.ksk_count
+        assert np.array_equal(c6.bk[:3], c3.bk) and np.array_equal(c6.x[:, :3], c3.x[:, :3]) and not c6.x[:, 6].any()
+        assert np.array_equal(c6.digits, c3.digits) and np.array_equal(c6.target, c3.target)
+        assert np.array_equal(c6.ksk, ksk) and len(np.unique(ksk)) > ksk.size // 2
+        for s in range(3, 6):
+            amounts = [CS.further_amounts(r, s) for r in range(5)]
+            assert c6.x[:, s].tolist() == [CS.amount_word(a, 1024) for a in amounts]
+            assert 0 in amounts and any(a in CS.BOUNDARY_AMOUNTS and a for a in amounts), s
+            assert len(np.unique(c6.bk[s])) > c6.bk[s].size // 2, s
+    assert np.array_equal(CS.uniform_ksk(ia, 1024), CS.uniform_ksk(ia, 1024)) and CS.uniform_ksk(ia, 1024).size == c3.p.ksk_count
+
+
+@pytest.fixture(scope="module")
+def crafted(ia, O):
+    """The case the GPU file runs (l = 3 / Bgbit = 7, 24 random bits off every key word, bits_seed B0_BITS_SEED) with a uniform
+    ksk, its oracle key, the oracle's final accumulators of the five rows, their extracted samples and their bootstraps."""
+    case = CS.worst_alignment(ia, 3, 7, 1024, 4, ksk=CS.uniform_ksk(ia, 1024), bits_seed=CS.B0_BITS_SEED)
+    ck = CS.open_oracle(O, case.p, case.bk, case.ksk)
+    acc = CS.oracle_accumulators(ck, case.x, (-1,))[-1]
+    ext = np.stack([ck.sample_extract(a) for a in acc])
+    boot = np.stack([ck.bootstrap(r) for r in case.x])
+    for r in range(5):  # the blind rotation IS the bootstrap's: what the gate proofs below rest on
+        assert np.array_equal(ck.keyswitch(ext[r]), boot[r]) and np.array_equal(ck.bootstrap_woks(case.x[r]), ext[r]), r
+    assert len({bytes(b) for b in boot}) == 5 and boot[:, :3].any()  # the uniform ksk makes every word of the output depend on the rotation
+    return case, ck, acc, ext, boot
+
+
+TWO_INPUT = {CS.GATE_AND: "and", CS.GATE_XOR: "xor", CS.GATE_OR: "or", CS.GATE_NAND: "nand"}
+
+
+@pytest.mark.parametrize("gate", [CS.GATE_OR, CS.GATE_AND, CS.GATE_NAND, CS.GATE_XOR, CS.GATE_MAJ3, CS.GATE_XOR3])
+def test_gate_operands_bootstrap_the_crafted_rows(crafted, gate):
+    from test_three_input_gates_gpu import combination
+    case, ck, acc, ext, boot = crafted
+    ops = CS.gate_operands(gate, case.x)
+    assert all(o.dtype == np.int32 and o.shape == case.x.shape for o in ops) and not any(o.any() for o in ops[1:])
+    assert np.array_equal(CS.gate_combination(gate, *ops), case.x)
+    if gate in TWO_INPUT:
+        for r in range(5):
+            assert np.array_equal(ck.gate(TWO_INPUT[gate], ops[0][r], ops[1][r]), boot[r]), r
+            assert np.array_equal(oracle_gate(ck, gate, ops[0][r], ops[1][r]), boot[r]), r
+    else:  # the oracle has no entry point: the combination as the three-input tests state it, then its bootstrap
+        x = combination(gate, *ops)
+        assert np.array_equal(x, case.x)
+        assert np.array_equal(CS.oracle_accumulators(ck, x, (-1,))[-1], acc)
+    if gate == CS.GATE_XOR:  # halved operands: the doubled words are the row's
+        assert np.array_equal(np_tfhe._wrap32(2 * np_tfhe._u32(ops[0]) + np.array([0] * case.p.n + [0x40000000])), case.x)
+    # a gate type's own form against the libtfhe gates random_netlists states (cst, ka, kb) for
+    assert np.array_equal(CS.gate_combination(CS.GATE_NAND, case.x, case.x[::-1]),
+                          np_tfhe._wrap32(np_tfhe._u32(-case.x.astype(np.int64) - case.x[::-1]) + np.array([0] * case.p.n + [1 << 29])))
+
+
+def test_mux_operands_bootstrap_two_crafted_rows(crafted):
+    case, ck, acc, ext, boot = crafted
+    x0, x1 = case.x, np.roll(case.x, -1, axis=0)
+    sel = np_tfhe.uniform32(np.random.default_rng(21), case.x.shape)
+    for a in (None, sel):
+        a_, b, c = CS.mux_operands(x0, x1, a)
+        h0, h1 = CS.mux_combinations(a_, b, c)
+        assert np.array_equal(h0, x0) and np.array_equal(h1, x1) and (a is None) == (not a_.any())
+        for r in range(5):  # boot-gates.cpp: the two extractions and (0, 1/8) added, one key switch
+            u = np_tfhe._wrap32(ext[r].astype(np.int64) + ext[(r + 1) % 5])
+            u[-1] = np_tfhe._wrap32(int(u[-1]) + CS.MU)
+            assert np.array_equal(ck.mux(a_[r], b[r], c[r]), ck.keyswitch(u)), r
+            assert np.array_equal(oracle_gate(ck, CS.GATE_MUX, a_[r], b[r], c[r]), ck.keyswitch(u)), r
+
+
+def test_pbs_with_the_constant_polynomial_is_the_gate_bootstrap(crafted):
+    case, ck, acc, ext, boot = crafted
+    v = CS.pbs_constant_poly(case.p.N)
+    for r in range(5):
+        assert np.array_equal(LR.pbs_reference(ck, case.x[r], v), boot[r]) and np.array_equal(LR.pbs_reference(ck, case.x[r], v, keyswitch=False), ext[r])
+
+
+def test_crafted_netlist_bootstraps_the_crafted_rows_at_level_0(ia, crafted):
+    case, ck, acc, ext, boot = crafted
+    with CS.crafted_netlist(ia) as cn:
+        info = cn.info()
+        assert (info.n_inputs, info.n_outputs, info.depth, info.bootstraps) == (7, 3, 3, 12)  # nothing folded: 10 gates, 2 of them MUX
+        assert sum(g + m for g, m in CS.NETLIST_LEVEL_ITEMS) == 12 and cn.gates_by_type()[CS.GATE_MUX] == 2
+        assert all(r >= 0 for g in cn.gates for r in g[1:]) and all(o >= 0 for o in cn.outputs)  # no netlist constant
+        rows = CS.netlist_inputs(case.x)
+        assert rows.shape == (7, 4) and not rows[6].any()
+        # what level 0 blind-rotates, gate by gate as resolve() combines the wires
+        lv0 = [CS.gate_combination(t, rows[a], rows[b]) for t, a, b, _ in CS.NETLIST_GATES[:4]] + list(CS.mux_combinations(rows[6], rows[4], rows[5]))
+        assert np.array_equal(np.stack(lv0), CS.netlist_level0_rows(case.x))
+        ref = oracle_netlist(types.SimpleNamespace(ck=ck), cn, rows)
+        # the level-0 output taken directly is the MUX of rows 4 and 0; the other two depend on every level-0 wire
+        u = np_tfhe._wrap32(ext[4].astype(np.int64) + ext[0])
+        u[-1] = np_tfhe._wrap32(int(u[-1]) + CS.MU)
+        assert np.array_equal(ref[2], ck.keyswitch(u))
+        w = [boot[0], boot[1], boot[2], boot[3], ref[2]]                       # wires 7 .. 11
+        l1 = [ck.gate("xor", w[0], w[1]), ck.gate("and", w[2], w[3]), ck.mux(w[4], w[0], w[3])]
+        assert np.array_equal(ref[0], ck.gate("xor", l1[0], l1[1])) and np.array_equal(ref[1], ck.gate("and", l1[2], w[2]))
+        read = {r >> 1 for g in cn.gates[5:] for r in (g[1:] if g[0] == CS.GATE_MUX else g[1:3])}
+        assert set(range(7, 12)) <= read                                        # levels 1 and 2 consume every level-0 output
+
+
+def test_old_set_rows_take_the_same_builders(ia, O):
+    """l = 2 / Bgbit = 10 with a uniform ksk: gate operands and the pbs row reach the first worst-alignment rows there too."""
+    case = CS.worst_alignment(ia, 2, 10, 1024, 0, ksk=CS.uniform_ksk(ia, 1024))
+    ck = CS.open_oracle(O, case.p, case.bk, case.ksk)
+    for gate in (CS.GATE_OR, CS.GATE_XOR):
+        a, b = CS.gate_operands(gate, case.x)
+        assert np.array_equal(CS.gate_combination(gate, a, b), case.x)
+        assert np.array_equal(ck.gate(TWO_INPUT[gate], a[0], b[0]), ck.bootstrap(case.x[0]))
+    assert np.array_equal(LR.pbs_reference(ck, case.x[4], CS.pbs_constant_poly(1024)), ck.bootstrap(case.x[4]))
+
+
+def test_smallest_set_at_which_five_gates_per_cu_mix(ia):
+    """mix_plan.h: one round of three phases is 2 x 2 mix_s1 + mix_s1 steps and has to leave a step, so n = 6 at mix_s1 = 1 -- on
+    256 and on 304 CUs, each alone and together; 5 gates per CU lie inside the 4 .. 7 per CU the rotation of roles takes."""
+    assert CS.smallest_mixing_set(ia) == CS.smallest_mixing_set(ia, (256,)) == CS.smallest_mixing_set(ia, (304,)) == (6, 1)
+    import ctypes
+    out = (ctypes.c_int * 9)()
+    for cus in (256, 304):
+        assert ia.lib().ieache_debug_mix_plan(cus, 5, 5 * cus, 1, 200, out) == 0      # n = 5: no whole round fits
+        assert ia.lib().ieache_debug_mix_plan(cus, 6, 5 * cus, 1, 200, out) == 1 and list(out)[:5] == [3, 2, 1, 2, 1] and out[7] == 5
+        assert ia.lib().ieache_debug_mix_plan(cus, 6, 4 * cus, 1, 200, out) == 0      # 4 per CU: every gate fits on two waves
