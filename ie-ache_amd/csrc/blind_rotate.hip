@@ -103,14 +103,23 @@ __global__ __launch_bounds__(kThreads) void k_blind_rotate_generic(DevKeys K, Wo
             s_barb = bar;
     }
     __syncthreads();
-    // K2: acc = (0, X^{2N-barb} * (mu,...,mu)); a programmable bootstrap starts from its item's test polynomial instead
+    // K2: acc = (0, X^{2N-barb} * (mu,...,mu)); a programmable bootstrap starts from its item's test polynomial instead, or
+    // (a table of TLWE samples) from both halves of its item's sample, rotated alike
     {
         const int32_t a0 = (2 * N - s_barb) & (2 * N - 1);
-        const Torus32* v = test_poly_row(W, W.item0 + item, N);
-        for (int32_t j = threadIdx.x; j < N; j += blockDim.x) {
-            acc[j] = 0;
-            const int32_t idx = (j - a0) & (2 * N - 1);
-            acc[N + j] = v ? rot_coef(v, j, a0, N) : (idx < N ? kMU : -kMU);
+        const bool tlwe = W.flat_type == kFlatRawTlwe;
+        const Torus32* v = test_poly_row(W, W.item0 + item, tlwe ? 2 * N : N);
+        if (v && tlwe) {
+            for (int32_t j = threadIdx.x; j < N; j += blockDim.x) {
+                acc[j] = rot_coef(v, j, a0, N);
+                acc[N + j] = rot_coef(v + N, j, a0, N);
+            }
+        } else {
+            for (int32_t j = threadIdx.x; j < N; j += blockDim.x) {
+                acc[j] = 0;
+                const int32_t idx = (j - a0) & (2 * N - 1);
+                acc[N + j] = v ? rot_coef(v, j, a0, N) : (idx < N ? kMU : -kMU);
+            }
         }
     }
     __syncthreads();

@@ -134,6 +134,35 @@ __global__ __launch_bounds__(128) void k_br_prologue(DevKeys K, WorkDesc W, uint
     }
 }
 
+// The third build: a programmable bootstrap from a table of TLWE samples (W.flat_type == kFlatRawTlwe, rows of 2N words, A
+// then B) -- the accumulator starts from X^{2N-barb} * (A, B), both halves rotated by the same amount with the same rule.  A
+// kernel of its own, so that the two builds above keep their names and their code.
+__global__ __launch_bounds__(128) void k_br_prologue_tlwe(DevKeys K, WorkDesc W, uint16_t* st_bara, int32_t nb, int32_t* st_acc) {
+    __shared__ int32_t s_barb;
+    const int tid = threadIdx.x;
+    const int32_t n = K.n;
+    const int64_t item = (int64_t)blockIdx.x;
+    const GateInst g = resolve(W, W.item0 + item, K.stride);
+    uint16_t* bara = st_bara + (size_t)item * nb;
+    for (int32_t i = tid; i <= n; i += 128) {
+        const int32_t bar = modswitch2N(combined_coef(g, i, n), 11);
+        if (i < n)
+            bara[i] = (uint16_t)bar;
+        else
+            s_barb = bar;
+    }
+    __syncthreads();
+    const int32_t a0 = (2 * kN - s_barb) & (2 * kN - 1);
+    int32_t* acc = st_acc + (size_t)item * 2 * kN;
+    const Torus32* v = test_poly_row(W, W.item0 + item, 2 * kN);
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const int32_t j = 128 * r + tid;
+        acc[j] = rot_coef(v, j, a0, kN);
+        acc[kN + j] = rot_coef(v + kN, j, a0, kN);
+    }
+}
+
 // ---- K3 (+K4): CMux steps [i0, i1) for every gate instance of the launch ----
 // One 128-thread workgroup (two waves) per gate instance.  The step index is the
 // OUTER loop of the evaluator: a chunk of gates is advanced S steps per launch, so
@@ -1381,7 +1410,9 @@ int launch(const Params& p, const DevKeys& K, const Tables& t, const BrPlan& pla
         const WorkDesc& W = parts[q].W;
         uint16_t* bara = st_bara + (size_t)off * nb;
         int32_t* acc = st_acc + (size_t)off * 2 * kN;
-        if (!W.gates && W.tv)  // a programmable bootstrap (BlindRotate::launch has checked the table)
+        if (!W.gates && W.tv && W.flat_type == kFlatRawTlwe)  // a programmable bootstrap from TLWE samples
+            hipLaunchKernelGGL(k_br_prologue_tlwe, dim3((unsigned)parts[q].cnt), dim3(128), 0, stream, K, W, bara, nb, acc);
+        else if (!W.gates && W.tv)  // a programmable bootstrap (BlindRotate::launch has checked the table)
             hipLaunchKernelGGL(k_br_prologue<true>, dim3((unsigned)parts[q].cnt), dim3(128), 0, stream, K, W, bara, nb, acc);
         else
             hipLaunchKernelGGL(k_br_prologue<false>, dim3((unsigned)parts[q].cnt), dim3(128), 0, stream, K, W, bara, nb, acc);

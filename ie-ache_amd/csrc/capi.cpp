@@ -122,13 +122,14 @@ int with_stats(ieache_stats* stats, F&& body) {
 // What can be judged of a programmable bootstrap's arguments without the context, in the order the entry points report it:
 // the message of the first failing check, or null.  The host and the device form share them.
 const char* pbs_args_error(int flags, int32_t n_polys, const int32_t* test_polys) {
-    if (flags & ~IEACHE_PBS_NO_KEYSWITCH) return "pbs: unknown flag";
+    if (flags & ~(IEACHE_PBS_NO_KEYSWITCH | IEACHE_PBS_TLWE_POLYS | IEACHE_PBS_ACCUMULATOR)) return "pbs: unknown flag";
     if (n_polys < 1) return "pbs: n_polys must be at least 1";
     if (!test_polys) return "pbs: null test polynomial table";
     return nullptr;
 }
 const char* pbs_multi_args_error(int flags, int32_t n_polys, const int32_t* test_polys, int32_t n_factors, const int32_t* factors) {
-    if (flags & ~IEACHE_PBS_NO_KEYSWITCH) return "pbs_multi: unknown flag";
+    if (flags & IEACHE_PBS_ACCUMULATOR) return "pbs_multi: IEACHE_PBS_ACCUMULATOR is a flag of ieache_pbs: a multi-output call has no accumulator output";
+    if (flags & ~(IEACHE_PBS_NO_KEYSWITCH | IEACHE_PBS_TLWE_POLYS)) return "pbs_multi: unknown flag";
     if (n_polys < 1) return "pbs_multi: n_polys must be at least 1";
     if (!test_polys) return "pbs_multi: null test polynomial table";
     if (n_factors < 1 || n_factors > IEACHE_PBS_MULTI_MAX_FACTORS) return "pbs_multi: n_factors must be 1 .. 64";
@@ -716,7 +717,16 @@ struct HostCall {
     }
     // key-switched rows carry n + 1 words, extracted samples N + 1
     void download(StagedRows& out, int32_t* h, bool extracted = false) { out.download(h, extracted ? (size_t)p.N + 1 : (size_t)p.n + 1); }
+    // a table of a programmable bootstrap: n_polys polynomials, or (IEACHE_PBS_TLWE_POLYS) n_polys samples of two each, packed
+    StagedRows table(const int32_t* h, int32_t n_polys, int flags) {
+        return polys(kStageTestPolys, h, (size_t)n_polys * ((flags & IEACHE_PBS_TLWE_POLYS) ? 2 : 1));
+    }
 };
+// words per host row of a programmable bootstrap's output
+size_t pbs_out_words(const Params& p, int flags) {
+    if (flags & IEACHE_PBS_ACCUMULATOR) return (size_t)2 * (size_t)p.N;
+    return (flags & IEACHE_PBS_NO_KEYSWITCH) ? (size_t)p.N + 1 : (size_t)p.n + 1;
+}
 }  // namespace
 
 // ---- flat calls.  Device form: validate, check the pointers, run.  Host form: validate, stage the inputs, run the same
@@ -802,12 +812,16 @@ int ieache_pbs(ieache_ctx* ctx, size_t count, const int32_t* x, const int32_t* t
                int32_t* out, int flags, ieache_stats* stats) {
     return guarded([&] {
         if (const int rc = check_pbs(ctx, count, x, test_polys, n_polys, poly_of, out, flags)) return rc;
-        const bool woks = (flags & IEACHE_PBS_NO_KEYSWITCH) != 0;
+        const bool woks = (flags & IEACHE_PBS_NO_KEYSWITCH) != 0, accs = (flags & IEACHE_PBS_ACCUMULATOR) != 0;
         HostCall h(ctx, count);
-        StagedRows dx = h.operand(kStageA, x), dout = h.results(count, woks);
-        StagedRows dtv = h.polys(kStageTestPolys, test_polys, (size_t)n_polys), dof = h.words(kStagePolyOf, poly_of, count);
+        // whole accumulators: packed rows of 2N words, on the device as on the host
+        StagedRows dx = h.operand(kStageA, x), dout = accs ? StagedRows(h.ev, kStageOut, count, (size_t)2 * (size_t)h.p.N) : h.results(count, woks);
+        StagedRows dtv = h.table(test_polys, n_polys, flags), dof = h.words(kStagePolyOf, poly_of, count);
         with_stats(stats, [&](EvalStats* st) { h.ev.pbs_device(count, dx.p, dtv.p, n_polys, dof.p, dout.p, flags, st); });
-        h.download(dout, out, woks);
+        if (accs)
+            dout.download(out, (size_t)2 * (size_t)h.p.N);
+        else
+            h.download(dout, out, woks);
         return 0;
     });
 }
@@ -833,12 +847,31 @@ int ieache_pbs_multi(ieache_ctx* ctx, size_t count, const int32_t* x, const int3
         const bool woks = (flags & IEACHE_PBS_NO_KEYSWITCH) != 0;
         HostCall h(ctx, count);
         StagedRows dx = h.operand(kStageA, x), dout = h.results(count * (size_t)n_factors, woks);
-        StagedRows dtv = h.polys(kStageTestPolys, test_polys, (size_t)n_polys), dof = h.words(kStagePolyOf, poly_of, count);
+        StagedRows dtv = h.table(test_polys, n_polys, flags), dof = h.words(kStagePolyOf, poly_of, count);
         StagedRows dfa = h.polys(kStageFactors, factors, (size_t)n_factors), dbi = h.words(kStageBias, bias, (size_t)n_factors);
         with_stats(stats, [&](EvalStats* st) {
             h.ev.pbs_multi_device(count, dx.p, dtv.p, n_polys, dof.p, dfa.p, n_factors, dbi.p, dout.p, flags, st);
         });
         h.download(dout, out, woks);
+        return 0;
+    });
+}
+
+int ieache_keyswitch_device(ieache_ctx* ctx, size_t count, const int32_t* d_u, int32_t* d_out, ieache_stats* stats) {
+    return guarded([&] {
+        if (!ctx || !d_u || !d_out) return fail(IEACHE_EINVAL, "null argument");
+        require_device_pointers(count, {{d_u, "d_u"}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->keyswitch_device(count, d_u, d_out, st); });
+    });
+}
+
+int ieache_keyswitch(ieache_ctx* ctx, size_t count, const int32_t* u, int32_t* out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_rows({ctx, u, out})) return rc;
+        HostCall h(ctx, count);
+        StagedRows du(h.ev, kStageExtracted, count, (size_t)h.ev.extract_stride(), u, (size_t)h.p.N + 1), dout = h.results(count);
+        with_stats(stats, [&](EvalStats* st) { h.ev.keyswitch_device(count, du.p, dout.p, st); });
+        h.download(dout, out);
         return 0;
     });
 }
@@ -1132,7 +1165,7 @@ int ieache_group_pbs(ieache_group* g, size_t count, const int32_t* x, const int3
             if (const int rc = check_pbs(g->member(0), count, x, test_polys, n_polys, poly_of, out, flags)) return rc;
         // rows in: n + 1 words; rows out: N + 1 without the key switch.  The table goes to every member whole, the indices with the rows.
         const Params& p = g->member(0)->eval->params();
-        const size_t W = (size_t)p.n + 1, V = (flags & IEACHE_PBS_NO_KEYSWITCH) ? (size_t)p.N + 1 : W;
+        const size_t W = (size_t)p.n + 1, V = pbs_out_words(p, flags);  // 2N for whole accumulators
         return group_call(g, count, stats, [&](ieache_ctx* ctx, size_t first, size_t n, ieache_stats* st) {
             return ieache_pbs(ctx, n, at(x, first * W), test_polys, n_polys, at(poly_of, first), at(out, first * V), flags, st);
         });
@@ -1206,6 +1239,28 @@ int ieache_encrypt_bits(const ieache_params* p, const int32_t* lwe_key, const ui
         const Params pp = to_params(*p);
         Rng rng = seed ? Rng(seed) : Rng::secure();
         for (size_t i = 0; i < count; i++) lwe_encrypt_bit(pp, lwe_key, bits[i] & 1, rng, out + i * (size_t)(pp.n + 1));
+        return 0;
+    });
+}
+
+int ieache_tlwe_encrypt(const ieache_params* p, const int32_t* tlwe_key, const int32_t* polys, size_t count, double alpha, uint64_t seed,
+                        int32_t* out) {
+    return guarded([&] {
+        if (!p || !tlwe_key || (count && (!polys || !out))) return fail(IEACHE_EINVAL, "null argument");
+        const Params pp = to_params(*p);
+        if (pp.k != 1 || pp.N < 1) return fail(IEACHE_EINVAL, "tlwe_encrypt: k must be 1 and N positive");
+        Rng rng = seed ? Rng(seed) : Rng::secure();
+        tlwe_encrypt(pp, tlwe_key, polys, count, alpha > 0 ? alpha : pp.tlwe_alpha_min, rng, out);
+        return 0;
+    });
+}
+
+int ieache_tlwe_phase(const ieache_params* p, const int32_t* tlwe_key, const int32_t* samples, size_t count, int32_t* phase) {
+    return guarded([&] {
+        if (!p || !tlwe_key || (count && (!samples || !phase))) return fail(IEACHE_EINVAL, "null argument");
+        const Params pp = to_params(*p);
+        if (pp.k != 1 || pp.N < 1) return fail(IEACHE_EINVAL, "tlwe_phase: k must be 1 and N positive");
+        tlwe_phase(pp, tlwe_key, samples, count, phase);
         return 0;
     });
 }

@@ -30,7 +30,9 @@ struct DevKeys {
 // the arithmetic below is the identity it has always been (only GateInst::out is used there).
 // Programmable bootstrap (flat mode only, tv non-null): the row in flat_a is bootstrapped as it stands (flat_type < 0) and the
 // accumulator starts from X^(2N-barb) * tv[row] instead of the constant polynomial, row = tv_of[item] (null: row 0) clamped
-// into [0, n_tv).  Only the two prologues read these fields.  The descriptor is an argument of every key-switch kernel as
+// into [0, n_tv).  flat_type == kFlatRawTlwe: the same call on a table of TLWE samples under the ring key -- rows of tv are 2N
+// words, A then B, and the accumulator starts from X^(2N-barb) * (A, B) (kFlatRaw: rows of N words, the B half; A = 0).  To
+// resolve() both are the raw row.  Only the prologues read these fields.  The descriptor is an argument of every key-switch kernel as
 // well, and a larger one would move their other arguments -- and with them their code -- so the three fields take the bytes
 // of circuit-mode fields, which a flat launch leaves at zero, and of a padding word: sizeof(WorkDesc) is what it was.
 struct WorkDesc {
@@ -39,7 +41,7 @@ struct WorkDesc {
         struct {
             int32_t g0, ng;
         };
-        const Torus32* tv;  // flat mode: test polynomials, [n_tv][N]
+        const Torus32* tv;  // flat mode: test polynomials, [n_tv][N] (kFlatRawTlwe: [n_tv][2][N])
     };
     int32_t nm;            // circuit mode: MUX gates among the ng (the last ones)
     int32_t n_tv;          // flat mode: rows of tv
@@ -57,12 +59,17 @@ struct WorkDesc {
 };
 static_assert(sizeof(WorkDesc) == 88, "WorkDesc is a kernel argument: its size and field offsets are part of every kernel that takes it");
 
-// the test polynomial of a programmable-bootstrap item, or null for a gate item (whose test polynomial is the constant kMU)
-__device__ __forceinline__ const Torus32* test_poly_row(const WorkDesc& W, int64_t item, int32_t N) {
+// flat_type of a programmable bootstrap: the row in flat_a as it stands; the table holds plain polynomials / TLWE samples
+constexpr int32_t kFlatRaw = -1;
+constexpr int32_t kFlatRawTlwe = -2;
+
+// the test polynomial of a programmable-bootstrap item -- the start of its row of `row_words` words: N for a table of plain
+// polynomials, 2N (A then B) for one of TLWE samples -- or null for a gate item (whose test polynomial is the constant kMU)
+__device__ __forceinline__ const Torus32* test_poly_row(const WorkDesc& W, int64_t item, int32_t row_words) {
     if (W.gates || !W.tv) return nullptr;
     int32_t r = W.tv_of ? W.tv_of[item] : 0;
     r = r < 0 ? 0 : (r >= W.n_tv ? W.n_tv - 1 : r);  // a bad index gives a wrong answer, never a read outside the table
-    return W.tv + (size_t)r * N;
+    return W.tv + (size_t)r * row_words;
 }
 
 // flat_type of the two blind rotations of bootsMUX(a,b,c) (boot-gates.cpp): item 2g is

@@ -34,10 +34,12 @@ enum StageSlot : int {
     kStageB,
     kStageC,
     kStageOut,        // results
-    kStageTestPolys,  // programmable bootstrap: test polynomials [n][N]
+    kStageTestPolys,  // programmable bootstrap: test polynomials [n][N], or TLWE samples [n][2][N]
     kStagePolyOf,     //   ... and the row of that table each item takes
     kStageFactors,    // multi-output programmable bootstrap: factor polynomials [n_factors][N]
     kStageBias,       //   ... and the bias of each factor
+    kStageExtracted,  // key switch alone: extracted samples, rows of extract_stride() words (a slot of its own: the operand
+                      // slots' padding words stay zero)
     kStageSlots
 };
 
@@ -93,7 +95,16 @@ public:
     // gates_device: pieces, level halves, rotation of roles, guard and audit.  kPbsNoKeyswitch: the extracted samples are
     // the result (tfhe_bootstrap_woKS_FFT) -- rows of extract_stride() words, N + 1 of them written, no key-switch launch;
     // d_out must then not overlap an input (its rows are longer than x's).  An index outside [0, n_tv) is clamped on the device.
+    // kPbsTlwePolys: d_tv is [n_tv][2][N], TLWE samples under the ring key (A then B, phase B - A s), and the accumulator starts
+    // from X^(2N-barb) * (A, B): tfhe_blindRotate_FFT on a caller's accumulator.  With A = 0 it is the plain call on B bit for
+    // bit.  Everything after the prologue is the same call; the overlap checks use the 2N-word rows.
+    // kPbsAccumulator (pbs_device only): row i of d_out is the whole rotated accumulator [2][N], 2N packed words; no
+    // extraction and no key switch whether or not kPbsNoKeyswitch is set; the audit compares whole accumulators.  No in-place
+    // form: an output over the rows, the table or the indices throws std::invalid_argument.
+    // The value 2 names no flag and stays refused.
     static constexpr int32_t kPbsNoKeyswitch = 1;
+    static constexpr int32_t kPbsTlwePolys = 4;
+    static constexpr int32_t kPbsAccumulator = 8;
     void pbs_device(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of, Torus32* d_out,
                     int32_t flags, EvalStats* stats);
     // words per device row of extracted samples (N + 1 rounded up to a multiple of 4)
@@ -107,9 +118,16 @@ public:
     // a piece of the call is max(1, chunk / n_factors) items, so that its key switch stays within `chunk` rows.  The
     // sampled audit compares the PLAIN extraction of the audited accumulators, which covers the rotation bit for bit; the
     // integer products have nothing to audit.  d_out must not overlap any input (it is n_factors times as long as x): such
-    // a call, n_factors outside 1 .. kMultiMaxFactors or a null factor table throw std::invalid_argument.
+    // a call, n_factors outside 1 .. kMultiMaxFactors or a null factor table throw std::invalid_argument.  kPbsTlwePolys as for
+    // pbs_device; kPbsAccumulator is refused (the accumulators stay in lane scratch here).
     void pbs_multi_device(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of,
                           const int32_t* d_factors, int32_t n_factors, const Torus32* d_bias, Torus32* d_out, int32_t flags, EvalStats* stats);
+
+    // lweKeySwitch alone: rows d_u [count][extract_stride()] (N + 1 words read, shaped as kPbsNoKeyswitch shapes its output)
+    // -> d_out [count][lwe_stride], in pieces of at most `chunk` rows through the key-switch unit's door with a flat
+    // descriptor over the caller's rows.  No rotation, so nothing for the guard or the audit to see.  stats: bootstraps 0,
+    // one key-switch launch and one chunk per piece, levels 1.  An output over the input throws std::invalid_argument.
+    void keyswitch_device(size_t count, const Torus32* d_u, Torus32* d_out, EvalStats* stats);
 
     // bootsMUX: out[i] = a[i] ? b[i] : c[i] (two blind rotations + one key switch per gate)
     void mux_device(size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,

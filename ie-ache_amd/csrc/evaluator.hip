@@ -526,12 +526,16 @@ struct After {
     //     accumulators in the lane's scratch (what the audit compares: the factors read every word of them), k_mv_extract turns
     //     them into the lane's ordinary `ext` rows and n_factors rows per item: output row = item x n_factors + factor.  Pieces are max(1, chunk / n_factors) items at
     //     most, so the key switch and the rows stay within what `chunk` bounds (n_factors > chunk: one item, n_factors rows).
-    enum Stage { kNone, kMuxCombine, kMultiExtract } stage = kNone;
+    //   kAccumulator (flat calls, planned lanes, rows_out set): the rotation's whole accumulators ARE the result -- each piece
+    //     hands its accumulators, [2][N] per item, to rows_out at the piece's first row (rows of 2N words) once its last
+    //     slice -- after a rotation of roles has joined its subsets -- is behind it; no extraction, no key switch, and the
+    //     audit compares whole accumulators there.
+    enum Stage { kNone, kMuxCombine, kMultiExtract, kAccumulator } stage = kNone;
     int32_t n_factors = 1;          // kMultiExtract
     const Torus32* bias = nullptr;  // kMultiExtract: device, [n_factors], or null
     // Where the rows go: null -- through the key switch to where the descriptor puts them; else (flat calls, not after
     // kMuxCombine) the extracted samples are the result -- rows of N + 4 words written there, at the piece's first row, and no
-    // key switch follows.
+    // key switch follows.  kAccumulator: rows of 2N words instead.
     Torus32* rows_out = nullptr;
 };
 
@@ -578,7 +582,8 @@ static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t i
     //     stream wait for every subset's stream (launch_mixed_phases' join) before the final slices write `ext` there: what is
     //     queued on the lane's stream afterwards -- audit, combine, key switch -- sees the whole piece.
     // The mode, decided here once for every piece:
-    const bool mux = after.stage == After::kMuxCombine, mv = after.stage == After::kMultiExtract;
+    const bool mux = after.stage == After::kMuxCombine, mv = after.stage == After::kMultiExtract, accs = after.stage == After::kAccumulator;
+    if (accs && !after.rows_out) throw std::logic_error("accumulator output without rows to put it in");
     const bool flat_mux = mux && !W.gates, to_caller = after.rows_out != nullptr;
     const int32_t ng = flat_mux ? 1 : W.ng, nm = flat_mux ? 1 : W.nm;  // read only where mux
     const int64_t nf = mv ? after.n_factors : 1;                       // output rows per item
@@ -610,15 +615,17 @@ static void run_items(const Params& p, Evaluator::Impl* d, WorkDesc W, int64_t i
             throw std::logic_error("piece larger than the lane's multi-output scratch");
         const BrPlan plan = plan_blind_rotate(p, d, ln, cnt);  // once: the launch and the audit see the same choice
         // ext: the rotation's extracted samples, one row per item; rows: what the stage after it leaves for the output
-        Torus32* ext = to_caller && !mv ? after.rows_out + (size_t)done * row_words : (Torus32*)ln.ext;
+        Torus32* ext = accs ? nullptr : to_caller && !mv ? after.rows_out + (size_t)done * row_words : (Torus32*)ln.ext;
+        // whole accumulators the rotation leaves: a multi-output piece's in the lane's scratch, or the caller's rows
+        Torus32* acc = mv ? (Torus32*)ln.mv.acc : accs ? after.rows_out + (size_t)done * 2 * (size_t)d->K.N : nullptr;
         Torus32* rows = mux ? (Torus32*)ln.comb : !mv ? ext : to_caller ? after.rows_out + (size_t)(done * nf) * row_words : (Torus32*)ln.mv.rows;
         tbr.mark(ln.stream);
         const BrPart part{w, cnt};
-        const int nbr = launch_blind_rotate(d, ln, plan, &part, 1, mv ? nullptr : ext, -1, mv ? (Torus32*)ln.mv.acc : nullptr);
+        const int nbr = launch_blind_rotate(d, ln, plan, &part, 1, acc ? nullptr : ext, -1, acc);
         tbr.mark(ln.stream);
         HIP_CHECK(hipGetLastError());
         if (mv) d->mv.extract(ln.stream, ln.mv.acc, cnt, after.n_factors, after.bias, ext, rows);
-        d->br.audit(ln.br, plan, d->opt, ln.stream, &part, 1, ext, mv ? (const Torus32*)ln.mv.acc : nullptr);
+        d->br.audit(ln.br, plan, d->opt, ln.stream, &part, 1, ext, acc);
         if (!to_caller) {
             tks.mark(ln.stream);
             WorkDesc wk = w;
@@ -798,9 +805,10 @@ void Evaluator::mux_device(size_t count, const Torus32* d_a, const Torus32* d_b,
 // tfhe_blindRotateAndExtract_FFT from a caller's test polynomial (+ lweKeySwitch): a gate call with the raw row of flat_a as
 // the combination (flat_type < 0 -- resolve(): the row as it stands, no second operand, no constant) and the descriptor
 // carrying the table, so every cut of the launch finds its polynomial.  Without key switch the extracted samples are the result.
+// tlwe: the table holds TLWE samples, rows of 2N words (kFlatRawTlwe: the prologue's third build).
 static Evaluator::FlatCall pbs_call(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of, Torus32* d_out,
-                                    bool woks) {
-    Evaluator::FlatCall call = gate_call(-1, count, d_x, nullptr, nullptr, woks ? nullptr : d_out);
+                                    bool woks, bool tlwe) {
+    Evaluator::FlatCall call = gate_call(tlwe ? kFlatRawTlwe : kFlatRaw, count, d_x, nullptr, nullptr, woks ? nullptr : d_out);
     call.W.tv = d_tv;
     call.W.n_tv = n_tv;
     call.W.tv_of = d_tv_of;
@@ -810,17 +818,21 @@ static Evaluator::FlatCall pbs_call(size_t count, const Torus32* d_x, const Toru
 
 void Evaluator::pbs_device(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of, Torus32* d_out,
                            int32_t flags, EvalStats* stats) {
-    if (flags & ~kPbsNoKeyswitch) throw std::invalid_argument("programmable bootstrap: unknown flag");
+    if (flags & ~(kPbsNoKeyswitch | kPbsTlwePolys | kPbsAccumulator)) throw std::invalid_argument("programmable bootstrap: unknown flag");
     if (n_tv < 1 || !d_tv) throw std::invalid_argument("programmable bootstrap: no test polynomial");
-    const bool woks = (flags & kPbsNoKeyswitch) != 0;
-    const size_t len = count * (size_t)d_->K.stride, out_len = count * (size_t)(woks ? extract_stride() : d_->K.stride);
+    const bool tlwe = (flags & kPbsTlwePolys) != 0, accs = (flags & kPbsAccumulator) != 0;
+    const bool woks = accs || (flags & kPbsNoKeyswitch) != 0;  // the accumulators are the result: nothing to key-switch
+    const size_t len = count * (size_t)d_->K.stride;
+    const size_t out_len = count * (accs ? (size_t)2 * (size_t)p_.N : (size_t)(woks ? extract_stride() : d_->K.stride));
     const bool over_x = overlaps(d_out, out_len, {{d_x, len}});
     // a repeat reads the table and the indices again: an output over either of them is over an input as much as one over x
-    const bool over_table = overlaps(d_out, out_len, {{d_tv, (size_t)n_tv * (size_t)p_.N}, {d_tv_of, count}});
+    const bool over_table = overlaps(d_out, out_len, {{d_tv, (size_t)n_tv * (size_t)p_.N * (tlwe ? 2 : 1)}, {d_tv_of, count}});
     if (over_table || (woks && over_x))
         throw std::invalid_argument(over_table ? "programmable bootstrap: the output overlaps the test polynomials or their indices"
+                                    : accs     ? "programmable bootstrap with accumulator output: the output overlaps the input rows"
                                                : "programmable bootstrap without key switch: the output overlaps the input rows");
-    const FlatCall call = pbs_call(count, d_x, d_tv, n_tv, d_tv_of, d_out, woks);
+    FlatCall call = pbs_call(count, d_x, d_tv, n_tv, d_tv_of, d_out, woks, tlwe);
+    if (accs) call.after.stage = After::kAccumulator;
     run_guarded(!over_x, stats, [&] { flat_device_once(call, stats); });
 }
 
@@ -828,23 +840,58 @@ void Evaluator::pbs_device(size_t count, const Torus32* d_x, const Torus32* d_tv
 void Evaluator::pbs_multi_device(size_t count, const Torus32* d_x, const Torus32* d_tv, int32_t n_tv, const int32_t* d_tv_of,
                                  const int32_t* d_factors, int32_t n_factors, const Torus32* d_bias, Torus32* d_out, int32_t flags,
                                  EvalStats* stats) {
-    if (flags & ~kPbsNoKeyswitch) throw std::invalid_argument("multi-output programmable bootstrap: unknown flag");
+    if (flags & kPbsAccumulator) throw std::invalid_argument("multi-output programmable bootstrap: no accumulator output (IEACHE_PBS_ACCUMULATOR is for pbs)");
+    if (flags & ~(kPbsNoKeyswitch | kPbsTlwePolys)) throw std::invalid_argument("multi-output programmable bootstrap: unknown flag");
     if (n_tv < 1 || !d_tv) throw std::invalid_argument("multi-output programmable bootstrap: no test polynomial");
     if (n_factors < 1 || n_factors > kMultiMaxFactors || !d_factors)
         throw std::invalid_argument("multi-output programmable bootstrap: n_factors must be 1 .. 64 and the factor table non-null");
-    const bool woks = (flags & kPbsNoKeyswitch) != 0;
+    const bool woks = (flags & kPbsNoKeyswitch) != 0, tlwe = (flags & kPbsTlwePolys) != 0;
     const size_t out_len = count * (size_t)n_factors * (size_t)(woks ? extract_stride() : d_->K.stride);
     // no in-place form: the output is n_factors times the input, and a repeat reads every input again
     if (overlaps(d_out, out_len,
-                 {{d_x, count * (size_t)d_->K.stride}, {d_tv, (size_t)n_tv * (size_t)p_.N}, {d_tv_of, count},
+                 {{d_x, count * (size_t)d_->K.stride}, {d_tv, (size_t)n_tv * (size_t)p_.N * (tlwe ? 2 : 1)}, {d_tv_of, count},
                   {d_factors, (size_t)n_factors * (size_t)p_.N}, {d_bias, (size_t)n_factors}}))
         throw std::invalid_argument("multi-output programmable bootstrap: the output overlaps an input (rows, test polynomials, indices, factors or bias)");
-    FlatCall call = pbs_call(count, d_x, d_tv, n_tv, d_tv_of, d_out, woks);
+    FlatCall call = pbs_call(count, d_x, d_tv, n_tv, d_tv_of, d_out, woks, tlwe);
     call.after.stage = After::kMultiExtract;
     call.after.n_factors = n_factors;
     call.after.bias = d_bias;
     call.factors = d_factors;
     run_guarded(true, stats, [&] { flat_device_once(call, stats); });
+}
+
+// lweKeySwitch alone: a flat call without a rotation.  Pieces of at most a chunk on the evaluator's stream, each one launch of
+// the key-switch unit with a flat descriptor whose flat_out is the caller's rows (what the multi-output call hands it);
+// every piece's scratch is reserved before the first launch.  No run_guarded: no one-limb transform runs, nothing can trip.
+void Evaluator::keyswitch_device(size_t count, const Torus32* d_u, Torus32* d_out, EvalStats* stats) {
+    if (overlaps(d_out, count * (size_t)d_->K.stride, {{d_u, count * (size_t)extract_stride()}}))
+        throw std::invalid_argument("key switch: the output overlaps the input rows");
+    begin_call();
+    if (count == 0) return;
+    if (!d_u || !d_out) throw std::invalid_argument("key switch: null rows");
+    Lane& ln = d_->lane[0];
+    const int64_t rows = (int64_t)count, piece = std::min<int64_t>(rows, (int64_t)d_->opt.chunk);
+    d_->ks.reserve(ln.ks, piece, d_->opt, d_->force_generic_ks);
+    Timer tall(stats != nullptr, stream_), tks(stats != nullptr, stream_), tbr(false, stream_);
+    tall.mark();
+    WorkDesc W{};
+    W.flat_out = d_out;
+    W.flat_type = kFlatRaw;
+    for (int64_t done = 0; done < rows; done += piece) {
+        const int64_t cnt = std::min<int64_t>(piece, rows - done);
+        tks.mark();
+        launch_keyswitch(d_, ln, rows_desc(W, done), cnt, d_u + (size_t)done * (size_t)extract_stride(), nullptr);
+        tks.mark();
+        HIP_CHECK(hipGetLastError());
+        if (stats) {
+            stats->keyswitch_launches++;
+            stats->chunks++;
+        }
+    }
+    tall.mark();
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    add_times(stats, tall, tbr, tks);
+    if (stats) stats->levels += 1;
 }
 
 void Evaluator::eval_circuit_device(const Circuit& c, size_t batch, const Torus32* d_in, Torus32* d_out, EvalStats* stats) {

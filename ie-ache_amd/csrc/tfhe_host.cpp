@@ -9,7 +9,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <stdexcept>
+#include <vector>
 #ifdef _OPENMP
 #include <omp.h>
 #endif
@@ -157,6 +159,37 @@ static void add_mul_binary_key(int32_t N, uint32_t* b, const Torus32* a, const i
     }
 }
 
+void tlwe_encrypt_zero(const Params& p, const int32_t* tlwe_key, double alpha, Rng& rng, Torus32* sample) {
+    const int32_t N = p.N, k = p.k;
+    Torus32* a = sample;  // polys a_0..a_{k-1}, then b
+    uint32_t* b = (uint32_t*)(a + (size_t)k * N);
+    for (int32_t j = 0; j < N; j++) b[j] = (uint32_t)rng.gaussian_torus32(alpha);
+    for (int32_t c = 0; c < k; c++) {
+        for (int32_t j = 0; j < N; j++) a[(size_t)c * N + j] = rng.uniform_torus32();
+        add_mul_binary_key(N, b, a + (size_t)c * N, tlwe_key + (size_t)c * N);
+    }
+}
+
+void tlwe_encrypt(const Params& p, const int32_t* tlwe_key, const Torus32* polys, size_t count, double alpha, Rng& rng, Torus32* out) {
+    const size_t N = (size_t)p.N, row = (size_t)(p.k + 1) * N;
+    for (size_t i = 0; i < count; i++) {
+        tlwe_encrypt_zero(p, tlwe_key, alpha, rng, out + i * row);
+        uint32_t* b = (uint32_t*)(out + i * row + (size_t)p.k * N);
+        for (size_t j = 0; j < N; j++) b[j] += (uint32_t)polys[i * N + j];
+    }
+}
+
+void tlwe_phase(const Params& p, const int32_t* tlwe_key, const Torus32* samples, size_t count, Torus32* phase) {
+    const size_t N = (size_t)p.N, row = (size_t)(p.k + 1) * N;
+    std::vector<uint32_t> as(N);
+    for (size_t i = 0; i < count; i++) {
+        std::fill(as.begin(), as.end(), 0u);
+        for (int32_t c = 0; c < p.k; c++) add_mul_binary_key(p.N, as.data(), samples + i * row + (size_t)c * N, tlwe_key + (size_t)c * N);
+        const Torus32* b = samples + i * row + (size_t)p.k * N;
+        for (size_t j = 0; j < N; j++) phase[i * N + j] = (Torus32)((uint32_t)b[j] - as[j]);
+    }
+}
+
 // Threads for the two key-generation loops: OpenMP's default is every hardware thread of the host, but a
 // container is often allowed far less CPU time than that (cgroup cpu.max), and hundreds of threads on a
 // 16-CPU share only contend.
@@ -204,13 +237,7 @@ void keygen(const Params& p, const uint32_t* seed_words, int nseed, SecretKeyDat
         Rng rng = make_rng(1 + (uint64_t)i);
         Torus32* bki = out->cloud.bk.data() + (size_t)i * kpl * (k + 1) * N;
         for (int32_t row = 0; row < kpl; row++) {
-            Torus32* a = bki + (size_t)row * (k + 1) * N;  // polys a_0..a_{k-1}, then b
-            uint32_t* b = (uint32_t*)(a + (size_t)k * N);
-            for (int32_t j = 0; j < N; j++) b[j] = (uint32_t)rng.gaussian_torus32(p.tlwe_alpha_min);
-            for (int32_t c = 0; c < k; c++) {
-                for (int32_t j = 0; j < N; j++) a[(size_t)c * N + j] = rng.uniform_torus32();
-                add_mul_binary_key(N, b, a + (size_t)c * N, out->tlwe_key.data() + (size_t)c * N);
-            }
+            tlwe_encrypt_zero(p, out->tlwe_key.data(), p.tlwe_alpha_min, rng, bki + (size_t)row * (k + 1) * N);
         }
         // + mu * H : gadget on the constant coefficient of poly `bloc` in row bloc*l+q
         for (int32_t bloc = 0; bloc <= k; bloc++)

@@ -49,6 +49,14 @@ private:
 void keygen(const Params& p, const uint32_t* seed_words, int nseed, SecretKeyData* out,
             bool with_cloud = true);
 
+// TLWE samples under the ring key, [k+1][N]: polynomials a_0 .. a_{k-1}, then b; phase b - sum a_c s_c, negacyclic mod 2^32.
+// tlwe_encrypt_zero: a uniform, b = a s + e with e Gaussian of standard deviation alpha -- what key generation makes a row of
+// the bootstrapping key from, in its order of draws.  tlwe_encrypt: the same plus polys[i] on b, `count` samples one after
+// another from one generator.  tlwe_phase: the exact phase of each sample -> [count][N].
+void tlwe_encrypt_zero(const Params& p, const int32_t* tlwe_key, double alpha, Rng& rng, Torus32* sample);
+void tlwe_encrypt(const Params& p, const int32_t* tlwe_key, const Torus32* polys, size_t count, double alpha, Rng& rng, Torus32* out);
+void tlwe_phase(const Params& p, const int32_t* tlwe_key, const Torus32* samples, size_t count, Torus32* phase);
+
 // bootsSymEncrypt / bootsSymDecrypt on raw samples (int32[n+1]).
 void lwe_encrypt_bit(const Params& p, const int32_t* lwe_key, int bit, Rng& rng, Torus32* out);
 Torus32 lwe_phase(const Params& p, const int32_t* lwe_key, const Torus32* sample);

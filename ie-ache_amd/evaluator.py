@@ -21,6 +21,8 @@ GATE_NOR, GATE_XNOR, GATE_ANDNY, GATE_ANDYN, GATE_ORNY, GATE_ORYN = 5, 6, 7, 8, 
 GATE_TYPES = 11
 PBS_MULTI_MAX_FACTORS = 64  # most factor polynomials of one ieache_pbs_multi* call
 PBS_NO_KEYSWITCH = 1  # flag of ieache_pbs*: the extracted samples are the result (tfhe_bootstrap_woKS_FFT)
+PBS_TLWE_POLYS = 4    # ... the table is [n_polys][2][N]: TLWE samples under the ring key (an encrypted table)
+PBS_ACCUMULATOR = 8   # ... of ieache_pbs only: the whole rotated accumulators [2][N] are the result (tfhe_blindRotate_FFT)
 GATE_MAJ3, GATE_XOR3 = 32, 33  # three-input gates of one bootstrap each (codes outside 0 .. GATE_TYPES-1: include/ieache.h)
 CIRC_ADD_FA, CIRC_SUB_FA, CIRC_RSUB_FA, CIRC_MUL_FA = 16, 17, 18, 19  # on the MAJ3 / XOR3 full adder (decrypt-identical)
 GROUP_MAX_DEVICES = 16  # most members of a device group (IEACHE_GROUP_MAX_DEVICES)
@@ -171,6 +173,10 @@ def lib():
     L.ieache_pbs.argtypes = [vp, C.c_size_t, i32p, i32p, C.c_int32, i32p, i32p, C.c_int, sp]
     L.ieache_pbs_multi_device.argtypes = [vp, C.c_size_t, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int, sp]
     L.ieache_pbs_multi.argtypes = [vp, C.c_size_t, i32p, i32p, C.c_int32, i32p, i32p, C.c_int32, i32p, i32p, C.c_int, sp]
+    L.ieache_keyswitch_device.argtypes = [vp, C.c_size_t, vp, vp, sp]
+    L.ieache_keyswitch.argtypes = [vp, C.c_size_t, i32p, i32p, sp]
+    L.ieache_tlwe_encrypt.argtypes = [pp, i32p, i32p, C.c_size_t, C.c_double, C.c_uint64, i32p]
+    L.ieache_tlwe_phase.argtypes = [pp, i32p, i32p, C.c_size_t, i32p]
     L.ieache_lut_factor_poly.argtypes = [pp, C.c_int32, i32p, i32p]
     L.ieache_extract_stride.argtypes = [vp]
     L.ieache_lut_test_poly.argtypes = [pp, C.c_int32, i32p, i32p]
@@ -253,6 +259,23 @@ def check(rc):
 def _i32(a):
     assert a.dtype == np.int32 and a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _pbs_flags(keyswitch=True, tlwe=False, accumulator=False):
+    return (0 if keyswitch else PBS_NO_KEYSWITCH) | (PBS_TLWE_POLYS if tlwe else 0) | (PBS_ACCUMULATOR if accumulator else 0)
+
+
+def _pbs_table(params, test_polys, tlwe):
+    """the table of a programmable bootstrap as the library takes it: [n_polys][N], or for TLWE samples [n_polys][2][N]"""
+    if tlwe:
+        return np.ascontiguousarray(test_polys, dtype=np.int32).reshape(-1, 2, params.N)
+    return np.ascontiguousarray(test_polys, dtype=np.int32).reshape(-1, params.N)
+
+
+def _pbs_out(params, count, keyswitch, accumulator):
+    if accumulator:
+        return np.zeros((count, 2, params.N), dtype=np.int32)
+    return np.zeros((count, (params.n if keyswitch else params.N) + 1), dtype=np.int32)
 
 
 def _stats_ref(stats):
@@ -628,35 +651,51 @@ class Context:
         """int32 per device row of extracted samples (pbs_device with keyswitch=False): N + 1 rounded up to a multiple of 4."""
         return lib().ieache_extract_stride(self.h)
 
-    def pbs(self, x, test_polys, poly_of=None, keyswitch=True, stats=None):
+    def pbs(self, x, test_polys, poly_of=None, keyswitch=True, stats=None, tlwe=False, accumulator=False):
         """Programmable bootstrap on host rows: x [count][n+1] is bootstrapped row by row as it stands from the test polynomial
         test_polys[poly_of[i]] (test_polys [n_polys][N] or one polynomial [N]; poly_of None: row 0 for every row).  With the
         row's mod-switched phase phi in [0, 2N) the result encrypts v[phi] for phi < N and -v[phi - N] otherwise
         (include/ieache.h; tools.lut_test_poly builds v from a table) -> [count][n+1], or with keyswitch=False the
-        extracted samples [count][N+1] under the ring key."""
+        extracted samples [count][N+1] under the ring key.
+        tlwe=True: test_polys is [n_polys][2][N] (or one [2][N]), TLWE samples under the ring key (tools.tlwe_encrypt of a
+        table): the rotation starts from X^(2N-barb) (A, B).  accumulator=True: the whole rotated accumulators
+        [count][2][N] are the result, no extraction and no key switch (tools.tlwe_phase reads them)."""
         x = np.ascontiguousarray(x, dtype=np.int32).reshape(-1, self.params.n + 1)
-        tv = np.ascontiguousarray(test_polys, dtype=np.int32).reshape(-1, self.params.N)
+        tv = _pbs_table(self.params, test_polys, tlwe)
         of = None if poly_of is None else np.ascontiguousarray(poly_of, dtype=np.int32).reshape(-1)
         assert of is None or of.shape[0] == x.shape[0]
-        out = np.zeros((x.shape[0], (self.params.n if keyswitch else self.params.N) + 1), dtype=np.int32)
+        out = _pbs_out(self.params, x.shape[0], keyswitch, accumulator)
         check(lib().ieache_pbs(self.h, x.shape[0], _i32(x), _i32(tv), tv.shape[0], None if of is None else _i32(of), _i32(out),
-                               0 if keyswitch else PBS_NO_KEYSWITCH, _stats_ref(stats)))
+                               _pbs_flags(keyswitch, tlwe, accumulator), _stats_ref(stats)))
         return out
 
-    def pbs_device(self, count, d_x, d_test_polys, n_polys, d_poly_of, d_out, keyswitch=True, stats=None):
-        """Device pointers (ints; d_poly_of may be None / 0): x rows of lwe_stride, test polynomials [n_polys][N] packed, out rows of
-        lwe_stride or, with keyswitch=False, of extract_stride."""
+    def pbs_device(self, count, d_x, d_test_polys, n_polys, d_poly_of, d_out, keyswitch=True, stats=None, tlwe=False, accumulator=False):
+        """Device pointers (ints; d_poly_of may be None / 0): x rows of lwe_stride, test polynomials [n_polys][N] packed
+        (tlwe=True: [n_polys][2][N]), out rows of lwe_stride or, with keyswitch=False, of extract_stride (accumulator=True:
+        packed rows of 2N)."""
         check(lib().ieache_pbs_device(self.h, count, C.c_void_p(d_x), C.c_void_p(d_test_polys), int(n_polys),
-                                      C.c_void_p(d_poly_of or None), C.c_void_p(d_out), 0 if keyswitch else PBS_NO_KEYSWITCH, _stats_ref(stats)))
+                                      C.c_void_p(d_poly_of or None), C.c_void_p(d_out), _pbs_flags(keyswitch, tlwe, accumulator), _stats_ref(stats)))
 
-    def pbs_multi(self, x, test_polys, factors, poly_of=None, bias=None, keyswitch=True, stats=None):
+    def keyswitch(self, u, stats=None):
+        """lweKeySwitch on host rows: extracted samples u [count][N+1] under the ring key (what pbs(..., keyswitch=False) returns,
+        or sums of such rows) -> [count][n+1] under the LWE key."""
+        u = np.ascontiguousarray(u, dtype=np.int32).reshape(-1, self.params.N + 1)
+        out = np.zeros((u.shape[0], self.params.n + 1), dtype=np.int32)
+        check(lib().ieache_keyswitch(self.h, u.shape[0], _i32(u), _i32(out), _stats_ref(stats)))
+        return out
+
+    def keyswitch_device(self, count, d_u, d_out, stats=None):
+        """Device pointers (ints): d_u rows of extract_stride, d_out rows of lwe_stride."""
+        check(lib().ieache_keyswitch_device(self.h, count, C.c_void_p(d_u), C.c_void_p(d_out), _stats_ref(stats)))
+
+    def pbs_multi(self, x, test_polys, factors, poly_of=None, bias=None, keyswitch=True, stats=None, tlwe=False):
         """Multi-output programmable bootstrap on host rows: ONE blind rotation per row of x [count][n+1], as pbs does it, and
         one output per factor polynomial of factors [n_factors][N] (or one [N]): coefficient 0 of factor x accumulator,
         negacyclic and mod 2^32, plus bias[t] (None: 0) on its b term (include/ieache.h; tools.lut_factor_poly builds a factor
         from a table of small integers) -> [count][n_factors][n+1], or with keyswitch=False the extracted samples
-        [count][n_factors][N+1] under the ring key.  The factor 1 gives pbs's own output."""
+        [count][n_factors][N+1] under the ring key.  The factor 1 gives pbs's own output.  tlwe=True: as for pbs."""
         x = np.ascontiguousarray(x, dtype=np.int32).reshape(-1, self.params.n + 1)
-        tv = np.ascontiguousarray(test_polys, dtype=np.int32).reshape(-1, self.params.N)
+        tv = _pbs_table(self.params, test_polys, tlwe)
         fa = np.ascontiguousarray(factors, dtype=np.int32).reshape(-1, self.params.N)
         of = None if poly_of is None else np.ascontiguousarray(poly_of, dtype=np.int32).reshape(-1)
         bi = None if bias is None else np.ascontiguousarray(bias, dtype=np.int32).reshape(-1)
@@ -664,15 +703,16 @@ class Context:
         assert bi is None or bi.shape[0] == fa.shape[0]
         out = np.zeros((x.shape[0], fa.shape[0], (self.params.n if keyswitch else self.params.N) + 1), dtype=np.int32)
         check(lib().ieache_pbs_multi(self.h, x.shape[0], _i32(x), _i32(tv), tv.shape[0], None if of is None else _i32(of), _i32(fa),
-                                     fa.shape[0], None if bi is None else _i32(bi), _i32(out), 0 if keyswitch else PBS_NO_KEYSWITCH, _stats_ref(stats)))
+                                     fa.shape[0], None if bi is None else _i32(bi), _i32(out), _pbs_flags(keyswitch, tlwe), _stats_ref(stats)))
         return out
 
-    def pbs_multi_device(self, count, d_x, d_test_polys, n_polys, d_poly_of, d_factors, n_factors, d_bias, d_out, keyswitch=True, stats=None):
+    def pbs_multi_device(self, count, d_x, d_test_polys, n_polys, d_poly_of, d_factors, n_factors, d_bias, d_out, keyswitch=True, stats=None,
+                         tlwe=False):
         """Device pointers (ints; d_poly_of and d_bias may be None / 0): x rows of lwe_stride, test polynomials [n_polys][N] and
         factors [n_factors][N] packed, out [count * n_factors] rows of lwe_stride or, with keyswitch=False, of extract_stride."""
         check(lib().ieache_pbs_multi_device(self.h, count, C.c_void_p(d_x), C.c_void_p(d_test_polys), int(n_polys),
                                             C.c_void_p(d_poly_of or None), C.c_void_p(d_factors), int(n_factors), C.c_void_p(d_bias or None),
-                                            C.c_void_p(d_out), 0 if keyswitch else PBS_NO_KEYSWITCH, _stats_ref(stats)))
+                                            C.c_void_p(d_out), _pbs_flags(keyswitch, tlwe), _stats_ref(stats)))
 
     def mux(self, a, b, c, stats=None):
         """bootsMUX on host rows: out[i] = a[i] ? b[i] : c[i]."""
@@ -860,23 +900,23 @@ class Group:
         st.deliver()
         return out
 
-    def pbs(self, x, test_polys, poly_of=None, keyswitch=True, stats=None):
+    def pbs(self, x, test_polys, poly_of=None, keyswitch=True, stats=None, tlwe=False, accumulator=False):
         """Context.pbs: the test polynomials go to every member whole, poly_of is cut with the rows."""
         x = np.ascontiguousarray(x, dtype=np.int32).reshape(-1, self.params.n + 1)
-        tv = np.ascontiguousarray(test_polys, dtype=np.int32).reshape(-1, self.params.N)
+        tv = _pbs_table(self.params, test_polys, tlwe)
         of = None if poly_of is None else np.ascontiguousarray(poly_of, dtype=np.int32).reshape(-1)
         assert of is None or of.shape[0] == x.shape[0]
-        out = np.zeros((x.shape[0], (self.params.n if keyswitch else self.params.N) + 1), dtype=np.int32)
+        out = _pbs_out(self.params, x.shape[0], keyswitch, accumulator)
         st = _MemberStats(stats, len(self))
         check(lib().ieache_group_pbs(self.h, x.shape[0], _i32(x), _i32(tv), tv.shape[0], None if of is None else _i32(of), _i32(out),
-                                     0 if keyswitch else PBS_NO_KEYSWITCH, st.ref))
+                                     _pbs_flags(keyswitch, tlwe, accumulator), st.ref))
         st.deliver()
         return out
 
-    def pbs_multi(self, x, test_polys, factors, poly_of=None, bias=None, keyswitch=True, stats=None):
+    def pbs_multi(self, x, test_polys, factors, poly_of=None, bias=None, keyswitch=True, stats=None, tlwe=False):
         """Context.pbs_multi: test polynomials, factors and bias go to every member whole -> [count][n_factors][rows]."""
         x = np.ascontiguousarray(x, dtype=np.int32).reshape(-1, self.params.n + 1)
-        tv = np.ascontiguousarray(test_polys, dtype=np.int32).reshape(-1, self.params.N)
+        tv = _pbs_table(self.params, test_polys, tlwe)
         fa = np.ascontiguousarray(factors, dtype=np.int32).reshape(-1, self.params.N)
         of = None if poly_of is None else np.ascontiguousarray(poly_of, dtype=np.int32).reshape(-1)
         bi = None if bias is None else np.ascontiguousarray(bias, dtype=np.int32).reshape(-1)
@@ -885,6 +925,6 @@ class Group:
         out = np.zeros((x.shape[0], fa.shape[0], (self.params.n if keyswitch else self.params.N) + 1), dtype=np.int32)
         st = _MemberStats(stats, len(self))
         check(lib().ieache_group_pbs_multi(self.h, x.shape[0], _i32(x), _i32(tv), tv.shape[0], None if of is None else _i32(of), _i32(fa),
-                                           fa.shape[0], None if bi is None else _i32(bi), _i32(out), 0 if keyswitch else PBS_NO_KEYSWITCH, st.ref))
+                                           fa.shape[0], None if bi is None else _i32(bi), _i32(out), _pbs_flags(keyswitch, tlwe), st.ref))
         st.deliver()
         return out

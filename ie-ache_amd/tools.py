@@ -79,6 +79,28 @@ def lut_factor_poly(params, table):
     return P
 
 
+def tlwe_encrypt(params, tlwe_key, polys, seed, alpha=None):
+    """TLWE encryptions under the ring key of polys [count][N] (or one [N]) -> [count][2][N], A then B with B = A s + poly + e:
+    an encrypted table for Context.pbs(..., tlwe=True).  alpha None: the parameter set's tlwe_alpha_min; seed as for
+    encrypt_bits (0: kernel entropy)."""
+    polys = np.ascontiguousarray(polys, dtype=np.int32).reshape(-1, params.N)
+    tlwe_key = np.ascontiguousarray(tlwe_key, dtype=np.int32)
+    out = np.zeros((polys.shape[0], 2, params.N), dtype=np.int32)
+    check(lib().ieache_tlwe_encrypt(C.byref(params), _i32(tlwe_key), _i32(polys), polys.shape[0], 0.0 if alpha is None else float(alpha),
+                                    seed, _i32(out)))
+    return out
+
+
+def tlwe_phase(params, tlwe_key, samples):
+    """Exact phase B - A s (negacyclic, mod 2^32) of TLWE samples [count][2][N] (or one [2][N]) -> [count][N]: the table behind
+    an encryption, or the polynomial a returned accumulator (Context.pbs(..., accumulator=True)) holds."""
+    samples = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, 2, params.N)
+    tlwe_key = np.ascontiguousarray(tlwe_key, dtype=np.int32)
+    phase = np.zeros((samples.shape[0], params.N), dtype=np.int32)
+    check(lib().ieache_tlwe_phase(C.byref(params), _i32(tlwe_key), _i32(samples), samples.shape[0], _i32(phase)))
+    return phase
+
+
 def int_to_bits(value, nbits):
     return np.array([(int(value) >> i) & 1 for i in range(nbits)], dtype=np.uint8)
 

@@ -12,7 +12,8 @@
  * Streams: a context launches on its own non-blocking HIP stream
  * (ieache_ctx_stream).  Every entry point that takes DEVICE pointers
  * (ieache_ctx_create_device, ieache_eval_batch_device, ieache_gates_device,
- * ieache_gates3_device, ieache_pbs_device, ieache_pbs_multi_device, ieache_mux_device) reads them on that stream without ordering against the
+ * ieache_gates3_device, ieache_pbs_device, ieache_pbs_multi_device, ieache_keyswitch_device, ieache_mux_device) reads them on that stream
+ * without ordering against the
  * stream that produced them: the caller must either have synchronised the
  * producing stream (torch.cuda.synchronize(), hipStreamSynchronize) or call
  * ieache_ctx_wait_stream(ctx, producer) first.  Outputs are complete when the
@@ -377,17 +378,47 @@ int ieache_gates3(ieache_ctx* ctx, int gate_type, size_t count, const int32_t* a
  * not read on the host; the kernel clamps each into [0, n_polys), so a bad one gives a wrong answer, never a stray read.
  * IEACHE_PBS_NO_KEYSWITCH: the extracted samples (a'[0..N-1], b) under the ring key are the result and no key switch is
  * launched (stats->keyswitch_launches == 0); host rows of N+1, device rows of ieache_extract_stride() int32 (N+1 rounded
- * up to a multiple of 4), and d_out must not overlap d_x.  ieache_debug_keyswitch is its partner.  Otherwise rows as for
+ * up to a multiple of 4), and d_out must not overlap d_x.  ieache_keyswitch* is its partner.  Otherwise rows as for
  * ieache_gates*, and d_out may be d_x (the call then runs on the two-limb kernels from the start).
  * One blind rotation and (unless skipped) one key switch per row; stats->bootstraps == count.  Noise budget of tables:
- * DESIGN.md section 7 (at libtfhe's gate parameters four entries is the recommended ceiling). */
+ * DESIGN.md section 7 (at libtfhe's gate parameters four entries is the recommended ceiling).
+ *
+ * IEACHE_PBS_TLWE_POLYS (ieache_pbs*, ieache_pbs_multi*, and their group forms): the table is ENCRYPTED.  test_polys is
+ * [n_polys][2][N]: TLWE samples under the ring key, A then B, phase B - A s -- the samples key generation makes for the rows
+ * of the bootstrapping key, and what ieache_tlwe_encrypt makes of a table (section 4).  The accumulator starts from
+ * X^(2N-barb) * (A, B), both polynomials rotated by the same amount with the same negacyclic rule: libtfhe's
+ * tfhe_blindRotate_FFT on a caller's accumulator.  Everything after that is the call without the flag: poly_of and its
+ * clamping, IEACHE_PBS_NO_KEYSWITCH, the in-place rule, guard, audit and repeat; the overlap checks use the 2N-word rows.
+ * Convention: with A = 0 the call is the plain call on B, bit for bit.  With an encryption of v the output encrypts what
+ * the plain call on v encrypts, plus the table's own encryption noise, which a monomial rotation does not amplify
+ * (DESIGN.md section 7).
+ * IEACHE_PBS_ACCUMULATOR (ieache_pbs, ieache_pbs_device and ieache_group_pbs; IEACHE_EINVAL on ieache_pbs_multi*): output
+ * row i is the WHOLE rotated accumulator [2][N], A then B -- 2N packed int32 on the host and on the device alike (2N is a
+ * multiple of 4 for every supported N): libtfhe's tfhe_blindRotate_FFT applied to X^(2N-barb) * test_poly.  There is no
+ * extraction and no key switch whether or not IEACHE_PBS_NO_KEYSWITCH is set (stats->keyswitch_launches == 0), and no
+ * in-place form: an output overlapping rows, polynomials or indices is IEACHE_EINVAL.  It combines with
+ * IEACHE_PBS_TLWE_POLYS.  ieache_tlwe_phase (section 4) decrypts such rows; the sample ieache_pbs extracts is
+ * (A[0], -A[N-1], ..., -A[1]; B[0]).
+ * The value 2 names no flag and is refused as every unknown bit is. */
 #define IEACHE_PBS_NO_KEYSWITCH 1
+#define IEACHE_PBS_TLWE_POLYS 4
+#define IEACHE_PBS_ACCUMULATOR 8
 int ieache_pbs_device(ieache_ctx* ctx, size_t count, const int32_t* d_x, const int32_t* d_test_polys, int32_t n_polys,
                       const int32_t* d_poly_of, int32_t* d_out, int flags, ieache_stats* stats);
 int ieache_pbs(ieache_ctx* ctx, size_t count, const int32_t* x, const int32_t* test_polys, int32_t n_polys, const int32_t* poly_of,
                int32_t* out, int flags, ieache_stats* stats);
 /* int32 per device row of extracted samples (ieache_pbs_device with IEACHE_PBS_NO_KEYSWITCH) */
 int ieache_extract_stride(const ieache_ctx* ctx);
+/* The key switch alone: libtfhe's lweKeySwitch over `count` extracted samples under the ring key -> rows under the LWE key.
+ * Rows are shaped exactly as IEACHE_PBS_NO_KEYSWITCH shapes its outputs, so one call's output is the other's input -- after
+ * whatever additions the caller makes in between (bootsMUX adds two extracted samples before ONE key switch): host rows
+ * u [count][N+1] -> out [count][n+1]; device rows d_u [count][ieache_extract_stride()] -> d_out [count][lwe_stride].
+ * The call is cut by "chunk" like every flat call; stats->bootstraps == 0, stats->keyswitch_launches >= 1 (one per piece),
+ * stats->levels == 1.  count == 0 is a no-op.  IEACHE_EINVAL when the output overlaps the input.  The host form goes through
+ * the context's staging rows: a warm call allocates nothing.  ieache_debug_keyswitch gives the same rows.  There is no
+ * group form: a key switch is a small fraction of a bootstrap, and cutting it over devices is out of scope. */
+int ieache_keyswitch_device(ieache_ctx* ctx, size_t count, const int32_t* d_u, int32_t* d_out, ieache_stats* stats);
+int ieache_keyswitch(ieache_ctx* ctx, size_t count, const int32_t* u, int32_t* out, ieache_stats* stats);
 /* Host only: the test polynomial of a lookup table f[0 .. entries-1] of Torus32 values for messages m encoded at phase
  * m / (2 entries) (padding bit clear: phases below 1/2): v[j] = f[((j + N/(2 entries)) * entries) div N] for
  * j < N - N/(2 entries), -f[0] on the last N/(2 entries) coefficients -- every slot centred on its message, and the negacyclic
@@ -655,6 +686,16 @@ int ieache_encrypt_bits(const ieache_params* p, const int32_t* lwe_key, const ui
                         uint64_t seed, int32_t* out);
 int ieache_decrypt_bits(const ieache_params* p, const int32_t* lwe_key, const int32_t* samples, size_t count,
                         uint8_t* bits);
+/* TLWE samples under the ring key (k = 1), [2][N] each, A then B, phase B - A s negacyclic mod 2^32: the form of a row of the
+ * bootstrapping key, of an encrypted table of ieache_pbs (IEACHE_PBS_TLWE_POLYS) and of a returned accumulator
+ * (IEACHE_PBS_ACCUMULATOR).  ieache_tlwe_encrypt draws A uniform and sets B = A s + polys + e, e Gaussian of standard
+ * deviation alpha (alpha <= 0: p->tlwe_alpha_min), with the routine key generation uses for the rows of the bootstrapping
+ * key; seed as for ieache_encrypt_bits (0: ChaCha20 from kernel entropy).  ieache_tlwe_phase is the exact B - A s.
+ * count == 0 is a no-op. */
+int ieache_tlwe_encrypt(const ieache_params* p, const int32_t* tlwe_key, const int32_t* polys /*[count][N]*/, size_t count,
+                        double alpha, uint64_t seed, int32_t* out /*[count][2][N]*/);
+int ieache_tlwe_phase(const ieache_params* p, const int32_t* tlwe_key, const int32_t* samples /*[count][2][N]*/, size_t count,
+                      int32_t* phase /*[count][N]*/);
 /* key files -> raw arrays (sizes from ieache_params; pass NULL to query params only) */
 int ieache_read_secret_key(const char* path, ieache_params* p, int32_t* lwe_key, int32_t* tlwe_key);
 int ieache_read_cloud_key(const char* path, ieache_params* p, int32_t* bk, int32_t* ksk);
