@@ -21,6 +21,7 @@
 #include "group.h"
 #include "group_run.h"
 #include "mix_plan.h"
+#include "pack_plan.h"
 #include "program.h"
 #include "tfhe_host.h"
 
@@ -876,6 +877,57 @@ int ieache_keyswitch(ieache_ctx* ctx, size_t count, const int32_t* u, int32_t* o
     });
 }
 
+// ---- packing key switch: LWE rows -> TLWE samples ----
+namespace {
+// what both forms of the call refuse before anything is staged or launched: 0, or the code after fail()
+int check_pack(const ieache_ctx* ctx, int32_t m, int32_t spread, int32_t shift, const int32_t* rows, const int32_t* out) {
+    if (!ctx || !rows || !out) return fail(IEACHE_EINVAL, "null argument");
+    if (!ctx->eval->has_packing_key()) return fail(IEACHE_EINVAL, "pack: no packing key set");
+    if (const char* e = pack_call_error(ctx->eval->params(), m, spread, shift)) return fail(IEACHE_EINVAL, e);
+    return 0;
+}
+}  // namespace
+
+int ieache_ctx_set_packing_key(ieache_ctx* ctx, int32_t pk_t, int32_t pk_basebit, const int32_t* pk) {
+    return guarded([&] {
+        if (!ctx) return fail(IEACHE_EINVAL, "null context");
+        if (pk)
+            if (const char* e = pack_set_error(ctx->eval->params(), pk_t, pk_basebit)) return fail(IEACHE_EINVAL, e);
+        ctx->eval->set_packing_key(pk_t, pk_basebit, pk);
+        return 0;
+    });
+}
+
+int ieache_debug_pack_plan(const ieache_ctx* ctx, size_t groups, int32_t m, int64_t out[4]) {
+    return guarded([&] {
+        if (!ctx || !out) return fail(IEACHE_EINVAL, "null argument");
+        if (m < 1) return fail(IEACHE_EINVAL, "pack: m must be at least 1");
+        ctx->eval->pack_plan_figures(groups, m, out);
+        return 0;
+    });
+}
+
+int ieache_pack_device(ieache_ctx* ctx, size_t groups, int32_t m, int32_t spread, int32_t shift, const int32_t* d_rows, int32_t* d_out,
+                       ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_pack(ctx, m, spread, shift, d_rows, d_out)) return rc;
+        require_device_pointers(groups, {{d_rows, "d_rows"}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->pack_device(groups, m, spread, shift, d_rows, d_out, st); });
+    });
+}
+
+int ieache_pack(ieache_ctx* ctx, size_t groups, int32_t m, int32_t spread, int32_t shift, const int32_t* rows, int32_t* out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_pack(ctx, m, spread, shift, rows, out)) return rc;
+        HostCall h(ctx, groups * (size_t)m);
+        const size_t sample = (size_t)2 * (size_t)h.p.N;
+        StagedRows drows = h.operand(kStageA, rows), dout(h.ev, kStageOut, groups, sample);
+        with_stats(stats, [&](EvalStats* st) { h.ev.pack_device(groups, m, spread, shift, drows.p, dout.p, st); });
+        dout.download(out, sample);
+        return 0;
+    });
+}
+
 int ieache_lut_factor_poly(const ieache_params* p, int32_t entries, const int32_t* w, int32_t* P) {
     if (!p || !w || !P) return fail(IEACHE_EINVAL, "null argument");
     const int64_t N = p->N;
@@ -1251,6 +1303,30 @@ int ieache_tlwe_encrypt(const ieache_params* p, const int32_t* tlwe_key, const i
         if (pp.k != 1 || pp.N < 1) return fail(IEACHE_EINVAL, "tlwe_encrypt: k must be 1 and N positive");
         Rng rng = seed ? Rng(seed) : Rng::secure();
         tlwe_encrypt(pp, tlwe_key, polys, count, alpha > 0 ? alpha : pp.tlwe_alpha_min, rng, out);
+        return 0;
+    });
+}
+
+int ieache_packing_keygen(const ieache_params* p, const int32_t* lwe_key, const int32_t* tlwe_key, int32_t pk_t, int32_t pk_basebit, double alpha,
+                          uint64_t seed, int32_t* out) {
+    return guarded([&] {
+        if (!p || !lwe_key || !tlwe_key || !out) return fail(IEACHE_EINVAL, "null argument");
+        const Params pp = to_params(*p);
+        if (const char* e = pack_set_error(pp, pk_t, pk_basebit)) return fail(IEACHE_EINVAL, e);
+        Rng rng = seed ? Rng(seed) : Rng::secure();
+        packing_keygen(pp, lwe_key, tlwe_key, pk_t, pk_basebit, alpha > 0 ? alpha : pp.tlwe_alpha_min, rng, out);
+        return 0;
+    });
+}
+
+int ieache_pack_reference(const ieache_params* p, int32_t pk_t, int32_t pk_basebit, const int32_t* pk, size_t groups, int32_t m, int32_t spread,
+                          int32_t shift, const int32_t* rows, int32_t* out) {
+    return guarded([&] {
+        if (!p || !pk || (groups && (!rows || !out))) return fail(IEACHE_EINVAL, "null argument");
+        const Params pp = to_params(*p);
+        if (const char* e = pack_set_error(pp, pk_t, pk_basebit)) return fail(IEACHE_EINVAL, e);
+        if (const char* e = pack_call_error(pp, m, spread, shift)) return fail(IEACHE_EINVAL, e);
+        pack_reference(pp, pk_t, pk_basebit, pk, groups, m, spread, shift, rows, out);
         return 0;
     });
 }

@@ -129,6 +129,19 @@ public:
     // one key-switch launch and one chunk per piece, levels 1.  An output over the input throws std::invalid_argument.
     void keyswitch_device(size_t count, const Torus32* d_u, Torus32* d_out, EvalStats* stats);
 
+    // Packing key switch (pack.h; include/ieache.h section 3e states the definition).  set_packing_key: pk [n][t][2][N] on the
+    // host; a second key replaces the first, null drops it; std::invalid_argument for a decomposition pack_set_error refuses.
+    // pack_device: rows d_rows [groups m][lwe_stride] -> d_out [groups][2][N], in pieces of whole groups (pack_plan.h) on the
+    // evaluator's stream, every piece's scratch reserved before the first.  Exact integer arithmetic: no guard, no audit.  stats:
+    // bootstraps 0, one key-switch launch and one chunk per piece, levels 1.  std::invalid_argument without a key, for a shape
+    // pack_call_error refuses, and for an output over the input.
+    void set_packing_key(int32_t t, int32_t basebit, const Torus32* pk);
+    bool has_packing_key() const;
+    // the plan pack_device would follow for such a call under the options as they are (pack_plan.h): pieces, groups per piece,
+    // K split, K steps.  std::invalid_argument without a key.
+    void pack_plan_figures(size_t groups, int32_t m, int64_t out[4]) const;
+    void pack_device(size_t groups, int32_t m, int32_t spread, int32_t shift, const Torus32* d_rows, Torus32* d_out, EvalStats* stats);
+
     // bootsMUX: out[i] = a[i] ? b[i] : c[i] (two blind rotations + one key switch per gate)
     void mux_device(size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,
                     EvalStats* stats);

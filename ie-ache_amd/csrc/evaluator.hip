@@ -27,6 +27,7 @@
 #include "joint_plan.h"
 #include "keyswitch.h"
 #include "multi_extract.h"
+#include "pack.h"
 #include "scoped_set.h"
 
 #include <algorithm>
@@ -127,6 +128,7 @@ struct Lane {
     BrScratch br;                   // blind rotation: state between slices, the audit's sample
     KsScratch ks;                   // key switch
     MvScratch mv;                   // multi-output programmable bootstrap: a piece's accumulators and its extracted rows
+    std::unique_ptr<PackScratch> pack;  // packing key switch: a piece's R rows and digits; there while a packing key is set
     Event ev_join;                  // the lane's share of a level / of an evaluation is queued
     Event ev_mix;
 };
@@ -156,6 +158,7 @@ struct Evaluator::Impl {
     int64_t guard_reruns = 0;    // calls repeated on the two-limb kernel
     DeviceBuffer<int32_t> ksk;
     KeySwitch ks;  // K5: kernels, key form, LDS grants and the choice among them
+    Pack pack;  // the packing key switch (LWE rows -> TLWE samples): kernels, key form and the cut of a call (pack_plan.h)
     MultiExtract mv;  // between K3 and K5 of a multi-output programmable bootstrap: the factors' lists and the extraction by factor
     DeviceBuffer<Torus32> store;    // circuits: the wire store, the gate and the output table
     DeviceBuffer<DevGate> d_gates;
@@ -227,6 +230,7 @@ void Evaluator::init() {
     d_->br.init(p, K);
     d_->ks.init(p, K);
     d_->mv.init(p);
+    d_->pack.init(p);
 }
 
 Evaluator::~Evaluator() { destroy(); }
@@ -279,6 +283,7 @@ void Evaluator::set_chunk(size_t items) { d_->opt.chunk = items < 1 ? 1 : (int64
 bool Evaluator::option_hook(const OptionRow& r, int64_t& v) {
     if (r.at == &EvalOptions::force_generic) v = v != 0;
     if (r.at == &EvalOptions::ks_mfma_split) return v == 0 || ks_mfma_split_ok(p_, (int32_t)v);  // every split holds whole loop trips
+    if (r.at == &EvalOptions::pack_split) return v == 0 || (d_->pack.has_key() && pack_split_ok(pack_k_steps(p_, d_->pack.t()), (int32_t)v));
     if (r.at == &EvalOptions::br_variant && !variant_known((int32_t)v)) {
         // a retired number (an old A/B script): say so rather than measure another kernel under the wrong label
         fprintf(stderr, "ieache: br_variant %d names no kernel of this build (csrc/br_plan.h); the choice of kernels stays as it is\n", (int)v);
@@ -881,6 +886,58 @@ void Evaluator::keyswitch_device(size_t count, const Torus32* d_u, Torus32* d_ou
         const int64_t cnt = std::min<int64_t>(piece, rows - done);
         tks.mark();
         launch_keyswitch(d_, ln, rows_desc(W, done), cnt, d_u + (size_t)done * (size_t)extract_stride(), nullptr);
+        tks.mark();
+        HIP_CHECK(hipGetLastError());
+        if (stats) {
+            stats->keyswitch_launches++;
+            stats->chunks++;
+        }
+    }
+    tall.mark();
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    add_times(stats, tall, tbr, tks);
+    if (stats) stats->levels += 1;
+}
+
+void Evaluator::set_packing_key(int32_t t, int32_t basebit, const Torus32* pk) {
+    HIP_CHECK(hipSetDevice(device_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    d_->pack.set_key(t, basebit, pk, stream_);
+    if (!pk) d_->lane[0].pack.reset();  // the key is gone (the stream is idle): so is the scratch of its calls
+    d_->opt.pack_split = 0;  // a forced split was accepted for the walk of the key that is gone
+}
+
+bool Evaluator::has_packing_key() const { return d_->pack.has_key(); }
+
+void Evaluator::pack_plan_figures(size_t groups, int32_t m, int64_t out[4]) const {
+    if (!d_->pack.has_key()) throw std::invalid_argument("pack: no packing key set");
+    const PackPlan pl = pack_plan(p_, d_->pack.t(), (int64_t)groups, m, d_->opt.pack_piece_rows, (int32_t)d_->opt.pack_split, d_->opt.cus);
+    out[0] = pl.pieces;
+    out[1] = pl.groups_per_piece;
+    out[2] = pl.ksplit;
+    out[3] = pl.k_steps;
+}
+
+// The packing key switch: pieces of whole groups on the evaluator's stream, each four launches of the unit (digits, init,
+// product, placement).  No run_guarded: integer arithmetic throughout, nothing can trip.
+void Evaluator::pack_device(size_t groups, int32_t m, int32_t spread, int32_t shift, const Torus32* d_rows, Torus32* d_out, EvalStats* stats) {
+    if (!d_->pack.has_key()) throw std::invalid_argument("pack: no packing key set");
+    if (const char* e = pack_call_error(p_, m, spread, shift)) throw std::invalid_argument(e);
+    const size_t row_words = (size_t)m * (size_t)d_->K.stride, out_words = (size_t)2 * (size_t)p_.N;
+    if (overlaps(d_out, groups * out_words, {{d_rows, groups * row_words}})) throw std::invalid_argument("pack: the output overlaps the input rows");
+    begin_call();
+    if (groups == 0) return;
+    if (!d_rows || !d_out) throw std::invalid_argument("pack: null rows");
+    Lane& ln = d_->lane[0];
+    const PackPlan pl = pack_plan(p_, d_->pack.t(), (int64_t)groups, m, d_->opt.pack_piece_rows, (int32_t)d_->opt.pack_split, d_->opt.cus);
+    if (!ln.pack) ln.pack.reset(new PackScratch);
+    d_->pack.reserve(*ln.pack, pl);
+    Timer tall(stats != nullptr, stream_), tks(stats != nullptr, stream_), tbr(false, stream_);
+    tall.mark();
+    for (int64_t i = 0; i < pl.pieces; i++) {
+        const int64_t g0 = pack_piece_first(pl, i), cnt = pack_piece_groups(pl, (int64_t)groups, i);
+        tks.mark();
+        d_->pack.launch(*ln.pack, stream_, pl, cnt, m, spread, shift, d_rows + (size_t)g0 * row_words, d_->K.stride, d_out + (size_t)g0 * out_words);
         tks.mark();
         HIP_CHECK(hipGetLastError());
         if (stats) {

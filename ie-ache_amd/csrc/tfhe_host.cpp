@@ -210,6 +210,62 @@ static int host_threads() {
     return n < 1 ? 1 : (n > 64 ? 64 : n);
 }
 
+void packing_keygen(const Params& p, const int32_t* lwe_key, const int32_t* tlwe_key, int32_t t, int32_t basebit, double alpha, Rng& rng,
+                    Torus32* out) {
+    const size_t N = (size_t)p.N, row = 2 * N;
+    for (int32_t i = 0; i < p.n; i++)
+        for (int32_t j = 0; j < t; j++) {
+            Torus32* s = out + ((size_t)i * t + j) * row;
+            tlwe_encrypt_zero(p, tlwe_key, alpha, rng, s);
+            // the constant polynomial s_i 2^(32 - (j+1) b): coefficient 0 of B
+            ((uint32_t*)s)[N] += (uint32_t)(lwe_key[i] & 1) << (32 - (j + 1) * basebit);
+        }
+}
+
+void pack_reference(const Params& p, int32_t t, int32_t basebit, const Torus32* pk, size_t groups, int32_t m, int32_t spread, int32_t shift,
+                    const Torus32* rows, Torus32* out) {
+    const size_t N = (size_t)p.N, cols = 2 * N, n = (size_t)p.n, nrows = groups * (size_t)m;
+    const uint32_t prec = 1u << (31 - t * basebit), mask = (1u << basebit) - 1u;
+    std::vector<uint32_t> R(nrows * cols, 0u);
+    const int n_threads = host_threads();
+    (void)n_threads;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(n_threads)
+    for (int64_t r = 0; r < (int64_t)nrows; r++) {
+        const Torus32* x = rows + (size_t)r * (n + 1);
+        uint32_t* Rr = R.data() + (size_t)r * cols;
+        Rr[N] = (uint32_t)x[n];  // (0, b X^0)
+        for (size_t i = 0; i < n; i++) {
+            const uint32_t abar = (uint32_t)x[i] + prec;
+            for (int32_t j = 0; j < t; j++) {
+                const uint32_t d = (abar >> (32 - (j + 1) * basebit)) & mask;
+                if (!d) continue;
+                const uint32_t* key = (const uint32_t*)pk + (i * (size_t)t + (size_t)j) * cols;
+                for (size_t c = 0; c < cols; c++) Rr[c] -= d * key[c];
+            }
+        }
+    }
+    uint32_t* o = (uint32_t*)out;
+    std::fill(o, o + groups * cols, 0u);
+    for (size_t g = 0; g < groups; g++)
+        for (int32_t pp = 0; pp < m; pp++)
+            for (int32_t q = 0; q < spread; q++) {
+                const size_t a = ((size_t)pp * (size_t)spread + (size_t)q + (size_t)shift) % cols;  // X^a with a in [0, 2N)
+                for (size_t c = 0; c < 2; c++) {
+                    const uint32_t* src = R.data() + (g * (size_t)m + (size_t)pp) * cols + c * N;
+                    uint32_t* dst = o + g * cols + c * N;
+                    // coefficient j of the row lands on j + a, negated for every wrap past N
+                    if (a < N) {
+                        for (size_t j = 0; j < N - a; j++) dst[j + a] += src[j];
+                        for (size_t j = N - a; j < N; j++) dst[j + a - N] -= src[j];
+                    } else {
+                        const size_t aa = a - N;
+                        for (size_t j = 0; j < N - aa; j++) dst[j + aa] -= src[j];
+                        for (size_t j = N - aa; j < N; j++) dst[j + aa - N] += src[j];
+                    }
+                }
+            }
+}
+
 void keygen(const Params& p, const uint32_t* seed_words, int nseed, SecretKeyData* out,
             bool with_cloud) {
     out->p = p;

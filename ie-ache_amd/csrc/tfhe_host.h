@@ -57,6 +57,15 @@ void tlwe_encrypt_zero(const Params& p, const int32_t* tlwe_key, double alpha, R
 void tlwe_encrypt(const Params& p, const int32_t* tlwe_key, const Torus32* polys, size_t count, double alpha, Rng& rng, Torus32* out);
 void tlwe_phase(const Params& p, const int32_t* tlwe_key, const Torus32* samples, size_t count, Torus32* phase);
 
+// Packing key switch (LWE rows -> TLWE samples; include/ieache.h section 3e states the definition).  packing_keygen:
+// out [n][t][2][N], PK[i][j] = tlwe_encrypt_zero + the constant polynomial lwe_key[i] 2^(32 - (j+1) basebit), rows one after
+// another from one generator.  pack_reference: the definition on raw arrays, rows [groups m][n+1] -> out [groups][2][N]; the
+// caller has checked (t, basebit) and (m, spread, shift) (pack_plan.h).
+void packing_keygen(const Params& p, const int32_t* lwe_key, const int32_t* tlwe_key, int32_t t, int32_t basebit, double alpha, Rng& rng,
+                    Torus32* out);
+void pack_reference(const Params& p, int32_t t, int32_t basebit, const Torus32* pk, size_t groups, int32_t m, int32_t spread, int32_t shift,
+                    const Torus32* rows, Torus32* out);
+
 // bootsSymEncrypt / bootsSymDecrypt on raw samples (int32[n+1]).
 void lwe_encrypt_bit(const Params& p, const int32_t* lwe_key, int bit, Rng& rng, Torus32* out);
 Torus32 lwe_phase(const Params& p, const int32_t* lwe_key, const Torus32* sample);

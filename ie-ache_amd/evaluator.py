@@ -175,6 +175,12 @@ def lib():
     L.ieache_pbs_multi.argtypes = [vp, C.c_size_t, i32p, i32p, C.c_int32, i32p, i32p, C.c_int32, i32p, i32p, C.c_int, sp]
     L.ieache_keyswitch_device.argtypes = [vp, C.c_size_t, vp, vp, sp]
     L.ieache_keyswitch.argtypes = [vp, C.c_size_t, i32p, i32p, sp]
+    L.ieache_ctx_set_packing_key.argtypes = [vp, C.c_int32, C.c_int32, i32p]
+    L.ieache_debug_pack_plan.argtypes = [vp, C.c_size_t, C.c_int32, C.POINTER(C.c_int64)]
+    L.ieache_pack_device.argtypes = [vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, vp, vp, sp]
+    L.ieache_pack.argtypes = [vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, i32p, i32p, sp]
+    L.ieache_packing_keygen.argtypes = [pp, i32p, i32p, C.c_int32, C.c_int32, C.c_double, C.c_uint64, i32p]
+    L.ieache_pack_reference.argtypes = [pp, C.c_int32, C.c_int32, i32p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, i32p, i32p]
     L.ieache_tlwe_encrypt.argtypes = [pp, i32p, i32p, C.c_size_t, C.c_double, C.c_uint64, i32p]
     L.ieache_tlwe_phase.argtypes = [pp, i32p, i32p, C.c_size_t, i32p]
     L.ieache_lut_factor_poly.argtypes = [pp, C.c_int32, i32p, i32p]
@@ -687,6 +693,46 @@ class Context:
     def keyswitch_device(self, count, d_u, d_out, stats=None):
         """Device pointers (ints): d_u rows of extract_stride, d_out rows of lwe_stride."""
         check(lib().ieache_keyswitch_device(self.h, count, C.c_void_p(d_u), C.c_void_p(d_out), _stats_ref(stats)))
+
+    def set_packing_key(self, pk, t=8, basebit=2):
+        """The packing key [n][t][2][N] (tools.packing_keygen) for pack(): replaces an earlier one; pk=None drops it."""
+        if pk is None:
+            check(lib().ieache_ctx_set_packing_key(self.h, 0, 0, None))
+            return
+        pk = np.ascontiguousarray(pk, dtype=np.int32)
+        if int(t) >= 1 and pk.size != self.params.n * int(t) * 2 * self.params.N:  # (t < 1: the library refuses it)
+            raise ValueError("packing key: expected [n][t][2][N] = %d words, got %d" % (self.params.n * t * 2 * self.params.N, pk.size))
+        check(lib().ieache_ctx_set_packing_key(self.h, int(t), int(basebit), _i32(pk)))
+
+    def pack(self, rows, m=None, spread=1, shift=0, stats=None):
+        """Packing key switch on host rows: rows [groups][m][n+1] (or [m][n+1] for one group; or any [..][n+1] with m given)
+        -> TLWE samples [groups][2][N] whose phase holds row p's phase on coefficients p spread + shift .. + spread - 1
+        (include/ieache.h section 3e).  spread=1, shift=0: bit p at coefficient p; tools.lut_pack_layout gives the placement of
+        a table for pbs(..., tlwe=True)."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        if m is None:
+            if rows.ndim < 2:
+                raise ValueError("pack: rows must be [groups][m][n+1] or [m][n+1]")
+            m = rows.shape[-2]
+        m = int(m)
+        rows = rows.reshape(-1, self.params.n + 1)
+        if m >= 1 and rows.shape[0] % m:
+            raise ValueError("pack: %d rows are no whole number of groups of %d" % (rows.shape[0], m))
+        groups = rows.shape[0] // m if m >= 1 else 0
+        out = np.zeros((groups, 2, self.params.N), dtype=np.int32)
+        check(lib().ieache_pack(self.h, groups, m, int(spread), int(shift), _i32(rows), _i32(out), _stats_ref(stats)))
+        return out
+
+    def pack_plan(self, groups, m):
+        """How pack() would cut such a call under the options as they are (csrc/pack_plan.h): dict(pieces, groups_per_piece,
+        k_split, k_steps)."""
+        out = (C.c_int64 * 4)()
+        check(lib().ieache_debug_pack_plan(self.h, groups, int(m), out))
+        return dict(zip(("pieces", "groups_per_piece", "k_split", "k_steps"), (int(v) for v in out)))
+
+    def pack_device(self, groups, m, spread, shift, d_rows, d_out, stats=None):
+        """Device pointers (ints): d_rows [groups m] rows of lwe_stride, d_out [groups][2][N] packed."""
+        check(lib().ieache_pack_device(self.h, groups, int(m), int(spread), int(shift), C.c_void_p(d_rows), C.c_void_p(d_out), _stats_ref(stats)))
 
     def pbs_multi(self, x, test_polys, factors, poly_of=None, bias=None, keyswitch=True, stats=None, tlwe=False):
         """Multi-output programmable bootstrap on host rows: ONE blind rotation per row of x [count][n+1], as pbs does it, and

@@ -101,6 +101,41 @@ def tlwe_phase(params, tlwe_key, samples):
     return phase
 
 
+def packing_keygen(params, lwe_key, tlwe_key, t=8, basebit=2, alpha=None, seed=0):
+    """The packing key [n][t][2][N] for Context.set_packing_key: PK[i][j] a TLWE encryption under the ring key of the constant
+    polynomial lwe_key[i] 2^(32 - (j+1) basebit).  Needs both secret keys.  alpha None: tlwe_alpha_min; seed as for tlwe_encrypt."""
+    lwe_key = np.ascontiguousarray(lwe_key, dtype=np.int32)
+    tlwe_key = np.ascontiguousarray(tlwe_key, dtype=np.int32)
+    out = np.zeros((params.n, max(int(t), 0), 2, params.N), dtype=np.int32)
+    check(lib().ieache_packing_keygen(C.byref(params), _i32(lwe_key), _i32(tlwe_key), int(t), int(basebit), 0.0 if alpha is None else float(alpha),
+                                      seed, _i32(out)))
+    return out
+
+
+def pack_reference(params, pk, rows, m=None, spread=1, shift=0, t=8, basebit=2):
+    """CPU reference of Context.pack on raw arrays (ieache_pack_reference; no GPU, no context): pk [n][t][2][N],
+    rows [groups][m][n+1] (or [m][n+1]; or any [..][n+1] with m given) -> [groups][2][N]."""
+    pk = np.ascontiguousarray(pk, dtype=np.int32)
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    if m is None:
+        m = rows.shape[-2]
+    m = int(m)
+    rows = rows.reshape(-1, params.n + 1)
+    groups = rows.shape[0] // m if m >= 1 else 0
+    out = np.zeros((groups, 2, params.N), dtype=np.int32)
+    check(lib().ieache_pack_reference(C.byref(params), int(t), int(basebit), _i32(pk), groups, m, int(spread), int(shift), _i32(rows), _i32(out)))
+    return out
+
+
+def lut_pack_layout(params, entries):
+    """(spread, shift) with which Context.pack of `entries` encrypted table entries f[e] gives an encryption of exactly
+    lut_test_poly(f): a table for Context.pbs(..., tlwe=True) built from encrypted results.  2 entries must divide N."""
+    entries = int(entries)
+    if entries < 1 or params.N % (2 * entries):
+        raise ValueError("lut_pack_layout: 2 x entries must divide N")
+    return params.N // entries, 2 * params.N - params.N // (2 * entries)
+
+
 def int_to_bits(value, nbits):
     return np.array([(int(value) >> i) & 1 for i in range(nbits)], dtype=np.uint8)
 

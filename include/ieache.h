@@ -664,6 +664,54 @@ int ieache_debug_keyswitch(ieache_ctx* ctx, size_t count, const int32_t* u, int3
 int ieache_debug_mix_plan(int cus, int n, int64_t gates, int s1, int ratio_x100, int out[9]);
 
 /* ------------------------------------------------------------------ *
+ * 3e. Packing key switch: LWE rows into one TLWE sample.  The public   *
+ *    functional key switch of Chillotti, Gama, Georgieva, Izabachene   *
+ *    (Algorithm 2) with f = placement of the phases into coefficients. *
+ * ------------------------------------------------------------------ */
+/* The contract.  The parameter set p comes from the context; the packing decomposition (pk_t, pk_basebit) is written t, b.
+ * The LWE key s is n binary words, the ring key N binary words.
+ *
+ * Packing key PK [n][t][2][N] int32: PK[i][j] is a TLWE sample under the ring key (A then B, phase B - A s_ring, as
+ * everywhere here) of the constant polynomial whose coefficient 0 is s_i 2^(32 - (j+1) b) and whose other coefficients are 0.
+ * There is no `base` dimension, unlike the LWE key-switch key: the digit multiplies the row.
+ *
+ * Digits are lweKeySwitch's: abar = a_i + 2^(31 - t b) (uint32), d_{i,j} = (abar >> (32 - (j+1) b)) & (2^b - 1), j = 0 .. t-1.
+ *
+ * A call takes groups x m LWE rows (m >= 1), an integer spread w >= 1 with m w <= N, and a shift in [0, 2N).  Per row r
+ * with words (a, b_r):
+ *
+ *   R_r   = (0, b_r X^0) - sum_{i<n} sum_{j<t} d_{r,i,j} PK[i][j]              (scalar x [2][N], mod 2^32)
+ *   out_g = sum_{p<m} sum_{q<w} X^((p w + q + shift) mod 2N) R_{g m + p}       (negacyclic: X^N = -1, mod 2^32)
+ *
+ * out is [groups][2][N], A then B.  The phase of out_g is sum_p phi_p X^shift (X^(p w) + ... + X^(p w + w - 1)) plus noise,
+ * phi_p the phase of row p.  spread = 1, shift = 0 puts bit p at coefficient p: output compaction, read back with
+ * ieache_tlwe_phase.  m = entries, spread = N / entries, shift = 2N - N / (2 entries) gives an encryption of exactly
+ * ieache_lut_test_poly(f) from encrypted entries f[e]: a table for ieache_pbs with IEACHE_PBS_TLWE_POLYS built by the cloud.
+ * This is an integer definition: every implementation gives the same words whatever its order of summation (the device
+ * computes the first line as an int8 matrix product, csrc/pack_keyswitch.hip; nothing is rounded, guarded or audited).
+ *
+ * Accepted: b in 1 .. 4, t >= 1, t b < 32, n t (2^b - 1) 128 < 2^31, on any supported parameter set; anything else is
+ * IEACHE_EINVAL with a message, when the key is generated and when it is set.
+ *
+ * ieache_ctx_set_packing_key takes the key from HOST memory and keeps only its device form; a second call replaces the first
+ * key, pk == NULL drops it and the device scratch of its calls (pk_t / pk_basebit are then ignored).  ieache_pack_device: d_rows [groups m][lwe_stride] ->
+ * d_out [groups][2][N], on the context's stream like every device form; ieache_pack: rows [groups m][n+1] through the
+ * context's staging rows (a warm call allocates nothing).  A call is cut into pieces of whole groups of at most
+ * "pack_piece_rows" rows (default and most 4096); "pack_split" forces the product's K split (1, 2, 4 or 8, no more than the
+ * K steps ceil(n t / 32); 0 = by size; a new key resets it).  stats: bootstraps == 0, levels == 1, keyswitch_launches == chunks
+ * == pieces, keyswitch_ms and total_ms filled.  groups == 0 is a no-op.  IEACHE_EINVAL with ieache_last_error text: no
+ * packing key set; m < 1, spread < 1, m spread > N; shift outside [0, 2N); device form: output overlapping input.
+ * ieache_packing_keygen and ieache_pack_reference are in section 4.  There is no group form. */
+int ieache_ctx_set_packing_key(ieache_ctx* ctx, int32_t pk_t, int32_t pk_basebit, const int32_t* pk /*host [n][t][2][N]*/);
+/* How a call of `groups` groups of m rows would be cut under the options as they are (csrc/pack_plan.h decides, nothing else):
+ * out = {pieces, groups per piece, K split of the product, K steps}.  IEACHE_EINVAL without a packing key or for m < 1. */
+int ieache_debug_pack_plan(const ieache_ctx* ctx, size_t groups, int32_t m, int64_t out[4]);
+int ieache_pack_device(ieache_ctx* ctx, size_t groups, int32_t m, int32_t spread, int32_t shift,
+                       const int32_t* d_rows /*[groups*m][lwe_stride]*/, int32_t* d_out /*[groups][2][N]*/, ieache_stats* stats);
+int ieache_pack(ieache_ctx* ctx, size_t groups, int32_t m, int32_t spread, int32_t shift,
+                const int32_t* rows /*[groups*m][n+1]*/, int32_t* out /*[groups][2][N]*/, ieache_stats* stats);
+
+/* ------------------------------------------------------------------ *
  * 4. CPU tools around the path (no GPU): what Keygen/keygen.c:22-51,  *
  *    Client1/alice.c:116-191 and Output/verif.c:41-76 get from        *
  *    libtfhe.  Needed to produce and check ciphertexts without it.    *
@@ -696,6 +744,16 @@ int ieache_tlwe_encrypt(const ieache_params* p, const int32_t* tlwe_key, const i
                         double alpha, uint64_t seed, int32_t* out /*[count][2][N]*/);
 int ieache_tlwe_phase(const ieache_params* p, const int32_t* tlwe_key, const int32_t* samples /*[count][2][N]*/, size_t count,
                       int32_t* phase /*[count][N]*/);
+/* The packing key of section 3e, made by whoever holds both secret keys: out [n][pk_t][2][N], every row through the routine
+ * ieache_tlwe_encrypt and key generation use, rows (i, j) one after another from one generator (existing keys and their
+ * draw order are unchanged).  alpha <= 0: p->tlwe_alpha_min; seed as for ieache_tlwe_encrypt.  IEACHE_EINVAL for a
+ * decomposition section 3e does not accept. */
+int ieache_packing_keygen(const ieache_params* p, const int32_t* lwe_key, const int32_t* tlwe_key, int32_t pk_t, int32_t pk_basebit,
+                          double alpha, uint64_t seed, int32_t* out);
+/* CPU reference of the definition of section 3e on raw arrays, no GPU, no context: rows [groups*m][n+1] -> out [groups][2][N].
+ * The refusals of the decomposition and of (m, spread, shift) are those of section 3e. */
+int ieache_pack_reference(const ieache_params* p, int32_t pk_t, int32_t pk_basebit, const int32_t* pk, size_t groups, int32_t m,
+                          int32_t spread, int32_t shift, const int32_t* rows /*[groups*m][n+1]*/, int32_t* out /*[groups][2][N]*/);
 /* key files -> raw arrays (sizes from ieache_params; pass NULL to query params only) */
 int ieache_read_secret_key(const char* path, ieache_params* p, int32_t* lwe_key, int32_t* tlwe_key);
 int ieache_read_cloud_key(const char* path, ieache_params* p, int32_t* bk, int32_t* ksk);
