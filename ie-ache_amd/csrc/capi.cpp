@@ -12,9 +12,11 @@
 #include <string>
 #include <vector>
 
+#include "br_plan.h"
 #include "circuit.h"
 #include "circuit_cache.h"
 #include "cloud_run.h"
+#include "cmux.h"
 #include "codec.h"
 #include "daemon.h"
 #include "evaluator.h"
@@ -928,6 +930,162 @@ int ieache_pack(ieache_ctx* ctx, size_t groups, int32_t m, int32_t spread, int32
     });
 }
 
+// ---- CMux on caller TGSW samples, the CMux-tree lookup, extraction of a coefficient ----
+struct ieache_tgsw {
+    std::unique_ptr<TgswSet> set;
+};
+
+namespace {
+// what both forms of the two calls refuse before anything is staged or launched: 0, or the code after fail()
+int check_tgsw(const ieache_ctx* ctx, const ieache_tgsw* set) {
+    if (!ctx || !set || !set->set) return fail(IEACHE_EINVAL, "null argument");
+    if (set->set->owner != ctx->eval->cmux_id()) return fail(IEACHE_EINVAL, "the TGSW set was prepared on another context");
+    return 0;
+}
+int check_tree(int32_t depth, int32_t n_tables) {
+    if (depth < 0 || depth > IEACHE_LUT_TREE_MAX_DEPTH) return fail(IEACHE_EINVAL, "lut_tree: depth must lie in 0 .. 12");
+    if (n_tables < 1) return fail(IEACHE_EINVAL, "lut_tree: n_tables must be at least 1");
+    return 0;
+}
+// host indices: every one of idx[0 .. count) inside [0, bound), or the code after fail()
+int check_indices(const int32_t* idx, size_t count, int64_t bound, const char* what) {
+    if (idx)
+        for (size_t i = 0; i < count; i++)
+            if (idx[i] < 0 || idx[i] >= bound)
+                return fail(IEACHE_EINVAL, std::string(what) + "[" + std::to_string(i) + "] = " + std::to_string(idx[i]) + " is outside [0, " + std::to_string(bound) + ")");
+    return 0;
+}
+}  // namespace
+
+ieache_tgsw* ieache_tgsw_prepare_device(ieache_ctx* ctx, const int32_t* d_samples, size_t n) {
+    ieache_tgsw* out = nullptr;
+    guarded([&] {
+        if (!ctx || !d_samples) return fail(IEACHE_EINVAL, "null argument");
+        if (n < 1) return fail(IEACHE_EINVAL, "tgsw_prepare: no samples");
+        require_device_pointer(d_samples, "d_samples");
+        std::unique_ptr<ieache_tgsw> h(new ieache_tgsw);
+        h->set.reset(ctx->eval->tgsw_prepare_device(d_samples, n));
+        out = h.release();
+        return 0;
+    });
+    return out;
+}
+
+ieache_tgsw* ieache_tgsw_prepare(ieache_ctx* ctx, const int32_t* samples, size_t n) {
+    ieache_tgsw* out = nullptr;
+    guarded([&] {
+        if (!ctx || !samples) return fail(IEACHE_EINVAL, "null argument");
+        if (n < 1) return fail(IEACHE_EINVAL, "tgsw_prepare: no samples");
+        const Params& p = ctx->eval->params();
+        if (!br_supported(p)) return fail(IEACHE_EINVAL, "tgsw_prepare: the CMux kernels cover N = 1024, k = 1 with (l, Bgbit) = (3, 7) or (2, 10) only");
+        HIP_CHECK(hipSetDevice(ctx->eval->device()));
+        DevRows words(n, (size_t)p.kpl() * 2 * (size_t)p.N);  // the int32 samples: scratch of this call
+        HIP_CHECK(hipMemcpy(words.p, samples, words.rows * words.stride * 4, hipMemcpyHostToDevice));
+        std::unique_ptr<ieache_tgsw> h(new ieache_tgsw);
+        h->set.reset(ctx->eval->tgsw_prepare_device(words.p, n));
+        out = h.release();
+        return 0;
+    });
+    return out;
+}
+
+void ieache_tgsw_free(ieache_tgsw* set) {
+    if (!set) return;
+    try {
+        if (set->set) (void)hipSetDevice(set->set->device);  // the set owns its memory: the context may be gone already
+        delete set;
+    } catch (...) {
+    }
+}
+
+int ieache_debug_cmux_plan(const ieache_ctx* ctx, size_t count, int32_t depth, int64_t out[4]) {
+    return guarded([&] {
+        if (!ctx || !out) return fail(IEACHE_EINVAL, "null argument");
+        if (depth > IEACHE_LUT_TREE_MAX_DEPTH) return fail(IEACHE_EINVAL, "lut_tree: depth must lie in 0 .. 12");
+        ctx->eval->cmux_plan_figures(count, depth, out);
+        return 0;
+    });
+}
+
+int ieache_cmux_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, const int32_t* d_sel_of, const int32_t* d_d1, const int32_t* d_d0,
+                       int32_t* d_out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_tgsw(ctx, set)) return rc;
+        if (!d_d1 || !d_out) return fail(IEACHE_EINVAL, "null argument");
+        require_device_pointers(count, {{d_sel_of, "d_sel_of", true}, {d_d1, "d_d1"}, {d_d0, "d_d0", true}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->cmux_device(*set->set, count, d_sel_of, d_d1, d_d0, d_out, st); });
+    });
+}
+
+int ieache_cmux(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, const int32_t* sel_of, const int32_t* d1, const int32_t* d0, int32_t* out,
+                ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_tgsw(ctx, set)) return rc;
+        if (!d1 || !out) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_indices(sel_of, count, (int64_t)set->set->n, "cmux: sel_of")) return rc;
+        HostCall h(ctx, count);
+        const size_t sample = (size_t)2 * (size_t)h.p.N;
+        StagedRows dd1(h.ev, kStageTlweA, count, sample, d1, sample), dd0(h.ev, kStageTlweB, count, sample, d0, sample);
+        StagedRows dsel = h.words(kStagePolyOf, sel_of, count), dout(h.ev, kStageOut, count, sample);
+        with_stats(stats, [&](EvalStats* st) { h.ev.cmux_device(*set->set, count, dsel.p, dd1.p, dd0.p, dout.p, st); });
+        dout.download(out, sample);
+        return 0;
+    });
+}
+
+int ieache_lut_tree_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* d_sel_of, const int32_t* d_tables,
+                           int32_t n_tables, const int32_t* d_table_of, int32_t* d_out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_tgsw(ctx, set)) return rc;
+        if (!d_tables || !d_out) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_tree(depth, n_tables)) return rc;
+        require_device_pointers(count, {{d_sel_of, "d_sel_of", true}, {d_tables, "d_tables"}, {d_table_of, "d_table_of", true}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) {
+            ctx->eval->lut_tree_device(*set->set, count, depth, d_sel_of, d_tables, n_tables, d_table_of, d_out, st);
+        });
+    });
+}
+
+int ieache_lut_tree(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* sel_of, const int32_t* tables,
+                    int32_t n_tables, const int32_t* table_of, int32_t* out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_tgsw(ctx, set)) return rc;
+        if (!tables || !out) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_tree(depth, n_tables)) return rc;
+        if (const int rc = check_indices(sel_of, count * (size_t)depth, (int64_t)set->set->n, "lut_tree: sel_of")) return rc;
+        if (const int rc = check_indices(table_of, count, n_tables, "lut_tree: table_of")) return rc;
+        HostCall h(ctx, count);
+        const size_t sample = (size_t)2 * (size_t)h.p.N;
+        StagedRows dt(h.ev, kStageTestPolys, (size_t)n_tables << depth, sample, tables, sample);
+        StagedRows dsel = h.words(kStagePolyOf, sel_of, count * (size_t)depth), dof = h.words(kStageBias, table_of, count);
+        StagedRows dout(h.ev, kStageOut, count, sample);
+        with_stats(stats, [&](EvalStats* st) { h.ev.lut_tree_device(*set->set, count, depth, dsel.p, dt.p, n_tables, dof.p, dout.p, st); });
+        dout.download(out, sample);
+        return 0;
+    });
+}
+
+int ieache_tlwe_extract_device(ieache_ctx* ctx, size_t count, const int32_t* d_tlwe, const int32_t* d_coef_of, int32_t* d_u, ieache_stats* stats) {
+    return guarded([&] {
+        if (!ctx || !d_tlwe || !d_u) return fail(IEACHE_EINVAL, "null argument");
+        require_device_pointers(count, {{d_tlwe, "d_tlwe"}, {d_coef_of, "d_coef_of", true}, {d_u, "d_u"}});
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->tlwe_extract_device(count, d_tlwe, d_coef_of, d_u, st); });
+    });
+}
+
+int ieache_tlwe_extract(ieache_ctx* ctx, size_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_rows({ctx, tlwe, u})) return rc;
+        if (const int rc = check_indices(coef_of, count, ctx->eval->params().N, "tlwe_extract: coef_of")) return rc;
+        HostCall h(ctx, count);
+        const size_t sample = (size_t)2 * (size_t)h.p.N;
+        StagedRows dt(h.ev, kStageTlweA, count, sample, tlwe, sample), dof = h.words(kStagePolyOf, coef_of, count), du = h.results(count, true);
+        with_stats(stats, [&](EvalStats* st) { h.ev.tlwe_extract_device(count, dt.p, dof.p, du.p, st); });
+        h.download(du, u, true);
+        return 0;
+    });
+}
+
 int ieache_lut_factor_poly(const ieache_params* p, int32_t entries, const int32_t* w, int32_t* P) {
     if (!p || !w || !P) return fail(IEACHE_EINVAL, "null argument");
     const int64_t N = p->N;
@@ -1327,6 +1485,57 @@ int ieache_pack_reference(const ieache_params* p, int32_t pk_t, int32_t pk_baseb
         if (const char* e = pack_set_error(pp, pk_t, pk_basebit)) return fail(IEACHE_EINVAL, e);
         if (const char* e = pack_call_error(pp, m, spread, shift)) return fail(IEACHE_EINVAL, e);
         pack_reference(pp, pk_t, pk_basebit, pk, groups, m, spread, shift, rows, out);
+        return 0;
+    });
+}
+
+int ieache_tgsw_encrypt(const ieache_params* p, const int32_t* tlwe_key, const int32_t* mu, size_t count, double alpha, uint64_t seed, int32_t* out) {
+    return guarded([&] {
+        if (!p || !tlwe_key || (count && (!mu || !out))) return fail(IEACHE_EINVAL, "null argument");
+        const Params pp = to_params(*p);
+        if (!pp.supported()) return fail(IEACHE_EINVAL, "tgsw_encrypt: unsupported TFHE parameter set");
+        Rng rng = seed ? Rng(seed) : Rng::secure();
+        const size_t sample = (size_t)pp.kpl() * 2 * (size_t)pp.N;
+        for (size_t i = 0; i < count; i++) tgsw_encrypt_sample(pp, tlwe_key, mu[i], alpha > 0 ? alpha : pp.tlwe_alpha_min, rng, out + i * sample);
+        return 0;
+    });
+}
+
+int ieache_cmux_reference(const ieache_params* p, const int32_t* set, size_t n, size_t count, const int32_t* sel_of, const int32_t* d1,
+                          const int32_t* d0, int32_t* out) {
+    return guarded([&] {
+        if (!p || !set || (count && (!d1 || !out))) return fail(IEACHE_EINVAL, "null argument");
+        const Params pp = to_params(*p);
+        if (!pp.supported()) return fail(IEACHE_EINVAL, "cmux_reference: unsupported TFHE parameter set");
+        if (n < 1) return fail(IEACHE_EINVAL, "cmux_reference: no samples");
+        if (const int rc = check_indices(sel_of, count, (int64_t)n, "cmux: sel_of")) return rc;
+        cmux_reference(pp, set, n, count, sel_of, d1, d0, out);
+        return 0;
+    });
+}
+
+int ieache_lut_tree_reference(const ieache_params* p, const int32_t* set, size_t n, size_t count, int32_t depth, const int32_t* sel_of,
+                              const int32_t* tables, int32_t n_tables, const int32_t* table_of, int32_t* out) {
+    return guarded([&] {
+        if (!p || !set || (count && (!tables || !out))) return fail(IEACHE_EINVAL, "null argument");
+        const Params pp = to_params(*p);
+        if (!pp.supported()) return fail(IEACHE_EINVAL, "lut_tree_reference: unsupported TFHE parameter set");
+        if (n < 1) return fail(IEACHE_EINVAL, "lut_tree_reference: no samples");
+        if (const int rc = check_tree(depth, n_tables)) return rc;
+        if (const int rc = check_indices(sel_of, count * (size_t)depth, (int64_t)n, "lut_tree: sel_of")) return rc;
+        if (const int rc = check_indices(table_of, count, n_tables, "lut_tree: table_of")) return rc;
+        lut_tree_reference(pp, set, n, count, depth, sel_of, tables, table_of, out);
+        return 0;
+    });
+}
+
+int ieache_tlwe_extract_reference(const ieache_params* p, size_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u) {
+    return guarded([&] {
+        if (!p || (count && (!tlwe || !u))) return fail(IEACHE_EINVAL, "null argument");
+        const Params pp = to_params(*p);
+        if (!pp.supported()) return fail(IEACHE_EINVAL, "tlwe_extract_reference: unsupported TFHE parameter set");
+        if (const int rc = check_indices(coef_of, count, pp.N, "tlwe_extract: coef_of")) return rc;
+        tlwe_extract_reference(pp, count, tlwe, coef_of, u);
         return 0;
     });
 }

@@ -1,0 +1,78 @@
+// The CMux on TGSW samples the caller supplies, the CMux-tree lookup built from it and the extraction of a coefficient of a
+// TLWE sample (include/ieache.h section 3f), the one door: the kernels, the spectrum form of a prepared set, the twiddle table
+// and the scratch of a tree are behind this object; how a call is cut is cmux_plan.h.  Kernels: cmux.hip.
+#pragma once
+#include <cstdint>
+
+#include "cmux_plan.h"
+#include "device_buffer.h"
+#include "params.h"
+
+namespace ieache {
+
+// A prepared set of n TGSW samples: their two-limb spectrum [n][2l][q = 2 c + limb][8][64] double2 -- the layout of the
+// bootstrapping key's spectrum, one sample where that has one BK_i (192 KB at l = 3).  It owns its device memory and nothing of
+// the context's, so it may be freed before or after the context that made it is closed; `owner` names that context among all
+// the process has had, and only it accepts the set.
+struct TgswSet {
+    dev::DeviceBuffer<double2> spectrum;
+    size_t n = 0;
+    uint64_t owner = 0;
+    int device = 0;
+};
+
+// Where the rows of one launch of k_cmux_x1 live: source and destination bases plus the rule that maps row r to (d1 row, d0 row,
+// selector) -- no pointer tables.
+//   flat (depth < 0):       d1 = src + r, d0 = src0 + r (src0 null: zeros), out = dst + r, selector sel_of[r] (null: item0 + r)
+//   tree level k, width w:  item = r / w, pair = r % w; block = item, or at level 0 (shared) table_of[item0 + item] clamped (null: 0);
+//                           d0 = src + block 2 w + 2 pair, d1 = d0 + 1, out = dst + r, selector sel_of[(item0 + item) depth + k]
+//                           (null: (item0 + item) depth + k)
+// An explicit selector is clamped into [0, n_set), an implied one taken mod n_set: a bad index reads another sample, never
+// memory outside the set.  Rows are [2][1024] words.
+struct CmuxRows {
+    const int32_t* src = nullptr;
+    const int32_t* src0 = nullptr;
+    int32_t* dst = nullptr;
+    const int32_t* sel_of = nullptr;
+    const int32_t* table_of = nullptr;  // read only when `shared`; indexed by call item, like the tree's selectors
+    int64_t rows = 0;
+    int64_t item0 = 0;                  // first row / item of the piece within the call (a flat piece's src, dst and sel_of are already offset)
+    int32_t n_set = 1, n_tables = 1;
+    int32_t depth = -1, level = 0, width = 1;
+    int32_t shared = 0;
+};
+
+// Scratch of a tree on one stream: the two buffers whose roles swap from level to level.
+struct CmuxScratch {
+    dev::DeviceBuffer<int32_t> a, b;
+};
+
+// One per evaluator.  All methods expect the evaluator's device to be current.
+struct Cmux {
+    void init(const Params& p, int device);
+    uint64_t id() const { return id_; }
+    // d_samples [n][2l][2][N] int32 on the device -> a new set (the caller owns it).  Synchronises the stream.  Throws
+    // std::invalid_argument where the parameter set is not one of the 64-lane kernels' (br_supported(), br_plan.h) or n < 1.
+    TgswSet* prepare(const int32_t* d_samples, size_t n, hipStream_t stream);
+    // std::invalid_argument unless `set` was prepared by this object
+    void check_owner(const TgswSet& set) const;
+    // scratch for every piece of a tree's plan ahead of the loop, so that no piece allocates
+    void reserve(CmuxScratch& scratch, const CmuxPlan& pl);
+    // one launch of `rows.rows` CMuxes
+    void launch(const TgswSet& set, hipStream_t stream, CmuxRows rows);
+    // one piece of a tree: `items` items from call item `item0` on, tables [n_tables][2^depth][2][N] -> out [items][2][N];
+    // returns the kernel launches issued (depth, or 1 for the copy of depth 0)
+    int launch_tree(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth,
+                    const int32_t* sel_of, const int32_t* tables, int32_t n_tables, const int32_t* table_of, int32_t* out);
+    // coefficient coef_of[i] (null: 0; clamped into [0, N)) of tlwe [count][2][N] -> u [count][stride], N + 1 words written.
+    // Any supported parameter set.
+    void launch_extract(hipStream_t stream, int64_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u, int32_t stride);
+
+private:
+    Params p_;
+    int device_ = 0;
+    uint64_t id_ = 0;
+    dev::DeviceBuffer<double2> tw_;  // the 64-lane transforms' twiddle table, built with the first set
+};
+
+}  // namespace ieache

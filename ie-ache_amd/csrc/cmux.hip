@@ -1,0 +1,290 @@
+// The CMux on TGSW samples the caller supplies (include/ieache.h section 3f): out = d0 + C_sel [.] (d1 - d0), the external
+// product of libtfhe's tGswExternMulToTLwe on the provably exact two-limb spectrum -- k_blind_rotate_x1's step
+// (blind_rotate_w64.hip) with the operand taken from global memory instead of a rotating LDS accumulator and the key block
+// chosen per row.  Built from the pieces of br_step.h and fft512.h; no kernel of the blind rotation is touched.
+// N = 1024, k = 1 and libtfhe's two (l, Bgbit), as br_supported() says; the extraction kernel at the end takes any set.
+#include "cmux.h"
+
+#include <atomic>
+#include <memory>
+#include <stdexcept>
+#include <type_traits>
+
+#include "blind_rotate_w64.h"
+#include "br_step.h"
+
+namespace ieache {
+
+using namespace dev;
+using namespace w64;
+
+namespace {
+
+// one row [2][1024] int32 as a buffer resource, and word j + lane of it (j a multiple of 64 known at compile time)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_resource(const int32_t* row) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(row), (short)0, 2 * kN * 4, 0x00020000);
+}
+__device__ __forceinline__ uint32_t row_word(__amdgpu_buffer_rsrc_t rsrc, int lane4, int j) {
+    return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, lane4, j * 4, 0);
+}
+
+// ---- one CMux per wave ----
+// Per row: 2L forward transforms of the digits of d1 - d0, 4 x 2L row products against block `sel` of the set's spectrum into
+// the four sums s[2 c + limb], two interleaved pairs of inverse transforms, the limbs recombined as lo + (hi << 16) mod 2^32,
+// d0 added, vector stores.  Every rounded sum stays below 2L x 1024 x 2^(BGBIT-1) x 2^15 <= 2^37 of the 2^53 an FP64 mantissa
+// holds, so the words are exact for ANY caller words: no guard.
+//   * there is no rotation, so no LDS accumulator: the lane reads its 16 coefficients of d1 and d0 per polynomial (j = 64 r +
+//     lane and j + 512: the forward transform's own (register, lane) order, 256 contiguous bytes per load) straight into
+//     registers and forms ((d1 - d0) + offset) ^ offset, every digit's field ready for signed_digit;
+//   * d0 is NOT kept across the products (32 registers the four sums leave no room for): the epilogue reads it again (16 more
+//     loads per polynomial, which the caches are left to serve; kept in registers it spilled);
+//   * the selector, the row rule and with them every base address are wave-uniform: the spectrum block goes into the buffer
+//     resource's base (sel x step bytes), the rows of a block into the scalar offset, as for BK_i;
+//   * BK loads as in k_blind_rotate_x1: block 0 of a row requested inside its forward transform, block q + 2 when block q has
+//     been multiplied; forward transforms' lane-high transpose cross-lane, everything else through the wave's tile.
+// G = 4 rows per workgroup share the twiddle table only; one workgroup barrier (after the table is in LDS).
+// hipcc reports 252 VGPRs, no scratch, for both parameter sets -> 2 waves per SIMD, 8 rows per CU, the bound stated to the
+// compiler as __launch_bounds__(256, 2); LDS is static: sT [4][kTile] | tw [kTwElems] double2 = 46 080 B, three workgroups' worth
+// per CU, so the registers bind, not the LDS.  G = 8 would halve the table copies per row and changes nothing else; not measured.
+template <int L, int BGBIT, int G = kCmuxWaveRows>
+__global__ __launch_bounds__(64 * G, 2) void k_cmux_x1(CmuxRows A, const double2* __restrict__ bkf, const double2* __restrict__ gtw) {
+    __shared__ __align__(16) double2 sT_all[G * kTile];
+    __shared__ __align__(16) double2 sTw[kTwElems];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    double2* sT = sT_all + wave * kTile;
+    load_twiddles(sTw, gtw, tid, 64 * G);
+    __syncthreads();  // the only workgroup barrier
+    const int64_t r = (int64_t)blockIdx.x * G + wave;
+    if (r >= A.rows) return;
+    const LaneRoots R = make_roots(sTw, lane);
+
+    // row r -> (d1, d0, selector): all wave-uniform
+    const int32_t* p1;
+    const int32_t* p0;
+    int64_t sel;
+    bool implied;
+    if (A.depth < 0) {
+        p1 = A.src + (size_t)r * 2 * kN;
+        p0 = A.src0 ? A.src0 + (size_t)r * 2 * kN : nullptr;
+        implied = A.sel_of == nullptr;
+        sel = implied ? A.item0 + r : (int64_t)A.sel_of[r];
+    } else {
+        const int64_t item = r / A.width, pair = r - item * A.width;
+        int64_t block = item;
+        if (A.shared) {
+            const int64_t t = A.table_of ? (int64_t)A.table_of[A.item0 + item] : 0;
+            block = t < 0 ? 0 : (t >= A.n_tables ? A.n_tables - 1 : t);
+        }
+        p0 = A.src + ((size_t)block * 2 * A.width + 2 * (size_t)pair) * 2 * kN;
+        p1 = p0 + 2 * kN;
+        const int64_t at = (A.item0 + item) * A.depth + A.level;
+        implied = A.sel_of == nullptr;
+        sel = implied ? at : (int64_t)A.sel_of[at];
+    }
+    if (implied)
+        sel %= A.n_set;
+    else
+        sel = sel < 0 ? 0 : (sel >= A.n_set ? A.n_set - 1 : sel);
+    int32_t* po = A.dst + (size_t)r * 2 * kN;
+    // d0 = zeros: the loads read d1's words instead and a wave-uniform mask clears them -- no branch per load
+    const uint32_t keep0 = p0 ? 0xFFFFFFFFu : 0u;
+    if (!p0) p0 = p1;
+    // rows through the buffer path as well: resource (the row's 8 KB, so nothing past it can be touched) and word offset in
+    // SGPRs, the lane's 4 bytes the only vector operand -- as plain global accesses the 48 of them each got a 64-bit vector
+    // address, which the kernel spilled
+    const __amdgpu_buffer_rsrc_t r1 = row_resource(p1), r0 = row_resource(p0), ro = row_resource(po);
+    const int lane4 = lane * 4;
+
+    constexpr int kBlockBytes = kM * (int)sizeof(double2), kRowBytes = 4 * kBlockBytes, kStepBytes = 2 * L * kRowBytes;
+    // the resource covers the selected sample only: its rows [2L][q = 2 c + limb][8][64] double2
+    const __amdgpu_buffer_rsrc_t bk_rsrc = bk_resource(bkf + (size_t)sel * (kStepBytes / sizeof(double2)), 1, kStepBytes);
+    const int lane16 = bk_lane_offset(lane);
+    const uint32_t dec_offset = decomposition_offset<L, BGBIT>();
+
+    double2 s[4][8];
+    uint32_t v0[8], v1[8];
+    auto decompose = [&](const int c) {
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const int j = c * kN + 64 * q;
+            const uint32_t a0 = row_word(r0, lane4, j) & keep0, a1 = row_word(r0, lane4, j + kM) & keep0;
+            v0[q] = ((row_word(r1, lane4, j) - a0) + dec_offset) ^ dec_offset;
+            v1[q] = ((row_word(r1, lane4, j + kM) - a1) + dec_offset) ^ dec_offset;
+        }
+    };
+    auto digit_row = [&](const int sh, const int brow, auto first) {
+        constexpr bool FIRST = decltype(first)::value;
+        double2 x[8], bA[8], bB[8];
+        digits_to_double2<BGBIT>(x, v0, v1, sh);
+        __builtin_amdgcn_sched_barrier(0);
+        auto req = [&]() { load_bk_block(bA, bk_rsrc, lane16, brow); };  // block 0: output 0, low limb
+        fft512_forward<true, 1, decltype(req), true>(x, sT, lane, R, req);
+        load_bk_block(bB, bk_rsrc, lane16, brow + kBlockBytes);          // block 1: output 0, high limb
+        __builtin_amdgcn_sched_barrier(0);
+        mac_row<FIRST>(s[0], x, bA);
+        __builtin_amdgcn_sched_barrier(0);
+        load_bk_block(bA, bk_rsrc, lane16, brow + 2 * kBlockBytes);      // block 2: output 1, low limb
+        __builtin_amdgcn_sched_barrier(0);
+        mac_row<FIRST>(s[1], x, bB);
+        __builtin_amdgcn_sched_barrier(0);
+        load_bk_block(bB, bk_rsrc, lane16, brow + 3 * kBlockBytes);      // block 3: output 1, high limb
+        __builtin_amdgcn_sched_barrier(0);
+        mac_row<FIRST>(s[2], x, bA);
+        mac_row<FIRST>(s[3], x, bB);
+    };
+    decompose(0);
+    digit_row(32 - BGBIT, 0, std::true_type{});
+    // ONE loop over the other 2L - 1 rows, the second decomposition inside it: as two loops, the L = 2 build (one trip each) became
+    // straight-line code whose BK requests the compiler gathered at the top and spilled (287 VGPRs)
+#pragma unroll 1
+    for (int row = 1; row < 2 * L; row++) {
+        const int c = row >= L ? 1 : 0, q = row - c * L;
+        if (q == 0) decompose(1);
+        digit_row(32 - (q + 1) * BGBIT, row * kRowBytes, std::false_type{});
+    }
+    // opaque copy: d0 is read AGAIN below.  Through the same pointer the compiler would keep the 32 words it loaded for the
+    // decompositions alive across every product instead -- registers this kernel does not have (they were spilled)
+    const int32_t* p0e = p0;
+    asm volatile("" : "+s"(p0e));
+    const __amdgpu_buffer_rsrc_t r0e = row_resource(p0e);
+    // back to coefficients: s[2 c] / s[2 c + 1] hold the low / high limb sums of output polynomial c
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        fft512_inverse_pair<true>(s[2 * c], s[2 * c + 1], sT, lane, R);
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            double unused = 0.0;  // nothing to watch: every rounded sum is below 2^37
+            const uint32_t e0 = round_coef(s[2 * c][q].x, untwist_gain(q), false, unused) + (round_coef(s[2 * c + 1][q].x, untwist_gain(q), false, unused) << 16);
+            const uint32_t e1 = round_coef(s[2 * c][q].y, untwist_gain(q), false, unused) + (round_coef(s[2 * c + 1][q].y, untwist_gain(q), false, unused) << 16);
+            const int j = c * kN + 64 * q;
+            const uint32_t a0 = row_word(r0e, lane4, j) & keep0, a1 = row_word(r0e, lane4, j + kM) & keep0;
+            __builtin_amdgcn_raw_buffer_store_b32(a0 + e0, ro, lane4, j * 4, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(a1 + e1, ro, lane4, (j + kM) * 4, 0);
+        }
+    }
+}
+
+// ---- a tree of depth 0: out_i = row 0 of its table ----
+__global__ __launch_bounds__(256) void k_cmux_copy(const int32_t* __restrict__ tables, int32_t n_tables, const int32_t* __restrict__ table_of,
+                                                   int64_t item0, int32_t* __restrict__ out) {
+    const int64_t i = blockIdx.x;
+    const int64_t t0 = table_of ? (int64_t)table_of[item0 + i] : 0;
+    const int64_t t = t0 < 0 ? 0 : (t0 >= n_tables ? n_tables - 1 : t0);
+    const int4* src = reinterpret_cast<const int4*>(tables + (size_t)t * 2 * kN);
+    int4* dst = reinterpret_cast<int4*>(out + (size_t)i * 2 * kN);
+    for (int q = threadIdx.x; q < 2 * kN / 4; q += 256) dst[q] = src[q];
+}
+
+// ---- coefficient j of a TLWE sample as an extracted row: u[i] = A[j - i] for i <= j, -A[N + j - i] otherwise, u[N] = B[j] ----
+__global__ __launch_bounds__(256) void k_tlwe_extract(const int32_t* __restrict__ tlwe, const int32_t* __restrict__ coef_of, int32_t* __restrict__ u,
+                                                      int32_t N, int32_t stride) {
+    const int64_t row = blockIdx.x;
+    const int32_t j0 = coef_of ? coef_of[row] : 0;
+    const int32_t j = j0 < 0 ? 0 : (j0 >= N ? N - 1 : j0);
+    const int32_t* A = tlwe + (size_t)row * 2 * N;
+    int32_t* dst = u + (size_t)row * stride;
+    for (int32_t i = threadIdx.x; i <= N; i += 256)
+        dst[i] = i == N ? A[N + j] : (i <= j ? A[j - i] : (int32_t)(0u - (uint32_t)A[N + j - i]));
+}
+
+std::atomic<uint64_t> g_next_id{1};
+
+template <class F>
+void with_param_set(int32_t l, F&& f) {
+    if (l == 3)
+        f(std::integral_constant<int, 3>{}, std::integral_constant<int, 7>{});
+    else
+        f(std::integral_constant<int, 2>{}, std::integral_constant<int, 10>{});
+}
+
+}  // namespace
+
+void Cmux::init(const Params& p, int device) {
+    p_ = p;
+    device_ = device;
+    id_ = g_next_id.fetch_add(1);
+}
+
+TgswSet* Cmux::prepare(const int32_t* d_samples, size_t n, hipStream_t stream) {
+    if (!br_supported(p_)) throw std::invalid_argument("tgsw_prepare: the CMux kernels cover N = 1024, k = 1 with (l, Bgbit) = (3, 7) or (2, 10) only");
+    if (!d_samples || n < 1) throw std::invalid_argument("tgsw_prepare: no samples");
+    if (n > ((size_t)1 << 20)) throw std::invalid_argument("tgsw_prepare: more than 2^20 samples");
+    if (!tw_) {
+        tw_.allocate(twiddle_table_elems());
+        hipLaunchKernelGGL(k_build_twiddle_table, dim3(1), dim3(128), 0, stream, (double2*)tw_);
+        HIP_CHECK(hipGetLastError());
+    }
+    std::unique_ptr<TgswSet> set(new TgswSet);
+    Params as_key = p_;
+    as_key.n = (int32_t)n;  // the spectrum kernel sees n samples where the bootstrapping key has n blocks BK_i
+    set->spectrum.allocate(spectrum_elems(as_key));
+    prepare_spectrum(as_key, d_samples, set->spectrum, stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(stream));
+    set->n = n;
+    set->owner = id_;
+    set->device = device_;
+    return set.release();
+}
+
+void Cmux::check_owner(const TgswSet& set) const {
+    if (set.owner != id_ || !set.spectrum || set.n < 1) throw std::invalid_argument("the TGSW set was prepared on another context");
+}
+
+void Cmux::reserve(CmuxScratch& scratch, const CmuxPlan& pl) {
+    scratch.a.reserve_exact((size_t)pl.a_rows * 2 * kN);
+    scratch.b.reserve_exact((size_t)pl.b_rows * 2 * kN);
+}
+
+void Cmux::launch(const TgswSet& set, hipStream_t stream, CmuxRows rows) {
+    check_owner(set);
+    if (rows.rows <= 0) return;
+    rows.n_set = (int32_t)set.n;
+    const unsigned grid = (unsigned)((rows.rows + kCmuxWaveRows - 1) / kCmuxWaveRows);
+    with_param_set(p_.l, [&](auto l, auto bgbit) {
+        hipLaunchKernelGGL((k_cmux_x1<decltype(l)::value, decltype(bgbit)::value>), dim3(grid), dim3(64 * kCmuxWaveRows), 0, stream, rows,
+                           (const double2*)set.spectrum, (const double2*)tw_);
+    });
+}
+
+int Cmux::launch_tree(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth,
+                      const int32_t* sel_of, const int32_t* tables, int32_t n_tables, const int32_t* table_of, int32_t* out) {
+    check_owner(set);
+    if (items <= 0) return 0;
+    if (depth < 0 || depth > kCmuxMaxDepth || n_tables < 1) throw std::invalid_argument("lut_tree: depth or n_tables out of range");
+    if (depth == 0) {
+        hipLaunchKernelGGL(k_cmux_copy, dim3((unsigned)items), dim3(256), 0, stream, tables, n_tables, table_of, item0, out);
+        return 1;
+    }
+    const size_t row = (size_t)2 * kN;
+    const int64_t level0_rows = items << (depth - 1);
+    if ((depth >= 2 && scratch.a.items() < (size_t)level0_rows * row) || (depth >= 3 && scratch.b.items() < (size_t)(level0_rows / 2) * row))
+        throw std::invalid_argument("lut_tree: piece larger than the reserved scratch");
+    const int32_t* src = tables;
+    for (int32_t k = 0; k < depth; k++) {
+        CmuxRows R;
+        R.depth = depth;
+        R.level = k;
+        R.width = 1 << (depth - 1 - k);
+        R.rows = items * R.width;
+        R.item0 = item0;
+        R.sel_of = sel_of;
+        R.src = src;
+        R.shared = k == 0;
+        R.table_of = table_of;
+        R.n_tables = n_tables;
+        // the last level writes the caller's rows; the others alternate between the two scratch buffers
+        R.dst = k == depth - 1 ? out : (k % 2 == 0 ? (int32_t*)scratch.a : (int32_t*)scratch.b);
+        launch(set, stream, R);
+        src = R.dst;
+    }
+    return depth;
+}
+
+void Cmux::launch_extract(hipStream_t stream, int64_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u, int32_t stride) {
+    if (count <= 0) return;
+    hipLaunchKernelGGL(k_tlwe_extract, dim3((unsigned)count), dim3(256), 0, stream, tlwe, coef_of, u, p_.N, stride);
+}
+
+}  // namespace ieache

@@ -1,0 +1,56 @@
+// The CMux on caller TGSW samples and the CMux-tree lookup (cmux.hip; include/ieache.h section 3f): how a call is cut into
+// pieces: THE statement of it (the evaluator loops by the answer and cmux.hip sizes its scratch by it; nothing else decides).
+// Free of HIP so that the CPU tests can check it (tests/native/cmux_plan_test.cpp).
+//
+//   k_cmux_x1        one CMux per wave: out = d0 + C_sel [.] (d1 - d0) on the two-limb spectrum
+//   k_cmux_copy      a tree of depth 0: out_i = tables[table_of[i]][0]
+//   k_tlwe_extract   coefficient j of a TLWE sample as an extracted LWE row
+//
+// A tree call over `items` items of depth d runs level k = 0 .. d-1 as ONE launch of items x 2^(d-1-k) CMuxes.  Level 0 reads
+// the caller's tables and the last level writes the caller's output; the levels between go through two scratch buffers that
+// swap roles: A holds the output of levels 0, 2, 4 .., B of levels 1, 3, ...  A piece is a run of WHOLE items whose level-0
+// output stays within the cap, so A is items x 2^(d-1) rows and B half of that; a single item wider than the cap (d = 12 at a
+// cap below 2 048) is a piece of its own.  A flat call has no scratch; the same cap bounds the rows of one launch.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace ieache {
+
+constexpr int32_t kCmuxMaxDepth = 12;       // IEACHE_LUT_TREE_MAX_DEPTH: a table of 4 096 samples (32 MB at N = 1024) per item
+constexpr int32_t kCmuxWaveRows = 4;        // rows (= waves) per workgroup of k_cmux_x1
+// Rows of a piece at most: 8 192 rows of [2][1024] int32 are 64 MB of scratch A and 32 MB of B, which a depth-10 tree over 16
+// items or a depth-12 tree over 4 fills; a launch of 8 192 waves is 4 rounds of the 2 048 resident on 256 CUs, so the ragged
+// end of a piece costs little.
+constexpr int64_t kCmuxPieceRows = 8192;
+constexpr int64_t kCmuxPieceRowsMax = (int64_t)1 << 20;
+
+struct CmuxPlan {
+    int64_t items_per_piece = 0, pieces = 0;
+    int64_t level0_rows = 0;   // rows the first level of the largest piece (the first) writes: items_per_piece x 2^(depth-1); flat: its rows
+    int64_t a_rows = 0, b_rows = 0;  // scratch rows of [2][N] words: A (depth >= 2), B (depth >= 3)
+};
+// items [first, first + count) of piece `i`
+inline int64_t cmux_piece_first(const CmuxPlan& pl, int64_t i) { return i * pl.items_per_piece; }
+inline int64_t cmux_piece_items(const CmuxPlan& pl, int64_t items, int64_t i) {
+    const int64_t left = items - cmux_piece_first(pl, i);
+    return left < pl.items_per_piece ? left : pl.items_per_piece;
+}
+
+// A call of `items` items: depth < 0 names a flat call (rows = items), 0 .. kCmuxMaxDepth a tree.  piece_rows_opt:
+// "cmux_piece_rows" (anything outside 1 .. kCmuxPieceRowsMax: the default).
+inline CmuxPlan cmux_plan(int64_t items, int32_t depth, int64_t piece_rows_opt) {
+    CmuxPlan pl;
+    if (items <= 0 || depth > kCmuxMaxDepth) return pl;
+    if (piece_rows_opt < 1 || piece_rows_opt > kCmuxPieceRowsMax) piece_rows_opt = kCmuxPieceRows;
+    const int64_t per_item = depth < 1 ? 1 : (int64_t)1 << (depth - 1);  // level-0 output rows of one item (a copy: one)
+    pl.items_per_piece = piece_rows_opt / per_item < 1 ? 1 : piece_rows_opt / per_item;
+    if (pl.items_per_piece > items) pl.items_per_piece = items;
+    pl.pieces = (items + pl.items_per_piece - 1) / pl.items_per_piece;
+    pl.level0_rows = pl.items_per_piece * per_item;
+    pl.a_rows = depth >= 2 ? pl.level0_rows : 0;
+    pl.b_rows = depth >= 3 ? pl.level0_rows / 2 : 0;
+    return pl;
+}
+
+}  // namespace ieache

@@ -15,6 +15,7 @@
 namespace ieache {
 
 struct OptionRow;  // evaluator_options.h
+struct TgswSet;    // cmux.h
 
 struct EvalStats {
     double total_ms = 0;         // wall time of the call on the GPU timeline (events on the stream)
@@ -40,6 +41,8 @@ enum StageSlot : int {
     kStageBias,       //   ... and the bias of each factor
     kStageExtracted,  // key switch alone: extracted samples, rows of extract_stride() words (a slot of its own: the operand
                       // slots' padding words stay zero)
+    kStageTlweA,      // CMux / extraction: TLWE rows [count][2][N] (d1, or the samples to extract from), and d0
+    kStageTlweB,
     kStageSlots
 };
 
@@ -141,6 +144,30 @@ public:
     // K split, K steps.  std::invalid_argument without a key.
     void pack_plan_figures(size_t groups, int32_t m, int64_t out[4]) const;
     void pack_device(size_t groups, int32_t m, int32_t spread, int32_t shift, const Torus32* d_rows, Torus32* d_out, EvalStats* stats);
+
+    // CMux on caller TGSW samples, the CMux-tree lookup and the extraction of a coefficient (cmux.h; include/ieache.h section
+    // 3f states the definitions).  tgsw_prepare_device: d_samples [n][2l][2][N] -> a set the caller owns (delete it before or
+    // after this evaluator goes; only this evaluator accepts it); std::invalid_argument unless br_supported().
+    // cmux_device: out[i] = d0[i] + set[sel] [.] (d1[i] - d0[i]), rows [2][N]; d_sel_of null: sample i mod n; d_d0 null: zeros.
+    // lut_tree_device: item i folds d_tables[table_of[i]] ([2^depth][2][N]; table_of null: 0) by the selectors
+    // sel_of[i depth + k] (null: (i depth + k) mod n), LSB first, level by level on two scratch buffers the evaluator keeps.
+    // Both in pieces (cmux_plan.h, "cmux_piece_rows") on the evaluator's stream, a tree's scratch reserved before the first.
+    // Indices are read on the device only and clamped there.  Exact on the two-limb spectrum: no guard, no audit.  stats:
+    // bootstraps 0, no key-switch launch, one chunk per piece, levels 1 / depth, the CMux launches and their time in the
+    // blind-rotation fields.  std::invalid_argument for an output over any input, depth outside 0 .. kCmuxMaxDepth,
+    // n_tables < 1 and a set of another evaluator.
+    // tlwe_extract_device: coefficient coef_of[i] (null: 0) of d_tlwe [count][2][N] -> d_u [count][extract_stride()], N + 1
+    // words written: what keyswitch_device takes.  Any supported parameter set.
+    TgswSet* tgsw_prepare_device(const Torus32* d_samples, size_t n);
+    uint64_t cmux_id() const;  // what TgswSet::owner holds for this evaluator's sets
+    void cmux_device(const TgswSet& set, size_t count, const int32_t* d_sel_of, const Torus32* d_d1, const Torus32* d_d0, Torus32* d_out,
+                     EvalStats* stats);
+    void lut_tree_device(const TgswSet& set, size_t count, int32_t depth, const int32_t* d_sel_of, const Torus32* d_tables, int32_t n_tables,
+                         const int32_t* d_table_of, Torus32* d_out, EvalStats* stats);
+    void tlwe_extract_device(size_t count, const Torus32* d_tlwe, const int32_t* d_coef_of, Torus32* d_u, EvalStats* stats);
+    // the plan such a call would follow under the options as they are (cmux_plan.h; depth < 0: a flat call of `count` rows):
+    // pieces, items per piece, rows of scratch A, rows of scratch B
+    void cmux_plan_figures(size_t count, int32_t depth, int64_t out[4]) const;
 
     // bootsMUX: out[i] = a[i] ? b[i] : c[i] (two blind rotations + one key switch per gate)
     void mux_device(size_t count, const Torus32* d_a, const Torus32* d_b, const Torus32* d_c, Torus32* d_out,

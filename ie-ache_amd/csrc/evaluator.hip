@@ -24,6 +24,7 @@
 #include "device_buffer.h"
 #include "device_common.h"
 #include "evaluator_options.h"
+#include "cmux.h"
 #include "joint_plan.h"
 #include "keyswitch.h"
 #include "multi_extract.h"
@@ -129,6 +130,7 @@ struct Lane {
     KsScratch ks;                   // key switch
     MvScratch mv;                   // multi-output programmable bootstrap: a piece's accumulators and its extracted rows
     std::unique_ptr<PackScratch> pack;  // packing key switch: a piece's R rows and digits; there while a packing key is set
+    CmuxScratch cmux;               // CMux tree: the two buffers whose roles swap from level to level (empty until a tree runs)
     Event ev_join;                  // the lane's share of a level / of an evaluation is queued
     Event ev_mix;
 };
@@ -159,6 +161,7 @@ struct Evaluator::Impl {
     DeviceBuffer<int32_t> ksk;
     KeySwitch ks;  // K5: kernels, key form, LDS grants and the choice among them
     Pack pack;  // the packing key switch (LWE rows -> TLWE samples): kernels, key form and the cut of a call (pack_plan.h)
+    Cmux cmux;  // CMux on caller TGSW samples, its tree and the extraction of a coefficient: kernels, twiddles, the cut (cmux_plan.h)
     MultiExtract mv;  // between K3 and K5 of a multi-output programmable bootstrap: the factors' lists and the extraction by factor
     DeviceBuffer<Torus32> store;    // circuits: the wire store, the gate and the output table
     DeviceBuffer<DevGate> d_gates;
@@ -231,6 +234,7 @@ void Evaluator::init() {
     d_->ks.init(p, K);
     d_->mv.init(p);
     d_->pack.init(p);
+    d_->cmux.init(p, device_);
 }
 
 Evaluator::~Evaluator() { destroy(); }
@@ -949,6 +953,114 @@ void Evaluator::pack_device(size_t groups, int32_t m, int32_t spread, int32_t sh
     HIP_CHECK(hipStreamSynchronize(stream_));
     add_times(stats, tall, tbr, tks);
     if (stats) stats->levels += 1;
+}
+
+TgswSet* Evaluator::tgsw_prepare_device(const Torus32* d_samples, size_t n) {
+    HIP_CHECK(hipSetDevice(device_));
+    return d_->cmux.prepare(d_samples, n, stream_);
+}
+
+uint64_t Evaluator::cmux_id() const { return d_->cmux.id(); }
+
+void Evaluator::cmux_plan_figures(size_t count, int32_t depth, int64_t out[4]) const {
+    if (depth > kCmuxMaxDepth) throw std::invalid_argument("lut_tree: depth must lie in 0 .. 12");
+    const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
+    out[0] = pl.pieces;
+    out[1] = pl.items_per_piece;
+    out[2] = pl.a_rows;
+    out[3] = pl.b_rows;
+}
+
+// The flat CMux: pieces of at most "cmux_piece_rows" rows on the evaluator's stream, one launch each.  No run_guarded: the
+// two-limb product is exact, nothing can trip.
+void Evaluator::cmux_device(const TgswSet& set, size_t count, const int32_t* d_sel_of, const Torus32* d_d1, const Torus32* d_d0, Torus32* d_out,
+                            EvalStats* stats) {
+    d_->cmux.check_owner(set);
+    const size_t row = (size_t)2 * (size_t)p_.N;
+    if (overlaps(d_out, count * row, {{d_d1, count * row}, {d_d0, count * row}, {d_sel_of, count}}))
+        throw std::invalid_argument("cmux: the output overlaps an input");
+    begin_call();
+    if (count == 0) return;
+    if (!d_d1 || !d_out) throw std::invalid_argument("cmux: null rows");
+    const CmuxPlan pl = cmux_plan((int64_t)count, -1, d_->opt.cmux_piece_rows);
+    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(false, stream_);
+    tall.mark();
+    for (int64_t i = 0; i < pl.pieces; i++) {
+        const int64_t r0 = cmux_piece_first(pl, i);
+        CmuxRows R;
+        R.rows = cmux_piece_items(pl, (int64_t)count, i);
+        R.src = d_d1 + (size_t)r0 * row;
+        R.src0 = d_d0 ? d_d0 + (size_t)r0 * row : nullptr;
+        R.dst = d_out + (size_t)r0 * row;
+        R.sel_of = d_sel_of ? d_sel_of + r0 : nullptr;
+        R.item0 = r0;
+        tbr.mark();
+        d_->cmux.launch(set, stream_, R);
+        tbr.mark();
+        HIP_CHECK(hipGetLastError());
+        if (stats) {
+            stats->blind_rotate_launches++;
+            stats->chunks++;
+        }
+    }
+    tall.mark();
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    add_times(stats, tall, tbr, tks);
+    if (stats) stats->levels += 1;
+}
+
+// The CMux tree: pieces of whole items, each `depth` launches through the two scratch buffers, which are reserved for the
+// largest piece before the first.
+void Evaluator::lut_tree_device(const TgswSet& set, size_t count, int32_t depth, const int32_t* d_sel_of, const Torus32* d_tables, int32_t n_tables,
+                                const int32_t* d_table_of, Torus32* d_out, EvalStats* stats) {
+    d_->cmux.check_owner(set);
+    if (depth < 0 || depth > kCmuxMaxDepth) throw std::invalid_argument("lut_tree: depth must lie in 0 .. 12");
+    if (n_tables < 1) throw std::invalid_argument("lut_tree: n_tables must be at least 1");
+    const size_t row = (size_t)2 * (size_t)p_.N;
+    if (overlaps(d_out, count * row, {{d_tables, ((size_t)n_tables << depth) * row}, {d_sel_of, count * (size_t)depth}, {d_table_of, count}}))
+        throw std::invalid_argument("lut_tree: the output overlaps an input");
+    begin_call();
+    if (count == 0) return;
+    if (!d_tables || !d_out) throw std::invalid_argument("lut_tree: null rows");
+    Lane& ln = d_->lane[0];
+    const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
+    d_->cmux.reserve(ln.cmux, pl);
+    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(false, stream_);
+    tall.mark();
+    for (int64_t i = 0; i < pl.pieces; i++) {
+        const int64_t i0 = cmux_piece_first(pl, i), cnt = cmux_piece_items(pl, (int64_t)count, i);
+        tbr.mark();
+        const int launches = d_->cmux.launch_tree(set, ln.cmux, stream_, i0, cnt, depth, d_sel_of, d_tables, n_tables, d_table_of, d_out + (size_t)i0 * row);
+        tbr.mark();
+        HIP_CHECK(hipGetLastError());
+        if (stats) {
+            stats->blind_rotate_launches += launches;
+            stats->chunks++;
+        }
+    }
+    tall.mark();
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    add_times(stats, tall, tbr, tks);
+    if (stats) stats->levels += depth;
+}
+
+void Evaluator::tlwe_extract_device(size_t count, const Torus32* d_tlwe, const int32_t* d_coef_of, Torus32* d_u, EvalStats* stats) {
+    if (overlaps(d_u, count * (size_t)extract_stride(), {{d_tlwe, count * (size_t)2 * (size_t)p_.N}, {d_coef_of, count}}))
+        throw std::invalid_argument("tlwe_extract: the output overlaps an input");
+    begin_call();
+    if (count == 0) return;
+    if (!d_tlwe || !d_u) throw std::invalid_argument("tlwe_extract: null rows");
+    Timer tall(stats != nullptr, stream_), tbr(false, stream_), tks(false, stream_);
+    tall.mark();
+    d_->cmux.launch_extract(stream_, (int64_t)count, d_tlwe, d_coef_of, d_u, extract_stride());
+    HIP_CHECK(hipGetLastError());
+    tall.mark();
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    add_times(stats, tall, tbr, tks);
+    if (stats) {
+        stats->chunks++;
+        stats->levels += 1;
+    }
 }
 
 void Evaluator::eval_circuit_device(const Circuit& c, size_t batch, const Torus32* d_in, Torus32* d_out, EvalStats* stats) {

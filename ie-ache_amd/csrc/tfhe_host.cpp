@@ -266,6 +266,96 @@ void pack_reference(const Params& p, int32_t t, int32_t basebit, const Torus32* 
             }
 }
 
+void tgsw_encrypt_sample(const Params& p, const int32_t* tlwe_key, int32_t mu, double alpha, Rng& rng, Torus32* out) {
+    const int32_t N = p.N, k = p.k, l = p.l, kpl = p.kpl();
+    for (int32_t row = 0; row < kpl; row++) tlwe_encrypt_zero(p, tlwe_key, alpha, rng, out + (size_t)row * (k + 1) * N);
+    // + mu * H : gadget on the constant coefficient of poly `bloc` in row bloc*l+q
+    for (int32_t bloc = 0; bloc <= k; bloc++)
+        for (int32_t q = 0; q < l; q++) {
+            const uint32_t h = 1u << (32 - (q + 1) * p.Bgbit);
+            uint32_t* coef = (uint32_t*)(out + ((size_t)(bloc * l + q) * (k + 1) + bloc) * N);
+            coef[0] += (uint32_t)mu * h;
+        }
+}
+
+// out (+)= C [.] d for one TGSW sample C [2l][2][N] and the TLWE difference d [2][N]: schoolbook, every word mod 2^32
+static void external_product_add(const Params& p, const Torus32* C, const uint32_t* d, uint32_t* out) {
+    const int32_t N = p.N, l = p.l, Bgbit = p.Bgbit;
+    const uint32_t halfBg = 1u << (Bgbit - 1), mask = Bgbit >= 32 ? 0xFFFFFFFFu : (1u << Bgbit) - 1u;
+    uint32_t offset = 0;
+    for (int32_t q = 1; q <= l; q++) offset += halfBg << (32 - q * Bgbit);
+    std::vector<uint32_t> dig(N);
+    for (int32_t row = 0; row < 2 * l; row++) {
+        const int32_t c = row / l, q = row % l + 1;
+        for (int32_t j = 0; j < N; j++) dig[j] = (((d[(size_t)c * N + j] + offset) >> (32 - q * Bgbit)) & mask) - halfBg;
+        for (int32_t o = 0; o < 2; o++) {
+            const uint32_t* key = (const uint32_t*)C + ((size_t)row * 2 + o) * N;
+            uint32_t* dst = out + (size_t)o * N;
+            // X^i key scaled by digit i: coefficient j of key lands on j + i, negated past N
+            for (int32_t i = 0; i < N; i++) {
+                const uint32_t e = dig[i];
+                if (!e) continue;
+                for (int32_t j = 0; j < N - i; j++) dst[j + i] += e * key[j];
+                for (int32_t j = N - i; j < N; j++) dst[j + i - N] -= e * key[j];
+            }
+        }
+    }
+}
+static void cmux_one(const Params& p, const Torus32* C, const Torus32* d1, const Torus32* d0, Torus32* out) {
+    const size_t W = (size_t)2 * p.N;
+    std::vector<uint32_t> d(W), acc(W);
+    for (size_t j = 0; j < W; j++) {
+        acc[j] = d0 ? (uint32_t)d0[j] : 0u;
+        d[j] = (uint32_t)d1[j] - acc[j];
+    }
+    external_product_add(p, C, d.data(), acc.data());
+    for (size_t j = 0; j < W; j++) out[j] = (Torus32)acc[j];
+}
+
+void cmux_reference(const Params& p, const Torus32* set, size_t n_set, size_t count, const int32_t* sel_of, const Torus32* d1, const Torus32* d0,
+                    Torus32* out) {
+    const size_t W = (size_t)2 * p.N, S = (size_t)p.kpl() * W;
+    const int n_threads = host_threads();
+    (void)n_threads;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(n_threads)
+    for (int64_t r = 0; r < (int64_t)count; r++) {
+        const size_t sel = sel_of ? (size_t)sel_of[r] : (size_t)r % n_set;
+        cmux_one(p, set + sel * S, d1 + (size_t)r * W, d0 ? d0 + (size_t)r * W : nullptr, out + (size_t)r * W);
+    }
+}
+
+void lut_tree_reference(const Params& p, const Torus32* set, size_t n_set, size_t count, int32_t depth, const int32_t* sel_of,
+                        const Torus32* tables, const int32_t* table_of, Torus32* out) {
+    const size_t W = (size_t)2 * p.N, S = (size_t)p.kpl() * W, T = (size_t)1 << depth;
+    const int n_threads = host_threads();
+    (void)n_threads;
+    for (size_t i = 0; i < count; i++) {
+        const Torus32* table = tables + (table_of ? (size_t)table_of[i] : 0) * T * W;
+        std::vector<Torus32> level(table, table + T * W), next;
+        for (int32_t k = 0; k < depth; k++) {
+            const size_t w = T >> (k + 1);
+            const size_t sel = sel_of ? (size_t)sel_of[i * (size_t)depth + k] : (i * (size_t)depth + k) % n_set;
+            next.assign(w * W, 0);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(n_threads)
+            for (int64_t j = 0; j < (int64_t)w; j++)
+                cmux_one(p, set + sel * S, level.data() + (2 * (size_t)j + 1) * W, level.data() + 2 * (size_t)j * W, next.data() + (size_t)j * W);
+            level.swap(next);
+        }
+        std::copy(level.begin(), level.begin() + W, out + i * W);
+    }
+}
+
+void tlwe_extract_reference(const Params& p, size_t count, const Torus32* tlwe, const int32_t* coef_of, Torus32* u) {
+    const int32_t N = p.N;
+    for (size_t r = 0; r < count; r++) {
+        const Torus32* A = tlwe + r * 2 * (size_t)N;
+        Torus32* dst = u + r * ((size_t)N + 1);
+        const int32_t j = coef_of ? coef_of[r] : 0;
+        for (int32_t i = 0; i < N; i++) dst[i] = i <= j ? A[j - i] : (Torus32)(0u - (uint32_t)A[N + j - i]);
+        dst[N] = A[N + j];
+    }
+}
+
 void keygen(const Params& p, const uint32_t* seed_words, int nseed, SecretKeyData* out,
             bool with_cloud) {
     out->p = p;
@@ -284,24 +374,14 @@ void keygen(const Params& p, const uint32_t* seed_words, int nseed, SecretKeyDat
 
     const int n_threads = host_threads();
     (void)n_threads;
-    const int32_t N = p.N, k = p.k, l = p.l, kpl = p.kpl();
+    const int32_t N = p.N, k = p.k, kpl = p.kpl();
     // Bootstrapping key: BK_i = TGSW_enc(lwe_key[i]) under the TLWE key.
     // One RNG stream per i so the loop can run in any order / in parallel.
     out->cloud.bk.assign(p.bk_count(), 0);
 #pragma omp parallel for schedule(dynamic, 4) num_threads(n_threads)
     for (int32_t i = 0; i < p.n; i++) {
         Rng rng = make_rng(1 + (uint64_t)i);
-        Torus32* bki = out->cloud.bk.data() + (size_t)i * kpl * (k + 1) * N;
-        for (int32_t row = 0; row < kpl; row++) {
-            tlwe_encrypt_zero(p, out->tlwe_key.data(), p.tlwe_alpha_min, rng, bki + (size_t)row * (k + 1) * N);
-        }
-        // + mu * H : gadget on the constant coefficient of poly `bloc` in row bloc*l+q
-        for (int32_t bloc = 0; bloc <= k; bloc++)
-            for (int32_t q = 0; q < l; q++) {
-                const uint32_t h = 1u << (32 - (q + 1) * p.Bgbit);
-                uint32_t* coef = (uint32_t*)(bki + ((size_t)(bloc * l + q) * (k + 1) + bloc) * N);
-                coef[0] += (uint32_t)out->lwe_key[i] * h;
-            }
+        tgsw_encrypt_sample(p, out->tlwe_key.data(), out->lwe_key[i], p.tlwe_alpha_min, rng, out->cloud.bk.data() + (size_t)i * kpl * (k + 1) * N);
     }
     // Key-switch key: KSK[i][j][d] = LWE_enc(d * tlwe_key[i] / base^(j+1)) under the n-key
     const int32_t base = p.ks_base(), n = p.n;

@@ -66,6 +66,21 @@ void packing_keygen(const Params& p, const int32_t* lwe_key, const int32_t* tlwe
 void pack_reference(const Params& p, int32_t t, int32_t basebit, const Torus32* pk, size_t groups, int32_t m, int32_t spread, int32_t shift,
                     const Torus32* rows, Torus32* out);
 
+// TGSW samples and the CMux (include/ieache.h section 3f states the definitions).  tgsw_encrypt_sample: out [2l][2][N], 2l rows
+// of tlwe_encrypt_zero one after another, then mu 2^(32 - (q+1) Bgbit) on coefficient 0 of polynomial `bloc` of row bloc l + q:
+// the routine keygen() makes BK_i with (mu = the key bit), so a seeded key is word for word what it was.
+// cmux_reference: out[r] = d0[r] + set[sel] [.] (d1[r] - d0[r]), sel = sel_of[r] (null: r mod n_set), d0 null = zeros.
+// lut_tree_reference: item i folds tables[table_of[i]] (null: 0) of 2^depth rows by the selectors sel_of[i depth + k]
+// (null: (i depth + k) mod n_set), LSB first.  Raw arrays, indices already checked by the caller.
+void tgsw_encrypt_sample(const Params& p, const int32_t* tlwe_key, int32_t mu, double alpha, Rng& rng, Torus32* out);
+void cmux_reference(const Params& p, const Torus32* set, size_t n_set, size_t count, const int32_t* sel_of, const Torus32* d1, const Torus32* d0,
+                    Torus32* out);
+void lut_tree_reference(const Params& p, const Torus32* set, size_t n_set, size_t count, int32_t depth, const int32_t* sel_of,
+                        const Torus32* tables, const int32_t* table_of, Torus32* out);
+
+// coefficient coef_of[r] (null: 0; checked by the caller) of tlwe [count][2][N] as extracted rows u [count][N+1]
+void tlwe_extract_reference(const Params& p, size_t count, const Torus32* tlwe, const int32_t* coef_of, Torus32* u);
+
 // bootsSymEncrypt / bootsSymDecrypt on raw samples (int32[n+1]).
 void lwe_encrypt_bit(const Params& p, const int32_t* lwe_key, int bit, Rng& rng, Torus32* out);
 Torus32 lwe_phase(const Params& p, const int32_t* lwe_key, const Torus32* sample);

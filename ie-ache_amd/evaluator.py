@@ -19,6 +19,7 @@ CIRC_MUL_WALLACE = 9  # carry-save multiplier (decrypt-identical, not bit-identi
 GATE_AND, GATE_XOR, GATE_OR, GATE_NAND, GATE_MUX = 0, 1, 2, 3, 4
 GATE_NOR, GATE_XNOR, GATE_ANDNY, GATE_ANDYN, GATE_ORNY, GATE_ORYN = 5, 6, 7, 8, 9, 10  # libtfhe boot-gates.cpp
 GATE_TYPES = 11
+LUT_TREE_MAX_DEPTH = 12  # IEACHE_LUT_TREE_MAX_DEPTH
 PBS_MULTI_MAX_FACTORS = 64  # most factor polynomials of one ieache_pbs_multi* call
 PBS_NO_KEYSWITCH = 1  # flag of ieache_pbs*: the extracted samples are the result (tfhe_bootstrap_woKS_FFT)
 PBS_TLWE_POLYS = 4    # ... the table is [n_polys][2][N]: TLWE samples under the ring key (an encrypted table)
@@ -181,6 +182,23 @@ def lib():
     L.ieache_pack.argtypes = [vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, i32p, i32p, sp]
     L.ieache_packing_keygen.argtypes = [pp, i32p, i32p, C.c_int32, C.c_int32, C.c_double, C.c_uint64, i32p]
     L.ieache_pack_reference.argtypes = [pp, C.c_int32, C.c_int32, i32p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, i32p, i32p]
+    L.ieache_tgsw_prepare.restype = vp
+    L.ieache_tgsw_prepare.argtypes = [vp, i32p, C.c_size_t]
+    L.ieache_tgsw_prepare_device.restype = vp
+    L.ieache_tgsw_prepare_device.argtypes = [vp, vp, C.c_size_t]
+    L.ieache_tgsw_free.restype = None
+    L.ieache_tgsw_free.argtypes = [vp]
+    L.ieache_cmux.argtypes = [vp, vp, C.c_size_t, i32p, i32p, i32p, i32p, sp]
+    L.ieache_cmux_device.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, sp]
+    L.ieache_lut_tree.argtypes = [vp, vp, C.c_size_t, C.c_int32, i32p, i32p, C.c_int32, i32p, i32p, sp]
+    L.ieache_lut_tree_device.argtypes = [vp, vp, C.c_size_t, C.c_int32, vp, vp, C.c_int32, vp, vp, sp]
+    L.ieache_tlwe_extract.argtypes = [vp, C.c_size_t, i32p, i32p, i32p, sp]
+    L.ieache_tlwe_extract_device.argtypes = [vp, C.c_size_t, vp, vp, vp, sp]
+    L.ieache_debug_cmux_plan.argtypes = [vp, C.c_size_t, C.c_int32, C.POINTER(C.c_int64)]
+    L.ieache_tgsw_encrypt.argtypes = [pp, i32p, i32p, C.c_size_t, C.c_double, C.c_uint64, i32p]
+    L.ieache_cmux_reference.argtypes = [pp, i32p, C.c_size_t, C.c_size_t, i32p, i32p, i32p, i32p]
+    L.ieache_lut_tree_reference.argtypes = [pp, i32p, C.c_size_t, C.c_size_t, C.c_int32, i32p, i32p, C.c_int32, i32p, i32p]
+    L.ieache_tlwe_extract_reference.argtypes = [pp, C.c_size_t, i32p, i32p, i32p]
     L.ieache_tlwe_encrypt.argtypes = [pp, i32p, i32p, C.c_size_t, C.c_double, C.c_uint64, i32p]
     L.ieache_tlwe_phase.argtypes = [pp, i32p, i32p, C.c_size_t, i32p]
     L.ieache_lut_factor_poly.argtypes = [pp, C.c_int32, i32p, i32p]
@@ -457,6 +475,29 @@ class CompiledNetlist:
         return out
 
 
+class TgswSet:
+    """ieache_tgsw: a prepared set of n TGSW samples (Context.tgsw_prepare).  It owns its device memory: close() may come
+    before or after the close of the context that prepared it, and only that context accepts it."""
+
+    def __init__(self, handle, n):
+        if not handle:
+            raise IeacheError(-22, lib().ieache_last_error().decode())
+        self.h, self.n = handle, n
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ieache_tgsw_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 class Context:
     """Cloud key resident on one GPU (ieache_ctx)."""
 
@@ -693,6 +734,77 @@ class Context:
     def keyswitch_device(self, count, d_u, d_out, stats=None):
         """Device pointers (ints): d_u rows of extract_stride, d_out rows of lwe_stride."""
         check(lib().ieache_keyswitch_device(self.h, count, C.c_void_p(d_u), C.c_void_p(d_out), _stats_ref(stats)))
+
+    def tgsw_prepare(self, samples):
+        """A prepared set of TGSW samples [n][2l][2][N] (or one [2l][2][N]; tools.tgsw_encrypt, or rows bk[i] of a key) for
+        cmux() and lut_tree(): a TgswSet, to be closed (or used as a context manager) before or after this context."""
+        kpl = (self.params.k + 1) * self.params.l
+        samples = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, kpl, 2, self.params.N)
+        return TgswSet(lib().ieache_tgsw_prepare(self.h, _i32(samples), samples.shape[0]), samples.shape[0])
+
+    def tgsw_prepare_device(self, d_samples, n):
+        """Device pointer (int): samples [n][2l][2][N] packed."""
+        return TgswSet(lib().ieache_tgsw_prepare_device(self.h, C.c_void_p(d_samples), int(n)), int(n))
+
+    def cmux(self, tgsw, d1, d0=None, sel_of=None, stats=None):
+        """CMux on host rows: out[i] = d0[i] + C [.] (d1[i] - d0[i]) with C = sample sel_of[i] of the set (None: i mod n), rows
+        [count][2][N]; d0 None: zeros, the external product alone (include/ieache.h section 3f)."""
+        d1 = np.ascontiguousarray(d1, dtype=np.int32).reshape(-1, 2, self.params.N)
+        count = d1.shape[0]
+        d0 = None if d0 is None else np.ascontiguousarray(d0, dtype=np.int32).reshape(-1, 2, self.params.N)
+        of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1)
+        assert (d0 is None or d0.shape[0] == count) and (of is None or of.shape[0] == count)
+        out = np.zeros((count, 2, self.params.N), dtype=np.int32)
+        check(lib().ieache_cmux(self.h, tgsw.h, count, None if of is None else _i32(of), _i32(d1), None if d0 is None else _i32(d0), _i32(out),
+                                _stats_ref(stats)))
+        return out
+
+    def cmux_device(self, tgsw, count, d_sel_of, d_d1, d_d0, d_out, stats=None):
+        """Device pointers (ints; d_sel_of and d_d0 may be None / 0): rows [count][2][N] packed, indices [count] int32."""
+        check(lib().ieache_cmux_device(self.h, tgsw.h, count, C.c_void_p(d_sel_of or None), C.c_void_p(d_d1), C.c_void_p(d_d0 or None),
+                                       C.c_void_p(d_out), _stats_ref(stats)))
+
+    def lut_tree(self, tgsw, tables, depth, sel_of=None, table_of=None, count=None, stats=None):
+        """CMux-tree lookup on host rows: item i folds tables[table_of[i]] (tables [n_tables][2^depth][2][N] or one table;
+        table_of None: table 0) by the selectors sel_of[i] ([count][depth], bit k of the index first; None: samples
+        i depth + k mod n) -> [count][2][N], an encryption of the table's row at the encrypted index.  count: the number of
+        items where neither index array gives it (default 1)."""
+        depth = int(depth)
+        tables = np.ascontiguousarray(tables, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, self.params.N)
+        of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(depth, 1))
+        tof = None if table_of is None else np.ascontiguousarray(table_of, dtype=np.int32).reshape(-1)
+        if count is None:
+            count = tof.shape[0] if tof is not None else (of.shape[0] if of is not None and depth > 0 else 1)
+        assert (tof is None or tof.shape[0] == count) and (of is None or depth < 1 or of.shape[0] == count)
+        out = np.zeros((count, 2, self.params.N), dtype=np.int32)
+        check(lib().ieache_lut_tree(self.h, tgsw.h, count, depth, None if of is None else _i32(of), _i32(tables), tables.shape[0],
+                                    None if tof is None else _i32(tof), _i32(out), _stats_ref(stats)))
+        return out
+
+    def lut_tree_device(self, tgsw, count, depth, d_sel_of, d_tables, n_tables, d_table_of, d_out, stats=None):
+        """Device pointers (ints; the index arrays may be None / 0): tables [n_tables][2^depth][2][N] packed, out [count][2][N]."""
+        check(lib().ieache_lut_tree_device(self.h, tgsw.h, count, int(depth), C.c_void_p(d_sel_of or None), C.c_void_p(d_tables), int(n_tables),
+                                           C.c_void_p(d_table_of or None), C.c_void_p(d_out), _stats_ref(stats)))
+
+    def cmux_plan(self, count, depth=-1):
+        """How cmux() (depth < 0) or lut_tree() would cut such a call under the options as they are (csrc/cmux_plan.h):
+        dict(pieces, items_per_piece, scratch_a_rows, scratch_b_rows)."""
+        out = (C.c_int64 * 4)()
+        check(lib().ieache_debug_cmux_plan(self.h, count, int(depth), out))
+        return dict(zip(("pieces", "items_per_piece", "scratch_a_rows", "scratch_b_rows"), (int(v) for v in out)))
+
+    def tlwe_extract(self, tlwe, coef_of=None, stats=None):
+        """Coefficient coef_of[i] (None: 0) of TLWE samples [count][2][N] as extracted rows [count][N+1]: what keyswitch() takes."""
+        tlwe = np.ascontiguousarray(tlwe, dtype=np.int32).reshape(-1, 2, self.params.N)
+        of = None if coef_of is None else np.ascontiguousarray(coef_of, dtype=np.int32).reshape(-1)
+        assert of is None or of.shape[0] == tlwe.shape[0]
+        u = np.zeros((tlwe.shape[0], self.params.N + 1), dtype=np.int32)
+        check(lib().ieache_tlwe_extract(self.h, tlwe.shape[0], _i32(tlwe), None if of is None else _i32(of), _i32(u), _stats_ref(stats)))
+        return u
+
+    def tlwe_extract_device(self, count, d_tlwe, d_coef_of, d_u, stats=None):
+        """Device pointers (ints; d_coef_of may be None / 0): samples [count][2][N] packed, d_u rows of extract_stride."""
+        check(lib().ieache_tlwe_extract_device(self.h, count, C.c_void_p(d_tlwe), C.c_void_p(d_coef_of or None), C.c_void_p(d_u), _stats_ref(stats)))
 
     def set_packing_key(self, pk, t=8, basebit=2):
         """The packing key [n][t][2][N] (tools.packing_keygen) for pack(): replaces an earlier one; pk=None drops it."""

@@ -136,6 +136,65 @@ def lut_pack_layout(params, entries):
     return params.N // entries, 2 * params.N - params.N // (2 * entries)
 
 
+def tgsw_encrypt(params, tlwe_key, mu, seed, alpha=None):
+    """TGSW samples under the ring key of the int32 messages mu [count] (or one; selector bits are 0 / 1) -> [count][2l][2][N]:
+    what Context.tgsw_prepare takes, made by the routine key generation makes BK_i with.  alpha None: tlwe_alpha_min; seed as for
+    tlwe_encrypt."""
+    mu = np.ascontiguousarray(mu, dtype=np.int32).reshape(-1)
+    tlwe_key = np.ascontiguousarray(tlwe_key, dtype=np.int32)
+    out = np.zeros((mu.shape[0], (params.k + 1) * params.l, 2, params.N), dtype=np.int32)
+    check(lib().ieache_tgsw_encrypt(C.byref(params), _i32(tlwe_key), _i32(mu), mu.shape[0], 0.0 if alpha is None else float(alpha), seed, _i32(out)))
+    return out
+
+
+def trivial_tlwe(polys):
+    """Plain polynomials [count][N] (or one [N]) as noiseless TLWE samples with A = 0: [count][2][N]."""
+    polys = np.ascontiguousarray(polys, dtype=np.int32)
+    polys = polys.reshape(-1, polys.shape[-1])
+    return np.ascontiguousarray(np.stack([np.zeros_like(polys), polys], axis=1))
+
+
+def cmux_reference(params, samples, d1, d0=None, sel_of=None):
+    """CPU reference of Context.cmux on raw arrays (ieache_cmux_reference; no GPU, no context, any supported set):
+    samples [n][2l][2][N], d1 / d0 [count][2][N] -> [count][2][N]."""
+    kpl = (params.k + 1) * params.l
+    samples = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, kpl, 2, params.N)
+    d1 = np.ascontiguousarray(d1, dtype=np.int32).reshape(-1, 2, params.N)
+    d0 = None if d0 is None else np.ascontiguousarray(d0, dtype=np.int32).reshape(-1, 2, params.N)
+    of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1)
+    assert (d0 is None or d0.shape == d1.shape) and (of is None or of.shape[0] == d1.shape[0])
+    out = np.zeros_like(d1)
+    check(lib().ieache_cmux_reference(C.byref(params), _i32(samples), samples.shape[0], d1.shape[0], None if of is None else _i32(of), _i32(d1),
+                                      None if d0 is None else _i32(d0), _i32(out)))
+    return out
+
+
+def lut_tree_reference(params, samples, tables, depth, sel_of=None, table_of=None, count=None):
+    """CPU reference of Context.lut_tree on raw arrays (ieache_lut_tree_reference), arguments as there."""
+    depth = int(depth)
+    kpl = (params.k + 1) * params.l
+    samples = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, kpl, 2, params.N)
+    tables = np.ascontiguousarray(tables, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, params.N)
+    of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(depth, 1))
+    tof = None if table_of is None else np.ascontiguousarray(table_of, dtype=np.int32).reshape(-1)
+    if count is None:
+        count = tof.shape[0] if tof is not None else (of.shape[0] if of is not None and depth > 0 else 1)
+    out = np.zeros((count, 2, params.N), dtype=np.int32)
+    check(lib().ieache_lut_tree_reference(C.byref(params), _i32(samples), samples.shape[0], count, depth, None if of is None else _i32(of),
+                                          _i32(tables), tables.shape[0], None if tof is None else _i32(tof), _i32(out)))
+    return out
+
+
+def tlwe_extract_reference(params, tlwe, coef_of=None):
+    """CPU reference of Context.tlwe_extract (ieache_tlwe_extract_reference): tlwe [count][2][N] -> [count][N+1]."""
+    tlwe = np.ascontiguousarray(tlwe, dtype=np.int32).reshape(-1, 2, params.N)
+    of = None if coef_of is None else np.ascontiguousarray(coef_of, dtype=np.int32).reshape(-1)
+    assert of is None or of.shape[0] == tlwe.shape[0]
+    u = np.zeros((tlwe.shape[0], params.N + 1), dtype=np.int32)
+    check(lib().ieache_tlwe_extract_reference(C.byref(params), tlwe.shape[0], _i32(tlwe), None if of is None else _i32(of), _i32(u)))
+    return u
+
+
 def int_to_bits(value, nbits):
     return np.array([(int(value) >> i) & 1 for i in range(nbits)], dtype=np.uint8)
 

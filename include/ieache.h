@@ -712,6 +712,81 @@ int ieache_pack(ieache_ctx* ctx, size_t groups, int32_t m, int32_t spread, int32
                 const int32_t* rows /*[groups*m][n+1]*/, int32_t* out /*[groups][2][N]*/, ieache_stats* stats);
 
 /* ------------------------------------------------------------------ *
+ * 3f. External product and CMux on TGSW samples the caller supplies,  *
+ *    the CMux-tree lookup, and the extraction of a coefficient:       *
+ *    levelled evaluation (Chillotti, Gama, Georgieva, Izabachene,     *
+ *    tGswExternMulToTLwe / CMux) as public calls.                     *
+ * ------------------------------------------------------------------ */
+/* The contract.  Integer definitions, mod 2^32, polynomial products negacyclic (X^N = -1).  l, Bgbit come from the context.
+ *
+ * TGSW sample C [2l][2][N] int32: every row a TLWE sample under the ring key (A then B, phase B - A s_ring); row bloc l + q
+ * (bloc 0 = A, 1 = B; q = 0 .. l-1) encrypts zero plus mu 2^(32 - (q+1) Bgbit) added to coefficient 0 of polynomial `bloc`.
+ * That is how the bootstrapping key's BK_i is built (mu = the key bit): bk[i] of any key IS a valid sample, and
+ * ieache_tgsw_encrypt (section 4) makes fresh ones with the same routine.
+ *
+ * External product C [.] d of a TLWE sample d = (dA, dB), with the blind rotation's decomposition (truncating, with offset):
+ *   offset = sum_{q=1..l} 2^(Bgbit-1) << (32 - q Bgbit),  w = u32(x) + offset,
+ *   dig_q(x) = ((w >> (32 - q Bgbit)) & (2^Bgbit - 1)) - 2^(Bgbit-1)             per coefficient x,
+ *   rows 0 .. l-1 take the digits q = 1 .. l of dA, rows l .. 2l-1 those of dB,
+ *   C [.] d = sum_r dig_r (A_r, B_r),  every product negacyclic and exact.
+ * CMux: out = d0 + C [.] (d1 - d0): d1's message when mu = 1, d0's when mu = 0; d0 == NULL stands for zeros and gives the
+ * external product alone.
+ * Tree: an item has `depth` selectors C_0 .. C_{depth-1} (bit k of the index, least significant first) and a table
+ * T [2^depth][2][N]; level k maps rows (2j, 2j+1) of the level before to CMux(C_k, row 2j+1, row 2j); the row left after `depth`
+ * levels is T[index] plus noise.  depth = 0 copies row 0 of the table.
+ * Every implementation returns the same words: the device computes the products on the two-limb spectrum, whose sums stay
+ * below 2l N 2^(Bgbit-1) 2^15 <= 2^37 of the 2^53 an FP64 mantissa holds, so the result is exact for ANY caller words, key-like
+ * or not.  Nothing is rounded, guarded or audited.
+ *
+ * A prepared set of n samples is an object: its spectrum (192 KB per sample at l = 3) is made once and used by many rows.
+ * ieache_tgsw_prepare takes samples [n][2l][2][N] from host memory, ieache_tgsw_prepare_device from device memory; NULL with
+ * ieache_last_error text for n < 1 and on a context whose parameter set the CMux kernels do not cover (they cover N = 1024,
+ * k = 1 with (l, Bgbit) = (3, 7) or (2, 10); the CPU references of section 4 take every supported set).  The set owns its
+ * device memory and nothing of the context's: ieache_tgsw_free may come BEFORE OR AFTER ieache_ctx_destroy of the context that
+ * prepared it.  Only that context accepts it.
+ *
+ * Row i of ieache_cmux uses sample sel_of[i]; sel_of == NULL: sample i mod n.  Item i of ieache_lut_tree uses samples
+ * sel_of[i depth + k], k = 0 .. depth-1; sel_of == NULL: (i depth + k) mod n; and table table_of[i] of
+ * tables [n_tables][2^depth][2][N]; table_of == NULL: table 0.  A call is cut into pieces of whole rows / items so that no
+ * launch, and no first level of a tree, holds more than "cmux_piece_rows" rows (default 8192, which bounds the tree's scratch --
+ * two buffers the context keeps -- at 96 MB; a single item wider than that still runs, alone).  ieache_tlwe_extract is the
+ * partner of ieache_keyswitch: coefficient j = coef_of[i] (NULL: 0) of TLWE sample i becomes the extracted row u[i'] = A[j - i']
+ * for i' <= j, -A[N + j - i'] otherwise, u[N] = B[j], rows shaped as IEACHE_PBS_NO_KEYSWITCH shapes them (host: N + 1 words;
+ * device: ieache_extract_stride words, N + 1 written), on any supported parameter set; so lut_tree -> tlwe_extract -> keyswitch
+ * brings a tree's result back among the gates.
+ *
+ * Host forms check every index and return IEACHE_EINVAL naming the first bad one; they stage through rows the context keeps
+ * (a warm call allocates nothing).  Device forms never read an index on the host: the kernel clamps an explicit index into its
+ * range, so a bad one gives a wrong answer, never a stray read.  IEACHE_EINVAL with ieache_last_error text: the output
+ * overlapping any input (device forms), depth outside 0 .. IEACHE_LUT_TREE_MAX_DEPTH, n_tables < 1, a set prepared on another
+ * context.  count == 0 is a no-op.  stats: bootstraps == 0, keyswitch_launches == 0, levels = 1 (cmux, tlwe_extract) or depth
+ * (tree), chunks = pieces, total_ms filled.  ieache_stats has no version field, so none was added: the CMux kernel launches
+ * (pieces for ieache_cmux, pieces x max(depth, 1) for a tree) and their time are reported in blind_rotate_launches and
+ * blind_rotate_ms.  There is no group form and no cloudd verb. */
+#define IEACHE_LUT_TREE_MAX_DEPTH 12
+typedef struct ieache_tgsw ieache_tgsw;
+ieache_tgsw* ieache_tgsw_prepare(ieache_ctx* ctx, const int32_t* samples /*host [n][2l][2][N]*/, size_t n);
+ieache_tgsw* ieache_tgsw_prepare_device(ieache_ctx* ctx, const int32_t* d_samples /*[n][2l][2][N]*/, size_t n);
+void ieache_tgsw_free(ieache_tgsw* set);
+int ieache_cmux(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, const int32_t* sel_of /*[count] or NULL*/,
+                const int32_t* d1 /*[count][2][N]*/, const int32_t* d0 /*[count][2][N] or NULL*/, int32_t* out /*[count][2][N]*/, ieache_stats* stats);
+int ieache_cmux_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, const int32_t* d_sel_of, const int32_t* d_d1, const int32_t* d_d0,
+                       int32_t* d_out, ieache_stats* stats);
+int ieache_lut_tree(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* sel_of /*[count][depth] or NULL*/,
+                    const int32_t* tables /*[n_tables][2^depth][2][N]*/, int32_t n_tables, const int32_t* table_of /*[count] or NULL*/,
+                    int32_t* out /*[count][2][N]*/, ieache_stats* stats);
+int ieache_lut_tree_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* d_sel_of, const int32_t* d_tables,
+                           int32_t n_tables, const int32_t* d_table_of, int32_t* d_out, ieache_stats* stats);
+int ieache_tlwe_extract(ieache_ctx* ctx, size_t count, const int32_t* tlwe /*[count][2][N]*/, const int32_t* coef_of /*[count] or NULL*/,
+                        int32_t* u /*[count][N+1]*/, ieache_stats* stats);
+int ieache_tlwe_extract_device(ieache_ctx* ctx, size_t count, const int32_t* d_tlwe, const int32_t* d_coef_of,
+                               int32_t* d_u /*[count][extract_stride]*/, ieache_stats* stats);
+/* How a call would be cut under the options as they are (csrc/cmux_plan.h decides, nothing else): depth < 0 names a flat call
+ * of `count` rows, 0 .. IEACHE_LUT_TREE_MAX_DEPTH a tree over `count` items; out = {pieces, items per piece, rows of scratch A,
+ * rows of scratch B}. */
+int ieache_debug_cmux_plan(const ieache_ctx* ctx, size_t count, int32_t depth, int64_t out[4]);
+
+/* ------------------------------------------------------------------ *
  * 4. CPU tools around the path (no GPU): what Keygen/keygen.c:22-51,  *
  *    Client1/alice.c:116-191 and Output/verif.c:41-76 get from        *
  *    libtfhe.  Needed to produce and check ciphertexts without it.    *
@@ -754,6 +829,21 @@ int ieache_packing_keygen(const ieache_params* p, const int32_t* lwe_key, const 
  * The refusals of the decomposition and of (m, spread, shift) are those of section 3e. */
 int ieache_pack_reference(const ieache_params* p, int32_t pk_t, int32_t pk_basebit, const int32_t* pk, size_t groups, int32_t m,
                           int32_t spread, int32_t shift, const int32_t* rows /*[groups*m][n+1]*/, int32_t* out /*[groups][2][N]*/);
+/* TGSW samples of section 3f, made by whoever holds the ring key: out [count][2l][2][N], sample i of the int32 message mu[i]
+ * (selector bits: 0 or 1), through the routine key generation makes BK_i with -- 2l rows of ieache_tlwe_encrypt's zero
+ * encryption one after another from one generator, then the gadget (existing keys and their draw order are unchanged).
+ * alpha <= 0: p->tlwe_alpha_min; seed as for ieache_tlwe_encrypt.  Any supported parameter set. */
+int ieache_tgsw_encrypt(const ieache_params* p, const int32_t* tlwe_key, const int32_t* mu /*[count]*/, size_t count, double alpha, uint64_t seed,
+                        int32_t* out /*[count][2l][2][N]*/);
+/* CPU references of the definitions of section 3f on raw arrays, no GPU, no context, any supported parameter set:
+ * set [n][2l][2][N]; arguments, defaults of the NULL index arrays and refusals (indices, depth, n_tables) as for the host forms
+ * ieache_cmux and ieache_lut_tree. */
+int ieache_cmux_reference(const ieache_params* p, const int32_t* set, size_t n, size_t count, const int32_t* sel_of, const int32_t* d1,
+                          const int32_t* d0, int32_t* out);
+int ieache_lut_tree_reference(const ieache_params* p, const int32_t* set, size_t n, size_t count, int32_t depth, const int32_t* sel_of,
+                              const int32_t* tables, int32_t n_tables, const int32_t* table_of, int32_t* out);
+/* ... and of ieache_tlwe_extract: tlwe [count][2][N] -> u [count][N+1]. */
+int ieache_tlwe_extract_reference(const ieache_params* p, size_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u);
 /* key files -> raw arrays (sizes from ieache_params; pass NULL to query params only) */
 int ieache_read_secret_key(const char* path, ieache_params* p, int32_t* lwe_key, int32_t* tlwe_key);
 int ieache_read_cloud_key(const char* path, ieache_params* p, int32_t* bk, int32_t* ksk);
