@@ -947,6 +947,10 @@ int check_tree(int32_t depth, int32_t n_tables) {
     if (n_tables < 1) return fail(IEACHE_EINVAL, "lut_tree: n_tables must be at least 1");
     return 0;
 }
+int check_scatter(int32_t depth) {
+    if (depth < 0 || depth > IEACHE_LUT_TREE_MAX_DEPTH) return fail(IEACHE_EINVAL, "lut_scatter: depth must lie in 0 .. 12");
+    return 0;
+}
 // host indices: every one of idx[0 .. count) inside [0, bound), or the code after fail()
 int check_indices(const int32_t* idx, size_t count, int64_t bound, const char* what) {
     if (idx)
@@ -1060,6 +1064,37 @@ int ieache_lut_tree(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32
         StagedRows dsel = h.words(kStagePolyOf, sel_of, count * (size_t)depth), dof = h.words(kStageBias, table_of, count);
         StagedRows dout(h.ev, kStageOut, count, sample);
         with_stats(stats, [&](EvalStats* st) { h.ev.lut_tree_device(*set->set, count, depth, dsel.p, dt.p, n_tables, dof.p, dout.p, st); });
+        dout.download(out, sample);
+        return 0;
+    });
+}
+
+// ---- the scatter (section 3g): the tree's partner ----
+int ieache_lut_scatter_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* d_sel_of, const int32_t* d_values,
+                              const int32_t* d_mem, int32_t* d_out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_tgsw(ctx, set)) return rc;
+        if (!d_values || !d_out) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_scatter(depth)) return rc;
+        require_device_pointers(count, {{d_sel_of, "d_sel_of", true}, {d_values, "d_values"}, {d_mem, "d_mem", true}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->lut_scatter_device(*set->set, count, depth, d_sel_of, d_values, d_mem, d_out, st); });
+    });
+}
+
+int ieache_lut_scatter(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* sel_of, const int32_t* values,
+                       const int32_t* mem, int32_t* out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_tgsw(ctx, set)) return rc;
+        if (!values || !out) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_scatter(depth)) return rc;
+        if (const int rc = check_indices(sel_of, count * (size_t)depth, (int64_t)set->set->n, "lut_scatter: sel_of")) return rc;
+        HostCall h(ctx, count);
+        const size_t sample = (size_t)2 * (size_t)h.p.N, rows = count << depth;
+        StagedRows dv(h.ev, kStageTlweA, count, sample, values, sample), dsel = h.words(kStagePolyOf, sel_of, count * (size_t)depth);
+        // the memory goes into the result rows and the call runs in place
+        StagedRows dout(h.ev, kStageOut, rows, sample);
+        if (mem && rows) HIP_CHECK(hipMemcpy(dout.p, mem, rows * sample * 4, hipMemcpyHostToDevice));
+        with_stats(stats, [&](EvalStats* st) { h.ev.lut_scatter_device(*set->set, count, depth, dsel.p, dv.p, mem ? dout.p : nullptr, dout.p, st); });
         dout.download(out, sample);
         return 0;
     });
@@ -1525,6 +1560,20 @@ int ieache_lut_tree_reference(const ieache_params* p, const int32_t* set, size_t
         if (const int rc = check_indices(sel_of, count * (size_t)depth, (int64_t)n, "lut_tree: sel_of")) return rc;
         if (const int rc = check_indices(table_of, count, n_tables, "lut_tree: table_of")) return rc;
         lut_tree_reference(pp, set, n, count, depth, sel_of, tables, table_of, out);
+        return 0;
+    });
+}
+
+int ieache_lut_scatter_reference(const ieache_params* p, const int32_t* set, size_t n, size_t count, int32_t depth, const int32_t* sel_of,
+                                 const int32_t* values, const int32_t* mem, int32_t* out) {
+    return guarded([&] {
+        if (!p || !set || (count && (!values || !out))) return fail(IEACHE_EINVAL, "null argument");
+        const Params pp = to_params(*p);
+        if (!pp.supported()) return fail(IEACHE_EINVAL, "lut_scatter_reference: unsupported TFHE parameter set");
+        if (n < 1) return fail(IEACHE_EINVAL, "lut_scatter_reference: no samples");
+        if (const int rc = check_scatter(depth)) return rc;
+        if (const int rc = check_indices(sel_of, count * (size_t)depth, (int64_t)n, "lut_scatter: sel_of")) return rc;
+        lut_scatter_reference(pp, set, n, count, depth, sel_of, values, mem, out);
         return 0;
     });
 }

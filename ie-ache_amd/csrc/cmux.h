@@ -1,5 +1,5 @@
 // The CMux on TGSW samples the caller supplies, the CMux-tree lookup built from it and the extraction of a coefficient of a
-// TLWE sample (include/ieache.h section 3f), the one door: the kernels, the spectrum form of a prepared set, the twiddle table
+// TLWE sample (include/ieache.h section 3f), and the scatter that writes at an encrypted index (section 3g), the one door: the kernels, the spectrum form of a prepared set, the twiddle table
 // and the scratch of a tree are behind this object; how a call is cut is cmux_plan.h.  Kernels: cmux.hip.
 #pragma once
 #include <cstdint>
@@ -42,6 +42,24 @@ struct CmuxRows {
     int32_t shared = 0;
 };
 
+// Where the rows of one launch of k_demux_x1 live (step t of a scatter, include/ieache.h section 3g): parent row r of the
+// piece splits into two children -- again a rule, no pointer tables, everything wave-uniform.
+//   width w = 2^t parents per item:  item = r / w, j = r % w;  parent = src + item w + j = src + r,
+//   children = dst + item 2 w + 2 j = dst + 2 r (lo = parent - hi) and the row after it (hi = C [.] parent),
+//   selector sel_of[(item0 + item) depth + depth - 1 - t] (null: that index mod n_set; explicit: clamped into the set).
+//   On the last step (2 w = 2^depth) `base` is null (zeros) or the piece's memory rows: child c is stored as base[2 r + c] + child.
+// base == dst is allowed (k_demux_x1 says why); no other overlap is.
+struct DemuxRows {
+    const int32_t* src = nullptr;
+    int32_t* dst = nullptr;
+    const int32_t* base = nullptr;
+    const int32_t* sel_of = nullptr;
+    int64_t rows = 0;                   // parents of this launch: items x w
+    int64_t item0 = 0;                  // first item of the piece within the call (src, dst and base are already offset)
+    int32_t n_set = 1;
+    int32_t depth = 1, step = 0, width = 1;
+};
+
 // Scratch of a tree on one stream: the two buffers whose roles swap from level to level.
 struct CmuxScratch {
     dev::DeviceBuffer<int32_t> a, b;
@@ -64,6 +82,14 @@ struct Cmux {
     // returns the kernel launches issued (depth, or 1 for the copy of depth 0)
     int launch_tree(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth,
                     const int32_t* sel_of, const int32_t* tables, int32_t n_tables, const int32_t* table_of, int32_t* out);
+    // one launch of `rows.rows` demux steps (2 x rows.rows rows written)
+    void launch_demux(const TgswSet& set, hipStream_t stream, DemuxRows rows);
+    // one piece of a scatter: `items` items from call item `item0` on, values [items][2][N] (+ mem [items][2^depth][2][N], or
+    // null: zeros) -> out [items][2^depth][2][N]; out == mem is allowed.  Step t < depth - 1 writes the scratch buffer that
+    // (depth - 2 - t) names: even A, odd B, so the widest intermediate (items x 2^(depth-1) rows) lands in A and the sizes are
+    // the tree's (cmux_plan.h).  Returns the kernel launches issued (depth, or 1 for the add of depth 0).
+    int launch_scatter(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth,
+                       const int32_t* sel_of, const int32_t* values, const int32_t* mem, int32_t* out);
     // coefficient coef_of[i] (null: 0; clamped into [0, N)) of tlwe [count][2][N] -> u [count][stride], N + 1 words written.
     // Any supported parameter set.
     void launch_extract(hipStream_t stream, int64_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u, int32_t stride);

@@ -3,6 +3,7 @@
 // (blind_rotate_w64.hip) with the operand taken from global memory instead of a rotating LDS accumulator and the key block
 // chosen per row.  Built from the pieces of br_step.h and fft512.h; no kernel of the blind rotation is touched.
 // N = 1024, k = 1 and libtfhe's two (l, Bgbit), as br_supported() says; the extraction kernel at the end takes any set.
+// k_demux_x1 is the same product as a demultiplexer: the write at an encrypted index (section 3g).
 #include "cmux.h"
 
 #include <atomic>
@@ -165,6 +166,145 @@ __global__ __launch_bounds__(64 * G, 2) void k_cmux_x1(CmuxRows A, const double2
     }
 }
 
+// ---- one demux step per wave: the scatter of include/ieache.h section 3g ----
+// Parent row p splits into hi = C_sel [.] p (child 2 r + 1) and lo = p - hi (child 2 r): k_cmux_x1's body with no d0 -- the
+// digits are those of p itself -- and another epilogue.  The orchestration is repeated here, not shared with k_cmux_x1 through
+// a common body: that kernel's instruction stream is to stay what it was.
+//   * p is NOT kept across the products; the epilogue reads it again through an opaque copy of its pointer, for k_cmux_x1's
+//     reason (kept live, its 32 words were spilled);
+//   * the last step of a scatter adds the memory: base rows 2 r and 2 r + 1 are read here and the sums stored, so no separate
+//     add pass moves 2 x 16 KB per parent more than the products do.  base null (no memory, or an earlier step) is a
+//     wave-uniform branch around those loads;
+//   * IN PLACE (base == dst) is sound: child row c of parent r is words [2 r + c][j], and the lane that stores word j of it is
+//     the only lane of the whole launch that reads word j of base row 2 r + c (rows are disjoint between waves, j = 64 q' + lane
+//     belongs to one lane), and its load stands before its store in program order on the same buffer path, which the compiler
+//     does not exchange (the two may alias).  No other word of base is touched by anyone.  The parent rows never overlap dst:
+//     they are the caller's values, which the host refuses over the output, or the other scratch buffer.
+// Rows through 8 KB buffer resources as in k_cmux_x1, so nothing past a row can be touched whatever the indices hold.
+template <int L, int BGBIT, int G = kCmuxWaveRows>
+__global__ __launch_bounds__(64 * G, 2) void k_demux_x1(DemuxRows A, const double2* __restrict__ bkf, const double2* __restrict__ gtw) {
+    __shared__ __align__(16) double2 sT_all[G * kTile];
+    __shared__ __align__(16) double2 sTw[kTwElems];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    double2* sT = sT_all + wave * kTile;
+    load_twiddles(sTw, gtw, tid, 64 * G);
+    __syncthreads();  // the only workgroup barrier
+    const int64_t r = (int64_t)blockIdx.x * G + wave;
+    if (r >= A.rows) return;
+    const LaneRoots R = make_roots(sTw, lane);
+
+    // row r -> (parent, children, base rows, selector): all wave-uniform
+    const int64_t item = r / A.width;
+    const int64_t at = (A.item0 + item) * A.depth + (A.depth - 1 - A.step);
+    int64_t sel;
+    if (A.sel_of == nullptr) {
+        sel = at % A.n_set;
+    } else {
+        sel = (int64_t)A.sel_of[at];
+        sel = sel < 0 ? 0 : (sel >= A.n_set ? A.n_set - 1 : sel);
+    }
+    const int32_t* pp = A.src + (size_t)r * 2 * kN;
+    int32_t* po = A.dst + (size_t)r * 4 * kN;
+    const bool add = A.base != nullptr;
+    const int32_t* pb = add ? A.base + (size_t)r * 4 * kN : pp;  // never read when !add: any valid row will do for the resource
+    const __amdgpu_buffer_rsrc_t rp = row_resource(pp);
+    const int lane4 = lane * 4;
+
+    constexpr int kBlockBytes = kM * (int)sizeof(double2), kRowBytes = 4 * kBlockBytes, kStepBytes = 2 * L * kRowBytes;
+    const __amdgpu_buffer_rsrc_t bk_rsrc = bk_resource(bkf + (size_t)sel * (kStepBytes / sizeof(double2)), 1, kStepBytes);
+    const int lane16 = bk_lane_offset(lane);
+    const uint32_t dec_offset = decomposition_offset<L, BGBIT>();
+
+    double2 s[4][8];
+    uint32_t v0[8], v1[8];
+    auto decompose = [&](const int c) {
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const int j = c * kN + 64 * q;
+            v0[q] = (row_word(rp, lane4, j) + dec_offset) ^ dec_offset;
+            v1[q] = (row_word(rp, lane4, j + kM) + dec_offset) ^ dec_offset;
+        }
+    };
+    auto digit_row = [&](const int sh, const int brow, auto first) {
+        constexpr bool FIRST = decltype(first)::value;
+        double2 x[8], bA[8], bB[8];
+        digits_to_double2<BGBIT>(x, v0, v1, sh);
+        __builtin_amdgcn_sched_barrier(0);
+        auto req = [&]() { load_bk_block(bA, bk_rsrc, lane16, brow); };  // block 0: output 0, low limb
+        fft512_forward<true, 1, decltype(req), true>(x, sT, lane, R, req);
+        load_bk_block(bB, bk_rsrc, lane16, brow + kBlockBytes);          // block 1: output 0, high limb
+        __builtin_amdgcn_sched_barrier(0);
+        mac_row<FIRST>(s[0], x, bA);
+        __builtin_amdgcn_sched_barrier(0);
+        load_bk_block(bA, bk_rsrc, lane16, brow + 2 * kBlockBytes);      // block 2: output 1, low limb
+        __builtin_amdgcn_sched_barrier(0);
+        mac_row<FIRST>(s[1], x, bB);
+        __builtin_amdgcn_sched_barrier(0);
+        load_bk_block(bB, bk_rsrc, lane16, brow + 3 * kBlockBytes);      // block 3: output 1, high limb
+        __builtin_amdgcn_sched_barrier(0);
+        mac_row<FIRST>(s[2], x, bA);
+        mac_row<FIRST>(s[3], x, bB);
+    };
+    decompose(0);
+    digit_row(32 - BGBIT, 0, std::true_type{});
+    // one loop over the other 2L - 1 rows, as in k_cmux_x1 and for its reason
+#pragma unroll 1
+    for (int row = 1; row < 2 * L; row++) {
+        const int c = row >= L ? 1 : 0, q = row - c * L;
+        if (q == 0) decompose(1);
+        digit_row(32 - (q + 1) * BGBIT, row * kRowBytes, std::false_type{});
+    }
+    // opaque copies: the parent is read AGAIN below, and the children's and the base rows' addresses are formed only now
+    const int32_t* ppe = pp;
+    asm volatile("" : "+s"(ppe));
+    asm volatile("" : "+s"(po));
+    asm volatile("" : "+s"(pb));
+    const __amdgpu_buffer_rsrc_t rpe = row_resource(ppe);
+    const __amdgpu_buffer_rsrc_t ro0 = row_resource(po), ro1 = row_resource(po + 2 * kN);
+    const __amdgpu_buffer_rsrc_t rb0 = row_resource(pb), rb1 = row_resource(pb + 2 * kN);
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        fft512_inverse_pair<true>(s[2 * c], s[2 * c + 1], sT, lane, R);
+        uint32_t h0[8], h1[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            double unused = 0.0;  // nothing to watch: every rounded sum is below 2^37
+            h0[q] = round_coef(s[2 * c][q].x, untwist_gain(q), false, unused) + (round_coef(s[2 * c + 1][q].x, untwist_gain(q), false, unused) << 16);
+            h1[q] = round_coef(s[2 * c][q].y, untwist_gain(q), false, unused) + (round_coef(s[2 * c + 1][q].y, untwist_gain(q), false, unused) << 16);
+        }
+        if (add) {
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                const int j = c * kN + 64 * q;
+                const uint32_t p0 = row_word(rpe, lane4, j), p1 = row_word(rpe, lane4, j + kM);
+                const uint32_t b00 = row_word(rb0, lane4, j), b01 = row_word(rb0, lane4, j + kM);
+                const uint32_t b10 = row_word(rb1, lane4, j), b11 = row_word(rb1, lane4, j + kM);
+                __builtin_amdgcn_raw_buffer_store_b32(b00 + (p0 - h0[q]), ro0, lane4, j * 4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(b01 + (p1 - h1[q]), ro0, lane4, (j + kM) * 4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(b10 + h0[q], ro1, lane4, j * 4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(b11 + h1[q], ro1, lane4, (j + kM) * 4, 0);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                const int j = c * kN + 64 * q;
+                const uint32_t p0 = row_word(rpe, lane4, j), p1 = row_word(rpe, lane4, j + kM);
+                __builtin_amdgcn_raw_buffer_store_b32(p0 - h0[q], ro0, lane4, j * 4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(p1 - h1[q], ro0, lane4, (j + kM) * 4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(h0[q], ro1, lane4, j * 4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(h1[q], ro1, lane4, (j + kM) * 4, 0);
+            }
+        }
+    }
+}
+
+// ---- a scatter of depth 0: out_i = mem_i + v_i (mem null: v_i).  out == mem is sound: a word is read by the thread that stores it ----
+__global__ __launch_bounds__(256) void k_demux_add(const int32_t* __restrict__ values, const int32_t* mem, int32_t* out) {
+    const size_t at = (size_t)blockIdx.x * 2 * kN;
+    for (int q = threadIdx.x; q < 2 * kN; q += 256) out[at + q] = (int32_t)((uint32_t)values[at + q] + (mem ? (uint32_t)mem[at + q] : 0u));
+}
+
 // ---- a tree of depth 0: out_i = row 0 of its table ----
 __global__ __launch_bounds__(256) void k_cmux_copy(const int32_t* __restrict__ tables, int32_t n_tables, const int32_t* __restrict__ table_of,
                                                    int64_t item0, int32_t* __restrict__ out) {
@@ -277,6 +417,50 @@ int Cmux::launch_tree(const TgswSet& set, CmuxScratch& scratch, hipStream_t stre
         // the last level writes the caller's rows; the others alternate between the two scratch buffers
         R.dst = k == depth - 1 ? out : (k % 2 == 0 ? (int32_t*)scratch.a : (int32_t*)scratch.b);
         launch(set, stream, R);
+        src = R.dst;
+    }
+    return depth;
+}
+
+void Cmux::launch_demux(const TgswSet& set, hipStream_t stream, DemuxRows rows) {
+    check_owner(set);
+    if (rows.rows <= 0) return;
+    rows.n_set = (int32_t)set.n;
+    const unsigned grid = (unsigned)((rows.rows + kCmuxWaveRows - 1) / kCmuxWaveRows);
+    with_param_set(p_.l, [&](auto l, auto bgbit) {
+        hipLaunchKernelGGL((k_demux_x1<decltype(l)::value, decltype(bgbit)::value>), dim3(grid), dim3(64 * kCmuxWaveRows), 0, stream, rows,
+                           (const double2*)set.spectrum, (const double2*)tw_);
+    });
+}
+
+int Cmux::launch_scatter(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth,
+                         const int32_t* sel_of, const int32_t* values, const int32_t* mem, int32_t* out) {
+    check_owner(set);
+    if (items <= 0) return 0;
+    if (depth < 0 || depth > kCmuxMaxDepth) throw std::invalid_argument("lut_scatter: depth out of range");
+    if (depth == 0) {
+        hipLaunchKernelGGL(k_demux_add, dim3((unsigned)items), dim3(256), 0, stream, values, mem, out);
+        return 1;
+    }
+    const size_t row = (size_t)2 * kN;
+    const int64_t widest = items << (depth - 1);  // rows step depth - 2 writes
+    if ((depth >= 2 && scratch.a.items() < (size_t)widest * row) || (depth >= 3 && scratch.b.items() < (size_t)(widest / 2) * row))
+        throw std::invalid_argument("lut_scatter: piece larger than the reserved scratch");
+    const int32_t* src = values;
+    for (int32_t t = 0; t < depth; t++) {
+        DemuxRows R;
+        R.depth = depth;
+        R.step = t;
+        R.width = 1 << t;
+        R.rows = items * R.width;
+        R.item0 = item0;
+        R.sel_of = sel_of;
+        R.src = src;
+        const bool last = t == depth - 1;
+        // the last step writes the caller's rows over the memory; the others alternate so that step depth - 2 writes A
+        R.dst = last ? out : ((depth - 2 - t) % 2 == 0 ? (int32_t*)scratch.a : (int32_t*)scratch.b);
+        R.base = last ? mem : nullptr;
+        launch_demux(set, stream, R);
         src = R.dst;
     }
     return depth;

@@ -5,12 +5,17 @@
 //   k_cmux_x1        one CMux per wave: out = d0 + C_sel [.] (d1 - d0) on the two-limb spectrum
 //   k_cmux_copy      a tree of depth 0: out_i = tables[table_of[i]][0]
 //   k_tlwe_extract   coefficient j of a TLWE sample as an extracted LWE row
+//   k_demux_x1       one demux step per wave (section 3g): parent p -> hi = C_sel [.] p and lo = p - hi, the memory added on the last step
+//   k_demux_add      a scatter of depth 0: out_i = mem_i + v_i
 //
 // A tree call over `items` items of depth d runs level k = 0 .. d-1 as ONE launch of items x 2^(d-1-k) CMuxes.  Level 0 reads
 // the caller's tables and the last level writes the caller's output; the levels between go through two scratch buffers that
 // swap roles: A holds the output of levels 0, 2, 4 .., B of levels 1, 3, ...  A piece is a run of WHOLE items whose level-0
 // output stays within the cap, so A is items x 2^(d-1) rows and B half of that; a single item wider than the cap (d = 12 at a
 // cap below 2 048) is a piece of its own.  A flat call has no scratch; the same cap bounds the rows of one launch.
+// A scatter (lut_scatter) over `items` items of depth d is the same plan run the other way: step t = 0 .. d-1 is one launch of
+// items x 2^t parents writing items x 2^(t+1) rows; step d-1 writes the caller's output, step d-2 (items x 2^(d-1) rows) A,
+// step d-3 B, and so on backwards -- the tree's sizes, so cmux_plan(items, d, ...) is its cut unchanged.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -165,6 +165,13 @@ public:
     void lut_tree_device(const TgswSet& set, size_t count, int32_t depth, const int32_t* d_sel_of, const Torus32* d_tables, int32_t n_tables,
                          const int32_t* d_table_of, Torus32* d_out, EvalStats* stats);
     void tlwe_extract_device(size_t count, const Torus32* d_tlwe, const int32_t* d_coef_of, Torus32* d_u, EvalStats* stats);
+    // lut_scatter_device (include/ieache.h section 3g), the tree's partner: item i demultiplexes d_values[i] ([2][N]) by its
+    // selectors sel_of[i depth + k] (null: (i depth + k) mod n), most significant first, into 2^depth leaves -- the value at the
+    // encrypted index, encryptions of zero elsewhere -- and out[i][j] = mem[i][j] + leaf j (d_mem null: zeros), rows
+    // [count][2^depth][2][N].  Pieces, scratch, clamping, stats and refusals as for lut_tree_device (the same plan: cmux_plan.h
+    // for (count, depth)), except that d_out == d_mem exactly is accepted: the write is in place.
+    void lut_scatter_device(const TgswSet& set, size_t count, int32_t depth, const int32_t* d_sel_of, const Torus32* d_values, const Torus32* d_mem,
+                            Torus32* d_out, EvalStats* stats);
     // the plan such a call would follow under the options as they are (cmux_plan.h; depth < 0: a flat call of `count` rows):
     // pieces, items per piece, rows of scratch A, rows of scratch B
     void cmux_plan_figures(size_t count, int32_t depth, int64_t out[4]) const;

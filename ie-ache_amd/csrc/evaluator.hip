@@ -1044,6 +1044,42 @@ void Evaluator::lut_tree_device(const TgswSet& set, size_t count, int32_t depth,
     if (stats) stats->levels += depth;
 }
 
+// The scatter: the tree's pieces and scratch with the steps run the other way (Cmux::launch_scatter); the last step of a piece
+// adds the memory rows and may write over them.
+void Evaluator::lut_scatter_device(const TgswSet& set, size_t count, int32_t depth, const int32_t* d_sel_of, const Torus32* d_values,
+                                   const Torus32* d_mem, Torus32* d_out, EvalStats* stats) {
+    d_->cmux.check_owner(set);
+    if (depth < 0 || depth > kCmuxMaxDepth) throw std::invalid_argument("lut_scatter: depth must lie in 0 .. 12");
+    const size_t row = (size_t)2 * (size_t)p_.N, leaves = (size_t)1 << depth;
+    if (overlaps(d_out, count * leaves * row, {{d_values, count * row}, {d_sel_of, count * (size_t)depth}}) ||
+        (d_mem != d_out && overlaps(d_out, count * leaves * row, {{d_mem, count * leaves * row}})))
+        throw std::invalid_argument("lut_scatter: the output overlaps an input (only d_out == d_mem, the write in place, is accepted)");
+    begin_call();
+    if (count == 0) return;
+    if (!d_values || !d_out) throw std::invalid_argument("lut_scatter: null rows");
+    Lane& ln = d_->lane[0];
+    const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
+    d_->cmux.reserve(ln.cmux, pl);
+    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(false, stream_);
+    tall.mark();
+    for (int64_t i = 0; i < pl.pieces; i++) {
+        const int64_t i0 = cmux_piece_first(pl, i), cnt = cmux_piece_items(pl, (int64_t)count, i);
+        tbr.mark();
+        const int launches = d_->cmux.launch_scatter(set, ln.cmux, stream_, i0, cnt, depth, d_sel_of, d_values + (size_t)i0 * row,
+                                                     d_mem ? d_mem + (size_t)i0 * leaves * row : nullptr, d_out + (size_t)i0 * leaves * row);
+        tbr.mark();
+        HIP_CHECK(hipGetLastError());
+        if (stats) {
+            stats->blind_rotate_launches += launches;
+            stats->chunks++;
+        }
+    }
+    tall.mark();
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    add_times(stats, tall, tbr, tks);
+    if (stats) stats->levels += depth;
+}
+
 void Evaluator::tlwe_extract_device(size_t count, const Torus32* d_tlwe, const int32_t* d_coef_of, Torus32* d_u, EvalStats* stats) {
     if (overlaps(d_u, count * (size_t)extract_stride(), {{d_tlwe, count * (size_t)2 * (size_t)p_.N}, {d_coef_of, count}}))
         throw std::invalid_argument("tlwe_extract: the output overlaps an input");

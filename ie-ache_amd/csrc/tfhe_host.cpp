@@ -345,6 +345,33 @@ void lut_tree_reference(const Params& p, const Torus32* set, size_t n_set, size_
     }
 }
 
+void lut_scatter_reference(const Params& p, const Torus32* set, size_t n_set, size_t count, int32_t depth, const int32_t* sel_of,
+                           const Torus32* values, const Torus32* mem, Torus32* out) {
+    const size_t W = (size_t)2 * p.N, S = (size_t)p.kpl() * W, T = (size_t)1 << depth;
+    const int n_threads = host_threads();
+    (void)n_threads;
+    for (size_t i = 0; i < count; i++) {
+        std::vector<uint32_t> level(values + i * W, values + (i + 1) * W), next;
+        for (int32_t t = 0; t < depth; t++) {
+            const size_t w = (size_t)1 << t, at = i * (size_t)depth + (size_t)(depth - 1 - t);
+            const size_t sel = sel_of ? (size_t)sel_of[at] : at % n_set;
+            next.assign(2 * w * W, 0u);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(n_threads)
+            for (int64_t j = 0; j < (int64_t)w; j++) {
+                const uint32_t* parent = level.data() + (size_t)j * W;
+                uint32_t* lo = next.data() + 2 * (size_t)j * W;
+                uint32_t* hi = lo + W;  // zeros: the product alone
+                external_product_add(p, set + sel * S, parent, hi);
+                for (size_t c = 0; c < W; c++) lo[c] = parent[c] - hi[c];
+            }
+            level.swap(next);
+        }
+        const Torus32* base = mem ? mem + i * T * W : nullptr;
+        Torus32* dst = out + i * T * W;
+        for (size_t c = 0; c < T * W; c++) dst[c] = (Torus32)((base ? (uint32_t)base[c] : 0u) + level[c]);
+    }
+}
+
 void tlwe_extract_reference(const Params& p, size_t count, const Torus32* tlwe, const int32_t* coef_of, Torus32* u) {
     const int32_t N = p.N;
     for (size_t r = 0; r < count; r++) {

@@ -77,6 +77,11 @@ void cmux_reference(const Params& p, const Torus32* set, size_t n_set, size_t co
                     Torus32* out);
 void lut_tree_reference(const Params& p, const Torus32* set, size_t n_set, size_t count, int32_t depth, const int32_t* sel_of,
                         const Torus32* tables, const int32_t* table_of, Torus32* out);
+// lut_scatter_reference (section 3g): item i splits values[i] from the most significant selector down -- a row p at position j
+// becomes hi = C_k [.] p at 2 j + 1 and p - hi at 2 j -- and out[i][j] = mem[i][j] + leaf j (mem null: zeros),
+// [count][2^depth][2][N].  out may be mem itself.  Indices already checked by the caller.
+void lut_scatter_reference(const Params& p, const Torus32* set, size_t n_set, size_t count, int32_t depth, const int32_t* sel_of,
+                           const Torus32* values, const Torus32* mem, Torus32* out);
 
 // coefficient coef_of[r] (null: 0; checked by the caller) of tlwe [count][2][N] as extracted rows u [count][N+1]
 void tlwe_extract_reference(const Params& p, size_t count, const Torus32* tlwe, const int32_t* coef_of, Torus32* u);

@@ -192,6 +192,9 @@ def lib():
     L.ieache_cmux_device.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, sp]
     L.ieache_lut_tree.argtypes = [vp, vp, C.c_size_t, C.c_int32, i32p, i32p, C.c_int32, i32p, i32p, sp]
     L.ieache_lut_tree_device.argtypes = [vp, vp, C.c_size_t, C.c_int32, vp, vp, C.c_int32, vp, vp, sp]
+    L.ieache_lut_scatter.argtypes = [vp, vp, C.c_size_t, C.c_int32, i32p, i32p, i32p, i32p, sp]
+    L.ieache_lut_scatter_device.argtypes = [vp, vp, C.c_size_t, C.c_int32, vp, vp, vp, vp, sp]
+    L.ieache_lut_scatter_reference.argtypes = [pp, i32p, C.c_size_t, C.c_size_t, C.c_int32, i32p, i32p, i32p, i32p]
     L.ieache_tlwe_extract.argtypes = [vp, C.c_size_t, i32p, i32p, i32p, sp]
     L.ieache_tlwe_extract_device.argtypes = [vp, C.c_size_t, vp, vp, vp, sp]
     L.ieache_debug_cmux_plan.argtypes = [vp, C.c_size_t, C.c_int32, C.POINTER(C.c_int64)]
@@ -786,8 +789,45 @@ class Context:
         check(lib().ieache_lut_tree_device(self.h, tgsw.h, count, int(depth), C.c_void_p(d_sel_of or None), C.c_void_p(d_tables), int(n_tables),
                                            C.c_void_p(d_table_of or None), C.c_void_p(d_out), _stats_ref(stats)))
 
+    def lut_scatter(self, tgsw, values, depth, sel_of=None, mem=None, count=None, stats=None):
+        """The write at an encrypted index on host rows (include/ieache.h section 3g), lut_tree's partner: item i
+        demultiplexes values[i] ([count][2][N], or one row) by the selectors sel_of[i] ([count][depth], bit k of the index
+        first as for lut_tree; None: samples i depth + k mod n) and returns mem[i] + leaves ([count][2^depth][2][N]): values[i]
+        added at the encrypted index, encryptions of zero elsewhere.  mem None: zeros, the leaves themselves.  count: checked
+        against the rows of values where given."""
+        depth = int(depth)
+        values = np.ascontiguousarray(values, dtype=np.int32).reshape(-1, 2, self.params.N)
+        n = values.shape[0] if count is None else int(count)
+        of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(depth, 1))
+        mem = None if mem is None else np.ascontiguousarray(mem, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, self.params.N)
+        assert values.shape[0] == n and (of is None or depth < 1 or of.shape[0] == n) and (mem is None or mem.shape[0] == n)
+        out = np.zeros((n, 1 << max(depth, 0), 2, self.params.N), dtype=np.int32)
+        check(lib().ieache_lut_scatter(self.h, tgsw.h, n, depth, None if of is None else _i32(of), _i32(values), None if mem is None else _i32(mem),
+                                       _i32(out), _stats_ref(stats)))
+        return out
+
+    def lut_scatter_device(self, tgsw, count, depth, d_sel_of, d_values, d_mem, d_out, stats=None):
+        """Device pointers (ints; d_sel_of and d_mem may be None / 0): values [count][2][N], mem and out [count][2^depth][2][N]
+        packed; d_out == d_mem writes in place."""
+        check(lib().ieache_lut_scatter_device(self.h, tgsw.h, count, int(depth), C.c_void_p(d_sel_of or None), C.c_void_p(d_values),
+                                              C.c_void_p(d_mem or None), C.c_void_p(d_out), _stats_ref(stats)))
+
+    def lut_write(self, tgsw, mem, depth, new, sel_of=None):
+        """The replace write mem[i][addr_i] := new[i] on host arrays, addr_i the index item i's selectors encrypt: a read
+        (lut_tree with table_of = arange(count)), a wrapping subtraction and lut_scatter of the difference.  mem
+        [count][2^depth][2][N], new [count][2][N] -> the new memory.  The addressed slot ends at new plus the noise of a tree and a
+        scatter; every other slot gains a scatter's."""
+        depth = int(depth)
+        mem = np.ascontiguousarray(mem, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, self.params.N)
+        new = np.ascontiguousarray(new, dtype=np.int32).reshape(-1, 2, self.params.N)
+        count = mem.shape[0]
+        assert new.shape[0] == count
+        old = self.lut_tree(tgsw, mem, depth, sel_of=sel_of, table_of=np.arange(count, dtype=np.int32), count=count)
+        delta = ((new.astype(np.int64) - old.astype(np.int64)) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+        return self.lut_scatter(tgsw, delta, depth, sel_of=sel_of, mem=mem, count=count)
+
     def cmux_plan(self, count, depth=-1):
-        """How cmux() (depth < 0) or lut_tree() would cut such a call under the options as they are (csrc/cmux_plan.h):
+        """How cmux() (depth < 0) or lut_tree() / lut_scatter() would cut such a call under the options as they are (csrc/cmux_plan.h):
         dict(pieces, items_per_piece, scratch_a_rows, scratch_b_rows)."""
         out = (C.c_int64 * 4)()
         check(lib().ieache_debug_cmux_plan(self.h, count, int(depth), out))

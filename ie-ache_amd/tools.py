@@ -185,6 +185,22 @@ def lut_tree_reference(params, samples, tables, depth, sel_of=None, table_of=Non
     return out
 
 
+def lut_scatter_reference(params, samples, values, depth, sel_of=None, mem=None, count=None):
+    """CPU reference of Context.lut_scatter on raw arrays (ieache_lut_scatter_reference; any supported set), arguments as there."""
+    depth = int(depth)
+    kpl = (params.k + 1) * params.l
+    samples = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, kpl, 2, params.N)
+    values = np.ascontiguousarray(values, dtype=np.int32).reshape(-1, 2, params.N)
+    n = values.shape[0] if count is None else int(count)
+    of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(depth, 1))
+    mem = None if mem is None else np.ascontiguousarray(mem, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, params.N)
+    assert values.shape[0] == n and (of is None or depth < 1 or of.shape[0] == n) and (mem is None or mem.shape[0] == n)
+    out = np.zeros((n, 1 << max(depth, 0), 2, params.N), dtype=np.int32)
+    check(lib().ieache_lut_scatter_reference(C.byref(params), _i32(samples), samples.shape[0], n, depth, None if of is None else _i32(of),
+                                             _i32(values), None if mem is None else _i32(mem), _i32(out)))
+    return out
+
+
 def tlwe_extract_reference(params, tlwe, coef_of=None):
     """CPU reference of Context.tlwe_extract (ieache_tlwe_extract_reference): tlwe [count][2][N] -> [count][N+1]."""
     tlwe = np.ascontiguousarray(tlwe, dtype=np.int32).reshape(-1, 2, params.N)

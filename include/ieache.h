@@ -786,6 +786,36 @@ int ieache_tlwe_extract_device(ieache_ctx* ctx, size_t count, const int32_t* d_t
  * rows of scratch B}. */
 int ieache_debug_cmux_plan(const ieache_ctx* ctx, size_t count, int32_t depth, int64_t out[4]);
 
+/* 3g. The write at an encrypted index: the CMux demux tree, partner of ieache_lut_tree.  Conventions, sets, decomposition and
+ * exactness are those of 3f (integers mod 2^32; N = 1024, k = 1, (l, Bgbit) = (3, 7) or (2, 10) on the device).
+ *
+ * Item i has `depth` selectors C_0 .. C_{depth-1} (bit k of the index, least significant first, exactly as for the tree:
+ * sample sel_of[i depth + k]; sel_of == NULL: (i depth + k) mod n), a value v [2][N] and optionally a memory block
+ * mem [2^depth][2][N] of its own.  The demux runs from the most significant bit down: step t = 0 .. depth-1 uses selector
+ * k = depth-1-t, and every row p at position j of the step's 2^t rows becomes two:
+ *   hi = C_k [.] p  at position 2j + 1,     lo = p - hi  at position 2j.
+ * After `depth` steps the 2^depth leaves are v at the encrypted index and encryptions of zero elsewhere, each plus noise, and
+ *   out[j] = mem[j] + leaf[j];
+ * mem == NULL stands for zeros and returns the leaves themselves: the encrypted one-hot vector times v.  depth = 0 gives
+ * out[0] = mem[0] + v.  The leaves of an item always sum to v word for word.  One item costs 2^depth - 1 external products, as
+ * a lookup does.  A replace write mem[addr] := new is a read, a subtraction and a scatter: delta = new - lut_tree(mem), then
+ * scatter delta (the Python binding's Context.lut_write does that on host arrays).
+ *
+ * The device form accepts d_out == d_mem EXACTLY: the write is then in place (every word of the memory is read by the one
+ * lane that later stores it).  Any other overlap of the output with an input is refused.  Pieces and scratch are the tree's:
+ * whole items so that items 2^(depth-1) stays within "cmux_piece_rows", the two scratch buffers the context keeps, and
+ * ieache_debug_cmux_plan(count, depth) describes a scatter as it describes a tree.  Host forms check every index and name the
+ * first bad one and stage through rows the context keeps; device forms clamp.  IEACHE_EINVAL: depth outside
+ * 0 .. IEACHE_LUT_TREE_MAX_DEPTH, overlap, a set prepared on another context.  count == 0 is a no-op.  stats: bootstraps == 0,
+ * keyswitch_launches == 0, levels = depth, chunks = pieces, the kernel launches (pieces x max(depth, 1)) and their time in
+ * blind_rotate_launches and blind_rotate_ms.  Several items writing into ONE memory in a single call are not offered (take the
+ * leaves with mem == NULL and add them); there is no group form and no cloudd verb. */
+int ieache_lut_scatter(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* sel_of /*[count][depth] or NULL*/,
+                       const int32_t* values /*[count][2][N]*/, const int32_t* mem /*[count][2^depth][2][N] or NULL*/,
+                       int32_t* out /*[count][2^depth][2][N]*/, ieache_stats* stats);
+int ieache_lut_scatter_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* d_sel_of,
+                              const int32_t* d_values, const int32_t* d_mem, int32_t* d_out /* == d_mem: in place */, ieache_stats* stats);
+
 /* ------------------------------------------------------------------ *
  * 4. CPU tools around the path (no GPU): what Keygen/keygen.c:22-51,  *
  *    Client1/alice.c:116-191 and Output/verif.c:41-76 get from        *
@@ -842,6 +872,9 @@ int ieache_cmux_reference(const ieache_params* p, const int32_t* set, size_t n, 
                           const int32_t* d0, int32_t* out);
 int ieache_lut_tree_reference(const ieache_params* p, const int32_t* set, size_t n, size_t count, int32_t depth, const int32_t* sel_of,
                               const int32_t* tables, int32_t n_tables, const int32_t* table_of, int32_t* out);
+/* ... of ieache_lut_scatter (section 3g), arguments and refusals as for its host form; out may be mem itself ... */
+int ieache_lut_scatter_reference(const ieache_params* p, const int32_t* set, size_t n, size_t count, int32_t depth, const int32_t* sel_of,
+                                 const int32_t* values, const int32_t* mem, int32_t* out);
 /* ... and of ieache_tlwe_extract: tlwe [count][2][N] -> u [count][N+1]. */
 int ieache_tlwe_extract_reference(const ieache_params* p, size_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u);
 /* key files -> raw arrays (sizes from ieache_params; pass NULL to query params only) */
