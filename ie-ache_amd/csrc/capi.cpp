@@ -1100,6 +1100,91 @@ int ieache_lut_scatter(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, in
     });
 }
 
+// ---- the rotation by caller selectors and the coefficient-level lookup (section 3h) ----
+namespace {
+int check_rotate(int32_t steps, const char* who) {
+    if (steps < 0 || steps > IEACHE_ROTATE_MAX_STEPS) return fail(IEACHE_EINVAL, std::string(who) + ": steps must lie in 0 .. 64");
+    return 0;
+}
+int check_read(int32_t depth, int32_t steps, int32_t n_tables, int flags) {
+    if (depth < 0 || depth > IEACHE_LUT_TREE_MAX_DEPTH) return fail(IEACHE_EINVAL, "lut_read: depth must lie in 0 .. 12");
+    if (const int rc = check_rotate(steps, "lut_read")) return rc;
+    if (n_tables < 1) return fail(IEACHE_EINVAL, "lut_read: n_tables must be at least 1");
+    if (flags & ~IEACHE_LUT_READ_NO_KEYSWITCH) return fail(IEACHE_EINVAL, "lut_read: unknown flag");
+    return 0;
+}
+}  // namespace
+
+int ieache_tlwe_rotate_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t steps, const int32_t* d_sel_of,
+                              const int32_t* d_amount_of, const int32_t* d_in, int32_t* d_out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_tgsw(ctx, set)) return rc;
+        if (!d_in || !d_out) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_rotate(steps, "tlwe_rotate")) return rc;
+        require_device_pointers(count, {{d_sel_of, "d_sel_of", true}, {d_amount_of, "d_amount_of", true}, {d_in, "d_in"}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->tlwe_rotate_device(*set->set, count, steps, d_sel_of, d_amount_of, d_in, d_out, st); });
+    });
+}
+
+int ieache_tlwe_rotate(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t steps, const int32_t* sel_of, const int32_t* amount_of,
+                       const int32_t* in, int32_t* out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_tgsw(ctx, set)) return rc;
+        if (!in || !out) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_rotate(steps, "tlwe_rotate")) return rc;
+        if (const int rc = check_indices(sel_of, count * (size_t)steps, (int64_t)set->set->n, "tlwe_rotate: sel_of")) return rc;
+        if (const int rc = check_indices(amount_of, (size_t)steps, 2 * (int64_t)ctx->eval->params().N, "tlwe_rotate: amount_of")) return rc;
+        HostCall h(ctx, count);
+        const size_t sample = (size_t)2 * (size_t)h.p.N;
+        StagedRows din(h.ev, kStageTlweA, count, sample, in, sample), dsel = h.words(kStagePolyOf, sel_of, count * (size_t)steps);
+        StagedRows dam = h.words(kStageBias, amount_of, (size_t)steps), dout(h.ev, kStageOut, count, sample);
+        with_stats(stats, [&](EvalStats* st) { h.ev.tlwe_rotate_device(*set->set, count, steps, dsel.p, dam.p, din.p, dout.p, st); });
+        dout.download(out, sample);
+        return 0;
+    });
+}
+
+int ieache_lut_read_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of,
+                           const int32_t* d_amount_of, const int32_t* d_tables, int32_t n_tables, const int32_t* d_table_of, int32_t coef, int flags,
+                           int32_t* d_out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_tgsw(ctx, set)) return rc;
+        if (!d_tables || !d_out) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_read(depth, steps, n_tables, flags)) return rc;
+        require_device_pointers(count, {{d_sel_of, "d_sel_of", true}, {d_amount_of, "d_amount_of", true}, {d_tables, "d_tables"},
+                                        {d_table_of, "d_table_of", true}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) {
+            ctx->eval->lut_read_device(*set->set, count, depth, steps, d_sel_of, d_amount_of, d_tables, n_tables, d_table_of, coef, flags, d_out, st);
+        });
+    });
+}
+
+int ieache_lut_read(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, const int32_t* sel_of,
+                    const int32_t* amount_of, const int32_t* tables, int32_t n_tables, const int32_t* table_of, int32_t coef, int flags, int32_t* out,
+                    ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_tgsw(ctx, set)) return rc;
+        if (!tables || !out) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_read(depth, steps, n_tables, flags)) return rc;
+        const int64_t N = ctx->eval->params().N;
+        if (const int rc = check_indices(sel_of, count * (size_t)(depth + steps), (int64_t)set->set->n, "lut_read: sel_of")) return rc;
+        if (const int rc = check_indices(amount_of, (size_t)steps, 2 * N, "lut_read: amount_of")) return rc;
+        if (const int rc = check_indices(table_of, count, n_tables, "lut_read: table_of")) return rc;
+        if (const int rc = check_indices(&coef, 1, N, "lut_read: coef")) return rc;
+        HostCall h(ctx, count);
+        const size_t sample = (size_t)2 * (size_t)h.p.N;
+        const bool woks = (flags & IEACHE_LUT_READ_NO_KEYSWITCH) != 0;
+        StagedRows dt(h.ev, kStageTestPolys, (size_t)n_tables << depth, sample, tables, sample);
+        StagedRows dsel = h.words(kStagePolyOf, sel_of, count * (size_t)(depth + steps)), dof = h.words(kStageBias, table_of, count);
+        StagedRows dam = h.words(kStageFactors, amount_of, (size_t)steps), dout = h.results(count, woks);
+        with_stats(stats, [&](EvalStats* st) {
+            h.ev.lut_read_device(*set->set, count, depth, steps, dsel.p, dam.p, dt.p, n_tables, dof.p, coef, flags, dout.p, st);
+        });
+        h.download(dout, out, woks);
+        return 0;
+    });
+}
+
 int ieache_tlwe_extract_device(ieache_ctx* ctx, size_t count, const int32_t* d_tlwe, const int32_t* d_coef_of, int32_t* d_u, ieache_stats* stats) {
     return guarded([&] {
         if (!ctx || !d_tlwe || !d_u) return fail(IEACHE_EINVAL, "null argument");
@@ -1574,6 +1659,41 @@ int ieache_lut_scatter_reference(const ieache_params* p, const int32_t* set, siz
         if (const int rc = check_scatter(depth)) return rc;
         if (const int rc = check_indices(sel_of, count * (size_t)depth, (int64_t)n, "lut_scatter: sel_of")) return rc;
         lut_scatter_reference(pp, set, n, count, depth, sel_of, values, mem, out);
+        return 0;
+    });
+}
+
+int ieache_tlwe_rotate_reference(const ieache_params* p, const int32_t* set, size_t n, size_t count, int32_t steps, const int32_t* sel_of,
+                                 const int32_t* amount_of, const int32_t* in, int32_t* out) {
+    return guarded([&] {
+        if (!p || !set || (count && (!in || !out))) return fail(IEACHE_EINVAL, "null argument");
+        const Params pp = to_params(*p);
+        if (!pp.supported()) return fail(IEACHE_EINVAL, "tlwe_rotate_reference: unsupported TFHE parameter set");
+        if (n < 1) return fail(IEACHE_EINVAL, "tlwe_rotate_reference: no samples");
+        if (const int rc = check_rotate(steps, "tlwe_rotate")) return rc;
+        if (const int rc = check_indices(sel_of, count * (size_t)steps, (int64_t)n, "tlwe_rotate: sel_of")) return rc;
+        if (const int rc = check_indices(amount_of, (size_t)steps, 2 * (int64_t)pp.N, "tlwe_rotate: amount_of")) return rc;
+        tlwe_rotate_reference(pp, set, n, count, steps, sel_of, amount_of, in, out);
+        return 0;
+    });
+}
+
+int ieache_lut_read_reference(const ieache_params* p, const int32_t* set, size_t n, const int32_t* ksk, size_t count, int32_t depth, int32_t steps,
+                              const int32_t* sel_of, const int32_t* amount_of, const int32_t* tables, int32_t n_tables, const int32_t* table_of,
+                              int32_t coef, int flags, int32_t* out) {
+    return guarded([&] {
+        if (!p || !set || (count && (!tables || !out))) return fail(IEACHE_EINVAL, "null argument");
+        const Params pp = to_params(*p);
+        if (!pp.supported()) return fail(IEACHE_EINVAL, "lut_read_reference: unsupported TFHE parameter set");
+        if (n < 1) return fail(IEACHE_EINVAL, "lut_read_reference: no samples");
+        if (const int rc = check_read(depth, steps, n_tables, flags)) return rc;
+        const bool woks = (flags & IEACHE_LUT_READ_NO_KEYSWITCH) != 0;
+        if (!woks && !ksk) return fail(IEACHE_EINVAL, "lut_read_reference: the key switch needs ksk");
+        if (const int rc = check_indices(sel_of, count * (size_t)(depth + steps), (int64_t)n, "lut_read: sel_of")) return rc;
+        if (const int rc = check_indices(amount_of, (size_t)steps, 2 * (int64_t)pp.N, "lut_read: amount_of")) return rc;
+        if (const int rc = check_indices(table_of, count, n_tables, "lut_read: table_of")) return rc;
+        if (const int rc = check_indices(&coef, 1, pp.N, "lut_read: coef")) return rc;
+        lut_read_reference(pp, set, n, woks ? nullptr : ksk, count, depth, steps, sel_of, amount_of, tables, table_of, coef, out);
         return 0;
     });
 }

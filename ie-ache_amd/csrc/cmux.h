@@ -1,6 +1,7 @@
 // The CMux on TGSW samples the caller supplies, the CMux-tree lookup built from it and the extraction of a coefficient of a
 // TLWE sample (include/ieache.h section 3f), and the scatter that writes at an encrypted index (section 3g), the one door: the kernels, the spectrum form of a prepared set, the twiddle table
-// and the scratch of a tree are behind this object; how a call is cut is cmux_plan.h.  Kernels: cmux.hip.
+// and the scratch of a tree are behind this object; how a call is cut is cmux_plan.h.  Kernels: cmux.hip, and rotate.hip for
+// the rotation by caller selectors and the coefficient-level lookup (section 3h).
 #pragma once
 #include <cstdint>
 
@@ -60,9 +61,29 @@ struct DemuxRows {
     int32_t depth = 1, step = 0, width = 1;
 };
 
-// Scratch of a tree on one stream: the two buffers whose roles swap from level to level.
+// Where the rows of one launch of k_rotate_x1 live (include/ieache.h section 3h): row r of the piece is rotated by its
+// selectors in `steps` steps inside the launch -- a rule again, everything wave-uniform.
+//   in = src + r, out = dst + r (dst == src is allowed: k_rotate_x1 says why);
+//   selector of step t: sel_of[(item0 + r) sel_stride + t] (null: that index mod n_set; explicit: clamped into the set);
+//   amount of step t: amount_of[t] masked to 2N - 1 (null: 2N - 2^t, which is 0 from t = 11 on).
+// sel_stride is `steps` for a rotation of its own and depth + steps inside a coefficient-level lookup.
+struct RotateRows {
+    const int32_t* src = nullptr;
+    int32_t* dst = nullptr;
+    const int32_t* sel_of = nullptr;
+    const int32_t* amount_of = nullptr;
+    int64_t rows = 0;
+    int64_t item0 = 0;                  // first row of the piece within the call (src and dst are already offset)
+    int32_t n_set = 1;
+    int32_t steps = 0, sel_stride = 0;  // steps in 0 .. kRotateMaxSteps
+};
+
+// Scratch of a tree on one stream: the two buffers whose roles swap from level to level.  A coefficient-level lookup
+// (lut_read) adds the rows its trees select, which the rotation turns in place, and the indices its launches read: the tree's
+// selectors [items][depth] taken out of the call's [count][depth + steps], then the public coefficient once per item.
 struct CmuxScratch {
     dev::DeviceBuffer<int32_t> a, b;
+    dev::DeviceBuffer<int32_t> rows, idx;
 };
 
 // One per evaluator.  All methods expect the evaluator's device to be current.
@@ -90,6 +111,16 @@ struct Cmux {
     // the tree's (cmux_plan.h).  Returns the kernel launches issued (depth, or 1 for the add of depth 0).
     int launch_scatter(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth,
                        const int32_t* sel_of, const int32_t* values, const int32_t* mem, int32_t* out);
+    // one launch of `rows.rows` rotations, all `rows.steps` steps of a row inside it (rotate.hip); no scratch
+    void launch_rotate(const TgswSet& set, hipStream_t stream, RotateRows rows);
+    // a coefficient-level lookup (lut_read): besides the tree's buffers, the selected rows and the indices of the largest piece
+    void reserve_read(CmuxScratch& scratch, const CmuxPlan& pl, int32_t depth);
+    // one piece of a lookup up to the extraction: the tree by selectors steps .. steps + depth - 1 of each item into
+    // scratch.rows, the rotation of those rows in place by selectors 0 .. steps - 1, coefficient `coef` (clamped into [0, N))
+    // of each as an extracted row u [items][stride].  Returns the kernel launches issued.
+    int launch_read(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, int32_t steps,
+                    const int32_t* sel_of, const int32_t* amount_of, const int32_t* tables, int32_t n_tables, const int32_t* table_of, int32_t coef,
+                    int32_t* u, int32_t stride);
     // coefficient coef_of[i] (null: 0; clamped into [0, N)) of tlwe [count][2][N] -> u [count][stride], N + 1 words written.
     // Any supported parameter set.
     void launch_extract(hipStream_t stream, int64_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u, int32_t stride);

@@ -7,6 +7,8 @@
 //   k_tlwe_extract   coefficient j of a TLWE sample as an extracted LWE row
 //   k_demux_x1       one demux step per wave (section 3g): parent p -> hi = C_sel [.] p and lo = p - hi, the memory added on the last step
 //   k_demux_add      a scatter of depth 0: out_i = mem_i + v_i
+//   k_rotate_x1      (rotate.hip, section 3h) one row per wave, every step inside the launch: acc += C_t [.] (X^a_t acc - acc)
+//   k_read_indices   (rotate.hip) a lookup's tree selectors and its public coefficient as the arrays the two kernels above read
 //
 // A tree call over `items` items of depth d runs level k = 0 .. d-1 as ONE launch of items x 2^(d-1-k) CMuxes.  Level 0 reads
 // the caller's tables and the last level writes the caller's output; the levels between go through two scratch buffers that
@@ -16,6 +18,8 @@
 // A scatter (lut_scatter) over `items` items of depth d is the same plan run the other way: step t = 0 .. d-1 is one launch of
 // items x 2^t parents writing items x 2^(t+1) rows; step d-1 writes the caller's output, step d-2 (items x 2^(d-1) rows) A,
 // step d-3 B, and so on backwards -- the tree's sizes, so cmux_plan(items, d, ...) is its cut unchanged.
+// A rotation (tlwe_rotate) is a flat call: rows = items, one launch per piece whatever the number of steps, no scratch.  A
+// coefficient-level lookup (lut_read) is cut as its tree is, cmux_plan(items, d, ...), and keeps one selected row per item.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -24,6 +28,7 @@ namespace ieache {
 
 constexpr int32_t kCmuxMaxDepth = 12;       // IEACHE_LUT_TREE_MAX_DEPTH: a table of 4 096 samples (32 MB at N = 1024) per item
 constexpr int32_t kCmuxWaveRows = 4;        // rows (= waves) per workgroup of k_cmux_x1
+constexpr int32_t kRotateMaxSteps = 64;     // IEACHE_ROTATE_MAX_STEPS: what one lane-held vector of amounts and selectors covers
 // Rows of a piece at most: 8 192 rows of [2][1024] int32 are 64 MB of scratch A and 32 MB of B, which a depth-10 tree over 16
 // items or a depth-12 tree over 4 fills; a launch of 8 192 waves is 4 rounds of the 2 048 resident on 256 CUs, so the ragged
 // end of a piece costs little.

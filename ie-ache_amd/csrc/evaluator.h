@@ -172,6 +172,23 @@ public:
     // for (count, depth)), except that d_out == d_mem exactly is accepted: the write is in place.
     void lut_scatter_device(const TgswSet& set, size_t count, int32_t depth, const int32_t* d_sel_of, const Torus32* d_values, const Torus32* d_mem,
                             Torus32* d_out, EvalStats* stats);
+    // tlwe_rotate_device (include/ieache.h section 3h): row i goes through acc <- acc + C_t [.] (X^(a_t) acc - acc) for
+    // t = 0 .. steps-1, C_t = sample sel_of[i steps + t] (null: (i steps + t) mod n), a_t = d_amount_of[t] masked to 2N - 1
+    // (null: 2N - 2^t).  The flat call's pieces, ONE launch per piece with every step inside it, no scratch; d_out == d_in
+    // exactly is accepted.  stats: levels = steps, otherwise as cmux_device.  std::invalid_argument for steps outside
+    // 0 .. kRotateMaxSteps, any other overlap, a set of another evaluator.
+    // lut_read_device: the vertical-packing lookup -- lut_tree_device by selectors steps .. steps+depth-1 of each item's
+    // depth + steps, the rotation of the ONE selected row per item by selectors 0 .. steps-1, coefficient `coef` (clamped into
+    // [0, N)) extracted and key-switched, all on the evaluator's stream: d_out [count][lwe_stride], or with kLutReadNoKeyswitch
+    // the extracted rows [count][extract_stride()].  The tree's plan for (count, depth); the selected rows, the indices and the
+    // key switch's scratch are reserved before the first piece.  stats: levels = depth + steps, chunks = pieces, a key-switch
+    // launch per run of at most `chunk` rows.
+    static constexpr int32_t kLutReadNoKeyswitch = 1;
+    void tlwe_rotate_device(const TgswSet& set, size_t count, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of, const Torus32* d_in,
+                            Torus32* d_out, EvalStats* stats);
+    void lut_read_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of,
+                         const Torus32* d_tables, int32_t n_tables, const int32_t* d_table_of, int32_t coef, int32_t flags, Torus32* d_out,
+                         EvalStats* stats);
     // the plan such a call would follow under the options as they are (cmux_plan.h; depth < 0: a flat call of `count` rows):
     // pieces, items per piece, rows of scratch A, rows of scratch B
     void cmux_plan_figures(size_t count, int32_t depth, int64_t out[4]) const;

@@ -1080,6 +1080,105 @@ void Evaluator::lut_scatter_device(const TgswSet& set, size_t count, int32_t dep
     if (stats) stats->levels += depth;
 }
 
+// The rotation by caller selectors: the flat CMux's pieces, one launch each whatever the number of steps; no scratch.
+void Evaluator::tlwe_rotate_device(const TgswSet& set, size_t count, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of,
+                                   const Torus32* d_in, Torus32* d_out, EvalStats* stats) {
+    d_->cmux.check_owner(set);
+    if (steps < 0 || steps > kRotateMaxSteps) throw std::invalid_argument("tlwe_rotate: steps must lie in 0 .. 64");
+    const size_t row = (size_t)2 * (size_t)p_.N;
+    if (overlaps(d_out, count * row, {{d_sel_of, count * (size_t)steps}, {d_amount_of, (size_t)steps}}) ||
+        (d_in != d_out && overlaps(d_out, count * row, {{d_in, count * row}})))
+        throw std::invalid_argument("tlwe_rotate: the output overlaps an input (only d_out == d_in, the rotation in place, is accepted)");
+    begin_call();
+    if (count == 0) return;
+    if (!d_in || !d_out) throw std::invalid_argument("tlwe_rotate: null rows");
+    const CmuxPlan pl = cmux_plan((int64_t)count, -1, d_->opt.cmux_piece_rows);
+    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(false, stream_);
+    tall.mark();
+    for (int64_t i = 0; i < pl.pieces; i++) {
+        const int64_t r0 = cmux_piece_first(pl, i);
+        RotateRows R;
+        R.rows = cmux_piece_items(pl, (int64_t)count, i);
+        R.src = d_in + (size_t)r0 * row;
+        R.dst = d_out + (size_t)r0 * row;
+        R.sel_of = d_sel_of;
+        R.amount_of = d_amount_of;
+        R.item0 = r0;
+        R.steps = R.sel_stride = steps;
+        tbr.mark();
+        d_->cmux.launch_rotate(set, stream_, R);
+        tbr.mark();
+        HIP_CHECK(hipGetLastError());
+        if (stats) {
+            stats->blind_rotate_launches++;
+            stats->chunks++;
+        }
+    }
+    tall.mark();
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    add_times(stats, tall, tbr, tks);
+    if (stats) stats->levels += steps;
+}
+
+// The coefficient-level lookup: the tree's pieces; per piece the tree into the rows the lane keeps, their rotation in place, the
+// extraction (into the caller's rows, or the lane's for the key switch) and the key switch in runs of at most a chunk.
+// Everything is reserved before the first piece.
+void Evaluator::lut_read_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of,
+                                const Torus32* d_tables, int32_t n_tables, const int32_t* d_table_of, int32_t coef, int32_t flags, Torus32* d_out,
+                                EvalStats* stats) {
+    d_->cmux.check_owner(set);
+    if (depth < 0 || depth > kCmuxMaxDepth) throw std::invalid_argument("lut_read: depth must lie in 0 .. 12");
+    if (steps < 0 || steps > kRotateMaxSteps) throw std::invalid_argument("lut_read: steps must lie in 0 .. 64");
+    if (n_tables < 1) throw std::invalid_argument("lut_read: n_tables must be at least 1");
+    if (flags & ~kLutReadNoKeyswitch) throw std::invalid_argument("lut_read: unknown flag");
+    const bool woks = (flags & kLutReadNoKeyswitch) != 0;
+    const size_t row = (size_t)2 * (size_t)p_.N, out_stride = (size_t)(woks ? extract_stride() : d_->K.stride);
+    if (overlaps(d_out, count * out_stride,
+                 {{d_tables, ((size_t)n_tables << depth) * row}, {d_sel_of, count * (size_t)(depth + steps)}, {d_amount_of, (size_t)steps}, {d_table_of, count}}))
+        throw std::invalid_argument("lut_read: the output overlaps an input");
+    begin_call();
+    if (count == 0) return;
+    if (!d_tables || !d_out) throw std::invalid_argument("lut_read: null rows");
+    Lane& ln = d_->lane[0];
+    const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
+    d_->cmux.reserve_read(ln.cmux, pl, depth);
+    const int64_t ks_piece = std::min<int64_t>(pl.items_per_piece, (int64_t)d_->opt.chunk);
+    if (!woks) {
+        ln.ext.reserve_exact((size_t)pl.items_per_piece, d_->ext_row_bytes());
+        d_->ks.reserve(ln.ks, ks_piece, d_->opt, d_->force_generic_ks);
+    }
+    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(stats != nullptr && !woks, stream_);
+    tall.mark();
+    WorkDesc W{};
+    W.flat_out = d_out;
+    W.flat_type = kFlatRaw;
+    for (int64_t i = 0; i < pl.pieces; i++) {
+        const int64_t i0 = cmux_piece_first(pl, i), cnt = cmux_piece_items(pl, (int64_t)count, i);
+        Torus32* u = woks ? d_out + (size_t)i0 * out_stride : (Torus32*)ln.ext;
+        tbr.mark();
+        const int launches = d_->cmux.launch_read(set, ln.cmux, stream_, i0, cnt, depth, steps, d_sel_of, d_amount_of, d_tables, n_tables, d_table_of, coef,
+                                                  u, extract_stride());
+        tbr.mark();
+        HIP_CHECK(hipGetLastError());
+        if (stats) {
+            stats->blind_rotate_launches += launches;
+            stats->chunks++;
+        }
+        for (int64_t done = 0; !woks && done < cnt; done += ks_piece) {
+            const int64_t run = std::min<int64_t>(ks_piece, cnt - done);
+            tks.mark();
+            launch_keyswitch(d_, ln, rows_desc(W, i0 + done), run, u + (size_t)done * (size_t)extract_stride(), nullptr);
+            tks.mark();
+            HIP_CHECK(hipGetLastError());
+            if (stats) stats->keyswitch_launches++;
+        }
+    }
+    tall.mark();
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    add_times(stats, tall, tbr, tks);
+    if (stats) stats->levels += depth + steps;
+}
+
 void Evaluator::tlwe_extract_device(size_t count, const Torus32* d_tlwe, const int32_t* d_coef_of, Torus32* d_u, EvalStats* stats) {
     if (overlaps(d_u, count * (size_t)extract_stride(), {{d_tlwe, count * (size_t)2 * (size_t)p_.N}, {d_coef_of, count}}))
         throw std::invalid_argument("tlwe_extract: the output overlaps an input");

@@ -1,0 +1,251 @@
+// The rotation of a TLWE sample by an encrypted amount (include/ieache.h section 3h): for t = 0 .. steps - 1
+//   acc <- acc + C_t [.] (X^(a_t) acc - acc),
+// the blind rotation's own step with the selector a TGSW sample of the caller's set instead of BK_i and the amount public.  It
+// is the last stage of vertical packing: after a CMux tree has chosen one of 2^d samples, this brings one of its N coefficients
+// to a public position.  k_rotate_x1 is k_blind_rotate_x1 (blind_rotate_w64.hip) with the key block chosen per row and step;
+// built from the pieces of br_step.h and fft512.h, no kernel of the blind rotation or of cmux.hip is touched.
+// N = 1024, k = 1 and libtfhe's two (l, Bgbit), as br_supported() says.
+#include "cmux.h"
+
+#include <stdexcept>
+#include <type_traits>
+
+#include "blind_rotate_w64.h"
+// fft512.h defines the kernel that builds the twiddle table; Cmux::prepare (cmux.hip) launches it, nothing here does
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wunused-function"
+#include "br_step.h"
+#pragma clang diagnostic pop
+
+namespace ieache {
+
+using namespace dev;
+using namespace w64;
+
+namespace {
+
+// ---- one row per wave, every step of it inside the launch ----
+// What stays as in k_blind_rotate_x1: one wave owns a row, G = 4 rows share a workgroup for the twiddle table only (one workgroup
+// barrier, after the table is in LDS), the accumulator [2][1024] stands first in LDS on a 4 KiB boundary so that the rotated
+// decomposition addresses it with one v_and_or of a per-step lane value, 2L forward transforms of the digits, 8L row products
+// on the two-limb spectrum into four sums, two interleaved pairs of inverse transforms, the limbs recombined as
+// lo + (hi << 16), the wavefront-scope ds_add update and wave_sync, and the loop over the steps.  Every rounded sum stays
+// below 2^37 of the 2^53 an FP64 mantissa holds, so the words are exact for ANY caller words: no guard, no audit.
+// What differs:
+//   * the key block is chosen per row AND per step.  Lane t holds step t's amount (11 bits) and selector index (below 2^20, what
+//     a set may hold) in ONE register, fetched once ahead of the loop like the blind rotation's amounts and read back per step
+//     with v_readlane: the step loop has no register to spare for a second vector;
+//   * the selected sample goes into the buffer resource's BASE, rebuilt per step with num_records = one sample's bytes, as in
+//     k_cmux_x1: a set may hold 2^20 samples of 192 KB, which the 32-bit scalar offset that addresses BK_i cannot reach.  The rows
+//     of the sample go into the scalar offset.  Nothing past the selected sample can be touched whatever the indices hold: an
+//     explicit index is clamped into the set, an implied one taken mod n_set, an amount masked to 2N - 1;
+//   * the amounts come from the call's shared [steps] array (null: 2N - 2^t, which brings coefficient sum b_t 2^t to position 0);
+//   * the accumulator is loaded from src + r and stored to dst + r after the last step.
+// IN PLACE (dst == src) is sound: the wave copies its WHOLE row into LDS (the sixteen 16-byte loads per lane below, then
+// wave_sync) before the step loop starts, nothing in the loop reads global memory but the set and nothing in it writes
+// global memory at all, and the stores after the loop write row r only -- a row no other wave of the launch reads or writes
+// (rows are disjoint between waves).  So every load of a row precedes every store to it, in one wave's program order.
+// Everything that selects memory is wave-uniform scalar arithmetic; there are no pointer tables; stores are vector stores.
+// dynamic LDS as k_blind_rotate_x1: acc [4][2][1024] int32 | sT [4][kTile] double2 | tw [kTwElems] double2   (78 848 B -> 2 per CU)
+template <int L, int BGBIT, int G = kCmuxWaveRows>
+__global__ __launch_bounds__(64 * G, 2) void k_rotate_x1(RotateRows A, const double2* __restrict__ bkf, const double2* __restrict__ gtw) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    int32_t* acc_all = reinterpret_cast<int32_t*>(smem);
+    double2* sT_all = reinterpret_cast<double2*>(smem + (size_t)G * 2 * kN * 4);
+    double2* sTw = sT_all + G * kTile;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    double2* sT = sT_all + wave * kTile;
+    int32_t* acc = acc_all + wave * 2 * kN;
+    const int64_t r = (int64_t)blockIdx.x * G + wave;
+    load_twiddles(sTw, gtw, tid, 64 * G);
+    __syncthreads();  // the only workgroup barrier
+    if (r >= A.rows) return;
+    const LaneRoots R = make_roots(sTw, lane);
+    {
+        const int4* src = reinterpret_cast<const int4*>(A.src + (size_t)r * 2 * kN);
+        int4* dst = reinterpret_cast<int4*>(acc);
+#pragma unroll
+        for (int q = 0; q < 8; q++) dst[64 * q + lane] = src[64 * q + lane];
+    }
+    wave_sync();
+
+    // lane t: (selector << 11) | amount of step t; amount 0 beyond the last step
+    int32_t my_step = 0;
+    if (lane < A.steps) {
+        const int64_t at = (A.item0 + r) * A.sel_stride + lane;
+        int64_t sel;
+        if (A.sel_of == nullptr) {
+            sel = at % A.n_set;
+        } else {
+            sel = (int64_t)A.sel_of[at];
+            sel = sel < 0 ? 0 : (sel >= A.n_set ? A.n_set - 1 : sel);
+        }
+        const int32_t a = A.amount_of ? A.amount_of[lane] : (lane < 11 ? 2 * kN - (1 << lane) : 0);
+        my_step = ((int32_t)sel << 11) | (a & (2 * kN - 1));
+    }
+
+    const uint32_t dec_offset = decomposition_offset<L, BGBIT>();
+    constexpr int kBlockBytes = kM * (int)sizeof(double2), kRowBytes = 4 * kBlockBytes, kStepBytes = 2 * L * kRowBytes;
+    const int lane16 = bk_lane_offset(lane);
+    const unsigned char* accb = reinterpret_cast<const unsigned char*>(acc_all);  // LDS offset 0 of the workgroup
+    const uint32_t pb0 = (uint32_t)wave * (2 * kN * 4);                            // this row's polynomial 0; polynomial 1 at + 4096
+
+#pragma unroll 1
+    for (int32_t t = 0; t < A.steps; t++) {
+        const int32_t both = __builtin_amdgcn_readlane(my_step, t);
+        const int32_t a = both & (2 * kN - 1);
+        if (a == 0) continue;  // wave-uniform; exact arithmetic makes the step a no-op
+        // the resource covers the selected sample only: its rows [2L][q = 2 c + limb][8][64] double2
+        const __amdgpu_buffer_rsrc_t bk_rsrc = bk_resource(bkf + (size_t)(both >> 11) * (kStepBytes / sizeof(double2)), 1, kStepBytes);
+        double2 s[4][8];
+        uint32_t v0[8], v1[8];
+        // byte offset of coefficient (lane - a) in the 2N-ring [acc, -acc]: bits 2..11 address, bit 12 = negate
+        const uint32_t jb4 = ((uint32_t)(lane - a) & (2 * kN - 1)) << 2;
+        auto decompose = [&](const uint32_t pb, const uint32_t jb) {
+            const int32_t* accp = reinterpret_cast<const int32_t*>(accb + pb);
+            decompose_rotated(v0, v1, accb, accp, pb, jb, lane, dec_offset);
+        };
+        auto digit_row = [&](const int sh, const int brow, auto first) {
+            constexpr bool FIRST = decltype(first)::value;
+            double2 x[8], bA[8], bB[8];
+            digits_to_double2<BGBIT>(x, v0, v1, sh);
+            __builtin_amdgcn_sched_barrier(0);
+            auto req = [&]() { load_bk_block(bA, bk_rsrc, lane16, brow); };  // block 0: output 0, low limb
+            fft512_forward<true, 1, decltype(req), true>(x, sT, lane, R, req);
+            load_bk_block(bB, bk_rsrc, lane16, brow + kBlockBytes);          // block 1: output 0, high limb
+            __builtin_amdgcn_sched_barrier(0);
+            mac_row<FIRST>(s[0], x, bA);
+            __builtin_amdgcn_sched_barrier(0);
+            load_bk_block(bA, bk_rsrc, lane16, brow + 2 * kBlockBytes);      // block 2: output 1, low limb
+            __builtin_amdgcn_sched_barrier(0);
+            mac_row<FIRST>(s[1], x, bB);
+            __builtin_amdgcn_sched_barrier(0);
+            load_bk_block(bB, bk_rsrc, lane16, brow + 3 * kBlockBytes);      // block 3: output 1, high limb
+            __builtin_amdgcn_sched_barrier(0);
+            mac_row<FIRST>(s[2], x, bA);
+            mac_row<FIRST>(s[3], x, bB);
+        };
+        decompose(pb0, jb4);
+        digit_row(32 - BGBIT, 0, std::true_type{});
+#pragma unroll 1
+        for (int row = 1; row < L; row++) digit_row(32 - (row + 1) * BGBIT, row * kRowBytes, std::false_type{});
+        // opaque copy, as in k_blind_rotate_x1: the second decomposition's addresses and sign masks are recomputed, not kept
+        uint32_t jb4b = jb4;
+        asm volatile("" : "+v"(jb4b));
+        decompose(pb0 + 4096u, jb4b);
+#pragma unroll 1
+        for (int row = L; row < 2 * L; row++) digit_row(32 - (row - L + 1) * BGBIT, row * kRowBytes, std::false_type{});
+        // back to coefficients: s[2 c] / s[2 c + 1] hold the low / high limb sums of output polynomial c
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            fft512_inverse_pair<true>(s[2 * c], s[2 * c + 1], sT, lane, R);
+            uint32_t* accc = reinterpret_cast<uint32_t*>(acc) + c * kN;
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                double unused = 0.0;  // nothing to watch: every rounded sum is below 2^37
+                const uint32_t d0 = round_coef(s[2 * c][q].x, untwist_gain(q), false, unused) + (round_coef(s[2 * c + 1][q].x, untwist_gain(q), false, unused) << 16);
+                const uint32_t d1 = round_coef(s[2 * c][q].y, untwist_gain(q), false, unused) + (round_coef(s[2 * c + 1][q].y, untwist_gain(q), false, unused) << 16);
+                const int32_t j = 64 * q + lane;
+                __hip_atomic_fetch_add(&accc[j], d0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                __hip_atomic_fetch_add(&accc[j + kM], d1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            }
+        }
+        wave_sync();
+    }
+    // the epilogue forms its addresses from the lane number again (k_blind_rotate_w1b's remedy): shared with the prologue's
+    // they would be held across the step loop, which has no register to spare
+    int elane = lane;
+    asm volatile("" : "+v"(elane));
+    {
+        const int4* src = reinterpret_cast<const int4*>(acc);
+        int4* dst = reinterpret_cast<int4*>(A.dst + (size_t)r * 2 * kN);
+#pragma unroll
+        for (int q = 0; q < 8; q++) dst[64 * q + elane] = src[64 * q + elane];
+    }
+}
+
+// ---- what a lookup's tree and extraction read: selectors steps .. steps + depth - 1 of each item as a [items][depth] array of
+// explicit indices (an implied one taken mod n_set, an explicit one clamped: the rule of the call, applied once), and the
+// public coefficient once per item ----
+__global__ __launch_bounds__(256) void k_read_indices(const int32_t* __restrict__ sel_of, int64_t item0, int64_t items, int32_t depth, int32_t steps,
+                                                      int32_t n_set, int32_t coef, int32_t* __restrict__ tree_sel, int32_t* __restrict__ coef_of) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q < items) coef_of[q] = coef;
+    if (q >= items * depth) return;
+    const int64_t item = q / depth, k = q - item * depth;
+    const int64_t at = (item0 + item) * (depth + steps) + steps + k;
+    int64_t sel;
+    if (sel_of == nullptr) {
+        sel = at % n_set;
+    } else {
+        sel = (int64_t)sel_of[at];
+        sel = sel < 0 ? 0 : (sel >= n_set ? n_set - 1 : sel);
+    }
+    tree_sel[q] = (int32_t)sel;
+}
+
+template <class F>
+void with_param_set(int32_t l, F&& f) {
+    if (l == 3)
+        f(std::integral_constant<int, 3>{}, std::integral_constant<int, 7>{});
+    else
+        f(std::integral_constant<int, 2>{}, std::integral_constant<int, 10>{});
+}
+
+constexpr size_t kRotateLds = (size_t)kCmuxWaveRows * 2 * kN * 4 + ((size_t)kCmuxWaveRows * kTile + kTwElems) * sizeof(double2);
+LdsGrant g_rotate_grant[2];
+
+}  // namespace
+
+void Cmux::launch_rotate(const TgswSet& set, hipStream_t stream, RotateRows rows) {
+    check_owner(set);
+    if (rows.rows <= 0) return;
+    if (rows.steps < 0 || rows.steps > kRotateMaxSteps || rows.sel_stride < rows.steps) throw std::invalid_argument("tlwe_rotate: steps out of range");
+    rows.n_set = (int32_t)set.n;
+    const unsigned grid = (unsigned)((rows.rows + kCmuxWaveRows - 1) / kCmuxWaveRows);
+    with_param_set(p_.l, [&](auto l, auto bgbit) {
+        auto kernel = k_rotate_x1<decltype(l)::value, decltype(bgbit)::value>;
+        allow_dynamic_lds_once(g_rotate_grant[decltype(l)::value == 3 ? 0 : 1], (const void*)kernel, kRotateLds, "k_rotate_x1");
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * kCmuxWaveRows), kRotateLds, stream, rows, (const double2*)set.spectrum, (const double2*)tw_);
+    });
+}
+
+void Cmux::reserve_read(CmuxScratch& scratch, const CmuxPlan& pl, int32_t depth) {
+    reserve(scratch, pl);
+    scratch.rows.reserve_exact((size_t)pl.items_per_piece * 2 * kN);
+    scratch.idx.reserve_exact((size_t)pl.items_per_piece * (size_t)(depth + 1));
+}
+
+int Cmux::launch_read(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, int32_t steps,
+                      const int32_t* sel_of, const int32_t* amount_of, const int32_t* tables, int32_t n_tables, const int32_t* table_of, int32_t coef,
+                      int32_t* u, int32_t stride) {
+    check_owner(set);
+    if (items <= 0) return 0;
+    if (steps < 0 || steps > kRotateMaxSteps) throw std::invalid_argument("lut_read: steps out of range");
+    if (scratch.rows.items() < (size_t)items * 2 * kN || scratch.idx.items() < (size_t)items * (size_t)(depth + 1))
+        throw std::invalid_argument("lut_read: piece larger than the reserved scratch");
+    int32_t* tree_sel = scratch.idx;
+    int32_t* coef_of = tree_sel + (size_t)items * depth;
+    const int64_t words = items * (depth > 1 ? depth : 1);
+    hipLaunchKernelGGL(k_read_indices, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, sel_of, item0, items, depth, steps, (int32_t)set.n,
+                       coef < 0 ? 0 : (coef >= p_.N ? p_.N - 1 : coef), tree_sel, coef_of);
+    // the tree sees a piece of its own: items 0 .. items - 1 with their explicit selectors, but the call's table_of
+    int launches = 1 + launch_tree(set, scratch, stream, 0, items, depth, tree_sel, tables, n_tables, table_of ? table_of + item0 : nullptr, scratch.rows);
+    if (steps > 0) {
+        RotateRows R;
+        R.src = R.dst = scratch.rows;
+        R.rows = items;
+        R.item0 = item0;
+        R.sel_of = sel_of;
+        R.amount_of = amount_of;
+        R.steps = steps;
+        R.sel_stride = depth + steps;
+        launch_rotate(set, stream, R);
+        launches++;
+    }
+    launch_extract(stream, items, scratch.rows, coef_of, u, stride);
+    return launches + 1;
+}
+
+}  // namespace ieache

@@ -372,6 +372,76 @@ void lut_scatter_reference(const Params& p, const Torus32* set, size_t n_set, si
     }
 }
 
+// rows [count][2][N] rotated in `steps` steps each; the selector of (row r, step t) is index r stride + t of the call
+static void rotate_rows(const Params& p, const Torus32* set, size_t n_set, size_t count, int32_t steps, size_t stride, const int32_t* sel_of,
+                        const int32_t* amount_of, const Torus32* in, Torus32* out) {
+    const size_t N = (size_t)p.N, W = 2 * N, S = (size_t)p.kpl() * W;
+    const int n_threads = host_threads();
+    (void)n_threads;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(n_threads)
+    for (int64_t r = 0; r < (int64_t)count; r++) {
+        std::vector<uint32_t> acc(in + (size_t)r * W, in + ((size_t)r + 1) * W), d(W);
+        for (int32_t t = 0; t < steps; t++) {
+            const size_t a = amount_of ? (size_t)amount_of[t] : (t < 31 && ((size_t)1 << t) < W ? W - ((size_t)1 << t) : 0);
+            if (a == 0) continue;  // the operand is zero and so is its truncating decomposition
+            const size_t at = (size_t)r * stride + (size_t)t, sel = sel_of ? (size_t)sel_of[at] : at % n_set;
+            // X^a acc - acc: coefficient j takes +/- coefficient j - a mod 2N
+            for (size_t c = 0; c < 2; c++)
+                for (size_t j = 0; j < N; j++) {
+                    const size_t from = (j + W - a) & (W - 1);
+                    const uint32_t v = acc[c * N + (from & (N - 1))];
+                    d[c * N + j] = ((from & N) ? 0u - v : v) - acc[c * N + j];
+                }
+            external_product_add(p, set + sel * S, d.data(), acc.data());
+        }
+        for (size_t j = 0; j < W; j++) out[(size_t)r * W + j] = (Torus32)acc[j];
+    }
+}
+
+void tlwe_rotate_reference(const Params& p, const Torus32* set, size_t n_set, size_t count, int32_t steps, const int32_t* sel_of,
+                           const int32_t* amount_of, const Torus32* in, Torus32* out) {
+    rotate_rows(p, set, n_set, count, steps, (size_t)steps, sel_of, amount_of, in, out);
+}
+
+void keyswitch_reference(const Params& p, const Torus32* ksk, size_t count, const Torus32* u, Torus32* out) {
+    const size_t N = (size_t)p.k * (size_t)p.N, n = (size_t)p.n, base = (size_t)p.ks_base();
+    const int32_t t = p.ks_t, bb = p.ks_basebit;
+    const uint32_t prec_offset = 1u << (32 - (1 + bb * t)), mask = (1u << bb) - 1u;
+    for (size_t r = 0; r < count; r++) {
+        const Torus32* x = u + r * (N + 1);
+        uint32_t* o = (uint32_t*)out + r * (n + 1);
+        std::fill(o, o + n, 0u);
+        o[n] = (uint32_t)x[N];
+        for (size_t i = 0; i < N; i++) {
+            const uint32_t abar = (uint32_t)x[i] + prec_offset;
+            for (int32_t j = 0; j < t; j++) {
+                const uint32_t dig = (abar >> (32 - (j + 1) * bb)) & mask;
+                if (!dig) continue;  // libtfhe subtracts nothing for digit 0
+                const uint32_t* row = (const uint32_t*)ksk + ((i * (size_t)t + (size_t)j) * base + dig) * (n + 1);
+                for (size_t q = 0; q <= n; q++) o[q] -= row[q];
+            }
+        }
+    }
+}
+
+void lut_read_reference(const Params& p, const Torus32* set, size_t n_set, const Torus32* ksk, size_t count, int32_t depth, int32_t steps,
+                        const int32_t* sel_of, const int32_t* amount_of, const Torus32* tables, const int32_t* table_of, int32_t coef,
+                        Torus32* out) {
+    const size_t W = (size_t)2 * p.N, stride = (size_t)depth + (size_t)steps;
+    // the tree's selectors are indices steps .. steps + depth - 1 of each item
+    std::vector<int32_t> tree_sel(count * (size_t)depth), coef_of(count, coef);
+    for (size_t i = 0; i < count; i++)
+        for (size_t k = 0; k < (size_t)depth; k++) {
+            const size_t at = i * stride + (size_t)steps + k;
+            tree_sel[i * (size_t)depth + k] = sel_of ? sel_of[at] : (int32_t)(at % n_set);
+        }
+    std::vector<Torus32> rows(count * W), u(ksk ? count * ((size_t)p.N + 1) : 0);
+    lut_tree_reference(p, set, n_set, count, depth, tree_sel.data(), tables, table_of, rows.data());
+    rotate_rows(p, set, n_set, count, steps, stride, sel_of, amount_of, rows.data(), rows.data());
+    tlwe_extract_reference(p, count, rows.data(), coef_of.data(), ksk ? u.data() : out);
+    if (ksk) keyswitch_reference(p, ksk, count, u.data(), out);
+}
+
 void tlwe_extract_reference(const Params& p, size_t count, const Torus32* tlwe, const int32_t* coef_of, Torus32* u) {
     const int32_t N = p.N;
     for (size_t r = 0; r < count; r++) {

@@ -83,6 +83,19 @@ void lut_tree_reference(const Params& p, const Torus32* set, size_t n_set, size_
 void lut_scatter_reference(const Params& p, const Torus32* set, size_t n_set, size_t count, int32_t depth, const int32_t* sel_of,
                            const Torus32* values, const Torus32* mem, Torus32* out);
 
+// tlwe_rotate_reference (section 3h): row r goes through acc <- acc + C_t [.] (X^(a_t) acc - acc) for t = 0 .. steps-1, C_t =
+// set[sel_of[r steps + t]] (null: (r steps + t) mod n_set), a_t = amount_of[t] (null: 2N - 2^t, 0 once 2^t reaches 2N).  out may
+// be `in`.  lut_read_reference: the tree by selectors steps .. steps+depth-1 of each item's depth + steps, the rotation of the
+// selected row by selectors 0 .. steps-1, coefficient `coef` extracted, and keyswitch_reference (lweKeySwitch on raw arrays:
+// u [count][N+1] -> out [count][n+1], ksk [N][t][base][n+1]) unless ksk is null: then out is the extracted rows [count][N+1].
+// Indices and amounts already checked by the caller.
+void tlwe_rotate_reference(const Params& p, const Torus32* set, size_t n_set, size_t count, int32_t steps, const int32_t* sel_of,
+                           const int32_t* amount_of, const Torus32* in, Torus32* out);
+void keyswitch_reference(const Params& p, const Torus32* ksk, size_t count, const Torus32* u, Torus32* out);
+void lut_read_reference(const Params& p, const Torus32* set, size_t n_set, const Torus32* ksk, size_t count, int32_t depth, int32_t steps,
+                        const int32_t* sel_of, const int32_t* amount_of, const Torus32* tables, const int32_t* table_of, int32_t coef,
+                        Torus32* out);
+
 // coefficient coef_of[r] (null: 0; checked by the caller) of tlwe [count][2][N] as extracted rows u [count][N+1]
 void tlwe_extract_reference(const Params& p, size_t count, const Torus32* tlwe, const int32_t* coef_of, Torus32* u);
 

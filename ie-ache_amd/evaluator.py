@@ -20,6 +20,8 @@ GATE_AND, GATE_XOR, GATE_OR, GATE_NAND, GATE_MUX = 0, 1, 2, 3, 4
 GATE_NOR, GATE_XNOR, GATE_ANDNY, GATE_ANDYN, GATE_ORNY, GATE_ORYN = 5, 6, 7, 8, 9, 10  # libtfhe boot-gates.cpp
 GATE_TYPES = 11
 LUT_TREE_MAX_DEPTH = 12  # IEACHE_LUT_TREE_MAX_DEPTH
+ROTATE_MAX_STEPS = 64  # IEACHE_ROTATE_MAX_STEPS
+LUT_READ_NO_KEYSWITCH = 1  # flag of ieache_lut_read*: the extracted rows are the result
 PBS_MULTI_MAX_FACTORS = 64  # most factor polynomials of one ieache_pbs_multi* call
 PBS_NO_KEYSWITCH = 1  # flag of ieache_pbs*: the extracted samples are the result (tfhe_bootstrap_woKS_FFT)
 PBS_TLWE_POLYS = 4    # ... the table is [n_polys][2][N]: TLWE samples under the ring key (an encrypted table)
@@ -195,6 +197,13 @@ def lib():
     L.ieache_lut_scatter.argtypes = [vp, vp, C.c_size_t, C.c_int32, i32p, i32p, i32p, i32p, sp]
     L.ieache_lut_scatter_device.argtypes = [vp, vp, C.c_size_t, C.c_int32, vp, vp, vp, vp, sp]
     L.ieache_lut_scatter_reference.argtypes = [pp, i32p, C.c_size_t, C.c_size_t, C.c_int32, i32p, i32p, i32p, i32p]
+    L.ieache_tlwe_rotate.argtypes = [vp, vp, C.c_size_t, C.c_int32, i32p, i32p, i32p, i32p, sp]
+    L.ieache_tlwe_rotate_device.argtypes = [vp, vp, C.c_size_t, C.c_int32, vp, vp, vp, vp, sp]
+    L.ieache_tlwe_rotate_reference.argtypes = [pp, i32p, C.c_size_t, C.c_size_t, C.c_int32, i32p, i32p, i32p, i32p]
+    L.ieache_lut_read.argtypes = [vp, vp, C.c_size_t, C.c_int32, C.c_int32, i32p, i32p, i32p, C.c_int32, i32p, C.c_int32, C.c_int, i32p, sp]
+    L.ieache_lut_read_device.argtypes = [vp, vp, C.c_size_t, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int, vp, sp]
+    L.ieache_lut_read_reference.argtypes = [pp, i32p, C.c_size_t, i32p, C.c_size_t, C.c_int32, C.c_int32, i32p, i32p, i32p, C.c_int32, i32p,
+                                            C.c_int32, C.c_int, i32p]
     L.ieache_tlwe_extract.argtypes = [vp, C.c_size_t, i32p, i32p, i32p, sp]
     L.ieache_tlwe_extract_device.argtypes = [vp, C.c_size_t, vp, vp, vp, sp]
     L.ieache_debug_cmux_plan.argtypes = [vp, C.c_size_t, C.c_int32, C.POINTER(C.c_int64)]
@@ -825,6 +834,56 @@ class Context:
         old = self.lut_tree(tgsw, mem, depth, sel_of=sel_of, table_of=np.arange(count, dtype=np.int32), count=count)
         delta = ((new.astype(np.int64) - old.astype(np.int64)) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
         return self.lut_scatter(tgsw, delta, depth, sel_of=sel_of, mem=mem, count=count)
+
+    def tlwe_rotate(self, tgsw, rows, steps, sel_of=None, amounts=None, stats=None):
+        """Rotation by an encrypted amount on host rows (include/ieache.h section 3h): row i ([count][2][N], or one row) goes
+        through acc <- acc + C_t [.] (X^(a_t) acc - acc) for t = 0 .. steps-1, C_t = sample sel_of[i][t] of the set
+        ([count][steps]; None: samples i steps + t mod n), a_t = amounts[t] in [0, 2N) shared by all rows (None: 2N - 2^t, which
+        brings coefficient sum b_t 2^t to position 0; tools.rotate_amounts gives both directions)."""
+        steps = int(steps)
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 2, self.params.N)
+        count = rows.shape[0]
+        of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(steps, 1))
+        am = None if amounts is None else np.ascontiguousarray(amounts, dtype=np.int32).reshape(-1)
+        assert (of is None or steps < 1 or of.shape[0] == count) and (am is None or am.shape[0] == max(steps, 0))
+        out = np.zeros((count, 2, self.params.N), dtype=np.int32)
+        check(lib().ieache_tlwe_rotate(self.h, tgsw.h, count, steps, None if of is None else _i32(of), None if am is None else _i32(am), _i32(rows),
+                                       _i32(out), _stats_ref(stats)))
+        return out
+
+    def tlwe_rotate_device(self, tgsw, count, steps, d_sel_of, d_amounts, d_in, d_out, stats=None):
+        """Device pointers (ints; d_sel_of and d_amounts may be None / 0): rows [count][2][N] packed, selectors [count][steps] and
+        amounts [steps] int32; d_out == d_in rotates in place."""
+        check(lib().ieache_tlwe_rotate_device(self.h, tgsw.h, count, int(steps), C.c_void_p(d_sel_of or None), C.c_void_p(d_amounts or None),
+                                              C.c_void_p(d_in), C.c_void_p(d_out), _stats_ref(stats)))
+
+    def lut_read(self, tgsw, tables, depth, steps, sel_of=None, amounts=None, table_of=None, coef=0, keyswitch=True, count=None, stats=None):
+        """The coefficient-level lookup on host rows (section 3h): item i looks up tables[table_of[i]] ([n_tables][2^depth][2][N])
+        by its depth + steps address bits sel_of[i] ([count][steps + depth]: the `steps` LOW bits first, least significant first,
+        then the `depth` HIGH ones; None: samples i (steps + depth) + t mod n) -- a CMux tree by the high bits, the rotation of the
+        selected sample by the low bits, coefficient `coef` extracted and key-switched -> LWE rows [count][n+1] (keyswitch=False:
+        the extracted rows [count][N+1])."""
+        depth, steps = int(depth), int(steps)
+        tables = np.ascontiguousarray(tables, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, self.params.N)
+        of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(depth + steps, 1))
+        am = None if amounts is None else np.ascontiguousarray(amounts, dtype=np.int32).reshape(-1)
+        tof = None if table_of is None else np.ascontiguousarray(table_of, dtype=np.int32).reshape(-1)
+        if count is None:
+            count = tof.shape[0] if tof is not None else (of.shape[0] if of is not None and depth + steps > 0 else 1)
+        assert (tof is None or tof.shape[0] == count) and (of is None or depth + steps < 1 or of.shape[0] == count)
+        assert am is None or am.shape[0] == max(steps, 0)
+        out = np.zeros((count, (self.params.n if keyswitch else self.params.N) + 1), dtype=np.int32)
+        check(lib().ieache_lut_read(self.h, tgsw.h, count, depth, steps, None if of is None else _i32(of), None if am is None else _i32(am),
+                                    _i32(tables), tables.shape[0], None if tof is None else _i32(tof), int(coef),
+                                    0 if keyswitch else LUT_READ_NO_KEYSWITCH, _i32(out), _stats_ref(stats)))
+        return out
+
+    def lut_read_device(self, tgsw, count, depth, steps, d_sel_of, d_amounts, d_tables, n_tables, d_table_of, d_out, coef=0, keyswitch=True, stats=None):
+        """Device pointers (ints; the index arrays and d_amounts may be None / 0): tables [n_tables][2^depth][2][N] packed, out rows
+        of lwe_stride words (keyswitch=False: of extract_stride words)."""
+        check(lib().ieache_lut_read_device(self.h, tgsw.h, count, int(depth), int(steps), C.c_void_p(d_sel_of or None), C.c_void_p(d_amounts or None),
+                                           C.c_void_p(d_tables), int(n_tables), C.c_void_p(d_table_of or None), int(coef),
+                                           0 if keyswitch else LUT_READ_NO_KEYSWITCH, C.c_void_p(d_out), _stats_ref(stats)))
 
     def cmux_plan(self, count, depth=-1):
         """How cmux() (depth < 0) or lut_tree() / lut_scatter() would cut such a call under the options as they are (csrc/cmux_plan.h):

@@ -201,6 +201,52 @@ def lut_scatter_reference(params, samples, values, depth, sel_of=None, mem=None,
     return out
 
 
+def rotate_amounts(steps, unit=1, toward_zero=True, N=1024):
+    """The public amounts of Context.tlwe_rotate / lut_read for address bits of weight unit 2^t, t = 0 .. steps-1, mod 2N:
+    2N - unit 2^t (toward_zero: coefficient unit sum b_t 2^t comes to position 0 -- the read; unit = 1 is the calls' default) or
+    unit 2^t (coefficient 0 goes to that position -- the write) -> int32 [steps].  N: the ring's degree."""
+    two_n = 2 * int(N)
+    w = np.array([(int(unit) << t) % two_n for t in range(int(steps))], dtype=np.int64)
+    return ((two_n - w) % two_n if toward_zero else w).astype(np.int32)
+
+
+def tlwe_rotate_reference(params, samples, rows, steps, sel_of=None, amounts=None):
+    """CPU reference of Context.tlwe_rotate on raw arrays (ieache_tlwe_rotate_reference; no GPU, any supported set), arguments as
+    there."""
+    steps = int(steps)
+    kpl = (params.k + 1) * params.l
+    samples = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, kpl, 2, params.N)
+    rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 2, params.N)
+    of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(steps, 1))
+    am = None if amounts is None else np.ascontiguousarray(amounts, dtype=np.int32).reshape(-1)
+    assert (of is None or steps < 1 or of.shape[0] == rows.shape[0]) and (am is None or am.shape[0] == max(steps, 0))
+    out = np.zeros_like(rows)
+    check(lib().ieache_tlwe_rotate_reference(C.byref(params), _i32(samples), samples.shape[0], rows.shape[0], steps, None if of is None else _i32(of),
+                                             None if am is None else _i32(am), _i32(rows), _i32(out)))
+    return out
+
+
+def lut_read_reference(params, samples, tables, depth, steps, sel_of=None, amounts=None, table_of=None, coef=0, ksk=None, count=None):
+    """CPU reference of Context.lut_read on raw arrays (ieache_lut_read_reference), arguments as there; ksk: the key-switch key
+    [N][t][base][n+1] as keygen_raw gives it -> [count][n+1], or None: no key switch, the extracted rows [count][N+1]."""
+    depth, steps = int(depth), int(steps)
+    kpl = (params.k + 1) * params.l
+    samples = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, kpl, 2, params.N)
+    tables = np.ascontiguousarray(tables, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, params.N)
+    of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(depth + steps, 1))
+    am = None if amounts is None else np.ascontiguousarray(amounts, dtype=np.int32).reshape(-1)
+    tof = None if table_of is None else np.ascontiguousarray(table_of, dtype=np.int32).reshape(-1)
+    ksk = None if ksk is None else np.ascontiguousarray(ksk, dtype=np.int32)
+    if count is None:
+        count = tof.shape[0] if tof is not None else (of.shape[0] if of is not None and depth + steps > 0 else 1)
+    assert am is None or am.shape[0] == max(steps, 0)
+    out = np.zeros((count, (params.N if ksk is None else params.n) + 1), dtype=np.int32)
+    check(lib().ieache_lut_read_reference(C.byref(params), _i32(samples), samples.shape[0], None if ksk is None else _i32(ksk), count, depth, steps,
+                                          None if of is None else _i32(of), None if am is None else _i32(am), _i32(tables), tables.shape[0],
+                                          None if tof is None else _i32(tof), int(coef), 1 if ksk is None else 0, _i32(out)))
+    return out
+
+
 def tlwe_extract_reference(params, tlwe, coef_of=None):
     """CPU reference of Context.tlwe_extract (ieache_tlwe_extract_reference): tlwe [count][2][N] -> [count][N+1]."""
     tlwe = np.ascontiguousarray(tlwe, dtype=np.int32).reshape(-1, 2, params.N)

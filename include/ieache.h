@@ -816,6 +816,56 @@ int ieache_lut_scatter(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, in
 int ieache_lut_scatter_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* d_sel_of,
                               const int32_t* d_values, const int32_t* d_mem, int32_t* d_out /* == d_mem: in place */, ieache_stats* stats);
 
+/* 3h. Rotation of a TLWE sample by an encrypted amount, and the coefficient-level lookup: the last stage of vertical packing.
+ * Conventions, sets, decomposition and exactness are those of 3f.
+ *
+ * Item i has a sample in[i] [2][N], `steps` selectors C_0 .. C_{steps-1} (sample sel_of[i steps + t]; sel_of == NULL:
+ * (i steps + t) mod n) and the call has public amounts a_t in [0, 2N), shared by all items.  For t = 0 .. steps-1 in order
+ *   acc <- acc + C_t [.] (X^(a_t) acc - acc),        integers mod 2^32,
+ * where X^a is the negacyclic monomial product (coefficient j takes +/- coefficient j - a mod 2N: libtfhe's
+ * tfhe_MuxRotate_FFT).  It is the blind rotation's step on a caller's selector: with C_t = BK_i one step is the rotation's step i
+ * word for word.  A step with a_t = 0 is an exact no-op.  If C_t encrypts the bit b_t, the result encrypts
+ * X^(sum b_t a_t) in[i] plus the noise of `steps` external products.  amount_of == NULL stands for a_t = 2N - 2^t (0 from
+ * t = log2(2N) on): it brings coefficient sum b_t 2^t of in[i] to position 0.  With a_t = +2^t the same call moves
+ * coefficient 0 to position sum b_t 2^t: followed by ieache_lut_scatter it places a value at an encrypted (slot, coefficient).
+ * steps ranges over 0 .. IEACHE_ROTATE_MAX_STEPS; steps = 0 copies.
+ *
+ * The device form accepts d_out == d_in EXACTLY (a row is read whole before any of it is stored, and rows are disjoint); any
+ * other overlap is refused.  Pieces: the flat rule of 3f, rows = items, under "cmux_piece_rows"; one launch per piece, all the
+ * steps of a row inside it; no scratch, a warm call allocates nothing.  Host forms check every index and amount and name the
+ * first bad one; on the device an explicit index is clamped into the set, an implied one is taken mod n and an amount is
+ * masked to 2N - 1.  IEACHE_EINVAL: steps outside 0 .. IEACHE_ROTATE_MAX_STEPS, overlap, a set prepared on another context.
+ * count == 0 is a no-op.  stats: bootstraps == 0, keyswitch_launches == 0, levels = steps, chunks = pieces, one launch per piece
+ * (steps == 0: the same launch, which then only copies), the launches and their time in blind_rotate_launches and
+ * blind_rotate_ms.
+ *
+ * ieache_lut_read is the vertical-packing lookup over depth + steps address bits, run on the context's stream with no host
+ * round trip.  Item i has selectors sel_of[i (steps + depth) + t] (NULL: that index mod n): t = 0 .. steps-1 are the LOW address
+ * bits, least significant first, t = steps .. steps+depth-1 the HIGH ones.  (1) ieache_lut_tree by the high bits over
+ * tables[table_of[i]] selects one sample; (2) that ONE row per item is rotated by the low bits; (3) the public coefficient
+ * `coef` (0 with the default amounts) is extracted as ieache_tlwe_extract does; (4) the key switch.  out is [count][n+1] LWE rows
+ * under the LWE key, what the gates take; with IEACHE_LUT_READ_NO_KEYSWITCH the extracted rows (host: N + 1 words; device:
+ * ieache_extract_stride() words).  A table of 2^(depth + log2 N) bits is 2^depth samples and costs 2^depth - 1 CMuxes plus
+ * `steps` products per item.  The cut is the tree's plan for (count, depth); the selected rows and the indices of a piece are
+ * reserved with the tree's scratch ahead of the loop.  stats: levels = depth + steps, chunks = pieces, the tree's, the
+ * rotation's and the extraction's launches in blind_rotate_launches, the key switch's in keyswitch_launches.  Refusals as for
+ * ieache_lut_tree and ieache_tlwe_rotate, coef outside [0, N) (host form; the device form clamps), an unknown flag.
+ * No group form, no cloudd verb, no replace-write of a single coefficient, no other rings, no one-limb form. */
+#define IEACHE_ROTATE_MAX_STEPS 64
+#define IEACHE_LUT_READ_NO_KEYSWITCH 1
+int ieache_tlwe_rotate(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t steps, const int32_t* sel_of /*[count][steps] or NULL*/,
+                       const int32_t* amount_of /*[steps] or NULL*/, const int32_t* in /*[count][2][N]*/, int32_t* out /*[count][2][N]*/,
+                       ieache_stats* stats);
+int ieache_tlwe_rotate_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t steps, const int32_t* d_sel_of,
+                              const int32_t* d_amount_of, const int32_t* d_in, int32_t* d_out /* == d_in: in place */, ieache_stats* stats);
+int ieache_lut_read(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps,
+                    const int32_t* sel_of /*[count][steps+depth] or NULL*/, const int32_t* amount_of /*[steps] or NULL*/,
+                    const int32_t* tables /*[n_tables][2^depth][2][N]*/, int32_t n_tables, const int32_t* table_of /*[count] or NULL*/, int32_t coef,
+                    int flags, int32_t* out, ieache_stats* stats);
+int ieache_lut_read_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of,
+                           const int32_t* d_amount_of, const int32_t* d_tables, int32_t n_tables, const int32_t* d_table_of, int32_t coef, int flags,
+                           int32_t* d_out, ieache_stats* stats);
+
 /* ------------------------------------------------------------------ *
  * 4. CPU tools around the path (no GPU): what Keygen/keygen.c:22-51,  *
  *    Client1/alice.c:116-191 and Output/verif.c:41-76 get from        *
@@ -875,6 +925,14 @@ int ieache_lut_tree_reference(const ieache_params* p, const int32_t* set, size_t
 /* ... of ieache_lut_scatter (section 3g), arguments and refusals as for its host form; out may be mem itself ... */
 int ieache_lut_scatter_reference(const ieache_params* p, const int32_t* set, size_t n, size_t count, int32_t depth, const int32_t* sel_of,
                                  const int32_t* values, const int32_t* mem, int32_t* out);
+/* ... of ieache_tlwe_rotate and ieache_lut_read (section 3h), arguments and refusals as for their host forms; out may be `in`
+ * itself.  The lookup's key switch is lweKeySwitch with ksk [N][ks_t][2^ks_basebit][n+1] as ieache_keygen_raw gives it; ksk may
+ * be NULL under IEACHE_LUT_READ_NO_KEYSWITCH, and out is then [count][N+1] ... */
+int ieache_tlwe_rotate_reference(const ieache_params* p, const int32_t* set, size_t n, size_t count, int32_t steps, const int32_t* sel_of,
+                                 const int32_t* amount_of, const int32_t* in, int32_t* out);
+int ieache_lut_read_reference(const ieache_params* p, const int32_t* set, size_t n, const int32_t* ksk, size_t count, int32_t depth, int32_t steps,
+                              const int32_t* sel_of, const int32_t* amount_of, const int32_t* tables, int32_t n_tables, const int32_t* table_of,
+                              int32_t coef, int flags, int32_t* out);
 /* ... and of ieache_tlwe_extract: tlwe [count][2][N] -> u [count][N+1]. */
 int ieache_tlwe_extract_reference(const ieache_params* p, size_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u);
 /* key files -> raw arrays (sizes from ieache_params; pass NULL to query params only) */
