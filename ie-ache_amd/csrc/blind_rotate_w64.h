@@ -17,6 +17,20 @@ void prepare_spectrum(const Params& p, const Torus32* d_bk_raw, double2* d_bkf, 
 void prepare_spectrum1(const Params& p, const Torus32* d_bk_raw, double2* d_bkf1, hipStream_t stream);
 void build_twiddle_table(double2* d_tw, hipStream_t stream);
 
+// the one place that turns the runtime parameter set into template arguments (br_supported(): these two only); the
+// CMux family (cmux.hip, rotate.hip) dispatches its kernels through it as well
+template <int L_, int BGBIT_>
+struct ParamSet {
+    static constexpr int L = L_, BGBIT = BGBIT_, index = L_ == 3 ? 0 : 1;
+};
+template <class F>
+void with_param_set(int32_t l, F&& f) {
+    if (l == 3)
+        f(ParamSet<3, 7>{});
+    else
+        f(ParamSet<2, 10>{});
+}
+
 // what the kernels read besides the work: both spectra, the twiddle table, the three-word guard record of the one-limb
 // kernels, and the stamp buffer of the diagnostic builds (16 words; null unless the plan names one of them)
 struct Tables {

@@ -497,26 +497,7 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_x1(DevKeys K, const 
             decompose_rotated(v0, v1, accb, accp, pb, jb, lane, dec_offset);
         };
         auto digit_row = [&](const int sh, const int brow, auto first) {
-            constexpr bool FIRST = decltype(first)::value;
-            double2 x[8], bA[8], bB[8];
-            digits_to_double2<BGBIT>(x, v0, v1, sh);
-            __builtin_amdgcn_sched_barrier(0);
-            auto req = [&]() { load_bk_block(bA, bk_rsrc, lane16, brow); };  // block 0: output 0, low limb
-            fft512_forward<true, 1, decltype(req), true>(x, sT, lane, R, req);
-            load_bk_block(bB, bk_rsrc, lane16, brow + kBlockBytes);          // block 1: output 0, high limb
-            __builtin_amdgcn_sched_barrier(0);
-            // block q + 2 is requested when block q has been multiplied (re-requesting register by register, right behind the
-            // products that consumed each one, measured the same: profiles/r4_x1_ab.txt)
-            mac_row<FIRST>(s[0], x, bA);
-            __builtin_amdgcn_sched_barrier(0);
-            load_bk_block(bA, bk_rsrc, lane16, brow + 2 * kBlockBytes);            // block 2: output 1, low limb
-            __builtin_amdgcn_sched_barrier(0);
-            mac_row<FIRST>(s[1], x, bB);
-            __builtin_amdgcn_sched_barrier(0);
-            load_bk_block(bB, bk_rsrc, lane16, brow + 3 * kBlockBytes);            // block 3: output 1, high limb
-            __builtin_amdgcn_sched_barrier(0);
-            mac_row<FIRST>(s[2], x, bA);
-            mac_row<FIRST>(s[3], x, bB);
+            digit_row_two_limb<BGBIT, decltype(first)::value>(s, v0, v1, sh, bk_rsrc, lane16, brow, sT, lane, R);
         };
         decompose(pb0, jb4);
         digit_row(32 - BGBIT, bki, std::true_type{});
@@ -536,9 +517,7 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_x1(DevKeys K, const 
             uint32_t* accc = reinterpret_cast<uint32_t*>(acc) + c * kN;
 #pragma unroll
             for (int r = 0; r < 8; r++) {
-                double unused = 0.0;  // nothing to watch: every rounded sum is below 2^35
-                const uint32_t d0 = round_coef(s[2 * c][r].x, untwist_gain(r), false, unused) + (round_coef(s[2 * c + 1][r].x, untwist_gain(r), false, unused) << 16);
-                const uint32_t d1 = round_coef(s[2 * c][r].y, untwist_gain(r), false, unused) + (round_coef(s[2 * c + 1][r].y, untwist_gain(r), false, unused) << 16);
+                const uint32_t d0 = join_limbs(s[2 * c][r].x, s[2 * c + 1][r].x, r), d1 = join_limbs(s[2 * c][r].y, s[2 * c + 1][r].y, r);
                 const int32_t j = 64 * r + lane;
                 __hip_atomic_fetch_add(&accc[j], d0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                 __hip_atomic_fetch_add(&accc[j + kM], d1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -1116,6 +1095,9 @@ __global__ __launch_bounds__(128 * L) void k_blind_rotate_wide4(DevKeys K, const
     }
 }
 
+// the transforms' twiddle table (fft512.h), built once per context
+__global__ __launch_bounds__(128) void k_build_twiddle_table(double2* tw) { build_twiddles(tw, threadIdx.x, 128); }
+
 }  // namespace
 
 size_t spectrum_elems(const Params& p) { return (size_t)p.n * p.kpl() * 4 * kM; }
@@ -1177,18 +1159,6 @@ struct LaunchRow {
 };
 static LdsGrant& granted(const LaunchRow& v, int param_set);  // ... remembered per kernel (parameter set) and device
 
-// the one place that turns the runtime parameter set into template arguments (br_supported(): these two only)
-template <int L_, int BGBIT_>
-struct ParamSet {
-    static constexpr int L = L_, BGBIT = BGBIT_, index = L_ == 3 ? 0 : 1;
-};
-template <class F>
-static void with_param_set(int32_t l, F&& f) {
-    if (l == 3)
-        f(ParamSet<3, 7>{});
-    else
-        f(ParamSet<2, 10>{});
-}
 template <class T>
 struct as_is {
     using type = T;

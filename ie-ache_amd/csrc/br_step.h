@@ -19,6 +19,15 @@
 //   accumulator load              _w2 _wide                              _w1b _x1 _wide4 (changes instruction count), _w2r _w4r (with the others above)
 //   decomposition offset          _w2                                    the other six (_w1b _x1 _wide _wide4 alone, _w2r _w4r in combination)
 //   round + ds_add_u32 update     --                                     all (a shared form reorders the GUARD = 2 builds of _w2r / _w4r)
+//   two-limb digit row            _x1 k_cmux_x1 k_demux_x1 k_rotate_x1   --
+//   limb recombination            _x1 k_cmux_x1 k_demux_x1 k_rotate_x1   -- (k_cmux_x1: the three sources of 16 v_add3_u32 come out in another order)
+// k_cmux_x1 / k_demux_x1 (cmux.hip) and k_rotate_x1 (rotate.hip) are the CMux family: _x1's step on caller TGSW samples.  What
+// only they share is cmux_step.h, under the same rule:
+//   selector rule                 k_demux_x1 k_rotate_x1 k_read_indices  k_cmux_x1 (its flat form implies another position than it reads: any shared form moves it)
+//   index clamp                   k_cmux_x1 k_tlwe_extract               k_cmux_copy (one instruction fewer), the selector rule itself (narrowed to 32 bits in k_demux_x1)
+//   wave prologue                 k_cmux_x1 k_demux_x1 k_rotate_x1       --
+//   row resource / row word       k_cmux_x1 k_demux_x1                   --
+//   loop over the digit rows      --                                     k_cmux_x1 k_demux_x1 (one helper over the loop moves both)
 // The transform itself is fft512.h / dft8_twist.h.
 #pragma once
 #include "device_common.h"
@@ -155,6 +164,42 @@ __device__ __forceinline__ void mac_row(double2 (&s)[8], const double2 (&x)[8], 
 #pragma unroll
     for (int k = 0; k < 8; k++) s[k] = mac<FIRST>(s[k], x[k], b[k]);
 }
+
+// ---- one digit row on the two-limb spectrum (k_blind_rotate_x1 and the CMux family: cmux.hip, rotate.hip) ----
+// The digit at shift `sh` of the decomposed words, transformed, times the row's four blocks [q = 2 c + limb] at byte offset
+// brow of the resource, into the four sums s[q].  With the sums taking half the register file only two BK blocks are in
+// flight at a time: block 0 is requested inside the forward transform (once the second twiddle set is consumed), block 1
+// behind it, block q + 2 when block q has been multiplied (re-requesting register by register, right behind the products
+// that consumed each one, measured the same: profiles/r4_x1_ab.txt).
+template <int BGBIT, bool FIRST>
+__device__ __forceinline__ void digit_row_two_limb(double2 (&s)[4][8], const uint32_t (&v0)[8], const uint32_t (&v1)[8], int sh,
+                                                   __amdgpu_buffer_rsrc_t bk_rsrc, int lane16, int brow, double2* sT, int lane, const LaneRoots& R) {
+    constexpr int kBlockBytes = kM * (int)sizeof(double2);
+    double2 x[8], bA[8], bB[8];
+    digits_to_double2<BGBIT>(x, v0, v1, sh);
+    __builtin_amdgcn_sched_barrier(0);
+    auto req = [&]() { load_bk_block(bA, bk_rsrc, lane16, brow); };  // block 0: output 0, low limb
+    fft512_forward<true, 1, decltype(req), true>(x, sT, lane, R, req);
+    load_bk_block(bB, bk_rsrc, lane16, brow + kBlockBytes);          // block 1: output 0, high limb
+    __builtin_amdgcn_sched_barrier(0);
+    mac_row<FIRST>(s[0], x, bA);
+    __builtin_amdgcn_sched_barrier(0);
+    load_bk_block(bA, bk_rsrc, lane16, brow + 2 * kBlockBytes);      // block 2: output 1, low limb
+    __builtin_amdgcn_sched_barrier(0);
+    mac_row<FIRST>(s[1], x, bB);
+    __builtin_amdgcn_sched_barrier(0);
+    load_bk_block(bB, bk_rsrc, lane16, brow + 3 * kBlockBytes);      // block 3: output 1, high limb
+    __builtin_amdgcn_sched_barrier(0);
+    mac_row<FIRST>(s[2], x, bA);
+    mac_row<FIRST>(s[3], x, bB);
+}
+// ... and a coefficient back from its two inverse-transformed limb sums: lo + (hi << 16) mod 2^32, register q's gain folded
+// into the rounding.  Nothing to watch: every rounded sum is below 2^37 of the 2^53 an FP64 mantissa holds.
+__device__ __forceinline__ uint32_t join_limbs(double lo, double hi, int q) {
+    double unused = 0.0;
+    return round_coef(lo, untwist_gain(q), false, unused) + (round_coef(hi, untwist_gain(q), false, unused) << 16);
+}
+
 // ---- phase stamps of the diagnostic builds (br_variant 8 / 49): s_memtime ticks since the last stamp, summed per segment ----
 template <bool DIAG>
 __device__ __forceinline__ void stamp_phase(unsigned long long (&tsum)[8], unsigned long long& tlast, int idx) {

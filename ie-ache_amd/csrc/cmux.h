@@ -1,7 +1,9 @@
-// The CMux on TGSW samples the caller supplies, the CMux-tree lookup built from it and the extraction of a coefficient of a
-// TLWE sample (include/ieache.h section 3f), and the scatter that writes at an encrypted index (section 3g), the one door: the kernels, the spectrum form of a prepared set, the twiddle table
-// and the scratch of a tree are behind this object; how a call is cut is cmux_plan.h.  Kernels: cmux.hip, and rotate.hip for
-// the rotation by caller selectors and the coefficient-level lookup (section 3h).
+// The one door to the operations on TGSW samples the caller supplies (include/ieache.h):
+//   section 3f  the CMux, the CMux-tree lookup built from it, and the extraction of a coefficient of a TLWE sample;
+//   section 3g  the scatter that writes at an encrypted index;
+//   section 3h  the rotation by caller selectors and the coefficient-level lookup.
+// The kernels, the spectrum form of a prepared set, the twiddle table and the scratch of a tree are behind this object; how
+// a call is cut is cmux_plan.h.  Kernels: cmux.hip (3f, 3g) and rotate.hip (3h); what the two share is cmux_step.h.
 #pragma once
 #include <cstdint>
 
@@ -10,6 +12,9 @@
 #include "params.h"
 
 namespace ieache {
+namespace dev {
+struct LdsGrant;  // device_common.h
+}
 
 // A prepared set of n TGSW samples: their two-limb spectrum [n][2l][q = 2 c + limb][8][64] double2 -- the layout of the
 // bootstrapping key's spectrum, one sample where that has one BK_i (192 KB at l = 3).  It owns its device memory and nothing of
@@ -126,6 +131,12 @@ struct Cmux {
     void launch_extract(hipStream_t stream, int64_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u, int32_t stride);
 
 private:
+    // The one launcher of the one-wave kernels (k_cmux_x1, k_demux_x1, k_rotate_x1), defined in cmux_step.h: the owner check,
+    // nothing for no rows, n_set filled in, kCmuxWaveRows rows per workgroup, kernel_of(parameter set) launched with `lds`
+    // bytes of dynamic LDS -- which `grant`[parameter set], where given, allows first, once per device.
+    template <class Rows, class KernelOf>
+    void launch_rows(const TgswSet& set, hipStream_t stream, Rows rows, KernelOf kernel_of, size_t lds = 0, dev::LdsGrant* grant = nullptr,
+                     const char* name = nullptr);
     Params p_;
     int device_ = 0;
     uint64_t id_ = 0;

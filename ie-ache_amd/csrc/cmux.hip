@@ -1,7 +1,7 @@
 // The CMux on TGSW samples the caller supplies (include/ieache.h section 3f): out = d0 + C_sel [.] (d1 - d0), the external
 // product of libtfhe's tGswExternMulToTLwe on the provably exact two-limb spectrum -- k_blind_rotate_x1's step
 // (blind_rotate_w64.hip) with the operand taken from global memory instead of a rotating LDS accumulator and the key block
-// chosen per row.  Built from the pieces of br_step.h and fft512.h; no kernel of the blind rotation is touched.
+// chosen per row.  Built from the pieces of br_step.h and fft512.h, which that kernel uses too, and of cmux_step.h.
 // N = 1024, k = 1 and libtfhe's two (l, Bgbit), as br_supported() says; the extraction kernel at the end takes any set.
 // k_demux_x1 is the same product as a demultiplexer: the write at an encrypted index (section 3g).
 #include "cmux.h"
@@ -12,7 +12,7 @@
 #include <type_traits>
 
 #include "blind_rotate_w64.h"
-#include "br_step.h"
+#include "cmux_step.h"
 
 namespace ieache {
 
@@ -20,14 +20,6 @@ using namespace dev;
 using namespace w64;
 
 namespace {
-
-// one row [2][1024] int32 as a buffer resource, and word j + lane of it (j a multiple of 64 known at compile time)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_resource(const int32_t* row) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(row), (short)0, 2 * kN * 4, 0x00020000);
-}
-__device__ __forceinline__ uint32_t row_word(__amdgpu_buffer_rsrc_t rsrc, int lane4, int j) {
-    return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, lane4, j * 4, 0);
-}
 
 // ---- one CMux per wave ----
 // Per row: 2L forward transforms of the digits of d1 - d0, 4 x 2L row products against block `sel` of the set's spectrum into
@@ -51,12 +43,10 @@ template <int L, int BGBIT, int G = kCmuxWaveRows>
 __global__ __launch_bounds__(64 * G, 2) void k_cmux_x1(CmuxRows A, const double2* __restrict__ bkf, const double2* __restrict__ gtw) {
     __shared__ __align__(16) double2 sT_all[G * kTile];
     __shared__ __align__(16) double2 sTw[kTwElems];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    double2* sT = sT_all + wave * kTile;
-    load_twiddles(sTw, gtw, tid, 64 * G);
-    __syncthreads();  // the only workgroup barrier
-    const int64_t r = (int64_t)blockIdx.x * G + wave;
+    const WaveRow W = wave_prologue<G>(sT_all, sTw, gtw);
+    const int lane = W.lane;
+    double2* sT = W.sT;
+    const int64_t r = W.r;
     if (r >= A.rows) return;
     const LaneRoots R = make_roots(sTw, lane);
 
@@ -73,20 +63,18 @@ __global__ __launch_bounds__(64 * G, 2) void k_cmux_x1(CmuxRows A, const double2
     } else {
         const int64_t item = r / A.width, pair = r - item * A.width;
         int64_t block = item;
-        if (A.shared) {
-            const int64_t t = A.table_of ? (int64_t)A.table_of[A.item0 + item] : 0;
-            block = t < 0 ? 0 : (t >= A.n_tables ? A.n_tables - 1 : t);
-        }
+        if (A.shared) block = clamp_index(A.table_of ? (int64_t)A.table_of[A.item0 + item] : 0, A.n_tables);
         p0 = A.src + ((size_t)block * 2 * A.width + 2 * (size_t)pair) * 2 * kN;
         p1 = p0 + 2 * kN;
         const int64_t at = (A.item0 + item) * A.depth + A.level;
         implied = A.sel_of == nullptr;
         sel = implied ? at : (int64_t)A.sel_of[at];
     }
+    // selector_at's rule (cmux_step.h), open-coded: the flat form reads the piece's array at r but implies the call's item0 + r
     if (implied)
         sel %= A.n_set;
     else
-        sel = sel < 0 ? 0 : (sel >= A.n_set ? A.n_set - 1 : sel);
+        sel = clamp_index(sel, A.n_set);
     int32_t* po = A.dst + (size_t)r * 2 * kN;
     // d0 = zeros: the loads read d1's words instead and a wave-uniform mask clears them -- no branch per load
     const uint32_t keep0 = p0 ? 0xFFFFFFFFu : 0u;
@@ -115,24 +103,7 @@ __global__ __launch_bounds__(64 * G, 2) void k_cmux_x1(CmuxRows A, const double2
         }
     };
     auto digit_row = [&](const int sh, const int brow, auto first) {
-        constexpr bool FIRST = decltype(first)::value;
-        double2 x[8], bA[8], bB[8];
-        digits_to_double2<BGBIT>(x, v0, v1, sh);
-        __builtin_amdgcn_sched_barrier(0);
-        auto req = [&]() { load_bk_block(bA, bk_rsrc, lane16, brow); };  // block 0: output 0, low limb
-        fft512_forward<true, 1, decltype(req), true>(x, sT, lane, R, req);
-        load_bk_block(bB, bk_rsrc, lane16, brow + kBlockBytes);          // block 1: output 0, high limb
-        __builtin_amdgcn_sched_barrier(0);
-        mac_row<FIRST>(s[0], x, bA);
-        __builtin_amdgcn_sched_barrier(0);
-        load_bk_block(bA, bk_rsrc, lane16, brow + 2 * kBlockBytes);      // block 2: output 1, low limb
-        __builtin_amdgcn_sched_barrier(0);
-        mac_row<FIRST>(s[1], x, bB);
-        __builtin_amdgcn_sched_barrier(0);
-        load_bk_block(bB, bk_rsrc, lane16, brow + 3 * kBlockBytes);      // block 3: output 1, high limb
-        __builtin_amdgcn_sched_barrier(0);
-        mac_row<FIRST>(s[2], x, bA);
-        mac_row<FIRST>(s[3], x, bB);
+        digit_row_two_limb<BGBIT, decltype(first)::value>(s, v0, v1, sh, bk_rsrc, lane16, brow, sT, lane, R);
     };
     decompose(0);
     digit_row(32 - BGBIT, 0, std::true_type{});
@@ -155,9 +126,7 @@ __global__ __launch_bounds__(64 * G, 2) void k_cmux_x1(CmuxRows A, const double2
         fft512_inverse_pair<true>(s[2 * c], s[2 * c + 1], sT, lane, R);
 #pragma unroll
         for (int q = 0; q < 8; q++) {
-            double unused = 0.0;  // nothing to watch: every rounded sum is below 2^37
-            const uint32_t e0 = round_coef(s[2 * c][q].x, untwist_gain(q), false, unused) + (round_coef(s[2 * c + 1][q].x, untwist_gain(q), false, unused) << 16);
-            const uint32_t e1 = round_coef(s[2 * c][q].y, untwist_gain(q), false, unused) + (round_coef(s[2 * c + 1][q].y, untwist_gain(q), false, unused) << 16);
+            const uint32_t e0 = join_limbs(s[2 * c][q].x, s[2 * c + 1][q].x, q), e1 = join_limbs(s[2 * c][q].y, s[2 * c + 1][q].y, q);
             const int j = c * kN + 64 * q;
             const uint32_t a0 = row_word(r0e, lane4, j) & keep0, a1 = row_word(r0e, lane4, j + kM) & keep0;
             __builtin_amdgcn_raw_buffer_store_b32(a0 + e0, ro, lane4, j * 4, 0);
@@ -168,8 +137,9 @@ __global__ __launch_bounds__(64 * G, 2) void k_cmux_x1(CmuxRows A, const double2
 
 // ---- one demux step per wave: the scatter of include/ieache.h section 3g ----
 // Parent row p splits into hi = C_sel [.] p (child 2 r + 1) and lo = p - hi (child 2 r): k_cmux_x1's body with no d0 -- the
-// digits are those of p itself -- and another epilogue.  The orchestration is repeated here, not shared with k_cmux_x1 through
-// a common body: that kernel's instruction stream is to stay what it was.
+// digits are those of p itself -- and another epilogue.  What the two share is stated once -- the wave prologue, the selector
+// rule and the rows of cmux_step.h, the digit row and the limb recombination of br_step.h -- and each keeps its own
+// decomposition, its three-line loop over the digit rows (one helper over that loop moved both kernels' code) and its epilogue.
 //   * p is NOT kept across the products; the epilogue reads it again through an opaque copy of its pointer, for k_cmux_x1's
 //     reason (kept live, its 32 words were spilled);
 //   * the last step of a scatter adds the memory: base rows 2 r and 2 r + 1 are read here and the sums stored, so no separate
@@ -185,25 +155,16 @@ template <int L, int BGBIT, int G = kCmuxWaveRows>
 __global__ __launch_bounds__(64 * G, 2) void k_demux_x1(DemuxRows A, const double2* __restrict__ bkf, const double2* __restrict__ gtw) {
     __shared__ __align__(16) double2 sT_all[G * kTile];
     __shared__ __align__(16) double2 sTw[kTwElems];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    double2* sT = sT_all + wave * kTile;
-    load_twiddles(sTw, gtw, tid, 64 * G);
-    __syncthreads();  // the only workgroup barrier
-    const int64_t r = (int64_t)blockIdx.x * G + wave;
+    const WaveRow W = wave_prologue<G>(sT_all, sTw, gtw);
+    const int lane = W.lane;
+    double2* sT = W.sT;
+    const int64_t r = W.r;
     if (r >= A.rows) return;
     const LaneRoots R = make_roots(sTw, lane);
 
     // row r -> (parent, children, base rows, selector): all wave-uniform
     const int64_t item = r / A.width;
-    const int64_t at = (A.item0 + item) * A.depth + (A.depth - 1 - A.step);
-    int64_t sel;
-    if (A.sel_of == nullptr) {
-        sel = at % A.n_set;
-    } else {
-        sel = (int64_t)A.sel_of[at];
-        sel = sel < 0 ? 0 : (sel >= A.n_set ? A.n_set - 1 : sel);
-    }
+    const int64_t sel = selector_at(A.sel_of, (A.item0 + item) * A.depth + (A.depth - 1 - A.step), A.n_set);
     const int32_t* pp = A.src + (size_t)r * 2 * kN;
     int32_t* po = A.dst + (size_t)r * 4 * kN;
     const bool add = A.base != nullptr;
@@ -227,24 +188,7 @@ __global__ __launch_bounds__(64 * G, 2) void k_demux_x1(DemuxRows A, const doubl
         }
     };
     auto digit_row = [&](const int sh, const int brow, auto first) {
-        constexpr bool FIRST = decltype(first)::value;
-        double2 x[8], bA[8], bB[8];
-        digits_to_double2<BGBIT>(x, v0, v1, sh);
-        __builtin_amdgcn_sched_barrier(0);
-        auto req = [&]() { load_bk_block(bA, bk_rsrc, lane16, brow); };  // block 0: output 0, low limb
-        fft512_forward<true, 1, decltype(req), true>(x, sT, lane, R, req);
-        load_bk_block(bB, bk_rsrc, lane16, brow + kBlockBytes);          // block 1: output 0, high limb
-        __builtin_amdgcn_sched_barrier(0);
-        mac_row<FIRST>(s[0], x, bA);
-        __builtin_amdgcn_sched_barrier(0);
-        load_bk_block(bA, bk_rsrc, lane16, brow + 2 * kBlockBytes);      // block 2: output 1, low limb
-        __builtin_amdgcn_sched_barrier(0);
-        mac_row<FIRST>(s[1], x, bB);
-        __builtin_amdgcn_sched_barrier(0);
-        load_bk_block(bB, bk_rsrc, lane16, brow + 3 * kBlockBytes);      // block 3: output 1, high limb
-        __builtin_amdgcn_sched_barrier(0);
-        mac_row<FIRST>(s[2], x, bA);
-        mac_row<FIRST>(s[3], x, bB);
+        digit_row_two_limb<BGBIT, decltype(first)::value>(s, v0, v1, sh, bk_rsrc, lane16, brow, sT, lane, R);
     };
     decompose(0);
     digit_row(32 - BGBIT, 0, std::true_type{});
@@ -269,9 +213,8 @@ __global__ __launch_bounds__(64 * G, 2) void k_demux_x1(DemuxRows A, const doubl
         uint32_t h0[8], h1[8];
 #pragma unroll
         for (int q = 0; q < 8; q++) {
-            double unused = 0.0;  // nothing to watch: every rounded sum is below 2^37
-            h0[q] = round_coef(s[2 * c][q].x, untwist_gain(q), false, unused) + (round_coef(s[2 * c + 1][q].x, untwist_gain(q), false, unused) << 16);
-            h1[q] = round_coef(s[2 * c][q].y, untwist_gain(q), false, unused) + (round_coef(s[2 * c + 1][q].y, untwist_gain(q), false, unused) << 16);
+            h0[q] = join_limbs(s[2 * c][q].x, s[2 * c + 1][q].x, q);
+            h1[q] = join_limbs(s[2 * c][q].y, s[2 * c + 1][q].y, q);
         }
         if (add) {
 #pragma unroll
@@ -310,7 +253,7 @@ __global__ __launch_bounds__(256) void k_cmux_copy(const int32_t* __restrict__ t
                                                    int64_t item0, int32_t* __restrict__ out) {
     const int64_t i = blockIdx.x;
     const int64_t t0 = table_of ? (int64_t)table_of[item0 + i] : 0;
-    const int64_t t = t0 < 0 ? 0 : (t0 >= n_tables ? n_tables - 1 : t0);
+    const int64_t t = t0 < 0 ? 0 : (t0 >= n_tables ? n_tables - 1 : t0);  // clamp_index (cmux_step.h), open-coded: the helper moves this kernel's code
     const int4* src = reinterpret_cast<const int4*>(tables + (size_t)t * 2 * kN);
     int4* dst = reinterpret_cast<int4*>(out + (size_t)i * 2 * kN);
     for (int q = threadIdx.x; q < 2 * kN / 4; q += 256) dst[q] = src[q];
@@ -320,8 +263,7 @@ __global__ __launch_bounds__(256) void k_cmux_copy(const int32_t* __restrict__ t
 __global__ __launch_bounds__(256) void k_tlwe_extract(const int32_t* __restrict__ tlwe, const int32_t* __restrict__ coef_of, int32_t* __restrict__ u,
                                                       int32_t N, int32_t stride) {
     const int64_t row = blockIdx.x;
-    const int32_t j0 = coef_of ? coef_of[row] : 0;
-    const int32_t j = j0 < 0 ? 0 : (j0 >= N ? N - 1 : j0);
+    const int32_t j = clamp_index(coef_of ? coef_of[row] : 0, N);
     const int32_t* A = tlwe + (size_t)row * 2 * N;
     int32_t* dst = u + (size_t)row * stride;
     for (int32_t i = threadIdx.x; i <= N; i += 256)
@@ -330,13 +272,14 @@ __global__ __launch_bounds__(256) void k_tlwe_extract(const int32_t* __restrict_
 
 std::atomic<uint64_t> g_next_id{1};
 
-template <class F>
-void with_param_set(int32_t l, F&& f) {
-    if (l == 3)
-        f(std::integral_constant<int, 3>{}, std::integral_constant<int, 7>{});
-    else
-        f(std::integral_constant<int, 2>{}, std::integral_constant<int, 10>{});
+// The intermediates of a tree or a scatter piece alternate between the two scratch buffers: A or B by the parity of the
+// distance from the widest one (items x 2^(depth-1) rows: what level 0 of a tree and step depth - 2 of a scatter write),
+// so that it lands in A and the sizes are cmux_plan.h's.
+void check_scratch(const CmuxScratch& scratch, int64_t items, int32_t depth, const char* refusal) {
+    const size_t widest = (size_t)(items << (depth - 1)) * 2 * kN;
+    if ((depth >= 2 && scratch.a.items() < widest) || (depth >= 3 && scratch.b.items() < widest / 2)) throw std::invalid_argument(refusal);
 }
+int32_t* scratch_rows(CmuxScratch& scratch, int32_t from_widest) { return from_widest % 2 == 0 ? (int32_t*)scratch.a : (int32_t*)scratch.b; }
 
 }  // namespace
 
@@ -352,7 +295,7 @@ TgswSet* Cmux::prepare(const int32_t* d_samples, size_t n, hipStream_t stream) {
     if (n > ((size_t)1 << 20)) throw std::invalid_argument("tgsw_prepare: more than 2^20 samples");
     if (!tw_) {
         tw_.allocate(twiddle_table_elems());
-        hipLaunchKernelGGL(k_build_twiddle_table, dim3(1), dim3(128), 0, stream, (double2*)tw_);
+        build_twiddle_table(tw_, stream);
         HIP_CHECK(hipGetLastError());
     }
     std::unique_ptr<TgswSet> set(new TgswSet);
@@ -378,14 +321,7 @@ void Cmux::reserve(CmuxScratch& scratch, const CmuxPlan& pl) {
 }
 
 void Cmux::launch(const TgswSet& set, hipStream_t stream, CmuxRows rows) {
-    check_owner(set);
-    if (rows.rows <= 0) return;
-    rows.n_set = (int32_t)set.n;
-    const unsigned grid = (unsigned)((rows.rows + kCmuxWaveRows - 1) / kCmuxWaveRows);
-    with_param_set(p_.l, [&](auto l, auto bgbit) {
-        hipLaunchKernelGGL((k_cmux_x1<decltype(l)::value, decltype(bgbit)::value>), dim3(grid), dim3(64 * kCmuxWaveRows), 0, stream, rows,
-                           (const double2*)set.spectrum, (const double2*)tw_);
-    });
+    launch_rows(set, stream, rows, [](auto ps) { return k_cmux_x1<ps.L, ps.BGBIT>; });
 }
 
 int Cmux::launch_tree(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth,
@@ -397,10 +333,7 @@ int Cmux::launch_tree(const TgswSet& set, CmuxScratch& scratch, hipStream_t stre
         hipLaunchKernelGGL(k_cmux_copy, dim3((unsigned)items), dim3(256), 0, stream, tables, n_tables, table_of, item0, out);
         return 1;
     }
-    const size_t row = (size_t)2 * kN;
-    const int64_t level0_rows = items << (depth - 1);
-    if ((depth >= 2 && scratch.a.items() < (size_t)level0_rows * row) || (depth >= 3 && scratch.b.items() < (size_t)(level0_rows / 2) * row))
-        throw std::invalid_argument("lut_tree: piece larger than the reserved scratch");
+    check_scratch(scratch, items, depth, "lut_tree: piece larger than the reserved scratch");
     const int32_t* src = tables;
     for (int32_t k = 0; k < depth; k++) {
         CmuxRows R;
@@ -414,8 +347,7 @@ int Cmux::launch_tree(const TgswSet& set, CmuxScratch& scratch, hipStream_t stre
         R.shared = k == 0;
         R.table_of = table_of;
         R.n_tables = n_tables;
-        // the last level writes the caller's rows; the others alternate between the two scratch buffers
-        R.dst = k == depth - 1 ? out : (k % 2 == 0 ? (int32_t*)scratch.a : (int32_t*)scratch.b);
+        R.dst = k == depth - 1 ? out : scratch_rows(scratch, k);  // the last level writes the caller's rows; level 0 the widest
         launch(set, stream, R);
         src = R.dst;
     }
@@ -423,14 +355,7 @@ int Cmux::launch_tree(const TgswSet& set, CmuxScratch& scratch, hipStream_t stre
 }
 
 void Cmux::launch_demux(const TgswSet& set, hipStream_t stream, DemuxRows rows) {
-    check_owner(set);
-    if (rows.rows <= 0) return;
-    rows.n_set = (int32_t)set.n;
-    const unsigned grid = (unsigned)((rows.rows + kCmuxWaveRows - 1) / kCmuxWaveRows);
-    with_param_set(p_.l, [&](auto l, auto bgbit) {
-        hipLaunchKernelGGL((k_demux_x1<decltype(l)::value, decltype(bgbit)::value>), dim3(grid), dim3(64 * kCmuxWaveRows), 0, stream, rows,
-                           (const double2*)set.spectrum, (const double2*)tw_);
-    });
+    launch_rows(set, stream, rows, [](auto ps) { return k_demux_x1<ps.L, ps.BGBIT>; });
 }
 
 int Cmux::launch_scatter(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth,
@@ -442,10 +367,7 @@ int Cmux::launch_scatter(const TgswSet& set, CmuxScratch& scratch, hipStream_t s
         hipLaunchKernelGGL(k_demux_add, dim3((unsigned)items), dim3(256), 0, stream, values, mem, out);
         return 1;
     }
-    const size_t row = (size_t)2 * kN;
-    const int64_t widest = items << (depth - 1);  // rows step depth - 2 writes
-    if ((depth >= 2 && scratch.a.items() < (size_t)widest * row) || (depth >= 3 && scratch.b.items() < (size_t)(widest / 2) * row))
-        throw std::invalid_argument("lut_scatter: piece larger than the reserved scratch");
+    check_scratch(scratch, items, depth, "lut_scatter: piece larger than the reserved scratch");
     const int32_t* src = values;
     for (int32_t t = 0; t < depth; t++) {
         DemuxRows R;
@@ -457,8 +379,7 @@ int Cmux::launch_scatter(const TgswSet& set, CmuxScratch& scratch, hipStream_t s
         R.sel_of = sel_of;
         R.src = src;
         const bool last = t == depth - 1;
-        // the last step writes the caller's rows over the memory; the others alternate so that step depth - 2 writes A
-        R.dst = last ? out : ((depth - 2 - t) % 2 == 0 ? (int32_t*)scratch.a : (int32_t*)scratch.b);
+        R.dst = last ? out : scratch_rows(scratch, depth - 2 - t);  // the last step writes the caller's rows over the memory; step depth - 2 the widest
         R.base = last ? mem : nullptr;
         launch_demux(set, stream, R);
         src = R.dst;

@@ -16,6 +16,7 @@ namespace ieache {
 
 struct OptionRow;  // evaluator_options.h
 struct TgswSet;    // cmux.h
+struct CmuxPlan;   // cmux_plan.h
 
 struct EvalStats {
     double total_ms = 0;         // wall time of the call on the GPU timeline (events on the stream)
@@ -289,6 +290,11 @@ private:
     // runs `once`, and again on the two-limb kernels if the rounding guard or the audit asks for it (evaluator.hip)
     template <class F>
     void run_guarded(bool inputs_intact, EvalStats* stats, F&& once);
+    // the piece loop of the calls on caller TGSW samples (evaluator.hip)
+    template <class Body, class KeySwitch>
+    void run_cmux_pieces(const CmuxPlan& pl, size_t count, int32_t levels, EvalStats* stats, Body&& body, int64_t ks_rows, KeySwitch&& ks);
+    template <class Body>
+    void run_cmux_pieces(const CmuxPlan& pl, size_t count, int32_t levels, EvalStats* stats, Body&& body);
     void init();
     void destroy();
     void begin_call();

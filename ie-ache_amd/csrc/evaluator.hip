@@ -971,8 +971,44 @@ void Evaluator::cmux_plan_figures(size_t count, int32_t depth, int64_t out[4]) c
     out[3] = pl.b_rows;
 }
 
-// The flat CMux: pieces of at most "cmux_piece_rows" rows on the evaluator's stream, one launch each.  No run_guarded: the
-// two-limb product is exact, nothing can trip.
+// The piece loop of the calls on caller TGSW samples, on the evaluator's stream: per piece of the plan body(first item, items),
+// which launches and returns how many kernels it did ("blind_rotate_launches", timed as blind_rotate_ms; one chunk per piece),
+// then -- a coefficient-level lookup that ends in LWE rows only -- ks(first item, rows done, rows) over the piece in runs of
+// at most ks_rows rows (one "keyswitch_launches" each, timed as keyswitch_ms).  The call counts as `levels` levels.  No
+// run_guarded: the two-limb product is exact, nothing can trip.
+template <class Body, class KeySwitch>
+void Evaluator::run_cmux_pieces(const CmuxPlan& pl, size_t count, int32_t levels, EvalStats* stats, Body&& body, int64_t ks_rows, KeySwitch&& ks) {
+    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(stats != nullptr && ks_rows > 0, stream_);
+    tall.mark();
+    for (int64_t i = 0; i < pl.pieces; i++) {
+        const int64_t i0 = cmux_piece_first(pl, i), cnt = cmux_piece_items(pl, (int64_t)count, i);
+        tbr.mark();
+        const int launches = body(i0, cnt);
+        tbr.mark();
+        HIP_CHECK(hipGetLastError());
+        if (stats) {
+            stats->blind_rotate_launches += launches;
+            stats->chunks++;
+        }
+        for (int64_t done = 0; ks_rows > 0 && done < cnt; done += ks_rows) {
+            tks.mark();
+            ks(i0, done, std::min<int64_t>(ks_rows, cnt - done));
+            tks.mark();
+            HIP_CHECK(hipGetLastError());
+            if (stats) stats->keyswitch_launches++;
+        }
+    }
+    tall.mark();
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    add_times(stats, tall, tbr, tks);
+    if (stats) stats->levels += levels;
+}
+template <class Body>
+void Evaluator::run_cmux_pieces(const CmuxPlan& pl, size_t count, int32_t levels, EvalStats* stats, Body&& body) {
+    run_cmux_pieces(pl, count, levels, stats, body, 0, [](int64_t, int64_t, int64_t) {});
+}
+
+// The flat CMux: pieces of at most "cmux_piece_rows" rows, one launch each.
 void Evaluator::cmux_device(const TgswSet& set, size_t count, const int32_t* d_sel_of, const Torus32* d_d1, const Torus32* d_d0, Torus32* d_out,
                             EvalStats* stats) {
     d_->cmux.check_owner(set);
@@ -982,31 +1018,17 @@ void Evaluator::cmux_device(const TgswSet& set, size_t count, const int32_t* d_s
     begin_call();
     if (count == 0) return;
     if (!d_d1 || !d_out) throw std::invalid_argument("cmux: null rows");
-    const CmuxPlan pl = cmux_plan((int64_t)count, -1, d_->opt.cmux_piece_rows);
-    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(false, stream_);
-    tall.mark();
-    for (int64_t i = 0; i < pl.pieces; i++) {
-        const int64_t r0 = cmux_piece_first(pl, i);
+    run_cmux_pieces(cmux_plan((int64_t)count, -1, d_->opt.cmux_piece_rows), count, 1, stats, [&](int64_t r0, int64_t rows) {
         CmuxRows R;
-        R.rows = cmux_piece_items(pl, (int64_t)count, i);
+        R.rows = rows;
         R.src = d_d1 + (size_t)r0 * row;
         R.src0 = d_d0 ? d_d0 + (size_t)r0 * row : nullptr;
         R.dst = d_out + (size_t)r0 * row;
         R.sel_of = d_sel_of ? d_sel_of + r0 : nullptr;
         R.item0 = r0;
-        tbr.mark();
         d_->cmux.launch(set, stream_, R);
-        tbr.mark();
-        HIP_CHECK(hipGetLastError());
-        if (stats) {
-            stats->blind_rotate_launches++;
-            stats->chunks++;
-        }
-    }
-    tall.mark();
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    add_times(stats, tall, tbr, tks);
-    if (stats) stats->levels += 1;
+        return 1;
+    });
 }
 
 // The CMux tree: pieces of whole items, each `depth` launches through the two scratch buffers, which are reserved for the
@@ -1025,23 +1047,9 @@ void Evaluator::lut_tree_device(const TgswSet& set, size_t count, int32_t depth,
     Lane& ln = d_->lane[0];
     const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
     d_->cmux.reserve(ln.cmux, pl);
-    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(false, stream_);
-    tall.mark();
-    for (int64_t i = 0; i < pl.pieces; i++) {
-        const int64_t i0 = cmux_piece_first(pl, i), cnt = cmux_piece_items(pl, (int64_t)count, i);
-        tbr.mark();
-        const int launches = d_->cmux.launch_tree(set, ln.cmux, stream_, i0, cnt, depth, d_sel_of, d_tables, n_tables, d_table_of, d_out + (size_t)i0 * row);
-        tbr.mark();
-        HIP_CHECK(hipGetLastError());
-        if (stats) {
-            stats->blind_rotate_launches += launches;
-            stats->chunks++;
-        }
-    }
-    tall.mark();
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    add_times(stats, tall, tbr, tks);
-    if (stats) stats->levels += depth;
+    run_cmux_pieces(pl, count, depth, stats, [&](int64_t i0, int64_t cnt) {
+        return d_->cmux.launch_tree(set, ln.cmux, stream_, i0, cnt, depth, d_sel_of, d_tables, n_tables, d_table_of, d_out + (size_t)i0 * row);
+    });
 }
 
 // The scatter: the tree's pieces and scratch with the steps run the other way (Cmux::launch_scatter); the last step of a piece
@@ -1060,24 +1068,10 @@ void Evaluator::lut_scatter_device(const TgswSet& set, size_t count, int32_t dep
     Lane& ln = d_->lane[0];
     const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
     d_->cmux.reserve(ln.cmux, pl);
-    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(false, stream_);
-    tall.mark();
-    for (int64_t i = 0; i < pl.pieces; i++) {
-        const int64_t i0 = cmux_piece_first(pl, i), cnt = cmux_piece_items(pl, (int64_t)count, i);
-        tbr.mark();
-        const int launches = d_->cmux.launch_scatter(set, ln.cmux, stream_, i0, cnt, depth, d_sel_of, d_values + (size_t)i0 * row,
-                                                     d_mem ? d_mem + (size_t)i0 * leaves * row : nullptr, d_out + (size_t)i0 * leaves * row);
-        tbr.mark();
-        HIP_CHECK(hipGetLastError());
-        if (stats) {
-            stats->blind_rotate_launches += launches;
-            stats->chunks++;
-        }
-    }
-    tall.mark();
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    add_times(stats, tall, tbr, tks);
-    if (stats) stats->levels += depth;
+    run_cmux_pieces(pl, count, depth, stats, [&](int64_t i0, int64_t cnt) {
+        return d_->cmux.launch_scatter(set, ln.cmux, stream_, i0, cnt, depth, d_sel_of, d_values + (size_t)i0 * row,
+                                       d_mem ? d_mem + (size_t)i0 * leaves * row : nullptr, d_out + (size_t)i0 * leaves * row);
+    });
 }
 
 // The rotation by caller selectors: the flat CMux's pieces, one launch each whatever the number of steps; no scratch.
@@ -1092,32 +1086,18 @@ void Evaluator::tlwe_rotate_device(const TgswSet& set, size_t count, int32_t ste
     begin_call();
     if (count == 0) return;
     if (!d_in || !d_out) throw std::invalid_argument("tlwe_rotate: null rows");
-    const CmuxPlan pl = cmux_plan((int64_t)count, -1, d_->opt.cmux_piece_rows);
-    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(false, stream_);
-    tall.mark();
-    for (int64_t i = 0; i < pl.pieces; i++) {
-        const int64_t r0 = cmux_piece_first(pl, i);
+    run_cmux_pieces(cmux_plan((int64_t)count, -1, d_->opt.cmux_piece_rows), count, steps, stats, [&](int64_t r0, int64_t rows) {
         RotateRows R;
-        R.rows = cmux_piece_items(pl, (int64_t)count, i);
+        R.rows = rows;
         R.src = d_in + (size_t)r0 * row;
         R.dst = d_out + (size_t)r0 * row;
         R.sel_of = d_sel_of;
         R.amount_of = d_amount_of;
         R.item0 = r0;
         R.steps = R.sel_stride = steps;
-        tbr.mark();
         d_->cmux.launch_rotate(set, stream_, R);
-        tbr.mark();
-        HIP_CHECK(hipGetLastError());
-        if (stats) {
-            stats->blind_rotate_launches++;
-            stats->chunks++;
-        }
-    }
-    tall.mark();
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    add_times(stats, tall, tbr, tks);
-    if (stats) stats->levels += steps;
+        return 1;
+    });
 }
 
 // The coefficient-level lookup: the tree's pieces; per piece the tree into the rows the lane keeps, their rotation in place, the
@@ -1147,36 +1127,21 @@ void Evaluator::lut_read_device(const TgswSet& set, size_t count, int32_t depth,
         ln.ext.reserve_exact((size_t)pl.items_per_piece, d_->ext_row_bytes());
         d_->ks.reserve(ln.ks, ks_piece, d_->opt, d_->force_generic_ks);
     }
-    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(stats != nullptr && !woks, stream_);
-    tall.mark();
     WorkDesc W{};
     W.flat_out = d_out;
     W.flat_type = kFlatRaw;
-    for (int64_t i = 0; i < pl.pieces; i++) {
-        const int64_t i0 = cmux_piece_first(pl, i), cnt = cmux_piece_items(pl, (int64_t)count, i);
-        Torus32* u = woks ? d_out + (size_t)i0 * out_stride : (Torus32*)ln.ext;
-        tbr.mark();
-        const int launches = d_->cmux.launch_read(set, ln.cmux, stream_, i0, cnt, depth, steps, d_sel_of, d_amount_of, d_tables, n_tables, d_table_of, coef,
-                                                  u, extract_stride());
-        tbr.mark();
-        HIP_CHECK(hipGetLastError());
-        if (stats) {
-            stats->blind_rotate_launches += launches;
-            stats->chunks++;
-        }
-        for (int64_t done = 0; !woks && done < cnt; done += ks_piece) {
-            const int64_t run = std::min<int64_t>(ks_piece, cnt - done);
-            tks.mark();
-            launch_keyswitch(d_, ln, rows_desc(W, i0 + done), run, u + (size_t)done * (size_t)extract_stride(), nullptr);
-            tks.mark();
-            HIP_CHECK(hipGetLastError());
-            if (stats) stats->keyswitch_launches++;
-        }
-    }
-    tall.mark();
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    add_times(stats, tall, tbr, tks);
-    if (stats) stats->levels += depth + steps;
+    // the extracted rows of a piece: the caller's, or the lane's for the key switch
+    auto rows_of = [&](int64_t i0) { return woks ? d_out + (size_t)i0 * out_stride : (Torus32*)ln.ext; };
+    run_cmux_pieces(
+        pl, count, depth + steps, stats,
+        [&](int64_t i0, int64_t cnt) {
+            return d_->cmux.launch_read(set, ln.cmux, stream_, i0, cnt, depth, steps, d_sel_of, d_amount_of, d_tables, n_tables, d_table_of, coef,
+                                        rows_of(i0), extract_stride());
+        },
+        woks ? 0 : ks_piece,
+        [&](int64_t i0, int64_t done, int64_t run) {
+            launch_keyswitch(d_, ln, rows_desc(W, i0 + done), run, rows_of(i0) + (size_t)done * (size_t)extract_stride(), nullptr);
+        });
 }
 
 void Evaluator::tlwe_extract_device(size_t count, const Torus32* d_tlwe, const int32_t* d_coef_of, Torus32* d_u, EvalStats* stats) {

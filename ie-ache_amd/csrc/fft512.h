@@ -106,10 +106,8 @@ __device__ __forceinline__ void build_twiddles(double2* tw, int tid, int nthread
     }
 }
 
-// The table is built once per context (k_build_twiddle_table) and copied into LDS at kernel start:
+// The table is built once per context (k_build_twiddle_table, blind_rotate_w64.hip) and copied into LDS at kernel start:
 // computing it per workgroup (4.5 sincospi per thread) cost ~4 % of a 16-step slice's vector work.
-__global__ __launch_bounds__(128) void k_build_twiddle_table(double2* tw) { build_twiddles(tw, threadIdx.x, 128); }
-
 __device__ __forceinline__ void load_twiddles(double2* sTw, const double2* __restrict__ gtw, int tid, int nthreads) {
     for (int idx = tid; idx < kTwElems; idx += nthreads) sTw[idx] = gtw[idx];
 }

@@ -3,7 +3,7 @@
 // the blind rotation's own step with the selector a TGSW sample of the caller's set instead of BK_i and the amount public.  It
 // is the last stage of vertical packing: after a CMux tree has chosen one of 2^d samples, this brings one of its N coefficients
 // to a public position.  k_rotate_x1 is k_blind_rotate_x1 (blind_rotate_w64.hip) with the key block chosen per row and step;
-// built from the pieces of br_step.h and fft512.h, no kernel of the blind rotation or of cmux.hip is touched.
+// built from the pieces of br_step.h and fft512.h, and of cmux_step.h, which it shares with the kernels of cmux.hip.
 // N = 1024, k = 1 and libtfhe's two (l, Bgbit), as br_supported() says.
 #include "cmux.h"
 
@@ -11,11 +11,7 @@
 #include <type_traits>
 
 #include "blind_rotate_w64.h"
-// fft512.h defines the kernel that builds the twiddle table; Cmux::prepare (cmux.hip) launches it, nothing here does
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"
-#include "br_step.h"
-#pragma clang diagnostic pop
+#include "cmux_step.h"
 
 namespace ieache {
 
@@ -53,13 +49,11 @@ __global__ __launch_bounds__(64 * G, 2) void k_rotate_x1(RotateRows A, const dou
     int32_t* acc_all = reinterpret_cast<int32_t*>(smem);
     double2* sT_all = reinterpret_cast<double2*>(smem + (size_t)G * 2 * kN * 4);
     double2* sTw = sT_all + G * kTile;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    double2* sT = sT_all + wave * kTile;
+    const WaveRow W = wave_prologue<G>(sT_all, sTw, gtw);
+    const int lane = W.lane, wave = W.wave;
+    double2* sT = W.sT;
     int32_t* acc = acc_all + wave * 2 * kN;
-    const int64_t r = (int64_t)blockIdx.x * G + wave;
-    load_twiddles(sTw, gtw, tid, 64 * G);
-    __syncthreads();  // the only workgroup barrier
+    const int64_t r = W.r;
     if (r >= A.rows) return;
     const LaneRoots R = make_roots(sTw, lane);
     {
@@ -73,14 +67,7 @@ __global__ __launch_bounds__(64 * G, 2) void k_rotate_x1(RotateRows A, const dou
     // lane t: (selector << 11) | amount of step t; amount 0 beyond the last step
     int32_t my_step = 0;
     if (lane < A.steps) {
-        const int64_t at = (A.item0 + r) * A.sel_stride + lane;
-        int64_t sel;
-        if (A.sel_of == nullptr) {
-            sel = at % A.n_set;
-        } else {
-            sel = (int64_t)A.sel_of[at];
-            sel = sel < 0 ? 0 : (sel >= A.n_set ? A.n_set - 1 : sel);
-        }
+        const int64_t sel = selector_at(A.sel_of, (A.item0 + r) * A.sel_stride + lane, A.n_set);
         const int32_t a = A.amount_of ? A.amount_of[lane] : (lane < 11 ? 2 * kN - (1 << lane) : 0);
         my_step = ((int32_t)sel << 11) | (a & (2 * kN - 1));
     }
@@ -107,24 +94,7 @@ __global__ __launch_bounds__(64 * G, 2) void k_rotate_x1(RotateRows A, const dou
             decompose_rotated(v0, v1, accb, accp, pb, jb, lane, dec_offset);
         };
         auto digit_row = [&](const int sh, const int brow, auto first) {
-            constexpr bool FIRST = decltype(first)::value;
-            double2 x[8], bA[8], bB[8];
-            digits_to_double2<BGBIT>(x, v0, v1, sh);
-            __builtin_amdgcn_sched_barrier(0);
-            auto req = [&]() { load_bk_block(bA, bk_rsrc, lane16, brow); };  // block 0: output 0, low limb
-            fft512_forward<true, 1, decltype(req), true>(x, sT, lane, R, req);
-            load_bk_block(bB, bk_rsrc, lane16, brow + kBlockBytes);          // block 1: output 0, high limb
-            __builtin_amdgcn_sched_barrier(0);
-            mac_row<FIRST>(s[0], x, bA);
-            __builtin_amdgcn_sched_barrier(0);
-            load_bk_block(bA, bk_rsrc, lane16, brow + 2 * kBlockBytes);      // block 2: output 1, low limb
-            __builtin_amdgcn_sched_barrier(0);
-            mac_row<FIRST>(s[1], x, bB);
-            __builtin_amdgcn_sched_barrier(0);
-            load_bk_block(bB, bk_rsrc, lane16, brow + 3 * kBlockBytes);      // block 3: output 1, high limb
-            __builtin_amdgcn_sched_barrier(0);
-            mac_row<FIRST>(s[2], x, bA);
-            mac_row<FIRST>(s[3], x, bB);
+            digit_row_two_limb<BGBIT, decltype(first)::value>(s, v0, v1, sh, bk_rsrc, lane16, brow, sT, lane, R);
         };
         decompose(pb0, jb4);
         digit_row(32 - BGBIT, 0, std::true_type{});
@@ -143,9 +113,7 @@ __global__ __launch_bounds__(64 * G, 2) void k_rotate_x1(RotateRows A, const dou
             uint32_t* accc = reinterpret_cast<uint32_t*>(acc) + c * kN;
 #pragma unroll
             for (int q = 0; q < 8; q++) {
-                double unused = 0.0;  // nothing to watch: every rounded sum is below 2^37
-                const uint32_t d0 = round_coef(s[2 * c][q].x, untwist_gain(q), false, unused) + (round_coef(s[2 * c + 1][q].x, untwist_gain(q), false, unused) << 16);
-                const uint32_t d1 = round_coef(s[2 * c][q].y, untwist_gain(q), false, unused) + (round_coef(s[2 * c + 1][q].y, untwist_gain(q), false, unused) << 16);
+                const uint32_t d0 = join_limbs(s[2 * c][q].x, s[2 * c + 1][q].x, q), d1 = join_limbs(s[2 * c][q].y, s[2 * c + 1][q].y, q);
                 const int32_t j = 64 * q + lane;
                 __hip_atomic_fetch_add(&accc[j], d0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                 __hip_atomic_fetch_add(&accc[j + kM], d1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -174,23 +142,7 @@ __global__ __launch_bounds__(256) void k_read_indices(const int32_t* __restrict_
     if (q < items) coef_of[q] = coef;
     if (q >= items * depth) return;
     const int64_t item = q / depth, k = q - item * depth;
-    const int64_t at = (item0 + item) * (depth + steps) + steps + k;
-    int64_t sel;
-    if (sel_of == nullptr) {
-        sel = at % n_set;
-    } else {
-        sel = (int64_t)sel_of[at];
-        sel = sel < 0 ? 0 : (sel >= n_set ? n_set - 1 : sel);
-    }
-    tree_sel[q] = (int32_t)sel;
-}
-
-template <class F>
-void with_param_set(int32_t l, F&& f) {
-    if (l == 3)
-        f(std::integral_constant<int, 3>{}, std::integral_constant<int, 7>{});
-    else
-        f(std::integral_constant<int, 2>{}, std::integral_constant<int, 10>{});
+    tree_sel[q] = (int32_t)selector_at(sel_of, (item0 + item) * (depth + steps) + steps + k, n_set);
 }
 
 constexpr size_t kRotateLds = (size_t)kCmuxWaveRows * 2 * kN * 4 + ((size_t)kCmuxWaveRows * kTile + kTwElems) * sizeof(double2);
@@ -199,16 +151,10 @@ LdsGrant g_rotate_grant[2];
 }  // namespace
 
 void Cmux::launch_rotate(const TgswSet& set, hipStream_t stream, RotateRows rows) {
-    check_owner(set);
-    if (rows.rows <= 0) return;
-    if (rows.steps < 0 || rows.steps > kRotateMaxSteps || rows.sel_stride < rows.steps) throw std::invalid_argument("tlwe_rotate: steps out of range");
-    rows.n_set = (int32_t)set.n;
-    const unsigned grid = (unsigned)((rows.rows + kCmuxWaveRows - 1) / kCmuxWaveRows);
-    with_param_set(p_.l, [&](auto l, auto bgbit) {
-        auto kernel = k_rotate_x1<decltype(l)::value, decltype(bgbit)::value>;
-        allow_dynamic_lds_once(g_rotate_grant[decltype(l)::value == 3 ? 0 : 1], (const void*)kernel, kRotateLds, "k_rotate_x1");
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * kCmuxWaveRows), kRotateLds, stream, rows, (const double2*)set.spectrum, (const double2*)tw_);
-    });
+    check_owner(set);  // ahead of the steps, as the shared launcher's own check would not be
+    if (rows.rows > 0 && (rows.steps < 0 || rows.steps > kRotateMaxSteps || rows.sel_stride < rows.steps))
+        throw std::invalid_argument("tlwe_rotate: steps out of range");
+    launch_rows(set, stream, rows, [](auto ps) { return k_rotate_x1<ps.L, ps.BGBIT>; }, kRotateLds, g_rotate_grant, "k_rotate_x1");
 }
 
 void Cmux::reserve_read(CmuxScratch& scratch, const CmuxPlan& pl, int32_t depth) {

@@ -5,7 +5,8 @@ Kernels are paired by mangled name.  Comments and every directive except the .am
 labels lose the function ordinal (.LBB12_3 -> .LBB_3), and each kernel is put in one of three classes:
   identical   the same instruction stream
   swapped     the same stream up to exchanged sources of a commutative instruction (v_mul_f64 v[0:1], v[2:3], v[4:5] against
-              v_mul_f64 v[0:1], v[4:5], v[2:3]): same opcode, same destination, same position, same count
+              v_mul_f64 v[0:1], v[4:5], v[2:3]; the three sources of v_add3_u32 in any order): same opcode, same destination,
+              same position, same count
   DIFFERENT   anything else, or a kernel only one file has
 with the instruction counts and .amdhsa_next_free_vgpr / _sgpr / group_segment_fixed_size / private_segment_fixed_size
 (VGPRs, SGPRs, static LDS, scratch) of both.  Exit status 1 if a kernel is DIFFERENT or any .amdhsa_* value differs."""
@@ -16,6 +17,9 @@ RESOURCES = ("next_free_vgpr", "next_free_sgpr", "group_segment_fixed_size", "pr
 # two-source operations whose sources may be exchanged, and three-source ones whose first two may
 COMMUTE2 = re.compile(r"^[vs]_(pk_)?(add|mul|mul_lo|mul_hi|and|or|xor|xnor|max|min)_[a-z]*\d+(_e32|_e64)?$")
 COMMUTE3 = re.compile(r"^v_(pk_)?(fma|mad)_[a-z]*\d+(_e64)?$")
+# ... and the one three-source operation ALL of whose sources commute, the integer add; v_xad_u32, v_and_or_b32 and
+# v_lshl_add_u32 treat their sources differently and stay strict
+COMMUTE_ALL3 = re.compile(r"^v_add3_u32(_e64)?$")
 
 
 def parse(text):
@@ -63,6 +67,8 @@ def swapped_sources(a, b):
         return oa[0] == ob[0] and oa[1] == ob[2] and oa[2] == ob[1]
     if COMMUTE3.match(ma) and len(oa) >= 4:
         return oa[0] == ob[0] and oa[1] == ob[2] and oa[2] == ob[1] and oa[3:] == ob[3:]
+    if COMMUTE_ALL3.match(ma) and len(oa) == 4:
+        return oa[0] == ob[0] and sorted(oa[1:]) == sorted(ob[1:])
     return False
 
 

@@ -74,6 +74,30 @@ def test_exchanged_sources_of_a_commutative_instruction_are_their_own_class():
     assert run(old, bad)[0] == 1 and "DIFFERENT" in run(old, bad)[1]
 
 
+ADD3 = "\tv_add3_u32 v8, v8, v18, v14\n"
+
+
+def test_the_three_sources_of_an_integer_add_commute():
+    old = kernel("_Z1aPd", ADD3 + BODY % (0, 0))
+    rc, text = run(old, kernel("_Z1aPd", ADD3.replace("v8, v18, v14", "v14, v18, v8") + BODY % (0, 0)))
+    assert rc == 0 and text.splitlines()[1].startswith("swapped") and "(1 exchanged)" in text
+    # the same destination and the same multiset of sources, nothing less: another source is another sum
+    for other in ("v14, v18, v9", "v8, v8, v18", "v18, v14, v14"):
+        rc, text = run(old, kernel("_Z1aPd", ADD3.replace("v8, v18, v14", other) + BODY % (0, 0)))
+        assert rc == 1 and text.splitlines()[1].startswith("DIFFERENT"), other
+    rc, text = run(old, kernel("_Z1aPd", ADD3.replace("v8, v8, v18, v14", "v14, v8, v18, v8") + BODY % (0, 0)))
+    assert rc == 1 and "DIFFERENT" in text
+
+
+def test_three_source_operations_whose_sources_do_not_all_commute_stay_strict():
+    for mnem in ("v_and_or_b32", "v_xad_u32", "v_lshl_add_u32"):
+        line = "\t%s v8, v9, v18, v14\n" % mnem
+        old = kernel("_Z1aPd", line + BODY % (0, 0))
+        for other in ("v14, v18, v9", "v18, v9, v14", "v9, v14, v18"):
+            rc, text = run(old, kernel("_Z1aPd", line.replace("v9, v18, v14", other) + BODY % (0, 0)))
+            assert rc == 1 and text.splitlines()[1].startswith("DIFFERENT"), (mnem, other)
+
+
 def test_real_differences_fail():
     old = kernel("_Z1aPd", BODY % (0, 0))
     extra = kernel("_Z1aPd", (BODY % (0, 0)).replace("\tv_sub_u32", "\tv_mov_b32_e32 v11, v1\n\tv_sub_u32"))
