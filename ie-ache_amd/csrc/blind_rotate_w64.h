@@ -17,8 +17,8 @@ void prepare_spectrum(const Params& p, const Torus32* d_bk_raw, double2* d_bkf, 
 void prepare_spectrum1(const Params& p, const Torus32* d_bk_raw, double2* d_bkf1, hipStream_t stream);
 void build_twiddle_table(double2* d_tw, hipStream_t stream);
 
-// the one place that turns the runtime parameter set into template arguments (br_supported(): these two only); the
-// CMux family (cmux.hip, rotate.hip) dispatches its kernels through it as well
+// the one place that turns the runtime parameter set into template arguments (br_supported(): these two only).  The CMux
+// family (cmux.hip, rotate.hip) names its two fixed builds by ParamSet too but dispatches by the SET's gadget: with_gadget, cmux_step.h
 template <int L_, int BGBIT_>
 struct ParamSet {
     static constexpr int L = L_, BGBIT = BGBIT_, index = L_ == 3 ? 0 : 1;

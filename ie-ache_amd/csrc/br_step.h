@@ -21,6 +21,7 @@
 //   round + ds_add_u32 update     --                                     all (a shared form reorders the GUARD = 2 builds of _w2r / _w4r)
 //   two-limb digit row            _x1 k_cmux_x1 k_demux_x1 k_rotate_x1   --
 //   limb recombination            _x1 k_cmux_x1 k_demux_x1 k_rotate_x1   -- (k_cmux_x1: the three sources of 16 v_add3_u32 come out in another order)
+//   ... with a run-time digit width k_cmux_rt k_demux_rt k_rotate_rt      -- (digit_row_two_limb_rt, decomposition_offset_rt: siblings, the rows above keep their code)
 // k_cmux_x1 / k_demux_x1 (cmux.hip) and k_rotate_x1 (rotate.hip) are the CMux family: _x1's step on caller TGSW samples.  What
 // only they share is cmux_step.h, under the same rule:
 //   selector rule                 k_demux_x1 k_rotate_x1 k_read_indices  k_cmux_x1 (its flat form implies another position than it reads: any shared form moves it)
@@ -193,6 +194,43 @@ __device__ __forceinline__ void digit_row_two_limb(double2 (&s)[4][8], const uin
     mac_row<FIRST>(s[2], x, bA);
     mac_row<FIRST>(s[3], x, bB);
 }
+// ---- the same with the gadget (l, Bgbit) a launch argument (the run-time builds of the CMux family: cmux.hip, rotate.hip) ----
+// Siblings, not a parameter of the pieces above: those keep their code.  l and bgbit are wave-uniform (SGPRs); the width operand
+// of v_bfe_i32 may be a register, the offset is formed once per wave.
+__device__ __forceinline__ uint32_t decomposition_offset_rt(int l, int bgbit) {
+    const uint32_t halfBg = 1u << (bgbit - 1);
+    uint32_t dec_offset = 0;
+#pragma unroll 1
+    for (int q = 1; q <= l; q++) dec_offset += halfBg << (32 - q * bgbit);
+    return dec_offset;
+}
+template <bool FIRST>
+__device__ __forceinline__ void digit_row_two_limb_rt(double2 (&s)[4][8], const uint32_t (&v0)[8], const uint32_t (&v1)[8], int sh, int bgbit,
+                                                      __amdgpu_buffer_rsrc_t bk_rsrc, int lane16, int brow, double2* sT, int lane, const LaneRoots& R) {
+    constexpr int kBlockBytes = kM * (int)sizeof(double2);
+    double2 x[8], bA[8], bB[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const int32_t e0 = __builtin_amdgcn_sbfe((int32_t)v0[r], sh, bgbit), e1 = __builtin_amdgcn_sbfe((int32_t)v1[r], sh, bgbit);
+        x[r] = make_double2((double)e0, (double)e1);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    auto req = [&]() { load_bk_block(bA, bk_rsrc, lane16, brow); };
+    fft512_forward<true, 1, decltype(req), true>(x, sT, lane, R, req);
+    load_bk_block(bB, bk_rsrc, lane16, brow + kBlockBytes);
+    __builtin_amdgcn_sched_barrier(0);
+    mac_row<FIRST>(s[0], x, bA);
+    __builtin_amdgcn_sched_barrier(0);
+    load_bk_block(bA, bk_rsrc, lane16, brow + 2 * kBlockBytes);
+    __builtin_amdgcn_sched_barrier(0);
+    mac_row<FIRST>(s[1], x, bB);
+    __builtin_amdgcn_sched_barrier(0);
+    load_bk_block(bB, bk_rsrc, lane16, brow + 3 * kBlockBytes);
+    __builtin_amdgcn_sched_barrier(0);
+    mac_row<FIRST>(s[2], x, bA);
+    mac_row<FIRST>(s[3], x, bB);
+}
+
 // ... and a coefficient back from its two inverse-transformed limb sums: lo + (hi << 16) mod 2^32, register q's gain folded
 // into the rounding.  Nothing to watch: every rounded sum is below 2^37 of the 2^53 an FP64 mantissa holds.
 __device__ __forceinline__ uint32_t join_limbs(double lo, double hi, int q) {

@@ -1185,6 +1185,86 @@ int ieache_lut_read(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32
     });
 }
 
+// ---- sets with a gadget of their own, and the replace write (section 3i) ----
+ieache_tgsw* ieache_tgsw_prepare_gadget_device(ieache_ctx* ctx, const int32_t* d_samples, size_t n, int32_t l, int32_t Bgbit) {
+    ieache_tgsw* out = nullptr;
+    guarded([&] {
+        if (!ctx || !d_samples) return fail(IEACHE_EINVAL, "null argument");
+        if (const char* why = gadget_refusal(ctx->eval->params(), l, Bgbit)) return fail(IEACHE_EINVAL, why);
+        if (n < 1) return fail(IEACHE_EINVAL, "tgsw_prepare: no samples");
+        require_device_pointer(d_samples, "d_samples");
+        std::unique_ptr<ieache_tgsw> h(new ieache_tgsw);
+        h->set.reset(ctx->eval->tgsw_prepare_device(d_samples, n, l, Bgbit));
+        out = h.release();
+        return 0;
+    });
+    return out;
+}
+
+ieache_tgsw* ieache_tgsw_prepare_gadget(ieache_ctx* ctx, const int32_t* samples, size_t n, int32_t l, int32_t Bgbit) {
+    ieache_tgsw* out = nullptr;
+    guarded([&] {
+        if (!ctx || !samples) return fail(IEACHE_EINVAL, "null argument");
+        const Params& p = ctx->eval->params();
+        if (const char* why = gadget_refusal(p, l, Bgbit)) return fail(IEACHE_EINVAL, why);
+        if (n < 1) return fail(IEACHE_EINVAL, "tgsw_prepare: no samples");
+        HIP_CHECK(hipSetDevice(ctx->eval->device()));
+        DevRows words(n, (size_t)2 * (size_t)l * 2 * (size_t)p.N);  // the int32 samples: scratch of this call
+        HIP_CHECK(hipMemcpy(words.p, samples, words.rows * words.stride * 4, hipMemcpyHostToDevice));
+        std::unique_ptr<ieache_tgsw> h(new ieache_tgsw);
+        h->set.reset(ctx->eval->tgsw_prepare_device(words.p, n, l, Bgbit));
+        out = h.release();
+        return 0;
+    });
+    return out;
+}
+
+int ieache_tgsw_gadget(const ieache_tgsw* set, int32_t* l, int32_t* Bgbit) {
+    return guarded([&] {
+        if (!set || !set->set) return fail(IEACHE_EINVAL, "null argument");
+        if (l) *l = set->set->l;
+        if (Bgbit) *Bgbit = set->set->Bgbit;
+        return 0;
+    });
+}
+
+namespace {
+int check_write(int32_t depth) {
+    if (depth < 0 || depth > IEACHE_LUT_TREE_MAX_DEPTH) return fail(IEACHE_EINVAL, "lut_write: depth must lie in 0 .. 12");
+    return 0;
+}
+}  // namespace
+
+int ieache_lut_write_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* d_sel_of, const int32_t* d_new,
+                            const int32_t* d_mem, int32_t* d_out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_tgsw(ctx, set)) return rc;
+        if (!d_new || !d_mem || !d_out) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_write(depth)) return rc;
+        require_device_pointers(count, {{d_sel_of, "d_sel_of", true}, {d_new, "d_new"}, {d_mem, "d_mem"}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->lut_write_device(*set->set, count, depth, d_sel_of, d_new, d_mem, d_out, st); });
+    });
+}
+
+int ieache_lut_write(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* sel_of, const int32_t* fresh,
+                     const int32_t* mem, int32_t* out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_tgsw(ctx, set)) return rc;
+        if (!fresh || !mem || !out) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_write(depth)) return rc;
+        if (const int rc = check_indices(sel_of, count * (size_t)depth, (int64_t)set->set->n, "lut_write: sel_of")) return rc;
+        HostCall h(ctx, count);
+        const size_t sample = (size_t)2 * (size_t)h.p.N, rows = count << depth;
+        StagedRows dv(h.ev, kStageTlweA, count, sample, fresh, sample), dsel = h.words(kStagePolyOf, sel_of, count * (size_t)depth);
+        // the memory goes into the result rows and the call runs in place
+        StagedRows dout(h.ev, kStageOut, rows, sample);
+        if (rows) HIP_CHECK(hipMemcpy(dout.p, mem, rows * sample * 4, hipMemcpyHostToDevice));
+        with_stats(stats, [&](EvalStats* st) { h.ev.lut_write_device(*set->set, count, depth, dsel.p, dv.p, dout.p, dout.p, st); });
+        dout.download(out, sample);
+        return 0;
+    });
+}
+
 int ieache_tlwe_extract_device(ieache_ctx* ctx, size_t count, const int32_t* d_tlwe, const int32_t* d_coef_of, int32_t* d_u, ieache_stats* stats) {
     return guarded([&] {
         if (!ctx || !d_tlwe || !d_u) return fail(IEACHE_EINVAL, "null argument");

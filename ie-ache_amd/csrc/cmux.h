@@ -1,7 +1,8 @@
 // The one door to the operations on TGSW samples the caller supplies (include/ieache.h):
 //   section 3f  the CMux, the CMux-tree lookup built from it, and the extraction of a coefficient of a TLWE sample;
 //   section 3g  the scatter that writes at an encrypted index;
-//   section 3h  the rotation by caller selectors and the coefficient-level lookup.
+//   section 3h  the rotation by caller selectors and the coefficient-level lookup;
+//   section 3i  sets with a gadget of their own, and the replace write.
 // The kernels, the spectrum form of a prepared set, the twiddle table and the scratch of a tree are behind this object; how
 // a call is cut is cmux_plan.h.  Kernels: cmux.hip (3f, 3g) and rotate.hip (3h); what the two share is cmux_step.h.
 #pragma once
@@ -19,10 +20,12 @@ struct LdsGrant;  // device_common.h
 // A prepared set of n TGSW samples: their two-limb spectrum [n][2l][q = 2 c + limb][8][64] double2 -- the layout of the
 // bootstrapping key's spectrum, one sample where that has one BK_i (192 KB at l = 3).  It owns its device memory and nothing of
 // the context's, so it may be freed before or after the context that made it is closed; `owner` names that context among all
-// the process has had, and only it accepts the set.
+// the process has had, and only it accepts the set.  The set carries its gadget (l, Bgbit): the context's unless the caller
+// prepared it with another (section 3i), and the one everything about the set is sized and dispatched by -- never the key's.
 struct TgswSet {
     dev::DeviceBuffer<double2> spectrum;
     size_t n = 0;
+    int32_t l = 0, Bgbit = 0;
     uint64_t owner = 0;
     int device = 0;
 };
@@ -92,12 +95,28 @@ struct CmuxScratch {
 };
 
 // One per evaluator.  All methods expect the evaluator's device to be current.
+// What ieache_tgsw_prepare_gadget accepts on a context with parameters p: null, or the rule that failed.  HIP-free.
+inline const char* gadget_refusal(const Params& p, int32_t l, int32_t Bgbit) {
+    if (p.N != 1024 || p.k != 1) return "tgsw_prepare_gadget: the CMux kernels cover N = 1024, k = 1 only";
+    if (l < 1) return "tgsw_prepare_gadget: l must be at least 1";
+    if (Bgbit < 1 || Bgbit >= 32) return "tgsw_prepare_gadget: Bgbit must lie in 1 .. 31";
+    if ((int64_t)l * Bgbit > 32) return "tgsw_prepare_gadget: l x Bgbit must not exceed 32";
+    if (((int64_t)2 * l * p.N << Bgbit) > ((int64_t)1 << 32))
+        return "tgsw_prepare_gadget: 2 l N 2^Bgbit must not exceed 2^32 (the exactness bound of the two-limb product, Params::br_exact)";
+    return nullptr;
+}
+
 struct Cmux {
-    void init(const Params& p, int device);
+    // runtime_always: where the debug option "cmux_gadget_runtime" lives (null: never) -- non-zero sends every set to the
+    // run-time-gadget builds of the kernels, libtfhe's two gadgets included
+    void init(const Params& p, int device, const int64_t* runtime_always = nullptr);
     uint64_t id() const { return id_; }
     // d_samples [n][2l][2][N] int32 on the device -> a new set (the caller owns it).  Synchronises the stream.  Throws
     // std::invalid_argument where the parameter set is not one of the 64-lane kernels' (br_supported(), br_plan.h) or n < 1.
     TgswSet* prepare(const int32_t* d_samples, size_t n, hipStream_t stream);
+    // the same with a gadget of the set's own, d_samples [n][2l][2][N] with that l, on any context with N = 1024 and k = 1
+    // whatever the key's gadget.  std::invalid_argument naming the rule of gadget_refusal() that failed.
+    TgswSet* prepare(const int32_t* d_samples, size_t n, int32_t l, int32_t Bgbit, hipStream_t stream);
     // std::invalid_argument unless `set` was prepared by this object
     void check_owner(const TgswSet& set) const;
     // scratch for every piece of a tree's plan ahead of the loop, so that no piece allocates
@@ -116,6 +135,13 @@ struct Cmux {
     // the tree's (cmux_plan.h).  Returns the kernel launches issued (depth, or 1 for the add of depth 0).
     int launch_scatter(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth,
                        const int32_t* sel_of, const int32_t* values, const int32_t* mem, int32_t* out);
+    // one piece of a replace write (section 3i): old_i = the tree of item i's own memory rows by its selectors, delta_i = fresh_i
+    // - old_i mod 2^32 (k_write_delta, over scratch.rows), the scatter of delta onto the memory -> out; out == mem is allowed: a
+    // piece reads and writes its own items' rows only, the tree has finished reading them when the scatter's last step -- the
+    // only launch that writes them -- starts (one stream), and that step is in place by k_demux_x1's argument.  scratch as
+    // reserve_read's.  Returns the kernel launches issued.
+    int launch_write(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, const int32_t* sel_of,
+                     const int32_t* fresh, const int32_t* mem, int32_t* out);
     // one launch of `rows.rows` rotations, all `rows.steps` steps of a row inside it (rotate.hip); no scratch
     void launch_rotate(const TgswSet& set, hipStream_t stream, RotateRows rows);
     // a coefficient-level lookup (lut_read): besides the tree's buffers, the selected rows and the indices of the largest piece
@@ -133,11 +159,13 @@ struct Cmux {
 private:
     // The one launcher of the one-wave kernels (k_cmux_x1, k_demux_x1, k_rotate_x1), defined in cmux_step.h: the owner check,
     // nothing for no rows, n_set filled in, kCmuxWaveRows rows per workgroup, kernel_of(parameter set) launched with `lds`
-    // bytes of dynamic LDS -- which `grant`[parameter set], where given, allows first, once per device.
+    // bytes of dynamic LDS -- which `grant`[build], where given, allows first, once per device, under the build's own name
+    // (`name`: the two fixed builds, `name_rt`: the run-time-gadget build).
     template <class Rows, class KernelOf>
     void launch_rows(const TgswSet& set, hipStream_t stream, Rows rows, KernelOf kernel_of, size_t lds = 0, dev::LdsGrant* grant = nullptr,
-                     const char* name = nullptr);
+                     const char* name = nullptr, const char* name_rt = nullptr);
     Params p_;
+    const int64_t* runtime_always_ = nullptr;
     int device_ = 0;
     uint64_t id_ = 0;
     dev::DeviceBuffer<double2> tw_;  // the 64-lane transforms' twiddle table, built with the first set

@@ -2,7 +2,8 @@
 // product of libtfhe's tGswExternMulToTLwe on the provably exact two-limb spectrum -- k_blind_rotate_x1's step
 // (blind_rotate_w64.hip) with the operand taken from global memory instead of a rotating LDS accumulator and the key block
 // chosen per row.  Built from the pieces of br_step.h and fft512.h, which that kernel uses too, and of cmux_step.h.
-// N = 1024, k = 1 and libtfhe's two (l, Bgbit), as br_supported() says; the extraction kernel at the end takes any set.
+// N = 1024, k = 1; libtfhe's two (l, Bgbit) as template arguments (k_cmux_x1, k_demux_x1) and every other admissible gadget of a
+// set as launch arguments (k_cmux_rt, k_demux_rt: section 3i); the extraction kernel at the end takes any set.
 // k_demux_x1 is the same product as a demultiplexer: the write at an encrypted index (section 3g).
 #include "cmux.h"
 
@@ -242,6 +243,190 @@ __global__ __launch_bounds__(64 * G, 2) void k_demux_x1(DemuxRows A, const doubl
     }
 }
 
+// ---- the two kernels once more with the set's gadget (l, bgbit) as launch arguments ----
+// A set prepared with a gadget of its own (ieache_tgsw_prepare_gadget) that is not one of the two above runs here.  The bodies
+// are k_cmux_x1's and k_demux_x1's line for line -- what those say about registers, the buffer path, the opaque copies and the
+// write in place holds here and is not repeated -- with four differences, all wave-uniform: the decomposition offset comes
+// from decomposition_offset_rt, the digit row is digit_row_two_limb_rt (the width of its v_bfe_i32 a register), the bytes
+// of a sample in the set are 2 l kRowBytes computed once, and the row loop runs to 2 l.  They are copies and not a parameter
+// of the kernels above because those must keep their code (br_step.h's rule).  Exactness: 2 l x 1024 x 2^(bgbit-1) x 2^15 <= 2^46
+// of 2^53 for every gadget the door admits (l bgbit <= 32, 2 l N 2^bgbit <= 2^32), so no guard here either.
+template <int G = kCmuxWaveRows>
+__global__ __launch_bounds__(64 * G, 2) void k_cmux_rt(CmuxRows A, const double2* __restrict__ bkf, const double2* __restrict__ gtw, int l, int bgbit) {
+    __shared__ __align__(16) double2 sT_all[G * kTile];
+    __shared__ __align__(16) double2 sTw[kTwElems];
+    const WaveRow W = wave_prologue<G>(sT_all, sTw, gtw);
+    const int lane = W.lane;
+    double2* sT = W.sT;
+    const int64_t r = W.r;
+    if (r >= A.rows) return;
+    const LaneRoots R = make_roots(sTw, lane);
+
+    const int32_t* p1;
+    const int32_t* p0;
+    int64_t sel;
+    bool implied;
+    if (A.depth < 0) {
+        p1 = A.src + (size_t)r * 2 * kN;
+        p0 = A.src0 ? A.src0 + (size_t)r * 2 * kN : nullptr;
+        implied = A.sel_of == nullptr;
+        sel = implied ? A.item0 + r : (int64_t)A.sel_of[r];
+    } else {
+        const int64_t item = r / A.width, pair = r - item * A.width;
+        int64_t block = item;
+        if (A.shared) block = clamp_index(A.table_of ? (int64_t)A.table_of[A.item0 + item] : 0, A.n_tables);
+        p0 = A.src + ((size_t)block * 2 * A.width + 2 * (size_t)pair) * 2 * kN;
+        p1 = p0 + 2 * kN;
+        const int64_t at = (A.item0 + item) * A.depth + A.level;
+        implied = A.sel_of == nullptr;
+        sel = implied ? at : (int64_t)A.sel_of[at];
+    }
+    if (implied)
+        sel %= A.n_set;
+    else
+        sel = clamp_index(sel, A.n_set);
+    int32_t* po = A.dst + (size_t)r * 2 * kN;
+    const uint32_t keep0 = p0 ? 0xFFFFFFFFu : 0u;
+    if (!p0) p0 = p1;
+    const __amdgpu_buffer_rsrc_t r1 = row_resource(p1), r0 = row_resource(p0), ro = row_resource(po);
+    const int lane4 = lane * 4;
+
+    constexpr int kBlockBytes = kM * (int)sizeof(double2), kRowBytes = 4 * kBlockBytes;
+    const int rows2l = 2 * l, step_bytes = rows2l * kRowBytes;
+    const __amdgpu_buffer_rsrc_t bk_rsrc = bk_resource(bkf + (size_t)sel * ((size_t)step_bytes / sizeof(double2)), 1, step_bytes);
+    const int lane16 = bk_lane_offset(lane);
+    const uint32_t dec_offset = decomposition_offset_rt(l, bgbit);
+
+    double2 s[4][8];
+    uint32_t v0[8], v1[8];
+    auto decompose = [&](const int c) {
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const int j = c * kN + 64 * q;
+            const uint32_t a0 = row_word(r0, lane4, j) & keep0, a1 = row_word(r0, lane4, j + kM) & keep0;
+            v0[q] = ((row_word(r1, lane4, j) - a0) + dec_offset) ^ dec_offset;
+            v1[q] = ((row_word(r1, lane4, j + kM) - a1) + dec_offset) ^ dec_offset;
+        }
+    };
+    decompose(0);
+    digit_row_two_limb_rt<true>(s, v0, v1, 32 - bgbit, bgbit, bk_rsrc, lane16, 0, sT, lane, R);
+#pragma unroll 1
+    for (int row = 1; row < rows2l; row++) {
+        const int c = row >= l ? 1 : 0, q = row - c * l;
+        if (q == 0) decompose(1);
+        digit_row_two_limb_rt<false>(s, v0, v1, 32 - (q + 1) * bgbit, bgbit, bk_rsrc, lane16, row * kRowBytes, sT, lane, R);
+    }
+    const int32_t* p0e = p0;
+    asm volatile("" : "+s"(p0e));
+    const __amdgpu_buffer_rsrc_t r0e = row_resource(p0e);
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        fft512_inverse_pair<true>(s[2 * c], s[2 * c + 1], sT, lane, R);
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const uint32_t e0 = join_limbs(s[2 * c][q].x, s[2 * c + 1][q].x, q), e1 = join_limbs(s[2 * c][q].y, s[2 * c + 1][q].y, q);
+            const int j = c * kN + 64 * q;
+            const uint32_t a0 = row_word(r0e, lane4, j) & keep0, a1 = row_word(r0e, lane4, j + kM) & keep0;
+            __builtin_amdgcn_raw_buffer_store_b32(a0 + e0, ro, lane4, j * 4, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(a1 + e1, ro, lane4, (j + kM) * 4, 0);
+        }
+    }
+}
+
+template <int G = kCmuxWaveRows>
+__global__ __launch_bounds__(64 * G, 2) void k_demux_rt(DemuxRows A, const double2* __restrict__ bkf, const double2* __restrict__ gtw, int l, int bgbit) {
+    __shared__ __align__(16) double2 sT_all[G * kTile];
+    __shared__ __align__(16) double2 sTw[kTwElems];
+    const WaveRow W = wave_prologue<G>(sT_all, sTw, gtw);
+    const int lane = W.lane;
+    double2* sT = W.sT;
+    const int64_t r = W.r;
+    if (r >= A.rows) return;
+    const LaneRoots R = make_roots(sTw, lane);
+
+    const int64_t item = r / A.width;
+    const int64_t sel = selector_at(A.sel_of, (A.item0 + item) * A.depth + (A.depth - 1 - A.step), A.n_set);
+    const int32_t* pp = A.src + (size_t)r * 2 * kN;
+    int32_t* po = A.dst + (size_t)r * 4 * kN;
+    const bool add = A.base != nullptr;
+    const int32_t* pb = add ? A.base + (size_t)r * 4 * kN : pp;
+    const __amdgpu_buffer_rsrc_t rp = row_resource(pp);
+    const int lane4 = lane * 4;
+
+    constexpr int kBlockBytes = kM * (int)sizeof(double2), kRowBytes = 4 * kBlockBytes;
+    const int rows2l = 2 * l, step_bytes = rows2l * kRowBytes;
+    const __amdgpu_buffer_rsrc_t bk_rsrc = bk_resource(bkf + (size_t)sel * ((size_t)step_bytes / sizeof(double2)), 1, step_bytes);
+    const int lane16 = bk_lane_offset(lane);
+    const uint32_t dec_offset = decomposition_offset_rt(l, bgbit);
+
+    double2 s[4][8];
+    uint32_t v0[8], v1[8];
+    auto decompose = [&](const int c) {
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const int j = c * kN + 64 * q;
+            v0[q] = (row_word(rp, lane4, j) + dec_offset) ^ dec_offset;
+            v1[q] = (row_word(rp, lane4, j + kM) + dec_offset) ^ dec_offset;
+        }
+    };
+    decompose(0);
+    digit_row_two_limb_rt<true>(s, v0, v1, 32 - bgbit, bgbit, bk_rsrc, lane16, 0, sT, lane, R);
+#pragma unroll 1
+    for (int row = 1; row < rows2l; row++) {
+        const int c = row >= l ? 1 : 0, q = row - c * l;
+        if (q == 0) decompose(1);
+        digit_row_two_limb_rt<false>(s, v0, v1, 32 - (q + 1) * bgbit, bgbit, bk_rsrc, lane16, row * kRowBytes, sT, lane, R);
+    }
+    const int32_t* ppe = pp;
+    asm volatile("" : "+s"(ppe));
+    asm volatile("" : "+s"(po));
+    asm volatile("" : "+s"(pb));
+    const __amdgpu_buffer_rsrc_t rpe = row_resource(ppe);
+    const __amdgpu_buffer_rsrc_t ro0 = row_resource(po), ro1 = row_resource(po + 2 * kN);
+    const __amdgpu_buffer_rsrc_t rb0 = row_resource(pb), rb1 = row_resource(pb + 2 * kN);
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        fft512_inverse_pair<true>(s[2 * c], s[2 * c + 1], sT, lane, R);
+        uint32_t h0[8], h1[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            h0[q] = join_limbs(s[2 * c][q].x, s[2 * c + 1][q].x, q);
+            h1[q] = join_limbs(s[2 * c][q].y, s[2 * c + 1][q].y, q);
+        }
+        if (add) {
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                const int j = c * kN + 64 * q;
+                const uint32_t p0 = row_word(rpe, lane4, j), p1 = row_word(rpe, lane4, j + kM);
+                const uint32_t b00 = row_word(rb0, lane4, j), b01 = row_word(rb0, lane4, j + kM);
+                const uint32_t b10 = row_word(rb1, lane4, j), b11 = row_word(rb1, lane4, j + kM);
+                __builtin_amdgcn_raw_buffer_store_b32(b00 + (p0 - h0[q]), ro0, lane4, j * 4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(b01 + (p1 - h1[q]), ro0, lane4, (j + kM) * 4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(b10 + h0[q], ro1, lane4, j * 4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(b11 + h1[q], ro1, lane4, (j + kM) * 4, 0);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                const int j = c * kN + 64 * q;
+                const uint32_t p0 = row_word(rpe, lane4, j), p1 = row_word(rpe, lane4, j + kM);
+                __builtin_amdgcn_raw_buffer_store_b32(p0 - h0[q], ro0, lane4, j * 4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(p1 - h1[q], ro0, lane4, (j + kM) * 4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(h0[q], ro1, lane4, j * 4, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(h1[q], ro1, lane4, (j + kM) * 4, 0);
+            }
+        }
+    }
+}
+
+// ---- the subtraction of a replace write (include/ieache.h section 3i): delta_i = new_i - old_i mod 2^32, in place over old ----
+// A pass of its own over the piece's [items][2][N] words between the tree and the scatter: 16 KB read and 8 KB written per item,
+// against the 2^depth rows of 8 KB the scatter's last step moves.
+__global__ __launch_bounds__(256) void k_write_delta(const int32_t* __restrict__ fresh, int32_t* old_to_delta) {
+    const size_t at = (size_t)blockIdx.x * 2 * kN;
+    for (int q = threadIdx.x; q < 2 * kN; q += 256) old_to_delta[at + q] = (int32_t)((uint32_t)fresh[at + q] - (uint32_t)old_to_delta[at + q]);
+}
+
 // ---- a scatter of depth 0: out_i = mem_i + v_i (mem null: v_i).  out == mem is sound: a word is read by the thread that stores it ----
 __global__ __launch_bounds__(256) void k_demux_add(const int32_t* __restrict__ values, const int32_t* mem, int32_t* out) {
     const size_t at = (size_t)blockIdx.x * 2 * kN;
@@ -283,14 +468,20 @@ int32_t* scratch_rows(CmuxScratch& scratch, int32_t from_widest) { return from_w
 
 }  // namespace
 
-void Cmux::init(const Params& p, int device) {
+void Cmux::init(const Params& p, int device, const int64_t* runtime_always) {
     p_ = p;
+    runtime_always_ = runtime_always;
     device_ = device;
     id_ = g_next_id.fetch_add(1);
 }
 
 TgswSet* Cmux::prepare(const int32_t* d_samples, size_t n, hipStream_t stream) {
     if (!br_supported(p_)) throw std::invalid_argument("tgsw_prepare: the CMux kernels cover N = 1024, k = 1 with (l, Bgbit) = (3, 7) or (2, 10) only");
+    return prepare(d_samples, n, p_.l, p_.Bgbit, stream);
+}
+
+TgswSet* Cmux::prepare(const int32_t* d_samples, size_t n, int32_t l, int32_t Bgbit, hipStream_t stream) {
+    if (const char* why = gadget_refusal(p_, l, Bgbit)) throw std::invalid_argument(why);
     if (!d_samples || n < 1) throw std::invalid_argument("tgsw_prepare: no samples");
     if (n > ((size_t)1 << 20)) throw std::invalid_argument("tgsw_prepare: more than 2^20 samples");
     if (!tw_) {
@@ -301,11 +492,15 @@ TgswSet* Cmux::prepare(const int32_t* d_samples, size_t n, hipStream_t stream) {
     std::unique_ptr<TgswSet> set(new TgswSet);
     Params as_key = p_;
     as_key.n = (int32_t)n;  // the spectrum kernel sees n samples where the bootstrapping key has n blocks BK_i
+    as_key.l = l;           // ... of the set's 2l rows: it works per polynomial and knows no gadget
+    as_key.Bgbit = Bgbit;
     set->spectrum.allocate(spectrum_elems(as_key));
     prepare_spectrum(as_key, d_samples, set->spectrum, stream);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(stream));
     set->n = n;
+    set->l = l;
+    set->Bgbit = Bgbit;
     set->owner = id_;
     set->device = device_;
     return set.release();
@@ -321,7 +516,12 @@ void Cmux::reserve(CmuxScratch& scratch, const CmuxPlan& pl) {
 }
 
 void Cmux::launch(const TgswSet& set, hipStream_t stream, CmuxRows rows) {
-    launch_rows(set, stream, rows, [](auto ps) { return k_cmux_x1<ps.L, ps.BGBIT>; });
+    launch_rows(set, stream, rows, [](auto ps) {
+        if constexpr (decltype(ps)::L == 0)
+            return k_cmux_rt<>;
+        else
+            return k_cmux_x1<ps.L, ps.BGBIT>;
+    });
 }
 
 int Cmux::launch_tree(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth,
@@ -355,7 +555,12 @@ int Cmux::launch_tree(const TgswSet& set, CmuxScratch& scratch, hipStream_t stre
 }
 
 void Cmux::launch_demux(const TgswSet& set, hipStream_t stream, DemuxRows rows) {
-    launch_rows(set, stream, rows, [](auto ps) { return k_demux_x1<ps.L, ps.BGBIT>; });
+    launch_rows(set, stream, rows, [](auto ps) {
+        if constexpr (decltype(ps)::L == 0)
+            return k_demux_rt<>;
+        else
+            return k_demux_x1<ps.L, ps.BGBIT>;
+    });
 }
 
 int Cmux::launch_scatter(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth,
@@ -385,6 +590,40 @@ int Cmux::launch_scatter(const TgswSet& set, CmuxScratch& scratch, hipStream_t s
         src = R.dst;
     }
     return depth;
+}
+
+int Cmux::launch_write(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, const int32_t* sel_of,
+                       const int32_t* fresh, const int32_t* mem, int32_t* out) {
+    check_owner(set);
+    if (items <= 0) return 0;
+    if (depth < 0 || depth > kCmuxMaxDepth) throw std::invalid_argument("lut_write: depth out of range");
+    if (scratch.rows.items() < (size_t)items * 2 * kN) throw std::invalid_argument("lut_write: piece larger than the reserved scratch");
+    int32_t* delta = scratch.rows;
+    // old: item i looks up its own memory -- tables [items][2^depth] with table_of[i] = i, which is the tree's level 0 unshared
+    int launches;
+    if (depth == 0) {
+        HIP_CHECK(hipMemcpyAsync(delta, mem, (size_t)items * 2 * kN * 4, hipMemcpyDeviceToDevice, stream));
+        launches = 1;
+    } else {
+        check_scratch(scratch, items, depth, "lut_write: piece larger than the reserved scratch");
+        const int32_t* src = mem;
+        for (int32_t k = 0; k < depth; k++) {
+            CmuxRows R;
+            R.depth = depth;
+            R.level = k;
+            R.width = 1 << (depth - 1 - k);
+            R.rows = items * R.width;
+            R.item0 = item0;
+            R.sel_of = sel_of;
+            R.src = src;
+            R.dst = k == depth - 1 ? delta : scratch_rows(scratch, k);
+            launch(set, stream, R);
+            src = R.dst;
+        }
+        launches = depth;
+    }
+    hipLaunchKernelGGL(k_write_delta, dim3((unsigned)items), dim3(256), 0, stream, fresh, delta);
+    return launches + 1 + launch_scatter(set, scratch, stream, item0, items, depth, sel_of, delta, mem, out);
 }
 
 void Cmux::launch_extract(hipStream_t stream, int64_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u, int32_t stride) {

@@ -62,17 +62,39 @@ __device__ __forceinline__ uint32_t row_word(__amdgpu_buffer_rsrc_t rsrc, int la
 }  // namespace
 }  // namespace w64
 
+// ---- which build of a one-wave kernel serves a set's gadget ----
+// libtfhe's two gadgets keep the builds they had (w64::ParamSet, as the blind rotation's with_param_set names them; that
+// dispatch is keyed by l alone and is not touched); every other gadget, and the two as well under the debug option
+// "cmux_gadget_runtime", takes the build whose (l, Bgbit) are launch arguments.
+struct RuntimeGadget {
+    static constexpr int L = 0, BGBIT = 0, index = 2;
+};
+template <class F>
+void with_gadget(int32_t l, int32_t Bgbit, bool runtime, F&& f) {
+    if (!runtime && l == 3 && Bgbit == 7)
+        f(w64::ParamSet<3, 7>{});
+    else if (!runtime && l == 2 && Bgbit == 10)
+        f(w64::ParamSet<2, 10>{});
+    else
+        f(RuntimeGadget{});
+}
+
 // ---- the launcher cmux.h declares ----
 template <class Rows, class KernelOf>
-void Cmux::launch_rows(const TgswSet& set, hipStream_t stream, Rows rows, KernelOf kernel_of, size_t lds, dev::LdsGrant* grant, const char* name) {
+void Cmux::launch_rows(const TgswSet& set, hipStream_t stream, Rows rows, KernelOf kernel_of, size_t lds, dev::LdsGrant* grant, const char* name,
+                       const char* name_rt) {
     check_owner(set);
     if (rows.rows <= 0) return;
     rows.n_set = (int32_t)set.n;
     const unsigned grid = (unsigned)((rows.rows + kCmuxWaveRows - 1) / kCmuxWaveRows);
-    w64::with_param_set(p_.l, [&](auto ps) {
+    with_gadget(set.l, set.Bgbit, runtime_always_ && *runtime_always_ != 0, [&](auto ps) {
         auto kernel = kernel_of(ps);
-        if (grant) dev::allow_dynamic_lds_once(grant[ps.index], (const void*)kernel, lds, name);
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * kCmuxWaveRows), lds, stream, rows, (const double2*)set.spectrum, (const double2*)tw_);
+        if (grant) dev::allow_dynamic_lds_once(grant[ps.index], (const void*)kernel, lds, decltype(ps)::L == 0 ? name_rt : name);
+        if constexpr (decltype(ps)::L == 0)
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * kCmuxWaveRows), lds, stream, rows, (const double2*)set.spectrum, (const double2*)tw_,
+                               (int)set.l, (int)set.Bgbit);
+        else
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * kCmuxWaveRows), lds, stream, rows, (const double2*)set.spectrum, (const double2*)tw_);
     });
 }
 

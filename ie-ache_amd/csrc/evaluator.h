@@ -160,6 +160,9 @@ public:
     // tlwe_extract_device: coefficient coef_of[i] (null: 0) of d_tlwe [count][2][N] -> d_u [count][extract_stride()], N + 1
     // words written: what keyswitch_device takes.  Any supported parameter set.
     TgswSet* tgsw_prepare_device(const Torus32* d_samples, size_t n);
+    // ... with a gadget of the set's own (include/ieache.h section 3i): d_samples [n][2l][2][N] with that l; any context with
+    // N = 1024 and k = 1, whatever the key's gadget.  std::invalid_argument naming the rule that failed (gadget_refusal, cmux.h).
+    TgswSet* tgsw_prepare_device(const Torus32* d_samples, size_t n, int32_t l, int32_t Bgbit);
     uint64_t cmux_id() const;  // what TgswSet::owner holds for this evaluator's sets
     void cmux_device(const TgswSet& set, size_t count, const int32_t* d_sel_of, const Torus32* d_d1, const Torus32* d_d0, Torus32* d_out,
                      EvalStats* stats);
@@ -185,6 +188,11 @@ public:
     // key switch's scratch are reserved before the first piece.  stats: levels = depth + steps, chunks = pieces, a key-switch
     // launch per run of at most `chunk` rows.
     static constexpr int32_t kLutReadNoKeyswitch = 1;
+    // lut_write_device (section 3i), the replace write mem[addr] := new: per item old = the tree over its own memory rows,
+    // delta = new - old mod 2^32 on the device, the scatter of delta onto the memory.  d_new [count][2][N], d_mem and d_out
+    // [count][2^depth][2][N]; d_out == d_mem writes in place, no other overlap.  Pieces, scratch and stream as the tree's.
+    void lut_write_device(const TgswSet& set, size_t count, int32_t depth, const int32_t* d_sel_of, const Torus32* d_new, const Torus32* d_mem,
+                          Torus32* d_out, EvalStats* stats = nullptr);
     void tlwe_rotate_device(const TgswSet& set, size_t count, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of, const Torus32* d_in,
                             Torus32* d_out, EvalStats* stats);
     void lut_read_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of,

@@ -234,7 +234,7 @@ void Evaluator::init() {
     d_->ks.init(p, K);
     d_->mv.init(p);
     d_->pack.init(p);
-    d_->cmux.init(p, device_);
+    d_->cmux.init(p, device_, &d_->opt.cmux_gadget_runtime);
 }
 
 Evaluator::~Evaluator() { destroy(); }
@@ -960,6 +960,11 @@ TgswSet* Evaluator::tgsw_prepare_device(const Torus32* d_samples, size_t n) {
     return d_->cmux.prepare(d_samples, n, stream_);
 }
 
+TgswSet* Evaluator::tgsw_prepare_device(const Torus32* d_samples, size_t n, int32_t l, int32_t Bgbit) {
+    HIP_CHECK(hipSetDevice(device_));
+    return d_->cmux.prepare(d_samples, n, l, Bgbit, stream_);
+}
+
 uint64_t Evaluator::cmux_id() const { return d_->cmux.id(); }
 
 void Evaluator::cmux_plan_figures(size_t count, int32_t depth, int64_t out[4]) const {
@@ -1071,6 +1076,28 @@ void Evaluator::lut_scatter_device(const TgswSet& set, size_t count, int32_t dep
     run_cmux_pieces(pl, count, depth, stats, [&](int64_t i0, int64_t cnt) {
         return d_->cmux.launch_scatter(set, ln.cmux, stream_, i0, cnt, depth, d_sel_of, d_values + (size_t)i0 * row,
                                        d_mem ? d_mem + (size_t)i0 * leaves * row : nullptr, d_out + (size_t)i0 * leaves * row);
+    });
+}
+
+// The replace write mem[addr] := new: the tree's pieces; per piece the tree over the items' own memories, the subtraction and the
+// scatter (Cmux::launch_write).  A piece touches its own items' rows only, so the pieces are independent and d_out == d_mem is sound.
+void Evaluator::lut_write_device(const TgswSet& set, size_t count, int32_t depth, const int32_t* d_sel_of, const Torus32* d_new, const Torus32* d_mem,
+                                 Torus32* d_out, EvalStats* stats) {
+    d_->cmux.check_owner(set);
+    if (depth < 0 || depth > kCmuxMaxDepth) throw std::invalid_argument("lut_write: depth must lie in 0 .. 12");
+    const size_t row = (size_t)2 * (size_t)p_.N, leaves = (size_t)1 << depth;
+    if (overlaps(d_out, count * leaves * row, {{d_new, count * row}, {d_sel_of, count * (size_t)depth}}) ||
+        (d_mem != d_out && overlaps(d_out, count * leaves * row, {{d_mem, count * leaves * row}})))
+        throw std::invalid_argument("lut_write: the output overlaps an input (only d_out == d_mem, the write in place, is accepted)");
+    begin_call();
+    if (count == 0) return;
+    if (!d_new || !d_mem || !d_out) throw std::invalid_argument("lut_write: null rows");
+    Lane& ln = d_->lane[0];
+    const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
+    d_->cmux.reserve_read(ln.cmux, pl, depth);
+    run_cmux_pieces(pl, count, 2 * depth, stats, [&](int64_t i0, int64_t cnt) {
+        return d_->cmux.launch_write(set, ln.cmux, stream_, i0, cnt, depth, d_sel_of, d_new + (size_t)i0 * row, d_mem + (size_t)i0 * leaves * row,
+                                     d_out + (size_t)i0 * leaves * row);
     });
 }
 

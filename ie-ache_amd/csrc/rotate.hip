@@ -4,7 +4,8 @@
 // is the last stage of vertical packing: after a CMux tree has chosen one of 2^d samples, this brings one of its N coefficients
 // to a public position.  k_rotate_x1 is k_blind_rotate_x1 (blind_rotate_w64.hip) with the key block chosen per row and step;
 // built from the pieces of br_step.h and fft512.h, and of cmux_step.h, which it shares with the kernels of cmux.hip.
-// N = 1024, k = 1 and libtfhe's two (l, Bgbit), as br_supported() says.
+// N = 1024, k = 1; libtfhe's two (l, Bgbit) as template arguments (k_rotate_x1), every other admissible gadget of a set as launch
+// arguments (k_rotate_rt: include/ieache.h section 3i).
 #include "cmux.h"
 
 #include <stdexcept>
@@ -133,6 +134,92 @@ __global__ __launch_bounds__(64 * G, 2) void k_rotate_x1(RotateRows A, const dou
     }
 }
 
+// ---- the same kernel with the set's gadget (l, bgbit) as launch arguments ----
+// k_rotate_x1's body line for line -- what it says about the packed step word, the resource per step and the rotation in place
+// holds here -- with the wave-uniform differences of k_cmux_rt (cmux.hip): decomposition_offset_rt, digit_row_two_limb_rt,
+// the bytes of a sample 2 l kRowBytes, the row loops to l and 2 l.  A copy because k_rotate_x1 must keep its code.
+template <int G = kCmuxWaveRows>
+__global__ __launch_bounds__(64 * G, 2) void k_rotate_rt(RotateRows A, const double2* __restrict__ bkf, const double2* __restrict__ gtw, int l, int bgbit) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    int32_t* acc_all = reinterpret_cast<int32_t*>(smem);
+    double2* sT_all = reinterpret_cast<double2*>(smem + (size_t)G * 2 * kN * 4);
+    double2* sTw = sT_all + G * kTile;
+    const WaveRow W = wave_prologue<G>(sT_all, sTw, gtw);
+    const int lane = W.lane, wave = W.wave;
+    double2* sT = W.sT;
+    int32_t* acc = acc_all + wave * 2 * kN;
+    const int64_t r = W.r;
+    if (r >= A.rows) return;
+    const LaneRoots R = make_roots(sTw, lane);
+    {
+        const int4* src = reinterpret_cast<const int4*>(A.src + (size_t)r * 2 * kN);
+        int4* dst = reinterpret_cast<int4*>(acc);
+#pragma unroll
+        for (int q = 0; q < 8; q++) dst[64 * q + lane] = src[64 * q + lane];
+    }
+    wave_sync();
+
+    int32_t my_step = 0;
+    if (lane < A.steps) {
+        const int64_t sel = selector_at(A.sel_of, (A.item0 + r) * A.sel_stride + lane, A.n_set);
+        const int32_t a = A.amount_of ? A.amount_of[lane] : (lane < 11 ? 2 * kN - (1 << lane) : 0);
+        my_step = ((int32_t)sel << 11) | (a & (2 * kN - 1));
+    }
+
+    const uint32_t dec_offset = decomposition_offset_rt(l, bgbit);
+    constexpr int kBlockBytes = kM * (int)sizeof(double2), kRowBytes = 4 * kBlockBytes;
+    const int rows2l = 2 * l, step_bytes = rows2l * kRowBytes;
+    const int lane16 = bk_lane_offset(lane);
+    const unsigned char* accb = reinterpret_cast<const unsigned char*>(acc_all);
+    const uint32_t pb0 = (uint32_t)wave * (2 * kN * 4);
+
+#pragma unroll 1
+    for (int32_t t = 0; t < A.steps; t++) {
+        const int32_t both = __builtin_amdgcn_readlane(my_step, t);
+        const int32_t a = both & (2 * kN - 1);
+        if (a == 0) continue;
+        const __amdgpu_buffer_rsrc_t bk_rsrc = bk_resource(bkf + (size_t)(both >> 11) * ((size_t)step_bytes / sizeof(double2)), 1, step_bytes);
+        double2 s[4][8];
+        uint32_t v0[8], v1[8];
+        const uint32_t jb4 = ((uint32_t)(lane - a) & (2 * kN - 1)) << 2;
+        auto decompose = [&](const uint32_t pb, const uint32_t jb) {
+            const int32_t* accp = reinterpret_cast<const int32_t*>(accb + pb);
+            decompose_rotated(v0, v1, accb, accp, pb, jb, lane, dec_offset);
+        };
+        decompose(pb0, jb4);
+        digit_row_two_limb_rt<true>(s, v0, v1, 32 - bgbit, bgbit, bk_rsrc, lane16, 0, sT, lane, R);
+#pragma unroll 1
+        for (int row = 1; row < l; row++) digit_row_two_limb_rt<false>(s, v0, v1, 32 - (row + 1) * bgbit, bgbit, bk_rsrc, lane16, row * kRowBytes, sT, lane, R);
+        uint32_t jb4b = jb4;
+        asm volatile("" : "+v"(jb4b));
+        decompose(pb0 + 4096u, jb4b);
+#pragma unroll 1
+        for (int row = l; row < rows2l; row++)
+            digit_row_two_limb_rt<false>(s, v0, v1, 32 - (row - l + 1) * bgbit, bgbit, bk_rsrc, lane16, row * kRowBytes, sT, lane, R);
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            fft512_inverse_pair<true>(s[2 * c], s[2 * c + 1], sT, lane, R);
+            uint32_t* accc = reinterpret_cast<uint32_t*>(acc) + c * kN;
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                const uint32_t d0 = join_limbs(s[2 * c][q].x, s[2 * c + 1][q].x, q), d1 = join_limbs(s[2 * c][q].y, s[2 * c + 1][q].y, q);
+                const int32_t j = 64 * q + lane;
+                __hip_atomic_fetch_add(&accc[j], d0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                __hip_atomic_fetch_add(&accc[j + kM], d1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            }
+        }
+        wave_sync();
+    }
+    int elane = lane;
+    asm volatile("" : "+v"(elane));
+    {
+        const int4* src = reinterpret_cast<const int4*>(acc);
+        int4* dst = reinterpret_cast<int4*>(A.dst + (size_t)r * 2 * kN);
+#pragma unroll
+        for (int q = 0; q < 8; q++) dst[64 * q + elane] = src[64 * q + elane];
+    }
+}
+
 // ---- what a lookup's tree and extraction read: selectors steps .. steps + depth - 1 of each item as a [items][depth] array of
 // explicit indices (an implied one taken mod n_set, an explicit one clamped: the rule of the call, applied once), and the
 // public coefficient once per item ----
@@ -146,7 +233,7 @@ __global__ __launch_bounds__(256) void k_read_indices(const int32_t* __restrict_
 }
 
 constexpr size_t kRotateLds = (size_t)kCmuxWaveRows * 2 * kN * 4 + ((size_t)kCmuxWaveRows * kTile + kTwElems) * sizeof(double2);
-LdsGrant g_rotate_grant[2];
+LdsGrant g_rotate_grant[3];  // one per build: cmux_step.h's with_gadget
 
 }  // namespace
 
@@ -154,7 +241,15 @@ void Cmux::launch_rotate(const TgswSet& set, hipStream_t stream, RotateRows rows
     check_owner(set);  // ahead of the steps, as the shared launcher's own check would not be
     if (rows.rows > 0 && (rows.steps < 0 || rows.steps > kRotateMaxSteps || rows.sel_stride < rows.steps))
         throw std::invalid_argument("tlwe_rotate: steps out of range");
-    launch_rows(set, stream, rows, [](auto ps) { return k_rotate_x1<ps.L, ps.BGBIT>; }, kRotateLds, g_rotate_grant, "k_rotate_x1");
+    launch_rows(
+        set, stream, rows,
+        [](auto ps) {
+            if constexpr (decltype(ps)::L == 0)
+                return k_rotate_rt<>;
+            else
+                return k_rotate_x1<ps.L, ps.BGBIT>;
+        },
+        kRotateLds, g_rotate_grant, "k_rotate_x1", "k_rotate_rt");
 }
 
 void Cmux::reserve_read(CmuxScratch& scratch, const CmuxPlan& pl, int32_t depth) {

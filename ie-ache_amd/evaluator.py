@@ -188,6 +188,13 @@ def lib():
     L.ieache_tgsw_prepare.argtypes = [vp, i32p, C.c_size_t]
     L.ieache_tgsw_prepare_device.restype = vp
     L.ieache_tgsw_prepare_device.argtypes = [vp, vp, C.c_size_t]
+    L.ieache_tgsw_prepare_gadget.restype = vp
+    L.ieache_tgsw_prepare_gadget.argtypes = [vp, i32p, C.c_size_t, C.c_int32, C.c_int32]
+    L.ieache_tgsw_prepare_gadget_device.restype = vp
+    L.ieache_tgsw_prepare_gadget_device.argtypes = [vp, vp, C.c_size_t, C.c_int32, C.c_int32]
+    L.ieache_tgsw_gadget.argtypes = [vp, i32p, i32p]
+    L.ieache_lut_write.argtypes = [vp, vp, C.c_size_t, C.c_int32, i32p, i32p, i32p, i32p, sp]
+    L.ieache_lut_write_device.argtypes = [vp, vp, C.c_size_t, C.c_int32, vp, vp, vp, vp, sp]
     L.ieache_tgsw_free.restype = None
     L.ieache_tgsw_free.argtypes = [vp]
     L.ieache_cmux.argtypes = [vp, vp, C.c_size_t, i32p, i32p, i32p, i32p, sp]
@@ -489,12 +496,16 @@ class CompiledNetlist:
 
 class TgswSet:
     """ieache_tgsw: a prepared set of n TGSW samples (Context.tgsw_prepare).  It owns its device memory: close() may come
-    before or after the close of the context that prepared it, and only that context accepts it."""
+    before or after the close of the context that prepared it, and only that context accepts it.  l, Bgbit: the set's gadget --
+    the context's, or the one given to Context.tgsw_prepare."""
 
     def __init__(self, handle, n):
         if not handle:
             raise IeacheError(-22, lib().ieache_last_error().decode())
         self.h, self.n = handle, n
+        l, Bgbit = C.c_int32(), C.c_int32()
+        check(lib().ieache_tgsw_gadget(self.h, C.byref(l), C.byref(Bgbit)))
+        self.l, self.Bgbit = l.value, Bgbit.value
 
     def close(self):
         if getattr(self, "h", None):
@@ -747,16 +758,33 @@ class Context:
         """Device pointers (ints): d_u rows of extract_stride, d_out rows of lwe_stride."""
         check(lib().ieache_keyswitch_device(self.h, count, C.c_void_p(d_u), C.c_void_p(d_out), _stats_ref(stats)))
 
-    def tgsw_prepare(self, samples):
-        """A prepared set of TGSW samples [n][2l][2][N] (or one [2l][2][N]; tools.tgsw_encrypt, or rows bk[i] of a key) for
-        cmux() and lut_tree(): a TgswSet, to be closed (or used as a context manager) before or after this context."""
-        kpl = (self.params.k + 1) * self.params.l
-        samples = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, kpl, 2, self.params.N)
-        return TgswSet(lib().ieache_tgsw_prepare(self.h, _i32(samples), samples.shape[0]), samples.shape[0])
+    def _gadget(self, l, Bgbit):
+        if (l is None) != (Bgbit is None):
+            raise ValueError("tgsw_prepare: give both l and Bgbit, or neither")
+        return None if l is None else (int(l), int(Bgbit))
 
-    def tgsw_prepare_device(self, d_samples, n):
-        """Device pointer (int): samples [n][2l][2][N] packed."""
-        return TgswSet(lib().ieache_tgsw_prepare_device(self.h, C.c_void_p(d_samples), int(n)), int(n))
+    def tgsw_prepare(self, samples, l=None, Bgbit=None):
+        """A prepared set of TGSW samples [n][2l][2][N] (or one [2l][2][N]; tools.tgsw_encrypt, or rows bk[i] of a key) for
+        cmux() and lut_tree(): a TgswSet, to be closed (or used as a context manager) before or after this context.
+        l, Bgbit: the gadget the samples were made with (tools.tgsw_encrypt on tools.with_gadget(params, l, Bgbit)), any
+        admissible one whatever the key's (include/ieache.h section 3i); None: the context's."""
+        gadget = self._gadget(l, Bgbit)
+        samples = np.ascontiguousarray(samples, dtype=np.int32)
+        per = (self.params.k + 1) * (self.params.l if gadget is None else max(gadget[0], 0)) * 2 * self.params.N
+        if per and samples.size % per:
+            raise ValueError("tgsw_prepare: %d words are no whole number of samples [2l][2][N] with 2l = %d rows" % (samples.size, per // (2 * self.params.N)))
+        if gadget is None:
+            samples = samples.reshape(-1, per // (2 * self.params.N), 2, self.params.N)
+            return TgswSet(lib().ieache_tgsw_prepare(self.h, _i32(samples), samples.shape[0]), samples.shape[0])
+        n = samples.size // per if per else 0
+        return TgswSet(lib().ieache_tgsw_prepare_gadget(self.h, _i32(samples), n, gadget[0], gadget[1]), n)
+
+    def tgsw_prepare_device(self, d_samples, n, l=None, Bgbit=None):
+        """Device pointer (int): samples [n][2l][2][N] packed; l, Bgbit as for tgsw_prepare."""
+        gadget = self._gadget(l, Bgbit)
+        if gadget is None:
+            return TgswSet(lib().ieache_tgsw_prepare_device(self.h, C.c_void_p(d_samples), int(n)), int(n))
+        return TgswSet(lib().ieache_tgsw_prepare_gadget_device(self.h, C.c_void_p(d_samples), int(n), gadget[0], gadget[1]), int(n))
 
     def cmux(self, tgsw, d1, d0=None, sel_of=None, stats=None):
         """CMux on host rows: out[i] = d0[i] + C [.] (d1[i] - d0[i]) with C = sample sel_of[i] of the set (None: i mod n), rows
@@ -834,6 +862,13 @@ class Context:
         old = self.lut_tree(tgsw, mem, depth, sel_of=sel_of, table_of=np.arange(count, dtype=np.int32), count=count)
         delta = ((new.astype(np.int64) - old.astype(np.int64)) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
         return self.lut_scatter(tgsw, delta, depth, sel_of=sel_of, mem=mem, count=count)
+
+    def lut_write_device(self, tgsw, count, depth, d_sel_of, d_new, d_mem, d_out, stats=None):
+        """The replace write on the device (include/ieache.h section 3i), word for word lut_write's composition with no host round
+        trip.  Device pointers (ints; d_sel_of may be None / 0): new [count][2][N], mem and out [count][2^depth][2][N] packed;
+        d_out == d_mem writes in place."""
+        check(lib().ieache_lut_write_device(self.h, tgsw.h, count, int(depth), C.c_void_p(d_sel_of or None), C.c_void_p(d_new), C.c_void_p(d_mem),
+                                            C.c_void_p(d_out), _stats_ref(stats)))
 
     def tlwe_rotate(self, tgsw, rows, steps, sel_of=None, amounts=None, stats=None):
         """Rotation by an encrypted amount on host rows (include/ieache.h section 3h): row i ([count][2][N], or one row) goes

@@ -201,6 +201,25 @@ def lut_scatter_reference(params, samples, values, depth, sel_of=None, mem=None,
     return out
 
 
+def lut_write_reference(params, samples, mem, depth, new, sel_of=None):
+    """CPU reference of Context.lut_write / lut_write_device on raw arrays: the composition of the two C references -- the tree
+    over each item's own memory, the wrapping subtraction, the scatter of the difference.  Arguments as Context.lut_write."""
+    depth = int(depth)
+    mem = np.ascontiguousarray(mem, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, params.N)
+    new = np.ascontiguousarray(new, dtype=np.int32).reshape(-1, 2, params.N)
+    count = mem.shape[0]
+    assert new.shape[0] == count
+    old = lut_tree_reference(params, samples, mem, depth, sel_of=sel_of, table_of=np.arange(count, dtype=np.int32), count=count)
+    delta = ((new.astype(np.int64) - old.astype(np.int64)) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+    return lut_scatter_reference(params, samples, delta, depth, sel_of=sel_of, mem=mem, count=count)
+
+
+def with_gadget(params, l, Bgbit):
+    """A copy of `params` with the gadget (l, Bgbit): what tgsw_encrypt and every *_reference here take for a TGSW set with a
+    gadget of its own (Context.tgsw_prepare(samples, l, Bgbit)).  `params` itself is left alone."""
+    return params.copy(l=int(l), Bgbit=int(Bgbit))
+
+
 def rotate_amounts(steps, unit=1, toward_zero=True, N=1024):
     """The public amounts of Context.tlwe_rotate / lut_read for address bits of weight unit 2^t, t = 0 .. steps-1, mod 2N:
     2N - unit 2^t (toward_zero: coefficient unit sum b_t 2^t comes to position 0 -- the read; unit = 1 is the calls' default) or

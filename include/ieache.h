@@ -866,6 +866,39 @@ int ieache_lut_read_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count
                            const int32_t* d_amount_of, const int32_t* d_tables, int32_t n_tables, const int32_t* d_table_of, int32_t coef, int flags,
                            int32_t* d_out, ieache_stats* stats);
 
+/* 3i. TGSW sets with a gadget of their own, and the replace write.
+ * A set prepared by ieache_tgsw_prepare uses the context's (l, Bgbit), the bootstrapping key's gadget.  Nothing ties a
+ * caller's selector samples to the key's decomposition: ieache_tgsw_prepare_gadget takes samples [n][2l][2][N] made with ANY
+ * admissible gadget (tools: ieache_tgsw_encrypt with l and Bgbit of the ieache_params changed), on any context with N = 1024
+ * and k = 1 whatever the key's own gadget -- a (2, 10) key may use (6, 5) selectors.  A finer gadget trades digit rows (the
+ * work of a product grows with 2l) for noise: the truncation ramp of a product falls with 2^-(l Bgbit), its key-noise term
+ * with 2^Bgbit.  Admissible: l >= 1, 1 <= Bgbit < 32, l Bgbit <= 32, 2 l N 2^Bgbit <= 2^32 (the bound
+ * under which the two-limb product is exact for any words); anything else is NULL with IEACHE_EINVAL and a message naming
+ * the rule that failed.  ieache_tgsw_gadget reads a set's gadget back.  Every call of sections 3f to 3h accepts such a set
+ * unchanged: rows stay [2][N], pieces and scratch do not depend on the gadget, the host forms validate as before.  Sets at
+ * (3, 7) and (2, 10) run on the kernels they always had; every other gadget on one further build of each kernel that takes
+ * (l, Bgbit) as launch arguments.  ieache_tgsw_prepare and ieache_tgsw_prepare_device are unchanged.
+ *
+ * ieache_lut_write is the replace write mem[i][addr_i] := new[i], addr_i the index item i's `depth` selectors encrypt
+ * (sel_of as for ieache_lut_tree and ieache_lut_scatter: [count][depth], bit k of the index first; NULL: i depth + k mod n):
+ *   old_i = ieache_lut_tree over item i's own memory (table_of[i] = i),  delta_i = new[i] - old_i mod 2^32,
+ *   out[i] = ieache_lut_scatter of delta_i onto mem[i],
+ * word for word what the three calls composed give, on the context's stream with no host round trip; the subtraction is a
+ * small pass of its own over the piece's [items][2][N] words.  It is cut into the tree's pieces for (count, depth); a piece
+ * reads and writes only its own items' memories, so the device form accepts d_out == d_mem EXACTLY (the write in place);
+ * any other overlap is refused.  depth 0 .. IEACHE_LUT_TREE_MAX_DEPTH.  Refusals as for ieache_lut_scatter (host form: every
+ * index checked; device form: clamped / mod n), a set prepared on another context, a host pointer to a device form.
+ * stats: levels = 2 depth, chunks = pieces, the launches in blind_rotate_launches.  A warm call allocates nothing. */
+ieache_tgsw* ieache_tgsw_prepare_gadget(ieache_ctx* ctx, const int32_t* samples /*host [n][2l][2][N], l the set's*/, size_t n, int32_t l,
+                                        int32_t Bgbit);
+ieache_tgsw* ieache_tgsw_prepare_gadget_device(ieache_ctx* ctx, const int32_t* d_samples /*[n][2l][2][N]*/, size_t n, int32_t l, int32_t Bgbit);
+int ieache_tgsw_gadget(const ieache_tgsw* set, int32_t* l, int32_t* Bgbit);
+int ieache_lut_write(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* sel_of /*[count][depth] or NULL*/,
+                     const int32_t* fresh /*new: [count][2][N]*/, const int32_t* mem /*[count][2^depth][2][N]*/,
+                     int32_t* out /*[count][2^depth][2][N]*/, ieache_stats* stats);
+int ieache_lut_write_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* d_sel_of, const int32_t* d_new,
+                            const int32_t* d_mem, int32_t* d_out /* == d_mem: in place */, ieache_stats* stats);
+
 /* ------------------------------------------------------------------ *
  * 4. CPU tools around the path (no GPU): what Keygen/keygen.c:22-51,  *
  *    Client1/alice.c:116-191 and Output/verif.c:41-76 get from        *
