@@ -80,6 +80,14 @@ struct BlindRotate {
     void guard_rearm();   // the two counts only; the maximum stays
     bool guard_inject();  // test hook: the next read finds a launch over the limit
 
+    // What a launch reads of the key, for the transform probe's read-back (Evaluator::debug_spectrum, debug_twiddles): null
+    // where load_key has not made it.  generic: [n 2l 2][2 limbs][M] in the radix-2 transform's bit-reversed order;
+    // w64: [n 2l 2][2 limbs][8][64]; w64_1: [n 2l 2][8][64]; twiddles: w64::twiddle_table_elems() entries.
+    struct KeyForms {
+        const double2 *generic, *w64, *w64_1, *twiddles;
+    };
+    KeyForms key_forms() const { return KeyForms{bkf_, bkf_w64_, bkf1_w64_, tw_w64_}; }
+
 private:
     Params p_;
     dev::DevKeys K_{};

@@ -1341,6 +1341,31 @@ int ieache_debug_keyswitch(ieache_ctx* ctx, size_t count, const int32_t* u, int3
     });
 }
 
+// the transform probe: the evaluator checks every argument before it writes (its refusals: std::invalid_argument -> EINVAL)
+int ieache_debug_twiddles(ieache_ctx* ctx, int which, double* out) {
+    return guarded([&] {
+        if (!ctx || !out) return fail(IEACHE_EINVAL, "null argument");
+        ctx->eval->debug_twiddles(which, out);
+        return 0;
+    });
+}
+
+int ieache_debug_fft512(ieache_ctx* ctx, int form, size_t count, const double* in, double* out) {
+    return guarded([&] {
+        if (!ctx || !in || !out) return fail(IEACHE_EINVAL, "null argument");
+        ctx->eval->debug_fft512(form, count, in, out);
+        return 0;
+    });
+}
+
+int ieache_debug_spectrum(ieache_ctx* ctx, int which, size_t first, size_t count, double* out) {
+    return guarded([&] {
+        if (!ctx || !out) return fail(IEACHE_EINVAL, "null argument");
+        ctx->eval->debug_spectrum(which, first, count, out);
+        return 0;
+    });
+}
+
 // ---- 2b. device group: one key on several GPUs, one call ----
 struct ieache_group {
     std::unique_ptr<DeviceGroup> g;

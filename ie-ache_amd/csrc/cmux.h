@@ -155,6 +155,9 @@ struct Cmux {
     // coefficient coef_of[i] (null: 0; clamped into [0, N)) of tlwe [count][2][N] -> u [count][stride], N + 1 words written.
     // Any supported parameter set.
     void launch_extract(hipStream_t stream, int64_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u, int32_t stride);
+    // The family's twiddle table, built on `stream` if no set has been prepared yet -- the one step of prepare() that makes it.
+    // For the transform probe's read-back (Evaluator::debug_twiddles).
+    const double2* twiddles(hipStream_t stream);
 
 private:
     // The one launcher of the one-wave kernels (k_cmux_x1, k_demux_x1, k_rotate_x1), defined in cmux_step.h: the owner check,

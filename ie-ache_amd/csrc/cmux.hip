@@ -480,15 +480,20 @@ TgswSet* Cmux::prepare(const int32_t* d_samples, size_t n, hipStream_t stream) {
     return prepare(d_samples, n, p_.l, p_.Bgbit, stream);
 }
 
-TgswSet* Cmux::prepare(const int32_t* d_samples, size_t n, int32_t l, int32_t Bgbit, hipStream_t stream) {
-    if (const char* why = gadget_refusal(p_, l, Bgbit)) throw std::invalid_argument(why);
-    if (!d_samples || n < 1) throw std::invalid_argument("tgsw_prepare: no samples");
-    if (n > ((size_t)1 << 20)) throw std::invalid_argument("tgsw_prepare: more than 2^20 samples");
+const double2* Cmux::twiddles(hipStream_t stream) {
     if (!tw_) {
         tw_.allocate(twiddle_table_elems());
         build_twiddle_table(tw_, stream);
         HIP_CHECK(hipGetLastError());
     }
+    return tw_;
+}
+
+TgswSet* Cmux::prepare(const int32_t* d_samples, size_t n, int32_t l, int32_t Bgbit, hipStream_t stream) {
+    if (const char* why = gadget_refusal(p_, l, Bgbit)) throw std::invalid_argument(why);
+    if (!d_samples || n < 1) throw std::invalid_argument("tgsw_prepare: no samples");
+    if (n > ((size_t)1 << 20)) throw std::invalid_argument("tgsw_prepare: more than 2^20 samples");
+    twiddles(stream);
     std::unique_ptr<TgswSet> set(new TgswSet);
     Params as_key = p_;
     as_key.n = (int32_t)n;  // the spectrum kernel sees n samples where the bootstrapping key has n blocks BK_i

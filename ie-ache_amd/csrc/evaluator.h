@@ -236,6 +236,15 @@ public:
     void debug_blind_rotate(size_t count, const Torus32* d_x, Torus32* d_acc, int32_t steps);
     // u [count][N+1] -> out [count][lwe_stride]
     void debug_keyswitch(size_t count, const Torus32* d_u, Torus32* d_out);
+    // The transform probe (fft_probe.h; include/ieache.h states the shapes), on HOST arrays: the twiddle table of the blind
+    // rotation (which = 0), of the CMux family (1, built now if no set has been) or as a 64-thread kernel builds it (2); `count`
+    // transforms in one of the probe's forms; `count` polynomials of a prepared key form from polynomial `first` on (which =
+    // 0: two-limb w64, 1: one-limb w64, 2: the any-parameter kernel's).  std::invalid_argument, with nothing written, for a
+    // null array, a ring other than N = 1024 / k = 1 (all but the any-parameter form), an unknown `which` or form, an odd
+    // count on a paired form, polynomials outside the key.
+    void debug_twiddles(int which, double* out);
+    void debug_fft512(int form, size_t count, const double* in, double* out);
+    void debug_spectrum(int which, size_t first, size_t count, double* out);
 
     // Force the generic (any-parameter) kernels even where a specialised one exists.
     void set_force_generic(bool v);

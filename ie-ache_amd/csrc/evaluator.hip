@@ -25,6 +25,7 @@
 #include "device_common.h"
 #include "evaluator_options.h"
 #include "cmux.h"
+#include "fft_probe.h"
 #include "joint_plan.h"
 #include "keyswitch.h"
 #include "multi_extract.h"
@@ -1593,6 +1594,63 @@ void Evaluator::debug_keyswitch(size_t count, const Torus32* d_u, Torus32* d_out
     hipError_t e = hipGetLastError();
     (void)hipStreamSynchronize(stream_);  // before tmp goes
     HIP_CHECK(e);
+}
+
+// ---- the transform probe (fft_probe.h): every refusal is thrown before anything is written to the caller's array ----
+static const char* const kProbeRing = "the transform probe covers the 512-point transform of N = 1024, k = 1 contexts only";
+static const char* const kProbeNoKey = "this context holds no key form of the 64-lane kernels (br_supported(), br_plan.h)";
+
+void Evaluator::debug_twiddles(int which, double* out) {
+    if (!out) throw std::invalid_argument("null argument");
+    if (p_.N != 1024 || p_.k != 1) throw std::invalid_argument(kProbeRing);
+    if (which < 0 || which > 2) throw std::invalid_argument("debug_twiddles: which must be 0 (blind rotation), 1 (CMux family) or 2 (built in a wave)");
+    begin_call();
+    const size_t bytes = probe::kTwiddleElems * sizeof(double2);
+    DeviceBuffer<double2> built;
+    const double2* src = nullptr;
+    if (which == 0) {
+        src = d_->br.key_forms().twiddles;
+        if (!src) throw std::invalid_argument(kProbeNoKey);
+    } else if (which == 1) {
+        src = d_->cmux.twiddles(stream_);
+    } else {
+        built.allocate(probe::kTwiddleElems);
+        probe::build_twiddles_in_wave(built, stream_);
+        src = built;
+    }
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    HIP_CHECK(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+}
+
+void Evaluator::debug_fft512(int form, size_t count, const double* in, double* out) {
+    if (!in || !out) throw std::invalid_argument("null argument");
+    if (p_.N != 1024 || p_.k != 1) throw std::invalid_argument(kProbeRing);
+    if (const char* why = probe::form_refusal(form, count)) throw std::invalid_argument(why);
+    begin_call();
+    const double2* tw = d_->br.key_forms().twiddles;
+    if (!tw) throw std::invalid_argument(kProbeNoKey);
+    const size_t elems = count * probe::kTransformElems;
+    DeviceBuffer<double2> d_in, d_out;
+    d_in.allocate(elems);
+    d_out.allocate(elems);
+    HIP_CHECK(hipMemcpy(d_in, in, elems * sizeof(double2), hipMemcpyHostToDevice));
+    probe::run_fft512(form, count, d_in, d_out, tw, stream_);  // synchronises the stream
+    HIP_CHECK(hipMemcpy(out, d_out, elems * sizeof(double2), hipMemcpyDeviceToHost));
+}
+
+void Evaluator::debug_spectrum(int which, size_t first, size_t count, double* out) {
+    if (!out) throw std::invalid_argument("null argument");
+    if (which < 0 || which > 2) throw std::invalid_argument("debug_spectrum: which must be 0 (two-limb w64), 1 (one-limb w64) or 2 (generic two-limb)");
+    if (which != 2 && (p_.N != 1024 || p_.k != 1)) throw std::invalid_argument(kProbeRing);
+    const size_t npoly = (size_t)p_.n * p_.kpl() * 2;
+    if (count < 1 || first >= npoly || count > npoly - first) throw std::invalid_argument("debug_spectrum: polynomials outside the key's n x 2l x 2");
+    begin_call();
+    const BlindRotate::KeyForms f = d_->br.key_forms();
+    const double2* src = which == 0 ? f.w64 : which == 1 ? f.w64_1 : f.generic;
+    if (!src) throw std::invalid_argument(kProbeNoKey);
+    const size_t per_poly = which == 1 ? (size_t)512 : which == 0 ? (size_t)1024 : (size_t)p_.N;  // double2: one limb, or two
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    HIP_CHECK(hipMemcpy(out, src + first * per_poly, count * per_poly * sizeof(double2), hipMemcpyDeviceToHost));
 }
 
 }  // namespace ieache

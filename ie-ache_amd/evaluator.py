@@ -267,6 +267,10 @@ def lib():
     L.ieache_group_pbs_multi.argtypes = [vp, C.c_size_t, i32p, i32p, C.c_int32, i32p, i32p, C.c_int32, i32p, i32p, C.c_int, sp]
     L.ieache_debug_blind_rotate.argtypes = [vp, C.c_size_t, i32p, i32p, C.c_int32]
     L.ieache_debug_keyswitch.argtypes = [vp, C.c_size_t, i32p, i32p]
+    f64p = C.POINTER(C.c_double)
+    L.ieache_debug_twiddles.argtypes = [vp, C.c_int, f64p]
+    L.ieache_debug_fft512.argtypes = [vp, C.c_int, C.c_size_t, f64p, f64p]
+    L.ieache_debug_spectrum.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, f64p]
     L.ieache_keygen_raw.argtypes = [pp, u32p, C.c_int, i32p, i32p, i32p, i32p]
     L.ieache_keygen_files.argtypes = [C.c_char_p, pp, u32p, C.c_int, u32p, C.c_int]
     L.ieache_encrypt_bits.argtypes = [pp, i32p, u8p, C.c_size_t, C.c_uint64, i32p]
@@ -302,6 +306,16 @@ def check(rc):
 def _i32(a):
     assert a.dtype == np.int32 and a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _f64(a):
+    assert a.dtype == np.float64 and a.flags["C_CONTIGUOUS"]
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+# the transform probe's forms (csrc/fft_probe.h): forward 0 .. 4, inverse 5, paired inverses 6 and 7
+FFT_FORWARD_FORMS, FFT_INVERSE_FORMS, FFT_PAIRED_FORMS = (0, 1, 2, 3, 4), (5, 6, 7), (6, 7)
+TWIDDLE_ENTRIES = 576
 
 
 def _pbs_flags(keyswitch=True, tlwe=False, accumulator=False):
@@ -1027,6 +1041,30 @@ class Context:
         u = np.ascontiguousarray(u, dtype=np.int32).reshape(-1, self.params.N + 1)
         out = np.zeros((u.shape[0], self.params.n + 1), dtype=np.int32)
         check(lib().ieache_debug_keyswitch(self.h, u.shape[0], _i32(u), _i32(out)))
+        return out
+
+    # ---- the transform probe (csrc/fft_probe.h; include/ieache.h states the shapes) ----
+    def debug_twiddles(self, which):
+        """The 576-entry twiddle table as complex128: of the blind rotation (0), of the CMux family (1), as a 64-thread kernel
+        builds it (2)."""
+        out = np.zeros((TWIDDLE_ENTRIES, 2), dtype=np.float64)
+        check(lib().ieache_debug_twiddles(self.h, which, _f64(out)))
+        return out.view(np.complex128)[:, 0]
+
+    def debug_fft512(self, form, x):
+        """x [count][512] complex (forward forms: natural order; inverse forms: [count][8][64] flattened) -> complex128
+        [count][8][64], raw in (register, lane) order."""
+        x = np.ascontiguousarray(x, dtype=np.complex128).reshape(-1, 512)
+        out = np.zeros((x.shape[0], 8, 64), dtype=np.complex128)
+        check(lib().ieache_debug_fft512(self.h, form, x.shape[0], _f64(x.view(np.float64)), _f64(out.view(np.float64))))
+        return out
+
+    def debug_spectrum(self, which, first, count):
+        """`count` prepared key polynomials from polynomial `first` on, complex128: [count][2][8][64] (which = 0, two-limb),
+        [count][8][64] (1, one-limb) or [count][2][N/2] (2, the any-parameter kernel's bit-reversed order)."""
+        shape = {0: (count, 2, 8, 64), 1: (count, 8, 64)}.get(which, (count, 2, self.params.N // 2))
+        out = np.zeros(shape, dtype=np.complex128)
+        check(lib().ieache_debug_spectrum(self.h, which, first, count, _f64(out.view(np.float64))))
         return out
 
 

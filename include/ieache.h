@@ -657,6 +657,36 @@ int ieache_circuit_simulate_ex(int kind, int bits, int fold_constants, const uin
  * key switch u [count][N+1] -> out [count][n+1] */
 int ieache_debug_blind_rotate(ieache_ctx* ctx, size_t count, const int32_t* x, int32_t* acc, int32_t steps);
 int ieache_debug_keyswitch(ieache_ctx* ctx, size_t count, const int32_t* u, int32_t* out);
+/* The transform probe (csrc/fft_probe.h), for tests: the 512-point transform every N = 1024 kernel multiplies polynomials
+ * with, its twiddle table and the prepared key spectra, as doubles before any rounding.  Host arrays in and out; complex values
+ * are (re, im) pairs of doubles.  Each returns IEACHE_EINVAL with the reason in ieache_last_error() -- and has written nothing --
+ * for a null pointer, for a context whose ring is not N = 1024, k = 1 (all but ieache_debug_spectrum's which = 2), for an
+ * unknown `which` or form, an odd count on a paired form, and polynomials outside the key.
+ *
+ * ieache_debug_twiddles: out [576][2], the table of csrc/tw_roots.h -- entry 64 k + lane = exp(i pi lane (1 - 4 k) / 1024),
+ * entry 512 + 8 k + p0 = exp(-2 pi i p0 k / 64).  which = 0: the table the blind-rotation kernels load; 1: the CMux
+ * family's, built now if no TGSW set has been prepared yet, as the first ieache_tgsw_prepare would; 2: a table built
+ * inside a 64-thread kernel, as the key-preparation kernels build theirs.
+ *
+ * ieache_debug_fft512: `count` transforms in form `form`, four per workgroup as the kernels sit.
+ *   form 0 .. 4, forward: in [count][512][2], y_j = p[j] + i p[j + 512] in natural order; out [count][8][64][2] raw,
+ *     out[t][k2][lane] = X[k0 + 8 k1 + 64 k2] with lane = 8 k0 + k1, X_k = sum_j y_j exp(i pi j (1 - 4 k) / 1024).
+ *     0: <true, 0>; 1: <true, 1>; 2: <true, 1, hook, late>; 3: <true, 1, hook, early, resident roots>; 4: <true, 0, hook>.
+ *   form 5 .. 7, inverse: in [count][8][64][2] in that layout; out [count][8][64][2], out[t][r][lane] = y_{64 r + lane}, the
+ *     double a kernel is about to round (normalised: the 1/512 and the untwist applied).  5: fft512_inverse; 6: the paired
+ *     inverse, transforms 2 i and 2 i + 1 through one call (count even); 7: the paired inverse on resident roots.
+ *   csrc/fft_probe.h lists which kernels use which form.
+ *
+ * ieache_debug_spectrum: `count` prepared polynomials of the bootstrapping key from polynomial `first` on, polynomial
+ * (i 2l + row) 2 + c being bk[i][row][c], as a launch reads them.
+ *   which = 0: two-limb, 64-lane order: out [count][2 limbs: low, high][8][64][2], each limb laid out as a forward form's output
+ *   which = 1: one-limb, 64-lane order: out [count][8][64][2], the transform of the 32-bit words themselves
+ *   which = 2: the any-parameter kernel's, any ring: out [count][2 limbs][N/2][2], entry m of a limb = X_{bitrev(m)} (bit reversal
+ *     over log2(N/2) bits), X_k = sum_j y_j exp(i pi j / N) exp(-2 pi i j k / (N/2))
+ * The limbs of a word w: low = (int16_t)w, high = (w - low) >> 16, so that w = low + 2^16 high with high in [-2^15, 2^15]. */
+int ieache_debug_twiddles(ieache_ctx* ctx, int which, double* out);
+int ieache_debug_fft512(ieache_ctx* ctx, int form, size_t count, const double* in, double* out);
+int ieache_debug_spectrum(ieache_ctx* ctx, int which, size_t first, size_t count, double* out);
 /* The plan of a rotation of roles (option "br_mix") for a launch of `gates` gate instances on a device of `cus` compute units,
  * rotations of n steps, one-wave turns of s1 steps, two-wave turns of s1 x ratio_x100 / 100: returns 1 and out = {subsets k,
  * subsets on two waves at a time, s1, s2, whole rounds, shortened round's s1, s2, steps covered by the rounds (< n), gate
