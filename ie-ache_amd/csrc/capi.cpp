@@ -1265,6 +1265,63 @@ int ieache_lut_write(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int3
     });
 }
 
+// ---- many values into shared memories (section 3j) ----
+namespace {
+int check_lut_add(int32_t depth, int32_t steps, int32_t n_mems) {
+    if (depth < 0 || depth > IEACHE_LUT_TREE_MAX_DEPTH) return fail(IEACHE_EINVAL, "lut_add: depth must lie in 0 .. 12");
+    if (const int rc = check_rotate(steps, "lut_add")) return rc;
+    if (n_mems < 1) return fail(IEACHE_EINVAL, "lut_add: n_mems must be at least 1");
+    return 0;
+}
+// the host indices of a call: selectors, amounts, memories
+int check_lut_add_indices(size_t n_set, int64_t N, size_t count, int32_t depth, int32_t steps, const int32_t* sel_of, const int32_t* amount_of,
+                          int32_t n_mems, const int32_t* mem_of) {
+    if (const int rc = check_indices(sel_of, count * (size_t)(depth + steps), (int64_t)n_set, "lut_add: sel_of")) return rc;
+    if (const int rc = check_indices(amount_of, (size_t)steps, 2 * N, "lut_add: amount_of")) return rc;
+    return check_indices(mem_of, count, n_mems, "lut_add: mem_of");
+}
+}  // namespace
+
+int ieache_lut_add_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of,
+                          const int32_t* d_amount_of, const int32_t* d_values, const int32_t* d_mems, int32_t n_mems, const int32_t* d_mem_of,
+                          int32_t* d_out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_tgsw(ctx, set)) return rc;
+        if ((count && !d_values) || !d_out) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_lut_add(depth, steps, n_mems)) return rc;
+        // the memories are touched (copied or zero-filled) by an empty call as well
+        require_device_pointers(1, {{d_mems, "d_mems", true}, {d_out, "d_out"}});
+        require_device_pointers(count, {{d_sel_of, "d_sel_of", true}, {d_amount_of, "d_amount_of", true}, {d_values, "d_values"},
+                                        {d_mem_of, "d_mem_of", true}});
+        return with_stats(stats, [&](EvalStats* st) {
+            ctx->eval->lut_add_device(*set->set, count, depth, steps, d_sel_of, d_amount_of, d_values, d_mems, n_mems, d_mem_of, d_out, st);
+        });
+    });
+}
+
+int ieache_lut_add(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, const int32_t* sel_of,
+                   const int32_t* amount_of, const int32_t* values, const int32_t* mems, int32_t n_mems, const int32_t* mem_of, int32_t* out,
+                   ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_tgsw(ctx, set)) return rc;
+        if ((count && !values) || !out) return fail(IEACHE_EINVAL, "null argument");
+        if (const int rc = check_lut_add(depth, steps, n_mems)) return rc;
+        if (const int rc = check_lut_add_indices(set->set->n, ctx->eval->params().N, count, depth, steps, sel_of, amount_of, n_mems, mem_of)) return rc;
+        HostCall h(ctx, count);
+        const size_t sample = (size_t)2 * (size_t)h.p.N, rows = (size_t)n_mems << depth;
+        StagedRows dv(h.ev, kStageTlweA, count, sample, values, sample), dsel = h.words(kStagePolyOf, sel_of, count * (size_t)(depth + steps));
+        StagedRows dam = h.words(kStageFactors, amount_of, (size_t)steps), dof = h.words(kStageBias, mem_of, count);
+        // the memories go into the result rows and the call runs in place
+        StagedRows dout(h.ev, kStageOut, rows, sample);
+        if (mems) HIP_CHECK(hipMemcpy(dout.p, mems, rows * sample * 4, hipMemcpyHostToDevice));
+        with_stats(stats, [&](EvalStats* st) {
+            h.ev.lut_add_device(*set->set, count, depth, steps, dsel.p, dam.p, dv.p, mems ? dout.p : nullptr, n_mems, dof.p, dout.p, st);
+        });
+        dout.download(out, sample);
+        return 0;
+    });
+}
+
 int ieache_tlwe_extract_device(ieache_ctx* ctx, size_t count, const int32_t* d_tlwe, const int32_t* d_coef_of, int32_t* d_u, ieache_stats* stats) {
     return guarded([&] {
         if (!ctx || !d_tlwe || !d_u) return fail(IEACHE_EINVAL, "null argument");
@@ -1799,6 +1856,20 @@ int ieache_lut_read_reference(const ieache_params* p, const int32_t* set, size_t
         if (const int rc = check_indices(table_of, count, n_tables, "lut_read: table_of")) return rc;
         if (const int rc = check_indices(&coef, 1, pp.N, "lut_read: coef")) return rc;
         lut_read_reference(pp, set, n, woks ? nullptr : ksk, count, depth, steps, sel_of, amount_of, tables, table_of, coef, out);
+        return 0;
+    });
+}
+
+int ieache_lut_add_reference(const ieache_params* p, const int32_t* set, size_t n, size_t count, int32_t depth, int32_t steps, const int32_t* sel_of,
+                             const int32_t* amount_of, const int32_t* values, const int32_t* mems, int32_t n_mems, const int32_t* mem_of, int32_t* out) {
+    return guarded([&] {
+        if (!p || !set || (count && !values) || !out) return fail(IEACHE_EINVAL, "null argument");
+        const Params pp = to_params(*p);
+        if (!pp.supported()) return fail(IEACHE_EINVAL, "lut_add_reference: unsupported TFHE parameter set");
+        if (n < 1) return fail(IEACHE_EINVAL, "lut_add_reference: no samples");
+        if (const int rc = check_lut_add(depth, steps, n_mems)) return rc;
+        if (const int rc = check_lut_add_indices(n, pp.N, count, depth, steps, sel_of, amount_of, n_mems, mem_of)) return rc;
+        lut_add_reference(pp, set, n, count, depth, steps, sel_of, amount_of, values, mems, (size_t)n_mems, mem_of, out);
         return 0;
     });
 }

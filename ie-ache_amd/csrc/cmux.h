@@ -2,7 +2,8 @@
 //   section 3f  the CMux, the CMux-tree lookup built from it, and the extraction of a coefficient of a TLWE sample;
 //   section 3g  the scatter that writes at an encrypted index;
 //   section 3h  the rotation by caller selectors and the coefficient-level lookup;
-//   section 3i  sets with a gadget of their own, and the replace write.
+//   section 3i  sets with a gadget of their own, and the replace write;
+//   section 3j  many values added into shared memories in one call.
 // The kernels, the spectrum form of a prepared set, the twiddle table and the scratch of a tree are behind this object; how
 // a call is cut is cmux_plan.h.  Kernels: cmux.hip (3f, 3g) and rotate.hip (3h); what the two share is cmux_step.h.
 #pragma once
@@ -66,6 +67,24 @@ struct DemuxRows {
     int64_t rows = 0;                   // parents of this launch: items x w
     int64_t item0 = 0;                  // first item of the piece within the call (src, dst and base are already offset)
     int32_t n_set = 1;
+    int32_t depth = 1, step = 0, width = 1;
+};
+
+// Where the rows of one launch of k_demux_acc live: the LAST step of a piece of lut_add (include/ieache.h section 3j), DemuxRows'
+// sibling.  The parents are a piece's as above; the children are not stored per item but ADDED into the memory the item names:
+//   width w = 2^(depth-1):  item = r / w, j = r % w;  parent = src + r;  m = mem_of[item] clamped into [0, n_mems) (null: 0);
+//   child c of the parent is added into out + (m 2^depth + 2 j + c), 2 j + c < 2^depth: a row of memory m whatever mem_of holds;
+//   selector sel_of[item depth + depth - 1 - step] with DemuxRows' rule.
+// sel_of and mem_of are the PIECE's (already offset by its first item): the selectors are the explicit ones k_read_indices
+// wrote, which the earlier steps of the piece read through DemuxRows with item0 = 0.  `out` is the call's, the same for every
+// piece.  Nothing of out is read: any number of rows of any number of pieces may name one memory row.
+struct DemuxAccRows {
+    const int32_t* src = nullptr;
+    int32_t* out = nullptr;
+    const int32_t* sel_of = nullptr;
+    const int32_t* mem_of = nullptr;
+    int64_t rows = 0;                   // parents of this launch: items x w
+    int32_t n_set = 1, n_mems = 1;
     int32_t depth = 1, step = 0, width = 1;
 };
 
@@ -152,6 +171,21 @@ struct Cmux {
     int launch_read(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, int32_t steps,
                     const int32_t* sel_of, const int32_t* amount_of, const int32_t* tables, int32_t n_tables, const int32_t* table_of, int32_t coef,
                     int32_t* u, int32_t stride);
+    // one launch of `rows.rows` accumulating demux steps (k_demux_acc: 2 x rows.rows rows added into rows.out)
+    void launch_demux_acc(const TgswSet& set, hipStream_t stream, DemuxAccRows rows);
+    // the scatter of one piece of lut_add (section 3j): `items` parents src [items][2][N] by the piece's explicit selectors
+    // tree_sel [items][depth]; steps 0 .. depth - 2 are launch_scatter's (k_demux_x1, the same scratch buffers), the last is
+    // k_demux_acc into out [n_mems][2^depth][2][N] by mem_of (the piece's, null: memory 0); depth 0 adds the parents themselves
+    // (k_demux_acc0).  Returns the kernel launches issued (max(depth, 1)).
+    int launch_scatter_acc(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t items, int32_t depth, const int32_t* tree_sel,
+                           const int32_t* src, const int32_t* mem_of, int32_t n_mems, int32_t* out);
+    // one piece of lut_add: the rotation of values [items][2][N] into scratch.rows by selectors 0 .. steps - 1 of each item's
+    // depth + steps (amount_of null: +2^t mod 2N, the amounts that move coefficient 0 to the encrypted position; steps == 0: the
+    // values are the parents), the selectors steps .. steps + depth - 1 made explicit in scratch.idx (k_read_indices; not
+    // counted as a launch), launch_scatter_acc.  `values` is the PIECE's (already offset by item0); sel_of, mem_of and out are
+    // the call's.  scratch as reserve_read's.  Returns (steps > 0) + max(depth, 1).
+    int launch_add(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, int32_t steps,
+                   const int32_t* sel_of, const int32_t* amount_of, const int32_t* values, int32_t n_mems, const int32_t* mem_of, int32_t* out);
     // coefficient coef_of[i] (null: 0; clamped into [0, N)) of tlwe [count][2][N] -> u [count][stride], N + 1 words written.
     // Any supported parameter set.
     void launch_extract(hipStream_t stream, int64_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u, int32_t stride);
@@ -172,6 +206,7 @@ private:
     int device_ = 0;
     uint64_t id_ = 0;
     dev::DeviceBuffer<double2> tw_;  // the 64-lane transforms' twiddle table, built with the first set
+    dev::DeviceBuffer<int32_t> add_amounts_;  // lut_add's default amounts [kRotateMaxSteps]: +2^t mod 2N, made by the first call that needs them
 };
 
 }  // namespace ieache

@@ -4,7 +4,8 @@
 // chosen per row.  Built from the pieces of br_step.h and fft512.h, which that kernel uses too, and of cmux_step.h.
 // N = 1024, k = 1; libtfhe's two (l, Bgbit) as template arguments (k_cmux_x1, k_demux_x1) and every other admissible gadget of a
 // set as launch arguments (k_cmux_rt, k_demux_rt: section 3i); the extraction kernel at the end takes any set.
-// k_demux_x1 is the same product as a demultiplexer: the write at an encrypted index (section 3g).
+// k_demux_x1 is the same product as a demultiplexer: the write at an encrypted index (section 3g); k_demux_acc is its last step
+// with the children added into shared memories by atomic adds: many values into one memory in one call (section 3j).
 #include "cmux.h"
 
 #include <atomic>
@@ -419,6 +420,123 @@ __global__ __launch_bounds__(64 * G, 2) void k_demux_rt(DemuxRows A, const doubl
     }
 }
 
+// ---- the accumulating demux step: the LAST step of a piece of lut_add (include/ieache.h section 3j) ----
+// k_demux_x1's body -- prologue, selector rule, decomposition, digit rows, inverse transforms, the parent read again through an
+// opaque copy -- with a third epilogue: child c of parent r of item i is not stored at 2 r + c of the piece's own rows but
+// ADDED into row 2 j + c of the memory the item names (DemuxAccRows: the rule, no pointer tables, everything wave-uniform), with
+// integer atomic adds that return nothing.
+//   * nothing of `out` is read, so any number of waves of any number of launches may add into one row: the sums are mod 2^32,
+//     which is commutative and associative, so the words are determined whatever the order the adds arrive in (what
+//     k_pack_gemm's K splits rest on) -- no float, no order, no run-to-run difference;
+//   * one atomic instruction of the wave covers words 64 q + lane of a row half: 256 contiguous bytes, the shape the adds run
+//     fastest in; the rows are again 8 KB buffer resources, the memory index clamped, so nothing past a row of `out` can be
+//     touched whatever mem_of holds;
+//   * a new kernel and not a flag of k_demux_x1, which must keep its code (br_step.h's rule).  Being new it states the body
+//     ONCE for the three builds: L > 0 takes the compile-time digit row, L == 0 the run-time one (k_demux_rt's differences).
+// hipcc: the register and LDS figures are in DESIGN.md section 4.11; __launch_bounds__(256, 2) as the family's.
+template <int L, int BGBIT, int G>
+__device__ __forceinline__ void demux_acc_body(const DemuxAccRows& A, const double2* __restrict__ bkf, const double2* __restrict__ gtw, const int l,
+                                               const int bgbit, double2* sT_all, double2* sTw) {
+    const WaveRow W = wave_prologue<G>(sT_all, sTw, gtw);
+    const int lane = W.lane;
+    double2* sT = W.sT;
+    const int64_t r = W.r;
+    if (r >= A.rows) return;
+    const LaneRoots R = make_roots(sTw, lane);
+
+    // row r -> (parent, the two rows of the item's memory, selector): all wave-uniform
+    const int64_t item = r / A.width, j = r - item * A.width;
+    const int64_t sel = selector_at(A.sel_of, item * A.depth + (A.depth - 1 - A.step), A.n_set);
+    const int64_t m0 = A.mem_of ? (int64_t)A.mem_of[item] : 0;
+    const int64_t m = m0 < 0 ? 0 : (m0 >= A.n_mems ? A.n_mems - 1 : m0);
+    const int32_t* pp = A.src + (size_t)r * 2 * kN;
+    int32_t* po = A.out + (((size_t)m << A.depth) + 2 * (size_t)j) * 2 * kN;
+    const __amdgpu_buffer_rsrc_t rp = row_resource(pp);
+    const int lane4 = lane * 4;
+
+    constexpr int kBlockBytes = kM * (int)sizeof(double2), kRowBytes = 4 * kBlockBytes;
+    const int rows2l = L > 0 ? 2 * L : 2 * l, half = L > 0 ? L : l, width = L > 0 ? BGBIT : bgbit, step_bytes = rows2l * kRowBytes;
+    const __amdgpu_buffer_rsrc_t bk_rsrc = bk_resource(bkf + (size_t)sel * ((size_t)step_bytes / sizeof(double2)), 1, step_bytes);
+    const int lane16 = bk_lane_offset(lane);
+    uint32_t dec_offset;
+    if constexpr (L > 0)
+        dec_offset = decomposition_offset<L, BGBIT>();
+    else
+        dec_offset = decomposition_offset_rt(l, bgbit);
+
+    double2 s[4][8];
+    uint32_t v0[8], v1[8];
+    auto decompose = [&](const int c) {
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const int jj = c * kN + 64 * q;
+            v0[q] = (row_word(rp, lane4, jj) + dec_offset) ^ dec_offset;
+            v1[q] = (row_word(rp, lane4, jj + kM) + dec_offset) ^ dec_offset;
+        }
+    };
+    auto digit_row = [&](const int sh, const int brow, auto first) {
+        if constexpr (L > 0)
+            digit_row_two_limb<BGBIT, decltype(first)::value>(s, v0, v1, sh, bk_rsrc, lane16, brow, sT, lane, R);
+        else
+            digit_row_two_limb_rt<decltype(first)::value>(s, v0, v1, sh, bgbit, bk_rsrc, lane16, brow, sT, lane, R);
+    };
+    decompose(0);
+    digit_row(32 - width, 0, std::true_type{});
+    // one loop over the other rows, as in k_cmux_x1 and for its reason
+#pragma unroll 1
+    for (int row = 1; row < rows2l; row++) {
+        const int c = row >= half ? 1 : 0, q = row - c * half;
+        if (q == 0) decompose(1);
+        digit_row(32 - (q + 1) * width, row * kRowBytes, std::false_type{});
+    }
+    // opaque copies: the parent is read AGAIN below, and the memory rows' addresses are formed only now
+    const int32_t* ppe = pp;
+    asm volatile("" : "+s"(ppe));
+    asm volatile("" : "+s"(po));
+    const __amdgpu_buffer_rsrc_t rpe = row_resource(ppe);
+    const __amdgpu_buffer_rsrc_t ro0 = row_resource(po), ro1 = row_resource(po + 2 * kN);
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        fft512_inverse_pair<true>(s[2 * c], s[2 * c + 1], sT, lane, R);
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const uint32_t h0 = join_limbs(s[2 * c][q].x, s[2 * c + 1][q].x, q), h1 = join_limbs(s[2 * c][q].y, s[2 * c + 1][q].y, q);
+            const int jj = c * kN + 64 * q;
+            const uint32_t p0 = row_word(rpe, lane4, jj), p1 = row_word(rpe, lane4, jj + kM);
+            // the results are not used: the adds are issued in the form that returns nothing
+            (void)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32((int)(p0 - h0), ro0, lane4, jj * 4, 0);
+            (void)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32((int)(p1 - h1), ro0, lane4, (jj + kM) * 4, 0);
+            (void)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32((int)h0, ro1, lane4, jj * 4, 0);
+            (void)__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32((int)h1, ro1, lane4, (jj + kM) * 4, 0);
+        }
+    }
+}
+
+template <int L, int BGBIT, int G = kCmuxWaveRows>
+__global__ __launch_bounds__(64 * G, 2) void k_demux_acc(DemuxAccRows A, const double2* __restrict__ bkf, const double2* __restrict__ gtw) {
+    __shared__ __align__(16) double2 sT_all[G * kTile];
+    __shared__ __align__(16) double2 sTw[kTwElems];
+    demux_acc_body<L, BGBIT, G>(A, bkf, gtw, L, BGBIT, sT_all, sTw);
+}
+template <int G = kCmuxWaveRows>
+__global__ __launch_bounds__(64 * G, 2) void k_demux_acc_rt(DemuxAccRows A, const double2* __restrict__ bkf, const double2* __restrict__ gtw, int l,
+                                                            int bgbit) {
+    __shared__ __align__(16) double2 sT_all[G * kTile];
+    __shared__ __align__(16) double2 sTw[kTwElems];
+    demux_acc_body<0, 0, G>(A, bkf, gtw, l, bgbit, sT_all, sTw);
+}
+
+// ---- lut_add at depth 0: out[mem_of[i]][0] += v_i, the same order-free adds; a wave's instruction covers 256 contiguous bytes ----
+__global__ __launch_bounds__(256) void k_demux_acc0(const int32_t* __restrict__ values, const int32_t* __restrict__ mem_of, int32_t n_mems,
+                                                    int32_t* out) {
+    const int64_t i = blockIdx.x;
+    const int64_t m0 = mem_of ? (int64_t)mem_of[i] : 0;
+    const int64_t m = m0 < 0 ? 0 : (m0 >= n_mems ? n_mems - 1 : m0);
+    const uint32_t* v = reinterpret_cast<const uint32_t*>(values) + (size_t)i * 2 * kN;
+    uint32_t* dst = reinterpret_cast<uint32_t*>(out) + (size_t)m * 2 * kN;
+    for (int q = threadIdx.x; q < 2 * kN; q += 256) atomicAdd(dst + q, v[q]);
+}
+
 // ---- the subtraction of a replace write (include/ieache.h section 3i): delta_i = new_i - old_i mod 2^32, in place over old ----
 // A pass of its own over the piece's [items][2][N] words between the tree and the scatter: 16 KB read and 8 KB written per item,
 // against the 2^depth rows of 8 KB the scatter's last step moves.
@@ -594,6 +712,55 @@ int Cmux::launch_scatter(const TgswSet& set, CmuxScratch& scratch, hipStream_t s
         launch_demux(set, stream, R);
         src = R.dst;
     }
+    return depth;
+}
+
+void Cmux::launch_demux_acc(const TgswSet& set, hipStream_t stream, DemuxAccRows rows) {
+    // the rule that keeps 2 j + c inside a memory: only the last step of a scatter accumulates
+    if (rows.rows > 0 && (rows.depth < 1 || rows.depth > kCmuxMaxDepth || rows.step != rows.depth - 1 || rows.width != 1 << (rows.depth - 1) ||
+                          rows.rows % rows.width != 0 || rows.n_mems < 1))
+        throw std::invalid_argument("lut_add: the accumulating step is the last step of a scatter");
+    launch_rows(set, stream, rows, [](auto ps) {
+        if constexpr (decltype(ps)::L == 0)
+            return k_demux_acc_rt<>;
+        else
+            return k_demux_acc<ps.L, ps.BGBIT>;
+    });
+}
+
+int Cmux::launch_scatter_acc(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t items, int32_t depth, const int32_t* tree_sel,
+                             const int32_t* src, const int32_t* mem_of, int32_t n_mems, int32_t* out) {
+    check_owner(set);
+    if (items <= 0) return 0;
+    if (depth < 0 || depth > kCmuxMaxDepth || n_mems < 1) throw std::invalid_argument("lut_add: depth or n_mems out of range");
+    if (depth == 0) {
+        hipLaunchKernelGGL(k_demux_acc0, dim3((unsigned)items), dim3(256), 0, stream, src, mem_of, n_mems, out);
+        return 1;
+    }
+    check_scratch(scratch, items, depth, "lut_add: piece larger than the reserved scratch");
+    for (int32_t t = 0; t < depth - 1; t++) {
+        DemuxRows R;
+        R.depth = depth;
+        R.step = t;
+        R.width = 1 << t;
+        R.rows = items * R.width;
+        R.sel_of = tree_sel;  // the piece's own array: item0 stays 0
+        R.src = src;
+        R.dst = scratch_rows(scratch, depth - 2 - t);  // launch_scatter's buffers: step depth - 2 the widest, in A
+        launch_demux(set, stream, R);
+        src = R.dst;
+    }
+    DemuxAccRows R;
+    R.depth = depth;
+    R.step = depth - 1;
+    R.width = 1 << (depth - 1);
+    R.rows = items * R.width;
+    R.sel_of = tree_sel;
+    R.mem_of = mem_of;
+    R.n_mems = n_mems;
+    R.src = src;
+    R.out = out;
+    launch_demux_acc(set, stream, R);
     return depth;
 }
 

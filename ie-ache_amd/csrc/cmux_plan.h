@@ -7,6 +7,8 @@
 //   k_tlwe_extract   coefficient j of a TLWE sample as an extracted LWE row
 //   k_demux_x1       one demux step per wave (section 3g): parent p -> hi = C_sel [.] p and lo = p - hi, the memory added on the last step
 //   k_demux_add      a scatter of depth 0: out_i = mem_i + v_i
+//   k_demux_acc      (section 3j) the last demux step of a piece of lut_add: the children ADDED into the memory the item names
+//   k_demux_acc0     lut_add at depth 0: out[mem_of[i]][0] += v_i
 //   k_rotate_x1      (rotate.hip, section 3h) one row per wave, every step inside the launch: acc += C_t [.] (X^a_t acc - acc)
 //   k_read_indices   (rotate.hip) a lookup's tree selectors and its public coefficient as the arrays the two kernels above read
 //
@@ -20,6 +22,8 @@
 // step d-3 B, and so on backwards -- the tree's sizes, so cmux_plan(items, d, ...) is its cut unchanged.
 // A rotation (tlwe_rotate) is a flat call: rows = items, one launch per piece whatever the number of steps, no scratch.  A
 // coefficient-level lookup (lut_read) is cut as its tree is, cmux_plan(items, d, ...), and keeps one selected row per item.
+// The shared write (lut_add) is cut as a scatter of its depth is, cmux_plan(items, d, ...), with lut_read's scratch: the
+// rotated row per item; its last step adds into the caller's memories, so which piece an item falls into does not matter.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -193,6 +193,15 @@ public:
     // [count][2^depth][2][N]; d_out == d_mem writes in place, no other overlap.  Pieces, scratch and stream as the tree's.
     void lut_write_device(const TgswSet& set, size_t count, int32_t depth, const int32_t* d_sel_of, const Torus32* d_new, const Torus32* d_mem,
                           Torus32* d_out, EvalStats* stats = nullptr);
+    // lut_add_device (section 3j), the shared write mem[m_i][hi_i].coef[lo_i] += v_i: per item the rotation of d_values[i] by
+    // selectors 0 .. steps-1 of its depth + steps (d_amount_of null: +2^t mod 2N), the scatter by selectors steps ..
+    // steps+depth-1, and the leaves ADDED into memory d_mem_of[i] (clamped into [0, n_mems); null: 0) by the last demux step
+    // itself.  d_mems and d_out [n_mems][2^depth][2][N]; d_out is initialised from d_mems (null: zeros) on the stream unless
+    // d_out == d_mems exactly, the write in place; no other overlap.  The tree's plan for (count, depth), reserve_read's scratch.
+    // stats: levels = depth + steps, chunks = pieces, launches pieces x ((steps > 0) + max(depth, 1)).
+    void lut_add_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of,
+                        const Torus32* d_values, const Torus32* d_mems, int32_t n_mems, const int32_t* d_mem_of, Torus32* d_out,
+                        EvalStats* stats = nullptr);
     void tlwe_rotate_device(const TgswSet& set, size_t count, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of, const Torus32* d_in,
                             Torus32* d_out, EvalStats* stats);
     void lut_read_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of,

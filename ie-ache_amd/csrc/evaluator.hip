@@ -1102,6 +1102,40 @@ void Evaluator::lut_write_device(const TgswSet& set, size_t count, int32_t depth
     });
 }
 
+// The shared write mem[m_i][hi_i].coef[lo_i] += v_i: the tree's pieces for (count, depth); out starts as the memories (or zeros,
+// or is the memories themselves) and every piece ADDS into it (Cmux::launch_add), so which piece an item falls into does not
+// matter: the adds are order-free mod 2^32 and all on one stream behind the initialising copy.
+void Evaluator::lut_add_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of,
+                               const Torus32* d_values, const Torus32* d_mems, int32_t n_mems, const int32_t* d_mem_of, Torus32* d_out, EvalStats* stats) {
+    d_->cmux.check_owner(set);
+    if (depth < 0 || depth > kCmuxMaxDepth) throw std::invalid_argument("lut_add: depth must lie in 0 .. 12");
+    if (steps < 0 || steps > kRotateMaxSteps) throw std::invalid_argument("lut_add: steps must lie in 0 .. 64");
+    if (n_mems < 1) throw std::invalid_argument("lut_add: n_mems must be at least 1");
+    const size_t row = (size_t)2 * (size_t)p_.N, words = ((size_t)n_mems << depth) * row;
+    if (overlaps(d_out, words, {{d_values, count * row}, {d_sel_of, count * (size_t)(depth + steps)}, {d_amount_of, (size_t)steps}, {d_mem_of, count}}) ||
+        (d_mems != d_out && overlaps(d_out, words, {{d_mems, words}})))
+        throw std::invalid_argument("lut_add: the output overlaps an input (only d_out == d_mems, the write in place, is accepted)");
+    begin_call();
+    if (!d_out) throw std::invalid_argument("lut_add: null rows");
+    if (count > 0 && !d_values) throw std::invalid_argument("lut_add: null rows");
+    // not a launch of the call's: the copy or fill the sums start from
+    if (d_mems && d_mems != d_out)
+        HIP_CHECK(hipMemcpyAsync(d_out, d_mems, words * 4, hipMemcpyDeviceToDevice, stream_));
+    else if (!d_mems)
+        HIP_CHECK(hipMemsetAsync(d_out, 0, words * 4, stream_));
+    if (count == 0) {
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        return;
+    }
+    Lane& ln = d_->lane[0];
+    const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
+    d_->cmux.reserve_read(ln.cmux, pl, depth);
+    run_cmux_pieces(pl, count, depth + steps, stats, [&](int64_t i0, int64_t cnt) {
+        return d_->cmux.launch_add(set, ln.cmux, stream_, i0, cnt, depth, steps, d_sel_of, d_amount_of, d_values + (size_t)i0 * row, n_mems, d_mem_of,
+                                   d_out);
+    });
+}
+
 // The rotation by caller selectors: the flat CMux's pieces, one launch each whatever the number of steps; no scratch.
 void Evaluator::tlwe_rotate_device(const TgswSet& set, size_t count, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of,
                                    const Torus32* d_in, Torus32* d_out, EvalStats* stats) {

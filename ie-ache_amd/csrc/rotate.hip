@@ -289,4 +289,48 @@ int Cmux::launch_read(const TgswSet& set, CmuxScratch& scratch, hipStream_t stre
     return launches + 1;
 }
 
+int Cmux::launch_add(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, int32_t steps,
+                     const int32_t* sel_of, const int32_t* amount_of, const int32_t* values, int32_t n_mems, const int32_t* mem_of, int32_t* out) {
+    check_owner(set);
+    if (items <= 0) return 0;
+    if (steps < 0 || steps > kRotateMaxSteps) throw std::invalid_argument("lut_add: steps out of range");
+    if (scratch.rows.items() < (size_t)items * 2 * kN || scratch.idx.items() < (size_t)items * (size_t)(depth + 1))
+        throw std::invalid_argument("lut_add: piece larger than the reserved scratch");
+    int launches = 0;
+    const int32_t* parents = values;
+    if (steps > 0) {
+        if (!amount_of) {
+            // the write's direction, +2^t mod 2N (0 from t = 11 on): k_rotate_x1's own default is the read's
+            if (!add_amounts_) {
+                int32_t host[kRotateMaxSteps];
+                for (int32_t t = 0; t < kRotateMaxSteps; t++) host[t] = t < 11 ? 1 << t : 0;
+                add_amounts_.allocate(kRotateMaxSteps);
+                HIP_CHECK(hipMemcpy(add_amounts_, host, sizeof host, hipMemcpyHostToDevice));
+            }
+            amount_of = add_amounts_;
+        }
+        RotateRows R;
+        R.src = values;
+        R.dst = scratch.rows;
+        R.rows = items;
+        R.item0 = item0;
+        R.sel_of = sel_of;
+        R.amount_of = amount_of;
+        R.steps = steps;
+        R.sel_stride = depth + steps;
+        launch_rotate(set, stream, R);
+        launches++;
+        parents = scratch.rows;
+    }
+    int32_t* tree_sel = scratch.idx;
+    if (depth > 0) {
+        // selectors steps .. steps + depth - 1 of each item, explicit, for the piece alone; the coefficient array it also writes
+        // (items words after them) is not read
+        const int64_t words = items * depth;
+        hipLaunchKernelGGL(k_read_indices, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, sel_of, item0, items, depth, steps, (int32_t)set.n, 0,
+                           tree_sel, tree_sel + (size_t)items * depth);
+    }
+    return launches + launch_scatter_acc(set, scratch, stream, items, depth, tree_sel, parents, mem_of ? mem_of + item0 : nullptr, n_mems, out);
+}
+
 }  // namespace ieache

@@ -442,6 +442,31 @@ void lut_read_reference(const Params& p, const Torus32* set, size_t n_set, const
     if (ksk) keyswitch_reference(p, ksk, count, u.data(), out);
 }
 
+void lut_add_reference(const Params& p, const Torus32* set, size_t n_set, size_t count, int32_t depth, int32_t steps, const int32_t* sel_of,
+                       const int32_t* amount_of, const Torus32* values, const Torus32* mems, size_t n_mems, const int32_t* mem_of, Torus32* out) {
+    const size_t W = (size_t)2 * p.N, T = (size_t)1 << depth, stride = (size_t)depth + (size_t)steps;
+    // the write's default amounts, +2^t mod 2N; the scatter's selectors are indices steps .. steps + depth - 1 of each item
+    std::vector<int32_t> plus(steps);
+    for (int32_t t = 0; t < steps; t++) plus[t] = t < 31 ? (int32_t)(((size_t)1 << t) & (W - 1)) : 0;
+    std::vector<int32_t> tree_sel(count * (size_t)depth);
+    for (size_t i = 0; i < count; i++)
+        for (size_t k = 0; k < (size_t)depth; k++) {
+            const size_t at = i * stride + (size_t)steps + k;
+            tree_sel[i * (size_t)depth + k] = sel_of ? sel_of[at] : (int32_t)(at % n_set);
+        }
+    std::vector<Torus32> rows(count * W), leaves(count * T * W);
+    rotate_rows(p, set, n_set, count, steps, stride, sel_of, amount_of ? amount_of : plus.data(), values, rows.data());
+    lut_scatter_reference(p, set, n_set, count, depth, tree_sel.data(), rows.data(), nullptr, leaves.data());
+    // out may be mems itself
+    if (out != mems)
+        for (size_t c = 0; c < n_mems * T * W; c++) out[c] = mems ? mems[c] : 0;
+    for (size_t i = 0; i < count; i++) {
+        Torus32* dst = out + (mem_of ? (size_t)mem_of[i] : 0) * T * W;
+        const Torus32* leaf = leaves.data() + i * T * W;
+        for (size_t c = 0; c < T * W; c++) dst[c] = (Torus32)((uint32_t)dst[c] + (uint32_t)leaf[c]);
+    }
+}
+
 void tlwe_extract_reference(const Params& p, size_t count, const Torus32* tlwe, const int32_t* coef_of, Torus32* u) {
     const int32_t N = p.N;
     for (size_t r = 0; r < count; r++) {

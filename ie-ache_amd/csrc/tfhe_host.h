@@ -96,6 +96,14 @@ void lut_read_reference(const Params& p, const Torus32* set, size_t n_set, const
                         const int32_t* sel_of, const int32_t* amount_of, const Torus32* tables, const int32_t* table_of, int32_t coef,
                         Torus32* out);
 
+// lut_add_reference (section 3j), the three references above composed and summed: w_i = the rotation of values[i] by selectors
+// 0 .. steps-1 of item i's depth + steps with amounts a_t (null: +2^t mod 2N, the write's direction), leaves_i = the scatter of
+// w_i by selectors steps .. steps+depth-1 with no memory, out[m][j] = mems[m][j] + the sum of leaves_i[j] over the items with
+// mem_of[i] = m (mems null: zeros; mem_of null: memory 0).  mems and out [n_mems][2^depth][2][N]; out may be mems itself.
+// Indices and amounts already checked by the caller.
+void lut_add_reference(const Params& p, const Torus32* set, size_t n_set, size_t count, int32_t depth, int32_t steps, const int32_t* sel_of,
+                       const int32_t* amount_of, const Torus32* values, const Torus32* mems, size_t n_mems, const int32_t* mem_of, Torus32* out);
+
 // coefficient coef_of[r] (null: 0; checked by the caller) of tlwe [count][2][N] as extracted rows u [count][N+1]
 void tlwe_extract_reference(const Params& p, size_t count, const Torus32* tlwe, const int32_t* coef_of, Torus32* u);
 

@@ -211,6 +211,9 @@ def lib():
     L.ieache_lut_read_device.argtypes = [vp, vp, C.c_size_t, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int, vp, sp]
     L.ieache_lut_read_reference.argtypes = [pp, i32p, C.c_size_t, i32p, C.c_size_t, C.c_int32, C.c_int32, i32p, i32p, i32p, C.c_int32, i32p,
                                             C.c_int32, C.c_int, i32p]
+    L.ieache_lut_add.argtypes = [vp, vp, C.c_size_t, C.c_int32, C.c_int32, i32p, i32p, i32p, i32p, C.c_int32, i32p, i32p, sp]
+    L.ieache_lut_add_device.argtypes = [vp, vp, C.c_size_t, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, vp, sp]
+    L.ieache_lut_add_reference.argtypes = [pp, i32p, C.c_size_t, C.c_size_t, C.c_int32, C.c_int32, i32p, i32p, i32p, i32p, C.c_int32, i32p, i32p]
     L.ieache_tlwe_extract.argtypes = [vp, C.c_size_t, i32p, i32p, i32p, sp]
     L.ieache_tlwe_extract_device.argtypes = [vp, C.c_size_t, vp, vp, vp, sp]
     L.ieache_debug_cmux_plan.argtypes = [vp, C.c_size_t, C.c_int32, C.POINTER(C.c_int64)]
@@ -933,6 +936,38 @@ class Context:
         check(lib().ieache_lut_read_device(self.h, tgsw.h, count, int(depth), int(steps), C.c_void_p(d_sel_of or None), C.c_void_p(d_amounts or None),
                                            C.c_void_p(d_tables), int(n_tables), C.c_void_p(d_table_of or None), int(coef),
                                            0 if keyswitch else LUT_READ_NO_KEYSWITCH, C.c_void_p(d_out), _stats_ref(stats)))
+
+    def lut_add(self, tgsw, values, depth, steps=0, sel_of=None, amounts=None, mems=None, n_mems=1, mem_of=None, stats=None):
+        """Many values into shared memories in one call (include/ieache.h section 3j): mem[m_i][hi_i].coef[lo_i] += values[i].
+        values [count][2][N] (or one row); sel_of [count][steps + depth], the `steps` LOW address bits first, then the `depth` HIGH
+        ones (None: samples i (steps + depth) + t mod n); amounts [steps] (None: +2^t mod 2N, which moves coefficient 0 to the
+        encrypted position); mems [n_mems][2^depth][2][N] (None: zeros; given, it fixes n_mems); mem_of [count] (None: memory 0)
+        -> the new memories [n_mems][2^depth][2][N].  Word for word tlwe_rotate, lut_scatter(mem=None) and the sum of the leaves
+        per memory, which the last demux step forms on the device."""
+        depth, steps = int(depth), int(steps)
+        values = np.ascontiguousarray(values, dtype=np.int32).reshape(-1, 2, self.params.N)
+        count = values.shape[0]
+        of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(depth + steps, 1))
+        am = None if amounts is None else np.ascontiguousarray(amounts, dtype=np.int32).reshape(-1)
+        mof = None if mem_of is None else np.ascontiguousarray(mem_of, dtype=np.int32).reshape(-1)
+        if mems is not None:
+            mems = np.ascontiguousarray(mems, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, self.params.N)
+            n_mems = mems.shape[0]
+        n_mems = int(n_mems)
+        assert (of is None or depth + steps < 1 or of.shape[0] == count) and (am is None or am.shape[0] == max(steps, 0))
+        assert mof is None or mof.shape[0] == count
+        out = np.zeros((max(n_mems, 0), 1 << max(depth, 0), 2, self.params.N), dtype=np.int32)
+        check(lib().ieache_lut_add(self.h, tgsw.h, count, depth, steps, None if of is None else _i32(of), None if am is None else _i32(am),
+                                   _i32(values), None if mems is None else _i32(mems), n_mems, None if mof is None else _i32(mof), _i32(out),
+                                   _stats_ref(stats)))
+        return out
+
+    def lut_add_device(self, tgsw, count, depth, steps, d_sel_of, d_amounts, d_values, d_mems, n_mems, d_mem_of, d_out, stats=None):
+        """Device pointers (ints; the index arrays, d_amounts and d_mems may be None / 0): values [count][2][N], mems and out
+        [n_mems][2^depth][2][N] packed; d_out == d_mems adds in place."""
+        check(lib().ieache_lut_add_device(self.h, tgsw.h, count, int(depth), int(steps), C.c_void_p(d_sel_of or None), C.c_void_p(d_amounts or None),
+                                          C.c_void_p(d_values), C.c_void_p(d_mems or None), int(n_mems), C.c_void_p(d_mem_of or None),
+                                          C.c_void_p(d_out), _stats_ref(stats)))
 
     def cmux_plan(self, count, depth=-1):
         """How cmux() (depth < 0) or lut_tree() / lut_scatter() would cut such a call under the options as they are (csrc/cmux_plan.h):

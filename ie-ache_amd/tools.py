@@ -266,6 +266,30 @@ def lut_read_reference(params, samples, tables, depth, steps, sel_of=None, amoun
     return out
 
 
+def lut_add_reference(params, samples, values, depth, steps=0, sel_of=None, amounts=None, mems=None, n_mems=1, mem_of=None):
+    """CPU reference of Context.lut_add on raw arrays (ieache_lut_add_reference: the references of tlwe_rotate and lut_scatter
+    composed and the leaves summed per memory; no GPU, any supported set), arguments as there -> [n_mems][2^depth][2][N]."""
+    depth, steps = int(depth), int(steps)
+    kpl = (params.k + 1) * params.l
+    samples = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, kpl, 2, params.N)
+    values = np.ascontiguousarray(values, dtype=np.int32).reshape(-1, 2, params.N)
+    count = values.shape[0]
+    of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(depth + steps, 1))
+    am = None if amounts is None else np.ascontiguousarray(amounts, dtype=np.int32).reshape(-1)
+    mof = None if mem_of is None else np.ascontiguousarray(mem_of, dtype=np.int32).reshape(-1)
+    if mems is not None:
+        mems = np.ascontiguousarray(mems, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, params.N)
+        n_mems = mems.shape[0]
+    n_mems = int(n_mems)
+    assert (of is None or depth + steps < 1 or of.shape[0] == count) and (am is None or am.shape[0] == max(steps, 0))
+    assert mof is None or mof.shape[0] == count
+    out = np.zeros((max(n_mems, 0), 1 << max(depth, 0), 2, params.N), dtype=np.int32)
+    check(lib().ieache_lut_add_reference(C.byref(params), _i32(samples), samples.shape[0], count, depth, steps, None if of is None else _i32(of),
+                                         None if am is None else _i32(am), _i32(values), None if mems is None else _i32(mems), n_mems,
+                                         None if mof is None else _i32(mof), _i32(out)))
+    return out
+
+
 def tlwe_extract_reference(params, tlwe, coef_of=None):
     """CPU reference of Context.tlwe_extract (ieache_tlwe_extract_reference): tlwe [count][2][N] -> [count][N+1]."""
     tlwe = np.ascontiguousarray(tlwe, dtype=np.int32).reshape(-1, 2, params.N)

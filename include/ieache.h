@@ -838,8 +838,8 @@ int ieache_debug_cmux_plan(const ieache_ctx* ctx, size_t count, int32_t depth, i
  * first bad one and stage through rows the context keeps; device forms clamp.  IEACHE_EINVAL: depth outside
  * 0 .. IEACHE_LUT_TREE_MAX_DEPTH, overlap, a set prepared on another context.  count == 0 is a no-op.  stats: bootstraps == 0,
  * keyswitch_launches == 0, levels = depth, chunks = pieces, the kernel launches (pieces x max(depth, 1)) and their time in
- * blind_rotate_launches and blind_rotate_ms.  Several items writing into ONE memory in a single call are not offered (take the
- * leaves with mem == NULL and add them); there is no group form and no cloudd verb. */
+ * blind_rotate_launches and blind_rotate_ms.  Several items writing into ONE memory in a single call are ieache_lut_add
+ * (section 3j), which sums the leaves on the device; there is no group form and no cloudd verb. */
 int ieache_lut_scatter(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* sel_of /*[count][depth] or NULL*/,
                        const int32_t* values /*[count][2][N]*/, const int32_t* mem /*[count][2^depth][2][N] or NULL*/,
                        int32_t* out /*[count][2^depth][2][N]*/, ieache_stats* stats);
@@ -929,6 +929,44 @@ int ieache_lut_write(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int3
 int ieache_lut_write_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* d_sel_of, const int32_t* d_new,
                             const int32_t* d_mem, int32_t* d_out /* == d_mem: in place */, ieache_stats* stats);
 
+/* 3j. Many values into shared memories in one call: mem[m_i][hi_i].coef[lo_i] += v_i.  Conventions, sets, gadgets and
+ * exactness are those of 3f to 3i (integers mod 2^32; any set section 3i admits).
+ *
+ * The call has n_mems memories mems [n_mems][2^depth][2][N]; item i has a value values[i] [2][N], a memory mem_of[i] in
+ * [0, n_mems) (mem_of == NULL: every item writes memory 0) and depth + steps selectors sel_of[i (steps + depth) + t] (NULL:
+ * that index mod n), laid out as for ieache_lut_read: t = 0 .. steps-1 are the LOW address bits, least significant first,
+ * t = steps .. steps+depth-1 the HIGH ones.  Three steps, each an existing definition:
+ *   (1) w_i = ieache_tlwe_rotate of values[i] by selectors 0 .. steps-1 with the public amounts a_t; amount_of == NULL stands
+ *       for a_t = +2^t mod 2N -- the OPPOSITE of ieache_lut_read's default: it moves coefficient 0 to the encrypted position;
+ *       steps == 0 gives w_i = values[i];
+ *   (2) leaves_i = ieache_lut_scatter of w_i by selectors steps .. steps+depth-1 with mem == NULL: [2^depth][2][N];
+ *   (3) out[m][j] = mems[m][j] + the sum of leaves_i[j] over the items with mem_of[i] = m;  mems == NULL stands for zeros.
+ * Word for word the three references composed and summed: depth == 0, steps == 0 is out[m][0] = mems[m][0] + sum v_i, and one
+ * item with n_mems = 1 and steps = 0 is ieache_lut_scatter bit for bit.  The sum is formed on the device by the last demux
+ * step of each piece itself, with integer atomic adds: they are order-free mod 2^32, so the words do not depend on the order
+ * the adds arrive in, and a call repeated gives identical words.  Nothing of the size of the leaves (count x 2^depth rows) is
+ * ever stored.  Each addition brings a scatter's noise (and a rotation's) to EVERY slot of its memory: DESIGN.md section 7
+ * gives the number of additions a memory takes.
+ *
+ * The device form accepts d_out == d_mems EXACTLY: the write in place -- nothing of the memory is read, it is only added to.
+ * Any other overlap of d_out with an input is refused; with distinct buffers d_out is initialised from d_mems (NULL: zero-filled)
+ * on the context's stream before the first piece.  The cut is the tree's plan for (count, depth), ieache_debug_cmux_plan; the
+ * items of one memory may fall into different pieces, which changes nothing.  Scratch is ieache_lut_read's; a warm call
+ * allocates nothing.  depth 0 .. IEACHE_LUT_TREE_MAX_DEPTH, steps 0 .. IEACHE_ROTATE_MAX_STEPS, n_mems >= 1.  Host forms check
+ * every index and amount and name the first bad one; device forms clamp an explicit selector (an implied one is taken mod n),
+ * clamp mem_of into [0, n_mems) and mask amounts to 2N - 1.  count == 0 returns mems unchanged (zeros for NULL).
+ * IEACHE_EINVAL: depth, steps or n_mems out of range, overlap, a set prepared on another context, a host pointer to a device
+ * form.  stats: bootstraps == 0, keyswitch_launches == 0, levels = depth + steps, chunks = pieces, blind_rotate_launches =
+ * pieces x ((steps > 0 ? 1 : 0) + max(depth, 1)); the initialising copy or fill and the small index pass are not counted.
+ * No group form, no cloudd verb, no replace-write of a single coefficient, no other rings, no one-limb form. */
+int ieache_lut_add(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps,
+                   const int32_t* sel_of /*[count][steps+depth] or NULL*/, const int32_t* amount_of /*[steps] or NULL*/,
+                   const int32_t* values /*[count][2][N]*/, const int32_t* mems /*[n_mems][2^depth][2][N] or NULL*/, int32_t n_mems,
+                   const int32_t* mem_of /*[count] or NULL*/, int32_t* out /*[n_mems][2^depth][2][N]*/, ieache_stats* stats);
+int ieache_lut_add_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of,
+                          const int32_t* d_amount_of, const int32_t* d_values, const int32_t* d_mems, int32_t n_mems, const int32_t* d_mem_of,
+                          int32_t* d_out /* == d_mems: in place */, ieache_stats* stats);
+
 /* ------------------------------------------------------------------ *
  * 4. CPU tools around the path (no GPU): what Keygen/keygen.c:22-51,  *
  *    Client1/alice.c:116-191 and Output/verif.c:41-76 get from        *
@@ -996,6 +1034,11 @@ int ieache_tlwe_rotate_reference(const ieache_params* p, const int32_t* set, siz
 int ieache_lut_read_reference(const ieache_params* p, const int32_t* set, size_t n, const int32_t* ksk, size_t count, int32_t depth, int32_t steps,
                               const int32_t* sel_of, const int32_t* amount_of, const int32_t* tables, int32_t n_tables, const int32_t* table_of,
                               int32_t coef, int flags, int32_t* out);
+/* ... of ieache_lut_add (section 3j): the references of ieache_tlwe_rotate and ieache_lut_scatter composed and the leaves summed
+ * per memory; arguments, defaults and refusals as for its host form; out may be mems itself ... */
+int ieache_lut_add_reference(const ieache_params* p, const int32_t* set, size_t n, size_t count, int32_t depth, int32_t steps,
+                             const int32_t* sel_of, const int32_t* amount_of, const int32_t* values, const int32_t* mems, int32_t n_mems,
+                             const int32_t* mem_of, int32_t* out);
 /* ... and of ieache_tlwe_extract: tlwe [count][2][N] -> u [count][N+1]. */
 int ieache_tlwe_extract_reference(const ieache_params* p, size_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u);
 /* key files -> raw arrays (sizes from ieache_params; pass NULL to query params only) */
