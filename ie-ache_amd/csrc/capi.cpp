@@ -25,6 +25,7 @@
 #include "mix_plan.h"
 #include "pack_plan.h"
 #include "program.h"
+#include "set_calls.h"
 #include "tfhe_host.h"
 
 using namespace ieache;
@@ -942,56 +943,136 @@ int check_tgsw(const ieache_ctx* ctx, const ieache_tgsw* set) {
     if (set->set->owner != ctx->eval->cmux_id()) return fail(IEACHE_EINVAL, "the TGSW set was prepared on another context");
     return 0;
 }
-int check_tree(int32_t depth, int32_t n_tables) {
-    if (depth < 0 || depth > IEACHE_LUT_TREE_MAX_DEPTH) return fail(IEACHE_EINVAL, "lut_tree: depth must lie in 0 .. 12");
-    if (n_tables < 1) return fail(IEACHE_EINVAL, "lut_tree: n_tables must be at least 1");
-    return 0;
-}
-int check_scatter(int32_t depth) {
-    if (depth < 0 || depth > IEACHE_LUT_TREE_MAX_DEPTH) return fail(IEACHE_EINVAL, "lut_scatter: depth must lie in 0 .. 12");
-    return 0;
-}
-// host indices: every one of idx[0 .. count) inside [0, bound), or the code after fail()
-int check_indices(const int32_t* idx, size_t count, int64_t bound, const char* what) {
+// host indices: every one of idx[0 .. count) inside [0, bound), or the code after fail(); the message names "<call>: <name>"
+int check_indices(const int32_t* idx, size_t count, int64_t bound, const char* call, const char* name) {
     if (idx)
         for (size_t i = 0; i < count; i++)
             if (idx[i] < 0 || idx[i] >= bound)
-                return fail(IEACHE_EINVAL, std::string(what) + "[" + std::to_string(i) + "] = " + std::to_string(idx[i]) + " is outside [0, " + std::to_string(bound) + ")");
+                return fail(IEACHE_EINVAL, std::string(call) + ": " + name + "[" + std::to_string(i) + "] = " + std::to_string(idx[i]) +
+                                               " is outside [0, " + std::to_string(bound) + ")");
     return 0;
 }
-}  // namespace
 
-ieache_tgsw* ieache_tgsw_prepare_device(ieache_ctx* ctx, const int32_t* d_samples, size_t n) {
-    ieache_tgsw* out = nullptr;
-    guarded([&] {
-        if (!ctx || !d_samples) return fail(IEACHE_EINVAL, "null argument");
-        if (n < 1) return fail(IEACHE_EINVAL, "tgsw_prepare: no samples");
-        require_device_pointer(d_samples, "d_samples");
-        std::unique_ptr<ieache_tgsw> h(new ieache_tgsw);
-        h->set.reset(ctx->eval->tgsw_prepare_device(d_samples, n));
-        out = h.release();
+// ---- The calls on a set (sections 3f to 3j).  set_calls.h states what each is; these read it.  `a`: the call's pointer
+// arguments in the order of its signature (kSetCalls[..].args). ----
+static_assert(kSetCalls[kCallLutRead].known_flags == IEACHE_LUT_READ_NO_KEYSWITCH && Evaluator::kLutReadNoKeyswitch == IEACHE_LUT_READ_NO_KEYSWITCH,
+              "set_calls.h knows, and the evaluator reads, the flags of include/ieache.h");
+int check_set_scalars(const SetCall& c) {
+    const std::string refusal = set_call_refusal(c);
+    return refusal.empty() ? 0 : fail(IEACHE_EINVAL, refusal);
+}
+// what the device and the host form refuse first: the context and the set, a null required argument; the scalars come next
+int check_set_call(const ieache_ctx* ctx, const ieache_tgsw* set, const SetCall& c, SetPtrs a) {
+    if (const int rc = check_tgsw(ctx, set)) return rc;
+    const SetCallShape& s = kSetCalls[c.kind];
+    for (int i = 0; i < s.n_args; i++)
+        if (!a.begin()[i] && set_arg_required(c, s.args[i])) return fail(IEACHE_EINVAL, "null argument");
+    return 0;
+}
+// the host and the reference forms: the scalars, then the first bad entry of the index arrays in argument order, then lut_read's coef
+int check_set_indices(const SetCall& c, SetPtrs a, int32_t N, size_t n_set) {
+    if (const int rc = check_set_scalars(c)) return rc;
+    const SetCallShape& s = kSetCalls[c.kind];
+    for (int i = 0; i < s.n_args; i++) {
+        const SetArg& arg = s.args[i];
+        if (arg.kind != kArgIndices) continue;
+        if (const int rc = check_indices(static_cast<const int32_t*>(a.begin()[i]), set_arg_units(c, arg), set_arg_bound(c, arg, N, n_set), s.name, arg.name + 2))
+            return rc;
+    }
+    return c.kind == kCallLutRead ? check_indices(&c.coef, 1, N, s.name, "coef") : 0;
+}
+// the device forms: the scalars, then every pointer the call will read or write; a null optional one is none
+int check_set_pointers(const SetCall& c, SetPtrs args) {
+    if (const int rc = check_set_scalars(c)) return rc;
+    const SetCallShape& s = kSetCalls[c.kind];
+    const void* const* a = args.begin();
+    for (int i = 0; i < s.n_args; i++)  // first, and always, what a call without items touches as well (lut_add's memories and output)
+        if (s.args[i].empty_too && (a[i] || s.args[i].need != kOptional)) require_device_pointer(a[i], s.args[i].name);
+    for (int i = 0; i < s.n_args && c.count; i++)  // then the rest, which only a call with items reads
+        if (!s.args[i].empty_too && (a[i] || s.args[i].need != kOptional)) require_device_pointer(a[i], s.args[i].name);
+    return 0;
+}
+extern "C++" {  // templates
+// The device form: refuse, check the pointers, run(stats).
+template <class Run>
+int set_call_device(ieache_ctx* ctx, const ieache_tgsw* set, const SetCall& c, const SetPtrs& a, ieache_stats* stats, Run&& run) {
+    return guarded([&] {
+        if (const int rc = check_set_call(ctx, set, c, a)) return rc;
+        if (const int rc = check_set_pointers(c, a)) return rc;
+        return with_stats(stats, run);
+    });
+}
+// The host form: refuse, stage every input where the table says (a null one stages nothing and stays null), run(evaluator, d,
+// stats) with d[i] argument i on the device, download `out` (a's last entry, as the pointer to write through).  An input staged
+// at the result rows is uploaded into them: the call then runs in place.  lut_read's rows are LWE rows, key-switched or extracted.
+template <class Run>
+int set_call_host(ieache_ctx* ctx, const ieache_tgsw* set, const SetCall& c, const SetPtrs& a, int32_t* out, ieache_stats* stats, Run&& run) {
+    return guarded([&] {
+        if (const int rc = check_set_call(ctx, set, c, a)) return rc;
+        if (const int rc = check_set_indices(c, a, ctx->eval->params().N, set->set->n)) return rc;
+        static constexpr StageSlot kSlot[] = {kStageOut, kStagePolyOf, kStageBias, kStageFactors, kStageTlweA, kStageTlweB, kStageTestPolys, kStageOut};
+        const SetCallShape& s = kSetCalls[c.kind];
+        HostCall h(ctx, c.count);
+        const size_t sample = (size_t)2 * (size_t)h.p.N, out_rows = set_arg_units(c, set_call_output(c));
+        const bool lwe = c.kind == kCallLutRead, extracted = lwe && (c.flags & IEACHE_LUT_READ_NO_KEYSWITCH);
+        StagedRows dout = lwe ? h.results(out_rows, extracted) : StagedRows(h.ev, kStageOut, out_rows, sample);
+        Torus32* d[kSetCallMaxArgs] = {};
+        d[s.n_args - 1] = dout.p;
+        for (int i = 0; i + 1 < s.n_args; i++) {
+            const SetArg& arg = s.args[i];
+            const int32_t* src = static_cast<const int32_t*>(a.begin()[i]);
+            const size_t units = set_arg_units(c, arg);
+            if (arg.kind == kArgIndices) {
+                d[i] = h.words(kSlot[arg.stage], src, units).p;
+            } else if (arg.stage == kAtResult) {
+                if (src && units) HIP_CHECK(hipMemcpy(dout.p, src, units * sample * 4, hipMemcpyHostToDevice));
+                d[i] = src ? dout.p : nullptr;
+            } else {
+                d[i] = StagedRows(h.ev, kSlot[arg.stage], units, sample, src, sample).p;
+            }
+        }
+        with_stats(stats, [&](EvalStats* st) { run(h.ev, d, st); });
+        if (lwe)
+            h.download(dout, out, extracted);
+        else
+            dout.download(out, sample);
         return 0;
     });
-    return out;
 }
+}  // extern "C++"
 
-ieache_tgsw* ieache_tgsw_prepare(ieache_ctx* ctx, const int32_t* samples, size_t n) {
+// The one preparation behind the four exported forms: samples on the host or the device, made with the context's gadget
+// (gadget false) or with (l, Bgbit).
+ieache_tgsw* tgsw_prepare(ieache_ctx* ctx, const int32_t* samples, size_t n, bool on_device, bool gadget, int32_t l, int32_t Bgbit) {
     ieache_tgsw* out = nullptr;
     guarded([&] {
         if (!ctx || !samples) return fail(IEACHE_EINVAL, "null argument");
-        if (n < 1) return fail(IEACHE_EINVAL, "tgsw_prepare: no samples");
         const Params& p = ctx->eval->params();
-        if (!br_supported(p)) return fail(IEACHE_EINVAL, "tgsw_prepare: the CMux kernels cover N = 1024, k = 1 with (l, Bgbit) = (3, 7) or (2, 10) only");
+        if (const char* why = gadget ? gadget_refusal(p, l, Bgbit) : nullptr) return fail(IEACHE_EINVAL, why);
+        if (n < 1) return fail(IEACHE_EINVAL, "tgsw_prepare: no samples");
+        auto prepare = [&](const Torus32* d_samples) {
+            std::unique_ptr<ieache_tgsw> h(new ieache_tgsw);
+            h->set.reset(gadget ? ctx->eval->tgsw_prepare_device(d_samples, n, l, Bgbit) : ctx->eval->tgsw_prepare_device(d_samples, n));
+            out = h.release();
+            return 0;
+        };
+        if (on_device) {
+            require_device_pointer(samples, "d_samples");
+            return prepare(samples);
+        }
+        if (!gadget && !br_supported(p))
+            return fail(IEACHE_EINVAL, "tgsw_prepare: the CMux kernels cover N = 1024, k = 1 with (l, Bgbit) = (3, 7) or (2, 10) only");
         HIP_CHECK(hipSetDevice(ctx->eval->device()));
-        DevRows words(n, (size_t)p.kpl() * 2 * (size_t)p.N);  // the int32 samples: scratch of this call
+        DevRows words(n, (gadget ? (size_t)2 * (size_t)l : (size_t)p.kpl()) * 2 * (size_t)p.N);  // the int32 samples: scratch of this call
         HIP_CHECK(hipMemcpy(words.p, samples, words.rows * words.stride * 4, hipMemcpyHostToDevice));
-        std::unique_ptr<ieache_tgsw> h(new ieache_tgsw);
-        h->set.reset(ctx->eval->tgsw_prepare_device(words.p, n));
-        out = h.release();
-        return 0;
+        return prepare(words.p);
     });
     return out;
 }
+}  // namespace
+
+ieache_tgsw* ieache_tgsw_prepare_device(ieache_ctx* ctx, const int32_t* d_samples, size_t n) { return tgsw_prepare(ctx, d_samples, n, true, false, 0, 0); }
+ieache_tgsw* ieache_tgsw_prepare(ieache_ctx* ctx, const int32_t* samples, size_t n) { return tgsw_prepare(ctx, samples, n, false, false, 0, 0); }
 
 void ieache_tgsw_free(ieache_tgsw* set) {
     if (!set) return;
@@ -1005,7 +1086,8 @@ void ieache_tgsw_free(ieache_tgsw* set) {
 int ieache_debug_cmux_plan(const ieache_ctx* ctx, size_t count, int32_t depth, int64_t out[4]) {
     return guarded([&] {
         if (!ctx || !out) return fail(IEACHE_EINVAL, "null argument");
-        if (depth > IEACHE_LUT_TREE_MAX_DEPTH) return fail(IEACHE_EINVAL, "lut_tree: depth must lie in 0 .. 12");
+        // a negative depth asks for the flat plan, so only the upper bound is a refusal here: lut_tree's, in its words
+        if (depth > IEACHE_LUT_TREE_MAX_DEPTH) return check_set_scalars(SetCall{kCallLutTree, count, depth});
         ctx->eval->cmux_plan_figures(count, depth, out);
         return 0;
     });
@@ -1013,210 +1095,84 @@ int ieache_debug_cmux_plan(const ieache_ctx* ctx, size_t count, int32_t depth, i
 
 int ieache_cmux_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, const int32_t* d_sel_of, const int32_t* d_d1, const int32_t* d_d0,
                        int32_t* d_out, ieache_stats* stats) {
-    return guarded([&] {
-        if (const int rc = check_tgsw(ctx, set)) return rc;
-        if (!d_d1 || !d_out) return fail(IEACHE_EINVAL, "null argument");
-        require_device_pointers(count, {{d_sel_of, "d_sel_of", true}, {d_d1, "d_d1"}, {d_d0, "d_d0", true}, {d_out, "d_out"}});
-        return with_stats(stats, [&](EvalStats* st) { ctx->eval->cmux_device(*set->set, count, d_sel_of, d_d1, d_d0, d_out, st); });
-    });
+    return set_call_device(ctx, set, {kCallCmux, count}, {d_sel_of, d_d1, d_d0, d_out}, stats,
+                           [&](EvalStats* st) { ctx->eval->cmux_device(*set->set, count, d_sel_of, d_d1, d_d0, d_out, st); });
 }
 
 int ieache_cmux(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, const int32_t* sel_of, const int32_t* d1, const int32_t* d0, int32_t* out,
                 ieache_stats* stats) {
-    return guarded([&] {
-        if (const int rc = check_tgsw(ctx, set)) return rc;
-        if (!d1 || !out) return fail(IEACHE_EINVAL, "null argument");
-        if (const int rc = check_indices(sel_of, count, (int64_t)set->set->n, "cmux: sel_of")) return rc;
-        HostCall h(ctx, count);
-        const size_t sample = (size_t)2 * (size_t)h.p.N;
-        StagedRows dd1(h.ev, kStageTlweA, count, sample, d1, sample), dd0(h.ev, kStageTlweB, count, sample, d0, sample);
-        StagedRows dsel = h.words(kStagePolyOf, sel_of, count), dout(h.ev, kStageOut, count, sample);
-        with_stats(stats, [&](EvalStats* st) { h.ev.cmux_device(*set->set, count, dsel.p, dd1.p, dd0.p, dout.p, st); });
-        dout.download(out, sample);
-        return 0;
+    return set_call_host(ctx, set, {kCallCmux, count}, {sel_of, d1, d0, out}, out, stats, [&](Evaluator& ev, Torus32* const* d, EvalStats* st) {
+        ev.cmux_device(*set->set, count, d[0], d[1], d[2], d[3], st);
     });
 }
 
 int ieache_lut_tree_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* d_sel_of, const int32_t* d_tables,
                            int32_t n_tables, const int32_t* d_table_of, int32_t* d_out, ieache_stats* stats) {
-    return guarded([&] {
-        if (const int rc = check_tgsw(ctx, set)) return rc;
-        if (!d_tables || !d_out) return fail(IEACHE_EINVAL, "null argument");
-        if (const int rc = check_tree(depth, n_tables)) return rc;
-        require_device_pointers(count, {{d_sel_of, "d_sel_of", true}, {d_tables, "d_tables"}, {d_table_of, "d_table_of", true}, {d_out, "d_out"}});
-        return with_stats(stats, [&](EvalStats* st) {
-            ctx->eval->lut_tree_device(*set->set, count, depth, d_sel_of, d_tables, n_tables, d_table_of, d_out, st);
-        });
+    return set_call_device(ctx, set, {kCallLutTree, count, depth, 0, n_tables}, {d_sel_of, d_tables, d_table_of, d_out}, stats, [&](EvalStats* st) {
+        ctx->eval->lut_tree_device(*set->set, count, depth, d_sel_of, d_tables, n_tables, d_table_of, d_out, st);
     });
 }
 
 int ieache_lut_tree(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* sel_of, const int32_t* tables,
                     int32_t n_tables, const int32_t* table_of, int32_t* out, ieache_stats* stats) {
-    return guarded([&] {
-        if (const int rc = check_tgsw(ctx, set)) return rc;
-        if (!tables || !out) return fail(IEACHE_EINVAL, "null argument");
-        if (const int rc = check_tree(depth, n_tables)) return rc;
-        if (const int rc = check_indices(sel_of, count * (size_t)depth, (int64_t)set->set->n, "lut_tree: sel_of")) return rc;
-        if (const int rc = check_indices(table_of, count, n_tables, "lut_tree: table_of")) return rc;
-        HostCall h(ctx, count);
-        const size_t sample = (size_t)2 * (size_t)h.p.N;
-        StagedRows dt(h.ev, kStageTestPolys, (size_t)n_tables << depth, sample, tables, sample);
-        StagedRows dsel = h.words(kStagePolyOf, sel_of, count * (size_t)depth), dof = h.words(kStageBias, table_of, count);
-        StagedRows dout(h.ev, kStageOut, count, sample);
-        with_stats(stats, [&](EvalStats* st) { h.ev.lut_tree_device(*set->set, count, depth, dsel.p, dt.p, n_tables, dof.p, dout.p, st); });
-        dout.download(out, sample);
-        return 0;
-    });
+    return set_call_host(ctx, set, {kCallLutTree, count, depth, 0, n_tables}, {sel_of, tables, table_of, out}, out, stats,
+                         [&](Evaluator& ev, Torus32* const* d, EvalStats* st) { ev.lut_tree_device(*set->set, count, depth, d[0], d[1], n_tables, d[2], d[3], st); });
 }
 
 // ---- the scatter (section 3g): the tree's partner ----
 int ieache_lut_scatter_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* d_sel_of, const int32_t* d_values,
                               const int32_t* d_mem, int32_t* d_out, ieache_stats* stats) {
-    return guarded([&] {
-        if (const int rc = check_tgsw(ctx, set)) return rc;
-        if (!d_values || !d_out) return fail(IEACHE_EINVAL, "null argument");
-        if (const int rc = check_scatter(depth)) return rc;
-        require_device_pointers(count, {{d_sel_of, "d_sel_of", true}, {d_values, "d_values"}, {d_mem, "d_mem", true}, {d_out, "d_out"}});
-        return with_stats(stats, [&](EvalStats* st) { ctx->eval->lut_scatter_device(*set->set, count, depth, d_sel_of, d_values, d_mem, d_out, st); });
+    return set_call_device(ctx, set, {kCallLutScatter, count, depth}, {d_sel_of, d_values, d_mem, d_out}, stats, [&](EvalStats* st) {
+        ctx->eval->lut_scatter_device(*set->set, count, depth, d_sel_of, d_values, d_mem, d_out, st);
     });
 }
 
 int ieache_lut_scatter(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* sel_of, const int32_t* values,
                        const int32_t* mem, int32_t* out, ieache_stats* stats) {
-    return guarded([&] {
-        if (const int rc = check_tgsw(ctx, set)) return rc;
-        if (!values || !out) return fail(IEACHE_EINVAL, "null argument");
-        if (const int rc = check_scatter(depth)) return rc;
-        if (const int rc = check_indices(sel_of, count * (size_t)depth, (int64_t)set->set->n, "lut_scatter: sel_of")) return rc;
-        HostCall h(ctx, count);
-        const size_t sample = (size_t)2 * (size_t)h.p.N, rows = count << depth;
-        StagedRows dv(h.ev, kStageTlweA, count, sample, values, sample), dsel = h.words(kStagePolyOf, sel_of, count * (size_t)depth);
-        // the memory goes into the result rows and the call runs in place
-        StagedRows dout(h.ev, kStageOut, rows, sample);
-        if (mem && rows) HIP_CHECK(hipMemcpy(dout.p, mem, rows * sample * 4, hipMemcpyHostToDevice));
-        with_stats(stats, [&](EvalStats* st) { h.ev.lut_scatter_device(*set->set, count, depth, dsel.p, dv.p, mem ? dout.p : nullptr, dout.p, st); });
-        dout.download(out, sample);
-        return 0;
-    });
+    return set_call_host(ctx, set, {kCallLutScatter, count, depth}, {sel_of, values, mem, out}, out, stats,
+                         [&](Evaluator& ev, Torus32* const* d, EvalStats* st) { ev.lut_scatter_device(*set->set, count, depth, d[0], d[1], d[2], d[3], st); });
 }
 
 // ---- the rotation by caller selectors and the coefficient-level lookup (section 3h) ----
-namespace {
-int check_rotate(int32_t steps, const char* who) {
-    if (steps < 0 || steps > IEACHE_ROTATE_MAX_STEPS) return fail(IEACHE_EINVAL, std::string(who) + ": steps must lie in 0 .. 64");
-    return 0;
-}
-int check_read(int32_t depth, int32_t steps, int32_t n_tables, int flags) {
-    if (depth < 0 || depth > IEACHE_LUT_TREE_MAX_DEPTH) return fail(IEACHE_EINVAL, "lut_read: depth must lie in 0 .. 12");
-    if (const int rc = check_rotate(steps, "lut_read")) return rc;
-    if (n_tables < 1) return fail(IEACHE_EINVAL, "lut_read: n_tables must be at least 1");
-    if (flags & ~IEACHE_LUT_READ_NO_KEYSWITCH) return fail(IEACHE_EINVAL, "lut_read: unknown flag");
-    return 0;
-}
-}  // namespace
-
 int ieache_tlwe_rotate_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t steps, const int32_t* d_sel_of,
                               const int32_t* d_amount_of, const int32_t* d_in, int32_t* d_out, ieache_stats* stats) {
-    return guarded([&] {
-        if (const int rc = check_tgsw(ctx, set)) return rc;
-        if (!d_in || !d_out) return fail(IEACHE_EINVAL, "null argument");
-        if (const int rc = check_rotate(steps, "tlwe_rotate")) return rc;
-        require_device_pointers(count, {{d_sel_of, "d_sel_of", true}, {d_amount_of, "d_amount_of", true}, {d_in, "d_in"}, {d_out, "d_out"}});
-        return with_stats(stats, [&](EvalStats* st) { ctx->eval->tlwe_rotate_device(*set->set, count, steps, d_sel_of, d_amount_of, d_in, d_out, st); });
+    return set_call_device(ctx, set, {kCallTlweRotate, count, 0, steps}, {d_sel_of, d_amount_of, d_in, d_out}, stats, [&](EvalStats* st) {
+        ctx->eval->tlwe_rotate_device(*set->set, count, steps, d_sel_of, d_amount_of, d_in, d_out, st);
     });
 }
 
 int ieache_tlwe_rotate(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t steps, const int32_t* sel_of, const int32_t* amount_of,
                        const int32_t* in, int32_t* out, ieache_stats* stats) {
-    return guarded([&] {
-        if (const int rc = check_tgsw(ctx, set)) return rc;
-        if (!in || !out) return fail(IEACHE_EINVAL, "null argument");
-        if (const int rc = check_rotate(steps, "tlwe_rotate")) return rc;
-        if (const int rc = check_indices(sel_of, count * (size_t)steps, (int64_t)set->set->n, "tlwe_rotate: sel_of")) return rc;
-        if (const int rc = check_indices(amount_of, (size_t)steps, 2 * (int64_t)ctx->eval->params().N, "tlwe_rotate: amount_of")) return rc;
-        HostCall h(ctx, count);
-        const size_t sample = (size_t)2 * (size_t)h.p.N;
-        StagedRows din(h.ev, kStageTlweA, count, sample, in, sample), dsel = h.words(kStagePolyOf, sel_of, count * (size_t)steps);
-        StagedRows dam = h.words(kStageBias, amount_of, (size_t)steps), dout(h.ev, kStageOut, count, sample);
-        with_stats(stats, [&](EvalStats* st) { h.ev.tlwe_rotate_device(*set->set, count, steps, dsel.p, dam.p, din.p, dout.p, st); });
-        dout.download(out, sample);
-        return 0;
-    });
+    return set_call_host(ctx, set, {kCallTlweRotate, count, 0, steps}, {sel_of, amount_of, in, out}, out, stats,
+                         [&](Evaluator& ev, Torus32* const* d, EvalStats* st) { ev.tlwe_rotate_device(*set->set, count, steps, d[0], d[1], d[2], d[3], st); });
 }
 
 int ieache_lut_read_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of,
                            const int32_t* d_amount_of, const int32_t* d_tables, int32_t n_tables, const int32_t* d_table_of, int32_t coef, int flags,
                            int32_t* d_out, ieache_stats* stats) {
-    return guarded([&] {
-        if (const int rc = check_tgsw(ctx, set)) return rc;
-        if (!d_tables || !d_out) return fail(IEACHE_EINVAL, "null argument");
-        if (const int rc = check_read(depth, steps, n_tables, flags)) return rc;
-        require_device_pointers(count, {{d_sel_of, "d_sel_of", true}, {d_amount_of, "d_amount_of", true}, {d_tables, "d_tables"},
-                                        {d_table_of, "d_table_of", true}, {d_out, "d_out"}});
-        return with_stats(stats, [&](EvalStats* st) {
-            ctx->eval->lut_read_device(*set->set, count, depth, steps, d_sel_of, d_amount_of, d_tables, n_tables, d_table_of, coef, flags, d_out, st);
-        });
-    });
+    return set_call_device(ctx, set, {kCallLutRead, count, depth, steps, n_tables, flags, coef}, {d_sel_of, d_amount_of, d_tables, d_table_of, d_out}, stats,
+                           [&](EvalStats* st) {
+                               ctx->eval->lut_read_device(*set->set, count, depth, steps, d_sel_of, d_amount_of, d_tables, n_tables, d_table_of, coef, flags,
+                                                          d_out, st);
+                           });
 }
 
 int ieache_lut_read(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, const int32_t* sel_of,
                     const int32_t* amount_of, const int32_t* tables, int32_t n_tables, const int32_t* table_of, int32_t coef, int flags, int32_t* out,
                     ieache_stats* stats) {
-    return guarded([&] {
-        if (const int rc = check_tgsw(ctx, set)) return rc;
-        if (!tables || !out) return fail(IEACHE_EINVAL, "null argument");
-        if (const int rc = check_read(depth, steps, n_tables, flags)) return rc;
-        const int64_t N = ctx->eval->params().N;
-        if (const int rc = check_indices(sel_of, count * (size_t)(depth + steps), (int64_t)set->set->n, "lut_read: sel_of")) return rc;
-        if (const int rc = check_indices(amount_of, (size_t)steps, 2 * N, "lut_read: amount_of")) return rc;
-        if (const int rc = check_indices(table_of, count, n_tables, "lut_read: table_of")) return rc;
-        if (const int rc = check_indices(&coef, 1, N, "lut_read: coef")) return rc;
-        HostCall h(ctx, count);
-        const size_t sample = (size_t)2 * (size_t)h.p.N;
-        const bool woks = (flags & IEACHE_LUT_READ_NO_KEYSWITCH) != 0;
-        StagedRows dt(h.ev, kStageTestPolys, (size_t)n_tables << depth, sample, tables, sample);
-        StagedRows dsel = h.words(kStagePolyOf, sel_of, count * (size_t)(depth + steps)), dof = h.words(kStageBias, table_of, count);
-        StagedRows dam = h.words(kStageFactors, amount_of, (size_t)steps), dout = h.results(count, woks);
-        with_stats(stats, [&](EvalStats* st) {
-            h.ev.lut_read_device(*set->set, count, depth, steps, dsel.p, dam.p, dt.p, n_tables, dof.p, coef, flags, dout.p, st);
-        });
-        h.download(dout, out, woks);
-        return 0;
-    });
+    return set_call_host(ctx, set, {kCallLutRead, count, depth, steps, n_tables, flags, coef}, {sel_of, amount_of, tables, table_of, out}, out, stats,
+                         [&](Evaluator& ev, Torus32* const* d, EvalStats* st) {
+                             Torus32 *dsel = d[0], *damount = d[1], *dtables = d[2], *dof = d[3], *dout = d[4];
+                             ev.lut_read_device(*set->set, count, depth, steps, dsel, damount, dtables, n_tables, dof, coef, flags, dout, st);
+                         });
 }
 
 // ---- sets with a gadget of their own, and the replace write (section 3i) ----
 ieache_tgsw* ieache_tgsw_prepare_gadget_device(ieache_ctx* ctx, const int32_t* d_samples, size_t n, int32_t l, int32_t Bgbit) {
-    ieache_tgsw* out = nullptr;
-    guarded([&] {
-        if (!ctx || !d_samples) return fail(IEACHE_EINVAL, "null argument");
-        if (const char* why = gadget_refusal(ctx->eval->params(), l, Bgbit)) return fail(IEACHE_EINVAL, why);
-        if (n < 1) return fail(IEACHE_EINVAL, "tgsw_prepare: no samples");
-        require_device_pointer(d_samples, "d_samples");
-        std::unique_ptr<ieache_tgsw> h(new ieache_tgsw);
-        h->set.reset(ctx->eval->tgsw_prepare_device(d_samples, n, l, Bgbit));
-        out = h.release();
-        return 0;
-    });
-    return out;
+    return tgsw_prepare(ctx, d_samples, n, true, true, l, Bgbit);
 }
-
 ieache_tgsw* ieache_tgsw_prepare_gadget(ieache_ctx* ctx, const int32_t* samples, size_t n, int32_t l, int32_t Bgbit) {
-    ieache_tgsw* out = nullptr;
-    guarded([&] {
-        if (!ctx || !samples) return fail(IEACHE_EINVAL, "null argument");
-        const Params& p = ctx->eval->params();
-        if (const char* why = gadget_refusal(p, l, Bgbit)) return fail(IEACHE_EINVAL, why);
-        if (n < 1) return fail(IEACHE_EINVAL, "tgsw_prepare: no samples");
-        HIP_CHECK(hipSetDevice(ctx->eval->device()));
-        DevRows words(n, (size_t)2 * (size_t)l * 2 * (size_t)p.N);  // the int32 samples: scratch of this call
-        HIP_CHECK(hipMemcpy(words.p, samples, words.rows * words.stride * 4, hipMemcpyHostToDevice));
-        std::unique_ptr<ieache_tgsw> h(new ieache_tgsw);
-        h->set.reset(ctx->eval->tgsw_prepare_device(words.p, n, l, Bgbit));
-        out = h.release();
-        return 0;
-    });
-    return out;
+    return tgsw_prepare(ctx, samples, n, false, true, l, Bgbit);
 }
 
 int ieache_tgsw_gadget(const ieache_tgsw* set, int32_t* l, int32_t* Bgbit) {
@@ -1228,98 +1184,37 @@ int ieache_tgsw_gadget(const ieache_tgsw* set, int32_t* l, int32_t* Bgbit) {
     });
 }
 
-namespace {
-int check_write(int32_t depth) {
-    if (depth < 0 || depth > IEACHE_LUT_TREE_MAX_DEPTH) return fail(IEACHE_EINVAL, "lut_write: depth must lie in 0 .. 12");
-    return 0;
-}
-}  // namespace
-
 int ieache_lut_write_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* d_sel_of, const int32_t* d_new,
                             const int32_t* d_mem, int32_t* d_out, ieache_stats* stats) {
-    return guarded([&] {
-        if (const int rc = check_tgsw(ctx, set)) return rc;
-        if (!d_new || !d_mem || !d_out) return fail(IEACHE_EINVAL, "null argument");
-        if (const int rc = check_write(depth)) return rc;
-        require_device_pointers(count, {{d_sel_of, "d_sel_of", true}, {d_new, "d_new"}, {d_mem, "d_mem"}, {d_out, "d_out"}});
-        return with_stats(stats, [&](EvalStats* st) { ctx->eval->lut_write_device(*set->set, count, depth, d_sel_of, d_new, d_mem, d_out, st); });
+    return set_call_device(ctx, set, {kCallLutWrite, count, depth}, {d_sel_of, d_new, d_mem, d_out}, stats, [&](EvalStats* st) {
+        ctx->eval->lut_write_device(*set->set, count, depth, d_sel_of, d_new, d_mem, d_out, st);
     });
 }
 
 int ieache_lut_write(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, const int32_t* sel_of, const int32_t* fresh,
                      const int32_t* mem, int32_t* out, ieache_stats* stats) {
-    return guarded([&] {
-        if (const int rc = check_tgsw(ctx, set)) return rc;
-        if (!fresh || !mem || !out) return fail(IEACHE_EINVAL, "null argument");
-        if (const int rc = check_write(depth)) return rc;
-        if (const int rc = check_indices(sel_of, count * (size_t)depth, (int64_t)set->set->n, "lut_write: sel_of")) return rc;
-        HostCall h(ctx, count);
-        const size_t sample = (size_t)2 * (size_t)h.p.N, rows = count << depth;
-        StagedRows dv(h.ev, kStageTlweA, count, sample, fresh, sample), dsel = h.words(kStagePolyOf, sel_of, count * (size_t)depth);
-        // the memory goes into the result rows and the call runs in place
-        StagedRows dout(h.ev, kStageOut, rows, sample);
-        if (rows) HIP_CHECK(hipMemcpy(dout.p, mem, rows * sample * 4, hipMemcpyHostToDevice));
-        with_stats(stats, [&](EvalStats* st) { h.ev.lut_write_device(*set->set, count, depth, dsel.p, dv.p, dout.p, dout.p, st); });
-        dout.download(out, sample);
-        return 0;
-    });
+    return set_call_host(ctx, set, {kCallLutWrite, count, depth}, {sel_of, fresh, mem, out}, out, stats,
+                         [&](Evaluator& ev, Torus32* const* d, EvalStats* st) { ev.lut_write_device(*set->set, count, depth, d[0], d[1], d[2], d[3], st); });
 }
 
 // ---- many values into shared memories (section 3j) ----
-namespace {
-int check_lut_add(int32_t depth, int32_t steps, int32_t n_mems) {
-    if (depth < 0 || depth > IEACHE_LUT_TREE_MAX_DEPTH) return fail(IEACHE_EINVAL, "lut_add: depth must lie in 0 .. 12");
-    if (const int rc = check_rotate(steps, "lut_add")) return rc;
-    if (n_mems < 1) return fail(IEACHE_EINVAL, "lut_add: n_mems must be at least 1");
-    return 0;
-}
-// the host indices of a call: selectors, amounts, memories
-int check_lut_add_indices(size_t n_set, int64_t N, size_t count, int32_t depth, int32_t steps, const int32_t* sel_of, const int32_t* amount_of,
-                          int32_t n_mems, const int32_t* mem_of) {
-    if (const int rc = check_indices(sel_of, count * (size_t)(depth + steps), (int64_t)n_set, "lut_add: sel_of")) return rc;
-    if (const int rc = check_indices(amount_of, (size_t)steps, 2 * N, "lut_add: amount_of")) return rc;
-    return check_indices(mem_of, count, n_mems, "lut_add: mem_of");
-}
-}  // namespace
-
 int ieache_lut_add_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of,
                           const int32_t* d_amount_of, const int32_t* d_values, const int32_t* d_mems, int32_t n_mems, const int32_t* d_mem_of,
                           int32_t* d_out, ieache_stats* stats) {
-    return guarded([&] {
-        if (const int rc = check_tgsw(ctx, set)) return rc;
-        if ((count && !d_values) || !d_out) return fail(IEACHE_EINVAL, "null argument");
-        if (const int rc = check_lut_add(depth, steps, n_mems)) return rc;
-        // the memories are touched (copied or zero-filled) by an empty call as well
-        require_device_pointers(1, {{d_mems, "d_mems", true}, {d_out, "d_out"}});
-        require_device_pointers(count, {{d_sel_of, "d_sel_of", true}, {d_amount_of, "d_amount_of", true}, {d_values, "d_values"},
-                                        {d_mem_of, "d_mem_of", true}});
-        return with_stats(stats, [&](EvalStats* st) {
-            ctx->eval->lut_add_device(*set->set, count, depth, steps, d_sel_of, d_amount_of, d_values, d_mems, n_mems, d_mem_of, d_out, st);
-        });
-    });
+    return set_call_device(ctx, set, {kCallLutAdd, count, depth, steps, n_mems}, {d_sel_of, d_amount_of, d_values, d_mems, d_mem_of, d_out}, stats,
+                           [&](EvalStats* st) {
+                               ctx->eval->lut_add_device(*set->set, count, depth, steps, d_sel_of, d_amount_of, d_values, d_mems, n_mems, d_mem_of, d_out, st);
+                           });
 }
 
 int ieache_lut_add(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, const int32_t* sel_of,
                    const int32_t* amount_of, const int32_t* values, const int32_t* mems, int32_t n_mems, const int32_t* mem_of, int32_t* out,
                    ieache_stats* stats) {
-    return guarded([&] {
-        if (const int rc = check_tgsw(ctx, set)) return rc;
-        if ((count && !values) || !out) return fail(IEACHE_EINVAL, "null argument");
-        if (const int rc = check_lut_add(depth, steps, n_mems)) return rc;
-        if (const int rc = check_lut_add_indices(set->set->n, ctx->eval->params().N, count, depth, steps, sel_of, amount_of, n_mems, mem_of)) return rc;
-        HostCall h(ctx, count);
-        const size_t sample = (size_t)2 * (size_t)h.p.N, rows = (size_t)n_mems << depth;
-        StagedRows dv(h.ev, kStageTlweA, count, sample, values, sample), dsel = h.words(kStagePolyOf, sel_of, count * (size_t)(depth + steps));
-        StagedRows dam = h.words(kStageFactors, amount_of, (size_t)steps), dof = h.words(kStageBias, mem_of, count);
-        // the memories go into the result rows and the call runs in place
-        StagedRows dout(h.ev, kStageOut, rows, sample);
-        if (mems) HIP_CHECK(hipMemcpy(dout.p, mems, rows * sample * 4, hipMemcpyHostToDevice));
-        with_stats(stats, [&](EvalStats* st) {
-            h.ev.lut_add_device(*set->set, count, depth, steps, dsel.p, dam.p, dv.p, mems ? dout.p : nullptr, n_mems, dof.p, dout.p, st);
-        });
-        dout.download(out, sample);
-        return 0;
-    });
+    return set_call_host(ctx, set, {kCallLutAdd, count, depth, steps, n_mems}, {sel_of, amount_of, values, mems, mem_of, out}, out, stats,
+                         [&](Evaluator& ev, Torus32* const* d, EvalStats* st) {
+                             Torus32 *dsel = d[0], *damount = d[1], *dvalues = d[2], *dmems = d[3], *dof = d[4], *dout = d[5];
+                             ev.lut_add_device(*set->set, count, depth, steps, dsel, damount, dvalues, dmems, n_mems, dof, dout, st);
+                         });
 }
 
 int ieache_tlwe_extract_device(ieache_ctx* ctx, size_t count, const int32_t* d_tlwe, const int32_t* d_coef_of, int32_t* d_u, ieache_stats* stats) {
@@ -1333,7 +1228,7 @@ int ieache_tlwe_extract_device(ieache_ctx* ctx, size_t count, const int32_t* d_t
 int ieache_tlwe_extract(ieache_ctx* ctx, size_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u, ieache_stats* stats) {
     return guarded([&] {
         if (const int rc = check_rows({ctx, tlwe, u})) return rc;
-        if (const int rc = check_indices(coef_of, count, ctx->eval->params().N, "tlwe_extract: coef_of")) return rc;
+        if (const int rc = check_indices(coef_of, count, ctx->eval->params().N, "tlwe_extract", "coef_of")) return rc;
         HostCall h(ctx, count);
         const size_t sample = (size_t)2 * (size_t)h.p.N;
         StagedRows dt(h.ev, kStageTlweA, count, sample, tlwe, sample), dof = h.words(kStagePolyOf, coef_of, count), du = h.results(count, true);
@@ -1790,7 +1685,7 @@ int ieache_cmux_reference(const ieache_params* p, const int32_t* set, size_t n, 
         const Params pp = to_params(*p);
         if (!pp.supported()) return fail(IEACHE_EINVAL, "cmux_reference: unsupported TFHE parameter set");
         if (n < 1) return fail(IEACHE_EINVAL, "cmux_reference: no samples");
-        if (const int rc = check_indices(sel_of, count, (int64_t)n, "cmux: sel_of")) return rc;
+        if (const int rc = check_set_indices({kCallCmux, count}, {sel_of, d1, d0, out}, pp.N, n)) return rc;
         cmux_reference(pp, set, n, count, sel_of, d1, d0, out);
         return 0;
     });
@@ -1803,9 +1698,7 @@ int ieache_lut_tree_reference(const ieache_params* p, const int32_t* set, size_t
         const Params pp = to_params(*p);
         if (!pp.supported()) return fail(IEACHE_EINVAL, "lut_tree_reference: unsupported TFHE parameter set");
         if (n < 1) return fail(IEACHE_EINVAL, "lut_tree_reference: no samples");
-        if (const int rc = check_tree(depth, n_tables)) return rc;
-        if (const int rc = check_indices(sel_of, count * (size_t)depth, (int64_t)n, "lut_tree: sel_of")) return rc;
-        if (const int rc = check_indices(table_of, count, n_tables, "lut_tree: table_of")) return rc;
+        if (const int rc = check_set_indices({kCallLutTree, count, depth, 0, n_tables}, {sel_of, tables, table_of, out}, pp.N, n)) return rc;
         lut_tree_reference(pp, set, n, count, depth, sel_of, tables, table_of, out);
         return 0;
     });
@@ -1818,8 +1711,7 @@ int ieache_lut_scatter_reference(const ieache_params* p, const int32_t* set, siz
         const Params pp = to_params(*p);
         if (!pp.supported()) return fail(IEACHE_EINVAL, "lut_scatter_reference: unsupported TFHE parameter set");
         if (n < 1) return fail(IEACHE_EINVAL, "lut_scatter_reference: no samples");
-        if (const int rc = check_scatter(depth)) return rc;
-        if (const int rc = check_indices(sel_of, count * (size_t)depth, (int64_t)n, "lut_scatter: sel_of")) return rc;
+        if (const int rc = check_set_indices({kCallLutScatter, count, depth}, {sel_of, values, mem, out}, pp.N, n)) return rc;
         lut_scatter_reference(pp, set, n, count, depth, sel_of, values, mem, out);
         return 0;
     });
@@ -1832,9 +1724,7 @@ int ieache_tlwe_rotate_reference(const ieache_params* p, const int32_t* set, siz
         const Params pp = to_params(*p);
         if (!pp.supported()) return fail(IEACHE_EINVAL, "tlwe_rotate_reference: unsupported TFHE parameter set");
         if (n < 1) return fail(IEACHE_EINVAL, "tlwe_rotate_reference: no samples");
-        if (const int rc = check_rotate(steps, "tlwe_rotate")) return rc;
-        if (const int rc = check_indices(sel_of, count * (size_t)steps, (int64_t)n, "tlwe_rotate: sel_of")) return rc;
-        if (const int rc = check_indices(amount_of, (size_t)steps, 2 * (int64_t)pp.N, "tlwe_rotate: amount_of")) return rc;
+        if (const int rc = check_set_indices({kCallTlweRotate, count, 0, steps}, {sel_of, amount_of, in, out}, pp.N, n)) return rc;
         tlwe_rotate_reference(pp, set, n, count, steps, sel_of, amount_of, in, out);
         return 0;
     });
@@ -1848,13 +1738,11 @@ int ieache_lut_read_reference(const ieache_params* p, const int32_t* set, size_t
         const Params pp = to_params(*p);
         if (!pp.supported()) return fail(IEACHE_EINVAL, "lut_read_reference: unsupported TFHE parameter set");
         if (n < 1) return fail(IEACHE_EINVAL, "lut_read_reference: no samples");
-        if (const int rc = check_read(depth, steps, n_tables, flags)) return rc;
+        const SetCall c{kCallLutRead, count, depth, steps, n_tables, flags, coef};
+        if (const int rc = check_set_scalars(c)) return rc;
         const bool woks = (flags & IEACHE_LUT_READ_NO_KEYSWITCH) != 0;
         if (!woks && !ksk) return fail(IEACHE_EINVAL, "lut_read_reference: the key switch needs ksk");
-        if (const int rc = check_indices(sel_of, count * (size_t)(depth + steps), (int64_t)n, "lut_read: sel_of")) return rc;
-        if (const int rc = check_indices(amount_of, (size_t)steps, 2 * (int64_t)pp.N, "lut_read: amount_of")) return rc;
-        if (const int rc = check_indices(table_of, count, n_tables, "lut_read: table_of")) return rc;
-        if (const int rc = check_indices(&coef, 1, pp.N, "lut_read: coef")) return rc;
+        if (const int rc = check_set_indices(c, {sel_of, amount_of, tables, table_of, out}, pp.N, n)) return rc;
         lut_read_reference(pp, set, n, woks ? nullptr : ksk, count, depth, steps, sel_of, amount_of, tables, table_of, coef, out);
         return 0;
     });
@@ -1867,8 +1755,7 @@ int ieache_lut_add_reference(const ieache_params* p, const int32_t* set, size_t 
         const Params pp = to_params(*p);
         if (!pp.supported()) return fail(IEACHE_EINVAL, "lut_add_reference: unsupported TFHE parameter set");
         if (n < 1) return fail(IEACHE_EINVAL, "lut_add_reference: no samples");
-        if (const int rc = check_lut_add(depth, steps, n_mems)) return rc;
-        if (const int rc = check_lut_add_indices(n, pp.N, count, depth, steps, sel_of, amount_of, n_mems, mem_of)) return rc;
+        if (const int rc = check_set_indices({kCallLutAdd, count, depth, steps, n_mems}, {sel_of, amount_of, values, mems, mem_of, out}, pp.N, n)) return rc;
         lut_add_reference(pp, set, n, count, depth, steps, sel_of, amount_of, values, mems, (size_t)n_mems, mem_of, out);
         return 0;
     });
@@ -1879,7 +1766,7 @@ int ieache_tlwe_extract_reference(const ieache_params* p, size_t count, const in
         if (!p || (count && (!tlwe || !u))) return fail(IEACHE_EINVAL, "null argument");
         const Params pp = to_params(*p);
         if (!pp.supported()) return fail(IEACHE_EINVAL, "tlwe_extract_reference: unsupported TFHE parameter set");
-        if (const int rc = check_indices(coef_of, count, pp.N, "tlwe_extract: coef_of")) return rc;
+        if (const int rc = check_indices(coef_of, count, pp.N, "tlwe_extract", "coef_of")) return rc;
         tlwe_extract_reference(pp, count, tlwe, coef_of, u);
         return 0;
     });

@@ -5,7 +5,8 @@
 //   section 3i  sets with a gadget of their own, and the replace write;
 //   section 3j  many values added into shared memories in one call.
 // The kernels, the spectrum form of a prepared set, the twiddle table and the scratch of a tree are behind this object; how
-// a call is cut is cmux_plan.h.  Kernels: cmux.hip (3f, 3g) and rotate.hip (3h); what the two share is cmux_step.h.
+// a call is cut is cmux_plan.h; what a call is -- scalars, refusals, arguments -- is set_calls.h.  Kernels: cmux.hip (3f, 3g)
+// and rotate.hip (3h); what the two share is cmux_step.h.
 #pragma once
 #include <cstdint>
 

@@ -17,6 +17,7 @@ namespace ieache {
 struct OptionRow;  // evaluator_options.h
 struct TgswSet;    // cmux.h
 struct CmuxPlan;   // cmux_plan.h
+struct SetCall;    // set_calls.h
 
 struct EvalStats {
     double total_ms = 0;         // wall time of the call on the GPU timeline (events on the stream)
@@ -316,7 +317,9 @@ private:
     // runs `once`, and again on the two-limb kernels if the rounding guard or the audit asks for it (evaluator.hip)
     template <class F>
     void run_guarded(bool inputs_intact, EvalStats* stats, F&& once);
-    // the piece loop of the calls on caller TGSW samples (evaluator.hip)
+    // what the calls on caller TGSW samples open with, from the table of set_calls.h -> whether there are items to run (evaluator.hip)
+    bool begin_set_call(const TgswSet& set, const SetCall& c, std::initializer_list<const void*> args, size_t out_row_words);
+    // their piece loop (evaluator.hip)
     template <class Body, class KeySwitch>
     void run_cmux_pieces(const CmuxPlan& pl, size_t count, int32_t levels, EvalStats* stats, Body&& body, int64_t ks_rows, KeySwitch&& ks);
     template <class Body>

@@ -31,6 +31,7 @@
 #include "multi_extract.h"
 #include "pack.h"
 #include "scoped_set.h"
+#include "set_calls.h"
 
 #include <algorithm>
 #include <cmath>
@@ -969,7 +970,8 @@ TgswSet* Evaluator::tgsw_prepare_device(const Torus32* d_samples, size_t n, int3
 uint64_t Evaluator::cmux_id() const { return d_->cmux.id(); }
 
 void Evaluator::cmux_plan_figures(size_t count, int32_t depth, int64_t out[4]) const {
-    if (depth > kCmuxMaxDepth) throw std::invalid_argument("lut_tree: depth must lie in 0 .. 12");
+    // a negative depth asks for the flat plan: only the upper bound is refused, as lut_tree refuses it
+    if (depth > kCmuxMaxDepth) throw std::invalid_argument(set_call_refusal(SetCall{kCallLutTree, count, depth}));
     const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
     out[0] = pl.pieces;
     out[1] = pl.items_per_piece;
@@ -1014,16 +1016,38 @@ void Evaluator::run_cmux_pieces(const CmuxPlan& pl, size_t count, int32_t levels
     run_cmux_pieces(pl, count, levels, stats, body, 0, [](int64_t, int64_t, int64_t) {});
 }
 
+// What every call on a set opens with, from the table of set_calls.h (`a`: the call's pointer arguments in its order): the
+// set is this context's, the scalars are in range, the output shares no word with an input -- but for the one input that may
+// be the output exactly -- then begin_call() and the rows a call needs are there.  -> whether there are items to run
+bool Evaluator::begin_set_call(const TgswSet& set, const SetCall& c, std::initializer_list<const void*> args, size_t out_row_words) {
+    const void* const* a = args.begin();
+    d_->cmux.check_owner(set);
+    const std::string refusal = set_call_refusal(c);
+    if (!refusal.empty()) throw std::invalid_argument(refusal);
+    const SetCallShape& s = kSetCalls[c.kind];
+    const int out = s.n_args - 1;
+    const SetArg* alias = nullptr;
+    bool shared = false;
+    for (int i = 0; i < out; i++) {
+        if (s.args[i].role == kMayBeOutput) alias = &s.args[i];
+        if (s.args[i].role == kMayBeOutput && a[i] == a[out]) continue;
+        shared |= overlaps(static_cast<const Torus32*>(a[out]), set_arg_words(c, s.args[out], p_.N, out_row_words),
+                           {{a[i], set_arg_words(c, s.args[i], p_.N, out_row_words)}});
+    }
+    if (shared)
+        throw std::invalid_argument(std::string(s.name) + ": the output overlaps an input" +
+                                    (alias ? std::string(" (only d_out == ") + alias->name + ", the " + s.in_place + " in place, is accepted)" : ""));
+    begin_call();
+    for (int i = 0; i <= out; i++)
+        if (!a[i] && s.args[i].need != kOptional && (c.count > 0 || s.args[i].empty_too)) throw std::invalid_argument(std::string(s.name) + ": null rows");
+    return c.count > 0;
+}
+
 // The flat CMux: pieces of at most "cmux_piece_rows" rows, one launch each.
 void Evaluator::cmux_device(const TgswSet& set, size_t count, const int32_t* d_sel_of, const Torus32* d_d1, const Torus32* d_d0, Torus32* d_out,
                             EvalStats* stats) {
-    d_->cmux.check_owner(set);
     const size_t row = (size_t)2 * (size_t)p_.N;
-    if (overlaps(d_out, count * row, {{d_d1, count * row}, {d_d0, count * row}, {d_sel_of, count}}))
-        throw std::invalid_argument("cmux: the output overlaps an input");
-    begin_call();
-    if (count == 0) return;
-    if (!d_d1 || !d_out) throw std::invalid_argument("cmux: null rows");
+    if (!begin_set_call(set, SetCall{kCallCmux, count}, {d_sel_of, d_d1, d_d0, d_out}, row)) return;
     run_cmux_pieces(cmux_plan((int64_t)count, -1, d_->opt.cmux_piece_rows), count, 1, stats, [&](int64_t r0, int64_t rows) {
         CmuxRows R;
         R.rows = rows;
@@ -1041,15 +1065,8 @@ void Evaluator::cmux_device(const TgswSet& set, size_t count, const int32_t* d_s
 // largest piece before the first.
 void Evaluator::lut_tree_device(const TgswSet& set, size_t count, int32_t depth, const int32_t* d_sel_of, const Torus32* d_tables, int32_t n_tables,
                                 const int32_t* d_table_of, Torus32* d_out, EvalStats* stats) {
-    d_->cmux.check_owner(set);
-    if (depth < 0 || depth > kCmuxMaxDepth) throw std::invalid_argument("lut_tree: depth must lie in 0 .. 12");
-    if (n_tables < 1) throw std::invalid_argument("lut_tree: n_tables must be at least 1");
     const size_t row = (size_t)2 * (size_t)p_.N;
-    if (overlaps(d_out, count * row, {{d_tables, ((size_t)n_tables << depth) * row}, {d_sel_of, count * (size_t)depth}, {d_table_of, count}}))
-        throw std::invalid_argument("lut_tree: the output overlaps an input");
-    begin_call();
-    if (count == 0) return;
-    if (!d_tables || !d_out) throw std::invalid_argument("lut_tree: null rows");
+    if (!begin_set_call(set, SetCall{kCallLutTree, count, depth, 0, n_tables}, {d_sel_of, d_tables, d_table_of, d_out}, row)) return;
     Lane& ln = d_->lane[0];
     const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
     d_->cmux.reserve(ln.cmux, pl);
@@ -1062,21 +1079,14 @@ void Evaluator::lut_tree_device(const TgswSet& set, size_t count, int32_t depth,
 // adds the memory rows and may write over them.
 void Evaluator::lut_scatter_device(const TgswSet& set, size_t count, int32_t depth, const int32_t* d_sel_of, const Torus32* d_values,
                                    const Torus32* d_mem, Torus32* d_out, EvalStats* stats) {
-    d_->cmux.check_owner(set);
-    if (depth < 0 || depth > kCmuxMaxDepth) throw std::invalid_argument("lut_scatter: depth must lie in 0 .. 12");
-    const size_t row = (size_t)2 * (size_t)p_.N, leaves = (size_t)1 << depth;
-    if (overlaps(d_out, count * leaves * row, {{d_values, count * row}, {d_sel_of, count * (size_t)depth}}) ||
-        (d_mem != d_out && overlaps(d_out, count * leaves * row, {{d_mem, count * leaves * row}})))
-        throw std::invalid_argument("lut_scatter: the output overlaps an input (only d_out == d_mem, the write in place, is accepted)");
-    begin_call();
-    if (count == 0) return;
-    if (!d_values || !d_out) throw std::invalid_argument("lut_scatter: null rows");
+    const size_t row = (size_t)2 * (size_t)p_.N;
+    if (!begin_set_call(set, SetCall{kCallLutScatter, count, depth}, {d_sel_of, d_values, d_mem, d_out}, row)) return;
     Lane& ln = d_->lane[0];
     const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
     d_->cmux.reserve(ln.cmux, pl);
     run_cmux_pieces(pl, count, depth, stats, [&](int64_t i0, int64_t cnt) {
         return d_->cmux.launch_scatter(set, ln.cmux, stream_, i0, cnt, depth, d_sel_of, d_values + (size_t)i0 * row,
-                                       d_mem ? d_mem + (size_t)i0 * leaves * row : nullptr, d_out + (size_t)i0 * leaves * row);
+                                       d_mem ? d_mem + ((size_t)i0 << depth) * row : nullptr, d_out + ((size_t)i0 << depth) * row);
     });
 }
 
@@ -1084,21 +1094,14 @@ void Evaluator::lut_scatter_device(const TgswSet& set, size_t count, int32_t dep
 // scatter (Cmux::launch_write).  A piece touches its own items' rows only, so the pieces are independent and d_out == d_mem is sound.
 void Evaluator::lut_write_device(const TgswSet& set, size_t count, int32_t depth, const int32_t* d_sel_of, const Torus32* d_new, const Torus32* d_mem,
                                  Torus32* d_out, EvalStats* stats) {
-    d_->cmux.check_owner(set);
-    if (depth < 0 || depth > kCmuxMaxDepth) throw std::invalid_argument("lut_write: depth must lie in 0 .. 12");
-    const size_t row = (size_t)2 * (size_t)p_.N, leaves = (size_t)1 << depth;
-    if (overlaps(d_out, count * leaves * row, {{d_new, count * row}, {d_sel_of, count * (size_t)depth}}) ||
-        (d_mem != d_out && overlaps(d_out, count * leaves * row, {{d_mem, count * leaves * row}})))
-        throw std::invalid_argument("lut_write: the output overlaps an input (only d_out == d_mem, the write in place, is accepted)");
-    begin_call();
-    if (count == 0) return;
-    if (!d_new || !d_mem || !d_out) throw std::invalid_argument("lut_write: null rows");
+    const size_t row = (size_t)2 * (size_t)p_.N;
+    if (!begin_set_call(set, SetCall{kCallLutWrite, count, depth}, {d_sel_of, d_new, d_mem, d_out}, row)) return;
     Lane& ln = d_->lane[0];
     const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
     d_->cmux.reserve_read(ln.cmux, pl, depth);
     run_cmux_pieces(pl, count, 2 * depth, stats, [&](int64_t i0, int64_t cnt) {
-        return d_->cmux.launch_write(set, ln.cmux, stream_, i0, cnt, depth, d_sel_of, d_new + (size_t)i0 * row, d_mem + (size_t)i0 * leaves * row,
-                                     d_out + (size_t)i0 * leaves * row);
+        return d_->cmux.launch_write(set, ln.cmux, stream_, i0, cnt, depth, d_sel_of, d_new + (size_t)i0 * row, d_mem + ((size_t)i0 << depth) * row,
+                                     d_out + ((size_t)i0 << depth) * row);
     });
 }
 
@@ -1107,23 +1110,16 @@ void Evaluator::lut_write_device(const TgswSet& set, size_t count, int32_t depth
 // matter: the adds are order-free mod 2^32 and all on one stream behind the initialising copy.
 void Evaluator::lut_add_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of,
                                const Torus32* d_values, const Torus32* d_mems, int32_t n_mems, const int32_t* d_mem_of, Torus32* d_out, EvalStats* stats) {
-    d_->cmux.check_owner(set);
-    if (depth < 0 || depth > kCmuxMaxDepth) throw std::invalid_argument("lut_add: depth must lie in 0 .. 12");
-    if (steps < 0 || steps > kRotateMaxSteps) throw std::invalid_argument("lut_add: steps must lie in 0 .. 64");
-    if (n_mems < 1) throw std::invalid_argument("lut_add: n_mems must be at least 1");
-    const size_t row = (size_t)2 * (size_t)p_.N, words = ((size_t)n_mems << depth) * row;
-    if (overlaps(d_out, words, {{d_values, count * row}, {d_sel_of, count * (size_t)(depth + steps)}, {d_amount_of, (size_t)steps}, {d_mem_of, count}}) ||
-        (d_mems != d_out && overlaps(d_out, words, {{d_mems, words}})))
-        throw std::invalid_argument("lut_add: the output overlaps an input (only d_out == d_mems, the write in place, is accepted)");
-    begin_call();
-    if (!d_out) throw std::invalid_argument("lut_add: null rows");
-    if (count > 0 && !d_values) throw std::invalid_argument("lut_add: null rows");
+    const size_t row = (size_t)2 * (size_t)p_.N;
+    const SetCall c{kCallLutAdd, count, depth, steps, n_mems};
+    const bool items = begin_set_call(set, c, {d_sel_of, d_amount_of, d_values, d_mems, d_mem_of, d_out}, row);
     // not a launch of the call's: the copy or fill the sums start from
+    const size_t words = set_arg_words(c, set_call_output(c), p_.N, row);
     if (d_mems && d_mems != d_out)
         HIP_CHECK(hipMemcpyAsync(d_out, d_mems, words * 4, hipMemcpyDeviceToDevice, stream_));
     else if (!d_mems)
         HIP_CHECK(hipMemsetAsync(d_out, 0, words * 4, stream_));
-    if (count == 0) {
+    if (!items) {
         HIP_CHECK(hipStreamSynchronize(stream_));
         return;
     }
@@ -1139,15 +1135,8 @@ void Evaluator::lut_add_device(const TgswSet& set, size_t count, int32_t depth, 
 // The rotation by caller selectors: the flat CMux's pieces, one launch each whatever the number of steps; no scratch.
 void Evaluator::tlwe_rotate_device(const TgswSet& set, size_t count, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of,
                                    const Torus32* d_in, Torus32* d_out, EvalStats* stats) {
-    d_->cmux.check_owner(set);
-    if (steps < 0 || steps > kRotateMaxSteps) throw std::invalid_argument("tlwe_rotate: steps must lie in 0 .. 64");
     const size_t row = (size_t)2 * (size_t)p_.N;
-    if (overlaps(d_out, count * row, {{d_sel_of, count * (size_t)steps}, {d_amount_of, (size_t)steps}}) ||
-        (d_in != d_out && overlaps(d_out, count * row, {{d_in, count * row}})))
-        throw std::invalid_argument("tlwe_rotate: the output overlaps an input (only d_out == d_in, the rotation in place, is accepted)");
-    begin_call();
-    if (count == 0) return;
-    if (!d_in || !d_out) throw std::invalid_argument("tlwe_rotate: null rows");
+    if (!begin_set_call(set, SetCall{kCallTlweRotate, count, 0, steps}, {d_sel_of, d_amount_of, d_in, d_out}, row)) return;
     run_cmux_pieces(cmux_plan((int64_t)count, -1, d_->opt.cmux_piece_rows), count, steps, stats, [&](int64_t r0, int64_t rows) {
         RotateRows R;
         R.rows = rows;
@@ -1168,19 +1157,10 @@ void Evaluator::tlwe_rotate_device(const TgswSet& set, size_t count, int32_t ste
 void Evaluator::lut_read_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of,
                                 const Torus32* d_tables, int32_t n_tables, const int32_t* d_table_of, int32_t coef, int32_t flags, Torus32* d_out,
                                 EvalStats* stats) {
-    d_->cmux.check_owner(set);
-    if (depth < 0 || depth > kCmuxMaxDepth) throw std::invalid_argument("lut_read: depth must lie in 0 .. 12");
-    if (steps < 0 || steps > kRotateMaxSteps) throw std::invalid_argument("lut_read: steps must lie in 0 .. 64");
-    if (n_tables < 1) throw std::invalid_argument("lut_read: n_tables must be at least 1");
-    if (flags & ~kLutReadNoKeyswitch) throw std::invalid_argument("lut_read: unknown flag");
     const bool woks = (flags & kLutReadNoKeyswitch) != 0;
-    const size_t row = (size_t)2 * (size_t)p_.N, out_stride = (size_t)(woks ? extract_stride() : d_->K.stride);
-    if (overlaps(d_out, count * out_stride,
-                 {{d_tables, ((size_t)n_tables << depth) * row}, {d_sel_of, count * (size_t)(depth + steps)}, {d_amount_of, (size_t)steps}, {d_table_of, count}}))
-        throw std::invalid_argument("lut_read: the output overlaps an input");
-    begin_call();
-    if (count == 0) return;
-    if (!d_tables || !d_out) throw std::invalid_argument("lut_read: null rows");
+    const size_t out_stride = (size_t)(woks ? extract_stride() : d_->K.stride);
+    const SetCall c{kCallLutRead, count, depth, steps, n_tables, flags, coef};
+    if (!begin_set_call(set, c, {d_sel_of, d_amount_of, d_tables, d_table_of, d_out}, out_stride)) return;
     Lane& ln = d_->lane[0];
     const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
     d_->cmux.reserve_read(ln.cmux, pl, depth);

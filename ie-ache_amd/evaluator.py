@@ -311,6 +311,21 @@ def _i32(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def _opt_i32(a, *shape):
+    """an optional int32 array of this shape: None stays None"""
+    return None if a is None else np.ascontiguousarray(a, dtype=np.int32).reshape(*shape)
+
+
+def _opt(a):
+    """the optional host array of an entry point as its pointer: None is null"""
+    return None if a is None else _i32(a)
+
+
+def _dev(d):
+    """the optional device pointer (int) of an entry point: None / 0 is null"""
+    return C.c_void_p(d or None)
+
+
 def _f64(a):
     assert a.dtype == np.float64 and a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(C.POINTER(C.c_double))
@@ -808,18 +823,16 @@ class Context:
         [count][2][N]; d0 None: zeros, the external product alone (include/ieache.h section 3f)."""
         d1 = np.ascontiguousarray(d1, dtype=np.int32).reshape(-1, 2, self.params.N)
         count = d1.shape[0]
-        d0 = None if d0 is None else np.ascontiguousarray(d0, dtype=np.int32).reshape(-1, 2, self.params.N)
-        of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1)
+        d0 = _opt_i32(d0, -1, 2, self.params.N)
+        of = _opt_i32(sel_of, -1)
         assert (d0 is None or d0.shape[0] == count) and (of is None or of.shape[0] == count)
         out = np.zeros((count, 2, self.params.N), dtype=np.int32)
-        check(lib().ieache_cmux(self.h, tgsw.h, count, None if of is None else _i32(of), _i32(d1), None if d0 is None else _i32(d0), _i32(out),
-                                _stats_ref(stats)))
+        check(lib().ieache_cmux(self.h, tgsw.h, count, _opt(of), _i32(d1), _opt(d0), _i32(out), _stats_ref(stats)))
         return out
 
     def cmux_device(self, tgsw, count, d_sel_of, d_d1, d_d0, d_out, stats=None):
         """Device pointers (ints; d_sel_of and d_d0 may be None / 0): rows [count][2][N] packed, indices [count] int32."""
-        check(lib().ieache_cmux_device(self.h, tgsw.h, count, C.c_void_p(d_sel_of or None), C.c_void_p(d_d1), C.c_void_p(d_d0 or None),
-                                       C.c_void_p(d_out), _stats_ref(stats)))
+        check(lib().ieache_cmux_device(self.h, tgsw.h, count, _dev(d_sel_of), C.c_void_p(d_d1), _dev(d_d0), C.c_void_p(d_out), _stats_ref(stats)))
 
     def lut_tree(self, tgsw, tables, depth, sel_of=None, table_of=None, count=None, stats=None):
         """CMux-tree lookup on host rows: item i folds tables[table_of[i]] (tables [n_tables][2^depth][2][N] or one table;
@@ -828,20 +841,19 @@ class Context:
         items where neither index array gives it (default 1)."""
         depth = int(depth)
         tables = np.ascontiguousarray(tables, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, self.params.N)
-        of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(depth, 1))
-        tof = None if table_of is None else np.ascontiguousarray(table_of, dtype=np.int32).reshape(-1)
+        of = _opt_i32(sel_of, -1, max(depth, 1))
+        tof = _opt_i32(table_of, -1)
         if count is None:
             count = tof.shape[0] if tof is not None else (of.shape[0] if of is not None and depth > 0 else 1)
         assert (tof is None or tof.shape[0] == count) and (of is None or depth < 1 or of.shape[0] == count)
         out = np.zeros((count, 2, self.params.N), dtype=np.int32)
-        check(lib().ieache_lut_tree(self.h, tgsw.h, count, depth, None if of is None else _i32(of), _i32(tables), tables.shape[0],
-                                    None if tof is None else _i32(tof), _i32(out), _stats_ref(stats)))
+        check(lib().ieache_lut_tree(self.h, tgsw.h, count, depth, _opt(of), _i32(tables), tables.shape[0], _opt(tof), _i32(out), _stats_ref(stats)))
         return out
 
     def lut_tree_device(self, tgsw, count, depth, d_sel_of, d_tables, n_tables, d_table_of, d_out, stats=None):
         """Device pointers (ints; the index arrays may be None / 0): tables [n_tables][2^depth][2][N] packed, out [count][2][N]."""
-        check(lib().ieache_lut_tree_device(self.h, tgsw.h, count, int(depth), C.c_void_p(d_sel_of or None), C.c_void_p(d_tables), int(n_tables),
-                                           C.c_void_p(d_table_of or None), C.c_void_p(d_out), _stats_ref(stats)))
+        check(lib().ieache_lut_tree_device(self.h, tgsw.h, count, int(depth), _dev(d_sel_of), C.c_void_p(d_tables), int(n_tables),
+                                           _dev(d_table_of), C.c_void_p(d_out), _stats_ref(stats)))
 
     def lut_scatter(self, tgsw, values, depth, sel_of=None, mem=None, count=None, stats=None):
         """The write at an encrypted index on host rows (include/ieache.h section 3g), lut_tree's partner: item i
@@ -852,19 +864,18 @@ class Context:
         depth = int(depth)
         values = np.ascontiguousarray(values, dtype=np.int32).reshape(-1, 2, self.params.N)
         n = values.shape[0] if count is None else int(count)
-        of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(depth, 1))
-        mem = None if mem is None else np.ascontiguousarray(mem, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, self.params.N)
+        of = _opt_i32(sel_of, -1, max(depth, 1))
+        mem = _opt_i32(mem, -1, 1 << max(depth, 0), 2, self.params.N)
         assert values.shape[0] == n and (of is None or depth < 1 or of.shape[0] == n) and (mem is None or mem.shape[0] == n)
         out = np.zeros((n, 1 << max(depth, 0), 2, self.params.N), dtype=np.int32)
-        check(lib().ieache_lut_scatter(self.h, tgsw.h, n, depth, None if of is None else _i32(of), _i32(values), None if mem is None else _i32(mem),
-                                       _i32(out), _stats_ref(stats)))
+        check(lib().ieache_lut_scatter(self.h, tgsw.h, n, depth, _opt(of), _i32(values), _opt(mem), _i32(out), _stats_ref(stats)))
         return out
 
     def lut_scatter_device(self, tgsw, count, depth, d_sel_of, d_values, d_mem, d_out, stats=None):
         """Device pointers (ints; d_sel_of and d_mem may be None / 0): values [count][2][N], mem and out [count][2^depth][2][N]
         packed; d_out == d_mem writes in place."""
-        check(lib().ieache_lut_scatter_device(self.h, tgsw.h, count, int(depth), C.c_void_p(d_sel_of or None), C.c_void_p(d_values),
-                                              C.c_void_p(d_mem or None), C.c_void_p(d_out), _stats_ref(stats)))
+        check(lib().ieache_lut_scatter_device(self.h, tgsw.h, count, int(depth), _dev(d_sel_of), C.c_void_p(d_values),
+                                              _dev(d_mem), C.c_void_p(d_out), _stats_ref(stats)))
 
     def lut_write(self, tgsw, mem, depth, new, sel_of=None):
         """The replace write mem[i][addr_i] := new[i] on host arrays, addr_i the index item i's selectors encrypt: a read
@@ -884,7 +895,7 @@ class Context:
         """The replace write on the device (include/ieache.h section 3i), word for word lut_write's composition with no host round
         trip.  Device pointers (ints; d_sel_of may be None / 0): new [count][2][N], mem and out [count][2^depth][2][N] packed;
         d_out == d_mem writes in place."""
-        check(lib().ieache_lut_write_device(self.h, tgsw.h, count, int(depth), C.c_void_p(d_sel_of or None), C.c_void_p(d_new), C.c_void_p(d_mem),
+        check(lib().ieache_lut_write_device(self.h, tgsw.h, count, int(depth), _dev(d_sel_of), C.c_void_p(d_new), C.c_void_p(d_mem),
                                             C.c_void_p(d_out), _stats_ref(stats)))
 
     def tlwe_rotate(self, tgsw, rows, steps, sel_of=None, amounts=None, stats=None):
@@ -895,18 +906,17 @@ class Context:
         steps = int(steps)
         rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 2, self.params.N)
         count = rows.shape[0]
-        of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(steps, 1))
-        am = None if amounts is None else np.ascontiguousarray(amounts, dtype=np.int32).reshape(-1)
+        of = _opt_i32(sel_of, -1, max(steps, 1))
+        am = _opt_i32(amounts, -1)
         assert (of is None or steps < 1 or of.shape[0] == count) and (am is None or am.shape[0] == max(steps, 0))
         out = np.zeros((count, 2, self.params.N), dtype=np.int32)
-        check(lib().ieache_tlwe_rotate(self.h, tgsw.h, count, steps, None if of is None else _i32(of), None if am is None else _i32(am), _i32(rows),
-                                       _i32(out), _stats_ref(stats)))
+        check(lib().ieache_tlwe_rotate(self.h, tgsw.h, count, steps, _opt(of), _opt(am), _i32(rows), _i32(out), _stats_ref(stats)))
         return out
 
     def tlwe_rotate_device(self, tgsw, count, steps, d_sel_of, d_amounts, d_in, d_out, stats=None):
         """Device pointers (ints; d_sel_of and d_amounts may be None / 0): rows [count][2][N] packed, selectors [count][steps] and
         amounts [steps] int32; d_out == d_in rotates in place."""
-        check(lib().ieache_tlwe_rotate_device(self.h, tgsw.h, count, int(steps), C.c_void_p(d_sel_of or None), C.c_void_p(d_amounts or None),
+        check(lib().ieache_tlwe_rotate_device(self.h, tgsw.h, count, int(steps), _dev(d_sel_of), _dev(d_amounts),
                                               C.c_void_p(d_in), C.c_void_p(d_out), _stats_ref(stats)))
 
     def lut_read(self, tgsw, tables, depth, steps, sel_of=None, amounts=None, table_of=None, coef=0, keyswitch=True, count=None, stats=None):
@@ -917,24 +927,23 @@ class Context:
         the extracted rows [count][N+1])."""
         depth, steps = int(depth), int(steps)
         tables = np.ascontiguousarray(tables, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, self.params.N)
-        of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(depth + steps, 1))
-        am = None if amounts is None else np.ascontiguousarray(amounts, dtype=np.int32).reshape(-1)
-        tof = None if table_of is None else np.ascontiguousarray(table_of, dtype=np.int32).reshape(-1)
+        of = _opt_i32(sel_of, -1, max(depth + steps, 1))
+        am = _opt_i32(amounts, -1)
+        tof = _opt_i32(table_of, -1)
         if count is None:
             count = tof.shape[0] if tof is not None else (of.shape[0] if of is not None and depth + steps > 0 else 1)
         assert (tof is None or tof.shape[0] == count) and (of is None or depth + steps < 1 or of.shape[0] == count)
         assert am is None or am.shape[0] == max(steps, 0)
         out = np.zeros((count, (self.params.n if keyswitch else self.params.N) + 1), dtype=np.int32)
-        check(lib().ieache_lut_read(self.h, tgsw.h, count, depth, steps, None if of is None else _i32(of), None if am is None else _i32(am),
-                                    _i32(tables), tables.shape[0], None if tof is None else _i32(tof), int(coef),
+        check(lib().ieache_lut_read(self.h, tgsw.h, count, depth, steps, _opt(of), _opt(am), _i32(tables), tables.shape[0], _opt(tof), int(coef),
                                     0 if keyswitch else LUT_READ_NO_KEYSWITCH, _i32(out), _stats_ref(stats)))
         return out
 
     def lut_read_device(self, tgsw, count, depth, steps, d_sel_of, d_amounts, d_tables, n_tables, d_table_of, d_out, coef=0, keyswitch=True, stats=None):
         """Device pointers (ints; the index arrays and d_amounts may be None / 0): tables [n_tables][2^depth][2][N] packed, out rows
         of lwe_stride words (keyswitch=False: of extract_stride words)."""
-        check(lib().ieache_lut_read_device(self.h, tgsw.h, count, int(depth), int(steps), C.c_void_p(d_sel_of or None), C.c_void_p(d_amounts or None),
-                                           C.c_void_p(d_tables), int(n_tables), C.c_void_p(d_table_of or None), int(coef),
+        check(lib().ieache_lut_read_device(self.h, tgsw.h, count, int(depth), int(steps), _dev(d_sel_of), _dev(d_amounts),
+                                           C.c_void_p(d_tables), int(n_tables), _dev(d_table_of), int(coef),
                                            0 if keyswitch else LUT_READ_NO_KEYSWITCH, C.c_void_p(d_out), _stats_ref(stats)))
 
     def lut_add(self, tgsw, values, depth, steps=0, sel_of=None, amounts=None, mems=None, n_mems=1, mem_of=None, stats=None):
@@ -947,9 +956,9 @@ class Context:
         depth, steps = int(depth), int(steps)
         values = np.ascontiguousarray(values, dtype=np.int32).reshape(-1, 2, self.params.N)
         count = values.shape[0]
-        of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(depth + steps, 1))
-        am = None if amounts is None else np.ascontiguousarray(amounts, dtype=np.int32).reshape(-1)
-        mof = None if mem_of is None else np.ascontiguousarray(mem_of, dtype=np.int32).reshape(-1)
+        of = _opt_i32(sel_of, -1, max(depth + steps, 1))
+        am = _opt_i32(amounts, -1)
+        mof = _opt_i32(mem_of, -1)
         if mems is not None:
             mems = np.ascontiguousarray(mems, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, self.params.N)
             n_mems = mems.shape[0]
@@ -957,17 +966,15 @@ class Context:
         assert (of is None or depth + steps < 1 or of.shape[0] == count) and (am is None or am.shape[0] == max(steps, 0))
         assert mof is None or mof.shape[0] == count
         out = np.zeros((max(n_mems, 0), 1 << max(depth, 0), 2, self.params.N), dtype=np.int32)
-        check(lib().ieache_lut_add(self.h, tgsw.h, count, depth, steps, None if of is None else _i32(of), None if am is None else _i32(am),
-                                   _i32(values), None if mems is None else _i32(mems), n_mems, None if mof is None else _i32(mof), _i32(out),
+        check(lib().ieache_lut_add(self.h, tgsw.h, count, depth, steps, _opt(of), _opt(am), _i32(values), _opt(mems), n_mems, _opt(mof), _i32(out),
                                    _stats_ref(stats)))
         return out
 
     def lut_add_device(self, tgsw, count, depth, steps, d_sel_of, d_amounts, d_values, d_mems, n_mems, d_mem_of, d_out, stats=None):
         """Device pointers (ints; the index arrays, d_amounts and d_mems may be None / 0): values [count][2][N], mems and out
         [n_mems][2^depth][2][N] packed; d_out == d_mems adds in place."""
-        check(lib().ieache_lut_add_device(self.h, tgsw.h, count, int(depth), int(steps), C.c_void_p(d_sel_of or None), C.c_void_p(d_amounts or None),
-                                          C.c_void_p(d_values), C.c_void_p(d_mems or None), int(n_mems), C.c_void_p(d_mem_of or None),
-                                          C.c_void_p(d_out), _stats_ref(stats)))
+        check(lib().ieache_lut_add_device(self.h, tgsw.h, count, int(depth), int(steps), _dev(d_sel_of), _dev(d_amounts), C.c_void_p(d_values),
+                                          _dev(d_mems), int(n_mems), _dev(d_mem_of), C.c_void_p(d_out), _stats_ref(stats)))
 
     def cmux_plan(self, count, depth=-1):
         """How cmux() (depth < 0) or lut_tree() / lut_scatter() would cut such a call under the options as they are (csrc/cmux_plan.h):
@@ -979,15 +986,15 @@ class Context:
     def tlwe_extract(self, tlwe, coef_of=None, stats=None):
         """Coefficient coef_of[i] (None: 0) of TLWE samples [count][2][N] as extracted rows [count][N+1]: what keyswitch() takes."""
         tlwe = np.ascontiguousarray(tlwe, dtype=np.int32).reshape(-1, 2, self.params.N)
-        of = None if coef_of is None else np.ascontiguousarray(coef_of, dtype=np.int32).reshape(-1)
+        of = _opt_i32(coef_of, -1)
         assert of is None or of.shape[0] == tlwe.shape[0]
         u = np.zeros((tlwe.shape[0], self.params.N + 1), dtype=np.int32)
-        check(lib().ieache_tlwe_extract(self.h, tlwe.shape[0], _i32(tlwe), None if of is None else _i32(of), _i32(u), _stats_ref(stats)))
+        check(lib().ieache_tlwe_extract(self.h, tlwe.shape[0], _i32(tlwe), _opt(of), _i32(u), _stats_ref(stats)))
         return u
 
     def tlwe_extract_device(self, count, d_tlwe, d_coef_of, d_u, stats=None):
         """Device pointers (ints; d_coef_of may be None / 0): samples [count][2][N] packed, d_u rows of extract_stride."""
-        check(lib().ieache_tlwe_extract_device(self.h, count, C.c_void_p(d_tlwe), C.c_void_p(d_coef_of or None), C.c_void_p(d_u), _stats_ref(stats)))
+        check(lib().ieache_tlwe_extract_device(self.h, count, C.c_void_p(d_tlwe), _dev(d_coef_of), C.c_void_p(d_u), _stats_ref(stats)))
 
     def set_packing_key(self, pk, t=8, basebit=2):
         """The packing key [n][t][2][N] (tools.packing_keygen) for pack(): replaces an earlier one; pk=None drops it."""
