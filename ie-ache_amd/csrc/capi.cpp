@@ -1217,6 +1217,108 @@ int ieache_lut_add(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_
                          });
 }
 
+// ---- automata over words of TGSW-encrypted bits (section 3k).  The call stands beside the table of set_calls.h
+// (automaton_plan.h says why); the device and host forms below follow set_call_device's and set_call_host's steps. ----
+struct ieache_automaton {
+    std::unique_ptr<Automaton> a;
+};
+
+namespace {
+// what both forms refuse before anything is staged or launched: 0, or the code after fail()
+int check_automaton_call(const ieache_ctx* ctx, const ieache_tgsw* set, const ieache_automaton* a, size_t count, const int32_t* finals, const int32_t* out,
+                         int32_t n_finals) {
+    if (const int rc = check_tgsw(ctx, set)) return rc;
+    if (!a || !a->a) return fail(IEACHE_EINVAL, "null argument");
+    if (a->a->owner != ctx->eval->cmux_id()) return fail(IEACHE_EINVAL, "the automaton was compiled on another context");
+    if (count && (!finals || !out)) return fail(IEACHE_EINVAL, "null argument");
+    if (n_finals < 1) return fail(IEACHE_EINVAL, "automaton_run: n_finals must be at least 1");
+    return 0;
+}
+}  // namespace
+
+ieache_automaton* ieache_automaton_create(ieache_ctx* ctx, int32_t states, int32_t steps, int32_t n_out, const int32_t* next0, const int32_t* next1) {
+    ieache_automaton* out = nullptr;
+    guarded([&] {
+        if (!ctx) return fail(IEACHE_EINVAL, "null argument");
+        const std::string refusal = automaton_refusal(states, steps, n_out, next0, next1);
+        if (!refusal.empty()) return fail(IEACHE_EINVAL, refusal);
+        std::unique_ptr<ieache_automaton> h(new ieache_automaton);
+        h->a.reset(ctx->eval->automaton_create(states, steps, n_out, next0, next1));
+        out = h.release();
+        return 0;
+    });
+    return out;
+}
+
+void ieache_automaton_free(ieache_automaton* a) {
+    if (!a) return;
+    try {
+        if (a->a) (void)hipSetDevice(a->a->device);  // the automaton owns its memory: the context may be gone already
+        delete a;
+    } catch (...) {
+    }
+}
+
+int ieache_automaton_info(const ieache_automaton* a, int32_t* states, int32_t* steps, int32_t* n_out, int64_t* cmuxes) {
+    return guarded([&] {
+        if (!a || !a->a) return fail(IEACHE_EINVAL, "null argument");
+        if (states) *states = a->a->states;
+        if (steps) *steps = a->a->steps;
+        if (n_out) *n_out = a->a->n_out;
+        if (cmuxes) *cmuxes = a->a->cmuxes;
+        return 0;
+    });
+}
+
+int ieache_automaton_check(int32_t states, int32_t steps, int32_t n_out, const int32_t* next0, const int32_t* next1) {
+    return guarded([&] {
+        const std::string refusal = automaton_refusal(states, steps, n_out, next0, next1);
+        return refusal.empty() ? 0 : fail(IEACHE_EINVAL, refusal);
+    });
+}
+
+int ieache_debug_automaton_plan(const ieache_ctx* ctx, const ieache_automaton* a, size_t count, int64_t out[5]) {
+    return guarded([&] {
+        if (!ctx || !a || !a->a || !out) return fail(IEACHE_EINVAL, "null argument");
+        ctx->eval->automaton_plan_figures(*a->a, count, out);
+        return 0;
+    });
+}
+
+int ieache_automaton_run_device(ieache_ctx* ctx, const ieache_tgsw* set, const ieache_automaton* a, size_t count, const int32_t* d_sel_of,
+                                const int32_t* d_finals, int32_t n_finals, const int32_t* d_final_of, int32_t* d_out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_automaton_call(ctx, set, a, count, d_finals, d_out, n_finals)) return rc;
+        if (count) {
+            require_device_pointer(d_finals, "d_finals");
+            require_device_pointer(d_out, "d_out");
+            if (d_sel_of && a->a->steps > 0) require_device_pointer(d_sel_of, "d_sel_of");
+            if (d_final_of) require_device_pointer(d_final_of, "d_final_of");
+        }
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->automaton_run_device(*set->set, *a->a, count, d_sel_of, d_finals, n_finals, d_final_of, d_out, st); });
+    });
+}
+
+int ieache_automaton_run(ieache_ctx* ctx, const ieache_tgsw* set, const ieache_automaton* a, size_t count, const int32_t* sel_of, const int32_t* finals,
+                         int32_t n_finals, const int32_t* final_of, int32_t* out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_automaton_call(ctx, set, a, count, finals, out, n_finals)) return rc;
+        const Automaton& au = *a->a;
+        if (const int rc = check_indices(sel_of, count * (size_t)au.steps, (int64_t)set->set->n, "automaton_run", "sel_of")) return rc;
+        if (const int rc = check_indices(final_of, count, n_finals, "automaton_run", "final_of")) return rc;
+        if (count == 0) return with_stats(stats, [&](EvalStats*) {});
+        HostCall h(ctx, count);
+        const size_t sample = (size_t)2 * (size_t)h.p.N;
+        StagedRows dout(h.ev, kStageOut, count * (size_t)au.n_out, sample);
+        StagedRows dfinals(h.ev, kStageTestPolys, (size_t)n_finals * (size_t)au.states, sample, finals, sample);
+        StagedRows dsel = h.words(kStagePolyOf, au.steps > 0 ? sel_of : nullptr, count * (size_t)au.steps);
+        StagedRows dof = h.words(kStageBias, final_of, count);
+        with_stats(stats, [&](EvalStats* st) { h.ev.automaton_run_device(*set->set, au, count, dsel.p, dfinals.p, n_finals, dof.p, dout.p, st); });
+        dout.download(out, sample);
+        return 0;
+    });
+}
+
 int ieache_tlwe_extract_device(ieache_ctx* ctx, size_t count, const int32_t* d_tlwe, const int32_t* d_coef_of, int32_t* d_u, ieache_stats* stats) {
     return guarded([&] {
         if (!ctx || !d_tlwe || !d_u) return fail(IEACHE_EINVAL, "null argument");
@@ -1757,6 +1859,24 @@ int ieache_lut_add_reference(const ieache_params* p, const int32_t* set, size_t 
         if (n < 1) return fail(IEACHE_EINVAL, "lut_add_reference: no samples");
         if (const int rc = check_set_indices({kCallLutAdd, count, depth, steps, n_mems}, {sel_of, amount_of, values, mems, mem_of, out}, pp.N, n)) return rc;
         lut_add_reference(pp, set, n, count, depth, steps, sel_of, amount_of, values, mems, (size_t)n_mems, mem_of, out);
+        return 0;
+    });
+}
+
+int ieache_automaton_reference(const ieache_params* p, const int32_t* set, size_t n, int32_t states, int32_t steps, int32_t n_out, const int32_t* next0,
+                               const int32_t* next1, size_t count, const int32_t* sel_of, const int32_t* finals, int32_t n_finals, const int32_t* final_of,
+                               int32_t* out) {
+    return guarded([&] {
+        if (!p || !set || (count && (!finals || !out))) return fail(IEACHE_EINVAL, "null argument");
+        const Params pp = to_params(*p);
+        if (!pp.supported()) return fail(IEACHE_EINVAL, "automaton_reference: unsupported TFHE parameter set");
+        if (n < 1) return fail(IEACHE_EINVAL, "automaton_reference: no samples");
+        const std::string refusal = automaton_refusal(states, steps, n_out, next0, next1);
+        if (!refusal.empty()) return fail(IEACHE_EINVAL, refusal);
+        if (n_finals < 1) return fail(IEACHE_EINVAL, "automaton_run: n_finals must be at least 1");
+        if (const int rc = check_indices(sel_of, count * (size_t)steps, (int64_t)n, "automaton_run", "sel_of")) return rc;
+        if (const int rc = check_indices(final_of, count, n_finals, "automaton_run", "final_of")) return rc;
+        automaton_reference(pp, set, n, states, steps, n_out, next0, next1, count, sel_of, finals, final_of, out);
         return 0;
     });
 }

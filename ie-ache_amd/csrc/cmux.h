@@ -3,13 +3,15 @@
 //   section 3g  the scatter that writes at an encrypted index;
 //   section 3h  the rotation by caller selectors and the coefficient-level lookup;
 //   section 3i  sets with a gadget of their own, and the replace write;
-//   section 3j  many values added into shared memories in one call.
+//   section 3j  many values added into shared memories in one call;
+//   section 3k  deterministic automata over words of encrypted bits, every step of an item in one launch.
 // The kernels, the spectrum form of a prepared set, the twiddle table and the scratch of a tree are behind this object; how
-// a call is cut is cmux_plan.h; what a call is -- scalars, refusals, arguments -- is set_calls.h.  Kernels: cmux.hip (3f, 3g)
-// and rotate.hip (3h); what the two share is cmux_step.h.
+// a call is cut is cmux_plan.h; what a call is -- scalars, refusals, arguments -- is set_calls.h.  Kernels: cmux.hip (3f, 3g),
+// rotate.hip (3h) and automaton.hip (3k, cut by automaton_plan.h); what they share is cmux_step.h.
 #pragma once
 #include <cstdint>
 
+#include "automaton_plan.h"
 #include "cmux_plan.h"
 #include "device_buffer.h"
 #include "params.h"
@@ -106,6 +108,42 @@ struct RotateRows {
     int32_t steps = 0, sel_stride = 0;  // steps in 0 .. kRotateMaxSteps
 };
 
+// A compiled automaton (include/ieache.h section 3k; automaton_plan.h states what one is): the public transition tables
+// next [2][steps][states] (next0 first) and the live masks [steps] on the device.  Like a TgswSet it owns its device memory and
+// nothing of the context's, may be freed before or after the context, and only the context named by `owner` accepts it.
+struct Automaton {
+    dev::DeviceBuffer<int32_t> next;
+    dev::DeviceBuffer<uint64_t> live;
+    int32_t states = 0, steps = 0, n_out = 0;
+    int64_t cmuxes = 0;  // live CMuxes per item (automaton_live)
+    uint64_t owner = 0;
+    int device = 0;
+};
+
+// Where the rows of one launch of k_automaton_x1 live: workgroup b owns item b of the piece and runs steps t = hi-1 .. lo of it
+// -- a rule again, no pointer tables, everything wave-uniform.
+//   V_t, 0 < t < steps: scratch + (b 2 states + (t & 1) states) rows; V_steps: finals + fo states rows, fo = final_of[item0 + b]
+//   clamped into [0, n_finals) (null: 0); V_0: out + b n_out rows, states 0 .. n_out-1 only.
+//   State q of step t (bit q of live[t] set): d0 = V_{t+1}[next0[t][q]], d1 = V_{t+1}[next1[t][q]] -> V_t[q]; the two equal: a copy.
+//   Selector of step t: sel_of[(item0 + b) steps + t] (null: that index mod n_set; explicit: clamped into the set).
+// out and scratch are the PIECE's (already offset); sel_of and final_of are the call's.  `rows` counts WAVES, items x
+// kCmuxWaveRows, so that the family's launcher makes one workgroup per item.
+struct AutomatonRows {
+    const int32_t* finals = nullptr;
+    int32_t* out = nullptr;
+    int32_t* scratch = nullptr;
+    const int32_t* sel_of = nullptr;
+    const int32_t* final_of = nullptr;
+    const int32_t* next0 = nullptr;
+    const int32_t* next1 = nullptr;
+    const uint64_t* live = nullptr;
+    int64_t rows = 0;
+    int64_t item0 = 0;
+    int32_t n_set = 1, n_finals = 1;
+    int32_t states = 1, steps = 0, n_out = 1;
+    int32_t hi = 0, lo = 0;
+};
+
 // Scratch of a tree on one stream: the two buffers whose roles swap from level to level.  A coefficient-level lookup
 // (lut_read) adds the rows its trees select, which the rotation turns in place, and the indices its launches read: the tree's
 // selectors [items][depth] taken out of the call's [count][depth + steps], then the public coefficient once per item.
@@ -187,6 +225,17 @@ struct Cmux {
     // the call's.  scratch as reserve_read's.  Returns (steps > 0) + max(depth, 1).
     int launch_add(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, int32_t steps,
                    const int32_t* sel_of, const int32_t* amount_of, const int32_t* values, int32_t n_mems, const int32_t* mem_of, int32_t* out);
+    // ---- automata (section 3k; automaton.hip) ----
+    // the tables [steps][states] from host memory -> a new automaton (the caller owns it).  std::invalid_argument with
+    // automaton_refusal()'s message, or where the context's ring is not N = 1024, k = 1.
+    Automaton* automaton_create(int32_t states, int32_t steps, int32_t n_out, const int32_t* next0, const int32_t* next1);
+    void check_owner(const Automaton& a) const;
+    // the two state buffers of the largest piece, in scratch.a
+    void reserve_automaton(CmuxScratch& scratch, const AutomatonPlan& pl);
+    // one piece: `items` items from call item `item0` on through every launch of the plan; out is the piece's
+    // [items][n_out][2][N], sel_of, final_of and finals the call's.  Returns the kernel launches issued (pl.launches).
+    int launch_automaton(const TgswSet& set, const Automaton& a, CmuxScratch& scratch, hipStream_t stream, const AutomatonPlan& pl, int64_t item0,
+                         int64_t items, const int32_t* sel_of, const int32_t* finals, int32_t n_finals, const int32_t* final_of, int32_t* out);
     // coefficient coef_of[i] (null: 0; clamped into [0, N)) of tlwe [count][2][N] -> u [count][stride], N + 1 words written.
     // Any supported parameter set.
     void launch_extract(hipStream_t stream, int64_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u, int32_t stride);

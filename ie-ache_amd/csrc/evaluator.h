@@ -16,6 +16,7 @@ namespace ieache {
 
 struct OptionRow;  // evaluator_options.h
 struct TgswSet;    // cmux.h
+struct Automaton;  // cmux.h
 struct CmuxPlan;   // cmux_plan.h
 struct SetCall;    // set_calls.h
 
@@ -208,6 +209,22 @@ public:
     void lut_read_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of,
                          const Torus32* d_tables, int32_t n_tables, const int32_t* d_table_of, int32_t coef, int32_t flags, Torus32* d_out,
                          EvalStats* stats);
+    // Automata over words of TGSW-encrypted bits (include/ieache.h section 3k; automaton_plan.h states what one is and how a
+    // call is cut).  automaton_create: the tables [steps][states] from host memory -> an object the caller owns (delete it before
+    // or after this evaluator goes; only this evaluator accepts it); std::invalid_argument with the first rule broken.
+    // automaton_run_device: item i runs V_t[q] = CMux(C_sel(i,t), V_{t+1}[next1[t][q]], V_{t+1}[next0[t][q]]) for t = steps-1 .. 0
+    // from V_steps = d_finals[final_of[i]] ([n_finals][states][2][N]; d_final_of null: 0, clamped) with the selectors
+    // sel_of[i steps + t] (null: (i steps + t) mod n; explicit: clamped) -> d_out [count][n_out][2][N] = V_0[0 .. n_out).  Pieces of
+    // whole items ("cmux_piece_rows" over 2 states rows each) on the evaluator's stream, every step of a piece in one launch or in
+    // chunks ("automaton_steps_per_launch"), the two state buffers reserved before the first piece.  stats: bootstraps 0, no
+    // key-switch launch, levels = steps, chunks = pieces, the launches and their time in the blind-rotation fields.
+    // std::invalid_argument for an output over any input (there is no in-place form), n_finals < 1, null rows, a set or an
+    // automaton of another evaluator.  automaton_plan_figures: pieces, items per piece, scratch rows, steps per launch, launches
+    // per piece of such a call under the options as they are.
+    Automaton* automaton_create(int32_t states, int32_t steps, int32_t n_out, const int32_t* next0, const int32_t* next1);
+    void automaton_run_device(const TgswSet& set, const Automaton& a, size_t count, const int32_t* d_sel_of, const Torus32* d_finals, int32_t n_finals,
+                              const int32_t* d_final_of, Torus32* d_out, EvalStats* stats = nullptr);
+    void automaton_plan_figures(const Automaton& a, size_t count, int64_t out[5]) const;
     // the plan such a call would follow under the options as they are (cmux_plan.h; depth < 0: a flat call of `count` rows):
     // pieces, items per piece, rows of scratch A, rows of scratch B
     void cmux_plan_figures(size_t count, int32_t depth, int64_t out[4]) const;

@@ -1132,6 +1132,47 @@ void Evaluator::lut_add_device(const TgswSet& set, size_t count, int32_t depth, 
     });
 }
 
+// Automata (section 3k).  The call stands beside the table of set_calls.h (automaton_plan.h says why), so its prelude is written
+// out here: owners, n_finals, the overlap of the output with any input, begin_call(), null rows -- begin_set_call's order.
+Automaton* Evaluator::automaton_create(int32_t states, int32_t steps, int32_t n_out, const int32_t* next0, const int32_t* next1) {
+    HIP_CHECK(hipSetDevice(device_));
+    return d_->cmux.automaton_create(states, steps, n_out, next0, next1);
+}
+
+void Evaluator::automaton_plan_figures(const Automaton& a, size_t count, int64_t out[5]) const {
+    d_->cmux.check_owner(a);
+    const AutomatonPlan pl = automaton_plan((int64_t)count, a.states, a.steps, d_->opt.cmux_piece_rows, d_->opt.automaton_steps_per_launch);
+    out[0] = pl.pieces;
+    out[1] = pl.items_per_piece;
+    out[2] = pl.scratch_rows;
+    out[3] = pl.steps_per_launch;
+    out[4] = pl.launches;
+}
+
+void Evaluator::automaton_run_device(const TgswSet& set, const Automaton& a, size_t count, const int32_t* d_sel_of, const Torus32* d_finals,
+                                     int32_t n_finals, const int32_t* d_final_of, Torus32* d_out, EvalStats* stats) {
+    d_->cmux.check_owner(set);
+    d_->cmux.check_owner(a);
+    if (n_finals < 1) throw std::invalid_argument("automaton_run: n_finals must be at least 1");
+    const size_t row = (size_t)2 * (size_t)p_.N;
+    if (overlaps(d_out, count * (size_t)a.n_out * row,
+                 {{d_finals, (size_t)n_finals * (size_t)a.states * row}, {d_sel_of, count * (size_t)a.steps}, {d_final_of, count}}))
+        throw std::invalid_argument("automaton_run: the output overlaps an input");
+    begin_call();
+    if (count == 0) return;
+    if (!d_finals || !d_out) throw std::invalid_argument("automaton_run: null rows");
+    Lane& ln = d_->lane[0];
+    const AutomatonPlan pl = automaton_plan((int64_t)count, a.states, a.steps, d_->opt.cmux_piece_rows, d_->opt.automaton_steps_per_launch);
+    d_->cmux.reserve_automaton(ln.cmux, pl);
+    CmuxPlan pieces;  // the piece loop's view of the cut
+    pieces.items_per_piece = pl.items_per_piece;
+    pieces.pieces = pl.pieces;
+    run_cmux_pieces(pieces, count, a.steps, stats, [&](int64_t i0, int64_t cnt) {
+        return d_->cmux.launch_automaton(set, a, ln.cmux, stream_, pl, i0, cnt, d_sel_of, d_finals, n_finals, d_final_of,
+                                         d_out + (size_t)i0 * (size_t)a.n_out * row);
+    });
+}
+
 // The rotation by caller selectors: the flat CMux's pieces, one launch each whatever the number of steps; no scratch.
 void Evaluator::tlwe_rotate_device(const TgswSet& set, size_t count, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of,
                                    const Torus32* d_in, Torus32* d_out, EvalStats* stats) {

@@ -467,6 +467,27 @@ void lut_add_reference(const Params& p, const Torus32* set, size_t n_set, size_t
     }
 }
 
+void automaton_reference(const Params& p, const Torus32* set, size_t n_set, int32_t states, int32_t steps, int32_t n_out, const int32_t* next0,
+                         const int32_t* next1, size_t count, const int32_t* sel_of, const Torus32* finals, const int32_t* final_of, Torus32* out) {
+    const size_t W = (size_t)2 * p.N, Q = (size_t)states;
+    std::vector<Torus32> v(Q * W), d1(Q * W), d0(Q * W);
+    std::vector<int32_t> sel(Q);
+    for (size_t i = 0; i < count; i++) {
+        const Torus32* fin = finals + (final_of ? (size_t)final_of[i] : 0) * Q * W;
+        std::copy(fin, fin + Q * W, v.begin());
+        for (int32_t t = steps - 1; t >= 0; t--) {
+            const size_t at = i * (size_t)steps + (size_t)t;
+            std::fill(sel.begin(), sel.end(), sel_of ? sel_of[at] : (int32_t)(at % n_set));
+            for (size_t q = 0; q < Q; q++) {
+                std::copy(v.begin() + (size_t)next1[(size_t)t * Q + q] * W, v.begin() + ((size_t)next1[(size_t)t * Q + q] + 1) * W, d1.begin() + q * W);
+                std::copy(v.begin() + (size_t)next0[(size_t)t * Q + q] * W, v.begin() + ((size_t)next0[(size_t)t * Q + q] + 1) * W, d0.begin() + q * W);
+            }
+            cmux_reference(p, set, n_set, Q, sel.data(), d1.data(), d0.data(), v.data());
+        }
+        std::copy(v.begin(), v.begin() + (size_t)n_out * W, out + i * (size_t)n_out * W);
+    }
+}
+
 void tlwe_extract_reference(const Params& p, size_t count, const Torus32* tlwe, const int32_t* coef_of, Torus32* u) {
     const int32_t N = p.N;
     for (size_t r = 0; r < count; r++) {

@@ -104,6 +104,13 @@ void lut_read_reference(const Params& p, const Torus32* set, size_t n_set, const
 void lut_add_reference(const Params& p, const Torus32* set, size_t n_set, size_t count, int32_t depth, int32_t steps, const int32_t* sel_of,
                        const int32_t* amount_of, const Torus32* values, const Torus32* mems, size_t n_mems, const int32_t* mem_of, Torus32* out);
 
+// automaton_reference (section 3k), composed from cmux_reference: per item V_steps = finals[final_of[i]] (null: 0) and for
+// t = steps-1 .. 0 one flat cmux_reference call over the `states` rows of the step -- d1 = V_{t+1}[next1[t][q]], d0 =
+// V_{t+1}[next0[t][q]], every row with the sample sel_of[i steps + t] (null: (i steps + t) mod n_set) -> out[i] = V_0[0 .. n_out).
+// Every state of every step is computed: no liveness, no copies.  Tables and indices already checked by the caller.
+void automaton_reference(const Params& p, const Torus32* set, size_t n_set, int32_t states, int32_t steps, int32_t n_out, const int32_t* next0,
+                         const int32_t* next1, size_t count, const int32_t* sel_of, const Torus32* finals, const int32_t* final_of, Torus32* out);
+
 // coefficient coef_of[r] (null: 0; checked by the caller) of tlwe [count][2][N] as extracted rows u [count][N+1]
 void tlwe_extract_reference(const Params& p, size_t count, const Torus32* tlwe, const int32_t* coef_of, Torus32* u);
 

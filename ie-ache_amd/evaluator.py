@@ -214,6 +214,17 @@ def lib():
     L.ieache_lut_add.argtypes = [vp, vp, C.c_size_t, C.c_int32, C.c_int32, i32p, i32p, i32p, i32p, C.c_int32, i32p, i32p, sp]
     L.ieache_lut_add_device.argtypes = [vp, vp, C.c_size_t, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, vp, sp]
     L.ieache_lut_add_reference.argtypes = [pp, i32p, C.c_size_t, C.c_size_t, C.c_int32, C.c_int32, i32p, i32p, i32p, i32p, C.c_int32, i32p, i32p]
+    L.ieache_automaton_create.restype = vp
+    L.ieache_automaton_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, i32p, i32p]
+    L.ieache_automaton_free.restype = None
+    L.ieache_automaton_free.argtypes = [vp]
+    L.ieache_automaton_info.argtypes = [vp, i32p, i32p, i32p, C.POINTER(C.c_int64)]
+    L.ieache_automaton_check.argtypes = [C.c_int32, C.c_int32, C.c_int32, i32p, i32p]
+    L.ieache_automaton_run.argtypes = [vp, vp, vp, C.c_size_t, i32p, i32p, C.c_int32, i32p, i32p, sp]
+    L.ieache_automaton_run_device.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.c_int32, vp, vp, sp]
+    L.ieache_automaton_reference.argtypes = [pp, i32p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, i32p, i32p, C.c_size_t, i32p, i32p, C.c_int32,
+                                             i32p, i32p]
+    L.ieache_debug_automaton_plan.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_int64)]
     L.ieache_tlwe_extract.argtypes = [vp, C.c_size_t, i32p, i32p, i32p, sp]
     L.ieache_tlwe_extract_device.argtypes = [vp, C.c_size_t, vp, vp, vp, sp]
     L.ieache_debug_cmux_plan.argtypes = [vp, C.c_size_t, C.c_int32, C.POINTER(C.c_int64)]
@@ -542,6 +553,47 @@ class TgswSet:
     def close(self):
         if getattr(self, "h", None):
             lib().ieache_tgsw_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+AUTOMATON_MAX_STATES, AUTOMATON_MAX_STEPS = 64, 4096
+
+
+def automaton_tables(next0, next1):
+    """the transition tables of an automaton as two int32 arrays [steps][states] (one row [states]: one step)"""
+    next0, next1 = np.ascontiguousarray(next0, dtype=np.int32), np.ascontiguousarray(next1, dtype=np.int32)
+    if next0.ndim == 1:
+        next0, next1 = next0.reshape(1, -1), next1.reshape(1, -1)
+    if next0.ndim != 2 or next0.shape != next1.shape:
+        raise ValueError("automaton: next0 and next1 must both be [steps][states]")
+    return next0, next1
+
+
+class Automaton:
+    """ieache_automaton: a compiled deterministic automaton (Context.automaton; include/ieache.h section 3k) -- the public
+    transition tables and the live masks on the device.  Like a TgswSet it owns its device memory: close() may come before or
+    after the close of the context that compiled it, and only that context accepts it.  states, steps, n_out; cmuxes: the live
+    CMuxes per item."""
+
+    def __init__(self, handle):
+        if not handle:
+            raise IeacheError(-22, lib().ieache_last_error().decode())
+        self.h = handle
+        st, sp, no, cm = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        check(lib().ieache_automaton_info(self.h, C.byref(st), C.byref(sp), C.byref(no), C.byref(cm)))
+        self.states, self.steps, self.n_out, self.cmuxes = st.value, sp.value, no.value, cm.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ieache_automaton_free(self.h)
             self.h = None
 
     __del__ = close
@@ -975,6 +1027,44 @@ class Context:
         [n_mems][2^depth][2][N] packed; d_out == d_mems adds in place."""
         check(lib().ieache_lut_add_device(self.h, tgsw.h, count, int(depth), int(steps), _dev(d_sel_of), _dev(d_amounts), C.c_void_p(d_values),
                                           _dev(d_mems), int(n_mems), _dev(d_mem_of), C.c_void_p(d_out), _stats_ref(stats)))
+
+    def automaton(self, next0, next1, n_out=1):
+        """Compile a deterministic automaton (include/ieache.h section 3k): next0, next1 [steps][states] int32, the state after
+        reading letter 0 / 1 at step t from state q (they may differ from step to step; ieache_amd.automata has worked examples);
+        outputs for the start states 0 .. n_out-1 -> an Automaton, to be closed (or used as a context manager) before or after
+        this context."""
+        next0, next1 = automaton_tables(next0, next1)
+        return Automaton(lib().ieache_automaton_create(self.h, next0.shape[1], next0.shape[0], int(n_out), _i32(next0), _i32(next1)))
+
+    def automaton_run(self, tgsw, a, finals, sel_of=None, final_of=None, count=None, stats=None):
+        """Run an automaton on words of TGSW-encrypted letters, host rows: item i starts from V_steps = finals[final_of[i]]
+        (finals [n_finals][states][2][N] or one [states][2][N]; final_of None: 0) and folds backward by the selectors sel_of[i]
+        ([count][steps], letter t the one read t-th; None: samples i steps + t mod n) -> [count][n_out][2][N]: out[i][q]
+        encrypts the final row the run from state q over item i's word ends in.  count: the number of items where neither
+        index array gives it (default 1)."""
+        N = self.params.N
+        finals = np.ascontiguousarray(finals, dtype=np.int32).reshape(-1, a.states, 2, N)
+        of = _opt_i32(sel_of, -1, max(a.steps, 1))
+        fof = _opt_i32(final_of, -1)
+        if count is None:
+            count = fof.shape[0] if fof is not None else (of.shape[0] if of is not None and a.steps > 0 else 1)
+        assert (fof is None or fof.shape[0] == count) and (of is None or a.steps < 1 or of.shape[0] == count)
+        out = np.zeros((count, a.n_out, 2, N), dtype=np.int32)
+        check(lib().ieache_automaton_run(self.h, tgsw.h, a.h, count, _opt(of), _i32(finals), finals.shape[0], _opt(fof), _i32(out), _stats_ref(stats)))
+        return out
+
+    def automaton_run_device(self, tgsw, a, count, d_sel_of, d_finals, n_finals, d_final_of, d_out, stats=None):
+        """Device pointers (ints; the index arrays may be None / 0): finals [n_finals][states][2][N], out [count][n_out][2][N]
+        packed; no overlap of out with an input is accepted."""
+        check(lib().ieache_automaton_run_device(self.h, tgsw.h, a.h, count, _dev(d_sel_of), C.c_void_p(d_finals), int(n_finals), _dev(d_final_of),
+                                                C.c_void_p(d_out), _stats_ref(stats)))
+
+    def automaton_plan(self, a, count):
+        """How automaton_run() would cut such a call under the options as they are (csrc/automaton_plan.h): dict(pieces,
+        items_per_piece, scratch_rows, steps_per_launch, launches) -- launches per piece."""
+        out = (C.c_int64 * 5)()
+        check(lib().ieache_debug_automaton_plan(self.h, a.h, count, out))
+        return dict(zip(("pieces", "items_per_piece", "scratch_rows", "steps_per_launch", "launches"), (int(v) for v in out)))
 
     def cmux_plan(self, count, depth=-1):
         """How cmux() (depth < 0) or lut_tree() / lut_scatter() would cut such a call under the options as they are (csrc/cmux_plan.h):

@@ -290,6 +290,34 @@ def lut_add_reference(params, samples, values, depth, steps=0, sel_of=None, amou
     return out
 
 
+def automaton_check(next0, next1, n_out=1):
+    """ieache_automaton_check: the validation of Context.automaton with no context and no GPU; raises IeacheError naming the
+    first rule broken."""
+    from .evaluator import automaton_tables
+    next0, next1 = automaton_tables(next0, next1)
+    check(lib().ieache_automaton_check(next0.shape[1], next0.shape[0], int(n_out), _i32(next0), _i32(next1)))
+
+
+def automaton_reference(params, samples, next0, next1, finals, n_out=1, sel_of=None, final_of=None, count=None):
+    """CPU reference of Context.automaton_run on raw arrays (ieache_automaton_reference: the CMux reference composed; no GPU,
+    any supported set): samples [n][2l][2][N], tables [steps][states], finals [n_finals][states][2][N] -> [count][n_out][2][N]."""
+    from .evaluator import automaton_tables
+    next0, next1 = automaton_tables(next0, next1)
+    steps, states = next0.shape
+    kpl = (params.k + 1) * params.l
+    samples = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, kpl, 2, params.N)
+    finals = np.ascontiguousarray(finals, dtype=np.int32).reshape(-1, max(states, 1), 2, params.N)
+    of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(steps, 1))
+    fof = None if final_of is None else np.ascontiguousarray(final_of, dtype=np.int32).reshape(-1)
+    if count is None:
+        count = fof.shape[0] if fof is not None else (of.shape[0] if of is not None and steps > 0 else 1)
+    assert (fof is None or fof.shape[0] == count) and (of is None or steps < 1 or of.shape[0] == count)
+    out = np.zeros((count, max(int(n_out), 0), 2, params.N), dtype=np.int32)
+    check(lib().ieache_automaton_reference(C.byref(params), _i32(samples), samples.shape[0], states, steps, int(n_out), _i32(next0), _i32(next1), count,
+                                           None if of is None else _i32(of), _i32(finals), finals.shape[0], None if fof is None else _i32(fof), _i32(out)))
+    return out
+
+
 def tlwe_extract_reference(params, tlwe, coef_of=None):
     """CPU reference of Context.tlwe_extract (ieache_tlwe_extract_reference): tlwe [count][2][N] -> [count][N+1]."""
     tlwe = np.ascontiguousarray(tlwe, dtype=np.int32).reshape(-1, 2, params.N)

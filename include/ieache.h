@@ -967,6 +967,62 @@ int ieache_lut_add_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count,
                           const int32_t* d_amount_of, const int32_t* d_values, const int32_t* d_mems, int32_t n_mems, const int32_t* d_mem_of,
                           int32_t* d_out /* == d_mems: in place */, ieache_stats* stats);
 
+/* 3k. Deterministic (weighted) finite automata over words whose letters are TGSW-encrypted bits: the sequential shape among
+ * the calls on a set, where 3f to 3j are a tree, a demux tree and a rotation.  Conventions, sets, gadgets and exactness are
+ * those of 3f to 3i (integers mod 2^32; any set section 3i admits; N = 1024, k = 1).
+ *
+ * An automaton has `states` Q in 1 .. IEACHE_AUTOMATON_MAX_STATES, `steps` p in 0 .. IEACHE_AUTOMATON_MAX_STEPS, n_out in
+ * 1 .. Q and public transition tables next0, next1 [steps][states] with entries in [0, Q), which may differ from step to step.
+ * For item i, with the set's samples C, the selectors sel_of[i steps + t] (NULL: that index mod n) and the final rows
+ * finals[final_of[i]] [states][2][N] (final_of == NULL: 0):
+ *     V_p[q] = finals[final_of[i]][q]
+ *     V_t[q] = CMux(C_sel(i,t), d1 = V_{t+1}[next1[t][q]], d0 = V_{t+1}[next0[t][q]])      t = p-1 .. 0
+ *     out[i][q] = V_0[q]                                                                   q < n_out
+ * CMux is word for word ieache_cmux_reference, d0 + C [.] (d1 - d0) with the SET's gadget.  Letter t of the word is the one the
+ * automaton reads t-th when it runs forward from state q; the evaluation runs backward, as in the TFHE paper, so out[i][q] is an
+ * encryption of the final row the forward run from q ends in.  With finals of +-1/8 in coefficient 0, ieache_tlwe_extract and
+ * ieache_keyswitch turn out[i][0] into a gate input.  p CMuxes bring p times a CMux's noise: DESIGN.md section 7 gives the steps
+ * each gadget allows.
+ *
+ * The automaton is an object compiled once and run many times, like a netlist or a set.  ieache_automaton_create takes the
+ * tables from host memory, refuses a bad scalar or the first out-of-range entry by name ("next1[t][q] = v is outside [0, Q)":
+ * scalars first, then entries in the order step, state, next0 before next1), computes per step the 64-bit mask of LIVE states
+ * (live_0 = [0, n_out), live_{t+1} = the image of live_t under both tables of step t) and uploads tables and masks.  It returns
+ * NULL on failure (ieache_last_error).  ieache_automaton_free may come before or after the context is destroyed; only the
+ * context that compiled an automaton accepts it.  ieache_automaton_info: states, steps, n_out and the live CMuxes per item --
+ * the live (t, q) whose two tables differ; where they agree the CMux is exactly d0 and the device copies the row.
+ * ieache_automaton_check is the same validation with no context and no GPU: 0, or IEACHE_EINVAL with the message.
+ *
+ * ieache_automaton_run is the host form, ieache_automaton_run_device the same on device pointers on the context's stream:
+ * finals [n_finals][states][2][N], out [count][n_out][2][N] packed.  ANY overlap of out with finals (or an index array) is
+ * refused: there is no in-place form.  One workgroup runs every step of an item inside one launch and hands the state vector
+ * from wave to wave through two scratch buffers of `states` rows per item; dead states are skipped and
+ * states whose tables agree copied, which leaves every word of out unchanged.  The cut (ieache_debug_automaton_plan: pieces,
+ * items per piece, scratch rows, steps per launch, launches per piece): pieces of whole items with 2 x states scratch rows each
+ * within the option "cmux_piece_rows" (an item wider than the cap runs alone); the steps of a piece in one launch, or with the
+ * option "automaton_steps_per_launch" = k > 0 in consecutive launches of at most k steps (1: a launch per step); the default 0
+ * cuts only where steps x ceil(states / 4) exceeds 8 192.  Scratch is reserved before the first piece; a warm call allocates
+ * nothing.  steps == 0 copies the final rows.  Host form: every index is checked first and the first bad one named; device
+ * form: an explicit selector is clamped into the set (an implied one taken mod n) and final_of into [0, n_finals).
+ * IEACHE_EINVAL: a set or an automaton of another context, N != 1024, null pointers, n_finals < 1, overlap, a host pointer to the
+ * device form.  stats: bootstraps == 0, keyswitch_launches == 0, levels = steps, chunks = pieces, blind_rotate_launches =
+ * pieces x launches per piece, their time in blind_rotate_ms.
+ * No per-item automata in one call, no group form, no cloudd verb, no weights other than TLWE rows, no other rings, no one-limb form. */
+#define IEACHE_AUTOMATON_MAX_STATES 64
+#define IEACHE_AUTOMATON_MAX_STEPS 4096
+typedef struct ieache_automaton ieache_automaton;
+ieache_automaton* ieache_automaton_create(ieache_ctx* ctx, int32_t states, int32_t steps, int32_t n_out, const int32_t* next0 /*[steps][states]*/,
+                                          const int32_t* next1 /*[steps][states]*/);
+void ieache_automaton_free(ieache_automaton* a);
+int ieache_automaton_info(const ieache_automaton* a, int32_t* states, int32_t* steps, int32_t* n_out, int64_t* cmuxes);
+int ieache_automaton_check(int32_t states, int32_t steps, int32_t n_out, const int32_t* next0, const int32_t* next1);
+int ieache_automaton_run(ieache_ctx* ctx, const ieache_tgsw* set, const ieache_automaton* a, size_t count, const int32_t* sel_of /*[count][steps] or NULL*/,
+                         const int32_t* finals /*[n_finals][states][2][N]*/, int32_t n_finals, const int32_t* final_of /*[count] or NULL*/,
+                         int32_t* out /*[count][n_out][2][N]*/, ieache_stats* stats);
+int ieache_automaton_run_device(ieache_ctx* ctx, const ieache_tgsw* set, const ieache_automaton* a, size_t count, const int32_t* d_sel_of,
+                                const int32_t* d_finals, int32_t n_finals, const int32_t* d_final_of, int32_t* d_out, ieache_stats* stats);
+int ieache_debug_automaton_plan(const ieache_ctx* ctx, const ieache_automaton* a, size_t count, int64_t out[5]);
+
 /* ------------------------------------------------------------------ *
  * 4. CPU tools around the path (no GPU): what Keygen/keygen.c:22-51,  *
  *    Client1/alice.c:116-191 and Output/verif.c:41-76 get from        *
@@ -1039,6 +1095,12 @@ int ieache_lut_read_reference(const ieache_params* p, const int32_t* set, size_t
 int ieache_lut_add_reference(const ieache_params* p, const int32_t* set, size_t n, size_t count, int32_t depth, int32_t steps,
                              const int32_t* sel_of, const int32_t* amount_of, const int32_t* values, const int32_t* mems, int32_t n_mems,
                              const int32_t* mem_of, int32_t* out);
+/* ... of ieache_automaton_run (section 3k), composed from the CMux reference: set [n][2l][2][N] with p's gadget, tables
+ * [steps][states], finals [n_finals][states][2][N] -> out [count][n_out][2][N]; arguments, defaults and refusals (the automaton's
+ * and the indices') as for ieache_automaton_create and the host form ... */
+int ieache_automaton_reference(const ieache_params* p, const int32_t* set, size_t n, int32_t states, int32_t steps, int32_t n_out,
+                               const int32_t* next0, const int32_t* next1, size_t count, const int32_t* sel_of, const int32_t* finals,
+                               int32_t n_finals, const int32_t* final_of, int32_t* out);
 /* ... and of ieache_tlwe_extract: tlwe [count][2][N] -> u [count][N+1]. */
 int ieache_tlwe_extract_reference(const ieache_params* p, size_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u);
 /* key files -> raw arrays (sizes from ieache_params; pass NULL to query params only) */
