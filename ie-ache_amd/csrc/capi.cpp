@@ -24,6 +24,7 @@
 #include "group_run.h"
 #include "mix_plan.h"
 #include "pack_plan.h"
+#include "project_plan.h"
 #include "program.h"
 #include "set_calls.h"
 #include "tfhe_host.h"
@@ -1217,6 +1218,103 @@ int ieache_lut_add(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_
                          });
 }
 
+// ---- the TLWE projection and the replace write of a window (section 3l).  project_plan.h states what the calls accept; the write
+// stands beside the table of set_calls.h (it takes two further scalars and needs the projection key), so its device and host
+// forms follow set_call_device's and set_call_host's steps written out. ----
+namespace {
+int check_project(const ieache_ctx* ctx, int32_t first, int32_t width, int32_t dest, size_t count, const int32_t* in, const int32_t* out) {
+    if (!ctx || (count && (!in || !out))) return fail(IEACHE_EINVAL, "null argument");
+    if (!ctx->eval->has_projection_key()) return fail(IEACHE_EINVAL, "tlwe_project: no projection key set");
+    if (const char* e = project_call_error(ctx->eval->params(), first, width, dest)) return fail(IEACHE_EINVAL, e);
+    return 0;
+}
+int check_write_coef(const ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit,
+                     const int32_t* fresh, const int32_t* mem, const int32_t* out) {
+    if (const int rc = check_tgsw(ctx, set)) return rc;
+    if (count && (!fresh || !mem || !out)) return fail(IEACHE_EINVAL, "null argument");
+    if (!ctx->eval->has_projection_key()) return fail(IEACHE_EINVAL, "lut_write_coef: no projection key set");
+    if (const char* e = write_coef_error(ctx->eval->params(), depth, steps, width, unit)) return fail(IEACHE_EINVAL, e);
+    return 0;
+}
+}  // namespace
+
+int ieache_ctx_set_projection_key(ieache_ctx* ctx, int32_t pk_t, int32_t pk_basebit, const int32_t* pk) {
+    return guarded([&] {
+        if (!ctx) return fail(IEACHE_EINVAL, "null context");
+        if (pk)
+            if (const char* e = project_set_error(ctx->eval->params(), pk_t, pk_basebit)) return fail(IEACHE_EINVAL, e);
+        ctx->eval->set_projection_key(pk_t, pk_basebit, pk);
+        return 0;
+    });
+}
+
+int ieache_debug_project_plan(const ieache_ctx* ctx, size_t count, int32_t width, int64_t out[4]) {
+    return guarded([&] {
+        if (!ctx || !out) return fail(IEACHE_EINVAL, "null argument");
+        if (!ctx->eval->has_projection_key()) return fail(IEACHE_EINVAL, "tlwe_project: no projection key set");
+        if (const char* e = project_call_error(ctx->eval->params(), 0, width, 0)) return fail(IEACHE_EINVAL, e);
+        ctx->eval->project_plan_figures(count, width, out);
+        return 0;
+    });
+}
+
+int ieache_tlwe_project_device(ieache_ctx* ctx, size_t count, int32_t first, int32_t width, int32_t dest, const int32_t* d_in, int32_t* d_out,
+                               ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_project(ctx, first, width, dest, count, d_in, d_out)) return rc;
+        require_device_pointers(count, {{d_in, "d_in"}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->tlwe_project_device(count, first, width, dest, d_in, d_out, st); });
+    });
+}
+
+int ieache_tlwe_project(ieache_ctx* ctx, size_t count, int32_t first, int32_t width, int32_t dest, const int32_t* in, int32_t* out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_project(ctx, first, width, dest, count, in, out)) return rc;
+        HostCall h(ctx, count);
+        const size_t sample = (size_t)2 * (size_t)h.p.N;
+        StagedRows din(h.ev, kStageTlweA, count, sample, in, sample), dout(h.ev, kStageOut, count, sample);
+        with_stats(stats, [&](EvalStats* st) { h.ev.tlwe_project_device(count, first, width, dest, din.p, dout.p, st); });
+        dout.download(out, sample);
+        return 0;
+    });
+}
+
+int ieache_lut_write_coef_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit,
+                                 const int32_t* d_sel_of, const int32_t* d_new, const int32_t* d_mem, int32_t* d_out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_write_coef(ctx, set, count, depth, steps, width, unit, d_new, d_mem, d_out)) return rc;
+        if (count) {
+            require_device_pointer(d_new, "d_new");
+            require_device_pointer(d_mem, "d_mem");
+            require_device_pointer(d_out, "d_out");
+            if (d_sel_of && depth + steps > 0) require_device_pointer(d_sel_of, "d_sel_of");
+        }
+        return with_stats(stats, [&](EvalStats* st) {
+            ctx->eval->lut_write_coef_device(*set->set, count, depth, steps, width, unit, d_sel_of, d_new, d_mem, d_out, st);
+        });
+    });
+}
+
+int ieache_lut_write_coef(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit,
+                          const int32_t* sel_of, const int32_t* fresh, const int32_t* mem, int32_t* out, ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_write_coef(ctx, set, count, depth, steps, width, unit, fresh, mem, out)) return rc;
+        if (const int rc = check_indices(sel_of, count * (size_t)(depth + steps), (int64_t)set->set->n, "lut_write_coef", "sel_of")) return rc;
+        HostCall h(ctx, count);
+        const size_t sample = (size_t)2 * (size_t)h.p.N, leaves = count << depth;
+        // the memory is uploaded into the result rows: the call runs in place
+        StagedRows dout(h.ev, kStageOut, leaves, sample);
+        if (leaves) HIP_CHECK(hipMemcpy(dout.p, mem, leaves * sample * 4, hipMemcpyHostToDevice));
+        StagedRows dnew(h.ev, kStageTlweA, count, sample, fresh, sample);
+        StagedRows dsel = h.words(kStagePolyOf, depth + steps > 0 ? sel_of : nullptr, count * (size_t)(depth + steps));
+        with_stats(stats, [&](EvalStats* st) {
+            h.ev.lut_write_coef_device(*set->set, count, depth, steps, width, unit, dsel.p, dnew.p, dout.p, dout.p, st);
+        });
+        dout.download(out, sample);
+        return 0;
+    });
+}
+
 // ---- automata over words of TGSW-encrypted bits (section 3k).  The call stands beside the table of set_calls.h
 // (automaton_plan.h says why); the device and host forms below follow set_call_device's and set_call_host's steps. ----
 struct ieache_automaton {
@@ -1888,6 +1986,35 @@ int ieache_tlwe_extract_reference(const ieache_params* p, size_t count, const in
         if (!pp.supported()) return fail(IEACHE_EINVAL, "tlwe_extract_reference: unsupported TFHE parameter set");
         if (const int rc = check_indices(coef_of, count, pp.N, "tlwe_extract", "coef_of")) return rc;
         tlwe_extract_reference(pp, count, tlwe, coef_of, u);
+        return 0;
+    });
+}
+
+int ieache_tlwe_project_reference(const ieache_params* p, int32_t pk_t, int32_t pk_basebit, const int32_t* pk, size_t count, int32_t first, int32_t width,
+                                  int32_t dest, const int32_t* in, int32_t* out) {
+    return guarded([&] {
+        if (!p || !pk || (count && (!in || !out))) return fail(IEACHE_EINVAL, "null argument");
+        const Params pp = to_params(*p);
+        if (const char* e = project_set_error(pp, pk_t, pk_basebit)) return fail(IEACHE_EINVAL, e);
+        if (const char* e = project_call_error(pp, first, width, dest)) return fail(IEACHE_EINVAL, e);
+        tlwe_project_reference(pp, pk_t, pk_basebit, pk, count, first, width, dest, in, out);
+        return 0;
+    });
+}
+
+int ieache_lut_write_coef_reference(const ieache_params* p, const int32_t* set, size_t n, int32_t pk_t, int32_t pk_basebit, const int32_t* pk, size_t count,
+                                    int32_t depth, int32_t steps, int32_t width, int32_t unit, const int32_t* sel_of, const int32_t* fresh,
+                                    const int32_t* mem, int32_t* out) {
+    return guarded([&] {
+        if (!p || !set || (count && (!fresh || !mem || !out))) return fail(IEACHE_EINVAL, "null argument");
+        if (!pk) return fail(IEACHE_EINVAL, "lut_write_coef: no projection key set");
+        const Params pp = to_params(*p);
+        if (!pp.supported()) return fail(IEACHE_EINVAL, "lut_write_coef_reference: unsupported TFHE parameter set");
+        if (n < 1) return fail(IEACHE_EINVAL, "lut_write_coef_reference: no samples");
+        if (const char* e = project_set_error(pp, pk_t, pk_basebit)) return fail(IEACHE_EINVAL, e);
+        if (const char* e = write_coef_error(pp, depth, steps, width, unit)) return fail(IEACHE_EINVAL, e);
+        if (const int rc = check_indices(sel_of, count * (size_t)(depth + steps), (int64_t)n, "lut_write_coef", "sel_of")) return rc;
+        lut_write_coef_reference(pp, set, n, pk_t, pk_basebit, pk, count, depth, steps, width, unit, sel_of, fresh, mem, out);
         return 0;
     });
 }

@@ -148,6 +148,19 @@ public:
     void pack_plan_figures(size_t groups, int32_t m, int64_t out[4]) const;
     void pack_device(size_t groups, int32_t m, int32_t spread, int32_t shift, const Torus32* d_rows, Torus32* d_out, EvalStats* stats);
 
+    // The TLWE projection (include/ieache.h section 3l; project_plan.h): the packing unit a second time, on the parameter set
+    // with n := N and the projection key pk [N][t][2][N] (host; a second key replaces the first, null drops it and its scratch),
+    // independent of the packing key.  tlwe_project_device: d_in [count][2][N] -> d_out [count][2][N], sample i's coefficients
+    // first .. first + width - 1 at dest .., nothing else, in pieces of whole items (project_plan) on the evaluator's stream,
+    // every piece's scratch reserved before the first; the extracted rows are never stored.  stats as pack_device's.
+    // std::invalid_argument without a key, for a window project_call_error refuses, and for ANY overlap of d_out with d_in.
+    // project_plan_figures: pieces, items per piece, K split, K steps of such a call under the options as they are
+    // ("pack_piece_rows", "project_split").
+    void set_projection_key(int32_t t, int32_t basebit, const Torus32* pk);
+    bool has_projection_key() const;
+    void project_plan_figures(size_t count, int32_t width, int64_t out[4]) const;
+    void tlwe_project_device(size_t count, int32_t first, int32_t width, int32_t dest, const Torus32* d_in, Torus32* d_out, EvalStats* stats);
+
     // CMux on caller TGSW samples, the CMux-tree lookup and the extraction of a coefficient (cmux.h; include/ieache.h section
     // 3f states the definitions).  tgsw_prepare_device: d_samples [n][2l][2][N] -> a set the caller owns (delete it before or
     // after this evaluator goes; only this evaluator accepts it); std::invalid_argument unless br_supported().
@@ -204,6 +217,17 @@ public:
     void lut_add_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of,
                         const Torus32* d_values, const Torus32* d_mems, int32_t n_mems, const int32_t* d_mem_of, Torus32* d_out,
                         EvalStats* stats = nullptr);
+    // lut_write_coef_device (section 3l), the replace write of a window mem[i][hi_i].coef[lo_i unit .. + width) := new[i].coef[0 ..
+    // width): per piece of the tree's plan for (count, depth) the tree over the items' own memories, the rotation toward
+    // position 0, the projection onto (0, width, 0) in runs of the projection's plan, delta = new - old, and lut_add_device's
+    // piece with memory i for item i and the amounts +unit 2^t.  d_new [count][2][N], d_mem and d_out [count][2^depth][2][N];
+    // d_out == d_mem writes in place (a piece reads and adds into its own items' memories only), no other overlap; with
+    // distinct buffers d_out starts as a copy of d_mem on the stream.  Everything is reserved before the first piece.  stats:
+    // levels = 2 (depth + steps) + 1, chunks = pieces, keyswitch_launches = the projection's runs, blind_rotate_launches =
+    // pieces x (2 max(depth, 1) + 2 (steps > 0) + 1).  std::invalid_argument without a projection key, for scalars
+    // write_coef_error refuses, an overlap, a set of another evaluator.
+    void lut_write_coef_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit, const int32_t* d_sel_of,
+                               const Torus32* d_new, const Torus32* d_mem, Torus32* d_out, EvalStats* stats = nullptr);
     void tlwe_rotate_device(const TgswSet& set, size_t count, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of, const Torus32* d_in,
                             Torus32* d_out, EvalStats* stats);
     void lut_read_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of,

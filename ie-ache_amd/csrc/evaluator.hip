@@ -32,6 +32,7 @@
 #include "pack.h"
 #include "scoped_set.h"
 #include "set_calls.h"
+#include "write_coef.h"
 
 #include <algorithm>
 #include <cmath>
@@ -133,6 +134,9 @@ struct Lane {
     MvScratch mv;                   // multi-output programmable bootstrap: a piece's accumulators and its extracted rows
     std::unique_ptr<PackScratch> pack;  // packing key switch: a piece's R rows and digits; there while a packing key is set
     CmuxScratch cmux;               // CMux tree: the two buffers whose roles swap from level to level (empty until a tree runs)
+    std::unique_ptr<PackScratch> project;  // projection: a piece's R rows and digits; there while a projection key is set
+    DeviceBuffer<Torus32> coef_old;  // replace write of a window: a piece's projected old words, then the differences [items][2][N]
+    DeviceBuffer<int32_t> coef_idx;  // ... the two amount arrays [kRotateMaxSteps] each, then own [count] = 0, 1, ..
     Event ev_join;                  // the lane's share of a level / of an evaluation is queued
     Event ev_mix;
 };
@@ -163,6 +167,7 @@ struct Evaluator::Impl {
     DeviceBuffer<int32_t> ksk;
     KeySwitch ks;  // K5: kernels, key form, LDS grants and the choice among them
     Pack pack;  // the packing key switch (LWE rows -> TLWE samples): kernels, key form and the cut of a call (pack_plan.h)
+    Pack project;  // the same unit on project_params(): the projection key (TLWE sample -> the window of its coefficients, section 3l)
     Cmux cmux;  // CMux on caller TGSW samples, its tree and the extraction of a coefficient: kernels, twiddles, the cut (cmux_plan.h)
     MultiExtract mv;  // between K3 and K5 of a multi-output programmable bootstrap: the factors' lists and the extraction by factor
     DeviceBuffer<Torus32> store;    // circuits: the wire store, the gate and the output table
@@ -236,6 +241,7 @@ void Evaluator::init() {
     d_->ks.init(p, K);
     d_->mv.init(p);
     d_->pack.init(p);
+    d_->project.init(project_params(p));
     d_->cmux.init(p, device_, &d_->opt.cmux_gadget_runtime);
 }
 
@@ -290,6 +296,8 @@ bool Evaluator::option_hook(const OptionRow& r, int64_t& v) {
     if (r.at == &EvalOptions::force_generic) v = v != 0;
     if (r.at == &EvalOptions::ks_mfma_split) return v == 0 || ks_mfma_split_ok(p_, (int32_t)v);  // every split holds whole loop trips
     if (r.at == &EvalOptions::pack_split) return v == 0 || (d_->pack.has_key() && pack_split_ok(pack_k_steps(p_, d_->pack.t()), (int32_t)v));
+    if (r.at == &EvalOptions::project_split)
+        return v == 0 || (d_->project.has_key() && pack_split_ok(pack_k_steps(project_params(p_), d_->project.t()), (int32_t)v));
     if (r.at == &EvalOptions::br_variant && !variant_known((int32_t)v)) {
         // a retired number (an old A/B script): say so rather than measure another kernel under the wrong label
         fprintf(stderr, "ieache: br_variant %d names no kernel of this build (csrc/br_plan.h); the choice of kernels stays as it is\n", (int)v);
@@ -955,6 +963,160 @@ void Evaluator::pack_device(size_t groups, int32_t m, int32_t spread, int32_t sh
     HIP_CHECK(hipStreamSynchronize(stream_));
     add_times(stats, tall, tbr, tks);
     if (stats) stats->levels += 1;
+}
+
+void Evaluator::set_projection_key(int32_t t, int32_t basebit, const Torus32* pk) {
+    HIP_CHECK(hipSetDevice(device_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    d_->project.set_key(t, basebit, pk, stream_);
+    if (!pk) d_->lane[0].project.reset();  // the key is gone (the stream is idle): so is the scratch of its calls
+    d_->opt.project_split = 0;  // a forced split was accepted for the walk of the key that is gone
+}
+
+bool Evaluator::has_projection_key() const { return d_->project.has_key(); }
+
+void Evaluator::project_plan_figures(size_t count, int32_t width, int64_t out[4]) const {
+    if (!d_->project.has_key()) throw std::invalid_argument("tlwe_project: no projection key set");
+    const PackPlan pl =
+        project_plan(p_, d_->project.t(), (int64_t)count, width, d_->opt.pack_piece_rows, (int32_t)d_->opt.project_split, d_->opt.cus);
+    out[0] = pl.pieces;
+    out[1] = pl.groups_per_piece;
+    out[2] = pl.ksplit;
+    out[3] = pl.k_steps;
+}
+
+// The projection: pieces of whole items on the evaluator's stream, each three launches of the unit (window digits, product,
+// placement).  Integer arithmetic throughout, as pack_device.
+void Evaluator::tlwe_project_device(size_t count, int32_t first, int32_t width, int32_t dest, const Torus32* d_in, Torus32* d_out, EvalStats* stats) {
+    if (!d_->project.has_key()) throw std::invalid_argument("tlwe_project: no projection key set");
+    if (const char* e = project_call_error(p_, first, width, dest)) throw std::invalid_argument(e);
+    const size_t row = (size_t)2 * (size_t)p_.N;
+    if (overlaps(d_out, count * row, {{d_in, count * row}})) throw std::invalid_argument("tlwe_project: the output overlaps the input samples");
+    begin_call();
+    if (count == 0) return;
+    if (!d_in || !d_out) throw std::invalid_argument("tlwe_project: null rows");
+    Lane& ln = d_->lane[0];
+    const PackPlan pl =
+        project_plan(p_, d_->project.t(), (int64_t)count, width, d_->opt.pack_piece_rows, (int32_t)d_->opt.project_split, d_->opt.cus);
+    if (!ln.project) ln.project.reset(new PackScratch);
+    d_->project.reserve(*ln.project, pl);
+    Timer tall(stats != nullptr, stream_), tks(stats != nullptr, stream_), tbr(false, stream_);
+    tall.mark();
+    for (int64_t i = 0; i < pl.pieces; i++) {
+        const int64_t i0 = pack_piece_first(pl, i), cnt = pack_piece_groups(pl, (int64_t)count, i);
+        tks.mark();
+        d_->project.launch_window(*ln.project, stream_, pl, cnt, first, width, dest, d_in + (size_t)i0 * row, d_out + (size_t)i0 * row);
+        tks.mark();
+        HIP_CHECK(hipGetLastError());
+        if (stats) {
+            stats->keyswitch_launches++;
+            stats->chunks++;
+        }
+    }
+    tall.mark();
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    add_times(stats, tall, tbr, tks);
+    if (stats) stats->levels += 1;
+}
+
+// The replace write of a window: the tree's pieces; per piece the read path (tree over the items' own memories, rotation toward
+// position 0), the projection in runs of its own plan, the subtraction, and lut_add's piece with memory i for item i.  A piece
+// reads and adds into its own items' memories only and has read them before it adds (one stream), so d_out == d_mem is sound.
+void Evaluator::lut_write_coef_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit,
+                                      const int32_t* d_sel_of, const Torus32* d_new, const Torus32* d_mem, Torus32* d_out, EvalStats* stats) {
+    d_->cmux.check_owner(set);
+    if (!d_->project.has_key()) throw std::invalid_argument("lut_write_coef: no projection key set");
+    if (const char* e = write_coef_error(p_, depth, steps, width, unit)) throw std::invalid_argument(e);
+    const size_t row = (size_t)2 * (size_t)p_.N, leaves = count << depth;
+    if (overlaps(d_out, leaves * row, {{d_new, count * row}, {d_sel_of, count * (size_t)(depth + steps)}}) ||
+        (d_mem != d_out && overlaps(d_out, leaves * row, {{d_mem, leaves * row}})))
+        throw std::invalid_argument("lut_write_coef: the output overlaps an input (only d_out == d_mem, the write in place, is accepted)");
+    begin_call();
+    if (count == 0) return;
+    if (!d_new || !d_mem || !d_out) throw std::invalid_argument("lut_write_coef: null rows");
+    Lane& ln = d_->lane[0];
+    const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
+    const PackPlan pp =
+        project_plan(p_, d_->project.t(), pl.items_per_piece, width, d_->opt.pack_piece_rows, (int32_t)d_->opt.project_split, d_->opt.cus);
+    d_->cmux.reserve_read(ln.cmux, pl, depth);
+    if (!ln.project) ln.project.reset(new PackScratch);
+    d_->project.reserve(*ln.project, pp);
+    ln.coef_old.reserve_exact((size_t)pl.items_per_piece * row);
+    ln.coef_idx.reserve_exact((size_t)2 * kRotateMaxSteps + count);
+    int32_t *toward = ln.coef_idx, *back = toward + kRotateMaxSteps, *own = back + kRotateMaxSteps;
+    // not launches of the call's: the copy the sums start from, and the public amounts and memory indices
+    if (d_out != d_mem) HIP_CHECK(hipMemcpyAsync(d_out, d_mem, leaves * row * 4, hipMemcpyDeviceToDevice, stream_));
+    launch_write_coef_tables(stream_, unit, steps, 2 * p_.N, (int64_t)count, toward, back, own);
+    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(stats != nullptr, stream_);
+    tall.mark();
+    for (int64_t i = 0; i < pl.pieces; i++) {
+        const int64_t i0 = cmux_piece_first(pl, i), cnt = cmux_piece_items(pl, (int64_t)count, i);
+        const Torus32* mem = d_mem + ((size_t)i0 << depth) * row;
+        Torus32* rows = ln.cmux.rows;
+        int launches = 0;
+        tbr.mark();
+        // (1) old row: the tree over each item's own memory by its high selectors, made explicit for the piece
+        if (depth == 0) {
+            HIP_CHECK(hipMemcpyAsync(rows, mem, (size_t)cnt * row * 4, hipMemcpyDeviceToDevice, stream_));
+            launches++;
+        } else {
+            int32_t* tree_sel = ln.cmux.idx;
+            launch_write_coef_indices(stream_, d_sel_of, i0, cnt, depth, steps, (int32_t)set.n, tree_sel);
+            const Torus32* src = mem;
+            for (int32_t k = 0; k < depth; k++) {
+                CmuxRows R;
+                R.depth = depth;
+                R.level = k;
+                R.width = 1 << (depth - 1 - k);
+                R.rows = cnt * R.width;
+                R.sel_of = tree_sel;  // the piece's own array: item0 stays 0
+                R.src = src;
+                R.dst = k == depth - 1 ? rows : (k % 2 == 0 ? (Torus32*)ln.cmux.a : (Torus32*)ln.cmux.b);  // launch_tree's buffers
+                d_->cmux.launch(set, stream_, R);
+                src = R.dst;
+            }
+            launches += depth;
+        }
+        // (2) the addressed word to position 0
+        if (steps > 0) {
+            RotateRows R;
+            R.src = R.dst = rows;
+            R.rows = cnt;
+            R.item0 = i0;
+            R.sel_of = d_sel_of;
+            R.amount_of = toward;
+            R.steps = steps;
+            R.sel_stride = depth + steps;
+            d_->cmux.launch_rotate(set, stream_, R);
+            launches++;
+        }
+        tbr.mark();
+        HIP_CHECK(hipGetLastError());
+        // (3) old = the window alone
+        Torus32* old = ln.coef_old;
+        for (int64_t r = 0, runs = project_runs(pp, cnt); r < runs; r++) {
+            const int64_t g0 = pack_piece_first(pp, r), g = pack_piece_groups(pp, cnt, r);
+            tks.mark();
+            d_->project.launch_window(*ln.project, stream_, pp, g, 0, width, 0, rows + (size_t)g0 * row, old + (size_t)g0 * row);
+            tks.mark();
+            HIP_CHECK(hipGetLastError());
+            if (stats) stats->keyswitch_launches++;
+        }
+        // (4) delta = new - old, (5) added at the address into the items' own memories
+        tbr.mark();
+        launch_write_coef_delta(stream_, cnt, p_.N, d_new + (size_t)i0 * row, old);
+        launches += 1 + d_->cmux.launch_add(set, ln.cmux, stream_, i0, cnt, depth, steps, d_sel_of, back, old, (int32_t)count, own, d_out);
+        tbr.mark();
+        HIP_CHECK(hipGetLastError());
+        if (stats) {
+            stats->blind_rotate_launches += launches;
+            stats->chunks++;
+        }
+    }
+    tall.mark();
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    add_times(stats, tall, tbr, tks);
+    if (stats) stats->levels += 2 * (depth + steps) + 1;
 }
 
 TgswSet* Evaluator::tgsw_prepare_device(const Torus32* d_samples, size_t n) {

@@ -25,6 +25,7 @@ struct EvalOptions {
     int64_t ks_xcd = 0;
     // packing key switch: how a call is cut (pack_plan.h)
     int64_t pack_split = 0, pack_piece_rows = 4096;
+    int64_t project_split = 0;  // the projection (project_plan.h): pack_split's sibling for the projection key's walk
     // CMux on caller TGSW samples and its tree: rows of a piece (cmux_plan.h)
     int64_t cmux_piece_rows = 8192;
     int64_t cmux_gadget_runtime = 0;  // debug: every TGSW set on the run-time-gadget builds (cmux_step.h)
@@ -77,7 +78,8 @@ inline constexpr OptionRow kOptionTable[] = {
     {IEACHE_OPT(ks_xcd, "IEACHE_KS_XCD"), 0, 1, nullptr, "measurement aid: 1 = each XCD walks its own eighth of the MFMA key switch's streams (measured slower, see k_ksm_gemm)"},
     {IEACHE_OPT(ks_split_max, nullptr), 1, 64, nullptr, "workgroups the per-gate key switch may cut one gate's walk into when a launch holds a handful of gates; 1 = never"},
     {IEACHE_OPT(pack_split, nullptr), 0, 8, pow2_or_0, "hook (pack_split_ok, pack_plan.h, for the packing key that is set): waves the packing key switch's walk over K is cut into per tile; 0 = by size"},
-    {IEACHE_OPT(pack_piece_rows, nullptr), 1, 4096, nullptr, "rows of a piece of a packing call at most (whole groups; up to kPackPieceRows, pack_plan.h)"},
+    {IEACHE_OPT(pack_piece_rows, nullptr), 1, 4096, nullptr, "rows of a piece of a packing call, and of a projection (whole items of `width` rows), at most (whole groups; up to kPackPieceRows, pack_plan.h)"},
+    {IEACHE_OPT(project_split, nullptr), 0, 8, pow2_or_0, "hook (pack_split_ok for the projection key that is set, project_plan.h): waves the projection's walk over K = N t is cut into per tile; 0 = by size"},
     {IEACHE_OPT(cmux_piece_rows, nullptr), 1, 1 << 20, nullptr, "rows of a launch of a CMux call, and of the first level of a piece of a CMux tree, at most (whole items; default kCmuxPieceRows = 8192: 96 MB of tree scratch; cmux_plan.h)"},
     {IEACHE_OPT(cmux_gadget_runtime, nullptr), 0, 1, nullptr, "unstable, measurement aid: 1 = every TGSW set runs on the builds of the CMux kernels that take (l, Bgbit) as launch arguments, the key's two gadgets included"},
     {IEACHE_OPT(automaton_steps_per_launch, nullptr), 0, 4096, nullptr, "steps of an automaton per launch at most (1 = a launch per step, the hand-off a kernel boundary); 0 = every step in one launch while steps x rounds stays within kAutomatonLaunchRounds, equal chunks above (automaton_plan.h)"},

@@ -6,6 +6,7 @@
 
 #include "device_buffer.h"
 #include "pack_plan.h"
+#include "project_plan.h"
 
 namespace ieache {
 
@@ -14,7 +15,8 @@ struct PackScratch {
     dev::DeviceBuffer<char> r, digits;
 };
 
-// One per evaluator.  All methods expect the evaluator's device to be current.
+// One per evaluator and key: the packing key's, and a second one on project_params() for the projection key (section 3l).
+// All methods expect the evaluator's device to be current.
 struct Pack {
     void init(const Params& p) { p_ = p; }
     // pk [n][t][2][N] int32 on the HOST -> the byte-limb form on the device, the only form kept (the int32 key is scratch of
@@ -28,6 +30,11 @@ struct Pack {
     // one piece: `groups` groups of m rows of `stride` words (n + 1 read) -> out [groups][2][N]
     void launch(PackScratch& scratch, hipStream_t stream, const PackPlan& pl, int64_t groups, int32_t m, int32_t spread, int32_t shift,
                 const Torus32* rows, int32_t stride, Torus32* out);
+    // one piece of a projection (section 3l; project_plan.h), on an object initialised with project_params(): `items` TLWE
+    // samples tlwe [items][2][N] and the window (first, width, dest) instead of rows -> out [items][2][N]; the extracted rows
+    // are never stored (k_window_digits), the product and the placement are launch()'s.  out must not overlap tlwe.
+    void launch_window(PackScratch& scratch, hipStream_t stream, const PackPlan& pl, int64_t items, int32_t first, int32_t width, int32_t dest,
+                       const Torus32* tlwe, Torus32* out);
 
 private:
     Params p_;

@@ -22,6 +22,8 @@
 // k = 32 step + 16 (lane / 32) + byte.  K splits meet in R through integer atomic adds, order-free mod 2^32.
 // The second line is k_pack_place: 32 output words per workgroup, the m w reads of R of each cut over eight threads; it writes
 // every word of out.
+// The projection of section 3l is the same product and placement on the parameter set with n := N: its rows are the extracted
+// rows of a window of a TLWE sample, which k_window_digits turns into digits without storing them (Pack::launch_window).
 #include "pack.h"
 
 #include <hip/hip_runtime.h>
@@ -83,6 +85,55 @@ __global__ __launch_bounds__(256) void k_pack_init(const Torus32* __restrict__ r
     const uint32_t b = (uint32_t)rows[(size_t)r * stride + n];
     uint32_t* dst = R + (size_t)r * 2 * N;
     for (int32_t q = threadIdx.x; q < 2 * N; q += 256) dst[q] = q == N ? b : 0u;
+}
+
+// ---- per piece of a projection (include/ieache.h section 3l; project_plan.h): what k_pack_digits and k_pack_init do, for rows that
+// are never stored.  Row r of the piece is coefficient c = first + r % width of sample r / width, whose extracted row is
+// u[i] = A[c - i] for i <= c and -A[N + c - i] above (k_tlwe_extract's rule), u[N] = B[c]: the digits of abar = u[i] + 2^(31 - t b)
+// -- of the NEGATED word where the rule negates, not the negated digits -- go straight into the product's A layout, and
+// R_r = (0, B[c] X^0).  A workgroup owns 32 consecutive padded rows and (blockIdx.y) a share of the K steps; thread (row, w)
+// writes dword w of each of those steps of its row, so a step's store is 1 KiB contiguous.  The rows of a sample read it through the caches: it comes from memory once.  Rows past
+// the piece and k >= N t get zero digits. ----
+constexpr int kWindowRows = 32, kWindowStepParts = 16;
+__global__ __launch_bounds__(kWindowRows * 8) void k_window_digits(const Torus32* __restrict__ tlwe, uint32_t* __restrict__ dig, uint32_t* __restrict__ R,
+                                                                   int64_t nrows, int64_t rpad, int32_t N, int32_t first, int32_t width, int32_t t,
+                                                                   int32_t basebit, int32_t k_steps) {
+    const int64_t r0 = (int64_t)blockIdx.x * kWindowRows;  // < rpad by the grid: rpad is a whole number of blocks of 128 rows
+    const int32_t rr = threadIdx.x >> 3, w = threadIdx.x & 7;
+    const int64_t r = r0 + rr;
+    const bool live = r < nrows;
+    const int64_t item = live ? r / width : 0;
+    const int32_t c = first + (live ? (int32_t)(r - item * width) : 0);  // < N: first + width <= N
+    const uint32_t* A = reinterpret_cast<const uint32_t*>(tlwe) + (size_t)item * 2 * N;
+    const uint32_t prec = 1u << (31 - t * basebit), mask = (1u << basebit) - 1u;
+    const int32_t K = N * t;  // < 2^15: t < 32, N <= 1024
+    // blockIdx.y takes its share of the K steps (consecutive, together every step once: gridDim.y <= k_steps), so that a thread's
+    // chain of dependent loads stays short: 256 steps in one thread made a piece of 32 rows latency-bound
+    const int32_t s0 = (int32_t)(k_steps * blockIdx.y / gridDim.y), s1 = (int32_t)(k_steps * (blockIdx.y + 1) / gridDim.y);
+    for (int32_t s = s0; s < s1; s++) {
+        uint32_t v = 0;
+        if (live) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int32_t k = s * kPackKStep + 4 * w + e;
+                if (k < K) {
+                    const int32_t i = k / t, j = k - i * t;                        // i < N
+                    const uint32_t u = i <= c ? A[c - i] : 0u - A[N + c - i];      // indices in [0, N) either way
+                    v |= (((u + prec) >> (32 - (j + 1) * basebit)) & mask) << (8 * e);
+                }
+            }
+        }
+        dig[((size_t)s * rpad + r) * 8 + w] = v;
+    }
+    if (blockIdx.y != 0) return;  // R is written once per row
+    for (int32_t q = 0; q < kWindowRows; q++) {
+        const int64_t row = r0 + q;
+        if (row >= nrows) break;
+        const int64_t it = row / width;
+        const uint32_t b = reinterpret_cast<const uint32_t*>(tlwe)[(size_t)it * 2 * N + N + first + (int32_t)(row - it * width)];
+        uint32_t* dst = R + (size_t)row * 2 * N;
+        for (int32_t x = threadIdx.x; x < 2 * N; x += kWindowRows * 8) dst[x] = x == N ? b : 0u;
+    }
 }
 
 // ---- the product.  grid: one wave per (column block, K split, block of 128 rows), streams fastest as in k_ksm_gemm ----
@@ -234,6 +285,30 @@ void Pack::launch(PackScratch& scratch, hipStream_t stream, const PackPlan& pl, 
                        pl.ksplit, 2 * N);
     hipLaunchKernelGGL(k_pack_place, dim3((unsigned)(2 * N / kPlaceWords), (unsigned)groups), dim3(kPlaceWords * kPlaceParts), 0, stream, R,
                        reinterpret_cast<uint32_t*>(out), N, m, spread, shift);
+}
+
+void Pack::launch_window(PackScratch& scratch, hipStream_t stream, const PackPlan& pl, int64_t items, int32_t first, int32_t width, int32_t dest,
+                         const Torus32* tlwe, Torus32* out) {
+    if (!limbs_) throw std::invalid_argument("tlwe_project: no projection key set");
+    if (p_.n != p_.N) throw std::logic_error("tlwe_project: the unit was not initialised on the n := N parameter set");
+    if (const char* e = project_call_error(p_, first, width, dest)) throw std::invalid_argument(e);
+    const int64_t nrows = items * width, rpad = pack_padded_rows(nrows);
+    if (nrows <= 0) return;
+    if (!pack_split_ok(pl.k_steps, pl.ksplit) || pl.k_steps != pack_k_steps(p_, t_)) throw std::invalid_argument("tlwe_project: plan of another key");
+    if ((size_t)nrows * 2 * (size_t)p_.N * 4 > scratch.r.items() || (size_t)pl.k_steps * (size_t)rpad * kPackKStep > scratch.digits.items())
+        throw std::invalid_argument("tlwe_project: piece larger than the reserved scratch");
+    const int32_t N = p_.N, ncb = pack_col_blocks(p_);
+    const int64_t row_blocks = rpad / kPackBlockRows;
+    uint32_t* R = reinterpret_cast<uint32_t*>((char*)scratch.r);
+    uint32_t* dig = reinterpret_cast<uint32_t*>((char*)scratch.digits);
+    const int32_t step_parts = pl.k_steps < kWindowStepParts ? pl.k_steps : kWindowStepParts;
+    hipLaunchKernelGGL(k_window_digits, dim3((unsigned)(rpad / kWindowRows), (unsigned)step_parts), dim3(kWindowRows * 8), 0, stream, tlwe, dig, R, nrows,
+                       rpad, N, first, width, t_, basebit_, pl.k_steps);
+    hipLaunchKernelGGL(k_pack_gemm, dim3((unsigned)(row_blocks * ncb * pl.ksplit)), dim3(64), 0, stream,
+                       reinterpret_cast<const v4i*>((const int8_t*)*limbs_), reinterpret_cast<const v4i*>(dig), R, nrows, rpad, pl.k_steps, ncb,
+                       pl.ksplit, 2 * N);
+    hipLaunchKernelGGL(k_pack_place, dim3((unsigned)(2 * N / kPlaceWords), (unsigned)items), dim3(kPlaceWords * kPlaceParts), 0, stream, R,
+                       reinterpret_cast<uint32_t*>(out), N, width, 1, dest);
 }
 
 }  // namespace ieache

@@ -499,6 +499,45 @@ void tlwe_extract_reference(const Params& p, size_t count, const Torus32* tlwe, 
     }
 }
 
+void tlwe_project_reference(const Params& p, int32_t t, int32_t basebit, const Torus32* pk, size_t count, int32_t first, int32_t width, int32_t dest,
+                            const Torus32* in, Torus32* out) {
+    Params q = p;
+    q.n = p.N;  // the packing key switch whose source key is the ring key
+    const size_t N = (size_t)p.N, W = 2 * N;
+    std::vector<Torus32> u((size_t)width * (N + 1));
+    for (size_t i = 0; i < count; i++) {
+        for (int32_t c = 0; c < width; c++) {
+            const int32_t coef = first + c;
+            tlwe_extract_reference(p, 1, in + i * W, &coef, u.data() + (size_t)c * (N + 1));
+        }
+        pack_reference(q, t, basebit, pk, 1, width, 1, dest, u.data(), out + i * W);
+    }
+}
+
+void lut_write_coef_reference(const Params& p, const Torus32* set, size_t n_set, int32_t t, int32_t basebit, const Torus32* pk, size_t count,
+                              int32_t depth, int32_t steps, int32_t width, int32_t unit, const int32_t* sel_of, const Torus32* fresh, const Torus32* mem,
+                              Torus32* out) {
+    const size_t W = (size_t)2 * p.N, stride = (size_t)depth + (size_t)steps;
+    std::vector<int32_t> toward(steps), back(steps), tree_sel(count * (size_t)depth), own(count);
+    for (int32_t s = 0; s < steps; s++) {
+        back[s] = (int32_t)(((size_t)unit << s) & (W - 1));
+        toward[s] = (int32_t)((W - (size_t)back[s]) & (W - 1));
+    }
+    for (size_t i = 0; i < count; i++) {
+        own[i] = (int32_t)i;
+        for (size_t k = 0; k < (size_t)depth; k++) {
+            const size_t at = i * stride + (size_t)steps + k;
+            tree_sel[i * (size_t)depth + k] = sel_of ? sel_of[at] : (int32_t)(at % n_set);
+        }
+    }
+    std::vector<Torus32> rows(count * W), old(count * W);
+    lut_tree_reference(p, set, n_set, count, depth, tree_sel.data(), mem, own.data(), rows.data());
+    rotate_rows(p, set, n_set, count, steps, stride, sel_of, toward.data(), rows.data(), rows.data());
+    tlwe_project_reference(p, t, basebit, pk, count, 0, width, 0, rows.data(), old.data());
+    for (size_t c = 0; c < count * W; c++) old[c] = (Torus32)((uint32_t)fresh[c] - (uint32_t)old[c]);  // delta, in place over old
+    lut_add_reference(p, set, n_set, count, depth, steps, sel_of, back.data(), old.data(), mem, count, own.data(), out);
+}
+
 void keygen(const Params& p, const uint32_t* seed_words, int nseed, SecretKeyData* out,
             bool with_cloud) {
     out->p = p;

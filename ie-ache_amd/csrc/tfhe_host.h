@@ -114,6 +114,19 @@ void automaton_reference(const Params& p, const Torus32* set, size_t n_set, int3
 // coefficient coef_of[r] (null: 0; checked by the caller) of tlwe [count][2][N] as extracted rows u [count][N+1]
 void tlwe_extract_reference(const Params& p, size_t count, const Torus32* tlwe, const int32_t* coef_of, Torus32* u);
 
+// The projection and the replace write of a window (include/ieache.h section 3l), the references above composed; the caller has
+// checked the decomposition, the window and the scalars (project_plan.h) and the indices.  tlwe_project_reference: per sample
+// tlwe_extract_reference of coefficients first .. first + width - 1, then pack_reference on the parameter set with n := N
+// (pk [N][t][2][N], the projection key) as one group of `width` rows, spread 1, shift dest -> out [count][2][N], not `in`.
+// lut_write_coef_reference: old_i = the tree over item i's own memory by selectors steps .. steps+depth-1, rotated by selectors
+// 0 .. steps-1 with amounts 2N - unit 2^t and projected onto (0, width, 0); delta_i = fresh_i - old_i; out = lut_add_reference of
+// delta with amounts +unit 2^t, memory i for item i.  mem and out [count][2^depth][2][N]; out may be mem itself.
+void tlwe_project_reference(const Params& p, int32_t t, int32_t basebit, const Torus32* pk, size_t count, int32_t first, int32_t width, int32_t dest,
+                            const Torus32* in, Torus32* out);
+void lut_write_coef_reference(const Params& p, const Torus32* set, size_t n_set, int32_t t, int32_t basebit, const Torus32* pk, size_t count,
+                              int32_t depth, int32_t steps, int32_t width, int32_t unit, const int32_t* sel_of, const Torus32* fresh, const Torus32* mem,
+                              Torus32* out);
+
 // bootsSymEncrypt / bootsSymDecrypt on raw samples (int32[n+1]).
 void lwe_encrypt_bit(const Params& p, const int32_t* lwe_key, int bit, Rng& rng, Torus32* out);
 Torus32 lwe_phase(const Params& p, const int32_t* lwe_key, const Torus32* sample);

@@ -214,6 +214,15 @@ def lib():
     L.ieache_lut_add.argtypes = [vp, vp, C.c_size_t, C.c_int32, C.c_int32, i32p, i32p, i32p, i32p, C.c_int32, i32p, i32p, sp]
     L.ieache_lut_add_device.argtypes = [vp, vp, C.c_size_t, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, vp, sp]
     L.ieache_lut_add_reference.argtypes = [pp, i32p, C.c_size_t, C.c_size_t, C.c_int32, C.c_int32, i32p, i32p, i32p, i32p, C.c_int32, i32p, i32p]
+    L.ieache_ctx_set_projection_key.argtypes = [vp, C.c_int32, C.c_int32, i32p]
+    L.ieache_debug_project_plan.argtypes = [vp, C.c_size_t, C.c_int32, C.POINTER(C.c_int64)]
+    L.ieache_tlwe_project.argtypes = [vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, i32p, i32p, sp]
+    L.ieache_tlwe_project_device.argtypes = [vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, vp, vp, sp]
+    L.ieache_tlwe_project_reference.argtypes = [pp, C.c_int32, C.c_int32, i32p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, i32p, i32p]
+    L.ieache_lut_write_coef.argtypes = [vp, vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p, i32p, i32p, i32p, sp]
+    L.ieache_lut_write_coef_device.argtypes = [vp, vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, sp]
+    L.ieache_lut_write_coef_reference.argtypes = [pp, i32p, C.c_size_t, C.c_int32, C.c_int32, i32p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32,
+                                                  C.c_int32, i32p, i32p, i32p, i32p]
     L.ieache_automaton_create.restype = vp
     L.ieache_automaton_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, i32p, i32p]
     L.ieache_automaton_free.restype = None
@@ -1125,6 +1134,60 @@ class Context:
     def pack_device(self, groups, m, spread, shift, d_rows, d_out, stats=None):
         """Device pointers (ints): d_rows [groups m] rows of lwe_stride, d_out [groups][2][N] packed."""
         check(lib().ieache_pack_device(self.h, groups, int(m), int(spread), int(shift), C.c_void_p(d_rows), C.c_void_p(d_out), _stats_ref(stats)))
+
+    def set_projection_key(self, pk, t=8, basebit=2):
+        """The projection key [N][t][2][N] (tools.projection_keygen) for tlwe_project() and lut_write_coef(): replaces an earlier
+        one; pk=None drops it.  Independent of the packing key."""
+        if pk is None:
+            check(lib().ieache_ctx_set_projection_key(self.h, 0, 0, None))
+            return
+        pk = np.ascontiguousarray(pk, dtype=np.int32)
+        if int(t) >= 1 and pk.size != self.params.N * int(t) * 2 * self.params.N:  # (t < 1: the library refuses it)
+            raise ValueError("projection key: expected [N][t][2][N] = %d words, got %d" % (self.params.N * t * 2 * self.params.N, pk.size))
+        check(lib().ieache_ctx_set_projection_key(self.h, int(t), int(basebit), _i32(pk)))
+
+    def tlwe_project(self, tlwe, first=0, width=1, dest=0, stats=None):
+        """The projection on host rows (include/ieache.h section 3l): TLWE samples [count][2][N] (or one [2][N]) -> samples
+        [count][2][N] that carry the phase of coefficients first .. first + width - 1 at dest .. (negacyclic, dest in [0, 2N))
+        and zero elsewhere, plus the key switch's noise."""
+        tlwe = np.ascontiguousarray(tlwe, dtype=np.int32).reshape(-1, 2, self.params.N)
+        out = np.zeros_like(tlwe)
+        check(lib().ieache_tlwe_project(self.h, tlwe.shape[0], int(first), int(width), int(dest), _i32(tlwe), _i32(out), _stats_ref(stats)))
+        return out
+
+    def tlwe_project_device(self, count, first, width, dest, d_in, d_out, stats=None):
+        """Device pointers (ints): d_in and d_out [count][2][N] packed; no overlap of the two is accepted."""
+        check(lib().ieache_tlwe_project_device(self.h, count, int(first), int(width), int(dest), C.c_void_p(d_in), C.c_void_p(d_out), _stats_ref(stats)))
+
+    def project_plan(self, count, width):
+        """How tlwe_project() would cut such a call under the options as they are (csrc/project_plan.h): dict(pieces,
+        items_per_piece, k_split, k_steps)."""
+        out = (C.c_int64 * 4)()
+        check(lib().ieache_debug_project_plan(self.h, count, int(width), out))
+        return dict(zip(("pieces", "items_per_piece", "k_split", "k_steps"), (int(v) for v in out)))
+
+    def lut_write_coef(self, tgsw, mem, depth, steps, new, width=1, unit=None, sel_of=None, stats=None):
+        """The replace write of a window on host arrays (include/ieache.h section 3l):
+        mem[i][hi_i].coef[lo_i unit .. lo_i unit + width) := new[i].coef[0 .. width).  mem [count][2^depth][2][N], new [count][2][N]
+        with nothing outside its first `width` coefficients; sel_of [count][steps + depth], the `steps` LOW address bits first
+        (None: samples i (steps + depth) + t mod n); unit defaults to width; width <= unit, unit 2^steps <= N -> the new memory."""
+        depth, steps, width = int(depth), int(steps), int(width)
+        unit = width if unit is None else int(unit)
+        mem = np.ascontiguousarray(mem, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, self.params.N)
+        new = np.ascontiguousarray(new, dtype=np.int32).reshape(-1, 2, self.params.N)
+        count = mem.shape[0]
+        of = _opt_i32(sel_of, -1, max(depth + steps, 1))
+        assert new.shape[0] == count and (of is None or depth + steps < 1 or of.shape[0] == count)
+        out = np.zeros_like(mem)
+        check(lib().ieache_lut_write_coef(self.h, tgsw.h, count, depth, steps, width, unit, _opt(of), _i32(new), _i32(mem), _i32(out),
+                                          _stats_ref(stats)))
+        return out
+
+    def lut_write_coef_device(self, tgsw, count, depth, steps, width, unit, d_sel_of, d_new, d_mem, d_out, stats=None):
+        """Device pointers (ints; d_sel_of may be None / 0): new [count][2][N], mem and out [count][2^depth][2][N] packed;
+        d_out == d_mem writes in place."""
+        check(lib().ieache_lut_write_coef_device(self.h, tgsw.h, count, int(depth), int(steps), int(width), int(unit), _dev(d_sel_of),
+                                                 C.c_void_p(d_new), C.c_void_p(d_mem), C.c_void_p(d_out), _stats_ref(stats)))
 
     def pbs_multi(self, x, test_polys, factors, poly_of=None, bias=None, keyswitch=True, stats=None, tlwe=False):
         """Multi-output programmable bootstrap on host rows: ONE blind rotation per row of x [count][n+1], as pbs does it, and

@@ -127,6 +127,47 @@ def pack_reference(params, pk, rows, m=None, spread=1, shift=0, t=8, basebit=2):
     return out
 
 
+def projection_params(params):
+    """The parameter set on which the projection is the packing key switch: n := N (the source key is the ring key)."""
+    return params.copy(n=params.N)
+
+
+def projection_keygen(params, tlwe_key, t=8, basebit=2, alpha=None, seed=0):
+    """The projection key [N][t][2][N] for Context.set_projection_key: packing_keygen on projection_params(params) with the ring
+    key's N words as the source key (include/ieache.h section 3l).  Needs the ring key only."""
+    return packing_keygen(projection_params(params), tlwe_key, tlwe_key, t=t, basebit=basebit, alpha=alpha, seed=seed)
+
+
+def tlwe_project_reference(params, pk, tlwe, first=0, width=1, dest=0, t=8, basebit=2):
+    """CPU reference of Context.tlwe_project on raw arrays (ieache_tlwe_project_reference: the references of tlwe_extract and
+    pack composed; no GPU, any supported set): pk [N][t][2][N], tlwe [count][2][N] (or one) -> [count][2][N]."""
+    pk = np.ascontiguousarray(pk, dtype=np.int32)
+    tlwe = np.ascontiguousarray(tlwe, dtype=np.int32).reshape(-1, 2, params.N)
+    out = np.zeros_like(tlwe)
+    check(lib().ieache_tlwe_project_reference(C.byref(params), int(t), int(basebit), _i32(pk), tlwe.shape[0], int(first), int(width), int(dest),
+                                              _i32(tlwe), _i32(out)))
+    return out
+
+
+def lut_write_coef_reference(params, samples, pk, mem, depth, steps, new, width=1, unit=None, sel_of=None, t=8, basebit=2):
+    """CPU reference of Context.lut_write_coef on raw arrays (ieache_lut_write_coef_reference: the references of lut_tree,
+    tlwe_rotate, tlwe_project and lut_add composed), arguments as there; pk [N][t][2][N] or None (refused: no key)."""
+    depth, steps, width = int(depth), int(steps), int(width)
+    unit = width if unit is None else int(unit)
+    kpl = (params.k + 1) * params.l
+    samples = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, kpl, 2, params.N)
+    pk = None if pk is None else np.ascontiguousarray(pk, dtype=np.int32)
+    mem = np.ascontiguousarray(mem, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, params.N)
+    new = np.ascontiguousarray(new, dtype=np.int32).reshape(-1, 2, params.N)
+    count = mem.shape[0]
+    of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(depth + steps, 1))
+    assert new.shape[0] == count and (of is None or depth + steps < 1 or of.shape[0] == count)
+    out = np.zeros_like(mem)
+    check(lib().ieache_lut_write_coef_reference(C.byref(params), _i32(samples), samples.shape[0], int(t), int(basebit), None if pk is None else _i32(pk),
+                                                count, depth, steps, width, unit, None if of is None else _i32(of), _i32(new), _i32(mem), _i32(out)))
+    return out
+
+
 def lut_pack_layout(params, entries):
     """(spread, shift) with which Context.pack of `entries` encrypted table entries f[e] gives an encryption of exactly
     lut_test_poly(f): a table for Context.pbs(..., tlwe=True) built from encrypted results.  2 entries must divide N."""

@@ -880,7 +880,7 @@ int ieache_lut_scatter_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t co
  * reserved with the tree's scratch ahead of the loop.  stats: levels = depth + steps, chunks = pieces, the tree's, the
  * rotation's and the extraction's launches in blind_rotate_launches, the key switch's in keyswitch_launches.  Refusals as for
  * ieache_lut_tree and ieache_tlwe_rotate, coef outside [0, N) (host form; the device form clamps), an unknown flag.
- * No group form, no cloudd verb, no replace-write of a single coefficient, no other rings, no one-limb form. */
+ * No group form, no cloudd verb, no other rings, no one-limb form; the replace write of single coefficients is section 3l. */
 #define IEACHE_ROTATE_MAX_STEPS 64
 #define IEACHE_LUT_READ_NO_KEYSWITCH 1
 int ieache_tlwe_rotate(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t steps, const int32_t* sel_of /*[count][steps] or NULL*/,
@@ -958,7 +958,7 @@ int ieache_lut_write_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t coun
  * IEACHE_EINVAL: depth, steps or n_mems out of range, overlap, a set prepared on another context, a host pointer to a device
  * form.  stats: bootstraps == 0, keyswitch_launches == 0, levels = depth + steps, chunks = pieces, blind_rotate_launches =
  * pieces x ((steps > 0 ? 1 : 0) + max(depth, 1)); the initialising copy or fill and the small index pass are not counted.
- * No group form, no cloudd verb, no replace-write of a single coefficient, no other rings, no one-limb form. */
+ * No group form, no cloudd verb, no other rings, no one-limb form; the replace write of single coefficients is section 3l. */
 int ieache_lut_add(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps,
                    const int32_t* sel_of /*[count][steps+depth] or NULL*/, const int32_t* amount_of /*[steps] or NULL*/,
                    const int32_t* values /*[count][2][N]*/, const int32_t* mems /*[n_mems][2^depth][2][N] or NULL*/, int32_t n_mems,
@@ -1023,6 +1023,73 @@ int ieache_automaton_run_device(ieache_ctx* ctx, const ieache_tgsw* set, const i
                                 const int32_t* d_finals, int32_t n_finals, const int32_t* d_final_of, int32_t* d_out, ieache_stats* stats);
 int ieache_debug_automaton_plan(const ieache_ctx* ctx, const ieache_automaton* a, size_t count, int64_t out[5]);
 
+/* 3l. The TLWE projection, and the replace write of single coefficients of an encrypted memory.
+ *
+ * The projection is a public functional key switch with f = projection onto a window of coefficients: out carries the phase of
+ * coefficients first .. first + width - 1 of a TLWE sample at dest .. dest + width - 1 (negacyclic) and ZERO everywhere else,
+ * plus the key switch's noise.  It is section 3e's packing key switch on the parameter set with n := N and the ring key as its
+ * source key -- the extracted key of a TLWE sample is the ring key itself -- so every definition is one that exists:
+ *
+ * Projection key PK' [N][t][2][N] int32: ieache_packing_keygen for the parameter set with n := N, given the ring key's N words
+ * as its "LWE key" (ieache_amd.tools.projection_keygen).  ieache_ctx_set_projection_key takes it from HOST memory and keeps only
+ * the byte-limb device form (67 MB at t = 8); it replaces and drops exactly as ieache_ctx_set_packing_key does, refuses the
+ * decompositions section 3e refuses on that parameter set, and is independent of the packing key: a context may hold both.
+ *
+ * ieache_tlwe_project: the window (first in [0, N), width >= 1 with first + width <= N, dest in [0, 2N)) is public and shared by
+ * the call.  Word for word, for item i:
+ *   u_q    = ieache_tlwe_extract(in[i], coef = first + q),  q < width                       (N + 1 words each)
+ *   out[i] = ieache_pack_reference(p', PK', groups = 1, m = width, spread = 1, shift = dest, rows = u_0 .. u_{width-1})
+ * An integer definition, the same words in any order of summation; nothing is rounded, guarded or audited.  On the device the
+ * extracted rows (count x width x 4 KB) are never stored: one kernel writes their digits and R = (0, B[first + q] X^0) from the
+ * samples, then section 3e's product (K = N t) and placement run unchanged.  The digit of an entry -A[.] is the digit of the
+ * negated word, not the negated digit.  Pieces are whole items with items x width rows within "pack_piece_rows";
+ * "project_split" forces the product's K split as "pack_split" does (a new key resets it); ieache_debug_project_plan reports
+ * {pieces, items per piece, K split, K steps}.  Scratch is reserved before the loop: a warm call allocates nothing.  Device
+ * form: d_in, d_out [count][2][N] packed, ANY overlap of d_out with d_in refused.  stats as ieache_pack: bootstraps == 0,
+ * levels == 1, keyswitch_launches == chunks == pieces.  count == 0 is a no-op.  IEACHE_EINVAL with text: no projection key set; a
+ * window out of range; a host pointer to the device form.
+ *
+ * ieache_lut_write_coef is the replace write  mem[i][hi_i].coef[lo_i unit .. lo_i unit + width) := new[i].coef[0 .. width).
+ * Memories are per item as in ieache_lut_write, [count][2^depth][2][N]; sel_of is [count][steps + depth] laid out as for
+ * ieache_lut_read and ieache_lut_add (the `steps` LOW address bits first; NULL: that index mod n); width <= unit and
+ * unit 2^steps <= N (the Python forms default unit to width).  Each step is an existing definition:
+ *   (1) r_i     = ieache_lut_tree over mem[i] by the high selectors;
+ *   (2) r_i    <- ieache_tlwe_rotate by the low selectors with the amounts (2N - unit 2^t) mod 2N;
+ *   (3) old_i   = ieache_tlwe_project(r_i, first 0, width, dest 0);
+ *   (4) delta_i = new[i] - old_i mod 2^32, on all 2N words;
+ *   (5) out     = ieache_lut_add(values = delta, depth, steps, amounts +unit 2^t, mems = mem, n_mems = count, mem_of[i] = i).
+ * `new` must carry NOTHING outside its first `width` coefficients -- an ieache_pack result, a client's encryption, an
+ * ieache_tlwe_project result; the call does not project it.  The written window ends as new's phase plus the noise of one read
+ * path, one projection and one write path (the old content's own noise cancels); every other coefficient and slot takes one
+ * ieache_lut_add's noise.  depth = steps = 0 gives mem + new - project(mem).
+ * The device form runs on the context's stream with no host round trip; step (4) is a small pass of its own.  It is cut into the
+ * tree's pieces for (count, depth), the projection in runs of its own plan inside a piece; a piece reads and adds into its own
+ * items' memories only, so d_out == d_mem EXACTLY is the write in place, and any other overlap is refused; with distinct buffers
+ * d_out starts as a copy of d_mem.  A warm call allocates nothing.  Any set section 3i admits.  Host form: every selector
+ * checked and the first bad one named; device form: clamped / mod n.  stats: bootstraps == 0, levels = 2 (depth + steps) + 1,
+ * chunks = pieces, keyswitch_launches = the projection's runs (pieces while a piece's items x width fit "pack_piece_rows"),
+ * blind_rotate_launches = pieces x (2 max(depth, 1) + 2 (steps > 0 ? 1 : 0) + 1): the tree (a copy at depth 0), the two
+ * rotations, the subtraction and the scatter; the small index passes and the initialising copy are not counted.
+ * IEACHE_EINVAL: no projection key set; depth, steps outside their ranges; width < 1; unit < width; unit 2^steps > N; overlap; a set
+ * of another context; a host pointer to the device form.
+ * Not here: a word read for the gates, projecting `new`, several items replacing into ONE memory (two at one address would both
+ * subtract the old value), a group form, a cloudd verb, a key-file format; the tree, rotation and scatter cover N = 1024 only,
+ * the projection alone any supported set. */
+int ieache_ctx_set_projection_key(ieache_ctx* ctx, int32_t pk_t, int32_t pk_basebit, const int32_t* pk /*host [N][t][2][N]*/);
+int ieache_debug_project_plan(const ieache_ctx* ctx, size_t count, int32_t width, int64_t out[4]);
+int ieache_tlwe_project(ieache_ctx* ctx, size_t count, int32_t first, int32_t width, int32_t dest, const int32_t* in /*[count][2][N]*/,
+                        int32_t* out /*[count][2][N]*/, ieache_stats* stats);
+int ieache_tlwe_project_device(ieache_ctx* ctx, size_t count, int32_t first, int32_t width, int32_t dest, const int32_t* d_in, int32_t* d_out,
+                               ieache_stats* stats);
+/* (The ieache_lut_write_coef declarations are spelled with `extern`, which changes nothing for a C or C++ caller: it sets them
+ * apart from section 3i's ieache_lut_write family, whose declarations tests/test_gadget_cpu.py enumerates by that prefix.) */
+extern int ieache_lut_write_coef(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit,
+                                 const int32_t* sel_of /*[count][steps+depth] or NULL*/, const int32_t* fresh /*new: [count][2][N]*/,
+                                 const int32_t* mem /*[count][2^depth][2][N]*/, int32_t* out /*[count][2^depth][2][N]*/, ieache_stats* stats);
+extern int ieache_lut_write_coef_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit,
+                                 const int32_t* d_sel_of, const int32_t* d_new, const int32_t* d_mem, int32_t* d_out /* == d_mem: in place */,
+                                 ieache_stats* stats);
+
 /* ------------------------------------------------------------------ *
  * 4. CPU tools around the path (no GPU): what Keygen/keygen.c:22-51,  *
  *    Client1/alice.c:116-191 and Output/verif.c:41-76 get from        *
@@ -1066,6 +1133,15 @@ int ieache_packing_keygen(const ieache_params* p, const int32_t* lwe_key, const 
  * The refusals of the decomposition and of (m, spread, shift) are those of section 3e. */
 int ieache_pack_reference(const ieache_params* p, int32_t pk_t, int32_t pk_basebit, const int32_t* pk, size_t groups, int32_t m,
                           int32_t spread, int32_t shift, const int32_t* rows /*[groups*m][n+1]*/, int32_t* out /*[groups][2][N]*/);
+/* CPU references of section 3l on raw arrays, no GPU, no context, any supported set: the references of ieache_tlwe_extract and
+ * ieache_pack composed, and those of ieache_lut_tree, ieache_tlwe_rotate, the projection and ieache_lut_add composed.
+ * pk [N][pk_t][2][N] is the projection key; refusals as in section 3l (the write also names the first bad selector). */
+int ieache_tlwe_project_reference(const ieache_params* p, int32_t pk_t, int32_t pk_basebit, const int32_t* pk, size_t count, int32_t first,
+                                  int32_t width, int32_t dest, const int32_t* in /*[count][2][N]*/, int32_t* out /*[count][2][N]*/);
+extern int ieache_lut_write_coef_reference(const ieache_params* p, const int32_t* set /*[n][2l][2][N]*/, size_t n, int32_t pk_t, int32_t pk_basebit,
+                                    const int32_t* pk, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit,
+                                    const int32_t* sel_of /*[count][steps+depth] or NULL*/, const int32_t* fresh /*[count][2][N]*/,
+                                    const int32_t* mem /*[count][2^depth][2][N]*/, int32_t* out /*[count][2^depth][2][N]*/);
 /* TGSW samples of section 3f, made by whoever holds the ring key: out [count][2l][2][N], sample i of the int32 message mu[i]
  * (selector bits: 0 or 1), through the routine key generation makes BK_i with -- 2l rows of ieache_tlwe_encrypt's zero
  * encryption one after another from one generator, then the gadget (existing keys and their draw order are unchanged).
