@@ -8,7 +8,7 @@ from .evaluator import (  # noqa: F401
     GATE_AND, GATE_XOR, GATE_OR, GATE_NAND, GATE_MUX, circ_chain,
     GATE_NOR, GATE_XNOR, GATE_ANDNY, GATE_ANDYN, GATE_ORNY, GATE_ORYN, GATE_TYPES, FALSE, TRUE, NOT, Netlist, CompiledNetlist,
     CircuitInfo, Context, IeacheError, Params, Stats, build_library, circuit_info, circuit_level_cap, circuit_simulate,
-    default_params, device_count, lib, library_path,
+    default_params, device_count, debug_forward_path, lib, library_path,
     GATE_MAJ3, GATE_XOR3, CIRC_ADD_FA, CIRC_SUB_FA, CIRC_RSUB_FA, CIRC_MUL_FA, circuit_gate_count,
     PBS_NO_KEYSWITCH, PBS_TLWE_POLYS, PBS_ACCUMULATOR, PBS_MULTI_MAX_FACTORS, Group, GROUP_MAX_DEVICES, Job,
     TgswSet, Automaton, AUTOMATON_MAX_STATES, AUTOMATON_MAX_STEPS, automaton_tables, LUT_TREE_MAX_DEPTH, ROTATE_MAX_STEPS, LUT_READ_NO_KEYSWITCH,

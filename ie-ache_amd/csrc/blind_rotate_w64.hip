@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "br_step.h"
+#include "fft_probe.h"
 #include "mix_plan.h"
 
 namespace ieache {
@@ -298,21 +299,31 @@ __global__ __launch_bounds__(128, 2) void k_blind_rotate_w2(DevKeys K, const dou
 //   * (X^a - 1) acc + offset is formed as (rot ^ m) + ((offset - acc_j) - m)  (v_xad_u32);
 //   * BK_i through buffer loads: the first block of a row requested inside its forward transform, once the first twiddle
 //     set's 32 registers are free (fft512_forward's MID hook), the second behind the transform;
-//   * six of the seven second inter-pass twiddles resident in 24 VGPRs for the whole kernel (LaneRootsResident, fft512.h): a
-//     transform reads 9 twiddles from the LDS table instead of 15.  All seven do not fit: the <3,7> builds then spill 5 VGPRs;
+//   * second inter-pass twiddles resident for the whole kernel (fft512.h): the four odd ones, signed, for the forward
+//     transforms (XLANE = 2 below: a forward transform reads 11 twiddles from the LDS table instead of 15), or six of the
+//     seven for both directions (XLANE = 1: 9 instead of 15; all seven do not fit: the <3,7> builds then spill 5 VGPRs);
 //   * the unrotated operands of a decomposition are read back from LDS, which the compiler pairs as ds_read2st64_b32;
 //     carrying polynomial 0's from the update (ds_add_rtn_u32) measured within noise and is not kept;
 //   * the rounding guard's running maximum between steps is a float (what is published; rounding is monotone, so the
 //     figure is the same), and the epilogue forms its addresses again instead of sharing the prologue's: with these the
-//     kernel holds 256 VGPRs without scratch.  303 LDS instructions per step against 345 (profiles/lds_trim_isa_mix.txt);
+//     kernel holds 256 VGPRs without scratch;
 //   * the forward transforms' lane-high transpose cross-lane, every other transpose through the gate's padded LDS tile; the
 //     two inverse transforms interleaved through that one tile; ds_add_u32 update;
+//   * XLANE = 2: that transpose in the exchange form (fft512.h): lane bit 3 at one v_mov_b32_dpp per dword instead of two
+//     v_cndmask_b32_dpp, 96 vector instructions fewer per step (3 143 -> 3 047, profiles/xlane3_isa_mix.txt).  A lane then
+//     gathers the inputs of the relabelled position xl_pi(lane) -- the decomposition reads through `plane`, the update behind
+//     the inverse transforms stays in the lanes' own order -- and holds two signed cosines, a second table base and a second
+//     tile base across the step loop.  For those registers only the four ODD second twiddles are resident (LaneRootsExchange,
+//     16 VGPRs), with the form's per-lane sign, so the inverse pair reads the whole set from the table: 321 LDS instructions
+//     per step against 303, and every ds_read_b32 of the decomposition is a 2-way bank conflict (lanes l and l ^ 8 gather
+//     dwords 32 apart).  Still +1.6 % (profiles/xlane3_ab.txt).  With one even entry resident as well the <3,7> builds spill
+//     6 VGPRs.  XLANE = 1: v_cndmask_b32_dpp pairs and six resident twiddles (LaneRootsResident), the form before;
 //   * GUARD = 2 watches ONE rounded coefficient in four (registers r = 0 and r = 4 of both output polynomials), 1 every one,
 //     0 none (measurement only); DIAG: s_memtime phase stamps on stderr (br_variant 49).
 // Measured and dropped (profiles/r3_w1_ab.txt; source in git history, see attic/README.md): software-pipelined rows, both
 // forward transposes cross-lane, twiddles through the buffer path, an L2 prefetch of the next step's BK blocks.
 // dynamic LDS: acc [4][2][1024] int32 | sT [4][kTile] double2 | tw [kTwElems] double2          (78 848 B -> 2 per CU)
-template <int L, int BGBIT, int GUARD, bool DIAG = false, int G = kW1Gates>
+template <int L, int BGBIT, int GUARD, bool DIAG = false, int G = kW1Gates, int XLANE = 2>
 __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_w1b(DevKeys K, const double2* __restrict__ bkf1,
                                                                        const uint16_t* __restrict__ st_bara, int32_t nb,
                                                                        int32_t* st_acc, int64_t items, int32_t i0, int32_t i1,
@@ -327,10 +338,15 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_w1b(DevKeys K, const
     double2* sT = sT_all + wave * kTile;
     int32_t* acc = acc_all + wave * 2 * kN;
     const int64_t item = (int64_t)blockIdx.x * G + wave;
+    static_assert(XLANE == 1 || XLANE == 2, "the forward transforms' lane-high transpose: v_cndmask pairs (1) or the exchange form (2)");
+    using Roots = typename std::conditional<XLANE == 2, LaneRootsExchange, LaneRootsResident>::type;
     load_twiddles(sTw, gtw, tid, 64 * G);
     __syncthreads();  // the only workgroup barrier
     if (item >= items) return;
-    const LaneRootsResident R = make_roots<LaneRootsResident>(sTw, lane);  // second twiddle set: 24 VGPRs for the whole kernel
+    const Roots R = make_roots<Roots>(sTw, lane);  // resident second twiddles: 16 VGPRs (XLANE = 2) or 24 for the whole kernel
+    // the position whose inputs this lane gathers: the exchange form takes them relabelled (tw_roots.h); the update below, behind
+    // the inverse transforms, is in the lanes' own order either way
+    const int plane = XLANE == 2 ? xl_pi(lane) : lane;
     const uint16_t* __restrict__ bara = st_bara + (size_t)item * nb;
     int32_t* gacc = st_acc + (size_t)item * 2 * kN;
     {
@@ -366,10 +382,10 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_w1b(DevKeys K, const
         uint32_t v0[8], v1[8];
         double dev_max = 0.0;  // of this step
         // byte offset of coefficient (lane - a) in the 2N-ring [acc, -acc]: bits 2..11 address, bit 12 = negate
-        const uint32_t jb4 = ((uint32_t)(lane - a) & (2 * kN - 1)) << 2;
+        const uint32_t jb4 = ((uint32_t)(plane - a) & (2 * kN - 1)) << 2;
         auto decompose = [&](const uint32_t pb) {
             const int32_t* accp = reinterpret_cast<const int32_t*>(accb + pb);
-            decompose_rotated(v0, v1, accb, accp, pb, jb4, lane, dec_offset);
+            decompose_rotated(v0, v1, accb, accp, pb, jb4, plane, dec_offset);
         };
         auto digit_row = [&](const int sh, const int brow, auto first) {
             constexpr bool FIRST = decltype(first)::value;
@@ -380,7 +396,7 @@ __global__ __launch_bounds__(64 * G, 2) void k_blind_rotate_w1b(DevKeys K, const
             digits_to_double2<BGBIT>(x, v0, v1, sh);
             __builtin_amdgcn_sched_barrier(0);
             stamp_phase<DIAG>(tsum, tlast, 1);
-            fft512_forward<true, 1>(x, sT, lane, R, request_a);
+            fft512_forward<true, XLANE>(x, sT, lane, R, request_a);
             stamp_phase<DIAG>(tsum, tlast, 2);
             load_bk_block(bB, bk_rsrc, lane16, brow + kRowBytes / 2);
             __builtin_amdgcn_sched_barrier(0);
@@ -1163,15 +1179,20 @@ template <class T>
 struct as_is {
     using type = T;
 };
+// `grant`: the opt-in of this kernel; a row's own unless the row launches a second build (go_w1b)
 template <class PS, class... P>
-static void launch_row(PS, const LaunchRow& v, const Slice& s, void (*kernel)(P...), typename as_is<P>::type... args) {
+static void launch_row_granted(PS, const LaunchRow& v, const Slice& s, LdsGrant& grant, void (*kernel)(P...), typename as_is<P>::type... args) {
     if (v.allow) {
         char what[96];  // the instantiation, for the message of a refused opt-in
         snprintf(what, sizeof what, "%s<%d,%d> (br_variant %d, %d gates per workgroup)", br_variant(v.number)->name, PS::L, PS::BGBIT, (int)v.number, v.gates);
-        allow_dynamic_lds_once(granted(v, PS::index), (const void*)kernel, v.allow, what);
+        allow_dynamic_lds_once(grant, (const void*)kernel, v.allow, what);
     }
     hipLaunchKernelGGL(kernel, dim3((unsigned)((s.items + v.gates - 1) / v.gates)), dim3(v.threads == kTwoLWaves ? 128 * PS::L : v.threads),
                        v.lds(PS::L, s.nb, v.gates), s.stream, args...);
+}
+template <class PS, class... P>
+static void launch_row(PS ps, const LaunchRow& v, const Slice& s, void (*kernel)(P...), typename as_is<P>::type... args) {
+    launch_row_granted(ps, v, s, granted(v, PS::index), kernel, args...);
 }
 // one launcher per kernel (their argument lists differ), instantiated for both parameter sets
 template <int XLANE>
@@ -1193,10 +1214,22 @@ static void go_wide(const LaunchRow& v, const Slice& s) {
                    s.i0, s.i1, s.ext, DIAG ? s.t.diag : nullptr, s.t.twiddles, LIMBS == 2 ? nullptr : s.t.guard);
     });
 }
+// The forward transforms' lane-high transpose takes the exchange form (XLANE = 2: +1.6 %, profiles/xlane3_ab.txt) but in the
+// stamped l = 2 build, which does not hold it without scratch.  The default-guard builds have the v_cndmask form (1) beside
+// them, as the partner of an A/B and of tests/test_xlane_exchange_gpu.py, launched while probe::w1b_forward_path() says so.
 template <int GUARD, bool DIAG = false, int G = kW1Gates>
 static void go_w1b(const LaunchRow& v, const Slice& s) {
     with_param_set(s.l, [&](auto ps) {
-        launch_row(ps, v, s, k_blind_rotate_w1b<ps.L, ps.BGBIT, GUARD, DIAG, G>, s.K, s.t.bkf1, s.st_bara, s.nb, s.st_acc, s.items, s.i0, s.i1,
+        constexpr int XL = (DIAG && ps.L == 2) ? 1 : 2;
+        if constexpr (GUARD == 2 && !DIAG) {
+            if (probe::w1b_forward_path() == 1) {
+                static LdsGrant partner;  // per instantiation: G and the parameter set
+                launch_row_granted(ps, v, s, partner, k_blind_rotate_w1b<ps.L, ps.BGBIT, GUARD, DIAG, G, 1>, s.K, s.t.bkf1, s.st_bara, s.nb, s.st_acc,
+                                   s.items, s.i0, s.i1, s.ext, s.t.guard, s.t.twiddles, nullptr);
+                return;
+            }
+        }
+        launch_row(ps, v, s, k_blind_rotate_w1b<ps.L, ps.BGBIT, GUARD, DIAG, G, XL>, s.K, s.t.bkf1, s.st_bara, s.nb, s.st_acc, s.items, s.i0, s.i1,
                    s.ext, s.t.guard, s.t.twiddles, DIAG ? s.t.diag : nullptr);
     });
 }

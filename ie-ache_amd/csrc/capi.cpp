@@ -20,6 +20,7 @@
 #include "codec.h"
 #include "daemon.h"
 #include "evaluator.h"
+#include "fft_probe.h"
 #include "group.h"
 #include "group_run.h"
 #include "mix_plan.h"
@@ -1514,6 +1515,13 @@ int ieache_debug_spectrum(ieache_ctx* ctx, int which, size_t first, size_t count
     return guarded([&] {
         if (!ctx || !out) return fail(IEACHE_EINVAL, "null argument");
         ctx->eval->debug_spectrum(which, first, count, out);
+        return 0;
+    });
+}
+
+int ieache_debug_forward_path(int xlane) {
+    return guarded([&] {
+        probe::set_w1b_forward_path(xlane);  // its refusal: std::invalid_argument -> EINVAL
         return 0;
     });
 }

@@ -31,28 +31,10 @@ __device__ __forceinline__ double2 cmulx(double2 a, double2 b) {
                 : make_double2(fma(a.x, b.x, -a.y * b.y), fma(a.x, b.y, a.y * b.x));
 }
 
-// 8-point DFT in registers, natural order in and out.  52 FP64 operations.
+// 8-point DFT in registers, natural order in and out.  52 FP64 operations (dft8_plain, dft8_twist.h).
 template <bool INV>
 __device__ __forceinline__ void dft8(double2 (&x)[8]) {
-    const double2 a0 = cadd(x[0], x[4]), a1 = cadd(x[1], x[5]), a2 = cadd(x[2], x[6]), a3 = cadd(x[3], x[7]);
-    const double2 b0 = csub(x[0], x[4]), t1 = csub(x[1], x[5]), t2 = csub(x[2], x[6]), t3 = csub(x[3], x[7]);
-    // even outputs: DFT4(a)
-    const double2 c0 = cadd(a0, a2), c1 = cadd(a1, a3), c2 = csub(a0, a2), c3 = rot90<INV>(csub(a1, a3));
-    x[0] = cadd(c0, c1);
-    x[4] = csub(c0, c1);
-    x[2] = cadd(c2, c3);
-    x[6] = csub(c2, c3);
-    // odd outputs: DFT4(b), b_j = t_j * W8^j with the 1/sqrt2 factors deferred into the last FMAs
-    const double2 b2 = rot90<INV>(t2);
-    // forward: t1*(1-i), t3*(-1-i) ; inverse: t1*(1+i), t3*(-1+i)
-    const double2 b1 = INV ? make_double2(t1.x - t1.y, t1.x + t1.y) : make_double2(t1.x + t1.y, t1.y - t1.x);
-    const double2 b3 = INV ? make_double2(-t3.x - t3.y, t3.x - t3.y) : make_double2(t3.y - t3.x, -t3.x - t3.y);
-    const double2 e0 = cadd(b0, b2), e2 = csub(b0, b2);
-    const double2 s = cadd(b1, b3), d = rot90<INV>(csub(b1, b3));
-    x[1] = make_double2(fma(kR, s.x, e0.x), fma(kR, s.y, e0.y));
-    x[5] = make_double2(fma(-kR, s.x, e0.x), fma(-kR, s.y, e0.y));
-    x[3] = make_double2(fma(kR, d.x, e2.x), fma(kR, d.y, e2.y));
-    x[7] = make_double2(fma(-kR, d.x, e2.x), fma(-kR, d.y, e2.y));
+    dft8_plain<INV>(x);
 }
 
 // Orders this wave's LDS traffic without a workgroup barrier: the DS instructions of
@@ -86,12 +68,18 @@ __device__ __forceinline__ void tile_sync() {
 //   LaneRoots           every transform reads both sets from the table (15 ds_read_b128): the default, every kernel but one.
 //   LaneRootsResident   six of the seven entries of the second set, which depends on lane & 7 alone, held in 24 VGPRs for the
 //                       whole kernel, so a transform reads 9 twiddles (ds_read_b128) instead of 15.  k_blind_rotate_w1b
-//                       takes it, whose eight transforms per step keep the CU's LDS ~80 % busy; it pays with the first BK
+//                       takes it in its XLANE = 1 build (LaneRootsExchange below otherwise), whose eight transforms per step keep the CU's LDS ~80 % busy; it pays with the first BK
 //                       block of a row being requested inside the forward transform (MID hook) instead of before it.  The
 //                       seventh entry spills that kernel; both sets resident cost 60 VGPRs, which the BK prefetch needs more.
 // The transforms take the roots type as a template parameter and read the second set through R.b(k) either way.
 using LaneRoots = TableRoots<double2>;
 using LaneRootsResident = ResidentRoots<double2, 6>;
+//   LaneRootsExchange   the resident form of a kernel whose forward transforms take the exchange form (XLANE = 2): the four odd
+//                       entries resident with that form's per-lane sign -- so the inverse transforms read those from the
+//                       table -- and NEVEN of the three even ones for both directions; a lane holds two bases into the first
+//                       set and the two signed cosines of the first pass as well (tw_roots.h).
+// NEVEN = 0: with one even entry resident as well k_blind_rotate_w1b<3,7> spills 6 VGPRs, with two 10 (profiles/xlane3_isa_mix.txt)
+using LaneRootsExchange = ExchangeRoots<double2, 0>;
 __device__ __forceinline__ void build_twiddles(double2* tw, int tid, int nthreads) {
     double s, c;
     for (int idx = tid; idx < 512; idx += nthreads) {
@@ -190,6 +178,43 @@ __device__ __forceinline__ void xlane_hi(double2 (&x)[8]) {
     bitswap<5>(x);
 }
 
+// The same transpose at one move per dword for lane bit 3 (XLANE = 2 of fft512_forward; 16 + 16 + 16 instructions per transform
+// where xlane_hi takes 32 + 16 + 16).  In every exchange a lane keeps one
+// register of a pair, gives the other and receives into the slot it gave; the two v_cndmask above are needed only because WHICH
+// one is given depends on the lane.  Here lanes with bit 3 set hold the members of every pair (q, q + 4) in each other's
+// registers already (dft8_twist_fwd_signed, and their first-set twiddles read swapped), so every lane gives registers 4 .. 7 and
+// receives into them: one v_mov_b32_dpp row_ror:8 per dword, no VCC.  That pairs register bit 2 with lane bit 3, so the swap
+// instructions take register bit 0 <-> lane bit 4 and register bit 1 <-> lane bit 5, and lanes with bit 3 set come out with
+// register s holding p1 = s ^ 4 (tw_roots.h: what absorbs all of it).
+template <int B, int M>
+__device__ __forceinline__ void bitswap_reg(double2 (&x)[8]) {
+    static_assert(B == 5 || B == 4, "v_permlane32_swap / v_permlane16_swap");
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        if (r & M) continue;
+        unsigned a[4] = {(unsigned)__double2loint(x[r].x), (unsigned)__double2hiint(x[r].x), (unsigned)__double2loint(x[r].y),
+                         (unsigned)__double2hiint(x[r].y)};
+        unsigned b[4] = {(unsigned)__double2loint(x[r | M].x), (unsigned)__double2hiint(x[r | M].x), (unsigned)__double2loint(x[r | M].y),
+                         (unsigned)__double2hiint(x[r | M].y)};
+#pragma unroll
+        for (int q = 0; q < 4; q++) swap_dwords<B>(a[q], b[q]);
+        x[r] = make_double2(__hiloint2double((int)a[1], (int)a[0]), __hiloint2double((int)a[3], (int)a[2]));
+        x[r | M] = make_double2(__hiloint2double((int)b[1], (int)b[0]), __hiloint2double((int)b[3], (int)b[2]));
+    }
+}
+__device__ __forceinline__ double give_row_ror8(double v) {
+    constexpr int kRowRor8 = 0x128;  // DPP control: rotate right by 8 within each row of 16 lanes = lane ^ 8
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), kRowRor8, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), kRowRor8, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ void xlane_hi_give(double2 (&x)[8]) {
+#pragma unroll
+    for (int r = 4; r < 8; r++) x[r] = make_double2(give_row_ror8(x[r].x), give_row_ror8(x[r].y));
+    bitswap_reg<4, 1>(x);
+    bitswap_reg<5, 2>(x);
+}
+
 // Transpose tiles hold element (h, m, l) -- three 3-bit digits -- at h*72 + m*9 + l.
 // The 9/72 padding makes every ds_write_b128 / ds_read_b128 of both transposes
 // bank-conflict free AND lets each access be "per-lane base + immediate offset".
@@ -199,6 +224,13 @@ constexpr int kTile = 8 * 72;  // double2 elements per tile (9216 B)
 //   in : x[r] = y_{64r+lane}, untwisted (the first pass applies exp(i*pi*r/16), the first twiddle set the lane part tL)
 //   out: x[k2] = X[k0 + 8*k1 + 64*k2] with lane = 8*k0 + k1
 // XLANE = 1: the first (lane-high) transpose cross-lane (v_permlane*_swap / v_cndmask_b32_dpp) instead of through the tile.
+// XLANE = 2: the same at one move per dword for lane bit 3 (xlane_hi_give: 48 cross-lane instructions instead of 64), the
+//   exchange form.  It takes roots with the forward accessors fa / fb and the signed cosines (LaneRootsExchange), and
+//   in : x[r] = y_{64r + xl_pi(lane)}: the caller gathers the inputs of the relabelled position (tw_roots.h)
+//   out: as above, the same words as XLANE = 1 (tests/native/xlane_exchange_test.cpp, tests/test_xlane_exchange_gpu.py).
+//   What it costs outside the instruction count: lanes l and l ^ 8 gather dwords 32 apart, a 2-way bank conflict for every
+//   ds_read_b32 of the caller's gather, and the resident odd second-set entries are of no use to the inverse transforms.
+//   k_blind_rotate_w1b takes it all the same: +1.6 % (profiles/xlane3_ab.txt).
 // MID: called once the first inter-pass twiddles are consumed (their 32 VGPRs are free from there on) or, MID_LATE, once
 // the second set is consumed too: the place to request data the caller needs right after the transform.
 struct NoHook {
@@ -206,15 +238,22 @@ struct NoHook {
 };
 template <bool WSYNC, int XLANE = 0, class MID = NoHook, bool MID_LATE = false, class ROOTS = LaneRoots>
 __device__ __forceinline__ void fft512_forward(double2 (&x)[8], double2* sT, int lane, const ROOTS& R, MID mid = MID()) {
-    static_assert(XLANE == 0 || XLANE == 1, "lane-low transposes go through the tile");
+    static_assert(XLANE == 0 || XLANE == 1 || XLANE == 2, "lane-low transposes go through the tile");
     const int hi = lane >> 3, lo = lane & 7;
     const int own = hi * 9 + lo;   // (m, l) = (lane>>3, lane&7) inside a row-block h
-    const int blk = hi * 72 + lo;  // (h, l) = (lane>>3, lane&7)
+    // (h, l) = (k0, lane&7): k0 is lane>>3, or what lane bits 3..5 carry after the exchange form's transpose
+    const int blk = (XLANE == 2 ? xl_k0(lane) : hi) * 72 + lo;
     // twiddles are fetched from the LDS table ahead of the butterflies that hide their latency (R.b: or are resident)
     double2 tA[8], tB[8];
+    if constexpr (XLANE == 2) {
 #pragma unroll
-    for (int k = 0; k < 8; k++) tA[k] = R.a(k);
-    dft8_twist_fwd(x);                       // over r -> k0, the register part e^{i pi r/16} of the twist included
+        for (int k = 0; k < 8; k++) tA[k] = R.fa(k);
+        dft8_twist_fwd_signed(x, R.c16, R.c316);  // lanes with bit 3 set: output k0 ^ 4 in register k0
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; k++) tA[k] = R.a(k);
+        dft8_twist_fwd(x);                   // over r -> k0, the register part e^{i pi r/16} of the twist included
+    }
 #pragma unroll
     for (int k = 0; k < 8; k++) x[k] = cmulx<false>(x[k], tA[k]);  // * tL * w512^(lane*k0)
     if (!std::is_same<MID, NoHook>::value && !MID_LATE) {
@@ -222,11 +261,17 @@ __device__ __forceinline__ void fft512_forward(double2 (&x)[8], double2* sT, int
         mid();
         __builtin_amdgcn_sched_barrier(0);
     }
+    if constexpr (XLANE == 2) {
 #pragma unroll
-    for (int k = 1; k < 8; k++) tB[k] = R.b(k);
-    if (XLANE) {
-        xlane_hi(x);                                                // reg k0 <-> lane bits 3..5: lane = (k0, p0), reg = p1
+        for (int k = 1; k < 8; k++) tB[k] = R.fb(k);                // odd entries negated in lanes with bit 3 set
+        xlane_hi_give(x);                                           // lane bits 3..5 <- k0 bits (2,0,1), reg = p1 (^ 4: bit 3 set)
     } else {
+#pragma unroll
+        for (int k = 1; k < 8; k++) tB[k] = R.b(k);
+    }
+    if (XLANE == 1) {
+        xlane_hi(x);                                                // reg k0 <-> lane bits 3..5: lane = (k0, p0), reg = p1
+    } else if (XLANE == 0) {
 #pragma unroll
         for (int k0 = 0; k0 < 8; k0++) sT[own + 72 * k0] = x[k0];   // element (k0, p1, p0), lane = (p1, p0)
         tile_sync<WSYNC>();

@@ -1,6 +1,8 @@
 // The transform probe (fft_probe.h): fft512.h's transforms and its twiddle builder on caller data, for tests only.
 #include "fft_probe.h"
 
+#include <atomic>
+#include <cstdlib>
 #include <stdexcept>
 
 #include "evaluator.h"  // HIP_CHECK
@@ -133,6 +135,17 @@ void run_fft512(int form, size_t count, const double2* d_in, double2* d_out, con
     HIP_CHECK(launched);
     HIP_CHECK(done);
 }
+
+static int forward_path_at_start() {
+    const char* e = getenv("IEACHE_W1B_FORWARD");
+    return e && e[0] == '1' && !e[1] ? 1 : 2;
+}
+static std::atomic<int> g_w1b_forward_path{forward_path_at_start()};
+void set_w1b_forward_path(int xlane) {
+    if (xlane != 1 && xlane != 2) throw std::invalid_argument("debug_forward_path: 1 (v_cndmask pairs) or 2 (the exchange form, the default)");
+    g_w1b_forward_path.store(xlane, std::memory_order_relaxed);
+}
+int w1b_forward_path() { return g_w1b_forward_path.load(std::memory_order_relaxed); }
 
 void build_twiddles_in_wave(double2* d_out, hipStream_t stream) {
     hipLaunchKernelGGL(k_probe_build_twiddles, dim3(1), dim3(64), 0, stream, d_out);

@@ -294,6 +294,7 @@ def lib():
     L.ieache_debug_twiddles.argtypes = [vp, C.c_int, f64p]
     L.ieache_debug_fft512.argtypes = [vp, C.c_int, C.c_size_t, f64p, f64p]
     L.ieache_debug_spectrum.argtypes = [vp, C.c_int, C.c_size_t, C.c_size_t, f64p]
+    L.ieache_debug_forward_path.argtypes = [C.c_int]
     L.ieache_keygen_raw.argtypes = [pp, u32p, C.c_int, i32p, i32p, i32p, i32p]
     L.ieache_keygen_files.argtypes = [C.c_char_p, pp, u32p, C.c_int, u32p, C.c_int]
     L.ieache_encrypt_bits.argtypes = [pp, i32p, u8p, C.c_size_t, C.c_uint64, i32p]
@@ -412,6 +413,13 @@ def default_params():
 
 def device_count():
     return lib().ieache_device_count()
+
+
+def debug_forward_path(xlane):
+    """Which form of the forward transforms' lane-high transpose k_blind_rotate_w1b's launches take from here on, in every
+    context of the process: 2 (the exchange form, the default) or 1 (the v_cndmask form built beside it).  Same words either
+    way: the partner of an A/B and of a test."""
+    check(lib().ieache_debug_forward_path(xlane))
 
 
 def circuit_info(kind, bits, fold=False, level_cap=0):

@@ -687,6 +687,11 @@ int ieache_debug_keyswitch(ieache_ctx* ctx, size_t count, const int32_t* u, int3
 int ieache_debug_twiddles(ieache_ctx* ctx, int which, double* out);
 int ieache_debug_fft512(ieache_ctx* ctx, int form, size_t count, const double* in, double* out);
 int ieache_debug_spectrum(ieache_ctx* ctx, int which, size_t first, size_t count, double* out);
+/* Which form of the forward transforms' lane-high transpose the launches of k_blind_rotate_w1b's default-guard builds take from
+ * here on, in every context of the process: 2, the exchange form (one DPP move per dword for lane bit 3; the default), or 1, the
+ * v_cndmask form built beside it.  Both give the same words: the partner of an A/B and of a test.  A process starts with
+ * the value of IEACHE_W1B_FORWARD (1 or 2) if that is set.  IEACHE_EINVAL for another value.  No device needed. */
+int ieache_debug_forward_path(int xlane);
 /* The plan of a rotation of roles (option "br_mix") for a launch of `gates` gate instances on a device of `cus` compute units,
  * rotations of n steps, one-wave turns of s1 steps, two-wave turns of s1 x ratio_x100 / 100: returns 1 and out = {subsets k,
  * subsets on two waves at a time, s1, s2, whole rounds, shortened round's s1, s2, steps covered by the rounds (< n), gate
