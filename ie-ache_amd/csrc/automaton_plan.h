@@ -5,7 +5,7 @@
 //
 // This call stands BESIDE the table of set_calls.h and is not a row of it: that table's calls are sized by (count, depth, steps,
 // n_sets) alone, while this one's arguments are sized by an object made earlier (states, steps, n_out), its scalar refusals are
-// the object's own, and the table is pinned at seven kinds.  What fits is reused: check_indices' messages, the staging slots,
+// the object's own, and the table is pinned at eight kinds.  What fits is reused: check_indices' messages, the staging slots,
 // the overlap rule, the piece loop.
 //
 //   k_automaton_x1   one workgroup of kCmuxWaveRows waves per item, every step of a launch inside it: per step t = hi-1 .. lo
@@ -80,12 +80,8 @@ struct AutomatonPlan {
     int64_t scratch_rows = 0;       // rows of [2][N] words of the largest piece (the first): items_per_piece x 2 states, or 0
     int32_t steps_per_launch = 0;   // of every launch but perhaps the last
     int32_t launches = 0;           // per piece
+    Cut cut() const { return {pieces, items_per_piece}; }  // of the items (cmux_plan.h)
 };
-inline int64_t automaton_piece_first(const AutomatonPlan& pl, int64_t i) { return i * pl.items_per_piece; }
-inline int64_t automaton_piece_items(const AutomatonPlan& pl, int64_t items, int64_t i) {
-    const int64_t left = items - automaton_piece_first(pl, i);
-    return left < pl.items_per_piece ? left : pl.items_per_piece;
-}
 // launch j = 0 .. launches-1 of a piece processes t = hi-1 down to lo: the chunks cover steps-1 .. 0 once, in that order
 inline void automaton_launch_steps(const AutomatonPlan& pl, int32_t steps, int32_t j, int32_t* hi, int32_t* lo) {
     *hi = steps - j * pl.steps_per_launch;

@@ -955,25 +955,27 @@ int check_indices(const int32_t* idx, size_t count, int64_t bound, const char* c
     return 0;
 }
 
-// ---- The calls on a set (sections 3f to 3j).  set_calls.h states what each is; these read it.  `a`: the call's pointer
+// ---- The calls on a set (sections 3f to 3j, and the replace write of a window of 3l).  set_calls.h states what each is; these read it.  `a`: the call's pointer
 // arguments in the order of its signature (kSetCalls[..].args). ----
 static_assert(kSetCalls[kCallLutRead].known_flags == IEACHE_LUT_READ_NO_KEYSWITCH && Evaluator::kLutReadNoKeyswitch == IEACHE_LUT_READ_NO_KEYSWITCH,
               "set_calls.h knows, and the evaluator reads, the flags of include/ieache.h");
-int check_set_scalars(const SetCall& c) {
-    const std::string refusal = set_call_refusal(c);
+int check_set_scalars(const SetCall& c, int32_t N) {
+    const std::string refusal = set_call_refusal(c, N);
     return refusal.empty() ? 0 : fail(IEACHE_EINVAL, refusal);
 }
-// what the device and the host form refuse first: the context and the set, a null required argument; the scalars come next
+// what the device and the host form refuse first: the context and the set, a null required argument, a missing projection key;
+// the scalars come next
 int check_set_call(const ieache_ctx* ctx, const ieache_tgsw* set, const SetCall& c, SetPtrs a) {
     if (const int rc = check_tgsw(ctx, set)) return rc;
     const SetCallShape& s = kSetCalls[c.kind];
     for (int i = 0; i < s.n_args; i++)
         if (!a.begin()[i] && set_arg_required(c, s.args[i])) return fail(IEACHE_EINVAL, "null argument");
+    if (s.window && !ctx->eval->has_projection_key()) return fail(IEACHE_EINVAL, std::string(s.name) + ": no projection key set");
     return 0;
 }
 // the host and the reference forms: the scalars, then the first bad entry of the index arrays in argument order, then lut_read's coef
 int check_set_indices(const SetCall& c, SetPtrs a, int32_t N, size_t n_set) {
-    if (const int rc = check_set_scalars(c)) return rc;
+    if (const int rc = check_set_scalars(c, N)) return rc;
     const SetCallShape& s = kSetCalls[c.kind];
     for (int i = 0; i < s.n_args; i++) {
         const SetArg& arg = s.args[i];
@@ -984,8 +986,8 @@ int check_set_indices(const SetCall& c, SetPtrs a, int32_t N, size_t n_set) {
     return c.kind == kCallLutRead ? check_indices(&c.coef, 1, N, s.name, "coef") : 0;
 }
 // the device forms: the scalars, then every pointer the call will read or write; a null optional one is none
-int check_set_pointers(const SetCall& c, SetPtrs args) {
-    if (const int rc = check_set_scalars(c)) return rc;
+int check_set_pointers(const SetCall& c, SetPtrs args, int32_t N) {
+    if (const int rc = check_set_scalars(c, N)) return rc;
     const SetCallShape& s = kSetCalls[c.kind];
     const void* const* a = args.begin();
     for (int i = 0; i < s.n_args; i++)  // first, and always, what a call without items touches as well (lut_add's memories and output)
@@ -1000,7 +1002,7 @@ template <class Run>
 int set_call_device(ieache_ctx* ctx, const ieache_tgsw* set, const SetCall& c, const SetPtrs& a, ieache_stats* stats, Run&& run) {
     return guarded([&] {
         if (const int rc = check_set_call(ctx, set, c, a)) return rc;
-        if (const int rc = check_set_pointers(c, a)) return rc;
+        if (const int rc = check_set_pointers(c, a, ctx->eval->params().N)) return rc;
         return with_stats(stats, run);
     });
 }
@@ -1089,7 +1091,7 @@ int ieache_debug_cmux_plan(const ieache_ctx* ctx, size_t count, int32_t depth, i
     return guarded([&] {
         if (!ctx || !out) return fail(IEACHE_EINVAL, "null argument");
         // a negative depth asks for the flat plan, so only the upper bound is a refusal here: lut_tree's, in its words
-        if (depth > IEACHE_LUT_TREE_MAX_DEPTH) return check_set_scalars(SetCall{kCallLutTree, count, depth});
+        if (depth > IEACHE_LUT_TREE_MAX_DEPTH) return check_set_scalars(SetCall{kCallLutTree, count, depth}, ctx->eval->params().N);
         ctx->eval->cmux_plan_figures(count, depth, out);
         return 0;
     });
@@ -1219,22 +1221,13 @@ int ieache_lut_add(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_
                          });
 }
 
-// ---- the TLWE projection and the replace write of a window (section 3l).  project_plan.h states what the calls accept; the write
-// stands beside the table of set_calls.h (it takes two further scalars and needs the projection key), so its device and host
-// forms follow set_call_device's and set_call_host's steps written out. ----
+// ---- the TLWE projection and the replace write of a window (section 3l).  project_plan.h states what the calls accept; the
+// write is a row of set_calls.h. ----
 namespace {
 int check_project(const ieache_ctx* ctx, int32_t first, int32_t width, int32_t dest, size_t count, const int32_t* in, const int32_t* out) {
     if (!ctx || (count && (!in || !out))) return fail(IEACHE_EINVAL, "null argument");
     if (!ctx->eval->has_projection_key()) return fail(IEACHE_EINVAL, "tlwe_project: no projection key set");
     if (const char* e = project_call_error(ctx->eval->params(), first, width, dest)) return fail(IEACHE_EINVAL, e);
-    return 0;
-}
-int check_write_coef(const ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit,
-                     const int32_t* fresh, const int32_t* mem, const int32_t* out) {
-    if (const int rc = check_tgsw(ctx, set)) return rc;
-    if (count && (!fresh || !mem || !out)) return fail(IEACHE_EINVAL, "null argument");
-    if (!ctx->eval->has_projection_key()) return fail(IEACHE_EINVAL, "lut_write_coef: no projection key set");
-    if (const char* e = write_coef_error(ctx->eval->params(), depth, steps, width, unit)) return fail(IEACHE_EINVAL, e);
     return 0;
 }
 }  // namespace
@@ -1282,38 +1275,16 @@ int ieache_tlwe_project(ieache_ctx* ctx, size_t count, int32_t first, int32_t wi
 
 int ieache_lut_write_coef_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit,
                                  const int32_t* d_sel_of, const int32_t* d_new, const int32_t* d_mem, int32_t* d_out, ieache_stats* stats) {
-    return guarded([&] {
-        if (const int rc = check_write_coef(ctx, set, count, depth, steps, width, unit, d_new, d_mem, d_out)) return rc;
-        if (count) {
-            require_device_pointer(d_new, "d_new");
-            require_device_pointer(d_mem, "d_mem");
-            require_device_pointer(d_out, "d_out");
-            if (d_sel_of && depth + steps > 0) require_device_pointer(d_sel_of, "d_sel_of");
-        }
-        return with_stats(stats, [&](EvalStats* st) {
-            ctx->eval->lut_write_coef_device(*set->set, count, depth, steps, width, unit, d_sel_of, d_new, d_mem, d_out, st);
-        });
-    });
+    return set_call_device(ctx, set, {kCallLutWriteCoef, count, depth, steps, 1, 0, 0, width, unit}, {d_sel_of, d_new, d_mem, d_out}, stats,
+                           [&](EvalStats* st) { ctx->eval->lut_write_coef_device(*set->set, count, depth, steps, width, unit, d_sel_of, d_new, d_mem, d_out, st); });
 }
 
 int ieache_lut_write_coef(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit,
                           const int32_t* sel_of, const int32_t* fresh, const int32_t* mem, int32_t* out, ieache_stats* stats) {
-    return guarded([&] {
-        if (const int rc = check_write_coef(ctx, set, count, depth, steps, width, unit, fresh, mem, out)) return rc;
-        if (const int rc = check_indices(sel_of, count * (size_t)(depth + steps), (int64_t)set->set->n, "lut_write_coef", "sel_of")) return rc;
-        HostCall h(ctx, count);
-        const size_t sample = (size_t)2 * (size_t)h.p.N, leaves = count << depth;
-        // the memory is uploaded into the result rows: the call runs in place
-        StagedRows dout(h.ev, kStageOut, leaves, sample);
-        if (leaves) HIP_CHECK(hipMemcpy(dout.p, mem, leaves * sample * 4, hipMemcpyHostToDevice));
-        StagedRows dnew(h.ev, kStageTlweA, count, sample, fresh, sample);
-        StagedRows dsel = h.words(kStagePolyOf, depth + steps > 0 ? sel_of : nullptr, count * (size_t)(depth + steps));
-        with_stats(stats, [&](EvalStats* st) {
-            h.ev.lut_write_coef_device(*set->set, count, depth, steps, width, unit, dsel.p, dnew.p, dout.p, dout.p, st);
-        });
-        dout.download(out, sample);
-        return 0;
-    });
+    return set_call_host(ctx, set, {kCallLutWriteCoef, count, depth, steps, 1, 0, 0, width, unit}, {sel_of, fresh, mem, out}, out, stats,
+                         [&](Evaluator& ev, Torus32* const* d, EvalStats* st) {
+                             ev.lut_write_coef_device(*set->set, count, depth, steps, width, unit, d[0], d[1], d[2], d[3], st);
+                         });
 }
 
 // ---- automata over words of TGSW-encrypted bits (section 3k).  The call stands beside the table of set_calls.h
@@ -1947,7 +1918,7 @@ int ieache_lut_read_reference(const ieache_params* p, const int32_t* set, size_t
         if (!pp.supported()) return fail(IEACHE_EINVAL, "lut_read_reference: unsupported TFHE parameter set");
         if (n < 1) return fail(IEACHE_EINVAL, "lut_read_reference: no samples");
         const SetCall c{kCallLutRead, count, depth, steps, n_tables, flags, coef};
-        if (const int rc = check_set_scalars(c)) return rc;
+        if (const int rc = check_set_scalars(c, pp.N)) return rc;
         const bool woks = (flags & IEACHE_LUT_READ_NO_KEYSWITCH) != 0;
         if (!woks && !ksk) return fail(IEACHE_EINVAL, "lut_read_reference: the key switch needs ksk");
         if (const int rc = check_set_indices(c, {sel_of, amount_of, tables, table_of, out}, pp.N, n)) return rc;
@@ -2020,8 +1991,7 @@ int ieache_lut_write_coef_reference(const ieache_params* p, const int32_t* set, 
         if (!pp.supported()) return fail(IEACHE_EINVAL, "lut_write_coef_reference: unsupported TFHE parameter set");
         if (n < 1) return fail(IEACHE_EINVAL, "lut_write_coef_reference: no samples");
         if (const char* e = project_set_error(pp, pk_t, pk_basebit)) return fail(IEACHE_EINVAL, e);
-        if (const char* e = write_coef_error(pp, depth, steps, width, unit)) return fail(IEACHE_EINVAL, e);
-        if (const int rc = check_indices(sel_of, count * (size_t)(depth + steps), (int64_t)n, "lut_write_coef", "sel_of")) return rc;
+        if (const int rc = check_set_indices({kCallLutWriteCoef, count, depth, steps, 1, 0, 0, width, unit}, {sel_of, fresh, mem, out}, pp.N, n)) return rc;
         lut_write_coef_reference(pp, set, n, pk_t, pk_basebit, pk, count, depth, steps, width, unit, sel_of, fresh, mem, out);
         return 0;
     });

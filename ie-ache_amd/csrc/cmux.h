@@ -4,8 +4,12 @@
 //   section 3h  the rotation by caller selectors and the coefficient-level lookup;
 //   section 3i  sets with a gadget of their own, and the replace write;
 //   section 3j  many values added into shared memories in one call;
-//   section 3k  deterministic automata over words of encrypted bits, every step of an item in one launch.
-// The kernels, the spectrum form of a prepared set, the twiddle table and the scratch of a tree are behind this object; how
+//   section 3k  deterministic automata over words of encrypted bits, every step of an item in one launch;
+//   section 3l  the two steps of the replace write of a window that are this family's: the read of each item's own memory toward
+//               position 0 (launch_read_own) and the subtraction (launch_delta); the projection between them is pack.h's.
+// The kernels, the spectrum form of a prepared set, the twiddle table and the scratch of a tree are behind this object: a tree
+// is ONE level loop (launch_levels) whether its level 0 reads shared tables or each item's own rows, whether its selectors are
+// the call's or a piece's explicit ones, and nothing outside fills in a CmuxRows of a tree.  How
 // a call is cut is cmux_plan.h; what a call is -- scalars, refusals, arguments -- is set_calls.h.  Kernels: cmux.hip (3f, 3g),
 // rotate.hip (3h) and automaton.hip (3k, cut by automaton_plan.h); what they share is cmux_step.h.
 #pragma once
@@ -195,7 +199,7 @@ struct Cmux {
                        const int32_t* sel_of, const int32_t* values, const int32_t* mem, int32_t* out);
     // one piece of a replace write (section 3i): old_i = the tree of item i's own memory rows by its selectors, delta_i = fresh_i
     // - old_i mod 2^32 (k_write_delta, over scratch.rows), the scatter of delta onto the memory -> out; out == mem is allowed: a
-    // piece reads and writes its own items' rows only, the tree has finished reading them when the scatter's last step -- the
+    // piece reads and writes its own items' rows only, the tree (launch_own_tree) has finished reading them when the scatter's last step -- the
     // only launch that writes them -- starts (one stream), and that step is in place by k_demux_x1's argument.  scratch as
     // reserve_read's.  Returns the kernel launches issued.
     int launch_write(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, const int32_t* sel_of,
@@ -210,6 +214,14 @@ struct Cmux {
     int launch_read(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, int32_t steps,
                     const int32_t* sel_of, const int32_t* amount_of, const int32_t* tables, int32_t n_tables, const int32_t* table_of, int32_t coef,
                     int32_t* u, int32_t stride);
+    // one piece of the read of a replace write of a window (section 3l), launch_read's sibling: selectors steps .. steps + depth - 1
+    // of each item made explicit in scratch.idx (k_read_indices; not counted as a launch), the tree of each item's OWN memory rows
+    // mem [items][2^depth][2][N] (the piece's, already offset) by them into scratch.rows, the rotation of those rows in place by
+    // selectors 0 .. steps - 1 and amount_of.  sel_of is the call's.  scratch as reserve_read's.  Returns max(depth, 1) + (steps > 0).
+    int launch_read_own(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, int32_t steps,
+                        const int32_t* sel_of, const int32_t* amount_of, const int32_t* mem);
+    // delta_i = fresh_i - old_i mod 2^32 in place over old [items][2][N] (k_write_delta): one launch
+    void launch_delta(hipStream_t stream, int64_t items, const int32_t* fresh, int32_t* old_to_delta);
     // one launch of `rows.rows` accumulating demux steps (k_demux_acc: 2 x rows.rows rows added into rows.out)
     void launch_demux_acc(const TgswSet& set, hipStream_t stream, DemuxAccRows rows);
     // the scatter of one piece of lut_add (section 3j): `items` parents src [items][2][N] by the piece's explicit selectors
@@ -251,6 +263,20 @@ private:
     template <class Rows, class KernelOf>
     void launch_rows(const TgswSet& set, hipStream_t stream, Rows rows, KernelOf kernel_of, size_t lds = 0, dev::LdsGrant* grant = nullptr,
                      const char* name = nullptr, const char* name_rt = nullptr);
+    // THE level loop of a tree of depth >= 1 over one piece: level k is one launch of items x 2^(depth-1-k) CMuxes; level 0
+    // reads `src` -- shared: tables [n_tables][2^depth] picked by table_of, otherwise each item's own 2^depth rows -- the last
+    // level writes `out`, the levels between the scratch buffers (scratch_rows).  sel_of with item0: the call's array and the
+    // piece's first item, or a piece's explicit array and 0.  `refusal`: what a scratch too small throws.  Returns depth.
+    int launch_levels(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, const int32_t* sel_of,
+                      const int32_t* src, bool shared, int32_t n_tables, const int32_t* table_of, int32_t* out, const char* refusal);
+    // item i looks up its own memory: launch_levels unshared over mem [items][2^depth][2][N] -> out [items][2][N]; depth 0: the
+    // rows copied (counted as one launch)
+    int launch_own_tree(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, const int32_t* sel_of,
+                        const int32_t* mem, int32_t* out, const char* refusal);
+    // the rows a lookup selected (scratch.rows) rotated in place by selectors 0 .. steps - 1 of each item's depth + steps;
+    // returns the launches (steps > 0)
+    int launch_rotate_selected(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, int32_t steps,
+                               const int32_t* sel_of, const int32_t* amount_of);
     Params p_;
     const int64_t* runtime_always_ = nullptr;
     int device_ = 0;

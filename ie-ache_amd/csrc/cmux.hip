@@ -656,8 +656,14 @@ int Cmux::launch_tree(const TgswSet& set, CmuxScratch& scratch, hipStream_t stre
         hipLaunchKernelGGL(k_cmux_copy, dim3((unsigned)items), dim3(256), 0, stream, tables, n_tables, table_of, item0, out);
         return 1;
     }
-    check_scratch(scratch, items, depth, "lut_tree: piece larger than the reserved scratch");
-    const int32_t* src = tables;
+    return launch_levels(set, scratch, stream, item0, items, depth, sel_of, tables, true, n_tables, table_of, out,
+                         "lut_tree: piece larger than the reserved scratch");
+}
+
+int Cmux::launch_levels(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth,
+                        const int32_t* sel_of, const int32_t* src, bool shared, int32_t n_tables, const int32_t* table_of, int32_t* out,
+                        const char* refusal) {
+    check_scratch(scratch, items, depth, refusal);
     for (int32_t k = 0; k < depth; k++) {
         CmuxRows R;
         R.depth = depth;
@@ -667,7 +673,7 @@ int Cmux::launch_tree(const TgswSet& set, CmuxScratch& scratch, hipStream_t stre
         R.item0 = item0;
         R.sel_of = sel_of;
         R.src = src;
-        R.shared = k == 0;
+        R.shared = shared && k == 0;
         R.table_of = table_of;
         R.n_tables = n_tables;
         R.dst = k == depth - 1 ? out : scratch_rows(scratch, k);  // the last level writes the caller's rows; level 0 the widest
@@ -675,6 +681,16 @@ int Cmux::launch_tree(const TgswSet& set, CmuxScratch& scratch, hipStream_t stre
         src = R.dst;
     }
     return depth;
+}
+
+int Cmux::launch_own_tree(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth,
+                          const int32_t* sel_of, const int32_t* mem, int32_t* out, const char* refusal) {
+    if (depth == 0) {
+        HIP_CHECK(hipMemcpyAsync(out, mem, (size_t)items * 2 * kN * 4, hipMemcpyDeviceToDevice, stream));
+        return 1;
+    }
+    // tables [items][2^depth] with table_of[i] = i, which is the tree's level 0 unshared
+    return launch_levels(set, scratch, stream, item0, items, depth, sel_of, mem, false, 1, nullptr, out, refusal);
 }
 
 void Cmux::launch_demux(const TgswSet& set, hipStream_t stream, DemuxRows rows) {
@@ -771,31 +787,14 @@ int Cmux::launch_write(const TgswSet& set, CmuxScratch& scratch, hipStream_t str
     if (depth < 0 || depth > kCmuxMaxDepth) throw std::invalid_argument("lut_write: depth out of range");
     if (scratch.rows.items() < (size_t)items * 2 * kN) throw std::invalid_argument("lut_write: piece larger than the reserved scratch");
     int32_t* delta = scratch.rows;
-    // old: item i looks up its own memory -- tables [items][2^depth] with table_of[i] = i, which is the tree's level 0 unshared
-    int launches;
-    if (depth == 0) {
-        HIP_CHECK(hipMemcpyAsync(delta, mem, (size_t)items * 2 * kN * 4, hipMemcpyDeviceToDevice, stream));
-        launches = 1;
-    } else {
-        check_scratch(scratch, items, depth, "lut_write: piece larger than the reserved scratch");
-        const int32_t* src = mem;
-        for (int32_t k = 0; k < depth; k++) {
-            CmuxRows R;
-            R.depth = depth;
-            R.level = k;
-            R.width = 1 << (depth - 1 - k);
-            R.rows = items * R.width;
-            R.item0 = item0;
-            R.sel_of = sel_of;
-            R.src = src;
-            R.dst = k == depth - 1 ? delta : scratch_rows(scratch, k);
-            launch(set, stream, R);
-            src = R.dst;
-        }
-        launches = depth;
-    }
-    hipLaunchKernelGGL(k_write_delta, dim3((unsigned)items), dim3(256), 0, stream, fresh, delta);
+    const int launches = launch_own_tree(set, scratch, stream, item0, items, depth, sel_of, mem, delta, "lut_write: piece larger than the reserved scratch");
+    launch_delta(stream, items, fresh, delta);
     return launches + 1 + launch_scatter(set, scratch, stream, item0, items, depth, sel_of, delta, mem, out);
+}
+
+void Cmux::launch_delta(hipStream_t stream, int64_t items, const int32_t* fresh, int32_t* old_to_delta) {
+    if (items <= 0) return;
+    hipLaunchKernelGGL(k_write_delta, dim3((unsigned)items), dim3(256), 0, stream, fresh, old_to_delta);
 }
 
 void Cmux::launch_extract(hipStream_t stream, int64_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u, int32_t stride) {

@@ -39,17 +39,26 @@ constexpr int32_t kRotateMaxSteps = 64;     // IEACHE_ROTATE_MAX_STEPS: what one
 constexpr int64_t kCmuxPieceRows = 8192;
 constexpr int64_t kCmuxPieceRowsMax = (int64_t)1 << 20;
 
+// THE cut of a levelled call -- of a tree's items, a packing call's groups (pack_plan.h), an automaton's items
+// (automaton_plan.h), the rows of a key switch: `pieces` runs of `per_piece`, the last perhaps shorter.  Piece i of a call over
+// `total` holds [piece_first, piece_first + piece_count); the evaluator's piece loop walks a cut and knows no plan.
+struct Cut {
+    int64_t pieces = 0, per_piece = 0;
+};
+inline int64_t piece_first(const Cut& c, int64_t i) { return i * c.per_piece; }
+inline int64_t piece_count(const Cut& c, int64_t total, int64_t i) {
+    const int64_t left = total - piece_first(c, i);
+    return left < c.per_piece ? left : c.per_piece;
+}
+// `total` in runs of at most `run` (nothing, or no run length: no pieces)
+inline Cut cut_in_runs(int64_t total, int64_t run) { return total <= 0 || run <= 0 ? Cut{} : Cut{(total + run - 1) / run, run}; }
+
 struct CmuxPlan {
     int64_t items_per_piece = 0, pieces = 0;
     int64_t level0_rows = 0;   // rows the first level of the largest piece (the first) writes: items_per_piece x 2^(depth-1); flat: its rows
     int64_t a_rows = 0, b_rows = 0;  // scratch rows of [2][N] words: A (depth >= 2), B (depth >= 3)
+    Cut cut() const { return {pieces, items_per_piece}; }
 };
-// items [first, first + count) of piece `i`
-inline int64_t cmux_piece_first(const CmuxPlan& pl, int64_t i) { return i * pl.items_per_piece; }
-inline int64_t cmux_piece_items(const CmuxPlan& pl, int64_t items, int64_t i) {
-    const int64_t left = items - cmux_piece_first(pl, i);
-    return left < pl.items_per_piece ? left : pl.items_per_piece;
-}
 
 // A call of `items` items: depth < 0 names a flat call (rows = items), 0 .. kCmuxMaxDepth a tree.  piece_rows_opt:
 // "cmux_piece_rows" (anything outside 1 .. kCmuxPieceRowsMax: the default).

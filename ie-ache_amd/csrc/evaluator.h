@@ -17,7 +17,7 @@ namespace ieache {
 struct OptionRow;  // evaluator_options.h
 struct TgswSet;    // cmux.h
 struct Automaton;  // cmux.h
-struct CmuxPlan;   // cmux_plan.h
+struct Cut;        // cmux_plan.h
 struct SetCall;    // set_calls.h
 
 struct EvalStats {
@@ -224,8 +224,8 @@ public:
     // d_out == d_mem writes in place (a piece reads and adds into its own items' memories only), no other overlap; with
     // distinct buffers d_out starts as a copy of d_mem on the stream.  Everything is reserved before the first piece.  stats:
     // levels = 2 (depth + steps) + 1, chunks = pieces, keyswitch_launches = the projection's runs, blind_rotate_launches =
-    // pieces x (2 max(depth, 1) + 2 (steps > 0) + 1).  std::invalid_argument without a projection key, for scalars
-    // write_coef_error refuses, an overlap, a set of another evaluator.
+    // pieces x (2 max(depth, 1) + 2 (steps > 0) + 1).  The eighth row of set_calls.h: std::invalid_argument without a projection
+    // key, for scalars write_coef_error refuses, an overlap, a set of another evaluator.
     void lut_write_coef_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit, const int32_t* d_sel_of,
                                const Torus32* d_new, const Torus32* d_mem, Torus32* d_out, EvalStats* stats = nullptr);
     void tlwe_rotate_device(const TgswSet& set, size_t count, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of, const Torus32* d_in,
@@ -349,6 +349,7 @@ public:
 
     struct Impl;      // device buffers; defined in evaluator.hip
     struct FlatCall;  // what a flat call (gates, mux, programmable bootstraps) hands its one body; defined in evaluator.hip
+    struct PackSide;  // the packing unit's object, scratch, option and names for one of its two uses; defined in evaluator.hip
 
 private:
     void flat_device_once(const FlatCall& call, EvalStats* stats);  // gates, gates3, mux, pbs and pbs_multi, once
@@ -360,11 +361,17 @@ private:
     void run_guarded(bool inputs_intact, EvalStats* stats, F&& once);
     // what the calls on caller TGSW samples open with, from the table of set_calls.h -> whether there are items to run (evaluator.hip)
     bool begin_set_call(const TgswSet& set, const SetCall& c, std::initializer_list<const void*> args, size_t out_row_words);
-    // their piece loop (evaluator.hip)
-    template <class Body, class KeySwitch>
-    void run_cmux_pieces(const CmuxPlan& pl, size_t count, int32_t levels, EvalStats* stats, Body&& body, int64_t ks_rows, KeySwitch&& ks);
+    // the piece loop of every levelled call: body(piece) per piece of the cut (evaluator.hip)
     template <class Body>
-    void run_cmux_pieces(const CmuxPlan& pl, size_t count, int32_t levels, EvalStats* stats, Body&& body);
+    void run_pieces(const Cut& cut, int64_t total, int32_t levels, EvalStats* stats, Body&& body);
+    // the packing key switch and the projection: one path over what differs between them (evaluator.hip)
+    PackSide packing() const;
+    PackSide projection() const;
+    void set_pack_key(const PackSide& side, int32_t t, int32_t basebit, const Torus32* pk);
+    void pack_side_figures(const PackSide& side, size_t groups, int32_t m, int64_t out[4]) const;
+    template <class Launch>
+    void pack_side_device(const PackSide& side, const char* shape_error, size_t groups, int32_t m, const Torus32* d_in, size_t in_words, Torus32* d_out,
+                          EvalStats* stats, Launch&& launch);
     void init();
     void destroy();
     void begin_call();

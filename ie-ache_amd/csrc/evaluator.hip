@@ -32,7 +32,6 @@
 #include "pack.h"
 #include "scoped_set.h"
 #include "set_calls.h"
-#include "write_coef.h"
 
 #include <algorithm>
 #include <cmath>
@@ -114,6 +113,20 @@ __global__ void k_gather_outputs(const OutRef* outs, int32_t n_out, const Torus3
         if (r.neg) v = 0u - v;
         dst[q] = q <= n ? (int32_t)v : 0;
     }
+}
+
+// The public tables of a replace write of a window (lut_write_coef; project_plan.h: write_coef_amount), once per call: the
+// amounts of its two rotations, toward [steps] = 2N - unit 2^t (the read) and back [steps] = unit 2^t (the write), and
+// own [count] = 0, 1, .. -- item i writes memory i.
+__global__ __launch_bounds__(256) void k_write_coef_tables(int32_t unit, int32_t steps, int32_t two_n, int64_t count, int32_t* __restrict__ toward,
+                                                           int32_t* __restrict__ back, int32_t* __restrict__ own) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q < steps) {
+        const int32_t w = (int32_t)(((int64_t)unit << q) & (two_n - 1));  // steps <= 30 (write_coef_error)
+        back[q] = w;
+        toward[q] = (two_n - w) & (two_n - 1);
+    }
+    if (q < count) own[q] = (int32_t)q;
 }
 
 }  // namespace
@@ -411,6 +424,37 @@ void add_times(EvalStats* stats, Timer& tall, Timer& tbr, Timer& tks) {
     stats->blind_rotate_ms += tbr.sum_ms();
     stats->keyswitch_ms += tks.sum_ms();
 }
+
+// One piece of a levelled call as its body sees it (Evaluator::run_pieces): items [first, first + count) of the call, and
+// the two kinds of phase a body runs on the evaluator's stream, in any order and any number of times.  A phase that never
+// runs records no event, so its time and its launches stay 0.
+struct Piece {
+    int64_t first, count;
+    // a rotation-side phase: fn() launches and returns how many kernels it did ("blind_rotate_launches", timed as blind_rotate_ms)
+    template <class F>
+    void rotate(F&& fn) {
+        tbr.mark();
+        const int launches = fn();
+        tbr.mark();
+        HIP_CHECK(hipGetLastError());
+        if (stats) stats->blind_rotate_launches += launches;
+    }
+    // a key-switch-side phase over `rows` rows in runs of at most run_rows: fn(rows done, rows of the run), one
+    // "keyswitch_launches" each, timed as keyswitch_ms
+    template <class F>
+    void keyswitch(int64_t rows, int64_t run_rows, F&& fn) {
+        const Cut runs = cut_in_runs(rows, run_rows);
+        for (int64_t r = 0; r < runs.pieces; r++) {
+            tks.mark();
+            fn(piece_first(runs, r), piece_count(runs, rows, r));
+            tks.mark();
+            HIP_CHECK(hipGetLastError());
+            if (stats) stats->keyswitch_launches++;
+        }
+    }
+    Timer &tbr, &tks;
+    EvalStats* stats;
+};
 }  // namespace
 
 // streams and join events of lanes 1 .. lanes-1, and the fork event
@@ -879,9 +923,27 @@ void Evaluator::pbs_multi_device(size_t count, const Torus32* d_x, const Torus32
     run_guarded(true, stats, [&] { flat_device_once(call, stats); });
 }
 
-// lweKeySwitch alone: a flat call without a rotation.  Pieces of at most a chunk on the evaluator's stream, each one launch of
-// the key-switch unit with a flat descriptor whose flat_out is the caller's rows (what the multi-output call hands it);
-// every piece's scratch is reserved before the first launch.  No run_guarded: no one-limb transform runs, nothing can trip.
+// THE piece loop of the levelled calls -- everything that is cut into pieces and is no gate bootstrapping -- on the evaluator's
+// stream: per piece of the cut body(piece), which runs the piece's phases (Piece above); one chunk per piece; the stream idle and
+// the three times folded in at the end.  The call counts as `levels` levels.  Every scratch is reserved before this is called.
+// No run_guarded: the two-limb product and the integer key switches are exact, nothing can trip.
+template <class Body>
+void Evaluator::run_pieces(const Cut& cut, int64_t total, int32_t levels, EvalStats* stats, Body&& body) {
+    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(stats != nullptr, stream_);
+    tall.mark();
+    for (int64_t i = 0; i < cut.pieces; i++) {
+        Piece piece{piece_first(cut, i), piece_count(cut, total, i), tbr, tks, stats};
+        body(piece);
+        if (stats) stats->chunks++;
+    }
+    tall.mark();
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    add_times(stats, tall, tbr, tks);
+    if (stats) stats->levels += levels;
+}
+
+// lweKeySwitch alone: a flat call without a rotation.  Pieces of at most a chunk, each one launch of the key-switch unit with a
+// flat descriptor whose flat_out is the caller's rows (what the multi-output call hands it).
 void Evaluator::keyswitch_device(size_t count, const Torus32* d_u, Torus32* d_out, EvalStats* stats) {
     if (overlaps(d_out, count * (size_t)d_->K.stride, {{d_u, count * (size_t)extract_stride()}}))
         throw std::invalid_argument("key switch: the output overlaps the input rows");
@@ -889,234 +951,138 @@ void Evaluator::keyswitch_device(size_t count, const Torus32* d_u, Torus32* d_ou
     if (count == 0) return;
     if (!d_u || !d_out) throw std::invalid_argument("key switch: null rows");
     Lane& ln = d_->lane[0];
-    const int64_t rows = (int64_t)count, piece = std::min<int64_t>(rows, (int64_t)d_->opt.chunk);
-    d_->ks.reserve(ln.ks, piece, d_->opt, d_->force_generic_ks);
-    Timer tall(stats != nullptr, stream_), tks(stats != nullptr, stream_), tbr(false, stream_);
-    tall.mark();
+    const Cut cut = cut_in_runs((int64_t)count, std::min<int64_t>((int64_t)count, (int64_t)d_->opt.chunk));
+    d_->ks.reserve(ln.ks, cut.per_piece, d_->opt, d_->force_generic_ks);
     WorkDesc W{};
     W.flat_out = d_out;
     W.flat_type = kFlatRaw;
-    for (int64_t done = 0; done < rows; done += piece) {
-        const int64_t cnt = std::min<int64_t>(piece, rows - done);
-        tks.mark();
-        launch_keyswitch(d_, ln, rows_desc(W, done), cnt, d_u + (size_t)done * (size_t)extract_stride(), nullptr);
-        tks.mark();
-        HIP_CHECK(hipGetLastError());
-        if (stats) {
-            stats->keyswitch_launches++;
-            stats->chunks++;
-        }
-    }
-    tall.mark();
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    add_times(stats, tall, tbr, tks);
-    if (stats) stats->levels += 1;
+    run_pieces(cut, (int64_t)count, 1, stats, [&](Piece& pc) {
+        pc.keyswitch(pc.count, pc.count, [&](int64_t, int64_t rows) {
+            launch_keyswitch(d_, ln, rows_desc(W, pc.first), rows, d_u + (size_t)pc.first * (size_t)extract_stride(), nullptr);
+        });
+    });
 }
 
-void Evaluator::set_packing_key(int32_t t, int32_t basebit, const Torus32* pk) {
+// The packing unit twice in a context (pack.h): the packing key switch and the projection, and what differs between their
+// evaluator paths -- the object, lane 0's scratch, the forced-split option, and the words of the messages.
+struct Evaluator::PackSide {
+    Pack& unit;
+    std::unique_ptr<PackScratch>& scratch;
+    int64_t& split;
+    const char *name, *key, *input;  // "<name>: no <key> key set", "<name>: the output overlaps the input <input>"
+    void require_key() const {
+        if (!unit.has_key()) throw std::invalid_argument(std::string(name) + ": no " + key + " key set");
+    }
+    // the cut of a call under the options as they are
+    PackPlan plan(const Impl* d, int64_t groups, int32_t m) const { return unit.plan(groups, m, d->opt.pack_piece_rows, (int32_t)split, d->opt.cus); }
+};
+Evaluator::PackSide Evaluator::packing() const { return {d_->pack, d_->lane[0].pack, d_->opt.pack_split, "pack", "packing", "rows"}; }
+Evaluator::PackSide Evaluator::projection() const {
+    return {d_->project, d_->lane[0].project, d_->opt.project_split, "tlwe_project", "projection", "samples"};
+}
+
+void Evaluator::set_pack_key(const PackSide& s, int32_t t, int32_t basebit, const Torus32* pk) {
     HIP_CHECK(hipSetDevice(device_));
     HIP_CHECK(hipStreamSynchronize(stream_));
-    d_->pack.set_key(t, basebit, pk, stream_);
-    if (!pk) d_->lane[0].pack.reset();  // the key is gone (the stream is idle): so is the scratch of its calls
-    d_->opt.pack_split = 0;  // a forced split was accepted for the walk of the key that is gone
+    s.unit.set_key(t, basebit, pk, stream_);
+    if (!pk) s.scratch.reset();  // the key is gone (the stream is idle): so is the scratch of its calls
+    s.split = 0;  // a forced split was accepted for the walk of the key that is gone
 }
-
+void Evaluator::set_packing_key(int32_t t, int32_t basebit, const Torus32* pk) { set_pack_key(packing(), t, basebit, pk); }
+void Evaluator::set_projection_key(int32_t t, int32_t basebit, const Torus32* pk) { set_pack_key(projection(), t, basebit, pk); }
 bool Evaluator::has_packing_key() const { return d_->pack.has_key(); }
-
-void Evaluator::pack_plan_figures(size_t groups, int32_t m, int64_t out[4]) const {
-    if (!d_->pack.has_key()) throw std::invalid_argument("pack: no packing key set");
-    const PackPlan pl = pack_plan(p_, d_->pack.t(), (int64_t)groups, m, d_->opt.pack_piece_rows, (int32_t)d_->opt.pack_split, d_->opt.cus);
-    out[0] = pl.pieces;
-    out[1] = pl.groups_per_piece;
-    out[2] = pl.ksplit;
-    out[3] = pl.k_steps;
-}
-
-// The packing key switch: pieces of whole groups on the evaluator's stream, each four launches of the unit (digits, init,
-// product, placement).  No run_guarded: integer arithmetic throughout, nothing can trip.
-void Evaluator::pack_device(size_t groups, int32_t m, int32_t spread, int32_t shift, const Torus32* d_rows, Torus32* d_out, EvalStats* stats) {
-    if (!d_->pack.has_key()) throw std::invalid_argument("pack: no packing key set");
-    if (const char* e = pack_call_error(p_, m, spread, shift)) throw std::invalid_argument(e);
-    const size_t row_words = (size_t)m * (size_t)d_->K.stride, out_words = (size_t)2 * (size_t)p_.N;
-    if (overlaps(d_out, groups * out_words, {{d_rows, groups * row_words}})) throw std::invalid_argument("pack: the output overlaps the input rows");
-    begin_call();
-    if (groups == 0) return;
-    if (!d_rows || !d_out) throw std::invalid_argument("pack: null rows");
-    Lane& ln = d_->lane[0];
-    const PackPlan pl = pack_plan(p_, d_->pack.t(), (int64_t)groups, m, d_->opt.pack_piece_rows, (int32_t)d_->opt.pack_split, d_->opt.cus);
-    if (!ln.pack) ln.pack.reset(new PackScratch);
-    d_->pack.reserve(*ln.pack, pl);
-    Timer tall(stats != nullptr, stream_), tks(stats != nullptr, stream_), tbr(false, stream_);
-    tall.mark();
-    for (int64_t i = 0; i < pl.pieces; i++) {
-        const int64_t g0 = pack_piece_first(pl, i), cnt = pack_piece_groups(pl, (int64_t)groups, i);
-        tks.mark();
-        d_->pack.launch(*ln.pack, stream_, pl, cnt, m, spread, shift, d_rows + (size_t)g0 * row_words, d_->K.stride, d_out + (size_t)g0 * out_words);
-        tks.mark();
-        HIP_CHECK(hipGetLastError());
-        if (stats) {
-            stats->keyswitch_launches++;
-            stats->chunks++;
-        }
-    }
-    tall.mark();
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    add_times(stats, tall, tbr, tks);
-    if (stats) stats->levels += 1;
-}
-
-void Evaluator::set_projection_key(int32_t t, int32_t basebit, const Torus32* pk) {
-    HIP_CHECK(hipSetDevice(device_));
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    d_->project.set_key(t, basebit, pk, stream_);
-    if (!pk) d_->lane[0].project.reset();  // the key is gone (the stream is idle): so is the scratch of its calls
-    d_->opt.project_split = 0;  // a forced split was accepted for the walk of the key that is gone
-}
-
 bool Evaluator::has_projection_key() const { return d_->project.has_key(); }
 
-void Evaluator::project_plan_figures(size_t count, int32_t width, int64_t out[4]) const {
-    if (!d_->project.has_key()) throw std::invalid_argument("tlwe_project: no projection key set");
-    const PackPlan pl =
-        project_plan(p_, d_->project.t(), (int64_t)count, width, d_->opt.pack_piece_rows, (int32_t)d_->opt.project_split, d_->opt.cus);
+void Evaluator::pack_side_figures(const PackSide& s, size_t groups, int32_t m, int64_t out[4]) const {
+    s.require_key();
+    const PackPlan pl = s.plan(d_, (int64_t)groups, m);
     out[0] = pl.pieces;
     out[1] = pl.groups_per_piece;
     out[2] = pl.ksplit;
     out[3] = pl.k_steps;
 }
+void Evaluator::pack_plan_figures(size_t groups, int32_t m, int64_t out[4]) const { pack_side_figures(packing(), groups, m, out); }
+void Evaluator::project_plan_figures(size_t count, int32_t width, int64_t out[4]) const { pack_side_figures(projection(), count, width, out); }
 
-// The projection: pieces of whole items on the evaluator's stream, each three launches of the unit (window digits, product,
-// placement).  Integer arithmetic throughout, as pack_device.
-void Evaluator::tlwe_project_device(size_t count, int32_t first, int32_t width, int32_t dest, const Torus32* d_in, Torus32* d_out, EvalStats* stats) {
-    if (!d_->project.has_key()) throw std::invalid_argument("tlwe_project: no projection key set");
-    if (const char* e = project_call_error(p_, first, width, dest)) throw std::invalid_argument(e);
-    const size_t row = (size_t)2 * (size_t)p_.N;
-    if (overlaps(d_out, count * row, {{d_in, count * row}})) throw std::invalid_argument("tlwe_project: the output overlaps the input samples");
+// A call of the packing unit: `groups` groups (items) of m rows, in_words words of d_in and 2N of d_out each; pieces of whole
+// groups, each one launch(plan, first group, groups) of the unit -- several kernels, counted as one key-switch launch.
+// shape_error: what the call's own rule says of its scalars, judged after the key.
+template <class Launch>
+void Evaluator::pack_side_device(const PackSide& s, const char* shape_error, size_t groups, int32_t m, const Torus32* d_in, size_t in_words,
+                                 Torus32* d_out, EvalStats* stats, Launch&& launch) {
+    const std::string who = std::string(s.name) + ": ";
+    s.require_key();
+    if (shape_error) throw std::invalid_argument(shape_error);
+    if (overlaps(d_out, groups * (size_t)2 * (size_t)p_.N, {{d_in, groups * in_words}})) throw std::invalid_argument(who + "the output overlaps the input " + s.input);
     begin_call();
-    if (count == 0) return;
-    if (!d_in || !d_out) throw std::invalid_argument("tlwe_project: null rows");
-    Lane& ln = d_->lane[0];
-    const PackPlan pl =
-        project_plan(p_, d_->project.t(), (int64_t)count, width, d_->opt.pack_piece_rows, (int32_t)d_->opt.project_split, d_->opt.cus);
-    if (!ln.project) ln.project.reset(new PackScratch);
-    d_->project.reserve(*ln.project, pl);
-    Timer tall(stats != nullptr, stream_), tks(stats != nullptr, stream_), tbr(false, stream_);
-    tall.mark();
-    for (int64_t i = 0; i < pl.pieces; i++) {
-        const int64_t i0 = pack_piece_first(pl, i), cnt = pack_piece_groups(pl, (int64_t)count, i);
-        tks.mark();
-        d_->project.launch_window(*ln.project, stream_, pl, cnt, first, width, dest, d_in + (size_t)i0 * row, d_out + (size_t)i0 * row);
-        tks.mark();
-        HIP_CHECK(hipGetLastError());
-        if (stats) {
-            stats->keyswitch_launches++;
-            stats->chunks++;
-        }
-    }
-    tall.mark();
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    add_times(stats, tall, tbr, tks);
-    if (stats) stats->levels += 1;
+    if (groups == 0) return;
+    if (!d_in || !d_out) throw std::invalid_argument(who + "null rows");
+    const PackPlan pl = s.plan(d_, (int64_t)groups, m);
+    if (!s.scratch) s.scratch.reset(new PackScratch);
+    s.unit.reserve(*s.scratch, pl);
+    run_pieces(pl.cut(), (int64_t)groups, 1, stats, [&](Piece& pc) {
+        pc.keyswitch(pc.count, pc.count, [&](int64_t, int64_t cnt) { launch(pl, pc.first, cnt); });
+    });
 }
 
-// The replace write of a window: the tree's pieces; per piece the read path (tree over the items' own memories, rotation toward
-// position 0), the projection in runs of its own plan, the subtraction, and lut_add's piece with memory i for item i.  A piece
-// reads and adds into its own items' memories only and has read them before it adds (one stream), so d_out == d_mem is sound.
+// The packing key switch: per piece four launches of the unit (digits, init, product, placement).
+void Evaluator::pack_device(size_t groups, int32_t m, int32_t spread, int32_t shift, const Torus32* d_rows, Torus32* d_out, EvalStats* stats) {
+    const PackSide s = packing();
+    const size_t row_words = (size_t)m * (size_t)d_->K.stride, out_words = (size_t)2 * (size_t)p_.N;
+    pack_side_device(s, pack_call_error(p_, m, spread, shift), groups, m, d_rows, row_words, d_out, stats, [&](const PackPlan& pl, int64_t g0, int64_t cnt) {
+        s.unit.launch(*s.scratch, stream_, pl, cnt, m, spread, shift, d_rows + (size_t)g0 * row_words, d_->K.stride, d_out + (size_t)g0 * out_words);
+    });
+}
+
+// The projection: per piece three launches of the unit (window digits, product, placement).
+void Evaluator::tlwe_project_device(size_t count, int32_t first, int32_t width, int32_t dest, const Torus32* d_in, Torus32* d_out, EvalStats* stats) {
+    const PackSide s = projection();
+    const size_t row = (size_t)2 * (size_t)p_.N;
+    pack_side_device(s, project_call_error(p_, first, width, dest), count, width, d_in, row, d_out, stats, [&](const PackPlan& pl, int64_t i0, int64_t cnt) {
+        s.unit.launch_window(*s.scratch, stream_, pl, cnt, first, width, dest, d_in + (size_t)i0 * row, d_out + (size_t)i0 * row);
+    });
+}
+
+// The replace write of a window: the tree's pieces; per piece the unit's read (the tree over the items' own memories, the rotation
+// toward position 0), the projection in runs of its own plan, and the unit's subtraction and lut_add's piece with memory i for item
+// i.  A piece reads and adds into its own items' memories only and has read them before it adds (one stream), so d_out == d_mem
+// is sound.
 void Evaluator::lut_write_coef_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit,
                                       const int32_t* d_sel_of, const Torus32* d_new, const Torus32* d_mem, Torus32* d_out, EvalStats* stats) {
-    d_->cmux.check_owner(set);
-    if (!d_->project.has_key()) throw std::invalid_argument("lut_write_coef: no projection key set");
-    if (const char* e = write_coef_error(p_, depth, steps, width, unit)) throw std::invalid_argument(e);
-    const size_t row = (size_t)2 * (size_t)p_.N, leaves = count << depth;
-    if (overlaps(d_out, leaves * row, {{d_new, count * row}, {d_sel_of, count * (size_t)(depth + steps)}}) ||
-        (d_mem != d_out && overlaps(d_out, leaves * row, {{d_mem, leaves * row}})))
-        throw std::invalid_argument("lut_write_coef: the output overlaps an input (only d_out == d_mem, the write in place, is accepted)");
-    begin_call();
-    if (count == 0) return;
-    if (!d_new || !d_mem || !d_out) throw std::invalid_argument("lut_write_coef: null rows");
+    const size_t row = (size_t)2 * (size_t)p_.N;
+    const SetCall c{kCallLutWriteCoef, count, depth, steps, 1, 0, 0, width, unit};
+    if (!begin_set_call(set, c, {d_sel_of, d_new, d_mem, d_out}, row)) return;
     Lane& ln = d_->lane[0];
+    const PackSide proj = projection();
     const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
-    const PackPlan pp =
-        project_plan(p_, d_->project.t(), pl.items_per_piece, width, d_->opt.pack_piece_rows, (int32_t)d_->opt.project_split, d_->opt.cus);
+    const PackPlan pp = proj.plan(d_, pl.items_per_piece, width);
     d_->cmux.reserve_read(ln.cmux, pl, depth);
-    if (!ln.project) ln.project.reset(new PackScratch);
-    d_->project.reserve(*ln.project, pp);
+    if (!proj.scratch) proj.scratch.reset(new PackScratch);
+    proj.unit.reserve(*proj.scratch, pp);
     ln.coef_old.reserve_exact((size_t)pl.items_per_piece * row);
     ln.coef_idx.reserve_exact((size_t)2 * kRotateMaxSteps + count);
     int32_t *toward = ln.coef_idx, *back = toward + kRotateMaxSteps, *own = back + kRotateMaxSteps;
     // not launches of the call's: the copy the sums start from, and the public amounts and memory indices
-    if (d_out != d_mem) HIP_CHECK(hipMemcpyAsync(d_out, d_mem, leaves * row * 4, hipMemcpyDeviceToDevice, stream_));
-    launch_write_coef_tables(stream_, unit, steps, 2 * p_.N, (int64_t)count, toward, back, own);
-    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(stats != nullptr, stream_);
-    tall.mark();
-    for (int64_t i = 0; i < pl.pieces; i++) {
-        const int64_t i0 = cmux_piece_first(pl, i), cnt = cmux_piece_items(pl, (int64_t)count, i);
-        const Torus32* mem = d_mem + ((size_t)i0 << depth) * row;
-        Torus32* rows = ln.cmux.rows;
-        int launches = 0;
-        tbr.mark();
-        // (1) old row: the tree over each item's own memory by its high selectors, made explicit for the piece
-        if (depth == 0) {
-            HIP_CHECK(hipMemcpyAsync(rows, mem, (size_t)cnt * row * 4, hipMemcpyDeviceToDevice, stream_));
-            launches++;
-        } else {
-            int32_t* tree_sel = ln.cmux.idx;
-            launch_write_coef_indices(stream_, d_sel_of, i0, cnt, depth, steps, (int32_t)set.n, tree_sel);
-            const Torus32* src = mem;
-            for (int32_t k = 0; k < depth; k++) {
-                CmuxRows R;
-                R.depth = depth;
-                R.level = k;
-                R.width = 1 << (depth - 1 - k);
-                R.rows = cnt * R.width;
-                R.sel_of = tree_sel;  // the piece's own array: item0 stays 0
-                R.src = src;
-                R.dst = k == depth - 1 ? rows : (k % 2 == 0 ? (Torus32*)ln.cmux.a : (Torus32*)ln.cmux.b);  // launch_tree's buffers
-                d_->cmux.launch(set, stream_, R);
-                src = R.dst;
-            }
-            launches += depth;
-        }
-        // (2) the addressed word to position 0
-        if (steps > 0) {
-            RotateRows R;
-            R.src = R.dst = rows;
-            R.rows = cnt;
-            R.item0 = i0;
-            R.sel_of = d_sel_of;
-            R.amount_of = toward;
-            R.steps = steps;
-            R.sel_stride = depth + steps;
-            d_->cmux.launch_rotate(set, stream_, R);
-            launches++;
-        }
-        tbr.mark();
-        HIP_CHECK(hipGetLastError());
-        // (3) old = the window alone
-        Torus32* old = ln.coef_old;
-        for (int64_t r = 0, runs = project_runs(pp, cnt); r < runs; r++) {
-            const int64_t g0 = pack_piece_first(pp, r), g = pack_piece_groups(pp, cnt, r);
-            tks.mark();
-            d_->project.launch_window(*ln.project, stream_, pp, g, 0, width, 0, rows + (size_t)g0 * row, old + (size_t)g0 * row);
-            tks.mark();
-            HIP_CHECK(hipGetLastError());
-            if (stats) stats->keyswitch_launches++;
-        }
-        // (4) delta = new - old, (5) added at the address into the items' own memories
-        tbr.mark();
-        launch_write_coef_delta(stream_, cnt, p_.N, d_new + (size_t)i0 * row, old);
-        launches += 1 + d_->cmux.launch_add(set, ln.cmux, stream_, i0, cnt, depth, steps, d_sel_of, back, old, (int32_t)count, own, d_out);
-        tbr.mark();
-        HIP_CHECK(hipGetLastError());
-        if (stats) {
-            stats->blind_rotate_launches += launches;
-            stats->chunks++;
-        }
-    }
-    tall.mark();
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    add_times(stats, tall, tbr, tks);
-    if (stats) stats->levels += 2 * (depth + steps) + 1;
+    if (d_out != d_mem) HIP_CHECK(hipMemcpyAsync(d_out, d_mem, set_arg_words(c, set_call_output(c), p_.N, row) * 4, hipMemcpyDeviceToDevice, stream_));
+    const int64_t tables = std::max<int64_t>((int64_t)count, steps);
+    hipLaunchKernelGGL(k_write_coef_tables, dim3((unsigned)((tables + 255) / 256)), dim3(256), 0, stream_, unit, steps, 2 * p_.N, (int64_t)count, toward,
+                       back, own);
+    run_pieces(pl.cut(), (int64_t)count, 2 * (depth + steps) + 1, stats, [&](Piece& pc) {
+        Torus32 *rows = ln.cmux.rows, *old = ln.coef_old;
+        // old row: the addressed word of each item's own memory at position 0
+        pc.rotate([&] {
+            return d_->cmux.launch_read_own(set, ln.cmux, stream_, pc.first, pc.count, depth, steps, d_sel_of, toward, d_mem + ((size_t)pc.first << depth) * row);
+        });
+        // old = the window alone
+        pc.keyswitch(pc.count, pp.groups_per_piece, [&](int64_t g0, int64_t g) {
+            proj.unit.launch_window(*proj.scratch, stream_, pp, g, 0, width, 0, rows + (size_t)g0 * row, old + (size_t)g0 * row);
+        });
+        // delta = new - old, added at the address into the items' own memories
+        pc.rotate([&] {
+            d_->cmux.launch_delta(stream_, pc.count, d_new + (size_t)pc.first * row, old);
+            return 1 + d_->cmux.launch_add(set, ln.cmux, stream_, pc.first, pc.count, depth, steps, d_sel_of, back, old, (int32_t)count, own, d_out);
+        });
+    });
 }
 
 TgswSet* Evaluator::tgsw_prepare_device(const Torus32* d_samples, size_t n) {
@@ -1133,7 +1099,7 @@ uint64_t Evaluator::cmux_id() const { return d_->cmux.id(); }
 
 void Evaluator::cmux_plan_figures(size_t count, int32_t depth, int64_t out[4]) const {
     // a negative depth asks for the flat plan: only the upper bound is refused, as lut_tree refuses it
-    if (depth > kCmuxMaxDepth) throw std::invalid_argument(set_call_refusal(SetCall{kCallLutTree, count, depth}));
+    if (depth > kCmuxMaxDepth) throw std::invalid_argument(set_call_refusal(SetCall{kCallLutTree, count, depth}, p_.N));
     const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
     out[0] = pl.pieces;
     out[1] = pl.items_per_piece;
@@ -1141,52 +1107,16 @@ void Evaluator::cmux_plan_figures(size_t count, int32_t depth, int64_t out[4]) c
     out[3] = pl.b_rows;
 }
 
-// The piece loop of the calls on caller TGSW samples, on the evaluator's stream: per piece of the plan body(first item, items),
-// which launches and returns how many kernels it did ("blind_rotate_launches", timed as blind_rotate_ms; one chunk per piece),
-// then -- a coefficient-level lookup that ends in LWE rows only -- ks(first item, rows done, rows) over the piece in runs of
-// at most ks_rows rows (one "keyswitch_launches" each, timed as keyswitch_ms).  The call counts as `levels` levels.  No
-// run_guarded: the two-limb product is exact, nothing can trip.
-template <class Body, class KeySwitch>
-void Evaluator::run_cmux_pieces(const CmuxPlan& pl, size_t count, int32_t levels, EvalStats* stats, Body&& body, int64_t ks_rows, KeySwitch&& ks) {
-    Timer tall(stats != nullptr, stream_), tbr(stats != nullptr, stream_), tks(stats != nullptr && ks_rows > 0, stream_);
-    tall.mark();
-    for (int64_t i = 0; i < pl.pieces; i++) {
-        const int64_t i0 = cmux_piece_first(pl, i), cnt = cmux_piece_items(pl, (int64_t)count, i);
-        tbr.mark();
-        const int launches = body(i0, cnt);
-        tbr.mark();
-        HIP_CHECK(hipGetLastError());
-        if (stats) {
-            stats->blind_rotate_launches += launches;
-            stats->chunks++;
-        }
-        for (int64_t done = 0; ks_rows > 0 && done < cnt; done += ks_rows) {
-            tks.mark();
-            ks(i0, done, std::min<int64_t>(ks_rows, cnt - done));
-            tks.mark();
-            HIP_CHECK(hipGetLastError());
-            if (stats) stats->keyswitch_launches++;
-        }
-    }
-    tall.mark();
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    add_times(stats, tall, tbr, tks);
-    if (stats) stats->levels += levels;
-}
-template <class Body>
-void Evaluator::run_cmux_pieces(const CmuxPlan& pl, size_t count, int32_t levels, EvalStats* stats, Body&& body) {
-    run_cmux_pieces(pl, count, levels, stats, body, 0, [](int64_t, int64_t, int64_t) {});
-}
-
 // What every call on a set opens with, from the table of set_calls.h (`a`: the call's pointer arguments in its order): the
-// set is this context's, the scalars are in range, the output shares no word with an input -- but for the one input that may
+// set is this context's, the projection key is there where the call needs it, the scalars are in range, the output shares no word with an input -- but for the one input that may
 // be the output exactly -- then begin_call() and the rows a call needs are there.  -> whether there are items to run
 bool Evaluator::begin_set_call(const TgswSet& set, const SetCall& c, std::initializer_list<const void*> args, size_t out_row_words) {
     const void* const* a = args.begin();
     d_->cmux.check_owner(set);
-    const std::string refusal = set_call_refusal(c);
-    if (!refusal.empty()) throw std::invalid_argument(refusal);
     const SetCallShape& s = kSetCalls[c.kind];
+    if (s.window && !d_->project.has_key()) throw std::invalid_argument(std::string(s.name) + ": no projection key set");
+    const std::string refusal = set_call_refusal(c, p_.N);
+    if (!refusal.empty()) throw std::invalid_argument(refusal);
     const int out = s.n_args - 1;
     const SetArg* alias = nullptr;
     bool shared = false;
@@ -1210,16 +1140,19 @@ void Evaluator::cmux_device(const TgswSet& set, size_t count, const int32_t* d_s
                             EvalStats* stats) {
     const size_t row = (size_t)2 * (size_t)p_.N;
     if (!begin_set_call(set, SetCall{kCallCmux, count}, {d_sel_of, d_d1, d_d0, d_out}, row)) return;
-    run_cmux_pieces(cmux_plan((int64_t)count, -1, d_->opt.cmux_piece_rows), count, 1, stats, [&](int64_t r0, int64_t rows) {
+    run_pieces(cmux_plan((int64_t)count, -1, d_->opt.cmux_piece_rows).cut(), (int64_t)count, 1, stats, [&](Piece& pc) {
+        const int64_t r0 = pc.first;
         CmuxRows R;
-        R.rows = rows;
+        R.rows = pc.count;
         R.src = d_d1 + (size_t)r0 * row;
         R.src0 = d_d0 ? d_d0 + (size_t)r0 * row : nullptr;
         R.dst = d_out + (size_t)r0 * row;
         R.sel_of = d_sel_of ? d_sel_of + r0 : nullptr;
         R.item0 = r0;
-        d_->cmux.launch(set, stream_, R);
-        return 1;
+        pc.rotate([&] {
+            d_->cmux.launch(set, stream_, R);
+            return 1;
+        });
     });
 }
 
@@ -1232,8 +1165,11 @@ void Evaluator::lut_tree_device(const TgswSet& set, size_t count, int32_t depth,
     Lane& ln = d_->lane[0];
     const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
     d_->cmux.reserve(ln.cmux, pl);
-    run_cmux_pieces(pl, count, depth, stats, [&](int64_t i0, int64_t cnt) {
-        return d_->cmux.launch_tree(set, ln.cmux, stream_, i0, cnt, depth, d_sel_of, d_tables, n_tables, d_table_of, d_out + (size_t)i0 * row);
+    run_pieces(pl.cut(), (int64_t)count, depth, stats, [&](Piece& pc) {
+        pc.rotate([&] {
+            return d_->cmux.launch_tree(set, ln.cmux, stream_, pc.first, pc.count, depth, d_sel_of, d_tables, n_tables, d_table_of,
+                                        d_out + (size_t)pc.first * row);
+        });
     });
 }
 
@@ -1246,9 +1182,12 @@ void Evaluator::lut_scatter_device(const TgswSet& set, size_t count, int32_t dep
     Lane& ln = d_->lane[0];
     const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
     d_->cmux.reserve(ln.cmux, pl);
-    run_cmux_pieces(pl, count, depth, stats, [&](int64_t i0, int64_t cnt) {
-        return d_->cmux.launch_scatter(set, ln.cmux, stream_, i0, cnt, depth, d_sel_of, d_values + (size_t)i0 * row,
-                                       d_mem ? d_mem + ((size_t)i0 << depth) * row : nullptr, d_out + ((size_t)i0 << depth) * row);
+    run_pieces(pl.cut(), (int64_t)count, depth, stats, [&](Piece& pc) {
+        const size_t i0 = (size_t)pc.first;
+        pc.rotate([&] {
+            return d_->cmux.launch_scatter(set, ln.cmux, stream_, pc.first, pc.count, depth, d_sel_of, d_values + i0 * row,
+                                           d_mem ? d_mem + (i0 << depth) * row : nullptr, d_out + (i0 << depth) * row);
+        });
     });
 }
 
@@ -1261,9 +1200,12 @@ void Evaluator::lut_write_device(const TgswSet& set, size_t count, int32_t depth
     Lane& ln = d_->lane[0];
     const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
     d_->cmux.reserve_read(ln.cmux, pl, depth);
-    run_cmux_pieces(pl, count, 2 * depth, stats, [&](int64_t i0, int64_t cnt) {
-        return d_->cmux.launch_write(set, ln.cmux, stream_, i0, cnt, depth, d_sel_of, d_new + (size_t)i0 * row, d_mem + ((size_t)i0 << depth) * row,
-                                     d_out + ((size_t)i0 << depth) * row);
+    run_pieces(pl.cut(), (int64_t)count, 2 * depth, stats, [&](Piece& pc) {
+        const size_t i0 = (size_t)pc.first;
+        pc.rotate([&] {
+            return d_->cmux.launch_write(set, ln.cmux, stream_, pc.first, pc.count, depth, d_sel_of, d_new + i0 * row, d_mem + (i0 << depth) * row,
+                                         d_out + (i0 << depth) * row);
+        });
     });
 }
 
@@ -1288,14 +1230,17 @@ void Evaluator::lut_add_device(const TgswSet& set, size_t count, int32_t depth, 
     Lane& ln = d_->lane[0];
     const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
     d_->cmux.reserve_read(ln.cmux, pl, depth);
-    run_cmux_pieces(pl, count, depth + steps, stats, [&](int64_t i0, int64_t cnt) {
-        return d_->cmux.launch_add(set, ln.cmux, stream_, i0, cnt, depth, steps, d_sel_of, d_amount_of, d_values + (size_t)i0 * row, n_mems, d_mem_of,
-                                   d_out);
+    run_pieces(pl.cut(), (int64_t)count, depth + steps, stats, [&](Piece& pc) {
+        pc.rotate([&] {
+            return d_->cmux.launch_add(set, ln.cmux, stream_, pc.first, pc.count, depth, steps, d_sel_of, d_amount_of, d_values + (size_t)pc.first * row,
+                                       n_mems, d_mem_of, d_out);
+        });
     });
 }
 
 // Automata (section 3k).  The call stands beside the table of set_calls.h (automaton_plan.h says why), so its prelude is written
-// out here: owners, n_finals, the overlap of the output with any input, begin_call(), null rows -- begin_set_call's order.
+// out here: owners, n_finals, the overlap of the output with any input, begin_call(), null rows -- begin_set_call's order.  Its
+// pieces go through the piece loop like every other call's.
 Automaton* Evaluator::automaton_create(int32_t states, int32_t steps, int32_t n_out, const int32_t* next0, const int32_t* next1) {
     HIP_CHECK(hipSetDevice(device_));
     return d_->cmux.automaton_create(states, steps, n_out, next0, next1);
@@ -1326,12 +1271,11 @@ void Evaluator::automaton_run_device(const TgswSet& set, const Automaton& a, siz
     Lane& ln = d_->lane[0];
     const AutomatonPlan pl = automaton_plan((int64_t)count, a.states, a.steps, d_->opt.cmux_piece_rows, d_->opt.automaton_steps_per_launch);
     d_->cmux.reserve_automaton(ln.cmux, pl);
-    CmuxPlan pieces;  // the piece loop's view of the cut
-    pieces.items_per_piece = pl.items_per_piece;
-    pieces.pieces = pl.pieces;
-    run_cmux_pieces(pieces, count, a.steps, stats, [&](int64_t i0, int64_t cnt) {
-        return d_->cmux.launch_automaton(set, a, ln.cmux, stream_, pl, i0, cnt, d_sel_of, d_finals, n_finals, d_final_of,
-                                         d_out + (size_t)i0 * (size_t)a.n_out * row);
+    run_pieces(pl.cut(), (int64_t)count, a.steps, stats, [&](Piece& pc) {
+        pc.rotate([&] {
+            return d_->cmux.launch_automaton(set, a, ln.cmux, stream_, pl, pc.first, pc.count, d_sel_of, d_finals, n_finals, d_final_of,
+                                             d_out + (size_t)pc.first * (size_t)a.n_out * row);
+        });
     });
 }
 
@@ -1340,17 +1284,20 @@ void Evaluator::tlwe_rotate_device(const TgswSet& set, size_t count, int32_t ste
                                    const Torus32* d_in, Torus32* d_out, EvalStats* stats) {
     const size_t row = (size_t)2 * (size_t)p_.N;
     if (!begin_set_call(set, SetCall{kCallTlweRotate, count, 0, steps}, {d_sel_of, d_amount_of, d_in, d_out}, row)) return;
-    run_cmux_pieces(cmux_plan((int64_t)count, -1, d_->opt.cmux_piece_rows), count, steps, stats, [&](int64_t r0, int64_t rows) {
+    run_pieces(cmux_plan((int64_t)count, -1, d_->opt.cmux_piece_rows).cut(), (int64_t)count, steps, stats, [&](Piece& pc) {
+        const int64_t r0 = pc.first;
         RotateRows R;
-        R.rows = rows;
+        R.rows = pc.count;
         R.src = d_in + (size_t)r0 * row;
         R.dst = d_out + (size_t)r0 * row;
         R.sel_of = d_sel_of;
         R.amount_of = d_amount_of;
         R.item0 = r0;
         R.steps = R.sel_stride = steps;
-        d_->cmux.launch_rotate(set, stream_, R);
-        return 1;
+        pc.rotate([&] {
+            d_->cmux.launch_rotate(set, stream_, R);
+            return 1;
+        });
     });
 }
 
@@ -1377,16 +1324,16 @@ void Evaluator::lut_read_device(const TgswSet& set, size_t count, int32_t depth,
     W.flat_type = kFlatRaw;
     // the extracted rows of a piece: the caller's, or the lane's for the key switch
     auto rows_of = [&](int64_t i0) { return woks ? d_out + (size_t)i0 * out_stride : (Torus32*)ln.ext; };
-    run_cmux_pieces(
-        pl, count, depth + steps, stats,
-        [&](int64_t i0, int64_t cnt) {
-            return d_->cmux.launch_read(set, ln.cmux, stream_, i0, cnt, depth, steps, d_sel_of, d_amount_of, d_tables, n_tables, d_table_of, coef,
-                                        rows_of(i0), extract_stride());
-        },
-        woks ? 0 : ks_piece,
-        [&](int64_t i0, int64_t done, int64_t run) {
-            launch_keyswitch(d_, ln, rows_desc(W, i0 + done), run, rows_of(i0) + (size_t)done * (size_t)extract_stride(), nullptr);
+    run_pieces(pl.cut(), (int64_t)count, depth + steps, stats, [&](Piece& pc) {
+        pc.rotate([&] {
+            return d_->cmux.launch_read(set, ln.cmux, stream_, pc.first, pc.count, depth, steps, d_sel_of, d_amount_of, d_tables, n_tables, d_table_of,
+                                        coef, rows_of(pc.first), extract_stride());
         });
+        if (woks) return;
+        pc.keyswitch(pc.count, ks_piece, [&](int64_t done, int64_t run) {
+            launch_keyswitch(d_, ln, rows_desc(W, pc.first + done), run, rows_of(pc.first) + (size_t)done * (size_t)extract_stride(), nullptr);
+        });
+    });
 }
 
 void Evaluator::tlwe_extract_device(size_t count, const Torus32* d_tlwe, const int32_t* d_coef_of, Torus32* d_u, EvalStats* stats) {
@@ -1395,17 +1342,11 @@ void Evaluator::tlwe_extract_device(size_t count, const Torus32* d_tlwe, const i
     begin_call();
     if (count == 0) return;
     if (!d_tlwe || !d_u) throw std::invalid_argument("tlwe_extract: null rows");
-    Timer tall(stats != nullptr, stream_), tbr(false, stream_), tks(false, stream_);
-    tall.mark();
-    d_->cmux.launch_extract(stream_, (int64_t)count, d_tlwe, d_coef_of, d_u, extract_stride());
-    HIP_CHECK(hipGetLastError());
-    tall.mark();
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    add_times(stats, tall, tbr, tks);
-    if (stats) {
-        stats->chunks++;
-        stats->levels += 1;
-    }
+    // one piece whose one launch belongs to neither kind of phase: it is timed in total_ms alone and counted nowhere
+    run_pieces(Cut{1, (int64_t)count}, (int64_t)count, 1, stats, [&](Piece&) {
+        d_->cmux.launch_extract(stream_, (int64_t)count, d_tlwe, d_coef_of, d_u, extract_stride());
+        HIP_CHECK(hipGetLastError());
+    });
 }
 
 void Evaluator::eval_circuit_device(const Circuit& c, size_t batch, const Torus32* d_in, Torus32* d_out, EvalStats* stats) {

@@ -25,6 +25,11 @@ struct Pack {
     void set_key(int32_t t, int32_t basebit, const int32_t* pk, hipStream_t stream);
     bool has_key() const { return limbs_ != nullptr; }
     int32_t t() const { return t_; }
+    // the cut of a call of `groups` groups of m rows with this object's key (pack_plan on its parameter set, which for the
+    // projection is project_plan): piece_rows_opt "pack_piece_rows", split_opt the object's forced split, cus the device's
+    PackPlan plan(int64_t groups, int32_t m, int64_t piece_rows_opt, int32_t split_opt, int64_t cus) const {
+        return pack_plan(p_, t_, groups, m, piece_rows_opt, split_opt, cus);
+    }
     // scratch for every piece of the plan ahead of the loop, so that no piece allocates
     void reserve(PackScratch& scratch, const PackPlan& pl);
     // one piece: `groups` groups of m rows of `stride` words (n + 1 read) -> out [groups][2][N]

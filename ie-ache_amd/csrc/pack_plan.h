@@ -12,6 +12,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "cmux_plan.h"
 #include "params.h"
 
 namespace ieache {
@@ -61,13 +62,8 @@ struct PackPlan {
     int32_t k_steps = 0, ksplit = 0;
     size_t r_bytes = 0;       // scratch every piece fits: R [piece_rows][2][N] int32
     size_t digit_bytes = 0;   //   and the digits [k_steps][padded_rows][32] int8
+    Cut cut() const { return {pieces, groups_per_piece}; }  // of the groups (cmux_plan.h)
 };
-// groups [first, first + count) of piece `i`
-inline int64_t pack_piece_first(const PackPlan& pl, int64_t i) { return i * pl.groups_per_piece; }
-inline int64_t pack_piece_groups(const PackPlan& pl, int64_t groups, int64_t i) {
-    const int64_t left = groups - pack_piece_first(pl, i);
-    return left < pl.groups_per_piece ? left : pl.groups_per_piece;
-}
 
 // A call of `groups` groups of `m` rows.  piece_rows_opt: "pack_piece_rows" (1 .. kPackPieceRows); split_opt: "pack_split",
 // 0 = by size; cus: compute units of the device (<= 0: 256).

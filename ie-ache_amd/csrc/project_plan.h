@@ -44,19 +44,18 @@ inline PackPlan project_plan(const Params& p, int32_t t, int64_t items, int32_t 
     return pack_plan(project_params(p), t, items, width, piece_rows_opt, split_opt, cus);
 }
 // runs of the projection inside a piece of `items` items of a replace write whose plan `pl` was made for the largest piece
-inline int64_t project_runs(const PackPlan& pl, int64_t items) {
-    return items <= 0 || pl.groups_per_piece <= 0 ? 0 : (items + pl.groups_per_piece - 1) / pl.groups_per_piece;
-}
+inline int64_t project_runs(const PackPlan& pl, int64_t items) { return cut_in_runs(items, pl.groups_per_piece).pieces; }
 
 // Why the scalars of a replace write of a window are refused, or null: depth and steps as for lut_add, width >= 1,
-// width <= unit, unit 2^steps <= N (so that every word lies inside one sample and the amounts stay below N).
+// width <= unit, unit 2^steps <= N (so that every word lies inside one sample and the amounts stay below N).  THE statement
+// of these rules: the call's row of set_calls.h refuses by it (set_call_refusal).
 static_assert(kCmuxMaxDepth == 12 && kRotateMaxSteps == 64, "the messages below spell the limits out");
-inline const char* write_coef_error(const Params& p, int32_t depth, int32_t steps, int32_t width, int32_t unit) {
+inline const char* write_coef_error(int32_t N, int32_t depth, int32_t steps, int32_t width, int32_t unit) {
     if (depth < 0 || depth > kCmuxMaxDepth) return "lut_write_coef: depth must lie in 0 .. 12";
     if (steps < 0 || steps > kRotateMaxSteps) return "lut_write_coef: steps must lie in 0 .. 64";
     if (width < 1) return "lut_write_coef: width must be at least 1";
     if (unit < width) return "lut_write_coef: unit must be at least width";
-    if (steps > 30 || ((int64_t)unit << steps) > p.N) return "lut_write_coef: unit x 2^steps must not exceed N";
+    if (steps > 30 || ((int64_t)unit << steps) > N) return "lut_write_coef: unit x 2^steps must not exceed N";
     return nullptr;
 }
 // the public amount of step t of the two rotations: the read brings coefficient unit sum b_t 2^t to position 0, the write

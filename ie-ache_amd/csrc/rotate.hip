@@ -232,6 +232,17 @@ __global__ __launch_bounds__(256) void k_read_indices(const int32_t* __restrict_
     tree_sel[q] = (int32_t)selector_at(sel_of, (item0 + item) * (depth + steps) + steps + k, n_set);
 }
 
+// selectors steps .. steps + depth - 1 of items item0 .. of the call, explicit, as the piece's own array tree_sel [items][depth],
+// and `coef` once per item in the `items` words after it (with_coef: written at depth 0 as well; otherwise not read).  Not
+// counted as a launch of the call's.
+void launch_read_indices(hipStream_t stream, const int32_t* sel_of, int64_t item0, int64_t items, int32_t depth, int32_t steps, int32_t n_set,
+                         bool with_coef, int32_t coef, int32_t* tree_sel) {
+    const int64_t words = items * (with_coef && depth < 1 ? 1 : depth);
+    if (words <= 0) return;
+    hipLaunchKernelGGL(k_read_indices, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, sel_of, item0, items, depth, steps, n_set, coef,
+                       tree_sel, tree_sel + (size_t)items * depth);
+}
+
 constexpr size_t kRotateLds = (size_t)kCmuxWaveRows * 2 * kN * 4 + ((size_t)kCmuxWaveRows * kTile + kTwElems) * sizeof(double2);
 LdsGrant g_rotate_grant[3];  // one per build: cmux_step.h's with_gadget
 
@@ -267,26 +278,41 @@ int Cmux::launch_read(const TgswSet& set, CmuxScratch& scratch, hipStream_t stre
     if (scratch.rows.items() < (size_t)items * 2 * kN || scratch.idx.items() < (size_t)items * (size_t)(depth + 1))
         throw std::invalid_argument("lut_read: piece larger than the reserved scratch");
     int32_t* tree_sel = scratch.idx;
-    int32_t* coef_of = tree_sel + (size_t)items * depth;
-    const int64_t words = items * (depth > 1 ? depth : 1);
-    hipLaunchKernelGGL(k_read_indices, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, sel_of, item0, items, depth, steps, (int32_t)set.n,
-                       coef < 0 ? 0 : (coef >= p_.N ? p_.N - 1 : coef), tree_sel, coef_of);
+    launch_read_indices(stream, sel_of, item0, items, depth, steps, (int32_t)set.n, true, coef < 0 ? 0 : (coef >= p_.N ? p_.N - 1 : coef), tree_sel);
     // the tree sees a piece of its own: items 0 .. items - 1 with their explicit selectors, but the call's table_of
     int launches = 1 + launch_tree(set, scratch, stream, 0, items, depth, tree_sel, tables, n_tables, table_of ? table_of + item0 : nullptr, scratch.rows);
-    if (steps > 0) {
-        RotateRows R;
-        R.src = R.dst = scratch.rows;
-        R.rows = items;
-        R.item0 = item0;
-        R.sel_of = sel_of;
-        R.amount_of = amount_of;
-        R.steps = steps;
-        R.sel_stride = depth + steps;
-        launch_rotate(set, stream, R);
-        launches++;
-    }
-    launch_extract(stream, items, scratch.rows, coef_of, u, stride);
+    launches += launch_rotate_selected(set, scratch, stream, item0, items, depth, steps, sel_of, amount_of);
+    launch_extract(stream, items, scratch.rows, tree_sel + (size_t)items * depth, u, stride);
     return launches + 1;
+}
+
+int Cmux::launch_rotate_selected(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, int32_t steps,
+                                 const int32_t* sel_of, const int32_t* amount_of) {
+    if (steps <= 0) return 0;
+    RotateRows R;
+    R.src = R.dst = scratch.rows;
+    R.rows = items;
+    R.item0 = item0;
+    R.sel_of = sel_of;
+    R.amount_of = amount_of;
+    R.steps = steps;
+    R.sel_stride = depth + steps;
+    launch_rotate(set, stream, R);
+    return 1;
+}
+
+int Cmux::launch_read_own(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, int32_t steps,
+                          const int32_t* sel_of, const int32_t* amount_of, const int32_t* mem) {
+    check_owner(set);
+    if (items <= 0) return 0;
+    if (depth < 0 || depth > kCmuxMaxDepth || steps < 0 || steps > kRotateMaxSteps) throw std::invalid_argument("lut_write_coef: depth or steps out of range");
+    if (scratch.rows.items() < (size_t)items * 2 * kN || scratch.idx.items() < (size_t)items * (size_t)(depth + 1))
+        throw std::invalid_argument("lut_write_coef: piece larger than the reserved scratch");
+    int32_t* tree_sel = scratch.idx;
+    launch_read_indices(stream, sel_of, item0, items, depth, steps, (int32_t)set.n, false, 0, tree_sel);
+    // the tree sees a piece of its own, as launch_read's does
+    const int tree = launch_own_tree(set, scratch, stream, 0, items, depth, tree_sel, mem, scratch.rows, "lut_write_coef: piece larger than the reserved scratch");
+    return tree + launch_rotate_selected(set, scratch, stream, item0, items, depth, steps, sel_of, amount_of);
 }
 
 int Cmux::launch_add(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, int32_t steps,
@@ -323,13 +349,7 @@ int Cmux::launch_add(const TgswSet& set, CmuxScratch& scratch, hipStream_t strea
         parents = scratch.rows;
     }
     int32_t* tree_sel = scratch.idx;
-    if (depth > 0) {
-        // selectors steps .. steps + depth - 1 of each item, explicit, for the piece alone; the coefficient array it also writes
-        // (items words after them) is not read
-        const int64_t words = items * depth;
-        hipLaunchKernelGGL(k_read_indices, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, sel_of, item0, items, depth, steps, (int32_t)set.n, 0,
-                           tree_sel, tree_sel + (size_t)items * depth);
-    }
+    launch_read_indices(stream, sel_of, item0, items, depth, steps, (int32_t)set.n, false, 0, tree_sel);
     return launches + launch_scatter_acc(set, scratch, stream, items, depth, tree_sel, parents, mem_of ? mem_of + item0 : nullptr, n_mems, out);
 }
 

@@ -1,5 +1,5 @@
-// The calls on caller TGSW sets (include/ieache.h sections 3f to 3j: cmux, lut_tree, lut_scatter, lut_write, tlwe_rotate,
-// lut_read, lut_add): THE statement of what such a call is -- its scalars and their refusal, and its arguments as plain data.
+// The calls on caller TGSW sets (include/ieache.h sections 3f to 3j and 3l: cmux, lut_tree, lut_scatter, lut_write, tlwe_rotate,
+// lut_read, lut_add, lut_write_coef): THE statement of what such a call is -- its scalars and their refusal, and its arguments as plain data.
 // The C ABI's device, host and reference forms (capi.cpp) and the evaluator's prelude (Evaluator::begin_set_call) loop over
 // this table; nothing else states a size, a bound or a rule of these calls.  How a call is cut into pieces is cmux_plan.h.
 // Free of HIP so that the CPU tests can check it (tests/native/set_calls_test.cpp).
@@ -10,10 +10,11 @@
 #include <string>
 
 #include "cmux_plan.h"
+#include "project_plan.h"
 
 namespace ieache {
 
-enum SetCallKind : int32_t { kCallCmux, kCallLutTree, kCallLutScatter, kCallLutWrite, kCallTlweRotate, kCallLutRead, kCallLutAdd, kSetCallKinds };
+enum SetCallKind : int32_t { kCallCmux, kCallLutTree, kCallLutScatter, kCallLutWrite, kCallTlweRotate, kCallLutRead, kCallLutAdd, kCallLutWriteCoef, kSetCallKinds };
 // The scalars of a call; what a call does not take stays as it is here.
 struct SetCall {
     SetCallKind kind;
@@ -21,6 +22,7 @@ struct SetCall {
     int32_t depth = 0, steps = 0;
     int32_t n_sets = 1;  // n_tables (lut_tree, lut_read) or n_mems (lut_add)
     int32_t flags = 0, coef = 0;  // lut_read; coef is an index under N that the host and reference forms check after the arrays
+    int32_t width = 0, unit = 0;  // lut_write_coef: the window's words and the distance between two addressed words
 };
 
 enum SetArgKind : int8_t { kArgRows, kArgIndices };
@@ -50,6 +52,8 @@ struct SetCallShape {
     const char* in_place;  // what the overlap refusal calls the accepted alias, or null
     int n_args;
     SetArg args[kSetCallMaxArgs];  // in the order of the signature; the output is the last
+    bool window = false;   // it takes width and unit and needs the context's projection key: "<name>: no projection key set"
+                           // after the context, set and null checks and before the scalars, which write_coef_error judges
 };
 
 // an index array: always optional
@@ -81,15 +85,23 @@ constexpr SetCallShape kSetCalls[kSetCallKinds] = {
     {"lut_add", true, true, "n_mems", 0, "write", 6,
      {kSelOf, kAmountOf, arg_rows("d_values", kSizeItems, kWithItems, kAtRowsA), arg_rows("d_mems", kSizeTables, kOptional, kAtResult, kMayBeOutput, true),
       arg_indices("d_mem_of", kSizeItems, kBoundSets, kAtIndicesA), arg_out(kSizeTables, true)}},
+    // lut_write's arguments with `steps` more selectors per item; a call without items takes null rows, the output included
+    {"lut_write_coef", true, true, nullptr, 0, "write", 4,
+     {kSelOf, arg_rows("d_new", kSizeItems, kWithItems, kAtRowsA), arg_rows("d_mem", kSizeLeaves, kWithItems, kAtResult, kMayBeOutput),
+      arg_rows("d_out", kSizeLeaves, kWithItems, kAtNone, kOutput)}, true},
 };
 using SetPtrs = std::initializer_list<const void*>;  // a call's pointer arguments in the order of `args`: entry i is begin()[i]
 inline const SetArg& set_call_output(const SetCall& c) { return kSetCalls[c.kind].args[kSetCalls[c.kind].n_args - 1]; }
 
 // The first rule the scalars break as the message of the refusal, or empty: depth, then steps, then the table or memory count,
-// then the flags.
+// then the flags; a call with a window: write_coef_error's rules in its order and words (project_plan.h).  N: the ring's.
 static_assert(kCmuxMaxDepth == 12 && kRotateMaxSteps == 64, "the messages below spell the limits out");
-inline std::string set_call_refusal(const SetCall& c) {
+inline std::string set_call_refusal(const SetCall& c, int32_t N) {
     const SetCallShape& s = kSetCalls[c.kind];
+    if (s.window) {
+        const char* e = write_coef_error(N, c.depth, c.steps, c.width, c.unit);
+        return e ? std::string(e) : std::string();
+    }
     const bool depth = s.depth && (c.depth < 0 || c.depth > kCmuxMaxDepth), steps = s.steps && (c.steps < 0 || c.steps > kRotateMaxSteps);
     const bool sets = s.sets && c.n_sets < 1;
     if (!depth && !steps && !sets && !(c.flags & ~s.known_flags)) return std::string();  // no string is built for a call that passes

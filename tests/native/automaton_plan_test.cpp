@@ -108,13 +108,13 @@ static int pieces_and_chunks() {
                         CHECK(pl.pieces >= 1 && pl.items_per_piece >= 1);
                         int64_t seen = 0;
                         for (int64_t i = 0; i < pl.pieces; i++) {
-                            const int64_t first = automaton_piece_first(pl, i), cnt = automaton_piece_items(pl, items, i);
+                            const int64_t first = piece_first(pl.cut(), i), cnt = piece_count(pl.cut(), items, i);
                             CHECK(first == seen && cnt >= 1 && cnt <= pl.items_per_piece);
                             CHECK(cnt * 2 * states <= eff || cnt == 1);
                             seen += cnt;
                         }
                         CHECK(seen == items);
-                        CHECK(automaton_piece_items(pl, items, pl.pieces) <= 0);
+                        CHECK(piece_count(pl.cut(), items, pl.pieces) <= 0);
                         CHECK(pl.scratch_rows == (steps >= 2 ? pl.items_per_piece * 2 * states : 0));
                         // the chunks cover steps-1 .. 0 once, in that order
                         if (steps == 0) {

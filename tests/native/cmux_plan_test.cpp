@@ -23,7 +23,7 @@ static void check(int64_t items, int32_t depth, int64_t cap_opt) {
     CHECK(pl.pieces >= 1 && pl.items_per_piece >= 1 && pl.items_per_piece <= items);
     int64_t next = 0;
     for (int64_t i = 0; i < pl.pieces; i++) {
-        const int64_t first = cmux_piece_first(pl, i), cnt = cmux_piece_items(pl, items, i);
+        const int64_t first = piece_first(pl.cut(), i), cnt = piece_count(pl.cut(), items, i);
         CHECK(first == next && cnt >= 1);
         // the cap, unless one item alone is wider
         CHECK(cnt * per_item <= cap || cnt == 1);

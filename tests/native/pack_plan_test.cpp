@@ -32,7 +32,7 @@ static int check_pieces(const Params& p, int32_t t, int64_t groups, int32_t m, i
     // whole groups, each row in exactly one piece
     std::vector<int> seen((size_t)(groups * m), 0);
     for (int64_t i = 0; i < pl.pieces; i++) {
-        const int64_t g0 = pack_piece_first(pl, i), cnt = pack_piece_groups(pl, groups, i);
+        const int64_t g0 = piece_first(pl.cut(), i), cnt = piece_count(pl.cut(), groups, i);
         CHECK(cnt >= 1 && g0 + cnt <= groups);
         const int64_t rows = cnt * m, rpad = pack_padded_rows(rows);
         // the reserved sizes bound the piece, and the piece stays under the named constant unless one group alone is longer

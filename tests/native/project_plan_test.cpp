@@ -35,7 +35,7 @@ static int check_cut(const Params& p, int32_t t, int64_t items, int32_t width, i
     const int64_t cap = piece_opt >= 1 && piece_opt <= kPackPieceRows ? piece_opt : kPackPieceRows;
     std::vector<int> seen((size_t)items, 0);
     for (int64_t i = 0; i < pl.pieces; i++) {
-        const int64_t i0 = pack_piece_first(pl, i), cnt = pack_piece_groups(pl, items, i);
+        const int64_t i0 = piece_first(pl.cut(), i), cnt = piece_count(pl.cut(), items, i);
         CHECK(cnt >= 1 && i0 + cnt <= items);
         const int64_t rows = cnt * width, rpad = pack_padded_rows(rows);
         CHECK(rows <= cap || cnt == 1);
@@ -48,8 +48,8 @@ static int check_cut(const Params& p, int32_t t, int64_t items, int32_t width, i
         const int64_t runs = project_runs(pl, piece_items);
         int64_t covered = 0;
         for (int64_t r = 0; r < runs; r++) {
-            const int64_t g = pack_piece_groups(pl, piece_items, r);
-            CHECK(g >= 1 && g <= pl.groups_per_piece && pack_piece_first(pl, r) == covered);
+            const int64_t g = piece_count(pl.cut(), piece_items, r);
+            CHECK(g >= 1 && g <= pl.groups_per_piece && piece_first(pl.cut(), r) == covered);
             covered += g;
         }
         CHECK(covered == piece_items);
@@ -76,13 +76,13 @@ static int check_accepted() {
     CHECK(says(project_call_error(p, 0, 1, -1), "dest") && says(project_call_error(p, 0, 1, 2048), "dest"));
     CHECK(!project_call_error(set(5, 16), 15, 1, 31) && project_call_error(set(5, 16), 15, 2, 0) && project_call_error(set(5, 16), 0, 1, 32));
     // the write's scalars
-    CHECK(!write_coef_error(p, 0, 0, 1, 1) && !write_coef_error(p, 12, 10, 1, 1) && !write_coef_error(p, 4, 5, 32, 32) && !write_coef_error(p, 0, 0, 1024, 1024));
-    CHECK(says(write_coef_error(p, -1, 0, 1, 1), "depth") && says(write_coef_error(p, 13, 0, 1, 1), "depth"));
-    CHECK(says(write_coef_error(p, 0, -1, 1, 1), "steps") && says(write_coef_error(p, 0, 65, 1, 1), "steps"));
-    CHECK(says(write_coef_error(p, 0, 0, 0, 1), "width") && says(write_coef_error(p, 0, 0, 4, 3), "unit must"));
-    CHECK(says(write_coef_error(p, 0, 11, 1, 1), "exceed N") && says(write_coef_error(p, 0, 5, 32, 33), "exceed N") &&
-          says(write_coef_error(p, 0, 64, 1, 1), "exceed N") && says(write_coef_error(p, 0, 31, 1, 1), "exceed N") &&
-          says(write_coef_error(p, 0, 1, 1, 2147483647), "exceed N"));
+    CHECK(!write_coef_error(p.N, 0, 0, 1, 1) && !write_coef_error(p.N, 12, 10, 1, 1) && !write_coef_error(p.N, 4, 5, 32, 32) && !write_coef_error(p.N, 0, 0, 1024, 1024));
+    CHECK(says(write_coef_error(p.N, -1, 0, 1, 1), "depth") && says(write_coef_error(p.N, 13, 0, 1, 1), "depth"));
+    CHECK(says(write_coef_error(p.N, 0, -1, 1, 1), "steps") && says(write_coef_error(p.N, 0, 65, 1, 1), "steps"));
+    CHECK(says(write_coef_error(p.N, 0, 0, 0, 1), "width") && says(write_coef_error(p.N, 0, 0, 4, 3), "unit must"));
+    CHECK(says(write_coef_error(p.N, 0, 11, 1, 1), "exceed N") && says(write_coef_error(p.N, 0, 5, 32, 33), "exceed N") &&
+          says(write_coef_error(p.N, 0, 64, 1, 1), "exceed N") && says(write_coef_error(p.N, 0, 31, 1, 1), "exceed N") &&
+          says(write_coef_error(p.N, 0, 1, 1, 2147483647), "exceed N"));
     // the amounts: the read's and the write's of a step cancel mod 2N
     for (int32_t unit : {1, 3, 32})
         for (int32_t s = 0; ((int64_t)unit << s) <= p.N; s++) {

@@ -1,7 +1,7 @@
-// csrc/set_calls.h on its own (no HIP): for each of the seven calls on a set the refusal of its scalars -- exact messages, the
+// csrc/set_calls.h on its own (no HIP): for each of the eight calls on a set the refusal of its scalars -- exact messages, the
 // first failing rule when two are broken -- the words of every argument at a few scalars, and which arguments are optional,
-// which one may be the output, and every bound.  The expectations restate include/ieache.h sections 3f to 3j on purpose: they
-// are the second statement that keeps the header's honest.  Built with AddressSanitizer + UBSan by tests/test_set_calls_cpu.py.
+// which one may be the output, and every bound.  The expectations restate include/ieache.h sections 3f to 3j, and 3l for the
+// eighth (lut_write_coef, whose block is write_coef() below), on purpose: they are the second statement that keeps the header's honest.  Built with AddressSanitizer + UBSan by tests/test_set_calls_cpu.py.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,6 +21,10 @@ using namespace ieache;
 
 static const int N = 1024;
 static const size_t ROW = 2048, LWE = 632, N_SET = 5;  // words of a TLWE row and of lut_read's output row; samples of the set
+static const int kSeven = kCallLutWriteCoef;  // the calls of sections 3f to 3j, which the three blocks after this one walk
+static_assert(kSeven == 7 && kSetCallKinds == 8, "seven calls sized by (count, depth, steps, n_sets) alone, and the write of a window");
+// every scalar refusal at the test's ring
+static std::string set_call_refusal(const SetCall& c) { return ieache::set_call_refusal(c, N); }
 
 static const SetArg& arg(SetCallKind k, const char* name) {
     const SetCallShape& s = kSetCalls[k];
@@ -69,10 +73,10 @@ static const Want kWant[] = {
 };
 
 static void shapes() {
-    const char* names[kSetCallKinds] = {"cmux", "lut_tree", "lut_scatter", "lut_write", "tlwe_rotate", "lut_read", "lut_add"};
-    const int n_args[kSetCallKinds] = {4, 4, 4, 4, 4, 5, 6};
-    int seen[kSetCallKinds] = {};
-    for (int k = 0; k < kSetCallKinds; k++) {
+    const char* names[kSeven] = {"cmux", "lut_tree", "lut_scatter", "lut_write", "tlwe_rotate", "lut_read", "lut_add"};
+    const int n_args[kSeven] = {4, 4, 4, 4, 4, 5, 6};
+    int seen[kSeven] = {};
+    for (int k = 0; k < kSeven; k++) {
         CHECK(!strcmp(kSetCalls[k].name, names[k]) && kSetCalls[k].n_args == n_args[k] && n_args[k] <= kSetCallMaxArgs);
         CHECK(&set_call_output(call((SetCallKind)k, 1)) == &kSetCalls[k].args[n_args[k] - 1]);
     }
@@ -86,11 +90,11 @@ static void shapes() {
         CHECK((a.bound == kBoundNone) == (w.bound < 0));
         if (w.bound >= 0) CHECK(set_arg_bound(c, a, N, N_SET) == w.bound);
     }
-    for (int k = 0; k < kSetCallKinds; k++) CHECK(seen[k] == n_args[k]);
+    for (int k = 0; k < kSeven; k++) CHECK(seen[k] == n_args[k]);
     // lut_add's values are required only with items, and an empty lut_add touches its memories and its output; nothing else is so
     const SetArg& v = arg(kCallLutAdd, "d_values");
     CHECK(v.need == kWithItems && !set_arg_required(call(kCallLutAdd, 0), v) && set_arg_required(call(kCallLutAdd, 1), v));
-    for (int k = 0; k < kSetCallKinds; k++)
+    for (int k = 0; k < kSeven; k++)
         for (int i = 0; i < kSetCalls[k].n_args; i++) {
             const SetArg& a = kSetCalls[k].args[i];
             CHECK(a.empty_too == (k == kCallLutAdd && (!strcmp(a.name, "d_mems") || !strcmp(a.name, "d_out"))));
@@ -99,7 +103,7 @@ static void shapes() {
 }
 
 static void refusals() {
-    for (int k = 0; k < kSetCallKinds; k++) {
+    for (int k = 0; k < kSeven; k++) {
         const SetCallKind kind = (SetCallKind)k;
         const std::string name = kSetCalls[k].name;
         const bool has_depth = k != kCallCmux && k != kCallTlweRotate, has_steps = k == kCallTlweRotate || k == kCallLutRead || k == kCallLutAdd;
@@ -137,7 +141,7 @@ static void sizes() {
     CHECK(words(call(kCallLutAdd, 0, 2, 10, 3), "d_mems") == 24576 && words(call(kCallLutAdd, 0, 2, 10, 3), "d_out") == 24576);
     CHECK(words(call(kCallLutAdd, 0, 2, 10, 3), "d_values") == 0 && words(call(kCallLutAdd, 0, 2, 10, 3), "d_mem_of") == 0);
     // count = 1, depth 0, steps 0
-    for (int k = 0; k < kSetCallKinds; k++) {
+    for (int k = 0; k < kSeven; k++) {
         const SetCall c = call((SetCallKind)k, 1);
         CHECK(words(c, "d_sel_of") == (k == kCallCmux ? 1u : 0u));
         CHECK(words(c, "d_out") == (k == kCallLutRead ? LWE : ROW));
@@ -174,10 +178,71 @@ static void sizes() {
     CHECK(words(call(kCallLutTree, 3, 2, 7, 1), "d_sel_of") == 6 && words(call(kCallLutScatter, 3, 2, 7), "d_sel_of") == 6);
 }
 
+// The eighth call, the replace write of a window (include/ieache.h section 3l): lut_write's arguments with `steps` more selectors
+// per item, the scalars width and unit, and the projection key (which the forms ask the context for: `window` marks it).
+static SetCall coef_call(size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit) {
+    SetCall c = call(kCallLutWriteCoef, count, depth, steps);
+    c.width = width, c.unit = unit;
+    return c;
+}
+static void write_coef() {
+    const SetCallShape& s = kSetCalls[kCallLutWriteCoef];
+    CHECK(!strcmp(s.name, "lut_write_coef") && s.n_args == 4 && s.depth && s.steps && !s.sets && s.known_flags == 0 && s.window && !strcmp(s.in_place, "write"));
+    for (int k = 0; k < kSeven; k++) CHECK(!kSetCalls[k].window);
+    // the arguments in the order of the signature: sel_of optional and bounded by the set; new, mem and out needed only with
+    // items; mem may be the output exactly and is staged at the result; nothing is touched by a call without items
+    const char* names[4] = {"d_sel_of", "d_new", "d_mem", "d_out"};
+    for (int i = 0; i < 4; i++) CHECK(!strcmp(s.args[i].name, names[i]) && !s.args[i].empty_too);
+    CHECK(&set_call_output(coef_call(1, 0, 0, 1, 1)) == &s.args[3] && s.args[3].role == kOutput && s.args[3].kind == kArgRows);
+    const SetArg &sel = s.args[0], &fresh = s.args[1], &mem = s.args[2], &out = s.args[3];
+    CHECK(sel.kind == kArgIndices && sel.need == kOptional && sel.role == kInput && sel.size == kSizeSelectors);
+    CHECK(set_arg_bound(coef_call(3, 2, 2, 1, 1), sel, N, N_SET) == (int64_t)N_SET);
+    CHECK(fresh.kind == kArgRows && fresh.role == kInput && fresh.bound == kBoundNone && fresh.stage == kAtRowsA);
+    CHECK(mem.kind == kArgRows && mem.role == kMayBeOutput && mem.bound == kBoundNone && mem.stage == kAtResult);
+    for (const SetArg* a : {&fresh, &mem, &out}) {
+        CHECK(a->need == kWithItems && set_arg_required(coef_call(1, 0, 0, 1, 1), *a) && !set_arg_required(coef_call(0, 0, 0, 1, 1), *a));
+    }
+    CHECK(!set_arg_required(coef_call(1, 0, 0, 1, 1), sel));
+    // every scalar rule with its exact message
+    const char *depth_msg = "lut_write_coef: depth must lie in 0 .. 12", *steps_msg = "lut_write_coef: steps must lie in 0 .. 64";
+    const char *width_msg = "lut_write_coef: width must be at least 1", *unit_msg = "lut_write_coef: unit must be at least width";
+    const char* span_msg = "lut_write_coef: unit x 2^steps must not exceed N";
+    for (int32_t d : {-1, 0, 12, 13}) CHECK(is(set_call_refusal(coef_call(1, d, 0, 1, 1)), d < 0 || d > 12 ? depth_msg : ""));
+    for (int32_t t : {-1, 65}) CHECK(is(set_call_refusal(coef_call(1, 0, t, 1, 1)), steps_msg));
+    for (int32_t w : {-1, 0}) CHECK(is(set_call_refusal(coef_call(1, 0, 0, w, 1)), width_msg));
+    CHECK(is(set_call_refusal(coef_call(1, 0, 0, 4, 3)), unit_msg) && is(set_call_refusal(coef_call(1, 0, 0, 4, 4)), ""));
+    // unit 2^steps against N = 1024: 10 steps of unit 1 and 5 of unit 32 fill a sample; one more, or steps the shift cannot take, do not
+    CHECK(is(set_call_refusal(coef_call(1, 12, 10, 1, 1)), "") && is(set_call_refusal(coef_call(1, 4, 5, 32, 32)), "") && is(set_call_refusal(coef_call(0, 0, 0, 1024, 1024)), ""));
+    CHECK(is(set_call_refusal(coef_call(1, 0, 11, 1, 1)), span_msg) && is(set_call_refusal(coef_call(1, 0, 5, 32, 33)), span_msg));
+    CHECK(is(set_call_refusal(coef_call(1, 0, 31, 1, 1)), span_msg) && is(set_call_refusal(coef_call(1, 0, 64, 1, 1)), span_msg));
+    CHECK(is(set_call_refusal(coef_call(1, 0, 1, 1, 2147483647)), span_msg) && is(set_call_refusal(coef_call(1, 0, 0, 1, 1025)), span_msg));
+    CHECK(is(ieache::set_call_refusal(coef_call(1, 0, 6, 1, 1), 64), "") && is(ieache::set_call_refusal(coef_call(1, 0, 7, 1, 1), 64), span_msg));  // N is the ring's
+    // the first failing rule: depth, steps, width, unit, unit x 2^steps
+    CHECK(is(set_call_refusal(coef_call(1, 13, 65, 0, -1)), depth_msg) && is(set_call_refusal(coef_call(1, 0, 65, 0, -1)), steps_msg));
+    CHECK(is(set_call_refusal(coef_call(1, 0, 11, 0, -1)), width_msg) && is(set_call_refusal(coef_call(1, 0, 11, 2, 1)), unit_msg));
+    CHECK(is(set_call_refusal(coef_call(1, 0, 11, 2, 2)), span_msg));
+    // n_sets, flags and coef are not this call's
+    SetCall odd = coef_call(1, 0, 0, 1, 1);
+    odd.n_sets = 0, odd.flags = 6, odd.coef = -1;
+    CHECK(is(set_call_refusal(odd), ""));
+    // the words of each argument: no items; 3 items at depth 2 with 2 steps; one item at depth 0 with no steps; 2^20 items at depth 12
+    CHECK(words(coef_call(0, 2, 2, 1, 1), "d_sel_of") == 0 && words(coef_call(0, 2, 2, 1, 1), "d_new") == 0 && words(coef_call(0, 2, 2, 1, 1), "d_mem") == 0 &&
+          words(coef_call(0, 2, 2, 1, 1), "d_out") == 0);
+    const SetCall c = coef_call(3, 2, 2, 1, 1);
+    CHECK(words(c, "d_sel_of") == 12 && words(c, "d_new") == 6144 && words(c, "d_mem") == 24576 && words(c, "d_out") == 24576);
+    CHECK(words(coef_call(1, 0, 0, 1, 1), "d_sel_of") == 0 && words(coef_call(1, 0, 0, 1, 1), "d_new") == 2048 && words(coef_call(1, 0, 0, 1, 1), "d_mem") == 2048 &&
+          words(coef_call(1, 0, 0, 1, 1), "d_out") == 2048);
+    const SetCall big = coef_call((size_t)1 << 20, 12, 10, 1, 1);
+    CHECK(words(big, "d_sel_of") == 23068672u && words(big, "d_new") == 2147483648u && words(big, "d_mem") == 8796093022208u && words(big, "d_out") == 8796093022208u);
+    // width and unit never enter a size
+    CHECK(words(coef_call(3, 2, 2, 32, 64), "d_sel_of") == 12 && words(coef_call(3, 2, 2, 32, 64), "d_mem") == 24576);
+}
+
 int main() {
     shapes();
     refusals();
     sizes();
+    write_coef();
     printf("SET_CALLS_OK\n");
     return 0;
 }

@@ -379,6 +379,10 @@ def test_write_device_form_in_place_clamps_and_refuses(ia, keyed):
         with pytest.raises(ia.IeacheError, match="not a device pointer") as e:
             ctx.lut_write_coef_device(S5, count, depth, steps, width, unit, None, new.ctypes.data, tmem.data_ptr(), tout.data_ptr())
         assert e.value.code == -22
+        # a host address for the selectors is refused like any other, even where none would be read (depth = steps = 0)
+        with pytest.raises(ia.IeacheError, match="d_sel_of is not a device pointer") as e:
+            ctx.lut_write_coef_device(S5, 1, 0, 0, 1, 1, sel.ctypes.data, tnew.data_ptr(), tmem.data_ptr(), tout.data_ptr())
+        assert e.value.code == -22
         for d, s, w, u, match in ((-1, 0, 1, 1, "depth must"), (13, 0, 1, 1, "depth must"), (1, -1, 1, 1, "steps must"), (1, 65, 1, 1, "steps must"),
                                   (1, 0, 0, 1, "width must"), (1, 0, 4, 3, "unit must"), (1, 3, 4, 129, "exceed N"), (1, 11, 1, 1, "exceed N")):
             with pytest.raises(ia.IeacheError, match=match) as e:

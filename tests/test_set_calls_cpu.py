@@ -7,9 +7,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_set_calls_under_asan_ubsan(tmp_path):
-    """tests/native/set_calls_test.cpp: a stand-alone program over csrc/set_calls.h -- for each of the seven calls every scalar
-    rule with its exact message and the first-failing order, the words of every argument (2^20 items at depth 12 among them), and
-    which arguments are optional, which may be the output, and every bound."""
+    """tests/native/set_calls_test.cpp: a stand-alone program over csrc/set_calls.h -- for each of the eight calls (the seven of
+    sections 3f to 3j, and lut_write_coef of section 3l with its width, unit and window mark) every scalar rule with its exact
+    message and the first-failing order, the words of every argument (2^20 items at depth 12 among them), and which arguments are
+    optional, which may be the output, and every bound."""
     exe = tmp_path / "set_calls_test"
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
                            "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",

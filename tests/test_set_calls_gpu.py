@@ -1,14 +1,15 @@
-"""Every refusal of the seven calls on a caller TGSW set (include/ieache.h sections 3f to 3j: cmux, lut_tree, lut_scatter,
-lut_write, tlwe_rotate, lut_read, lut_add), in both forms, through the C ABI as it stands: the code, the message, which rule
-wins when two are broken, and that a refused call writes nothing.  The data-carrying cases stay with each call's own file;
-this one is about refusals only, on the smallest shapes that reach every rule: a set of 2 samples, 3 items, depth 2, 2 steps,
-one table (or memory) of 4 rows."""
+"""Every refusal of the eight calls on a caller TGSW set (include/ieache.h sections 3f to 3j: cmux, lut_tree, lut_scatter,
+lut_write, tlwe_rotate, lut_read, lut_add; section 3l: lut_write_coef), in both forms, through the C ABI as it stands: the code,
+the message, which rule wins when two are broken, and that a refused call writes nothing.  The data-carrying cases stay with
+each call's own file; this one is about refusals only, on the smallest shapes that reach every rule: a set of 2 samples, 3
+items, depth 2, 2 steps, one table (or memory) of 4 rows, a window of width 1 at unit 1 under a projection key at (T, B)."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import cmux_reference as CR
+import pack_reference as PR
 
 pytestmark = pytest.mark.gpu
 
@@ -16,6 +17,7 @@ N = 1024
 ROW = 2 * N
 N_SET, COUNT, DEPTH, STEPS = 2, 3, 2, 2
 EINVAL = -22
+T, B = 2, 2  # the projection key's decomposition, as tests/test_project_gpu.py's bit-exact cases take it
 
 # Per call: the C arguments after (ctx, set) in order -- "@name" a pointer argument, anything else a scalar -- and per pointer
 # argument (kind, rows or indices at the scalars above, optional, exclusive bound of an index, may be exactly the output).
@@ -41,12 +43,27 @@ CALLS = {
     "lut_add": (["count", "depth", "steps", "@sel_of", "@amount_of", "@values", "@mems", "n_mems", "@mem_of", "@out"],
                 {"sel_of": ("idx", 12, True, N_SET, False), "amount_of": ("idx", 2, True, 2 * N, False), "values": ("rows", 3, False, None, False),
                  "mems": ("rows", 4, True, None, True), "mem_of": ("idx", 3, True, 1, False), "out": ("rows", 4, False, None, False)}),
+    # new, mem and out may be null in a call without items only: with the 3 items of this file they are required
+    "lut_write_coef": (["count", "depth", "steps", "width", "unit", "@sel_of", "@new", "@mem", "@out"],
+                       {"sel_of": ("idx", 12, True, N_SET, False), "new": ("rows", 3, False, None, False), "mem": ("rows", 12, False, None, True),
+                        "out": ("rows", 12, False, None, False)}),
 }
-SCALARS = {"count": COUNT, "depth": DEPTH, "steps": STEPS, "n_tables": 1, "n_mems": 1, "coef": 0, "flags": 0}
-# (scalar, bad value, fragment of the message), in the order the rules are tested: depth, steps, the count of tables, the flags
+SCALARS = {"count": COUNT, "depth": DEPTH, "steps": STEPS, "n_tables": 1, "n_mems": 1, "coef": 0, "flags": 0, "width": 1, "unit": 1}
+# (scalar, bad value, fragment of the message), in the order the rules are tested: depth, steps, the count of tables, the flags;
+# the window's: width, unit against width, unit x 2^steps against N (257 x 2^2 = 1028)
 RULES = [("depth", -1, "depth must lie in 0 .. 12"), ("depth", 13, "depth must lie in 0 .. 12"), ("steps", -1, "steps must lie in 0 .. 64"),
          ("steps", 65, "steps must lie in 0 .. 64"), ("n_tables", 0, "n_tables must be at least 1"), ("n_mems", 0, "n_mems must be at least 1"),
-         ("flags", 2, "unknown flag")]
+         ("flags", 2, "unknown flag"), ("width", 0, "width must be at least 1"), ("unit", 0, "unit must be at least width"),
+         ("unit", 257, "unit x 2^steps must not exceed N")]
+NO_KEY = "lut_write_coef: no projection key set"
+_key = []
+
+
+def projection_key():
+    """made once per module and left unchanged: full-range words, as the bit-exact cases of tests/test_project_gpu.py take them"""
+    if not _key:
+        _key.append(PR.full_range(np.random.default_rng(9901), (N, T, 2, N)))
+    return _key[0]
 
 
 class Walk:
@@ -229,6 +246,23 @@ def walk_empty_lut_add(w, host):
         check_inputs(w, host)
 
 
+def walk_no_key(w, other_set, host):
+    """lut_write_coef on a context without a projection key: refused after the context, the set and the null arguments, before the
+    scalars, the indices and the pointers"""
+    w.refused(NO_KEY)
+    w.refused("null argument", new=None)
+    w.refused("another context", tgsw=other_set.h)
+    for scalar, bad, _ in scalar_rules(w.name):
+        w.refused(NO_KEY, **{scalar: bad})
+    if w.device:
+        w.refused(NO_KEY, out=host["out"].ctypes.data)
+        check_inputs(w, host)
+    else:
+        bad = host["sel_of"].copy()
+        bad[0] = -1
+        w.refused(NO_KEY, sel_of=bad.ctypes.data_as(C.POINTER(C.c_int32)))
+
+
 def to_device(a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
@@ -249,6 +283,7 @@ def test_every_refusal_of_every_call_in_both_forms(ia, gpu_ctx):
     S = CR.full_range(rng, (N_SET, 2 * p.l, 2, N))
     lwe_host, lwe_dev = p.n + 1, ia.lib().ieache_lwe_stride(ctx.h)
     other = ia.Context.from_arrays(p, kb.bk, kb.ksk)
+    ctx.set_projection_key(projection_key(), t=T, basebit=B)
     try:
         with ctx.tgsw_prepare(S) as own_set, other.tgsw_prepare(S) as other_set:
             host = {name: host_buffers(name, rng, lwe_host) for name in CALLS}
@@ -261,7 +296,8 @@ def test_every_refusal_of_every_call_in_both_forms(ia, gpu_ctx):
             for w in walks:
                 walk_common(w, other_set)
                 walk_host(w)
-            walk_empty_lut_add(walks[-1], host["lut_add"])
+                if w.name == "lut_add":
+                    walk_empty_lut_add(w, host["lut_add"])
             for name in CALLS:
                 # one arena per call: every argument at an offset of its own, and behind them room for the largest output, so
                 # that an output pointer laid over any input stays inside the arena
@@ -281,11 +317,21 @@ def test_every_refusal_of_every_call_in_both_forms(ia, gpu_ctx):
                 walk_common(w, other_set)
                 walk_device(w, dev_host)
                 check_inputs(w, dev_host)
+                if name == "lut_add":
+                    walk_empty_lut_add(w, dev_host)
                 walks.append(w)
-            walk_empty_lut_add(walks[-1], dev_host)
             for w in walks[:len(CALLS)]:
                 w.accepted()
             assert ctx.get_option("staging_allocations") == warm
+            # the write of a window in both forms once the key is gone; the seven others do not ask for it
+            ctx.set_projection_key(None)
+            for w in walks:
+                reset_out(w)
+                if w.name == "lut_write_coef":
+                    walk_no_key(w, other_set, w.host)
+                else:
+                    w.accepted()
             print("set calls: %d C calls walked" % sum(w.calls for w in walks))
     finally:
+        ctx.set_projection_key(None)
         other.close()
