@@ -12,6 +12,7 @@ from .evaluator import (  # noqa: F401
     GATE_MAJ3, GATE_XOR3, CIRC_ADD_FA, CIRC_SUB_FA, CIRC_RSUB_FA, CIRC_MUL_FA, circuit_gate_count,
     PBS_NO_KEYSWITCH, PBS_TLWE_POLYS, PBS_ACCUMULATOR, PBS_MULTI_MAX_FACTORS, Group, GROUP_MAX_DEVICES, Job,
     TgswSet, Automaton, AUTOMATON_MAX_STATES, AUTOMATON_MAX_STEPS, automaton_tables, LUT_TREE_MAX_DEPTH, ROTATE_MAX_STEPS, LUT_READ_NO_KEYSWITCH,
+    UNPACK_NO_KEYSWITCH,
     FFT_FORWARD_FORMS, FFT_INVERSE_FORMS, FFT_PAIRED_FORMS, TWIDDLE_ENTRIES,
 )
 from . import tools  # noqa: F401

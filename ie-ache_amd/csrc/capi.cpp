@@ -967,7 +967,7 @@ int check_set_scalars(const SetCall& c, int32_t N) {
 // the scalars come next
 int check_set_call(const ieache_ctx* ctx, const ieache_tgsw* set, const SetCall& c, SetPtrs a) {
     if (const int rc = check_tgsw(ctx, set)) return rc;
-    const SetCallShape& s = kSetCalls[c.kind];
+    const SetCallShape& s = set_call_shape(c);
     for (int i = 0; i < s.n_args; i++)
         if (!a.begin()[i] && set_arg_required(c, s.args[i])) return fail(IEACHE_EINVAL, "null argument");
     if (s.window && !ctx->eval->has_projection_key()) return fail(IEACHE_EINVAL, std::string(s.name) + ": no projection key set");
@@ -976,7 +976,7 @@ int check_set_call(const ieache_ctx* ctx, const ieache_tgsw* set, const SetCall&
 // the host and the reference forms: the scalars, then the first bad entry of the index arrays in argument order, then lut_read's coef
 int check_set_indices(const SetCall& c, SetPtrs a, int32_t N, size_t n_set) {
     if (const int rc = check_set_scalars(c, N)) return rc;
-    const SetCallShape& s = kSetCalls[c.kind];
+    const SetCallShape& s = set_call_shape(c);
     for (int i = 0; i < s.n_args; i++) {
         const SetArg& arg = s.args[i];
         if (arg.kind != kArgIndices) continue;
@@ -988,7 +988,7 @@ int check_set_indices(const SetCall& c, SetPtrs a, int32_t N, size_t n_set) {
 // the device forms: the scalars, then every pointer the call will read or write; a null optional one is none
 int check_set_pointers(const SetCall& c, SetPtrs args, int32_t N) {
     if (const int rc = check_set_scalars(c, N)) return rc;
-    const SetCallShape& s = kSetCalls[c.kind];
+    const SetCallShape& s = set_call_shape(c);
     const void* const* a = args.begin();
     for (int i = 0; i < s.n_args; i++)  // first, and always, what a call without items touches as well (lut_add's memories and output)
         if (s.args[i].empty_too && (a[i] || s.args[i].need != kOptional)) require_device_pointer(a[i], s.args[i].name);
@@ -1015,7 +1015,7 @@ int set_call_host(ieache_ctx* ctx, const ieache_tgsw* set, const SetCall& c, con
         if (const int rc = check_set_call(ctx, set, c, a)) return rc;
         if (const int rc = check_set_indices(c, a, ctx->eval->params().N, set->set->n)) return rc;
         static constexpr StageSlot kSlot[] = {kStageOut, kStagePolyOf, kStageBias, kStageFactors, kStageTlweA, kStageTlweB, kStageTestPolys, kStageOut};
-        const SetCallShape& s = kSetCalls[c.kind];
+        const SetCallShape& s = set_call_shape(c);
         HostCall h(ctx, c.count);
         const size_t sample = (size_t)2 * (size_t)h.p.N, out_rows = set_arg_units(c, set_call_output(c));
         const bool lwe = c.kind == kCallLutRead, extracted = lwe && (c.flags & IEACHE_LUT_READ_NO_KEYSWITCH);
@@ -1408,6 +1408,61 @@ int ieache_tlwe_extract(ieache_ctx* ctx, size_t count, const int32_t* tlwe, cons
         h.download(du, u, true);
         return 0;
     });
+}
+
+// ---- the way back to the gates (section 3m).  unpack_plan.h states what the calls accept; word_read is kWordRead of
+// set_calls.h, lut_read's row under its own name. ----
+static_assert(kUnpackNoKeyswitch == IEACHE_UNPACK_NO_KEYSWITCH && IEACHE_UNPACK_NO_KEYSWITCH == IEACHE_LUT_READ_NO_KEYSWITCH,
+              "unpack_plan.h knows the flag of include/ieache.h, and set_call_host reads it as lut_read's");
+namespace {
+int check_unpack(const ieache_ctx* ctx, size_t count, int32_t first, int32_t width, int32_t spread, int flags, const int32_t* in, const int32_t* out) {
+    if (!ctx || (count && (!in || !out))) return fail(IEACHE_EINVAL, "null argument");
+    if (const char* e = unpack_call_error(ctx->eval->params().N, first, width, spread, flags)) return fail(IEACHE_EINVAL, e);
+    return 0;
+}
+extern "C++" SetCall word_read_call(size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit, int32_t n_tables, int flags) {
+    return SetCall{kCallLutRead, count, depth, steps, n_tables, flags, 0, width, unit, true};
+}
+}  // namespace
+
+int ieache_unpack_device(ieache_ctx* ctx, size_t count, int32_t first, int32_t width, int32_t spread, const int32_t* d_in, int flags, int32_t* d_out,
+                         ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_unpack(ctx, count, first, width, spread, flags, d_in, d_out)) return rc;
+        require_device_pointers(count, {{d_in, "d_in"}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->unpack_device(count, first, width, spread, flags, d_in, d_out, st); });
+    });
+}
+
+int ieache_unpack(ieache_ctx* ctx, size_t count, int32_t first, int32_t width, int32_t spread, const int32_t* in, int flags, int32_t* out,
+                  ieache_stats* stats) {
+    return guarded([&] {
+        if (const int rc = check_unpack(ctx, count, first, width, spread, flags, in, out)) return rc;
+        const bool woks = (flags & IEACHE_UNPACK_NO_KEYSWITCH) != 0;
+        HostCall h(ctx, count);
+        const size_t sample = (size_t)2 * (size_t)h.p.N;
+        StagedRows din(h.ev, kStageTlweA, count, sample, in, sample), dout = h.results(count * (size_t)width, woks);
+        with_stats(stats, [&](EvalStats* st) { h.ev.unpack_device(count, first, width, spread, flags, din.p, dout.p, st); });
+        h.download(dout, out, woks);
+        return 0;
+    });
+}
+
+int ieache_word_read_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit,
+                            const int32_t* d_sel_of, const int32_t* d_tables, int32_t n_tables, const int32_t* d_table_of, int flags, int32_t* d_out,
+                            ieache_stats* stats) {
+    return set_call_device(ctx, set, word_read_call(count, depth, steps, width, unit, n_tables, flags), {d_sel_of, nullptr, d_tables, d_table_of, d_out}, stats,
+                           [&](EvalStats* st) {
+                               ctx->eval->word_read_device(*set->set, count, depth, steps, width, unit, d_sel_of, d_tables, n_tables, d_table_of, flags, d_out, st);
+                           });
+}
+
+int ieache_word_read(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit, const int32_t* sel_of,
+                     const int32_t* tables, int32_t n_tables, const int32_t* table_of, int flags, int32_t* out, ieache_stats* stats) {
+    return set_call_host(ctx, set, word_read_call(count, depth, steps, width, unit, n_tables, flags), {sel_of, nullptr, tables, table_of, out}, out, stats,
+                         [&](Evaluator& ev, Torus32* const* d, EvalStats* st) {
+                             ev.word_read_device(*set->set, count, depth, steps, width, unit, d[0], d[2], n_tables, d[3], flags, d[4], st);
+                         });
 }
 
 int ieache_lut_factor_poly(const ieache_params* p, int32_t entries, const int32_t* w, int32_t* P) {
@@ -1993,6 +2048,38 @@ int ieache_lut_write_coef_reference(const ieache_params* p, const int32_t* set, 
         if (const char* e = project_set_error(pp, pk_t, pk_basebit)) return fail(IEACHE_EINVAL, e);
         if (const int rc = check_set_indices({kCallLutWriteCoef, count, depth, steps, 1, 0, 0, width, unit}, {sel_of, fresh, mem, out}, pp.N, n)) return rc;
         lut_write_coef_reference(pp, set, n, pk_t, pk_basebit, pk, count, depth, steps, width, unit, sel_of, fresh, mem, out);
+        return 0;
+    });
+}
+
+int ieache_unpack_reference(const ieache_params* p, const int32_t* ksk, size_t count, int32_t first, int32_t width, int32_t spread, const int32_t* in,
+                            int flags, int32_t* out) {
+    return guarded([&] {
+        if (!p || (count && (!in || !out))) return fail(IEACHE_EINVAL, "null argument");
+        const Params pp = to_params(*p);
+        if (!pp.supported()) return fail(IEACHE_EINVAL, "unpack_reference: unsupported TFHE parameter set");
+        if (const char* e = unpack_call_error(pp.N, first, width, spread, flags)) return fail(IEACHE_EINVAL, e);
+        const bool woks = (flags & IEACHE_UNPACK_NO_KEYSWITCH) != 0;
+        if (!woks && !ksk) return fail(IEACHE_EINVAL, "unpack_reference: the key switch needs ksk");
+        unpack_reference(pp, woks ? nullptr : ksk, count, first, width, spread, in, out);
+        return 0;
+    });
+}
+
+int ieache_word_read_reference(const ieache_params* p, const int32_t* set, size_t n, const int32_t* ksk, size_t count, int32_t depth, int32_t steps,
+                               int32_t width, int32_t unit, const int32_t* sel_of, const int32_t* tables, int32_t n_tables, const int32_t* table_of,
+                               int flags, int32_t* out) {
+    return guarded([&] {
+        if (!p || !set || (count && (!tables || !out))) return fail(IEACHE_EINVAL, "null argument");
+        const Params pp = to_params(*p);
+        if (!pp.supported()) return fail(IEACHE_EINVAL, "word_read_reference: unsupported TFHE parameter set");
+        if (n < 1) return fail(IEACHE_EINVAL, "word_read_reference: no samples");
+        const SetCall c = word_read_call(count, depth, steps, width, unit, n_tables, flags);
+        if (const int rc = check_set_scalars(c, pp.N)) return rc;
+        const bool woks = (flags & IEACHE_UNPACK_NO_KEYSWITCH) != 0;
+        if (!woks && !ksk) return fail(IEACHE_EINVAL, "word_read_reference: the key switch needs ksk");
+        if (const int rc = check_set_indices(c, {sel_of, nullptr, tables, table_of, out}, pp.N, n)) return rc;
+        word_read_reference(pp, set, n, woks ? nullptr : ksk, count, depth, steps, width, unit, sel_of, tables, table_of, out);
         return 0;
     });
 }

@@ -6,7 +6,9 @@
 //   section 3j  many values added into shared memories in one call;
 //   section 3k  deterministic automata over words of encrypted bits, every step of an item in one launch;
 //   section 3l  the two steps of the replace write of a window that are this family's: the read of each item's own memory toward
-//               position 0 (launch_read_own) and the subtraction (launch_delta); the projection between them is pack.h's.
+//               position 0 (launch_read_own) and the subtraction (launch_delta); the projection between them is pack.h's;
+//   section 3m  the read of an addressed word up to its rotation toward position 0 (launch_read_rows); the rows' way to the gates
+//               is keyswitch.h's.
 // The kernels, the spectrum form of a prepared set, the twiddle table and the scratch of a tree are behind this object: a tree
 // is ONE level loop (launch_levels) whether its level 0 reads shared tables or each item's own rows, whether its selectors are
 // the call's or a piece's explicit ones, and nothing outside fills in a CmuxRows of a tree.  How
@@ -220,6 +222,12 @@ struct Cmux {
     // selectors 0 .. steps - 1 and amount_of.  sel_of is the call's.  scratch as reserve_read's.  Returns max(depth, 1) + (steps > 0).
     int launch_read_own(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, int32_t steps,
                         const int32_t* sel_of, const int32_t* amount_of, const int32_t* mem);
+    // one piece of the read of an addressed word (section 3m), launch_read up to the rotation and with launch_read_own's count:
+    // selectors steps .. steps + depth - 1 of each item made explicit in scratch.idx (not counted as a launch), the tree over the
+    // shared tables [n_tables][2^depth][2][N] by them into scratch.rows, the rotation of those rows in place by selectors
+    // 0 .. steps - 1 and amount_of.  sel_of and table_of are the call's.  scratch as reserve_read's.  Returns max(depth, 1) + (steps > 0).
+    int launch_read_rows(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, int32_t steps,
+                         const int32_t* sel_of, const int32_t* amount_of, const int32_t* tables, int32_t n_tables, const int32_t* table_of);
     // delta_i = fresh_i - old_i mod 2^32 in place over old [items][2][N] (k_write_delta): one launch
     void launch_delta(hipStream_t stream, int64_t items, const int32_t* fresh, int32_t* old_to_delta);
     // one launch of `rows.rows` accumulating demux steps (k_demux_acc: 2 x rows.rows rows added into rows.out)

@@ -233,6 +233,22 @@ public:
     void lut_read_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, const int32_t* d_sel_of, const int32_t* d_amount_of,
                          const Torus32* d_tables, int32_t n_tables, const int32_t* d_table_of, int32_t coef, int32_t flags, Torus32* d_out,
                          EvalStats* stats);
+    // The way back to the gates (include/ieache.h section 3m; unpack_plan.h states the windows and the cut).
+    // unpack_device, the partner of pack_device: row (i, q) of d_out = the key switch of the extracted row of coefficient
+    // first + q spread of d_in[i] ([count][2][N]), q < width: [count][width] rows of lwe_stride words, or with kUnpackNoKeyswitch
+    // the extracted rows themselves, rows of extract_stride() words.  The count x width rows in runs of at most `chunk`, one piece
+    // per run, through KeySwitch::launch_window: where a run's plan is the MFMA product no extracted row is stored.  Any
+    // parameter set the key switch supports.  stats: bootstraps 0, levels 1, chunks = runs, one key-switch launch per run (none
+    // with the flag).  std::invalid_argument for a window or a flag unpack_call_error refuses and for ANY overlap of d_out with d_in.
+    // word_read_device, the partner of lut_write_coef_device: per piece of the tree's plan for (count, depth) the tree over
+    // d_tables by selectors steps .. steps+depth-1 of each item, the rotation of the selected rows in place by selectors
+    // 0 .. steps-1 with the amounts 2N - unit 2^t, and the window (0, width, 1) of those rows unpacked as above in runs of at most
+    // `chunk`: d_out [count][width] rows.  Everything is reserved before the first piece.  stats: levels = depth + steps, chunks =
+    // pieces, blind_rotate_launches = pieces x (max(depth, 1) + (steps > 0)), a key-switch launch per run.  kWordRead of
+    // set_calls.h: std::invalid_argument for scalars word_read_error refuses, an overlap, a set of another evaluator.
+    void unpack_device(size_t count, int32_t first, int32_t width, int32_t spread, int32_t flags, const Torus32* d_in, Torus32* d_out, EvalStats* stats);
+    void word_read_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit, const int32_t* d_sel_of,
+                          const Torus32* d_tables, int32_t n_tables, const int32_t* d_table_of, int32_t flags, Torus32* d_out, EvalStats* stats);
     // Automata over words of TGSW-encrypted bits (include/ieache.h section 3k; automaton_plan.h states what one is and how a
     // call is cut).  automaton_create: the tables [steps][states] from host memory -> an object the caller owns (delete it before
     // or after this evaluator goes; only this evaluator accepts it); std::invalid_argument with the first rule broken.

@@ -1113,7 +1113,7 @@ void Evaluator::cmux_plan_figures(size_t count, int32_t depth, int64_t out[4]) c
 bool Evaluator::begin_set_call(const TgswSet& set, const SetCall& c, std::initializer_list<const void*> args, size_t out_row_words) {
     const void* const* a = args.begin();
     d_->cmux.check_owner(set);
-    const SetCallShape& s = kSetCalls[c.kind];
+    const SetCallShape& s = set_call_shape(c);
     if (s.window && !d_->project.has_key()) throw std::invalid_argument(std::string(s.name) + ": no projection key set");
     const std::string refusal = set_call_refusal(c, p_.N);
     if (!refusal.empty()) throw std::invalid_argument(refusal);
@@ -1333,6 +1333,97 @@ void Evaluator::lut_read_device(const TgswSet& set, size_t count, int32_t depth,
         pc.keyswitch(pc.count, ks_piece, [&](int64_t done, int64_t run) {
             launch_keyswitch(d_, ln, rows_desc(W, pc.first + done), run, rows_of(pc.first) + (size_t)done * (size_t)extract_stride(), nullptr);
         });
+    });
+}
+
+// ---- the way back to the gates (section 3m; unpack_plan.h) ----
+namespace {
+// What both calls do with `rows` rows of a window of samples: runs of at most `chunk` rows through the key switch's door for such
+// rows, or (woks) the extracted rows themselves into the caller's.  Row r of `out` takes run row r.
+struct UnpackRows {
+    Evaluator::Impl* d;
+    Lane& ln;
+    UnpackWindow win;
+    bool woks;
+    size_t out_stride;
+    // the rows of a call whose runs have these sizes at most: the key switch's scratch, and the lane's extracted rows for the
+    // runs whose family walks stored rows (the product stores none)
+    void reserve(std::initializer_list<int64_t> run_sizes) const {
+        if (woks) return;
+        int64_t widest = 0, stored = 0;
+        for (const int64_t s : run_sizes) {
+            widest = std::max(widest, s);
+            if (d->ks.window_needs_rows(s, d->opt, d->force_generic_ks)) stored = std::max(stored, s);
+        }
+        d->ks.reserve(ln.ks, widest, d->opt, d->force_generic_ks);
+        if (stored) ln.ext.reserve_exact((size_t)stored, d->ext_row_bytes());
+    }
+    // rows row0 .. row0 + rows of `samples` seen as [..][width] rows, inside piece pc
+    void run(Piece& pc, const Torus32* samples, int64_t row0, int64_t rows, Torus32* out) const {
+        if (woks) {  // belongs to neither kind of phase, as tlwe_extract's launch: timed in total_ms alone and counted nowhere
+            d->ks.extract_window(ln.stream, rows, KsWindowRows{samples, row0, win}, out, (int32_t)out_stride);
+            HIP_CHECK(hipGetLastError());
+            return;
+        }
+        pc.keyswitch(rows, std::min<int64_t>(rows, (int64_t)d->opt.chunk), [&](int64_t done, int64_t run_rows) {
+            d->ks.launch_window(ln.ks, ln.stream, run_rows, KsWindowRows{samples, row0 + done, win}, ln.ext, out + (size_t)done * out_stride, d->opt,
+                                d->force_generic_ks);
+        });
+    }
+};
+// the sizes the runs of `rows` rows in runs of at most `chunk` take: the full run and the last
+std::pair<int64_t, int64_t> run_sizes(int64_t rows, int64_t chunk) {
+    const int64_t full = std::min(rows, std::max<int64_t>(chunk, 1));
+    return {full, rows > 0 && rows % full ? rows % full : full};
+}
+}  // namespace
+
+// The unpacking key switch: the call's rows in runs of at most a chunk, one piece per run.
+void Evaluator::unpack_device(size_t count, int32_t first, int32_t width, int32_t spread, int32_t flags, const Torus32* d_in, Torus32* d_out,
+                              EvalStats* stats) {
+    if (const char* e = unpack_call_error(p_.N, first, width, spread, flags)) throw std::invalid_argument(e);
+    const bool woks = (flags & kUnpackNoKeyswitch) != 0;
+    const size_t out_stride = (size_t)(woks ? extract_stride() : d_->K.stride);
+    const int64_t rows = unpack_rows((int64_t)count, width);
+    if (overlaps(d_out, (size_t)rows * out_stride, {{d_in, count * (size_t)2 * (size_t)p_.N}})) throw std::invalid_argument("unpack: the output overlaps the input samples");
+    begin_call();
+    if (count == 0) return;
+    if (!d_in || !d_out) throw std::invalid_argument("unpack: null rows");
+    const UnpackRows U{d_, d_->lane[0], UnpackWindow{first, width, spread}, woks, out_stride};
+    const Cut cut = unpack_runs((int64_t)count, width, (int64_t)d_->opt.chunk);
+    const auto sizes = run_sizes(rows, cut.per_piece);
+    U.reserve({sizes.first, sizes.second});
+    run_pieces(cut, rows, 1, stats, [&](Piece& pc) { U.run(pc, d_in, pc.first, pc.count, d_out + (size_t)pc.first * out_stride); });
+}
+
+// The read of an addressed word: the tree's pieces; per piece the tree into the rows the lane keeps and their rotation in place
+// toward position 0 (Cmux::launch_read_rows), then the window (0, width, 1) of those rows unpacked in runs of at most a chunk.
+// Everything is reserved before the first piece.
+void Evaluator::word_read_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit, const int32_t* d_sel_of,
+                                 const Torus32* d_tables, int32_t n_tables, const int32_t* d_table_of, int32_t flags, Torus32* d_out, EvalStats* stats) {
+    const bool woks = (flags & kUnpackNoKeyswitch) != 0;
+    const size_t out_stride = (size_t)(woks ? extract_stride() : d_->K.stride);
+    SetCall c{kCallLutRead, count, depth, steps, n_tables, flags, 0, width, unit};
+    c.word = true;
+    if (!begin_set_call(set, c, {d_sel_of, nullptr, d_tables, d_table_of, d_out}, out_stride)) return;
+    Lane& ln = d_->lane[0];
+    const CmuxPlan pl = cmux_plan((int64_t)count, depth, d_->opt.cmux_piece_rows);
+    d_->cmux.reserve_read(ln.cmux, pl, depth);
+    const UnpackRows U{d_, ln, UnpackWindow{0, width, 1}, woks, out_stride};
+    const int64_t last_items = (int64_t)count - (pl.pieces - 1) * pl.items_per_piece;
+    const auto widest = run_sizes(unpack_rows(pl.items_per_piece, width), (int64_t)d_->opt.chunk);
+    const auto last = run_sizes(unpack_rows(last_items, width), (int64_t)d_->opt.chunk);
+    U.reserve({widest.first, widest.second, last.first, last.second});
+    // not a launch of the call's: the public amounts 2N - unit 2^t of the rotation toward position 0 (lut_write_coef's table)
+    ln.coef_idx.reserve_exact((size_t)2 * kRotateMaxSteps);
+    int32_t *toward = ln.coef_idx, *back = toward + kRotateMaxSteps;
+    if (steps > 0)
+        hipLaunchKernelGGL(k_write_coef_tables, dim3((unsigned)((steps + 255) / 256)), dim3(256), 0, stream_, unit, steps, 2 * p_.N, (int64_t)0, toward, back, back);
+    run_pieces(pl.cut(), (int64_t)count, depth + steps, stats, [&](Piece& pc) {
+        pc.rotate([&] {
+            return d_->cmux.launch_read_rows(set, ln.cmux, stream_, pc.first, pc.count, depth, steps, d_sel_of, toward, d_tables, n_tables, d_table_of);
+        });
+        U.run(pc, ln.cmux.rows, 0, unpack_rows(pc.count, width), d_out + (size_t)unpack_rows(pc.first, width) * out_stride);
     });
 }
 

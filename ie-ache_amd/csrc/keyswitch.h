@@ -1,6 +1,6 @@
 // LWE key switch (K5), the one door: every kernel family, the byte-limb form of the key, the LDS grants and the choice among
-// them (ks_plan.h) are behind this object.  A caller hands it extracted samples and gets key-switched rows; it never learns
-// which kernel ran.  Kernels: keyswitch.hip (the per-gate and gate-batched walks), keyswitch_sliced.hip, keyswitch_mfma.hip.
+// them (ks_plan.h) are behind this object.  A caller hands it extracted samples -- or a window of TLWE samples whose extracted
+// rows it means (launch_window) -- and gets key-switched rows; it never learns which kernel ran.  Kernels: keyswitch.hip (the per-gate and gate-batched walks), keyswitch_sliced.hip, keyswitch_mfma.hip.
 #pragma once
 #include "device_buffer.h"
 #include "device_common.h"
@@ -28,6 +28,15 @@ struct KeySwitch {
     // instance W.item0 + i.  Every family gives the same bits.
     void launch(KsScratch& scratch, hipStream_t stream, const dev::WorkDesc& W, int64_t cnt, const Torus32* ext, Torus32* flat_out,
                 const EvalOptions& opt, bool force_generic);
+    // The same for rows given as a window of samples (KsWindowRows, ks_plan.h): run row g -> row g of out_rows.  Where the plan
+    // for `cnt` rows is the MFMA product the extracted rows are never stored and `ext` is not touched; otherwise they are
+    // stored in ext (cnt rows of N + 4 words at least) and go through launch() as they are.  Every family gives the same bits.
+    void launch_window(KsScratch& scratch, hipStream_t stream, int64_t cnt, const KsWindowRows& rows, Torus32* ext, Torus32* out_rows,
+                       const EvalOptions& opt, bool force_generic);
+    // whether launch_window of `cnt` rows needs `ext`
+    bool window_needs_rows(int64_t cnt, const EvalOptions& opt, bool force_generic) const;
+    // the extracted rows of such a window themselves: run row g -> N + 1 words of row g of u (rows of `stride` words)
+    void extract_window(hipStream_t stream, int64_t cnt, const KsWindowRows& rows, Torus32* u, int32_t stride);
 
 private:
     Params p_;

@@ -320,4 +320,26 @@ void KeySwitch::launch(KsScratch& scratch, hipStream_t stream, const WorkDesc& w
     }
 }
 
+bool KeySwitch::window_needs_rows(int64_t cnt, const EvalOptions& opt, bool force_generic) const {
+    return cnt > 0 && ks_plan(sup_, p_, opt, limbs_ != nullptr, force_generic, cnt).family != KsFamily::Mfma;
+}
+
+void KeySwitch::extract_window(hipStream_t stream, int64_t cnt, const KsWindowRows& rows, Torus32* u, int32_t stride) {
+    ksm::extract_window(p_, cnt, rows, u, stride, stream);
+}
+
+void KeySwitch::launch_window(KsScratch& scratch, hipStream_t stream, int64_t cnt, const KsWindowRows& rows, Torus32* ext, Torus32* out_rows,
+                              const EvalOptions& opt, bool force_generic) {
+    if (cnt <= 0) return;
+    const KsPlan pl = ks_plan(sup_, p_, opt, limbs_ != nullptr, force_generic, cnt);
+    if (pl.family == KsFamily::Mfma) {
+        reserve(scratch, cnt, opt, force_generic);  // in place already unless the caller did not reserve
+        ksm::launch_window(p_, K_, cnt, rows, out_rows, limbs_, scratch.digits, pl.ksplit, pl.xcd_map, stream);
+        return;
+    }
+    if (!ext) throw std::invalid_argument("key switch of a window: no rows to store the extracted samples in");
+    ksm::extract_window(p_, cnt, rows, ext, p_.N + 4, stream);
+    launch(scratch, stream, dev::WorkDesc{}, cnt, ext, out_rows, opt, force_generic);
+}
+
 }  // namespace ieache

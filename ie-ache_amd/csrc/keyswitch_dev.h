@@ -37,6 +37,13 @@ void prepare(const Params& p, const int32_t* d_ksk_padded, int8_t* d_limbs, hipS
 // Returns the number of kernel launches.
 int launch(const Params& p, const dev::DevKeys& K, const dev::WorkDesc& W, int64_t items, const Torus32* ext, Torus32* flat_out,
            const int8_t* d_limbs, void* d_digits, int32_t ksplit, int32_t xcd_map, hipStream_t stream);
+// The same product on rows given as a window of samples (KsWindowRows, ks_plan.h): k_ksm_window_digits and k_ksm_window_init
+// make the digits and the initial rows from the samples, k_ksm_gemm is launch()'s.  Run row g -> row g of out_rows (rows of
+// K.stride words).  The same scratch, split rule and return value.
+int launch_window(const Params& p, const dev::DevKeys& K, int64_t items, const KsWindowRows& rows, Torus32* out_rows, const int8_t* d_limbs,
+                  void* d_digits, int32_t ksplit, int32_t xcd_map, hipStream_t stream);
+// the extracted rows of such a window, stored: run row g -> N + 1 words of row g of u (rows of `stride` words).  Any parameter set.
+void extract_window(const Params& p, int64_t items, const KsWindowRows& rows, Torus32* u, int32_t stride, hipStream_t stream);
 }  // namespace ksm
 
 }  // namespace ieache

@@ -204,6 +204,77 @@ __global__ __launch_bounds__(64 * kWgWaves) void k_ksm_gemm(const v4i* __restric
     }
 }
 
+// ---- rows given as a window of samples (unpack_plan.h; KsWindowRows, ks_plan.h): run row g is row R.row0 + g of the call,
+// coefficient c = first + q spread of sample `item` with item = row / width, q = row % width.  Entry i of its extracted row is
+// A[c - i] for i <= c and -A[N + c - i] above, its last word B[c]: k_tlwe_extract's rule.  The product's front end below makes
+// what k_ksm_gemm reads from the samples themselves; the extracted rows are stored only for the families that walk them. ----
+__device__ __forceinline__ uint32_t window_entry(const Torus32* __restrict__ A, int32_t c, int32_t i, int32_t N) {
+    return i <= c ? (uint32_t)A[c - i] : 0u - (uint32_t)A[N + c - i];
+}
+// (sample's first word, coefficient) of call row `row`
+__device__ __forceinline__ void window_row(const KsWindowRows& R, int64_t row, int32_t N, size_t* base, int32_t* c) {
+    const int64_t item = row / R.win.width;
+    *base = (size_t)item * 2 * (size_t)N;
+    *c = R.win.first + (int32_t)(row - item * R.win.width) * R.win.spread;
+}
+
+// k_ksm_digits on such rows: the digit of a negated word is the digit of the NEGATED WORD (the entry is formed first); rows past
+// the run, up to the padded multiple of 512, get zero digit words
+__global__ __launch_bounds__(256) void k_ksm_window_digits(KsWindowRows R, unsigned long long* __restrict__ dig4, int64_t items, int64_t gpad, int32_t N) {
+    __shared__ uint16_t tile[64][66];
+    __shared__ size_t s_base[64];
+    __shared__ int32_t s_c[64];  // -1: a row past the run
+    const int64_t g0 = (int64_t)blockIdx.y * 64;
+    const int32_t i0 = blockIdx.x * 64;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    if (threadIdx.x < 64) {
+        size_t base = 0;
+        int32_t c = -1;
+        if (g0 + threadIdx.x < items) window_row(R, R.row0 + g0 + threadIdx.x, N, &base, &c);
+        s_base[threadIdx.x] = base;
+        s_c[threadIdx.x] = c;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int gy = ty + 4 * r;
+        const int32_t c = s_c[gy];
+        tile[gy][tx] = c >= 0 ? (uint16_t)((window_entry(R.samples + s_base[gy], c, i0 + tx, N) + 0x8000u) >> 16) : (uint16_t)0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int q = ty + 4 * r;  // local i / 4
+        const unsigned long long v = (unsigned long long)tile[tx][4 * q] | ((unsigned long long)tile[tx][4 * q + 1] << 16) |
+                                     ((unsigned long long)tile[tx][4 * q + 2] << 32) | ((unsigned long long)tile[tx][4 * q + 3] << 48);
+        dig4[(size_t)(i0 / 4 + q) * gpad + g0 + tx] = v;
+    }
+}
+
+// k_ksm_init on such rows: run row g -> row g of out_rows, started as (0, ..., 0, B[c]), its address kept for the epilogue
+__global__ __launch_bounds__(256) void k_ksm_window_init(KsWindowRows R, Torus32* __restrict__ out_rows, Torus32** __restrict__ out_ptr, int32_t N,
+                                                         int32_t n, int32_t stride) {
+    const int64_t g = (int64_t)blockIdx.x;
+    size_t base;
+    int32_t c;
+    window_row(R, R.row0 + g, N, &base, &c);
+    Torus32* out = out_rows + (size_t)g * stride;
+    if (threadIdx.x == 0) out_ptr[g] = out;
+    const Torus32 b = R.samples[base + N + c];
+    for (int32_t q = threadIdx.x; q < stride; q += 256) out[q] = q == n ? b : 0;
+}
+
+// the rows themselves, N + 1 words of each row of `stride` words: any parameter set
+__global__ __launch_bounds__(256) void k_ksm_window_rows(KsWindowRows R, Torus32* __restrict__ u, int32_t N, int32_t stride) {
+    const int64_t g = (int64_t)blockIdx.x;
+    size_t base;
+    int32_t c;
+    window_row(R, R.row0 + g, N, &base, &c);
+    const Torus32* A = R.samples + base;
+    Torus32* dst = u + (size_t)g * stride;
+    for (int32_t i = threadIdx.x; i <= N; i += 256) dst[i] = i == N ? A[N + c] : (Torus32)window_entry(A, c, i, N);
+}
+
 }  // namespace
 
 void prepare(const Params& p, const int32_t* d_ksk_padded, int8_t* d_limbs, hipStream_t stream) {
@@ -225,6 +296,27 @@ int launch(const Params& p, const DevKeys& K, const WorkDesc& W, int64_t items, 
     hipLaunchKernelGGL(k_ksm_gemm, dim3((unsigned)(gblocks * ncb * ksplit)), dim3(64 * kWgWaves), 0, stream,
                        reinterpret_cast<const v4i*>(d_limbs), dig4, out_ptr, items, gpad, gblocks, p.N, ncb, p.lwe_stride(), ksplit, xcd_map);
     return 3;
+}
+
+int launch_window(const Params& p, const DevKeys& K, int64_t items, const KsWindowRows& rows, Torus32* out_rows, const int8_t* d_limbs,
+                  void* d_digits, int32_t ksplit, int32_t xcd_map, hipStream_t stream) {
+    if (items <= 0) return 0;
+    if (!ks_mfma_split_ok(p, ksplit)) throw std::invalid_argument("key-switch K split does not leave every split a whole trip of the product's loop");
+    const int64_t gpad = ks_mfma_padded_items(items);
+    const int32_t ncb = ks_coef_blocks(p);
+    unsigned long long* dig4 = reinterpret_cast<unsigned long long*>(d_digits);
+    Torus32** out_ptr = reinterpret_cast<Torus32**>(dig4 + (size_t)(p.N / 4) * gpad);
+    const int64_t gblocks = gpad / kWgGates;
+    hipLaunchKernelGGL(k_ksm_window_digits, dim3((unsigned)(p.N / 64), (unsigned)(gpad / 64)), dim3(256), 0, stream, rows, dig4, items, gpad, p.N);
+    hipLaunchKernelGGL(k_ksm_window_init, dim3((unsigned)items), dim3(256), 0, stream, rows, out_rows, out_ptr, p.N, K.n, K.stride);
+    hipLaunchKernelGGL(k_ksm_gemm, dim3((unsigned)(gblocks * ncb * ksplit)), dim3(64 * kWgWaves), 0, stream,
+                       reinterpret_cast<const v4i*>(d_limbs), dig4, out_ptr, items, gpad, gblocks, p.N, ncb, p.lwe_stride(), ksplit, xcd_map);
+    return 3;
+}
+
+void extract_window(const Params& p, int64_t items, const KsWindowRows& rows, Torus32* u, int32_t stride, hipStream_t stream) {
+    if (items <= 0) return;
+    hipLaunchKernelGGL(k_ksm_window_rows, dim3((unsigned)items), dim3(256), 0, stream, rows, u, p.N, stride);
 }
 
 }  // namespace ksm

@@ -6,13 +6,26 @@
 //   Batched  k_keyswitch_batch<16>   compiler-scheduled gate-batched walk (the cross-check)
 //   Sliced   k_keyswitch_sliced<G>   hand-scheduled gate-batched walk, G gate instances per workgroup, `slice` coefficients per launch
 //   Mfma     k_ksm_digits / _init / _gemm   the int8 product on the MFMA pipe, the walk over K cut into `ksplit`
+//
+// Rows given as a window of samples (KsWindowRows; unpack_plan.h): the same plan for the run's row count.  Mfma takes them
+// through k_ksm_window_digits / k_ksm_window_init / k_ksm_gemm with no extracted row stored; every other family reads the rows
+// k_ksm_window_rows stores.
 #pragma once
 #include <cstdint>
 
 #include "evaluator_options.h"
 #include "params.h"
+#include "unpack_plan.h"
 
 namespace ieache {
+
+// `cnt` rows of a launch given as a window of TLWE samples: run row g is row row0 + g of samples [..][2][N] seen as
+// [..][win.width] rows, the extracted row of coefficient win.first + q win.spread of sample (row0 + g) / win.width.
+struct KsWindowRows {
+    const Torus32* samples = nullptr;
+    int64_t row0 = 0;
+    UnpackWindow win;
+};
 
 // coefficients of B fragments in flight per wave of k_ksm_gemm: 8 (round 4; 4 until then: 0.658 -> 0.610 ms per 8 192 gates, profiles/r4_keyswitch_ahead.txt).
 // 4 or 8: the walk of a K split is a multiple of 8 coefficients for every supported N (N % 64 == 0, splits <= 8).

@@ -50,13 +50,22 @@ inline int64_t project_runs(const PackPlan& pl, int64_t items) { return cut_in_r
 // width <= unit, unit 2^steps <= N (so that every word lies inside one sample and the amounts stay below N).  THE statement
 // of these rules: the call's row of set_calls.h refuses by it (set_call_refusal).
 static_assert(kCmuxMaxDepth == 12 && kRotateMaxSteps == 64, "the messages below spell the limits out");
+// Which rule the window of an addressed word breaks, for steps >= 0: 0 none, 1 width < 1, 2 unit < width, 3 unit 2^steps > N.
+// The write states its messages below, the read of such a word (word_read, unpack_plan.h) its own under its name.
+inline int word_window_rule(int32_t N, int32_t steps, int32_t width, int32_t unit) {
+    if (width < 1) return 1;
+    if (unit < width) return 2;
+    return steps > 30 || ((int64_t)unit << steps) > N ? 3 : 0;
+}
 inline const char* write_coef_error(int32_t N, int32_t depth, int32_t steps, int32_t width, int32_t unit) {
     if (depth < 0 || depth > kCmuxMaxDepth) return "lut_write_coef: depth must lie in 0 .. 12";
     if (steps < 0 || steps > kRotateMaxSteps) return "lut_write_coef: steps must lie in 0 .. 64";
-    if (width < 1) return "lut_write_coef: width must be at least 1";
-    if (unit < width) return "lut_write_coef: unit must be at least width";
-    if (steps > 30 || ((int64_t)unit << steps) > N) return "lut_write_coef: unit x 2^steps must not exceed N";
-    return nullptr;
+    switch (word_window_rule(N, steps, width, unit)) {
+    case 1: return "lut_write_coef: width must be at least 1";
+    case 2: return "lut_write_coef: unit must be at least width";
+    case 3: return "lut_write_coef: unit x 2^steps must not exceed N";
+    default: return nullptr;
+    }
 }
 // the public amount of step t of the two rotations: the read brings coefficient unit sum b_t 2^t to position 0, the write
 // takes position 0 back there.  unit 2^t < N for t < steps by write_coef_error.

@@ -315,6 +315,20 @@ int Cmux::launch_read_own(const TgswSet& set, CmuxScratch& scratch, hipStream_t 
     return tree + launch_rotate_selected(set, scratch, stream, item0, items, depth, steps, sel_of, amount_of);
 }
 
+int Cmux::launch_read_rows(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, int32_t steps,
+                           const int32_t* sel_of, const int32_t* amount_of, const int32_t* tables, int32_t n_tables, const int32_t* table_of) {
+    check_owner(set);
+    if (items <= 0) return 0;
+    if (depth < 0 || depth > kCmuxMaxDepth || steps < 0 || steps > kRotateMaxSteps) throw std::invalid_argument("word_read: depth or steps out of range");
+    if (scratch.rows.items() < (size_t)items * 2 * kN || scratch.idx.items() < (size_t)items * (size_t)(depth + 1))
+        throw std::invalid_argument("word_read: piece larger than the reserved scratch");
+    int32_t* tree_sel = scratch.idx;
+    launch_read_indices(stream, sel_of, item0, items, depth, steps, (int32_t)set.n, false, 0, tree_sel);
+    // the tree sees a piece of its own, as launch_read's does
+    const int tree = launch_tree(set, scratch, stream, 0, items, depth, tree_sel, tables, n_tables, table_of ? table_of + item0 : nullptr, scratch.rows);
+    return tree + launch_rotate_selected(set, scratch, stream, item0, items, depth, steps, sel_of, amount_of);
+}
+
 int Cmux::launch_add(const TgswSet& set, CmuxScratch& scratch, hipStream_t stream, int64_t item0, int64_t items, int32_t depth, int32_t steps,
                      const int32_t* sel_of, const int32_t* amount_of, const int32_t* values, int32_t n_mems, const int32_t* mem_of, int32_t* out) {
     check_owner(set);

@@ -1,5 +1,6 @@
 // The calls on caller TGSW sets (include/ieache.h sections 3f to 3j and 3l: cmux, lut_tree, lut_scatter, lut_write, tlwe_rotate,
-// lut_read, lut_add, lut_write_coef): THE statement of what such a call is -- its scalars and their refusal, and its arguments as plain data.
+// lut_read, lut_add, lut_write_coef; and word_read of 3m, stated beside the table as kWordRead): THE statement of what such a call
+// is -- its scalars and their refusal, and its arguments as plain data.
 // The C ABI's device, host and reference forms (capi.cpp) and the evaluator's prelude (Evaluator::begin_set_call) loop over
 // this table; nothing else states a size, a bound or a rule of these calls.  How a call is cut into pieces is cmux_plan.h.
 // Free of HIP so that the CPU tests can check it (tests/native/set_calls_test.cpp).
@@ -11,6 +12,7 @@
 
 #include "cmux_plan.h"
 #include "project_plan.h"
+#include "unpack_plan.h"
 
 namespace ieache {
 
@@ -23,10 +25,12 @@ struct SetCall {
     int32_t n_sets = 1;  // n_tables (lut_tree, lut_read) or n_mems (lut_add)
     int32_t flags = 0, coef = 0;  // lut_read; coef is an index under N that the host and reference forms check after the arrays
     int32_t width = 0, unit = 0;  // lut_write_coef: the window's words and the distance between two addressed words
+    bool word = false;  // word_read (section 3m): lut_read's kind and pointer arguments under kWordRead's statement below, `width`
+                        // and `unit` in place of coef and the amounts (amount_of is null), count x width output rows
 };
 
 enum SetArgKind : int8_t { kArgRows, kArgIndices };
-enum SetArgSize : int8_t { kSizeItems, kSizeSelectors, kSizeSteps, kSizeTables, kSizeLeaves };  // rows or indices: set_arg_units
+enum SetArgSize : int8_t { kSizeItems, kSizeSelectors, kSizeSteps, kSizeTables, kSizeLeaves, kSizeWords };  // rows or indices: set_arg_units
 enum SetArgNeed : int8_t { kOptional, kRequired, kWithItems };  // kWithItems: null is allowed in a call without items
 enum SetArgBound : int8_t { kBoundNone, kBoundSet, kBound2N, kBoundSets };  // exclusive: the set's n, 2N, n_sets
 enum SetArgRole : int8_t { kInput, kMayBeOutput, kOutput };  // kMayBeOutput: the one input that may coincide exactly with the output
@@ -90,14 +94,24 @@ constexpr SetCallShape kSetCalls[kSetCallKinds] = {
      {kSelOf, arg_rows("d_new", kSizeItems, kWithItems, kAtRowsA), arg_rows("d_mem", kSizeLeaves, kWithItems, kAtResult, kMayBeOutput),
       arg_rows("d_out", kSizeLeaves, kWithItems, kAtNone, kOutput)}, true},
 };
+// word_read, the statement beside the table (the table's size is fixed by the tests): lut_read's arguments, whose amounts the
+// call makes itself from `unit` -- so d_amount_of is always null -- and an output of count x width rows; its scalars are
+// word_read_error's (unpack_plan.h), the one known flag IEACHE_UNPACK_NO_KEYSWITCH.  A SetCall with `word` set names it.
+constexpr SetCallShape kWordRead = {"word_read", true, true, "n_tables", kUnpackNoKeyswitch, nullptr, 5, {kSelOf, kAmountOf, kTables, kTableOf, arg_out(kSizeWords)}};
+inline const SetCallShape& set_call_shape(const SetCall& c) { return c.word ? kWordRead : kSetCalls[c.kind]; }
 using SetPtrs = std::initializer_list<const void*>;  // a call's pointer arguments in the order of `args`: entry i is begin()[i]
-inline const SetArg& set_call_output(const SetCall& c) { return kSetCalls[c.kind].args[kSetCalls[c.kind].n_args - 1]; }
+inline const SetArg& set_call_output(const SetCall& c) { return set_call_shape(c).args[set_call_shape(c).n_args - 1]; }
 
 // The first rule the scalars break as the message of the refusal, or empty: depth, then steps, then the table or memory count,
-// then the flags; a call with a window: write_coef_error's rules in its order and words (project_plan.h).  N: the ring's.
+// then the flags; a call with a window: write_coef_error's rules in its order and words (project_plan.h); word_read:
+// word_read_error's (unpack_plan.h).  N: the ring's.
 static_assert(kCmuxMaxDepth == 12 && kRotateMaxSteps == 64, "the messages below spell the limits out");
 inline std::string set_call_refusal(const SetCall& c, int32_t N) {
-    const SetCallShape& s = kSetCalls[c.kind];
+    const SetCallShape& s = set_call_shape(c);
+    if (c.word) {
+        const char* e = word_read_error(N, c.depth, c.steps, c.n_sets, c.flags, c.width, c.unit);
+        return e ? std::string(e) : std::string();
+    }
     if (s.window) {
         const char* e = write_coef_error(N, c.depth, c.steps, c.width, c.unit);
         return e ? std::string(e) : std::string();
@@ -113,13 +127,14 @@ inline std::string set_call_refusal(const SetCall& c, int32_t N) {
 
 // rows (of kArgRows) or indices `a` holds in a call whose scalars passed set_call_refusal
 inline size_t set_arg_units(const SetCall& c, const SetArg& a) {
-    const SetCallShape& s = kSetCalls[c.kind];
+    const SetCallShape& s = set_call_shape(c);
     const size_t depth = s.depth ? (size_t)c.depth : 0, steps = s.steps ? (size_t)c.steps : 0;
     switch (a.size) {
     case kSizeItems: return c.count;
     case kSizeSelectors: return c.count * (depth + steps);
     case kSizeSteps: return steps;
     case kSizeTables: return (size_t)c.n_sets << depth;
+    case kSizeWords: return c.count * (size_t)c.width;
     default: return c.count << depth;  // kSizeLeaves
     }
 }

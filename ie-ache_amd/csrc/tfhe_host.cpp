@@ -538,6 +538,34 @@ void lut_write_coef_reference(const Params& p, const Torus32* set, size_t n_set,
     lut_add_reference(p, set, n_set, count, depth, steps, sel_of, back.data(), old.data(), mem, count, own.data(), out);
 }
 
+void unpack_reference(const Params& p, const Torus32* ksk, size_t count, int32_t first, int32_t width, int32_t spread, const Torus32* in, Torus32* out) {
+    const size_t N = (size_t)p.N, W = 2 * N, row = ksk ? (size_t)p.n + 1 : N + 1;
+    std::vector<Torus32> u(ksk ? N + 1 : 0);
+    for (size_t i = 0; i < count; i++)
+        for (int32_t q = 0; q < width; q++) {
+            const int32_t coef = first + q * spread;
+            Torus32* dst = out + (i * (size_t)width + (size_t)q) * row;
+            tlwe_extract_reference(p, 1, in + i * W, &coef, ksk ? u.data() : dst);
+            if (ksk) keyswitch_reference(p, ksk, 1, u.data(), dst);
+        }
+}
+
+void word_read_reference(const Params& p, const Torus32* set, size_t n_set, const Torus32* ksk, size_t count, int32_t depth, int32_t steps, int32_t width,
+                         int32_t unit, const int32_t* sel_of, const Torus32* tables, const int32_t* table_of, Torus32* out) {
+    const size_t W = (size_t)2 * p.N, stride = (size_t)depth + (size_t)steps;
+    std::vector<int32_t> toward(steps), tree_sel(count * (size_t)depth);
+    for (int32_t s = 0; s < steps; s++) toward[s] = (int32_t)((W - (((size_t)unit << s) & (W - 1))) & (W - 1));
+    for (size_t i = 0; i < count; i++)
+        for (size_t k = 0; k < (size_t)depth; k++) {
+            const size_t at = i * stride + (size_t)steps + k;
+            tree_sel[i * (size_t)depth + k] = sel_of ? sel_of[at] : (int32_t)(at % n_set);
+        }
+    std::vector<Torus32> rows(count * W);
+    lut_tree_reference(p, set, n_set, count, depth, tree_sel.data(), tables, table_of, rows.data());
+    rotate_rows(p, set, n_set, count, steps, stride, sel_of, toward.data(), rows.data(), rows.data());
+    unpack_reference(p, ksk, count, 0, width, 1, rows.data(), out);
+}
+
 void keygen(const Params& p, const uint32_t* seed_words, int nseed, SecretKeyData* out,
             bool with_cloud) {
     out->p = p;

@@ -127,6 +127,15 @@ void lut_write_coef_reference(const Params& p, const Torus32* set, size_t n_set,
                               int32_t depth, int32_t steps, int32_t width, int32_t unit, const int32_t* sel_of, const Torus32* fresh, const Torus32* mem,
                               Torus32* out);
 
+// The way back to the gates (include/ieache.h section 3m), the references above composed; the caller has checked the window,
+// the scalars and the indices (unpack_plan.h).  unpack_reference: row (i, q) of out = tlwe_extract_reference of coefficient
+// first + q spread of in[i], then keyswitch_reference -> out [count][width][n+1]; ksk null: the extracted rows [count][width][N+1].
+// word_read_reference: lut_read_reference's tree and rotation with the amounts 2N - unit 2^t, then unpack_reference of the
+// window (0, width, 1) of the rotated rows.
+void unpack_reference(const Params& p, const Torus32* ksk, size_t count, int32_t first, int32_t width, int32_t spread, const Torus32* in, Torus32* out);
+void word_read_reference(const Params& p, const Torus32* set, size_t n_set, const Torus32* ksk, size_t count, int32_t depth, int32_t steps, int32_t width,
+                         int32_t unit, const int32_t* sel_of, const Torus32* tables, const int32_t* table_of, Torus32* out);
+
 // bootsSymEncrypt / bootsSymDecrypt on raw samples (int32[n+1]).
 void lwe_encrypt_bit(const Params& p, const int32_t* lwe_key, int bit, Rng& rng, Torus32* out);
 Torus32 lwe_phase(const Params& p, const int32_t* lwe_key, const Torus32* sample);

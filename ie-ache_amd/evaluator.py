@@ -22,6 +22,7 @@ GATE_TYPES = 11
 LUT_TREE_MAX_DEPTH = 12  # IEACHE_LUT_TREE_MAX_DEPTH
 ROTATE_MAX_STEPS = 64  # IEACHE_ROTATE_MAX_STEPS
 LUT_READ_NO_KEYSWITCH = 1  # flag of ieache_lut_read*: the extracted rows are the result
+UNPACK_NO_KEYSWITCH = 1  # the same for ieache_unpack* and ieache_word_read*
 PBS_MULTI_MAX_FACTORS = 64  # most factor polynomials of one ieache_pbs_multi* call
 PBS_NO_KEYSWITCH = 1  # flag of ieache_pbs*: the extracted samples are the result (tfhe_bootstrap_woKS_FFT)
 PBS_TLWE_POLYS = 4    # ... the table is [n_polys][2][N]: TLWE samples under the ring key (an encrypted table)
@@ -223,6 +224,13 @@ def lib():
     L.ieache_lut_write_coef_device.argtypes = [vp, vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, sp]
     L.ieache_lut_write_coef_reference.argtypes = [pp, i32p, C.c_size_t, C.c_int32, C.c_int32, i32p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32,
                                                   C.c_int32, i32p, i32p, i32p, i32p]
+    L.ieache_unpack.argtypes = [vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, i32p, C.c_int, i32p, sp]
+    L.ieache_unpack_device.argtypes = [vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int, vp, sp]
+    L.ieache_unpack_reference.argtypes = [pp, i32p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, i32p, C.c_int, i32p]
+    L.ieache_word_read.argtypes = [vp, vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p, i32p, C.c_int32, i32p, C.c_int, i32p, sp]
+    L.ieache_word_read_device.argtypes = [vp, vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, C.c_int, vp, sp]
+    L.ieache_word_read_reference.argtypes = [pp, i32p, C.c_size_t, i32p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p, i32p, C.c_int32,
+                                             i32p, C.c_int, i32p]
     L.ieache_automaton_create.restype = vp
     L.ieache_automaton_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, i32p, i32p]
     L.ieache_automaton_free.restype = None
@@ -1196,6 +1204,48 @@ class Context:
         d_out == d_mem writes in place."""
         check(lib().ieache_lut_write_coef_device(self.h, tgsw.h, count, int(depth), int(steps), int(width), int(unit), _dev(d_sel_of),
                                                  C.c_void_p(d_new), C.c_void_p(d_mem), C.c_void_p(d_out), _stats_ref(stats)))
+
+    def unpack(self, tlwe, first=0, width=1, spread=1, keyswitch=True, stats=None):
+        """The unpacking key switch on host rows (include/ieache.h section 3m), the partner of pack(): coefficients
+        first + q spread, q < width, of TLWE samples [count][2][N] (or one [2][N]) -> LWE rows [count][width][n+1] under the gate
+        key (keyswitch=False: the extracted rows [count][width][N+1]).  unpack(first=shift, spread=spread) reads back what
+        pack(spread=spread, shift=shift) placed."""
+        tlwe = np.ascontiguousarray(tlwe, dtype=np.int32).reshape(-1, 2, self.params.N)
+        out = np.zeros((tlwe.shape[0], max(int(width), 0), (self.params.n if keyswitch else self.params.N) + 1), dtype=np.int32)
+        check(lib().ieache_unpack(self.h, tlwe.shape[0], int(first), int(width), int(spread), _i32(tlwe), 0 if keyswitch else UNPACK_NO_KEYSWITCH,
+                                  _i32(out), _stats_ref(stats)))
+        return out
+
+    def unpack_device(self, count, first, width, spread, d_in, d_out, keyswitch=True, stats=None):
+        """Device pointers (ints): d_in [count][2][N] packed, d_out [count][width] rows of lwe_stride words (keyswitch=False: of
+        extract_stride words); no overlap of the two is accepted."""
+        check(lib().ieache_unpack_device(self.h, count, int(first), int(width), int(spread), C.c_void_p(d_in), 0 if keyswitch else UNPACK_NO_KEYSWITCH,
+                                         C.c_void_p(d_out), _stats_ref(stats)))
+
+    def word_read(self, tgsw, tables, depth, steps, width=1, unit=None, sel_of=None, table_of=None, keyswitch=True, count=None, stats=None):
+        """The read of an addressed word on host rows (section 3m), the partner of lut_write_coef():
+        out[i][q] = LWE row of tables[table_of[i]][hi_i].coef[lo_i unit + q], q < width.  tables [n_tables][2^depth][2][N]; sel_of
+        [count][steps + depth], the `steps` LOW address bits first (None: samples i (steps + depth) + t mod n); unit defaults to
+        width; width <= unit, unit 2^steps <= N -> [count][width][n+1] (keyswitch=False: [count][width][N+1])."""
+        depth, steps, width = int(depth), int(steps), int(width)
+        unit = width if unit is None else int(unit)
+        tables = np.ascontiguousarray(tables, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, self.params.N)
+        of = _opt_i32(sel_of, -1, max(depth + steps, 1))
+        tof = _opt_i32(table_of, -1)
+        if count is None:
+            count = tof.shape[0] if tof is not None else (of.shape[0] if of is not None and depth + steps > 0 else 1)
+        assert (tof is None or tof.shape[0] == count) and (of is None or depth + steps < 1 or of.shape[0] == count)
+        out = np.zeros((count, max(width, 0), (self.params.n if keyswitch else self.params.N) + 1), dtype=np.int32)
+        check(lib().ieache_word_read(self.h, tgsw.h, count, depth, steps, width, unit, _opt(of), _i32(tables), tables.shape[0], _opt(tof),
+                                     0 if keyswitch else UNPACK_NO_KEYSWITCH, _i32(out), _stats_ref(stats)))
+        return out
+
+    def word_read_device(self, tgsw, count, depth, steps, width, unit, d_sel_of, d_tables, n_tables, d_table_of, d_out, keyswitch=True, stats=None):
+        """Device pointers (ints; the index arrays may be None / 0): tables [n_tables][2^depth][2][N] packed, out [count][width] rows
+        of lwe_stride words (keyswitch=False: of extract_stride words)."""
+        check(lib().ieache_word_read_device(self.h, tgsw.h, count, int(depth), int(steps), int(width), int(unit), _dev(d_sel_of), C.c_void_p(d_tables),
+                                            int(n_tables), _dev(d_table_of), 0 if keyswitch else UNPACK_NO_KEYSWITCH, C.c_void_p(d_out),
+                                            _stats_ref(stats)))
 
     def pbs_multi(self, x, test_polys, factors, poly_of=None, bias=None, keyswitch=True, stats=None, tlwe=False):
         """Multi-output programmable bootstrap on host rows: ONE blind rotation per row of x [count][n+1], as pbs does it, and

@@ -369,6 +369,38 @@ def tlwe_extract_reference(params, tlwe, coef_of=None):
     return u
 
 
+def unpack_reference(params, tlwe, first=0, width=1, spread=1, ksk=None):
+    """CPU reference of Context.unpack on raw arrays (ieache_unpack_reference: the references of tlwe_extract and the key switch
+    composed; no GPU, any supported set): tlwe [count][2][N]; ksk: the key-switch key [N][t][base][n+1] as keygen_raw gives it
+    -> [count][width][n+1], or None: no key switch, the extracted rows [count][width][N+1]."""
+    tlwe = np.ascontiguousarray(tlwe, dtype=np.int32).reshape(-1, 2, params.N)
+    ksk = None if ksk is None else np.ascontiguousarray(ksk, dtype=np.int32)
+    out = np.zeros((tlwe.shape[0], max(int(width), 0), (params.N if ksk is None else params.n) + 1), dtype=np.int32)
+    check(lib().ieache_unpack_reference(C.byref(params), None if ksk is None else _i32(ksk), tlwe.shape[0], int(first), int(width), int(spread),
+                                        _i32(tlwe), 1 if ksk is None else 0, _i32(out)))
+    return out
+
+
+def word_read_reference(params, samples, tables, depth, steps, width=1, unit=None, sel_of=None, table_of=None, ksk=None, count=None):
+    """CPU reference of Context.word_read on raw arrays (ieache_word_read_reference: the references of lut_tree, tlwe_rotate and
+    unpack composed), arguments as there; ksk as for unpack_reference."""
+    depth, steps, width = int(depth), int(steps), int(width)
+    unit = width if unit is None else int(unit)
+    kpl = (params.k + 1) * params.l
+    samples = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, kpl, 2, params.N)
+    tables = np.ascontiguousarray(tables, dtype=np.int32).reshape(-1, 1 << max(depth, 0), 2, params.N)
+    of = None if sel_of is None else np.ascontiguousarray(sel_of, dtype=np.int32).reshape(-1, max(depth + steps, 1))
+    tof = None if table_of is None else np.ascontiguousarray(table_of, dtype=np.int32).reshape(-1)
+    ksk = None if ksk is None else np.ascontiguousarray(ksk, dtype=np.int32)
+    if count is None:
+        count = tof.shape[0] if tof is not None else (of.shape[0] if of is not None and depth + steps > 0 else 1)
+    out = np.zeros((count, max(width, 0), (params.N if ksk is None else params.n) + 1), dtype=np.int32)
+    check(lib().ieache_word_read_reference(C.byref(params), _i32(samples), samples.shape[0], None if ksk is None else _i32(ksk), count, depth, steps,
+                                           width, unit, None if of is None else _i32(of), _i32(tables), tables.shape[0],
+                                           None if tof is None else _i32(tof), 1 if ksk is None else 0, _i32(out)))
+    return out
+
+
 def int_to_bits(value, nbits):
     return np.array([(int(value) >> i) & 1 for i in range(nbits)], dtype=np.uint8)
 

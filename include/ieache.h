@@ -1077,7 +1077,8 @@ int ieache_debug_automaton_plan(const ieache_ctx* ctx, const ieache_automaton* a
  * rotations, the subtraction and the scatter; the small index passes and the initialising copy are not counted.
  * IEACHE_EINVAL: no projection key set; depth, steps outside their ranges; width < 1; unit < width; unit 2^steps > N; overlap; a set
  * of another context; a host pointer to the device form.
- * Not here: a word read for the gates, projecting `new`, several items replacing into ONE memory (two at one address would both
+ * The way back to the gates -- the written word read as LWE rows -- is section 3m.
+ * Not here: projecting `new`, several items replacing into ONE memory (two at one address would both
  * subtract the old value), a group form, a cloudd verb, a key-file format; the tree, rotation and scatter cover N = 1024 only,
  * the projection alone any supported set. */
 int ieache_ctx_set_projection_key(ieache_ctx* ctx, int32_t pk_t, int32_t pk_basebit, const int32_t* pk /*host [N][t][2][N]*/);
@@ -1094,6 +1095,62 @@ extern int ieache_lut_write_coef(ieache_ctx* ctx, const ieache_tgsw* set, size_t
 extern int ieache_lut_write_coef_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit,
                                  const int32_t* d_sel_of, const int32_t* d_new, const int32_t* d_mem, int32_t* d_out /* == d_mem: in place */,
                                  ieache_stats* stats);
+
+/* 3m. The way back to the gates: the unpacking key switch, and the read of an addressed word.
+ *
+ * Sections 3e to 3l carry gate outputs into TLWE samples and work on them there; these two calls carry coefficients of TLWE
+ * samples back to LWE rows under the gate key, many per call.  All arithmetic is integer mod 2^32 and every definition is a
+ * composition of definitions that exist: nothing is rounded, guarded or audited.
+ *
+ * ieache_unpack, the partner of ieache_pack: the window (first, width, spread) is public and shared by the call.  For item i
+ * and q < width:
+ *   u_{i,q}   = ieache_tlwe_extract(in[i], coef = first + q spread)                        (N + 1 words)
+ *   out[i][q] = lweKeySwitch(u_{i,q})                     (what ieache_keyswitch gives for that row)
+ * Rule: first in [0, N), width >= 1, spread >= 1, first + (width - 1) spread < N; anything else is IEACHE_EINVAL naming the
+ * rule.  ieache_unpack(first = shift, spread) reads back what ieache_pack(spread, shift) placed.  in [count][2][N] packed; the
+ * host out [count][width][n+1]; the device d_out [count][width] rows of ieache_lwe_stride words.  IEACHE_UNPACK_NO_KEYSWITCH
+ * returns the extracted rows u instead: N + 1 words per row on the host, rows of ieache_extract_stride() words on the device.
+ * Any parameter set the key switch supports (no CMux kernel is involved).  The count x width rows are cut into runs of at most
+ * `chunk` rows as every flat call's are; a run may begin and end inside an item.  Where the key switch's plan for a run is the
+ * MFMA product, the extracted rows (rows x 4 KB) are never stored: k_ksm_window_digits and k_ksm_window_init write the product's
+ * transposed digits and initial rows from the samples (the digit of an entry -A[.] is the digit of the negated word, not the
+ * negated digit).  Below "ks_mfma_min", under force_generic and on a set without the product the run's rows are stored and walked
+ * as ieache_keyswitch walks them.  Every family gives the same words.  ANY overlap of the output with the input is refused;
+ * count == 0 is a no-op; a warm call allocates nothing.
+ * stats: bootstraps == 0, levels == 1, chunks == runs == ceil(count width / min(count width, chunk)); keyswitch_launches == runs
+ * and the runs' time in keyswitch_ms -- what ieache_keyswitch reports for the same rows; with IEACHE_UNPACK_NO_KEYSWITCH
+ * keyswitch_launches == 0 and the extraction is in total_ms alone; blind_rotate_launches == 0.
+ *
+ * ieache_word_read, the partner of ieache_lut_write_coef with its address convention:
+ *   out[i][q] = LWE row of  tables[table_of[i]][hi_i].coef[lo_i unit + q],   q < width
+ *   (1) r_i  = ieache_lut_tree over tables[table_of[i]] by item i's HIGH `depth` selectors;
+ *   (2) r_i <- ieache_tlwe_rotate by its LOW `steps` selectors with the amounts (2N - unit 2^t) mod 2N  (ieache_lut_write_coef's step 2);
+ *   (3) out[i] = ieache_unpack(r_i, first 0, width, spread 1), with the same flag.
+ * The arguments are ieache_lut_read's with coef and amount_of replaced by width and unit: sel_of [count][steps + depth] laid
+ * out as in 3h / 3l (NULL: that index mod n), tables [n_tables][2^depth][2][N], table_of [count] or NULL.  Any set section 3i
+ * admits; N = 1024 only, as the tree and the rotation are.  width 1 is ieache_lut_read with coef 0 and those amounts, word for
+ * word.  The device form runs on the context's stream with no host round trip: the tree's pieces for (count, depth), the
+ * selected rows rotated in place in the context's scratch, then a piece's items x width rows unpacked in runs of at most
+ * `chunk`; everything is reserved before the first piece.  Host form: every selector and table index checked and the first bad
+ * one named; device form: clamped / mod n.
+ * stats: bootstraps == 0, levels == depth + steps, chunks == pieces, blind_rotate_launches == pieces x (max(depth, 1) +
+ * (steps > 0 ? 1 : 0)) -- the tree (a copy at depth 0) and the rotation; the small index passes are not counted --
+ * keyswitch_launches == the sum over pieces of ceil(items width / min(items width, chunk)), 0 with the flag.
+ * IEACHE_EINVAL, in ieache_lut_read's order: depth, steps outside their ranges; n_tables < 1; an unknown flag; then the window's
+ * rules, which are ieache_lut_write_coef's: width < 1; unit < width; unit 2^steps > N; overlap of the output with any input; a set
+ * of another context; null pointers; a host pointer to the device form.  A refused call writes nothing.
+ * Not here: group forms, cloudd verbs, other rings for the tree and the rotation, a one-limb form. */
+#define IEACHE_UNPACK_NO_KEYSWITCH 1
+int ieache_unpack(ieache_ctx* ctx, size_t count, int32_t first, int32_t width, int32_t spread, const int32_t* in /*[count][2][N]*/, int flags,
+                  int32_t* out /*[count][width][n+1]*/, ieache_stats* stats);
+int ieache_unpack_device(ieache_ctx* ctx, size_t count, int32_t first, int32_t width, int32_t spread, const int32_t* d_in, int flags, int32_t* d_out,
+                         ieache_stats* stats);
+int ieache_word_read(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit,
+                     const int32_t* sel_of /*[count][steps+depth] or NULL*/, const int32_t* tables /*[n_tables][2^depth][2][N]*/, int32_t n_tables,
+                     const int32_t* table_of /*[count] or NULL*/, int flags, int32_t* out /*[count][width][n+1]*/, ieache_stats* stats);
+int ieache_word_read_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit,
+                            const int32_t* d_sel_of, const int32_t* d_tables, int32_t n_tables, const int32_t* d_table_of, int flags, int32_t* d_out,
+                            ieache_stats* stats);
 
 /* ------------------------------------------------------------------ *
  * 4. CPU tools around the path (no GPU): what Keygen/keygen.c:22-51,  *
@@ -1184,6 +1241,15 @@ int ieache_automaton_reference(const ieache_params* p, const int32_t* set, size_
                                int32_t n_finals, const int32_t* final_of, int32_t* out);
 /* ... and of ieache_tlwe_extract: tlwe [count][2][N] -> u [count][N+1]. */
 int ieache_tlwe_extract_reference(const ieache_params* p, size_t count, const int32_t* tlwe, const int32_t* coef_of, int32_t* u);
+/* CPU references of section 3m on raw arrays, no GPU, no context: the references of ieache_tlwe_extract and the lookup's
+ * lweKeySwitch composed (any supported set), and those of ieache_lut_tree, ieache_tlwe_rotate and the unpacking composed.
+ * ksk [N][ks_t][2^ks_basebit][n+1] as ieache_keygen_raw gives it; it may be NULL under IEACHE_UNPACK_NO_KEYSWITCH, and out rows
+ * are then N + 1 words.  Refusals as in section 3m (the read also names the first bad selector or table index). */
+int ieache_unpack_reference(const ieache_params* p, const int32_t* ksk, size_t count, int32_t first, int32_t width, int32_t spread,
+                            const int32_t* in /*[count][2][N]*/, int flags, int32_t* out /*[count][width][n+1]*/);
+int ieache_word_read_reference(const ieache_params* p, const int32_t* set /*[n][2l][2][N]*/, size_t n, const int32_t* ksk, size_t count, int32_t depth,
+                               int32_t steps, int32_t width, int32_t unit, const int32_t* sel_of, const int32_t* tables, int32_t n_tables,
+                               const int32_t* table_of, int flags, int32_t* out /*[count][width][n+1]*/);
 /* key files -> raw arrays (sizes from ieache_params; pass NULL to query params only) */
 int ieache_read_secret_key(const char* path, ieache_params* p, int32_t* lwe_key, int32_t* tlwe_key);
 int ieache_read_cloud_key(const char* path, ieache_params* p, int32_t* bk, int32_t* ksk);
