@@ -1,7 +1,8 @@
 // Blind rotation (K0-K4), the one door: every kernel, the forms of the bootstrapping key, the twiddle tables, the rounding
 // guard's record, the sampled audit and the LDS grants are behind this object; which kernel takes a launch and cut how is
 // br_plan.h.  A caller plans a launch (br_plan), hands the plan over with the work and gets extracted samples.
-// Kernels: blind_rotate.hip (any parameter set), blind_rotate_w64.hip (N = 1024, the nine 64-lane kernels).
+// Kernels: blind_rotate.hip (any parameter set), blind_rotate_w64.hip (N = 1024, the nine 64-lane kernels), blind_rotate_h2.hip
+// (N = 2048, one two-limb kernel).
 #pragma once
 #include "br_plan.h"
 #include "device_buffer.h"
@@ -36,7 +37,8 @@ struct BrPart {
 struct BlindRotate {
     // The twist and twiddle tables of the any-parameter kernel (K.twist / K.wtab are set to them) and its dynamic LDS on the
     // current device.  Of K the blind rotation reads everything but the key-switch fields.
-    // Throws std::invalid_argument for a parameter set whose generic kernel needs more than the LDS of a CU.
+    // Throws std::invalid_argument for a parameter set whose generic kernel needs more than the LDS of a CU, unless
+    // br_h2_supported(): there a launch of the generic kernel ("force_generic") throws it instead.
     void init(const Params& p, dev::DevKeys& K);
     // raw BK [n][2l][2][N] (device) -> every form the kernels read (allocated once): the generic two-limb spectrum and,
     // where br_supported(), the 64-lane kernels' two-limb and one-limb spectra, their twiddle table and the guard record.
@@ -97,6 +99,7 @@ private:
     dev::DeviceBuffer<double2> bkf_w64_;   // spectrum in the wave-per-gate kernels' layout
     dev::DeviceBuffer<double2> tw_w64_;    // their twiddle table
     dev::DeviceBuffer<double2> bkf1_w64_;  // one-limb spectrum
+    dev::DeviceBuffer<double2> bkf_h2_;    // N = 2048: two-limb spectra of the even and odd halves (blind_rotate_h2.h)
     dev::DeviceBuffer<unsigned> guard_;
     dev::DeviceBuffer<unsigned long long> diag_;  // diagnostic builds (br_variant 8 / 49): phase stamps, allocated on first use
 };

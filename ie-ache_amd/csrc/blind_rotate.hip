@@ -7,6 +7,7 @@
 // for libtfhe's two sets (l = 3 / Bgbit = 7, l = 2 / Bgbit = 10), carried with 15 spare mantissa bits, and at most 2^46 for
 // any set Params::supported() admits (params.h: kpl x N x 2^Bgbit <= 2^32), where the modelled distance to an integer is 1/32
 // at worst (tests/test_rounding_model_cpu.py, profiles/param_lattice.txt); rounding recovers the integer exactly.
+#include "blind_rotate_h2.h"
 #include "blind_rotate_w64.h"
 
 #include <algorithm>
@@ -19,6 +20,7 @@ namespace ieache {
 namespace {
 
 constexpr int kThreads = 256;
+const char* const kLdsRefusal = "parameter set exceeds the 160 KiB LDS of a CU";
 
 using namespace dev;
 
@@ -211,9 +213,9 @@ __global__ void k_audit_compare(const Torus32* primary, const Torus32* exact, in
 void BlindRotate::init(const Params& p, DevKeys& K) {
     p_ = p;
     const int32_t M = K.M;
-    const int32_t frows = K.kpl > 4 ? K.kpl : 4;
-    generic_lds_ = (size_t)frows * M * sizeof(double2) + (size_t)2 * p.N * 4 + (((size_t)p.n * 2 + 15) & ~(size_t)15);
-    if (generic_lds_ > 160 * 1024) throw std::invalid_argument("parameter set exceeds the 160 KiB LDS of a CU");
+    generic_lds_ = br_generic_lds_bytes(p);
+    // (a set k_blind_rotate_h2 serves is accepted without it: there only a "force_generic" launch is refused, in launch())
+    if (generic_lds_ > kBrLdsMax && !br_h2_supported(p)) throw std::invalid_argument(kLdsRefusal);
     // twiddles, computed once in double precision on the host
     std::vector<double2> tw(M), w(M / 2 > 0 ? M / 2 : 1);
     for (int32_t j = 0; j < M; j++) tw[j] = make_double2(std::cos(M_PI * j / p.N), std::sin(M_PI * j / p.N));
@@ -227,7 +229,7 @@ void BlindRotate::init(const Params& p, DevKeys& K) {
     K.wtab = wtab_;
     K_ = K;
     // (per context, on the context's device: the sizes depend on the parameter set)
-    allow_dynamic_lds((const void*)k_blind_rotate_generic, generic_lds_, "k_blind_rotate_generic");
+    if (generic_lds_ <= kBrLdsMax) allow_dynamic_lds((const void*)k_blind_rotate_generic, generic_lds_, "k_blind_rotate_generic");
 }
 
 void BlindRotate::load_key(const Torus32* d_bk_raw, hipStream_t stream) {
@@ -236,6 +238,16 @@ void BlindRotate::load_key(const Torus32* d_bk_raw, hipStream_t stream) {
     K_.bkf = bkf_;
     hipLaunchKernelGGL(k_bk_to_spectrum, dim3((unsigned)npoly), dim3(kThreads), 2 * K_.M * sizeof(double2), stream, K_, d_bk_raw, bkf_);
     HIP_CHECK(hipGetLastError());
+    if (br_h2_supported(p_)) {
+        if (!bkf_h2_) bkf_h2_.allocate(h2::spectrum_elems(p_));
+        if (!tw_w64_) {
+            tw_w64_.allocate(w64::twiddle_table_elems());
+            w64::build_twiddle_table(tw_w64_, stream);
+            HIP_CHECK(hipGetLastError());
+        }
+        h2::prepare_spectrum(p_, d_bk_raw, bkf_h2_, stream);
+        HIP_CHECK(hipGetLastError());
+    }
     if (!br_supported(p_)) return;
     if (!bkf_w64_) bkf_w64_.allocate(w64::spectrum_elems(p_));
     if (!tw_w64_) {
@@ -255,7 +267,7 @@ void BlindRotate::load_key(const Torus32* d_bk_raw, hipStream_t stream) {
 }
 
 void BlindRotate::reserve(BrScratch& scratch, size_t need, const EvalOptions& opt, bool use_w64) {
-    if (use_w64) scratch.state.reserve(need, (size_t)opt.chunk, br_state_bytes_per_item(p_));
+    if (use_w64 || (br_h2_supported(p_) && !opt.force_generic)) scratch.state.reserve(need, (size_t)opt.chunk, br_state_bytes_per_item(p_));
 }
 
 int BlindRotate::launch(BrScratch& scratch, const BrPlan& plan, const EvalOptions& opt, const BrLanes& lanes, hipStream_t stream, const BrPart* parts,
@@ -267,7 +279,12 @@ int BlindRotate::launch(BrScratch& scratch, const BrPlan& plan, const EvalOption
         if (parts[q].cnt < 1) throw std::logic_error("blind-rotation launch: an empty part");
         cnt += parts[q].cnt;
     }
+    if (plan.h2) {
+        reserve(scratch, (size_t)cnt, opt, false);  // in place already unless the caller did not reserve
+        return h2::launch(p_, K_, bkf_h2_, tw_w64_, plan, stream, parts, n_parts, scratch.state, ext, steps, dbg_acc);
+    }
     if (plan.generic) {
+        if (generic_lds_ > kBrLdsMax) throw std::invalid_argument(kLdsRefusal);  // an N = 2048 set only k_blind_rotate_h2 can serve
         // the any-parameter kernel has its prologue inside it: the parts one after another, each over its own rows -- the
         // same results as a shared launch would give, without the sharing
         int64_t off = 0;

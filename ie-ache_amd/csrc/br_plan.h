@@ -107,10 +107,21 @@ inline bool br_supported(const Params& p) {
 // rounding error is 35x below the guard's limit.  For l=2 / Bgbit=10 the worst case is 2^52 and the typical error 6.5x
 // larger -- inside 0.5 but no longer clear of the limit -- so that set stays on the two-limb kernels.
 inline bool br_one_limb_supported(const Params& p) { return br_supported(p) && p.l == 3 && p.Bgbit == 7; }
+// The ring of degree 2048 (blind_rotate_h2.hip): one two-limb kernel, two waves per gate, (l, Bgbit) as launch arguments for
+// every gadget of at most 16 digit rows; longer gadgets stay on the any-parameter kernel.  No one-limb form.
+inline bool br_h2_supported(const Params& p) { return p.N == 2048 && p.k == 1 && 2 * p.l <= 16 && p.supported(); }
 // rotation amounts per gate instance as the kernels keep them (u16, padded to 16 bytes)
 inline int32_t br_bara_stride(const Params& p) { return (p.n + 7) & ~7; }
 // bytes of blind-rotation state (accumulator + rotation amounts) one gate instance keeps in HBM between slices
-inline size_t br_state_bytes_per_item(const Params& p) { return (size_t)br_bara_stride(p) * 2 + (size_t)2 * 1024 * 4; }
+inline size_t br_state_bytes_per_item(const Params& p) { return (size_t)br_bara_stride(p) * 2 + (size_t)2 * (p.N == 2048 ? 2048 : 1024) * 4; }
+
+// dynamic LDS of k_blind_rotate_generic: F [max(kpl, 4)][N / 2] double2 | acc [2][N] int32 | bara [n] u16 (padded to 16 bytes).
+// BlindRotate::init refuses a set that needs more than kBrLdsMax.  At N = 2048: 2l = 8 rows of 16 KiB + 16 KiB + bara fit, l >= 5 does not.
+constexpr size_t kBrLdsMax = 160 * 1024;  // LDS of a CU
+inline size_t br_generic_lds_bytes(const Params& p) {
+    const size_t frows = p.kpl() > 4 ? p.kpl() : 4;
+    return frows * (size_t)(p.N / 2) * 16 + (size_t)2 * p.N * 4 + (((size_t)p.n * 2 + 15) & ~(size_t)15);
+}
 
 // What the choice reads of the call in progress, besides its options.
 struct BrCall {
@@ -123,6 +134,7 @@ struct BrCall {
 
 struct BrPlan {
     bool generic = true;    // k_blind_rotate_generic, one workgroup per gate instance; nothing below applies
+    bool h2 = false;        // k_blind_rotate_h2 (N = 2048): of the fields below only `slice` applies, 1 .. 64
     int32_t variant = 0;    // a number of kBrVariants
     int32_t slice = 0;      // CMux steps per launch, final: 1 .. 64, or up to br_bara_stride() where the kernel has long_slices
     int32_t wg_gates = 0;   // gate instances per workgroup, where the kernel has a build for it (else its default build)
@@ -153,7 +165,15 @@ inline BrPlan br_plan(const Params& p, const EvalOptions& o, const BrCall& c, bo
     BrPlan pl;
     pl.generic = !use_w64;
     pl.concurrency = c.concurrency;
-    if (pl.generic) return pl;
+    if (pl.generic) {
+        // N = 2048: the one kernel of that ring unless "force_generic"; slices as the one-wave kernels of N = 1024 take them
+        if (br_h2_supported(p) && !o.force_generic) {
+            pl.generic = false;
+            pl.h2 = true;
+            pl.slice = (o.br_slice >= 1 && o.br_slice <= 64) ? (int32_t)o.br_slice : (int32_t)o.br_slice_default;
+        }
+        return pl;
+    }
     const bool exact = o.exact_fft || c.exact;
     const int32_t nb = br_bara_stride(p);
     int32_t variant = (int32_t)o.br_variant, slice = (int32_t)o.br_slice;
@@ -218,6 +238,10 @@ inline BrPlan br_plan(const Params& p, const EvalOptions& o, const BrCall& c, bo
 inline std::string br_kernel_label(const Params& p, const BrPlan& pl) {
     if (pl.generic) return "k_blind_rotate_generic";
     char tag[96];
+    if (pl.h2) {
+        snprintf(tag, sizeof tag, "<%d,%d>", (int)p.l, (int)p.Bgbit);
+        return std::string("k_blind_rotate_h2") + tag;
+    }
     if (pl.mix_named.k) {  // tw of k subsets on two waves at a time
         snprintf(tag, sizeof tag, "<%d,%d> %d of %d subsets on two waves", (int)p.l, (int)p.Bgbit, pl.mix_named.tw, pl.mix_named.k);
         return std::string("k_blind_rotate_w2r+w1b") + tag;

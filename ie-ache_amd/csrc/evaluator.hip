@@ -339,6 +339,7 @@ bool Evaluator::get_option(const std::string& name, int64_t* value) const {
 }
 
 std::string Evaluator::kernel_variant() const {
+    if (br_h2_supported(p_) && !d_->opt.force_generic) return "h2x64-radix8-twolimb";  // N = 2048: two products on the half ring per step
     if (!br_supported(p_) || d_->opt.force_generic) return "generic-radix2";
     // the kernel wide launches take: one wave per gate, on the one-limb spectrum or ("exact_fft") on the two-limb one
     return d_->opt.exact_fft ? "x1x64-radix8-twolimb" : "w1x64-radix8-onelimb";

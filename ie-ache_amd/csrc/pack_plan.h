@@ -28,6 +28,9 @@ constexpr int64_t kPackPieceRows = 4096;   // rows of a piece at most (a single 
 // key switch), and n t (2^b - 1) 128 < 2^31, so that the int32 accumulator of one byte-limb column cannot overflow.
 inline const char* pack_set_error(const Params& p, int32_t t, int32_t b) {
     if (!p.supported()) return "packing key: unsupported TFHE parameter set";
+    // pieces, R rows and the placement are stated and measured for groups of up to 1 024 rows; an N = 2048 context blind-rotates
+    // and key-switches, and refuses this key (and with it the projection key and unpack, which are this unit on n := N)
+    if (p.N > 1024) return "packing key: the packing key switch covers rings up to N = 1024";
     if (b < 1 || b > 4) return "packing key: pk_basebit must be 1 .. 4";
     if (t < 1) return "packing key: pk_t must be at least 1";
     if (t * b >= 32) return "packing key: pk_t x pk_basebit must stay below 32";

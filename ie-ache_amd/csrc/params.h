@@ -37,8 +37,9 @@ struct Params {
     // tests/test_rounding_model_cpu.py (worst distance 1/32 at the bound, 1/16 one Bgbit above it; profiles/param_lattice.txt).
     // Only l = 1 reaches it (Bgbit <= 31 - log2 N); Bgbit = 32, whose digit mask 1u << Bgbit is undefined, lies outside too.
     bool br_exact() const { return Bgbit < 32 && ((int64_t)kpl() * N << Bgbit) <= ((int64_t)1 << 32); }
+    // N = 2048 (the ring of the multi-bit parameter sets): blind_rotate_h2.hip, or the any-parameter kernel; nothing above it.
     bool supported() const {
-        return k == 1 && N >= 16 && N <= 1024 && (N & (N - 1)) == 0 && n >= 1 && l >= 1 &&
+        return k == 1 && N >= 16 && N <= 2048 && (N & (N - 1)) == 0 && n >= 1 && l >= 1 &&
                l * Bgbit <= 32 && Bgbit >= 1 && br_exact() && ks_t >= 1 && ks_basebit >= 1 &&
                ks_t * ks_basebit < 32 && ks_basebit <= 4;
     }

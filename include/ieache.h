@@ -49,7 +49,17 @@ typedef struct ieache_params {
 } ieache_params;
 
 /* libtfhe >= 1.1 new_default_gate_bootstrapping_parameters(110) (keygen.c:22-23):
- * n=630 N=1024 k=1 l=3 Bgbit=7 ks_t=8 ks_basebit=2, sigma 2^-15 / 2^-25. */
+ * n=630 N=1024 k=1 l=3 Bgbit=7 ks_t=8 ks_basebit=2, sigma 2^-15 / 2^-25.
+ *
+ * Accepted sets (anything else is IEACHE_EINVAL when a key header is read, a key generated or a context created): k = 1; N a
+ * power of two in 16 .. 2048; n >= 1; l Bgbit <= 32 with 2 l N 2^Bgbit <= 2^32; ks_t ks_basebit < 32 with ks_basebit <= 4.
+ * N = 2048: gates, gates3, mux, eval_batch, netlists, programs, pbs / pbs_multi with every flag,
+ * keyswitch, tlwe_extract, lut_test_poly / lut_factor_poly and the group forms work as at N = 1024, on a two-limb kernel that is
+ * exact for any words: there is no one-limb form, no rounding guard and no audit, so ieache_ctx_fft_audit reports zero audited
+ * launches.  Refused on such a context, each with its message: ieache_tgsw_prepare* and with them every call on a TGSW set
+ * (N = 1024 only), the packing and the projection key and with them pack, tlwe_project, unpack and lut_write_coef, a gadget of
+ * more than 16 rows (l > 8), and ks_t >= 19 (the key switch's digit list of N ks_t words exceeds a CU's LDS); the "force_generic"
+ * option on a set with l >= 5 makes a call fail with the LDS message instead of running. */
 void ieache_default_params(ieache_params* out);
 
 typedef struct ieache_stats {
@@ -725,7 +735,7 @@ int ieache_debug_mix_plan(int cus, int n, int64_t gates, int s1, int ratio_x100,
  * This is an integer definition: every implementation gives the same words whatever its order of summation (the device
  * computes the first line as an int8 matrix product, csrc/pack_keyswitch.hip; nothing is rounded, guarded or audited).
  *
- * Accepted: b in 1 .. 4, t >= 1, t b < 32, n t (2^b - 1) 128 < 2^31, on any supported parameter set; anything else is
+ * Accepted: b in 1 .. 4, t >= 1, t b < 32, n t (2^b - 1) 128 < 2^31, on any supported parameter set with N <= 1024; anything else is
  * IEACHE_EINVAL with a message, when the key is generated and when it is set.
  *
  * ieache_ctx_set_packing_key takes the key from HOST memory and keeps only its device form; a second call replaces the first
