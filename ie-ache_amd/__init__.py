@@ -12,12 +12,13 @@ from .evaluator import (  # noqa: F401
     GATE_MAJ3, GATE_XOR3, CIRC_ADD_FA, CIRC_SUB_FA, CIRC_RSUB_FA, CIRC_MUL_FA, circuit_gate_count,
     PBS_NO_KEYSWITCH, PBS_TLWE_POLYS, PBS_ACCUMULATOR, PBS_MULTI_MAX_FACTORS, Group, GROUP_MAX_DEVICES, Job,
     TgswSet, Automaton, AUTOMATON_MAX_STATES, AUTOMATON_MAX_STEPS, automaton_tables, LUT_TREE_MAX_DEPTH, ROTATE_MAX_STEPS, LUT_READ_NO_KEYSWITCH,
-    UNPACK_NO_KEYSWITCH,
+    UNPACK_NO_KEYSWITCH, ROWS_LWE, ROWS_EXTRACTED, ROWS_TLWE, LINEAR_MAX_DIM,
     FFT_FORWARD_FORMS, FFT_INVERSE_FORMS, FFT_PAIRED_FORMS, TWIDDLE_ENTRIES,
 )
 from . import tools  # noqa: F401
 from . import netlists  # noqa: F401
 from . import automata  # noqa: F401
+from . import layers  # noqa: F401
 from . import programs  # noqa: F401
 from .programs import WordProgram, Register, netlist_export  # noqa: F401
 from .programs import FAMILY_REFERENCE, FAMILY_KOGGE_STONE, FAMILY_CARRY_SAVE, FAMILY_FULL_ADDER  # noqa: F401

@@ -23,6 +23,7 @@
 #include "fft_probe.h"
 #include "group.h"
 #include "group_run.h"
+#include "linear_plan.h"
 #include "mix_plan.h"
 #include "pack_plan.h"
 #include "project_plan.h"
@@ -878,6 +879,64 @@ int ieache_keyswitch(ieache_ctx* ctx, size_t count, const int32_t* u, int32_t* o
         StagedRows du(h.ev, kStageExtracted, count, (size_t)h.ev.extract_stride(), u, (size_t)h.p.N + 1), dout = h.results(count);
         with_stats(stats, [&](EvalStats* st) { h.ev.keyswitch_device(count, du.p, dout.p, st); });
         h.download(dout, out);
+        return 0;
+    });
+}
+
+// ---- linear layers on encrypted rows (section 3n).  linear_plan.h states the kinds and the rules; what needs no context is
+// judged before the context is looked at. ----
+static_assert(kLinearRowsLwe == IEACHE_ROWS_LWE && kLinearRowsExtracted == IEACHE_ROWS_EXTRACTED && kLinearRowsTlwe == IEACHE_ROWS_TLWE &&
+                  kLinearMaxDim == IEACHE_LINEAR_MAX_DIM,
+              "linear_plan.h knows the constants of include/ieache.h");
+namespace {
+// 0 with *c filled, or the code after fail()
+int check_linear(const ieache_ctx* ctx, bool device, int rows, size_t batch, int32_t n_out, int32_t n_in, const int8_t* w, const int32_t* bias,
+                 const int32_t* x, const int32_t* out, LinearCall* c) {
+    if (const char* e = linear_scalar_error(rows, n_out, n_in, bias != nullptr)) return fail(IEACHE_EINVAL, e);
+    if (!ctx) return fail(IEACHE_EINVAL, kLinearNull);
+    c->rows = rows, c->batch = batch, c->n_out = n_out, c->n_in = n_in, c->w = w, c->bias = bias, c->x = x, c->out = out, c->device = device;
+    if (const char* e = linear_call_error(ctx->eval->params(), *c)) return fail(IEACHE_EINVAL, e);
+    return 0;
+}
+}  // namespace
+
+int ieache_lwe_linear_device(ieache_ctx* ctx, int rows, size_t batch, int32_t n_out, int32_t n_in, const int8_t* d_w, const int32_t* d_bias,
+                             const int32_t* d_x, int32_t* d_out, ieache_stats* stats) {
+    return guarded([&] {
+        LinearCall c;
+        if (const int rc = check_linear(ctx, true, rows, batch, n_out, n_in, d_w, d_bias, d_x, d_out, &c)) return rc;
+        require_device_pointers(batch, {{d_w, "d_w"}, {d_bias, "d_bias", true}, {d_x, "d_x"}, {d_out, "d_out"}});
+        return with_stats(stats, [&](EvalStats* st) { ctx->eval->lwe_linear_device(rows, batch, n_out, n_in, d_w, d_bias, d_x, d_out, st); });
+    });
+}
+
+int ieache_lwe_linear(ieache_ctx* ctx, int rows, size_t batch, int32_t n_out, int32_t n_in, const int8_t* w, const int32_t* bias, const int32_t* x,
+                      int32_t* out, ieache_stats* stats) {
+    return guarded([&] {
+        LinearCall c;
+        if (const int rc = check_linear(ctx, false, rows, batch, n_out, n_in, w, bias, x, out, &c)) return rc;
+        if (batch == 0) return 0;
+        HostCall h(ctx, batch);
+        const LinearRows r = linear_rows(h.p, rows);
+        // each kind's rows in the slot that holds rows of its shape (LWE rows: an operand slot, n + 1 words of lwe_stride() as ever)
+        const StageSlot slot = rows == kLinearRowsLwe ? kStageA : rows == kLinearRowsExtracted ? kStageExtracted : kStageTlweA;
+        StagedRows dx(h.ev, slot, batch * (size_t)n_in, (size_t)r.stride, x, (size_t)r.words);
+        StagedRows dout(h.ev, kStageOut, batch * (size_t)n_out, (size_t)r.stride), dbi = h.words(kStageBias, bias, (size_t)n_out);
+        const size_t w_bytes = (size_t)n_out * (size_t)n_in;
+        int8_t* dw = reinterpret_cast<int8_t*>(h.ev.staging(kStageFactors, w_bytes));
+        HIP_CHECK(hipMemcpy(dw, w, w_bytes, hipMemcpyHostToDevice));
+        with_stats(stats, [&](EvalStats* st) { h.ev.lwe_linear_device(rows, batch, n_out, n_in, dw, dbi.p, dx.p, dout.p, st); });
+        dout.download(out, (size_t)r.words);
+        return 0;
+    });
+}
+
+int ieache_debug_linear_plan(const ieache_ctx* ctx, int rows, size_t batch, int32_t n_out, int32_t n_in, int64_t out[4]) {
+    return guarded([&] {
+        (void)batch;  // the tiling of a call does not depend on it: gridDim.x is batch x column blocks
+        if (const char* e = linear_scalar_error(rows, n_out, n_in, false)) return fail(IEACHE_EINVAL, e);
+        if (!ctx || !out) return fail(IEACHE_EINVAL, kLinearNull);
+        ctx->eval->linear_plan_figures(rows, n_out, n_in, out);
         return 0;
     });
 }
@@ -2009,6 +2068,21 @@ int ieache_automaton_reference(const ieache_params* p, const int32_t* set, size_
         if (const int rc = check_indices(sel_of, count * (size_t)steps, (int64_t)n, "automaton_run", "sel_of")) return rc;
         if (const int rc = check_indices(final_of, count, n_finals, "automaton_run", "final_of")) return rc;
         automaton_reference(pp, set, n, states, steps, n_out, next0, next1, count, sel_of, finals, final_of, out);
+        return 0;
+    });
+}
+
+int ieache_lwe_linear_reference(const ieache_params* p, int rows, size_t batch, int32_t n_out, int32_t n_in, const int8_t* w, const int32_t* bias,
+                                const int32_t* x, int32_t* out) {
+    return guarded([&] {
+        if (const char* e = linear_scalar_error(rows, n_out, n_in, bias != nullptr)) return fail(IEACHE_EINVAL, e);
+        if (!p) return fail(IEACHE_EINVAL, kLinearNull);
+        const Params pp = to_params(*p);
+        if (!pp.supported()) return fail(IEACHE_EINVAL, "lwe_linear_reference: unsupported TFHE parameter set");
+        LinearCall c;
+        c.rows = rows, c.batch = batch, c.n_out = n_out, c.n_in = n_in, c.w = w, c.bias = bias, c.x = x, c.out = out;
+        if (const char* e = linear_call_error(pp, c)) return fail(IEACHE_EINVAL, e);
+        lwe_linear_reference(linear_rows(pp, rows), batch, n_out, n_in, w, bias, x, out);
         return 0;
     });
 }

@@ -249,6 +249,17 @@ public:
     void unpack_device(size_t count, int32_t first, int32_t width, int32_t spread, int32_t flags, const Torus32* d_in, Torus32* d_out, EvalStats* stats);
     void word_read_device(const TgswSet& set, size_t count, int32_t depth, int32_t steps, int32_t width, int32_t unit, const int32_t* d_sel_of,
                           const Torus32* d_tables, int32_t n_tables, const int32_t* d_table_of, int32_t flags, Torus32* d_out, EvalStats* stats);
+    // Linear layers on encrypted rows (include/ieache.h section 3n; linear_plan.h states the row kinds, the rules and the choice
+    // of kernel).  lwe_linear_device: out[b][i] = sum_j W[i][j] x[b][j] (+ bias[i] on the kind's bias word) mod 2^32 over rows
+    // of the kind `rows`: d_x [batch][n_in] and d_out [batch][n_out] rows of the kind's stride, d_w [n_out][n_in] int8, d_bias
+    // [n_out] or null; every word of d_out up to the stride is written.  One launch of the unit (lwe_linear.h) on the
+    // evaluator's stream ("linear_kernel": 0 by n_out, 1 simple, 2 the MFMA product); needs no key.  Exact integer arithmetic: no
+    // guard, no audit.  stats: bootstraps 0, no rotation and no key-switch launch, levels 1, chunks 1, the time in total_ms alone.
+    // std::invalid_argument with linear_call_error's words.  linear_plan_figures: kernel (1 simple, 2 MFMA), column blocks,
+    // output tiles per wave, K steps of such a call under the option as it is.
+    void lwe_linear_device(int32_t rows, size_t batch, int32_t n_out, int32_t n_in, const int8_t* d_w, const int32_t* d_bias, const Torus32* d_x,
+                           Torus32* d_out, EvalStats* stats);
+    void linear_plan_figures(int32_t rows, int32_t n_out, int32_t n_in, int64_t out[4]) const;
     // Automata over words of TGSW-encrypted bits (include/ieache.h section 3k; automaton_plan.h states what one is and how a
     // call is cut).  automaton_create: the tables [steps][states] from host memory -> an object the caller owns (delete it before
     // or after this evaluator goes; only this evaluator accepts it); std::invalid_argument with the first rule broken.

@@ -28,6 +28,7 @@
 #include "fft_probe.h"
 #include "joint_plan.h"
 #include "keyswitch.h"
+#include "lwe_linear.h"
 #include "multi_extract.h"
 #include "pack.h"
 #include "scoped_set.h"
@@ -182,6 +183,7 @@ struct Evaluator::Impl {
     Pack pack;  // the packing key switch (LWE rows -> TLWE samples): kernels, key form and the cut of a call (pack_plan.h)
     Pack project;  // the same unit on project_params(): the projection key (TLWE sample -> the window of its coefficients, section 3l)
     Cmux cmux;  // CMux on caller TGSW samples, its tree and the extraction of a coefficient: kernels, twiddles, the cut (cmux_plan.h)
+    LweLinear linear;  // linear layers on encrypted rows: kernels and the prepared weights (linear_plan.h states the calls)
     MultiExtract mv;  // between K3 and K5 of a multi-output programmable bootstrap: the factors' lists and the extraction by factor
     DeviceBuffer<Torus32> store;    // circuits: the wire store, the gate and the output table
     DeviceBuffer<DevGate> d_gates;
@@ -255,6 +257,7 @@ void Evaluator::init() {
     d_->mv.init(p);
     d_->pack.init(p);
     d_->project.init(project_params(p));
+    d_->linear.init(p);
     d_->cmux.init(p, device_, &d_->opt.cmux_gadget_runtime);
 }
 
@@ -1439,6 +1442,32 @@ void Evaluator::tlwe_extract_device(size_t count, const Torus32* d_tlwe, const i
         d_->cmux.launch_extract(stream_, (int64_t)count, d_tlwe, d_coef_of, d_u, extract_stride());
         HIP_CHECK(hipGetLastError());
     });
+}
+
+// A linear layer: one piece whose one launch of the unit belongs to neither kind of phase, as tlwe_extract_device's.  No key is
+// read, so begin_call() is not asked for one.
+void Evaluator::lwe_linear_device(int32_t rows, size_t batch, int32_t n_out, int32_t n_in, const int8_t* d_w, const int32_t* d_bias, const Torus32* d_x,
+                                  Torus32* d_out, EvalStats* stats) {
+    LinearCall c;
+    c.rows = rows, c.batch = batch, c.n_out = n_out, c.n_in = n_in, c.w = d_w, c.bias = d_bias, c.x = d_x, c.out = d_out, c.device = true;
+    if (const char* e = linear_call_error(p_, c)) throw std::invalid_argument(e);
+    if (linear_rows(p_, kLinearRowsExtracted).stride != extract_stride()) throw std::logic_error("lwe_linear: linear_plan.h and extract_stride() disagree");
+    HIP_CHECK(hipSetDevice(device_));
+    if (batch == 0) return;
+    const LinearPlan pl = d_->linear.plan(rows, n_out, n_in, (int32_t)d_->opt.linear_kernel);
+    run_pieces(Cut{1, (int64_t)batch}, (int64_t)batch, 1, stats, [&](Piece&) {
+        d_->linear.launch(stream_, pl, rows, batch, n_out, n_in, d_w, d_bias, d_x, d_out);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+void Evaluator::linear_plan_figures(int32_t rows, int32_t n_out, int32_t n_in, int64_t out[4]) const {
+    if (const char* e = linear_scalar_error(rows, n_out, n_in, false)) throw std::invalid_argument(e);
+    const LinearPlan pl = d_->linear.plan(rows, n_out, n_in, (int32_t)d_->opt.linear_kernel);
+    out[0] = pl.kernel;
+    out[1] = pl.col_blocks;
+    out[2] = pl.wave_tiles;
+    out[3] = pl.k_steps;
 }
 
 void Evaluator::eval_circuit_device(const Circuit& c, size_t batch, const Torus32* d_in, Torus32* d_out, EvalStats* stats) {

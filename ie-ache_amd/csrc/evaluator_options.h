@@ -30,6 +30,7 @@ struct EvalOptions {
     int64_t cmux_piece_rows = 8192;
     int64_t cmux_gadget_runtime = 0;  // debug: every TGSW set on the run-time-gadget builds (cmux_step.h)
     int64_t automaton_steps_per_launch = 0;  // automata: steps of one launch at most (automaton_plan.h); 0 = by the plan
+    int64_t linear_kernel = 0;  // linear layers (linear_plan.h): 0 = by n_out, 1 = the simple kernel, 2 = the MFMA product
     // blind rotation: which kernel takes a launch of how many gate instances (br_plan.h)
     int64_t br_slice = 0, br_slice_default = 16, br_variant = 0;
     int64_t br_wide_max = 0, one_limb_min = 0, four_wave_max = 0, two_wave_max = 0;  // per CU
@@ -83,6 +84,7 @@ inline constexpr OptionRow kOptionTable[] = {
     {IEACHE_OPT(cmux_piece_rows, nullptr), 1, 1 << 20, nullptr, "rows of a launch of a CMux call, and of the first level of a piece of a CMux tree, at most (whole items; default kCmuxPieceRows = 8192: 96 MB of tree scratch; cmux_plan.h)"},
     {IEACHE_OPT(cmux_gadget_runtime, nullptr), 0, 1, nullptr, "unstable, measurement aid: 1 = every TGSW set runs on the builds of the CMux kernels that take (l, Bgbit) as launch arguments, the key's two gadgets included"},
     {IEACHE_OPT(automaton_steps_per_launch, nullptr), 0, 4096, nullptr, "steps of an automaton per launch at most (1 = a launch per step, the hand-off a kernel boundary); 0 = every step in one launch while steps x rounds stays within kAutomatonLaunchRounds, equal chunks above (automaton_plan.h)"},
+    {IEACHE_OPT(linear_kernel, nullptr), 0, 2, nullptr, "the kernel of lwe_linear: 1 = a thread per output word (k_linear_simple), 2 = the int8 MFMA product (k_linear_mfma); 0 = by n_out (kLinearMfmaMinOut, linear_plan.h)"},
     {IEACHE_OPT(br_slice, nullptr), 0, 4096, nullptr, "CMux steps per blind-rotation launch; 0 = by kernel and launch size (16 over several rounds of resident gates, 64 while all are resident, the whole rotation for the four-wave and latency kernels)"},
     {IEACHE_OPT(br_slice_default, "IEACHE_BR_SLICE"), 1, 64, nullptr, "... where neither br_slice nor the launch size says otherwise, and where the kernel cannot take what br_slice says"},
     {IEACHE_OPT(br_variant, "IEACHE_BR_VARIANT"), 0, 1000, nullptr, "hook (variant_known; a retired number is reported on stderr): a number of br_plan.h's table; 0 = by launch size"},

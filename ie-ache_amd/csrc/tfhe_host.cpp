@@ -488,6 +488,23 @@ void automaton_reference(const Params& p, const Torus32* set, size_t n_set, int3
     }
 }
 
+void lwe_linear_reference(const LinearRows& r, size_t batch, int32_t n_out, int32_t n_in, const int8_t* w, const int32_t* bias, const Torus32* x,
+                          Torus32* out) {
+    const size_t words = (size_t)r.words;
+#pragma omp parallel for collapse(2) schedule(static)
+    for (int64_t b = 0; b < (int64_t)batch; b++)
+        for (int32_t i = 0; i < n_out; i++) {
+            Torus32* dst = out + ((size_t)b * n_out + i) * words;
+            for (size_t q = 0; q < words; q++) dst[q] = 0;
+            for (int32_t j = 0; j < n_in; j++) {
+                const uint32_t f = (uint32_t)(int32_t)w[(size_t)i * n_in + j];
+                const Torus32* src = x + ((size_t)b * n_in + j) * words;
+                for (size_t q = 0; q < words; q++) dst[q] = (Torus32)((uint32_t)dst[q] + f * (uint32_t)src[q]);
+            }
+            if (bias && r.bias_word >= 0) dst[r.bias_word] = (Torus32)((uint32_t)dst[r.bias_word] + (uint32_t)bias[i]);
+        }
+}
+
 void tlwe_extract_reference(const Params& p, size_t count, const Torus32* tlwe, const int32_t* coef_of, Torus32* u) {
     const int32_t N = p.N;
     for (size_t r = 0; r < count; r++) {

@@ -6,6 +6,7 @@
 // 822-824 (bootsSymDecrypt / bootsSymEncrypt of the metadata words).
 // None of this is on the bootstrapped-gate hot path.
 #pragma once
+#include "linear_plan.h"
 #include "params.h"
 
 namespace ieache {
@@ -110,6 +111,12 @@ void lut_add_reference(const Params& p, const Torus32* set, size_t n_set, size_t
 // Every state of every step is computed: no liveness, no copies.  Tables and indices already checked by the caller.
 void automaton_reference(const Params& p, const Torus32* set, size_t n_set, int32_t states, int32_t steps, int32_t n_out, const int32_t* next0,
                          const int32_t* next1, size_t count, const int32_t* sel_of, const Torus32* finals, const int32_t* final_of, Torus32* out);
+
+// A linear layer (include/ieache.h section 3n) on packed host rows of r.words words: out[b][i][w] = sum_j W[i][j] x[b][j][w]
+// (+ bias[i] on r.bias_word; bias null: none) with 32-bit wrap-around, the definition as it reads.  Checked by the caller
+// (linear_call_error).
+void lwe_linear_reference(const LinearRows& r, size_t batch, int32_t n_out, int32_t n_in, const int8_t* w, const int32_t* bias, const Torus32* x,
+                          Torus32* out);
 
 // coefficient coef_of[r] (null: 0; checked by the caller) of tlwe [count][2][N] as extracted rows u [count][N+1]
 void tlwe_extract_reference(const Params& p, size_t count, const Torus32* tlwe, const int32_t* coef_of, Torus32* u);

@@ -243,6 +243,11 @@ def lib():
                                              i32p, i32p]
     L.ieache_debug_automaton_plan.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_int64)]
     L.ieache_tlwe_extract.argtypes = [vp, C.c_size_t, i32p, i32p, i32p, sp]
+    i8p = C.POINTER(C.c_int8)
+    L.ieache_lwe_linear_device.argtypes = [vp, C.c_int, C.c_size_t, C.c_int32, C.c_int32, vp, vp, vp, vp, sp]
+    L.ieache_lwe_linear.argtypes = [vp, C.c_int, C.c_size_t, C.c_int32, C.c_int32, i8p, i32p, i32p, i32p, sp]
+    L.ieache_lwe_linear_reference.argtypes = [pp, C.c_int, C.c_size_t, C.c_int32, C.c_int32, i8p, i32p, i32p, i32p]
+    L.ieache_debug_linear_plan.argtypes = [vp, C.c_int, C.c_size_t, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
     L.ieache_tlwe_extract_device.argtypes = [vp, C.c_size_t, vp, vp, vp, sp]
     L.ieache_debug_cmux_plan.argtypes = [vp, C.c_size_t, C.c_int32, C.POINTER(C.c_int64)]
     L.ieache_tgsw_encrypt.argtypes = [pp, i32p, i32p, C.c_size_t, C.c_double, C.c_uint64, i32p]
@@ -380,6 +385,47 @@ def _pbs_out(params, count, keyswitch, accumulator):
     if accumulator:
         return np.zeros((count, 2, params.N), dtype=np.int32)
     return np.zeros((count, (params.n if keyswitch else params.N) + 1), dtype=np.int32)
+
+
+# the row kinds of a linear layer (include/ieache.h section 3n)
+ROWS_LWE, ROWS_EXTRACTED, ROWS_TLWE = 0, 1, 2
+LINEAR_MAX_DIM = 65536
+_ROWS_KINDS = {"lwe": ROWS_LWE, "extracted": ROWS_EXTRACTED, "tlwe": ROWS_TLWE}
+
+
+def linear_rows_kind(rows):
+    """"lwe" / "extracted" / "tlwe", or the number itself (an unknown number goes to the library, which refuses it)"""
+    if isinstance(rows, str):
+        if rows not in _ROWS_KINDS:
+            raise ValueError("lwe_linear: rows must be one of %s" % ", ".join(sorted(_ROWS_KINDS)))
+        return _ROWS_KINDS[rows]
+    return int(rows)
+
+
+def linear_row_words(params, rows):
+    """words of a host row of that kind: n + 1, N + 1, 2N (None for a kind the library does not know)"""
+    return {ROWS_LWE: params.n + 1, ROWS_EXTRACTED: params.N + 1, ROWS_TLWE: 2 * params.N}.get(linear_rows_kind(rows))
+
+
+def linear_weights(W, bias=None):
+    """W as the int8 matrix [n_out][n_in] the library takes and bias as int32 [n_out] or None; ValueError for a weight outside
+    -128 .. 127 -- before the library is called -- or a bias of another length"""
+    W = np.asarray(W)
+    if W.ndim != 2 or not (np.issubdtype(W.dtype, np.integer) or W.dtype == np.bool_):
+        raise ValueError("lwe_linear: W must be an integer matrix [n_out][n_in]")
+    if W.size and (int(W.min()) < -128 or int(W.max()) > 127):
+        raise ValueError("lwe_linear: weights must lie in -128 .. 127 (wider ones: a second call with shifted weights)")
+    W = np.ascontiguousarray(W, dtype=np.int8)
+    if bias is not None:
+        bias = np.ascontiguousarray(np.asarray(bias, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32).view(np.int32).reshape(-1)
+        if bias.shape[0] != W.shape[0]:
+            raise ValueError("lwe_linear: bias must hold one word per output")
+    return W, bias
+
+
+def _i8(a):
+    assert a.dtype == np.int8 and a.flags["C_CONTIGUOUS"]
+    return a.ctypes.data_as(C.POINTER(C.c_int8))
 
 
 def _stats_ref(stats):
@@ -1110,6 +1156,36 @@ class Context:
     def tlwe_extract_device(self, count, d_tlwe, d_coef_of, d_u, stats=None):
         """Device pointers (ints; d_coef_of may be None / 0): samples [count][2][N] packed, d_u rows of extract_stride."""
         check(lib().ieache_tlwe_extract_device(self.h, count, C.c_void_p(d_tlwe), _dev(d_coef_of), C.c_void_p(d_u), _stats_ref(stats)))
+
+    def lwe_linear(self, x, W, bias=None, rows="lwe", stats=None):
+        """A linear layer on host rows (include/ieache.h section 3n): x [batch][n_in][words] (or [n_in][words] for one batch
+        element), W an integer matrix [n_out][n_in] with values in -128 .. 127, bias [n_out] Torus32 words or None, rows "lwe"
+        (n + 1 words, bias on b), "extracted" (N + 1) or "tlwe" (2N, no bias) -> out[b][i] = sum_j W[i][j] x[b][j] (+ bias[i])
+        mod 2^32, [batch][n_out][words]."""
+        kind = linear_rows_kind(rows)
+        W, bias = linear_weights(W, bias)
+        x = np.ascontiguousarray(x, dtype=np.int32)
+        words = linear_row_words(self.params, kind)
+        if words is not None:
+            if x.ndim < 2 or x.shape[-1] != words or x.shape[-2] != W.shape[1]:
+                raise ValueError("lwe_linear: x must be [batch][n_in = %d][words = %d]" % (W.shape[1], words))
+            x = x.reshape(-1, W.shape[1], words)
+        out = np.zeros((x.shape[0], W.shape[0], x.shape[-1]), dtype=np.int32)
+        check(lib().ieache_lwe_linear(self.h, kind, x.shape[0], W.shape[0], W.shape[1], _i8(W), _opt(bias), _i32(x), _i32(out), _stats_ref(stats)))
+        return out
+
+    def lwe_linear_device(self, rows, batch, n_out, n_in, d_w, d_bias, d_x, d_out, stats=None):
+        """Device pointers (ints): d_w int8 [n_out][n_in], d_bias int32 [n_out] or None, d_x [batch][n_in] and d_out
+        [batch][n_out] rows of the kind's stride (lwe_stride, extract_stride, 2N).  Runs on the context's stream."""
+        check(lib().ieache_lwe_linear_device(self.h, linear_rows_kind(rows), batch, int(n_out), int(n_in), C.c_void_p(d_w), _dev(d_bias),
+                                             C.c_void_p(d_x), C.c_void_p(d_out), _stats_ref(stats)))
+
+    def linear_plan(self, rows, batch, n_out, n_in):
+        """What such a call takes under "linear_kernel" as it is (csrc/linear_plan.h): dict(kernel -- 1 simple, 2 MFMA --,
+        col_blocks, wave_tiles, k_steps)."""
+        out = (C.c_int64 * 4)()
+        check(lib().ieache_debug_linear_plan(self.h, linear_rows_kind(rows), int(batch), int(n_out), int(n_in), out))
+        return dict(zip(("kernel", "col_blocks", "wave_tiles", "k_steps"), (int(v) for v in out)))
 
     def set_packing_key(self, pk, t=8, basebit=2):
         """The packing key [n][t][2][N] (tools.packing_keygen) for pack(): replaces an earlier one; pk=None drops it."""

@@ -359,6 +359,23 @@ def automaton_reference(params, samples, next0, next1, finals, n_out=1, sel_of=N
     return out
 
 
+def lwe_linear_reference(params, x, W, bias=None, rows="lwe"):
+    """CPU reference of Context.lwe_linear (ieache_lwe_linear_reference; no GPU, no context): x [batch][n_in][words], W an
+    integer matrix [n_out][n_in] in -128 .. 127, bias [n_out] or None, rows "lwe" / "extracted" / "tlwe" -> [batch][n_out][words]."""
+    from .evaluator import linear_rows_kind, linear_row_words, linear_weights, _i8, _opt
+    kind = linear_rows_kind(rows)
+    W, bias = linear_weights(W, bias)
+    x = np.ascontiguousarray(x, dtype=np.int32)
+    words = linear_row_words(params, kind)
+    if words is not None:
+        if x.ndim < 2 or x.shape[-1] != words or x.shape[-2] != W.shape[1]:
+            raise ValueError("lwe_linear: x must be [batch][n_in = %d][words = %d]" % (W.shape[1], words))
+        x = x.reshape(-1, W.shape[1], words)
+    out = np.zeros((x.shape[0], W.shape[0], x.shape[-1]), dtype=np.int32)
+    check(lib().ieache_lwe_linear_reference(C.byref(params), kind, x.shape[0], W.shape[0], W.shape[1], _i8(W), _opt(bias), _i32(x), _i32(out)))
+    return out
+
+
 def tlwe_extract_reference(params, tlwe, coef_of=None):
     """CPU reference of Context.tlwe_extract (ieache_tlwe_extract_reference): tlwe [count][2][N] -> [count][N+1]."""
     tlwe = np.ascontiguousarray(tlwe, dtype=np.int32).reshape(-1, 2, params.N)

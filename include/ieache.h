@@ -1162,6 +1162,60 @@ int ieache_word_read_device(ieache_ctx* ctx, const ieache_tgsw* set, size_t coun
                             const int32_t* d_sel_of, const int32_t* d_tables, int32_t n_tables, const int32_t* d_table_of, int flags, int32_t* d_out,
                             ieache_stats* stats);
 
+/* 3n. Linear layers on encrypted rows: a public int8 matrix times LWE rows.
+ *
+ * A computation on small encrypted integers alternates two steps: a linear combination of rows with public integer weights,
+ * then a table lookup (ieache_pbs).  This is the first step, on rows that stay on the device: scalar multiples and sums of
+ * ciphertexts, x p + y ahead of one bivariate table, sums ahead of a single key switch, slot-wise arithmetic on packed samples,
+ * a dense layer with a table activation.  Three kinds of rows:
+ *
+ *     kind                       words    device stride              bias word
+ *     IEACHE_ROWS_LWE       0    n + 1    ieache_lwe_stride()        n
+ *     IEACHE_ROWS_EXTRACTED 1    N + 1    ieache_extract_stride()    N
+ *     IEACHE_ROWS_TLWE      2    2N       2N                         none (bias must be NULL)
+ *
+ *     out[b][i][w] = ( sum_{j < n_in} W[i][j] x[b][j][w]  +  [w == bias word] bias[i] )  mod 2^32
+ *                    for b < batch, i < n_out, w < words
+ *
+ * x is [batch][n_in] rows and out [batch][n_out] rows; W is int8_t [n_out][n_in], row-major, the full range -128 .. 127; bias
+ * is int32 [n_out] (Torus32) or NULL.  Host arrays are packed rows of `words`; device rows use the stride above, and every
+ * padding word of an output row is written as zero, as ieache_pbs_multi writes it.  The call reads no key and works on every
+ * parameter set a context accepts, N = 2048 included.  All arithmetic is integer mod 2^32: nothing is rounded, guarded or
+ * audited, and the two kernels give the same words.  Noise: the output's variance is sum_j W[i][j]^2 times a row's, and an
+ * offset common to the rows enters with sum_j W[i][j] (DESIGN.md section 7 gives the margin of a layer).
+ * Kernels (context option "linear_kernel": 0 = by n_out, the default; 1; 2 -- any other value is refused):
+ *   1  k_linear_simple: a thread per output word, n_in 32-bit multiply-adds; any shape;
+ *   2  k_linear_mfma: the same sum as an exact product on the int8 MFMA pipe.  W is copied once per call into the context's
+ *      scratch in operand order, zero-padded to tiles of 32; a word v of x is cut in registers into four balanced byte limbs
+ *      -- u = (v + 0x80808080) ^ 0x80808080, whose bytes read as signed are b_k in [-128, 127] with v = sum_k b_k 2^(8k) mod 2^32
+ *      -- and out = sum_k (W x limb k) << 8k.  A limb's int32 accumulator holds at most n_in x 2^14, which is where
+ *      IEACHE_LINEAR_MAX_DIM = 65 536 comes from: 65 536 x 128 x 128 = 2^30 < 2^31.
+ * ieache_debug_linear_plan reports what a call would take under the option as it is: out[0] the kernel (1 or 2), out[1] the
+ * blocks of 32 words a device row is cut into, out[2] the output tiles of 32 a wave owns (1, 2 or 4), out[3] the K steps of 32
+ * inputs (csrc/linear_plan.h; the tiling figures describe the product whichever kernel runs).
+ * The device form runs on the context's stream, like every device form; the host form goes through the context's staging rows,
+ * so a warm call allocates nothing.  batch == 0 is a no-op.  There is no in-place form.
+ * stats: bootstraps == 0, blind_rotate_launches == 0, keyswitch_launches == 0, levels == 1, chunks == 1, total_ms > 0.
+ * IEACHE_EINVAL, with the message in ieache_last_error, in this order: (1) an unknown rows kind; (2) n_out or n_in outside
+ * 1 .. IEACHE_LINEAR_MAX_DIM; (3) a bias with the TLWE kind -- these three are judged before the context is looked at --;
+ * (4) a NULL context, or a NULL W, x or out when batch > 0; (5) device form only: d_out overlapping d_x, d_w or d_bias; then
+ * a host pointer to the device form.  A refused call writes nothing.
+ * ieache_lwe_linear_reference is the definition on the CPU, on packed rows, without a context (the words come from p).
+ * Weights wider than int8 are a second call with shifted weights and one more addition.  There is no group form and no cloudd
+ * verb: the call is a small fraction of the bootstrap that follows it, and cutting it over devices is out of scope. */
+#define IEACHE_ROWS_LWE 0
+#define IEACHE_ROWS_EXTRACTED 1
+#define IEACHE_ROWS_TLWE 2
+#define IEACHE_LINEAR_MAX_DIM 65536
+int ieache_lwe_linear_device(ieache_ctx* ctx, int rows, size_t batch, int32_t n_out, int32_t n_in, const int8_t* d_w /*[n_out][n_in]*/,
+                             const int32_t* d_bias /*[n_out] or NULL*/, const int32_t* d_x, int32_t* d_out, ieache_stats* stats);
+int ieache_lwe_linear(ieache_ctx* ctx, int rows, size_t batch, int32_t n_out, int32_t n_in, const int8_t* w /*[n_out][n_in]*/,
+                      const int32_t* bias /*[n_out] or NULL*/, const int32_t* x /*[batch][n_in][words]*/, int32_t* out /*[batch][n_out][words]*/,
+                      ieache_stats* stats);
+int ieache_lwe_linear_reference(const ieache_params* p, int rows, size_t batch, int32_t n_out, int32_t n_in, const int8_t* w, const int32_t* bias,
+                                const int32_t* x, int32_t* out);
+int ieache_debug_linear_plan(const ieache_ctx* ctx, int rows, size_t batch, int32_t n_out, int32_t n_in, int64_t out[4]);
+
 /* ------------------------------------------------------------------ *
  * 4. CPU tools around the path (no GPU): what Keygen/keygen.c:22-51,  *
  *    Client1/alice.c:116-191 and Output/verif.c:41-76 get from        *
