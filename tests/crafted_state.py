@@ -253,6 +253,60 @@ def boundary_amount_rows(n=16, N=1024):
                     dtype=np.int32)
 
 
+# ---- rows for the size axes of a ring: long keys, slices that reload their amounts (tests/test_ring2048_axes_*.py) ----
+
+def axis_amounts(N):
+    """0 (the step is skipped), 1, 2, N - 1, N, N + 1, 2N - 2, 2N - 1: even and odd amounts on both sides of the sign change."""
+    return (0, 1, 2, N - 1, N, N + 1, 2 * N - 2, 2 * N - 1)
+
+
+def axis_pattern_amounts(n, N):
+    """[8][n+1] amounts (the b word's last): row r meets axis_amounts[(r + 3 s) % 8] at step s, so over the eight rows every
+    step index -- every lane of a slice of any length -- meets every one of the eight amounts.  A row repeats every 8 steps,
+    so a step index that is wrong by a multiple of 8 reads the right amount: the isolating and the uniform rows see those."""
+    A = axis_amounts(N)
+    return np.array([[A[(r + 3 * s) % 8] for s in range(n)] + [A[(r + 5) % 8]] for r in range(8)], dtype=np.int64)
+
+
+def axis_isolating_amounts(n, N):
+    """[2][n+1] amounts.  Row 0: zero everywhere but 1 at step 63, N + 1 at step 64 (where the key has them) and, set last,
+    2N - 1 at step n - 1: lane 63 of a slice, the first step of the next one, the last step of the key.  Row 1: zero over steps
+    16 .. 31 -- one whole slice of the default length -- and odd amounts, all different, elsewhere; its b word is odd too."""
+    a = np.zeros((2, n + 1), dtype=np.int64)
+    for s, amount in ((63, 1), (64, N + 1)):
+        if s < n:
+            a[0, s] = amount
+    a[0, n - 1] = 2 * N - 1
+    s = np.arange(n + 1)
+    a[1] = (2 * (7 * s + 3) + 1) % (2 * N)
+    a[1, 16:min(32, n)] = 0
+    return a
+
+
+def amount_rows(amounts, N):
+    """Amounts [rows][n+1] -> the torus words that mod-switch to exactly them."""
+    shift = 32 - (2 * N).bit_length() + 1
+    return _wrap32((np.asarray(amounts, dtype=np.int64) % (2 * N)) << shift)
+
+
+# the edges of k_mv_compact's N / 256 = 8 coefficients per thread and of k_mv_extract_2048's j = tid + 256 r at N = 2048
+BOUNDARY_AT = (0, 7, 8, 255, 256, 1023, 1024, 2047)
+BOUNDARY_VALUES = (-(1 << 31), (1 << 31) - 1, 0x12345679, -0x6789ABCD, 1, -1, 0x40000001, -0x7FFFFFFF)
+
+
+def boundary_factor(N=2048):
+    """A factor polynomial of the multi-output bootstrap that is non-zero exactly at BOUNDARY_AT, full-range and all different."""
+    P = np.zeros(N, dtype=np.int32)
+    P[list(BOUNDARY_AT)] = np.array(BOUNDARY_VALUES, dtype=np.int64).astype(np.int32)
+    return P
+
+
+def first_difference(got, want):
+    """None where the arrays agree, else (index of the first differing word, number of differing words)."""
+    bad = np.argwhere(np.asarray(got) != np.asarray(want))
+    return None if bad.size == 0 else (tuple(int(v) for v in bad[0]), len(bad))
+
+
 # ---- key switch ----
 
 KS_WORDS = (0x80000000, 0x7FFFFFFF, 0x7F7F7F7F, 0x80808080, 0x7FFFFF80, 0xFFFFFF80, 0x00800080, 0xFFFFFFFF)
@@ -402,6 +456,15 @@ def oracle_accumulators(ck, x, steps_list=(0, 1, 2, -1)):
             if i < n:
                 acc = ck.blind_rotate_step(acc, i, bara[i])
     return {s: np.stack(v) for s, v in out.items()}
+
+
+def oracle_accumulators_threaded(ck, x, steps_list=(0, 1, 2, -1), threads=16):
+    """oracle_accumulators with a host thread per row, for long keys (the oracle's stages take the key read-only and ctypes
+    releases the interpreter lock, as multi_reference.multi_reference_rows relies on)."""
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(threads) as ex:
+        per_row = list(ex.map(lambda row: oracle_accumulators(ck, row[None], steps_list), np.asarray(x)))
+    return {s: np.concatenate([r[s] for r in per_row]) for s in steps_list}
 
 
 # ---- the sets the two files run ----

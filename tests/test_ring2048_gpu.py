@@ -2,7 +2,7 @@
 tests/test_ring2048_cpu.py), every case on both kernels of that ring: k_blind_rotate_h2 (csrc/blind_rotate_h2.hip: one CMux step
 as two products on the ring of degree 1024) and, under "force_generic", k_blind_rotate_generic with the any-parameter key switch.
 
-Every key has n <= 16.  The odd rotation amounts, where the even and odd halves of the accumulator change places, are what the
+Every key has n <= 16 and no launch more than 16 items: the size axes are tests/test_ring2048_axes_gpu.py's.  The odd rotation amounts, where the even and odd halves of the accumulator change places, are what the
 crafted rows aim at; tests/native/ring_split_test.cpp holds the identity itself."""
 import contextlib
 
